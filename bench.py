@@ -14,6 +14,13 @@ records are all-gathered over RCCL per step.
                                        before this process makes any GPU call, and relays rank 0's line)
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
          --master-port P bench.py --gpus N --steps K --warmup W
+  python bench.py ... --dump-outputs DIR  (also writes what the last timed step returned as DIR/*.npy)
+  python bench.py ... --full              (also the figures measured after the timed steps, below)
+
+A plain run sets up, warms up, times the K steps and prints the headline (`value`, `ms_per_step`,
+the workload, the last step's result).  Everything else is measured only with --full: the
+spread over four more windows, the rooflines, the early-exit / pipelined / batch / chain
+figures and the CPU baseline (--no-batch and --no-cpu-baseline leave parts of it out).
 
 Rank 0 prints ONE JSON line.  `roofline` is the dominant kernel (k_register: kNN + plane +
 Jacobian + block reduction) priced against HBM over the whole loop, `roofline_cold` the same for
@@ -140,6 +147,10 @@ def parse_args(argv=None):
     ap.add_argument("--cpu-scans", type=int, default=10)
     ap.add_argument("--no-batch", action="store_true", help="skip the side figures: 2, 4 and 8 scans in flight against one map (s2m_optimize_batch) and the pipelined stream of scans (s2m_slot_*)")
     ap.add_argument("--print-launch", action="store_true", help="print the command that would start the ranks and exit (no GPU call)")
+    ap.add_argument("--full", action="store_true", help="after the timed steps, also measure the side figures: timing spread, rooflines, "
+                    "early-exit / pipelined / batch / chain figures, CPU baseline (a plain run reports the headline only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the last timed step returned (pose, affine, result counters) "
+                    "as DIR/<name>.npy")
     return ap.parse_args(argv)
 
 
@@ -291,16 +302,75 @@ def run(args):
         dt = float(tt.item())
     ms_per_step = 1e3 * dt / args.steps
     value = world * args.steps * max_iter / dt            # whole-job LM iterations / s
+    device_ms = eng.timing()["optimize_ms"]
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, eng, r)
+    out = {
+        "metric": "LM iterations/sec (64-line scan vs 200k-pt map)",
+        "value": round(value, 1),
+        "unit": "LM iterations/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": round(ms_per_step, 4),
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "f32",
+        "data": "synthetic",
+        "config": {
+            "workload": f"{args.workload}: {n_q}-pt scan vs {n_m}-pt local surf map, {max_iter} LM iterations per "
+                        f"scan (early exit off), one scan per GPU at a time, {N_SCANS} distinct seeded scans in rotation, map replicated",
+            "n_q": n_q, "n_m": n_m, "lm_iters_per_step": max_iter, "distinct_scans": N_SCANS,
+            "parallelism": f"scan-per-gpu x{world}" + (" + RCCL all_gather of 8-float records, pipelined one step behind (the record of step k is exchanged while step k+1 runs)" if world > 1 else ""),
+        },
+        "device_ms_per_step": round(device_ms, 4),
+        "map_index_build_ms": round(tm["set_map_ms"], 4),
+        # SURVEY section 8(d)(i): "map index build reported separately and also amortised" - the reference rebuilds its kd-tree for
+        # every scan (:1302); with the device index build charged to every step:
+        "value_with_map_index_build": round(world * max_iter * 1e3 / (ms_per_step + tm["set_map_ms"]), 1),
+        "scan_prep_ms": round(tm["set_scan_ms"], 4),
+        "last_result": {"iters_run": r.iters_run, "converged": r.converged, "n_sel": r.n_sel_last, "scan_index": k_last,
+                        "pose_err_m": float(np.abs(np.array(r.pose)[3:] - cfgs[k_last]["pose_gt"][3:]).max())},
+    }
+    if args.full:
+        out.update(full_figures(args, eng, step, fence, cfgs, d_map, d_scans, ms_per_step, value))
+    if rank == 0:
+        print(json.dumps(out), flush=True)
+    eng.close()
+    if world > 1:
+        dist.destroy_process_group()
+
+
+def dump_outputs(path, eng, r):
+    """--dump-outputs DIR: what a caller of the timed path (s2m_optimize_collect) receives from its last step - the optimised
+    pose (transformTobeMapped), the incremental affine and the counters of the result record."""
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "pose.npy"), np.asarray(eng.transformTobeMapped, np.float32))
+    np.save(os.path.join(path, "affine.npy"), np.array(r.affine, np.float32).reshape(3, 4))
+    np.save(os.path.join(path, "result_counters.npy"),
+            np.array([r.iters_run, r.converged, r.is_degenerate, r.n_sel_last, r.skipped], np.float64))
+
+
+def full_figures(args, eng, step, fence, cfgs, d_map, d_scans, ms_per_step, value):
+    """--full: the figures beside the headline, each measured in runs of its own after the timed steps - the spread of
+    `ms_per_step`, the rooflines, the early-exit / pipelined / batch / chain figures and the CPU baseline."""
+    import torch
+    from liorf_amd import s2m, synth
+    rank = int(os.environ.get("RANK", "0"))
+    local_rank = int(os.environ.get("LOCAL_RANK", "0"))
+    world = int(os.environ.get("WORLD_SIZE", "1"))
+    cfg, d_scan = cfgs[0], d_scans[0]
+    n_q, n_m = cfg["scan"].shape[0], cfg["map"].shape[0]
     # four more windows of the same K steps, for the spread of the figure above (not part of `value`)
     windows = [ms_per_step]
     for _ in range(4):
         fence()
         t1 = time.perf_counter()
         for _ in range(args.steps):
-            r, k_last = step()
+            step()
         fence()
         windows.append(1e3 * (time.perf_counter() - t1) / args.steps)
-    device_ms = eng.timing()["optimize_ms"]
 
     # ---- dominant kernel, timed live with HIP events on the library's stream (scan 0) ---------
     eng.setScanDevice(d_scan.data_ptr(), n_q, 32)
@@ -314,7 +384,7 @@ def run(args):
     cold_ms = float(per_iter_ms[0])
     achieved_cold = b_alg / (cold_ms * 1e-3)
     # HBM-side bytes per launch from the committed PMC passes of this workload (profiles/): FETCH_SIZE is doubled (the gfx950
-    # correction for 16-B-per-lane reads, MI355X_MICROARCH.md), WRITE_SIZE as is.  The counters need rocprofv3 and cannot be
+    # correction for 16-B-per-lane reads), WRITE_SIZE as is.  The counters need rocprofv3 and cannot be
     # taken inside this run; they are reported only if they were taken on the kernel sources that are running (the file is
     # stamped with a hash of liorf_amd/csrc), otherwise traffic is null and traffic_stale says why.
     traffic = traffic_raw = None
@@ -422,24 +492,6 @@ def run(args):
         e2.close()
 
     out = {
-        "metric": "LM iterations/sec (64-line scan vs 200k-pt map)",
-        "value": round(value, 1),
-        "unit": "LM iterations/s",
-        "n_gpus": world,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": round(ms_per_step, 4),
-        "higher_is_better": True,
-        "scaling": "weak",
-        "vs_baseline": None,
-        "dtype": "f32",
-        "data": "synthetic",
-        "config": {
-            "workload": f"{args.workload}: {n_q}-pt scan vs {n_m}-pt local surf map, {max_iter} LM iterations per "
-                        f"scan (early exit off), one scan per GPU at a time, {N_SCANS} distinct seeded scans in rotation, map replicated",
-            "n_q": n_q, "n_m": n_m, "lm_iters_per_step": max_iter, "distinct_scans": N_SCANS,
-            "parallelism": f"scan-per-gpu x{world}" + (" + RCCL all_gather of 8-float records, pipelined one step behind (the record of step k is exchanged while step k+1 runs)" if world > 1 else ""),
-        },
         "roofline": {
             "bound": "hbm", "kernel": "k_register",
             "achieved": round(achieved / 1e9, 2), "peak": HBM_PEAK / 1e9, "unit": "GB/s",
@@ -469,15 +521,7 @@ def run(args):
         # kNN rate = the pass that searches: launch 0 (round 2 divided by the loop mean, most of whose launches search nothing)
         "knn_mpts_per_s": round(n_q / (cold_ms * 1e-3) / 1e6, 1),
         "points_per_s_loop_mean": round(n_q / (kernel_ms * 1e-3), 1),
-        "device_ms_per_step": round(device_ms, 4),
-        "map_index_build_ms": round(tm["set_map_ms"], 4),
-        # SURVEY section 8(d)(i): "map index build reported separately and also amortised" - the reference rebuilds its kd-tree for
-        # every scan (:1302); with the device index build charged to every step:
-        "value_with_map_index_build": round(world * max_iter * 1e3 / (ms_per_step + tm["set_map_ms"]), 1),
-        "scan_prep_ms": round(tm["set_scan_ms"], 4),
         **({"chain": chain_figures(local_rank)} if (rank == 0 and world == 1 and not args.no_batch) else {}),
-        "last_result": {"iters_run": r.iters_run, "converged": r.converged, "n_sel": r.n_sel_last, "scan_index": k_last,
-                        "pose_err_m": float(np.abs(np.array(r.pose)[3:] - cfgs[k_last]["pose_gt"][3:]).max())},
     }
 
     if rank == 0 and world == 1 and not args.no_cpu_baseline:
@@ -506,11 +550,7 @@ def run(args):
         if early:
             out["speedup_vs_cpu_4t_per_scan_early_exit"] = round(b4e["ms_per_scan"] / early["ms_per_scan_early_exit"], 1)
 
-    if rank == 0:
-        print(json.dumps(out), flush=True)
-    eng.close()
-    if world > 1:
-        dist.destroy_process_group()
+    return out
 
 
 if __name__ == "__main__":

@@ -104,7 +104,6 @@ def test_detect_loop_sequence():
 
 # ----------------------------------------------------------------------------- the reference's own ring-key search
 import os
-import pytest
 
 GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "sc_ringkey_ref_golden.npz")
 
@@ -138,19 +137,34 @@ def test_ringkey_candidates_equal_the_references_adaptor():
     orc.close()
 
 
-def test_ringkey_search_with_fewer_keys_than_candidates_and_ties():
-    """1 and 2 keys in the tree (the result vectors keep their zero initialisation, :289-290), and duplicated keys
-    (a robot standing still): where distances tie exactly, nanoflann returns them in tree-traversal order - the
-    oracle breaks ties towards the lower index, so only the distances and the SET of tied indices are comparable."""
-    if O.nanoflann_ringkey_knn(np.zeros((2, 20), np.float32), np.zeros(20, np.float32), 3) is None:
-        pytest.skip("oracle/_ref not built (reference tree absent)")
+def ringkey_tie_cases():
+    """(keys, query) of the three searches below: 1 key, 2 keys, and 40 keys of which 3, 7 and 21 are equal."""
     rng = np.random.default_rng(4)
     keys = rng.uniform(0, 3, (40, 20)).astype(np.float32)
     q = rng.uniform(0, 3, 20).astype(np.float32)
-    for ns in (1, 2):
-        idx, d2, found = O.nanoflann_ringkey_knn(keys[:ns], q, 3)
-        assert found == ns
+    cases = [(keys[:1].copy(), q), (keys[:2].copy(), q)]
     keys[7] = keys[3]
     keys[21] = keys[3]
-    idx, d2, found = O.nanoflann_ringkey_knn(keys, keys[3] + np.float32(0.01), 3)
-    assert sorted(idx.tolist()) == [3, 7, 21] and d2[0] == d2[1] == d2[2]
+    return cases + [(keys, keys[3] + np.float32(0.01))]
+
+
+def test_ringkey_search_with_fewer_keys_than_candidates_and_ties():
+    """1 and 2 keys in the tree (the result vectors keep their zero initialisation, :289-290), and duplicated keys
+    (a robot standing still): where distances tie exactly, nanoflann returns them in tree-traversal order - the
+    oracle breaks ties towards the lower index, so only the distances and the SET of tied indices are comparable.
+    What the reference's search returned is in tests/golden/nanoflann_ref_golden.npz (tests/golden/make_golden_nanoflann.py);
+    the live library, when present, must return the same."""
+    g = np.load(os.path.join(os.path.dirname(GOLD), "nanoflann_ref_golden.npz"))
+    cases = ringkey_tie_cases()
+    for c, (keys, q) in enumerate(cases):
+        idx, d2, found = g["ringkey_idx"][c], g["ringkey_d2"][c], int(g["ringkey_found"][c])
+        # the recorded distances are those of these keys (fp32 squared distances over the 20 ring entries)
+        want = ((keys[idx[:found]] - q) ** 2).sum(1, dtype=np.float32)
+        assert np.allclose(d2[:found], want, rtol=1e-6, atol=0), c
+        live = O.nanoflann_ringkey_knn(keys, q, 3)
+        if live is not None:
+            assert np.array_equal(live[0], idx) and np.array_equal(live[1], d2) and live[2] == found, c
+        if c < 2:
+            assert found == len(keys)
+        else:
+            assert sorted(idx.tolist()) == [3, 7, 21] and d2[0] == d2[1] == d2[2]

@@ -11,7 +11,7 @@ mkdir -p $OUT
 export TMPDIR=/tmp
 for W in "$@"; do
   echo "== $W: kernel trace of the bench command"
-  rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/kt_$W -- python3 bench.py --workload $W --steps 10 --warmup 2 --no-cpu-baseline --no-batch > $OUT/bench_under_trace_$W.log 2>&1 || echo "trace failed for $W"
+  rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/kt_$W -- python3 bench.py --full --workload $W --steps 10 --warmup 2 --no-cpu-baseline --no-batch > $OUT/bench_under_trace_$W.log 2>&1 || echo "trace failed for $W"
   f=$(find $OUT/kt_$W -name "*kernel_stats.csv" | head -1); [ -n "$f" ] && cp $f $OUT/r04_bench_kernel_stats_$W.csv
   tail -1 $OUT/bench_under_trace_$W.log | cut -c1-300
   python3 tools/launch_index_stats.py $OUT/kt_$W $OUT/r04_launch_index_stats_$W.json > /dev/null && echo "launch index stats written for $W"

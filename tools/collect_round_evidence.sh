@@ -5,8 +5,8 @@
 R=$(pwd)
 O=$R/gpurun_out/prof_r04
 mkdir -p $O
-python bench.py > $O/r04_bench_line.json 2> $O/r04_bench_line.err; tail -c 300 $O/r04_bench_line.json; echo
-for W in ouster128 dense1m small; do python bench.py --no-cpu-baseline --workload $W 2>> $O/r04_bench_line.err; done > $O/r04_bench_other_workloads.jsonl
+python bench.py --full > $O/r04_bench_line.json 2> $O/r04_bench_line.err; tail -c 300 $O/r04_bench_line.json; echo
+for W in ouster128 dense1m small; do python bench.py --full --no-cpu-baseline --workload $W 2>> $O/r04_bench_line.err; done > $O/r04_bench_other_workloads.jsonl
 bash tools/collect_profiles.sh kitti64 ouster128 dense1m > $O/collect.log 2>&1; tail -3 $O/collect.log
 python tools/bench_batch.py kitti64 20 > $O/r04_batch_one_gpu.json 2>> $O/r04_bench_line.err
 python tools/bench_stream.py kitti64 40 > $O/r04_stream_of_scans.json 2>> $O/r04_bench_line.err

@@ -1,6 +1,8 @@
-# kitti64 / ouster128 / dense1m bench lines (no CPU baseline) + the one-GPU batch table, into gpurun_out/<tag>_*.json
+# kitti64 / ouster128 / dense1m bench lines (no CPU baseline) + the one-GPU batch table, into OUT/<tag>_*.json
+#   bash tools/experiments/r4_bench3.sh TAG OUT
 TAG=${1:-r4}
-mkdir -p gpurun_out
-python bench.py --no-cpu-baseline > gpurun_out/${TAG}_kitti64.json 2> gpurun_out/${TAG}.err
-for W in ouster128 dense1m; do python bench.py --no-cpu-baseline --no-batch --workload $W > gpurun_out/${TAG}_$W.json 2>> gpurun_out/${TAG}.err; done
+OUT=${2:?usage: r4_bench3.sh TAG OUT}
+mkdir -p $OUT
+python bench.py --full --no-cpu-baseline > $OUT/${TAG}_kitti64.json 2> $OUT/${TAG}.err
+for W in ouster128 dense1m; do python bench.py --full --no-cpu-baseline --no-batch --workload $W > $OUT/${TAG}_$W.json 2>> $OUT/${TAG}.err; done
 echo done

@@ -2,7 +2,7 @@
 their LM loop (a loop begins behind k_chunk_table_density), loops of exactly max_iter registration launches are averaged by
 index.  The figure to trust for a single launch: no event packets around it, the loop runs as the captured graph issues it.
 
-   rocprofv3 --kernel-trace --output-format csv -d DIR -- python3 bench.py --no-cpu-baseline --steps 10
+   rocprofv3 --kernel-trace --output-format csv -d DIR -- python3 bench.py --full --no-cpu-baseline --steps 10
    python tools/launch_index_stats.py DIR profiles/r03_launch_index_stats_kitti64.json [max_iter=30]"""
 import csv, glob, json, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
