@@ -713,6 +713,8 @@ int download_records(s2m_context* h, const DevBuf& src, size_t n, void* out, siz
     S2M_HIP(h, hipMemcpy2DAsync(out, out_stride, src.p, kDsStride, out_stride < kDsStride ? out_stride : kDsStride, m,
                                 hipMemcpyDeviceToHost, h->stream));
     S2M_HIP(h, hipStreamSynchronize(h->stream));
+    if (out_stride > kDsStride)                // records wider than the device's: the fields past it are 0, as on the device path
+        for (size_t i = 0; i < m; i++) memset(static_cast<unsigned char*>(out) + i * out_stride + kDsStride, 0, out_stride - kDsStride);
     return S2M_OK;
 }
 

@@ -7,8 +7,10 @@
 // by one 64-bit atomicMin on (d2 bits << 32 | target index), i.e. ties go to the lower index like the
 // oracle; loop-closure submaps are 1e3..1e5 points, so the whole search is a few 1e8..1e9 distance
 // evaluations spread over ~1000 workgroups; (2) one pass over the correspondences within the distance
-// limit accumulates count, sum d2, the two centroids and the raw cross moments in fp64 (17 numbers); the
-// host turns them into Eigen::umeyama's mean / covariance, does the 3x3 SVD, the pose composition and
+// limit accumulates count, sum d2, the two centroids and the raw cross moments in fp64 (17 numbers): every
+// workgroup writes its partial row, one workgroup folds the rows in workgroup order (no atomics, so the sums
+// and everything after them are the same bits from run to run - fp64 adds in arrival order were not, at
+// 20 km from the origin one fp32 ulp of the covariance); the host turns them into Eigen::umeyama's mean / covariance, does the 3x3 SVD, the pose composition and
 // the convergence state machine exactly as PCL does; (3) the source cloud is transformed in place by the
 // incremental transform, as PCL transforms input_transformed.  fp32 distances use the operation order
 // of the oracle ((dx*dx + dy*dy) + dz*dz, -ffp-contract=off), so correspondences are identical to it.
@@ -29,6 +31,7 @@ namespace {
 constexpr int kNnThreads = 256;
 constexpr int kNnTile = 1024;                       // target points per LDS tile
 constexpr unsigned long long kNoMatch = ~0ull;
+constexpr int kSumBlocks = 256;                     // most k_icp_sums workgroups: rows of the partial-sum buffer
 
 struct Buf {
     void*  p = nullptr;
@@ -53,11 +56,10 @@ __global__ __launch_bounds__(256) void k_icp_load(const unsigned char* __restric
     out[i] = make_float4(p[0], p[1], p[2], 0.0f);
 }
 
-__global__ __launch_bounds__(256) void k_icp_reset(unsigned long long* __restrict__ best, int n, double* __restrict__ sums)
+__global__ __launch_bounds__(256) void k_icp_reset(unsigned long long* __restrict__ best, int n)
 {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) best[i] = kNoMatch;
-    if (i < 17) sums[i] = 0.0;
 }
 
 // grid (source blocks, target slices): 256 source points against target points [slice*len, (slice+1)*len)
@@ -102,10 +104,10 @@ __global__ __launch_bounds__(kNnThreads) void k_icp_nn(const float4* __restrict_
         atomicMin(&best[i], ((unsigned long long)__float_as_uint(bd) << 32) | (unsigned)bi);
 }
 
-// count, sum d2, centroids and raw cross moments of the correspondences with d2 <= max_d2 (fp64)
+// count, sum d2, centroids and raw cross moments of the correspondences with d2 <= max_d2 (fp64): this workgroup's row of `part`
 __global__ __launch_bounds__(256) void k_icp_sums(const float4* __restrict__ cur, int n_src, const float4* __restrict__ tgt,
                                                   const unsigned long long* __restrict__ best, float max_d2_f, double max_d2,
-                                                  double* __restrict__ sums)
+                                                  double* __restrict__ part)
 {
     __shared__ double sh[4][17];
     double a[17];
@@ -135,7 +137,17 @@ __global__ __launch_bounds__(256) void k_icp_sums(const float4* __restrict__ cur
         for (int k = 0; k < 17; k++) sh[wave][k] = a[k];
     }
     __syncthreads();
-    if (threadIdx.x < 17) atomicAdd(&sums[threadIdx.x], sh[0][threadIdx.x] + sh[1][threadIdx.x] + sh[2][threadIdx.x] + sh[3][threadIdx.x]);
+    if (threadIdx.x < 17) part[17 * blockIdx.x + threadIdx.x] = sh[0][threadIdx.x] + sh[1][threadIdx.x] + sh[2][threadIdx.x] + sh[3][threadIdx.x];
+}
+
+// the rows of k_icp_sums folded in workgroup order
+__global__ __launch_bounds__(64) void k_icp_fold(const double* __restrict__ part, int rows, double* __restrict__ sums)
+{
+    const int k = threadIdx.x;
+    if (k >= 17) return;
+    double a = 0.0;
+    for (int b = 0; b < rows; b++) a += part[17 * b + k];
+    sums[k] = a;
 }
 
 struct Mat34 { float m[12]; };
@@ -152,7 +164,7 @@ __global__ __launch_bounds__(256) void k_icp_transform(float4* __restrict__ cur,
 }  // namespace
 
 struct IcpWorkspace {
-    Buf cur, tgt, best, sums;
+    Buf cur, tgt, best, part, sums;
     double* h_sums = nullptr;            // pinned, 17 doubles
 };
 
@@ -170,7 +182,7 @@ IcpWorkspace* icp_create()
 void icp_destroy(IcpWorkspace* w)
 {
     if (!w) return;
-    Buf* bufs[] = { &w->cur, &w->tgt, &w->best, &w->sums };
+    Buf* bufs[] = { &w->cur, &w->tgt, &w->best, &w->part, &w->sums };
     for (Buf* b : bufs) if (b->p) (void)hipFree(b->p);
     if (w->h_sums) (void)hipHostFree(w->h_sums);
     delete w;
@@ -187,8 +199,7 @@ hipError_t nearest(IcpWorkspace* w, hipStream_t stream, int n_src, int n_tgt)
     slices = std::max(1, std::min(slices, (n_tgt + kNnTile - 1) / kNnTile));
     const int slice_len = (((n_tgt + slices - 1) / slices) + kNnTile - 1) / kNnTile * kNnTile;
     slices = (n_tgt + slice_len - 1) / slice_len;
-    hipLaunchKernelGGL(k_icp_reset, dim3((std::max(n_src, 17) + 255) / 256), dim3(256), 0, stream, w->best.as<unsigned long long>(), n_src,
-                       w->sums.as<double>());
+    hipLaunchKernelGGL(k_icp_reset, dim3((n_src + 255) / 256), dim3(256), 0, stream, w->best.as<unsigned long long>(), n_src);
     hipLaunchKernelGGL(k_icp_nn, dim3(sb, slices), dim3(kNnThreads), 0, stream, (const float4*)w->cur.as<float4>(), n_src,
                        (const float4*)w->tgt.as<float4>(), n_tgt, slice_len, w->best.as<unsigned long long>());
     return hipGetLastError();
@@ -196,9 +207,11 @@ hipError_t nearest(IcpWorkspace* w, hipStream_t stream, int n_src, int n_tgt)
 
 hipError_t sums(IcpWorkspace* w, hipStream_t stream, int n_src, double max_d2)
 {
-    hipLaunchKernelGGL(k_icp_sums, dim3(std::min((n_src + 255) / 256, 256)), dim3(256), 0, stream, (const float4*)w->cur.as<float4>(), n_src,
+    const int rows = std::min((n_src + 255) / 256, kSumBlocks);
+    hipLaunchKernelGGL(k_icp_sums, dim3(rows), dim3(256), 0, stream, (const float4*)w->cur.as<float4>(), n_src,
                        (const float4*)w->tgt.as<float4>(), (const unsigned long long*)w->best.as<unsigned long long>(), 0.0f, max_d2,
-                       w->sums.as<double>());
+                       w->part.as<double>());
+    hipLaunchKernelGGL(k_icp_fold, dim3(1), dim3(64), 0, stream, (const double*)w->part.as<double>(), rows, w->sums.as<double>());
     ICP_TRY(hipGetLastError());
     ICP_TRY(hipMemcpyAsync(w->h_sums, w->sums.p, sizeof(double) * 17, hipMemcpyDeviceToHost, stream));
     return hipStreamSynchronize(stream);
@@ -215,6 +228,7 @@ hipError_t icp_align(IcpWorkspace* w, hipStream_t stream, const unsigned char* d
     if (n_src == 0 || n_tgt == 0) return hipSuccess;
     ICP_TRY(w->cur.ensure(sizeof(float4) * n_src_)); ICP_TRY(w->tgt.ensure(sizeof(float4) * n_tgt_));
     ICP_TRY(w->best.ensure(sizeof(unsigned long long) * n_src_));
+    ICP_TRY(w->part.ensure(sizeof(double) * 17 * (size_t)std::min((n_src + 255) / 256, kSumBlocks)));
     hipLaunchKernelGGL(k_icp_load, dim3((n_src + 255) / 256), dim3(256), 0, stream, d_src, stride, n_src, w->cur.as<float4>());
     hipLaunchKernelGGL(k_icp_load, dim3((n_tgt + 255) / 256), dim3(256), 0, stream, d_tgt, stride, n_tgt, w->tgt.as<float4>());
     ICP_TRY(hipGetLastError());

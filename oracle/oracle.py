@@ -96,6 +96,7 @@ def lib() -> C.CDLL:
         L.orc_jacobian_row.argtypes = [fp, fp, fp, fp, fp]
         L.orc_xy2theta.argtypes = [C.c_float, C.c_float]
         L.orc_xy2theta.restype = C.c_float
+        L.orc_atanf_bulk.argtypes = [fp, C.c_size_t, fp]
         L.orc_makeScancontext.argtypes = [vp, C.c_size_t, C.c_size_t, C.POINTER(C.c_double)]
         L.orc_makeRingkeyFromScancontext.argtypes = [C.POINTER(C.c_double), C.POINTER(C.c_double)]
         dp = C.POINTER(C.c_double)
@@ -370,6 +371,14 @@ class SCManager:
         return lid, yaw.value, dict(min_dist=md.value, nn_idx=ni.value, nn_align=na.value, cand_idx=list(ci), cand_d2=list(cd))
 
 
+def atanf(x):
+    """The host libm's atanf of every element of the float32 array x (what the reference's xy2theta calls)."""
+    a = np.ascontiguousarray(x, np.float32)
+    out = np.empty_like(a)
+    lib().orc_atanf_bulk(_fp(a), a.size, _fp(out))
+    return out
+
+
 def icp_align(src, tgt, max_corr_dist=30.0, max_iter=100, trans_eps=1e-6, fit_eps=1e-6, num_threads=8):
     """pcl::IterativeClosestPoint as configured at reference src/mapOptmization.cpp:571-586:
     (T 4x4 float32, converged, fitness score, iterations)."""
@@ -390,12 +399,13 @@ def icp_umeyama(mean_src, mean_tgt, sigma):
     return T
 
 
-def voxel_grid(pts, leaf: float):
-    """pcl::VoxelGrid<PointXYZI> restatement: ((m, 8) float32 records, leaf_too_small flag)."""
+def voxel_grid(pts, leaf: float, out_stride: int = 32):
+    """pcl::VoxelGrid<PointXYZI> restatement: ((m, out_stride // 4) float32 records, leaf_too_small flag)."""
     a, n, st = _records(pts)
-    out = np.zeros((max(n, 1), 8), np.float32)
+    assert out_stride % 4 == 0 and out_stride >= 12
+    out = np.zeros((max(n, 1), out_stride // 4), np.float32)
     m = C.c_size_t(0)
-    rc = lib().orc_voxelGrid(a.ctypes.data, n, st, leaf, out.ctypes.data, 32, n, C.byref(m))
+    rc = lib().orc_voxelGrid(a.ctypes.data, n, st, leaf, out.ctypes.data, out_stride, n, C.byref(m))
     assert rc >= 0
     return out[:m.value], bool(rc == 1)
 

@@ -859,6 +859,11 @@ float orc_xy2theta(float x, float y)
     return NAN;   /* NaN inputs fall through every branch in the reference (UB there) */
 }
 
+void orc_atanf_bulk(const float* x, size_t n, float* out)
+{
+    for (size_t i = 0; i < n; i++) out[i] = atanf(x[i]);
+}
+
 static int clamp_ceil_bin(double v, int nbins)
 {
     /* std::max(std::min(N, int(ceil(v))), 1); int(NaN) is INT_MIN on x86-64 */

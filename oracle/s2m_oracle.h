@@ -111,6 +111,7 @@ void     orc_jacobian_row(const float pose[6], const float p_ori[3], const float
 
 /* ScanContext (include/Scancontext.cpp:23-36, 151-211) */
 float    orc_xy2theta(float x, float y);
+void     orc_atanf_bulk(const float* x, size_t n, float* out);           /* the host libm's atanf, test infrastructure */
 void     orc_makeScancontext(const void* pts, size_t n, size_t stride_bytes, double desc[20 * 60]);
 void     orc_makeRingkeyFromScancontext(const double desc[20 * 60], double key[20]);
 

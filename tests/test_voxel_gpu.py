@@ -38,7 +38,7 @@ def test_voxel_grid_bit_exact(gpu, n, leaf):
 
 def test_voxel_grid_long_runs_bit_exact(gpu):
     """Voxels that hold hundreds / thousands of points (overlapping key frames, the sensor's near field) are summed by a whole
-    wave (more than 96 points) or a whole workgroup (more than 1 024, 1 024 per round) - records gathered by all lanes, four lanes
+    wave (more than kLongRun = 40 points) or a whole workgroup (more than 1 024, 1 024 per round) - records gathered by all lanes, four lanes
     adding one component each in the run's order - and must give the bits of the oracle's sequential fp32 sums: runs of
     97 .. 20 000 points, on both sides of every boundary, next to ordinary ones, 12- and 32-byte records."""
     rng = np.random.default_rng(3)
