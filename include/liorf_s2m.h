@@ -124,7 +124,9 @@ int  s2m_get_params(s2m_handle h, s2m_params* out);
 /* ---- inputs ------------------------------------------------------------- */
 /* Replaces kdtreeSurfFromMap->setInputCloud(laserCloudSurfFromMapDS) (:1302):
  * uploads the local surf map and builds the device neighbour-search index.
- * n == 0 is allowed and models "cloudKeyPoses3D->points.empty()" (:1297). */
+ * n == 0 is allowed and models "cloudKeyPoses3D->points.empty()" (:1297).
+ * A map whose extent no search grid can cover (e.g. a finite point at 1e30) returns S2M_ERR_CAPACITY and leaves the
+ * handle with no map: s2m_optimize* then report skipped == 1 until a map is set that succeeds. */
 int  s2m_set_map(s2m_handle h, const void* pts, size_t n, size_t stride_bytes);
 /* Same, for a map that already lives in device memory (hipMalloc'd). */
 int  s2m_set_map_device(s2m_handle h, const void* d_pts, size_t n, size_t stride_bytes);
