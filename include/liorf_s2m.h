@@ -243,6 +243,53 @@ int  s2m_extract_cloud(s2m_handle h, int n_frames, const void* const* frames, co
 int  s2m_transform_cloud(s2m_handle h, const void* pts, size_t n, size_t stride_bytes, const float pose_xyzrpy[6],
                          void* out, size_t out_stride_bytes);
 
+/* ---- The resident key-frame store and extractSurroundingKeyFrames() -------------------------------------
+ * The key-frame containers of mapOptimization (cloudKeyPoses3D / cloudKeyPoses6D / surfCloudKeyFrames, :93-100)
+ * kept on the device, and extractSurroundingKeyFrames() (:1046-1059 -> extractNearby :975-1010 -> extractCloud
+ * :1012-1044) run against them. Key frames are numbered 0.. in the order they are added (at most 2^24: the
+ * reference carries key ids in a float intensity). With P[i] the position of key i, N the store size and R, D, L, W
+ * the four parameters below, the selection is:
+ *   (b) every key with d2(P[i], P[N-1]) < (float)(R*R), in ascending (d2, i); d2 = fp32 ((dx*dx + dy*dy) + dz*dz).
+ *       [ext] FLANN 1.9's radius search: L2_Simple accumulation, strict '<', ties in index order.
+ *   (c) those positions as records {P[i], 1, intensity i} through the VoxelGrid above with leaf D.
+ *   (d) for every centroid, in voxel order, its nearest key among all N (same d2; equal distances: lower index).
+ *   (e) then keys N-1, N-2, ... while time_cur - time[i] < W (double), stopping at the first that fails (duplicates
+ *       of (d) are kept, and concatenated twice, as in the reference).
+ *   (f) an entry is dropped when sqrtf(|x - P[N-1]|^2) > R, x being the CENTROID for entries of (d) (the reference
+ *       tests the down-sampled key pose, :1018) and the key's own position for entries of (e).
+ *   (g) the surviving keys' clouds, each transformed by its current pose, concatenated in that order, filtered with
+ *       leaf L and installed as the local map: bit for bit s2m_extract_cloud on those frames and poses.
+ * Each key's transform is computed once, when its pose is set (the reference's laserCloudMapContainer cache).
+ * (b)-(d) and (f) run on the device; the count of recent keys in (e) is taken on the host, from the key times it
+ * keeps, and handed to the kernels (a double comparison over the newest keys, no data leaves the device for it). */
+typedef struct s2m_kf_params {
+    float  search_radius;    /* surroundingKeyframeSearchRadius 50.0   include/utility.h:240 */
+    float  density;          /* surroundingKeyframeDensity 1.0         include/utility.h:238 (configs: 2.0) */
+    float  map_leaf;         /* surroundingKeyframeMapLeafSize 0.2     include/utility.h:228 (configs: 0.5) */
+    double recent_window_s;  /* 10.0, the literal at :1003 */
+} s2m_kf_params;
+#define S2M_KF_FROM_HOST            0   /* pts: host records of stride_bytes */
+#define S2M_KF_FROM_DEVICE          1   /* pts: device records of stride_bytes */
+#define S2M_KF_FROM_LAST_DOWNSAMPLE 2   /* laserCloudSurfLastDS as the last s2m_downsample_scan left it (:1577); pts, n and
+                                           stride_bytes are ignored; S2M_ERR_NO_SCAN before any s2m_downsample_scan */
+int  s2m_kf_default_params(s2m_kf_params* p);
+int  s2m_kf_reset(s2m_handle h);
+int  s2m_kf_size(s2m_handle h);                                   /* key frames stored, or a negative status */
+/* saveKeyFramesAndFactor() (:1549-1580): append key frame N with pose {x, y, z, roll, pitch, yaw} and time. The
+ * cloud is copied into the store as 32-byte records. A failed add leaves the store as it was. */
+int  s2m_kf_add(s2m_handle h, const float pose_xyzrpy[6], double time,
+                const void* pts, size_t n, size_t stride_bytes, int source);
+/* correctPoses() (:1611-1640): replace the poses of key frames first .. first+count-1 (a range inside [0, N)). */
+int  s2m_kf_set_poses(s2m_handle h, int first, int count, const float* poses_xyzrpy);
+/* extractSurroundingKeyFrames() at timeLaserInfoCur = time_cur, fused with s2m_set_map like s2m_extract_cloud: an
+ * empty store returns S2M_OK with *n_out = *n_keys = 0 and leaves the installed map alone (:1048-1049). If cap > 0
+ * the filtered map is copied to host `out`; keys (optional) receives the key id of every frame concatenated into the
+ * map, in concatenation order. *n_out and *n_keys (optional) always hold the full counts; an output that does not
+ * fit gets its first cap / keys_cap entries and the call returns S2M_ERR_CAPACITY (the map is installed). */
+int  s2m_extract_surrounding(s2m_handle h, double time_cur, const s2m_kf_params* p /* NULL = defaults */,
+                             void* out, size_t out_stride_bytes, size_t cap, size_t* n_out,
+                             int32_t* keys, size_t keys_cap, size_t* n_keys);
+
 /* ---- ScanContext descriptor (BASELINE config 5) ------------------------- */
 /* SCManager::makeScancontext + makeRingkeyFromScancontext
  * (reference include/Scancontext.cpp:151-211): desc is 20x60 row-major doubles,

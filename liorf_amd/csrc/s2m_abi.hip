@@ -12,6 +12,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <algorithm>
 #include <map>
 #include <new>
 #include <string>
@@ -59,6 +60,17 @@ struct s2m_context {
     VoxWorkspace* vox = nullptr;
     IcpWorkspace* icp = nullptr;       // ICP loop-closure alignment (section 8(f) F4)
     DevBuf icp_src, icp_tgt;           // staging of host clouds
+    // key-frame store (cloudKeyPoses3D / cloudKeyPoses6D / surfCloudKeyFrames, :93-100): every key's 32-byte records in an arena of
+    // blocks that are never moved (the frame table holds raw pointers into them), and per key its position and KfFrame (transform,
+    // records, count) on the device; poses, times and frames mirrored on the host
+    DevBuf kf_pos, kf_frames;
+    std::vector<void*> kf_blocks;
+    size_t kf_block_used = 0, kf_block_cap = 0, kf_cap = 0;
+    std::vector<float> kf_pose;        // 6 per key: x, y, z, roll, pitch, yaw
+    std::vector<double> kf_time;
+    std::vector<KfFrame> kf_frame;
+    size_t scan_ds_n = 0;              // records s2m_downsample_scan left in scan_ds
+    bool have_scan_ds = false;
 
     DevCtx hctx{};
     bool ctx_dirty = true;
@@ -903,6 +915,9 @@ int s2m_destroy(s2m_handle h)
     icp_destroy(h->icp);
     if (h->icp_src.p) (void)hipFree(h->icp_src.p);
     if (h->icp_tgt.p) (void)hipFree(h->icp_tgt.p);
+    for (void* b : h->kf_blocks) (void)hipFree(b);
+    if (h->kf_pos.p) (void)hipFree(h->kf_pos.p);
+    if (h->kf_frames.p) (void)hipFree(h->kf_frames.p);
     if (h->h_state) (void)hipHostFree(h->h_state);
     if (h->h_mm) (void)hipHostFree(h->h_mm);
     if (h->h_sc) (void)hipHostFree(h->h_sc);
@@ -1724,9 +1739,12 @@ int s2m_downsample_scan(s2m_handle h, const void* pts, size_t n, size_t stride_b
             S2M_HIP(h, hipMemcpyAsync(h->vox_in.p, pts, n * stride_bytes, hipMemcpyHostToDevice, h->stream));
             d_in = h->vox_in.as<unsigned char>();
         }
+        h->have_scan_ds = false;
         if ((rc = voxel_into(h, d_in, n, stride_bytes, leaf, h->scan_ds, &res))) return rc;
     }
     *n_out = res.n_out;
+    h->scan_ds_n = res.n_out;
+    h->have_scan_ds = true;
     // laserCloudSurfLastDS stays on the device as the registration's scan; the host copy is for the key-frame store
     if ((rc = set_scan_impl(h, h->scan_ds.p, res.n_out, kDsStride, true))) return rc;
     if (cap > 0 && (rc = download_records(h, h->scan_ds, res.n_out, out, out_stride_bytes, cap))) return rc;
@@ -1807,6 +1825,222 @@ int s2m_transform_cloud(s2m_handle h, const void* pts, size_t n, size_t stride_b
     hipError_t e = vox_transform_frames(h->vox, h->stream, src, stride_bytes, offsets, T, 1, h->frames_xf.as<unsigned char>(), kDsStride);
     if (e != hipSuccess) return fail(h, S2M_ERR_HIP, "cloud transform", e);
     return download_records(h, h->frames_xf, n, out, out_stride_bytes, n);
+}
+
+// ---- the resident key-frame store and extractSurroundingKeyFrames() (:1046-1059) ----------------------
+
+constexpr size_t kKfMaxKeys = (size_t)1 << 24;          // key ids travel in a float intensity in the reference (:991-997)
+constexpr size_t kKfBlockBytes = (size_t)64 << 20;      // arena block: ~2 000 key frames of 1 000 points
+
+int s2m_kf_default_params(s2m_kf_params* p)
+{
+    if (!p) return S2M_ERR_INVALID_ARG;
+    p->search_radius = 50.0f;       // surroundingKeyframeSearchRadius  include/utility.h:240
+    p->density = 1.0f;              // surroundingKeyframeDensity       include/utility.h:238
+    p->map_leaf = 0.2f;             // surroundingKeyframeMapLeafSize   include/utility.h:228
+    p->recent_window_s = 10.0;      // :1003
+    return S2M_OK;
+}
+
+int s2m_kf_reset(s2m_handle h)
+{
+    if (!h) return S2M_ERR_INVALID_ARG;
+    S2M_HIP(h, hipSetDevice(h->device));
+    S2M_HIP(h, hipStreamSynchronize(h->stream));
+    // the store is emptied whatever happens: a block whose hipFree fails is dropped, never freed twice
+    hipError_t e = hipSuccess;
+    for (void* b : h->kf_blocks) { const hipError_t eb = hipFree(b); if (eb != hipSuccess && e == hipSuccess) e = eb; }
+    h->kf_blocks.clear();
+    h->kf_block_used = h->kf_block_cap = 0;
+    h->kf_pose.clear(); h->kf_time.clear(); h->kf_frame.clear();
+    if (e != hipSuccess) return fail(h, S2M_ERR_HIP, "hipFree of a key-frame block", e);
+    return S2M_OK;
+}
+
+int s2m_kf_size(s2m_handle h) { return h ? (int)h->kf_time.size() : S2M_ERR_INVALID_ARG; }
+
+namespace {
+
+bool finite_pose(const float* p)
+{
+    for (int k = 0; k < 6; k++) if (!std::isfinite(p[k])) return false;
+    return true;
+}
+
+KfFrame kf_frame_of(const float pose_xyzrpy[6], const unsigned char* src, int32_t n)
+{
+    KfFrame f{};
+    const float rpyxyz[6] = { pose_xyzrpy[3], pose_xyzrpy[4], pose_xyzrpy[5], pose_xyzrpy[0], pose_xyzrpy[1], pose_xyzrpy[2] };
+    host_pose_to_transform(rpyxyz, f.T, nullptr);          // transCur of :317, once per pose (laserCloudMapContainer, :1025-1035)
+    f.src = src; f.n = n;
+    return f;
+}
+
+// the device arrays hold `want` keys (grow-with-copy: ensure() alone would drop them)
+int kf_reserve(s2m_context* h, size_t want)
+{
+    if (want <= h->kf_cap) return S2M_OK;
+    size_t cap = h->kf_cap ? h->kf_cap : 256;
+    while (cap < want) cap *= 2;
+    const size_t n = h->kf_time.size();
+    struct Part { DevBuf* b; size_t elem; } parts[2] = { { &h->kf_pos, sizeof(float4) }, { &h->kf_frames, sizeof(KfFrame) } };
+    void* np[2] = { nullptr, nullptr };
+    for (int k = 0; k < 2; k++) {
+        hipError_t e = hipMalloc(&np[k], parts[k].elem * cap);
+        if (e != hipSuccess) { if (np[0]) (void)hipFree(np[0]); return fail(h, S2M_ERR_HIP, "key-frame store", e); }
+    }
+    hipError_t e = hipSuccess;
+    for (int k = 0; k < 2 && e == hipSuccess; k++)
+        if (n) e = hipMemcpyAsync(np[k], parts[k].b->p, parts[k].elem * n, hipMemcpyDeviceToDevice, h->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+    if (e != hipSuccess) {                                 // the old arrays stay in place; the new ones go
+        (void)hipFree(np[0]); (void)hipFree(np[1]);
+        return fail(h, S2M_ERR_HIP, "key-frame store copy", e);
+    }
+    for (int k = 0; k < 2; k++) {                          // (the copies are complete: the new arrays are installed in any case)
+        if (parts[k].b->p) (void)hipFree(parts[k].b->p);
+        parts[k].b->p = np[k]; parts[k].b->cap = parts[k].elem * cap;
+    }
+    h->kf_cap = cap;
+    return S2M_OK;
+}
+
+// room for `bytes` of records in the arena (a new block when the current one is full; blocks never move)
+int kf_arena_take(s2m_context* h, size_t bytes, unsigned char** dst)
+{
+    *dst = nullptr;
+    if (bytes == 0) return S2M_OK;
+    if (h->kf_blocks.empty() || h->kf_block_used + bytes > h->kf_block_cap) {
+        const size_t cap = bytes > kKfBlockBytes ? bytes : kKfBlockBytes;
+        void* b = nullptr;
+        S2M_HIP(h, hipMalloc(&b, cap));
+        h->kf_blocks.push_back(b);
+        h->kf_block_cap = cap; h->kf_block_used = 0;
+    }
+    *dst = static_cast<unsigned char*>(h->kf_blocks.back()) + h->kf_block_used;
+    return S2M_OK;
+}
+
+}  // namespace
+
+int s2m_kf_add(s2m_handle h, const float pose_xyzrpy[6], double time, const void* pts, size_t n, size_t stride_bytes, int source)
+{
+    if (!h) return S2M_ERR_INVALID_ARG;
+    if (!pose_xyzrpy || !finite_pose(pose_xyzrpy) || !std::isfinite(time))
+        return fail(h, S2M_ERR_INVALID_ARG, "key pose and time must be finite");
+    if (source != S2M_KF_FROM_HOST && source != S2M_KF_FROM_DEVICE && source != S2M_KF_FROM_LAST_DOWNSAMPLE)
+        return fail(h, S2M_ERR_INVALID_ARG, "unknown key-frame source");
+    int rc;
+    if (source == S2M_KF_FROM_LAST_DOWNSAMPLE) {
+        if (!h->have_scan_ds) return fail(h, S2M_ERR_NO_SCAN, "no s2m_downsample_scan before S2M_KF_FROM_LAST_DOWNSAMPLE");
+        n = h->scan_ds_n;
+    } else if ((rc = check_records(h, pts, n, stride_bytes))) return rc;
+    const size_t N = h->kf_time.size();
+    if (N >= kKfMaxKeys) return fail(h, S2M_ERR_CAPACITY, "key-frame store full (2^24 keys)");
+    S2M_HIP(h, hipSetDevice(h->device));
+    if ((rc = kf_reserve(h, N + 1))) return rc;
+    unsigned char* dst = nullptr;
+    if ((rc = kf_arena_take(h, kDsStride * n, &dst))) return rc;
+    if (n > 0) {
+        hipError_t e = hipSuccess;
+        if (source == S2M_KF_FROM_LAST_DOWNSAMPLE)
+            e = hipMemcpyAsync(dst, h->scan_ds.p, kDsStride * n, hipMemcpyDeviceToDevice, h->stream);
+        else if (source == S2M_KF_FROM_DEVICE)
+            e = vox_copy_records(h->stream, static_cast<const unsigned char*>(pts), stride_bytes, n, dst, kDsStride);
+        else {
+            if ((rc = ensure(h, h->vox_in, n * stride_bytes))) return rc;
+            e = hipMemcpyAsync(h->vox_in.p, pts, n * stride_bytes, hipMemcpyHostToDevice, h->stream);
+            if (e == hipSuccess) e = vox_copy_records(h->stream, h->vox_in.as<unsigned char>(), stride_bytes, n, dst, kDsStride);
+        }
+        if (e != hipSuccess) return fail(h, S2M_ERR_HIP, "key-frame copy", e);
+    }
+    const KfFrame f = kf_frame_of(pose_xyzrpy, dst, (int32_t)n);
+    const float4 p = make_float4(pose_xyzrpy[0], pose_xyzrpy[1], pose_xyzrpy[2], 0.0f);
+    S2M_HIP(h, hipMemcpyAsync(h->kf_pos.as<float4>() + N, &p, sizeof(p), hipMemcpyHostToDevice, h->stream));
+    S2M_HIP(h, hipMemcpyAsync(h->kf_frames.as<KfFrame>() + N, &f, sizeof(f), hipMemcpyHostToDevice, h->stream));
+    S2M_HIP(h, hipStreamSynchronize(h->stream));          // the caller's cloud and the staged entries are free again
+    // committed only now: a failure above leaves the store as it was
+    h->kf_block_used += kDsStride * n;
+    h->kf_pose.insert(h->kf_pose.end(), pose_xyzrpy, pose_xyzrpy + 6);
+    h->kf_time.push_back(time);
+    h->kf_frame.push_back(f);
+    return S2M_OK;
+}
+
+int s2m_kf_set_poses(s2m_handle h, int first, int count, const float* poses_xyzrpy)
+{
+    if (!h) return S2M_ERR_INVALID_ARG;
+    const size_t N = h->kf_time.size();
+    if (first < 0 || count < 0 || (size_t)first + (size_t)count > N || (count > 0 && !poses_xyzrpy))
+        return fail(h, S2M_ERR_INVALID_ARG, "pose range outside the key-frame store");
+    for (int k = 0; k < count; k++)
+        if (!finite_pose(poses_xyzrpy + 6 * (size_t)k)) return fail(h, S2M_ERR_INVALID_ARG, "key poses must be finite");
+    if (count == 0) return S2M_OK;
+    S2M_HIP(h, hipSetDevice(h->device));
+    std::vector<float4> pos((size_t)count);
+    std::vector<KfFrame> fr((size_t)count);
+    for (int k = 0; k < count; k++) {
+        const float* q = poses_xyzrpy + 6 * (size_t)k;
+        pos[k] = make_float4(q[0], q[1], q[2], 0.0f);
+        fr[k] = kf_frame_of(q, h->kf_frame[first + k].src, h->kf_frame[first + k].n);
+    }
+    S2M_HIP(h, hipMemcpyAsync(h->kf_pos.as<float4>() + first, pos.data(), sizeof(float4) * count, hipMemcpyHostToDevice, h->stream));
+    S2M_HIP(h, hipMemcpyAsync(h->kf_frames.as<KfFrame>() + first, fr.data(), sizeof(KfFrame) * count, hipMemcpyHostToDevice, h->stream));
+    S2M_HIP(h, hipStreamSynchronize(h->stream));
+    std::copy(poses_xyzrpy, poses_xyzrpy + 6 * (size_t)count, h->kf_pose.begin() + 6 * (size_t)first);
+    for (int k = 0; k < count; k++) h->kf_frame[first + k] = fr[k];
+    return S2M_OK;
+}
+
+int s2m_extract_surrounding(s2m_handle h, double time_cur, const s2m_kf_params* p, void* out, size_t out_stride_bytes, size_t cap,
+                            size_t* n_out, int32_t* keys, size_t keys_cap, size_t* n_keys)
+{
+    if (!h) return S2M_ERR_INVALID_ARG;
+    s2m_kf_params prm;
+    if (p) prm = *p; else s2m_kf_default_params(&prm);
+    if (!(prm.search_radius > 0.0f) || !std::isfinite(prm.search_radius) || !(prm.density > 0.0f) || !std::isfinite(prm.density) ||
+        !std::isfinite(prm.recent_window_s) || !std::isfinite(time_cur))
+        return fail(h, S2M_ERR_INVALID_ARG, "search radius and density must be positive, window and time finite");
+    int rc = check_leaf(h, prm.map_leaf);
+    if (rc) return rc;
+    if (!n_out || (cap > 0 && (!out || out_stride_bytes < 12 || (out_stride_bytes & 3))) || (keys_cap > 0 && !keys))
+        return fail(h, S2M_ERR_INVALID_ARG, "bad output buffer");
+    *n_out = 0;
+    if (n_keys) *n_keys = 0;
+    const size_t N = h->kf_time.size();
+    if (N == 0) return S2M_OK;                             // cloudKeyPoses3D->points.empty(): nothing changes (:1048-1049)
+    // (e) the recent keys: i = N-1, N-2, ... while timeLaserInfoCur - time < 10.0 (:1000-1007)
+    int n_recent = 0;
+    for (size_t i = N; i-- > 0 && time_cur - h->kf_time[i] < prm.recent_window_s;) n_recent++;
+    S2M_HIP(h, hipSetDevice(h->device));
+    KfSelect sel;
+    KfTable tab;
+    hipError_t e = kf_select(h->vox, h->stream, h->kf_pos.as<float4>(), h->kf_frames.as<KfFrame>(), (int)N, n_recent,
+                             prm.search_radius, prm.density, &sel, &tab);
+    if (e != hipSuccess) return fail(h, S2M_ERR_HIP, "key-frame selection", e);
+    if (n_keys) *n_keys = (size_t)sel.n_frames;
+    if (sel.n_points > 0x3fffffffLL) return fail(h, S2M_ERR_CAPACITY, "too many points");
+    VoxResult res;
+    if (sel.n_points > 0) {
+        const size_t total = (size_t)sel.n_points;
+        if ((rc = ensure(h, h->frames_xf, kDsStride * total))) return rc;
+        e = vox_transform_frames_device(h->stream, tab.src, kDsStride, tab.offsets, tab.T, sel.n_frames, total,
+                                        h->frames_xf.as<unsigned char>(), kDsStride);
+        if (e != hipSuccess) return fail(h, S2M_ERR_HIP, "key-frame transform", e);
+        if ((rc = voxel_into(h, h->frames_xf.as<unsigned char>(), total, kDsStride, prm.map_leaf, h->map_ds, &res))) return rc;
+    }
+    *n_out = res.n_out;
+    // laserCloudSurfFromMapDS becomes the search index (:1302), as in s2m_extract_cloud
+    if ((rc = set_map_impl(h, h->map_ds.p, res.n_out, kDsStride, true))) return rc;
+    if (cap > 0 && (rc = download_records(h, h->map_ds, res.n_out, out, out_stride_bytes, cap))) return rc;
+    const size_t nk = (size_t)sel.n_frames < keys_cap ? (size_t)sel.n_frames : keys_cap;
+    if (nk > 0) {
+        S2M_HIP(h, hipMemcpyAsync(keys, tab.keys, sizeof(int32_t) * nk, hipMemcpyDeviceToHost, h->stream));
+        S2M_HIP(h, hipStreamSynchronize(h->stream));
+    }
+    if (cap > 0 && res.n_out > cap) return fail(h, S2M_ERR_CAPACITY, "output buffer too small for the local map");
+    if (keys_cap > 0 && (size_t)sel.n_frames > keys_cap) return fail(h, S2M_ERR_CAPACITY, "key buffer too small for the frame list");
+    return res.leaf_too_small ? S2M_WARN_LEAF_TOO_SMALL : S2M_OK;
 }
 
 // ---- section 8(f) row F4: ICP loop-closure alignment -----------------------------------------------

@@ -113,6 +113,8 @@ __global__ __launch_bounds__(256) void k_vox_bbox(const unsigned char* __restric
     }
 }
 
+__device__ void vox_setup_fill(VoxSetup* s, float leaf, const uint32_t lo[3], const uint32_t hi[3], int cnt);
+
 __global__ __launch_bounds__(64) void k_vox_setup(VoxSetup* s, float leaf, const uint32_t* __restrict__ part, int nparts)
 {
     uint32_t lo[3] = { 0xffffffffu, 0xffffffffu, 0xffffffffu }, hi[3] = { 0u, 0u, 0u };
@@ -130,6 +132,12 @@ __global__ __launch_bounds__(64) void k_vox_setup(VoxSetup* s, float leaf, const
         cnt += __shfl_down(cnt, off, 64);
     }
     if (threadIdx.x != 0) return;
+    vox_setup_fill(s, leaf, lo, hi, cnt);
+}
+
+// the setup of a filter run from the ordered-uint box and the count of the finite points (also the key-pose filter of k_kf_select_candidates)
+__device__ void vox_setup_fill(VoxSetup* s, float leaf, const uint32_t lo[3], const uint32_t hi[3], int cnt)
+{
     for (int d = 0; d < 3; d++) { s->mm[d] = lo[d]; s->mm[3 + d] = hi[d]; }
     s->n_valid = cnt; s->n_out = 0; s->leaf_too_small = 0; s->n_long = 0; s->n_vlong = 0;
     const float inv = 1.0f / leaf;
@@ -725,11 +733,244 @@ __global__ __launch_bounds__(256) void k_transform_frames(const unsigned char* c
     for (int k = 5; k < words; k++) o[k] = 0.0f;
 }
 
+
+// ------------------------------------------------------------------------------------------
+// extractSurroundingKeyFrames() on the resident key-frame store: three kernels choose the frames and leave the table that
+// k_transform_frames reads. Everything is a pure function of the store: no atomics, sums in a fixed order.
+//   k_kf_select_candidates  one workgroup: radius search (:984), sort by (d2, key), VoxelGrid of the key positions (:991-992)
+//   k_kf_select_nearest     nearest key of every centroid among all keys (:993-997), a workgroup per centroid
+//   k_kf_select_frames      one workgroup: centroid keys, then the recent keys (:1000-1007), distance filter (:1018), table
+// ------------------------------------------------------------------------------------------
+constexpr int kKfThreads = 1024;
+constexpr int kKfTile = 4096;          // candidates sorted in LDS; more are sorted in place in global memory by the same code
+
+struct KfSelState {
+    int32_t n_cand;
+    int32_t n_cent;
+};
+
+// FLANN's L2_Simple accumulation: ((dx^2 + dy^2) + dz^2), fp32, no contraction
+__device__ __forceinline__ float kf_d2(float4 a, float4 b)
+{
+    const float dx = a.x - b.x, dy = a.y - b.y, dz = a.z - b.z;
+    return (dx * dx + dy * dy) + dz * dz;
+}
+
+// exclusive prefix of v over the workgroup (kKfThreads lanes) and its total; s_w: kKfThreads / 64 words of LDS
+template <typename T>
+__device__ __forceinline__ T kf_block_scan(T v, T* s_w, T* total)
+{
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    T x = v;
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+        const T y = __shfl_up(x, off, 64);
+        if (lane >= off) x += y;
+    }
+    if (lane == 63) s_w[wave] = x;
+    __syncthreads();
+    T base = 0, tot = 0;
+    for (int k = 0; k < kKfThreads / 64; k++) {
+        const T c = s_w[k];
+        if (k < wave) base += c;
+        tot += c;
+    }
+    __syncthreads();
+    *total = tot;
+    return base + x - v;
+}
+
+// ascending bitonic sort of a[0 .. P), P a power of two, by the whole workgroup (a: LDS or global memory; keys are unique)
+__device__ void kf_bitonic(unsigned long long* a, int P)
+{
+    for (int k = 2; k <= P; k <<= 1)
+        for (int j = k >> 1; j > 0; j >>= 1) {
+            for (int t = threadIdx.x; t < (P >> 1); t += kKfThreads) {
+                const int i = 2 * t - (t & (j - 1)), l = i + j;
+                const unsigned long long x = a[i], y = a[l];
+                if ((x > y) == ((i & k) == 0)) { a[i] = y; a[l] = x; }
+            }
+            __syncthreads();
+        }
+}
+
+__global__ __launch_bounds__(kKfThreads) void k_kf_select_candidates(const float4* __restrict__ pos, int n, float r2, float density,
+                                                                     unsigned long long* __restrict__ g_key, int32_t* __restrict__ g_ord,
+                                                                     float4* __restrict__ cent, KfSelState* __restrict__ st)
+{
+    __shared__ unsigned long long s_key[kKfTile];
+    __shared__ int32_t s_ord[kKfTile];
+    __shared__ int s_w[kKfThreads / 64];
+    __shared__ uint32_t s_mm[kKfThreads / 64][6];
+    __shared__ VoxSetup s_vs;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const float4 q = pos[n - 1];
+    // (b) every key with d2 < r2, compacted in key order, as (d2 bits, key): FLANN's sorted radius result once sorted
+    uint32_t lo[3] = { 0xffffffffu, 0xffffffffu, 0xffffffffu }, hi[3] = { 0u, 0u, 0u };
+    int m = 0;
+    for (int base = 0; base < n; base += kKfThreads) {
+        const int i = base + tid;
+        bool in = false;
+        float4 p = q;
+        float d2 = 0.0f;
+        if (i < n) { p = pos[i]; d2 = kf_d2(p, q); in = d2 < r2; }
+        int tot;
+        const int at = m + kf_block_scan<int>(in ? 1 : 0, s_w, &tot);
+        if (in) {
+            g_key[at] = ((unsigned long long)__float_as_uint(d2) << 32) | (uint32_t)i;
+            const uint32_t o[3] = { f2ord(p.x), f2ord(p.y), f2ord(p.z) };
+#pragma unroll
+            for (int d = 0; d < 3; d++) { lo[d] = min(lo[d], o[d]); hi[d] = max(hi[d], o[d]); }
+        }
+        m += tot;
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1)
+#pragma unroll
+        for (int d = 0; d < 3; d++) {
+            lo[d] = min(lo[d], (uint32_t)__shfl_down((int)lo[d], off, 64));
+            hi[d] = max(hi[d], (uint32_t)__shfl_down((int)hi[d], off, 64));
+        }
+    if (lane == 0)
+        for (int d = 0; d < 3; d++) { s_mm[wave][d] = lo[d]; s_mm[wave][3 + d] = hi[d]; }
+    __syncthreads();
+    if (tid == 0) {
+        for (int w = 1; w < kKfThreads / 64; w++)
+            for (int d = 0; d < 3; d++) { lo[d] = min(lo[d], s_mm[w][d]); hi[d] = max(hi[d], s_mm[w][3 + d]); }
+        // (c) pcl::VoxelGrid over the records {P[i], 1, intensity i} in the order of (b): the filter's own setup
+        vox_setup_fill(&s_vs, density, lo, hi, m);
+        st->n_cand = m;
+    }
+    int P = 1;
+    while (P < m) P <<= 1;
+    const bool in_lds = P <= kKfTile;
+    unsigned long long* a = in_lds ? s_key : g_key;
+    int32_t* ord = in_lds ? s_ord : g_ord;
+    for (int r = tid; r < P; r += kKfThreads) a[r] = r < m ? g_key[r] : ~0ull;
+    __syncthreads();
+    kf_bitonic(a, P);
+    // ord[rank] = key; the filter's stable sort by voxel index: (voxel index, rank); PCL's leaf-too-small case passes the input through
+    const bool pass = s_vs.leaf_too_small != 0;
+    for (int r = tid; r < P; r += kKfThreads) {
+        unsigned long long v = ~0ull;
+        if (r < m) {
+            const int i = (int)(uint32_t)a[r];
+            ord[r] = i;
+            const float4 p = pos[i];
+            const uint32_t vk = pass ? (uint32_t)r : voxel_key(p.x, p.y, p.z, &s_vs);
+            v = ((unsigned long long)vk << 32) | (uint32_t)r;
+        }
+        a[r] = v;
+    }
+    __syncthreads();
+    if (!pass) kf_bitonic(a, P);
+    // one centroid per run of equal voxel index: sequential fp32 sums in rank order, / count (write_centroid)
+    int c0 = 0;
+    for (int base = 0; base < m; base += kKfThreads) {
+        const int r = base + tid;
+        const bool head = r < m && (r == 0 || (a[r] >> 32) != (a[r - 1] >> 32));
+        int tot;
+        const int c = c0 + kf_block_scan<int>(head ? 1 : 0, s_w, &tot);
+        if (head) {
+            const uint32_t vk = (uint32_t)(a[r] >> 32);
+            float sx = 0.0f, sy = 0.0f, sz = 0.0f;
+            int e = r;
+            for (; e < m && (uint32_t)(a[e] >> 32) == vk; e++) {
+                const float4 p = pos[ord[(int)(uint32_t)a[e]]];
+                sx += p.x; sy += p.y; sz += p.z;
+            }
+            const float cnt = (float)(e - r);
+            cent[c] = make_float4(sx / cnt, sy / cnt, sz / cnt, 0.0f);
+        }
+        c0 += tot;
+    }
+    if (tid == 0) st->n_cent = c0;
+}
+
+// (d) kdtreeSurroundingKeyPoses->nearestKSearch(centroid, 1) over all n keys: minimum of (d2 bits, key), ties to the lower key
+__global__ __launch_bounds__(256) void k_kf_select_nearest(const float4* __restrict__ pos, int n, const float4* __restrict__ cent,
+                                                           const KfSelState* __restrict__ st, int32_t* __restrict__ nn)
+{
+    __shared__ unsigned long long s_best[4];
+    const int n_cent = st->n_cent;
+    for (int c = blockIdx.x; c < n_cent; c += gridDim.x) {
+        const float4 p = cent[c];
+        unsigned long long best = ~0ull;
+        for (int i = threadIdx.x; i < n; i += 256) {
+            const unsigned long long v = ((unsigned long long)__float_as_uint(kf_d2(p, pos[i])) << 32) | (uint32_t)i;
+            best = v < best ? v : best;
+        }
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) {
+            const unsigned long long o = __shfl_down(best, off, 64);
+            best = o < best ? o : best;
+        }
+        if ((threadIdx.x & 63) == 0) s_best[threadIdx.x >> 6] = best;
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            unsigned long long b = s_best[0];
+            for (int w = 1; w < 4; w++) b = s_best[w] < b ? s_best[w] : b;
+            nn[c] = (int32_t)(uint32_t)b;
+        }
+        __syncthreads();
+    }
+}
+
+// (e) + (f) + the frame table: entry e < n_cent is centroid e's key tested at the centroid, entry n_cent + r is key n-1-r tested at
+// its own position; an entry farther than `radius` from the newest key is dropped; survivors keep their order
+__global__ __launch_bounds__(kKfThreads) void k_kf_select_frames(const float4* __restrict__ pos, const KfFrame* __restrict__ frames, int n,
+                                                                 int n_recent, float radius, const float4* __restrict__ cent,
+                                                                 const int32_t* __restrict__ nn, const KfSelState* __restrict__ st,
+                                                                 int32_t* __restrict__ keys, const unsigned char** __restrict__ t_src,
+                                                                 int32_t* __restrict__ t_off, float* __restrict__ t_T, KfSelect* out)
+{
+    __shared__ int s_w[kKfThreads / 64];
+    __shared__ long long s_wl[kKfThreads / 64];
+    const int n_cent = st->n_cent, n_ent = n_cent + n_recent;
+    const float4 q = pos[n - 1];
+    int nf = 0;
+    long long np = 0;
+    for (int base = 0; base < n_ent; base += kKfThreads) {
+        const int e = base + threadIdx.x;
+        bool keep = false;
+        int k = 0;
+        if (e < n_ent) {
+            float4 p;
+            if (e < n_cent) { k = nn[e]; p = cent[e]; }
+            else { k = n - 1 - (e - n_cent); p = pos[k]; }
+            const float dx = p.x - q.x, dy = p.y - q.y, dz = p.z - q.z;
+            keep = !(sqrtf(dx * dx + dy * dy + dz * dz) > radius);         // pointDistance(...) > surroundingKeyframeSearchRadius: continue
+        }
+        int tot;
+        long long ptot;
+        const int j = nf + kf_block_scan<int>(keep ? 1 : 0, s_w, &tot);
+        const long long cnt = keep ? (long long)frames[k].n : 0;
+        const long long o = np + kf_block_scan<long long>(cnt, s_wl, &ptot);
+        if (keep) {
+            keys[j] = k;
+            t_src[j] = frames[k].src;
+            t_off[j] = (int32_t)o;
+#pragma unroll
+            for (int u = 0; u < 12; u++) t_T[12 * (size_t)j + u] = frames[k].T[u];
+        }
+        nf += tot;
+        np += ptot;
+    }
+    if (threadIdx.x == 0) {
+        t_off[nf] = (int32_t)np;
+        out->n_frames = nf;
+        out->n_cent = n_cent;
+        out->n_points = np;
+    }
+}
+
 }  // namespace
 
 struct VoxWorkspace {
     Buf setup, keys_a, keys_b, vals_a, vals_b, heads, rs_hist, rs_tot, frame_tab, long_list;
     VoxSetup* h_setup = nullptr;          // pinned
+    Buf kf_key, kf_ord, kf_cent, kf_nn, kf_st, kf_tab;   // key-frame selection: sort keys, ranks, centroids, their keys, counts, table
+    KfSelect* h_kf = nullptr;             // pinned
 };
 
 VoxWorkspace* vox_create()
@@ -737,16 +978,19 @@ VoxWorkspace* vox_create()
     VoxWorkspace* w = new (std::nothrow) VoxWorkspace();
     if (!w) return nullptr;
     if (w->setup.ensure(sizeof(VoxSetup)) != hipSuccess ||
-        hipHostMalloc((void**)&w->h_setup, sizeof(VoxSetup)) != hipSuccess) { vox_destroy(w); return nullptr; }
+        hipHostMalloc((void**)&w->h_setup, sizeof(VoxSetup)) != hipSuccess ||
+        hipHostMalloc((void**)&w->h_kf, sizeof(KfSelect)) != hipSuccess) { vox_destroy(w); return nullptr; }
     return w;
 }
 
 void vox_destroy(VoxWorkspace* w)
 {
     if (!w) return;
-    Buf* bufs[] = { &w->setup, &w->keys_a, &w->keys_b, &w->vals_a, &w->vals_b, &w->heads, &w->rs_hist, &w->rs_tot, &w->frame_tab, &w->long_list };
+    Buf* bufs[] = { &w->setup, &w->keys_a, &w->keys_b, &w->vals_a, &w->vals_b, &w->heads, &w->rs_hist, &w->rs_tot, &w->frame_tab, &w->long_list,
+                    &w->kf_key, &w->kf_ord, &w->kf_cent, &w->kf_nn, &w->kf_st, &w->kf_tab };
     for (Buf* b : bufs) if (b->p) (void)hipFree(b->p);
     if (w->h_setup) (void)hipHostFree(w->h_setup);
+    if (w->h_kf) (void)hipHostFree(w->h_kf);
     delete w;
 }
 
@@ -838,10 +1082,64 @@ hipError_t vox_transform_frames(VoxWorkspace* w, hipStream_t stream, const unsig
     VOX_TRY(hipMemcpyAsync(tab, h_src, sizeof(void*) * (size_t)n_frames, hipMemcpyHostToDevice, stream));
     VOX_TRY(hipMemcpyAsync(tab + ptr_bytes, h_offsets, sizeof(int32_t) * (size_t)(n_frames + 1), hipMemcpyHostToDevice, stream));
     VOX_TRY(hipMemcpyAsync(tab + ptr_bytes + off_bytes, h_T, t_bytes, hipMemcpyHostToDevice, stream));
-    hipLaunchKernelGGL(k_transform_frames, dim3((n + 255) / 256), dim3(256), 0, stream,
-                       (const unsigned char* const*)tab, stride, (const int32_t*)(tab + ptr_bytes),
-                       (const float*)(tab + ptr_bytes + off_bytes), n_frames, d_out, out_stride);
+    return vox_transform_frames_device(stream, (const unsigned char* const*)tab, stride, (const int32_t*)(tab + ptr_bytes),
+                                       (const float*)(tab + ptr_bytes + off_bytes), n_frames, (size_t)n, d_out, out_stride);
+}
+
+hipError_t vox_transform_frames_device(hipStream_t stream, const unsigned char* const* d_src, size_t stride, const int32_t* d_offsets,
+                                       const float* d_T, int n_frames, size_t n_points, unsigned char* d_out, size_t out_stride)
+{
+    if (n_frames <= 0 || n_points == 0) return hipSuccess;
+    hipLaunchKernelGGL(k_transform_frames, dim3((unsigned)((n_points + 255) / 256)), dim3(256), 0, stream,
+                       d_src, stride, d_offsets, d_T, n_frames, d_out, out_stride);
     return hipGetLastError();
+}
+
+hipError_t vox_copy_records(hipStream_t stream, const unsigned char* d_in, size_t stride, size_t n, unsigned char* d_out, size_t out_stride)
+{
+    if (n == 0) return hipSuccess;
+    hipLaunchKernelGGL(k_copy_records, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, d_in, stride, (int)n, d_out, out_stride);
+    return hipGetLastError();
+}
+
+hipError_t kf_select(VoxWorkspace* w, hipStream_t stream, const float4* d_pos, const KfFrame* d_frames, int n, int n_recent,
+                     float radius, float density, KfSelect* out, KfTable* tab)
+{
+    *out = KfSelect{};
+    if (n <= 0) return hipSuccess;
+    size_t P = 1;
+    while (P < (size_t)n) P <<= 1;
+    const size_t n_ent = 2 * (size_t)n + 1;                    // centroids (<= n) + recent keys (<= n)
+    VOX_TRY(w->kf_key.ensure(sizeof(unsigned long long) * P));
+    VOX_TRY(w->kf_ord.ensure(sizeof(int32_t) * (size_t)n));
+    VOX_TRY(w->kf_cent.ensure(sizeof(float4) * (size_t)n));
+    VOX_TRY(w->kf_nn.ensure(sizeof(int32_t) * (size_t)n));
+    VOX_TRY(w->kf_st.ensure(sizeof(KfSelState)));
+    // table: source pointers | offsets | transforms | keys
+    const size_t ptr_bytes = (sizeof(void*) * n_ent + 15) & ~(size_t)15;
+    const size_t off_bytes = (sizeof(int32_t) * (n_ent + 1) + 15) & ~(size_t)15;
+    const size_t t_bytes = sizeof(float) * 12 * n_ent;
+    VOX_TRY(w->kf_tab.ensure(ptr_bytes + off_bytes + t_bytes + sizeof(int32_t) * n_ent));
+    unsigned char* t = w->kf_tab.as<unsigned char>();
+    tab->src = (const unsigned char* const*)t;
+    tab->offsets = (const int32_t*)(t + ptr_bytes);
+    tab->T = (const float*)(t + ptr_bytes + off_bytes);
+    tab->keys = (const int32_t*)(t + ptr_bytes + off_bytes + t_bytes);
+    KfSelState* st = w->kf_st.as<KfSelState>();
+    float4* cent = w->kf_cent.as<float4>();
+    int32_t* nn = w->kf_nn.as<int32_t>();
+    const float r2 = radius * radius;
+    hipLaunchKernelGGL(k_kf_select_candidates, dim3(1), dim3(kKfThreads), 0, stream, d_pos, n, r2, density,
+                       w->kf_key.as<unsigned long long>(), w->kf_ord.as<int32_t>(), cent, st);
+    hipLaunchKernelGGL(k_kf_select_nearest, dim3((unsigned)(n < 1024 ? n : 1024)), dim3(256), 0, stream, d_pos, n, (const float4*)cent,
+                       (const KfSelState*)st, nn);
+    hipLaunchKernelGGL(k_kf_select_frames, dim3(1), dim3(kKfThreads), 0, stream, d_pos, d_frames, n, n_recent, radius, (const float4*)cent,
+                       (const int32_t*)nn, (const KfSelState*)st, (int32_t*)tab->keys, (const unsigned char**)t, (int32_t*)tab->offsets,
+                       (float*)tab->T, w->h_kf);
+    VOX_TRY(hipGetLastError());
+    VOX_TRY(hipStreamSynchronize(stream));                   // the one wait: the counts size the transform launch
+    *out = *w->h_kf;
+    return hipSuccess;
 }
 
 }  // namespace s2m

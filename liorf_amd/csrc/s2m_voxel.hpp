@@ -34,4 +34,37 @@ hipError_t vox_transform_frames(VoxWorkspace* w, hipStream_t stream, const unsig
                                 const int32_t* h_offsets, const float* h_T, int n_frames,
                                 unsigned char* d_out, size_t out_stride);
 
+// The same with the frame table already in device memory (src[f], offsets[0 .. n_frames], T[12 f ..]): n_points = offsets[n_frames]
+// sizes the launch.
+hipError_t vox_transform_frames_device(hipStream_t stream, const unsigned char* const* d_src, size_t stride, const int32_t* d_offsets,
+                                       const float* d_T, int n_frames, size_t n_points, unsigned char* d_out, size_t out_stride);
+
+// n records of `stride` bytes -> records of out_stride bytes (words past the input's are 0), all on the device.
+hipError_t vox_copy_records(hipStream_t stream, const unsigned char* d_in, size_t stride, size_t n, unsigned char* d_out, size_t out_stride);
+
+// ---- extractSurroundingKeyFrames() on the resident key-frame store (extractNearby :975-1010 + the selection of extractCloud
+// :1012-1044). The store's per-key data the selection reads:
+struct KfFrame {                           // what the frame table takes from key k (64 bytes)
+    float                T[12];            // row-major 3x4 transform of the key pose (pcl::getTransformation, :317)
+    const unsigned char* src;              // the key's 32-byte records
+    int32_t              n;                // their count
+    int32_t              pad;
+};
+struct KfSelect {                          // written by the device (pinned host memory)
+    int32_t   n_frames;                    // entries of the frame table (= key ids reported)
+    int32_t   n_cent;                      // centroids of the key-pose filter
+    long long n_points;                    // records of the concatenated cloud
+};
+struct KfTable {                           // the frame table, device memory, valid until the next kf_select on the workspace
+    const unsigned char* const* src;
+    const int32_t* offsets;
+    const float* T;
+    const int32_t* keys;
+};
+// pos[k] = {x, y, z, 0} of key k, k = 0 .. n-1. n_recent: the newest keys whose time passes the recent-key test (:1000-1007, counted by
+// the caller in double). Chooses the frames (radius search, key-pose voxel filter with leaf `density`, nearest key of every
+// centroid, recent keys, distance filter), writes the table and synchronises `stream` once for the counts.
+hipError_t kf_select(VoxWorkspace* w, hipStream_t stream, const float4* d_pos, const KfFrame* d_frames, int n, int n_recent,
+                     float radius, float density, KfSelect* out, KfTable* tab);
+
 }  // namespace s2m

@@ -138,6 +138,57 @@ public:
         haveKeyPoses = !cloudKeyPoses6D.empty();
     }
 
+    // The resident key-frame store (s2m_kf_*): the device keeps every key frame's cloud and pose, so the handler's
+    // extractSurroundingKeyFrames() needs no kd-tree over the key poses and uploads no key-frame cloud. The host copies
+    // (cloudKeyPoses6D, surfCloudKeyFrames) stay for the loop-closure thread and map saving.
+    float surroundingKeyframeDensity = 1.0f;          // include/utility.h:238 (the shipped yaml files set 2.0)
+    double timeLaserInfoCur = 0;                      // (:255)
+    std::vector<int> surroundingKeyInds;              // the key ids the last extractSurroundingKeyFrames() concatenated
+
+    // void extractSurroundingKeyFrames() (:1046-1059): extractNearby + extractCloud against the store, map installed
+    void extractSurroundingKeyFrames()
+    {
+        s2m_kf_params p;
+        s2m_kf_default_params(&p);
+        p.search_radius = surroundingKeyframeSearchRadius;
+        p.density = surroundingKeyframeDensity;
+        p.map_leaf = surroundingKeyframeMapLeafSize;
+        surroundingKeyInds.resize(2 * cloudKeyPoses6D.size() + 1);
+        size_t n_out = 0, n_keys = 0;
+        checkVoxel(s2m_extract_surrounding(h_, timeLaserInfoCur, &p, nullptr, sizeof(PointXYZI), 0, &n_out,
+                                           surroundingKeyInds.data(), surroundingKeyInds.size(), &n_keys),
+                   "s2m_extract_surrounding");
+        surroundingKeyInds.resize(n_keys);
+        if (!cloudKeyPoses6D.empty()) {
+            laserCloudSurfFromMapDSNum = (int)n_out;
+            haveKeyPoses = true;
+        }
+    }
+
+    // the key-frame part of saveKeyFramesAndFactor() (:1549-1580): the pose after scan2MapOptimization() and
+    // laserCloudSurfLastDS as downsampleCurrentScan() left it on the device (copied device to device)
+    void saveKeyFrame()
+    {
+        PointTypePose p;
+        p.x = transformTobeMapped[3]; p.y = transformTobeMapped[4]; p.z = transformTobeMapped[5];
+        p.roll = transformTobeMapped[0]; p.pitch = transformTobeMapped[1]; p.yaw = transformTobeMapped[2];
+        p.intensity = (float)cloudKeyPoses6D.size();
+        p.time = timeLaserInfoCur;
+        const float v[6] = { p.x, p.y, p.z, p.roll, p.pitch, p.yaw };
+        check(s2m_kf_add(h_, v, timeLaserInfoCur, nullptr, 0, sizeof(PointXYZI), S2M_KF_FROM_LAST_DOWNSAMPLE), "s2m_kf_add");
+        cloudKeyPoses6D.push_back(p);
+        surfCloudKeyFrames.push_back(laserCloudSurfLastDS);
+    }
+
+    // correctPoses() (:1611-1640) after the pose graph moved the key poses: cloudKeyPoses6D holds the new values
+    void correctPoses()
+    {
+        std::vector<float> v;
+        v.reserve(6 * cloudKeyPoses6D.size());
+        for (const PointTypePose& p : cloudKeyPoses6D) { const float q[6] = { p.x, p.y, p.z, p.roll, p.pitch, p.yaw }; v.insert(v.end(), q, q + 6); }
+        check(s2m_kf_set_poses(h_, 0, (int)cloudKeyPoses6D.size(), v.data()), "s2m_kf_set_poses");
+    }
+
     // The reference reads imuType / imuRPYWeight / z_tollerance / rotation_tollerance (ParamServer members, set from
     // the yaml after construction) whenever transformUpdate() runs (:1325-1350): the current member values are
     // handed to the library before every registration.

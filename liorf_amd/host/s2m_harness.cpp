@@ -9,6 +9,9 @@
 //       the handler's three steps in order: extractCloud() over the key frames listed in frames.txt (one line
 //       "n_points x y z roll pitch yaw" per frame, clouds back to back in frames.bin), downsampleCurrentScan(),
 //       scan2MapOptimization().
+//   s2m_harness --keyframes scans.bin scans.txt map_leaf scan_leaf density
+//       a scripted trajectory through extractSurroundingKeyFrames() -> downsampleCurrentScan() ->
+//       scan2MapOptimization() -> saveKeyFrame() on the resident key-frame store; prints every pose.
 #include <cstdio>
 #include <cstdlib>
 #include <fstream>
@@ -67,6 +70,38 @@ static int run_chain(char** argv)
     return 0;
 }
 
+// --keyframes scans.bin scans.txt map_leaf scan_leaf density: a scripted trajectory through the handler with the resident
+// key-frame store. scans.txt holds one line "n_points time roll pitch yaw x y z" per scan (the guess), the raw scans back to back
+// in scans.bin; every scan runs extractSurroundingKeyFrames() -> downsampleCurrentScan() -> scan2MapOptimization() ->
+// saveKeyFrame() and prints "pose <i> roll pitch yaw x y z".
+static int run_keyframes(char** argv)
+{
+    liorf_amd::MapOptimizationS2M node;
+    const std::vector<liorf_amd::PointXYZI> all = read_cloud(argv[2]);
+    std::ifstream tab(argv[3]);
+    if (!tab) throw std::runtime_error(std::string("cannot open ") + argv[3]);
+    node.surroundingKeyframeMapLeafSize = (float)std::atof(argv[4]);
+    node.mappingSurfLeafSize = (float)std::atof(argv[5]);
+    node.surroundingKeyframeDensity = (float)std::atof(argv[6]);
+    size_t n, at = 0;
+    double t;
+    float g[6];
+    for (int i = 0; tab >> n >> t >> g[0] >> g[1] >> g[2] >> g[3] >> g[4] >> g[5]; i++) {
+        if (at + n > all.size()) throw std::runtime_error("scans.txt asks for more points than scans.bin holds");
+        node.timeLaserInfoCur = t;
+        node.extractSurroundingKeyFrames();
+        node.laserCloudSurfLast.assign(all.begin() + (std::ptrdiff_t)at, all.begin() + (std::ptrdiff_t)(at + n));
+        at += n;
+        node.downsampleCurrentScan();
+        for (int k = 0; k < 6; k++) node.transformTobeMapped[k] = g[k];
+        node.scan2MapOptimization();
+        node.saveKeyFrame();
+        const float* p = node.transformTobeMapped;
+        std::printf("pose %d %.9g %.9g %.9g %.9g %.9g %.9g\n", i, p[0], p[1], p[2], p[3], p[4], p[5]);
+    }
+    return 0;
+}
+
 // --many map.bin roll pitch yaw x y z scan0.bin scan1.bin ...: the same initial guess for every scan; the scans once as a batch
 // (scan2MapOptimizationBatch), once as a stream through two slots (prepareNextScan / launchSlot / collectSlot), once one by one
 // (scan2MapOptimization): prints "batch|stream|single <i> iters <n> pose ..." - the three must agree bit for bit.
@@ -114,6 +149,7 @@ int main(int argc, char** argv)
         if (argc == 2 && std::string(argv[1]) == "--version") { std::puts(s2m_version()); return 0; }
         if (argc == 13 && std::string(argv[1]) == "--chain") return run_chain(argv);
         if (argc >= 10 && std::string(argv[1]) == "--many") return run_many(argc, argv);
+        if (argc == 7 && std::string(argv[1]) == "--keyframes") return run_keyframes(argv);
         if (argc != 9 && argc != 16) {
             std::fprintf(stderr, "usage: %s map.bin scan.bin roll pitch yaw x y z [imuType imuRPYWeight z_tol rot_tol imuAvailable imuRoll imuPitch]\n", argv[0]);
             return 2;

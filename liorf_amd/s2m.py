@@ -35,7 +35,9 @@ ABI_SYMBOLS = [
     "s2m_transform_cloud",
     "s2m_icp_default_params", "s2m_icp_align", "s2m_debug_device_trig",
     "s2m_sc_reset", "s2m_sc_size", "s2m_sc_add_scan", "s2m_sc_add_descriptor", "s2m_sc_detect_loop", "s2m_sc_distance",
+    "s2m_kf_default_params", "s2m_kf_reset", "s2m_kf_size", "s2m_kf_add", "s2m_kf_set_poses", "s2m_extract_surrounding",
 ]
+S2M_KF_FROM_HOST, S2M_KF_FROM_DEVICE, S2M_KF_FROM_LAST_DOWNSAMPLE = 0, 1, 2
 S2M_WARN_LEAF_TOO_SMALL = 1
 
 
@@ -76,6 +78,10 @@ class IcpParams(C.Structure):
 
 class IcpResult(C.Structure):
     _fields_ = [("T", C.c_float * 16), ("converged", C.c_int32), ("iterations", C.c_int32), ("fitness_score", C.c_double)]
+
+
+class KfParams(C.Structure):
+    _fields_ = [("search_radius", C.c_float), ("density", C.c_float), ("map_leaf", C.c_float), ("recent_window_s", C.c_double)]
 
 
 class S2MError(RuntimeError):
@@ -167,6 +173,13 @@ def load_library(path: str | None = None) -> C.CDLL:
     L.s2m_sc_add_descriptor.argtypes = [vp, dp]
     L.s2m_sc_detect_loop.argtypes = [vp, i32p, fp, C.POINTER(ScMatch)]
     L.s2m_sc_distance.argtypes = [vp, C.c_int32, i32p, C.c_int32, dp, i32p]
+    L.s2m_kf_default_params.argtypes = [C.POINTER(KfParams)]
+    L.s2m_kf_reset.argtypes = [vp]
+    L.s2m_kf_size.argtypes = [vp]
+    L.s2m_kf_add.argtypes = [vp, fp, C.c_double, vp, C.c_size_t, C.c_size_t, C.c_int]
+    L.s2m_kf_set_poses.argtypes = [vp, C.c_int, C.c_int, fp]
+    L.s2m_extract_surrounding.argtypes = [vp, C.c_double, C.POINTER(KfParams), vp, C.c_size_t, C.c_size_t, szp, i32p,
+                                          C.c_size_t, szp]
     if path is None:
         _LIB = L
     return L
@@ -603,3 +616,61 @@ class MapOptimizationS2M:
                                                   desc.ctypes.data_as(C.POINTER(C.c_double)),
                                                   key.ctypes.data_as(C.POINTER(C.c_double))), "s2m_make_scancontext")
         return desc, key
+
+    # -- the resident key-frame store and extractSurroundingKeyFrames() (reference :1046-1059) --------
+    def kfReset(self):
+        self._check(self.lib.s2m_kf_reset(self.h), "s2m_kf_reset")
+
+    def kfSize(self) -> int:
+        return self.lib.s2m_kf_size(self.h)
+
+    def saveKeyFrame(self, pose_xyzrpy, time: float, cloud=None, device_ptr=None):
+        """saveKeyFramesAndFactor() (reference :1549-1580): append a key frame with pose {x, y, z, roll, pitch, yaw}.
+        cloud=None stores laserCloudSurfLastDS as the last downsampleCurrentScan left it (no copy through the host);
+        `device_ptr=(ptr, n, stride_bytes)` copies records that live in HBM."""
+        p = np.ascontiguousarray(pose_xyzrpy, np.float32).reshape(6)
+        if device_ptr is not None:
+            ptr, n, st = device_ptr
+            rc = self.lib.s2m_kf_add(self.h, _fp(p), float(time), C.c_void_p(ptr), n, st, S2M_KF_FROM_DEVICE)
+        elif cloud is None:
+            rc = self.lib.s2m_kf_add(self.h, _fp(p), float(time), None, 0, 32, S2M_KF_FROM_LAST_DOWNSAMPLE)
+        else:
+            a, n, st = _records(cloud)
+            rc = self.lib.s2m_kf_add(self.h, _fp(p), float(time), a.ctypes.data, n, st, S2M_KF_FROM_HOST)
+        self._check(rc, "s2m_kf_add")
+
+    def correctPoses(self, poses_xyzrpy, first: int = 0):
+        """correctPoses() (reference :1611-1640): new poses for key frames first .. first + len(poses) - 1."""
+        p = np.ascontiguousarray(poses_xyzrpy, np.float32).reshape(-1, 6)
+        self._check(self.lib.s2m_kf_set_poses(self.h, first, p.shape[0], _fp(p)), "s2m_kf_set_poses")
+
+    def extractSurroundingKeyFrames(self, timeLaserInfoCur: float, params: KfParams | None = None, readback: bool = True,
+                                    return_map: bool = False):
+        """Reference :1046-1059 on the resident store, fused with setInputCloud: returns the key id of every frame
+        concatenated into the local map (or None if !readback); with return_map also laserCloudSurfFromMapDS."""
+        n = max(self.kfSize(), 0)
+        keys = np.zeros(2 * n + 1, np.int32)
+        m, nk = C.c_size_t(0), C.c_size_t(0)
+        pp = C.byref(params) if params is not None else None
+
+        def run(out, cap):
+            return self._check_voxel(
+                self.lib.s2m_extract_surrounding(self.h, float(timeLaserInfoCur), pp, out, 32, cap, C.byref(m),
+                                                 keys.ctypes.data_as(C.POINTER(C.c_int32)) if readback else None,
+                                                 keys.size if readback else 0, C.byref(nk)), "s2m_extract_surrounding")
+        self.leaf_too_small = run(None, 0)
+        self.laserCloudSurfFromMapDSNum = m.value
+        k = keys[:nk.value].copy() if readback else None
+        if not return_map:
+            return k
+        out = np.zeros((max(m.value, 1), 8), np.float32)
+        run(out.ctypes.data, m.value)                 # (the same selection again: deterministic, same map)
+        return k, out[:m.value]
+
+
+def default_kf_params(**kw) -> KfParams:
+    p = KfParams()
+    load_library().s2m_kf_default_params(C.byref(p))
+    for k, v in kw.items():
+        setattr(p, k, v)
+    return p
