@@ -349,6 +349,74 @@ int  s2m_icp_default_params(s2m_icp_params* p);
 int  s2m_icp_align(s2m_handle h, const void* src, size_t n_src, const void* tgt, size_t n_tgt, size_t stride_bytes,
                    const s2m_icp_params* p /* NULL = defaults */, s2m_icp_result* out);
 
+/* ---- Loop closure against the key-frame store (SURVEY.md section 8(f), row F4 with its inputs) -------------------
+ * performRSLoopClosure() (reference src/mapOptmization.cpp:542-622) and the extraction / ICP / gate half of
+ * performSCLoopClosure() (:624-730) run against the resident key-frame store above, so that the loop thread keeps no
+ * host key-frame clouds and no kd-tree over the key poses. N is the store size; P[i], t[i], pose[i] the position, time
+ * and {x, y, z, roll, pitch, yaw} of key i as s2m_kf_add / s2m_kf_set_poses left them.
+ *   Detection, detectLoopClosureDistance() (:732-765): the candidates are keys with d2(P[i], P[N-1]) < (float)(R*R),
+ *       d2 and order as (b) of s2m_extract_surrounding (ascending d2, equal distances: lower index). key_pre is the
+ *       first candidate with fabs(t[i] - time_cur) > (double)time_diff_s; time_cur is timeLaserInfoCur, the current
+ *       scan's time, not t[N-1]. No such key, or key_pre == N-1: S2M_LOOP_NONE.
+ *       [ext] `abs` of a double at :755 is std::abs(double) (libstdc++ with <cmath>), not the int overload.
+ *   Loop-index container (loopIndexContainer, :146): the handle keeps key_cur -> key_pre of every accepted closure. A
+ *       key_cur already in it gives S2M_LOOP_ALREADY_CLOSED before any extraction (:737-739, :641-643). s2m_kf_reset
+ *       clears it.
+ *   Submaps, loopFindNearKeyframes(key, search_num, loop_index) (:821-844): for i = -search_num .. search_num the cloud
+ *       of key + i (skipped outside [0, N)), transformed by pose[loop_index != -1 ? loop_index : key + i], concatenated
+ *       in i order and filtered with leaf icp_leaf (downSizeFilterICP). An empty concatenation stays empty.
+ *       cur = (key_cur, 0, base_key), prev = (key_pre, search_num, base_key).
+ *   Gates and ICP (:565-586): n_cur < 300 or n_prev < 1000 gives S2M_LOOP_TOO_FEW_POINTS. Otherwise s2m_icp_align's
+ *       ICP (source cur, target prev, max correspondence distance (double)(search_radius * 2.0f), 100 iterations,
+ *       1e-6 / 1e-6) on the device submaps; !converged or fitness_score > (double)fitness_score gives
+ *       S2M_LOOP_REJECTED, anything else S2M_LOOP_ACCEPTED, recorded in the container.
+ *   Pose result (accepted closures): with C = icp.T,
+ *       base_key == -1 (RS): pose_from = getTranslationAndEulerAngles(C * getTransformation(pose[key_cur])) (:597-604),
+ *                            pose_to = pose[key_pre] (:606);
+ *       base_key >= 0  (SC): pose_from = getTranslationAndEulerAngles(C) (:707), pose_to = zeros (:709).
+ *       [ext] pcl::getTranslationAndEulerAngles (PCL 1.10 common/impl/eigen.hpp) in float: x, y, z = T(0..2, 3),
+ *       roll = atan2(T21, T22), pitch = asin(-T20), yaw = atan2(T10, T00); the Affine3f product in float, each entry
+ *       ((a0 b0 + a1 b1) + a2 b2). GTSAM stays with the caller: poseFrom.between(poseTo) and the noise model
+ *       (fitness_score for RS, the robust Cauchy model for SC) are formed from pose_from, pose_to and icp.
+ * None of these calls touches the installed local map and its index, the scan (scan_ds included, which
+ * S2M_KF_FROM_LAST_DOWNSAMPLE reads), the pose, the batch and stream slots, or the key store: the next registration is
+ * bit for bit the one without the loop call. Calls on a handle are not concurrent: the node's loop thread takes the same
+ * lock as the scan handler around them. The handle is held for the whole call, ICP included.
+ * Errors: a null handle, params outside their range or keys outside [0, N) give S2M_ERR_INVALID_ARG; an empty store gives
+ * S2M_OK with S2M_LOOP_NONE (or no records); a short output buffer gives S2M_ERR_CAPACITY after writing cap records. */
+typedef struct s2m_loop_params {
+    float   search_radius;   /* historyKeyframeSearchRadius   10.0  include/utility.h:245 (configs: 15.0) */
+    float   time_diff_s;     /* historyKeyframeSearchTimeDiff 30.0  include/utility.h:246 */
+    int32_t search_num;      /* historyKeyframeSearchNum      25    include/utility.h:247 */
+    float   fitness_score;   /* historyKeyframeFitnessScore   0.3   include/utility.h:248 */
+    float   icp_leaf;        /* loopClosureICPSurfLeafSize    0.3   include/utility.h:239 (configs: 0.5), downSizeFilterICP :196 */
+} s2m_loop_params;
+#define S2M_LOOP_NONE            0  /* no candidate, or the candidate is the current key (:761) */
+#define S2M_LOOP_ALREADY_CLOSED  1  /* the container already holds key_cur (:737-739, :641-643) */
+#define S2M_LOOP_TOO_FEW_POINTS  2  /* cureKeyframeCloud < 300 or prevKeyframeCloud < 1000 points (:565-566) */
+#define S2M_LOOP_REJECTED        3  /* !hasConverged() or getFitnessScore() > fitness_score (:585) */
+#define S2M_LOOP_ACCEPTED        4
+typedef struct s2m_loop_result {
+    int32_t status;                 /* S2M_LOOP_* */
+    int32_t key_cur, key_pre;       /* both -1 with S2M_LOOP_NONE; key_pre -1 when RS finds key_cur already closed */
+    int32_t n_cur, n_prev;          /* sizes of the two filtered submaps (0 when not built) */
+    s2m_icp_result icp;             /* valid when ICP ran (S2M_LOOP_REJECTED, S2M_LOOP_ACCEPTED) */
+    float pose_from[6];             /* x y z roll pitch yaw, accepted closures: see above */
+    float pose_to[6];
+} s2m_loop_result;
+int  s2m_loop_default_params(s2m_loop_params* p);
+/* loopFindNearKeyframes(key, search_num, loop_index) (:821-844) with leaf `leaf`, to host records (pubHistoryKeyFrames,
+ * MULTI_SCAN_FEAT). loop_index is -1 or a key. *n_out holds the full count; S2M_WARN_LEAF_TOO_SMALL as the voxel calls. */
+int  s2m_loop_near_keyframes(s2m_handle h, int32_t key, int32_t search_num, int32_t loop_index, float leaf,
+                             void* out, size_t out_stride_bytes, size_t cap, size_t* n_out);
+/* Extraction, gates, ICP and pose result for a given pair (the container test first). base_key = -1 is the RS / external
+ * form; base_key >= 0 is the SC form (performSCLoopClosure passes 0). */
+int  s2m_loop_align(s2m_handle h, int32_t key_cur, int32_t key_pre, int32_t base_key,
+                    const s2m_loop_params* p /* NULL = defaults */, s2m_loop_result* out);
+/* performRSLoopClosure() without the external detection: the container test for key N-1, the device detection at
+ * timeLaserInfoCur = time_cur, then s2m_loop_align(N-1, key_pre, -1, p). */
+int  s2m_loop_closure_rs(s2m_handle h, double time_cur, const s2m_loop_params* p /* NULL = defaults */, s2m_loop_result* out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -63,7 +63,7 @@ struct s2m_context {
     // key-frame store (cloudKeyPoses3D / cloudKeyPoses6D / surfCloudKeyFrames, :93-100): every key's 32-byte records in an arena of
     // blocks that are never moved (the frame table holds raw pointers into them), and per key its position and KfFrame (transform,
     // records, count) on the device; poses, times and frames mirrored on the host
-    DevBuf kf_pos, kf_frames;
+    DevBuf kf_pos, kf_frames, kf_tdev;  // kf_tdev: every key's time (double), read by the loop detection
     std::vector<void*> kf_blocks;
     size_t kf_block_used = 0, kf_block_cap = 0, kf_cap = 0;
     std::vector<float> kf_pose;        // 6 per key: x, y, z, roll, pitch, yaw
@@ -71,6 +71,9 @@ struct s2m_context {
     std::vector<KfFrame> kf_frame;
     size_t scan_ds_n = 0;              // records s2m_downsample_scan left in scan_ds
     bool have_scan_ds = false;
+    // loop closure against the store: loopIndexContainer (:146), the transformed frames and the two filtered submaps
+    std::map<int32_t, int32_t> loop_index;
+    DevBuf loop_xf, loop_cur, loop_prev;
 
     DevCtx hctx{};
     bool ctx_dirty = true;
@@ -909,7 +912,8 @@ int s2m_destroy(s2m_handle h)
                        &h->q_rank_of, &h->block_sums, &h->partials, &h->state, &h->dctx, &h->mm,
                        &h->dbg_idx5, &h->dbg_d2, &h->dbg_flag, &h->dbg_coeff, &h->dbg_clk, &h->sc_bins, &h->sc_out,
                        &h->vox_in, &h->vox_out, &h->frames_xf, &h->scan_ds, &h->map_ds,
-                       &h->sc_store_desc, &h->sc_store_ring, &h->sc_store_sector, &h->sc_cand, &h->sc_res };
+                       &h->sc_store_desc, &h->sc_store_ring, &h->sc_store_sector, &h->sc_cand, &h->sc_res,
+                       &h->loop_xf, &h->loop_cur, &h->loop_prev };
     for (DevBuf* b : bufs) if (b->p) (void)hipFree(b->p);
     vox_destroy(h->vox);
     icp_destroy(h->icp);
@@ -918,6 +922,7 @@ int s2m_destroy(s2m_handle h)
     for (void* b : h->kf_blocks) (void)hipFree(b);
     if (h->kf_pos.p) (void)hipFree(h->kf_pos.p);
     if (h->kf_frames.p) (void)hipFree(h->kf_frames.p);
+    if (h->kf_tdev.p) (void)hipFree(h->kf_tdev.p);
     if (h->h_state) (void)hipHostFree(h->h_state);
     if (h->h_mm) (void)hipHostFree(h->h_mm);
     if (h->h_sc) (void)hipHostFree(h->h_sc);
@@ -1853,6 +1858,7 @@ int s2m_kf_reset(s2m_handle h)
     h->kf_blocks.clear();
     h->kf_block_used = h->kf_block_cap = 0;
     h->kf_pose.clear(); h->kf_time.clear(); h->kf_frame.clear();
+    h->loop_index.clear();
     if (e != hipSuccess) return fail(h, S2M_ERR_HIP, "hipFree of a key-frame block", e);
     return S2M_OK;
 }
@@ -1883,21 +1889,23 @@ int kf_reserve(s2m_context* h, size_t want)
     size_t cap = h->kf_cap ? h->kf_cap : 256;
     while (cap < want) cap *= 2;
     const size_t n = h->kf_time.size();
-    struct Part { DevBuf* b; size_t elem; } parts[2] = { { &h->kf_pos, sizeof(float4) }, { &h->kf_frames, sizeof(KfFrame) } };
-    void* np[2] = { nullptr, nullptr };
-    for (int k = 0; k < 2; k++) {
+    constexpr int kParts = 3;
+    struct Part { DevBuf* b; size_t elem; } parts[kParts] = { { &h->kf_pos, sizeof(float4) }, { &h->kf_frames, sizeof(KfFrame) },
+                                                              { &h->kf_tdev, sizeof(double) } };
+    void* np[kParts] = { nullptr, nullptr, nullptr };
+    for (int k = 0; k < kParts; k++) {
         hipError_t e = hipMalloc(&np[k], parts[k].elem * cap);
-        if (e != hipSuccess) { if (np[0]) (void)hipFree(np[0]); return fail(h, S2M_ERR_HIP, "key-frame store", e); }
+        if (e != hipSuccess) { for (int j = 0; j < k; j++) (void)hipFree(np[j]); return fail(h, S2M_ERR_HIP, "key-frame store", e); }
     }
     hipError_t e = hipSuccess;
-    for (int k = 0; k < 2 && e == hipSuccess; k++)
+    for (int k = 0; k < kParts && e == hipSuccess; k++)
         if (n) e = hipMemcpyAsync(np[k], parts[k].b->p, parts[k].elem * n, hipMemcpyDeviceToDevice, h->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
     if (e != hipSuccess) {                                 // the old arrays stay in place; the new ones go
-        (void)hipFree(np[0]); (void)hipFree(np[1]);
+        for (int k = 0; k < kParts; k++) (void)hipFree(np[k]);
         return fail(h, S2M_ERR_HIP, "key-frame store copy", e);
     }
-    for (int k = 0; k < 2; k++) {                          // (the copies are complete: the new arrays are installed in any case)
+    for (int k = 0; k < kParts; k++) {                          // (the copies are complete: the new arrays are installed in any case)
         if (parts[k].b->p) (void)hipFree(parts[k].b->p);
         parts[k].b->p = np[k]; parts[k].b->cap = parts[k].elem * cap;
     }
@@ -1958,6 +1966,7 @@ int s2m_kf_add(s2m_handle h, const float pose_xyzrpy[6], double time, const void
     const float4 p = make_float4(pose_xyzrpy[0], pose_xyzrpy[1], pose_xyzrpy[2], 0.0f);
     S2M_HIP(h, hipMemcpyAsync(h->kf_pos.as<float4>() + N, &p, sizeof(p), hipMemcpyHostToDevice, h->stream));
     S2M_HIP(h, hipMemcpyAsync(h->kf_frames.as<KfFrame>() + N, &f, sizeof(f), hipMemcpyHostToDevice, h->stream));
+    S2M_HIP(h, hipMemcpyAsync(h->kf_tdev.as<double>() + N, &time, sizeof(time), hipMemcpyHostToDevice, h->stream));
     S2M_HIP(h, hipStreamSynchronize(h->stream));          // the caller's cloud and the staged entries are free again
     // committed only now: a failure above leaves the store as it was
     h->kf_block_used += kDsStride * n;
@@ -2080,6 +2089,171 @@ int s2m_icp_align(s2m_handle h, const void* src, size_t n_src, const void* tgt, 
     memcpy(out->T, r.T, sizeof(r.T));
     out->converged = r.converged; out->iterations = r.iterations; out->fitness_score = r.fitness;
     return S2M_OK;
+}
+
+// ---- loop closure against the key-frame store (:542-844) --------------------------------------------------
+
+int s2m_loop_default_params(s2m_loop_params* p)
+{
+    if (!p) return S2M_ERR_INVALID_ARG;
+    p->search_radius = 10.0f;       // historyKeyframeSearchRadius    include/utility.h:245
+    p->time_diff_s = 30.0f;         // historyKeyframeSearchTimeDiff  include/utility.h:246
+    p->search_num = 25;             // historyKeyframeSearchNum       include/utility.h:247
+    p->fitness_score = 0.3f;        // historyKeyframeFitnessScore    include/utility.h:248
+    p->icp_leaf = 0.3f;             // loopClosureICPSurfLeafSize     include/utility.h:239
+    return S2M_OK;
+}
+
+namespace {
+
+int loop_params(s2m_context* h, const s2m_loop_params* p, s2m_loop_params* prm)
+{
+    if (p) *prm = *p; else s2m_loop_default_params(prm);
+    if (!(prm->search_radius > 0.0f) || !std::isfinite(prm->search_radius) || !std::isfinite(prm->time_diff_s) ||
+        prm->search_num < 0 || std::isnan(prm->fitness_score))
+        return fail(h, S2M_ERR_INVALID_ARG, "loop search radius must be positive, time window finite, search_num >= 0");
+    return check_leaf(h, prm->icp_leaf);
+}
+
+void loop_result_init(s2m_loop_result* o)
+{
+    memset(o, 0, sizeof(*o));
+    o->status = S2M_LOOP_NONE;
+    o->key_cur = o->key_pre = -1;
+}
+
+// loopFindNearKeyframes(key, search_num, loop_index) (:821-844) into `dst`: the frame table from the host mirror of the store, then
+// the transform and the VoxelGrid of s2m_extract_cloud. An empty concatenation is not filtered (res->n_out = 0).
+int loop_submap(s2m_context* h, int32_t key, int32_t search_num, int32_t loop_index, float leaf, DevBuf& dst, VoxResult* res)
+{
+    *res = VoxResult{};
+    const long long N = (long long)h->kf_time.size();
+    const long long lo = std::max(0LL, (long long)key - search_num), hi = std::min(N - 1, (long long)key + search_num);
+    std::vector<const unsigned char*> src;
+    std::vector<int32_t> offsets(1, 0);
+    std::vector<float> T;
+    size_t total = 0;
+    for (long long k = lo; k <= hi; k++) {                  // i = -search_num .. search_num, keyNear outside [0, N) skipped
+        const KfFrame& f = h->kf_frame[(size_t)k];
+        const KfFrame& tf = h->kf_frame[(size_t)(loop_index != -1 ? (long long)loop_index : k)];
+        total += (size_t)f.n;
+        if (total > (size_t)0x3fffffff) return fail(h, S2M_ERR_CAPACITY, "too many points in the loop submap");
+        src.push_back(f.src);
+        offsets.push_back((int32_t)total);
+        T.insert(T.end(), tf.T, tf.T + 12);
+    }
+    if (total == 0) return S2M_OK;                          // nearKeyframes->empty(): returned unfiltered (:837-838)
+    int rc = ensure(h, h->loop_xf, kDsStride * total);
+    if (rc) return rc;
+    hipError_t e = vox_transform_frames(h->vox, h->stream, src.data(), kDsStride, offsets.data(), T.data(), (int)src.size(),
+                                        h->loop_xf.as<unsigned char>(), kDsStride);
+    if (e != hipSuccess) return fail(h, S2M_ERR_HIP, "loop submap transform", e);
+    return voxel_into(h, h->loop_xf.as<unsigned char>(), total, kDsStride, leaf, dst, res);   // (waits for the counts)
+}
+
+// the container test, both submaps, the size gate, ICP, the fitness gate and the pose result (:565-621, :641-715)
+int loop_align_impl(s2m_context* h, int32_t key_cur, int32_t key_pre, int32_t base_key, const s2m_loop_params& prm, s2m_loop_result* out)
+{
+    out->key_cur = key_cur;
+    out->key_pre = key_pre;
+    if (h->loop_index.count(key_cur)) { out->status = S2M_LOOP_ALREADY_CLOSED; return S2M_OK; }
+    VoxResult rc_cur, rc_prev;
+    int rc = loop_submap(h, key_cur, 0, base_key, prm.icp_leaf, h->loop_cur, &rc_cur);
+    if (rc) return rc;
+    if ((rc = loop_submap(h, key_pre, prm.search_num, base_key, prm.icp_leaf, h->loop_prev, &rc_prev))) return rc;
+    out->n_cur = (int32_t)rc_cur.n_out;
+    out->n_prev = (int32_t)rc_prev.n_out;
+    if (rc_cur.n_out < 300 || rc_prev.n_out < 1000) { out->status = S2M_LOOP_TOO_FEW_POINTS; return S2M_OK; }
+    // s2m_icp_align's path on the device submaps: historyKeyframeSearchRadius*2 (a float), 100, 1e-6, 1e-6 (:572-576)
+    const IcpParams ip{ (double)(prm.search_radius * 2.0f), 100, 1e-6, 1e-6 };
+    IcpResult r;
+    hipError_t e = icp_align(h->icp, h->stream, h->loop_cur.as<unsigned char>(), rc_cur.n_out, h->loop_prev.as<unsigned char>(),
+                             rc_prev.n_out, kDsStride, ip, &r);
+    if (e != hipSuccess) return fail(h, S2M_ERR_HIP, "loop ICP alignment", e);
+    S2M_HIP(h, hipStreamSynchronize(h->stream));
+    memcpy(out->icp.T, r.T, sizeof(r.T));
+    out->icp.converged = r.converged; out->icp.iterations = r.iterations; out->icp.fitness_score = r.fitness;
+    if (!r.converged || r.fitness > (double)prm.fitness_score) { out->status = S2M_LOOP_REJECTED; return S2M_OK; }   // (:585)
+    if (base_key == -1) {
+        float t_correct[12];                                // correctionLidarFrame * tWrong (:597-601)
+        host_affine_mul(r.T, h->kf_frame[(size_t)key_cur].T, t_correct);
+        host_translation_and_euler(t_correct, 4, out->pose_from);
+        memcpy(out->pose_to, &h->kf_pose[6 * (size_t)key_pre], sizeof(out->pose_to));
+    } else {
+        host_translation_and_euler(r.T, 4, out->pose_from);  // (:707); poseTo is the identity (:709)
+    }
+    out->status = S2M_LOOP_ACCEPTED;
+    h->loop_index[key_cur] = key_pre;                       // loopIndexContainer[loopKeyCur] = loopKeyPre (:621)
+    return S2M_OK;
+}
+
+bool loop_key_ok(int32_t k, size_t N) { return k >= 0 && (size_t)k < N; }
+
+}  // namespace
+
+int s2m_loop_near_keyframes(s2m_handle h, int32_t key, int32_t search_num, int32_t loop_index, float leaf,
+                            void* out, size_t out_stride_bytes, size_t cap, size_t* n_out)
+{
+    if (!h) return S2M_ERR_INVALID_ARG;
+    if (!n_out || (cap > 0 && (!out || out_stride_bytes < 12 || (out_stride_bytes & 3))))
+        return fail(h, S2M_ERR_INVALID_ARG, "bad output buffer");
+    *n_out = 0;
+    int rc = check_leaf(h, leaf);
+    if (rc) return rc;
+    if (search_num < 0) return fail(h, S2M_ERR_INVALID_ARG, "search_num must be >= 0");
+    const size_t N = h->kf_time.size();
+    if (N == 0) return S2M_OK;
+    if (!loop_key_ok(key, N) || (loop_index != -1 && !loop_key_ok(loop_index, N)))
+        return fail(h, S2M_ERR_INVALID_ARG, "key or loop_index outside the key-frame store");
+    S2M_HIP(h, hipSetDevice(h->device));
+    VoxResult res;
+    if ((rc = loop_submap(h, key, search_num, loop_index, leaf, h->loop_prev, &res))) return rc;
+    *n_out = res.n_out;
+    if ((rc = download_records(h, h->loop_prev, res.n_out, out, out_stride_bytes, cap))) return rc;
+    if (res.n_out > cap) return fail(h, S2M_ERR_CAPACITY, "output buffer too small for the loop submap");
+    return res.leaf_too_small ? S2M_WARN_LEAF_TOO_SMALL : S2M_OK;
+}
+
+int s2m_loop_align(s2m_handle h, int32_t key_cur, int32_t key_pre, int32_t base_key, const s2m_loop_params* p, s2m_loop_result* out)
+{
+    if (!h) return S2M_ERR_INVALID_ARG;
+    if (!out) return fail(h, S2M_ERR_INVALID_ARG, "null loop result");
+    loop_result_init(out);
+    s2m_loop_params prm;
+    int rc = loop_params(h, p, &prm);
+    if (rc) return rc;
+    const size_t N = h->kf_time.size();
+    if (N == 0) return S2M_OK;                             // cloudKeyPoses3D->points.empty() (:544-545, :627-628)
+    if (!loop_key_ok(key_cur, N) || !loop_key_ok(key_pre, N) || (base_key != -1 && !loop_key_ok(base_key, N)))
+        return fail(h, S2M_ERR_INVALID_ARG, "loop keys outside the key-frame store");
+    S2M_HIP(h, hipSetDevice(h->device));
+    return loop_align_impl(h, key_cur, key_pre, base_key, prm, out);
+}
+
+int s2m_loop_closure_rs(s2m_handle h, double time_cur, const s2m_loop_params* p, s2m_loop_result* out)
+{
+    if (!h) return S2M_ERR_INVALID_ARG;
+    if (!out) return fail(h, S2M_ERR_INVALID_ARG, "null loop result");
+    loop_result_init(out);
+    s2m_loop_params prm;
+    int rc = loop_params(h, p, &prm);
+    if (rc) return rc;
+    if (!std::isfinite(time_cur)) return fail(h, S2M_ERR_INVALID_ARG, "time_cur must be finite");
+    const size_t N = h->kf_time.size();
+    if (N == 0) return S2M_OK;                             // (:544-545)
+    const int32_t key_cur = (int32_t)N - 1;
+    if (h->loop_index.count(key_cur)) {                    // (:737-739)
+        out->key_cur = key_cur;
+        out->status = S2M_LOOP_ALREADY_CLOSED;
+        return S2M_OK;
+    }
+    S2M_HIP(h, hipSetDevice(h->device));
+    int key_pre = -1;
+    hipError_t e = loop_detect(h->vox, h->stream, h->kf_pos.as<float4>(), h->kf_tdev.as<double>(), (int)N, prm.search_radius,
+                               time_cur, (double)prm.time_diff_s, &key_pre);
+    if (e != hipSuccess) return fail(h, S2M_ERR_HIP, "loop detection", e);
+    if (key_pre == -1 || key_pre == key_cur) return S2M_OK;                 // (:761-762)
+    return loop_align_impl(h, key_cur, key_pre, -1, prm, out);
 }
 
 int s2m_make_scancontext(s2m_handle h, const void* pts, size_t n, size_t stride_bytes,

@@ -1,6 +1,6 @@
 // s2m_host_math.hpp — host-side scalar pieces of the path (per scan, not per point):
 // trans2Affine3f / pcl::getTransformation (reference src/mapOptmization.cpp:348-351),
-// the LMOptimization trig (:1170-1175) and transformUpdate() (:1323-1363).
+// the LMOptimization trig (:1170-1175), transformUpdate() (:1323-1363) and the loop-closure pose result (:597-604, :707).
 #pragma once
 #include <cmath>
 #include <utility>
@@ -92,6 +92,28 @@ inline void host_transform_update(const s2m_params& p, const s2m_imu_init* imu, 
     t[1] = constraint_transformation(t[1], p.rot_tol);
     t[5] = constraint_transformation(t[5], p.z_tol);
     host_pose_to_transform(t, affine, nullptr);
+}
+
+// Eigen::Affine3f * Affine3f (Eigen's transform_transform_product_impl: linear = A.linear * B.linear, translation =
+// A.linear * B.translation + A.translation), fp32, each entry ((a0 b0 + a1 b1) + a2 b2) [ext]. A: row-major 4x4 (an ICP
+// result), B, out: row-major 3x4.
+inline void host_affine_mul(const float A[16], const float B[12], float out[12])
+{
+    for (int i = 0; i < 3; i++) {
+        for (int j = 0; j < 3; j++)
+            out[i * 4 + j] = (A[i * 4 + 0] * B[0 * 4 + j] + A[i * 4 + 1] * B[1 * 4 + j]) + A[i * 4 + 2] * B[2 * 4 + j];
+        out[i * 4 + 3] = ((A[i * 4 + 0] * B[3] + A[i * 4 + 1] * B[7]) + A[i * 4 + 2] * B[11]) + A[i * 4 + 3];
+    }
+}
+
+// pcl::getTranslationAndEulerAngles (PCL 1.10 common/impl/eigen.hpp) [ext], in float: T row-major with row stride `ld`
+// (4 for a 3x4 or a 4x4); out = {x, y, z, roll, pitch, yaw}.
+inline void host_translation_and_euler(const float* T, int ld, float out[6])
+{
+    out[0] = T[0 * ld + 3]; out[1] = T[1 * ld + 3]; out[2] = T[2 * ld + 3];
+    out[3] = std::atan2(T[2 * ld + 1], T[2 * ld + 2]);
+    out[4] = std::asin(-T[2 * ld + 0]);
+    out[5] = std::atan2(T[1 * ld + 0], T[0 * ld + 0]);
 }
 
 // Eigen::umeyama without scaling, as pcl::registration::TransformationEstimationSVD uses it (reference

@@ -13,6 +13,7 @@
 // are compacted in two kernels (k_heads_*). Compiled with -ffp-contract=off like the rest.
 #include "s2m_voxel.hpp"
 
+#include <algorithm>
 #include <cmath>
 #include <cstring>
 #include <new>
@@ -964,6 +965,60 @@ __global__ __launch_bounds__(kKfThreads) void k_kf_select_frames(const float4* _
     }
 }
 
+// ------------------------------------------------------------------------------------------
+// detectLoopClosureDistance() (:732-765) on the resident key-frame store: every key's radius test against the newest key and
+// time test against time_cur, and the minimum of (d2 bits, key) over the keys that pass - FLANN's first candidate in
+// (ascending d2, lower index) order that passes the time test. d2 >= 0, so its bits order like its value; the minimum is exact
+// and does not depend on which lane or workgroup saw a key first.
+//   k_loop_detect        grid-stride over all n keys, one partial minimum per workgroup
+//   k_loop_detect_final  one workgroup folds the partials and writes the result to pinned host memory
+// ------------------------------------------------------------------------------------------
+constexpr int kLoopThreads = 256;
+constexpr int kLoopMaxGroups = 1024;    // 4 workgroups per CU on the 256 CUs; more keys than 2^18 are walked grid-stride
+
+__device__ __forceinline__ unsigned long long loop_block_min(unsigned long long v, unsigned long long* s_w)
+{
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        const unsigned long long o = __shfl_down(v, off, 64);
+        v = o < v ? o : v;
+    }
+    if ((threadIdx.x & 63) == 0) s_w[threadIdx.x >> 6] = v;
+    __syncthreads();
+    v = s_w[0];
+    for (int w = 1; w < kLoopThreads / 64; w++) v = s_w[w] < v ? s_w[w] : v;
+    return v;
+}
+
+__global__ __launch_bounds__(kLoopThreads) void k_loop_detect(const float4* __restrict__ pos, const double* __restrict__ t, int n,
+                                                              float r2, double time_cur, double time_diff,
+                                                              unsigned long long* __restrict__ part)
+{
+    __shared__ unsigned long long s_w[kLoopThreads / 64];
+    const float4 q = pos[n - 1];
+    unsigned long long best = ~0ull;
+    for (int i = blockIdx.x * kLoopThreads + threadIdx.x; i < n; i += gridDim.x * kLoopThreads) {
+        const float d2 = kf_d2(pos[i], q);
+        // radiusSearch: d2 < (float)(R*R); then abs(time - timeLaserInfoCur) > historyKeyframeSearchTimeDiff, std::abs(double) (:755)
+        if (d2 < r2 && fabs(t[i] - time_cur) > time_diff) {
+            const unsigned long long v = ((unsigned long long)__float_as_uint(d2) << 32) | (uint32_t)i;
+            best = v < best ? v : best;
+        }
+    }
+    best = loop_block_min(best, s_w);
+    if (threadIdx.x == 0) part[blockIdx.x] = best;
+}
+
+__global__ __launch_bounds__(kLoopThreads) void k_loop_detect_final(const unsigned long long* __restrict__ part, int n_part,
+                                                                    unsigned long long* out)
+{
+    __shared__ unsigned long long s_w[kLoopThreads / 64];
+    unsigned long long best = ~0ull;
+    for (int g = threadIdx.x; g < n_part; g += kLoopThreads) best = part[g] < best ? part[g] : best;
+    best = loop_block_min(best, s_w);
+    if (threadIdx.x == 0) *out = best;
+}
+
 }  // namespace
 
 struct VoxWorkspace {
@@ -971,6 +1026,8 @@ struct VoxWorkspace {
     VoxSetup* h_setup = nullptr;          // pinned
     Buf kf_key, kf_ord, kf_cent, kf_nn, kf_st, kf_tab;   // key-frame selection: sort keys, ranks, centroids, their keys, counts, table
     KfSelect* h_kf = nullptr;             // pinned
+    Buf loop_part;                        // loop detection: one partial minimum per workgroup
+    unsigned long long* h_loop = nullptr; // pinned: its result
 };
 
 VoxWorkspace* vox_create()
@@ -979,7 +1036,8 @@ VoxWorkspace* vox_create()
     if (!w) return nullptr;
     if (w->setup.ensure(sizeof(VoxSetup)) != hipSuccess ||
         hipHostMalloc((void**)&w->h_setup, sizeof(VoxSetup)) != hipSuccess ||
-        hipHostMalloc((void**)&w->h_kf, sizeof(KfSelect)) != hipSuccess) { vox_destroy(w); return nullptr; }
+        hipHostMalloc((void**)&w->h_kf, sizeof(KfSelect)) != hipSuccess ||
+        hipHostMalloc((void**)&w->h_loop, sizeof(unsigned long long)) != hipSuccess) { vox_destroy(w); return nullptr; }
     return w;
 }
 
@@ -987,10 +1045,11 @@ void vox_destroy(VoxWorkspace* w)
 {
     if (!w) return;
     Buf* bufs[] = { &w->setup, &w->keys_a, &w->keys_b, &w->vals_a, &w->vals_b, &w->heads, &w->rs_hist, &w->rs_tot, &w->frame_tab, &w->long_list,
-                    &w->kf_key, &w->kf_ord, &w->kf_cent, &w->kf_nn, &w->kf_st, &w->kf_tab };
+                    &w->kf_key, &w->kf_ord, &w->kf_cent, &w->kf_nn, &w->kf_st, &w->kf_tab, &w->loop_part };
     for (Buf* b : bufs) if (b->p) (void)hipFree(b->p);
     if (w->h_setup) (void)hipHostFree(w->h_setup);
     if (w->h_kf) (void)hipHostFree(w->h_kf);
+    if (w->h_loop) (void)hipHostFree(w->h_loop);
     delete w;
 }
 
@@ -1139,6 +1198,24 @@ hipError_t kf_select(VoxWorkspace* w, hipStream_t stream, const float4* d_pos, c
     VOX_TRY(hipGetLastError());
     VOX_TRY(hipStreamSynchronize(stream));                   // the one wait: the counts size the transform launch
     *out = *w->h_kf;
+    return hipSuccess;
+}
+
+hipError_t loop_detect(VoxWorkspace* w, hipStream_t stream, const float4* d_pos, const double* d_time, int n, float radius,
+                       double time_cur, double time_diff, int* key_pre)
+{
+    *key_pre = -1;
+    if (n <= 0) return hipSuccess;
+    const int groups = (int)std::min<long long>(((long long)n + kLoopThreads - 1) / kLoopThreads, kLoopMaxGroups);
+    VOX_TRY(w->loop_part.ensure(sizeof(unsigned long long) * kLoopMaxGroups));
+    unsigned long long* part = w->loop_part.as<unsigned long long>();
+    hipLaunchKernelGGL(k_loop_detect, dim3((unsigned)groups), dim3(kLoopThreads), 0, stream, d_pos, d_time, n, radius * radius,
+                       time_cur, time_diff, part);
+    hipLaunchKernelGGL(k_loop_detect_final, dim3(1), dim3(kLoopThreads), 0, stream, (const unsigned long long*)part, groups, w->h_loop);
+    VOX_TRY(hipGetLastError());
+    VOX_TRY(hipStreamSynchronize(stream));                   // the one wait: the key decides which frames the submaps take
+    const unsigned long long b = *w->h_loop;
+    if (b != ~0ull) *key_pre = (int)(uint32_t)b;
     return hipSuccess;
 }
 

@@ -67,4 +67,10 @@ struct KfTable {                           // the frame table, device memory, va
 hipError_t kf_select(VoxWorkspace* w, hipStream_t stream, const float4* d_pos, const KfFrame* d_frames, int n, int n_recent,
                      float radius, float density, KfSelect* out, KfTable* tab);
 
+// ---- detectLoopClosureDistance() (:732-765) on the same store: pos[k] and time[k] of key k = 0 .. n-1. *key_pre = the key with the
+// least (d2, k) among those with d2(P[k], P[n-1]) < radius * radius (fp32, as kf_select) and |time[k] - time_cur| > time_diff
+// (double), or -1. Two launches over all keys and one wait on `stream` for the result.
+hipError_t loop_detect(VoxWorkspace* w, hipStream_t stream, const float4* d_pos, const double* d_time, int n, float radius,
+                       double time_cur, double time_diff, int* key_pre);
+
 }  // namespace s2m

@@ -44,6 +44,8 @@ struct CloudInfo {
     float initialGuessRoll = 0, initialGuessPitch = 0, initialGuessYaw = 0;
 };
 
+class SCManagerS2M;
+
 class MapOptimizationS2M {
 public:
     // reference members, same names -----------------------------------------------------------
@@ -294,9 +296,61 @@ public:
         return true;
     }
 
+    // Loop closure against the resident key-frame store (:542-844): no host key-frame clouds and no kdtreeHistoryKeyPoses.
+    // Every call runs under the lock the scan handler holds (one handle, calls not concurrent). GTSAM stays here: an
+    // accepted result gives loopIndexQueue / loopPoseQueue / loopNoiseQueue as poseFrom.between(poseTo) of pose_from and
+    // pose_to, with the noise from icp.fitness_score (RS) or the robust model (SC).
+    float historyKeyframeSearchTimeDiff = 30.0f;      // include/utility.h:246
+    int   historyKeyframeSearchNum = 25;              // include/utility.h:247
+    float loopClosureICPSurfLeafSize = 0.3f;          // include/utility.h:239 (the shipped yaml files set 0.5)
+    s2m_loop_result lastLoop{};                       // what the last loop call did
+    std::vector<std::pair<int, int>> loopIndexContainer;   // accepted (key_cur, key_pre), in order (visualizeLoopClosure)
+
+    s2m_loop_params loopParams() const
+    {
+        s2m_loop_params p;
+        s2m_loop_default_params(&p);
+        p.search_radius = historyKeyframeSearchRadius;
+        p.time_diff_s = historyKeyframeSearchTimeDiff;
+        p.search_num = historyKeyframeSearchNum;
+        p.fitness_score = historyKeyframeFitnessScore;
+        p.icp_leaf = loopClosureICPSurfLeafSize;
+        return p;
+    }
+
+    // void performRSLoopClosure() (:542-622) with detectLoopClosureDistance() (:732-765) at timeLaserInfoCur
+    bool performRSLoopClosure()
+    {
+        const s2m_loop_params p = loopParams();
+        check(s2m_loop_closure_rs(h_, timeLaserInfoCur, &p, &lastLoop), "s2m_loop_closure_rs");
+        return accepted();
+    }
+
+    // void performSCLoopClosure() (:624-730): the ScanContext detector on this handle, then the store's extraction and ICP
+    inline bool performSCLoopClosure(SCManagerS2M& scManager);
+
+    // loopFindNearKeyframes(nearKeyframes, key, searchNum, loop_index) (:821-844), filtered with downSizeFilterICP
+    void loopFindNearKeyframes(std::vector<PointXYZI>& nearKeyframes, int key, int searchNum, int loop_index)
+    {
+        size_t n = 0;
+        int rc = s2m_loop_near_keyframes(h_, key, searchNum, loop_index, loopClosureICPSurfLeafSize, nullptr, sizeof(PointXYZI), 0, &n);
+        if (rc != S2M_ERR_CAPACITY) checkVoxel(rc, "s2m_loop_near_keyframes");
+        nearKeyframes.resize(n);
+        if (n > 0)
+            checkVoxel(s2m_loop_near_keyframes(h_, key, searchNum, loop_index, loopClosureICPSurfLeafSize, nearKeyframes.data(),
+                                               sizeof(PointXYZI), n, &n), "s2m_loop_near_keyframes");
+    }
+
     s2m_handle handle() const { return h_; }
 
 private:
+    bool accepted()
+    {
+        if (lastLoop.status != S2M_LOOP_ACCEPTED) return false;
+        loopIndexContainer.emplace_back(lastLoop.key_cur, lastLoop.key_pre);
+        return true;
+    }
+
     void check(int rc, const char* what)
     {
         if (rc != S2M_OK) throw std::runtime_error(std::string(what) + ": " + s2m_last_error(h_));
@@ -334,5 +388,17 @@ private:
     }
     s2m_handle h_;
 };
+
+inline bool MapOptimizationS2M::performSCLoopClosure(SCManagerS2M& scManager)
+{
+    lastLoop = s2m_loop_result{};
+    lastLoop.key_cur = lastLoop.key_pre = -1;
+    if (cloudKeyPoses6D.empty()) return false;                       // (:626-627)
+    const int loopKeyPre = scManager.detectLoopClosureID().first;    // (:636-639)
+    if (loopKeyPre == -1) return false;
+    const s2m_loop_params p = loopParams();
+    check(s2m_loop_align(h_, (int)cloudKeyPoses6D.size() - 1, loopKeyPre, 0, &p, &lastLoop), "s2m_loop_align");
+    return accepted();
+}
 
 }  // namespace liorf_amd

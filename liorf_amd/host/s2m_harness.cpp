@@ -12,6 +12,9 @@
 //   s2m_harness --keyframes scans.bin scans.txt map_leaf scan_leaf density
 //       a scripted trajectory through extractSurroundingKeyFrames() -> downsampleCurrentScan() ->
 //       scan2MapOptimization() -> saveKeyFrame() on the resident key-frame store; prints every pose.
+//   s2m_harness --loop keys.bin keys.txt scan_leaf search_radius search_num icp_leaf fitness_score
+//       a scripted revisit through downsampleCurrentScan() -> saveKeyFrame() -> makeAndSaveScancontextAndKeys() ->
+//       performRSLoopClosure() -> performSCLoopClosure() on the resident key-frame store; prints every loop result.
 #include <cstdio>
 #include <cstdlib>
 #include <fstream>
@@ -102,6 +105,58 @@ static int run_keyframes(char** argv)
     return 0;
 }
 
+static void print_loop(const char* what, int i, const s2m_loop_result& r)
+{
+    std::printf("%s %d status %d keys %d %d n %d %d iters %d converged %d fitness %.17g pose_from", what, i, r.status, r.key_cur,
+                r.key_pre, r.n_cur, r.n_prev, r.icp.iterations, r.icp.converged, r.icp.fitness_score);
+    for (int k = 0; k < 6; k++) std::printf(" %.9g", r.pose_from[k]);
+    std::printf(" pose_to");
+    for (int k = 0; k < 6; k++) std::printf(" %.9g", r.pose_to[k]);
+    std::printf("\n");
+}
+
+// --loop keys.bin keys.txt scan_leaf search_radius search_num icp_leaf fitness_score: keys.txt holds one line
+// "n_points time x y z roll pitch yaw" per key frame, the raw clouds back to back in keys.bin. Every key runs
+// downsampleCurrentScan() -> saveKeyFrame() -> makeAndSaveScancontextAndKeys() at its pose, then performRSLoopClosure() at its
+// time and performSCLoopClosure(); prints "rs <i> ..." and "sc <i> ..." for every key, then "near <n>" for
+// loopFindNearKeyframes(last key, search_num, -1).
+static int run_loop(char** argv)
+{
+    liorf_amd::MapOptimizationS2M node;
+    liorf_amd::SCManagerS2M sc(node.handle());
+    const std::vector<liorf_amd::PointXYZI> all = read_cloud(argv[2]);
+    std::ifstream tab(argv[3]);
+    if (!tab) throw std::runtime_error(std::string("cannot open ") + argv[3]);
+    node.mappingSurfLeafSize = (float)std::atof(argv[4]);
+    node.historyKeyframeSearchRadius = (float)std::atof(argv[5]);
+    node.historyKeyframeSearchNum = std::atoi(argv[6]);
+    node.loopClosureICPSurfLeafSize = (float)std::atof(argv[7]);
+    node.historyKeyframeFitnessScore = (float)std::atof(argv[8]);
+    size_t n, at = 0;
+    double t;
+    float p[6];
+    int i = 0;
+    for (; tab >> n >> t >> p[0] >> p[1] >> p[2] >> p[3] >> p[4] >> p[5]; i++) {
+        if (at + n > all.size()) throw std::runtime_error("keys.txt asks for more points than keys.bin holds");
+        node.timeLaserInfoCur = t;
+        node.laserCloudSurfLast.assign(all.begin() + (std::ptrdiff_t)at, all.begin() + (std::ptrdiff_t)(at + n));
+        at += n;
+        node.downsampleCurrentScan();
+        const float rpyxyz[6] = { p[3], p[4], p[5], p[0], p[1], p[2] };
+        for (int k = 0; k < 6; k++) node.transformTobeMapped[k] = rpyxyz[k];
+        node.saveKeyFrame();
+        sc.makeAndSaveScancontextAndKeys(node.laserCloudSurfLastDS);
+        node.performRSLoopClosure();
+        print_loop("rs", i, node.lastLoop);
+        node.performSCLoopClosure(sc);
+        print_loop("sc", i, node.lastLoop);
+    }
+    std::vector<liorf_amd::PointXYZI> near;
+    if (i > 0) node.loopFindNearKeyframes(near, i - 1, node.historyKeyframeSearchNum, -1);
+    std::printf("near %zu\n", near.size());
+    return 0;
+}
+
 // --many map.bin roll pitch yaw x y z scan0.bin scan1.bin ...: the same initial guess for every scan; the scans once as a batch
 // (scan2MapOptimizationBatch), once as a stream through two slots (prepareNextScan / launchSlot / collectSlot), once one by one
 // (scan2MapOptimization): prints "batch|stream|single <i> iters <n> pose ..." - the three must agree bit for bit.
@@ -150,6 +205,7 @@ int main(int argc, char** argv)
         if (argc == 13 && std::string(argv[1]) == "--chain") return run_chain(argv);
         if (argc >= 10 && std::string(argv[1]) == "--many") return run_many(argc, argv);
         if (argc == 7 && std::string(argv[1]) == "--keyframes") return run_keyframes(argv);
+        if (argc == 9 && std::string(argv[1]) == "--loop") return run_loop(argv);
         if (argc != 9 && argc != 16) {
             std::fprintf(stderr, "usage: %s map.bin scan.bin roll pitch yaw x y z [imuType imuRPYWeight z_tol rot_tol imuAvailable imuRoll imuPitch]\n", argv[0]);
             return 2;

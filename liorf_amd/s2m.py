@@ -20,6 +20,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("S2M_LIB") or os.path.join(_HERE, "libliorf_s2m.so")   # S2M_LIB: A/B measurements of two builds
 
 S2M_OK = 0
+S2M_ERR_CAPACITY = -5
 ERRORS = {-1: "S2M_ERR_INVALID_ARG", -2: "S2M_ERR_NO_DEVICE", -3: "S2M_ERR_HIP", -4: "S2M_ERR_NO_SCAN",
           -5: "S2M_ERR_CAPACITY"}
 
@@ -36,8 +37,10 @@ ABI_SYMBOLS = [
     "s2m_icp_default_params", "s2m_icp_align", "s2m_debug_device_trig",
     "s2m_sc_reset", "s2m_sc_size", "s2m_sc_add_scan", "s2m_sc_add_descriptor", "s2m_sc_detect_loop", "s2m_sc_distance",
     "s2m_kf_default_params", "s2m_kf_reset", "s2m_kf_size", "s2m_kf_add", "s2m_kf_set_poses", "s2m_extract_surrounding",
+    "s2m_loop_default_params", "s2m_loop_near_keyframes", "s2m_loop_align", "s2m_loop_closure_rs",
 ]
 S2M_KF_FROM_HOST, S2M_KF_FROM_DEVICE, S2M_KF_FROM_LAST_DOWNSAMPLE = 0, 1, 2
+S2M_LOOP_NONE, S2M_LOOP_ALREADY_CLOSED, S2M_LOOP_TOO_FEW_POINTS, S2M_LOOP_REJECTED, S2M_LOOP_ACCEPTED = 0, 1, 2, 3, 4
 S2M_WARN_LEAF_TOO_SMALL = 1
 
 
@@ -82,6 +85,16 @@ class IcpResult(C.Structure):
 
 class KfParams(C.Structure):
     _fields_ = [("search_radius", C.c_float), ("density", C.c_float), ("map_leaf", C.c_float), ("recent_window_s", C.c_double)]
+
+
+class LoopParams(C.Structure):
+    _fields_ = [("search_radius", C.c_float), ("time_diff_s", C.c_float), ("search_num", C.c_int32),
+                ("fitness_score", C.c_float), ("icp_leaf", C.c_float)]
+
+
+class LoopResult(C.Structure):
+    _fields_ = [("status", C.c_int32), ("key_cur", C.c_int32), ("key_pre", C.c_int32), ("n_cur", C.c_int32),
+                ("n_prev", C.c_int32), ("icp", IcpResult), ("pose_from", C.c_float * 6), ("pose_to", C.c_float * 6)]
 
 
 class S2MError(RuntimeError):
@@ -180,6 +193,10 @@ def load_library(path: str | None = None) -> C.CDLL:
     L.s2m_kf_set_poses.argtypes = [vp, C.c_int, C.c_int, fp]
     L.s2m_extract_surrounding.argtypes = [vp, C.c_double, C.POINTER(KfParams), vp, C.c_size_t, C.c_size_t, szp, i32p,
                                           C.c_size_t, szp]
+    L.s2m_loop_default_params.argtypes = [C.POINTER(LoopParams)]
+    L.s2m_loop_near_keyframes.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, C.c_float, vp, C.c_size_t, C.c_size_t, szp]
+    L.s2m_loop_align.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, C.POINTER(LoopParams), C.POINTER(LoopResult)]
+    L.s2m_loop_closure_rs.argtypes = [vp, C.c_double, C.POINTER(LoopParams), C.POINTER(LoopResult)]
     if path is None:
         _LIB = L
     return L
@@ -667,10 +684,60 @@ class MapOptimizationS2M:
         run(out.ctypes.data, m.value)                 # (the same selection again: deterministic, same map)
         return k, out[:m.value]
 
+    # -- loop closure against the resident key-frame store (reference :542-844) ----------------------
+    def loopFindNearKeyframes(self, key: int, searchNum: int, loop_index: int = -1, leaf: float = 0.3) -> np.ndarray:
+        """loopFindNearKeyframes(nearKeyframes, key, searchNum, loop_index) (reference :821-844) with downSizeFilterICP's
+        leaf: (m, 8) float32 records."""
+        m = C.c_size_t(0)
+        rc = self.lib.s2m_loop_near_keyframes(self.h, key, searchNum, loop_index, leaf, None, 32, 0, C.byref(m))
+        if rc != S2M_ERR_CAPACITY:
+            self.leaf_too_small = self._check_voxel(rc, "s2m_loop_near_keyframes")
+        out = np.zeros((max(m.value, 1), 8), np.float32)
+        if m.value:                                   # (the same submap again, now with room for it)
+            self.leaf_too_small = self._check_voxel(
+                self.lib.s2m_loop_near_keyframes(self.h, key, searchNum, loop_index, leaf, out.ctypes.data, 32, m.value,
+                                                 C.byref(m)), "s2m_loop_near_keyframes")
+        return out[:m.value]
+
+    def loopAlign(self, key_cur: int, key_pre: int, base_key: int = -1, params: LoopParams | None = None) -> LoopResult:
+        """Extraction, gates, ICP and pose result for a given pair: base_key -1 is the RS form, >= 0 the SC form."""
+        r = LoopResult()
+        pp = C.byref(params) if params is not None else None
+        self._check(self.lib.s2m_loop_align(self.h, key_cur, key_pre, base_key, pp, C.byref(r)), "s2m_loop_align")
+        return r
+
+    def performRSLoopClosure(self, timeLaserInfoCur: float, params: LoopParams | None = None) -> LoopResult:
+        """performRSLoopClosure() (reference :542-622) with detectLoopClosureDistance() (:732-765) on the device."""
+        r = LoopResult()
+        pp = C.byref(params) if params is not None else None
+        self._check(self.lib.s2m_loop_closure_rs(self.h, float(timeLaserInfoCur), pp, C.byref(r)), "s2m_loop_closure_rs")
+        return r
+
+    def performSCLoopClosure(self, params: LoopParams | None = None) -> LoopResult:
+        """performSCLoopClosure() (reference :624-730): the ScanContext detector on this handle's SC store, then
+        s2m_loop_align(kfSize() - 1, pre, 0, ..) (:634-655). yaw_diff is not used by the reference (:639)."""
+        r = LoopResult()
+        r.status, r.key_cur, r.key_pre = S2M_LOOP_NONE, -1, -1
+        n = self.kfSize()
+        if n <= 0:                                    # (:626-627): no detection either
+            return r
+        pre, _, _ = self.detectLoopClosureID()
+        if pre == -1:
+            return r
+        return self.loopAlign(n - 1, pre, 0, params)
+
 
 def default_kf_params(**kw) -> KfParams:
     p = KfParams()
     load_library().s2m_kf_default_params(C.byref(p))
+    for k, v in kw.items():
+        setattr(p, k, v)
+    return p
+
+
+def default_loop_params(**kw) -> LoopParams:
+    p = LoopParams()
+    load_library().s2m_loop_default_params(C.byref(p))
     for k, v in kw.items():
         setattr(p, k, v)
     return p

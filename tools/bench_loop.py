@@ -1,0 +1,154 @@
+"""Wall time of performRSLoopClosure() on the resident key-frame store against today's binding.
+
+Stores of 5 000 and 50 000 keys on a circle of 0.5 m key spacing (1 s apart) that ends where it started; the last key's stored
+pose carries a drift of (0.3, -0.2, 0) m and 0.02 rad of yaw. Keys 0 .. 27 and the last key hold 30 000-point ray-cast frames
+of bench_keyframes.py's scene (cast at the keys' true poses), every other key a 1 000-point cloud. kitti.yaml settings:
+search radius 15 m, search_num 25, ICP leaf 0.5, fitness 0.3, time window 30 s. Medians after warm-up of:
+  loop_closure_rs_ms   s2m_loop_closure_rs: detection, both submaps, ICP. Timed with fitness_score = -1, so that every
+                       repetition does the whole work and is rejected after ICP (an accepted closure is recorded and
+                       the next call on the same key stops at S2M_LOOP_ALREADY_CLOSED); one accepted call follows,
+                       reported as accepted_ms
+  host_path_ms         the same pair as the binding does it today with this library: host key-frame clouds, per-frame
+                       s2m_transform_cloud, concatenation, s2m_voxel_downsample of both submaps, s2m_icp_align
+                       (the PCL kd-tree detection of the binding is not included)
+  icp_ms               s2m_icp_align alone on the two submaps (host copies, upload included); icp_share = icp_ms /
+                       loop_closure_rs_ms
+  detect_ms            s2m_loop_closure_rs on a store whose newest key has no candidate (detection alone)
+
+  python tools/bench_loop.py                           one JSON line
+  python tools/bench_loop.py --kernel-stats stats.csv  folds the k_loop_detect* and k_icp* rows of a rocprofv3
+                                                       --kernel-trace --stats run into the JSON line
+"""
+import argparse
+import csv
+import ctypes as C
+import json
+import os
+import re
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+if ROOT not in sys.path:
+    sys.path.insert(0, ROOT)
+
+FRAME_PTS, SMALL_PTS, N_BIG = 30000, 1000, 28
+DRIFT = np.array([0.3, -0.2, 0.0, 0.0, 0.0, 0.02])
+
+
+def _true_poses(n):
+    th = 2 * np.pi * np.arange(n) / (n - 1)
+    r = 0.5 * (n - 1) / (2 * np.pi)
+    p = np.zeros((n, 6))
+    p[:, 0], p[:, 1], p[:, 5] = r * np.sin(th), r * (1 - np.cos(th)), th
+    p[-1] = [0, 0, 0, 0, 0, 0]                                         # exactly back at the start
+    return p
+
+
+def _clouds(true_near):
+    from liorf_amd import synth
+    scene = synth.make_scene(seed=11, half=70.0, n_boxes=92)
+    rng = np.random.default_rng(1)
+    out = []
+    for k, p in enumerate(true_near):
+        rpyxyz = np.array([p[3], p[4], p[5], p[0], p[1], 0.1 + p[2]])
+        c = synth.to_xyzi(synth.make_scan(scene, rpyxyz, "velodyne64", FRAME_PTS, seed=100 + k))
+        c[:, 4] = rng.uniform(0, 100, FRAME_PTS).astype(np.float32)
+        out.append(c)
+    return out
+
+
+def _median_ms(fn, warmup, reps):
+    for _ in range(warmup):
+        fn()
+    t = []
+    for _ in range(reps):
+        t0 = time.perf_counter()
+        fn()
+        t.append(time.perf_counter() - t0)
+    return round(1e3 * float(np.median(t)), 4)
+
+
+def _stats(path):
+    rows = {}
+    with open(path) as f:
+        for r in csv.DictReader(f):
+            m = re.search(r"k_loop_detect\w*|k_icp\w*", r.get("Name", ""))
+            if m:
+                rows[m.group(0)] = {"calls": int(r["Calls"]), "avg_us": round(float(r["AverageNs"]) / 1e3, 3)}
+    return rows
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--sizes", default="5000,50000")
+    ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--reps", type=int, default=10)
+    ap.add_argument("--kernel-stats", default="", help="rocprofv3 kernel_stats.csv of a run of this tool")
+    a = ap.parse_args(argv)
+    from liorf_amd import s2m
+
+    sizes = [int(s) for s in a.sizes.split(",")]
+    out = {"workload": "revisit: 30 000-point frames at keys 0..27 and the last key, 1 000 points elsewhere; R 15, search_num 25, "
+                       "leaf 0.5, fitness 0.3", "sizes": {}}
+    big = None
+    small = None
+    for n in sizes:
+        true = _true_poses(n)
+        if big is None:
+            near = [true[k] for k in range(N_BIG)] + [true[-1]]
+            big = _clouds(near)
+            small = big[1][:SMALL_PTS].copy()
+        stored = true.copy()
+        stored[-1] += DRIFT
+        stored = stored.astype(np.float32)
+        times = np.arange(n, dtype=np.float64)
+        clouds = [big[k] if k < N_BIG else small for k in range(n - 1)] + [big[-1]]
+        eng = s2m.MapOptimizationS2M()
+        for k in range(n):
+            eng.saveKeyFrame(stored[k], times[k], clouds[k])
+        prm = s2m.default_loop_params(search_radius=15.0, search_num=25, icp_leaf=0.5)
+        rej = s2m.default_loop_params(search_radius=15.0, search_num=25, icp_leaf=0.5, fitness_score=-1.0)
+        r = s2m.LoopResult()
+        ms = _median_ms(lambda: eng.lib.s2m_loop_closure_rs(eng.h, float(times[-1]), C.byref(rej), C.byref(r)), a.warmup, a.reps)
+        rej_status = r.status
+        t0 = time.perf_counter()                       # then the accepted call, once: it records the closure
+        acc = eng.performRSLoopClosure(times[-1], prm)
+        accepted_ms = 1e3 * (time.perf_counter() - t0)
+        row = {"status": acc.status, "key_cur": acc.key_cur, "key_pre": acc.key_pre, "n_cur": acc.n_cur, "n_prev": acc.n_prev,
+               "iterations": acc.icp.iterations, "converged": acc.icp.converged, "fitness": acc.icp.fitness_score,
+               "accepted_ms": round(accepted_ms, 4), "pose_from": [round(float(v), 5) for v in acc.pose_from],
+               "loop_closure_rs_ms": ms}
+        assert rej_status == s2m.S2M_LOOP_REJECTED and r.icp.iterations == acc.icp.iterations, (rej_status, row)
+        # today's binding: host clouds, per-frame transform, concatenation, two filters, ICP from host memory
+        kc, kp = acc.key_cur, acc.key_pre
+        ref = s2m.MapOptimizationS2M()
+
+        def host_path():
+            cur = ref.voxelGrid(ref.transformPointCloud(clouds[kc], stored[kc]), 0.5)
+            parts = [ref.transformPointCloud(clouds[k], stored[k]) for k in range(max(0, kp - 25), min(n - 1, kp + 25) + 1)]
+            prev = ref.voxelGrid(np.concatenate(parts), 0.5)
+            return cur, prev, ref.icpAlign(cur, prev, max_correspondence_distance=30.0)
+        cur, prev, icp = host_path()
+        assert (cur.shape[0], prev.shape[0], icp[3]) == (acc.n_cur, acc.n_prev, acc.icp.iterations)
+        assert np.array_equal(icp[0].reshape(-1), np.array(acc.icp.T, np.float32))
+        row["host_path_ms"] = _median_ms(host_path, a.warmup, a.reps)
+        row["icp_ms"] = _median_ms(lambda: ref.icpAlign(cur, prev, max_correspondence_distance=30.0), a.warmup, a.reps)
+        row["icp_share"] = round(row["icp_ms"] / row["loop_closure_rs_ms"], 3)
+        ref.close()
+        # detection alone: one more key far from everything, so that no key passes
+        eng.saveKeyFrame(np.array([1e4, 1e4, 0, 0, 0, 0], np.float32), float(n), small)
+        row["detect_ms"] = _median_ms(lambda: eng.lib.s2m_loop_closure_rs(eng.h, float(n), C.byref(prm), C.byref(r)), a.warmup, a.reps)
+        assert r.status == s2m.S2M_LOOP_NONE
+        eng.close()
+        out["sizes"][str(n)] = row
+    if a.kernel_stats:
+        out["kernels_device_us"] = _stats(a.kernel_stats)
+    out["note"] = "wall clock, median after warm-up; every call ends with the library's own synchronisation"
+    print(json.dumps(out))
+
+
+if __name__ == "__main__":
+    main()
