@@ -290,6 +290,35 @@ int  s2m_extract_surrounding(s2m_handle h, double time_cur, const s2m_kf_params*
                              void* out, size_t out_stride_bytes, size_t cap, size_t* n_out,
                              int32_t* keys, size_t keys_cap, size_t* n_keys);
 
+/* ---- The global map and the saved map from the key-frame store -------------------------------------------
+ * publishGlobalMap() (reference src/mapOptmization.cpp:453-502) and saveMapService() (:375-432) against the resident store,
+ * so that the node keeps no host copy of surfCloudKeyFrames. N, P[i] and pose[i] as above.
+ * s2m_global_map: (b), (c), (d) and (f) of the selection above around key N-1 with R = search_radius and D = pose_density,
+ *   and no recent keys (e); the surviving keys' clouds transformed by their current poses, concatenated in selection order
+ *   and filtered with leaf `leaf` (globalMapKeyFramesDS). Capacity, *n_out, keys, *n_keys and S2M_ERR_CAPACITY behave as in
+ *   s2m_extract_surrounding; an empty store gives S2M_OK with zero counts; S2M_WARN_LEAF_TOO_SMALL returns the unfiltered
+ *   concatenation. At most 2^31 - 2^21 concatenated points (S2M_ERR_CAPACITY beyond, before anything is transformed).
+ * s2m_kf_map_cloud: keys first .. first+count-1 (a range inside [0, N)) transformed by their current poses and concatenated in
+ *   key order (globalSurfCloud, :395-398); with leaf > 0 also filtered with that leaf (SurfMap.pcd at req.resolution, :400-407).
+ *   leaf == 0 is the unfiltered cloud (GlobalMap.pcd, and SurfMap.pcd at resolution 0): it is produced in bounded chunks of
+ *   frames and never held whole on the device; cap == 0 is the size query (*n_out set, nothing written). With leaf > 0 the
+ *   whole concatenation is filtered on the device: more than 2^31 - 2^21 points give S2M_ERR_CAPACITY before any launch.
+ *   *n_out always holds the full count; a short `out` gets its first cap records and S2M_ERR_CAPACITY.
+ * Neither call touches the installed local map and its index, the scan, the pose, the batch and stream slots, the key store
+ * or the loop-index container: the next registration is bit for bit the one without them. The handle is held for the whole
+ * call, the copy to `out` included. */
+typedef struct s2m_gmap_params {
+    float search_radius;     /* globalMapVisualizationSearchRadius 1e3  include/utility.h:250 */
+    float pose_density;      /* globalMapVisualizationPoseDensity  10.0 include/utility.h:251 (M2DGR.yaml: 3.0) */
+    float leaf;              /* globalMapVisualizationLeafSize     1.0  include/utility.h:252 */
+} s2m_gmap_params;
+int  s2m_gmap_default_params(s2m_gmap_params* p);
+int  s2m_global_map(s2m_handle h, const s2m_gmap_params* p /* NULL = defaults */,
+                    void* out, size_t out_stride_bytes, size_t cap, size_t* n_out,
+                    int32_t* keys, size_t keys_cap, size_t* n_keys);
+int  s2m_kf_map_cloud(s2m_handle h, int first, int count, float leaf /* 0 = no filter */,
+                      void* out, size_t out_stride_bytes, size_t cap, size_t* n_out);
+
 /* ---- ScanContext descriptor (BASELINE config 5) ------------------------- */
 /* SCManager::makeScancontext + makeRingkeyFromScancontext
  * (reference include/Scancontext.cpp:151-211): desc is 20x60 row-major doubles,

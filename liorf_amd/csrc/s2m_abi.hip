@@ -74,6 +74,11 @@ struct s2m_context {
     // loop closure against the store: loopIndexContainer (:146), the transformed frames and the two filtered submaps
     std::map<int32_t, int32_t> loop_index;
     DevBuf loop_xf, loop_cur, loop_prev;
+    // the global map and the saved map from the store: transformed frames, the filtered cloud, the chunked copy-out (frame table,
+    // two staging buffers that take turns, a copy stream and its events)
+    DevBuf map_xf, map_out, map_tab, map_stage[2];
+    hipStream_t map_copy_stream = nullptr;
+    hipEvent_t map_ev_xf[2] = { nullptr, nullptr }, map_ev_cp[2] = { nullptr, nullptr };
 
     DevCtx hctx{};
     bool ctx_dirty = true;
@@ -913,8 +918,13 @@ int s2m_destroy(s2m_handle h)
                        &h->dbg_idx5, &h->dbg_d2, &h->dbg_flag, &h->dbg_coeff, &h->dbg_clk, &h->sc_bins, &h->sc_out,
                        &h->vox_in, &h->vox_out, &h->frames_xf, &h->scan_ds, &h->map_ds,
                        &h->sc_store_desc, &h->sc_store_ring, &h->sc_store_sector, &h->sc_cand, &h->sc_res,
-                       &h->loop_xf, &h->loop_cur, &h->loop_prev };
+                       &h->loop_xf, &h->loop_cur, &h->loop_prev, &h->map_xf, &h->map_out, &h->map_tab, &h->map_stage[0], &h->map_stage[1] };
     for (DevBuf* b : bufs) if (b->p) (void)hipFree(b->p);
+    if (h->map_copy_stream) { (void)hipStreamSynchronize(h->map_copy_stream); (void)hipStreamDestroy(h->map_copy_stream); }
+    for (int k = 0; k < 2; k++) {
+        if (h->map_ev_xf[k]) (void)hipEventDestroy(h->map_ev_xf[k]);
+        if (h->map_ev_cp[k]) (void)hipEventDestroy(h->map_ev_cp[k]);
+    }
     vox_destroy(h->vox);
     icp_destroy(h->icp);
     if (h->icp_src.p) (void)hipFree(h->icp_src.p);
@@ -2254,6 +2264,210 @@ int s2m_loop_closure_rs(s2m_handle h, double time_cur, const s2m_loop_params* p,
     if (e != hipSuccess) return fail(h, S2M_ERR_HIP, "loop detection", e);
     if (key_pre == -1 || key_pre == key_cur) return S2M_OK;                 // (:761-762)
     return loop_align_impl(h, key_cur, key_pre, -1, prm, out);
+}
+
+// ---- the global map and the saved map from the key-frame store (publishGlobalMap :453-502, saveMapService :375-432) ---------
+
+int s2m_gmap_default_params(s2m_gmap_params* p)
+{
+    if (!p) return S2M_ERR_INVALID_ARG;
+    p->search_radius = 1e3f;        // globalMapVisualizationSearchRadius  include/utility.h:250
+    p->pose_density = 10.0f;        // globalMapVisualizationPoseDensity   include/utility.h:251
+    p->leaf = 1.0f;                 // globalMapVisualizationLeafSize      include/utility.h:252
+    return S2M_OK;
+}
+
+namespace {
+
+// Concatenations that go through the VoxelGrid: the voxel stage counts and places points in int32 (k_transform_frames' and
+// k_vox_centroid's one lane per point, the radix sort's positions, the run starts) and k_vox_bbox strides up to 2^20 past the
+// last point, so the total stays 2^21 below INT32_MAX.
+constexpr size_t kMapMaxPts = ((size_t)1 << 31) - ((size_t)1 << 21);
+constexpr size_t kMapChunkPts = (size_t)1 << 22;           // unfiltered copy-out: points per chunk (128 MiB of records per staging buffer)
+
+// frames first .. first+count-1 of the store, each transformed by its current pose, back to back into map_xf (total records)
+int map_transform_range(s2m_context* h, int first, int count, size_t total)
+{
+    std::vector<const unsigned char*> src((size_t)count);
+    std::vector<int32_t> offsets((size_t)count + 1, 0);
+    std::vector<float> T((size_t)count * 12);
+    for (int f = 0; f < count; f++) {
+        const KfFrame& kf = h->kf_frame[(size_t)first + f];
+        src[f] = kf.src;
+        offsets[f + 1] = offsets[f] + kf.n;
+        std::copy(kf.T, kf.T + 12, &T[12 * (size_t)f]);
+    }
+    int rc = ensure(h, h->map_xf, kDsStride * total);
+    if (rc) return rc;
+    hipError_t e = vox_transform_frames(h->vox, h->stream, src.data(), kDsStride, offsets.data(), T.data(), count,
+                                        h->map_xf.as<unsigned char>(), kDsStride);
+    if (e != hipSuccess) return fail(h, S2M_ERR_HIP, "key-frame transform", e);
+    S2M_HIP(h, hipStreamSynchronize(h->stream));           // (the host table above is read by the copies until here)
+    return S2M_OK;
+}
+
+// the unfiltered concatenation of frames first .. first+count-1 to host `out`, its first m records: chunks of whole frames are
+// transformed into two staging buffers in turn, and each chunk's copy to the host (a stream of its own) runs while the next
+// chunk is transformed
+int map_copy_out_chunked(s2m_context* h, int first, int count, size_t m, void* out, size_t out_stride)
+{
+    struct Chunk { int f0, nf; size_t at, n; };
+    std::vector<Chunk> chunks;
+    size_t at = 0, biggest = 0;
+    for (int f = 0; f < count && at < m;) {
+        Chunk c{ f, 0, at, 0 };
+        while (f < count && (c.nf == 0 || c.n + (size_t)h->kf_frame[(size_t)first + f].n <= kMapChunkPts)) {
+            c.n += (size_t)h->kf_frame[(size_t)first + f].n;
+            c.nf++; f++;
+        }
+        at += c.n;
+        biggest = std::max(biggest, c.n);
+        if (c.n) chunks.push_back(c);
+    }
+    if (chunks.empty()) return S2M_OK;
+    // device table: source pointers | transforms | per chunk its frames' offsets from the chunk's start
+    const size_t nf_all = (size_t)(chunks.back().f0 + chunks.back().nf);
+    const size_t ptr_bytes = (sizeof(void*) * nf_all + 15) & ~(size_t)15, t_bytes = (sizeof(float) * 12 * nf_all + 15) & ~(size_t)15;
+    std::vector<unsigned char> tab(ptr_bytes + t_bytes + sizeof(int32_t) * (nf_all + chunks.size()));
+    std::vector<size_t> off_at(chunks.size());
+    {
+        const unsigned char** src = reinterpret_cast<const unsigned char**>(tab.data());
+        float* T = reinterpret_cast<float*>(tab.data() + ptr_bytes);
+        int32_t* off = reinterpret_cast<int32_t*>(tab.data() + ptr_bytes + t_bytes);
+        size_t o = 0;
+        for (size_t c = 0; c < chunks.size(); c++) {
+            off_at[c] = o;
+            int32_t run = 0;
+            for (int f = chunks[c].f0; f < chunks[c].f0 + chunks[c].nf; f++) {
+                const KfFrame& kf = h->kf_frame[(size_t)first + f];
+                src[f] = kf.src;
+                std::copy(kf.T, kf.T + 12, T + 12 * (size_t)f);
+                off[o++] = run;
+                run += kf.n;
+            }
+            off[o++] = run;
+        }
+    }
+    int rc = ensure(h, h->map_tab, tab.size());
+    if (rc) return rc;
+    for (int k = 0; k < 2 && k < (int)chunks.size(); k++)
+        if ((rc = ensure(h, h->map_stage[k], kDsStride * biggest))) return rc;
+    if (!h->map_copy_stream) S2M_HIP(h, hipStreamCreateWithFlags(&h->map_copy_stream, hipStreamNonBlocking));
+    for (int k = 0; k < 2; k++) {
+        if (!h->map_ev_xf[k]) S2M_HIP(h, hipEventCreateWithFlags(&h->map_ev_xf[k], hipEventDisableTiming));
+        if (!h->map_ev_cp[k]) S2M_HIP(h, hipEventCreateWithFlags(&h->map_ev_cp[k], hipEventDisableTiming));
+    }
+    unsigned char* d_tab = h->map_tab.as<unsigned char>();
+    S2M_HIP(h, hipMemcpyAsync(d_tab, tab.data(), tab.size(), hipMemcpyHostToDevice, h->stream));
+    const unsigned char* const* d_src = reinterpret_cast<const unsigned char* const*>(d_tab);
+    const float* d_T = reinterpret_cast<const float*>(d_tab + ptr_bytes);
+    const int32_t* d_off = reinterpret_cast<const int32_t*>(d_tab + ptr_bytes + t_bytes);
+    auto transform = [&](size_t c) -> int {
+        const int b = (int)(c & 1);
+        if (c >= 2) S2M_HIP(h, hipStreamWaitEvent(h->stream, h->map_ev_cp[b], 0));     // chunk c-2's copy has left the buffer
+        hipError_t e = vox_transform_frames_device(h->stream, d_src + chunks[c].f0, kDsStride, d_off + off_at[c], d_T + 12 * (size_t)chunks[c].f0,
+                                                   chunks[c].nf, chunks[c].n, h->map_stage[b].as<unsigned char>(), kDsStride);
+        if (e != hipSuccess) return fail(h, S2M_ERR_HIP, "key-frame transform", e);
+        S2M_HIP(h, hipEventRecord(h->map_ev_xf[b], h->stream));
+        return S2M_OK;
+    };
+    const size_t width = out_stride < kDsStride ? out_stride : kDsStride;
+    if ((rc = transform(0))) return rc;
+    for (size_t c = 0; c < chunks.size(); c++) {
+        if (c + 1 < chunks.size() && (rc = transform(c + 1))) return rc;        // the next chunk is on its way before this one is copied
+        const int b = (int)(c & 1);
+        const size_t rows = std::min(chunks[c].n, m - chunks[c].at);
+        S2M_HIP(h, hipStreamWaitEvent(h->map_copy_stream, h->map_ev_xf[b], 0));
+        S2M_HIP(h, hipMemcpy2DAsync(static_cast<unsigned char*>(out) + chunks[c].at * out_stride, out_stride, h->map_stage[b].p, kDsStride,
+                                    width, rows, hipMemcpyDeviceToHost, h->map_copy_stream));
+        S2M_HIP(h, hipEventRecord(h->map_ev_cp[b], h->map_copy_stream));
+    }
+    S2M_HIP(h, hipStreamSynchronize(h->map_copy_stream));
+    S2M_HIP(h, hipStreamSynchronize(h->stream));
+    if (out_stride > kDsStride)                // records wider than the device's: the fields past it are 0, as download_records leaves them
+        for (size_t i = 0; i < m; i++) memset(static_cast<unsigned char*>(out) + i * out_stride + kDsStride, 0, out_stride - kDsStride);
+    return S2M_OK;
+}
+
+bool bad_out(void* out, size_t out_stride, size_t cap) { return cap > 0 && (!out || out_stride < 12 || (out_stride & 3)); }
+
+}  // namespace
+
+int s2m_global_map(s2m_handle h, const s2m_gmap_params* p, void* out, size_t out_stride_bytes, size_t cap, size_t* n_out,
+                   int32_t* keys, size_t keys_cap, size_t* n_keys)
+{
+    if (!h) return S2M_ERR_INVALID_ARG;
+    s2m_gmap_params prm;
+    if (p) prm = *p; else s2m_gmap_default_params(&prm);
+    if (!(prm.search_radius > 0.0f) || !std::isfinite(prm.search_radius) || !(prm.pose_density > 0.0f) || !std::isfinite(prm.pose_density))
+        return fail(h, S2M_ERR_INVALID_ARG, "search radius and pose density must be positive and finite");
+    int rc = check_leaf(h, prm.leaf);
+    if (rc) return rc;
+    if (!n_out || bad_out(out, out_stride_bytes, cap) || (keys_cap > 0 && !keys)) return fail(h, S2M_ERR_INVALID_ARG, "bad output buffer");
+    *n_out = 0;
+    if (n_keys) *n_keys = 0;
+    const size_t N = h->kf_time.size();
+    if (N == 0) return S2M_OK;                             // cloudKeyPoses3D->points.empty() (:458-459)
+    S2M_HIP(h, hipSetDevice(h->device));
+    // (b) radiusSearch around cloudKeyPoses3D->back(), (c) the key-pose VoxelGrid, (d) nearest key per centroid, (f) the distance
+    // test at the centroid (:466-491): kf_select with no recent keys
+    KfSelect sel;
+    KfTable tab;
+    hipError_t e = kf_select(h->vox, h->stream, h->kf_pos.as<float4>(), h->kf_frames.as<KfFrame>(), (int)N, 0,
+                             prm.search_radius, prm.pose_density, &sel, &tab);
+    if (e != hipSuccess) return fail(h, S2M_ERR_HIP, "global-map key selection", e);
+    if (n_keys) *n_keys = (size_t)sel.n_frames;
+    if ((unsigned long long)sel.n_points > kMapMaxPts) return fail(h, S2M_ERR_CAPACITY, "too many points in the global map");
+    VoxResult res;
+    if (sel.n_points > 0) {
+        const size_t total = (size_t)sel.n_points;
+        if ((rc = ensure(h, h->map_xf, kDsStride * total))) return rc;
+        e = vox_transform_frames_device(h->stream, tab.src, kDsStride, tab.offsets, tab.T, sel.n_frames, total, h->map_xf.as<unsigned char>(), kDsStride);
+        if (e != hipSuccess) return fail(h, S2M_ERR_HIP, "key-frame transform", e);
+        if ((rc = voxel_into(h, h->map_xf.as<unsigned char>(), total, kDsStride, prm.leaf, h->map_out, &res))) return rc;   // globalMapKeyFramesDS
+    }
+    *n_out = res.n_out;
+    if (cap > 0 && (rc = download_records(h, h->map_out, res.n_out, out, out_stride_bytes, cap))) return rc;
+    const size_t nk = (size_t)sel.n_frames < keys_cap ? (size_t)sel.n_frames : keys_cap;
+    if (nk > 0) {
+        S2M_HIP(h, hipMemcpyAsync(keys, tab.keys, sizeof(int32_t) * nk, hipMemcpyDeviceToHost, h->stream));
+        S2M_HIP(h, hipStreamSynchronize(h->stream));
+    }
+    if (cap > 0 && res.n_out > cap) return fail(h, S2M_ERR_CAPACITY, "output buffer too small for the global map");
+    if (keys_cap > 0 && (size_t)sel.n_frames > keys_cap) return fail(h, S2M_ERR_CAPACITY, "key buffer too small for the frame list");
+    return res.leaf_too_small ? S2M_WARN_LEAF_TOO_SMALL : S2M_OK;
+}
+
+int s2m_kf_map_cloud(s2m_handle h, int first, int count, float leaf, void* out, size_t out_stride_bytes, size_t cap, size_t* n_out)
+{
+    if (!h) return S2M_ERR_INVALID_ARG;
+    if (!n_out || bad_out(out, out_stride_bytes, cap)) return fail(h, S2M_ERR_INVALID_ARG, "bad output buffer");
+    *n_out = 0;
+    if (!(leaf >= 0.0f) || !std::isfinite(leaf)) return fail(h, S2M_ERR_INVALID_ARG, "leaf size must be 0 (no filter) or positive and finite");
+    const size_t N = h->kf_time.size();
+    if (first < 0 || count < 0 || (size_t)first + (size_t)count > N) return fail(h, S2M_ERR_INVALID_ARG, "key range outside the key-frame store");
+    unsigned long long total = 0;                          // 64 bits, from the host mirror of the per-key counts
+    for (int f = 0; f < count; f++) total += (unsigned long long)h->kf_frame[(size_t)first + f].n;
+    if (total == 0) return S2M_OK;
+    S2M_HIP(h, hipSetDevice(h->device));
+    if (leaf == 0.0f) {                                    // globalSurfCloud as it is (GlobalMap.pcd, :410-415)
+        *n_out = (size_t)total;
+        const size_t m = (size_t)total < cap ? (size_t)total : cap;
+        int rc = m > 0 ? map_copy_out_chunked(h, first, count, m, out, out_stride_bytes) : S2M_OK;
+        if (rc) return rc;
+        if (cap > 0 && (size_t)total > cap) return fail(h, S2M_ERR_CAPACITY, "output buffer too small for the map cloud");
+        return S2M_OK;
+    }
+    // downSizeFilterSurf at req.resolution (:400-407): the whole concatenation on the device
+    if (total > kMapMaxPts) return fail(h, S2M_ERR_CAPACITY, "too many points to filter on the device");
+    int rc = map_transform_range(h, first, count, (size_t)total);
+    if (rc) return rc;
+    VoxResult res;
+    if ((rc = voxel_into(h, h->map_xf.as<unsigned char>(), (size_t)total, kDsStride, leaf, h->map_out, &res))) return rc;
+    *n_out = res.n_out;
+    if (cap > 0 && (rc = download_records(h, h->map_out, res.n_out, out, out_stride_bytes, cap))) return rc;
+    if (cap > 0 && res.n_out > cap) return fail(h, S2M_ERR_CAPACITY, "output buffer too small for the map cloud");
+    return res.leaf_too_small ? S2M_WARN_LEAF_TOO_SMALL : S2M_OK;
 }
 
 int s2m_make_scancontext(s2m_handle h, const void* pts, size_t n, size_t stride_bytes,

@@ -795,9 +795,16 @@ __device__ void kf_bitonic(unsigned long long* a, int P)
         }
 }
 
+// PRE: stores of more than kKfTile keys, where (b) has already run on the whole grid (k_kf_radius_count / k_kf_radius_write): the
+// candidates are read from cand_d2 / cand_key (key order) and the filter's setup from `pre_vs` (k_vox_setup over the radius scan's
+// partial boxes). More than kKfTile candidates: nothing is done here but st->n_cand, and st->n_cent is 0 - the host runs the
+// device-wide sort (kf_select_wide) after its wait.
+template <bool PRE>
 __global__ __launch_bounds__(kKfThreads) void k_kf_select_candidates(const float4* __restrict__ pos, int n, float r2, float density,
                                                                      unsigned long long* __restrict__ g_key, int32_t* __restrict__ g_ord,
-                                                                     float4* __restrict__ cent, KfSelState* __restrict__ st)
+                                                                     float4* __restrict__ cent, KfSelState* __restrict__ st,
+                                                                     const VoxSetup* __restrict__ pre_vs, const uint32_t* __restrict__ cand_d2,
+                                                                     const int32_t* __restrict__ cand_key)
 {
     __shared__ unsigned long long s_key[kKfTile];
     __shared__ int32_t s_ord[kKfTile];
@@ -805,10 +812,20 @@ __global__ __launch_bounds__(kKfThreads) void k_kf_select_candidates(const float
     __shared__ uint32_t s_mm[kKfThreads / 64][6];
     __shared__ VoxSetup s_vs;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    int m = 0;
+    if (PRE) {
+        m = pre_vs->n_valid;
+        if (m > kKfTile) {
+            if (tid == 0) { st->n_cand = m; st->n_cent = 0; }
+            return;
+        }
+        if (tid == 0) { s_vs = *pre_vs; st->n_cand = m; }
+        for (int r = tid; r < m; r += kKfThreads) g_key[r] = ((unsigned long long)cand_d2[r] << 32) | (uint32_t)cand_key[r];
+        __syncthreads();
+    } else {
     const float4 q = pos[n - 1];
     // (b) every key with d2 < r2, compacted in key order, as (d2 bits, key): FLANN's sorted radius result once sorted
     uint32_t lo[3] = { 0xffffffffu, 0xffffffffu, 0xffffffffu }, hi[3] = { 0u, 0u, 0u };
-    int m = 0;
     for (int base = 0; base < n; base += kKfThreads) {
         const int i = base + tid;
         bool in = false;
@@ -841,6 +858,7 @@ __global__ __launch_bounds__(kKfThreads) void k_kf_select_candidates(const float
         // (c) pcl::VoxelGrid over the records {P[i], 1, intensity i} in the order of (b): the filter's own setup
         vox_setup_fill(&s_vs, density, lo, hi, m);
         st->n_cand = m;
+    }
     }
     int P = 1;
     while (P < m) P <<= 1;
@@ -961,8 +979,152 @@ __global__ __launch_bounds__(kKfThreads) void k_kf_select_frames(const float4* _
         t_off[nf] = (int32_t)np;
         out->n_frames = nf;
         out->n_cent = n_cent;
+        out->n_cand = st->n_cand;
         out->n_points = np;
     }
+}
+
+// ------------------------------------------------------------------------------------------
+// (b) and (c) device-wide, for stores of more than kKfTile keys (kf_select_wide). The result is the one of k_kf_select_candidates:
+//   k_kf_radius_count   every workgroup: kRsTile keys, its hit count and the ordered-uint box of its hits (k_vox_setup's layout)
+//   k_kf_radius_write   the hits compacted in key order: (d2 bits, key); a hit's place = hits of the blocks before + of the waves
+//                       before + of the rounds before + of the lanes before (ballots): a pure function of the store
+//   k_rs_* x 3          stable sort of the d2 bits (33 bits in three 11-bit passes) carrying the key: input in key order, so the
+//                       result is ascending (d2, key) - the bitonic sort's order of unique 64-bit keys
+//   k_kf_vox_keys       rank -> key (kf ord) and rank -> voxel index of the key's position (the rank itself when the leaf is too
+//                       small: PCL passes the input through)
+//   k_rs_* x 3          stable sort of the voxel indices carrying the rank: ascending (voxel, rank)
+//   k_heads_*           run starts, their number = centroids
+//   k_kf_gather         the candidate positions in (voxel, rank) order
+//   k_kf_centroids      one lane per run: sequential fp32 sums in rank order, / count - as k_kf_select_candidates
+// ------------------------------------------------------------------------------------------
+__device__ __forceinline__ int32_t kf_wave_sum(int32_t v)
+{
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+    return v;
+}
+
+__global__ __launch_bounds__(256) void k_kf_radius_count(const float4* __restrict__ pos, int n, float r2, uint32_t* __restrict__ part)
+{
+    __shared__ uint32_t s_mm[4][6];
+    __shared__ int32_t s_c[4];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int base = blockIdx.x * kRsTile + wave * (kRsTile / 4);
+    const float4 q = pos[n - 1];
+    uint32_t lo[3] = { 0xffffffffu, 0xffffffffu, 0xffffffffu }, hi[3] = { 0u, 0u, 0u };
+    int32_t c = 0;
+    for (int r = 0; r < kRsRounds; r++) {
+        const int i = base + r * 64 + lane;
+        if (i >= n) break;
+        const float4 p = pos[i];
+        if (kf_d2(p, q) < r2) {
+            const uint32_t o[3] = { f2ord(p.x), f2ord(p.y), f2ord(p.z) };
+#pragma unroll
+            for (int d = 0; d < 3; d++) { lo[d] = min(lo[d], o[d]); hi[d] = max(hi[d], o[d]); }
+            c++;
+        }
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1)
+#pragma unroll
+        for (int d = 0; d < 3; d++) {
+            lo[d] = min(lo[d], (uint32_t)__shfl_xor((int)lo[d], off, 64));
+            hi[d] = max(hi[d], (uint32_t)__shfl_xor((int)hi[d], off, 64));
+        }
+    c = kf_wave_sum(c);
+    if (lane == 0) {
+        for (int d = 0; d < 3; d++) { s_mm[wave][d] = lo[d]; s_mm[wave][3 + d] = hi[d]; }
+        s_c[wave] = c;
+    }
+    __syncthreads();
+    uint32_t* mine = part + 8 * blockIdx.x;
+    if (threadIdx.x < 3) {
+        const int d = threadIdx.x;
+        mine[d] = min(min(s_mm[0][d], s_mm[1][d]), min(s_mm[2][d], s_mm[3][d]));
+        mine[3 + d] = max(max(s_mm[0][3 + d], s_mm[1][3 + d]), max(s_mm[2][3 + d], s_mm[3][3 + d]));
+    } else if (threadIdx.x == 3) {
+        mine[6] = (uint32_t)(s_c[0] + s_c[1] + s_c[2] + s_c[3]);
+    }
+}
+
+__global__ __launch_bounds__(256) void k_kf_radius_write(const float4* __restrict__ pos, int n, float r2, const uint32_t* __restrict__ part,
+                                                         uint32_t* __restrict__ cand_d2, int32_t* __restrict__ cand_key)
+{
+    __shared__ int32_t wsum[4], bsum[4];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int base = blockIdx.x * kRsTile + wave * (kRsTile / 4);
+    const float4 q = pos[n - 1];
+    int32_t before = 0;                               // hits in the blocks before this one
+    for (int j = threadIdx.x; j < (int)blockIdx.x; j += 256) before += (int32_t)part[8 * j + 6];
+    before = kf_wave_sum(before);
+    uint32_t d2b[kRsRounds];
+    unsigned long long m[kRsRounds];
+    int32_t mine = 0;
+#pragma unroll
+    for (int r = 0; r < kRsRounds; r++) {
+        const int i = base + r * 64 + lane;
+        bool in = false;
+        d2b[r] = 0u;
+        if (i < n) { const float d2 = kf_d2(pos[i], q); in = d2 < r2; d2b[r] = __float_as_uint(d2); }
+        m[r] = __ballot(in);
+        mine += __popcll(m[r]);
+    }
+    if (lane == 0) { wsum[wave] = mine; bsum[wave] = before; }
+    __syncthreads();
+    int32_t off = bsum[0] + bsum[1] + bsum[2] + bsum[3];
+    for (int w = 0; w < wave; w++) off += wsum[w];
+#pragma unroll
+    for (int r = 0; r < kRsRounds; r++) {
+        if ((m[r] >> lane) & 1ull) {
+            const int32_t at = off + __popcll(m[r] & ((1ull << lane) - 1ull));
+            cand_d2[at] = d2b[r];
+            cand_key[at] = base + r * 64 + lane;
+        }
+        off += __popcll(m[r]);
+    }
+}
+
+// ord[rank] = key; vkey[rank] = voxel index of the key's position (or the rank: PCL's leaf-too-small pass-through)
+__global__ __launch_bounds__(256) void k_kf_vox_keys(const float4* __restrict__ pos, const int32_t* __restrict__ sorted_key, int m,
+                                                     const VoxSetup* __restrict__ vs, int32_t* __restrict__ ord, uint32_t* __restrict__ vkey)
+{
+    const int r = blockIdx.x * 256 + threadIdx.x;
+    if (r >= m) return;
+    const int k = sorted_key[r];
+    ord[r] = k;
+    const float4 p = pos[k];
+    vkey[r] = vs->leaf_too_small ? (uint32_t)r : voxel_key(p.x, p.y, p.z, vs);
+}
+
+// the positions in (voxel, rank) order: sp[e] = pos[ord[rank[e]]] (so that the sums below read contiguous records, whose loads do
+// not wait for one another)
+__global__ __launch_bounds__(256) void k_kf_gather(const float4* __restrict__ pos, const int32_t* __restrict__ ord,
+                                                   const int32_t* __restrict__ rank, int m, float4* __restrict__ sp)
+{
+    const int e = blockIdx.x * 256 + threadIdx.x;
+    if (e < m) sp[e] = pos[ord[rank[e]]];
+}
+
+// one lane per run: sequential fp32 sums in rank order (eight records requested at once, added one after the other), / count
+__global__ __launch_bounds__(256) void k_kf_centroids(const float4* __restrict__ sp, const int32_t* __restrict__ heads, int m,
+                                                      const KfSelState* __restrict__ st, float4* __restrict__ cent)
+{
+    const int c = blockIdx.x * 256 + threadIdx.x;
+    const int n_cent = st->n_cent;
+    if (c >= n_cent) return;
+    const int first = heads[c], last = c + 1 < n_cent ? heads[c + 1] : m;
+    float sx = 0.0f, sy = 0.0f, sz = 0.0f;
+    for (int e = first; e < last; e += 8) {
+        float4 p[8];
+#pragma unroll
+        for (int u = 0; u < 8; u++) p[u] = sp[min(e + u, last - 1)];      // (clamped to the run; values past its end not added)
+#pragma unroll
+        for (int u = 0; u < 8; u++)
+            if (e + u < last) { sx += p[u].x; sy += p[u].y; sz += p[u].z; }
+    }
+    const float cnt = (float)(last - first);
+    cent[c] = make_float4(sx / cnt, sy / cnt, sz / cnt, 0.0f);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1025,6 +1187,8 @@ struct VoxWorkspace {
     Buf setup, keys_a, keys_b, vals_a, vals_b, heads, rs_hist, rs_tot, frame_tab, long_list;
     VoxSetup* h_setup = nullptr;          // pinned
     Buf kf_key, kf_ord, kf_cent, kf_nn, kf_st, kf_tab;   // key-frame selection: sort keys, ranks, centroids, their keys, counts, table
+    Buf kf_part, kf_vs, kf_sp;            // ... stores past kKfTile keys: the radius scan's partial boxes and counts, the key-pose filter's
+                                          // setup, the candidate positions in (voxel, rank) order
     KfSelect* h_kf = nullptr;             // pinned
     Buf loop_part;                        // loop detection: one partial minimum per workgroup
     unsigned long long* h_loop = nullptr; // pinned: its result
@@ -1045,7 +1209,7 @@ void vox_destroy(VoxWorkspace* w)
 {
     if (!w) return;
     Buf* bufs[] = { &w->setup, &w->keys_a, &w->keys_b, &w->vals_a, &w->vals_b, &w->heads, &w->rs_hist, &w->rs_tot, &w->frame_tab, &w->long_list,
-                    &w->kf_key, &w->kf_ord, &w->kf_cent, &w->kf_nn, &w->kf_st, &w->kf_tab, &w->loop_part };
+                    &w->kf_key, &w->kf_ord, &w->kf_cent, &w->kf_nn, &w->kf_st, &w->kf_tab, &w->kf_part, &w->kf_vs, &w->kf_sp, &w->loop_part };
     for (Buf* b : bufs) if (b->p) (void)hipFree(b->p);
     if (w->h_setup) (void)hipHostFree(w->h_setup);
     if (w->h_kf) (void)hipHostFree(w->h_kf);
@@ -1161,13 +1325,65 @@ hipError_t vox_copy_records(hipStream_t stream, const unsigned char* d_in, size_
     return hipGetLastError();
 }
 
+namespace {
+
+// stable sort of (key, value) pairs by the whole 32-bit key: three 11-bit passes a -> b -> a -> b (vals_a == nullptr: the value is
+// the pair's position). The result is in keys_b / vals_b.
+void kf_sort32(VoxWorkspace* w, hipStream_t stream, int m, const int32_t* vals_a)
+{
+    const int nblk = (m + kRsTile - 1) / kRsTile;
+    uint32_t* keys_a = w->keys_a.as<uint32_t>(); uint32_t* keys_b = w->keys_b.as<uint32_t>();
+    int32_t* va = w->vals_a.as<int32_t>();       int32_t* vb = w->vals_b.as<int32_t>();
+    int32_t* rs_hist = w->rs_hist.as<int32_t>(); int32_t* rs_tot = w->rs_tot.as<int32_t>();
+    for (int pass = 0; pass < 3; pass++) {
+        const uint32_t* kin = (pass & 1) ? keys_b : keys_a; uint32_t* kout = (pass & 1) ? keys_a : keys_b;
+        const int32_t* vin = pass == 0 ? vals_a : ((pass & 1) ? vb : va); int32_t* vout = (pass & 1) ? va : vb;
+        const int shift = pass * kRsBits;
+        hipLaunchKernelGGL(k_rs_hist<false>, dim3(nblk), dim3(256), 0, stream, kin, m, shift, rs_hist, (const unsigned char*)nullptr,
+                           (size_t)0, (const VoxSetup*)nullptr, (uint32_t*)nullptr);
+        hipLaunchKernelGGL(k_rs_scan_bins, dim3(kRsBins / kScanDigits), dim3(256), 0, stream, rs_hist, nblk, rs_tot);
+        hipLaunchKernelGGL(k_rs_scatter, dim3(nblk), dim3(256), 0, stream, kin, vin, m, shift, nblk, (const int32_t*)rs_hist,
+                           (const int32_t*)rs_tot, kout, vout);
+    }
+}
+
+// (b) and (c) for m > kKfTile radius candidates, left by k_kf_radius_write in keys_a (d2 bits) / vals_a (keys): centroids into
+// kf_cent, their number into st->n_cent. Grids are sized by m (the host has waited for it).
+hipError_t kf_select_wide(VoxWorkspace* w, hipStream_t stream, const float4* d_pos, int m)
+{
+    const int nblk = (m + kRsTile - 1) / kRsTile;
+    VOX_TRY(w->keys_b.ensure(4 * (size_t)m)); VOX_TRY(w->vals_b.ensure(4 * (size_t)m));
+    VOX_TRY(w->heads.ensure(4 * (size_t)m));
+    VOX_TRY(w->kf_sp.ensure(sizeof(float4) * (size_t)m));
+    VOX_TRY(w->rs_hist.ensure(sizeof(int32_t) * (size_t)kRsBins * (size_t)nblk));
+    VOX_TRY(w->rs_tot.ensure(sizeof(int32_t) * (size_t)(kRsBins > nblk ? kRsBins : nblk)));
+    KfSelState* st = w->kf_st.as<KfSelState>();
+    // (b) ascending (d2, key): the keys travel as the values of the d2 sort
+    kf_sort32(w, stream, m, w->vals_a.as<int32_t>());
+    // (c) ranks -> keys and voxel indices (keys_a, free again), then ascending (voxel, rank)
+    hipLaunchKernelGGL(k_kf_vox_keys, dim3((m + 255) / 256), dim3(256), 0, stream, d_pos, (const int32_t*)w->vals_b.as<int32_t>(), m,
+                       (const VoxSetup*)w->kf_vs.as<VoxSetup>(), w->kf_ord.as<int32_t>(), w->keys_a.as<uint32_t>());
+    kf_sort32(w, stream, m, nullptr);
+    hipLaunchKernelGGL(k_heads_count, dim3(nblk), dim3(256), 0, stream, (const uint32_t*)w->keys_b.as<uint32_t>(), m, w->rs_tot.as<int32_t>());
+    hipLaunchKernelGGL(k_heads_write, dim3(nblk), dim3(256), 0, stream, (const uint32_t*)w->keys_b.as<uint32_t>(), m,
+                       (const int32_t*)w->rs_tot.as<int32_t>(), nblk, w->heads.as<int32_t>(), &st->n_cent);
+    hipLaunchKernelGGL(k_kf_gather, dim3((m + 255) / 256), dim3(256), 0, stream, d_pos, (const int32_t*)w->kf_ord.as<int32_t>(),
+                       (const int32_t*)w->vals_b.as<int32_t>(), m, w->kf_sp.as<float4>());
+    hipLaunchKernelGGL(k_kf_centroids, dim3((m + 255) / 256), dim3(256), 0, stream, (const float4*)w->kf_sp.as<float4>(),
+                       (const int32_t*)w->heads.as<int32_t>(), m, (const KfSelState*)st, w->kf_cent.as<float4>());
+    return hipGetLastError();
+}
+
+}  // namespace
+
 hipError_t kf_select(VoxWorkspace* w, hipStream_t stream, const float4* d_pos, const KfFrame* d_frames, int n, int n_recent,
                      float radius, float density, KfSelect* out, KfTable* tab)
 {
     *out = KfSelect{};
     if (n <= 0) return hipSuccess;
+    const bool wide = n > kKfTile;                             // (b) over the whole grid; (c) too when the candidates pass the tile
     size_t P = 1;
-    while (P < (size_t)n) P <<= 1;
+    while (P < (size_t)(wide ? kKfTile : n)) P <<= 1;
     const size_t n_ent = 2 * (size_t)n + 1;                    // centroids (<= n) + recent keys (<= n)
     VOX_TRY(w->kf_key.ensure(sizeof(unsigned long long) * P));
     VOX_TRY(w->kf_ord.ensure(sizeof(int32_t) * (size_t)n));
@@ -1188,15 +1404,43 @@ hipError_t kf_select(VoxWorkspace* w, hipStream_t stream, const float4* d_pos, c
     float4* cent = w->kf_cent.as<float4>();
     int32_t* nn = w->kf_nn.as<int32_t>();
     const float r2 = radius * radius;
-    hipLaunchKernelGGL(k_kf_select_candidates, dim3(1), dim3(kKfThreads), 0, stream, d_pos, n, r2, density,
-                       w->kf_key.as<unsigned long long>(), w->kf_ord.as<int32_t>(), cent, st);
-    hipLaunchKernelGGL(k_kf_select_nearest, dim3((unsigned)(n < 1024 ? n : 1024)), dim3(256), 0, stream, d_pos, n, (const float4*)cent,
-                       (const KfSelState*)st, nn);
-    hipLaunchKernelGGL(k_kf_select_frames, dim3(1), dim3(kKfThreads), 0, stream, d_pos, d_frames, n, n_recent, radius, (const float4*)cent,
-                       (const int32_t*)nn, (const KfSelState*)st, (int32_t*)tab->keys, (const unsigned char**)t, (int32_t*)tab->offsets,
-                       (float*)tab->T, w->h_kf);
+    auto nearest_and_frames = [&]() {
+        hipLaunchKernelGGL(k_kf_select_nearest, dim3((unsigned)(n < 1024 ? n : 1024)), dim3(256), 0, stream, d_pos, n, (const float4*)cent,
+                           (const KfSelState*)st, nn);
+        hipLaunchKernelGGL(k_kf_select_frames, dim3(1), dim3(kKfThreads), 0, stream, d_pos, d_frames, n, n_recent, radius, (const float4*)cent,
+                           (const int32_t*)nn, (const KfSelState*)st, (int32_t*)tab->keys, (const unsigned char**)t, (int32_t*)tab->offsets,
+                           (float*)tab->T, w->h_kf);
+    };
+    if (!wide) {
+        hipLaunchKernelGGL(k_kf_select_candidates<false>, dim3(1), dim3(kKfThreads), 0, stream, d_pos, n, r2, density,
+                           w->kf_key.as<unsigned long long>(), w->kf_ord.as<int32_t>(), cent, st,
+                           (const VoxSetup*)nullptr, (const uint32_t*)nullptr, (const int32_t*)nullptr);
+    } else {
+        const int nblk = (n + kRsTile - 1) / kRsTile;
+        VOX_TRY(w->kf_part.ensure(sizeof(uint32_t) * 8 * (size_t)nblk));
+        VOX_TRY(w->kf_vs.ensure(sizeof(VoxSetup)));
+        VOX_TRY(w->keys_a.ensure(4 * (size_t)n)); VOX_TRY(w->vals_a.ensure(4 * (size_t)n));
+        uint32_t* part = w->kf_part.as<uint32_t>();
+        hipLaunchKernelGGL(k_kf_radius_count, dim3(nblk), dim3(256), 0, stream, d_pos, n, r2, part);
+        hipLaunchKernelGGL(k_vox_setup, dim3(1), dim3(64), 0, stream, w->kf_vs.as<VoxSetup>(), density, (const uint32_t*)part, nblk);
+        hipLaunchKernelGGL(k_kf_radius_write, dim3(nblk), dim3(256), 0, stream, d_pos, n, r2, (const uint32_t*)part,
+                           w->keys_a.as<uint32_t>(), w->vals_a.as<int32_t>());
+        // up to kKfTile candidates: the single-workgroup kernel takes them from here; more: it only reports their number
+        hipLaunchKernelGGL(k_kf_select_candidates<true>, dim3(1), dim3(kKfThreads), 0, stream, d_pos, n, r2, density,
+                           w->kf_key.as<unsigned long long>(), w->kf_ord.as<int32_t>(), cent, st,
+                           (const VoxSetup*)w->kf_vs.as<VoxSetup>(), (const uint32_t*)w->keys_a.as<uint32_t>(),
+                           (const int32_t*)w->vals_a.as<int32_t>());
+    }
+    nearest_and_frames();
     VOX_TRY(hipGetLastError());
     VOX_TRY(hipStreamSynchronize(stream));                   // the one wait: the counts size the transform launch
+    if (wide && w->h_kf->n_cand > kKfTile) {
+        // more candidates than the tile: the pass above chose no centroid; the device-wide sort, then (d) - (f) again (a second wait)
+        VOX_TRY(kf_select_wide(w, stream, d_pos, w->h_kf->n_cand));
+        nearest_and_frames();
+        VOX_TRY(hipGetLastError());
+        VOX_TRY(hipStreamSynchronize(stream));
+    }
     *out = *w->h_kf;
     return hipSuccess;
 }

@@ -53,6 +53,8 @@ struct KfFrame {                           // what the frame table takes from ke
 struct KfSelect {                          // written by the device (pinned host memory)
     int32_t   n_frames;                    // entries of the frame table (= key ids reported)
     int32_t   n_cent;                      // centroids of the key-pose filter
+    int32_t   n_cand;                      // radius candidates
+    int32_t   pad;
     long long n_points;                    // records of the concatenated cloud
 };
 struct KfTable {                           // the frame table, device memory, valid until the next kf_select on the workspace
@@ -63,7 +65,9 @@ struct KfTable {                           // the frame table, device memory, va
 };
 // pos[k] = {x, y, z, 0} of key k, k = 0 .. n-1. n_recent: the newest keys whose time passes the recent-key test (:1000-1007, counted by
 // the caller in double). Chooses the frames (radius search, key-pose voxel filter with leaf `density`, nearest key of every
-// centroid, recent keys, distance filter), writes the table and synchronises `stream` once for the counts.
+// centroid, recent keys, distance filter), writes the table and synchronises `stream` once for the counts. Stores of more than
+// 4 096 keys run the radius search over the whole grid; more than 4 096 candidates are sorted and filtered by device-wide radix
+// passes after a first wait for their number (a second wait). Either way the result is that of the single-workgroup kernel.
 hipError_t kf_select(VoxWorkspace* w, hipStream_t stream, const float4* d_pos, const KfFrame* d_frames, int n, int n_recent,
                      float radius, float density, KfSelect* out, KfTable* tab);
 

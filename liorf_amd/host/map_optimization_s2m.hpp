@@ -141,8 +141,9 @@ public:
     }
 
     // The resident key-frame store (s2m_kf_*): the device keeps every key frame's cloud and pose, so the handler's
-    // extractSurroundingKeyFrames() needs no kd-tree over the key poses and uploads no key-frame cloud. The host copies
-    // (cloudKeyPoses6D, surfCloudKeyFrames) stay for the loop-closure thread and map saving.
+    // extractSurroundingKeyFrames() needs no kd-tree over the key poses and uploads no key-frame cloud. The host copy of
+    // cloudKeyPoses6D stays for the pose graph; surfCloudKeyFrames only for extractCloud() above (the global map and the saved
+    // map come from the store: publishGlobalMap(), globalMapCloud()).
     float surroundingKeyframeDensity = 1.0f;          // include/utility.h:238 (the shipped yaml files set 2.0)
     double timeLaserInfoCur = 0;                      // (:255)
     std::vector<int> surroundingKeyInds;              // the key ids the last extractSurroundingKeyFrames() concatenated
@@ -189,6 +190,51 @@ public:
         v.reserve(6 * cloudKeyPoses6D.size());
         for (const PointTypePose& p : cloudKeyPoses6D) { const float q[6] = { p.x, p.y, p.z, p.roll, p.pitch, p.yaw }; v.insert(v.end(), q, q + 6); }
         check(s2m_kf_set_poses(h_, 0, (int)cloudKeyPoses6D.size(), v.data()), "s2m_kf_set_poses");
+    }
+
+    // The global map and the saved map from the store (s2m_global_map, s2m_kf_map_cloud): visualizeGlobalMapThread() and
+    // saveMapService() need no host copy of surfCloudKeyFrames. Both run under the lock the scan handler holds, for the
+    // whole call; the node still publishes the cloud and writes the PCD files (trajectory.pcd / transformations.pcd from
+    // cloudKeyPoses3D / cloudKeyPoses6D, as before).
+    float globalMapVisualizationSearchRadius = 1e3f;   // include/utility.h:250
+    float globalMapVisualizationPoseDensity = 10.0f;   // include/utility.h:251 (M2DGR.yaml: 3.0)
+    float globalMapVisualizationLeafSize = 1.0f;       // include/utility.h:252
+    std::vector<PointXYZI> globalMapKeyFramesDS;       // what publishGlobalMap() publishes (:500)
+    std::vector<int> globalMapKeyInds;                 // the key ids concatenated into it, in order
+
+    // publishGlobalMap() (:453-502) without the subscriber test and the publish: fills globalMapKeyFramesDS
+    void publishGlobalMap()
+    {
+        s2m_gmap_params p;
+        s2m_gmap_default_params(&p);
+        p.search_radius = globalMapVisualizationSearchRadius;
+        p.pose_density = globalMapVisualizationPoseDensity;
+        p.leaf = globalMapVisualizationLeafSize;
+        globalMapKeyInds.resize(cloudKeyPoses6D.size() + 1);
+        globalMapKeyFramesDS.resize(globalMapKeyFramesDS.capacity());      // the last call's size: one call in the steady state
+        size_t n_out = 0, n_keys = 0;
+        int rc = S2M_OK;
+        for (int attempt = 0; attempt < 2; attempt++) {          // a cloud larger than the buffer: once more with room for it
+            rc = s2m_global_map(h_, &p, globalMapKeyFramesDS.data(), sizeof(PointXYZI), globalMapKeyFramesDS.size(), &n_out,
+                                globalMapKeyInds.data(), globalMapKeyInds.size(), &n_keys);
+            if ((rc != S2M_OK && rc != S2M_ERR_CAPACITY && rc != S2M_WARN_LEAF_TOO_SMALL) || n_out <= globalMapKeyFramesDS.size()) break;
+            globalMapKeyFramesDS.resize(n_out);
+        }
+        checkVoxel(rc, "s2m_global_map");
+        globalMapKeyFramesDS.resize(n_out);
+        globalMapKeyInds.resize(n_keys);
+    }
+
+    // saveMapService()'s clouds (:395-407): globalSurfCloud of keys first .. first+count-1 (resolution 0: GlobalMap.pcd, and
+    // SurfMap.pcd at resolution 0) or its VoxelGrid at `resolution` (SurfMap.pcd)
+    void globalMapCloud(std::vector<PointXYZI>& cloud, float resolution, int first = 0, int count = -1)
+    {
+        if (count < 0) count = (int)cloudKeyPoses6D.size() - first;
+        size_t n = 0;
+        check(s2m_kf_map_cloud(h_, first, count, 0.0f, nullptr, sizeof(PointXYZI), 0, &n), "s2m_kf_map_cloud");   // the size query
+        cloud.resize(n);
+        if (n > 0) checkVoxel(s2m_kf_map_cloud(h_, first, count, resolution, cloud.data(), sizeof(PointXYZI), n, &n), "s2m_kf_map_cloud");
+        cloud.resize(n);
     }
 
     // The reference reads imuType / imuRPYWeight / z_tollerance / rotation_tollerance (ParamServer members, set from

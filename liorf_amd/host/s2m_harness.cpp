@@ -15,6 +15,9 @@
 //   s2m_harness --loop keys.bin keys.txt scan_leaf search_radius search_num icp_leaf fitness_score
 //       a scripted revisit through downsampleCurrentScan() -> saveKeyFrame() -> makeAndSaveScancontextAndKeys() ->
 //       performRSLoopClosure() -> performSCLoopClosure() on the resident key-frame store; prints every loop result.
+//   s2m_harness --global-map keys.bin keys.txt scan_leaf search_radius pose_density leaf out.bin
+//       the key frames through downsampleCurrentScan() -> saveKeyFrame(), then publishGlobalMap() (globalMapKeyFramesDS written
+//       to out.bin) and saveMapService()'s unfiltered cloud; prints the key list and both sizes.
 #include <cstdio>
 #include <cstdlib>
 #include <fstream>
@@ -157,6 +160,45 @@ static int run_loop(char** argv)
     return 0;
 }
 
+// --global-map keys.bin keys.txt scan_leaf search_radius pose_density leaf out.bin: keys.txt as for --loop. Prints
+// "keys <n> k0 k1 ...", "global_map <n>" (the records go to out.bin) and "map_cloud <n>" (globalSurfCloud of all keys).
+static int run_global_map(char** argv)
+{
+    liorf_amd::MapOptimizationS2M node;
+    const std::vector<liorf_amd::PointXYZI> all = read_cloud(argv[2]);
+    std::ifstream tab(argv[3]);
+    if (!tab) throw std::runtime_error(std::string("cannot open ") + argv[3]);
+    node.mappingSurfLeafSize = (float)std::atof(argv[4]);
+    node.globalMapVisualizationSearchRadius = (float)std::atof(argv[5]);
+    node.globalMapVisualizationPoseDensity = (float)std::atof(argv[6]);
+    node.globalMapVisualizationLeafSize = (float)std::atof(argv[7]);
+    size_t n, at = 0;
+    double t;
+    float p[6];
+    while (tab >> n >> t >> p[0] >> p[1] >> p[2] >> p[3] >> p[4] >> p[5]) {
+        if (at + n > all.size()) throw std::runtime_error("keys.txt asks for more points than keys.bin holds");
+        node.timeLaserInfoCur = t;
+        node.laserCloudSurfLast.assign(all.begin() + (std::ptrdiff_t)at, all.begin() + (std::ptrdiff_t)(at + n));
+        at += n;
+        node.downsampleCurrentScan();
+        const float rpyxyz[6] = { p[3], p[4], p[5], p[0], p[1], p[2] };
+        for (int k = 0; k < 6; k++) node.transformTobeMapped[k] = rpyxyz[k];
+        node.saveKeyFrame();
+    }
+    node.publishGlobalMap();
+    std::printf("keys %zu", node.globalMapKeyInds.size());
+    for (int k : node.globalMapKeyInds) std::printf(" %d", k);
+    std::printf("\nglobal_map %zu\n", node.globalMapKeyFramesDS.size());
+    std::ofstream o(argv[8], std::ios::binary);
+    o.write(reinterpret_cast<const char*>(node.globalMapKeyFramesDS.data()),
+            (std::streamsize)(node.globalMapKeyFramesDS.size() * sizeof(liorf_amd::PointXYZI)));
+    if (!o) throw std::runtime_error(std::string("cannot write ") + argv[8]);
+    std::vector<liorf_amd::PointXYZI> cloud;
+    node.globalMapCloud(cloud, 0.0f);
+    std::printf("map_cloud %zu\n", cloud.size());
+    return 0;
+}
+
 // --many map.bin roll pitch yaw x y z scan0.bin scan1.bin ...: the same initial guess for every scan; the scans once as a batch
 // (scan2MapOptimizationBatch), once as a stream through two slots (prepareNextScan / launchSlot / collectSlot), once one by one
 // (scan2MapOptimization): prints "batch|stream|single <i> iters <n> pose ..." - the three must agree bit for bit.
@@ -206,6 +248,7 @@ int main(int argc, char** argv)
         if (argc >= 10 && std::string(argv[1]) == "--many") return run_many(argc, argv);
         if (argc == 7 && std::string(argv[1]) == "--keyframes") return run_keyframes(argv);
         if (argc == 9 && std::string(argv[1]) == "--loop") return run_loop(argv);
+        if (argc == 9 && std::string(argv[1]) == "--global-map") return run_global_map(argv);
         if (argc != 9 && argc != 16) {
             std::fprintf(stderr, "usage: %s map.bin scan.bin roll pitch yaw x y z [imuType imuRPYWeight z_tol rot_tol imuAvailable imuRoll imuPitch]\n", argv[0]);
             return 2;

@@ -38,6 +38,7 @@ ABI_SYMBOLS = [
     "s2m_sc_reset", "s2m_sc_size", "s2m_sc_add_scan", "s2m_sc_add_descriptor", "s2m_sc_detect_loop", "s2m_sc_distance",
     "s2m_kf_default_params", "s2m_kf_reset", "s2m_kf_size", "s2m_kf_add", "s2m_kf_set_poses", "s2m_extract_surrounding",
     "s2m_loop_default_params", "s2m_loop_near_keyframes", "s2m_loop_align", "s2m_loop_closure_rs",
+    "s2m_gmap_default_params", "s2m_global_map", "s2m_kf_map_cloud",
 ]
 S2M_KF_FROM_HOST, S2M_KF_FROM_DEVICE, S2M_KF_FROM_LAST_DOWNSAMPLE = 0, 1, 2
 S2M_LOOP_NONE, S2M_LOOP_ALREADY_CLOSED, S2M_LOOP_TOO_FEW_POINTS, S2M_LOOP_REJECTED, S2M_LOOP_ACCEPTED = 0, 1, 2, 3, 4
@@ -95,6 +96,10 @@ class LoopParams(C.Structure):
 class LoopResult(C.Structure):
     _fields_ = [("status", C.c_int32), ("key_cur", C.c_int32), ("key_pre", C.c_int32), ("n_cur", C.c_int32),
                 ("n_prev", C.c_int32), ("icp", IcpResult), ("pose_from", C.c_float * 6), ("pose_to", C.c_float * 6)]
+
+
+class GmapParams(C.Structure):
+    _fields_ = [("search_radius", C.c_float), ("pose_density", C.c_float), ("leaf", C.c_float)]
 
 
 class S2MError(RuntimeError):
@@ -197,6 +202,9 @@ def load_library(path: str | None = None) -> C.CDLL:
     L.s2m_loop_near_keyframes.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, C.c_float, vp, C.c_size_t, C.c_size_t, szp]
     L.s2m_loop_align.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, C.POINTER(LoopParams), C.POINTER(LoopResult)]
     L.s2m_loop_closure_rs.argtypes = [vp, C.c_double, C.POINTER(LoopParams), C.POINTER(LoopResult)]
+    L.s2m_gmap_default_params.argtypes = [C.POINTER(GmapParams)]
+    L.s2m_global_map.argtypes = [vp, C.POINTER(GmapParams), vp, C.c_size_t, C.c_size_t, szp, i32p, C.c_size_t, szp]
+    L.s2m_kf_map_cloud.argtypes = [vp, C.c_int, C.c_int, C.c_float, vp, C.c_size_t, C.c_size_t, szp]
     if path is None:
         _LIB = L
     return L
@@ -684,6 +692,50 @@ class MapOptimizationS2M:
         run(out.ctypes.data, m.value)                 # (the same selection again: deterministic, same map)
         return k, out[:m.value]
 
+    # -- the global map and the saved map from the resident store (reference :453-502, :375-432) --------
+    def publishGlobalMap(self, params: GmapParams | None = None, return_keys: bool = False):
+        """publishGlobalMap() (reference :453-502) on the resident store: globalMapKeyFramesDS as (m, 8) float32 records;
+        with return_keys also the key id of every frame concatenated into it, in order."""
+        pp = C.byref(params) if params is not None else None
+        n = max(self.kfSize(), 0)
+        keys = np.zeros(max(n, 1), np.int32)
+        m, nk = C.c_size_t(0), C.c_size_t(0)
+        out = getattr(self, "_gmap_buf", None)
+        if out is None:
+            out = np.zeros((1, 8), np.float32)
+        for _ in range(2):                            # a buffer too small for this call: grown to the count, and once more
+            rc = self.lib.s2m_global_map(self.h, pp, out.ctypes.data, 32, out.shape[0], C.byref(m),
+                                         keys.ctypes.data_as(C.POINTER(C.c_int32)), keys.size, C.byref(nk))
+            if rc not in (S2M_OK, S2M_ERR_CAPACITY, S2M_WARN_LEAF_TOO_SMALL) or m.value <= out.shape[0]:
+                break
+            out = np.zeros((m.value, 8), np.float32)
+        self._gmap_buf = out
+        self.leaf_too_small = self._check_voxel(rc, "s2m_global_map")
+        cloud = out[:m.value].copy()
+        return (cloud, keys[:nk.value].copy()) if return_keys else cloud
+
+    def globalMapCloud(self, first: int = 0, count: int | None = None, leaf: float = 0.0) -> np.ndarray:
+        """saveMapService()'s globalSurfCloud (reference :395-398) for keys first .. first + count - 1, and with leaf > 0
+        its downSizeFilterSurf at that resolution (:400-407): (m, 8) float32 records."""
+        if count is None:
+            count = max(self.kfSize(), 0) - first
+        m = C.c_size_t(0)
+        if leaf == 0.0:
+            self._check(self.lib.s2m_kf_map_cloud(self.h, first, count, 0.0, None, 32, 0, C.byref(m)), "s2m_kf_map_cloud")
+            out = np.zeros((max(m.value, 1), 8), np.float32)
+            if m.value:
+                self._check(self.lib.s2m_kf_map_cloud(self.h, first, count, 0.0, out.ctypes.data, 32, m.value, C.byref(m)),
+                            "s2m_kf_map_cloud")
+            self.leaf_too_small = False
+            return out[:m.value]
+        # filtered: the voxel count is known only after the filter; room for the unfiltered count never falls short
+        self._check(self.lib.s2m_kf_map_cloud(self.h, first, count, 0.0, None, 32, 0, C.byref(m)), "s2m_kf_map_cloud")
+        out = np.zeros((max(m.value, 1), 8), np.float32)
+        self.leaf_too_small = self._check_voxel(
+            self.lib.s2m_kf_map_cloud(self.h, first, count, float(leaf), out.ctypes.data, 32, out.shape[0], C.byref(m)),
+            "s2m_kf_map_cloud")
+        return out[:m.value]
+
     # -- loop closure against the resident key-frame store (reference :542-844) ----------------------
     def loopFindNearKeyframes(self, key: int, searchNum: int, loop_index: int = -1, leaf: float = 0.3) -> np.ndarray:
         """loopFindNearKeyframes(nearKeyframes, key, searchNum, loop_index) (reference :821-844) with downSizeFilterICP's
@@ -738,6 +790,14 @@ def default_kf_params(**kw) -> KfParams:
 def default_loop_params(**kw) -> LoopParams:
     p = LoopParams()
     load_library().s2m_loop_default_params(C.byref(p))
+    for k, v in kw.items():
+        setattr(p, k, v)
+    return p
+
+
+def default_gmap_params(**kw) -> GmapParams:
+    p = GmapParams()
+    load_library().s2m_gmap_default_params(C.byref(p))
     for k, v in kw.items():
         setattr(p, k, v)
     return p
