@@ -319,6 +319,116 @@ int  s2m_global_map(s2m_handle h, const s2m_gmap_params* p /* NULL = defaults */
 int  s2m_kf_map_cloud(s2m_handle h, int first, int count, float leaf /* 0 = no filter */,
                       void* out, size_t out_stride_bytes, size_t cap, size_t* n_out);
 
+/* ---- imageProjection's point filter and IMU deskew (reference src/imageProjection.cpp) ---------------------
+ * projectPointCloud() (:568-598) with deskewPoint() (:536-566) and findRotation() (:493-518) on the raw records of one
+ * lidar message, and the host half that prepares it, imuDeskewInfo() (:350-409). The raw bytes of a
+ * sensor_msgs::PointCloud2 (or of the reference's PCL structs, :4-57) are read in place through an s2m_scan_layout, so the
+ * per-sensor conversion loops (:216-274) have no counterpart. Citations below are into src/imageProjection.cpp.
+ *
+ * A record i survives when, in this order and with these types,
+ *   range = sqrtf((x*x + y*y) + z*z) is not < lidar_min_range and not > lidar_max_range (a NaN range survives, :581),
+ *   0 <= ring < n_scan (:585; ring as int: an i32 ring is taken as it is, the reference narrows it to uint16_t first),
+ *   ring % downsample_rate == 0 (:588), i % point_filter_num == 0 (:591).
+ * Survivors keep index order. With deskew == 0 a survivor is copied (:538-539). Otherwise, per survivor:
+ *   pointTime = time_scan_cur + (double)time (:541), time being the record's time field converted as time_type says;
+ *   findRotation() as written: front = the first table index in [0, imu_pointer_cur) with pointTime < imu_time[front], else
+ *     imu_pointer_cur; pointTime > imu_time[front] or front == 0 copies entry front; otherwise the two ratios and the
+ *     two-term sums in double, narrowed to float (a point time equal to the last table time therefore interpolates with
+ *     ratio 1, and front == 0 copies entry 0);
+ *   R = pcl::getTransformation(0, 0, 0, rotX, rotY, rotZ) in float with the host libm's sinf / cosf;
+ *   S = inverse(R of the first survivor) (transStartInverse, :551); B = S * R; the output is
+ *     ((B00*x + B01*y) + B02*z) + B03 and so on (:560-562), intensity copied, the record's other 4-byte slots zero.
+ *   [ext] Eigen 3.3 Transform<float,3,Affine>::inverse() is the general 3x3 inverse: Linv(r, c) = cofactor(c, r) * (1 / det)
+ *     with cofactor(i, j) = m(i+1, j+1) * m(i+2, j+2) - m(i+1, j+2) * m(i+2, j+1) (indices mod 3) and
+ *     det = (cof(0,0)*m00 + cof(1,0)*m10) + cof(2,0)*m20, translation -(Linv * t) - not the transpose.
+ *   [ext] the 4x4 product accumulates ((a0*b0 + a1*b1) + a2*b2) + a3*b3 without contraction (the reference builds with -O3
+ *     only). The translation column is kept and added although findPosition() returns zeros: it decides the sign of a zero.
+ *     The particular doubt: Eigen 3.3's transform_transform_product_impl for two Affine (non-projective) transforms may
+ *     instead form linear = L * L (three terms per entry) and translation = L * t + t. With R's zero translation and
+ *     (0, 0, 0, 1) bottom row the extra terms are signed zeros, so the two forms can differ only in the sign of a zero
+ *     entry of B. Eigen is not available to this repository; this stays unpinned.
+ * Output records are 32 bytes on the device (pcl::PointXYZI): the handle's cloud_deskewed, which stays resident with its
+ * count for s2m_downsample_projected / s2m_sc_add_projected. */
+#define S2M_RING_U8        0
+#define S2M_RING_U16       1
+#define S2M_RING_I32       2
+#define S2M_TIME_F32       0   /* float, as stored (Velodyne, Livox :216-219)                                   */
+#define S2M_TIME_U32_NS    1   /* uint32 t: (float)t * 1e-9f, the product in float (Ouster :235)               */
+#define S2M_TIME_U32       2   /* uint32 t: (float)t (MulRan :253)                                              */
+#define S2M_TIME_F64_REL   3   /* double timestamp: (float)(timestamp - timestamp of record 0) (Robosense :263, :272) */
+#define S2M_SENSOR_VELODYNE  0
+#define S2M_SENSOR_LIVOX     1
+#define S2M_SENSOR_OUSTER    2
+#define S2M_SENSOR_MULRAN    3
+#define S2M_SENSOR_ROBOSENSE 4
+#define S2M_IMU_QUEUE_LENGTH 2000   /* queueLength (:62): entries of the four deskew tables */
+typedef struct s2m_scan_layout {
+    uint32_t stride;          /* bytes per record (PointCloud2.point_step)                                      */
+    uint32_t off_x;           /* byte offset of float x; y and z follow                                         */
+    uint32_t off_intensity;   /* float intensity                                                                */
+    uint32_t off_ring;
+    uint32_t off_time;
+    int32_t  ring_type;       /* S2M_RING_*                                                                     */
+    int32_t  time_type;       /* S2M_TIME_*                                                                     */
+} s2m_scan_layout;
+/* The reference's own structs (:4-57): Velodyne / Livox 32 bytes (intensity 16, ring u16 20, time f32 24), Ouster 48
+ * (intensity 16, t u32 20, ring u8 26), MulRan 32 (t u32 20, ring i32 24), Robosense 32 (ring u16 20, timestamp f64 24).
+ * A layout is valid when every field lies inside the stride and is naturally aligned (offset and stride multiples of
+ * the field's size); everything else is S2M_ERR_INVALID_ARG, from every call that takes a layout. */
+int  s2m_scan_layout_preset(int32_t sensor, s2m_scan_layout* out);
+typedef struct s2m_project_params {
+    int32_t n_scan;            /* N_SCAN 16              include/utility.h:204 */
+    int32_t downsample_rate;   /* downsampleRate 1       include/utility.h:206 */
+    int32_t point_filter_num;  /* point_filter_num 3     include/utility.h:207 */
+    float   lidar_min_range;   /* lidarMinRange 1.0      include/utility.h:208 */
+    float   lidar_max_range;   /* lidarMaxRange 1000.0   include/utility.h:209 */
+} s2m_project_params;
+int  s2m_project_default_params(s2m_project_params* p);
+/* imuDeskewInfo() (:350-409) without the queue and without the imuType RPY lines: imu holds n samples {time, wx, wy, wz}
+ * (doubles; already through imuConverter, already popped to time_scan_cur - 0.01). Fills the four tables (room for
+ * S2M_IMU_QUEUE_LENGTH entries each) with the reference's double arithmetic, its break at > time_scan_end + 0.01 and its
+ * final --imuPointerCur; *imu_available = imuPointerCur > 0. n == 0 gives pointer 0, not available. More than
+ * S2M_IMU_QUEUE_LENGTH used samples: S2M_ERR_CAPACITY (the reference would write past its arrays). Host code: no handle,
+ * no GPU. */
+int  s2m_imu_deskew_info(const double* imu, size_t n, double time_scan_cur, double time_scan_end,
+                         double* imu_time, double* imu_rot_x, double* imu_rot_y, double* imu_rot_z,
+                         int32_t* imu_pointer_cur, int32_t* imu_available);
+typedef struct s2m_deskew_info {
+    double  time_scan_cur;     /* timeScanCur (:282)                                                            */
+    int32_t deskew;            /* deskewFlag == 1 && cloudInfo.imuAvailable; 0 copies the survivors             */
+    int32_t imu_pointer_cur;   /* imuPointerCur after imuDeskewInfo(): the tables hold imu_pointer_cur + 1 entries */
+    const double* imu_time;
+    const double* imu_rot_x;
+    const double* imu_rot_y;
+    const double* imu_rot_z;
+} s2m_deskew_info;
+/* The argument checks of s2m_project_scan on their own (host code, no handle, no GPU): S2M_OK or S2M_ERR_INVALID_ARG.
+ * params and deskew may be NULL (defaults, no deskew). Why it is part of the boundary: s2m_project_scan answers a null
+ * handle with the same S2M_ERR_INVALID_ARG, so on a machine without a GPU (no handle can be created there) a caller - a
+ * node validating its yaml and message fields at start-up, or a test - could not tell a refused layout from a refused
+ * handle through s2m_project_scan alone. */
+int  s2m_project_check_args(const s2m_scan_layout* layout, const s2m_project_params* params, const s2m_deskew_info* deskew);
+/* projectPointCloud() on records `pts` (host bytes, or device bytes when on_device != 0; 8-byte aligned). With
+ * deskew->deskew != 0 the table times must be non-decreasing and 1 <= imu_pointer_cur < S2M_IMU_QUEUE_LENGTH, else
+ * S2M_ERR_INVALID_ARG (for non-decreasing times the reference's linear walk and the device's bisection find the same
+ * index; nothing else is promised). params: downsample_rate < 1, point_filter_num < 1, n_scan < 1 or a non-finite range
+ * are S2M_ERR_INVALID_ARG (the reference would divide by zero); NULL = defaults. deskew NULL = no deskew.
+ * The result stays on the device as cloud_deskewed; cap > 0 also copies it to host `out` (out_stride >= 12, a multiple
+ * of 4); *n_out is always the full count; a short `out` gets cap records and S2M_ERR_CAPACITY. n == 0 or no survivor:
+ * S2M_OK, count 0, cloud_deskewed empty and valid. Three launches; the host waits once, for the count (and for the kernels
+ * to have left `pts`), and with cap > 0 a second time for the copy. The call does not touch the map and its index, the
+ * scan, scan_ds, the pose, the slots, the key store, the ScanContext store or the loop container. */
+int  s2m_project_scan(s2m_handle h, const void* pts, size_t n, const s2m_scan_layout* layout, int on_device,
+                      const s2m_project_params* params, const s2m_deskew_info* deskew,
+                      void* out, size_t out_stride_bytes, size_t cap, size_t* n_out);
+/* downsampleCurrentScan() on the resident cloud_deskewed: exactly s2m_downsample_scan(on_device = 1) on that buffer (same
+ * scan_ds, same installed scan, same warnings). S2M_ERR_NO_SCAN before the first s2m_project_scan. */
+int  s2m_downsample_projected(s2m_handle h, float leaf, void* out, size_t out_stride_bytes, size_t cap, size_t* n_out);
+/* makeAndSaveScancontextAndKeys(cloud_deskewed) (src/mapOptmization.cpp:1591-1594) from the resident buffer: the stored
+ * descriptor and keys are those of s2m_sc_add_scan on the downloaded cloud. S2M_ERR_NO_SCAN before the first
+ * s2m_project_scan. */
+int  s2m_sc_add_projected(s2m_handle h);
+
 /* ---- ScanContext descriptor (BASELINE config 5) ------------------------- */
 /* SCManager::makeScancontext + makeRingkeyFromScancontext
  * (reference include/Scancontext.cpp:151-211): desc is 20x60 row-major doubles,

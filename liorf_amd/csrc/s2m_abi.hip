@@ -22,6 +22,7 @@
 #include "s2m_kernels.hpp"
 #include "s2m_voxel.hpp"
 #include "s2m_icp.hpp"
+#include "s2m_project.hpp"
 
 using namespace s2m;
 
@@ -78,6 +79,12 @@ struct s2m_context {
     // two staging buffers that take turns, a copy stream and its events)
     DevBuf map_xf, map_out, map_tab, map_stage[2];
     hipStream_t map_copy_stream = nullptr;
+    // imageProjection's filter and deskew (s2m_project_scan): staging of host records, the survivor masks, the per-workgroup
+    // counts, the IMU table, transStartInverse, and cloud_deskewed - the resident result the next stages read
+    DevBuf proj_in, proj_mask, proj_part, proj_table, proj_start, cloud_deskewed;
+    size_t deskewed_n = 0;
+    bool have_deskewed = false;
+    ProjCount* h_proj = nullptr;       // pinned: the count, written by the device
     hipEvent_t map_ev_xf[2] = { nullptr, nullptr }, map_ev_cp[2] = { nullptr, nullptr };
 
     DevCtx hctx{};
@@ -775,16 +782,19 @@ int sc_append_from_out(s2m_context* h)
 }
 
 // SCManager::makeScancontext + ring key of a host cloud into h->sc_out (device)
-int sc_build_descriptor(s2m_context* h, const void* pts, size_t n, size_t stride_bytes)
+int sc_build_descriptor(s2m_context* h, const void* pts, size_t n, size_t stride_bytes, bool on_device = false)
 {
     S2M_HIP(h, hipMemsetAsync(h->sc_bins.p, 0, sizeof(uint32_t) * kScDesc, h->stream));
     if (n > 0) {
-        int rc = ensure(h, h->raw_scan, n * stride_bytes);
-        if (rc) return rc;
-        S2M_HIP(h, hipMemcpyAsync(h->raw_scan.p, pts, n * stride_bytes, hipMemcpyHostToDevice, h->stream));
+        const unsigned char* d_pts = static_cast<const unsigned char*>(pts);
+        if (!on_device) {
+            int rc = ensure(h, h->raw_scan, n * stride_bytes);
+            if (rc) return rc;
+            S2M_HIP(h, hipMemcpyAsync(h->raw_scan.p, pts, n * stride_bytes, hipMemcpyHostToDevice, h->stream));
+            d_pts = h->raw_scan.as<unsigned char>();
+        }
         const int blocks = std::min((int)((n + 255) / 256), 1024);
-        hipLaunchKernelGGL(k_sc_polar_max, dim3(blocks), dim3(256), 0, h->stream,
-                           (const unsigned char*)h->raw_scan.as<unsigned char>(), stride_bytes, (int)n, h->sc_bins.as<uint32_t>());
+        hipLaunchKernelGGL(k_sc_polar_max, dim3(blocks), dim3(256), 0, h->stream, d_pts, stride_bytes, (int)n, h->sc_bins.as<uint32_t>());
     }
     hipLaunchKernelGGL(k_sc_finish, dim3(1), dim3(64), 0, h->stream, (const uint32_t*)h->sc_bins.as<uint32_t>(),
                        h->sc_out.as<double>(), h->sc_out.as<double>() + kScDesc);
@@ -918,7 +928,8 @@ int s2m_destroy(s2m_handle h)
                        &h->dbg_idx5, &h->dbg_d2, &h->dbg_flag, &h->dbg_coeff, &h->dbg_clk, &h->sc_bins, &h->sc_out,
                        &h->vox_in, &h->vox_out, &h->frames_xf, &h->scan_ds, &h->map_ds,
                        &h->sc_store_desc, &h->sc_store_ring, &h->sc_store_sector, &h->sc_cand, &h->sc_res,
-                       &h->loop_xf, &h->loop_cur, &h->loop_prev, &h->map_xf, &h->map_out, &h->map_tab, &h->map_stage[0], &h->map_stage[1] };
+                       &h->loop_xf, &h->loop_cur, &h->loop_prev, &h->map_xf, &h->map_out, &h->map_tab, &h->map_stage[0], &h->map_stage[1],
+                       &h->proj_in, &h->proj_mask, &h->proj_part, &h->proj_table, &h->proj_start, &h->cloud_deskewed };
     for (DevBuf* b : bufs) if (b->p) (void)hipFree(b->p);
     if (h->map_copy_stream) { (void)hipStreamSynchronize(h->map_copy_stream); (void)hipStreamDestroy(h->map_copy_stream); }
     for (int k = 0; k < 2; k++) {
@@ -936,6 +947,7 @@ int s2m_destroy(s2m_handle h)
     if (h->h_state) (void)hipHostFree(h->h_state);
     if (h->h_mm) (void)hipHostFree(h->h_mm);
     if (h->h_sc) (void)hipHostFree(h->h_sc);
+    if (h->h_proj) (void)hipHostFree(h->h_proj);
     if (h->ev_a) (void)hipEventDestroy(h->ev_a);
     if (h->ev_b) (void)hipEventDestroy(h->ev_b);
     if (h->ev_a2) (void)hipEventDestroy(h->ev_a2);
@@ -2573,6 +2585,127 @@ int s2m_sc_distance(s2m_handle h, int32_t query_idx, const int32_t* cand_idx, in
     S2M_HIP(h, hipGetLastError());
     S2M_HIP(h, hipMemcpyAsync(dist, base + off_d, sizeof(double) * (size_t)m, hipMemcpyDeviceToHost, h->stream));
     S2M_HIP(h, hipMemcpyAsync(shift, base + off_s, sizeof(int32_t) * (size_t)m, hipMemcpyDeviceToHost, h->stream));
+    S2M_HIP(h, hipStreamSynchronize(h->stream));
+    return S2M_OK;
+}
+
+// ---- imageProjection's point filter and IMU deskew (reference src/imageProjection.cpp:350-409, :493-598) ---------------
+
+int s2m_scan_layout_preset(int32_t sensor, s2m_scan_layout* out)
+{
+    if (!out) return S2M_ERR_INVALID_ARG;
+    switch (sensor) {                                     // the reference's point structs (:4-57)
+        case S2M_SENSOR_VELODYNE: case S2M_SENSOR_LIVOX: *out = s2m_scan_layout{ 32, 0, 16, 20, 24, S2M_RING_U16, S2M_TIME_F32 }; return S2M_OK;
+        case S2M_SENSOR_OUSTER:    *out = s2m_scan_layout{ 48, 0, 16, 26, 20, S2M_RING_U8, S2M_TIME_U32_NS }; return S2M_OK;
+        case S2M_SENSOR_MULRAN:    *out = s2m_scan_layout{ 32, 0, 16, 24, 20, S2M_RING_I32, S2M_TIME_U32 }; return S2M_OK;
+        case S2M_SENSOR_ROBOSENSE: *out = s2m_scan_layout{ 32, 0, 16, 20, 24, S2M_RING_U16, S2M_TIME_F64_REL }; return S2M_OK;
+        default: return S2M_ERR_INVALID_ARG;
+    }
+}
+
+int s2m_project_default_params(s2m_project_params* p)
+{
+    if (!p) return S2M_ERR_INVALID_ARG;
+    p->n_scan = 16; p->downsample_rate = 1; p->point_filter_num = 3;         // include/utility.h:204-207
+    p->lidar_min_range = 1.0f; p->lidar_max_range = 1000.0f;                 // include/utility.h:208-209
+    return S2M_OK;
+}
+
+int s2m_imu_deskew_info(const double* imu, size_t n, double time_scan_cur, double time_scan_end, double* imu_time, double* imu_rot_x,
+                        double* imu_rot_y, double* imu_rot_z, int32_t* imu_pointer_cur, int32_t* imu_available)
+{
+    if ((n > 0 && !imu) || !imu_time || !imu_rot_x || !imu_rot_y || !imu_rot_z || !imu_pointer_cur || !imu_available) return S2M_ERR_INVALID_ARG;
+    return proj_imu_deskew_info(imu, n, time_scan_cur, time_scan_end, imu_time, imu_rot_x, imu_rot_y, imu_rot_z, imu_pointer_cur, imu_available);
+}
+
+int s2m_project_check_args(const s2m_scan_layout* layout, const s2m_project_params* params, const s2m_deskew_info* deskew)
+{
+    if (!layout || !proj_layout_ok(*layout)) return S2M_ERR_INVALID_ARG;
+    if (params && !proj_params_ok(*params)) return S2M_ERR_INVALID_ARG;
+    if (deskew && !proj_deskew_ok(*deskew)) return S2M_ERR_INVALID_ARG;
+    return S2M_OK;
+}
+
+int s2m_project_scan(s2m_handle h, const void* pts, size_t n, const s2m_scan_layout* layout, int on_device, const s2m_project_params* params,
+                     const s2m_deskew_info* deskew, void* out, size_t out_stride_bytes, size_t cap, size_t* n_out)
+{
+    if (s2m_project_check_args(layout, params, deskew) != S2M_OK)
+        return fail(h, S2M_ERR_INVALID_ARG, "scan layout (fields inside the stride, naturally aligned), project params (n_scan, downsample_rate, "
+                                            "point_filter_num >= 1, finite ranges) or deskew tables (1 <= imu_pointer_cur < 2000, non-decreasing times)");
+    s2m_project_params prm;
+    if (params) prm = *params; else s2m_project_default_params(&prm);
+    if (!n_out || (cap > 0 && (!out || out_stride_bytes < 12 || (out_stride_bytes & 3)))) return fail(h, S2M_ERR_INVALID_ARG, "bad output buffer");
+    *n_out = 0;
+    if (!h) return S2M_ERR_INVALID_ARG;
+    if (n > 0 && !pts) return fail(h, S2M_ERR_INVALID_ARG, "null record buffer");
+    if (on_device && (reinterpret_cast<uintptr_t>(pts) & 7) != 0) return fail(h, S2M_ERR_INVALID_ARG, "device records must be 8-byte aligned");
+    if (n > (size_t)0x3fffffff) return fail(h, S2M_ERR_CAPACITY, "too many records");
+    S2M_HIP(h, hipSetDevice(h->device));
+    if (!h->h_proj) S2M_HIP(h, hipHostMalloc((void**)&h->h_proj, 64));
+    const int do_deskew = (deskew && deskew->deskew) ? 1 : 0;
+    h->have_deskewed = false;
+    h->deskewed_n = 0;
+    int rc;
+    if ((rc = ensure(h, h->cloud_deskewed, kProjOutStride))) return rc;      // empty and valid
+    if (n == 0) { h->have_deskewed = true; return S2M_OK; }
+
+    const size_t ub = (n + (size_t)prm.point_filter_num - 1) / (size_t)prm.point_filter_num;      // survivors pass i % point_filter_num == 0
+    if ((rc = ensure(h, h->cloud_deskewed, kProjOutStride * ub)) || (rc = ensure(h, h->proj_mask, proj_mask_bytes(n))) ||
+        (rc = ensure(h, h->proj_part, proj_part_bytes(n))) || (rc = ensure(h, h->proj_table, kProjTableBytes)) ||
+        (rc = ensure(h, h->proj_start, kProjStartBytes))) return rc;
+    ProjArgs a{};
+    a.d_in = static_cast<const unsigned char*>(pts);
+    if (!on_device) {
+        const size_t bytes = n * (size_t)layout->stride;
+        if ((rc = ensure(h, h->proj_in, bytes))) return rc;
+        S2M_HIP(h, hipMemcpyAsync(h->proj_in.p, pts, bytes, hipMemcpyHostToDevice, h->stream));
+        a.d_in = h->proj_in.as<unsigned char>();
+    }
+    if (do_deskew) {
+        const size_t m = sizeof(double) * (size_t)(deskew->imu_pointer_cur + 1);
+        double* t = h->proj_table.as<double>();
+        S2M_HIP(h, hipMemcpyAsync(t, deskew->imu_time, m, hipMemcpyHostToDevice, h->stream));
+        S2M_HIP(h, hipMemcpyAsync(t + S2M_IMU_QUEUE_LENGTH, deskew->imu_rot_x, m, hipMemcpyHostToDevice, h->stream));
+        S2M_HIP(h, hipMemcpyAsync(t + 2 * S2M_IMU_QUEUE_LENGTH, deskew->imu_rot_y, m, hipMemcpyHostToDevice, h->stream));
+        S2M_HIP(h, hipMemcpyAsync(t + 3 * S2M_IMU_QUEUE_LENGTH, deskew->imu_rot_z, m, hipMemcpyHostToDevice, h->stream));
+    }
+    a.n = n; a.lay = *layout; a.prm = prm; a.deskew = do_deskew;
+    a.imu_pointer_cur = do_deskew ? deskew->imu_pointer_cur : 0;
+    a.time_scan_cur = deskew ? deskew->time_scan_cur : 0.0;
+    a.d_table = h->proj_table.as<double>();
+    a.d_mask = h->proj_mask.as<unsigned long long>();
+    a.d_part = h->proj_part.as<int32_t>();
+    a.d_start = h->proj_start.as<float>();
+    a.d_out = h->cloud_deskewed.as<unsigned char>();
+    a.h_count = h->h_proj;
+    hipError_t e = proj_launch(h->stream, a);
+    if (e != hipSuccess) return fail(h, S2M_ERR_HIP, "point filter and deskew", e);
+    // the one wait: the count is in pinned memory and the kernels have left the caller's records (host or device)
+    S2M_HIP(h, hipStreamSynchronize(h->stream));
+    const size_t cnt = (size_t)h->h_proj->n_out;
+    *n_out = cnt;
+    h->deskewed_n = cnt;
+    h->have_deskewed = true;
+    if (cap > 0 && (rc = download_records(h, h->cloud_deskewed, cnt, out, out_stride_bytes, cap))) return rc;
+    if (cap > 0 && cnt > cap) return fail(h, S2M_ERR_CAPACITY, "output buffer too small for the deskewed cloud");
+    return S2M_OK;
+}
+
+int s2m_downsample_projected(s2m_handle h, float leaf, void* out, size_t out_stride_bytes, size_t cap, size_t* n_out)
+{
+    if (!h) return S2M_ERR_INVALID_ARG;
+    if (!h->have_deskewed) return fail(h, S2M_ERR_NO_SCAN, "s2m_downsample_projected before s2m_project_scan");
+    return s2m_downsample_scan(h, h->cloud_deskewed.p, h->deskewed_n, kProjOutStride, 1, leaf, out, out_stride_bytes, cap, n_out);
+}
+
+int s2m_sc_add_projected(s2m_handle h)
+{
+    if (!h) return S2M_ERR_INVALID_ARG;
+    if (!h->have_deskewed) return fail(h, S2M_ERR_NO_SCAN, "s2m_sc_add_projected before s2m_project_scan");
+    S2M_HIP(h, hipSetDevice(h->device));
+    int rc;
+    if ((rc = sc_build_descriptor(h, h->cloud_deskewed.p, h->deskewed_n, kProjOutStride, true))) return rc;
+    if ((rc = sc_append_from_out(h))) return rc;
     S2M_HIP(h, hipStreamSynchronize(h->stream));
     return S2M_OK;
 }

@@ -106,6 +106,25 @@ public:
         scanResident_ = true;
     }
 
+    // downsampleCurrentScan() on the cloud_deskewed an ImageProjectionS2M::projectPointCloud() left on this handle's device: no
+    // deskewed cloud crosses the bus. cloudDeskewedNum is that projection's count (ImageProjectionS2M::fullCloudNum): the filter
+    // never returns more points than it was given, so it sizes laserCloudSurfLastDS the way laserCloudSurfLast.size() does in
+    // downsampleCurrentScan(). With readback off laserCloudSurfLastDS is left empty (the scan is resident; saveKeyFrame() would
+    // store an empty host cloud) and only laserCloudSurfLastDSNum is set.
+    void downsampleCurrentScanProjected(size_t cloudDeskewedNum, bool readback = true)
+    {
+        size_t n_out = 0;
+        laserCloudSurfLastDS.resize(readback ? cloudDeskewedNum : 0);
+        checkVoxel(s2m_downsample_projected(h_, mappingSurfLeafSize, readback ? laserCloudSurfLastDS.data() : nullptr, sizeof(PointXYZI),
+                                            laserCloudSurfLastDS.size(), &n_out), "s2m_downsample_projected");
+        if (readback) {
+            if (n_out > laserCloudSurfLastDS.size()) throw std::runtime_error("s2m_downsample_projected: cloudDeskewedNum is not the projection's count");
+            laserCloudSurfLastDS.resize(n_out);
+        }
+        laserCloudSurfLastDSNum = (int)n_out;
+        scanResident_ = true;
+    }
+
     // void extractCloud(cloudToExtract) (:1014-1039): `keyInds` are the key-frame ids the caller's radius
     // search and time filter chose (extractNearby, :973-1012). Frames farther than
     // surroundingKeyframeSearchRadius from the newest key pose are dropped (:1018), the rest are transformed
@@ -417,6 +436,8 @@ public:
     {
         check(s2m_sc_add_scan(h_, scan_down.data(), scan_down.size(), sizeof(PointXYZI)), "s2m_sc_add_scan");
     }
+    // makeAndSaveScancontextAndKeys(cloud_deskewed) at key-frame save (src/mapOptmization.cpp:1591-1594) from the resident cloud
+    void makeAndSaveScancontextAndKeysProjected() { check(s2m_sc_add_projected(h_), "s2m_sc_add_projected"); }
     // std::pair<int, float> detectLoopClosureID(void) (Scancontext.cpp:253-344): {loop_id or -1, yaw_diff_rad}
     std::pair<int, float> detectLoopClosureID()
     {

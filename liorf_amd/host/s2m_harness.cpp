@@ -18,12 +18,18 @@
 //   s2m_harness --global-map keys.bin keys.txt scan_leaf search_radius pose_density leaf out.bin
 //       the key frames through downsampleCurrentScan() -> saveKeyFrame(), then publishGlobalMap() (globalMapKeyFramesDS written
 //       to out.bin) and saveMapService()'s unfiltered cloud; prints the key list and both sizes.
+//   s2m_harness --project raw.bin sensor stamp imu.bin n_scan downsample_rate point_filter_num scan_leaf out.bin ds.bin
+//       the front end: cachePointCloud() of the raw records (sensor 0..4), imuDeskewInfo() over the samples of imu.bin
+//       ({time, wx, wy, wz} doubles), projectPointCloud(), downsampleCurrentScanProjected(), the ScanContext add from the
+//       resident cloud; fullCloud goes to out.bin, laserCloudSurfLastDS to ds.bin; prints the counts.
+#include <array>
 #include <cstdio>
 #include <cstdlib>
 #include <fstream>
 #include <iostream>
 
 #include "map_optimization_s2m.hpp"
+#include "image_projection_s2m.hpp"
 
 static std::vector<liorf_amd::PointXYZI> read_cloud(const char* path)
 {
@@ -199,6 +205,42 @@ static int run_global_map(char** argv)
     return 0;
 }
 
+static int run_project(char** argv)
+{
+    liorf_amd::MapOptimizationS2M node;
+    liorf_amd::SCManagerS2M sc(node.handle());
+    liorf_amd::ImageProjectionS2M proj(node.handle(), std::atoi(argv[3]));
+    std::ifstream f(argv[2], std::ios::binary | std::ios::ate);
+    if (!f) throw std::runtime_error(std::string("cannot open ") + argv[2]);
+    std::vector<unsigned char> raw((size_t)f.tellg());
+    f.seekg(0);
+    f.read(reinterpret_cast<char*>(raw.data()), (std::streamsize)raw.size());
+    std::ifstream fi(argv[5], std::ios::binary | std::ios::ate);
+    if (!fi) throw std::runtime_error(std::string("cannot open ") + argv[5]);
+    std::vector<std::array<double, 4>> imu((size_t)fi.tellg() / 32);
+    fi.seekg(0);
+    fi.read(reinterpret_cast<char*>(imu.data()), (std::streamsize)(imu.size() * 32));
+    proj.params.n_scan = std::atoi(argv[6]);
+    proj.params.downsample_rate = std::atoi(argv[7]);
+    proj.params.point_filter_num = std::atoi(argv[8]);
+    node.mappingSurfLeafSize = (float)std::atof(argv[9]);
+    proj.cachePointCloud(raw.data(), raw.size(), std::atof(argv[4]));
+    proj.imuDeskewInfo(imu);
+    proj.projectPointCloud();
+    node.downsampleCurrentScanProjected(proj.fullCloudNum);
+    sc.makeAndSaveScancontextAndKeysProjected();
+    std::ofstream o(argv[10], std::ios::binary);
+    o.write(reinterpret_cast<const char*>(proj.fullCloud.data()), (std::streamsize)(proj.fullCloud.size() * sizeof(liorf_amd::PointXYZI)));
+    if (!o) throw std::runtime_error(std::string("cannot write ") + argv[10]);
+    std::ofstream od(argv[11], std::ios::binary);
+    od.write(reinterpret_cast<const char*>(node.laserCloudSurfLastDS.data()),
+             (std::streamsize)(node.laserCloudSurfLastDS.size() * sizeof(liorf_amd::PointXYZI)));
+    if (!od) throw std::runtime_error(std::string("cannot write ") + argv[11]);
+    std::printf("timeScanEnd %.17g imuPointerCur %d imuAvailable %d\n", proj.timeScanEnd, proj.imuPointerCur, proj.imuAvailable ? 1 : 0);
+    std::printf("fullCloud %zu laserCloudSurfLastDSNum %d sc_size %d\n", proj.fullCloud.size(), node.laserCloudSurfLastDSNum, sc.size());
+    return 0;
+}
+
 // --many map.bin roll pitch yaw x y z scan0.bin scan1.bin ...: the same initial guess for every scan; the scans once as a batch
 // (scan2MapOptimizationBatch), once as a stream through two slots (prepareNextScan / launchSlot / collectSlot), once one by one
 // (scan2MapOptimization): prints "batch|stream|single <i> iters <n> pose ..." - the three must agree bit for bit.
@@ -249,6 +291,7 @@ int main(int argc, char** argv)
         if (argc == 7 && std::string(argv[1]) == "--keyframes") return run_keyframes(argv);
         if (argc == 9 && std::string(argv[1]) == "--loop") return run_loop(argv);
         if (argc == 9 && std::string(argv[1]) == "--global-map") return run_global_map(argv);
+        if (argc == 12 && std::string(argv[1]) == "--project") return run_project(argv);
         if (argc != 9 && argc != 16) {
             std::fprintf(stderr, "usage: %s map.bin scan.bin roll pitch yaw x y z [imuType imuRPYWeight z_tol rot_tol imuAvailable imuRoll imuPitch]\n", argv[0]);
             return 2;

@@ -39,7 +39,13 @@ ABI_SYMBOLS = [
     "s2m_kf_default_params", "s2m_kf_reset", "s2m_kf_size", "s2m_kf_add", "s2m_kf_set_poses", "s2m_extract_surrounding",
     "s2m_loop_default_params", "s2m_loop_near_keyframes", "s2m_loop_align", "s2m_loop_closure_rs",
     "s2m_gmap_default_params", "s2m_global_map", "s2m_kf_map_cloud",
+    "s2m_scan_layout_preset", "s2m_project_default_params", "s2m_imu_deskew_info", "s2m_project_check_args", "s2m_project_scan",
+    "s2m_downsample_projected", "s2m_sc_add_projected",
 ]
+S2M_RING_U8, S2M_RING_U16, S2M_RING_I32 = 0, 1, 2
+S2M_TIME_F32, S2M_TIME_U32_NS, S2M_TIME_U32, S2M_TIME_F64_REL = 0, 1, 2, 3
+S2M_SENSOR_VELODYNE, S2M_SENSOR_LIVOX, S2M_SENSOR_OUSTER, S2M_SENSOR_MULRAN, S2M_SENSOR_ROBOSENSE = 0, 1, 2, 3, 4
+S2M_IMU_QUEUE_LENGTH = 2000
 S2M_KF_FROM_HOST, S2M_KF_FROM_DEVICE, S2M_KF_FROM_LAST_DOWNSAMPLE = 0, 1, 2
 S2M_LOOP_NONE, S2M_LOOP_ALREADY_CLOSED, S2M_LOOP_TOO_FEW_POINTS, S2M_LOOP_REJECTED, S2M_LOOP_ACCEPTED = 0, 1, 2, 3, 4
 S2M_WARN_LEAF_TOO_SMALL = 1
@@ -100,6 +106,22 @@ class LoopResult(C.Structure):
 
 class GmapParams(C.Structure):
     _fields_ = [("search_radius", C.c_float), ("pose_density", C.c_float), ("leaf", C.c_float)]
+
+
+class ScanLayout(C.Structure):
+    _fields_ = [("stride", C.c_uint32), ("off_x", C.c_uint32), ("off_intensity", C.c_uint32), ("off_ring", C.c_uint32),
+                ("off_time", C.c_uint32), ("ring_type", C.c_int32), ("time_type", C.c_int32)]
+
+
+class ProjectParams(C.Structure):
+    _fields_ = [("n_scan", C.c_int32), ("downsample_rate", C.c_int32), ("point_filter_num", C.c_int32),
+                ("lidar_min_range", C.c_float), ("lidar_max_range", C.c_float)]
+
+
+class DeskewInfo(C.Structure):
+    _fields_ = [("time_scan_cur", C.c_double), ("deskew", C.c_int32), ("imu_pointer_cur", C.c_int32),
+                ("imu_time", C.POINTER(C.c_double)), ("imu_rot_x", C.POINTER(C.c_double)),
+                ("imu_rot_y", C.POINTER(C.c_double)), ("imu_rot_z", C.POINTER(C.c_double))]
 
 
 class S2MError(RuntimeError):
@@ -205,6 +227,14 @@ def load_library(path: str | None = None) -> C.CDLL:
     L.s2m_gmap_default_params.argtypes = [C.POINTER(GmapParams)]
     L.s2m_global_map.argtypes = [vp, C.POINTER(GmapParams), vp, C.c_size_t, C.c_size_t, szp, i32p, C.c_size_t, szp]
     L.s2m_kf_map_cloud.argtypes = [vp, C.c_int, C.c_int, C.c_float, vp, C.c_size_t, C.c_size_t, szp]
+    L.s2m_scan_layout_preset.argtypes = [C.c_int32, C.POINTER(ScanLayout)]
+    L.s2m_project_default_params.argtypes = [C.POINTER(ProjectParams)]
+    L.s2m_imu_deskew_info.argtypes = [dp, C.c_size_t, C.c_double, C.c_double, dp, dp, dp, dp, i32p, i32p]
+    L.s2m_project_check_args.argtypes = [C.POINTER(ScanLayout), C.POINTER(ProjectParams), C.POINTER(DeskewInfo)]
+    L.s2m_project_scan.argtypes = [vp, vp, C.c_size_t, C.POINTER(ScanLayout), C.c_int, C.POINTER(ProjectParams),
+                                   C.POINTER(DeskewInfo), vp, C.c_size_t, C.c_size_t, szp]
+    L.s2m_downsample_projected.argtypes = [vp, C.c_float, vp, C.c_size_t, C.c_size_t, szp]
+    L.s2m_sc_add_projected.argtypes = [vp]
     if path is None:
         _LIB = L
     return L
@@ -383,6 +413,31 @@ class MapOptimizationS2M:
         self._check(self.lib.s2m_transform_cloud(self.h, a.ctypes.data, n, st, _fp(p), out.ctypes.data, 32),
                     "s2m_transform_cloud")
         return out[:n]
+
+    # -- the resident cloud_deskewed of an ImageProjectionS2M on this handle ------------------------------
+    def downsampleCurrentScanProjected(self, leaf: float, readback: bool = True, cloud_num: int | None = None):
+        """downsampleCurrentScan() (reference :1061-1067) on the cloud_deskewed the last projectPointCloud() left on the
+        device (s2m_downsample_projected): returns laserCloudSurfLastDS, or None if !readback. cloud_num is that projection's
+        count (the filter never returns more); ImageProjectionS2M.projectPointCloud() records it on this object."""
+        m = C.c_size_t(0)
+        if not readback:
+            self.leaf_too_small = self._check_voxel(
+                self.lib.s2m_downsample_projected(self.h, leaf, None, 32, 0, C.byref(m)), "s2m_downsample_projected")
+            self.laserCloudSurfLastDSNum = m.value
+            return None
+        if cloud_num is None:
+            cloud_num = getattr(self, "cloudDeskewedNum", None)
+        if cloud_num is None:
+            raise ValueError("cloud_num: the count of the projection (s2m_project_scan's n_out) sizes the host buffer")
+        out = np.zeros((max(int(cloud_num), 1), 8), np.float32)
+        self.leaf_too_small = self._check_voxel(
+            self.lib.s2m_downsample_projected(self.h, leaf, out.ctypes.data, 32, int(cloud_num), C.byref(m)), "s2m_downsample_projected")
+        self.laserCloudSurfLastDSNum = m.value
+        return out[:m.value]
+
+    def makeAndSaveScancontextAndKeysProjected(self):
+        """makeAndSaveScancontextAndKeys(cloud_deskewed) (reference :1591-1594) from the resident buffer."""
+        self._check(self.lib.s2m_sc_add_projected(self.h), "s2m_sc_add_projected")
 
     # -- the path ----------------------------------------------------------
     def scan2MapOptimization(self, imu: ImuInit | None = None) -> Result:
@@ -801,3 +856,124 @@ def default_gmap_params(**kw) -> GmapParams:
     for k, v in kw.items():
         setattr(p, k, v)
     return p
+
+
+# ---- imageProjection's point filter and IMU deskew (reference src/imageProjection.cpp) ------------------------------
+def scan_layout_preset(sensor: int) -> ScanLayout:
+    lay = ScanLayout()
+    if load_library().s2m_scan_layout_preset(sensor, C.byref(lay)) != S2M_OK:
+        raise ValueError(f"unknown sensor {sensor}")
+    return lay
+
+
+def default_project_params(**kw) -> ProjectParams:
+    p = ProjectParams()
+    load_library().s2m_project_default_params(C.byref(p))
+    for k, v in kw.items():
+        setattr(p, k, v)
+    return p
+
+
+def imu_deskew_info(imu, time_scan_cur: float, time_scan_end: float):
+    """s2m_imu_deskew_info (host code, no GPU): imu is (n, 4) float64 {time, wx, wy, wz}. Returns
+    (rc, imuTime, imuRotX, imuRotY, imuRotZ, imuPointerCur, imuAvailable); the tables have S2M_IMU_QUEUE_LENGTH entries."""
+    a = np.ascontiguousarray(imu, np.float64).reshape(-1, 4)
+    tabs = [np.zeros(S2M_IMU_QUEUE_LENGTH, np.float64) for _ in range(4)]
+    cur, avail = C.c_int32(0), C.c_int32(0)
+    dp = C.POINTER(C.c_double)
+    rc = load_library().s2m_imu_deskew_info(a.ctypes.data_as(dp), a.shape[0], float(time_scan_cur), float(time_scan_end),
+                                            *[t.ctypes.data_as(dp) for t in tabs], C.byref(cur), C.byref(avail))
+    return (rc, *tabs, cur.value, bool(avail.value))
+
+
+def make_deskew_info(time_scan_cur: float, deskew: bool, imu_pointer_cur: int, imu_time, rot_x, rot_y, rot_z):
+    """An s2m_deskew_info over the four arrays (kept alive on the returned object)."""
+    dp = C.POINTER(C.c_double)
+    keep = [np.ascontiguousarray(t, np.float64) for t in (imu_time, rot_x, rot_y, rot_z)]
+    d = DeskewInfo(float(time_scan_cur), 1 if deskew else 0, int(imu_pointer_cur), *[k.ctypes.data_as(dp) for k in keep])
+    d._keep = keep
+    return d
+
+
+class ImageProjectionS2M:
+    """The cloud path of the reference's ImageProjection node (src/imageProjection.cpp) over a MapOptimizationS2M's
+    handle: imuDeskewInfo() on the host, projectPointCloud() on the device. The deskewed cloud stays resident on that
+    handle for downsampleCurrentScanProjected() / makeAndSaveScancontextAndKeysProjected()."""
+
+    def __init__(self, mapper: MapOptimizationS2M, sensor: int | None = S2M_SENSOR_VELODYNE, layout: ScanLayout | None = None,
+                 **params):
+        self.mapper = mapper
+        self.lib = mapper.lib
+        self.layout = layout if layout is not None else scan_layout_preset(sensor)
+        self.params = default_project_params(**params)
+        self.deskewFlag = 1                                    # (:310-323: 1 when the cloud has a time field, else -1)
+        self.timeScanCur = 0.0
+        self.timeScanEnd = 0.0
+        self.imuTime = np.zeros(S2M_IMU_QUEUE_LENGTH, np.float64)
+        self.imuRotX = np.zeros(S2M_IMU_QUEUE_LENGTH, np.float64)
+        self.imuRotY = np.zeros(S2M_IMU_QUEUE_LENGTH, np.float64)
+        self.imuRotZ = np.zeros(S2M_IMU_QUEUE_LENGTH, np.float64)
+        self.imuPointerCur = 0
+        self.imuAvailable = False
+        self.fullCloud = None
+        self.fullCloudNum = 0
+        self._raw = None
+
+    def record_times(self, raw: np.ndarray) -> np.ndarray:
+        """laserCloudIn->points[i].time of every record, as the conversion loops leave it (:216-274)."""
+        lay, n = self.layout, raw.size // self.layout.stride
+        rec = raw.reshape(n, lay.stride)
+        b = rec[:, lay.off_time:lay.off_time + (8 if lay.time_type == S2M_TIME_F64_REL else 4)]
+        if lay.time_type == S2M_TIME_F32:
+            return np.ascontiguousarray(b).view(np.float32).reshape(n)
+        if lay.time_type == S2M_TIME_U32_NS:
+            return np.ascontiguousarray(b).view(np.uint32).reshape(n).astype(np.float32) * np.float32(1e-9)
+        if lay.time_type == S2M_TIME_U32:
+            return np.ascontiguousarray(b).view(np.uint32).reshape(n).astype(np.float32)
+        ts = np.ascontiguousarray(b).view(np.float64).reshape(n)
+        return (ts - ts[0]).astype(np.float32)
+
+    def cachePointCloud(self, raw_bytes, stamp: float):
+        """The part of cachePointCloud() (:206-343) that reaches the cloud path: keep the raw bytes as they are,
+        timeScanCur = header stamp, timeScanEnd = timeScanCur + time of the last record (:282-283)."""
+        raw = np.ascontiguousarray(np.frombuffer(raw_bytes, np.uint8) if not isinstance(raw_bytes, np.ndarray) else raw_bytes.view(np.uint8).reshape(-1))
+        if raw.size % self.layout.stride:
+            raise ValueError("the buffer is not a whole number of records")
+        self._raw = raw
+        self.timeScanCur = float(stamp)
+        n = raw.size // self.layout.stride
+        last = float(self.record_times(raw)[-1]) if n else 0.0
+        self.timeScanEnd = self.timeScanCur + last
+
+    def imuDeskewInfo(self, imu) -> bool:
+        """imuDeskewInfo() (:350-409) on samples {time, wx, wy, wz} already popped to timeScanCur - 0.01."""
+        rc, self.imuTime, self.imuRotX, self.imuRotY, self.imuRotZ, self.imuPointerCur, self.imuAvailable = \
+            imu_deskew_info(imu, self.timeScanCur, self.timeScanEnd)
+        if rc != S2M_OK:
+            raise S2MError(f"s2m_imu_deskew_info: {ERRORS.get(rc, rc)}")
+        return self.imuAvailable
+
+    def deskewInfo(self) -> DeskewInfo:
+        on = self.deskewFlag == 1 and self.imuAvailable
+        return make_deskew_info(self.timeScanCur, on, self.imuPointerCur if on else 0, self.imuTime, self.imuRotX, self.imuRotY,
+                                self.imuRotZ)
+
+    def projectPointCloud(self, readback: bool = True, device_ptr=None):
+        """projectPointCloud() (:568-598) on the cached records (or device_ptr=(ptr, n) for records already in HBM):
+        cloud_deskewed stays on the device; with readback fullCloud is its host copy, (m, 8) float32."""
+        lay = self.layout
+        if device_ptr is not None:
+            src, n, on_dev = C.c_void_p(device_ptr[0]), int(device_ptr[1]), 1
+        else:
+            n = self._raw.size // lay.stride
+            src, on_dev = self._raw.ctypes.data, 0
+        d = self.deskewInfo()
+        m = C.c_size_t(0)
+        cap = (n + self.params.point_filter_num - 1) // max(self.params.point_filter_num, 1) if readback else 0
+        out = np.zeros((max(cap, 1), 8), np.float32) if readback else None
+        self.mapper._check(self.lib.s2m_project_scan(self.mapper.h, src, n, C.byref(lay), on_dev, C.byref(self.params), C.byref(d),
+                                                     out.ctypes.data if readback else None, 32, cap, C.byref(m)), "s2m_project_scan")
+        self.fullCloudNum = m.value
+        self.mapper.cloudDeskewedNum = m.value                 # sizes downsampleCurrentScanProjected()'s host buffer
+        self.fullCloud = out[:m.value] if readback else None
+        return self.fullCloud

@@ -11,7 +11,9 @@ so lidar rays intersect in closed form.  Produces
 * lidar SCANS in the lidar frame: analytic ray casts from a ground-truth sensor pose
   with N(0, 0.02 m) range noise (Velodyne-64 / Ouster-128 / dense rosette patterns),
 
-plus the ground-truth pose and the perturbed initial guess.  This is workload data for
+plus the ground-truth pose and the perturbed initial guess, and (make_raw_scan) RAW lidar
+messages for the front end: the same scenes swept over 0.1 s by a turning sensor, as records
+in the reference's sensor layouts, with the IMU samples.  This is workload data for
 tests/ and bench.py; it is not part of the registration path itself.
 """
 from __future__ import annotations
@@ -267,3 +269,98 @@ def move_config(cfg, yaw: float, t):
         out[key] = q.astype(np.float32)
     out["meta"] = dict(cfg["meta"], moved=(float(yaw), [float(v) for v in t]))
     return out
+
+
+# --------------------------------------------------------------------------- raw scans for the front end
+# The reference's point structs (src/imageProjection.cpp:4-57): stride, offsets of x / intensity / ring / time, ring type
+# (0 u8, 1 u16, 2 i32), time type (0 f32 s, 1 u32 ns, 2 u32 taken as it is, 3 f64 absolute stamp).
+RAW_LAYOUTS = {
+    "velodyne":  (32, 0, 16, 20, 24, 1, 0),
+    "livox":     (32, 0, 16, 20, 24, 1, 0),
+    "ouster":    (48, 0, 16, 26, 20, 0, 1),
+    "mulran":    (32, 0, 16, 24, 20, 2, 2),
+    "robosense": (32, 0, 16, 20, 24, 1, 3),
+}
+
+
+def _rodrigues(w: np.ndarray, dt: float) -> np.ndarray:
+    th = float(np.linalg.norm(w)) * dt
+    if th == 0.0:
+        return np.eye(3)
+    k = w / np.linalg.norm(w)
+    K = np.array([[0, -k[2], k[1]], [k[2], 0, -k[0]], [-k[1], k[0], 0]])
+    return np.eye(3) + math.sin(th) * K + (1 - math.cos(th)) * (K @ K)
+
+
+def pack_raw(layout, xyz, intensity, ring, time, stamp: float = 0.0) -> np.ndarray:
+    """Records of `layout` (a RAW_LAYOUTS tuple) as a flat uint8 array; bytes no field covers are 0. `time` is seconds
+    from the message stamp: stored as float32, as whole nanoseconds (both u32 forms), or as stamp + time (f64)."""
+    stride, ox, oi, orr, ot, rt, tt = layout
+    n = xyz.shape[0]
+    rec = np.zeros((n, stride), np.uint8)
+    rec[:, ox:ox + 12] = np.ascontiguousarray(xyz, np.float32).view(np.uint8).reshape(n, 12)
+    rec[:, oi:oi + 4] = np.ascontiguousarray(intensity, np.float32).view(np.uint8).reshape(n, 4)
+    rdt = (np.uint8, np.uint16, np.int32)[rt]
+    rb = np.dtype(rdt).itemsize
+    rec[:, orr:orr + rb] = np.ascontiguousarray(np.asarray(ring).astype(rdt)).view(np.uint8).reshape(n, rb)
+    t = np.asarray(time, np.float64)
+    if tt == 0:
+        tb = np.ascontiguousarray(t.astype(np.float32)).view(np.uint8).reshape(n, 4)
+    elif tt in (1, 2):
+        tb = np.ascontiguousarray(np.round(t * 1e9).astype(np.uint32)).view(np.uint8).reshape(n, 4)
+    else:
+        tb = np.ascontiguousarray(stamp + t).view(np.uint8).reshape(n, 8)
+    rec[:, ot:ot + tb.shape[1]] = tb
+    return rec.reshape(-1)
+
+
+def make_raw_scan(scene: Scene, pose_gt: np.ndarray, layout: str = "velodyne", n_rings: int = 16, n_az: int = 1800,
+                  angular_velocity=None, imu_rate: float = 500.0, stamp: float = 0.0, sweep: float = 0.1,
+                  max_range: float = 100.0, keep_misses: bool = False):
+    """One raw lidar message of a sensor that stays at pose_gt's position and turns: the rays of azimuth column j leave at
+    time sweep * j / n_az (all rings of a column together, records azimuth-major) from the orientation the sensor has
+    then. angular_velocity(t) gives the body-frame rate (rad/s, 3-vector) at time t from the stamp (default: none); the
+    orientation is integrated column by column with the rate at the column's start. Returns a dict:
+      raw (uint8 records of RAW_LAYOUTS[layout]), n, layout, time (s from the stamp), ring, points (float32, sensor frame at
+      the point's own time - what the lidar reports), world (float64 hit points), origin, col (column of every record),
+      R_cols (sensor-to-world rotation of every column), imu ((k, 4) float64 {time, wx, wy, wz} at imu_rate, from 8 ms before
+      the stamp to 20 ms after the sweep), time_scan_cur, time_scan_end.
+    keep_misses keeps rays without a hit as points at the origin (range 0: the range filter's work) so that the record count
+    is exactly n_rings * n_az."""
+    if angular_velocity is None:
+        angular_velocity = lambda t: np.zeros(3)          # noqa: E731
+    lay = RAW_LAYOUTS[layout]
+    R0 = rotation_rpy(*[float(v) for v in pose_gt[:3]])
+    origin = np.asarray(pose_gt[3:], np.float64)
+    lo, hi = (-15.0, 15.0) if n_rings <= 16 else ((-24.8, 2.0) if n_rings <= 64 else (-22.5, 22.5))
+    elev = np.radians(np.linspace(lo, hi, n_rings))
+    az = np.arange(n_az) * (2 * math.pi / n_az)
+    dt = sweep / n_az
+    R_cols = np.empty((n_az, 3, 3))
+    R = R0.copy()
+    for j in range(n_az):
+        R_cols[j] = R
+        R = R @ _rodrigues(np.asarray(angular_velocity(j * dt), np.float64), dt)
+    ce = np.cos(elev)
+    d_l = np.stack([np.outer(np.cos(az), ce), np.outer(np.sin(az), ce), np.outer(np.ones(n_az), np.sin(elev))], 2)     # (n_az, n_rings, 3)
+    d_w = np.einsum("jab,jrb->jra", R_cols, d_l).reshape(-1, 3)
+    d_l = d_l.reshape(-1, 3)
+    t = _cast(scene, origin, d_w, max_range)
+    col = np.repeat(np.arange(n_az), n_rings)
+    ring = np.tile(np.arange(n_rings), n_az)
+    hit = np.isfinite(t)
+    if keep_misses:
+        t = np.where(hit, t, 0.0)
+    else:
+        d_l, d_w, t, col, ring = d_l[hit], d_w[hit], t[hit], col[hit], ring[hit]
+    pts = (d_l * t[:, None]).astype(np.float32)
+    world = origin[None, :] + d_w * t[:, None]
+    time = col * dt
+    inten = (10.0 + ring).astype(np.float32)
+    imu_t = np.arange(stamp - 0.008, stamp + sweep + 0.02, 1.0 / imu_rate)
+    imu = np.stack([np.concatenate([[ti], np.asarray(angular_velocity(ti - stamp), np.float64)]) for ti in imu_t], 0)
+    raw = pack_raw(lay, pts, inten, ring, time, stamp)
+    last = np.float32(time[-1]) if lay[6] == 0 else (np.float32(np.uint32(round(time[-1] * 1e9))) * np.float32(1e-9) if lay[6] == 1 else
+                                                     (np.float32(np.uint32(round(time[-1] * 1e9))) if lay[6] == 2 else np.float32(time[-1] - time[0])))
+    return dict(raw=raw, n=pts.shape[0], layout=lay, time=time, ring=ring, points=pts, world=world, origin=origin, col=col,
+                R_cols=R_cols, imu=imu, time_scan_cur=float(stamp), time_scan_end=float(stamp) + float(last))
