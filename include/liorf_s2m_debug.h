@@ -71,6 +71,43 @@ int  s2m_debug_time_steady(s2m_handle h, const float pose[6], int reps, int solv
 #define S2M_PROF_WORDS 32
 int  s2m_debug_wave_profile(s2m_handle h, const float pose[6], int launches, uint64_t* out, size_t cap_waves);
 
+/* Observation hook: hypotf of n pairs of host floats as the device computes it in the Jacobi rotations of the
+ * iteration-0 degeneracy analysis (cv::eigen): glibc's arithmetic, so that the device gives what the host's libm gives. */
+int  s2m_debug_device_hypot(s2m_handle h, const float* x, const float* y, size_t n, float* r);
+
+/* Observation hook: closes ONE LM iteration on given partial sums - everything of LMOptimization() behind the
+ * per-point work (:1177-1292): second stage of the reduction, fp32 matAtA / matAtB, the QR solve, at iteration 0 the
+ * degeneracy analysis, the projection, the pose update and the convergence test - and returns what the close wrote.
+ *   rows     n_rows x 28 doubles in the layout of a workgroup's partial row: 21 upper-triangular JtJ sums (row-major),
+ *            6 Jtr sums, the correspondence count. They go to the slot of parity iter & 1; the other active rows of
+ *            that slot are zero; every row the close must not read (inactive rows, the whole other slot) is NaN.
+ *            n_rows larger than the number of workgroups the resident scan's wave table needs: S2M_ERR_INVALID_ARG.
+ *   pose0    the pose iteration `iter` ran with; degen_in / matP_in: isDegenerate and matP as left by iteration 0
+ *   form 0   the stand-alone close k_finalize(iter) (iter == 0: with the degeneracy analysis)
+ *   form 1   the prologue of the fused registration launch iter + 1 (iter >= 1), in the workgroup shape of the resident
+ *            scan; the registration pass behind the prologue runs on the resident scan and map at the pose the close
+ *            produced, its own results are ignored
+ * Uses the handle's current parameters (min_corr, eig_thresh, conv_deg, conv_cm, early_exit, max_iter); iter in
+ * 0 .. max_iter-1. Needs a resident scan and map (S2M_ERR_NO_SCAN). No kernel exists for the hook: it prepares the
+ * state and launches what the loop launches. The state that persists from scan to scan (isDegenerate, matP) is not
+ * touched: the next registration on the handle is the one a handle that never saw the hook computes. */
+typedef struct s2m_debug_lm_close_out {
+    float   AtA[36], AtB[6];   /* matAtA, matAtB as stored (fp32)                                  */
+    int32_t n_sel_last;
+    s2m_iter_trace trace;      /* the record of iteration `iter`                                   */
+    float   pose[6];           /* transformTobeMapped after the close                              */
+    float   pose_next[6];      /* the pose launch iter + 1 runs with (NaN: the close wrote none)   */
+    int32_t iters_run, converged, done, stalled, is_degenerate;
+    int32_t n_rows_active;     /* rows the close read: the workgroups the resident scan's wave table needs */
+    float   matP[36];
+} s2m_debug_lm_close_out;
+int  s2m_debug_lm_close(s2m_handle h, int form, int iter, const double* rows, int n_rows, const float pose0[6],
+                        int degen_in, const float matP_in[36], s2m_debug_lm_close_out* out);
+/* The argument checks of s2m_debug_lm_close that need no handle and no GPU: S2M_OK or S2M_ERR_INVALID_ARG (a null pointer
+ * - rows may be null when n_rows == 0 -, n_rows < 0, form outside {0, 1}, iter outside 0 .. max_iter-1, form 1 at iter 0). */
+int  s2m_debug_lm_close_check_args(int form, int iter, int max_iter, const double* rows, int n_rows, const float pose0[6],
+                                   const float matP_in[36], const s2m_debug_lm_close_out* out);
+
 
 #ifdef __cplusplus
 }

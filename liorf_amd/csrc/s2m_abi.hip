@@ -13,6 +13,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <algorithm>
+#include <limits>
 #include <map>
 #include <new>
 #include <string>
@@ -1547,6 +1548,84 @@ int s2m_debug_device_trig(s2m_handle h, const float* x, size_t n, float* s, floa
     S2M_HIP(h, hipMemcpyAsync(c, d + 2 * n, sizeof(float) * n, hipMemcpyDeviceToHost, h->stream));
     if (a) S2M_HIP(h, hipMemcpyAsync(a, d + 3 * n, sizeof(float) * n, hipMemcpyDeviceToHost, h->stream));
     S2M_HIP(h, hipStreamSynchronize(h->stream));
+    return S2M_OK;
+}
+
+int s2m_debug_device_hypot(s2m_handle h, const float* x, const float* y, size_t n, float* r)
+{
+    if (!h || (n > 0 && (!x || !y || !r)) || n > (size_t)0x3fffffff) return S2M_ERR_INVALID_ARG;
+    if (n == 0) return S2M_OK;
+    S2M_HIP(h, hipSetDevice(h->device));
+    int rc = ensure(h, h->vox_in, sizeof(float) * 3 * n);
+    if (rc) return rc;
+    float* d = h->vox_in.as<float>();
+    S2M_HIP(h, hipMemcpyAsync(d, x, sizeof(float) * n, hipMemcpyHostToDevice, h->stream));
+    S2M_HIP(h, hipMemcpyAsync(d + n, y, sizeof(float) * n, hipMemcpyHostToDevice, h->stream));
+    hipLaunchKernelGGL(k_debug_hypot, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, (const float*)d, (const float*)(d + n), (int)n, d + 2 * n);
+    S2M_HIP(h, hipGetLastError());
+    S2M_HIP(h, hipMemcpyAsync(r, d + 2 * n, sizeof(float) * n, hipMemcpyDeviceToHost, h->stream));
+    S2M_HIP(h, hipStreamSynchronize(h->stream));
+    return S2M_OK;
+}
+
+int s2m_debug_lm_close_check_args(int form, int iter, int max_iter, const double* rows, int n_rows, const float pose0[6],
+                                  const float matP_in[36], const s2m_debug_lm_close_out* out)
+{
+    if (n_rows < 0 || (n_rows > 0 && !rows) || !pose0 || !matP_in || !out) return S2M_ERR_INVALID_ARG;
+    if (form != 0 && form != 1) return S2M_ERR_INVALID_ARG;
+    if (iter < 0 || iter >= max_iter) return S2M_ERR_INVALID_ARG;
+    if (form == 1 && iter == 0) return S2M_ERR_INVALID_ARG;     // launch 1 never closes: iteration 0 needs the degeneracy analysis
+    return S2M_OK;
+}
+
+int s2m_debug_lm_close(s2m_handle h, int form, int iter, const double* rows, int n_rows, const float pose0[6],
+                       int degen_in, const float matP_in[36], s2m_debug_lm_close_out* out)
+{
+    if (!h) return S2M_ERR_INVALID_ARG;
+    if (s2m_debug_lm_close_check_args(form, iter, h->prm.max_iter, rows, n_rows, pose0, matP_in, out))
+        return fail(h, S2M_ERR_INVALID_ARG, "null argument, form outside {0, 1}, iter outside 0 .. max_iter-1, or form 1 at iter 0");
+    if (h->opt_pending) return fail(h, S2M_ERR_INVALID_ARG, "an optimize launch is pending: collect it first");
+    if (!h->have_scan || h->n_m == 0 || h->n_q == 0) return fail(h, S2M_ERR_NO_SCAN, "needs a resident scan and map");
+    S2M_HIP(h, hipSetDevice(h->device));
+    int rc;
+    if ((rc = upload_ctx(h))) return rc;                   // (the parameters of the last s2m_set_params with it)
+    // the rows a close reads: one per workgroup the wave table of the resident scan needs (k_finalize, k_register)
+    int32_t n_waves = 0;
+    S2M_HIP(h, hipMemcpyAsync(&n_waves, h->n_waves.p, sizeof(n_waves), hipMemcpyDeviceToHost, h->stream));
+    S2M_HIP(h, hipStreamSynchronize(h->stream));
+    const int nblocks = h->hctx.nblocks, wpb = h->hctx.wpb;
+    const int nb_act = std::min((n_waves + wpb - 1) / wpb, nblocks);
+    if (n_rows > nb_act) return fail(h, S2M_ERR_INVALID_ARG, "more rows than the resident scan has active workgroups");
+    std::vector<double> part((size_t)2 * (size_t)nblocks * kAcc, std::numeric_limits<double>::quiet_NaN());
+    double* slot = part.data() + (size_t)(iter & 1) * (size_t)nblocks * kAcc;
+    for (size_t k = 0; k < (size_t)nb_act * kAcc; k++) slot[k] = k < (size_t)n_rows * kAcc ? rows[k] : 0.0;
+    S2M_HIP(h, hipMemcpyAsync(h->partials.p, part.data(), sizeof(double) * part.size(), hipMemcpyHostToDevice, h->stream));
+    DevState s;
+    fill_state(h, &s, pose0);
+    for (int k = 0; k < 6; k++) { s.pose2[iter & 1][k] = pose0[k]; s.pose2[(iter + 1) & 1][k] = NAN; }
+    s.T_valid = 0;
+    s.isDegenerate = degen_in;
+    memcpy(s.matP, matP_in, sizeof(s.matP));
+    hipLaunchKernelGGL(k_set_state, dim3(1), dim3(64), 0, h->stream, h->state.as<DevState>(), s, (const int32_t*)h->n_waves.as<int32_t>());
+    S2M_HIP(h, hipMemsetAsync(h->hctx.trace + iter, 0xff, sizeof(s2m_iter_trace), h->stream));
+    const LoopShape sh = shape_of(h);
+    if (form == 0) launch_finalize(h, sh, iter, 0);
+    else           launch_fused(h, sh, false, iter + 1, 1);
+    S2M_HIP(h, hipGetLastError());
+    S2M_HIP(h, hipMemcpyAsync(&h->h_state[1], h->state.p, sizeof(DevState), hipMemcpyDeviceToHost, h->stream));
+    S2M_HIP(h, hipMemcpyAsync(&h->h_trace[iter], h->hctx.trace + iter, sizeof(s2m_iter_trace), hipMemcpyDeviceToHost, h->stream));
+    S2M_HIP(h, hipStreamSynchronize(h->stream));
+    const DevState& r = h->h_state[1];
+    memcpy(out->AtA, r.AtA, sizeof(out->AtA));
+    memcpy(out->AtB, r.AtB, sizeof(out->AtB));
+    out->n_sel_last = r.n_sel_last;
+    out->trace = h->h_trace[iter];
+    memcpy(out->pose, r.pose, 24);
+    memcpy(out->pose_next, r.pose2[(iter + 1) & 1], 24);
+    out->iters_run = r.iters_run; out->converged = r.converged; out->done = r.done; out->stalled = r.stalled;
+    out->is_degenerate = r.isDegenerate;
+    out->n_rows_active = nb_act;
+    memcpy(out->matP, r.matP, sizeof(out->matP));
     return S2M_OK;
 }
 

@@ -184,6 +184,23 @@ S2M_HD inline float glibc_atanf(float x)
     return (hx < 0) ? -r : r;
 }
 
+// hypotf as glibc computes it (sysdeps/ieee754/flt-32/e_hypotf.c [ext]: glibc >= 2.35 states it this way, older
+// versions compute the same double expression): (float)sqrt((double)x * x + (double)y * y) with correctly rounded
+// fp64 multiply, add and sqrt, and +inf for an infinite argument whatever the other one is.  cv::eigen's Jacobi
+// rotations (eigen6_sym) call std::hypot on floats, i.e. the host's libm; the device library's hypotf scales by
+// the larger exponent and works in fp32 (fma, then the fp32 square root), which is a different rounding: one ulp
+// apart for about one argument pair in ten, and an ulp in a rotation moves the eigenvalues that the eig_thresh
+// comparison reads.  The products are exact in fp64 (24-bit factors), so contraction could not change the sum;
+// it stays unfused all the same.  tests/test_lm_close_gpu.py::test_device_hypot_is_the_hosts compares the device
+// results with the test host's libm.
+S2M_HD inline float glibc_hypotf(float x, float y)
+{
+    if (fabsf(x) == INFINITY || fabsf(y) == INFINITY) return INFINITY;
+    const double dx = (double)x, dy = (double)y;
+    const double xx = dx * dx, yy = dy * dy;
+    return (float)sqrt(xx + yy);
+}
+
 // ------------------------------------------------------------------------------------------
 // index build: bounding box, cell histogram with per-point rank, exclusive scan, scatter
 // ------------------------------------------------------------------------------------------
@@ -1000,8 +1017,8 @@ __device__ void eigen6_sym(float (*A)[6], float (*V)[6], float* W, int* indR, in
         const float p = A[k][l];
         if (fabsf(p) <= eps) break;
         const float y = (W[l] - W[k]) * 0.5f;
-        float t = fabsf(y) + hypotf(p, y);
-        float s = hypotf(p, t);
+        float t = fabsf(y) + glibc_hypotf(p, y);          // std::hypot of floats on the host: see glibc_hypotf
+        float s = glibc_hypotf(p, t);
         const float c = t / s;
         s = p / s; t = (p / t) * p;
         if (y < 0.0f) { s = -s; t = -t; }
@@ -1500,6 +1517,13 @@ __global__ __launch_bounds__(256) void k_debug_sincos(const float* __restrict__ 
 {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) { s[i] = glibc_sincosf(x[i], 0); c[i] = glibc_sincosf(x[i], 1); if (a) a[i] = glibc_atanf(x[i]); }
+}
+
+// Observation hook: the hypotf of eigen6_sym's Jacobi rotations on n argument pairs (tests compare with the host's libm).
+__global__ __launch_bounds__(256) void k_debug_hypot(const float* __restrict__ x, const float* __restrict__ y, int n, float* __restrict__ r)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) r[i] = glibc_hypotf(x[i], y[i]);
 }
 
 // Parameter blocks travel as kernel arguments (copied at launch), so the host never has to

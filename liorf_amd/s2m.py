@@ -34,7 +34,8 @@ ABI_SYMBOLS = [
     "s2m_time_iteration_kernel", "s2m_time_iterations", "s2m_make_scancontext", "s2m_debug_wave_profile", "s2m_debug_time_steady", "s2m_time_loop_launches",
     "s2m_voxel_downsample", "s2m_voxel_downsample_device", "s2m_downsample_scan", "s2m_extract_cloud",
     "s2m_transform_cloud",
-    "s2m_icp_default_params", "s2m_icp_align", "s2m_debug_device_trig",
+    "s2m_icp_default_params", "s2m_icp_align", "s2m_debug_device_trig", "s2m_debug_device_hypot",
+    "s2m_debug_lm_close", "s2m_debug_lm_close_check_args",
     "s2m_sc_reset", "s2m_sc_size", "s2m_sc_add_scan", "s2m_sc_add_descriptor", "s2m_sc_detect_loop", "s2m_sc_distance",
     "s2m_kf_default_params", "s2m_kf_reset", "s2m_kf_size", "s2m_kf_add", "s2m_kf_set_poses", "s2m_extract_surrounding",
     "s2m_loop_default_params", "s2m_loop_near_keyframes", "s2m_loop_align", "s2m_loop_closure_rs",
@@ -74,6 +75,14 @@ class Result(C.Structure):
 class IterTrace(C.Structure):
     _fields_ = [("n_sel", C.c_int32), ("stepped", C.c_int32), ("delta", C.c_float * 6),
                 ("pose", C.c_float * 6), ("deltaR", C.c_float), ("deltaT", C.c_float)]
+
+
+class LmCloseOut(C.Structure):
+    """s2m_debug_lm_close_out (include/liorf_s2m_debug.h)."""
+    _fields_ = [("AtA", C.c_float * 36), ("AtB", C.c_float * 6), ("n_sel_last", C.c_int32), ("trace", IterTrace),
+                ("pose", C.c_float * 6), ("pose_next", C.c_float * 6), ("iters_run", C.c_int32), ("converged", C.c_int32),
+                ("done", C.c_int32), ("stalled", C.c_int32), ("is_degenerate", C.c_int32), ("n_rows_active", C.c_int32),
+                ("matP", C.c_float * 36)]
 
 
 class ScMatch(C.Structure):
@@ -205,6 +214,9 @@ def load_library(path: str | None = None) -> C.CDLL:
     L.s2m_transform_cloud.argtypes = [vp, vp, C.c_size_t, C.c_size_t, fp, vp, C.c_size_t]
     dp, i32p = C.POINTER(C.c_double), C.POINTER(C.c_int32)
     L.s2m_debug_device_trig.argtypes = [vp, fp, C.c_size_t, fp, fp, fp]
+    L.s2m_debug_device_hypot.argtypes = [vp, fp, fp, C.c_size_t, fp]
+    L.s2m_debug_lm_close.argtypes = [vp, C.c_int, C.c_int, dp, C.c_int, fp, C.c_int, fp, C.POINTER(LmCloseOut)]
+    L.s2m_debug_lm_close_check_args.argtypes = [C.c_int, C.c_int, C.c_int, dp, C.c_int, fp, fp, C.POINTER(LmCloseOut)]
     L.s2m_icp_default_params.argtypes = [C.POINTER(IcpParams)]
     L.s2m_icp_align.argtypes = [vp, vp, C.c_size_t, vp, C.c_size_t, C.c_size_t, C.POINTER(IcpParams), C.POINTER(IcpResult)]
     L.s2m_sc_reset.argtypes = [vp]
@@ -596,6 +608,24 @@ class MapOptimizationS2M:
         sn, cs, at = np.zeros_like(a), np.zeros_like(a), np.zeros_like(a)
         self._check(self.lib.s2m_debug_device_trig(self.h, _fp(a), a.size, _fp(sn), _fp(cs), _fp(at)), "s2m_debug_device_trig")
         return sn, cs, at
+
+    def deviceHypot(self, x, y):
+        """Observation hook: hypotf(x, y) of two float32 arrays as the device computes it in cv::eigen's rotations."""
+        a, b = np.ascontiguousarray(x, np.float32), np.ascontiguousarray(y, np.float32)
+        assert a.shape == b.shape
+        r = np.zeros_like(a)
+        self._check(self.lib.s2m_debug_device_hypot(self.h, _fp(a), _fp(b), a.size, _fp(r)), "s2m_debug_device_hypot")
+        return r
+
+    def lmClose(self, form: int, it: int, rows, pose0, degen_in: int, matP_in) -> LmCloseOut:
+        """Observation hook: close LM iteration `it` on the partial rows `rows` (n x 28 float64); see s2m_debug_lm_close."""
+        r = np.ascontiguousarray(rows, np.float64).reshape(-1, 28)
+        p = np.ascontiguousarray(pose0, np.float32).reshape(6)
+        m = np.ascontiguousarray(matP_in, np.float32).reshape(36)
+        out = LmCloseOut()
+        self._check(self.lib.s2m_debug_lm_close(self.h, form, it, r.ctypes.data_as(C.POINTER(C.c_double)), r.shape[0], _fp(p),
+                                                int(degen_in), _fp(m), C.byref(out)), "s2m_debug_lm_close")
+        return out
 
     def timing(self):
         a, b, c = C.c_float(0), C.c_float(0), C.c_float(0)

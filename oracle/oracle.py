@@ -74,6 +74,8 @@ def lib() -> C.CDLL:
         L.orc_getTransformation.argtypes = [fp, fp]
         L.orc_LMOptimization.argtypes = [vp, C.c_int]
         L.orc_LMOptimization.restype = C.c_int
+        L.orc_lm_close.argtypes = [fp, fp, C.c_int, C.c_int, C.POINTER(Params), fp, C.POINTER(C.c_int), fp, C.POINTER(IterTrace)]
+        L.orc_lm_close.restype = C.c_int
         L.orc_transformUpdate.argtypes = [vp, C.POINTER(ImuInit)]
         L.orc_scan2MapOptimization.argtypes = [vp, C.POINTER(ImuInit), C.POINTER(Result)]
         L.orc_num_queries.argtypes = [vp]
@@ -238,6 +240,19 @@ def getTransformation(pose) -> np.ndarray:
     T = np.zeros(12, np.float32)
     lib().orc_getTransformation(_fp(a), _fp(T))
     return T.reshape(3, 4)
+
+
+def lm_close(AtA, AtB, n_sel: int, iterCount: int, params: Params, pose, isDegenerate: int, matP):
+    """The close of LMOptimization() on given normal equations (orc_lm_close, the function orc_LMOptimization calls).
+    Returns (converged, pose, isDegenerate, matP (6, 6), trace record)."""
+    A = np.ascontiguousarray(AtA, np.float32).reshape(36).copy()
+    b = np.ascontiguousarray(AtB, np.float32).reshape(6).copy()
+    p = np.ascontiguousarray(pose, np.float32).reshape(6).copy()
+    m = np.ascontiguousarray(matP, np.float32).reshape(36).copy()
+    d = C.c_int(int(isDegenerate))
+    tr = IterTrace()
+    conv = lib().orc_lm_close(_fp(A), _fp(b), int(n_sel), int(iterCount), C.byref(params), _fp(p), C.byref(d), _fp(m), C.byref(tr))
+    return conv, p, d.value, m.reshape(6, 6), tr
 
 
 def knn5_brute(map_xyz, q):

@@ -658,6 +658,55 @@ int orc_inv6_lu(const float Ain[36], float Ainv[36])
     return 1;
 }
 
+/* ---- the close of LMOptimization (:1178-1180, :1240-1292) ------------------------ */
+/* Everything behind matAtA / matAtB: the solve, at iteration 0 the degeneracy analysis, the projection, the pose
+ * update and the convergence test.  `pose`, `isDegenerate` and `matP` are the members transformTobeMapped,
+ * isDegenerate and matP (read and written as the reference does); `tr` receives the record of this iteration.
+ * Returns LMOptimization's return value (1 = converged).                                                        */
+int orc_lm_close(const float AtA[36], const float AtB[6], int n_sel, int iterCount, const orc_params* p,
+                 float pose[6], int* isDegenerate, float matP[36], orc_iter_trace* tr)
+{
+    memset(tr, 0, sizeof(*tr));
+    tr->n_sel = n_sel;
+    memcpy(tr->pose, pose, 24);
+    if (n_sel < p->min_corr) return 0;                                  /* :1178-1180 */
+
+    float X[6];
+    orc_solve6_qr(AtA, AtB, X);                                         /* :1240 */
+
+    if (iterCount == 0) {                                               /* :1242-1264 */
+        float E[6], V[36], V2[36], Vinv[36];
+        orc_eigen6_sym(AtA, E, V);
+        memcpy(V2, V, sizeof(V));
+        *isDegenerate = 0;
+        for (int i = 5; i >= 0; i--) {
+            if (E[i] < p->eig_thresh) { for (int j = 0; j < 6; j++) V2[i * 6 + j] = 0.0f; *isDegenerate = 1; }
+            else break;
+        }
+        orc_inv6_lu(V, Vinv);
+        for (int i = 0; i < 6; i++) for (int j = 0; j < 6; j++) {       /* matP = V.inv() * V2 */
+            double s = 0.0; for (int k = 0; k < 6; k++) s += (double)Vinv[i * 6 + k] * (double)V2[k * 6 + j];
+            matP[i * 6 + j] = (float)s;
+        }
+    }
+    if (*isDegenerate) {                                                /* :1266-1271 */
+        float X2[6]; memcpy(X2, X, 24);
+        for (int i = 0; i < 6; i++) { double s = 0.0; for (int k = 0; k < 6; k++) s += (double)matP[i * 6 + k] * (double)X2[k]; X[i] = (float)s; }
+    }
+    for (int k = 0; k < 6; k++) pose[k] += X[k];                        /* :1273-1278 */
+
+    /* pcl::rad2deg(float) = alpha * 57.29578f [ext]; pow(float, int) promotes to double */
+    double r0 = (double)(X[0] * 57.29578f), r1 = (double)(X[1] * 57.29578f), r2 = (double)(X[2] * 57.29578f);
+    float deltaR = (float)sqrt(r0 * r0 + r1 * r1 + r2 * r2);
+    double t0 = (double)(X[3] * 100), t1 = (double)(X[4] * 100), t2 = (double)(X[5] * 100);
+    float deltaT = (float)sqrt(t0 * t0 + t1 * t1 + t2 * t2);
+
+    tr->stepped = 1; memcpy(tr->delta, X, 24); memcpy(tr->pose, pose, 24);
+    tr->deltaR = deltaR; tr->deltaT = deltaT;
+    if ((double)deltaR < p->conv_deg && (double)deltaT < p->conv_cm) return 1;   /* :1289 */
+    return 0;
+}
+
 /* ---- LMOptimization (:1158-1293) ----------------------------------------------- */
 int orc_LMOptimization(orc_ctx* c, int iterCount)
 {
@@ -665,9 +714,8 @@ int orc_LMOptimization(orc_ctx* c, int iterCount)
     memset(tr, 0, sizeof(*tr));
     float sc[6]; pose_trig(c->transformTobeMapped, sc);                 /* :1170-1175 */
     int n = c->selNum;
-    tr->n_sel = n;
-    memcpy(tr->pose, c->transformTobeMapped, 24);
-    if (n < c->p.min_corr) return 0;                                    /* :1178-1180 */
+    if (n < c->p.min_corr)                                              /* :1178-1180: matAtA / matAtB are not formed */
+        return orc_lm_close(c->matAtA, c->matAtB, n, iterCount, &c->p, c->transformTobeMapped, &c->isDegenerate, c->matP, tr);
 
     /* matA (n x 6), matB (n x 1) fp32; matAtA = At*A, matAtB = At*B accumulate in
      * double and store fp32 (OpenCV gemm for CV_32F uses a double work type) [ext]. */
@@ -683,40 +731,7 @@ int orc_LMOptimization(orc_ctx* c, int iterCount)
     { int k = 0; for (int a = 0; a < 6; a++) for (int b = a; b < 6; b++) { float v = (float)acc[k++]; AtA[a * 6 + b] = v; AtA[b * 6 + a] = v; } }
     for (int a = 0; a < 6; a++) AtB[a] = (float)acc[21 + a];
 
-    float X[6];
-    orc_solve6_qr(AtA, AtB, X);                                         /* :1240 */
-
-    if (iterCount == 0) {                                               /* :1242-1264 */
-        float E[6], V[36], V2[36], Vinv[36];
-        orc_eigen6_sym(AtA, E, V);
-        memcpy(V2, V, sizeof(V));
-        c->isDegenerate = 0;
-        for (int i = 5; i >= 0; i--) {
-            if (E[i] < c->p.eig_thresh) { for (int j = 0; j < 6; j++) V2[i * 6 + j] = 0.0f; c->isDegenerate = 1; }
-            else break;
-        }
-        orc_inv6_lu(V, Vinv);
-        for (int i = 0; i < 6; i++) for (int j = 0; j < 6; j++) {       /* matP = V.inv() * V2 */
-            double s = 0.0; for (int k = 0; k < 6; k++) s += (double)Vinv[i * 6 + k] * (double)V2[k * 6 + j];
-            c->matP[i * 6 + j] = (float)s;
-        }
-    }
-    if (c->isDegenerate) {                                              /* :1266-1271 */
-        float X2[6]; memcpy(X2, X, 24);
-        for (int i = 0; i < 6; i++) { double s = 0.0; for (int k = 0; k < 6; k++) s += (double)c->matP[i * 6 + k] * (double)X2[k]; X[i] = (float)s; }
-    }
-    for (int k = 0; k < 6; k++) c->transformTobeMapped[k] += X[k];      /* :1273-1278 */
-
-    /* pcl::rad2deg(float) = alpha * 57.29578f [ext]; pow(float, int) promotes to double */
-    double r0 = (double)(X[0] * 57.29578f), r1 = (double)(X[1] * 57.29578f), r2 = (double)(X[2] * 57.29578f);
-    float deltaR = (float)sqrt(r0 * r0 + r1 * r1 + r2 * r2);
-    double t0 = (double)(X[3] * 100), t1 = (double)(X[4] * 100), t2 = (double)(X[5] * 100);
-    float deltaT = (float)sqrt(t0 * t0 + t1 * t1 + t2 * t2);
-
-    tr->stepped = 1; memcpy(tr->delta, X, 24); memcpy(tr->pose, c->transformTobeMapped, 24);
-    tr->deltaR = deltaR; tr->deltaT = deltaT;
-    if ((double)deltaR < c->p.conv_deg && (double)deltaT < c->p.conv_cm) return 1;   /* :1289 */
-    return 0;
+    return orc_lm_close(AtA, AtB, n, iterCount, &c->p, c->transformTobeMapped, &c->isDegenerate, c->matP, tr);
 }
 
 int orc_get_normal_eq(const orc_ctx* c, float AtA[36], float AtB[6])

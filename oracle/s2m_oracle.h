@@ -87,6 +87,10 @@ void     orc_getTransformation(const float pose_rpyxyz[6], float T[12]);
 void     orc_surfOptimization(orc_ctx* c);               /* :1074-1143 */
 void     orc_combineOptimizationCoeffs(orc_ctx* c);      /* :1145-1156 */
 int      orc_LMOptimization(orc_ctx* c, int iterCount);  /* :1158-1293 */
+/* the close of LMOptimization on given normal equations: solve, degeneracy analysis (iterCount == 0), projection,
+ * pose update, convergence test; orc_LMOptimization calls it. pose / isDegenerate / matP: the node's members. */
+int      orc_lm_close(const float AtA[36], const float AtB[6], int n_sel, int iterCount, const orc_params* p,
+                      float pose[6], int* isDegenerate, float matP[36], orc_iter_trace* tr);   /* :1178-1180, :1240-1292 */
 void     orc_transformUpdate(orc_ctx* c, const orc_imu_init* imu);  /* :1323-1353 */
 void     orc_scan2MapOptimization(orc_ctx* c, const orc_imu_init* imu, orc_result* out); /* :1295-1321 */
 
