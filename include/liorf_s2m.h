@@ -348,7 +348,8 @@ int  s2m_kf_map_cloud(s2m_handle h, int first, int count, float leaf /* 0 = no f
  *     (0, 0, 0, 1) bottom row the extra terms are signed zeros, so the two forms can differ only in the sign of a zero
  *     entry of B. Eigen is not available to this repository; this stays unpinned.
  * Output records are 32 bytes on the device (pcl::PointXYZI): the handle's cloud_deskewed, which stays resident with its
- * count for s2m_downsample_projected / s2m_sc_add_projected. */
+ * count for s2m_downsample_projected / s2m_sc_add_projected.
+ * odomDeskewInfo() and findPosition() with its commented lines live: s2m_odom_deskew_info / s2m_project_scan_motion below. */
 #define S2M_RING_U8        0
 #define S2M_RING_U16       1
 #define S2M_RING_I32       2
@@ -428,6 +429,116 @@ int  s2m_downsample_projected(s2m_handle h, float leaf, void* out, size_t out_st
  * descriptor and keys are those of s2m_sc_add_scan on the downloaded cloud. S2M_ERR_NO_SCAN before the first
  * s2m_project_scan. */
 int  s2m_sc_add_projected(s2m_handle h);
+
+/* ---- odomDeskewInfo(), positional deskew and the initial pose guess ---------------------------------------
+ * The rest of the chain from a raw lidar message to a registered pose: odomDeskewInfo() (src/imageProjection.cpp:411-491),
+ * findPosition() with its commented lines live (:520-534) inside deskewPoint(), and updateInitialGuess()
+ * (src/mapOptmization.cpp:899-958). The ROS queues, imuConverter, imuPreintegration and publishOdometry()'s IMU slerp
+ * stay with the node. */
+
+/* One nav_msgs::Odometry of odomQueue as odomDeskewInfo() reads it. */
+typedef struct s2m_odom_sample {
+    double time;               /* header.stamp.toSec()                                */
+    double px, py, pz;         /* pose.pose.position                                  */
+    double qx, qy, qz, qw;     /* pose.pose.orientation                               */
+    double cov0;               /* pose.covariance[0] (imuPreintegration's reset mark) */
+} s2m_odom_sample;
+typedef struct s2m_odom_deskew {
+    int32_t odom_available;    /* cloudInfo.odomAvailable (:413, :456)                                            */
+    int32_t odom_deskew_flag;  /* odomDeskewFlag (:459, :490)                                                     */
+    float   initial_guess[6];  /* cloudInfo.initialGuessX, Y, Z, Roll, Pitch, Yaw: the message's float32 fields (:449-454) */
+    float   odom_incre[3];     /* odomIncreX, Y, Z (:488)                                                          */
+    int32_t n_popped;          /* front samples the reference pops (:415-421): the caller pops as many             */
+} s2m_odom_deskew;
+/* odomDeskewInfo() (src/imageProjection.cpp:411-491) over odom[0 .. n) in queue order. Host code: no handle, no GPU.
+ *   - the front pop (:415-421): samples with time < time_scan_cur - sync_diff_time, sync_diff_time being the reference's
+ *     `static float` (imuRate >= 300) ? 0.01 : 0.20, i.e. 0.01f or 0.20f widened to double in the subtraction; *out reports
+ *     how many were popped. The reference evaluates the static once; a caller keeps imu_rate constant.
+ *   - the remaining queue empty, or its front later than time_scan_cur: not available (:423-427). The fields of *out other
+ *     than odom_available and n_popped are then zero - the reference leaves its members as the previous scan set them;
+ *     a node that wants that keeps its own copy, as the mirrors do.
+ *   - start sample: the first with time >= time_scan_cur, else the last (:432-440); end sample likewise at time_scan_end
+ *     (:466-474), after the `back().time < time_scan_end` return (:461-462: available, flag off, odom_incre zero).
+ *   - int(round(cov0)) of the two samples differing: available, flag off (:476-477).
+ *   - roll, pitch, yaw in double. [ext] tf::Matrix3x3(q).getRPY: Matrix3x3::setRotation with s = 2 / length2(q) (a
+ *     quaternion that is not unit length is scaled, not refused), entries 1 - (yy + zz), xy - wz, ...; getEulerYPR
+ *     solution 1: |m20| >= 1 gives yaw = 0, pitch = +-pi/2, roll = atan2(m01, m02) or atan2(-m01, -m02); otherwise
+ *     pitch = -asin(m20), roll = atan2(m21 / cos(pitch), m22 / cos(pitch)), yaw = atan2(m10 / cos(pitch), m00 / cos(pitch)).
+ *   - transBegin, transEnd = pcl::getTransformation of the six values narrowed to float (its parameters are float), term
+ *     order as everywhere in this library; transBegin.inverse() * transEnd with the Affine3f conventions stated for
+ *     s2m_project_scan above ([ext] general 3x3 inverse by cofactors, translation -(Linv * t); 4x4 product accumulating
+ *     ((a0*b0 + a1*b1) + a2*b2) + a3*b3); odom_incre = its translation column (pcl::getTranslationAndEulerAngles).
+ *   tf and PCL are not available to this repository: parity unpinned, like the float chain above.
+ * odom NULL with n > 0, out NULL or a non-finite time_scan_cur / time_scan_end: S2M_ERR_INVALID_ARG. */
+int  s2m_odom_deskew_info(const s2m_odom_sample* odom, size_t n, double time_scan_cur, double time_scan_end, float imu_rate,
+                          s2m_odom_deskew* out);
+
+/* Positional deskew: what findPosition() (:520-534) adds when its commented lines are live. The reference ships them
+ * commented out ("if the sensor moves relatively slow, like walking speed ..."); a vehicle at 10-30 m/s smears a 0.1 s
+ * sweep by 1-3 m. Opt-in: */
+typedef struct s2m_motion_info {
+    int32_t enabled;           /* cloudInfo.odomAvailable && odomDeskewFlag (the test of :526); 0 = s2m_project_scan */
+    double  time_scan_end;     /* timeScanEnd (:283)                                                              */
+    float   odom_incre[3];     /* odomIncreX, Y, Z (s2m_odom_deskew.odom_incre)                                   */
+} s2m_motion_info;
+/* s2m_project_check_args plus the motion argument: with motion != NULL and motion->enabled != 0 a non-finite
+ * time_scan_end or increment is S2M_ERR_INVALID_ARG (a disabled motion's other fields are not read). */
+int  s2m_project_check_args_motion(const s2m_scan_layout* layout, const s2m_project_params* params, const s2m_deskew_info* deskew,
+                                   const s2m_motion_info* motion);
+/* s2m_project_scan with findPosition() live. motion == NULL or motion->enabled == 0: s2m_project_scan bit for bit (the
+ * same kernels), the resident cloud_deskewed and its count included. deskew->deskew == 0 copies the survivors whatever
+ * motion says (:538-539). Otherwise, per survivor, after findRotation():
+ *   float ratio = relTime / (timeScanEnd - timeScanCur) (:529): relTime is the record's float time widened to double
+ *     (:594 -> :536), the subtraction and the division are in double, the quotient is narrowed once to float;
+ *   posX, Y, Z = ratio * odom_incre[0..2], in float (:531-533);
+ *   pcl::getTransformation(posX, posY, posZ, rotX, rotY, rotZ) replaces the pure rotation in both places: the first
+ *     survivor's transform, whose own position is in general not zero, inverted into transStartInverse (:551; the
+ *     translation of the inverse is -((Linv0*t0 + Linv1*t1) + Linv2*t2) per row), and every survivor's transFinal (:556);
+ *   B = S * T as the 4x4 product above - the translation column is ((S0*pos0 + S1*pos1) + S2*pos2) + S3*1.0f - and the
+ *     output expression are unchanged.
+ * time_scan_end == time_scan_cur is not refused: the ratio is infinite or NaN as the reference's arithmetic makes it.
+ * Zero increments with enabled != 0 may differ from s2m_project_scan in the sign of a zero.
+ * Arguments, outputs, waits (three launches, one wait, a second with cap > 0), errors and the "does not touch" promise
+ * are those of s2m_project_scan. */
+int  s2m_project_scan_motion(s2m_handle h, const void* pts, size_t n, const s2m_scan_layout* layout, int on_device,
+                             const s2m_project_params* params, const s2m_deskew_info* deskew, const s2m_motion_info* motion,
+                             void* out, size_t out_stride_bytes, size_t cap, size_t* n_out);
+
+/* updateInitialGuess() (src/mapOptmization.cpp:899-958). The caller owns the three function statics of the reference: */
+typedef struct s2m_guess_state {
+    float   last_imu_transformation[12];      /* lastImuTransformation (:904), row-major 3x4                       */
+    float   last_imu_pre_transformation[12];  /* lastImuPreTransformation (:921)                                   */
+    int32_t last_imu_pre_trans_available;     /* lastImuPreTransAvailable (:920)                                   */
+} s2m_guess_state;
+/* The cloud_info fields updateInitialGuess() reads (msg/cloud_info.msg:10-24). */
+typedef struct s2m_guess_info {
+    int64_t imuAvailable;      /* tested `== true` (:945), i.e. == 1, as s2m_imu_init.imuAvailable */
+    int64_t odomAvailable;     /* tested `== true` (:922), i.e. == 1                                */
+    float   imuRollInit, imuPitchInit, imuYawInit;
+    float   initialGuess[6];   /* X, Y, Z, Roll, Pitch, Yaw (s2m_odom_deskew.initial_guess)        */
+} s2m_guess_info;
+/* The state before the first scan: lastImuPreTransAvailable = false; the two transforms all zero ([ext] a function-static
+ * Eigen::Affine3f is zero-initialised storage; the reference writes lastImuTransformation on the first scan, before any
+ * read). */
+int  s2m_guess_state_init(s2m_guess_state* st);
+/* One call of updateInitialGuess(). Host code: no handle, no GPU. pose is transformTobeMapped {roll, pitch, yaw, x, y, z},
+ * in and out: the result is what s2m_optimize* takes as pose. affine_front receives incrementalOdometryAffineFront =
+ * trans2Affine3f(pose on entry) (:902), row-major 3x4 like s2m_result.affine (incrementalOdometryAffineBack).
+ * The reference's control flow exactly:
+ *   key_poses_empty (:906-917): pose[0..2] = the three imu*Init, pose[2] = 0 unless use_imu_heading_initialization;
+ *     lastImuTransformation = getTransformation(0, 0, 0, imu*Init); return.
+ *   odomAvailable == 1 (:922-942): transBack = getTransformation(initialGuess). First time: it becomes
+ *     lastImuPreTransformation, the flag is set, and control FALLS THROUGH to the IMU branch. Later:
+ *     pose = getTranslationAndEulerAngles(trans2Affine3f(pose) * (lastImuPreTransformation.inverse() * transBack)),
+ *     lastImuPreTransformation = transBack, lastImuTransformation refreshed; return.
+ *   imuAvailable == 1 && imu_type (:945-957): the same with transBack = getTransformation(0, 0, 0, imu*Init) against
+ *     lastImuTransformation, which is refreshed; return. Otherwise nothing changes (lastImuTransformation is NOT refreshed).
+ * All in float: getTransformation in host term order with libm sinf / cosf; [ext] the Affine3f product as for the
+ * loop-closure pose result (linear = ((a0 b0 + a1 b1) + a2 b2), translation = ((a0 t0 + a1 t1) + a2 t2) + a3);
+ * [ext] inverse() as stated for s2m_project_scan; [ext] pcl::getTranslationAndEulerAngles: roll = atan2f(T21, T22),
+ * pitch = asinf(-T20), yaw = atan2f(T10, T00). Parity unpinned. */
+int  s2m_update_initial_guess(s2m_guess_state* st, float pose[6], int key_poses_empty, const s2m_guess_info* info,
+                              int use_imu_heading_initialization, int imu_type, float affine_front[12]);
 
 /* ---- ScanContext descriptor (BASELINE config 5) ------------------------- */
 /* SCManager::makeScancontext + makeRingkeyFromScancontext

@@ -24,6 +24,7 @@
 #include "s2m_voxel.hpp"
 #include "s2m_icp.hpp"
 #include "s2m_project.hpp"
+#include "s2m_front_end.hpp"
 
 using namespace s2m;
 
@@ -2705,12 +2706,21 @@ int s2m_project_check_args(const s2m_scan_layout* layout, const s2m_project_para
     return S2M_OK;
 }
 
-int s2m_project_scan(s2m_handle h, const void* pts, size_t n, const s2m_scan_layout* layout, int on_device, const s2m_project_params* params,
-                     const s2m_deskew_info* deskew, void* out, size_t out_stride_bytes, size_t cap, size_t* n_out)
+int s2m_project_check_args_motion(const s2m_scan_layout* layout, const s2m_project_params* params, const s2m_deskew_info* deskew,
+                                  const s2m_motion_info* motion)
+{
+    if (s2m_project_check_args(layout, params, deskew) != S2M_OK) return S2M_ERR_INVALID_ARG;
+    return proj_motion_ok(motion) ? S2M_OK : S2M_ERR_INVALID_ARG;
+}
+
+// s2m_project_scan (motion == nullptr) and s2m_project_scan_motion
+static int project_scan_impl(s2m_handle h, const void* pts, size_t n, const s2m_scan_layout* layout, int on_device, const s2m_project_params* params,
+                             const s2m_deskew_info* deskew, const s2m_motion_info* motion, void* out, size_t out_stride_bytes, size_t cap, size_t* n_out)
 {
     if (s2m_project_check_args(layout, params, deskew) != S2M_OK)
         return fail(h, S2M_ERR_INVALID_ARG, "scan layout (fields inside the stride, naturally aligned), project params (n_scan, downsample_rate, "
                                             "point_filter_num >= 1, finite ranges) or deskew tables (1 <= imu_pointer_cur < 2000, non-decreasing times)");
+    if (!proj_motion_ok(motion)) return fail(h, S2M_ERR_INVALID_ARG, "motion: time_scan_end and the three increments must be finite");
     s2m_project_params prm;
     if (params) prm = *params; else s2m_project_default_params(&prm);
     if (!n_out || (cap > 0 && (!out || out_stride_bytes < 12 || (out_stride_bytes & 3)))) return fail(h, S2M_ERR_INVALID_ARG, "bad output buffer");
@@ -2751,6 +2761,11 @@ int s2m_project_scan(s2m_handle h, const void* pts, size_t n, const s2m_scan_lay
     a.n = n; a.lay = *layout; a.prm = prm; a.deskew = do_deskew;
     a.imu_pointer_cur = do_deskew ? deskew->imu_pointer_cur : 0;
     a.time_scan_cur = deskew ? deskew->time_scan_cur : 0.0;
+    if (motion && motion->enabled) {                                         // findPosition() live (:526-533)
+        a.motion = 1;
+        a.time_scan_end = motion->time_scan_end;
+        for (int k = 0; k < 3; k++) a.odom_incre[k] = motion->odom_incre[k];
+    }
     a.d_table = h->proj_table.as<double>();
     a.d_mask = h->proj_mask.as<unsigned long long>();
     a.d_part = h->proj_part.as<int32_t>();
@@ -2767,6 +2782,41 @@ int s2m_project_scan(s2m_handle h, const void* pts, size_t n, const s2m_scan_lay
     h->have_deskewed = true;
     if (cap > 0 && (rc = download_records(h, h->cloud_deskewed, cnt, out, out_stride_bytes, cap))) return rc;
     if (cap > 0 && cnt > cap) return fail(h, S2M_ERR_CAPACITY, "output buffer too small for the deskewed cloud");
+    return S2M_OK;
+}
+
+int s2m_project_scan(s2m_handle h, const void* pts, size_t n, const s2m_scan_layout* layout, int on_device, const s2m_project_params* params,
+                     const s2m_deskew_info* deskew, void* out, size_t out_stride_bytes, size_t cap, size_t* n_out)
+{
+    return project_scan_impl(h, pts, n, layout, on_device, params, deskew, nullptr, out, out_stride_bytes, cap, n_out);
+}
+
+int s2m_project_scan_motion(s2m_handle h, const void* pts, size_t n, const s2m_scan_layout* layout, int on_device, const s2m_project_params* params,
+                            const s2m_deskew_info* deskew, const s2m_motion_info* motion, void* out, size_t out_stride_bytes, size_t cap,
+                            size_t* n_out)
+{
+    return project_scan_impl(h, pts, n, layout, on_device, params, deskew, motion, out, out_stride_bytes, cap, n_out);
+}
+
+// ---- odomDeskewInfo() and updateInitialGuess(): host code, no handle ---------------------------------------------------
+int s2m_odom_deskew_info(const s2m_odom_sample* odom, size_t n, double time_scan_cur, double time_scan_end, float imu_rate, s2m_odom_deskew* out)
+{
+    if ((n > 0 && !odom) || !out || !std::isfinite(time_scan_cur) || !std::isfinite(time_scan_end)) return S2M_ERR_INVALID_ARG;
+    return host_odom_deskew_info(odom, n, time_scan_cur, time_scan_end, imu_rate, out);
+}
+
+int s2m_guess_state_init(s2m_guess_state* st)
+{
+    if (!st) return S2M_ERR_INVALID_ARG;
+    std::memset(st, 0, sizeof(*st));
+    return S2M_OK;
+}
+
+int s2m_update_initial_guess(s2m_guess_state* st, float pose[6], int key_poses_empty, const s2m_guess_info* info,
+                             int use_imu_heading_initialization, int imu_type, float affine_front[12])
+{
+    if (!st || !pose || !info || !affine_front) return S2M_ERR_INVALID_ARG;
+    host_update_initial_guess(st, pose, key_poses_empty, *info, use_imu_heading_initialization, imu_type, affine_front);
     return S2M_OK;
 }
 

@@ -13,6 +13,11 @@
 //                    survivor findRotation() by bisection over the IMU table in global memory (<= 2 000 x 4 doubles, hot in
 //                    L1/L2: a real scan has about 50 entries), getTransformation, B = S * R, the point.
 //
+// k_proj_prefix and k_proj_scatter are templates over MOTION: <false> is findPosition() as the reference ships it (zeros,
+// :520-534) and is what s2m_project_scan launches; <true> is findPosition() with its commented lines live (:526-533) -
+// the position ratio * odomIncre enters both getTransformation calls (:551, :556) - and is launched by
+// s2m_project_scan_motion when motion->enabled. time_scan_end and the increments are kernel arguments (scalar loads).
+//
 // The stage moves stride * n + 32 * n_out bytes and does a few hundred flops per survivor: it is launch- and PCIe-bound.
 #include "s2m_project.hpp"
 
@@ -149,13 +154,28 @@ __device__ __forceinline__ void proj_rotation(float roll, float pitch, float yaw
     R[6] = -D;    R[7] = C * F;          R[8] = C * E;
 }
 
-// Eigen 3.3 Transform<float,3,Affine>::inverse() [ext]: S row-major 3x4 from the linear part m and the translation (0, 0, 0)
+// findPosition() with its commented lines live (:529-533): ratio = relTime / (timeScanEnd - timeScanCur), the division in
+// double (relTime is the record's float time widened, :594 -> :536), narrowed once to float; the three products in float.
+// timeScanEnd == timeScanCur gives an infinite or NaN ratio, as the reference's arithmetic would.
+struct ProjMotion { double time_scan_end; float incre_x, incre_y, incre_z; };
+struct ProjNoMotion {};
+template <bool MOTION> struct ProjMotionArg { using type = ProjNoMotion; };
+template <> struct ProjMotionArg<true> { using type = ProjMotion; };
+__device__ __forceinline__ void proj_find_position(const ProjMotion& mo, double time_scan_cur, float relTime, float t[3])
+{
+    const float ratio = (float)((double)relTime / (mo.time_scan_end - time_scan_cur));
+    t[0] = ratio * mo.incre_x; t[1] = ratio * mo.incre_y; t[2] = ratio * mo.incre_z;
+}
+
+// Eigen 3.3 Transform<float,3,Affine>::inverse() [ext]: S row-major 3x4 from the linear part m and the translation t
+// ((0, 0, 0) without MOTION)
 __device__ __forceinline__ float proj_cof(const float m[9], int i, int j)
 {
     const int i1 = (i + 1) % 3, i2 = (i + 2) % 3, j1 = (j + 1) % 3, j2 = (j + 2) % 3;
     return m[i1 * 3 + j1] * m[i2 * 3 + j2] - m[i1 * 3 + j2] * m[i2 * 3 + j1];
 }
-__device__ inline void proj_affine_inverse(const float m[9], float S[12])
+template <bool MOTION>
+__device__ inline void proj_affine_inverse(const float m[9], const float t[3], float S[12])
 {
     const float c0 = proj_cof(m, 0, 0), c1 = proj_cof(m, 1, 0), c2 = proj_cof(m, 2, 0);
     const float det = (c0 * m[0] + c1 * m[3]) + c2 * m[6];
@@ -163,7 +183,7 @@ __device__ inline void proj_affine_inverse(const float m[9], float S[12])
     float L[9];
     L[0] = c0 * invdet; L[1] = c1 * invdet; L[2] = c2 * invdet;
     for (int c = 0; c < 3; c++) { L[3 + c] = proj_cof(m, c, 1) * invdet; L[6 + c] = proj_cof(m, c, 2) * invdet; }
-    const float t0 = 0.0f, t1 = 0.0f, t2 = 0.0f;
+    const float t0 = MOTION ? t[0] : 0.0f, t1 = MOTION ? t[1] : 0.0f, t2 = MOTION ? t[2] : 0.0f;
     for (int r = 0; r < 3; r++) {
         S[r * 4 + 0] = L[r * 3 + 0]; S[r * 4 + 1] = L[r * 3 + 1]; S[r * 4 + 2] = L[r * 3 + 2];
         S[r * 4 + 3] = -((L[r * 3 + 0] * t0 + L[r * 3 + 1] * t1) + L[r * 3 + 2] * t2);
@@ -207,9 +227,11 @@ __global__ __launch_bounds__(256) void k_proj_flag(const unsigned char* __restri
 }
 
 // ---- kernel 2: exclusive prefix over the workgroups, the count, the first survivor and S -----------------------------------
+template <bool MOTION>
 __global__ __launch_bounds__(1024) void k_proj_prefix(int32_t* __restrict__ part, int nblk, const unsigned char* __restrict__ in, s2m_scan_layout lay,
                                                       int deskew, int cur, double time_scan_cur, const double* __restrict__ tab,
-                                                      float* __restrict__ start, ProjCount* __restrict__ h_count)
+                                                      float* __restrict__ start, ProjCount* __restrict__ h_count,
+                                                      typename ProjMotionArg<MOTION>::type mo)
 {
     __shared__ int32_t s_w[16], s_f[16];
     __shared__ int32_t s_base;
@@ -248,21 +270,24 @@ __global__ __launch_bounds__(1024) void k_proj_prefix(int32_t* __restrict__ part
         h_count->first = total > 0 ? first : -1;
         if (deskew && total > 0) {                                        // transStartInverse from the first survivor (:549-553)
             const unsigned char* rec = in + (size_t)first * lay.stride;
-            const double pointTime = time_scan_cur + (double)proj_load_time(rec, in, lay.off_time, lay.time_type);      // :541
-            float rx, ry, rz, R[9], S[12];
+            const float relTime = proj_load_time(rec, in, lay.off_time, lay.time_type);
+            const double pointTime = time_scan_cur + (double)relTime;                                                  // :541
+            float rx, ry, rz, R[9], S[12], t[3] = { 0.0f, 0.0f, 0.0f };
             proj_find_rotation(tab, cur, pointTime, rx, ry, rz);
+            if constexpr (MOTION) proj_find_position(mo, time_scan_cur, relTime, t);                                   // :547
             proj_rotation(rx, ry, rz, R);
-            proj_affine_inverse(R, S);
+            proj_affine_inverse<MOTION>(R, t, S);
             for (int k = 0; k < 12; k++) start[k] = S[k];
         }
     }
 }
 
 // ---- kernel 3: survivors to their places, deskewed ----------------------------------------------------------------------
+template <bool MOTION>
 __global__ __launch_bounds__(256) void k_proj_scatter(const unsigned char* __restrict__ in, s2m_scan_layout lay, int vec, int deskew, int cur,
                                                       double time_scan_cur, const double* __restrict__ tab, const float* __restrict__ start,
                                                       const unsigned long long* __restrict__ mask, const int32_t* __restrict__ part,
-                                                      unsigned char* __restrict__ out)
+                                                      unsigned char* __restrict__ out, typename ProjMotionArg<MOTION>::type mo)
 {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int base = blockIdx.x * kProjTile + wave * (kProjTile / 4);
@@ -285,18 +310,32 @@ __global__ __launch_bounds__(256) void k_proj_scatter(const unsigned char* __res
             const float inten = *reinterpret_cast<const float*>(rec + lay.off_intensity);
             float ox = x, oy = y, oz = z;                                 // deskewFlag == -1 || !imuAvailable: return *point (:538-539)
             if (deskew) {
-                const double pointTime = time_scan_cur + (double)proj_load_time(rec, in, lay.off_time, lay.time_type);  // :541
+                const float relTime = proj_load_time(rec, in, lay.off_time, lay.time_type);
+                const double pointTime = time_scan_cur + (double)relTime;                                               // :541
                 float rx, ry, rz, R[9];
                 proj_find_rotation(tab, cur, pointTime, rx, ry, rz);      // :544
-                proj_rotation(rx, ry, rz, R);                             // transFinal (:556); findPosition() returns zeros (:520-534)
-                // transBt = transStartInverse * transFinal (:557) as a 4x4 product [ext]; row 3 of both is (0, 0, 0, 1), column 3 of R (0, 0, 0, 1)
+                proj_rotation(rx, ry, rz, R);                             // transFinal (:556); without MOTION findPosition() returns zeros (:520-534)
+                // transBt = transStartInverse * transFinal (:557) as a 4x4 product [ext]; row 3 of both is (0, 0, 0, 1), column 3 of
+                // transFinal is (0, 0, 0, 1) without MOTION and (posX, posY, posZ, 1) with it
                 float Bm[12];
+                if constexpr (MOTION) {
+                    float t[3];
+                    proj_find_position(mo, time_scan_cur, relTime, t);    // :547
 #pragma unroll
-                for (int a = 0; a < 3; a++) {
+                    for (int a = 0; a < 3; a++) {
 #pragma unroll
-                    for (int b = 0; b < 3; b++)
-                        Bm[a * 4 + b] = ((S[a * 4 + 0] * R[0 * 3 + b] + S[a * 4 + 1] * R[1 * 3 + b]) + S[a * 4 + 2] * R[2 * 3 + b]) + S[a * 4 + 3] * 0.0f;
-                    Bm[a * 4 + 3] = ((S[a * 4 + 0] * 0.0f + S[a * 4 + 1] * 0.0f) + S[a * 4 + 2] * 0.0f) + S[a * 4 + 3] * 1.0f;
+                        for (int b = 0; b < 3; b++)
+                            Bm[a * 4 + b] = ((S[a * 4 + 0] * R[0 * 3 + b] + S[a * 4 + 1] * R[1 * 3 + b]) + S[a * 4 + 2] * R[2 * 3 + b]) + S[a * 4 + 3] * 0.0f;
+                        Bm[a * 4 + 3] = ((S[a * 4 + 0] * t[0] + S[a * 4 + 1] * t[1]) + S[a * 4 + 2] * t[2]) + S[a * 4 + 3] * 1.0f;
+                    }
+                } else {
+#pragma unroll
+                    for (int a = 0; a < 3; a++) {
+#pragma unroll
+                        for (int b = 0; b < 3; b++)
+                            Bm[a * 4 + b] = ((S[a * 4 + 0] * R[0 * 3 + b] + S[a * 4 + 1] * R[1 * 3 + b]) + S[a * 4 + 2] * R[2 * 3 + b]) + S[a * 4 + 3] * 0.0f;
+                        Bm[a * 4 + 3] = ((S[a * 4 + 0] * 0.0f + S[a * 4 + 1] * 0.0f) + S[a * 4 + 2] * 0.0f) + S[a * 4 + 3] * 1.0f;
+                    }
                 }
                 ox = ((Bm[0] * x + Bm[1] * y) + Bm[2] * z) + Bm[3];       // :560-562
                 oy = ((Bm[4] * x + Bm[5] * y) + Bm[6] * z) + Bm[7];
@@ -319,10 +358,18 @@ hipError_t proj_launch(hipStream_t stream, const ProjArgs& a)
     const int vec = (l.stride % 16 == 0 && l.off_x % 16 == 0 && (uint64_t)l.off_x + 16 <= l.stride &&
                      (reinterpret_cast<uintptr_t>(a.d_in) & 15) == 0) ? 1 : 0;
     hipLaunchKernelGGL(k_proj_flag, dim3(nblk), dim3(256), 0, stream, a.d_in, (int)a.n, a.lay, a.prm, vec, a.d_mask, a.d_part);
-    hipLaunchKernelGGL(k_proj_prefix, dim3(1), dim3(1024), 0, stream, a.d_part, nblk, a.d_in, a.lay, a.deskew, a.imu_pointer_cur,
-                       a.time_scan_cur, a.d_table, a.d_start, a.h_count);
-    hipLaunchKernelGGL(k_proj_scatter, dim3(nblk), dim3(256), 0, stream, a.d_in, a.lay, vec, a.deskew, a.imu_pointer_cur, a.time_scan_cur,
-                       a.d_table, (const float*)a.d_start, (const unsigned long long*)a.d_mask, (const int32_t*)a.d_part, a.d_out);
+    if (a.motion && a.deskew) {                                           // deskew == 0 copies whatever motion says (:538-539)
+        const ProjMotion mo{ a.time_scan_end, a.odom_incre[0], a.odom_incre[1], a.odom_incre[2] };
+        hipLaunchKernelGGL(k_proj_prefix<true>, dim3(1), dim3(1024), 0, stream, a.d_part, nblk, a.d_in, a.lay, a.deskew, a.imu_pointer_cur,
+                           a.time_scan_cur, a.d_table, a.d_start, a.h_count, mo);
+        hipLaunchKernelGGL(k_proj_scatter<true>, dim3(nblk), dim3(256), 0, stream, a.d_in, a.lay, vec, a.deskew, a.imu_pointer_cur, a.time_scan_cur,
+                           a.d_table, (const float*)a.d_start, (const unsigned long long*)a.d_mask, (const int32_t*)a.d_part, a.d_out, mo);
+        return hipGetLastError();
+    }
+    hipLaunchKernelGGL(k_proj_prefix<false>, dim3(1), dim3(1024), 0, stream, a.d_part, nblk, a.d_in, a.lay, a.deskew, a.imu_pointer_cur,
+                       a.time_scan_cur, a.d_table, a.d_start, a.h_count, ProjNoMotion{});
+    hipLaunchKernelGGL(k_proj_scatter<false>, dim3(nblk), dim3(256), 0, stream, a.d_in, a.lay, vec, a.deskew, a.imu_pointer_cur, a.time_scan_cur,
+                       a.d_table, (const float*)a.d_start, (const unsigned long long*)a.d_mask, (const int32_t*)a.d_part, a.d_out, ProjNoMotion{});
     return hipGetLastError();
 }
 

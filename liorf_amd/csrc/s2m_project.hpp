@@ -42,6 +42,9 @@ struct ProjArgs {
     float*               d_start;
     unsigned char*       d_out;            // room for ceil(n / point_filter_num) records of kProjOutStride bytes
     ProjCount*           h_count;          // pinned, written by the device
+    int                  motion;           // findPosition() with its commented lines live (:526-533); acts only with deskew != 0
+    double               time_scan_end;    // (read when motion != 0)
+    float                odom_incre[3];
 };
 
 // Enqueues the three kernels on `stream` (n > 0); the count is in *h_count once the stream has drained.

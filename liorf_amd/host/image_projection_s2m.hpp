@@ -1,10 +1,11 @@
 // image_projection_s2m.hpp - C++ mirror of the cloud path of the reference's ImageProjection node (src/imageProjection.cpp)
-// over the C ABI of include/liorf_s2m.h: member and method names are the reference's. imuDeskewInfo() runs on the host,
+// over the C ABI of include/liorf_s2m.h: member and method names are the reference's. imuDeskewInfo() and odomDeskewInfo() run on the host,
 // projectPointCloud() on the device of the handle it is given (a MapOptimizationS2M's), where cloud_deskewed stays for
 // MapOptimizationS2M::downsampleCurrentScanProjected() and SCManagerS2M::makeAndSaveScancontextAndKeysProjected().
 #pragma once
 #include <array>
 #include <cstring>
+#include <deque>
 #include <stdexcept>
 #include <string>
 #include <vector>
@@ -34,6 +35,13 @@ public:
     bool imuAvailable = false;                         // cloudInfo.imuAvailable
     std::vector<PointXYZI> fullCloud;                  // host copy of cloud_deskewed, filled on request
     size_t fullCloudNum = 0;
+    float imuRate = 500.0f;                            // include/utility.h:212
+    std::deque<s2m_odom_sample> odomQueue;             // stand-in for odomQueue (:77): the node pushes, odomDeskewInfo() pops
+    bool odomAvailable = false;                        // cloudInfo.odomAvailable
+    bool odomDeskewFlag = false;                       // (:102)
+    float odomIncreX = 0, odomIncreY = 0, odomIncreZ = 0;      // (:103-105)
+    float initialGuess[6] = { 0, 0, 0, 0, 0, 0 };      // cloudInfo.initialGuessX, Y, Z, Roll, Pitch, Yaw
+    bool positionalDeskew = false;                     // findPosition() with its commented lines live (:526-533); off = the reference as shipped
 
     // the part of cachePointCloud() (:206-343) the cloud path needs: the raw bytes stay as they are; timeScanCur = header stamp,
     // timeScanEnd = timeScanCur + time of the last record (:282-283)
@@ -67,7 +75,34 @@ public:
         imuAvailable = avail != 0;
     }
 
-    // void projectPointCloud() (:568-598): cloud_deskewed stays on the device; fullCloud is filled when readback is set
+    // void odomDeskewInfo() (:411-491) on odomQueue: pops its front as the reference does; like the reference's members,
+    // initialGuess and odomIncre keep their previous values where the reference does not write them
+    void odomDeskewInfo()
+    {
+        const std::vector<s2m_odom_sample> q(odomQueue.begin(), odomQueue.end());
+        s2m_odom_deskew r{};
+        if (s2m_odom_deskew_info(q.empty() ? nullptr : q.data(), q.size(), timeScanCur, timeScanEnd, imuRate, &r) != S2M_OK)
+            throw std::runtime_error("s2m_odom_deskew_info: scan times are not finite");
+        odomQueue.erase(odomQueue.begin(), odomQueue.begin() + r.n_popped);
+        odomAvailable = r.odom_available != 0;
+        if (r.odom_available) {
+            std::memcpy(initialGuess, r.initial_guess, sizeof(initialGuess));
+            odomDeskewFlag = r.odom_deskew_flag != 0;
+        }
+        if (r.odom_deskew_flag) { odomIncreX = r.odom_incre[0]; odomIncreY = r.odom_incre[1]; odomIncreZ = r.odom_incre[2]; }
+    }
+
+    // cloudInfo.odomAvailable and the six initialGuess fields, as publishClouds() sends them to mapOptimization (:602-604)
+    void fillCloudInfo(CloudInfo& ci) const
+    {
+        ci.odomAvailable = odomAvailable ? 1 : 0;
+        ci.initialGuessX = initialGuess[0]; ci.initialGuessY = initialGuess[1]; ci.initialGuessZ = initialGuess[2];
+        ci.initialGuessRoll = initialGuess[3]; ci.initialGuessPitch = initialGuess[4]; ci.initialGuessYaw = initialGuess[5];
+        ci.imuAvailable = imuAvailable ? 1 : 0;
+    }
+
+    // void projectPointCloud() (:568-598): cloud_deskewed stays on the device; fullCloud is filled when readback is set.
+    // With positionalDeskew set, and odomAvailable and odomDeskewFlag (:526), findPosition()'s commented lines are live.
     void projectPointCloud(bool readback = true)
     {
         s2m_deskew_info d{};
@@ -78,7 +113,13 @@ public:
         const size_t cap = readback ? (n_ + (size_t)params.point_filter_num - 1) / (size_t)params.point_filter_num : 0;
         if (readback) fullCloud.resize(cap);
         size_t n_out = 0;
-        const int rc = s2m_project_scan(h_, raw_, n_, &layout, 0, &params, &d, readback ? fullCloud.data() : nullptr, sizeof(PointXYZI), cap, &n_out);
+        s2m_motion_info mo{};
+        mo.enabled = (positionalDeskew && odomAvailable && odomDeskewFlag) ? 1 : 0;
+        mo.time_scan_end = timeScanEnd;
+        mo.odom_incre[0] = odomIncreX; mo.odom_incre[1] = odomIncreY; mo.odom_incre[2] = odomIncreZ;
+        const int rc = mo.enabled
+            ? s2m_project_scan_motion(h_, raw_, n_, &layout, 0, &params, &d, &mo, readback ? fullCloud.data() : nullptr, sizeof(PointXYZI), cap, &n_out)
+            : s2m_project_scan(h_, raw_, n_, &layout, 0, &params, &d, readback ? fullCloud.data() : nullptr, sizeof(PointXYZI), cap, &n_out);
         if (rc != S2M_OK) throw std::runtime_error(std::string("s2m_project_scan: ") + s2m_last_error(h_));
         if (readback) fullCloud.resize(n_out);
         fullCloudNum = n_out;

@@ -62,6 +62,8 @@ public:
     float transformTobeMapped[6] = { 0, 0, 0, 0, 0, 0 };   // roll,pitch,yaw,x,y,z (:134)
     bool  isDegenerate = false;                       // (:139)
     float incrementalOdometryAffineBack[12] = { 0 };  // row-major 3x4 (:157)
+    float incrementalOdometryAffineFront[12] = { 0 }; // row-major 3x4 (:156), set by updateInitialGuess()
+    bool  useImuHeadingInitialization = false;        // include/utility.h:170
     CloudInfo cloudInfo;                              // (:99)
     bool  haveKeyPoses = false;                       // !cloudKeyPoses3D->points.empty() (:1297)
     // ParamServer values the path reads (include/utility.h:211-233)
@@ -76,6 +78,7 @@ public:
         s2m_default_params(&p);
         p.device_id = device_id;
         p.stream = hip_stream;
+        s2m_guess_state_init(&guessState_);
         const int rc = s2m_create(&p, &h_);       // the ParamServer members below are pushed before every call (pushParams)
         if (rc != S2M_OK)
             throw std::runtime_error("s2m_create failed (" + std::to_string(rc) + "): no gfx950 device; there is no CPU fallback");
@@ -269,6 +272,20 @@ public:
         check(s2m_set_params(h_, &p), "s2m_set_params");
     }
 
+    // void updateInitialGuess() (:899-958): transformTobeMapped becomes the pose scan2MapOptimization() starts from,
+    // incrementalOdometryAffineFront the transform before the update; the three function statics live in guessState_.
+    // haveKeyPoses is !cloudKeyPoses3D->points.empty() (:906).
+    void updateInitialGuess()
+    {
+        s2m_guess_info ci{};
+        ci.imuAvailable = cloudInfo.imuAvailable; ci.odomAvailable = cloudInfo.odomAvailable;
+        ci.imuRollInit = cloudInfo.imuRollInit; ci.imuPitchInit = cloudInfo.imuPitchInit; ci.imuYawInit = cloudInfo.imuYawInit;
+        ci.initialGuess[0] = cloudInfo.initialGuessX; ci.initialGuess[1] = cloudInfo.initialGuessY; ci.initialGuess[2] = cloudInfo.initialGuessZ;
+        ci.initialGuess[3] = cloudInfo.initialGuessRoll; ci.initialGuess[4] = cloudInfo.initialGuessPitch; ci.initialGuess[5] = cloudInfo.initialGuessYaw;
+        check(s2m_update_initial_guess(&guessState_, transformTobeMapped, haveKeyPoses ? 0 : 1, &ci, useImuHeadingInitialization ? 1 : 0, imuType,
+                                       incrementalOdometryAffineFront), "s2m_update_initial_guess");
+    }
+
     // void scan2MapOptimization() (:1295-1321)
     void scan2MapOptimization()
     {
@@ -424,6 +441,7 @@ private:
     void checkVoxel(int rc, const char* what) { if (rc != S2M_WARN_LEAF_TOO_SMALL) check(rc, what); }
     s2m_handle h_ = nullptr;
     bool scanResident_ = false;
+    s2m_guess_state guessState_{};                    // lastImuTransformation, lastImuPreTransformation, lastImuPreTransAvailable (:904, :920-921)
 };
 
 // SCManager (reference include/Scancontext.h:56-113) on top of the same handle: the descriptor store and the

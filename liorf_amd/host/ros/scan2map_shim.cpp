@@ -16,6 +16,7 @@
 #include "utility.h"                 // the reference's: PointType, PointTypePose, ParamServer members, pcl, ROS logging
 
 #include <cstring>
+#include <deque>
 #include <stdexcept>
 #include <vector>
 
@@ -126,6 +127,56 @@ public:
         incrementalOdometryAffineBack = Eigen::Affine3f(m);                                      // :1352
     }
 
+    // updateInitialGuess (:899-958): host code of the library; the three function statics of the reference live in guess_.
+    void updateInitialGuess(bool keyPosesEmpty, const liorf::cloud_info& cloudInfo, bool useImuHeadingInitialization, int imuType,
+                            float transformTobeMapped[6], Eigen::Affine3f& incrementalOdometryAffineFront)
+    {
+        s2m_guess_info ci{};
+        ci.imuAvailable = cloudInfo.imuAvailable; ci.odomAvailable = cloudInfo.odomAvailable;
+        ci.imuRollInit = cloudInfo.imuRollInit; ci.imuPitchInit = cloudInfo.imuPitchInit; ci.imuYawInit = cloudInfo.imuYawInit;
+        ci.initialGuess[0] = cloudInfo.initialGuessX; ci.initialGuess[1] = cloudInfo.initialGuessY; ci.initialGuess[2] = cloudInfo.initialGuessZ;
+        ci.initialGuess[3] = cloudInfo.initialGuessRoll; ci.initialGuess[4] = cloudInfo.initialGuessPitch; ci.initialGuess[5] = cloudInfo.initialGuessYaw;
+        float front[12];
+        check(s2m_update_initial_guess(&guess_, transformTobeMapped, keyPosesEmpty ? 1 : 0, &ci, useImuHeadingInitialization ? 1 : 0, imuType, front),
+              "s2m_update_initial_guess");
+        Eigen::Matrix4f m = Eigen::Matrix4f::Identity();
+        for (int r = 0; r < 3; r++) for (int c = 0; c < 4; c++) m(r, c) = front[4 * r + c];
+        incrementalOdometryAffineFront = Eigen::Affine3f(m);                                     // :902
+    }
+
+    // odomDeskewInfo (src/imageProjection.cpp:411-491) for a node that runs the front end in this process: the queue's
+    // samples are copied out, the library's count of popped samples is applied to the queue. Members the reference leaves
+    // untouched on an early return stay untouched.
+    void odomDeskewInfo(std::deque<nav_msgs::Odometry>& odomQueue, double timeScanCur, double timeScanEnd, float imuRate,
+                        liorf::cloud_info& cloudInfo, bool& odomDeskewFlag, float& odomIncreX, float& odomIncreY, float& odomIncreZ)
+    {
+        std::vector<s2m_odom_sample> q;
+        for (const nav_msgs::Odometry& o : odomQueue)
+            q.push_back(s2m_odom_sample{ o.header.stamp.toSec(), o.pose.pose.position.x, o.pose.pose.position.y, o.pose.pose.position.z,
+                                         o.pose.pose.orientation.x, o.pose.pose.orientation.y, o.pose.pose.orientation.z, o.pose.pose.orientation.w,
+                                         o.pose.covariance[0] });
+        s2m_odom_deskew r{};
+        check(s2m_odom_deskew_info(q.data(), q.size(), timeScanCur, timeScanEnd, imuRate, &r), "s2m_odom_deskew_info");
+        odomQueue.erase(odomQueue.begin(), odomQueue.begin() + r.n_popped);
+        cloudInfo.odomAvailable = r.odom_available != 0;
+        if (!r.odom_available) return;
+        cloudInfo.initialGuessX = r.initial_guess[0]; cloudInfo.initialGuessY = r.initial_guess[1]; cloudInfo.initialGuessZ = r.initial_guess[2];
+        cloudInfo.initialGuessRoll = r.initial_guess[3]; cloudInfo.initialGuessPitch = r.initial_guess[4]; cloudInfo.initialGuessYaw = r.initial_guess[5];
+        odomDeskewFlag = r.odom_deskew_flag != 0;
+        if (r.odom_deskew_flag) { odomIncreX = r.odom_incre[0]; odomIncreY = r.odom_incre[1]; odomIncreZ = r.odom_incre[2]; }
+    }
+
+    // The argument that turns findPosition()'s commented lines (:526-533) on in s2m_project_scan_motion.
+    static s2m_motion_info motionInfo(bool positionalDeskew, const liorf::cloud_info& cloudInfo, bool odomDeskewFlag, double timeScanEnd,
+                                      float odomIncreX, float odomIncreY, float odomIncreZ)
+    {
+        s2m_motion_info m{};
+        m.enabled = (positionalDeskew && cloudInfo.odomAvailable && odomDeskewFlag) ? 1 : 0;
+        m.time_scan_end = timeScanEnd;
+        m.odom_incre[0] = odomIncreX; m.odom_incre[1] = odomIncreY; m.odom_incre[2] = odomIncreZ;
+        return m;
+    }
+
 private:
     void check(int rc, const char* what)
     {
@@ -133,6 +184,7 @@ private:
     }
     s2m_handle h_ = nullptr;
     bool haveMap_ = false;
+    s2m_guess_state guess_{};                 // zero, as s2m_guess_state_init leaves it
 };
 
 }  // namespace liorf_amd
@@ -153,4 +205,9 @@ private:
 //       gpu.pushParams(imuType, imuRPYWeight, z_tollerance, rotation_tollerance);
 //       gpu.scan2MapOptimization(cloudKeyPoses3D->points.empty(), laserCloudSurfLastDSNum, cloudInfo, transformTobeMapped,
 //                                isDegenerate, incrementalOdometryAffineBack);
+//   }
+//   void updateInitialGuess()
+//   {
+//       gpu.updateInitialGuess(cloudKeyPoses3D->points.empty(), cloudInfo, useImuHeadingInitialization, imuType, transformTobeMapped,
+//                              incrementalOdometryAffineFront);
 //   }

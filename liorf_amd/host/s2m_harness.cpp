@@ -22,6 +22,11 @@
 //       the front end: cachePointCloud() of the raw records (sensor 0..4), imuDeskewInfo() over the samples of imu.bin
 //       ({time, wx, wy, wz} doubles), projectPointCloud(), downsampleCurrentScanProjected(), the ScanContext add from the
 //       resident cloud; fullCloud goes to out.bin, laserCloudSurfLastDS to ds.bin; prints the counts.
+//   s2m_harness --front-end raw.bin sensor stamp imu.bin odom.bin n_scan downsample_rate point_filter_num scan_leaf positional imu_rate out.bin
+//       the whole front end of one scan: cachePointCloud(), imuDeskewInfo(), odomDeskewInfo() over the samples of odom.bin ({time, px, py, pz, qx,
+//       qy, qz, qw, cov0} doubles), projectPointCloud() with positional deskew when `positional` is 1,
+//       downsampleCurrentScanProjected(), updateInitialGuess() three times (no key poses; first odometry sample; odometry
+//       increment of a queue shifted by its own increment); fullCloud goes to out.bin; prints the guess, the counts and a checksum.
 #include <array>
 #include <cstdio>
 #include <cstdlib>
@@ -241,6 +246,70 @@ static int run_project(char** argv)
     return 0;
 }
 
+template <typename T>
+static std::vector<T> read_records(const char* path)
+{
+    std::ifstream f(path, std::ios::binary | std::ios::ate);
+    if (!f) throw std::runtime_error(std::string("cannot open ") + path);
+    std::vector<T> v((size_t)f.tellg() / sizeof(T));
+    f.seekg(0);
+    f.read(reinterpret_cast<char*>(v.data()), (std::streamsize)(v.size() * sizeof(T)));
+    return v;
+}
+
+static int run_front_end(char** argv)
+{
+    liorf_amd::MapOptimizationS2M node;
+    liorf_amd::ImageProjectionS2M proj(node.handle(), std::atoi(argv[3]));
+    const std::vector<unsigned char> raw = read_records<unsigned char>(argv[2]);
+    const std::vector<std::array<double, 4>> imu = read_records<std::array<double, 4>>(argv[5]);
+    const std::vector<s2m_odom_sample> odom = read_records<s2m_odom_sample>(argv[6]);
+    proj.params.n_scan = std::atoi(argv[7]);
+    proj.params.downsample_rate = std::atoi(argv[8]);
+    proj.params.point_filter_num = std::atoi(argv[9]);
+    node.mappingSurfLeafSize = (float)std::atof(argv[10]);
+    proj.positionalDeskew = std::atoi(argv[11]) != 0;
+    proj.imuRate = (float)std::atof(argv[12]);
+    proj.odomQueue.assign(odom.begin(), odom.end());
+    proj.cachePointCloud(raw.data(), raw.size(), std::atof(argv[4]));
+    proj.imuDeskewInfo(imu);
+    proj.odomDeskewInfo();
+    proj.projectPointCloud();
+    node.downsampleCurrentScanProjected(proj.fullCloudNum);
+    std::ofstream o(argv[13], std::ios::binary);
+    o.write(reinterpret_cast<const char*>(proj.fullCloud.data()), (std::streamsize)(proj.fullCloud.size() * sizeof(liorf_amd::PointXYZI)));
+    if (!o) throw std::runtime_error(std::string("cannot write ") + argv[13]);
+    uint64_t sum = 0;                                   // checksum of fullCloud: the 32-bit words added up
+    const uint32_t* w = reinterpret_cast<const uint32_t*>(proj.fullCloud.data());
+    for (size_t k = 0; k < proj.fullCloud.size() * (sizeof(liorf_amd::PointXYZI) / 4); k++) sum += w[k];
+    std::printf("timeScanEnd %.17g imuPointerCur %d imuAvailable %d\n", proj.timeScanEnd, proj.imuPointerCur, proj.imuAvailable ? 1 : 0);
+    std::printf("odomAvailable %d odomDeskewFlag %d queue %zu\n", proj.odomAvailable ? 1 : 0, proj.odomDeskewFlag ? 1 : 0, proj.odomQueue.size());
+    std::printf("odomIncre %.9g %.9g %.9g\n", proj.odomIncreX, proj.odomIncreY, proj.odomIncreZ);
+    std::printf("initialGuess %.9g %.9g %.9g %.9g %.9g %.9g\n", proj.initialGuess[0], proj.initialGuess[1], proj.initialGuess[2], proj.initialGuess[3],
+                proj.initialGuess[4], proj.initialGuess[5]);
+    std::printf("fullCloud %zu laserCloudSurfLastDSNum %d checksum %llu\n", proj.fullCloud.size(), node.laserCloudSurfLastDSNum, (unsigned long long)sum);
+    // updateInitialGuess(): no key poses; then with key poses the first odometry sample (falls through to the IMU branch);
+    // then the same guess moved by odomIncre, as the next scan's odometry would be
+    node.imuType = 1;
+    node.useImuHeadingInitialization = true;
+    proj.fillCloudInfo(node.cloudInfo);
+    node.cloudInfo.imuRollInit = 0.01f; node.cloudInfo.imuPitchInit = -0.02f; node.cloudInfo.imuYawInit = proj.initialGuess[5];
+    for (int step = 0; step < 3; step++) {
+        node.haveKeyPoses = step > 0;
+        if (step == 2) {
+            node.cloudInfo.initialGuessX += proj.odomIncreX; node.cloudInfo.initialGuessY += proj.odomIncreY; node.cloudInfo.initialGuessZ += proj.odomIncreZ;
+            node.cloudInfo.imuYawInit += 0.005f;
+        }
+        node.updateInitialGuess();
+        std::printf("guess%d %.9g %.9g %.9g %.9g %.9g %.9g\n", step, node.transformTobeMapped[0], node.transformTobeMapped[1], node.transformTobeMapped[2],
+                    node.transformTobeMapped[3], node.transformTobeMapped[4], node.transformTobeMapped[5]);
+        std::printf("front%d", step);
+        for (int k = 0; k < 12; k++) std::printf(" %.9g", node.incrementalOdometryAffineFront[k]);
+        std::printf("\n");
+    }
+    return 0;
+}
+
 // --many map.bin roll pitch yaw x y z scan0.bin scan1.bin ...: the same initial guess for every scan; the scans once as a batch
 // (scan2MapOptimizationBatch), once as a stream through two slots (prepareNextScan / launchSlot / collectSlot), once one by one
 // (scan2MapOptimization): prints "batch|stream|single <i> iters <n> pose ..." - the three must agree bit for bit.
@@ -292,6 +361,7 @@ int main(int argc, char** argv)
         if (argc == 9 && std::string(argv[1]) == "--loop") return run_loop(argv);
         if (argc == 9 && std::string(argv[1]) == "--global-map") return run_global_map(argv);
         if (argc == 12 && std::string(argv[1]) == "--project") return run_project(argv);
+        if (argc == 14 && std::string(argv[1]) == "--front-end") return run_front_end(argv);
         if (argc != 9 && argc != 16) {
             std::fprintf(stderr, "usage: %s map.bin scan.bin roll pitch yaw x y z [imuType imuRPYWeight z_tol rot_tol imuAvailable imuRoll imuPitch]\n", argv[0]);
             return 2;

@@ -42,6 +42,7 @@ ABI_SYMBOLS = [
     "s2m_gmap_default_params", "s2m_global_map", "s2m_kf_map_cloud",
     "s2m_scan_layout_preset", "s2m_project_default_params", "s2m_imu_deskew_info", "s2m_project_check_args", "s2m_project_scan",
     "s2m_downsample_projected", "s2m_sc_add_projected",
+    "s2m_odom_deskew_info", "s2m_project_check_args_motion", "s2m_project_scan_motion", "s2m_guess_state_init", "s2m_update_initial_guess",
 ]
 S2M_RING_U8, S2M_RING_U16, S2M_RING_I32 = 0, 1, 2
 S2M_TIME_F32, S2M_TIME_U32_NS, S2M_TIME_U32, S2M_TIME_F64_REL = 0, 1, 2, 3
@@ -131,6 +132,30 @@ class DeskewInfo(C.Structure):
     _fields_ = [("time_scan_cur", C.c_double), ("deskew", C.c_int32), ("imu_pointer_cur", C.c_int32),
                 ("imu_time", C.POINTER(C.c_double)), ("imu_rot_x", C.POINTER(C.c_double)),
                 ("imu_rot_y", C.POINTER(C.c_double)), ("imu_rot_z", C.POINTER(C.c_double))]
+
+
+class OdomSample(C.Structure):
+    _fields_ = [("time", C.c_double), ("px", C.c_double), ("py", C.c_double), ("pz", C.c_double), ("qx", C.c_double),
+                ("qy", C.c_double), ("qz", C.c_double), ("qw", C.c_double), ("cov0", C.c_double)]
+
+
+class OdomDeskew(C.Structure):
+    _fields_ = [("odom_available", C.c_int32), ("odom_deskew_flag", C.c_int32), ("initial_guess", C.c_float * 6),
+                ("odom_incre", C.c_float * 3), ("n_popped", C.c_int32)]
+
+
+class MotionInfo(C.Structure):
+    _fields_ = [("enabled", C.c_int32), ("time_scan_end", C.c_double), ("odom_incre", C.c_float * 3)]
+
+
+class GuessState(C.Structure):
+    _fields_ = [("last_imu_transformation", C.c_float * 12), ("last_imu_pre_transformation", C.c_float * 12),
+                ("last_imu_pre_trans_available", C.c_int32)]
+
+
+class GuessInfo(C.Structure):
+    _fields_ = [("imuAvailable", C.c_int64), ("odomAvailable", C.c_int64), ("imuRollInit", C.c_float), ("imuPitchInit", C.c_float),
+                ("imuYawInit", C.c_float), ("initialGuess", C.c_float * 6)]
 
 
 class S2MError(RuntimeError):
@@ -247,6 +272,13 @@ def load_library(path: str | None = None) -> C.CDLL:
                                    C.POINTER(DeskewInfo), vp, C.c_size_t, C.c_size_t, szp]
     L.s2m_downsample_projected.argtypes = [vp, C.c_float, vp, C.c_size_t, C.c_size_t, szp]
     L.s2m_sc_add_projected.argtypes = [vp]
+    L.s2m_odom_deskew_info.argtypes = [C.POINTER(OdomSample), C.c_size_t, C.c_double, C.c_double, C.c_float, C.POINTER(OdomDeskew)]
+    L.s2m_project_check_args_motion.argtypes = [C.POINTER(ScanLayout), C.POINTER(ProjectParams), C.POINTER(DeskewInfo), C.POINTER(MotionInfo)]
+    L.s2m_project_scan_motion.argtypes = [vp, vp, C.c_size_t, C.POINTER(ScanLayout), C.c_int, C.POINTER(ProjectParams),
+                                          C.POINTER(DeskewInfo), C.POINTER(MotionInfo), vp, C.c_size_t, C.c_size_t, szp]
+    L.s2m_guess_state_init.argtypes = [C.POINTER(GuessState)]
+    L.s2m_update_initial_guess.argtypes = [C.POINTER(GuessState), C.POINTER(C.c_float), C.c_int, C.POINTER(GuessInfo), C.c_int, C.c_int,
+                                           C.POINTER(C.c_float)]
     if path is None:
         _LIB = L
     return L
@@ -297,6 +329,9 @@ class MapOptimizationS2M:
         self.transformTobeMapped = np.zeros(6, np.float32)     # reference :134
         self.isDegenerate = False                              # reference :139
         self.incrementalOdometryAffineBack = np.zeros((3, 4), np.float32)   # reference :157
+        self.incrementalOdometryAffineFront = np.zeros((3, 4), np.float32)  # reference :156
+        self.guessState = GuessState()                         # the three function statics of updateInitialGuess() (:904, :920-921)
+        self.lib.s2m_guess_state_init(C.byref(self.guessState))
         self.laserCloudSurfLastDSNum = 0
         self.last_result: Result | None = None
 
@@ -452,6 +487,21 @@ class MapOptimizationS2M:
         self._check(self.lib.s2m_sc_add_projected(self.h), "s2m_sc_add_projected")
 
     # -- the path ----------------------------------------------------------
+    def updateInitialGuess(self, cloudInfo: GuessInfo, key_poses_empty: bool | None = None, useImuHeadingInitialization: bool = False) -> np.ndarray:
+        """updateInitialGuess() (reference :899-958, s2m_update_initial_guess, host code): transformTobeMapped becomes the
+        pose scan2MapOptimization() starts from and incrementalOdometryAffineFront the transform before the update.
+        key_poses_empty defaults to the resident key-frame store being empty (cloudKeyPoses3D->points.empty(), :906)."""
+        if key_poses_empty is None:
+            key_poses_empty = self.kfSize() == 0
+        pose = np.ascontiguousarray(self.transformTobeMapped, np.float32).copy()
+        front = np.zeros(12, np.float32)
+        self._check(self.lib.s2m_update_initial_guess(C.byref(self.guessState), _fp(pose), 1 if key_poses_empty else 0, C.byref(cloudInfo),
+                                                      1 if useImuHeadingInitialization else 0, int(self.params.imu_type), _fp(front)),
+                    "s2m_update_initial_guess")
+        self.transformTobeMapped = pose
+        self.incrementalOdometryAffineFront = front.reshape(3, 4)
+        return pose
+
     def scan2MapOptimization(self, imu: ImuInit | None = None) -> Result:
         """Reference :1295-1321 on the resident scan and map; updates transformTobeMapped."""
         r = Result()
@@ -925,6 +975,27 @@ def make_deskew_info(time_scan_cur: float, deskew: bool, imu_pointer_cur: int, i
     return d
 
 
+def odom_deskew_info(odom, time_scan_cur: float, time_scan_end: float, imu_rate: float = 500.0) -> OdomDeskew:
+    """s2m_odom_deskew_info (host code, no GPU): odom is (n, 9) float64 {time, px, py, pz, qx, qy, qz, qw, cov0} in queue order."""
+    a = np.ascontiguousarray(odom, np.float64).reshape(-1, 9)
+    out = OdomDeskew()
+    rc = load_library().s2m_odom_deskew_info(a.ctypes.data_as(C.POINTER(OdomSample)), a.shape[0], float(time_scan_cur), float(time_scan_end),
+                                             float(imu_rate), C.byref(out))
+    if rc != S2M_OK:
+        raise S2MError(f"s2m_odom_deskew_info: {ERRORS.get(rc, rc)}")
+    return out
+
+
+def make_motion_info(enabled: bool, time_scan_end: float, odom_incre) -> MotionInfo:
+    return MotionInfo(1 if enabled else 0, float(time_scan_end), (C.c_float * 3)(*[float(v) for v in odom_incre]))
+
+
+def make_guess_info(imuAvailable=0, odomAvailable=0, imu=(0.0, 0.0, 0.0), guess=(0.0,) * 6) -> GuessInfo:
+    """The cloud_info fields updateInitialGuess() reads: imu = imuRollInit, imuPitchInit, imuYawInit; guess = initialGuessX, Y, Z,
+    Roll, Pitch, Yaw."""
+    return GuessInfo(int(imuAvailable), int(odomAvailable), float(imu[0]), float(imu[1]), float(imu[2]), (C.c_float * 6)(*[float(v) for v in guess]))
+
+
 class ImageProjectionS2M:
     """The cloud path of the reference's ImageProjection node (src/imageProjection.cpp) over a MapOptimizationS2M's
     handle: imuDeskewInfo() on the host, projectPointCloud() on the device. The deskewed cloud stays resident on that
@@ -948,6 +1019,13 @@ class ImageProjectionS2M:
         self.fullCloud = None
         self.fullCloudNum = 0
         self._raw = None
+        self.imuRate = 500.0                                   # include/utility.h:212
+        self.positionalDeskew = False                          # findPosition() with its commented lines live (:526-533); off = the reference as shipped
+        self.odomAvailable = False                             # cloudInfo.odomAvailable
+        self.odomDeskewFlag = False
+        self.odomIncre = np.zeros(3, np.float32)               # odomIncreX, Y, Z
+        self.initialGuess = np.zeros(6, np.float32)            # cloudInfo.initialGuessX, Y, Z, Roll, Pitch, Yaw
+        self.odomQueue = np.zeros((0, 9), np.float64)          # stand-in for odomQueue: rows {time, px, py, pz, qx, qy, qz, qw, cov0}
 
     def record_times(self, raw: np.ndarray) -> np.ndarray:
         """laserCloudIn->points[i].time of every record, as the conversion loops leave it (:216-274)."""
@@ -983,14 +1061,36 @@ class ImageProjectionS2M:
             raise S2MError(f"s2m_imu_deskew_info: {ERRORS.get(rc, rc)}")
         return self.imuAvailable
 
+    def odomDeskewInfo(self, odom=None) -> bool:
+        """odomDeskewInfo() (:411-491) on odomQueue (or on `odom`, which then becomes the queue): pops the front of the queue as
+        the reference does and sets odomAvailable, initialGuess, odomDeskewFlag and odomIncre. Like the reference's members,
+        initialGuess and odomIncre keep their previous values where the reference does not write them."""
+        if odom is not None:
+            self.odomQueue = np.ascontiguousarray(odom, np.float64).reshape(-1, 9)
+        r = odom_deskew_info(self.odomQueue, self.timeScanCur, self.timeScanEnd, self.imuRate)
+        self.odomQueue = self.odomQueue[r.n_popped:]
+        self.odomAvailable = bool(r.odom_available)
+        if r.odom_available:
+            self.initialGuess = np.array(r.initial_guess, np.float32)
+            self.odomDeskewFlag = bool(r.odom_deskew_flag)
+        if r.odom_deskew_flag:
+            self.odomIncre = np.array(r.odom_incre, np.float32)
+        return self.odomAvailable
+
+    def motionInfo(self, positional: bool | None = None) -> MotionInfo:
+        on = self.positionalDeskew if positional is None else positional
+        return make_motion_info(bool(on and self.odomAvailable and self.odomDeskewFlag), self.timeScanEnd, self.odomIncre)
+
     def deskewInfo(self) -> DeskewInfo:
         on = self.deskewFlag == 1 and self.imuAvailable
         return make_deskew_info(self.timeScanCur, on, self.imuPointerCur if on else 0, self.imuTime, self.imuRotX, self.imuRotY,
                                 self.imuRotZ)
 
-    def projectPointCloud(self, readback: bool = True, device_ptr=None):
+    def projectPointCloud(self, readback: bool = True, device_ptr=None, positional: bool | None = None):
         """projectPointCloud() (:568-598) on the cached records (or device_ptr=(ptr, n) for records already in HBM):
-        cloud_deskewed stays on the device; with readback fullCloud is its host copy, (m, 8) float32."""
+        cloud_deskewed stays on the device; with readback fullCloud is its host copy, (m, 8) float32. positional (default: the
+        positionalDeskew member) turns findPosition()'s commented lines on (s2m_project_scan_motion) when odomDeskewInfo() found
+        odomAvailable and odomDeskewFlag."""
         lay = self.layout
         if device_ptr is not None:
             src, n, on_dev = C.c_void_p(device_ptr[0]), int(device_ptr[1]), 1
@@ -1001,8 +1101,14 @@ class ImageProjectionS2M:
         m = C.c_size_t(0)
         cap = (n + self.params.point_filter_num - 1) // max(self.params.point_filter_num, 1) if readback else 0
         out = np.zeros((max(cap, 1), 8), np.float32) if readback else None
-        self.mapper._check(self.lib.s2m_project_scan(self.mapper.h, src, n, C.byref(lay), on_dev, C.byref(self.params), C.byref(d),
-                                                     out.ctypes.data if readback else None, 32, cap, C.byref(m)), "s2m_project_scan")
+        mo = self.motionInfo(positional)
+        if mo.enabled:
+            self.mapper._check(self.lib.s2m_project_scan_motion(self.mapper.h, src, n, C.byref(lay), on_dev, C.byref(self.params), C.byref(d),
+                                                                C.byref(mo), out.ctypes.data if readback else None, 32, cap, C.byref(m)),
+                               "s2m_project_scan_motion")
+        else:
+            self.mapper._check(self.lib.s2m_project_scan(self.mapper.h, src, n, C.byref(lay), on_dev, C.byref(self.params), C.byref(d),
+                                                         out.ctypes.data if readback else None, 32, cap, C.byref(m)), "s2m_project_scan")
         self.fullCloudNum = m.value
         self.mapper.cloudDeskewedNum = m.value                 # sizes downsampleCurrentScanProjected()'s host buffer
         self.fullCloud = out[:m.value] if readback else None

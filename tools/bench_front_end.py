@@ -16,7 +16,13 @@ For Velodyne-64 x 2048 (131 072 records of 32 bytes), Ouster-128 x 1024 (131 072
   chain_old_ms      the parent route: C restatement on the host + s2m_downsample_scan of the host cloud
   kernel_us         (after --merge-kernel-stats) mean device time of k_proj_flag / k_proj_prefix / k_proj_scatter over the
                     traced calls (half from host bytes, half from device bytes: the kernels are the same), and the calls
-The two chains are run interleaved (A B A B ...), so drift of the machine hits both alike."""
+The two chains are run interleaved (A B A B ...), so drift of the machine hits both alike.
+
+With --motion every row is measured with positional deskew on (s2m_project_scan_motion, the MOTION instantiations of
+k_proj_prefix / k_proj_scatter, odometry increments of a 30 m/s vehicle) and carries "motion": true; the host figure is then
+the C restatement with findPosition()'s commented lines live (tests/ref/front_end_odom_ref.c) and the default output file is
+profiles/front_end_odom_bench_line.json. Traced runs of such rows go to <stats_dir>/<config>_pfn<k>_motion. The rows'
+`project_scan_plain_device_ms` is s2m_project_scan on the same input in the same process, interleaved with the motion call."""
 import argparse
 import csv
 import glob
@@ -32,11 +38,14 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests", "ref"))
 from liorf_amd import s2m, synth  # noqa: E402
 import project_ref as PR  # noqa: E402
+import front_end_odom_ref as FR  # noqa: E402
 
 CONFIGS = [("velodyne64x2048", "velodyne", 64, 2048), ("ouster128x1024", "ouster", 128, 1024), ("ouster128x2048", "ouster", 128, 2048)]
 SENSOR = {"velodyne": s2m.S2M_SENSOR_VELODYNE, "ouster": s2m.S2M_SENSOR_OUSTER}
 KERNELS = ("k_proj_flag", "k_proj_prefix", "k_proj_scatter")
 DEFAULT_OUT = os.path.join(ROOT, "profiles", "front_end_bench_line.json")
+DEFAULT_OUT_MOTION = os.path.join(ROOT, "profiles", "front_end_odom_bench_line.json")
+ODOM_INCRE = (2.9, -0.35, 0.06)          # a 0.1 s sweep at about 30 m/s
 
 
 def median_ms(fn, reps, warmup):
@@ -54,7 +63,7 @@ def merge_kernel_stats(stats_dir, out):
     """rocprofv3's kernel_stats.csv of every <stats_dir>/<config>_pfn<k> run into the rows of `out`."""
     rec = json.load(open(out))
     for row in rec["rows"]:
-        d = os.path.join(stats_dir, "%s_pfn%d" % (row["config"], row["point_filter_num"]))
+        d = os.path.join(stats_dir, "%s_pfn%d%s" % (row["config"], row["point_filter_num"], "_motion" if row.get("motion") else ""))
         files = glob.glob(os.path.join(d, "**", "*kernel_stats.csv"), recursive=True)
         if len(files) != 1:
             raise SystemExit("expected one kernel_stats.csv under %s, found %d" % (d, len(files)))
@@ -76,12 +85,15 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=30)
     ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--out", default=DEFAULT_OUT)
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--motion", action="store_true", help="positional deskew on: s2m_project_scan_motion and the MOTION kernels")
     ap.add_argument("--profile-run", action="store_true", help="only run the projections (under rocprofv3 --kernel-trace --stats)")
     ap.add_argument("--config", default=None, help="one of the configs (default: all)")
     ap.add_argument("--pfn", type=int, default=None, help="one point_filter_num (default: 1 and 3)")
     ap.add_argument("--merge-kernel-stats", default=None, metavar="DIR")
     args = ap.parse_args()
+    if args.out is None:
+        args.out = DEFAULT_OUT_MOTION if args.motion else DEFAULT_OUT
     if args.merge_kernel_stats:
         return merge_kernel_stats(args.merge_kernel_stats, args.out)
     import torch
@@ -104,8 +116,18 @@ def main():
             proj.imuDeskewInfo(scan["imu"])
             case = dict(raw=scan["raw"], layout=PR.LAYOUTS[sensor], params=PR.default_params(n_scan=rings, point_filter_num=pfn),
                         deskew=dict(deskew=True, time_scan_cur=scan["time_scan_cur"], imu_pointer_cur=cur, tables=[T, RX, RY, RZ]))
-            c_call, c_out = PR.c_project_prepared(case, "-O3")
-            m = c_call()
+            if args.motion:                      # what odomDeskewInfo() would have left: available, flag on, the increments
+                proj.positionalDeskew, proj.odomAvailable, proj.odomDeskewFlag = True, True, True
+                proj.odomIncre = np.array(ODOM_INCRE, np.float32)
+                case["motion"] = dict(enabled=1, time_scan_end=proj.timeScanEnd, odom_incre=ODOM_INCRE)
+                c_out = FR.c_project_motion(case, "-O3")
+                m = c_out.shape[0]
+
+                def c_call(_case=case):
+                    return FR.c_project_motion(_case, "-O3").shape[0]
+            else:
+                c_call, c_out = PR.c_project_prepared(case, "-O3")
+                m = c_call()
             got = proj.projectPointCloud()
             assert PR.same_cloud(got, c_out[:m]), "the device result is not the C restatement's"
             if args.profile_run:
@@ -114,6 +136,18 @@ def main():
                     proj.projectPointCloud(readback=False, device_ptr=(d_raw.data_ptr(), scan["n"]))
                 continue
             row = dict(config=name, records=int(scan["n"]), stride=int(scan["layout"][0]), point_filter_num=pfn, survivors=int(m))
+            if args.motion:
+                row["motion"] = True
+                dev = (d_raw.data_ptr(), scan["n"])
+                tp, tm = [], []
+                for k in range(args.warmup + args.reps):
+                    a = time.perf_counter(); proj.projectPointCloud(readback=False, device_ptr=dev, positional=False)
+                    b = time.perf_counter(); proj.projectPointCloud(readback=False, device_ptr=dev, positional=True)
+                    c = time.perf_counter()
+                    if k >= args.warmup:
+                        tp.append((b - a) * 1e3); tm.append((c - b) * 1e3)
+                row["project_scan_plain_device_ms"] = float(np.median(tp))
+                row["project_scan_motion_device_ms_interleaved"] = float(np.median(tm))
             row["project_scan_host_ms"] = median_ms(lambda: proj.projectPointCloud(readback=False), args.reps, args.warmup)
             row["project_scan_device_ms"] = median_ms(lambda: proj.projectPointCloud(readback=False, device_ptr=(d_raw.data_ptr(), scan["n"])),
                                                       args.reps, args.warmup)
@@ -138,8 +172,9 @@ def main():
             print(json.dumps(row), flush=True)
     g.close()
     if not args.profile_run:
-        rec = dict(tool="tools/bench_front_end.py", reps=args.reps, warmup=args.warmup, rows=rows,
-                   note="cpu_project_ms leaves out pcl::moveFromROSMsg and the conversion loop (it flatters the host)")
+        rec = dict(tool="tools/bench_front_end.py" + (" --motion" if args.motion else ""), reps=args.reps, warmup=args.warmup, rows=rows,
+                   note="cpu_project_ms leaves out pcl::moveFromROSMsg and the conversion loop (it flatters the host)" +
+                        ("; with --motion it includes the Python call and the output allocation of the checker" if args.motion else ""))
         os.makedirs(os.path.dirname(args.out), exist_ok=True)
         with open(args.out, "w") as f:
             json.dump(rec, f, indent=1)
