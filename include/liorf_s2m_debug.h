@@ -15,7 +15,7 @@
  *   S2M_BIG_BLOCKS=0       8-wave workgroups whatever the scan size
  *   S2M_SPLIT=0|1|2        fused kernel always / certify + search always / late split in lockstep batches (default)
  *   S2M_SPLIT_FROM=n, S2M_SEARCH_GRID=n, S2M_CLOSE_IN_SEARCH=1, S2M_LEAN=0, S2M_LOCKSTEP=0, S2M_BATCH_MINW=n, S2M_BATCH_ENTRIES=n
- *                          shape of the batch loop (liorf_amd/csrc/s2m_abi.hip, s2m_context)
+ *                          shape of the batch loop (liorf_amd/csrc/s2m_context.hpp, s2m_context::Tuning)
  *   S2M_ABLATE=bits        switch tiers / search paths off (tests): 1 no certificates, 2 no re-measuring, 16 ignore the prior in
  *                          the search, 32 ignore the plane cache, 64 no tiles (lanes served one by one), 128 tiles for any lane count
  *   S2M_TUNE=a,b,c,d       experiment thresholds (s2m_types.h, DevCtx::tune)

@@ -1,0 +1,299 @@
+// s2m_context.hpp — the handle behind the C ABI (struct s2m_context) and the host helpers that more than one stage uses.
+// Internal: included by the s2m_abi*.hip translation units only, never installed, and nothing declared here leaves the library.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <cstddef>
+#include <cstdint>
+#include <map>
+#include <string>
+#include <vector>
+
+#include "s2m_types.h"
+#include "s2m_host_math.hpp"
+#include "s2m_voxel.hpp"
+#include "s2m_icp.hpp"
+#include "s2m_project.hpp"
+
+namespace s2m {
+namespace host __attribute__((visibility("hidden"))) {
+
+// A device allocation and its one owner: declaring a DevBuf member is all a new buffer needs, the destructor frees it.
+// A DevBuf that points into memory it does not own (a slot's `state`) is made to forget() it before it goes.
+struct DevBuf {
+    void*  p = nullptr;
+    size_t cap = 0;
+    DevBuf() = default;
+    DevBuf(const DevBuf&) = delete;
+    DevBuf& operator=(const DevBuf&) = delete;
+    ~DevBuf() { (void)reset(); }
+    template <typename T> T* as() const { return reinterpret_cast<T*>(p); }
+    // frees what is held and takes q (cap bytes) instead; the old memory is dropped whatever hipFree says, never freed twice
+    hipError_t reset(void* q = nullptr, size_t bytes = 0)
+    {
+        const hipError_t e = p ? hipFree(p) : hipSuccess;
+        p = q; cap = bytes;
+        return e;
+    }
+    void forget() { p = nullptr; cap = 0; }
+};
+
+constexpr size_t kDsStride = 32;       // filtered clouds are kept as pcl::PointXYZI records
+
+}  // namespace host
+}  // namespace s2m
+
+struct __attribute__((visibility("hidden"))) s2m_context {
+    using DevBuf = s2m::host::DevBuf;
+
+    s2m_params prm{};
+    int device = 0;
+    hipStream_t stream = nullptr;
+    bool own_stream = false;
+    std::string err;
+    s2m::DevCtx hctx{};                // host copy of the DevCtx block; ctx_dirty: it has to go to the device before the next launch
+    bool ctx_dirty = true;
+
+    // registration: the map index, the ordered scan, the LM loop's state and its captured graphs
+    struct Registration {
+        // map side
+        DevBuf raw_map, map_sorted, m_counts, m_cell_start, m_cell_of, m_rank_of;
+        // scan side
+        DevBuf raw_scan, qx, qy, qz, qperm, npos, front, cert, aux, plane_cache, plane_alt, npos_alt, chunk_parts, chunk_factor, wave_table, n_waves, q_counts, q_cell_start, q_cell_of, q_rank_of, q_block_hist;
+        // shared: scan scratch, partial rows + worklist, loop state + trace, the DevCtx block, bounding box, the debug outputs
+        DevBuf block_sums, partials, state, dctx, mm, dbg_idx5, dbg_d2, dbg_flag, dbg_coeff, dbg_clk;
+        size_t n_m = 0, n_q = 0;
+        bool have_scan = false;
+
+        // pinned host staging
+        s2m::DevState* h_state = nullptr;  // [2]: [0] upload, [1] download
+        s2m_iter_trace* h_trace = nullptr; // [kMaxIter], directly behind h_state[1]: state and trace come back in one copy
+        uint32_t* h_mm = nullptr;          // [6]
+
+        // state that persists across scans in the reference node (:139-140)
+        int persist_degenerate = 0;
+        float persist_matP[36] = { 0 };
+
+        std::map<long long, hipGraphExec_t> graphs;
+        std::vector<hipEvent_t> iter_events;
+        hipEvent_t ev_a = nullptr, ev_b = nullptr, ev_c = nullptr, ev_d = nullptr, ev_up = nullptr;
+        hipEvent_t ev_a2 = nullptr, ev_b2 = nullptr;     // around the second range of launches
+        float t_optimize_ms = 0, t_set_map_ms = 0, t_set_scan_ms = 0;
+        int base_parts = 1;
+        bool seg_pending = false;          // the launch in flight was the first range only
+        bool opt_pending = false;
+        bool scan_timing_pending = false;
+        int pending_skipped = 0;
+        float pending_pose_in[6] = { 0 };
+        s2m_iter_trace last_trace[s2m::kMaxIter];
+        int last_trace_n = 0;
+    } reg;
+
+    // batch of scans against this handle's map (s2m_optimize_batch): one child context per scan slot.  A child owns its scan-side
+    // buffers and DevCtx block, borrows the parent's map index, keeps its loop state and trace in the parent's block (kid_states)
+    // and runs on the parent's stream; inside the captured batch graph the slots advance in lockstep, one grid row each, or
+    // (S2M_LOCKSTEP=0) every child's loop is a branch of its own.
+    struct Batch {
+        s2m_context* parent = nullptr;
+        std::vector<s2m_context*> kids;
+        std::vector<hipStream_t> branch_streams;
+        std::vector<hipEvent_t> branch_events;
+        std::vector<hipEvent_t> prep_events;  // a slot's scan preparation runs on the slot's branch stream, next to the other slots': done when this fires
+        std::vector<char> prep_pending;
+        hipEvent_t ev_fork = nullptr, ev_prep = nullptr;
+        // loop state + trace of every slot in one block (device) with a pinned mirror: one copy brings all of a batch's results back
+        DevBuf kid_states;
+        unsigned char* h_kid_states = nullptr;
+        bool slot_mode = false;            // (a slot running a loop of its own on its own stream: s2m_slot_optimize_*)
+        bool state_borrowed = false;       // (a slot: `reg.state` and `reg.h_state` point into the parent's blocks)
+        std::map<std::vector<int>, hipGraphExec_t> graphs;
+        std::vector<int> live;             // the slots of the batch in flight that run a loop
+        bool seg_pending = false;          // the batch in flight was issued as its first range of launches only (early exit on)
+        unsigned long long map_epoch = 0;  // bumped by every s2m_set_map: children re-adopt the index when it changed
+        unsigned long long adopted_epoch = 0;
+    } batch;
+
+    // tuning switches, read from the environment once in s2m_create
+    struct Tuning {
+        bool use_graph = true;
+        bool fuse_solve = true;            // env S2M_NO_FUSE=1 keeps one k_finalize per iteration (A/B measurements)
+        int  fuse_max_blocks = 0;          // largest grid that closes iterations inside k_register (env S2M_FUSE_MAX overrides)
+        int  seg_iters = 8;                // with early exit on, the loop is issued as launches 0..seg-1 and, only if those did not converge, the rest (env S2M_SEGMENT, 0 = one piece)
+        int  split_mode = -1;              // env S2M_SPLIT: 1 = every loop runs certify + search kernels, 0 = every loop the fused kernel, 2 (and the default)
+                                           // = a lockstep batch whose iterations are closed by k_finalize runs the fused kernel up to launch split_from
+                                           // and k_certify_lean + the search kernel from there on; everything else the fused kernel
+        bool tune_env = false;             // S2M_TUNE given (DevCtx::tune holds the caller's values)
+        bool lean_certify = true;          // env S2M_LEAN=0: the certify role by the general kernel even where the 64-register one applies
+        int  batch_entries = 1;            // env S2M_BATCH_ENTRIES: wave-table entries per wave in the scan slots of a batch (fewer, longer-running workgroups)
+        int  batch_minw = 4;               // env S2M_BATCH_MINW=4: the search / fused kernel of batch slots in the 128-register build
+        bool close_in_search = false;      // env S2M_CLOSE_IN_SEARCH=1: late split iterations without a k_finalize launch - ONE search workgroup per slot walks the
+                                           // worklist and closes the iteration (1 % faster on the benchmark batch, but a slot with several deferred workgroups then
+                                           // works them off one after the other: 70 us in a launch that had three)
+        int  search_grid = 8;              // env S2M_SEARCH_GRID: workgroups per slot of a late search launch
+        int  split_from = 8;               // env S2M_SPLIT_FROM: first launch that runs certify + search under S2M_SPLIT=2
+        bool lockstep = true;              // env S2M_LOCKSTEP=0: the scans of a batch as parallel branches of the graph instead of one grid row each (A/B measurements)
+        bool big_blocks = true;            // env S2M_BIG_BLOCKS=0: 8-wave workgroups whatever the scan size (A/B measurements)
+        int  density_raw = 320;            // box points above which a wave asks for a finer cut (env S2M_DENSITY_RAW, 0 = off)
+    } tune;
+
+    // voxel-grid stages that feed the path (section 8(f) F1/F2): staging for host clouds, the filter's output for the host,
+    // transformed key frames, and the two filtered clouds that stay resident as the registration's scan and map
+    struct Voxel {
+        DevBuf in, out, frames_xf, scan_ds, map_ds;
+        s2m::VoxWorkspace* ws = nullptr;
+        size_t scan_ds_n = 0;              // records s2m_downsample_scan left in scan_ds
+        bool have_scan_ds = false;
+    } voxel;
+
+    // ScanContext (SCManager's containers, section 8(f) F3): the polar bins and descriptor + ring key of the cloud in hand, then
+    // the store - descriptors, fp32 ring keys, sector keys, by key-frame index - and the candidate list of s2m_sc_distance
+    struct ScanContext {
+        DevBuf bins, out;
+        DevBuf store_desc, store_ring, store_sector, cand;
+        size_t n = 0, cap = 0, n_search = 0;
+        int    counter = 0;                // tree_making_period_conter (include/Scancontext.cpp:270-283)
+        double* h_stage = nullptr;         // pinned [1200 + 20]: descriptor + ring key, or the detection's result
+    } sc;
+
+    // key-frame store (cloudKeyPoses3D / cloudKeyPoses6D / surfCloudKeyFrames, :93-100): every key's 32-byte records in an arena of
+    // blocks that are never moved (the frame table holds raw pointers into them), and per key its position, KfFrame (transform,
+    // records, count) and time on the device; poses, times and frames mirrored on the host
+    struct KeyFrames {
+        DevBuf pos, frames, tdev;          // tdev: every key's time (double), read by the loop detection
+        std::vector<void*> blocks;
+        size_t block_used = 0, block_cap = 0, cap = 0;
+        std::vector<float> pose;           // 6 per key: x, y, z, roll, pitch, yaw
+        std::vector<double> time;
+        std::vector<s2m::KfFrame> frame;
+        KeyFrames() = default;
+        KeyFrames(const KeyFrames&) = delete;
+        KeyFrames& operator=(const KeyFrames&) = delete;
+        ~KeyFrames() { for (void* b : blocks) (void)hipFree(b); }
+    } kf;
+
+    // loop closure: the ICP alignment (section 8(f) F4) with its staging of host clouds, and against the store loopIndexContainer
+    // (:146), the transformed frames and the two filtered submaps
+    struct LoopClosure {
+        s2m::IcpWorkspace* icp = nullptr;
+        DevBuf icp_src, icp_tgt;
+        std::map<int32_t, int32_t> index;
+        DevBuf xf, cur, prev;
+    } loop;
+
+    // the global map and the saved map from the store: transformed frames, the filtered cloud, the chunked copy-out (frame table,
+    // two staging buffers that take turns, a copy stream and its events)
+    struct GlobalMap {
+        DevBuf xf, out, tab, stage[2];
+        hipStream_t copy_stream = nullptr;
+        hipEvent_t ev_xf[2] = { nullptr, nullptr }, ev_cp[2] = { nullptr, nullptr };
+    } gmap;
+
+    // imageProjection's filter and deskew (s2m_project_scan): staging of host records, the survivor masks, the per-workgroup
+    // counts, the IMU table, transStartInverse, and cloud_deskewed - the resident result the next stages read
+    struct Projection {
+        DevBuf in, mask, part, table, start, cloud_deskewed;
+        size_t deskewed_n = 0;
+        bool have_deskewed = false;
+        s2m::ProjCount* h_count = nullptr; // pinned: the count, written by the device
+    } proj;
+};
+
+namespace s2m {
+namespace host __attribute__((visibility("hidden"))) {
+
+inline int fail(s2m_context* h, int code, const char* what, hipError_t e = hipSuccess)
+{
+    if (h) {
+        h->err = what;
+        if (e != hipSuccess) { h->err += ": "; h->err += hipGetErrorString(e); }
+    }
+    return code;
+}
+
+#define S2M_HIP(h, call)                                                     \
+    do {                                                                     \
+        hipError_t e__ = (call);                                             \
+        if (e__ != hipSuccess) return fail((h), S2M_ERR_HIP, #call, e__);   \
+    } while (0)
+
+inline int ensure(s2m_context* h, DevBuf& b, size_t bytes)
+{
+    if (bytes <= b.cap) return S2M_OK;
+    size_t want = bytes + bytes / 4 + 256;          // grow-only with slack
+    S2M_HIP(h, b.reset());
+    S2M_HIP(h, hipMalloc(&b.p, want));
+    b.cap = want;
+    h->ctx_dirty = true;
+    return S2M_OK;
+}
+
+// host records -> `buf` (grown to hold them), on the handle's stream
+inline int stage_host_records(s2m_context* h, DevBuf& buf, const void* pts, size_t bytes)
+{
+    int rc = ensure(h, buf, bytes);
+    if (rc) return rc;
+    S2M_HIP(h, hipMemcpyAsync(buf.p, pts, bytes, hipMemcpyHostToDevice, h->stream));
+    return S2M_OK;
+}
+
+inline int check_records(s2m_context* h, const void* pts, size_t n, size_t stride)
+{
+    if (!h) return S2M_ERR_INVALID_ARG;
+    if (n > 0 && !pts) return fail(h, S2M_ERR_INVALID_ARG, "null point buffer");
+    if (stride < 12 || (stride & 3)) return fail(h, S2M_ERR_INVALID_ARG, "stride_bytes must be >= 12 and a multiple of 4");
+    if ((reinterpret_cast<uintptr_t>(pts) & 3) != 0) return fail(h, S2M_ERR_INVALID_ARG, "point buffer must be 4-byte aligned");
+    if (n > (size_t)0x3fffffff) return fail(h, S2M_ERR_CAPACITY, "too many points");
+    return S2M_OK;
+}
+
+inline int check_leaf(s2m_context* h, float leaf)
+{
+    if (!(leaf > 0.0f) || !std::isfinite(leaf)) return fail(h, S2M_ERR_INVALID_ARG, "leaf size must be positive and finite");
+    return S2M_OK;
+}
+
+// an output buffer that is asked for (cap > 0) and cannot take records
+inline bool bad_out(const void* out, size_t out_stride, size_t cap) { return cap > 0 && (!out || out_stride < 12 || (out_stride & 3)); }
+
+// transCur = pcl::getTransformation(x, y, z, roll, pitch, yaw) of a key pose (:317) as a row-major 3x4
+inline void xyzrpy_to_transform(const float p[6], float T[12])
+{
+    const float rpyxyz[6] = { p[3], p[4], p[5], p[0], p[1], p[2] };
+    host_pose_to_transform(rpyxyz, T, nullptr);
+}
+
+// ---- s2m_abi.hip (they launch kernels of s2m_kernels.hpp) ----
+int set_map_impl(s2m_context* h, const void* pts, size_t n, size_t stride, bool on_device);
+int set_scan_impl(s2m_context* h, const void* pts, size_t n, size_t stride, bool on_device);
+// SCManager::makeScancontext + ring key of a cloud into h->sc.out (device); then: append them as key frame sc.n
+int sc_build_descriptor(s2m_context* h, const void* pts, size_t n, size_t stride_bytes, bool on_device = false);
+int sc_append_from_out(s2m_context* h);
+
+// ---- s2m_abi_voxel.hip ----
+// VoxelGrid of a device cloud into `dst` (grown to hold one record per input point, the worst case).
+int voxel_into(s2m_context* h, const unsigned char* d_in, size_t n, size_t stride, float leaf, DevBuf& dst, VoxResult* res);
+// strided device records -> caller's host buffer (min(n, cap) records)
+int download_records(s2m_context* h, const DevBuf& src, size_t n, void* out, size_t out_stride, size_t cap);
+// the end of a stage that left res.n_out records in `src`: the host copy if one is asked for (cap > 0), the capacity error with
+// the stage's message, the leaf warning
+int finish_cloud(s2m_context* h, const DevBuf& src, const VoxResult& res, void* out, size_t out_stride, size_t cap, const char* too_small);
+
+// the host side of a frame table: clouds on the device, each with its 3x4 transform, to be written back to back
+struct FrameTable {
+    std::vector<const unsigned char*> src;
+    std::vector<int32_t> offsets{ 0 };
+    std::vector<float> T;
+    size_t total = 0;
+    void push(const unsigned char* d_src, size_t n, const float t[12])
+    {
+        total += n;
+        src.push_back(d_src);
+        offsets.push_back((int32_t)total);
+        T.insert(T.end(), t, t + 12);
+    }
+    // transformPointCloud (:310-329) of every frame (records of `stride` bytes) into `dst`; `what` names the step in an error
+    int transform_into(s2m_context* h, DevBuf& dst, size_t stride, const char* what) const;
+};
+
+}  // namespace host
+}  // namespace s2m
