@@ -667,6 +667,90 @@ int  s2m_loop_align(s2m_handle h, int32_t key_cur, int32_t key_pre, int32_t base
  * timeLaserInfoCur = time_cur, then s2m_loop_align(N-1, key_pre, -1, p). */
 int  s2m_loop_closure_rs(s2m_handle h, double time_cur, const s2m_loop_params* p /* NULL = defaults */, s2m_loop_result* out);
 
+/* ---- Pose graph: factors, optimise, correct the key-frame store --------------------------------------------------
+ * saveKeyFramesAndFactor() with addOdomFactor / addGPSFactor / addLoopFactor (reference src/mapOptmization.cpp:1386-1534)
+ * and correctPoses() (:1611-1642) as a batch solve on the device. The graph lives in the handle beside the key-frame
+ * store; variable i of the graph is key i of the store. Variables are dense: with N variables a call may name keys
+ * 0..N, and key N creates variable N. Every variable needs an initial value before s2m_pg_optimize.
+ *   State: (R_i, t_i) in fp64 on the device. Pose vectors {x, y, z, roll, pitch, yaw} convert as
+ *       Rot3::RzRyRx(roll, pitch, yaw); read-out is roll = atan2(R21, R22), pitch = asin(-R20), yaw = atan2(R10, R00) in
+ *       fp64, then rounded to float.
+ *   Tangent and retraction: d = [w, v], rotation first (GTSAM's Pose3 order); R <- R Exp(w), t <- t + R v.
+ *   Residuals [ext]: between, with E = Z^-1 X_i^-1 X_j: r = [Log_SO3(R_E), t_E]; prior, the same with E = P^-1 X;
+ *       GPS: t_i - z. This is the first-order chart of a default GTSAM 4.0 build; a GTSAM built with POSE3_EXPMAP uses
+ *       the full SE(3) logarithm and differs at second order in the residual.
+ *   Weights: rows are whitened by 1 / sqrt(var) (var in tangent order: three rotation, three translation variances).
+ *       robust_k > 0 makes the factor Cauchy: w = k^2 / (k^2 + |whitened r|^2), recomputed at every linearisation
+ *       [ext]; its error term is k^2 / 2 log(1 + |whitened r|^2 / k^2), a plain factor's |whitened r|^2 / 2.
+ *   Iteration: Gauss-Newton; a step is kept only if it lowers the error. The loop ends after max_iterations steps, at
+ *       a step that does not lower the error (converged), or when a kept step lowered it by less than
+ *       absolute_error_tol or by less than relative_error_tol times the error (converged).
+ *   Linear solve: the chain prior(0), between(0,1), between(1,2), ... - the first prior on key 0 and, per i, the first
+ *       between factor i -> i+1 with robust_k == 0 - is solved exactly in square-root form (its whitened Jacobian is
+ *       never squared), every other factor enters through conjugate gradients preconditioned by that chain, with a
+ *       device-side stop flag. A graph without such a chain over all its variables is S2M_ERR_INVALID_ARG from
+ *       s2m_pg_optimize / s2m_pg_marginal (a disconnected variable, a missing prior on key 0), as is a variable
+ *       without an initial value; the graph stays as it was.
+ *   An empty graph optimises to S2M_OK with zero counts. A failed add leaves the graph as it was. Results are
+ *   reproducible run to run: every sum is taken in a fixed order. Calls on a handle are not concurrent. */
+typedef struct s2m_pg_params {
+    double  prior_var[6];          /* {1e-2, 1e-2, pi*pi, 1e8, 1e8, 1e8}  :1390 (rad^2 x3, m^2 x3) */
+    double  odom_var[6];           /* {1e-6 x3, 1e-4 x3}                  :1394 */
+    double  sc_loop_var[6];        /* 0.5 x6                              :712-713 */
+    double  sc_loop_robust_k;      /* Cauchy k = 1                        :716-719 */
+    double  relative_error_tol;    /* 1e-5 */
+    double  absolute_error_tol;    /* 1e-5 */
+    double  cg_rel_tol;            /* 1e-13: the inner solve ends at |residual| <= cg_rel_tol |right-hand side| */
+    int32_t max_iterations;        /* 100 */
+    int32_t cg_max_iterations;     /* 0: six per factor off the chain, plus 20 */
+} s2m_pg_params;
+typedef struct s2m_pg_result {
+    int32_t iterations;            /* Gauss-Newton steps kept */
+    int32_t inner_iterations;      /* CG iterations over all steps */
+    int32_t converged;
+    int32_t n_variables, n_factors;
+    int32_t reserved;
+    double  error_before, error_after;
+    double  robust_weight_min;     /* smallest Cauchy weight at the final estimate (1 without robust factors) */
+} s2m_pg_result;
+#define S2M_PG_PRIOR    0
+#define S2M_PG_BETWEEN  1
+#define S2M_PG_GPS      2
+#define S2M_PG_INITIAL  3
+int  s2m_pg_default_params(s2m_pg_params* p);
+/* The argument checks of the add calls on their own (host code, no handle, no GPU): S2M_OK or S2M_ERR_INVALID_ARG.
+ * kind is S2M_PG_*; n_variables the graph's current variable count; key_b is read for S2M_PG_BETWEEN only; values are
+ * 6 floats (3 for S2M_PG_GPS), var 6 doubles (3 for S2M_PG_GPS, not read for S2M_PG_INITIAL). Rejected: null pointers,
+ * non-finite values, variances that are not positive and finite, a negative or non-finite robust_k, negative keys, a
+ * key above n_variables or two new keys at once (a gap), key_a == key_b (a self loop). */
+int  s2m_pg_check_args(int32_t kind, int32_t n_variables, int32_t key_a, int32_t key_b, const float* values, const double* var,
+                       double robust_k);
+int  s2m_pg_reset(s2m_handle h);
+int  s2m_pg_size(s2m_handle h, int32_t* n_variables, int32_t* n_factors);
+int  s2m_pg_add_prior(s2m_handle h, int32_t key, const float pose_xyzrpy[6], const double var[6]);
+int  s2m_pg_add_between(s2m_handle h, int32_t key_from, int32_t key_to, const float rel_xyzrpy[6], const double var[6], double robust_k);
+int  s2m_pg_add_gps(s2m_handle h, int32_t key, const float xyz[3], const double var[3]);
+int  s2m_pg_set_initial(s2m_handle h, int32_t key, const float pose_xyzrpy[6]);
+/* addOdomFactor() (:1386-1400): on an empty graph the prior (prior_var) and initial value of key 0; otherwise the
+ * between factor (odom_var) from the last variable's current estimate, in fp64, to `pose`, and the new variable's
+ * initial value. The variances are those of s2m_pg_default_params. */
+int  s2m_pg_add_odometry(s2m_handle h, const float pose_xyzrpy[6]);
+int  s2m_pg_optimize(s2m_handle h, const s2m_pg_params* p /* NULL = defaults */, s2m_pg_result* out /* may be NULL */);
+/* The current estimates of variables first .. first+count-1 as floats; S2M_ERR_INVALID_ARG outside the graph or for a
+ * variable of that range without a value. */
+int  s2m_pg_get_poses(s2m_handle h, int32_t first, int32_t count, float* xyzrpy);
+/* poseCovariance (:1565): the marginal covariance of `key` at the current estimates, row-major 6x6 in the tangent
+ * order of rotation then translation, with the robust weights of those estimates. */
+int  s2m_pg_marginal(s2m_handle h, int32_t key, double cov[36]);
+/* correctPoses() (:1611-1642): the estimates of variables first .. first+count-1 become the poses of the same keys of
+ * the key-frame store, computed and written on the device: the float pose vector of s2m_pg_get_poses, the position, and
+ * each key's cached transform with the host libm's sinf / cosf restated on the device, so that the store ends up bit for
+ * bit what s2m_kf_set_poses makes of s2m_pg_get_poses' floats. One copy brings the new poses and transforms back to the
+ * library's host mirror of the store; nothing is uploaded. The range must lie inside both the graph and the store and
+ * every variable in it needs a value (S2M_ERR_INVALID_ARG); an estimate that is not finite is S2M_ERR_INVALID_ARG and
+ * leaves the store as it was. */
+int  s2m_pg_apply_to_store(s2m_handle h, int32_t first, int32_t count);
+
 #ifdef __cplusplus
 }
 #endif

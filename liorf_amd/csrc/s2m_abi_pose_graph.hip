@@ -1,0 +1,472 @@
+// s2m_abi_pose_graph.hip — C ABI of the pose graph: the factor list and the estimates' mirror on the host, the device tables,
+// the Gauss-Newton loop around s2m_pose_graph.hip's kernels, the marginal, and correctPoses() into the key-frame store.
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+
+#include "s2m_context.hpp"
+
+using namespace s2m;
+using namespace s2m::host;
+
+int s2m_pg_default_params(s2m_pg_params* p)
+{
+    if (!p) return S2M_ERR_INVALID_ARG;
+    const double prior[6] = { 1e-2, 1e-2, M_PI * M_PI, 1e8, 1e8, 1e8 };     // :1390
+    const double odom[6] = { 1e-6, 1e-6, 1e-6, 1e-4, 1e-4, 1e-4 };           // :1394
+    for (int k = 0; k < 6; k++) { p->prior_var[k] = prior[k]; p->odom_var[k] = odom[k]; p->sc_loop_var[k] = 0.5; }   // :712-713
+    p->sc_loop_robust_k = 1.0;                                               // :716-719
+    p->relative_error_tol = 1e-5;
+    p->absolute_error_tol = 1e-5;
+    p->cg_rel_tol = 1e-13;
+    p->max_iterations = 100;
+    p->cg_max_iterations = 0;
+    return S2M_OK;
+}
+
+int s2m_pg_check_args(int32_t kind, int32_t n_variables, int32_t key_a, int32_t key_b, const float* values, const double* var, double robust_k)
+{
+    if (kind < S2M_PG_PRIOR || kind > S2M_PG_INITIAL || n_variables < 0 || !values) return S2M_ERR_INVALID_ARG;
+    const int nv = kind == S2M_PG_GPS ? 3 : 6;
+    for (int k = 0; k < nv; k++) if (!std::isfinite(values[k])) return S2M_ERR_INVALID_ARG;
+    if (kind != S2M_PG_INITIAL) {
+        if (!var) return S2M_ERR_INVALID_ARG;
+        for (int k = 0; k < nv; k++) if (!(var[k] > 0.0) || !std::isfinite(var[k])) return S2M_ERR_INVALID_ARG;
+    }
+    if (!(robust_k >= 0.0) || !std::isfinite(robust_k)) return S2M_ERR_INVALID_ARG;
+    if (key_a < 0 || key_a > n_variables) return S2M_ERR_INVALID_ARG;
+    if (kind == S2M_PG_BETWEEN) {
+        if (key_b < 0 || key_b > n_variables || key_a == key_b) return S2M_ERR_INVALID_ARG;
+    }
+    return S2M_OK;                  // (key_a != key_b and both <= n_variables: at most one of them is new)
+}
+
+namespace {
+
+constexpr size_t kPgMaxVars = (size_t)1 << 24;          // as the key-frame store
+
+void pose_to_state(const float p[6], double X[12])     // Rot3::RzRyRx(roll, pitch, yaw), fp64
+{
+    const double cr = std::cos((double)p[3]), sr = std::sin((double)p[3]), cp = std::cos((double)p[4]), sp = std::sin((double)p[4]);
+    const double cy = std::cos((double)p[5]), sy = std::sin((double)p[5]);
+    X[0] = cy * cp; X[1] = cy * sp * sr - sy * cr; X[2] = sy * sr + cy * sp * cr;
+    X[3] = sy * cp; X[4] = cy * cr + sy * sp * sr; X[5] = sy * sp * cr - cy * sr;
+    X[6] = -sp;     X[7] = cp * sr;                X[8] = cp * cr;
+    X[9] = p[0]; X[10] = p[1]; X[11] = p[2];
+}
+
+size_t pg_n(const s2m_context* h) { return h->pg.has_init.size(); }
+
+void touch(s2m_context* h, int32_t key)
+{
+    if ((size_t)key == pg_n(h)) {
+        h->pg.has_init.push_back(0);
+        h->pg.dirty.push_back(0);
+        h->pg.X.resize(h->pg.X.size() + 12, 0.0);
+        h->pg.topo_dirty = true;
+    }
+}
+
+// the host mirror holds the newest estimates (the device's, except where set_initial wrote since)
+int host_current(s2m_context* h)
+{
+    auto& g = h->pg;
+    if (!g.dev_newer) return S2M_OK;
+    std::vector<double> tmp(12 * g.n_dev);
+    S2M_HIP(h, hipSetDevice(h->device));
+    S2M_HIP(h, hipMemcpyAsync(tmp.data(), g.est.p, sizeof(double) * tmp.size(), hipMemcpyDeviceToHost, h->stream));
+    S2M_HIP(h, hipStreamSynchronize(h->stream));
+    for (size_t k = 0; k < g.n_dev; k++)
+        if (!g.dirty[k]) std::copy(tmp.begin() + 12 * k, tmp.begin() + 12 * (k + 1), g.X.begin() + 12 * k);
+    g.dev_newer = false;
+    return S2M_OK;
+}
+
+// the device holds every variable's newest estimate; variables first .. first+count-1 must have one
+int upload_state(s2m_context* h, size_t first, size_t count)
+{
+    auto& g = h->pg;
+    const size_t n = pg_n(h);
+    for (size_t k = first; k < first + count; k++)
+        if (!g.has_init[k]) return fail(h, S2M_ERR_INVALID_ARG, "a pose-graph variable has no initial value");
+    if (n == 0) return S2M_OK;
+    S2M_HIP(h, hipSetDevice(h->device));
+    int rc;
+    const size_t bytes = sizeof(double) * 12 * n;
+    if (bytes > g.est.cap || bytes > g.trial.cap) {        // the arrays move: everything goes up again
+        if ((rc = host_current(h))) return rc;
+        std::fill(g.dirty.begin(), g.dirty.end(), 1);
+        if ((rc = ensure(h, g.est, 2 * bytes)) || (rc = ensure(h, g.trial, 2 * bytes))) return rc;
+        g.n_dev = 0;
+    }
+    for (size_t k = g.n_dev; k < n; k++) g.dirty[k] = 1;
+    for (size_t k = 0; k < n;) {
+        if (!g.dirty[k]) { k++; continue; }
+        size_t e = k;
+        while (e < n && g.dirty[e]) e++;
+        S2M_HIP(h, hipMemcpyAsync(g.est.as<double>() + 12 * k, g.X.data() + 12 * k, sizeof(double) * 12 * (e - k), hipMemcpyHostToDevice, h->stream));
+        k = e;
+    }
+    S2M_HIP(h, hipStreamSynchronize(h->stream));
+    std::fill(g.dirty.begin(), g.dirty.end(), 0);
+    g.n_dev = n;
+    return S2M_OK;
+}
+
+template <typename T>
+int upload_vec(s2m_context* h, DevBuf& b, const std::vector<T>& v)
+{
+    int rc = ensure(h, b, sizeof(T) * std::max<size_t>(v.size(), 1));
+    if (rc) return rc;
+    if (!v.empty()) S2M_HIP(h, hipMemcpyAsync(b.p, v.data(), sizeof(T) * v.size(), hipMemcpyHostToDevice, h->stream));
+    return S2M_OK;
+}
+
+int setup_scan(s2m_context* h, int which, int n, PgScan& sc)
+{
+    auto& g = h->pg;
+    sc.rev = which;
+    sc.levels = 0;
+    size_t total = 0;
+    for (int m = n;; m = (m + kPgGroup - 1) / kPgGroup) {
+        if (sc.levels >= kPgMaxLevels) return fail(h, S2M_ERR_CAPACITY, "pose graph too large");
+        sc.n[sc.levels++] = m;
+        total += (size_t)m;
+        if (m <= kPgGroup) break;
+    }
+    int rc;
+    if ((rc = ensure(h, g.scan_M[which], sizeof(double) * 36 * total)) || (rc = ensure(h, g.scan_Pre[which], sizeof(double) * 36 * total)) ||
+        (rc = ensure(h, g.scan_loc[which], sizeof(double) * 6 * total)) || (rc = ensure(h, g.scan_C0[which], sizeof(double) * 36 * (size_t)n))) return rc;
+    size_t at = 0;
+    for (int l = 0; l < sc.levels; l++) {
+        sc.M[l] = g.scan_M[which].as<double>() + 36 * at;
+        sc.Pre[l] = g.scan_Pre[which].as<double>() + 36 * at;
+        sc.loc[l] = g.scan_loc[which].as<double>() + 6 * at;
+        at += (size_t)sc.n[l];
+    }
+    sc.C0 = g.scan_C0[which].as<double>();
+    return S2M_OK;
+}
+
+// estimates, factor tables and work arrays on the device, h->pg.dev filled in
+int prepare(s2m_context* h)
+{
+    auto& g = h->pg;
+    const size_t n = pg_n(h);
+    int rc;
+    // the chain: the first prior on key 0 and, per i, the first plain between factor i -> i+1
+    std::vector<int> chain_of(n, -1);
+    for (size_t f = 0; f < g.factors.size(); f++) {
+        const PgFactor& fa = g.factors[f];
+        if (fa.type == kPgPrior && fa.i == 0 && chain_of[0] < 0) chain_of[0] = (int)f;
+        if (fa.type == kPgBetween && fa.j == fa.i + 1 && fa.k == 0.0 && chain_of[(size_t)fa.j] < 0) chain_of[(size_t)fa.j] = (int)f;
+    }
+    if (chain_of[0] < 0) return fail(h, S2M_ERR_INVALID_ARG, "pose graph: key 0 has no prior");
+    for (size_t k = 1; k < n; k++)
+        if (chain_of[k] < 0) return fail(h, S2M_ERR_INVALID_ARG, "pose graph: a variable is not on the odometry chain from key 0");
+    if ((rc = upload_state(h, 0, n))) return rc;
+    if (!g.h_sc) S2M_HIP(h, hipHostMalloc((void**)&g.h_sc, sizeof(PgScalars)));
+    if (g.topo_dirty) {
+        std::vector<char> on_chain(g.factors.size(), 0);
+        std::vector<PgFactor> chain(n), extra;
+        for (size_t k = 0; k < n; k++) { chain[k] = g.factors[(size_t)chain_of[k]]; on_chain[(size_t)chain_of[k]] = 1; }
+        for (size_t f = 0; f < g.factors.size(); f++) if (!on_chain[f]) extra.push_back(g.factors[f]);
+        std::vector<int32_t> start(n + 1, 0);
+        for (const PgFactor& fa : extra) { start[(size_t)fa.i + 1]++; if (fa.type == kPgBetween) start[(size_t)fa.j + 1]++; }
+        for (size_t k = 0; k < n; k++) start[k + 1] += start[k];
+        std::vector<PgIncidence> inc((size_t)start[n]);
+        std::vector<int32_t> fill(start.begin(), start.end() - 1);
+        for (size_t x = 0; x < extra.size(); x++) {          // in factor order: each key's sum has a fixed order
+            inc[(size_t)fill[(size_t)extra[x].i]++] = PgIncidence{ (int32_t)x, 0 };
+            if (extra[x].type == kPgBetween) inc[(size_t)fill[(size_t)extra[x].j]++] = PgIncidence{ (int32_t)x, 1 };
+        }
+        if ((rc = upload_vec(h, g.chain, chain)) || (rc = upload_vec(h, g.extra, extra)) || (rc = upload_vec(h, g.inc_start, start)) ||
+            (rc = upload_vec(h, g.inc, inc))) return rc;
+        S2M_HIP(h, hipStreamSynchronize(h->stream));       // (the host vectors above are read by the copies until here)
+        const size_t m = std::max<size_t>(extra.size(), 1);
+        if ((rc = ensure(h, g.Binv, sizeof(double) * 36 * n)) || (rc = ensure(h, g.Aof, sizeof(double) * 36 * n)) ||
+            (rc = ensure(h, g.rc, sizeof(double) * 6 * n)) || (rc = ensure(h, g.Ji, sizeof(double) * 36 * m)) ||
+            (rc = ensure(h, g.Jj, sizeof(double) * 36 * m)) || (rc = ensure(h, g.rx, sizeof(double) * 6 * m)) ||
+            (rc = ensure(h, g.ferr, sizeof(double) * (n + m))) || (rc = ensure(h, g.fw, sizeof(double) * (n + m))) ||
+            (rc = ensure(h, g.vecs, sizeof(double) * 6 * (9 * n + m))) || (rc = ensure(h, g.partial, sizeof(double) * kPgDotBlocks)) ||
+            (rc = ensure(h, g.sc, sizeof(PgScalars)))) return rc;
+        PgDev& d = g.dev;
+        d.n = (int32_t)n; d.n_extra = (int32_t)extra.size();
+        if ((rc = setup_scan(h, 0, d.n, d.fwd)) || (rc = setup_scan(h, 1, d.n, d.bwd))) return rc;
+        d.chain = g.chain.as<PgFactor>(); d.extra = g.extra.as<PgFactor>();
+        d.inc_start = g.inc_start.as<int32_t>(); d.inc = g.inc.as<PgIncidence>();
+        d.Binv = g.Binv.as<double>(); d.Aof = g.Aof.as<double>(); d.rc = g.rc.as<double>();
+        d.Ji = g.Ji.as<double>(); d.Jj = g.Jj.as<double>(); d.rx = g.rx.as<double>();
+        d.ferr = g.ferr.as<double>(); d.fw = g.fw.as<double>();
+        double* v = g.vecs.as<double>();
+        double** slots[9] = { &d.b, &d.y, &d.r, &d.p, &d.q, &d.t1, &d.t2, &d.g, &d.delta };
+        for (int k = 0; k < 9; k++) *slots[k] = v + 6 * n * (size_t)k;
+        d.u = v + 6 * n * 9;
+        d.partial = g.partial.as<double>();
+        d.sc = g.sc.as<PgScalars>();
+        g.topo_dirty = false;
+    }
+    g.dev.X = g.est.as<double>();
+    g.dev.Xtrial = g.trial.as<double>();
+    return S2M_OK;
+}
+
+int read_scalars(s2m_context* h)
+{
+    S2M_HIP(h, hipMemcpyAsync(h->pg.h_sc, h->pg.dev.sc, sizeof(PgScalars), hipMemcpyDeviceToHost, h->stream));
+    S2M_HIP(h, hipStreamSynchronize(h->stream));
+    return S2M_OK;
+}
+
+// CG on (I + K^T K) y = b with the b in place; the stop flag is read once per chunk of iterations
+int run_cg(s2m_context* h, const s2m_pg_params& prm, int* iters)
+{
+    const PgDev& d = h->pg.dev;
+    int max_cg = prm.cg_max_iterations > 0 ? prm.cg_max_iterations : 6 * d.n_extra + 20;
+    if (d.n_extra == 0) max_cg = 1;                        // K = 0: the first step is exact
+    S2M_HIP(h, pg_cg_begin(h->stream, d, prm.cg_rel_tol, max_cg));
+    constexpr int kChunk = 24;
+    for (int done = 0; done < max_cg;) {
+        const int c = std::min(kChunk, max_cg - done);
+        S2M_HIP(h, pg_cg_iterations(h->stream, d, c));
+        int rc = read_scalars(h);
+        if (rc) return rc;
+        done += c;
+        if (h->pg.h_sc->stop) break;
+    }
+    *iters = h->pg.h_sc->iters;
+    return S2M_OK;
+}
+
+bool params_ok(const s2m_pg_params& p)
+{
+    return p.max_iterations >= 0 && p.cg_max_iterations >= 0 && p.relative_error_tol >= 0.0 && std::isfinite(p.relative_error_tol) &&
+           p.absolute_error_tol >= 0.0 && std::isfinite(p.absolute_error_tol) && p.cg_rel_tol >= 0.0 && std::isfinite(p.cg_rel_tol);
+}
+
+int add_factor(s2m_context* h, const PgFactor& f)
+{
+    if (pg_n(h) + 1 >= kPgMaxVars) return fail(h, S2M_ERR_CAPACITY, "pose graph full (2^24 variables)");
+    touch(h, std::min(f.i, f.type == kPgBetween ? f.j : f.i));
+    touch(h, std::max(f.i, f.type == kPgBetween ? f.j : f.i));
+    h->pg.factors.push_back(f);
+    h->pg.topo_dirty = true;
+    return S2M_OK;
+}
+
+PgFactor make_factor(int type, int32_t i, int32_t j, const double X[12], const double* var, int rows, double k)
+{
+    PgFactor f{};
+    f.type = type; f.i = i; f.j = j; f.rows = rows; f.k = k;
+    for (int a = 0; a < 9; a++) f.R[a] = X[a];
+    for (int a = 0; a < 3; a++) f.t[a] = X[9 + a];
+    for (int a = 0; a < 6; a++) f.sw[a] = a < rows ? 1.0 / std::sqrt(var[a]) : 0.0;
+    return f;
+}
+
+}  // namespace
+
+int s2m_pg_reset(s2m_handle h)
+{
+    if (!h) return S2M_ERR_INVALID_ARG;
+    auto& g = h->pg;
+    g.factors.clear(); g.X.clear(); g.has_init.clear(); g.dirty.clear();
+    g.dev_newer = false; g.topo_dirty = true; g.n_dev = 0;
+    return S2M_OK;
+}
+
+int s2m_pg_size(s2m_handle h, int32_t* n_variables, int32_t* n_factors)
+{
+    if (!h) return S2M_ERR_INVALID_ARG;
+    if (n_variables) *n_variables = (int32_t)pg_n(h);
+    if (n_factors) *n_factors = (int32_t)h->pg.factors.size();
+    return S2M_OK;
+}
+
+int s2m_pg_add_prior(s2m_handle h, int32_t key, const float pose_xyzrpy[6], const double var[6])
+{
+    if (!h) return S2M_ERR_INVALID_ARG;
+    if (s2m_pg_check_args(S2M_PG_PRIOR, (int32_t)pg_n(h), key, 0, pose_xyzrpy, var, 0.0))
+        return fail(h, S2M_ERR_INVALID_ARG, "prior: finite pose, positive finite variances, key in 0..N");
+    double X[12];
+    pose_to_state(pose_xyzrpy, X);
+    return add_factor(h, make_factor(kPgPrior, key, -1, X, var, 6, 0.0));
+}
+
+int s2m_pg_add_between(s2m_handle h, int32_t key_from, int32_t key_to, const float rel_xyzrpy[6], const double var[6], double robust_k)
+{
+    if (!h) return S2M_ERR_INVALID_ARG;
+    if (s2m_pg_check_args(S2M_PG_BETWEEN, (int32_t)pg_n(h), key_from, key_to, rel_xyzrpy, var, robust_k))
+        return fail(h, S2M_ERR_INVALID_ARG, "between: finite pose, positive finite variances, robust_k >= 0, two different keys in 0..N");
+    double X[12];
+    pose_to_state(rel_xyzrpy, X);
+    return add_factor(h, make_factor(kPgBetween, key_from, key_to, X, var, 6, robust_k));
+}
+
+int s2m_pg_add_gps(s2m_handle h, int32_t key, const float xyz[3], const double var[3])
+{
+    if (!h) return S2M_ERR_INVALID_ARG;
+    if (s2m_pg_check_args(S2M_PG_GPS, (int32_t)pg_n(h), key, 0, xyz, var, 0.0))
+        return fail(h, S2M_ERR_INVALID_ARG, "gps: finite position, positive finite variances, key in 0..N");
+    double X[12] = { 1, 0, 0, 0, 1, 0, 0, 0, 1, xyz[0], xyz[1], xyz[2] };
+    return add_factor(h, make_factor(kPgGps, key, -1, X, var, 3, 0.0));
+}
+
+int s2m_pg_set_initial(s2m_handle h, int32_t key, const float pose_xyzrpy[6])
+{
+    if (!h) return S2M_ERR_INVALID_ARG;
+    if (s2m_pg_check_args(S2M_PG_INITIAL, (int32_t)pg_n(h), key, 0, pose_xyzrpy, nullptr, 0.0))
+        return fail(h, S2M_ERR_INVALID_ARG, "initial value: finite pose, key in 0..N");
+    if (pg_n(h) + 1 >= kPgMaxVars) return fail(h, S2M_ERR_CAPACITY, "pose graph full (2^24 variables)");
+    touch(h, key);
+    pose_to_state(pose_xyzrpy, h->pg.X.data() + 12 * (size_t)key);
+    h->pg.has_init[(size_t)key] = 1;
+    h->pg.dirty[(size_t)key] = 1;
+    return S2M_OK;
+}
+
+int s2m_pg_add_odometry(s2m_handle h, const float pose_xyzrpy[6])
+{
+    if (!h) return S2M_ERR_INVALID_ARG;
+    const int32_t n = (int32_t)pg_n(h);
+    if (s2m_pg_check_args(S2M_PG_INITIAL, n, n, 0, pose_xyzrpy, nullptr, 0.0)) return fail(h, S2M_ERR_INVALID_ARG, "odometry: the pose must be finite");
+    s2m_pg_params prm;
+    s2m_pg_default_params(&prm);
+    int rc;
+    if (n == 0) {
+        if ((rc = s2m_pg_add_prior(h, 0, pose_xyzrpy, prm.prior_var))) return rc;
+        return s2m_pg_set_initial(h, 0, pose_xyzrpy);
+    }
+    if (!h->pg.has_init[(size_t)n - 1]) return fail(h, S2M_ERR_INVALID_ARG, "odometry: the last variable has no value");
+    if ((rc = host_current(h))) return rc;
+    const double* L = h->pg.X.data() + 12 * (size_t)(n - 1);
+    double Xn[12], Z[12];
+    pose_to_state(pose_xyzrpy, Xn);
+    for (int a = 0; a < 3; a++) {                           // poseFrom.between(poseTo) = L^-1 Xn
+        for (int b = 0; b < 3; b++) Z[a * 3 + b] = L[a] * Xn[b] + L[3 + a] * Xn[3 + b] + L[6 + a] * Xn[6 + b];
+        Z[9 + a] = L[a] * (Xn[9] - L[9]) + L[3 + a] * (Xn[10] - L[10]) + L[6 + a] * (Xn[11] - L[11]);
+    }
+    if ((rc = add_factor(h, make_factor(kPgBetween, n - 1, n, Z, prm.odom_var, 6, 0.0)))) return rc;
+    std::copy(Xn, Xn + 12, h->pg.X.begin() + 12 * (size_t)n);
+    h->pg.has_init[(size_t)n] = 1;
+    h->pg.dirty[(size_t)n] = 1;
+    return S2M_OK;
+}
+
+int s2m_pg_optimize(s2m_handle h, const s2m_pg_params* p, s2m_pg_result* out)
+{
+    if (!h) return S2M_ERR_INVALID_ARG;
+    s2m_pg_params prm;
+    if (p) prm = *p; else s2m_pg_default_params(&prm);
+    if (!params_ok(prm)) return fail(h, S2M_ERR_INVALID_ARG, "pose-graph params: iteration counts and tolerances must be >= 0 and finite");
+    s2m_pg_result res{};
+    res.robust_weight_min = 1.0;
+    res.n_variables = (int32_t)pg_n(h);
+    res.n_factors = (int32_t)h->pg.factors.size();
+    if (out) *out = res;
+    if (pg_n(h) == 0) return S2M_OK;
+    int rc = prepare(h);
+    if (rc) return rc;
+    auto& g = h->pg;
+    PgDev& d = g.dev;
+    S2M_HIP(h, pg_linearize(h->stream, d, d.X));
+    if ((rc = read_scalars(h))) return rc;
+    double err = g.h_sc->err;
+    res.error_before = res.error_after = err;
+    res.robust_weight_min = g.h_sc->wmin;
+    for (int it = 0; it < prm.max_iterations; it++) {
+        S2M_HIP(h, pg_rhs(h->stream, d));
+        int cg = 0;
+        if ((rc = run_cg(h, prm, &cg))) return rc;
+        res.inner_iterations += cg;
+        S2M_HIP(h, pg_step(h->stream, d));
+        S2M_HIP(h, pg_linearize(h->stream, d, d.Xtrial));  // the trial point's error, and the next step's linearisation if it is kept
+        if ((rc = read_scalars(h))) return rc;
+        const double err_n = g.h_sc->err;
+        if (!(err_n < err)) { res.converged = 1; break; }
+        std::swap(g.est.p, g.trial.p);
+        std::swap(g.est.cap, g.trial.cap);
+        d.X = g.est.as<double>(); d.Xtrial = g.trial.as<double>();
+        g.dev_newer = true;
+        const double dec = err - err_n, old = err;
+        err = err_n;
+        res.iterations++;
+        res.error_after = err;
+        res.robust_weight_min = g.h_sc->wmin;
+        if (dec < prm.absolute_error_tol || dec < prm.relative_error_tol * old) { res.converged = 1; break; }
+    }
+    if (out) *out = res;
+    return S2M_OK;
+}
+
+int s2m_pg_get_poses(s2m_handle h, int32_t first, int32_t count, float* xyzrpy)
+{
+    if (!h) return S2M_ERR_INVALID_ARG;
+    if (first < 0 || count < 0 || (size_t)first + (size_t)count > pg_n(h) || (count > 0 && !xyzrpy))
+        return fail(h, S2M_ERR_INVALID_ARG, "pose range outside the pose graph");
+    if (count == 0) return S2M_OK;
+    int rc = upload_state(h, (size_t)first, (size_t)count);
+    if (rc) return rc;
+    if ((rc = ensure(h, h->pg.poses, sizeof(float) * 6 * (size_t)count))) return rc;
+    S2M_HIP(h, pg_poses(h->stream, h->pg.est.as<double>(), first, count, h->pg.poses.as<float>(), nullptr));
+    S2M_HIP(h, hipMemcpyAsync(xyzrpy, h->pg.poses.p, sizeof(float) * 6 * (size_t)count, hipMemcpyDeviceToHost, h->stream));
+    S2M_HIP(h, hipStreamSynchronize(h->stream));
+    return S2M_OK;
+}
+
+int s2m_pg_marginal(s2m_handle h, int32_t key, double cov[36])
+{
+    if (!h) return S2M_ERR_INVALID_ARG;
+    if (key < 0 || (size_t)key >= pg_n(h) || !cov) return fail(h, S2M_ERR_INVALID_ARG, "marginal: key outside the pose graph");
+    int rc = prepare(h);
+    if (rc) return rc;
+    s2m_pg_params prm;
+    s2m_pg_default_params(&prm);
+    const PgDev& d = h->pg.dev;
+    S2M_HIP(h, pg_linearize(h->stream, d, d.X));
+    // column a of (J^T J)^-1 = J_c^-1 (I + K^T K)^-1 J_c^-T e_a
+    for (int a = 0; a < 6; a++) {
+        S2M_HIP(h, pg_bwd_unit(h->stream, d, key, a));
+        int cg = 0;
+        if ((rc = run_cg(h, prm, &cg))) return rc;
+        S2M_HIP(h, pg_fwd_y(h->stream, d));
+        double col[6];
+        S2M_HIP(h, hipMemcpyAsync(col, d.delta + 6 * (size_t)key, sizeof(col), hipMemcpyDeviceToHost, h->stream));
+        S2M_HIP(h, hipStreamSynchronize(h->stream));
+        for (int b = 0; b < 6; b++) cov[b * 6 + a] = col[b];
+    }
+    return S2M_OK;
+}
+
+int s2m_pg_apply_to_store(s2m_handle h, int32_t first, int32_t count)
+{
+    if (!h) return S2M_ERR_INVALID_ARG;
+    if (first < 0 || count < 0 || (size_t)first + (size_t)count > pg_n(h) || (size_t)first + (size_t)count > h->kf.time.size())
+        return fail(h, S2M_ERR_INVALID_ARG, "pose range outside the pose graph or the key-frame store");
+    if (count == 0) return S2M_OK;
+    int rc = upload_state(h, (size_t)first, (size_t)count);
+    if (rc) return rc;
+    // Pose vectors and cached transforms are computed on the device into a staging block (the host libm's sinf / cosf are
+    // restated there, so each transform is bit for bit s2m_kf_set_poses'); one copy brings the block and its not-finite flag
+    // to the store's host mirror; only then a second launch writes positions and transforms into the store. A failure up
+    // to the flag leaves the store as it was; nothing is uploaded.
+    const size_t nf = 18 * (size_t)count;
+    if ((rc = ensure(h, h->pg.poses, sizeof(float) * nf + sizeof(int32_t)))) return rc;
+    float* stage = h->pg.poses.as<float>();
+    int32_t* bad = reinterpret_cast<int32_t*>(stage + nf);
+    std::vector<float> back(nf + 1);
+    S2M_HIP(h, hipMemsetAsync(bad, 0, sizeof(int32_t), h->stream));
+    S2M_HIP(h, pg_store_stage(h->stream, h->pg.est.as<double>(), first, count, stage, bad));
+    S2M_HIP(h, hipMemcpyAsync(back.data(), stage, sizeof(float) * nf + sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+    S2M_HIP(h, hipStreamSynchronize(h->stream));
+    int32_t flag;
+    memcpy(&flag, &back[nf], sizeof(flag));
+    if (flag) return fail(h, S2M_ERR_INVALID_ARG, "pose graph: an estimate is not finite; the key-frame store is unchanged");
+    S2M_HIP(h, pg_store_write(h->stream, stage, count, h->kf.pos.as<float4>() + first, h->kf.frames.as<KfFrame>() + first));
+    for (int k = 0; k < count; k++) {
+        const float* q = back.data() + 18 * (size_t)k;
+        std::copy(q, q + 6, h->kf.pose.begin() + 6 * (size_t)(first + k));
+        std::copy(q + 6, q + 18, h->kf.frame[(size_t)(first + k)].T);
+    }
+    return S2M_OK;
+}

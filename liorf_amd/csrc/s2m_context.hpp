@@ -14,6 +14,7 @@
 #include "s2m_voxel.hpp"
 #include "s2m_icp.hpp"
 #include "s2m_project.hpp"
+#include "s2m_pose_graph.hpp"
 
 namespace s2m {
 namespace host __attribute__((visibility("hidden"))) {
@@ -196,6 +197,21 @@ struct __attribute__((visibility("hidden"))) s2m_context {
         bool have_deskewed = false;
         s2m::ProjCount* h_count = nullptr; // pinned: the count, written by the device
     } proj;
+
+    // the pose graph beside the key-frame store (saveKeyFramesAndFactor / correctPoses, :1386-1642): factors and a mirror of the
+    // estimates on the host, the estimates (R, t in fp64), the linearisation, the two chain scans and the CG vectors on the device
+    struct PoseGraph {
+        std::vector<s2m::PgFactor> factors;        // in the order they were added
+        std::vector<double> X;                     // 12 per variable: R row-major, t
+        std::vector<char> has_init, dirty;         // dirty: the host value is newer than the device's
+        bool dev_newer = false;                    // an accepted step: the device's estimates are newer than X
+        bool topo_dirty = true;                    // factors were added since the device tables were built
+        size_t n_dev = 0;                          // variables the device arrays hold
+        DevBuf est, trial, chain, extra, inc_start, inc, Binv, Aof, rc, Ji, Jj, rx, ferr, fw, vecs, partial, sc, poses;
+        DevBuf scan_M[2], scan_Pre[2], scan_loc[2], scan_C0[2];
+        s2m::PgScalars* h_sc = nullptr;            // pinned
+        s2m::PgDev dev{};
+    } pg;
 };
 
 namespace s2m {

@@ -214,6 +214,51 @@ public:
         check(s2m_kf_set_poses(h_, 0, (int)cloudKeyPoses6D.size(), v.data()), "s2m_kf_set_poses");
     }
 
+    // One closure the loop thread queued (loopIndexQueue / loopPoseQueue / loopNoiseQueue, :1513-1534): rel is
+    // poseFrom.between(poseTo) as {x, y, z, roll, pitch, yaw}; robust_k > 0 is the SC loop's Cauchy model.
+    struct LoopFactor { int key_cur, key_pre; float rel[6]; double var[6]; double robust_k; };
+    std::vector<LoopFactor> loopQueue;
+    bool aLoopIsClosed = false;
+    s2m_pg_result lastGraphResult{};
+
+    // saveKeyFramesAndFactor() (:1536-1609) on the library's pose graph, without the saveFrame() gate and the GPS queue (the
+    // caller's): odometry factor, the queued loop factors, the update - twice after a closure, as the reference repeats
+    // isam->update() - then the key frame with the graph's latest estimate, which also becomes transformTobeMapped (:1583-1588).
+    void saveKeyFramesAndFactor()
+    {
+        const float v[6] = { transformTobeMapped[3], transformTobeMapped[4], transformTobeMapped[5],
+                             transformTobeMapped[0], transformTobeMapped[1], transformTobeMapped[2] };
+        check(s2m_pg_add_odometry(h_, v), "s2m_pg_add_odometry");
+        for (const LoopFactor& l : loopQueue) {
+            check(s2m_pg_add_between(h_, l.key_cur, l.key_pre, l.rel, l.var, l.robust_k), "s2m_pg_add_between");
+            aLoopIsClosed = true;
+        }
+        loopQueue.clear();
+        check(s2m_pg_optimize(h_, nullptr, &lastGraphResult), "s2m_pg_optimize");
+        if (aLoopIsClosed) check(s2m_pg_optimize(h_, nullptr, &lastGraphResult), "s2m_pg_optimize");
+        float latest[6];
+        check(s2m_pg_get_poses(h_, (int32_t)cloudKeyPoses6D.size(), 1, latest), "s2m_pg_get_poses");
+        transformTobeMapped[3] = latest[0]; transformTobeMapped[4] = latest[1]; transformTobeMapped[5] = latest[2];
+        transformTobeMapped[0] = latest[3]; transformTobeMapped[1] = latest[4]; transformTobeMapped[2] = latest[5];
+        saveKeyFrame();
+    }
+
+    // correctPoses() (:1611-1642) from the pose graph: the store is corrected in place on the device, cloudKeyPoses6D follows
+    bool correctPosesFromGraph()
+    {
+        if (cloudKeyPoses6D.empty() || !aLoopIsClosed) return false;
+        const int32_t n = (int32_t)cloudKeyPoses6D.size();
+        check(s2m_pg_apply_to_store(h_, 0, n), "s2m_pg_apply_to_store");
+        std::vector<float> v(6 * (size_t)n);
+        check(s2m_pg_get_poses(h_, 0, n, v.data()), "s2m_pg_get_poses");
+        for (int32_t k = 0; k < n; k++) {
+            PointTypePose& q = cloudKeyPoses6D[(size_t)k];
+            q.x = v[6 * k]; q.y = v[6 * k + 1]; q.z = v[6 * k + 2]; q.roll = v[6 * k + 3]; q.pitch = v[6 * k + 4]; q.yaw = v[6 * k + 5];
+        }
+        aLoopIsClosed = false;
+        return true;
+    }
+
     // The global map and the saved map from the store (s2m_global_map, s2m_kf_map_cloud): visualizeGlobalMapThread() and
     // saveMapService() need no host copy of surfCloudKeyFrames. Both run under the lock the scan handler holds, for the
     // whole call; the node still publishes the cloud and writes the PCD files (trajectory.pcd / transformations.pcd from

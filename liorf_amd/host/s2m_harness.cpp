@@ -18,6 +18,10 @@
 //   s2m_harness --global-map keys.bin keys.txt scan_leaf search_radius pose_density leaf out.bin
 //       the key frames through downsampleCurrentScan() -> saveKeyFrame(), then publishGlobalMap() (globalMapKeyFramesDS written
 //       to out.bin) and saveMapService()'s unfiltered cloud; prints the key list and both sizes.
+//   s2m_harness --pose-graph keys.bin keys.txt scan_leaf loops.txt out.bin
+//       the pose graph beside the store: every key through downsampleCurrentScan() -> saveKeyFramesAndFactor() (with the loop
+//       factors loops.txt queues for it) -> correctPosesFromGraph(); prints every update, the graph's estimates and the
+//       size of the unfiltered map cloud, which goes to out.bin.
 //   s2m_harness --project raw.bin sensor stamp imu.bin n_scan downsample_rate point_filter_num scan_leaf out.bin ds.bin
 //       the front end: cachePointCloud() of the raw records (sensor 0..4), imuDeskewInfo() over the samples of imu.bin
 //       ({time, wx, wy, wz} doubles), projectPointCloud(), downsampleCurrentScanProjected(), the ScanContext add from the
@@ -351,6 +355,61 @@ static int run_many(int argc, char** argv)
     return 0;
 }
 
+// --pose-graph keys.bin keys.txt scan_leaf loops.txt out.bin: keys.txt as for --loop (the pose is the front end's); loops.txt holds
+// one line "at key_cur key_pre x y z roll pitch yaw variance robust_k" per closure, queued before key `at` is processed. Prints
+// "key <i> iterations inner converged factors error pose(6) corrected" per key, then "kp <i> pose(6)" per key (the graph's
+// estimates) and "map_cloud <n>".
+static int run_pose_graph(char** argv)
+{
+    liorf_amd::MapOptimizationS2M node;
+    const std::vector<liorf_amd::PointXYZI> all = read_cloud(argv[2]);
+    std::ifstream tab(argv[3]);
+    if (!tab) throw std::runtime_error(std::string("cannot open ") + argv[3]);
+    node.mappingSurfLeafSize = (float)std::atof(argv[4]);
+    std::ifstream lf(argv[5]);
+    if (!lf) throw std::runtime_error(std::string("cannot open ") + argv[5]);
+    std::vector<std::pair<int, liorf_amd::MapOptimizationS2M::LoopFactor>> loops;
+    {
+        int at;
+        liorf_amd::MapOptimizationS2M::LoopFactor l;
+        double var;
+        while (lf >> at >> l.key_cur >> l.key_pre >> l.rel[0] >> l.rel[1] >> l.rel[2] >> l.rel[3] >> l.rel[4] >> l.rel[5] >> var >> l.robust_k) {
+            for (int k = 0; k < 6; k++) l.var[k] = var;
+            loops.push_back({ at, l });
+        }
+    }
+    size_t n, at = 0;
+    double t;
+    float p[6];
+    for (int i = 0; tab >> n >> t >> p[0] >> p[1] >> p[2] >> p[3] >> p[4] >> p[5]; i++) {
+        if (at + n > all.size()) throw std::runtime_error("keys.txt asks for more points than keys.bin holds");
+        node.timeLaserInfoCur = t;
+        node.laserCloudSurfLast.assign(all.begin() + (std::ptrdiff_t)at, all.begin() + (std::ptrdiff_t)(at + n));
+        at += n;
+        node.downsampleCurrentScan();
+        const float rpyxyz[6] = { p[3], p[4], p[5], p[0], p[1], p[2] };
+        for (int k = 0; k < 6; k++) node.transformTobeMapped[k] = rpyxyz[k];
+        for (const auto& l : loops) if (l.first == i) node.loopQueue.push_back(l.second);
+        node.saveKeyFramesAndFactor();
+        const bool corrected = node.correctPosesFromGraph();
+        const s2m_pg_result& r = node.lastGraphResult;
+        const float* q = node.transformTobeMapped;
+        std::printf("key %d %d %d %d %d %.17g %.9g %.9g %.9g %.9g %.9g %.9g %d\n", i, r.iterations, r.inner_iterations, r.converged, r.n_factors,
+                    r.error_after, q[3], q[4], q[5], q[0], q[1], q[2], corrected ? 1 : 0);
+    }
+    const size_t N = node.cloudKeyPoses6D.size();
+    std::vector<float> est(6 * N);
+    if (N > 0 && s2m_pg_get_poses(node.handle(), 0, (int32_t)N, est.data()) != S2M_OK) throw std::runtime_error("s2m_pg_get_poses");
+    for (size_t k = 0; k < N; k++)
+        std::printf("kp %zu %.9g %.9g %.9g %.9g %.9g %.9g\n", k, est[6 * k], est[6 * k + 1], est[6 * k + 2], est[6 * k + 3], est[6 * k + 4], est[6 * k + 5]);
+    std::vector<liorf_amd::PointXYZI> cloud;
+    node.globalMapCloud(cloud, 0.0f);
+    std::printf("map_cloud %zu\n", cloud.size());
+    std::ofstream out(argv[6], std::ios::binary);
+    out.write(reinterpret_cast<const char*>(cloud.data()), (std::streamsize)(cloud.size() * sizeof(liorf_amd::PointXYZI)));
+    return 0;
+}
+
 int main(int argc, char** argv)
 {
     try {
@@ -360,6 +419,7 @@ int main(int argc, char** argv)
         if (argc == 7 && std::string(argv[1]) == "--keyframes") return run_keyframes(argv);
         if (argc == 9 && std::string(argv[1]) == "--loop") return run_loop(argv);
         if (argc == 9 && std::string(argv[1]) == "--global-map") return run_global_map(argv);
+        if (argc == 7 && std::string(argv[1]) == "--pose-graph") return run_pose_graph(argv);
         if (argc == 12 && std::string(argv[1]) == "--project") return run_project(argv);
         if (argc == 14 && std::string(argv[1]) == "--front-end") return run_front_end(argv);
         if (argc != 9 && argc != 16) {

@@ -43,6 +43,8 @@ ABI_SYMBOLS = [
     "s2m_scan_layout_preset", "s2m_project_default_params", "s2m_imu_deskew_info", "s2m_project_check_args", "s2m_project_scan",
     "s2m_downsample_projected", "s2m_sc_add_projected",
     "s2m_odom_deskew_info", "s2m_project_check_args_motion", "s2m_project_scan_motion", "s2m_guess_state_init", "s2m_update_initial_guess",
+    "s2m_pg_default_params", "s2m_pg_check_args", "s2m_pg_reset", "s2m_pg_size", "s2m_pg_add_prior", "s2m_pg_add_between", "s2m_pg_add_gps",
+    "s2m_pg_set_initial", "s2m_pg_add_odometry", "s2m_pg_optimize", "s2m_pg_get_poses", "s2m_pg_marginal", "s2m_pg_apply_to_store",
 ]
 S2M_RING_U8, S2M_RING_U16, S2M_RING_I32 = 0, 1, 2
 S2M_TIME_F32, S2M_TIME_U32_NS, S2M_TIME_U32, S2M_TIME_F64_REL = 0, 1, 2, 3
@@ -51,6 +53,7 @@ S2M_IMU_QUEUE_LENGTH = 2000
 S2M_KF_FROM_HOST, S2M_KF_FROM_DEVICE, S2M_KF_FROM_LAST_DOWNSAMPLE = 0, 1, 2
 S2M_LOOP_NONE, S2M_LOOP_ALREADY_CLOSED, S2M_LOOP_TOO_FEW_POINTS, S2M_LOOP_REJECTED, S2M_LOOP_ACCEPTED = 0, 1, 2, 3, 4
 S2M_WARN_LEAF_TOO_SMALL = 1
+S2M_PG_PRIOR, S2M_PG_BETWEEN, S2M_PG_GPS, S2M_PG_INITIAL = 0, 1, 2, 3
 
 
 class Params(C.Structure):
@@ -156,6 +159,18 @@ class GuessState(C.Structure):
 class GuessInfo(C.Structure):
     _fields_ = [("imuAvailable", C.c_int64), ("odomAvailable", C.c_int64), ("imuRollInit", C.c_float), ("imuPitchInit", C.c_float),
                 ("imuYawInit", C.c_float), ("initialGuess", C.c_float * 6)]
+
+
+class PgParams(C.Structure):
+    _fields_ = [("prior_var", C.c_double * 6), ("odom_var", C.c_double * 6), ("sc_loop_var", C.c_double * 6),
+                ("sc_loop_robust_k", C.c_double), ("relative_error_tol", C.c_double), ("absolute_error_tol", C.c_double),
+                ("cg_rel_tol", C.c_double), ("max_iterations", C.c_int32), ("cg_max_iterations", C.c_int32)]
+
+
+class PgResult(C.Structure):
+    _fields_ = [("iterations", C.c_int32), ("inner_iterations", C.c_int32), ("converged", C.c_int32), ("n_variables", C.c_int32),
+                ("n_factors", C.c_int32), ("reserved", C.c_int32), ("error_before", C.c_double), ("error_after", C.c_double),
+                ("robust_weight_min", C.c_double)]
 
 
 class S2MError(RuntimeError):
@@ -277,6 +292,19 @@ def load_library(path: str | None = None) -> C.CDLL:
     L.s2m_project_scan_motion.argtypes = [vp, vp, C.c_size_t, C.POINTER(ScanLayout), C.c_int, C.POINTER(ProjectParams),
                                           C.POINTER(DeskewInfo), C.POINTER(MotionInfo), vp, C.c_size_t, C.c_size_t, szp]
     L.s2m_guess_state_init.argtypes = [C.POINTER(GuessState)]
+    L.s2m_pg_default_params.argtypes = [C.POINTER(PgParams)]
+    L.s2m_pg_check_args.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int32, fp, dp, C.c_double]
+    L.s2m_pg_reset.argtypes = [vp]
+    L.s2m_pg_size.argtypes = [vp, i32p, i32p]
+    L.s2m_pg_add_prior.argtypes = [vp, C.c_int32, fp, dp]
+    L.s2m_pg_add_between.argtypes = [vp, C.c_int32, C.c_int32, fp, dp, C.c_double]
+    L.s2m_pg_add_gps.argtypes = [vp, C.c_int32, fp, dp]
+    L.s2m_pg_set_initial.argtypes = [vp, C.c_int32, fp]
+    L.s2m_pg_add_odometry.argtypes = [vp, fp]
+    L.s2m_pg_optimize.argtypes = [vp, C.POINTER(PgParams), C.POINTER(PgResult)]
+    L.s2m_pg_get_poses.argtypes = [vp, C.c_int32, C.c_int32, fp]
+    L.s2m_pg_marginal.argtypes = [vp, C.c_int32, dp]
+    L.s2m_pg_apply_to_store.argtypes = [vp, C.c_int32, C.c_int32]
     L.s2m_update_initial_guess.argtypes = [C.POINTER(GuessState), C.POINTER(C.c_float), C.c_int, C.POINTER(GuessInfo), C.c_int, C.c_int,
                                            C.POINTER(C.c_float)]
     if path is None:
@@ -827,6 +855,91 @@ class MapOptimizationS2M:
         run(out.ctypes.data, m.value)                 # (the same selection again: deterministic, same map)
         return k, out[:m.value]
 
+    # -- the pose graph beside the store (reference :1386-1534, :1611-1642) --------
+    def pgReset(self):
+        self._check(self.lib.s2m_pg_reset(self.h), "s2m_pg_reset")
+        self.aLoopIsClosed = False
+
+    def pgSize(self) -> tuple[int, int]:
+        nv, nf = C.c_int32(0), C.c_int32(0)
+        self._check(self.lib.s2m_pg_size(self.h, C.byref(nv), C.byref(nf)), "s2m_pg_size")
+        return nv.value, nf.value
+
+    def pgAddPrior(self, key: int, pose_xyzrpy, var):
+        p, v = np.ascontiguousarray(pose_xyzrpy, np.float32).reshape(6), np.ascontiguousarray(var, np.float64).reshape(6)
+        self._check(self.lib.s2m_pg_add_prior(self.h, key, _fp(p), _dp(v)), "s2m_pg_add_prior")
+
+    def pgAddBetween(self, key_from: int, key_to: int, rel_xyzrpy, var, robust_k: float = 0.0):
+        p, v = np.ascontiguousarray(rel_xyzrpy, np.float32).reshape(6), np.ascontiguousarray(var, np.float64).reshape(6)
+        self._check(self.lib.s2m_pg_add_between(self.h, key_from, key_to, _fp(p), _dp(v), float(robust_k)), "s2m_pg_add_between")
+
+    def pgAddGps(self, key: int, xyz, var):
+        p, v = np.ascontiguousarray(xyz, np.float32).reshape(3), np.ascontiguousarray(var, np.float64).reshape(3)
+        self._check(self.lib.s2m_pg_add_gps(self.h, key, _fp(p), _dp(v)), "s2m_pg_add_gps")
+
+    def pgSetInitial(self, key: int, pose_xyzrpy):
+        p = np.ascontiguousarray(pose_xyzrpy, np.float32).reshape(6)
+        self._check(self.lib.s2m_pg_set_initial(self.h, key, _fp(p)), "s2m_pg_set_initial")
+
+    def addOdomFactor(self, pose_xyzrpy):
+        """addOdomFactor() (reference :1386-1400)."""
+        p = np.ascontiguousarray(pose_xyzrpy, np.float32).reshape(6)
+        self._check(self.lib.s2m_pg_add_odometry(self.h, _fp(p)), "s2m_pg_add_odometry")
+
+    def addLoopFactor(self, key_cur: int, key_pre: int, pose_from, pose_to, var, robust_k: float = 0.0, rel=None):
+        """addLoopFactor() (reference :1513-1534) for one queued closure: the between factor poseFrom.between(poseTo) of a
+        LoopResult (RS: var = six times icp.fitness_score; SC: default_pg_params().sc_loop_var and .sc_loop_robust_k)."""
+        if rel is None:                                  # (rel: the between pose itself, when the caller already holds it)
+            rel = between_xyzrpy(pose_from, pose_to)
+        self.pgAddBetween(key_cur, key_pre, rel, var, robust_k)
+        self.aLoopIsClosed = True
+
+    def pgOptimize(self, params: PgParams | None = None) -> PgResult:
+        out = PgResult()
+        self._check(self.lib.s2m_pg_optimize(self.h, C.byref(params) if params is not None else None, C.byref(out)), "s2m_pg_optimize")
+        return out
+
+    def pgPoses(self, first: int = 0, count: int | None = None) -> np.ndarray:
+        if count is None:
+            count = self.pgSize()[0] - first
+        out = np.zeros((max(count, 0), 6), np.float32)
+        self._check(self.lib.s2m_pg_get_poses(self.h, first, count, _fp(out)), "s2m_pg_get_poses")
+        return out
+
+    def pgMarginal(self, key: int) -> np.ndarray:
+        cov = np.zeros((6, 6), np.float64)
+        self._check(self.lib.s2m_pg_marginal(self.h, key, _dp(cov)), "s2m_pg_marginal")
+        return cov
+
+    def pgApplyToStore(self, first: int = 0, count: int | None = None):
+        if count is None:
+            count = self.pgSize()[0] - first
+        self._check(self.lib.s2m_pg_apply_to_store(self.h, first, count), "s2m_pg_apply_to_store")
+
+    def saveKeyFramesAndFactor(self, pose_xyzrpy, time: float, cloud=None, loops=(), params: PgParams | None = None):
+        """saveKeyFramesAndFactor() (reference :1536-1609) without the saveFrame() gate and the GPS queue, which stay with the
+        caller: odometry factor, the queued loop factors `loops` (tuples for addLoopFactor), the update - and, as the
+        reference runs isam->update() five more times after a closure, a second optimise - then the key frame with the
+        graph's latest estimate.  Returns (PgResult, the stored pose)."""
+        self.addOdomFactor(pose_xyzrpy)
+        for lp in loops:
+            self.addLoopFactor(*lp)
+        res = self.pgOptimize(params)
+        if getattr(self, "aLoopIsClosed", False):
+            res = self.pgOptimize(params)
+        n = self.pgSize()[0]
+        latest = self.pgPoses(n - 1, 1)[0]
+        self.saveKeyFrame(latest, time, cloud)
+        return res, latest
+
+    def correctPosesFromGraph(self) -> bool:
+        """correctPoses() (reference :1611-1642): after a closure every key of the store takes the graph's estimate."""
+        if self.kfSize() <= 0 or not getattr(self, "aLoopIsClosed", False):
+            return False
+        self.pgApplyToStore(0, self.kfSize())
+        self.aLoopIsClosed = False
+        return True
+
     # -- the global map and the saved map from the resident store (reference :453-502, :375-432) --------
     def publishGlobalMap(self, params: GmapParams | None = None, return_keys: bool = False):
         """publishGlobalMap() (reference :453-502) on the resident store: globalMapKeyFramesDS as (m, 8) float32 records;
@@ -912,6 +1025,45 @@ class MapOptimizationS2M:
         if pre == -1:
             return r
         return self.loopAlign(n - 1, pre, 0, params)
+
+
+def between_xyzrpy(pose_from, pose_to) -> np.ndarray:
+    """poseFrom.between(poseTo) of two {x, y, z, roll, pitch, yaw} poses (Rot3::RzRyRx), fp64, as a float pose vector."""
+    def mat(p):
+        p = np.asarray(p, np.float64)
+        cr, sr, cp, sp, cy, sy = np.cos(p[3]), np.sin(p[3]), np.cos(p[4]), np.sin(p[4]), np.cos(p[5]), np.sin(p[5])
+        return np.array([[cy * cp, cy * sp * sr - sy * cr, sy * sr + cy * sp * cr],
+                         [sy * cp, cy * cr + sy * sp * sr, sy * sp * cr - cy * sr],
+                         [-sp, cp * sr, cp * cr]]), p[:3]
+    Ra, ta = mat(pose_from)
+    Rb, tb = mat(pose_to)
+    R, t = Ra.T @ Rb, Ra.T @ (tb - ta)
+    return np.array([t[0], t[1], t[2], np.arctan2(R[2, 1], R[2, 2]), np.arcsin(np.clip(-R[2, 0], -1.0, 1.0)),
+                     np.arctan2(R[1, 0], R[0, 0])], np.float32)
+
+
+def default_pg_params(**kw) -> PgParams:
+    p = PgParams()
+    rc = load_library().s2m_pg_default_params(C.byref(p))
+    if rc != S2M_OK:
+        raise S2MError(rc, "s2m_pg_default_params")
+    for k, v in kw.items():
+        if isinstance(v, (list, tuple, np.ndarray)):
+            v = (C.c_double * 6)(*[float(x) for x in v])
+        setattr(p, k, v)
+    return p
+
+
+def _dp(a):
+    return a.ctypes.data_as(C.POINTER(C.c_double))
+
+
+def pg_check_args(kind: int, n_variables: int, key_a: int, key_b: int, values, var=None, robust_k: float = 0.0) -> int:
+    """s2m_pg_check_args (host only, no GPU): the status code."""
+    v = None if values is None else np.ascontiguousarray(values, np.float32)
+    w = None if var is None else np.ascontiguousarray(var, np.float64)
+    return load_library().s2m_pg_check_args(kind, n_variables, key_a, key_b, None if v is None else _fp(v),
+                                            None if w is None else _dp(w), float(robust_k))
 
 
 def default_kf_params(**kw) -> KfParams:

@@ -1,0 +1,101 @@
+"""Wall time of one pose-graph optimise after one added loop, and of s2m_pg_apply_to_store, against the CPU reference.
+
+The synthetic figure-of-eight of tests/ref/pose_graph_ref.py (seed 20250204, driven twice, keys 1 m apart, 40 loops) at
+2 000, 10 000 and 50 000 keys.  The graph is optimised once with its 40 loops; then one more loop is added and the next
+optimise is timed - the state a node is in when a closure arrives.  Beside each device figure:
+  cpu_optimize_ms   the reference's whole optimise of the same problem (numpy linearisation, scipy sparse normal equations)
+  cpu_solve_ms      of that, the sparse solves alone - what a compiled CPU library would also pay
+apply_to_store_ms is s2m_pg_apply_to_store over the whole store (10-point frames), set_poses_ms the path it replaces:
+s2m_pg_get_poses to the caller and s2m_kf_set_poses back.
+
+  python tools/bench_pose_graph.py [--sizes 2000,10000,50000] [--out profiles/pose_graph_bench_line.json]
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests", "ref"))
+import pose_graph_cases as CS  # noqa: E402
+import pose_graph_ref as P  # noqa: E402
+from liorf_amd import s2m, synth  # noqa: E402
+
+
+def one_size(n, reps):
+    g = P.figure_eight(n, 40)
+    half = n // 2
+    truth = P.figure_eight(n, 0, truth_only=True)
+    i, j = n - 3, n - 3 - half
+    rel = P.xyzrpy_from_pose(truth[i][0].T @ truth[j][0], truth[i][0].T @ (truth[j][1] - truth[i][1])).astype(np.float32)
+    m = s2m.MapOptimizationS2M()
+    out = {}
+    try:
+        cloud = synth.to_xyzi(np.random.default_rng(0).uniform(-5, 5, (10, 3)).astype(np.float32))
+        init = g.poses().astype(np.float32)
+        for k in range(n):
+            m.saveKeyFrame(init[k], float(k), cloud)
+        t = []
+        for _ in range(reps):
+            CS.load_into(m, g)
+            first = m.pgOptimize()
+            m.pgAddBetween(i, j, rel, np.full(6, 0.3))
+            t0 = time.perf_counter()
+            res = m.pgOptimize()
+            t.append(time.perf_counter() - t0)
+        out.update(first_iterations=first.iterations, first_inner_iterations=first.inner_iterations, iterations=res.iterations,
+                   inner_iterations=res.inner_iterations, converged=res.converged, error_after=res.error_after,
+                   optimize_ms=round(1e3 * float(np.median(t)), 3))
+        ta, ts = [], []
+        for _ in range(reps):
+            t0 = time.perf_counter(); m.pgApplyToStore(0, n); ta.append(time.perf_counter() - t0)
+            t0 = time.perf_counter(); m.correctPoses(m.pgPoses(), 0); ts.append(time.perf_counter() - t0)
+        out.update(apply_to_store_ms=round(1e3 * float(np.median(ta)), 3), set_poses_ms=round(1e3 * float(np.median(ts)), 3))
+    finally:
+        m.close()
+    # the CPU reference on the same problem
+    P.optimize(g, "normal")
+    g.add_between(i, j, rel, np.full(6, 0.3))
+    solve_s = [0.0]
+    inner = P.solve_step
+
+    def timed(*a):
+        t0 = time.perf_counter()
+        r = inner(*a)
+        solve_s[0] += time.perf_counter() - t0
+        return r
+    P.solve_step = timed
+    try:
+        t0 = time.perf_counter()
+        ref = P.optimize(g, "normal")
+        cpu = time.perf_counter() - t0
+    finally:
+        P.solve_step = inner
+    out.update(cpu_iterations=ref.iterations, cpu_error_after=ref.error_after, cpu_optimize_ms=round(1e3 * cpu, 3),
+               cpu_solve_ms=round(1e3 * solve_s[0], 3))
+    return out
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--sizes", default="2000,10000,50000")
+    ap.add_argument("--reps", type=int, default=3)
+    ap.add_argument("--out", default=None)
+    a = ap.parse_args()
+    line = {"workload": "figure-of-eight driven twice, 40 loops, one optimise after one added loop (seed %d)" % P.SEED, "sizes": {}}
+    for n in [int(x) for x in a.sizes.split(",")]:
+        line["sizes"][str(n)] = one_size(n, a.reps)
+        print(n, json.dumps(line["sizes"][str(n)]), file=sys.stderr, flush=True)
+    txt = json.dumps(line)
+    print(txt)
+    if a.out:
+        with open(a.out, "w") as f:
+            f.write(txt + "\n")
+
+
+if __name__ == "__main__":
+    main()
