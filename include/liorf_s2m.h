@@ -742,6 +742,21 @@ int  s2m_pg_get_poses(s2m_handle h, int32_t first, int32_t count, float* xyzrpy)
 /* poseCovariance (:1565): the marginal covariance of `key` at the current estimates, row-major 6x6 in the tangent
  * order of rotation then translation, with the robust weights of those estimates. */
 int  s2m_pg_marginal(s2m_handle h, int32_t key, double cov[36]);
+/* Marginals of many keys, and the joint marginal of two, by a block solve: the six columns of every key's block are
+ * right-hand sides that advance in lockstep through shared launches, S2M_PG_BLOCK_COLUMNS of them per pass, each bit for
+ * bit what s2m_pg_marginal computes for it. One linearisation per call; per pass one copy of the wanted rows back.
+ * Errors and chain requirements are those of s2m_pg_marginal; the graph is not changed.
+ *   s2m_pg_marginals_check_args: the key list's checks on their own (host code, no handle, no GPU): S2M_OK, or
+ *       S2M_ERR_INVALID_ARG for null keys with n_keys > 0, n_keys < 0, or a key outside 0..n_variables-1.
+ *   s2m_pg_marginals: cov is n_keys x 36, block k the marginal of keys[k] in s2m_pg_marginal's layout and order. Keys may
+ *       repeat; n_keys == 0 is S2M_OK.
+ *   s2m_pg_joint_marginal: row-major 12x12 over [key_a's tangent, key_b's tangent]; block (r, c) holds the rows of key r in
+ *       the columns solved for key c, so the diagonal blocks are s2m_pg_marginal's. Not symmetrised: cov[:6, 6:] and the
+ *       transpose of cov[6:, :6] agree to the solve's accuracy. key_a == key_b is S2M_ERR_INVALID_ARG. */
+#define S2M_PG_BLOCK_COLUMNS 24
+int  s2m_pg_marginals_check_args(int32_t n_variables, const int32_t* keys, int32_t n_keys);
+int  s2m_pg_marginals(s2m_handle h, const int32_t* keys, int32_t n_keys, double* cov);
+int  s2m_pg_joint_marginal(s2m_handle h, int32_t key_a, int32_t key_b, double cov[144]);
 /* correctPoses() (:1611-1642): the estimates of variables first .. first+count-1 become the poses of the same keys of
  * the key-frame store, computed and written on the device: the float pose vector of s2m_pg_get_poses, the position, and
  * each key's cached transform with the host libm's sinf / cosf restated on the device, so that the store ends up bit for

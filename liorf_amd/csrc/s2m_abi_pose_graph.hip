@@ -165,7 +165,7 @@ int prepare(s2m_context* h)
     for (size_t k = 1; k < n; k++)
         if (chain_of[k] < 0) return fail(h, S2M_ERR_INVALID_ARG, "pose graph: a variable is not on the odometry chain from key 0");
     if ((rc = upload_state(h, 0, n))) return rc;
-    if (!g.h_sc) S2M_HIP(h, hipHostMalloc((void**)&g.h_sc, sizeof(PgScalars)));
+    if (!g.h_sc) S2M_HIP(h, hipHostMalloc((void**)&g.h_sc, sizeof(PgScalars) * (1 + kPgBlockCols)));   // [0]: the single solve, then one per column
     if (g.topo_dirty) {
         std::vector<char> on_chain(g.factors.size(), 0);
         std::vector<PgFactor> chain(n), extra;
@@ -235,6 +235,65 @@ int run_cg(s2m_context* h, const s2m_pg_params& prm, int* iters)
         if (h->pg.h_sc->stop) break;
     }
     *iters = h->pg.h_sc->iters;
+    return S2M_OK;
+}
+
+// ---- the block solve behind s2m_pg_marginals / s2m_pg_joint_marginal ----
+static_assert(kPgBlockCols == S2M_PG_BLOCK_COLUMNS && kPgBlockCols >= 12 && kPgBlockCols % 6 == 0, "a pass holds whole keys, and a joint marginal");
+
+// block storage for `cols` columns (grow-only) after prepare(): db is the graph's PgDev with its work arrays in that storage
+int prepare_block(s2m_context* h, int cols, PgDev& db, PgCols& c)
+{
+    auto& g = h->pg;
+    const PgDev& d = g.dev;
+    const size_t n = (size_t)d.n, m = std::max<size_t>((size_t)d.n_extra, 1), C = (size_t)cols;
+    size_t total = 0;
+    for (int l = 0; l < d.fwd.levels; l++) total += (size_t)d.fwd.n[l];
+    int rc;
+    if ((rc = ensure(h, g.blk_vecs, sizeof(double) * 6 * (9 * n + m) * C)) || (rc = ensure(h, g.blk_loc[0], sizeof(double) * 6 * total * C)) ||
+        (rc = ensure(h, g.blk_loc[1], sizeof(double) * 6 * total * C)) || (rc = ensure(h, g.blk_partial, sizeof(double) * kPgDotBlocks * C)) ||
+        (rc = ensure(h, g.blk_sc, sizeof(PgScalars) * C)) || (rc = ensure(h, g.blk_rows, sizeof(double) * 12 * C))) return rc;
+    db = d;
+    double* v = g.blk_vecs.as<double>();
+    double** slots[9] = { &db.b, &db.y, &db.r, &db.p, &db.q, &db.t1, &db.t2, &db.g, &db.delta };
+    for (int k = 0; k < 9; k++) *slots[k] = v + 6 * n * C * (size_t)k;
+    db.u = v + 6 * n * C * 9;
+    db.partial = g.blk_partial.as<double>();
+    db.sc = g.blk_sc.as<PgScalars>();
+    for (int l = 0; l < d.fwd.levels; l++) {               // each column's levels lie as the single form's do
+        db.fwd.loc[l] = g.blk_loc[0].as<double>() + (d.fwd.loc[l] - d.fwd.loc[0]);
+        db.bwd.loc[l] = g.blk_loc[1].as<double>() + (d.bwd.loc[l] - d.bwd.loc[0]);
+    }
+    c = PgCols{ cols, 0, 6 * n, 6 * m, 6 * total, 6 * total };
+    return S2M_OK;
+}
+
+// One pass: column k is e_(at[k]) through J_c^-T, CG and J_c^-1; rows[12 k ..] holds its delta at keys ka[k] and kb[k].
+// Every column's scalars come back in one copy per chunk of iterations; the pass ends when all have stopped.
+int solve_pass(s2m_context* h, const PgDev& db, const PgCols& c, const s2m_pg_params& prm, const PgColAt& at, const PgColAt& ka, const PgColAt& kb,
+               double* rows)
+{
+    S2M_HIP(h, pg_bwd_unit_cols(h->stream, db, c, at));
+    int max_cg = prm.cg_max_iterations > 0 ? prm.cg_max_iterations : 6 * db.n_extra + 20;
+    if (db.n_extra == 0) max_cg = 1;
+    S2M_HIP(h, pg_cg_begin_cols(h->stream, db, c, prm.cg_rel_tol, max_cg));
+    constexpr int kChunk = 24;
+    PgScalars* hs = h->pg.h_sc + 1;
+    for (int done = 0; done < max_cg;) {
+        const int k = std::min(kChunk, max_cg - done);
+        S2M_HIP(h, pg_cg_iterations_cols(h->stream, db, c, k));
+        S2M_HIP(h, hipMemcpyAsync(hs, db.sc, sizeof(PgScalars) * (size_t)c.cols, hipMemcpyDeviceToHost, h->stream));
+        S2M_HIP(h, hipStreamSynchronize(h->stream));
+        done += k;
+        bool all = true;
+        for (int q = 0; q < c.cols; q++) all = all && hs[q].stop;
+        if (all) break;
+    }
+    S2M_HIP(h, pg_fwd_y_cols(h->stream, db, c));
+    double* dev_rows = h->pg.blk_rows.as<double>();
+    S2M_HIP(h, pg_rows_cols(h->stream, db, c, ka, kb, dev_rows));
+    S2M_HIP(h, hipMemcpyAsync(rows, dev_rows, sizeof(double) * 12 * (size_t)c.cols, hipMemcpyDeviceToHost, h->stream));
+    S2M_HIP(h, hipStreamSynchronize(h->stream));
     return S2M_OK;
 }
 
@@ -435,6 +494,65 @@ int s2m_pg_marginal(s2m_handle h, int32_t key, double cov[36])
         S2M_HIP(h, hipStreamSynchronize(h->stream));
         for (int b = 0; b < 6; b++) cov[b * 6 + a] = col[b];
     }
+    return S2M_OK;
+}
+
+int s2m_pg_marginals_check_args(int32_t n_variables, const int32_t* keys, int32_t n_keys)
+{
+    if (n_keys < 0 || (n_keys > 0 && !keys)) return S2M_ERR_INVALID_ARG;
+    for (int32_t k = 0; k < n_keys; k++)
+        if (keys[k] < 0 || keys[k] >= n_variables) return S2M_ERR_INVALID_ARG;
+    return S2M_OK;
+}
+
+int s2m_pg_marginals(s2m_handle h, const int32_t* keys, int32_t n_keys, double* cov)
+{
+    if (!h) return S2M_ERR_INVALID_ARG;
+    if (s2m_pg_marginals_check_args((int32_t)pg_n(h), keys, n_keys) || (n_keys > 0 && !cov))
+        return fail(h, S2M_ERR_INVALID_ARG, "marginals: a key outside the pose graph, or a null array");
+    if (n_keys == 0) return S2M_OK;
+    int rc = prepare(h);
+    if (rc) return rc;
+    s2m_pg_params prm;
+    s2m_pg_default_params(&prm);
+    constexpr int kKeys = kPgBlockCols / 6;                 // keys per pass
+    PgDev db;
+    PgCols c;
+    if ((rc = prepare_block(h, 6 * std::min<int>(n_keys, kKeys), db, c))) return rc;
+    S2M_HIP(h, pg_linearize(h->stream, h->pg.dev, h->pg.dev.X));
+    double rows[12 * kPgBlockCols];
+    for (int32_t k0 = 0; k0 < n_keys; k0 += kKeys) {
+        const int nk = std::min<int>(kKeys, n_keys - k0);
+        PgColAt at{}, ka{}, kb{};
+        for (int q = 0; q < 6 * nk; q++) { ka.v[q] = keys[k0 + q / 6]; at.v[q] = 6 * ka.v[q] + q % 6; kb.v[q] = -1; }
+        c.cols = 6 * nk;
+        if ((rc = solve_pass(h, db, c, prm, at, ka, kb, rows))) return rc;
+        for (int q = 0; q < 6 * nk; q++)                    // column q % 6 of key q / 6's block
+            for (int b = 0; b < 6; b++) cov[36 * (size_t)(k0 + q / 6) + b * 6 + q % 6] = rows[12 * q + b];
+    }
+    return S2M_OK;
+}
+
+int s2m_pg_joint_marginal(s2m_handle h, int32_t key_a, int32_t key_b, double cov[144])
+{
+    if (!h) return S2M_ERR_INVALID_ARG;
+    const int32_t keys[2] = { key_a, key_b };
+    if (s2m_pg_marginals_check_args((int32_t)pg_n(h), keys, 2) || key_a == key_b || !cov)
+        return fail(h, S2M_ERR_INVALID_ARG, "joint marginal: two different keys of the pose graph");
+    int rc = prepare(h);
+    if (rc) return rc;
+    s2m_pg_params prm;
+    s2m_pg_default_params(&prm);
+    PgDev db;
+    PgCols c;
+    if ((rc = prepare_block(h, 12, db, c))) return rc;
+    S2M_HIP(h, pg_linearize(h->stream, h->pg.dev, h->pg.dev.X));
+    PgColAt at{}, ka{}, kb{};
+    for (int q = 0; q < 12; q++) { at.v[q] = 6 * keys[q / 6] + q % 6; ka.v[q] = key_a; kb.v[q] = key_b; }
+    double rows[12 * 12];
+    if ((rc = solve_pass(h, db, c, prm, at, ka, kb, rows))) return rc;
+    for (int q = 0; q < 12; q++)
+        for (int b = 0; b < 12; b++) cov[b * 12 + q] = rows[12 * q + b];
     return S2M_OK;
 }
 

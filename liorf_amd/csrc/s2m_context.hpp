@@ -209,6 +209,7 @@ struct __attribute__((visibility("hidden"))) s2m_context {
         size_t n_dev = 0;                          // variables the device arrays hold
         DevBuf est, trial, chain, extra, inc_start, inc, Binv, Aof, rc, Ji, Jj, rx, ferr, fw, vecs, partial, sc, poses;
         DevBuf scan_M[2], scan_Pre[2], scan_loc[2], scan_C0[2];
+        DevBuf blk_vecs, blk_loc[2], blk_partial, blk_sc, blk_rows;   // the block solve's columns (s2m_pg_marginals, s2m_pg_joint_marginal)
         s2m::PgScalars* h_sc = nullptr;            // pinned
         s2m::PgDev dev{};
     } pg;

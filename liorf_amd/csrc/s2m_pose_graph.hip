@@ -532,6 +532,196 @@ __global__ void __launch_bounds__(kPgThreads) k_pg_store_write(const float* stag
     for (int a = 0; a < 12; a++) frames[k].T[a] = q[6 + a];
 }
 
+// ---- the block form: the kernels above for C right-hand sides at once, column c = blockIdx.y (PgCols in the header).  Each
+// body is its single form's with the column's offsets applied, on the same device functions (mat6_vec, mat6_tvec_add,
+// block_partial, partial_sum) and with blockIdx.x / threadIdx.x in the same roles, so a column's sums run in the single
+// form's order; Binv, M, Pre, C0, Ji, Jj are shared by all columns.
+__device__ inline bool col_stopped(const PgScalars* scs) { return scs && scs[blockIdx.y].stop; }
+
+__global__ void __launch_bounds__(64) k_pg_scan_up0_cols(PgScan sc, size_t ls, const double* in, size_t vs, const PgScalars* scs)
+{
+    if (col_stopped(scs)) return;
+    const int g = blockIdx.x * blockDim.x + threadIdx.x;
+    const int n = sc.n[0], e0 = g * kPgGroup;
+    if (e0 >= n) return;
+    const int e1 = min(e0 + kPgGroup, n);
+    in += blockIdx.y * vs;
+    double* loc0 = sc.loc[0] + blockIdx.y * ls;
+    double v[6] = { 0, 0, 0, 0, 0, 0 };
+    for (int e = e0; e < e1; e++) {
+        const double* x = in + 6 * (size_t)(sc.rev ? n - 1 - e : e);
+        const double xin[6] = { x[0], x[1], x[2], x[3], x[4], x[5] };
+        double c[6], o[6];
+        mat6_vec(sc.C0 + 36 * (size_t)e, xin, c);
+        mat6_vec(sc.M[0] + 36 * (size_t)e, v, o);
+        for (int a = 0; a < 6; a++) { v[a] = o[a] + c[a]; loc0[6 * (size_t)e + a] = v[a]; }
+    }
+}
+__global__ void __launch_bounds__(64) k_pg_scan_up_cols(PgScan sc, size_t ls, int lvl, const PgScalars* scs)
+{
+    if (col_stopped(scs)) return;
+    const int g = blockIdx.x * blockDim.x + threadIdx.x;
+    const int n = sc.n[lvl], e0 = g * kPgGroup;
+    if (e0 >= n) return;
+    const int e1 = min(e0 + kPgGroup, n);
+    const double* below = sc.loc[lvl - 1] + blockIdx.y * ls;
+    double* here = sc.loc[lvl] + blockIdx.y * ls;
+    double v[6] = { 0, 0, 0, 0, 0, 0 };
+    for (int e = e0; e < e1; e++) {
+        const int last = min(e * kPgGroup + kPgGroup, sc.n[lvl - 1]) - 1;
+        const double* c = below + 6 * (size_t)last;
+        double o[6];
+        mat6_vec(sc.M[lvl] + 36 * (size_t)e, v, o);
+        for (int a = 0; a < 6; a++) { v[a] = o[a] + c[a]; here[6 * (size_t)e + a] = v[a]; }
+    }
+}
+__global__ void __launch_bounds__(kPgThreads) k_pg_scan_down_cols(PgScan sc, size_t ls, int lvl, double* out, size_t vs, const PgScalars* scs)
+{
+    if (col_stopped(scs)) return;
+    const int e = blockIdx.x * blockDim.x + threadIdx.x;
+    const int n = sc.n[lvl];
+    if (e >= n) return;
+    const int g = e / kPgGroup;
+    double* here = sc.loc[lvl] + blockIdx.y * ls;
+    double v[6];
+    for (int a = 0; a < 6; a++) v[a] = here[6 * (size_t)e + a];
+    if (g > 0) {
+        const double* xin = sc.loc[lvl + 1] + blockIdx.y * ls + 6 * (size_t)(g - 1);
+        const double x6[6] = { xin[0], xin[1], xin[2], xin[3], xin[4], xin[5] };
+        double o[6];
+        mat6_vec(sc.Pre[lvl] + 36 * (size_t)e, x6, o);
+        for (int a = 0; a < 6; a++) v[a] += o[a];
+    }
+    double* dst = lvl == 0 ? out + blockIdx.y * vs + 6 * (size_t)(sc.rev ? n - 1 - e : e) : here + 6 * (size_t)e;
+    for (int a = 0; a < 6; a++) dst[a] = v[a];
+}
+
+__global__ void __launch_bounds__(kPgThreads) k_pg_extra_u_cols(PgDev d, PgCols s, const double* x, const PgScalars* scs)
+{
+    if (col_stopped(scs)) return;
+    const int f = blockIdx.x * blockDim.x + threadIdx.x;
+    if (f >= d.n_extra) return;
+    x += blockIdx.y * s.vec;
+    double* u = d.u + blockIdx.y * s.u;
+    const PgFactor& fac = d.extra[f];
+    double xi[6], o[6], o2[6] = { 0, 0, 0, 0, 0, 0 };
+    for (int a = 0; a < 6; a++) xi[a] = x[6 * (size_t)fac.i + a];
+    mat6_vec(d.Ji + 36 * (size_t)f, xi, o);
+    if (fac.type == kPgBetween) {
+        for (int a = 0; a < 6; a++) xi[a] = x[6 * (size_t)fac.j + a];
+        mat6_vec(d.Jj + 36 * (size_t)f, xi, o2);
+    }
+    for (int a = 0; a < 6; a++) u[6 * (size_t)f + a] = o[a] + o2[a];
+}
+__global__ void __launch_bounds__(kPgThreads) k_pg_extra_gather_cols(PgDev d, PgCols s, const PgScalars* scs)
+{
+    if (col_stopped(scs)) return;
+    const int k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= d.n) return;
+    const double* u = d.u + blockIdx.y * s.u;
+    double* g = d.g + blockIdx.y * s.vec;
+    double acc[6] = { 0, 0, 0, 0, 0, 0 };
+    for (int q = d.inc_start[k]; q < d.inc_start[k + 1]; q++) {
+        const PgIncidence in = d.inc[q];
+        double uf[6];
+        for (int a = 0; a < 6; a++) uf[a] = u[6 * (size_t)in.factor + a];
+        mat6_tvec_add((in.side ? d.Jj : d.Ji) + 36 * (size_t)in.factor, uf, acc);
+    }
+    for (int a = 0; a < 6; a++) g[6 * (size_t)k + a] = acc[a];
+}
+
+__global__ void __launch_bounds__(kPgThreads) k_pg_cg_init_cols(PgDev d, PgCols s)
+{
+    const size_t at = blockIdx.y * s.vec;
+    const double* b = d.b + at;
+    double *y = d.y + at, *r = d.r + at, *p = d.p + at;
+    double a = 0.0;
+    for (int k = blockIdx.x * kPgThreads + threadIdx.x; k < 6 * d.n; k += kPgDotBlocks * kPgThreads) {
+        const double v = b[k];
+        y[k] = 0.0; r[k] = v; p[k] = v;
+        a += v * v;
+    }
+    block_partial(a, d.partial + blockIdx.y * kPgDotBlocks);
+}
+__global__ void k_pg_cg_init2_cols(PgDev d, double tol, int max_iters)
+{
+    PgScalars* sc = d.sc + blockIdx.y;
+    const double bb = partial_sum(d.partial + blockIdx.y * kPgDotBlocks);
+    sc->rr = bb; sc->bb = bb; sc->tol2 = tol * tol;
+    sc->iters = 0; sc->max_iters = max_iters;
+    sc->stop = (bb == 0.0 || max_iters <= 0) ? 1 : 0;
+}
+__global__ void __launch_bounds__(kPgThreads) k_pg_cg_q_cols(PgDev d, PgCols s, int have_t2)
+{
+    if (d.sc[blockIdx.y].stop) return;
+    const size_t at = blockIdx.y * s.vec;
+    const double *pv = d.p + at, *t2 = d.t2 + at;
+    double* qv = d.q + at;
+    double a = 0.0;
+    for (int k = blockIdx.x * kPgThreads + threadIdx.x; k < 6 * d.n; k += kPgDotBlocks * kPgThreads) {
+        const double p = pv[k], q = p + (have_t2 ? t2[k] : 0.0);
+        qv[k] = q;
+        a += p * q;
+    }
+    block_partial(a, d.partial + blockIdx.y * kPgDotBlocks);
+}
+__global__ void k_pg_cg_alpha_cols(PgDev d)
+{
+    PgScalars* sc = d.sc + blockIdx.y;
+    if (sc->stop) return;
+    const double pq = partial_sum(d.partial + blockIdx.y * kPgDotBlocks);
+    sc->pq = pq;
+    sc->alpha = pq > 0.0 ? sc->rr / pq : 0.0;
+}
+__global__ void __launch_bounds__(kPgThreads) k_pg_cg_update_cols(PgDev d, PgCols s)
+{
+    if (d.sc[blockIdx.y].stop) return;
+    const size_t at = blockIdx.y * s.vec;
+    const double *pv = d.p + at, *qv = d.q + at;
+    double *y = d.y + at, *rv = d.r + at;
+    const double alpha = d.sc[blockIdx.y].alpha;
+    double a = 0.0;
+    for (int k = blockIdx.x * kPgThreads + threadIdx.x; k < 6 * d.n; k += kPgDotBlocks * kPgThreads) {
+        y[k] += alpha * pv[k];
+        const double r = rv[k] - alpha * qv[k];
+        rv[k] = r;
+        a += r * r;
+    }
+    block_partial(a, d.partial + blockIdx.y * kPgDotBlocks);
+}
+__global__ void k_pg_cg_beta_cols(PgDev d)
+{
+    PgScalars* sc = d.sc + blockIdx.y;
+    if (sc->stop) return;
+    const double rr = partial_sum(d.partial + blockIdx.y * kPgDotBlocks);
+    sc->beta = sc->rr > 0.0 ? rr / sc->rr : 0.0;
+    sc->rr = rr;
+    sc->iters += 1;
+    if (!(rr > sc->tol2 * sc->bb) || sc->iters >= sc->max_iters || !(sc->pq > 0.0)) sc->stop = 1;
+}
+__global__ void __launch_bounds__(kPgThreads) k_pg_cg_p_cols(PgDev d, PgCols s)
+{
+    if (d.sc[blockIdx.y].stop) return;
+    const int k = blockIdx.x * blockDim.x + threadIdx.x;
+    const size_t at = blockIdx.y * s.vec;
+    if (k < 6 * d.n) d.p[at + k] = d.r[at + k] + d.sc[blockIdx.y].beta * d.p[at + k];
+}
+
+__global__ void __launch_bounds__(kPgThreads) k_pg_unit_cols(PgDev d, PgCols s, PgColAt at)
+{
+    const int k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k < 6 * d.n) d.g[blockIdx.y * s.vec + k] = k == at.v[blockIdx.y] ? 1.0 : 0.0;
+}
+// the wanted rows of every column's delta, so that one copy brings a pass's result to the host
+__global__ void __launch_bounds__(64) k_pg_rows_cols(PgDev d, PgCols s, PgColAt ka, PgColAt kb, double* rows)
+{
+    const int t = threadIdx.x;
+    if (t >= 12) return;
+    const int key = t < 6 ? ka.v[blockIdx.y] : kb.v[blockIdx.y];
+    const bool in = key >= 0 && key < d.n;
+    rows[12 * (size_t)blockIdx.y + t] = in ? d.delta[blockIdx.y * s.vec + 6 * (size_t)key + t % 6] : 0.0;
+}
+
 inline int blocks_for(int n) { return (n + kPgThreads - 1) / kPgThreads; }
 
 // out = scan applied to in (both in key order)
@@ -561,7 +751,72 @@ void kt_apply(hipStream_t s, const PgDev& d, const int32_t* stop)
     scan_solve(s, d.bwd, d.g, d.t2, stop);
 }
 
+// the block form of scan_solve: every launch serves all columns (grid row = column)
+void scan_solve_cols(hipStream_t s, const PgScan& sc, size_t ls, const double* in, double* out, const PgCols& c, const PgScalars* scs)
+{
+    const unsigned C = (unsigned)c.cols;
+    for (int l = 0; l < sc.levels; l++) {
+        const int groups = (sc.n[l] + kPgGroup - 1) / kPgGroup;
+        if (l == 0) k_pg_scan_up0_cols<<<dim3((groups + 63) / 64, C), 64, 0, s>>>(sc, ls, in, c.vec, scs);
+        else k_pg_scan_up_cols<<<dim3((groups + 63) / 64, C), 64, 0, s>>>(sc, ls, l, scs);
+    }
+    for (int l = sc.levels - 2; l >= 1; l--) k_pg_scan_down_cols<<<dim3(blocks_for(sc.n[l]), C), kPgThreads, 0, s>>>(sc, ls, l, out, c.vec, scs);
+    k_pg_scan_down_cols<<<dim3(blocks_for(sc.n[0]), C), kPgThreads, 0, s>>>(sc, ls, 0, out, c.vec, scs);
+}
+
+bool cols_ok(const PgDev& d, const PgCols& c) { return d.n > 0 && c.cols >= 1 && c.cols <= kPgBlockCols; }
+
 }  // namespace
+
+hipError_t pg_bwd_unit_cols(hipStream_t s, const PgDev& d, const PgCols& c, const PgColAt& at)
+{
+    if (!cols_ok(d, c)) return hipErrorInvalidValue;
+    k_pg_unit_cols<<<dim3(blocks_for(6 * d.n), c.cols), kPgThreads, 0, s>>>(d, c, at);
+    scan_solve_cols(s, d.bwd, c.loc_b, d.g, d.b, c, nullptr);
+    return hipGetLastError();
+}
+
+hipError_t pg_cg_begin_cols(hipStream_t s, const PgDev& d, const PgCols& c, double tol, int max_iters)
+{
+    if (!cols_ok(d, c)) return hipErrorInvalidValue;
+    k_pg_cg_init_cols<<<dim3(kPgDotBlocks, c.cols), kPgThreads, 0, s>>>(d, c);
+    k_pg_cg_init2_cols<<<dim3(1, c.cols), 1, 0, s>>>(d, tol, max_iters);
+    return hipGetLastError();
+}
+
+hipError_t pg_cg_iterations_cols(hipStream_t s, const PgDev& d, const PgCols& c, int count)
+{
+    if (!cols_ok(d, c)) return hipErrorInvalidValue;
+    const unsigned C = (unsigned)c.cols;
+    for (int it = 0; it < count; it++) {
+        if (d.n_extra > 0) {
+            scan_solve_cols(s, d.fwd, c.loc_f, d.p, d.t1, c, d.sc);
+            k_pg_extra_u_cols<<<dim3(blocks_for(d.n_extra), C), kPgThreads, 0, s>>>(d, c, d.t1, d.sc);
+            k_pg_extra_gather_cols<<<dim3(blocks_for(d.n), C), kPgThreads, 0, s>>>(d, c, d.sc);
+            scan_solve_cols(s, d.bwd, c.loc_b, d.g, d.t2, c, d.sc);
+        }
+        k_pg_cg_q_cols<<<dim3(kPgDotBlocks, C), kPgThreads, 0, s>>>(d, c, d.n_extra > 0);
+        k_pg_cg_alpha_cols<<<dim3(1, C), 1, 0, s>>>(d);
+        k_pg_cg_update_cols<<<dim3(kPgDotBlocks, C), kPgThreads, 0, s>>>(d, c);
+        k_pg_cg_beta_cols<<<dim3(1, C), 1, 0, s>>>(d);
+        k_pg_cg_p_cols<<<dim3(blocks_for(6 * d.n), C), kPgThreads, 0, s>>>(d, c);
+    }
+    return hipGetLastError();
+}
+
+hipError_t pg_fwd_y_cols(hipStream_t s, const PgDev& d, const PgCols& c)
+{
+    if (!cols_ok(d, c)) return hipErrorInvalidValue;
+    scan_solve_cols(s, d.fwd, c.loc_f, d.y, d.delta, c, nullptr);
+    return hipGetLastError();
+}
+
+hipError_t pg_rows_cols(hipStream_t s, const PgDev& d, const PgCols& c, const PgColAt& ka, const PgColAt& kb, double* rows)
+{
+    if (!cols_ok(d, c)) return hipErrorInvalidValue;
+    k_pg_rows_cols<<<dim3(1, c.cols), 64, 0, s>>>(d, c, ka, kb, rows);
+    return hipGetLastError();
+}
 
 hipError_t pg_linearize(hipStream_t s, const PgDev& d, const double* X)
 {

@@ -14,6 +14,7 @@ constexpr int kPgGroup = 32;          // elements per group of the blocked scan
 constexpr int kPgMaxLevels = 6;       // 32^6 keys
 constexpr int kPgDotBlocks = 64;      // workgroups of a dot product's first stage (fixed, so sums are reproducible)
 constexpr int kPgThreads = 256;
+constexpr int kPgBlockCols = 24;      // right-hand sides one pass of the block solve advances in lockstep (a joint marginal: 12)
 
 enum { kPgPrior = 0, kPgBetween = 1, kPgGps = 2 };
 
@@ -65,6 +66,25 @@ hipError_t pg_cg_iterations(hipStream_t s, const PgDev& d, int count);          
 hipError_t pg_step(hipStream_t s, const PgDev& d);                                // delta = J_c^-1 y, Xtrial = X (+) delta
 hipError_t pg_bwd_unit(hipStream_t s, const PgDev& d, int key, int axis);         // b = J_c^-T e_(6 key + axis)
 hipError_t pg_fwd_y(hipStream_t s, const PgDev& d);                               // delta = J_c^-1 y
+
+// ---- the block form of the linear solve: C <= kPgBlockCols right-hand sides advance in lockstep through shared launches,
+// column c = grid row c (blockIdx.y).  `d` is a copy of the graph's PgDev whose vectors b .. delta, u, partial, sc and the
+// scans' loc[] point at column 0 of block storage; column c lies `vec` (`u`, `loc_f`, `loc_b`) doubles further on, its
+// kPgDotBlocks partials at partial + c kPgDotBlocks, its scalars at sc + c.  Every column runs the single form's per-column
+// code with the single form's assignment of elements to lanes and workgroups, and stops by its own flag, so column c is
+// bit for bit the single solve of the same right-hand side.
+struct PgCols {
+    int32_t cols, pad;
+    size_t vec, u, loc_f, loc_b;
+};
+struct PgColAt { int32_t v[kPgBlockCols]; };
+hipError_t pg_bwd_unit_cols(hipStream_t s, const PgDev& d, const PgCols& c, const PgColAt& at);   // b_c = J_c^-T e_(at[c])
+hipError_t pg_cg_begin_cols(hipStream_t s, const PgDev& d, const PgCols& c, double tol, int max_iters);
+hipError_t pg_cg_iterations_cols(hipStream_t s, const PgDev& d, const PgCols& c, int count);      // a stopped column is not touched
+hipError_t pg_fwd_y_cols(hipStream_t s, const PgDev& d, const PgCols& c);                         // delta_c = J_c^-1 y_c
+// rows[12 c + 0..5] = delta_c of key ka[c], rows[12 c + 6..11] = delta_c of key kb[c] (zeros where kb[c] < 0)
+hipError_t pg_rows_cols(hipStream_t s, const PgDev& d, const PgCols& c, const PgColAt& ka, const PgColAt& kb, double* rows);
+
 hipError_t pg_poses(hipStream_t s, const double* X, int first, int count, float* xyzrpy, float4* pos);   // pos: may be null
 // correctPoses() in two launches: 18 floats per key (pose vector, 3x4 transform) and a not-finite flag into `stage`, then - once
 // the host has seen the flag - positions and cached transforms into the key-frame store

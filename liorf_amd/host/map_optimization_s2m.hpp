@@ -243,6 +243,21 @@ public:
         saveKeyFrame();
     }
 
+    // poseCovariance (:1565) for several keys in one block solve (s2m_pg_marginals): 36 doubles per key, row-major 6x6 in the
+    // tangent order of rotation then translation; and the joint covariance of two keys (s2m_pg_joint_marginal), row-major 12x12
+    std::vector<double> poseCovariances(const std::vector<int32_t>& keys)
+    {
+        std::vector<double> cov(36 * keys.size());
+        check(s2m_pg_marginals(h_, keys.data(), (int32_t)keys.size(), cov.data()), "s2m_pg_marginals");
+        return cov;
+    }
+    std::vector<double> jointPoseCovariance(int32_t key_a, int32_t key_b)
+    {
+        std::vector<double> cov(144);
+        check(s2m_pg_joint_marginal(h_, key_a, key_b, cov.data()), "s2m_pg_joint_marginal");
+        return cov;
+    }
+
     // correctPoses() (:1611-1642) from the pose graph: the store is corrected in place on the device, cloudKeyPoses6D follows
     bool correctPosesFromGraph()
     {

@@ -358,7 +358,9 @@ static int run_many(int argc, char** argv)
 // --pose-graph keys.bin keys.txt scan_leaf loops.txt out.bin: keys.txt as for --loop (the pose is the front end's); loops.txt holds
 // one line "at key_cur key_pre x y z roll pitch yaw variance robust_k" per closure, queued before key `at` is processed. Prints
 // "key <i> iterations inner converged factors error pose(6) corrected" per key, then "kp <i> pose(6)" per key (the graph's
-// estimates) and "map_cloud <n>".
+// estimates) and "map_cloud <n>".  The last key's covariance goes to the standard error stream, so that the standard output stays
+// the record the Python mirror is compared with: "marginal_old 36 values" from s2m_pg_marginal, "marginal_new 36 values" from
+// poseCovariances() (%.17g: equal lines are equal bits).
 static int run_pose_graph(char** argv)
 {
     liorf_amd::MapOptimizationS2M node;
@@ -405,6 +407,16 @@ static int run_pose_graph(char** argv)
     std::vector<liorf_amd::PointXYZI> cloud;
     node.globalMapCloud(cloud, 0.0f);
     std::printf("map_cloud %zu\n", cloud.size());
+    if (N > 0) {
+        double old_cov[36];
+        if (s2m_pg_marginal(node.handle(), (int32_t)N - 1, old_cov) != S2M_OK) throw std::runtime_error("s2m_pg_marginal");
+        const std::vector<double> new_cov = node.poseCovariances({ (int32_t)N - 1 });
+        for (int which = 0; which < 2; which++) {
+            std::fprintf(stderr, which ? "marginal_new" : "marginal_old");
+            for (int k = 0; k < 36; k++) std::fprintf(stderr, " %.17g", which ? new_cov[(size_t)k] : old_cov[k]);
+            std::fprintf(stderr, "\n");
+        }
+    }
     std::ofstream out(argv[6], std::ios::binary);
     out.write(reinterpret_cast<const char*>(cloud.data()), (std::streamsize)(cloud.size() * sizeof(liorf_amd::PointXYZI)));
     return 0;

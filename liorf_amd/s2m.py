@@ -45,6 +45,7 @@ ABI_SYMBOLS = [
     "s2m_odom_deskew_info", "s2m_project_check_args_motion", "s2m_project_scan_motion", "s2m_guess_state_init", "s2m_update_initial_guess",
     "s2m_pg_default_params", "s2m_pg_check_args", "s2m_pg_reset", "s2m_pg_size", "s2m_pg_add_prior", "s2m_pg_add_between", "s2m_pg_add_gps",
     "s2m_pg_set_initial", "s2m_pg_add_odometry", "s2m_pg_optimize", "s2m_pg_get_poses", "s2m_pg_marginal", "s2m_pg_apply_to_store",
+    "s2m_pg_marginals_check_args", "s2m_pg_marginals", "s2m_pg_joint_marginal",
 ]
 S2M_RING_U8, S2M_RING_U16, S2M_RING_I32 = 0, 1, 2
 S2M_TIME_F32, S2M_TIME_U32_NS, S2M_TIME_U32, S2M_TIME_F64_REL = 0, 1, 2, 3
@@ -54,6 +55,8 @@ S2M_KF_FROM_HOST, S2M_KF_FROM_DEVICE, S2M_KF_FROM_LAST_DOWNSAMPLE = 0, 1, 2
 S2M_LOOP_NONE, S2M_LOOP_ALREADY_CLOSED, S2M_LOOP_TOO_FEW_POINTS, S2M_LOOP_REJECTED, S2M_LOOP_ACCEPTED = 0, 1, 2, 3, 4
 S2M_WARN_LEAF_TOO_SMALL = 1
 S2M_PG_PRIOR, S2M_PG_BETWEEN, S2M_PG_GPS, S2M_PG_INITIAL = 0, 1, 2, 3
+S2M_PG_BLOCK_COLUMNS = 24                                # right-hand sides per pass of the block solve
+PG_MARGINALS_KEYS_PER_PASS = S2M_PG_BLOCK_COLUMNS // 6   # keys one pass of s2m_pg_marginals serves
 
 
 class Params(C.Structure):
@@ -305,6 +308,9 @@ def load_library(path: str | None = None) -> C.CDLL:
     L.s2m_pg_get_poses.argtypes = [vp, C.c_int32, C.c_int32, fp]
     L.s2m_pg_marginal.argtypes = [vp, C.c_int32, dp]
     L.s2m_pg_apply_to_store.argtypes = [vp, C.c_int32, C.c_int32]
+    L.s2m_pg_marginals_check_args.argtypes = [C.c_int32, i32p, C.c_int32]
+    L.s2m_pg_marginals.argtypes = [vp, i32p, C.c_int32, dp]
+    L.s2m_pg_joint_marginal.argtypes = [vp, C.c_int32, C.c_int32, dp]
     L.s2m_update_initial_guess.argtypes = [C.POINTER(GuessState), C.POINTER(C.c_float), C.c_int, C.POINTER(GuessInfo), C.c_int, C.c_int,
                                            C.POINTER(C.c_float)]
     if path is None:
@@ -911,6 +917,19 @@ class MapOptimizationS2M:
         self._check(self.lib.s2m_pg_marginal(self.h, key, _dp(cov)), "s2m_pg_marginal")
         return cov
 
+    def pgMarginals(self, keys) -> np.ndarray:
+        """The marginals of `keys` (they may repeat) in one block solve: (len(keys), 6, 6), block k bitwise pgMarginal(keys[k])."""
+        k = np.ascontiguousarray(keys, np.int32).reshape(-1)
+        cov = np.zeros((k.shape[0], 6, 6), np.float64)
+        self._check(self.lib.s2m_pg_marginals(self.h, k.ctypes.data_as(C.POINTER(C.c_int32)), k.shape[0], _dp(cov)), "s2m_pg_marginals")
+        return cov
+
+    def pgJointMarginal(self, key_a: int, key_b: int) -> np.ndarray:
+        """The joint covariance of two keys, 12x12 over [key_a's tangent, key_b's tangent], not symmetrised."""
+        cov = np.zeros((12, 12), np.float64)
+        self._check(self.lib.s2m_pg_joint_marginal(self.h, key_a, key_b, _dp(cov)), "s2m_pg_joint_marginal")
+        return cov
+
     def pgApplyToStore(self, first: int = 0, count: int | None = None):
         if count is None:
             count = self.pgSize()[0] - first
@@ -1064,6 +1083,14 @@ def pg_check_args(kind: int, n_variables: int, key_a: int, key_b: int, values, v
     w = None if var is None else np.ascontiguousarray(var, np.float64)
     return load_library().s2m_pg_check_args(kind, n_variables, key_a, key_b, None if v is None else _fp(v),
                                             None if w is None else _dp(w), float(robust_k))
+
+
+def pg_marginals_check_args(n_variables: int, keys, n_keys: int | None = None) -> int:
+    """s2m_pg_marginals_check_args (host only, no GPU): the status code.  keys=None passes a null pointer."""
+    k = None if keys is None else np.ascontiguousarray(keys, np.int32).reshape(-1)
+    if n_keys is None:
+        n_keys = 0 if k is None else k.shape[0]
+    return load_library().s2m_pg_marginals_check_args(n_variables, None if k is None else k.ctypes.data_as(C.POINTER(C.c_int32)), n_keys)
 
 
 def default_kf_params(**kw) -> KfParams:

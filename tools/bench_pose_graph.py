@@ -9,6 +9,15 @@ apply_to_store_ms is s2m_pg_apply_to_store over the whole store (10-point frames
 s2m_pg_get_poses to the caller and s2m_kf_set_poses back.
 
   python tools/bench_pose_graph.py [--sizes 2000,10000,50000] [--out profiles/pose_graph_bench_line.json]
+
+--marginals times the covariance read-out instead, on the same graphs after their optimise (median of --reps runs after a
+warm-up of each call, the calls alternating inside every repetition):
+  marginal_single_ms    s2m_pg_marginal(last key): six CG solves one after the other, the path before the block solve
+  marginals_{1,2,8}_ms  s2m_pg_marginals for the last 1, 2 and 8 distinct keys (6, 12 and 48 right-hand sides in lockstep)
+  joint_marginal_ms     s2m_pg_joint_marginal(n // 2, last)
+with marginals_1_over_single (the ratio of the first two) and eight_times_marginals_1_ms beside marginals_8_ms.
+
+  python tools/bench_pose_graph.py --marginals --sizes 2000,10000 --reps 7 --out profiles/pose_graph_marginals_bench_line.json
 """
 import argparse
 import json
@@ -80,12 +89,54 @@ def one_size(n, reps):
     return out
 
 
+def marginals_one_size(n, reps):
+    g = P.figure_eight(n, 40)
+    m = s2m.MapOptimizationS2M()
+    try:
+        CS.load_into(m, g)
+        res = m.pgOptimize()
+        last = n - 1
+        spread = [last - k * (n // 9) for k in range(8)]            # eight distinct keys over the trajectory, the last one first
+        calls = [("marginal_single_ms", lambda: m.pgMarginal(last)), ("marginals_1_ms", lambda: m.pgMarginals(spread[:1])),
+                 ("marginals_2_ms", lambda: m.pgMarginals(spread[:2])), ("marginals_8_ms", lambda: m.pgMarginals(spread)),
+                 ("joint_marginal_ms", lambda: m.pgJointMarginal(n // 2, last))]
+        same = bool(np.array_equal(m.pgMarginal(last), m.pgMarginals([last])[0]))
+        t = {name: [] for name, _ in calls}
+        for rep in range(reps + 1):                                # the first round is the warm-up
+            for name, fn in calls:
+                t0 = time.perf_counter()
+                fn()                                               # (every call ends in a stream synchronise)
+                if rep > 0:
+                    t[name].append(time.perf_counter() - t0)
+        out = {name: round(1e3 * float(np.median(v)), 3) for name, v in t.items()}
+        out.update({name.replace("_ms", "_min_ms"): round(1e3 * float(np.min(v)), 3) for name, v in t.items()})
+        out.update(keys=n, n_factors=res.n_factors, optimize_inner_iterations=res.inner_iterations, reps=reps, block_columns=s2m.S2M_PG_BLOCK_COLUMNS,
+                   single_block_bitwise_equal=same,
+                   marginals_1_over_single=round(out["marginals_1_ms"] / out["marginal_single_ms"], 4),
+                   eight_times_marginals_1_ms=round(8 * out["marginals_1_ms"], 3))
+        return out
+    finally:
+        m.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--sizes", default="2000,10000,50000")
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--marginals", action="store_true", help="time the covariance read-out instead of the optimise")
     a = ap.parse_args()
+    if a.marginals:
+        line = {"workload": "figure-of-eight driven twice, 40 loops, optimised; marginal covariances at the estimates (seed %d)" % P.SEED, "sizes": {}}
+        for n in [int(x) for x in a.sizes.split(",")]:
+            line["sizes"][str(n)] = marginals_one_size(n, a.reps)
+            print(n, json.dumps(line["sizes"][str(n)]), file=sys.stderr, flush=True)
+        txt = json.dumps(line)
+        print(txt)
+        if a.out:
+            with open(a.out, "w") as f:
+                f.write(txt + "\n")
+        return
     line = {"workload": "figure-of-eight driven twice, 40 loops, one optimise after one added loop (seed %d)" % P.SEED, "sizes": {}}
     for n in [int(x) for x in a.sizes.split(",")]:
         line["sizes"][str(n)] = one_size(n, a.reps)
