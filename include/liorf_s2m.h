@@ -200,8 +200,13 @@ int  s2m_surf_optimization(s2m_handle h, const float pose[6],
 /* matAtA / matAtB / laserCloudSelNum of one iteration at `pose` (:1182-1239). */
 int  s2m_normal_eq(s2m_handle h, const float pose[6], float AtA[36], float AtB[6],
                    int32_t* n_sel);
-/* Raw device time (ms) of the last s2m_optimize* call, measured with HIP events
- * on the handle's stream; and of the last s2m_set_map / s2m_set_scan index build. */
+/* Raw device time (ms) of the last s2m_optimize* call and of the last s2m_set_map / s2m_set_scan index build.
+ * For a single scan both intervals come from the device's constant-frequency wall clock, stamped by the kernels
+ * that bracket them: set_scan_ms runs from the start of the first ordering kernel to the end of the last,
+ * optimize_ms from the end of the state upload of s2m_optimize_launch to the end of the last close of the loop
+ * (no longer from event to event: the idle time around an event record is not part of it, and no event record
+ * costs GPU time in a step).  A batch and s2m_set_map are timed with HIP events on the handle's stream.
+ * Synchronises the handle's stream when a scan preparation is still to be timed. */
 int  s2m_last_timing(s2m_handle h, float* optimize_ms, float* set_map_ms, float* set_scan_ms);
 /* Diagnostic and benchmark entry points (per-launch timing, per-wave profiles, the device's trig arithmetic, experiment
  * switches read from the environment) are declared in liorf_s2m_debug.h: they are exported by the same library but are not part

@@ -32,6 +32,14 @@ namespace {
 inline uint32_t host_f2ord(float f) { uint32_t u; memcpy(&u, &f, 4); return (u & 0x80000000u) ? ~u : (u | 0x80000000u); }
 inline float host_ord2f(uint32_t o) { uint32_t u = (o & 0x80000000u) ? (o & 0x7fffffffu) : ~o; float f; memcpy(&f, &u, 4); return f; }
 
+// milliseconds between two device stamps of the pinned block (valid once the stream has been synchronised behind the kernels
+// that wrote them)
+inline float stamps_ms(const s2m_context* h, int from, int to)
+{
+    const unsigned long long a = h->reg.h_stamps[from], b = h->reg.h_stamps[to];
+    return (b > a && h->reg.wall_clock_khz > 0) ? (float)((double)(b - a) / (double)h->reg.wall_clock_khz) : 0.0f;
+}
+
 // the partial rows of a launch (two slots, by launch parity) and, behind them, the search kernel's worklist
 int ensure_rows(s2m_context* h, int nblocks)
 {
@@ -270,6 +278,7 @@ int scan_slot_prepare(s2m_context* h, const void* pts, size_t n, size_t stride, 
     ps->qx = h->reg.qx.as<float>(); ps->qy = h->reg.qy.as<float>(); ps->qz = h->reg.qz.as<float>(); ps->qperm = h->reg.qperm.as<int32_t>();
     ps->cert = h->reg.cert.as<float4>(); ps->aux = h->reg.aux.as<int4>();
     ps->chunk_parts = h->reg.chunk_parts.as<int32_t>(); ps->wave_table = h->reg.wave_table.as<int2>(); ps->n_waves = h->reg.n_waves.as<int32_t>();
+    ps->stamps = nullptr;                                 // (set_scan_impl: a single scan times its preparation)
 
     h->hctx.qx = h->reg.qx.as<float>(); h->hctx.qy = h->reg.qy.as<float>(); h->hctx.qz = h->reg.qz.as<float>();
     h->hctx.qperm = h->reg.qperm.as<int32_t>();
@@ -315,14 +324,15 @@ void launch_scan_prep(hipStream_t stream, const PrepTable& t, int nslots)
 int s2m::host::set_scan_impl(s2m_context* h, const void* pts, size_t n, size_t stride, bool on_device)
 {
     S2M_HIP(h, hipSetDevice(h->device));
-    S2M_HIP(h, hipEventRecord(h->reg.ev_c, h->stream));
     PrepTable t;
     int rc = scan_slot_prepare(h, pts, n, stride, on_device, &t.s[0]);
     if (rc) return rc;
     if (n == 0) { h->reg.t_set_scan_ms = 0; h->reg.scan_timing_pending = false; return upload_ctx(h); }
+    // the first and the last ordering kernel stamp the device's wall clock into the pinned block (s2m_last_timing): an event
+    // record on either side is a packet of its own in the queue, 5.7 us of idle GPU each
+    t.s[0].stamps = h->reg.h_stamps + kStampPrep0;
     launch_scan_prep(h->stream, t, 1);
     S2M_HIP(h, hipGetLastError());
-    S2M_HIP(h, hipEventRecord(h->reg.ev_d, h->stream));
     h->reg.scan_timing_pending = true;
     // (the DevCtx block goes to the device with the next launch that needs it: upload_ctx / push_state)
     // A host source (pageable or pinned) has been copied by the time this returns; the ordering kernels behind the copy
@@ -344,17 +354,18 @@ void fill_state(s2m_context* h, DevState* s, const float pose[6])
     s->isDegenerate = h->reg.persist_degenerate;
 }
 
-int push_state(s2m_context* h, const float pose[6])
+// `stamp` (pinned, may be null): where the kernel leaves the wall clock once the state is stored
+int push_state(s2m_context* h, const float pose[6], unsigned long long* stamp = nullptr)
 {
     DevState s;
     fill_state(h, &s, pose);
     if (h->ctx_dirty) {
         hipLaunchKernelGGL(k_set_ctx_state, dim3(1), dim3(64), 0, h->stream, h->reg.dctx.as<DevCtx>(), h->hctx, h->reg.state.as<DevState>(), s,
-                           (const int32_t*)h->reg.n_waves.as<int32_t>());
+                           (const int32_t*)h->reg.n_waves.as<int32_t>(), stamp);
         h->ctx_dirty = false;
     } else
         hipLaunchKernelGGL(k_set_state, dim3(1), dim3(64), 0, h->stream, h->reg.state.as<DevState>(), s,
-                           (const int32_t*)h->reg.n_waves.as<int32_t>());
+                           (const int32_t*)h->reg.n_waves.as<int32_t>(), stamp);
     S2M_HIP(h, hipGetLastError());
     return S2M_OK;
 }
@@ -383,6 +394,10 @@ struct LoopShape {
     bool split = false;     // C + S per iteration instead of R
     bool late = false;      // the split iterations of this loop come late (few rows on the worklist): small search grid
     bool split_auto = false; // split if the loop's iterations are closed by k_finalize and the lean certify kernel applies
+    // a captured single-scan loop: the k_finalize that ends the range copies state + trace to `out` (the pinned mirror) and
+    // stamps the wall clock at `stamp`; both null: the caller copies (plain launches, batches, diagnostics)
+    DevState* out = nullptr;
+    unsigned long long* stamp = nullptr;
 };
 
 LoopShape shape_of(s2m_context* h)
@@ -452,9 +467,11 @@ inline void launch_iteration(s2m_context* h, const LoopShape& sh, int L, int sol
     launch_search(h, sh, L, false, sh.late);
 }
 
-inline void launch_finalize(s2m_context* h, const LoopShape& sh, int L, int mode)
+// ends_range: the last launch of the range (it hands the record over, see LoopShape::out)
+inline void launch_finalize(s2m_context* h, const LoopShape& sh, int L, int mode, bool ends_range = false)
 {
-    hipLaunchKernelGGL(k_finalize, dim3(1, sh.nslots), dim3(kFinThreads), 0, h->stream, sh.tbl, L, mode);
+    hipLaunchKernelGGL(k_finalize, dim3(1, sh.nslots), dim3(kFinThreads), 0, h->stream, sh.tbl, L, mode,
+                       ends_range ? sh.out : (DevState*)nullptr, ends_range ? sh.stamp : (unsigned long long*)nullptr);
 }
 
 inline void launch_density(s2m_context* h, const LoopShape& sh)
@@ -489,7 +506,7 @@ void enqueue_loop(s2m_context* h, const LoopShape& sh_in, hipEvent_t* events, bo
         sh.late = !sh_in.split && sh.split;
         launch_iteration(h, sh, L, (fuse && L >= 2 && L != L0) ? 1 : 0, fuse);
         if (close) (void)hipEventRecord(events[slot + 1], h->stream);
-        if ((!fuse || L == 0 || L == L1 - 1) && !(sh.late && h->tune.close_in_search)) launch_finalize(h, sh, L, 0);   // (late split: the search launch closes)
+        if ((!fuse || L == 0 || L == L1 - 1) && !(sh.late && h->tune.close_in_search)) launch_finalize(h, sh, L, 0, L == L1 - 1);   // (late split: the search launch closes)
     }
 }
 
@@ -497,7 +514,13 @@ void enqueue_loop(s2m_context* h, const LoopShape& sh_in, hipEvent_t* events, bo
 int get_graph(s2m_context* h, int nblocks, int part, hipGraphExec_t* out)
 {
     // table_cap fixes both grids in the captured loop: k_register's (nblocks) and k_wave_density's
-    const LoopShape sh = shape_of(h);
+    LoopShape sh = shape_of(h);
+    // Loop state + trace come back from inside the graph, into the pinned mirror (its address never changes).  The last launch
+    // of a single scan's range is always a k_finalize (only the late split of a lockstep batch closes in the search kernel):
+    // it writes the record there itself.  (A copy node as the graph's last: 4.4 us and a boundary; a copy issued behind the
+    // graph starts ~10 us after the graph's last kernel.)  The first range - the whole loop, mostly - also stamps its end.
+    sh.out = &h->reg.h_state[1];
+    sh.stamp = part == 2 ? nullptr : h->reg.h_stamps + kStampLoop1;
     const long long key = (((long long)h->hctx.table_cap * 4 + part) * 256 + (part ? h->tune.seg_iters : 0)) * 4 + (sh.split ? 1 : 0) + (sh.wpb == kBigWaves ? 2 : 0);
     auto it = h->reg.graphs.find(key);
     if (it != h->reg.graphs.end()) { *out = it->second; return S2M_OK; }
@@ -505,9 +528,6 @@ int get_graph(s2m_context* h, int nblocks, int part, hipGraphExec_t* out)
     hipGraphExec_t exec = nullptr;
     S2M_HIP(h, hipStreamBeginCapture(h->stream, hipStreamCaptureModeThreadLocal));
     enqueue_loop(h, sh, nullptr, false, part == 2 ? h->tune.seg_iters : 0, part == 1 ? h->tune.seg_iters : -1);
-    // loop state + trace come back as the last node of the graph (into the pinned mirror: its address never changes): a copy
-    // issued behind the graph starts ~10 us after the graph's last kernel
-    (void)hipMemcpyAsync(&h->reg.h_state[1], h->reg.state.p, sizeof(DevState) + sizeof(s2m_iter_trace) * h->prm.max_iter, hipMemcpyDeviceToHost, h->stream);
     hipError_t e = hipStreamEndCapture(h->stream, &graph);
     if (e != hipSuccess || !graph) return fail(h, S2M_ERR_HIP, "hipStreamEndCapture", e);
     e = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
@@ -521,23 +541,26 @@ int get_graph(s2m_context* h, int nblocks, int part, hipGraphExec_t* out)
 int launch_loop(s2m_context* h, int part = 0)
 {
     const int nblocks = h->hctx.nblocks;
-    hipEvent_t e0 = part == 2 ? h->reg.ev_a2 : h->reg.ev_a, e1 = part == 2 ? h->reg.ev_b2 : h->reg.ev_b;
+    // The first range is timed by device stamps: its start by the state upload before it (s2m_optimize_launch), its end by the
+    // k_finalize that closes it.  The second range, issued only for a scan that did not converge in the first, keeps an event pair.
     if (h->tune.use_graph) {
         hipGraphExec_t exec = nullptr;
         int rc = get_graph(h, nblocks, part, &exec);
         if (rc == S2M_OK) {
-            S2M_HIP(h, hipEventRecord(e0, h->stream));
+            if (part == 2) S2M_HIP(h, hipEventRecord(h->reg.ev_a2, h->stream));
             S2M_HIP(h, hipGraphLaunch(exec, h->stream));
-            S2M_HIP(h, hipEventRecord(e1, h->stream));
+            if (part == 2) S2M_HIP(h, hipEventRecord(h->reg.ev_b2, h->stream));
             h->hctx.density_pending = 0;                  // cleared on the device by k_chunk_table_density: keep the host copy in step
             return S2M_OK;
         }
         h->tune.use_graph = false;       // capture unsupported here: fall back to plain launches
     }
-    S2M_HIP(h, hipEventRecord(e0, h->stream));
-    enqueue_loop(h, shape_of(h), nullptr, false, part == 2 ? h->tune.seg_iters : 0, part == 1 ? h->tune.seg_iters : -1);
+    LoopShape sh = shape_of(h);
+    sh.stamp = part == 2 ? nullptr : h->reg.h_stamps + kStampLoop1;
+    if (part == 2) S2M_HIP(h, hipEventRecord(h->reg.ev_a2, h->stream));
+    enqueue_loop(h, sh, nullptr, false, part == 2 ? h->tune.seg_iters : 0, part == 1 ? h->tune.seg_iters : -1);
     S2M_HIP(h, hipGetLastError());
-    S2M_HIP(h, hipEventRecord(e1, h->stream));
+    if (part == 2) S2M_HIP(h, hipEventRecord(h->reg.ev_b2, h->stream));
     S2M_HIP(h, hipMemcpyAsync(&h->reg.h_state[1], h->reg.state.p, sizeof(DevState) + sizeof(s2m_iter_trace) * h->prm.max_iter, hipMemcpyDeviceToHost, h->stream));
     h->hctx.density_pending = 0;
     return S2M_OK;
@@ -684,6 +707,13 @@ int s2m_create(const s2m_params* p, s2m_handle* out)
     if (hipHostMalloc((void**)&h->reg.h_state, sizeof(DevState) * 2 + sizeof(s2m_iter_trace) * kMaxIter) != hipSuccess) return bail(S2M_ERR_HIP);
     h->reg.h_trace = reinterpret_cast<s2m_iter_trace*>(h->reg.h_state + 2);
     if (hipHostMalloc((void**)&h->reg.h_mm, 64) != hipSuccess) return bail(S2M_ERR_HIP);
+    if (hipHostMalloc((void**)&h->reg.h_stamps, sizeof(unsigned long long) * kStampCount) != hipSuccess) return bail(S2M_ERR_HIP);
+    memset(h->reg.h_stamps, 0, sizeof(unsigned long long) * kStampCount);
+    {   // the constant-frequency counter behind wall_clock64(); a runtime that does not tell its rate leaves the timings at zero
+        int khz = 0;
+        if (hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, prm.device_id) != hipSuccess || khz <= 0) { khz = 0; (void)hipGetLastError(); }
+        h->reg.wall_clock_khz = khz;
+    }
     if (hipHostMalloc((void**)&h->sc.h_stage, sizeof(double) * 1220) != hipSuccess) return bail(S2M_ERR_HIP);
     if (ensure(h, h->reg.state, sizeof(DevState) + sizeof(s2m_iter_trace) * kMaxIter) ||      // loop state, then the trace
         ensure(h, h->reg.dctx, sizeof(DevCtx)) || ensure(h, h->reg.mm, 64 + sizeof(uint32_t) * 8 * 1024) ||
@@ -733,7 +763,7 @@ int s2m_destroy(s2m_handle h)
     if (h->own_stream && h->stream) (void)hipStreamDestroy(h->stream);
     vox_destroy(h->voxel.ws);
     icp_destroy(h->loop.icp);
-    for (void* p : { (void*)h->batch.h_kid_states, (void*)h->reg.h_state, (void*)h->reg.h_mm, (void*)h->sc.h_stage, (void*)h->proj.h_count,
+    for (void* p : { (void*)h->batch.h_kid_states, (void*)h->reg.h_state, (void*)h->reg.h_mm, (void*)h->reg.h_stamps, (void*)h->sc.h_stage, (void*)h->proj.h_count,
                      (void*)h->pg.h_sc })
         if (p) (void)hipHostFree(p);
     delete h;                                              // every DevBuf and the key-frame arena go with their owners
@@ -791,7 +821,7 @@ int s2m_optimize_launch(s2m_handle h, const float pose[6])
     if (h->reg.n_m == 0) { h->reg.pending_skipped = 1; return S2M_OK; }                    // :1297
     if ((int)h->reg.n_q <= h->prm.min_feats) { h->reg.pending_skipped = 2; return S2M_OK; } // :1300
     int rc;
-    if ((rc = push_state(h, pose))) return rc;             // (with the DevCtx block when that changed)
+    if ((rc = push_state(h, pose, h->reg.h_stamps + kStampLoop0))) return rc;             // (with the DevCtx block when that changed)
     h->reg.seg_pending = h->prm.early_exit && h->tune.seg_iters > 1 && h->tune.seg_iters < h->prm.max_iter;
     if ((rc = launch_loop(h, h->reg.seg_pending ? 1 : 0))) return rc;        // (state + trace come back with it)
     return S2M_OK;
@@ -812,7 +842,7 @@ int s2m_optimize_collect(s2m_handle h, float pose[6], const s2m_imu_init* imu, s
         S2M_HIP(h, hipSetDevice(h->device));
         S2M_HIP(h, hipStreamSynchronize(h->stream));
         if (h->batch.parent && !h->batch.slot_mode) h->reg.t_optimize_ms = h->batch.parent->reg.t_optimize_ms;      // a slot of a batch: the batch was timed as a whole
-        else S2M_HIP(h, hipEventElapsedTime(&h->reg.t_optimize_ms, h->reg.ev_a, h->reg.ev_b));
+        else h->reg.t_optimize_ms = stamps_ms(h, kStampLoop0, kStampLoop1);
         if (h->reg.seg_pending && !h->reg.h_state[1].done) {
             // the first range did not converge: the rest of the loop
             int rc2 = launch_loop(h, 2);
@@ -1385,7 +1415,8 @@ int s2m_debug_lm_close(s2m_handle h, int form, int iter, const double* rows, int
     s.T_valid = 0;
     s.isDegenerate = degen_in;
     memcpy(s.matP, matP_in, sizeof(s.matP));
-    hipLaunchKernelGGL(k_set_state, dim3(1), dim3(64), 0, h->stream, h->reg.state.as<DevState>(), s, (const int32_t*)h->reg.n_waves.as<int32_t>());
+    hipLaunchKernelGGL(k_set_state, dim3(1), dim3(64), 0, h->stream, h->reg.state.as<DevState>(), s, (const int32_t*)h->reg.n_waves.as<int32_t>(),
+                       (unsigned long long*)nullptr);
     S2M_HIP(h, hipMemsetAsync(h->hctx.trace + iter, 0xff, sizeof(s2m_iter_trace), h->stream));
     const LoopShape sh = shape_of(h);
     if (form == 0) launch_finalize(h, sh, iter, 0);
@@ -1445,13 +1476,19 @@ int s2m_debug_deferred(s2m_handle h, int slot)
     return h->reg.h_state ? h->reg.h_state[1].deferred_total : 0;
 }
 
+// set_scan_ms: from the start of the first ordering kernel to the end of the last.  optimize_ms: from the end of the state upload
+// of s2m_optimize_launch to the end of the k_finalize that closes the loop (with early exit on: its first range; the second
+// range, where one was needed, is added from an event pair of its own).  Both intervals of a single scan are read from
+// wall_clock64() stamps the bracketing kernels store in pinned memory - event records around them cost GPU time in every step -
+// so optimize_ms no longer includes the idle time between an event's packet and the first kernel behind it.  A batch is still
+// timed by an event pair around its graph; set_map_ms by events.  Synchronises if a scan preparation is still to be timed.
 int s2m_last_timing(s2m_handle h, float* optimize_ms, float* set_map_ms, float* set_scan_ms)
 {
     if (!h) return S2M_ERR_INVALID_ARG;
     if (h->reg.scan_timing_pending) {
         S2M_HIP(h, hipSetDevice(h->device));
         S2M_HIP(h, hipStreamSynchronize(h->stream));
-        S2M_HIP(h, hipEventElapsedTime(&h->reg.t_set_scan_ms, h->reg.ev_c, h->reg.ev_d));
+        h->reg.t_set_scan_ms = stamps_ms(h, kStampPrep0, kStampPrep1);
         h->reg.scan_timing_pending = false;
     }
     if (optimize_ms) *optimize_ms = h->reg.t_optimize_ms;

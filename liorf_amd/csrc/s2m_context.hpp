@@ -41,6 +41,10 @@ struct DevBuf {
 
 constexpr size_t kDsStride = 32;       // filtered clouds are kept as pcl::PointXYZI records
 
+// s2m_context::Registration::h_stamps: k_polar_count starts, k_chunk_table ends (consecutive: PrepSlot::stamps), the state
+// upload of s2m_optimize_launch ends, the k_finalize that closes the loop's (first) range ends
+enum { kStampPrep0 = 0, kStampPrep1 = 1, kStampLoop0 = 2, kStampLoop1 = 3, kStampCount = 4 };
+
 }  // namespace host
 }  // namespace s2m
 
@@ -70,6 +74,10 @@ struct __attribute__((visibility("hidden"))) s2m_context {
         s2m::DevState* h_state = nullptr;  // [2]: [0] upload, [1] download
         s2m_iter_trace* h_trace = nullptr; // [kMaxIter], directly behind h_state[1]: state and trace come back in one copy
         uint32_t* h_mm = nullptr;          // [6]
+        // [kStampCount] wall_clock64() values the kernels that bracket a single scan's preparation and its loop leave behind
+        // (device-visible: the kernels store them directly), and the counter's rate
+        unsigned long long* h_stamps = nullptr;
+        int wall_clock_khz = 0;
 
         // state that persists across scans in the reference node (:139-140)
         int persist_degenerate = 0;

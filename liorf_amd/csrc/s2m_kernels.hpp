@@ -325,6 +325,7 @@ __global__ __launch_bounds__(kPolarBlock) void k_polar_count(const PrepTable tbl
 {
     const PrepSlot& ps = tbl.s[blockIdx.y];
     if ((int)blockIdx.x >= ps.npb) return;
+    if (ps.stamps && blockIdx.x == 0 && threadIdx.x == 0) ps.stamps[0] = wall_clock64();      // the scan preparation starts (s2m_last_timing)
     const unsigned char* __restrict__ pts = ps.pts; const size_t stride = ps.stride; const int n = ps.n;
     int32_t* __restrict__ cell_of = ps.cell_of; int32_t* __restrict__ rank_of = ps.rank_of; int32_t* __restrict__ block_hist = ps.block_hist;
     __shared__ int32_t hist[kPolarCells];
@@ -743,6 +744,10 @@ __global__ __launch_bounds__(1024) void k_chunk_table(const PrepTable tbl)
     const PrepSlot& ps = tbl.s[blockIdx.y];
     if (ps.n <= 0) return;                                // an empty slot of a batch
     chunk_table_body(ps.chunk_parts, ps.n, ps.n_chunks, ps.capacity, ps.wave_table, ps.n_waves, nullptr, nullptr);
+    if (ps.stamps) {                                      // ... and ends: every thread has emitted its entries
+        __syncthreads();
+        if (threadIdx.x == 0) ps.stamps[1] = wall_clock64();
+    }
 }
 
 // per scan before launch 0, inside the captured loop: everything comes from the DevCtx block
@@ -1478,8 +1483,29 @@ __global__ __launch_bounds__(256) void k_wave_density(const SlotTable tbl, int r
 // k_finalize: one workgroup closing iteration `iter` on its own (lm_close_iteration above):
 // iteration 0 with the degeneracy analysis, and the last iteration of a scan (or every iteration
 // when the grid is too large for the fused form).  mode 1 = normal equations only (observation hook).
+// The k_finalize that ends a range of launches of a captured single-scan loop is given `out`, the pinned mirror the host reads
+// the loop's record from (DevState, then the max_iter trace records that lie behind it on the device as well): all its threads
+// copy the record there, also when the loop had ended before this launch - a copy node behind the kernel would be one more
+// trip through the queue (as k_sc_detect's result; the kernel's completion makes the stores visible to the host).
+// `stamp` (pinned, may be null): the wall clock once every thread has issued its part of the copy, the end of the loop for
+// s2m_last_timing.
 // ------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(kFinThreads) void k_finalize(const SlotTable tbl, int iter, int mode)
+__device__ __forceinline__ void finalize_record_out(gptr<DevState> st, DevState* out, int max_iter, unsigned long long* stamp)
+{
+    static_assert(sizeof(DevState) % 4 == 0 && sizeof(s2m_iter_trace) % 4 == 0, "the record is copied word by word");
+    if (out) {
+        const auto src = (gptr<const uint32_t>)st;
+        const auto dst = G(reinterpret_cast<uint32_t*>(out));
+        const int nw = (int)((sizeof(DevState) + sizeof(s2m_iter_trace) * (size_t)max_iter) / 4);
+        for (int k = threadIdx.x; k < nw; k += kFinThreads) dst[k] = src[k];
+    }
+    if (stamp) {
+        __syncthreads();                                  // (uniform: a kernel argument)
+        if (threadIdx.x == 0) *stamp = wall_clock64();
+    }
+}
+
+__global__ __launch_bounds__(kFinThreads) void k_finalize(const SlotTable tbl, int iter, int mode, DevState* out, unsigned long long* stamp)
 {
     const CtxP cp = ctx_const(tbl.ctx[blockIdx.y]);
     const auto st = G(tbl.st[blockIdx.y]);
@@ -1489,7 +1515,7 @@ __global__ __launch_bounds__(kFinThreads) void k_finalize(const SlotTable tbl, i
     float pose0[6];
 #pragma unroll
     for (int k = 0; k < 6; k++) pose0[k] = st->pose2[iter & 1][k];
-    if (mode == 0 && done0) return;
+    if (mode == 0 && done0) { finalize_record_out(st, out, cp->max_iter, stamp); return; }
     __shared__ LmShared sh;
     __shared__ float s_out[8];
     // the worklists of the search kernel start empty behind every close of its own (the certify kernel of the next launch appends)
@@ -1508,6 +1534,10 @@ __global__ __launch_bounds__(kFinThreads) void k_finalize(const SlotTable tbl, i
             for (int k = 0; k < 6; k++) st->sc[k] = sc6[k];
             st->T_valid = 1;
         }
+    }
+    if (out || stamp) {
+        __syncthreads();                                  // what thread 0 and wave 1 stored above is part of the record
+        finalize_record_out(st, out, cp->max_iter, stamp);
     }
 }
 
@@ -1531,9 +1561,10 @@ __global__ __launch_bounds__(256) void k_debug_hypot(const float* __restrict__ x
 __global__ void k_set_ctx(DevCtx* dst, DevCtx v) { if (threadIdx.x == 0 && blockIdx.x == 0) *dst = v; }
 // The wave count of the resident scan (left by k_chunk_table) is folded into the state block here.
 // the DevCtx block and the loop state of a scan in one launch (s2m_optimize: both change with every scan)
-__global__ void k_set_ctx_state(DevCtx* cdst, DevCtx c, DevState* dst, DevState v, const int32_t* n_waves)
+// `stamp` (pinned, may be null): the wall clock once the state is stored, the start of the loop for s2m_last_timing
+__global__ void k_set_ctx_state(DevCtx* cdst, DevCtx c, DevState* dst, DevState v, const int32_t* n_waves, unsigned long long* stamp)
 {
-    if (threadIdx.x == 0 && blockIdx.x == 0) { *cdst = c; v.n_waves = n_waves ? *n_waves : 0; *dst = v; }
+    if (threadIdx.x == 0 && blockIdx.x == 0) { *cdst = c; v.n_waves = n_waves ? *n_waves : 0; *dst = v; if (stamp) *stamp = wall_clock64(); }
 }
 
 // the same for the scan slots of a batch: one launch for all of them (blockIdx.x = slot)
@@ -1556,9 +1587,9 @@ __global__ __launch_bounds__(256) void k_init_states(const StateInitTable t)
     }
 }
 
-__global__ void k_set_state(DevState* dst, DevState v, const int32_t* n_waves)
+__global__ void k_set_state(DevState* dst, DevState v, const int32_t* n_waves, unsigned long long* stamp)
 {
-    if (threadIdx.x == 0 && blockIdx.x == 0) { v.n_waves = n_waves ? *n_waves : 0; *dst = v; }
+    if (threadIdx.x == 0 && blockIdx.x == 0) { v.n_waves = n_waves ? *n_waves : 0; *dst = v; if (stamp) *stamp = wall_clock64(); }
 }
 
 // ------------------------------------------------------------------------------------------
