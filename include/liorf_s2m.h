@@ -40,6 +40,7 @@ extern "C" {
 #define S2M_ERR_HIP           -3   /* a HIP runtime call failed (see s2m_last_error) */
 #define S2M_ERR_NO_SCAN       -4   /* *_resident call without s2m_set_scan          */
 #define S2M_ERR_CAPACITY      -5   /* grid / buffer limit exceeded                   */
+#define S2M_ERR_BUSY          -6   /* a launched loop closure is pending and this call needs its buffers */
 #define S2M_WARN_LEAF_TOO_SMALL 1   /* voxel filter: PCL's "leaf size is too small" case, output = input */
 
 /* ScanContext descriptor shape (reference include/Scancontext.h:82-84) */
@@ -636,7 +637,8 @@ int  s2m_icp_align(s2m_handle h, const void* src, size_t n_src, const void* tgt,
  * None of these calls touches the installed local map and its index, the scan (scan_ds included, which
  * S2M_KF_FROM_LAST_DOWNSAMPLE reads), the pose, the batch and stream slots, or the key store: the next registration is
  * bit for bit the one without the loop call. Calls on a handle are not concurrent: the node's loop thread takes the same
- * lock as the scan handler around them. The handle is held for the whole call, ICP included.
+ * lock as the scan handler around them. s2m_loop_align and s2m_loop_closure_rs hold the handle for the whole call, ICP included;
+ * the launched forms below hold it up to the size gate only.
  * Errors: a null handle, params outside their range or keys outside [0, N) give S2M_ERR_INVALID_ARG; an empty store gives
  * S2M_OK with S2M_LOOP_NONE (or no records); a short output buffer gives S2M_ERR_CAPACITY after writing cap records. */
 typedef struct s2m_loop_params {
@@ -671,6 +673,42 @@ int  s2m_loop_align(s2m_handle h, int32_t key_cur, int32_t key_pre, int32_t base
 /* performRSLoopClosure() without the external detection: the container test for key N-1, the device detection at
  * timeLaserInfoCur = time_cur, then s2m_loop_align(N-1, key_pre, -1, p). */
 int  s2m_loop_closure_rs(s2m_handle h, double time_cur, const s2m_loop_params* p /* NULL = defaults */, s2m_loop_result* out);
+
+/* ---- Loop closure beside the scan handler: launch, poll, collect ------------------------------------------------
+ * The reference runs loop closure in a thread of its own (loopClosureThread, :506-622): ICP takes as long as it takes while
+ * laserCloudInfoHandler keeps registering scans. The launched forms give the handle the same property. A launch does what
+ * s2m_loop_align / s2m_loop_closure_rs do up to and including the size gate (argument checks, the container test, the
+ * detection of the RS form, both submaps, n_cur < 300 || n_prev < 1000) and waits for the device only where they do (the
+ * detection result, the voxel counts). A call decided there returns in `early` exactly what the synchronous call returns
+ * (S2M_LOOP_NONE, S2M_LOOP_ALREADY_CLOSED, S2M_LOOP_TOO_FEW_POINTS, the errors) and nothing is pending. Otherwise
+ * early->status = S2M_LOOP_PENDING with key_cur, key_pre, n_cur, n_prev filled, and the whole ICP - the search structure over
+ * the target submap, every iteration with its close and convergence test, the fitness pass - is queued on a stream of the
+ * handle's own, of the lowest priority the device offers, behind the submap writes; the call returns without waiting for it.
+ * The launch keeps what the pose result needs, transCur of key_cur and pose[key_pre], as they are at that moment (the
+ * reference copies copy_cloudKeyPoses6D the same way): a later s2m_kf_set_poses or s2m_pg_apply_to_store does not change
+ * the result.
+ *   s2m_loop_poll never waits for the device: it tests an event. While the queued iterations run it returns S2M_OK with
+ *       S2M_LOOP_PENDING (keys and sizes filled). Iterations are queued a range at a time; a poll that finds a range ended
+ *       and the alignment not, queues the next range; one that finds the alignment ended queues the fitness pass; one that
+ *       finds the fitness pass ended applies the fitness gate, forms the pose result from the launch-time poses, records an
+ *       accepted closure in the container and returns S2M_LOOP_REJECTED / S2M_LOOP_ACCEPTED - the bytes s2m_loop_align
+ *       returns for the same store. With nothing pending: S2M_LOOP_NONE, keys -1.
+ *   s2m_loop_collect is the same with waits: it returns the final result.
+ *   The container is written when the result is collected, not at launch. One closure is in flight per handle.
+ *   While a closure is pending, every call that does not use the loop's buffers works as before and returns what it
+ *       would without it (s2m_set_*, s2m_optimize*, batches, slots, s2m_extract_surrounding, s2m_kf_add, s2m_kf_set_poses,
+ *       s2m_pg_*, s2m_project_*, the voxel calls, s2m_sc_*); s2m_loop_align, s2m_loop_closure_rs, s2m_loop_near_keyframes,
+ *       s2m_icp_align and a second launch return S2M_ERR_BUSY and touch nothing; s2m_kf_reset and s2m_destroy first wait for
+ *       the loop stream and drop the pending closure. A call that has to grow a device buffer may wait for the closure (the
+ *       runtime frees memory only on an idle device).
+ *   The node's loop thread: take the scan handler's lock, launch, release; then lock, s2m_loop_poll, release, sleep, until
+ *       the status is not S2M_LOOP_PENDING. */
+#define S2M_LOOP_PENDING         5
+int  s2m_loop_align_launch(s2m_handle h, int32_t key_cur, int32_t key_pre, int32_t base_key,
+                           const s2m_loop_params* p /* NULL = defaults */, s2m_loop_result* early);
+int  s2m_loop_closure_rs_launch(s2m_handle h, double time_cur, const s2m_loop_params* p /* NULL = defaults */, s2m_loop_result* early);
+int  s2m_loop_poll(s2m_handle h, s2m_loop_result* out);      /* never waits for the device */
+int  s2m_loop_collect(s2m_handle h, s2m_loop_result* out);   /* waits; poll until not pending */
 
 /* ---- Pose graph: factors, optimise, correct the key-frame store --------------------------------------------------
  * saveKeyFramesAndFactor() with addOdomFactor / addGPSFactor / addLoopFactor (reference src/mapOptmization.cpp:1386-1534)

@@ -108,6 +108,30 @@ int  s2m_debug_lm_close(s2m_handle h, int form, int iter, const double* rows, in
 int  s2m_debug_lm_close_check_args(int form, int iter, int max_iter, const double* rows, int n_rows, const float pose0[6],
                                    const float matP_in[36], const s2m_debug_lm_close_out* out);
 
+/* ---- the device loop of the ICP alignment (what s2m_loop_*_launch queues) -------------------------------------------
+ * S2M_ICP_RANGE: iterations queued at a time; between two ranges the host looks at the state block once. */
+#define S2M_ICP_RANGE 8
+/* Observation hook: one nearest-neighbour search of every src point among the tgt points (host records, x y z at byte 0 / 4 / 8).
+ * mode 0 = k_icp_nn, the tiled brute force of s2m_icp_align; mode 1 = the search of the device loop: the uniform grid over the
+ * target with its brute-force fallback (after s2m_debug_icp_tuning(.., use_grid = 0): the brute force over every source). keys[i] = (fp32 d2 bits << 32) | target index with d2 = (dx*dx + dy*dy) + dz*dz, the
+ * minimum over all finite targets (equal distances: the lower index); ~0 = no match (a non-finite source, no finite target).
+ * *n_fallback: sources the grid handed to the brute force (0 in mode 0). The grid's cell edge is that of the default
+ * icp_leaf (s2m_loop_default_params). S2M_ERR_BUSY while a launched closure is pending. */
+int  s2m_debug_icp_nearest(s2m_handle h, const void* src, size_t n_src, const void* tgt, size_t n_tgt, size_t stride_bytes, int32_t mode,
+                           uint64_t* keys, int32_t* n_fallback);
+/* The same search `reps` times between HIP events on the loop stream: *us_search = microseconds per search, *us_build = the
+ * grid's construction (box, counts, scan, scatter; 0 in mode 0). reps == 0 is s2m_debug_icp_nearest. keys may be NULL. */
+int  s2m_debug_icp_time_nearest(s2m_handle h, const void* src, size_t n_src, const void* tgt, size_t n_tgt, size_t stride_bytes, int32_t mode,
+                                int32_t reps, uint64_t* keys, int32_t* n_fallback, float* us_build, float* us_search);
+/* s2m_icp_align's alignment by the device loop, synchronously on the loop stream and with no size gate: the grid search, every
+ * iteration closed on the device by the host loop's own source, ranges of S2M_ICP_RANGE iterations, the fitness pass. The
+ * result is bit for bit that of s2m_icp_align. */
+int  s2m_debug_icp_align_device(s2m_handle h, const void* src, size_t n_src, const void* tgt, size_t n_tgt, size_t stride_bytes,
+                                const s2m_icp_params* p /* NULL = defaults */, s2m_icp_result* out);
+/* Experiment switch of the device loop's search for the launches and debug calls that follow: the cell edge in units of
+ * icp_leaf (0 = built in), the largest shell radius searched before a point goes to the brute force (0 = built in), and
+ * use_grid (0 = brute force only, 1 = grid, < 0 = built in). */
+int  s2m_debug_icp_tuning(s2m_handle h, float cell_in_leaves, int32_t shell_cap, int32_t use_grid);
 
 #ifdef __cplusplus
 }

@@ -29,6 +29,7 @@ int s2m_kf_reset(s2m_handle h)
     if (!h) return S2M_ERR_INVALID_ARG;
     S2M_HIP(h, hipSetDevice(h->device));
     S2M_HIP(h, hipStreamSynchronize(h->stream));
+    loop_drop_pending(h, false);                           // a launched closure reads the store's clouds: it ends first and is dropped
     // the store is emptied whatever happens: a block whose hipFree fails is dropped, never freed twice
     hipError_t e = hipSuccess;
     for (void* b : h->kf.blocks) { const hipError_t eb = hipFree(b); if (eb != hipSuccess && e == hipSuccess) e = eb; }

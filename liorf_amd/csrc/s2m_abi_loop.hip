@@ -2,6 +2,8 @@
 // and alignment against the key-frame store.  Host orchestration of s2m_icp.hip's and s2m_voxel.hip's stages only.
 #include <algorithm>
 #include <cmath>
+#include <cstdio>
+#include <cfloat>
 #include <cstring>
 
 #include "s2m_context.hpp"
@@ -14,6 +16,54 @@ static void icp_result_out(const IcpResult& r, s2m_icp_result* out)
     memcpy(out->T, r.T, sizeof(r.T));
     out->converged = r.converged; out->iterations = r.iterations; out->fitness_score = r.fitness;
 }
+
+static_assert(S2M_ICP_RANGE == kIcpRange, "include/liorf_s2m_debug.h states the range length of the device loop");
+
+int s2m::host::loop_busy(s2m_context* h)
+{
+    return h->loop.pending ? fail(h, S2M_ERR_BUSY, "a launched loop closure is pending: s2m_loop_poll / s2m_loop_collect it first") : S2M_OK;
+}
+
+void s2m::host::loop_drop_pending(s2m_context* h, bool destroy)
+{
+    if (h->loop.stream) (void)hipStreamSynchronize(h->loop.stream);
+    if (h->loop.icp) icp_dev_cancel(h->loop.icp);
+    h->loop.pending = false;
+    if (!destroy) return;
+    if (h->loop.ev_submaps) (void)hipEventDestroy(h->loop.ev_submaps);
+    if (h->loop.stream) (void)hipStreamDestroy(h->loop.stream);
+    h->loop.ev_submaps = nullptr; h->loop.stream = nullptr;
+}
+
+namespace {
+
+// The loop stream: the lowest priority the device offers, so that a closure yields to the registration kernels. A device
+// that reports no range (or an error) gives a stream of the default priority; that is said once on stderr.
+int loop_stream(s2m_context* h)
+{
+    if (h->loop.stream) return S2M_OK;
+    int least = 0, greatest = 0;
+    const hipError_t e = hipDeviceGetStreamPriorityRange(&least, &greatest);
+    if (e != hipSuccess || least == greatest) {
+        (void)hipGetLastError();
+        fprintf(stderr, "liorf_s2m: no stream priority range on device %d (%s): the loop-closure stream runs at the default priority\n",
+                h->device, e != hipSuccess ? hipGetErrorString(e) : "least == greatest");
+        S2M_HIP(h, hipStreamCreateWithFlags(&h->loop.stream, hipStreamNonBlocking));
+    } else {
+        S2M_HIP(h, hipStreamCreateWithPriority(&h->loop.stream, hipStreamNonBlocking, least));
+    }
+    S2M_HIP(h, hipEventCreateWithFlags(&h->loop.ev_submaps, hipEventDisableTiming));
+    return S2M_OK;
+}
+
+IcpTuning loop_tuning(const s2m_context* h, float leaf)
+{
+    IcpTuning t = h->loop.tune;
+    t.cell = (t.cell > 0.0f ? t.cell : kIcpCellLeaves) * leaf;
+    return t;
+}
+
+}  // namespace
 
 // ---- section 8(f) row F4: ICP loop-closure alignment -----------------------------------------------
 
@@ -34,6 +84,7 @@ int s2m_icp_align(s2m_handle h, const void* src, size_t n_src, const void* tgt, 
     if (rc) return rc;
     if ((rc = check_records(h, tgt, n_tgt, stride_bytes))) return rc;
     if (!out) return S2M_ERR_INVALID_ARG;
+    if ((rc = loop_busy(h))) return rc;
     s2m_icp_params prm;
     if (p) prm = *p; else s2m_icp_default_params(&prm);
     if (!(prm.max_correspondence_distance > 0.0) || prm.max_iterations < 1)
@@ -102,9 +153,10 @@ int loop_submap(s2m_context* h, int32_t key, int32_t search_num, int32_t loop_in
     return voxel_into(h, h->loop.xf.as<unsigned char>(), tab.total, kDsStride, leaf, dst, res);   // (waits for the counts)
 }
 
-// the container test, both submaps, the size gate, ICP, the fitness gate and the pose result (:565-621, :641-715)
-int loop_align_impl(s2m_context* h, int32_t key_cur, int32_t key_pre, int32_t base_key, const s2m_loop_params& prm, s2m_loop_result* out)
+// the container test, both submaps and the size gate (:565-566, :641-661). *decided: `out` is final (ALREADY_CLOSED, TOO_FEW_POINTS)
+int loop_gates(s2m_context* h, int32_t key_cur, int32_t key_pre, int32_t base_key, const s2m_loop_params& prm, s2m_loop_result* out, bool* decided)
 {
+    *decided = true;
     out->key_cur = key_cur;
     out->key_pre = key_pre;
     if (h->loop.index.count(key_cur)) { out->status = S2M_LOOP_ALREADY_CLOSED; return S2M_OK; }
@@ -115,25 +167,92 @@ int loop_align_impl(s2m_context* h, int32_t key_cur, int32_t key_pre, int32_t ba
     out->n_cur = (int32_t)rc_cur.n_out;
     out->n_prev = (int32_t)rc_prev.n_out;
     if (rc_cur.n_out < 300 || rc_prev.n_out < 1000) { out->status = S2M_LOOP_TOO_FEW_POINTS; return S2M_OK; }
-    // s2m_icp_align's path on the device submaps: historyKeyframeSearchRadius*2 (a float), 100, 1e-6, 1e-6 (:572-576)
-    const IcpParams ip{ (double)(prm.search_radius * 2.0f), 100, 1e-6, 1e-6 };
-    IcpResult r;
-    hipError_t e = icp_align(h->loop.icp, h->stream, h->loop.cur.as<unsigned char>(), rc_cur.n_out, h->loop.prev.as<unsigned char>(),
-                             rc_prev.n_out, kDsStride, ip, &r);
-    if (e != hipSuccess) return fail(h, S2M_ERR_HIP, "loop ICP alignment", e);
-    S2M_HIP(h, hipStreamSynchronize(h->stream));
+    *decided = false;
+    return S2M_OK;
+}
+
+// the fitness gate, the pose result and the container (:585-621, :707-715). T_cur, pose_pre: transCur of key_cur and the pose of
+// key_pre - the store's for the synchronous call, the launch-time snapshot for a launched closure
+void loop_finish(s2m_context* h, const IcpResult& r, int32_t base_key, float fitness_score, const float T_cur[12], const float pose_pre[6],
+                 s2m_loop_result* out)
+{
     icp_result_out(r, &out->icp);
-    if (!r.converged || r.fitness > (double)prm.fitness_score) { out->status = S2M_LOOP_REJECTED; return S2M_OK; }   // (:585)
+    if (!r.converged || r.fitness > (double)fitness_score) { out->status = S2M_LOOP_REJECTED; return; }   // (:585)
     if (base_key == -1) {
         float t_correct[12];                                // correctionLidarFrame * tWrong (:597-601)
-        host_affine_mul(r.T, h->kf.frame[(size_t)key_cur].T, t_correct);
+        host_affine_mul(r.T, T_cur, t_correct);
         host_translation_and_euler(t_correct, 4, out->pose_from);
-        memcpy(out->pose_to, &h->kf.pose[6 * (size_t)key_pre], sizeof(out->pose_to));
+        memcpy(out->pose_to, pose_pre, sizeof(out->pose_to));
     } else {
         host_translation_and_euler(r.T, 4, out->pose_from);  // (:707); poseTo is the identity (:709)
     }
     out->status = S2M_LOOP_ACCEPTED;
-    h->loop.index[key_cur] = key_pre;                       // loopIndexContainer[loopKeyCur] = loopKeyPre (:621)
+    h->loop.index[out->key_cur] = out->key_pre;             // loopIndexContainer[loopKeyCur] = loopKeyPre (:621)
+}
+
+// s2m_icp_align's path on the device submaps: historyKeyframeSearchRadius*2 (a float), 100, 1e-6, 1e-6 (:572-576)
+IcpParams loop_icp_params(const s2m_loop_params& prm) { return IcpParams{ (double)(prm.search_radius * 2.0f), 100, 1e-6, 1e-6 }; }
+
+// the container test, both submaps, the size gate, ICP, the fitness gate and the pose result (:565-621, :641-715)
+int loop_align_impl(s2m_context* h, int32_t key_cur, int32_t key_pre, int32_t base_key, const s2m_loop_params& prm, s2m_loop_result* out)
+{
+    bool decided;
+    int rc = loop_gates(h, key_cur, key_pre, base_key, prm, out, &decided);
+    if (rc || decided) return rc;
+    IcpResult r;
+    hipError_t e = icp_align(h->loop.icp, h->stream, h->loop.cur.as<unsigned char>(), (size_t)out->n_cur, h->loop.prev.as<unsigned char>(),
+                             (size_t)out->n_prev, kDsStride, loop_icp_params(prm), &r);
+    if (e != hipSuccess) return fail(h, S2M_ERR_HIP, "loop ICP alignment", e);
+    S2M_HIP(h, hipStreamSynchronize(h->stream));
+    loop_finish(h, r, base_key, prm.fitness_score, h->kf.frame[(size_t)key_cur].T, &h->kf.pose[6 * (size_t)key_pre], out);
+    return S2M_OK;
+}
+
+// the launched form: the same gates, then the whole ICP queued on the loop stream behind the submap writes
+int loop_launch_impl(s2m_context* h, int32_t key_cur, int32_t key_pre, int32_t base_key, const s2m_loop_params& prm, s2m_loop_result* early)
+{
+    bool decided;
+    int rc = loop_gates(h, key_cur, key_pre, base_key, prm, early, &decided);
+    if (rc || decided) return rc;
+    if ((rc = loop_stream(h))) return rc;
+    S2M_HIP(h, hipEventRecord(h->loop.ev_submaps, h->stream));
+    S2M_HIP(h, hipStreamWaitEvent(h->loop.stream, h->loop.ev_submaps, 0));
+    hipError_t e = icp_dev_begin(h->loop.icp, h->loop.stream, h->loop.cur.as<unsigned char>(), (size_t)early->n_cur,
+                                 h->loop.prev.as<unsigned char>(), (size_t)early->n_prev, kDsStride, loop_icp_params(prm),
+                                 loop_tuning(h, prm.icp_leaf));
+    if (e != hipSuccess) {
+        (void)hipStreamSynchronize(h->loop.stream);         // (whatever was queued before the failure ends before the buffers are used again)
+        return fail(h, S2M_ERR_HIP, "loop ICP launch", e);
+    }
+    early->status = S2M_LOOP_PENDING;
+    h->loop.pend = *early;
+    h->loop.pend_fitness = prm.fitness_score;
+    h->loop.pend_base_key = base_key;
+    memcpy(h->loop.snap_T, h->kf.frame[(size_t)key_cur].T, sizeof(h->loop.snap_T));          // as the reference copies copy_cloudKeyPoses6D
+    memcpy(h->loop.snap_pose_pre, &h->kf.pose[6 * (size_t)key_pre], sizeof(h->loop.snap_pose_pre));
+    h->loop.pending = true;
+    return S2M_OK;
+}
+
+int loop_poll_impl(s2m_context* h, s2m_loop_result* out, bool wait)
+{
+    if (!h) return S2M_ERR_INVALID_ARG;
+    if (!out) return fail(h, S2M_ERR_INVALID_ARG, "null loop result");
+    loop_result_init(out);
+    if (!h->loop.pending) return S2M_OK;                    // S2M_LOOP_NONE, keys -1
+    S2M_HIP(h, hipSetDevice(h->device));
+    bool done = false;
+    IcpResult r;
+    const hipError_t e = icp_dev_advance(h->loop.icp, h->loop.stream, wait, &done, &r);
+    if (e != hipSuccess) {
+        loop_drop_pending(h, false);
+        return fail(h, S2M_ERR_HIP, "loop ICP on the loop stream", e);
+    }
+    *out = h->loop.pend;
+    if (!done) return S2M_OK;                               // S2M_LOOP_PENDING
+    h->loop.pending = false;
+    out->status = S2M_LOOP_NONE;
+    loop_finish(h, r, h->loop.pend_base_key, h->loop.pend_fitness, h->loop.snap_T, h->loop.snap_pose_pre, out);
     return S2M_OK;
 }
 
@@ -146,9 +265,10 @@ int s2m_loop_near_keyframes(s2m_handle h, int32_t key, int32_t search_num, int32
 {
     if (!h) return S2M_ERR_INVALID_ARG;
     if (!n_out || bad_out(out, out_stride_bytes, cap)) return fail(h, S2M_ERR_INVALID_ARG, "bad output buffer");
-    *n_out = 0;
-    int rc = check_leaf(h, leaf);
+    int rc = loop_busy(h);
     if (rc) return rc;
+    *n_out = 0;
+    if ((rc = check_leaf(h, leaf))) return rc;
     if (search_num < 0) return fail(h, S2M_ERR_INVALID_ARG, "search_num must be >= 0");
     const size_t N = h->kf.time.size();
     if (N == 0) return S2M_OK;
@@ -163,30 +283,37 @@ int s2m_loop_near_keyframes(s2m_handle h, int32_t key, int32_t search_num, int32
     return res.leaf_too_small ? S2M_WARN_LEAF_TOO_SMALL : S2M_OK;
 }
 
-int s2m_loop_align(s2m_handle h, int32_t key_cur, int32_t key_pre, int32_t base_key, const s2m_loop_params* p, s2m_loop_result* out)
+namespace {
+
+using LoopImpl = int (*)(s2m_context*, int32_t, int32_t, int32_t, const s2m_loop_params&, s2m_loop_result*);
+
+int loop_align_front(s2m_context* h, int32_t key_cur, int32_t key_pre, int32_t base_key, const s2m_loop_params* p, s2m_loop_result* out,
+                     LoopImpl impl)
 {
     if (!h) return S2M_ERR_INVALID_ARG;
     if (!out) return fail(h, S2M_ERR_INVALID_ARG, "null loop result");
+    int rc = loop_busy(h);
+    if (rc) return rc;
     loop_result_init(out);
     s2m_loop_params prm;
-    int rc = loop_params(h, p, &prm);
-    if (rc) return rc;
+    if ((rc = loop_params(h, p, &prm))) return rc;
     const size_t N = h->kf.time.size();
     if (N == 0) return S2M_OK;                             // cloudKeyPoses3D->points.empty() (:544-545, :627-628)
     if (!loop_key_ok(key_cur, N) || !loop_key_ok(key_pre, N) || (base_key != -1 && !loop_key_ok(base_key, N)))
         return fail(h, S2M_ERR_INVALID_ARG, "loop keys outside the key-frame store");
     S2M_HIP(h, hipSetDevice(h->device));
-    return loop_align_impl(h, key_cur, key_pre, base_key, prm, out);
+    return impl(h, key_cur, key_pre, base_key, prm, out);
 }
 
-int s2m_loop_closure_rs(s2m_handle h, double time_cur, const s2m_loop_params* p, s2m_loop_result* out)
+int loop_closure_rs_front(s2m_context* h, double time_cur, const s2m_loop_params* p, s2m_loop_result* out, LoopImpl impl)
 {
     if (!h) return S2M_ERR_INVALID_ARG;
     if (!out) return fail(h, S2M_ERR_INVALID_ARG, "null loop result");
+    int rc = loop_busy(h);
+    if (rc) return rc;
     loop_result_init(out);
     s2m_loop_params prm;
-    int rc = loop_params(h, p, &prm);
-    if (rc) return rc;
+    if ((rc = loop_params(h, p, &prm))) return rc;
     if (!std::isfinite(time_cur)) return fail(h, S2M_ERR_INVALID_ARG, "time_cur must be finite");
     const size_t N = h->kf.time.size();
     if (N == 0) return S2M_OK;                             // (:544-545)
@@ -202,5 +329,132 @@ int s2m_loop_closure_rs(s2m_handle h, double time_cur, const s2m_loop_params* p,
                                time_cur, (double)prm.time_diff_s, &key_pre);
     if (e != hipSuccess) return fail(h, S2M_ERR_HIP, "loop detection", e);
     if (key_pre == -1 || key_pre == key_cur) return S2M_OK;                 // (:761-762)
-    return loop_align_impl(h, key_cur, key_pre, -1, prm, out);
+    return impl(h, key_cur, key_pre, -1, prm, out);
+}
+
+}  // namespace
+
+int s2m_loop_align(s2m_handle h, int32_t key_cur, int32_t key_pre, int32_t base_key, const s2m_loop_params* p, s2m_loop_result* out)
+{
+    return loop_align_front(h, key_cur, key_pre, base_key, p, out, loop_align_impl);
+}
+
+int s2m_loop_closure_rs(s2m_handle h, double time_cur, const s2m_loop_params* p, s2m_loop_result* out)
+{
+    return loop_closure_rs_front(h, time_cur, p, out, loop_align_impl);
+}
+
+int s2m_loop_align_launch(s2m_handle h, int32_t key_cur, int32_t key_pre, int32_t base_key, const s2m_loop_params* p, s2m_loop_result* early)
+{
+    return loop_align_front(h, key_cur, key_pre, base_key, p, early, loop_launch_impl);
+}
+
+int s2m_loop_closure_rs_launch(s2m_handle h, double time_cur, const s2m_loop_params* p, s2m_loop_result* early)
+{
+    return loop_closure_rs_front(h, time_cur, p, early, loop_launch_impl);
+}
+
+int s2m_loop_poll(s2m_handle h, s2m_loop_result* out) { return loop_poll_impl(h, out, false); }
+
+int s2m_loop_collect(s2m_handle h, s2m_loop_result* out) { return loop_poll_impl(h, out, true); }
+
+// ---- diagnostics of the device loop (include/liorf_s2m_debug.h) ---------------------------------------------------------
+
+namespace {
+
+// both host clouds into the ICP staging buffers, on the loop stream
+int debug_stage(s2m_context* h, const void* src, size_t n_src, const void* tgt, size_t n_tgt, size_t stride)
+{
+    int rc = check_records(h, src, n_src, stride);
+    if (rc) return rc;
+    if ((rc = check_records(h, tgt, n_tgt, stride))) return rc;
+    if ((rc = loop_busy(h))) return rc;
+    S2M_HIP(h, hipSetDevice(h->device));
+    if ((rc = loop_stream(h))) return rc;
+    S2M_HIP(h, hipStreamSynchronize(h->stream));            // (the staging buffers are the synchronous call's too)
+    if ((rc = ensure(h, h->loop.icp_src, n_src * stride)) || (rc = ensure(h, h->loop.icp_tgt, n_tgt * stride))) return rc;
+    if (n_src) S2M_HIP(h, hipMemcpyAsync(h->loop.icp_src.p, src, n_src * stride, hipMemcpyHostToDevice, h->loop.stream));
+    if (n_tgt) S2M_HIP(h, hipMemcpyAsync(h->loop.icp_tgt.p, tgt, n_tgt * stride, hipMemcpyHostToDevice, h->loop.stream));
+    return S2M_OK;
+}
+
+}  // namespace
+
+int s2m_debug_icp_tuning(s2m_handle h, float cell_in_leaves, int32_t shell_cap, int32_t use_grid)
+{
+    if (!h) return S2M_ERR_INVALID_ARG;
+    if (!(cell_in_leaves >= 0.0f) || !std::isfinite(cell_in_leaves) || shell_cap < 0)
+        return fail(h, S2M_ERR_INVALID_ARG, "cell edge (in leaves) and shell cap must not be negative");
+    const int rc = loop_busy(h);
+    if (rc) return rc;
+    h->loop.tune.cell = cell_in_leaves;                     // 0: the built-in edge
+    h->loop.tune.shell_cap = shell_cap > 0 ? shell_cap : kIcpShellCap;
+    h->loop.tune.use_grid = use_grid < 0 ? (kIcpUseGrid ? 1 : 0) : (use_grid != 0);
+    return S2M_OK;
+}
+
+int s2m_debug_icp_nearest(s2m_handle h, const void* src, size_t n_src, const void* tgt, size_t n_tgt, size_t stride_bytes, int32_t mode,
+                          uint64_t* keys, int32_t* n_fallback)
+{
+    return s2m_debug_icp_time_nearest(h, src, n_src, tgt, n_tgt, stride_bytes, mode, 0, keys, n_fallback, nullptr, nullptr);
+}
+
+int s2m_debug_icp_time_nearest(s2m_handle h, const void* src, size_t n_src, const void* tgt, size_t n_tgt, size_t stride_bytes, int32_t mode,
+                               int32_t reps, uint64_t* keys, int32_t* n_fallback, float* us_build, float* us_search)
+{
+    if (!h) return S2M_ERR_INVALID_ARG;
+    if ((mode != 0 && mode != 1) || reps < 0 || (n_src && !keys && reps == 0)) return fail(h, S2M_ERR_INVALID_ARG, "mode is 0 or 1, keys must not be null");
+    int rc = debug_stage(h, src, n_src, tgt, n_tgt, stride_bytes);
+    if (rc) return rc;
+    if (n_fallback) *n_fallback = 0;
+    if (us_build) *us_build = 0.0f;
+    if (us_search) *us_search = 0.0f;
+    if (n_src == 0) return S2M_OK;
+    if (n_tgt == 0) {                                       // no target: no source has a match
+        for (size_t i = 0; keys && i < n_src; i++) keys[i] = ~0ull;
+        S2M_HIP(h, hipStreamSynchronize(h->loop.stream));
+        return S2M_OK;
+    }
+    s2m_loop_params lp;
+    s2m_loop_default_params(&lp);
+    int nf = 0;
+    const hipError_t e = icp_dev_nearest(h->loop.icp, h->loop.stream, h->loop.icp_src.as<unsigned char>(), n_src, h->loop.icp_tgt.as<unsigned char>(),
+                                         n_tgt, stride_bytes, mode, loop_tuning(h, lp.icp_leaf), reinterpret_cast<unsigned long long*>(keys), &nf,
+                                         reps, us_build, us_search);
+    if (e != hipSuccess) return fail(h, S2M_ERR_HIP, "ICP nearest-neighbour search", e);
+    if (n_fallback) *n_fallback = nf;
+    return S2M_OK;
+}
+
+int s2m_debug_icp_align_device(s2m_handle h, const void* src, size_t n_src, const void* tgt, size_t n_tgt, size_t stride_bytes,
+                               const s2m_icp_params* p, s2m_icp_result* out)
+{
+    if (!h) return S2M_ERR_INVALID_ARG;
+    if (!out) return fail(h, S2M_ERR_INVALID_ARG, "null ICP result");
+    s2m_icp_params prm;
+    if (p) prm = *p; else s2m_icp_default_params(&prm);
+    if (!(prm.max_correspondence_distance > 0.0) || prm.max_iterations < 1)
+        return fail(h, S2M_ERR_INVALID_ARG, "ICP needs a positive correspondence distance and at least one iteration");
+    int rc = debug_stage(h, src, n_src, tgt, n_tgt, stride_bytes);
+    if (rc) return rc;
+    IcpResult r;
+    for (int i = 0; i < 16; i++) r.T[i] = (i % 5 == 0) ? 1.0f : 0.0f;
+    r.converged = 0; r.iterations = 0; r.fitness = DBL_MAX;
+    if (n_src && n_tgt) {
+        s2m_loop_params lp;
+        s2m_loop_default_params(&lp);
+        const IcpParams ip{ prm.max_correspondence_distance, prm.max_iterations, prm.transformation_epsilon, prm.euclidean_fitness_epsilon };
+        hipError_t e = icp_dev_begin(h->loop.icp, h->loop.stream, h->loop.icp_src.as<unsigned char>(), n_src, h->loop.icp_tgt.as<unsigned char>(),
+                                     n_tgt, stride_bytes, ip, loop_tuning(h, lp.icp_leaf));
+        bool done = false;
+        if (e == hipSuccess) e = icp_dev_advance(h->loop.icp, h->loop.stream, true, &done, &r);
+        if (e != hipSuccess || !done) {
+            (void)hipStreamSynchronize(h->loop.stream);
+            icp_dev_cancel(h->loop.icp);
+            return fail(h, S2M_ERR_HIP, "ICP device loop", e);
+        }
+    }
+    S2M_HIP(h, hipStreamSynchronize(h->loop.stream));
+    icp_result_out(r, out);
+    return S2M_OK;
 }

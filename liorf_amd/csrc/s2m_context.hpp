@@ -187,6 +187,17 @@ struct __attribute__((visibility("hidden"))) s2m_context {
         DevBuf icp_src, icp_tgt;
         std::map<int32_t, int32_t> index;
         DevBuf xf, cur, prev;
+        // the launched closure (s2m_loop_*_launch): the stream its ICP runs on (lowest priority, created at the first launch), the
+        // event on the handle's stream behind the submap writes, and what the result needs from launch time
+        hipStream_t stream = nullptr;
+        hipEvent_t ev_submaps = nullptr;
+        bool pending = false;
+        s2m_loop_result pend{};            // key_cur, key_pre, n_cur, n_prev of the pending closure
+        float pend_fitness = 0.0f;         // s2m_loop_params::fitness_score of the launch
+        int32_t pend_base_key = -1;
+        float snap_T[12] = { 0 };          // kf.frame[key_cur].T at launch
+        float snap_pose_pre[6] = { 0 };    // kf.pose[key_pre] at launch
+        s2m::IcpTuning tune{ 0.0f, s2m::kIcpShellCap, s2m::kIcpUseGrid ? 1 : 0 };   // cell: edge in units of the leaf (s2m_debug_icp_tuning)
     } loop;
 
     // the global map and the saved map from the store: transformed frames, the filtered cloud, the chunked copy-out (frame table,
@@ -293,6 +304,12 @@ int set_scan_impl(s2m_context* h, const void* pts, size_t n, size_t stride, bool
 // SCManager::makeScancontext + ring key of a cloud into h->sc.out (device); then: append them as key frame sc.n
 int sc_build_descriptor(s2m_context* h, const void* pts, size_t n, size_t stride_bytes, bool on_device = false);
 int sc_append_from_out(s2m_context* h);
+
+// ---- s2m_abi_loop.hip ----
+// S2M_ERR_BUSY while a launched loop closure is pending (the calls that use its buffers start with this)
+int loop_busy(s2m_context* h);
+// waits for the loop stream and forgets the pending closure (s2m_kf_reset, s2m_destroy); `destroy`: the stream and event go too
+void loop_drop_pending(s2m_context* h, bool destroy);
 
 // ---- s2m_abi_voxel.hip ----
 // VoxelGrid of a device cloud into `dst` (grown to hold one record per input point, the worst case).

@@ -14,6 +14,12 @@
 // the convergence state machine exactly as PCL does; (3) the source cloud is transformed in place by the
 // incremental transform, as PCL transforms input_transformed.  fp32 distances use the operation order
 // of the oracle ((dx*dx + dy*dy) + dz*dz, -ffp-contract=off), so correspondences are identical to it.
+//
+// The device loop (icp_dev_*, what s2m_loop_*_launch queues) is the same alignment without the host in it: (1) becomes an exact
+// 1-NN through a uniform grid over the target, built once per alignment, with a brute-force worklist for the points the grid
+// does not settle (same keys); the host's part of (2) becomes k_icp_close, which runs the host loop's own source
+// (s2m_icp_close.hpp); iterations are queued in ranges and every kernel behind the end of the alignment returns at entry.
+// DESIGN.md section 12 has the stopping rule of the grid search and its derivation.
 #include "s2m_icp.hpp"
 
 #include <algorithm>
@@ -22,7 +28,7 @@
 #include <cstring>
 #include <new>
 
-#include "s2m_host_math.hpp"
+#include "s2m_icp_close.hpp"
 
 namespace s2m {
 
@@ -62,18 +68,11 @@ __global__ __launch_bounds__(256) void k_icp_reset(unsigned long long* __restric
     if (i < n) best[i] = kNoMatch;
 }
 
-// grid (source blocks, target slices): 256 source points against target points [slice*len, (slice+1)*len)
-__global__ __launch_bounds__(kNnThreads) void k_icp_nn(const float4* __restrict__ cur, int n_src, const float4* __restrict__ tgt, int n_tgt,
-                                                       int slice_len, unsigned long long* __restrict__ best)
+// the tile loop of the brute-force search: target points [j0, j1) staged through LDS in tiles of kNnTile, the nearest of them to p
+// (lowest index among equals) left in bd / bi. Every thread of the workgroup calls it (the staging is collective).
+__device__ __forceinline__ void nn_tiles(const float4 p, const bool fin, const float4* __restrict__ tgt, const int j0, const int j1,
+                                         float4* tile, float& bd, int& bi)
 {
-    __shared__ float4 tile[kNnTile];
-    const int i = blockIdx.x * kNnThreads + threadIdx.x;
-    const bool valid = i < n_src;
-    const float4 p = valid ? cur[i] : make_float4(0, 0, 0, 0);
-    const bool fin = valid && isfinite(p.x) && isfinite(p.y) && isfinite(p.z);
-    float bd = INFINITY;
-    int bi = -1;
-    const int j0 = blockIdx.y * slice_len, j1 = min(j0 + slice_len, n_tgt);
     for (int base = j0; base < j1; base += kNnTile) {
         const int m = min(kNnTile, j1 - base);
         __syncthreads();
@@ -100,16 +99,30 @@ __global__ __launch_bounds__(kNnThreads) void k_icp_nn(const float4* __restrict_
             }
         }
     }
+}
+
+// grid (source blocks, target slices): 256 source points against target points [slice*len, (slice+1)*len)
+__global__ __launch_bounds__(kNnThreads) void k_icp_nn(const float4* __restrict__ cur, int n_src, const float4* __restrict__ tgt, int n_tgt,
+                                                       int slice_len, unsigned long long* __restrict__ best)
+{
+    __shared__ float4 tile[kNnTile];
+    const int i = blockIdx.x * kNnThreads + threadIdx.x;
+    const bool valid = i < n_src;
+    const float4 p = valid ? cur[i] : make_float4(0, 0, 0, 0);
+    const bool fin = valid && isfinite(p.x) && isfinite(p.y) && isfinite(p.z);
+    float bd = INFINITY;
+    int bi = -1;
+    const int j0 = blockIdx.y * slice_len, j1 = min(j0 + slice_len, n_tgt);
+    nn_tiles(p, fin, tgt, j0, j1, tile, bd, bi);
     if (fin && bi >= 0)       // d2 >= 0: its bit pattern orders like the value; NaN distances (non-finite targets) never win above
         atomicMin(&best[i], ((unsigned long long)__float_as_uint(bd) << 32) | (unsigned)bi);
 }
 
 // count, sum d2, centroids and raw cross moments of the correspondences with d2 <= max_d2 (fp64): this workgroup's row of `part`
-__global__ __launch_bounds__(256) void k_icp_sums(const float4* __restrict__ cur, int n_src, const float4* __restrict__ tgt,
-                                                  const unsigned long long* __restrict__ best, float max_d2_f, double max_d2,
-                                                  double* __restrict__ part)
+__device__ __forceinline__ void sums_body(const float4* __restrict__ cur, int n_src, const float4* __restrict__ tgt,
+                                          const unsigned long long* __restrict__ best, double max_d2, double* __restrict__ part,
+                                          double (*sh)[17])
 {
-    __shared__ double sh[4][17];
     double a[17];
 #pragma unroll
     for (int k = 0; k < 17; k++) a[k] = 0.0;
@@ -125,7 +138,6 @@ __global__ __launch_bounds__(256) void k_icp_sums(const float4* __restrict__ cur
         a[11] += (double)t.y * s.x; a[12] += (double)t.y * s.y; a[13] += (double)t.y * s.z;
         a[14] += (double)t.z * s.x; a[15] += (double)t.z * s.y; a[16] += (double)t.z * s.z;
     }
-    (void)max_d2_f;
 #pragma unroll
     for (int k = 0; k < 17; k++) {
 #pragma unroll
@@ -140,8 +152,17 @@ __global__ __launch_bounds__(256) void k_icp_sums(const float4* __restrict__ cur
     if (threadIdx.x < 17) part[17 * blockIdx.x + threadIdx.x] = sh[0][threadIdx.x] + sh[1][threadIdx.x] + sh[2][threadIdx.x] + sh[3][threadIdx.x];
 }
 
+__global__ __launch_bounds__(256) void k_icp_sums(const float4* __restrict__ cur, int n_src, const float4* __restrict__ tgt,
+                                                  const unsigned long long* __restrict__ best, float max_d2_f, double max_d2,
+                                                  double* __restrict__ part)
+{
+    __shared__ double sh[4][17];
+    (void)max_d2_f;
+    sums_body(cur, n_src, tgt, best, max_d2, part, sh);
+}
+
 // the rows of k_icp_sums folded in workgroup order
-__global__ __launch_bounds__(64) void k_icp_fold(const double* __restrict__ part, int rows, double* __restrict__ sums)
+__device__ __forceinline__ void fold_body(const double* __restrict__ part, int rows, double* __restrict__ sums)
 {
     const int k = threadIdx.x;
     if (k >= 17) return;
@@ -150,15 +171,362 @@ __global__ __launch_bounds__(64) void k_icp_fold(const double* __restrict__ part
     sums[k] = a;
 }
 
+__global__ __launch_bounds__(64) void k_icp_fold(const double* __restrict__ part, int rows, double* __restrict__ sums)
+{
+    fold_body(part, rows, sums);
+}
+
 struct Mat34 { float m[12]; };
-__global__ __launch_bounds__(256) void k_icp_transform(float4* __restrict__ cur, int n, Mat34 T)
+__device__ __forceinline__ void transform_body(float4* __restrict__ cur, int n, const float* m)
 {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     const float4 p = cur[i];
-    cur[i] = make_float4(T.m[0] * p.x + T.m[1] * p.y + T.m[2]  * p.z + T.m[3],
-                         T.m[4] * p.x + T.m[5] * p.y + T.m[6]  * p.z + T.m[7],
-                         T.m[8] * p.x + T.m[9] * p.y + T.m[10] * p.z + T.m[11], 0.0f);
+    cur[i] = make_float4(m[0] * p.x + m[1] * p.y + m[2]  * p.z + m[3],
+                         m[4] * p.x + m[5] * p.y + m[6]  * p.z + m[7],
+                         m[8] * p.x + m[9] * p.y + m[10] * p.z + m[11], 0.0f);
+}
+
+__global__ __launch_bounds__(256) void k_icp_transform(float4* __restrict__ cur, int n, Mat34 T)
+{
+    transform_body(cur, n, T.m);
+}
+
+
+// ---- the device loop (icp_dev_*): an alignment that is queued and left alone ------------------------------------------------
+// Everything the loop carries lives in one device block, copied to the host in one piece at the end of a range of iterations.
+// phase 0 = a kernel of the iteration loop: it returns at entry once st.done is set (the idiom of k_pg_cg_*: no kernel waits on
+// another, the launches queued behind the end of an alignment are idle); phase 1 = the fitness pass, which runs after it.
+
+struct IcpGrid {
+    float lo[3];           // least finite target coordinate per axis: the grid's origin
+    float inv, cell;       // cell edge and 1.0f / cell (the edge asked for, or a larger one where the box needs more than kGridMaxCells)
+    int   n[3];            // cells per axis; a target's cell is floor((x - lo) * inv) per axis, x fastest
+    int   n_fin;           // finite targets (0: no source has a match)
+    int   usable;          // 0: no grid was built (an extent that overflows fp32) - every source goes to the brute force
+};
+
+struct IcpDevBlock {
+    IcpLoopState st;
+    IcpGrid      g;
+    unsigned     bbox[6];  // ordered-integer images of the finite targets' min (0..2) and max (3..5)
+    int          wl_count; // sources on the fallback list of the search in flight; k_icp_fold_dev zeroes it
+    int          n_fallback;   // wl_count of the search closed last
+    double       sums[17];
+    double       pad;
+};
+
+constexpr int kGridMaxCells = 1 << 18;
+constexpr int kGridThreads = 64;                    // one wave per workgroup: a few thousand source points reach ~50 CUs
+constexpr double kFaceSlack = 0x1p-22;              // 4 fp32 roundings: (x - lo) * inv with inv = 1 / cell rounds three times
+constexpr double kBoundSlack = 1e-6;                // > 6 fp32 roundings of d2 = (dx*dx + dy*dy) + dz*dz from the exact distance
+
+__device__ __forceinline__ unsigned ord_of(float f) { const unsigned b = __float_as_uint(f); return (b & 0x80000000u) ? ~b : (b | 0x80000000u); }
+__device__ __forceinline__ float ord_to(unsigned o) { return __uint_as_float((o & 0x80000000u) ? (o & 0x7fffffffu) : ~o); }
+__device__ __forceinline__ bool done_guard(const IcpDevBlock* blk, int phase) { return phase == 0 && blk->st.done != 0; }
+// the cell coordinate along one axis before floor and clamp: non-decreasing in x (a subtraction of and a product with constants)
+__device__ __forceinline__ float cell_coord(float x, float lo, float inv) { return (x - lo) * inv; }
+
+__global__ __launch_bounds__(64) void k_icp_begin(IcpDevBlock* blk)
+{
+    if (threadIdx.x != 0) return;
+    icp_state_init(&blk->st);
+    for (int a = 0; a < 3; a++) { blk->bbox[a] = 0xffffffffu; blk->bbox[3 + a] = 0u; }
+    blk->wl_count = 0; blk->n_fallback = 0;
+    blk->g.n_fin = 0; blk->g.usable = 0;
+}
+
+__global__ __launch_bounds__(256) void k_icp_grid_bbox(const float4* __restrict__ tgt, int n, IcpDevBlock* blk)
+{
+    __shared__ unsigned sh[4][6];
+    unsigned lo[3] = { 0xffffffffu, 0xffffffffu, 0xffffffffu }, hi[3] = { 0u, 0u, 0u };
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+        const float4 t = tgt[i];
+        if (!(isfinite(t.x) && isfinite(t.y) && isfinite(t.z))) continue;
+        const unsigned o[3] = { ord_of(t.x), ord_of(t.y), ord_of(t.z) };
+#pragma unroll
+        for (int a = 0; a < 3; a++) { lo[a] = min(lo[a], o[a]); hi[a] = max(hi[a], o[a]); }
+    }
+#pragma unroll
+    for (int a = 0; a < 3; a++)
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) {
+            lo[a] = min(lo[a], (unsigned)__shfl_down((int)lo[a], off, 64));
+            hi[a] = max(hi[a], (unsigned)__shfl_down((int)hi[a], off, 64));
+        }
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    if (lane == 0)
+        for (int a = 0; a < 3; a++) { sh[wave][a] = lo[a]; sh[wave][3 + a] = hi[a]; }
+    __syncthreads();
+    if (threadIdx.x < 3) atomicMin(&blk->bbox[threadIdx.x], min(min(sh[0][threadIdx.x], sh[1][threadIdx.x]), min(sh[2][threadIdx.x], sh[3][threadIdx.x])));
+    else if (threadIdx.x < 6) atomicMax(&blk->bbox[threadIdx.x], max(max(sh[0][threadIdx.x], sh[1][threadIdx.x]), max(sh[2][threadIdx.x], sh[3][threadIdx.x])));
+}
+
+// the grid's shape from the box: the edge asked for, enlarged until the box needs no more than kGridMaxCells cells
+__global__ __launch_bounds__(64) void k_icp_grid_setup(IcpDevBlock* blk, float cell_req)
+{
+    if (threadIdx.x != 0) return;
+    IcpGrid g{};
+    if (blk->bbox[0] == 0xffffffffu) { blk->g = g; return; }             // no finite target: n_fin stays 0
+    float hi[3];
+    bool ok = true;
+    for (int a = 0; a < 3; a++) {
+        g.lo[a] = ord_to(blk->bbox[a]); hi[a] = ord_to(blk->bbox[3 + a]);
+        ok = ok && isfinite(hi[a] - g.lo[a]);
+    }
+    float cell = cell_req;
+    for (int tries = 0; ok && tries < 96; tries++) {
+        const float inv = 1.0f / cell;
+        double prod = 1.0;
+        float fn[3];
+        for (int a = 0; a < 3; a++) { fn[a] = floorf(cell_coord(hi[a], g.lo[a], inv)) + 1.0f; prod *= (double)fn[a]; }
+        if (isfinite(inv) && inv > 0.0f && prod <= (double)kGridMaxCells) {
+            g.cell = cell; g.inv = inv;
+            for (int a = 0; a < 3; a++) g.n[a] = (int)fn[a];
+            g.usable = 1;
+            break;
+        }
+        if (!isfinite(cell) || !(prod == prod)) break;
+        cell *= fmaxf(1.1f, cbrtf((float)(prod / (double)kGridMaxCells)) * 1.02f);
+    }
+    g.n_fin = 1;                                                          // counted by k_icp_grid_count; > 0 here
+    blk->g = g;
+}
+
+__device__ __forceinline__ int cell_of(const IcpGrid& g, const float4 t)
+{
+    const int cx = (int)floorf(cell_coord(t.x, g.lo[0], g.inv)), cy = (int)floorf(cell_coord(t.y, g.lo[1], g.inv));
+    const int cz = (int)floorf(cell_coord(t.z, g.lo[2], g.inv));
+    // inside by construction (n = cell of the box's upper corner + 1 by the same expression); the clamp only guards the stores
+    return (min(max(cz, 0), g.n[2] - 1) * g.n[1] + min(max(cy, 0), g.n[1] - 1)) * g.n[0] + min(max(cx, 0), g.n[0] - 1);
+}
+
+__global__ __launch_bounds__(256) void k_icp_grid_count(const float4* __restrict__ tgt, int n, const IcpDevBlock* blk, int* __restrict__ counts)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n || !blk->g.usable) return;
+    const float4 t = tgt[i];
+    if (!(isfinite(t.x) && isfinite(t.y) && isfinite(t.z))) return;
+    atomicAdd(&counts[cell_of(blk->g, t)], 1);
+}
+
+// exclusive scan of the cell counts in one workgroup: cstart[c] = first slot of cell c, cursor[c] the same (k_icp_grid_scatter
+// advances it to the cell's end, which is the next cell's start)
+__global__ __launch_bounds__(1024) void k_icp_grid_scan(IcpDevBlock* blk, const int* __restrict__ counts, int* __restrict__ cstart, int* __restrict__ cursor)
+{
+    __shared__ int sh[1024];
+    if (!blk->g.usable) return;
+    const int ncells = blk->g.n[0] * blk->g.n[1] * blk->g.n[2];
+    const int per = (ncells + 1023) / 1024;
+    const int c0 = min(threadIdx.x * per, ncells), c1 = min(c0 + per, ncells);
+    int sum = 0;
+    for (int c = c0; c < c1; c++) sum += counts[c];
+    sh[threadIdx.x] = sum;
+    __syncthreads();
+    for (int off = 1; off < 1024; off <<= 1) {
+        const int v = threadIdx.x >= off ? sh[threadIdx.x - off] : 0;
+        __syncthreads();
+        sh[threadIdx.x] += v;
+        __syncthreads();
+    }
+    int run = sh[threadIdx.x] - sum;
+    for (int c = c0; c < c1; c++) { cstart[c] = run; cursor[c] = run; run += counts[c]; }
+    if (threadIdx.x == 1023) blk->g.n_fin = sh[1023];
+}
+
+__global__ __launch_bounds__(256) void k_icp_grid_scatter(const float4* __restrict__ tgt, int n, const IcpDevBlock* blk, int* __restrict__ cursor,
+                                                          float4* __restrict__ sorted)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n || !blk->g.usable) return;
+    const float4 t = tgt[i];
+    if (!(isfinite(t.x) && isfinite(t.y) && isfinite(t.z))) return;
+    const int pos = atomicAdd(&cursor[cell_of(blk->g, t)], 1);             // the order inside a cell is arbitrary: the search takes a minimum
+    if (pos >= 0 && pos < n) sorted[pos] = make_float4(t.x, t.y, t.z, __int_as_float(i));
+}
+
+// the points of cells [x0, x1] of one grid row against p: the minimum of (d2, original index)
+__device__ __forceinline__ void grid_visit(const float4 p, const float4* __restrict__ sorted, int a, int b, float& bd, int& bi)
+{
+    for (int k = a; k < b; k++) {
+        const float4 t = sorted[k];
+        const float dx = p.x - t.x, dy = p.y - t.y, dz = p.z - t.z;
+        const float d = (dx * dx + dy * dy) + dz * dz;
+        const int idx = __float_as_int(t.w);
+        if (d < bd || (d == bd && idx < bi)) { bd = d; bi = idx; }
+    }
+}
+
+// A lower bound on the fp32 d2 of every target outside the cube of cells [q - r, q + r], or "none is outside" (returns true
+// with *all_in set). A target in a cell with index >= k along an axis has x - lo >= k * cell * (1 - kFaceSlack), one in a cell
+// with index < k has x - lo < k * cell * (1 + kFaceSlack); both sides are measured from the grid origin in
+// fp64, 1e-12 of their size is taken off for the fp64 roundings, and a gap below 1e-15 m counts as none (its square would be
+// subnormal in fp32).
+__device__ __forceinline__ bool grid_settled(const IcpGrid& g, const float4 p, const int q[3], int r, float bd, int bi)
+{
+    const float pc[3] = { p.x, p.y, p.z };
+    double bound = DBL_MAX;
+    bool all_in = true;
+#pragma unroll
+    for (int a = 0; a < 3; a++) {
+        const double off = (double)pc[a] - (double)g.lo[a];
+        const int hk = q[a] + r + 1, lk = q[a] - r;
+        if (hk <= g.n[a] - 1) {
+            all_in = false;
+            const double face = (double)hk * (double)g.cell;
+            double gap = face * (1.0 - kFaceSlack) - off;
+            gap -= 1e-12 * (fabs(off) + face);
+            if (!(gap >= 1e-15)) gap = 0.0;
+            bound = fmin(bound, gap * gap);
+        }
+        if (lk >= 1) {
+            all_in = false;
+            const double face = (double)lk * (double)g.cell;
+            double gap = off - face * (1.0 + kFaceSlack);
+            gap -= 1e-12 * (fabs(off) + face);
+            if (!(gap >= 1e-15)) gap = 0.0;
+            bound = fmin(bound, gap * gap);
+        }
+    }
+    if (all_in) return true;
+    return bi >= 0 && (double)bd < bound * (1.0 - kBoundSlack);
+}
+
+// exact 1-NN through the grid: one lane per source point. First the 3 x 3 x 3 cells around the (clamped) cell of the point, their
+// nine row ranges fetched before any point is read; then shells of growing Chebyshev radius up to shell_cap. A point that is not
+// settled by then, or lies more than shell_cap cells outside the box, goes to the fallback list.
+__global__ __launch_bounds__(kGridThreads) void k_icp_nn_grid(const float4* __restrict__ cur, int n_src, IcpDevBlock* blk,
+                                                              const int* __restrict__ cstart, const int* __restrict__ cend,
+                                                              const float4* __restrict__ sorted, unsigned long long* __restrict__ best,
+                                                              int* __restrict__ list, int shell_cap, int phase)
+{
+    if (done_guard(blk, phase)) return;
+    const int i = blockIdx.x * kGridThreads + threadIdx.x;
+    if (i >= n_src) return;
+    const float4 p = cur[i];
+    const IcpGrid g = blk->g;
+    if (!(isfinite(p.x) && isfinite(p.y) && isfinite(p.z)) || g.n_fin == 0) { best[i] = kNoMatch; return; }
+    const float f[3] = { cell_coord(p.x, g.lo[0], g.inv), cell_coord(p.y, g.lo[1], g.inv), cell_coord(p.z, g.lo[2], g.inv) };
+    const float reach = (float)shell_cap;
+    bool settled = false;
+    float bd = INFINITY;
+    int bi = -1;
+    bool near_box = g.usable != 0;
+#pragma unroll
+    for (int a = 0; a < 3; a++) near_box = near_box && (f[a] >= -reach) && (f[a] <= (float)g.n[a] + reach);
+    if (near_box) {
+        int q[3];
+#pragma unroll
+        for (int a = 0; a < 3; a++) q[a] = (int)fminf(fmaxf(floorf(f[a]), 0.0f), (float)(g.n[a] - 1));
+        const int nx = g.n[0], ny = g.n[1], nz = g.n[2];
+        {
+            const int x0 = max(q[0] - 1, 0), x1 = min(q[0] + 1, nx - 1);
+            int ra[9], rb[9];
+#pragma unroll
+            for (int j = 0; j < 9; j++) {
+                const int y = q[1] + (j % 3) - 1, z = q[2] + (j / 3) - 1;
+                const bool in = y >= 0 && y < ny && z >= 0 && z < nz;
+                const int row = in ? (z * ny + y) * nx : 0;
+                ra[j] = in ? cstart[row + x0] : 0;
+                rb[j] = in ? cend[row + x1] : 0;
+            }
+#pragma unroll
+            for (int j = 0; j < 9; j++) grid_visit(p, sorted, ra[j], rb[j], bd, bi);
+            settled = grid_settled(g, p, q, 1, bd, bi);
+        }
+        for (int r = 2; !settled && r <= shell_cap; r++) {
+            const int xl = q[0] - r, xh = q[0] + r;
+            const int x0 = max(xl, 0), x1 = min(xh, nx - 1);
+            for (int dz = -r; dz <= r; dz++) {
+                const int z = q[2] + dz;
+                if (z < 0 || z >= nz) continue;
+                for (int dy = -r; dy <= r; dy++) {
+                    const int y = q[1] + dy;
+                    if (y < 0 || y >= ny) continue;
+                    const int row = (z * ny + y) * nx;
+                    if (max(abs(dy), abs(dz)) == r) {
+                        grid_visit(p, sorted, cstart[row + x0], cend[row + x1], bd, bi);
+                    } else {
+                        if (xl >= 0) grid_visit(p, sorted, cstart[row + xl], cend[row + xl], bd, bi);
+                        if (xh < nx) grid_visit(p, sorted, cstart[row + xh], cend[row + xh], bd, bi);
+                    }
+                }
+            }
+            settled = grid_settled(g, p, q, r, bd, bi);
+        }
+    }
+    if (settled) {
+        best[i] = bi >= 0 ? (((unsigned long long)__float_as_uint(bd) << 32) | (unsigned)bi) : kNoMatch;
+    } else {
+        best[i] = kNoMatch;
+        const int k = atomicAdd(&blk->wl_count, 1);
+        if (k < n_src) list[k] = i;
+    }
+}
+
+__global__ __launch_bounds__(256) void k_icp_reset_dev(unsigned long long* __restrict__ best, int n, const IcpDevBlock* blk, int phase)
+{
+    if (done_guard(blk, phase)) return;
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) best[i] = kNoMatch;
+}
+
+// k_icp_nn for the sources a list names (list == nullptr: all of them, the device loop's brute-force search): workgroups past
+// the end of the list return at entry
+__global__ __launch_bounds__(kNnThreads) void k_icp_nn_list(const float4* __restrict__ cur, int n_src, const float4* __restrict__ tgt, int n_tgt,
+                                                            int slice_len, unsigned long long* __restrict__ best, const int* __restrict__ list,
+                                                            const IcpDevBlock* blk, int phase)
+{
+    __shared__ float4 tile[kNnTile];
+    if (done_guard(blk, phase)) return;
+    const int count = list ? min(blk->wl_count, n_src) : n_src;
+    if ((int)(blockIdx.x * kNnThreads) >= count) return;
+    const int w = blockIdx.x * kNnThreads + threadIdx.x;
+    const bool valid = w < count;
+    const int i = valid ? (list ? list[w] : w) : 0;
+    const float4 p = valid ? cur[i] : make_float4(0, 0, 0, 0);
+    const bool fin = valid && isfinite(p.x) && isfinite(p.y) && isfinite(p.z);
+    float bd = INFINITY;
+    int bi = -1;
+    const int j0 = blockIdx.y * slice_len, j1 = min(j0 + slice_len, n_tgt);
+    nn_tiles(p, fin, tgt, j0, j1, tile, bd, bi);
+    if (fin && bi >= 0)
+        atomicMin(&best[i], ((unsigned long long)__float_as_uint(bd) << 32) | (unsigned)bi);
+}
+
+__global__ __launch_bounds__(256) void k_icp_sums_dev(const float4* __restrict__ cur, int n_src, const float4* __restrict__ tgt,
+                                                      const unsigned long long* __restrict__ best, double max_d2, double* __restrict__ part,
+                                                      const IcpDevBlock* blk, int phase)
+{
+    __shared__ double sh[4][17];
+    if (done_guard(blk, phase)) return;
+    sums_body(cur, n_src, tgt, best, max_d2, part, sh);
+}
+
+__global__ __launch_bounds__(64) void k_icp_fold_dev(const double* __restrict__ part, int rows, IcpDevBlock* blk, int phase)
+{
+    if (done_guard(blk, phase)) return;
+    fold_body(part, rows, blk->sums);
+    if (threadIdx.x == 0) { blk->n_fallback = blk->wl_count; blk->wl_count = 0; }
+}
+
+// closes the iteration on the folded sums: one lane runs icp_close_step, the host loop's own source
+__global__ __launch_bounds__(64) void k_icp_close(IcpDevBlock* blk, IcpCloseParams prm)
+{
+    if (threadIdx.x != 0 || blk->st.done) return;
+    double S[17];
+    for (int k = 0; k < 17; k++) S[k] = blk->sums[k];
+    IcpLoopState st = blk->st;
+    icp_close_step(S, prm, &st);
+    blk->st = st;
+}
+
+// phase 0: the source moves by the step of the iteration just closed (not once the alignment has ended); phase 1: the reloaded
+// source moves by the final transformation
+__global__ __launch_bounds__(256) void k_icp_transform_dev(float4* __restrict__ cur, int n, const IcpDevBlock* blk, int phase)
+{
+    if (done_guard(blk, phase)) return;
+    transform_body(cur, n, phase == 0 ? blk->st.T_step : blk->st.T);
 }
 
 }  // namespace
@@ -166,13 +534,28 @@ __global__ __launch_bounds__(256) void k_icp_transform(float4* __restrict__ cur,
 struct IcpWorkspace {
     Buf cur, tgt, best, part, sums;
     double* h_sums = nullptr;            // pinned, 17 doubles
+    // the device loop: its block with a pinned mirror, the grid (cell counts, starts, ends, the targets sorted by cell), the
+    // fallback list, the event behind the work queued last, and what the host keeps about the alignment in flight
+    Buf blk, gcount, gstart, gend, gsorted, list;
+    IcpDevBlock* h_blk = nullptr;
+    hipEvent_t ev = nullptr;
+    struct Flight {
+        int phase = 0;                   // 0 none, 1 a range of iterations is queued, 2 the fitness pass is queued
+        int n_src = 0, n_tgt = 0, queued = 0;
+        const unsigned char* d_src = nullptr;
+        size_t stride = 0;
+        IcpParams prm{};
+        IcpTuning tune{};
+    } fl;
 };
 
 IcpWorkspace* icp_create()
 {
     IcpWorkspace* w = new (std::nothrow) IcpWorkspace();
     if (!w) return nullptr;
-    if (w->sums.ensure(sizeof(double) * 17) != hipSuccess || hipHostMalloc((void**)&w->h_sums, sizeof(double) * 17) != hipSuccess) {
+    if (w->sums.ensure(sizeof(double) * 17) != hipSuccess || hipHostMalloc((void**)&w->h_sums, sizeof(double) * 17) != hipSuccess ||
+        w->blk.ensure(sizeof(IcpDevBlock)) != hipSuccess || hipHostMalloc((void**)&w->h_blk, sizeof(IcpDevBlock)) != hipSuccess ||
+        hipEventCreateWithFlags(&w->ev, hipEventDisableTiming) != hipSuccess) {
         icp_destroy(w);
         return nullptr;
     }
@@ -182,9 +565,11 @@ IcpWorkspace* icp_create()
 void icp_destroy(IcpWorkspace* w)
 {
     if (!w) return;
-    Buf* bufs[] = { &w->cur, &w->tgt, &w->best, &w->part, &w->sums };
+    Buf* bufs[] = { &w->cur, &w->tgt, &w->best, &w->part, &w->sums, &w->blk, &w->gcount, &w->gstart, &w->gend, &w->gsorted, &w->list };
     for (Buf* b : bufs) if (b->p) (void)hipFree(b->p);
     if (w->h_sums) (void)hipHostFree(w->h_sums);
+    if (w->h_blk) (void)hipHostFree(w->h_blk);
+    if (w->ev) (void)hipEventDestroy(w->ev);
     delete w;
 }
 
@@ -192,13 +577,19 @@ void icp_destroy(IcpWorkspace* w)
 
 namespace {
 
-hipError_t nearest(IcpWorkspace* w, hipStream_t stream, int n_src, int n_tgt)
+void nn_shape(int n_src, int n_tgt, int* sb_out, int* slices_out, int* slice_len_out)
 {
     const int sb = (n_src + kNnThreads - 1) / kNnThreads;
     int slices = (1024 + sb - 1) / sb;                                   // ~1000 workgroups in flight
     slices = std::max(1, std::min(slices, (n_tgt + kNnTile - 1) / kNnTile));
     const int slice_len = (((n_tgt + slices - 1) / slices) + kNnTile - 1) / kNnTile * kNnTile;
-    slices = (n_tgt + slice_len - 1) / slice_len;
+    *sb_out = sb; *slices_out = (n_tgt + slice_len - 1) / slice_len; *slice_len_out = slice_len;
+}
+
+hipError_t nearest(IcpWorkspace* w, hipStream_t stream, int n_src, int n_tgt)
+{
+    int sb, slices, slice_len;
+    nn_shape(n_src, n_tgt, &sb, &slices, &slice_len);
     hipLaunchKernelGGL(k_icp_reset, dim3((n_src + 255) / 256), dim3(256), 0, stream, w->best.as<unsigned long long>(), n_src);
     hipLaunchKernelGGL(k_icp_nn, dim3(sb, slices), dim3(kNnThreads), 0, stream, (const float4*)w->cur.as<float4>(), n_src,
                        (const float4*)w->tgt.as<float4>(), n_tgt, slice_len, w->best.as<unsigned long long>());
@@ -217,7 +608,205 @@ hipError_t sums(IcpWorkspace* w, hipStream_t stream, int n_src, double max_d2)
     return hipStreamSynchronize(stream);
 }
 
+hipError_t ensure_clouds(IcpWorkspace* w, size_t n_src, size_t n_tgt)
+{
+    ICP_TRY(w->cur.ensure(sizeof(float4) * n_src)); ICP_TRY(w->tgt.ensure(sizeof(float4) * n_tgt));
+    ICP_TRY(w->best.ensure(sizeof(unsigned long long) * n_src));
+    return w->part.ensure(sizeof(double) * 17 * (size_t)std::min(((int)n_src + 255) / 256, kSumBlocks));
+}
+
+// the device loop's buffers, the block reset, and with the grid on: box, shape, counts, scan, scatter - once per alignment
+hipError_t dev_prepare(IcpWorkspace* w, hipStream_t stream, int n_src, int n_tgt, const IcpTuning& tune)
+{
+    ICP_TRY(w->list.ensure(sizeof(int) * (size_t)n_src));
+    IcpDevBlock* blk = w->blk.as<IcpDevBlock>();
+    hipLaunchKernelGGL(k_icp_begin, dim3(1), dim3(64), 0, stream, blk);
+    if (tune.use_grid) {
+        ICP_TRY(w->gcount.ensure(sizeof(int) * kGridMaxCells)); ICP_TRY(w->gstart.ensure(sizeof(int) * kGridMaxCells));
+        ICP_TRY(w->gend.ensure(sizeof(int) * kGridMaxCells)); ICP_TRY(w->gsorted.ensure(sizeof(float4) * (size_t)n_tgt));
+        ICP_TRY(hipMemsetAsync(w->gcount.p, 0, sizeof(int) * kGridMaxCells, stream));
+        const float4* tgt = w->tgt.as<float4>();
+        const int tb = (n_tgt + 255) / 256;
+        hipLaunchKernelGGL(k_icp_grid_bbox, dim3(std::min(tb, 256)), dim3(256), 0, stream, tgt, n_tgt, blk);
+        hipLaunchKernelGGL(k_icp_grid_setup, dim3(1), dim3(64), 0, stream, blk, tune.cell);
+        hipLaunchKernelGGL(k_icp_grid_count, dim3(tb), dim3(256), 0, stream, tgt, n_tgt, (const IcpDevBlock*)blk, w->gcount.as<int>());
+        hipLaunchKernelGGL(k_icp_grid_scan, dim3(1), dim3(1024), 0, stream, blk, (const int*)w->gcount.as<int>(), w->gstart.as<int>(), w->gend.as<int>());
+        hipLaunchKernelGGL(k_icp_grid_scatter, dim3(tb), dim3(256), 0, stream, tgt, n_tgt, (const IcpDevBlock*)blk, w->gend.as<int>(), w->gsorted.as<float4>());
+    }
+    return hipGetLastError();
+}
+
+// one search of the device loop: the grid with its fallback, or (use_grid off) the brute force over every source
+hipError_t dev_nearest(IcpWorkspace* w, hipStream_t stream, int n_src, int n_tgt, const IcpTuning& tune, int phase)
+{
+    int sb, slices, slice_len;
+    nn_shape(n_src, n_tgt, &sb, &slices, &slice_len);
+    IcpDevBlock* blk = w->blk.as<IcpDevBlock>();
+    const float4* cur = w->cur.as<float4>();
+    const float4* tgt = w->tgt.as<float4>();
+    unsigned long long* best = w->best.as<unsigned long long>();
+    if (tune.use_grid) {
+        hipLaunchKernelGGL(k_icp_nn_grid, dim3((n_src + kGridThreads - 1) / kGridThreads), dim3(kGridThreads), 0, stream, cur, n_src, blk,
+                           (const int*)w->gstart.as<int>(), (const int*)w->gend.as<int>(), (const float4*)w->gsorted.as<float4>(), best,
+                           w->list.as<int>(), std::max(1, tune.shell_cap), phase);
+        hipLaunchKernelGGL(k_icp_nn_list, dim3(sb, slices), dim3(kNnThreads), 0, stream, cur, n_src, tgt, n_tgt, slice_len, best,
+                           (const int*)w->list.as<int>(), (const IcpDevBlock*)blk, phase);
+    } else {
+        hipLaunchKernelGGL(k_icp_reset_dev, dim3((n_src + 255) / 256), dim3(256), 0, stream, best, n_src, (const IcpDevBlock*)blk, phase);
+        hipLaunchKernelGGL(k_icp_nn_list, dim3(sb, slices), dim3(kNnThreads), 0, stream, cur, n_src, tgt, n_tgt, slice_len, best,
+                           (const int*)nullptr, (const IcpDevBlock*)blk, phase);
+    }
+    return hipGetLastError();
+}
+
+hipError_t dev_sums(IcpWorkspace* w, hipStream_t stream, int n_src, double max_d2, int phase)
+{
+    const int rows = std::min((n_src + 255) / 256, kSumBlocks);
+    IcpDevBlock* blk = w->blk.as<IcpDevBlock>();
+    hipLaunchKernelGGL(k_icp_sums_dev, dim3(rows), dim3(256), 0, stream, (const float4*)w->cur.as<float4>(), n_src,
+                       (const float4*)w->tgt.as<float4>(), (const unsigned long long*)w->best.as<unsigned long long>(), max_d2,
+                       w->part.as<double>(), (const IcpDevBlock*)blk, phase);
+    hipLaunchKernelGGL(k_icp_fold_dev, dim3(1), dim3(64), 0, stream, (const double*)w->part.as<double>(), rows, blk, phase);
+    return hipGetLastError();
+}
+
+// the block to the host and the event the host tests: the end of everything queued so far
+hipError_t dev_mark(IcpWorkspace* w, hipStream_t stream)
+{
+    ICP_TRY(hipMemcpyAsync(w->h_blk, w->blk.p, sizeof(IcpDevBlock), hipMemcpyDeviceToHost, stream));
+    return hipEventRecord(w->ev, stream);
+}
+
+hipError_t dev_queue_range(IcpWorkspace* w, hipStream_t stream)
+{
+    IcpWorkspace::Flight& f = w->fl;
+    const int n = std::min(kIcpRange, f.prm.max_iter - f.queued);
+    const IcpCloseParams cp = icp_close_params(f.prm.max_iter, f.prm.trans_eps, f.prm.fit_eps);
+    const double max_d2 = f.prm.max_corr_dist * f.prm.max_corr_dist;
+    IcpDevBlock* blk = w->blk.as<IcpDevBlock>();
+    for (int k = 0; k < n; k++) {
+        ICP_TRY(dev_nearest(w, stream, f.n_src, f.n_tgt, f.tune, 0));
+        ICP_TRY(dev_sums(w, stream, f.n_src, max_d2, 0));
+        hipLaunchKernelGGL(k_icp_close, dim3(1), dim3(64), 0, stream, blk, cp);
+        hipLaunchKernelGGL(k_icp_transform_dev, dim3((f.n_src + 255) / 256), dim3(256), 0, stream, w->cur.as<float4>(), f.n_src, (const IcpDevBlock*)blk, 0);
+        ICP_TRY(hipGetLastError());
+    }
+    f.queued += n;
+    return dev_mark(w, stream);
+}
+
+// getFitnessScore(): the original source under the final transformation, nearest distances with no limit
+hipError_t dev_queue_fitness(IcpWorkspace* w, hipStream_t stream)
+{
+    IcpWorkspace::Flight& f = w->fl;
+    hipLaunchKernelGGL(k_icp_load, dim3((f.n_src + 255) / 256), dim3(256), 0, stream, f.d_src, f.stride, f.n_src, w->cur.as<float4>());
+    hipLaunchKernelGGL(k_icp_transform_dev, dim3((f.n_src + 255) / 256), dim3(256), 0, stream, w->cur.as<float4>(), f.n_src,
+                       (const IcpDevBlock*)w->blk.as<IcpDevBlock>(), 1);
+    ICP_TRY(dev_nearest(w, stream, f.n_src, f.n_tgt, f.tune, 1));
+    ICP_TRY(dev_sums(w, stream, f.n_src, DBL_MAX, 1));
+    return dev_mark(w, stream);
+}
+
 }  // namespace
+
+void icp_dev_cancel(IcpWorkspace* w) { w->fl.phase = 0; }
+
+hipError_t icp_dev_begin(IcpWorkspace* w, hipStream_t stream, const unsigned char* d_src, size_t n_src_, const unsigned char* d_tgt,
+                         size_t n_tgt_, size_t stride, const IcpParams& prm, const IcpTuning& tune)
+{
+    const int n_src = (int)n_src_, n_tgt = (int)n_tgt_;
+    if (w->fl.phase != 0 || n_src <= 0 || n_tgt <= 0 || prm.max_iter < 1) return hipErrorInvalidValue;
+    ICP_TRY(ensure_clouds(w, n_src_, n_tgt_));
+    hipLaunchKernelGGL(k_icp_load, dim3((n_src + 255) / 256), dim3(256), 0, stream, d_src, stride, n_src, w->cur.as<float4>());
+    hipLaunchKernelGGL(k_icp_load, dim3((n_tgt + 255) / 256), dim3(256), 0, stream, d_tgt, stride, n_tgt, w->tgt.as<float4>());
+    ICP_TRY(hipGetLastError());
+    ICP_TRY(dev_prepare(w, stream, n_src, n_tgt, tune));
+    IcpWorkspace::Flight& f = w->fl;
+    f = IcpWorkspace::Flight{};
+    f.n_src = n_src; f.n_tgt = n_tgt; f.d_src = d_src; f.stride = stride; f.prm = prm; f.tune = tune;
+    ICP_TRY(dev_queue_range(w, stream));
+    f.phase = 1;
+    return hipSuccess;
+}
+
+hipError_t icp_dev_advance(IcpWorkspace* w, hipStream_t stream, bool wait, bool* done, IcpResult* res)
+{
+    IcpWorkspace::Flight& f = w->fl;
+    *done = false;
+    if (f.phase == 0) return hipErrorInvalidValue;
+    for (;;) {
+        if (wait) {
+            const hipError_t e = hipEventSynchronize(w->ev);
+            if (e != hipSuccess) { f.phase = 0; return e; }
+        } else {
+            const hipError_t e = hipEventQuery(w->ev);
+            if (e == hipErrorNotReady) { (void)hipGetLastError(); return hipSuccess; }
+            if (e != hipSuccess) { f.phase = 0; return e; }
+        }
+        hipError_t e = hipSuccess;
+        if (f.phase == 1) {
+            if (w->h_blk->st.done) { e = dev_queue_fitness(w, stream); f.phase = 2; }
+            else if (f.queued >= f.prm.max_iter) e = hipErrorUnknown;     // max_iter closes end every alignment: not reached
+            else e = dev_queue_range(w, stream);
+            if (e != hipSuccess) { f.phase = 0; return e; }
+            if (!wait) return hipSuccess;
+            continue;
+        }
+        const IcpDevBlock& b = *w->h_blk;
+        memcpy(res->T, b.st.T, sizeof(res->T));
+        res->converged = b.st.conv; res->iterations = b.st.it;
+        res->fitness = b.sums[0] > 0 ? b.sums[1] / b.sums[0] : DBL_MAX;
+        f.phase = 0;
+        *done = true;
+        return hipSuccess;
+    }
+}
+
+hipError_t icp_dev_nearest(IcpWorkspace* w, hipStream_t stream, const unsigned char* d_src, size_t n_src_, const unsigned char* d_tgt,
+                           size_t n_tgt_, size_t stride, int mode, const IcpTuning& tune_, unsigned long long* keys, int* n_fallback,
+                           int reps, float* us_build, float* us_search)
+{
+    const int n_src = (int)n_src_, n_tgt = (int)n_tgt_;
+    if (w->fl.phase != 0 || n_src <= 0 || n_tgt <= 0) return hipErrorInvalidValue;
+    ICP_TRY(ensure_clouds(w, n_src_, n_tgt_));
+    hipLaunchKernelGGL(k_icp_load, dim3((n_src + 255) / 256), dim3(256), 0, stream, d_src, stride, n_src, w->cur.as<float4>());
+    hipLaunchKernelGGL(k_icp_load, dim3((n_tgt + 255) / 256), dim3(256), 0, stream, d_tgt, stride, n_tgt, w->tgt.as<float4>());
+    ICP_TRY(hipGetLastError());
+    IcpTuning tune = tune_;
+    const bool grid = tune.use_grid != 0;
+    hipEvent_t e0 = nullptr, e1 = nullptr, e2 = nullptr;
+    const bool timed = reps > 0;
+    hipError_t e = hipSuccess;
+    if (timed) {
+        e = hipEventCreate(&e0);
+        if (e == hipSuccess) e = hipEventCreate(&e1);
+        if (e == hipSuccess) e = hipEventCreate(&e2);
+        if (e == hipSuccess) e = hipEventRecord(e0, stream);
+    }
+    if (e == hipSuccess && mode != 0) e = dev_prepare(w, stream, n_src, n_tgt, tune);
+    if (e == hipSuccess && timed) e = hipEventRecord(e1, stream);
+    for (int r = 0; e == hipSuccess && r < std::max(1, reps); r++) {
+        if (mode == 0) e = nearest(w, stream, n_src, n_tgt);
+        else {
+            if (r > 0) hipLaunchKernelGGL(k_icp_fold_dev, dim3(1), dim3(64), 0, stream, (const double*)w->part.as<double>(), 0, w->blk.as<IcpDevBlock>(), 1);   // (zeroes the list count)
+            e = dev_nearest(w, stream, n_src, n_tgt, tune, 1);
+        }
+    }
+    if (e == hipSuccess && timed) e = hipEventRecord(e2, stream);
+    if (e == hipSuccess && mode != 0) e = hipMemcpyAsync(w->h_blk, w->blk.p, sizeof(IcpDevBlock), hipMemcpyDeviceToHost, stream);
+    if (e == hipSuccess && keys) e = hipMemcpyAsync(keys, w->best.p, sizeof(unsigned long long) * n_src_, hipMemcpyDeviceToHost, stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(stream);
+    if (e == hipSuccess && timed) {
+        float a = 0, b = 0;
+        e = hipEventElapsedTime(&a, e0, e1);
+        if (e == hipSuccess) e = hipEventElapsedTime(&b, e1, e2);
+        if (us_build) *us_build = a * 1000.0f;
+        if (us_search) *us_search = b * 1000.0f / (float)reps;
+    }
+    for (hipEvent_t ev : { e0, e1, e2 }) if (ev) (void)hipEventDestroy(ev);
+    if (n_fallback) *n_fallback = (mode != 0 && grid && e == hipSuccess) ? w->h_blk->wl_count : 0;
+    return e;
+}
 
 hipError_t icp_align(IcpWorkspace* w, hipStream_t stream, const unsigned char* d_src, size_t n_src_, const unsigned char* d_tgt,
                      size_t n_tgt_, size_t stride, const IcpParams& prm, IcpResult* res)
@@ -226,55 +815,31 @@ hipError_t icp_align(IcpWorkspace* w, hipStream_t stream, const unsigned char* d
     for (int i = 0; i < 16; i++) res->T[i] = (i % 5 == 0) ? 1.0f : 0.0f;
     res->converged = 0; res->iterations = 0; res->fitness = DBL_MAX;
     if (n_src == 0 || n_tgt == 0) return hipSuccess;
-    ICP_TRY(w->cur.ensure(sizeof(float4) * n_src_)); ICP_TRY(w->tgt.ensure(sizeof(float4) * n_tgt_));
-    ICP_TRY(w->best.ensure(sizeof(unsigned long long) * n_src_));
-    ICP_TRY(w->part.ensure(sizeof(double) * 17 * (size_t)std::min((n_src + 255) / 256, kSumBlocks)));
+    ICP_TRY(ensure_clouds(w, n_src_, n_tgt_));
     hipLaunchKernelGGL(k_icp_load, dim3((n_src + 255) / 256), dim3(256), 0, stream, d_src, stride, n_src, w->cur.as<float4>());
     hipLaunchKernelGGL(k_icp_load, dim3((n_tgt + 255) / 256), dim3(256), 0, stream, d_tgt, stride, n_tgt, w->tgt.as<float4>());
     ICP_TRY(hipGetLastError());
 
-    // icp.hpp computeTransformation + default_convergence_criteria.hpp hasConverged
+    // icp.hpp computeTransformation + default_convergence_criteria.hpp hasConverged: icp_close_step, between two synchronisations
     const double max_d2 = prm.max_corr_dist * prm.max_corr_dist;
-    const double rot_thr = 1.0 - prm.trans_eps, trl_thr = prm.trans_eps, mse_abs = 1e-12, mse_rel = prm.fit_eps;
-    const int max_similar = 0;                                            // max_iterations_similar_transforms_
-    double prev_mse = DBL_MAX;
-    int it = 0, conv = 0, similar = 0;
+    const IcpCloseParams cp = icp_close_params(prm.max_iter, prm.trans_eps, prm.fit_eps);
+    IcpLoopState st;
+    icp_state_init(&st);
     for (;;) {
         ICP_TRY(nearest(w, stream, n_src, n_tgt));
         ICP_TRY(sums(w, stream, n_src, max_d2));
-        const double* S = w->h_sums;
-        const double cnt = S[0];
-        if (cnt < 3.0) { conv = 0; break; }                               // min_number_correspondences_
-        const double mse = S[1] / cnt;
-        float ms[3], mt[3], sg[9];
-        for (int d = 0; d < 3; d++) { ms[d] = (float)(S[2 + d] / cnt); mt[d] = (float)(S[5 + d] / cnt); }
-        for (int r = 0; r < 3; r++)
-            for (int c = 0; c < 3; c++) sg[r * 3 + c] = (float)(S[8 + r * 3 + c] / cnt - (S[5 + r] / cnt) * (S[2 + c] / cnt));
-        float T[16];
-        host_umeyama(ms, mt, sg, T);
-        Mat34 T34;
-        memcpy(T34.m, T, sizeof(float) * 12);
-        hipLaunchKernelGGL(k_icp_transform, dim3((n_src + 255) / 256), dim3(256), 0, stream, w->cur.as<float4>(), n_src, T34);
-        ICP_TRY(hipGetLastError());
-        float F[16];
-        for (int r = 0; r < 4; r++)
-            for (int c = 0; c < 4; c++) {
-                float a = 0;
-                for (int k = 0; k < 4; k++) a += T[r * 4 + k] * res->T[k * 4 + c];
-                F[r * 4 + c] = a;
-            }
-        memcpy(res->T, F, sizeof(F));
-        ++it;
-        int is_similar = 0;
-        if (it >= prm.max_iter) { conv = 1; break; }                      // CONVERGENCE_CRITERIA_ITERATIONS
-        const double cos_angle = 0.5 * ((double)T[0] + (double)T[5] + (double)T[10] - 1.0);
-        const double tsq = (double)T[3] * T[3] + (double)T[7] * T[7] + (double)T[11] * T[11];
-        if (cos_angle >= rot_thr && tsq <= trl_thr) { if (similar >= max_similar) { conv = 1; break; } is_similar = 1; }
-        if (std::fabs(mse - prev_mse) < mse_abs) { if (similar >= max_similar) { conv = 1; break; } is_similar = 1; }
-        if (std::fabs(mse - prev_mse) / prev_mse < mse_rel) { if (similar >= max_similar) { conv = 1; break; } is_similar = 1; }
-        similar = is_similar ? similar + 1 : 0;
-        prev_mse = mse;
+        const int it_before = st.it;
+        icp_close_step(w->h_sums, cp, &st);
+        if (st.it != it_before) {                                         // (not on the `fewer than 3 correspondences` exit)
+            Mat34 T34;
+            memcpy(T34.m, st.T_step, sizeof(float) * 12);
+            hipLaunchKernelGGL(k_icp_transform, dim3((n_src + 255) / 256), dim3(256), 0, stream, w->cur.as<float4>(), n_src, T34);
+            ICP_TRY(hipGetLastError());
+        }
+        if (st.done) break;
     }
+    memcpy(res->T, st.T, sizeof(res->T));
+    const int conv = st.conv, it = st.it;
     // getFitnessScore(): the original source under the final transform, mean squared nearest distance
     hipLaunchKernelGGL(k_icp_load, dim3((n_src + 255) / 256), dim3(256), 0, stream, d_src, stride, n_src, w->cur.as<float4>());
     Mat34 F34;

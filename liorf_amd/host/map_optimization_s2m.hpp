@@ -439,7 +439,8 @@ public:
     }
 
     // Loop closure against the resident key-frame store (:542-844): no host key-frame clouds and no kdtreeHistoryKeyPoses.
-    // Every call runs under the lock the scan handler holds (one handle, calls not concurrent). GTSAM stays here: an
+    // Every call runs under the lock the scan handler holds (one handle, calls not concurrent); the launched forms below hold it
+    // up to the size gate only. GTSAM stays here: an
     // accepted result gives loopIndexQueue / loopPoseQueue / loopNoiseQueue as poseFrom.between(poseTo) of pose_from and
     // pose_to, with the noise from icp.fitness_score (RS) or the robust model (SC).
     float historyKeyframeSearchTimeDiff = 30.0f;      // include/utility.h:246
@@ -465,6 +466,37 @@ public:
     {
         const s2m_loop_params p = loopParams();
         check(s2m_loop_closure_rs(h_, timeLaserInfoCur, &p, &lastLoop), "s2m_loop_closure_rs");
+        return accepted();
+    }
+
+    // The launched forms (loopClosureThread, :506-622, beside laserCloudInfoHandler): the launch runs detection, submaps and the
+    // size gate and queues the whole ICP on the handle's loop stream; the handle is free for the scan handler meanwhile. The
+    // loop thread takes the scan handler's lock, launches, releases; then lock, loopPoll(), release, sleep - until loopPending()
+    // is false. s2m_loop_align, s2m_loop_closure_rs, s2m_loop_near_keyframes and s2m_icp_align are S2M_ERR_BUSY in between.
+    // Return value: a closure is pending (false: lastLoop is final - none, closed, too few points).
+    bool performRSLoopClosureLaunch()
+    {
+        const s2m_loop_params p = loopParams();
+        check(s2m_loop_closure_rs_launch(h_, timeLaserInfoCur, &p, &lastLoop), "s2m_loop_closure_rs_launch");
+        return loopPending();
+    }
+    bool loopAlignLaunch(int key_cur, int key_pre, int base_key = -1)
+    {
+        const s2m_loop_params p = loopParams();
+        check(s2m_loop_align_launch(h_, key_cur, key_pre, base_key, &p, &lastLoop), "s2m_loop_align_launch");
+        return loopPending();
+    }
+    bool loopPending() const { return lastLoop.status == S2M_LOOP_PENDING; }
+    // never waits for the device; true once the closure has ended and was accepted (lastLoop holds the result either way)
+    bool loopPoll()
+    {
+        check(s2m_loop_poll(h_, &lastLoop), "s2m_loop_poll");
+        return accepted();
+    }
+    // waits for the pending closure; true if it was accepted
+    bool loopCollect()
+    {
+        check(s2m_loop_collect(h_, &lastLoop), "s2m_loop_collect");
         return accepted();
     }
 

@@ -12,7 +12,7 @@
 //   s2m_harness --keyframes scans.bin scans.txt map_leaf scan_leaf density
 //       a scripted trajectory through extractSurroundingKeyFrames() -> downsampleCurrentScan() ->
 //       scan2MapOptimization() -> saveKeyFrame() on the resident key-frame store; prints every pose.
-//   s2m_harness --loop keys.bin keys.txt scan_leaf search_radius search_num icp_leaf fitness_score
+//   s2m_harness --loop keys.bin keys.txt scan_leaf search_radius search_num icp_leaf fitness_score [--async]
 //       a scripted revisit through downsampleCurrentScan() -> saveKeyFrame() -> makeAndSaveScancontextAndKeys() ->
 //       performRSLoopClosure() -> performSCLoopClosure() on the resident key-frame store; prints every loop result.
 //   s2m_harness --global-map keys.bin keys.txt scan_leaf search_radius pose_density leaf out.bin
@@ -137,8 +137,9 @@ static void print_loop(const char* what, int i, const s2m_loop_result& r)
 // "n_points time x y z roll pitch yaw" per key frame, the raw clouds back to back in keys.bin. Every key runs
 // downsampleCurrentScan() -> saveKeyFrame() -> makeAndSaveScancontextAndKeys() at its pose, then performRSLoopClosure() at its
 // time and performSCLoopClosure(); prints "rs <i> ..." and "sc <i> ..." for every key, then "near <n>" for
-// loopFindNearKeyframes(last key, search_num, -1).
-static int run_loop(char** argv)
+// loopFindNearKeyframes(last key, search_num, -1). --async: the RS closure is launched (performRSLoopClosureLaunch) and polled,
+// the scan downsampled again between two polls as the scan handler would go on working; the lines printed are the same.
+static int run_loop(char** argv, bool async)
 {
     liorf_amd::MapOptimizationS2M node;
     liorf_amd::SCManagerS2M sc(node.handle());
@@ -164,7 +165,16 @@ static int run_loop(char** argv)
         for (int k = 0; k < 6; k++) node.transformTobeMapped[k] = rpyxyz[k];
         node.saveKeyFrame();
         sc.makeAndSaveScancontextAndKeys(node.laserCloudSurfLastDS);
-        node.performRSLoopClosure();
+        if (async) {
+            long polls = 0;
+            for (bool pending = node.performRSLoopClosureLaunch(); pending; pending = node.loopPending(), polls++) {
+                node.downsampleCurrentScan();
+                node.loopPoll();
+            }
+            std::fprintf(stderr, "rs %d polls %ld\n", i, polls);
+        } else {
+            node.performRSLoopClosure();
+        }
         print_loop("rs", i, node.lastLoop);
         node.performSCLoopClosure(sc);
         print_loop("sc", i, node.lastLoop);
@@ -429,7 +439,8 @@ int main(int argc, char** argv)
         if (argc == 13 && std::string(argv[1]) == "--chain") return run_chain(argv);
         if (argc >= 10 && std::string(argv[1]) == "--many") return run_many(argc, argv);
         if (argc == 7 && std::string(argv[1]) == "--keyframes") return run_keyframes(argv);
-        if (argc == 9 && std::string(argv[1]) == "--loop") return run_loop(argv);
+        if (argc == 9 && std::string(argv[1]) == "--loop") return run_loop(argv, false);
+        if (argc == 10 && std::string(argv[1]) == "--loop" && std::string(argv[9]) == "--async") return run_loop(argv, true);
         if (argc == 9 && std::string(argv[1]) == "--global-map") return run_global_map(argv);
         if (argc == 7 && std::string(argv[1]) == "--pose-graph") return run_pose_graph(argv);
         if (argc == 12 && std::string(argv[1]) == "--project") return run_project(argv);

@@ -21,8 +21,9 @@ LIB_PATH = os.environ.get("S2M_LIB") or os.path.join(_HERE, "libliorf_s2m.so")  
 
 S2M_OK = 0
 S2M_ERR_CAPACITY = -5
+S2M_ERR_BUSY = -6
 ERRORS = {-1: "S2M_ERR_INVALID_ARG", -2: "S2M_ERR_NO_DEVICE", -3: "S2M_ERR_HIP", -4: "S2M_ERR_NO_SCAN",
-          -5: "S2M_ERR_CAPACITY"}
+          -5: "S2M_ERR_CAPACITY", -6: "S2M_ERR_BUSY"}
 
 # every symbol include/liorf_s2m.h declares
 ABI_SYMBOLS = [
@@ -39,6 +40,8 @@ ABI_SYMBOLS = [
     "s2m_sc_reset", "s2m_sc_size", "s2m_sc_add_scan", "s2m_sc_add_descriptor", "s2m_sc_detect_loop", "s2m_sc_distance",
     "s2m_kf_default_params", "s2m_kf_reset", "s2m_kf_size", "s2m_kf_add", "s2m_kf_set_poses", "s2m_extract_surrounding",
     "s2m_loop_default_params", "s2m_loop_near_keyframes", "s2m_loop_align", "s2m_loop_closure_rs",
+    "s2m_loop_align_launch", "s2m_loop_closure_rs_launch", "s2m_loop_poll", "s2m_loop_collect",
+    "s2m_debug_icp_nearest", "s2m_debug_icp_time_nearest", "s2m_debug_icp_align_device", "s2m_debug_icp_tuning",
     "s2m_gmap_default_params", "s2m_global_map", "s2m_kf_map_cloud",
     "s2m_scan_layout_preset", "s2m_project_default_params", "s2m_imu_deskew_info", "s2m_project_check_args", "s2m_project_scan",
     "s2m_downsample_projected", "s2m_sc_add_projected",
@@ -53,6 +56,8 @@ S2M_SENSOR_VELODYNE, S2M_SENSOR_LIVOX, S2M_SENSOR_OUSTER, S2M_SENSOR_MULRAN, S2M
 S2M_IMU_QUEUE_LENGTH = 2000
 S2M_KF_FROM_HOST, S2M_KF_FROM_DEVICE, S2M_KF_FROM_LAST_DOWNSAMPLE = 0, 1, 2
 S2M_LOOP_NONE, S2M_LOOP_ALREADY_CLOSED, S2M_LOOP_TOO_FEW_POINTS, S2M_LOOP_REJECTED, S2M_LOOP_ACCEPTED = 0, 1, 2, 3, 4
+S2M_LOOP_PENDING = 5                                     # a launched closure whose ICP is still queued or running
+S2M_ICP_RANGE = 8                                        # iterations the device loop queues at a time (liorf_s2m_debug.h)
 S2M_WARN_LEAF_TOO_SMALL = 1
 S2M_PG_PRIOR, S2M_PG_BETWEEN, S2M_PG_GPS, S2M_PG_INITIAL = 0, 1, 2, 3
 S2M_PG_BLOCK_COLUMNS = 24                                # right-hand sides per pass of the block solve
@@ -279,6 +284,14 @@ def load_library(path: str | None = None) -> C.CDLL:
     L.s2m_loop_near_keyframes.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, C.c_float, vp, C.c_size_t, C.c_size_t, szp]
     L.s2m_loop_align.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, C.POINTER(LoopParams), C.POINTER(LoopResult)]
     L.s2m_loop_closure_rs.argtypes = [vp, C.c_double, C.POINTER(LoopParams), C.POINTER(LoopResult)]
+    L.s2m_loop_align_launch.argtypes = L.s2m_loop_align.argtypes
+    L.s2m_loop_closure_rs_launch.argtypes = L.s2m_loop_closure_rs.argtypes
+    L.s2m_loop_poll.argtypes = [vp, C.POINTER(LoopResult)]
+    L.s2m_loop_collect.argtypes = [vp, C.POINTER(LoopResult)]
+    L.s2m_debug_icp_nearest.argtypes = [vp, vp, C.c_size_t, vp, C.c_size_t, C.c_size_t, C.c_int32, vp, C.POINTER(C.c_int32)]
+    L.s2m_debug_icp_time_nearest.argtypes = [vp, vp, C.c_size_t, vp, C.c_size_t, C.c_size_t, C.c_int32, C.c_int32, vp, C.POINTER(C.c_int32), fp, fp]
+    L.s2m_debug_icp_align_device.argtypes = [vp, vp, C.c_size_t, vp, C.c_size_t, C.c_size_t, C.POINTER(IcpParams), C.POINTER(IcpResult)]
+    L.s2m_debug_icp_tuning.argtypes = [vp, C.c_float, C.c_int32, C.c_int32]
     L.s2m_gmap_default_params.argtypes = [C.POINTER(GmapParams)]
     L.s2m_global_map.argtypes = [vp, C.POINTER(GmapParams), vp, C.c_size_t, C.c_size_t, szp, i32p, C.c_size_t, szp]
     L.s2m_kf_map_cloud.argtypes = [vp, C.c_int, C.c_int, C.c_float, vp, C.c_size_t, C.c_size_t, szp]
@@ -1031,6 +1044,67 @@ class MapOptimizationS2M:
         pp = C.byref(params) if params is not None else None
         self._check(self.lib.s2m_loop_closure_rs(self.h, float(timeLaserInfoCur), pp, C.byref(r)), "s2m_loop_closure_rs")
         return r
+
+    # -- the launched forms: the ICP runs on the handle's loop stream while the handle registers scans -----------
+    def loopAlignLaunch(self, key_cur: int, key_pre: int, base_key: int = -1, params: LoopParams | None = None) -> LoopResult:
+        """s2m_loop_align_launch: loopAlign up to the size gate; status S2M_LOOP_PENDING when the ICP was queued, else the
+        final result (nothing pending). loopPoll() / loopCollect() bring the result."""
+        r = LoopResult()
+        pp = C.byref(params) if params is not None else None
+        self._check(self.lib.s2m_loop_align_launch(self.h, key_cur, key_pre, base_key, pp, C.byref(r)), "s2m_loop_align_launch")
+        return r
+
+    def performRSLoopClosureLaunch(self, timeLaserInfoCur: float, params: LoopParams | None = None) -> LoopResult:
+        """s2m_loop_closure_rs_launch: performRSLoopClosure() with the ICP queued instead of waited for."""
+        r = LoopResult()
+        pp = C.byref(params) if params is not None else None
+        self._check(self.lib.s2m_loop_closure_rs_launch(self.h, float(timeLaserInfoCur), pp, C.byref(r)), "s2m_loop_closure_rs_launch")
+        return r
+
+    def loopPoll(self) -> LoopResult:
+        """s2m_loop_poll: never waits for the device. S2M_LOOP_PENDING, the final result, or S2M_LOOP_NONE with nothing pending.
+        The loop thread: lock, loopPoll(), unlock, sleep - until the status is not S2M_LOOP_PENDING."""
+        r = LoopResult()
+        self._check(self.lib.s2m_loop_poll(self.h, C.byref(r)), "s2m_loop_poll")
+        return r
+
+    def loopCollect(self) -> LoopResult:
+        """s2m_loop_collect: loopPoll() with waits - the final result of the pending closure."""
+        r = LoopResult()
+        self._check(self.lib.s2m_loop_collect(self.h, C.byref(r)), "s2m_loop_collect")
+        return r
+
+    def debugIcpNearest(self, src, tgt, mode: int, reps: int = 0):
+        """s2m_debug_icp_nearest / s2m_debug_icp_time_nearest: (keys uint64 per source point, n_fallback[, us_build, us_search]);
+        mode 0 = k_icp_nn, mode 1 = the grid search with its fallback."""
+        a, na, st = _records(src)
+        b, nb, st2 = _records(tgt)
+        if st != st2:
+            raise ValueError("both clouds must share one record stride")
+        keys = np.zeros(max(na, 1), np.uint64)
+        nf, ub, us = C.c_int32(0), C.c_float(0), C.c_float(0)
+        self._check(self.lib.s2m_debug_icp_time_nearest(self.h, a.ctypes.data, na, b.ctypes.data, nb, st, mode, reps, keys.ctypes.data,
+                                                        C.byref(nf), C.byref(ub), C.byref(us)), "s2m_debug_icp_time_nearest")
+        return (keys[:na], nf.value) if reps == 0 else (keys[:na], nf.value, ub.value, us.value)
+
+    def debugIcpAlignDevice(self, cureKeyframeCloud, prevKeyframeCloud, **params):
+        """s2m_debug_icp_align_device: icpAlign() by the device loop (no size gate): (T 4x4, hasConverged, getFitnessScore, iterations)."""
+        a, na, st = _records(cureKeyframeCloud)
+        b, nb, st2 = _records(prevKeyframeCloud)
+        if st != st2:
+            raise ValueError("both clouds must share one record stride")
+        p = IcpParams()
+        self.lib.s2m_icp_default_params(C.byref(p))
+        for k, v in params.items():
+            setattr(p, k, v)
+        r = IcpResult()
+        self._check(self.lib.s2m_debug_icp_align_device(self.h, a.ctypes.data, na, b.ctypes.data, nb, st, C.byref(p), C.byref(r)),
+                    "s2m_debug_icp_align_device")
+        return np.array(r.T, np.float32).reshape(4, 4), bool(r.converged), r.fitness_score, r.iterations
+
+    def debugIcpTuning(self, cell_in_leaves: float = 0.0, shell_cap: int = 0, use_grid: int = -1):
+        """s2m_debug_icp_tuning: the grid's cell edge (in leaves), the shell cap, grid on / off for what follows (0, 0, -1 = built in)."""
+        self._check(self.lib.s2m_debug_icp_tuning(self.h, cell_in_leaves, shell_cap, use_grid), "s2m_debug_icp_tuning")
 
     def performSCLoopClosure(self, params: LoopParams | None = None) -> LoopResult:
         """performSCLoopClosure() (reference :624-730): the ScanContext detector on this handle's SC store, then

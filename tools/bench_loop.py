@@ -16,6 +16,15 @@ search radius 15 m, search_num 25, ICP leaf 0.5, fitness 0.3, time window 30 s. 
   detect_ms            s2m_loop_closure_rs on a store whose newest key has no candidate (detection alone)
 
   python tools/bench_loop.py                           one JSON line
+  python tools/bench_loop.py --async                   the same line, and profiles/loop_async_bench_line.json (--async-out) with
+                                                       the launched closure on the same stores:
+    held_ms              (a) time the handle is held: s2m_loop_closure_rs_launch plus every s2m_loop_poll until the result, polled
+                         every --poll-us microseconds (launch_ms, polls, polls_ms), against loop_closure_rs_ms of the same run
+    latency_ms           (b) launch to result, polled in that rhythm, and latency_tight_ms polled back to back
+    search_us            (c) device time of one nearest-neighbour search of the two submaps (HIP events, s2m_debug_icp_time_nearest):
+                         k_icp_nn against the grid at several cell edges and shell caps, with the grid's build time and n_fallback
+    registration_ms      (d) the early-exit registration of bench.py's scans (set_scan + optimize on host records) on this
+                         handle, with and without a closure pending
   python tools/bench_loop.py --kernel-stats stats.csv  folds the k_loop_detect* and k_icp* rows of a rocprofv3
                                                        --kernel-trace --stats run into the JSON line
 """
@@ -81,14 +90,97 @@ def _stats(path):
     return rows
 
 
+def _async_row(eng, s2m, a, time_cur, rej, sync_ms, kc, kp, scans):
+    """The launched closure on a filled store (fitness -1: every repetition runs the whole ICP and is rejected)."""
+    r = s2m.LoopResult()
+    lib, h = eng.lib, eng.h
+    pending, rejected = s2m.S2M_LOOP_PENDING, s2m.S2M_LOOP_REJECTED
+
+    def closure(poll_s):
+        t0 = time.perf_counter()
+        rc = lib.s2m_loop_closure_rs_launch(h, time_cur, C.byref(rej), C.byref(r))
+        t1 = time.perf_counter()
+        assert rc == 0 and r.status == pending, (rc, r.status)
+        held, polls = t1 - t0, 0
+        while r.status == pending:
+            if poll_s > 0:
+                time.sleep(poll_s)
+            p0 = time.perf_counter()
+            rc = lib.s2m_loop_poll(h, C.byref(r))
+            held += time.perf_counter() - p0
+            polls += 1
+            assert rc == 0
+        assert r.status == rejected
+        return t1 - t0, held, polls, time.perf_counter() - t0
+
+    rows = {"loop_closure_rs_ms": sync_ms, "poll_us": a.poll_us}
+    for name, poll_s in (("paced", a.poll_us * 1e-6), ("tight", 0.0)):
+        runs = [closure(poll_s) for _ in range(a.warmup + a.reps)][a.warmup:]
+        med = lambda k: round(1e3 * float(np.median([x[k] for x in runs])), 4)
+        if name == "paced":
+            rows.update(launch_ms=med(0), held_ms=med(1), polls=int(np.median([x[2] for x in runs])), latency_ms=med(3))
+            rows["polls_ms"] = round(rows["held_ms"] - rows["launch_ms"], 4)
+        else:
+            rows.update(latency_tight_ms=med(3), polls_tight=int(np.median([x[2] for x in runs])), held_tight_ms=med(1))
+    rows["iterations"] = r.icp.iterations
+    rows["ranges"] = -(-r.icp.iterations // s2m.S2M_ICP_RANGE)
+    # (c) one search of the two submaps: the brute force, then the grid over cell edges (metres) and shell caps
+    cur = eng.loopFindNearKeyframes(kc, 0, -1, 0.5)
+    prev = eng.loopFindNearKeyframes(kp, 25, -1, 0.5)
+    _, _, _, us0 = eng.debugIcpNearest(cur, prev, 0, reps=20)
+    search = {"n_cur": int(cur.shape[0]), "n_prev": int(prev.shape[0]), "k_icp_nn_us": round(us0, 2), "grid": []}
+    for cell_m in (0.5, 0.75, 1.0, 1.5, 2.0):
+        for cap in (2, 3, 4):
+            eng.debugIcpTuning(cell_m / 0.3, cap, 1)              # (the debug calls take the edge in units of the default leaf, 0.3)
+            _, nf, ub, us = eng.debugIcpNearest(cur, prev, 1, reps=20)
+            search["grid"].append({"cell_m": cell_m, "shell_cap": cap, "search_us": round(us, 2), "build_us": round(ub, 2), "n_fallback": nf})
+    eng.debugIcpTuning()
+    rows["search_us"] = search
+    # (d) registration with and without a closure pending
+    if scans:
+        m, cfgs = scans
+        eng.setInputCloud(m)
+        reg = {}
+        for name in ("no_closure", "closure_pending"):
+            ts = []
+            for j in range(3 + 4 * len(cfgs)):
+                k = j % len(cfgs)
+                if name == "closure_pending":
+                    rc = lib.s2m_loop_closure_rs_launch(h, time_cur, C.byref(rej), C.byref(r))
+                    assert rc == 0 and r.status == pending
+                t0 = time.perf_counter()
+                eng.setScan(cfgs[k][0])
+                eng.transformTobeMapped = cfgs[k][1].copy()
+                eng.scan2MapOptimization()
+                ts.append(time.perf_counter() - t0)
+                if name == "closure_pending":
+                    still = lib.s2m_loop_poll(h, C.byref(r)) == 0 and r.status == pending
+                    reg["still_pending_after_registration"] = reg.get("still_pending_after_registration", 0) + int(still)
+                    eng.loopCollect()
+            reg[name + "_ms"] = round(1e3 * float(np.median(ts[3:])), 4)
+        reg["registrations"] = 4 * len(cfgs)
+        rows["registration_ms"] = reg
+    return rows
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--sizes", default="5000,50000")
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--reps", type=int, default=10)
     ap.add_argument("--kernel-stats", default="", help="rocprofv3 kernel_stats.csv of a run of this tool")
+    ap.add_argument("--async", dest="run_async", action="store_true", help="also measure the launched closure (see above)")
+    ap.add_argument("--async-out", default=os.path.join(ROOT, "profiles", "loop_async_bench_line.json"))
+    ap.add_argument("--poll-us", type=float, default=200.0, help="sleep between two polls of the paced run")
     a = ap.parse_args(argv)
     from liorf_amd import s2m
+    async_out = {"workload": "tools/bench_loop.py --async: the revisit of the synchronous line, the closure launched and polled",
+                 "icp_range": s2m.S2M_ICP_RANGE, "sizes": {}}
+    scans = None
+    if a.run_async:
+        from liorf_amd import synth
+        cfgs = [synth.make_config("kitti64", scan_index=k) for k in range(4)]
+        scans = (synth.to_xyzi(cfgs[0]["map"]), [(synth.to_xyzi(c["scan"]), c["pose_init"]) for c in cfgs])
 
     sizes = [int(s) for s in a.sizes.split(",")]
     out = {"workload": "revisit: 30 000-point frames at keys 0..27 and the last key, 1 000 points elsewhere; R 15, search_num 25, "
@@ -114,6 +206,8 @@ def main(argv=None):
         r = s2m.LoopResult()
         ms = _median_ms(lambda: eng.lib.s2m_loop_closure_rs(eng.h, float(times[-1]), C.byref(rej), C.byref(r)), a.warmup, a.reps)
         rej_status = r.status
+        if a.run_async:
+            async_out["sizes"][str(n)] = _async_row(eng, s2m, a, float(times[-1]), rej, ms, r.key_cur, r.key_pre, scans)
         t0 = time.perf_counter()                       # then the accepted call, once: it records the closure
         acc = eng.performRSLoopClosure(times[-1], prm)
         accepted_ms = 1e3 * (time.perf_counter() - t0)
@@ -148,6 +242,11 @@ def main(argv=None):
         out["kernels_device_us"] = _stats(a.kernel_stats)
     out["note"] = "wall clock, median after warm-up; every call ends with the library's own synchronisation"
     print(json.dumps(out))
+    if a.run_async:
+        async_out["note"] = ("wall clock on the host, medians after warm-up; search_us are HIP-event times on the loop stream; the closure is "
+                             "timed with fitness_score = -1 (rejected after the whole ICP)")
+        with open(a.async_out, "w") as f:
+            f.write(json.dumps(async_out) + "\n")
 
 
 if __name__ == "__main__":
