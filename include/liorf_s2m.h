@@ -40,7 +40,8 @@ extern "C" {
 #define S2M_ERR_HIP           -3   /* a HIP runtime call failed (see s2m_last_error) */
 #define S2M_ERR_NO_SCAN       -4   /* *_resident call without s2m_set_scan          */
 #define S2M_ERR_CAPACITY      -5   /* grid / buffer limit exceeded                   */
-#define S2M_ERR_BUSY          -6   /* a launched loop closure is pending and this call needs its buffers */
+#define S2M_ERR_BUSY          -6   /* a launched loop closure is pending and this call needs its buffers, or a launched
+                                      pose-graph optimise is pending and this call needs the estimates it is working on */
 #define S2M_WARN_LEAF_TOO_SMALL 1   /* voxel filter: PCL's "leaf size is too small" case, output = input */
 
 /* ScanContext descriptor shape (reference include/Scancontext.h:82-84) */
@@ -779,6 +780,41 @@ int  s2m_pg_set_initial(s2m_handle h, int32_t key, const float pose_xyzrpy[6]);
  * initial value. The variances are those of s2m_pg_default_params. */
 int  s2m_pg_add_odometry(s2m_handle h, const float pose_xyzrpy[6]);
 int  s2m_pg_optimize(s2m_handle h, const s2m_pg_params* p /* NULL = defaults */, s2m_pg_result* out /* may be NULL */);
+/* The optimise beside the scan handler: launch, poll, collect. s2m_pg_optimize stays as it is and is the yardstick.
+ *   s2m_pg_optimize_launch does everything s2m_pg_optimize does before its first kernel (parameter, chain and initial-value
+ *       checks, uploads, device tables); every error is the synchronous call's, with nothing pending and the graph as it was.
+ *       An empty graph returns S2M_OK with the synchronous result in `early` and nothing pending. Otherwise the solve is
+ *       queued on a stream of the handle's own - the lowest priority the device offers, never the priority of the handle's
+ *       stream; it may share a hardware queue with the loop-closure stream - behind the launch's uploads, and the call returns
+ *       S2M_PG_PENDING without waiting: `early` holds n_variables, n_factors, robust_weight_min = 1 and zeros elsewhere. The
+ *       pending solve is over the N_l variables and F_l factors of that moment. The launch brings the library's host mirror of
+ *       the estimates up to date first; no later call reads the device's estimates while the solve runs.
+ *   s2m_pg_optimize_poll never waits for the device: it tests an event. While the queued work runs it returns S2M_PG_PENDING
+ *       and does not write *out. The Gauss-Newton loop's decisions (keep or reject a step, the two convergence tests, the
+ *       counts) are taken on the device and the solve is queued a range at a time; a poll that finds a range ended and the
+ *       solve not, queues the next range and returns S2M_PG_PENDING. The poll that finds the solve ended delivers the result
+ *       once: S2M_OK with *out bytewise what s2m_pg_optimize returns for the same graph, estimates and params, and the device
+ *       estimates of variables 0..N_l-1 bit for bit what it leaves. After that, and whenever nothing is pending: S2M_PG_IDLE,
+ *       *out not written.
+ *   s2m_pg_optimize_collect is the same with waits: S2M_OK with the final result, or S2M_PG_IDLE.
+ *   While an optimise is pending: s2m_pg_size, s2m_pg_add_odometry (it chains on the launch-time estimate of the last
+ *       variable), s2m_pg_add_prior / _between / _gps on any keys (the new factors are not part of the pending solve) and
+ *       s2m_pg_set_initial for keys >= N_l work on host state and do not wait. s2m_pg_optimize, a second launch,
+ *       s2m_pg_get_poses, s2m_pg_marginal, s2m_pg_marginals, s2m_pg_joint_marginal, s2m_pg_apply_to_store and
+ *       s2m_pg_set_initial for a key < N_l return S2M_ERR_BUSY and touch nothing. s2m_pg_reset and s2m_destroy wait for the
+ *       stream and drop the pending solve. Every call outside s2m_pg_* works as before and returns the bits it returns
+ *       without a pending optimise (a launched loop closure may be pending at the same time); a call that has to grow a
+ *       device buffer may wait for the solve.
+ *   The tail: when the result is delivered with iterations > 0 (and only then), every variable k >= N_l that has a value is
+ *       re-based on the host in fp64 by the correction of variable a = N_l - 1: with A its launch-time state and A' its
+ *       state after the solve, D_R = A'_R A_R^T, D_t = A'_t - D_R A_t, X_R <- D_R X_R, X_t <- D_R X_t + D_t
+ *       (s2m_debug_pg_rebase in liorf_s2m_debug.h is this rule). With only odometry factors added meanwhile that is the exact
+ *       optimum of the grown graph; with loops or GPS added meanwhile it is the next optimise's initial value. */
+#define S2M_PG_PENDING 2   /* positive, like S2M_WARN_LEAF_TOO_SMALL: an optimise is queued or running */
+#define S2M_PG_IDLE    3   /* poll / collect with nothing pending; *out is not written */
+int  s2m_pg_optimize_launch(s2m_handle h, const s2m_pg_params* p /* NULL = defaults */, s2m_pg_result* early /* may be NULL */);
+int  s2m_pg_optimize_poll(s2m_handle h, s2m_pg_result* out);      /* never waits for the device */
+int  s2m_pg_optimize_collect(s2m_handle h, s2m_pg_result* out);   /* waits */
 /* The current estimates of variables first .. first+count-1 as floats; S2M_ERR_INVALID_ARG outside the graph or for a
  * variable of that range without a value. */
 int  s2m_pg_get_poses(s2m_handle h, int32_t first, int32_t count, float* xyzrpy);

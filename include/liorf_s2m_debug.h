@@ -133,6 +133,13 @@ int  s2m_debug_icp_align_device(s2m_handle h, const void* src, size_t n_src, con
  * use_grid (0 = brute force only, 1 = grid, < 0 = built in). */
 int  s2m_debug_icp_tuning(s2m_handle h, float cell_in_leaves, int32_t shell_cap, int32_t use_grid);
 
+/* ---- the tail rule of a launched pose-graph optimise (s2m_pg_optimize_launch) ------------------------------------------
+ * Host code, no handle, no GPU, and the code the library runs when a launched optimise delivers its result: states are 12
+ * doubles (R row-major, then t); with D = a_now a_launch^-1, X <- D X, i.e. D_R = A'_R A_R^T, D_t = A'_t - D_R A_t,
+ * X_R <- D_R X_R, X_t <- D_R X_t + D_t, every three-term sum taken as ((a0 b0 + a1 b1) + a2 b2) with no fused products.
+ * S2M_OK, or S2M_ERR_INVALID_ARG for a null pointer. */
+int  s2m_debug_pg_rebase(const double a_launch[12], const double a_now[12], double X[12]);
+
 #ifdef __cplusplus
 }
 #endif

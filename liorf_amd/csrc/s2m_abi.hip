@@ -747,6 +747,7 @@ int s2m_destroy(s2m_handle h)
     (void)hipSetDevice(h->device);
     if (h->stream) (void)hipStreamSynchronize(h->stream);
     loop_drop_pending(h, true);                                                         // (a launched loop closure uses the loop buffers)
+    pg_drop_pending(h, true);                                                           // (a launched optimise uses the pose graph's)
     for (hipStream_t st : h->batch.branch_streams) (void)hipStreamSynchronize(st);      // (slot work in flight uses the slots' buffers)
     if (h->gmap.copy_stream) (void)hipStreamSynchronize(h->gmap.copy_stream);
     for (s2m_context* k : h->batch.kids) (void)s2m_destroy(k);

@@ -2,6 +2,7 @@
 // the Gauss-Newton loop around s2m_pose_graph.hip's kernels, the marginal, and correctPoses() into the key-frame store.
 #include <algorithm>
 #include <cmath>
+#include <cstdio>
 #include <cstring>
 
 #include "s2m_context.hpp"
@@ -39,6 +40,37 @@ int s2m_pg_check_args(int32_t kind, int32_t n_variables, int32_t key_a, int32_t 
         if (key_b < 0 || key_b > n_variables || key_a == key_b) return S2M_ERR_INVALID_ARG;
     }
     return S2M_OK;                  // (key_a != key_b and both <= n_variables: at most one of them is new)
+}
+
+// The tail rule of a launched optimise: X <- D X with D = a_now a_launch^-1, every three-term sum as ((a0 b0 + a1 b1) + a2 b2).
+int s2m_debug_pg_rebase(const double a_launch[12], const double a_now[12], double X[12])
+{
+    if (!a_launch || !a_now || !X) return S2M_ERR_INVALID_ARG;
+    double D[12], O[12];
+    for (int i = 0; i < 3; i++)                             // D_R = A'_R A_R^T
+        for (int j = 0; j < 3; j++)
+            D[i * 3 + j] = (a_now[i * 3] * a_launch[j * 3] + a_now[i * 3 + 1] * a_launch[j * 3 + 1]) + a_now[i * 3 + 2] * a_launch[j * 3 + 2];
+    for (int i = 0; i < 3; i++)                             // D_t = A'_t - D_R A_t
+        D[9 + i] = a_now[9 + i] - ((D[i * 3] * a_launch[9] + D[i * 3 + 1] * a_launch[10]) + D[i * 3 + 2] * a_launch[11]);
+    for (int i = 0; i < 3; i++) {
+        for (int j = 0; j < 3; j++) O[i * 3 + j] = (D[i * 3] * X[j] + D[i * 3 + 1] * X[3 + j]) + D[i * 3 + 2] * X[6 + j];
+        O[9 + i] = ((D[i * 3] * X[9] + D[i * 3 + 1] * X[10]) + D[i * 3 + 2] * X[11]) + D[9 + i];
+    }
+    std::copy(O, O + 12, X);
+    return S2M_OK;
+}
+
+void s2m::host::pg_drop_pending(s2m_context* h, bool destroy)
+{
+    auto& g = h->pg;
+    if (g.stream) (void)hipStreamSynchronize(g.stream);
+    g.pending = false;
+    if (!destroy) return;
+    if (g.ev_ready) (void)hipEventDestroy(g.ev_ready);
+    if (g.ev_range) (void)hipEventDestroy(g.ev_range);
+    if (g.stream) (void)hipStreamDestroy(g.stream);
+    if (g.h_rec) (void)hipHostFree(g.h_rec);
+    g.ev_ready = g.ev_range = nullptr; g.stream = nullptr; g.h_rec = nullptr;
 }
 
 namespace {
@@ -323,12 +355,85 @@ PgFactor make_factor(int type, int32_t i, int32_t j, const double X[12], const d
     return f;
 }
 
+// ---- the launched optimise ----
+constexpr int kPgCgChunk = 24;          // CG iterations per segment: the chunk s2m_pg_optimize reads its stop flag after
+constexpr int kPgRangeSegments = 2;     // segments queued at a time; between two ranges the host looks at the record once
+
+int pg_busy(s2m_context* h)
+{
+    return h->pg.pending ? fail(h, S2M_ERR_BUSY, "a launched pose-graph optimise is pending: s2m_pg_optimize_poll / s2m_pg_optimize_collect it first") : S2M_OK;
+}
+
+// The pose-graph stream: the lowest priority the device offers, as the loop stream, so that the solve yields to the
+// registration kernels. A device that reports no range (or an error) gives a stream of the default priority; that is said
+// once on stderr.
+int pg_stream(s2m_context* h)
+{
+    auto& g = h->pg;
+    if (!g.stream) {
+        int least = 0, greatest = 0;
+        const hipError_t e = hipDeviceGetStreamPriorityRange(&least, &greatest);
+        if (e != hipSuccess || least == greatest) {
+            (void)hipGetLastError();
+            fprintf(stderr, "liorf_s2m: no stream priority range on device %d (%s): the pose-graph stream runs at the default priority\n",
+                    h->device, e != hipSuccess ? hipGetErrorString(e) : "least == greatest");
+            S2M_HIP(h, hipStreamCreateWithFlags(&g.stream, hipStreamNonBlocking));
+        } else {
+            S2M_HIP(h, hipStreamCreateWithPriority(&g.stream, hipStreamNonBlocking, least));
+        }
+    }
+    if (!g.ev_ready) S2M_HIP(h, hipEventCreateWithFlags(&g.ev_ready, hipEventDisableTiming));
+    if (!g.ev_range) S2M_HIP(h, hipEventCreateWithFlags(&g.ev_range, hipEventDisableTiming));
+    if (!g.h_rec) S2M_HIP(h, hipHostMalloc((void**)&g.h_rec, sizeof(PgRecord)));
+    return S2M_OK;
+}
+
+// one range: segments, the record to pinned memory, the event a poll tests
+int queue_range(s2m_context* h)
+{
+    auto& g = h->pg;
+    PgRecord* rec = g.rec.as<PgRecord>();
+    for (int k = 0; k < kPgRangeSegments; k++)
+        S2M_HIP(h, pg_async_segment(g.stream, g.dev, rec, g.pend_prm.cg_rel_tol, g.pend_max_cg, std::min(kPgCgChunk, g.pend_max_cg)));
+    S2M_HIP(h, hipMemcpyAsync(g.h_rec, rec, sizeof(PgRecord), hipMemcpyDeviceToHost, g.stream));
+    S2M_HIP(h, hipEventRecord(g.ev_range, g.stream));
+    return S2M_OK;
+}
+
+// The range in flight has ended: the next one, or the result and the tail rule. Host memory only.
+int advance(s2m_context* h, s2m_pg_result* out)
+{
+    auto& g = h->pg;
+    const PgRecord& r = *g.h_rec;
+    if (!r.done) {
+        const int rc = queue_range(h);
+        if (rc) { pg_drop_pending(h, false); return rc; }
+        return S2M_PG_PENDING;
+    }
+    g.pending = false;
+    s2m_pg_result res{};
+    res.iterations = r.iterations; res.inner_iterations = r.inner_iterations; res.converged = r.converged;
+    res.n_variables = (int32_t)g.n_l; res.n_factors = (int32_t)g.f_l;
+    res.error_before = r.error_before; res.error_after = r.error_after; res.robust_weight_min = r.wmin;
+    if (r.iterations > 0) {
+        g.dev_newer = true;
+        for (size_t k = g.n_l; k < pg_n(h); k++) {          // variables added since the launch follow the last one of the solve
+            if (!g.has_init[k]) continue;
+            (void)s2m_debug_pg_rebase(g.a_launch, r.A, g.X.data() + 12 * k);
+            g.dirty[k] = 1;
+        }
+    }
+    if (out) *out = res;
+    return S2M_OK;
+}
+
 }  // namespace
 
 int s2m_pg_reset(s2m_handle h)
 {
     if (!h) return S2M_ERR_INVALID_ARG;
     auto& g = h->pg;
+    if (g.pending) { (void)hipSetDevice(h->device); pg_drop_pending(h, false); }
     g.factors.clear(); g.X.clear(); g.has_init.clear(); g.dirty.clear();
     g.dev_newer = false; g.topo_dirty = true; g.n_dev = 0;
     return S2M_OK;
@@ -376,6 +481,7 @@ int s2m_pg_set_initial(s2m_handle h, int32_t key, const float pose_xyzrpy[6])
     if (!h) return S2M_ERR_INVALID_ARG;
     if (s2m_pg_check_args(S2M_PG_INITIAL, (int32_t)pg_n(h), key, 0, pose_xyzrpy, nullptr, 0.0))
         return fail(h, S2M_ERR_INVALID_ARG, "initial value: finite pose, key in 0..N");
+    if (h->pg.pending && (size_t)key < h->pg.n_l) return pg_busy(h);
     if (pg_n(h) + 1 >= kPgMaxVars) return fail(h, S2M_ERR_CAPACITY, "pose graph full (2^24 variables)");
     touch(h, key);
     pose_to_state(pose_xyzrpy, h->pg.X.data() + 12 * (size_t)key);
@@ -397,7 +503,7 @@ int s2m_pg_add_odometry(s2m_handle h, const float pose_xyzrpy[6])
         return s2m_pg_set_initial(h, 0, pose_xyzrpy);
     }
     if (!h->pg.has_init[(size_t)n - 1]) return fail(h, S2M_ERR_INVALID_ARG, "odometry: the last variable has no value");
-    if ((rc = host_current(h))) return rc;
+    if (!h->pg.pending && (rc = host_current(h))) return rc;   // (pending: the mirror is current since the launch)
     const double* L = h->pg.X.data() + 12 * (size_t)(n - 1);
     double Xn[12], Z[12];
     pose_to_state(pose_xyzrpy, Xn);
@@ -415,6 +521,7 @@ int s2m_pg_add_odometry(s2m_handle h, const float pose_xyzrpy[6])
 int s2m_pg_optimize(s2m_handle h, const s2m_pg_params* p, s2m_pg_result* out)
 {
     if (!h) return S2M_ERR_INVALID_ARG;
+    if (h->pg.pending) return pg_busy(h);
     s2m_pg_params prm;
     if (p) prm = *p; else s2m_pg_default_params(&prm);
     if (!params_ok(prm)) return fail(h, S2M_ERR_INVALID_ARG, "pose-graph params: iteration counts and tolerances must be >= 0 and finite");
@@ -458,9 +565,67 @@ int s2m_pg_optimize(s2m_handle h, const s2m_pg_params* p, s2m_pg_result* out)
     return S2M_OK;
 }
 
+int s2m_pg_optimize_launch(s2m_handle h, const s2m_pg_params* p, s2m_pg_result* early)
+{
+    if (!h) return S2M_ERR_INVALID_ARG;
+    if (h->pg.pending) return pg_busy(h);
+    s2m_pg_params prm;
+    if (p) prm = *p; else s2m_pg_default_params(&prm);
+    if (!params_ok(prm)) return fail(h, S2M_ERR_INVALID_ARG, "pose-graph params: iteration counts and tolerances must be >= 0 and finite");
+    s2m_pg_result res{};
+    res.robust_weight_min = 1.0;
+    res.n_variables = (int32_t)pg_n(h);
+    res.n_factors = (int32_t)h->pg.factors.size();
+    if (pg_n(h) == 0) { if (early) *early = res; return S2M_OK; }
+    auto& g = h->pg;
+    int rc;
+    if ((rc = host_current(h)) || (rc = prepare(h))) return rc;      // from here on the host needs nothing the device holds
+    if ((rc = pg_stream(h)) || (rc = ensure(h, g.rec, sizeof(PgRecord)))) return rc;
+    const PgDev& d = g.dev;
+    g.n_l = pg_n(h); g.f_l = g.factors.size();
+    g.pend_prm = prm;
+    g.pend_max_cg = d.n_extra == 0 ? 1 : prm.cg_max_iterations > 0 ? prm.cg_max_iterations : 6 * d.n_extra + 20;   // as run_cg
+    std::copy(g.X.begin() + 12 * (g.n_l - 1), g.X.begin() + 12 * g.n_l, g.a_launch);
+    S2M_HIP(h, hipEventRecord(g.ev_ready, h->stream));               // behind the uploads of prepare()
+    S2M_HIP(h, hipStreamWaitEvent(g.stream, g.ev_ready, 0));
+    hipError_t e = pg_async_open(g.stream, d, g.rec.as<PgRecord>(), prm.max_iterations, prm.absolute_error_tol, prm.relative_error_tol);
+    if (e == hipSuccess && (rc = queue_range(h)) == S2M_OK) {
+        g.pending = true;
+        if (early) *early = res;
+        return S2M_PG_PENDING;
+    }
+    pg_drop_pending(h, false);                                       // what was queued ends; nothing stays pending
+    return e != hipSuccess ? fail(h, S2M_ERR_HIP, "pg_async_open", e) : rc;
+}
+
+int s2m_pg_optimize_poll(s2m_handle h, s2m_pg_result* out)
+{
+    if (!h) return S2M_ERR_INVALID_ARG;
+    if (!h->pg.pending) return S2M_PG_IDLE;
+    S2M_HIP(h, hipSetDevice(h->device));
+    const hipError_t e = hipEventQuery(h->pg.ev_range);
+    if (e == hipErrorNotReady) { (void)hipGetLastError(); return S2M_PG_PENDING; }   // (not an error of the launches that follow)
+    if (e != hipSuccess) { pg_drop_pending(h, false); return fail(h, S2M_ERR_HIP, "hipEventQuery(pose-graph range)", e); }
+    return advance(h, out);
+}
+
+int s2m_pg_optimize_collect(s2m_handle h, s2m_pg_result* out)
+{
+    if (!h) return S2M_ERR_INVALID_ARG;
+    if (!h->pg.pending) return S2M_PG_IDLE;
+    S2M_HIP(h, hipSetDevice(h->device));
+    for (;;) {
+        const hipError_t e = hipEventSynchronize(h->pg.ev_range);
+        if (e != hipSuccess) { pg_drop_pending(h, false); return fail(h, S2M_ERR_HIP, "hipEventSynchronize(pose-graph range)", e); }
+        const int rc = advance(h, out);
+        if (rc != S2M_PG_PENDING) return rc;
+    }
+}
+
 int s2m_pg_get_poses(s2m_handle h, int32_t first, int32_t count, float* xyzrpy)
 {
     if (!h) return S2M_ERR_INVALID_ARG;
+    if (h->pg.pending) return pg_busy(h);
     if (first < 0 || count < 0 || (size_t)first + (size_t)count > pg_n(h) || (count > 0 && !xyzrpy))
         return fail(h, S2M_ERR_INVALID_ARG, "pose range outside the pose graph");
     if (count == 0) return S2M_OK;
@@ -476,6 +641,7 @@ int s2m_pg_get_poses(s2m_handle h, int32_t first, int32_t count, float* xyzrpy)
 int s2m_pg_marginal(s2m_handle h, int32_t key, double cov[36])
 {
     if (!h) return S2M_ERR_INVALID_ARG;
+    if (h->pg.pending) return pg_busy(h);
     if (key < 0 || (size_t)key >= pg_n(h) || !cov) return fail(h, S2M_ERR_INVALID_ARG, "marginal: key outside the pose graph");
     int rc = prepare(h);
     if (rc) return rc;
@@ -508,6 +674,7 @@ int s2m_pg_marginals_check_args(int32_t n_variables, const int32_t* keys, int32_
 int s2m_pg_marginals(s2m_handle h, const int32_t* keys, int32_t n_keys, double* cov)
 {
     if (!h) return S2M_ERR_INVALID_ARG;
+    if (h->pg.pending) return pg_busy(h);
     if (s2m_pg_marginals_check_args((int32_t)pg_n(h), keys, n_keys) || (n_keys > 0 && !cov))
         return fail(h, S2M_ERR_INVALID_ARG, "marginals: a key outside the pose graph, or a null array");
     if (n_keys == 0) return S2M_OK;
@@ -536,6 +703,7 @@ int s2m_pg_marginals(s2m_handle h, const int32_t* keys, int32_t n_keys, double* 
 int s2m_pg_joint_marginal(s2m_handle h, int32_t key_a, int32_t key_b, double cov[144])
 {
     if (!h) return S2M_ERR_INVALID_ARG;
+    if (h->pg.pending) return pg_busy(h);
     const int32_t keys[2] = { key_a, key_b };
     if (s2m_pg_marginals_check_args((int32_t)pg_n(h), keys, 2) || key_a == key_b || !cov)
         return fail(h, S2M_ERR_INVALID_ARG, "joint marginal: two different keys of the pose graph");
@@ -559,6 +727,7 @@ int s2m_pg_joint_marginal(s2m_handle h, int32_t key_a, int32_t key_b, double cov
 int s2m_pg_apply_to_store(s2m_handle h, int32_t first, int32_t count)
 {
     if (!h) return S2M_ERR_INVALID_ARG;
+    if (h->pg.pending) return pg_busy(h);
     if (first < 0 || count < 0 || (size_t)first + (size_t)count > pg_n(h) || (size_t)first + (size_t)count > h->kf.time.size())
         return fail(h, S2M_ERR_INVALID_ARG, "pose range outside the pose graph or the key-frame store");
     if (count == 0) return S2M_OK;

@@ -231,6 +231,18 @@ struct __attribute__((visibility("hidden"))) s2m_context {
         DevBuf blk_vecs, blk_loc[2], blk_partial, blk_sc, blk_rows;   // the block solve's columns (s2m_pg_marginals, s2m_pg_joint_marginal)
         s2m::PgScalars* h_sc = nullptr;            // pinned
         s2m::PgDev dev{};
+        // the launched optimise (s2m_pg_optimize_launch): the stream its solve runs on (lowest priority, created at the first
+        // launch), the event on the handle's stream behind the launch's uploads, the event behind the range in flight, the
+        // record on the device and its pinned copy (written at the end of every range), and what the result needs from launch time
+        hipStream_t stream = nullptr;
+        hipEvent_t ev_ready = nullptr, ev_range = nullptr;
+        DevBuf rec;
+        s2m::PgRecord* h_rec = nullptr;            // pinned
+        bool pending = false;
+        size_t n_l = 0, f_l = 0;                   // variables and factors of the pending solve
+        s2m_pg_params pend_prm{};
+        int pend_max_cg = 0;
+        double a_launch[12] = { 0 };               // variable n_l - 1 at launch
     } pg;
 };
 
@@ -310,6 +322,11 @@ int sc_append_from_out(s2m_context* h);
 int loop_busy(s2m_context* h);
 // waits for the loop stream and forgets the pending closure (s2m_kf_reset, s2m_destroy); `destroy`: the stream and event go too
 void loop_drop_pending(s2m_context* h, bool destroy);
+
+// ---- s2m_abi_pose_graph.hip ----
+// waits for the pose-graph stream and forgets the pending optimise (s2m_pg_reset, s2m_destroy); `destroy`: stream, events and the
+// pinned record go too
+void pg_drop_pending(s2m_context* h, bool destroy);
 
 // ---- s2m_abi_voxel.hip ----
 // VoxelGrid of a device cloud into `dst` (grown to hold one record per input point, the worst case).

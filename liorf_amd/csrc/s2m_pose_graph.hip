@@ -196,7 +196,9 @@ __device__ void factor_eval(const PgFactor& f, const double* X, double* Ji, doub
     }
 }
 
-__global__ void __launch_bounds__(kPgThreads) k_pg_linearize(PgDev d, const double* X)
+// (the bodies of the kernels that also have a gated form for the launched optimise, further down, are device functions: the two
+// forms run the same code)
+__device__ inline void linearize_body(const PgDev& d, const double* X)
 {
     const int f = blockIdx.x * blockDim.x + threadIdx.x;
     if (f >= d.n + d.n_extra) return;
@@ -215,9 +217,10 @@ __global__ void __launch_bounds__(kPgThreads) k_pg_linearize(PgDev d, const doub
         factor_eval(d.extra[x], X, d.Ji + 36 * (size_t)x, d.Jj + 36 * (size_t)x, d.rx + 6 * (size_t)x, nullptr, d.ferr + f, d.fw + f);
     }
 }
+__global__ void __launch_bounds__(kPgThreads) k_pg_linearize(PgDev d, const double* X) { linearize_body(d, X); }
 
 // sum of the error terms and minimum of the weights, one workgroup, fixed order
-__global__ void __launch_bounds__(kPgThreads) k_pg_err_reduce(PgDev d)
+__device__ inline void err_reduce_body(const PgDev& d)
 {
     __shared__ double se[kPgThreads], sw[kPgThreads];
     const int n = d.n + d.n_extra;
@@ -231,9 +234,10 @@ __global__ void __launch_bounds__(kPgThreads) k_pg_err_reduce(PgDev d)
     }
     if (threadIdx.x == 0) { d.sc->err = se[0]; d.sc->wmin = sw[0]; }
 }
+__global__ void __launch_bounds__(kPgThreads) k_pg_err_reduce(PgDev d) { err_reduce_body(d); }
 
 // level-0 matrices of both scans: forward M_i = -Binv_i A_(i-1), C0 = Binv_i; transposed (e = n-1-i) M_e = -(A_i Binv_i)^T, C0 = Binv_i^T
-__global__ void __launch_bounds__(kPgThreads) k_pg_scan_m0(PgDev d)
+__device__ inline void scan_m0_body(const PgDev& d)
 {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= d.n) return;
@@ -261,9 +265,10 @@ __global__ void __launch_bounds__(kPgThreads) k_pg_scan_m0(PgDev d)
             Cb[a * 6 + b] = B[b * 6 + a];
         }
 }
+__global__ void __launch_bounds__(kPgThreads) k_pg_scan_m0(PgDev d) { scan_m0_body(d); }
 
 // prefix products inside each group, one thread per (group, column); the group's product is the next level's matrix
-__global__ void __launch_bounds__(kPgThreads) k_pg_scan_pre(const double* M, double* Pre, double* Mnext, int n)
+__device__ inline void scan_pre_body(const double* M, double* Pre, double* Mnext, int n)
 {
     const int t = blockIdx.x * blockDim.x + threadIdx.x;
     const int g = t / 6, col = t % 6;
@@ -280,6 +285,7 @@ __global__ void __launch_bounds__(kPgThreads) k_pg_scan_pre(const double* M, dou
     if (Mnext)
         for (int a = 0; a < 6; a++) Mnext[36 * (size_t)g + a * 6 + col] = v[a];
 }
+__global__ void __launch_bounds__(kPgThreads) k_pg_scan_pre(const double* M, double* Pre, double* Mnext, int n) { scan_pre_body(M, Pre, Mnext, n); }
 
 // up-sweep, one thread per group: the group's recurrence from a zero input
 __global__ void __launch_bounds__(64) k_pg_scan_up0(PgScan sc, const double* in, const int32_t* stop)
@@ -386,12 +392,13 @@ __device__ inline double partial_sum(const double* partial)
     return s;
 }
 
-__global__ void __launch_bounds__(kPgThreads) k_pg_rhs(PgDev d, int have_t2)        // b = -(rc + t2)
+__device__ inline void rhs_body(const PgDev& d, int have_t2)                        // b = -(rc + t2)
 {
     const int k = blockIdx.x * blockDim.x + threadIdx.x;
     if (k < 6 * d.n) d.b[k] = -(d.rc[k] + (have_t2 ? d.t2[k] : 0.0));
 }
-__global__ void __launch_bounds__(kPgThreads) k_pg_cg_init(PgDev d)                 // y = 0, r = p = b, partial of b.b
+__global__ void __launch_bounds__(kPgThreads) k_pg_rhs(PgDev d, int have_t2) { rhs_body(d, have_t2); }
+__device__ inline void cg_init_body(const PgDev& d)                                 // y = 0, r = p = b, partial of b.b
 {
     double a = 0.0;
     for (int k = blockIdx.x * kPgThreads + threadIdx.x; k < 6 * d.n; k += kPgDotBlocks * kPgThreads) {
@@ -401,13 +408,15 @@ __global__ void __launch_bounds__(kPgThreads) k_pg_cg_init(PgDev d)             
     }
     block_partial(a, d.partial);
 }
-__global__ void k_pg_cg_init2(PgDev d, double tol, int max_iters)
+__global__ void __launch_bounds__(kPgThreads) k_pg_cg_init(PgDev d) { cg_init_body(d); }
+__device__ inline void cg_init2_body(const PgDev& d, double tol, int max_iters)
 {
     const double bb = partial_sum(d.partial);
     d.sc->rr = bb; d.sc->bb = bb; d.sc->tol2 = tol * tol;
     d.sc->iters = 0; d.sc->max_iters = max_iters;
     d.sc->stop = (bb == 0.0 || max_iters <= 0) ? 1 : 0;
 }
+__global__ void k_pg_cg_init2(PgDev d, double tol, int max_iters) { cg_init2_body(d, tol, max_iters); }
 __global__ void __launch_bounds__(kPgThreads) k_pg_cg_q(PgDev d, int have_t2)       // q = p + K^T K p, partial of p.q
 {
     if (d.sc->stop) return;
@@ -455,7 +464,7 @@ __global__ void __launch_bounds__(kPgThreads) k_pg_cg_p(PgDev d)
     if (k < 6 * d.n) d.p[k] = d.r[k] + d.sc->beta * d.p[k];
 }
 
-__global__ void __launch_bounds__(kPgThreads) k_pg_retract(PgDev d)
+__device__ inline void retract_body(const PgDev& d)
 {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= d.n) return;
@@ -470,6 +479,7 @@ __global__ void __launch_bounds__(kPgThreads) k_pg_retract(PgDev d)
     for (int k = 0; k < 9; k++) O[k] = Rn[k];
     for (int k = 0; k < 3; k++) O[9 + k] = X[9 + k] + Rv[k];
 }
+__global__ void __launch_bounds__(kPgThreads) k_pg_retract(PgDev d) { retract_body(d); }
 
 __global__ void __launch_bounds__(kPgThreads) k_pg_unit(PgDev d, int at)
 {
@@ -722,6 +732,78 @@ __global__ void __launch_bounds__(64) k_pg_rows_cols(PgDev d, PgCols s, PgColAt 
     rows[12 * (size_t)blockIdx.y + t] = in ? d.delta[blockIdx.y * s.vec + 6 * (size_t)key + t % 6] : 0.0;
 }
 
+// ---- the launched optimise (s2m_pg_optimize_launch): the outer loop's decisions on the device.  PgRecord (in the header) holds
+// the result and three gates, each "nonzero = return at the head": skip_head (rhs and CG begin of a step), skip_tail (the step,
+// the trial point's linearisation and the close) and skip_keep (trial -> estimate).  A kernel reads its gate before anything
+// else and no kernel waits for another; the kernels of s2m_pg_optimize run between them unchanged (the scans and the extra
+// factors' products take the gate as their stop pointer, the CG iterations stop by sc->stop as ever).
+__global__ void __launch_bounds__(kPgThreads) k_pg_linearize_g(PgDev d, const double* X, const int32_t* skip) { if (*skip) return; linearize_body(d, X); }
+__global__ void __launch_bounds__(kPgThreads) k_pg_err_reduce_g(PgDev d, const int32_t* skip) { if (*skip) return; err_reduce_body(d); }
+__global__ void __launch_bounds__(kPgThreads) k_pg_scan_m0_g(PgDev d, const int32_t* skip) { if (*skip) return; scan_m0_body(d); }
+__global__ void __launch_bounds__(kPgThreads) k_pg_scan_pre_g(const double* M, double* Pre, double* Mnext, int n, const int32_t* skip)
+{
+    if (*skip) return;
+    scan_pre_body(M, Pre, Mnext, n);
+}
+__global__ void __launch_bounds__(kPgThreads) k_pg_rhs_g(PgDev d, int have_t2, const int32_t* skip) { if (*skip) return; rhs_body(d, have_t2); }
+__global__ void __launch_bounds__(kPgThreads) k_pg_cg_init_g(PgDev d, const int32_t* skip) { if (*skip) return; cg_init_body(d); }
+__global__ void __launch_bounds__(kPgThreads) k_pg_retract_g(PgDev d, const int32_t* skip) { if (*skip) return; retract_body(d); }
+__global__ void __launch_bounds__(kPgThreads) k_pg_copy_g(const double* src, double* dst, int n, const int32_t* skip)
+{
+    if (*skip) return;
+    const int k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k < n) dst[k] = src[k];
+}
+// the CG begin of a step that was opened; the head is closed behind it.  After `done` it is not opened again.
+__global__ void k_pg_cg_init2_g(PgDev d, double tol, int max_iters, PgRecord* rec)
+{
+    if (rec->skip_head) return;
+    cg_init2_body(d, tol, max_iters);
+    rec->skip_head = 1;
+}
+// behind the linearisation at the launch-time estimates: the record of s2m_pg_optimize before its first step
+__global__ void k_pg_open(PgDev d, PgRecord* rec, int max_iterations, double abs_tol, double rel_tol)
+{
+    const double err = d.sc->err;
+    rec->iterations = 0; rec->inner_iterations = 0; rec->converged = 0;
+    rec->max_iterations = max_iterations; rec->abs_tol = abs_tol; rec->rel_tol = rel_tol;
+    rec->err = err; rec->error_before = err; rec->error_after = err; rec->wmin = d.sc->wmin;
+    for (int k = 0; k < 12; k++) rec->A[k] = d.X[12 * (size_t)(d.n - 1) + k];
+    rec->done = max_iterations <= 0 ? 1 : 0;
+    rec->skip_head = rec->done; rec->skip_tail = 1; rec->skip_keep = 1;
+}
+// behind a chunk of CG iterations: the tail runs once the CG has stopped
+__global__ void k_pg_gate(PgDev d, PgRecord* rec)
+{
+    rec->skip_tail = (rec->done || !d.sc->stop) ? 1 : 0;
+    rec->skip_keep = 1;
+}
+// The close of a Gauss-Newton step, behind the trial point's linearisation: s2m_pg_optimize's comparisons in its order.
+__global__ void k_pg_close(PgDev d, PgRecord* rec)
+{
+    if (rec->skip_tail) return;
+    rec->inner_iterations += d.sc->iters;
+    const double err_n = d.sc->err, err = rec->err;
+    if (!(err_n < err)) { rec->converged = 1; rec->done = 1; return; }
+    const double dec = err - err_n, old = err;
+    rec->err = err_n;
+    rec->iterations += 1;
+    rec->error_after = err_n;
+    rec->wmin = d.sc->wmin;
+    rec->skip_keep = 0;
+    for (int k = 0; k < 12; k++) rec->A[k] = d.Xtrial[12 * (size_t)(d.n - 1) + k];
+    if (dec < rec->abs_tol || dec < rec->rel_tol * old) { rec->converged = 1; rec->done = 1; }
+    else if (rec->iterations >= rec->max_iterations) rec->done = 1;
+    else rec->skip_head = 0;
+}
+// a kept step: the trial point becomes the estimate
+__global__ void __launch_bounds__(kPgThreads) k_pg_keep(PgDev d, const PgRecord* rec)
+{
+    if (rec->skip_keep) return;
+    const int k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k < 12 * d.n) d.X[k] = d.Xtrial[k];
+}
+
 inline int blocks_for(int n) { return (n + kPgThreads - 1) / kPgThreads; }
 
 // out = scan applied to in (both in key order)
@@ -861,6 +943,46 @@ hipError_t pg_cg_iterations(hipStream_t s, const PgDev& d, int count)
         k_pg_cg_beta<<<1, 1, 0, s>>>(d);
         k_pg_cg_p<<<blocks_for(6 * d.n), kPgThreads, 0, s>>>(d);
     }
+    return hipGetLastError();
+}
+
+hipError_t pg_async_open(hipStream_t s, const PgDev& d, PgRecord* rec, int max_iterations, double abs_tol, double rel_tol)
+{
+    if (d.n <= 0) return hipErrorInvalidValue;
+    hipError_t e = pg_linearize(s, d, d.X);
+    if (e != hipSuccess) return e;
+    k_pg_open<<<1, 1, 0, s>>>(d, rec, max_iterations, abs_tol, rel_tol);
+    return hipGetLastError();
+}
+
+hipError_t pg_async_segment(hipStream_t s, const PgDev& d, PgRecord* rec, double tol, int max_cg, int cg_chunk)
+{
+    if (d.n <= 0 || cg_chunk <= 0) return hipErrorInvalidValue;
+    const int32_t *head = &rec->skip_head, *tail = &rec->skip_tail;
+    // head of a step: pg_rhs and pg_cg_begin
+    if (d.n_extra > 0) {
+        k_pg_copy_g<<<blocks_for(6 * d.n_extra), kPgThreads, 0, s>>>(d.rx, d.u, 6 * d.n_extra, head);
+        kt_apply(s, d, head);
+    }
+    k_pg_rhs_g<<<blocks_for(6 * d.n), kPgThreads, 0, s>>>(d, d.n_extra > 0, head);
+    k_pg_cg_init_g<<<kPgDotBlocks, kPgThreads, 0, s>>>(d, head);
+    k_pg_cg_init2_g<<<1, 1, 0, s>>>(d, tol, max_cg, rec);
+    hipError_t e = pg_cg_iterations(s, d, cg_chunk);
+    if (e != hipSuccess) return e;
+    k_pg_gate<<<1, 1, 0, s>>>(d, rec);
+    // tail: pg_step, pg_linearize at the trial point, the close
+    scan_solve(s, d.fwd, d.y, d.delta, tail);
+    k_pg_retract_g<<<blocks_for(d.n), kPgThreads, 0, s>>>(d, tail);
+    k_pg_linearize_g<<<blocks_for(d.n + d.n_extra), kPgThreads, 0, s>>>(d, d.Xtrial, tail);
+    k_pg_err_reduce_g<<<1, kPgThreads, 0, s>>>(d, tail);
+    k_pg_scan_m0_g<<<blocks_for(d.n), kPgThreads, 0, s>>>(d, tail);
+    for (const PgScan* sc : { &d.fwd, &d.bwd })
+        for (int l = 0; l < sc->levels; l++) {
+            const int groups = (sc->n[l] + kPgGroup - 1) / kPgGroup;
+            k_pg_scan_pre_g<<<blocks_for(groups * 6), kPgThreads, 0, s>>>(sc->M[l], sc->Pre[l], l + 1 < sc->levels ? sc->M[l + 1] : nullptr, sc->n[l], tail);
+        }
+    k_pg_close<<<1, 1, 0, s>>>(d, rec);
+    k_pg_keep<<<blocks_for(12 * d.n), kPgThreads, 0, s>>>(d, rec);
     return hipGetLastError();
 }
 

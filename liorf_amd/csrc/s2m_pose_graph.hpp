@@ -85,6 +85,22 @@ hipError_t pg_fwd_y_cols(hipStream_t s, const PgDev& d, const PgCols& c);       
 // rows[12 c + 0..5] = delta_c of key ka[c], rows[12 c + 6..11] = delta_c of key kb[c] (zeros where kb[c] < 0)
 hipError_t pg_rows_cols(hipStream_t s, const PgDev& d, const PgCols& c, const PgColAt& ka, const PgColAt& kb, double* rows);
 
+// ---- the launched optimise: the Gauss-Newton loop of s2m_pg_optimize with its decisions taken on the device.  The record holds
+// the result's fields, the running error, the gates of the kernels that return at their head (nonzero = skip) and A, the
+// estimate of the last variable (12 doubles) after the last kept step.  pg_async_open linearises at d.X and opens the record;
+// pg_async_segment queues, in this order: the head of a step (rhs, CG begin; runs if a step was opened), cg_chunk CG
+// iterations (they stop by sc->stop), and the tail (step, linearisation at the trial point, close, trial -> d.X if the step
+// is kept; runs if the CG has stopped).  Segments are queued back to back until `done` shows in the record; every kernel
+// behind `done` returns at its head.  d.X holds the estimates throughout (no pointer swap).
+struct PgRecord {
+    int32_t iterations, inner_iterations, converged, done;
+    int32_t skip_head, skip_tail, skip_keep, max_iterations;
+    double  err, error_before, error_after, wmin, abs_tol, rel_tol;
+    double  A[12];
+};
+hipError_t pg_async_open(hipStream_t s, const PgDev& d, PgRecord* rec, int max_iterations, double abs_tol, double rel_tol);
+hipError_t pg_async_segment(hipStream_t s, const PgDev& d, PgRecord* rec, double tol, int max_cg, int cg_chunk);
+
 hipError_t pg_poses(hipStream_t s, const double* X, int first, int count, float* xyzrpy, float4* pos);   // pos: may be null
 // correctPoses() in two launches: 18 floats per key (pose vector, 3x4 transform) and a not-finite flag into `stage`, then - once
 // the host has seen the flag - positions and cached transforms into the key-frame store

@@ -243,6 +243,16 @@ public:
         saveKeyFrame();
     }
 
+    // The optimise beside the scan handler (s2m_pg_optimize_launch / _poll / _collect), for the update after a loop or GPS factor
+    // went in: take the scan handler's lock, pgOptimizeLaunch(), release; key frames keep going into the graph meanwhile
+    // (s2m_pg_add_odometry chains on the launch-time estimate); then lock, pgOptimizePoll(), release, sleep - until it returns
+    // S2M_OK, and then correctPosesFromGraph(). Each returns the status: S2M_PG_PENDING, S2M_PG_IDLE (nothing pending) or
+    // S2M_OK with lastGraphResult final (from the launch: an empty graph). Everything else throws.
+    int pgOptimizeLaunch(const s2m_pg_params* p = nullptr) { return pgCode(s2m_pg_optimize_launch(h_, p, &lastGraphEarly), "s2m_pg_optimize_launch", &lastGraphEarly); }
+    int pgOptimizePoll() { s2m_pg_result r{}; return pgCode(s2m_pg_optimize_poll(h_, &r), "s2m_pg_optimize_poll", &r); }       // never waits for the device
+    int pgOptimizeCollect() { s2m_pg_result r{}; return pgCode(s2m_pg_optimize_collect(h_, &r), "s2m_pg_optimize_collect", &r); }
+    s2m_pg_result lastGraphEarly{};
+
     // poseCovariance (:1565) for several keys in one block solve (s2m_pg_marginals): 36 doubles per key, row-major 6x6 in the
     // tangent order of rotation then translation; and the joint covariance of two keys (s2m_pg_joint_marginal), row-major 12x12
     std::vector<double> poseCovariances(const std::vector<int32_t>& keys)
@@ -528,6 +538,12 @@ private:
     void check(int rc, const char* what)
     {
         if (rc != S2M_OK) throw std::runtime_error(std::string(what) + ": " + s2m_last_error(h_));
+    }
+    int pgCode(int rc, const char* what, const s2m_pg_result* r)
+    {
+        if (rc != S2M_PG_PENDING && rc != S2M_PG_IDLE) check(rc, what);
+        if (rc == S2M_OK) lastGraphResult = *r;
+        return rc;
     }
     // S2M_WARN_LEAF_TOO_SMALL is PCL's PCL_WARN case (output = input): not an error
     void checkVoxel(int rc, const char* what) { if (rc != S2M_WARN_LEAF_TOO_SMALL) check(rc, what); }

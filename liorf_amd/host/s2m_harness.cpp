@@ -18,7 +18,7 @@
 //   s2m_harness --global-map keys.bin keys.txt scan_leaf search_radius pose_density leaf out.bin
 //       the key frames through downsampleCurrentScan() -> saveKeyFrame(), then publishGlobalMap() (globalMapKeyFramesDS written
 //       to out.bin) and saveMapService()'s unfiltered cloud; prints the key list and both sizes.
-//   s2m_harness --pose-graph keys.bin keys.txt scan_leaf loops.txt out.bin
+//   s2m_harness --pose-graph keys.bin keys.txt scan_leaf loops.txt out.bin [--async]
 //       the pose graph beside the store: every key through downsampleCurrentScan() -> saveKeyFramesAndFactor() (with the loop
 //       factors loops.txt queues for it) -> correctPosesFromGraph(); prints every update, the graph's estimates and the
 //       size of the unfiltered map cloud, which goes to out.bin.
@@ -370,8 +370,17 @@ static int run_many(int argc, char** argv)
 // "key <i> iterations inner converged factors error pose(6) corrected" per key, then "kp <i> pose(6)" per key (the graph's
 // estimates) and "map_cloud <n>".  The last key's covariance goes to the standard error stream, so that the standard output stays
 // the record the Python mirror is compared with: "marginal_old 36 values" from s2m_pg_marginal, "marginal_new 36 values" from
-// poseCovariances() (%.17g: equal lines are equal bits).
-static int run_pose_graph(char** argv)
+// poseCovariances() (%.17g: equal lines are equal bits).  With --async two more lines follow "map_cloud": the final estimates as
+// an odometry chain with every closure of loops.txt, on two fresh nodes, optimised once by s2m_pg_optimize ("optimize_sync") and
+// once by launch and polls ("optimize_launched": "iterations inner converged variables factors error_before error_after
+// robust_weight_min"; equal lines are equal bits), and the number of polls on the standard error stream.
+static void print_pg_result(const char* name, const s2m_pg_result& r)
+{
+    std::printf("%s %d %d %d %d %d %.17g %.17g %.17g\n", name, r.iterations, r.inner_iterations, r.converged, r.n_variables, r.n_factors,
+                r.error_before, r.error_after, r.robust_weight_min);
+}
+
+static int run_pose_graph(char** argv, bool launched)
 {
     liorf_amd::MapOptimizationS2M node;
     const std::vector<liorf_amd::PointXYZI> all = read_cloud(argv[2]);
@@ -417,6 +426,27 @@ static int run_pose_graph(char** argv)
     std::vector<liorf_amd::PointXYZI> cloud;
     node.globalMapCloud(cloud, 0.0f);
     std::printf("map_cloud %zu\n", cloud.size());
+    if (launched) {
+        for (int which = 0; which < 2; which++) {
+            liorf_amd::MapOptimizationS2M twin;
+            for (size_t k = 0; k < N; k++)
+                if (s2m_pg_add_odometry(twin.handle(), est.data() + 6 * k) != S2M_OK) throw std::runtime_error("s2m_pg_add_odometry");
+            for (const auto& l : loops)
+                if ((size_t)l.second.key_cur < N && (size_t)l.second.key_pre < N &&
+                    s2m_pg_add_between(twin.handle(), l.second.key_cur, l.second.key_pre, l.second.rel, l.second.var, l.second.robust_k) != S2M_OK)
+                    throw std::runtime_error("s2m_pg_add_between");
+            if (which == 0) {
+                if (s2m_pg_optimize(twin.handle(), nullptr, &twin.lastGraphResult) != S2M_OK) throw std::runtime_error("s2m_pg_optimize");
+                print_pg_result("optimize_sync", twin.lastGraphResult);
+            } else {
+                long polls = 0;
+                int rc = twin.pgOptimizeLaunch();
+                while (rc == S2M_PG_PENDING) { rc = twin.pgOptimizePoll(); polls++; }
+                print_pg_result("optimize_launched", twin.lastGraphResult);
+                std::fprintf(stderr, "polls %ld\n", polls);
+            }
+        }
+    }
     if (N > 0) {
         double old_cov[36];
         if (s2m_pg_marginal(node.handle(), (int32_t)N - 1, old_cov) != S2M_OK) throw std::runtime_error("s2m_pg_marginal");
@@ -442,7 +472,8 @@ int main(int argc, char** argv)
         if (argc == 9 && std::string(argv[1]) == "--loop") return run_loop(argv, false);
         if (argc == 10 && std::string(argv[1]) == "--loop" && std::string(argv[9]) == "--async") return run_loop(argv, true);
         if (argc == 9 && std::string(argv[1]) == "--global-map") return run_global_map(argv);
-        if (argc == 7 && std::string(argv[1]) == "--pose-graph") return run_pose_graph(argv);
+        if (argc == 7 && std::string(argv[1]) == "--pose-graph") return run_pose_graph(argv, false);
+        if (argc == 8 && std::string(argv[1]) == "--pose-graph" && std::string(argv[7]) == "--async") return run_pose_graph(argv, true);
         if (argc == 12 && std::string(argv[1]) == "--project") return run_project(argv);
         if (argc == 14 && std::string(argv[1]) == "--front-end") return run_front_end(argv);
         if (argc != 9 && argc != 16) {

@@ -49,6 +49,7 @@ ABI_SYMBOLS = [
     "s2m_pg_default_params", "s2m_pg_check_args", "s2m_pg_reset", "s2m_pg_size", "s2m_pg_add_prior", "s2m_pg_add_between", "s2m_pg_add_gps",
     "s2m_pg_set_initial", "s2m_pg_add_odometry", "s2m_pg_optimize", "s2m_pg_get_poses", "s2m_pg_marginal", "s2m_pg_apply_to_store",
     "s2m_pg_marginals_check_args", "s2m_pg_marginals", "s2m_pg_joint_marginal",
+    "s2m_pg_optimize_launch", "s2m_pg_optimize_poll", "s2m_pg_optimize_collect", "s2m_debug_pg_rebase",
 ]
 S2M_RING_U8, S2M_RING_U16, S2M_RING_I32 = 0, 1, 2
 S2M_TIME_F32, S2M_TIME_U32_NS, S2M_TIME_U32, S2M_TIME_F64_REL = 0, 1, 2, 3
@@ -60,6 +61,7 @@ S2M_LOOP_PENDING = 5                                     # a launched closure wh
 S2M_ICP_RANGE = 8                                        # iterations the device loop queues at a time (liorf_s2m_debug.h)
 S2M_WARN_LEAF_TOO_SMALL = 1
 S2M_PG_PRIOR, S2M_PG_BETWEEN, S2M_PG_GPS, S2M_PG_INITIAL = 0, 1, 2, 3
+S2M_PG_PENDING, S2M_PG_IDLE = 2, 3                       # s2m_pg_optimize_launch / _poll / _collect: queued or running; nothing pending
 S2M_PG_BLOCK_COLUMNS = 24                                # right-hand sides per pass of the block solve
 PG_MARGINALS_KEYS_PER_PASS = S2M_PG_BLOCK_COLUMNS // 6   # keys one pass of s2m_pg_marginals serves
 
@@ -318,6 +320,10 @@ def load_library(path: str | None = None) -> C.CDLL:
     L.s2m_pg_set_initial.argtypes = [vp, C.c_int32, fp]
     L.s2m_pg_add_odometry.argtypes = [vp, fp]
     L.s2m_pg_optimize.argtypes = [vp, C.POINTER(PgParams), C.POINTER(PgResult)]
+    L.s2m_pg_optimize_launch.argtypes = [vp, C.POINTER(PgParams), C.POINTER(PgResult)]
+    L.s2m_pg_optimize_poll.argtypes = [vp, C.POINTER(PgResult)]
+    L.s2m_pg_optimize_collect.argtypes = [vp, C.POINTER(PgResult)]
+    L.s2m_debug_pg_rebase.argtypes = [dp, dp, dp]
     L.s2m_pg_get_poses.argtypes = [vp, C.c_int32, C.c_int32, fp]
     L.s2m_pg_marginal.argtypes = [vp, C.c_int32, dp]
     L.s2m_pg_apply_to_store.argtypes = [vp, C.c_int32, C.c_int32]
@@ -918,6 +924,29 @@ class MapOptimizationS2M:
         self._check(self.lib.s2m_pg_optimize(self.h, C.byref(params) if params is not None else None, C.byref(out)), "s2m_pg_optimize")
         return out
 
+    def _pg_code(self, rc: int, what: str) -> int:
+        if rc not in (S2M_OK, S2M_PG_PENDING, S2M_PG_IDLE):
+            self._check(rc, what)
+        return rc
+
+    def pgOptimizeLaunch(self, params: PgParams | None = None) -> tuple[int, PgResult]:
+        """s2m_pg_optimize_launch: (S2M_PG_PENDING, the early result) with the solve queued beside the scan handler, or
+        (S2M_OK, the synchronous result) for an empty graph."""
+        out = PgResult()
+        rc = self.lib.s2m_pg_optimize_launch(self.h, C.byref(params) if params is not None else None, C.byref(out))
+        return self._pg_code(rc, "s2m_pg_optimize_launch"), out
+
+    def pgOptimizePoll(self) -> tuple[int, PgResult]:
+        """s2m_pg_optimize_poll: never waits for the device. (S2M_PG_PENDING, untouched), (S2M_OK, the result) once, or
+        (S2M_PG_IDLE, untouched) with nothing pending."""
+        out = PgResult()
+        return self._pg_code(self.lib.s2m_pg_optimize_poll(self.h, C.byref(out)), "s2m_pg_optimize_poll"), out
+
+    def pgOptimizeCollect(self) -> tuple[int, PgResult]:
+        """s2m_pg_optimize_collect: waits. (S2M_OK, the result) or (S2M_PG_IDLE, untouched)."""
+        out = PgResult()
+        return self._pg_code(self.lib.s2m_pg_optimize_collect(self.h, C.byref(out)), "s2m_pg_optimize_collect"), out
+
     def pgPoses(self, first: int = 0, count: int | None = None) -> np.ndarray:
         if count is None:
             count = self.pgSize()[0] - first
@@ -1157,6 +1186,18 @@ def pg_check_args(kind: int, n_variables: int, key_a: int, key_b: int, values, v
     w = None if var is None else np.ascontiguousarray(var, np.float64)
     return load_library().s2m_pg_check_args(kind, n_variables, key_a, key_b, None if v is None else _fp(v),
                                             None if w is None else _dp(w), float(robust_k))
+
+
+def pg_rebase(a_launch, a_now, X) -> np.ndarray:
+    """s2m_debug_pg_rebase (host only, no GPU): the tail rule of a launched optimise, X <- (a_now a_launch^-1) X on states of
+    12 doubles (R row-major, then t)."""
+    a = np.ascontiguousarray(a_launch, np.float64).reshape(12)
+    b = np.ascontiguousarray(a_now, np.float64).reshape(12)
+    x = np.array(X, np.float64).reshape(12).copy()
+    rc = load_library().s2m_debug_pg_rebase(_dp(a), _dp(b), _dp(x))
+    if rc != S2M_OK:
+        raise S2MError(rc, "s2m_debug_pg_rebase")
+    return x
 
 
 def pg_marginals_check_args(n_variables: int, keys, n_keys: int | None = None) -> int:

@@ -18,8 +18,20 @@ warm-up of each call, the calls alternating inside every repetition):
 with marginals_1_over_single (the ratio of the first two) and eight_times_marginals_1_ms beside marginals_8_ms.
 
   python tools/bench_pose_graph.py --marginals --sizes 2000,10000 --reps 7 --out profiles/pose_graph_marginals_bench_line.json
+
+--async measures the launched optimise (s2m_pg_optimize_launch / _poll / _collect) against the synchronous call of the same
+session, for the same one optimise after one added loop (medians of --reps runs after one warm-up run):
+  optimize_ms            (a) s2m_pg_optimize
+  launch_ms, held_ms     (b) the launch, and the time the handle is held: the launch plus all polls, one every --poll-us
+  latency_ms             (c) from the launch to the poll that delivers the result (polls, ranges: how many of each)
+  held_over_sync         held_ms / optimize_ms
+  bitwise_equal          result bytes and estimates of the launched solve against the synchronous one, every run
+  registration_ms        (d) a 12 000 x 30 000 registration (set_scan + optimize) alone and with the optimise pending
+
+  python tools/bench_pose_graph.py --async --sizes 2000,10000 --out profiles/pose_graph_async_bench_line.json
 """
 import argparse
+import ctypes as C
 import json
 import os
 import sys
@@ -119,13 +131,119 @@ def marginals_one_size(n, reps):
         m.close()
 
 
+def async_one_size(n, reps, poll_us, scans):
+    g = P.figure_eight(n, 40)
+    half = n // 2
+    truth = P.figure_eight(n, 0, truth_only=True)
+    i, j = n - 3, n - 3 - half
+    rel = P.xyzrpy_from_pose(truth[i][0].T @ truth[j][0], truth[i][0].T @ (truth[j][1] - truth[i][1])).astype(np.float32)
+    m = s2m.MapOptimizationS2M()
+    lib, h = m.lib, m.h
+    pending = s2m.S2M_PG_PENDING
+    raw = lambda r: C.string_at(C.addressof(r), C.sizeof(r))
+
+    def ready():                                                   # the state a node is in when a closure arrives
+        CS.load_into(m, g)
+        m.pgOptimize()
+        m.pgAddBetween(i, j, rel, np.full(6, 0.3))
+
+    def launched(poll_s, beside=None):
+        r = s2m.PgResult()
+        t0 = time.perf_counter()
+        rc = lib.s2m_pg_optimize_launch(h, None, C.byref(r))
+        t1 = time.perf_counter()
+        assert rc == pending, rc
+        if beside:
+            beside()
+        held, polls = t1 - t0, 0
+        while rc == pending:
+            if poll_s > 0:
+                time.sleep(poll_s)
+            p0 = time.perf_counter()
+            rc = lib.s2m_pg_optimize_poll(h, C.byref(r))
+            held += time.perf_counter() - p0
+            polls += 1
+        assert rc == 0, rc
+        return t1 - t0, held, polls, time.perf_counter() - t0, r
+
+    try:
+        sync, runs, same = [], [], True
+        for k in range(reps + 1):                                  # the first round is the warm-up
+            ready()
+            t0 = time.perf_counter()
+            want = m.pgOptimize()
+            t = time.perf_counter() - t0
+            want_poses = m.pgPoses()
+            ready()
+            run = launched(poll_us * 1e-6)
+            same = same and raw(run[4]) == raw(want) and bool(np.array_equal(m.pgPoses(), want_poses))
+            if k > 0:
+                sync.append(t)
+                runs.append(run)
+        med = lambda k: round(1e3 * float(np.median([x[k] for x in runs])), 4)
+        out = dict(keys=n, n_factors=want.n_factors, iterations=want.iterations, inner_iterations=want.inner_iterations, reps=reps, poll_us=poll_us,
+                   optimize_ms=round(1e3 * float(np.median(sync)), 4), launch_ms=med(0), held_ms=med(1), latency_ms=med(3),
+                   polls=int(np.median([x[2] for x in runs])), bitwise_equal=same)
+        out["polls_ms"] = round(out["held_ms"] - out["launch_ms"], 4)
+        out["held_over_sync"] = round(out["held_ms"] / out["optimize_ms"], 4)
+        out["latency_over_sync"] = round(out["latency_ms"] / out["optimize_ms"], 4)
+        ready()
+        tight = launched(0.0)
+        out.update(latency_tight_ms=round(1e3 * tight[3], 4), polls_tight=tight[2])
+        # (d) a registration alone, and between the launch and the first poll of a pending optimise
+        cloud, cfgs = scans
+        m.setInputCloud(cloud)
+        reg = {}
+        for name in ("alone", "optimise_pending"):
+            ts, still = [], 0
+            for q in range(2 + 2 * len(cfgs)):
+                scan, pose = cfgs[q % len(cfgs)]
+
+                def register():
+                    t0 = time.perf_counter()
+                    m.setScan(scan)
+                    m.transformTobeMapped = pose.copy()
+                    m.scan2MapOptimization()
+                    ts.append(time.perf_counter() - t0)
+                if name == "alone":
+                    register()
+                else:
+                    ready()
+                    run = launched(poll_us * 1e-6, register)
+                    still += int(run[2] > 1)                       # (the first poll behind the registration still said pending)
+            reg[name + "_ms"] = round(1e3 * float(np.median(ts[2:])), 4)
+            if name != "alone":
+                reg["still_pending_after_registration"] = still
+        reg["registrations"] = 2 * len(cfgs)
+        out["registration_ms"] = reg
+        return out
+    finally:
+        m.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--sizes", default="2000,10000,50000")
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--out", default=None)
     ap.add_argument("--marginals", action="store_true", help="time the covariance read-out instead of the optimise")
+    ap.add_argument("--async", dest="run_async", action="store_true", help="time the launched optimise against the synchronous call")
+    ap.add_argument("--poll-us", type=float, default=200.0, help="--async: sleep between two polls")
     a = ap.parse_args()
+    if a.run_async:
+        cfgs = [synth.make_config("small", scan_index=k) for k in range(4)]
+        scans = (synth.to_xyzi(cfgs[0]["map"]), [(synth.to_xyzi(c["scan"]), c["pose_init"]) for c in cfgs])
+        line = {"workload": "figure-of-eight driven twice, 40 loops, one optimise after one added loop, synchronous and launched (seed %d); "
+                            "registration: %d x %d points" % (P.SEED, scans[1][0][0].shape[0], scans[0].shape[0]), "sizes": {}}
+        for n in [int(x) for x in a.sizes.split(",")]:
+            line["sizes"][str(n)] = async_one_size(n, a.reps, a.poll_us, scans)
+            print(n, json.dumps(line["sizes"][str(n)]), file=sys.stderr, flush=True)
+        txt = json.dumps(line)
+        print(txt)
+        if a.out:
+            with open(a.out, "w") as f:
+                f.write(txt + "\n")
+        return
     if a.marginals:
         line = {"workload": "figure-of-eight driven twice, 40 loops, optimised; marginal covariances at the estimates (seed %d)" % P.SEED, "sizes": {}}
         for n in [int(x) for x in a.sizes.split(",")]:
