@@ -5,6 +5,8 @@
  * what the repository's own tools and tests use to look inside the registration path - per-launch timing of the
  * registration kernel, per-wave stage stamps, the device's sinf / cosf / atanf arithmetic, worklist statistics - and the
  * list of environment switches the library reads at s2m_create for A/B experiments.  They may change between rounds.
+ * The observation hooks (s2m_debug_device_*, s2m_debug_lm_close, s2m_debug_icp_*, s2m_debug_pg_*) run the product's own
+ * kernels on given inputs and hand back what a stage wrote, so that tests can hold a stage against a reference of its own.
  *
  * Environment switches (all optional; defaults are what bench.py measures):
  *   S2M_NO_GRAPH=1         plain launches instead of the captured loop graph
@@ -139,6 +141,52 @@ int  s2m_debug_icp_tuning(s2m_handle h, float cell_in_leaves, int32_t shell_cap,
  * X_R <- D_R X_R, X_t <- D_R X_t + D_t, every three-term sum taken as ((a0 b0 + a1 b1) + a2 b2) with no fused products.
  * S2M_OK, or S2M_ERR_INVALID_ARG for a null pointer. */
 int  s2m_debug_pg_rebase(const double a_launch[12], const double a_now[12], double X[12]);
+
+/* ---- observation hooks of the pose graph's stages (liorf_amd/csrc/s2m_pose_graph.hip) ----------------
+ * What s2m_pg_optimize and the marginals compute between their inputs and their results, one stage at a time. No kernel exists
+ * for a hook: each prepares the device tables as an optimise does and queues the launches the product queues, on the work
+ * arrays that every optimise and marginal rewrites before reading them, so that afterwards the graph is in the state a handle
+ * that never saw the hook holds (s2m_debug_pg_set_estimate excepted: it is s2m_pg_set_initial in fp64). Every hook returns
+ * S2M_ERR_BUSY while a launched optimise is pending. States are 12 doubles (R row-major, then t), tangent vectors 6 doubles
+ * per key (rotation, translation). The chain is the first prior on key 0 and, per i, the first plain between i -> i+1, indexed
+ * by key; the n_extra = n_factors - n_variables extra factors keep the order in which they were added.
+ *
+ * s2m_debug_pg_set_estimate: the estimate of `key` (0..N, N appends) from 12 doubles, past the float xyzrpy of
+ * s2m_pg_set_initial. The values are taken as they are - not orthonormalised, not checked for finiteness. */
+int  s2m_debug_pg_set_estimate(s2m_handle h, int32_t key, const double X[12]);
+/* Linearises at the current estimates (pg_linearize) and reads back, each array optional (NULL skips it): rc n x 6, Binv and
+ * Aof n x 36 (row-major 6x6; Aof[i] = whitened Jacobian of chain factor i with respect to key i-1, zero at i = 0), Ji, Jj
+ * n_extra x 36, rx n_extra x 6, ferr and fw n + n_extra (chain first), the error sum and the minimum robust weight.
+ * n_variables and n_extra must be the graph's (S2M_ERR_INVALID_ARG otherwise). */
+int  s2m_debug_pg_linearize(s2m_handle h, int32_t n_variables, int32_t n_extra, double* rc, double* Binv, double* Aof, double* Ji, double* Jj,
+                            double* rx, double* ferr, double* fw, double* err, double* wmin);
+/* Linearises at the current estimates and applies one operator of that linearisation to host vectors. With J_c the chain's
+ * whitened Jacobian, J_x the extra factors' and K = J_x J_c^-1:
+ *   S2M_DEBUG_PG_FWD  out = J_c^-1 in   (6n -> 6n, the forward blocked scan)
+ *   S2M_DEBUG_PG_BWD  out = J_c^-T in   (6n -> 6n, the backward blocked scan)
+ *   S2M_DEBUG_PG_K    out = K in        (6n -> 6 n_extra, the forward scan, then k_pg_extra_u)
+ *   S2M_DEBUG_PG_KT   out = K^T in      (6 n_extra -> 6n, k_pg_extra_gather, then the backward scan)
+ * cols == 0: the single form, one vector. cols = 1 .. S2M_PG_BLOCK_COLUMNS: the block form, `cols` vectors one after the
+ * other in `in` and in `out`. K and K^T need an extra factor. */
+#define S2M_DEBUG_PG_FWD 0
+#define S2M_DEBUG_PG_BWD 1
+#define S2M_DEBUG_PG_K   2
+#define S2M_DEBUG_PG_KT  3
+int  s2m_debug_pg_apply(s2m_handle h, int32_t op, int32_t cols, const double* in, double* out);
+/* The argument checks of s2m_debug_pg_apply that need no handle and no GPU: S2M_OK or S2M_ERR_INVALID_ARG (an empty graph,
+ * op outside 0..3, K or K^T without an extra factor, cols outside 0 .. S2M_PG_BLOCK_COLUMNS, a null array). */
+int  s2m_debug_pg_apply_check_args(int32_t n_variables, int32_t n_extra, int32_t op, int32_t cols, const double* in, const double* out);
+/* Linearises at the current estimates and runs the CG on (I + K^T K) y = b for the given b, driven as the optimise drives it
+ * (single form, cols == 0) or as the marginals' block solve does (cols >= 1, `cols` right-hand sides one after the other):
+ * p->cg_rel_tol and p->cg_max_iterations as s2m_pg_optimize reads them (NULL: defaults; without an extra factor one
+ * iteration). y: cols x 6n; out[c]: the recurrence's |r|^2, |b|^2, the iterations run and the stop flag of column c. */
+typedef struct s2m_debug_pg_cg_out {
+    double  rr, bb;
+    int32_t iters, stop;
+} s2m_debug_pg_cg_out;
+int  s2m_debug_pg_cg(s2m_handle h, const s2m_pg_params* p, int32_t cols, const double* b, double* y, s2m_debug_pg_cg_out* out);
+/* X[12 k ..] = estimate of key k (+) delta[6 k ..] through k_pg_retract; the estimates stay. n_variables must be the graph's. */
+int  s2m_debug_pg_retract(s2m_handle h, int32_t n_variables, const double* delta, double* X);
 
 #ifdef __cplusplus
 }

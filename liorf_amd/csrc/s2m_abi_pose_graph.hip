@@ -300,12 +300,10 @@ int prepare_block(s2m_context* h, int cols, PgDev& db, PgCols& c)
     return S2M_OK;
 }
 
-// One pass: column k is e_(at[k]) through J_c^-T, CG and J_c^-1; rows[12 k ..] holds its delta at keys ka[k] and kb[k].
-// Every column's scalars come back in one copy per chunk of iterations; the pass ends when all have stopped.
-int solve_pass(s2m_context* h, const PgDev& db, const PgCols& c, const s2m_pg_params& prm, const PgColAt& at, const PgColAt& ka, const PgColAt& kb,
-               double* rows)
+// run_cg for the columns of a block: the b_c in place; every column's scalars come back in one copy per chunk of
+// iterations (h_sc[1 + c]); ends when all have stopped
+int run_cg_cols(s2m_context* h, const PgDev& db, const PgCols& c, const s2m_pg_params& prm)
 {
-    S2M_HIP(h, pg_bwd_unit_cols(h->stream, db, c, at));
     int max_cg = prm.cg_max_iterations > 0 ? prm.cg_max_iterations : 6 * db.n_extra + 20;
     if (db.n_extra == 0) max_cg = 1;
     S2M_HIP(h, pg_cg_begin_cols(h->stream, db, c, prm.cg_rel_tol, max_cg));
@@ -321,6 +319,16 @@ int solve_pass(s2m_context* h, const PgDev& db, const PgCols& c, const s2m_pg_pa
         for (int q = 0; q < c.cols; q++) all = all && hs[q].stop;
         if (all) break;
     }
+    return S2M_OK;
+}
+
+// One pass: column k is e_(at[k]) through J_c^-T, CG and J_c^-1; rows[12 k ..] holds its delta at keys ka[k] and kb[k].
+int solve_pass(s2m_context* h, const PgDev& db, const PgCols& c, const s2m_pg_params& prm, const PgColAt& at, const PgColAt& ka, const PgColAt& kb,
+               double* rows)
+{
+    S2M_HIP(h, pg_bwd_unit_cols(h->stream, db, c, at));
+    int rc = run_cg_cols(h, db, c, prm);
+    if (rc) return rc;
     S2M_HIP(h, pg_fwd_y_cols(h->stream, db, c));
     double* dev_rows = h->pg.blk_rows.as<double>();
     S2M_HIP(h, pg_rows_cols(h->stream, db, c, ka, kb, dev_rows));
@@ -620,6 +628,138 @@ int s2m_pg_optimize_collect(s2m_handle h, s2m_pg_result* out)
         const int rc = advance(h, out);
         if (rc != S2M_PG_PENDING) return rc;
     }
+}
+
+// ---- observation hooks of the stages (include/liorf_s2m_debug.h): each prepares the device tables as an optimise does and
+// queues the product's own launches on the work vectors, which every optimise and marginal rewrites before it reads them.
+namespace {
+
+int32_t pg_n_extra(const s2m_context* h) { return (int32_t)h->pg.factors.size() - (int32_t)pg_n(h); }   // (a solvable graph: the chain holds n factors)
+
+int pg_hook_begin(s2m_context* h, bool linearize)
+{
+    if (pg_n(h) == 0) return fail(h, S2M_ERR_INVALID_ARG, "pose-graph hook: the graph is empty");
+    const int rc = prepare(h);
+    if (rc) return rc;
+    if (linearize) S2M_HIP(h, pg_linearize(h->stream, h->pg.dev, h->pg.dev.X));
+    return S2M_OK;
+}
+
+int pg_up(s2m_context* h, double* dst, const double* src, size_t count)
+{
+    if (count) S2M_HIP(h, hipMemcpyAsync(dst, src, sizeof(double) * count, hipMemcpyHostToDevice, h->stream));
+    return S2M_OK;
+}
+
+int pg_down(s2m_context* h, double* dst, const double* src, size_t count)
+{
+    if (dst && count) S2M_HIP(h, hipMemcpyAsync(dst, src, sizeof(double) * count, hipMemcpyDeviceToHost, h->stream));
+    return S2M_OK;
+}
+
+}  // namespace
+
+int s2m_debug_pg_apply_check_args(int32_t n_variables, int32_t n_extra, int32_t op, int32_t cols, const double* in, const double* out)
+{
+    if (n_variables <= 0 || n_extra < 0 || op < S2M_DEBUG_PG_FWD || op > S2M_DEBUG_PG_KT || cols < 0 || cols > S2M_PG_BLOCK_COLUMNS) return S2M_ERR_INVALID_ARG;
+    if (op >= S2M_DEBUG_PG_K && n_extra == 0) return S2M_ERR_INVALID_ARG;
+    if (!in || !out) return S2M_ERR_INVALID_ARG;
+    return S2M_OK;
+}
+
+int s2m_debug_pg_set_estimate(s2m_handle h, int32_t key, const double X[12])
+{
+    if (!h) return S2M_ERR_INVALID_ARG;
+    if (h->pg.pending) return pg_busy(h);
+    if (!X || key < 0 || (size_t)key > pg_n(h)) return fail(h, S2M_ERR_INVALID_ARG, "estimate: 12 doubles, key in 0..N");
+    if (pg_n(h) + 1 >= kPgMaxVars) return fail(h, S2M_ERR_CAPACITY, "pose graph full (2^24 variables)");
+    touch(h, key);
+    std::copy(X, X + 12, h->pg.X.begin() + 12 * (size_t)key);
+    h->pg.has_init[(size_t)key] = 1;
+    h->pg.dirty[(size_t)key] = 1;
+    return S2M_OK;
+}
+
+int s2m_debug_pg_linearize(s2m_handle h, int32_t n_variables, int32_t n_extra, double* rc_, double* Binv, double* Aof, double* Ji, double* Jj,
+                           double* rx, double* ferr, double* fw, double* err, double* wmin)
+{
+    if (!h) return S2M_ERR_INVALID_ARG;
+    if (h->pg.pending) return pg_busy(h);
+    if (n_variables <= 0 || (size_t)n_variables != pg_n(h) || n_extra != pg_n_extra(h))
+        return fail(h, S2M_ERR_INVALID_ARG, "linearise: the array sizes must be the graph's variables and extra factors");
+    int rc = pg_hook_begin(h, true);
+    if (rc) return rc;
+    const PgDev& d = h->pg.dev;
+    const size_t n = (size_t)d.n, m = (size_t)d.n_extra;
+    if ((rc = pg_down(h, rc_, d.rc, 6 * n)) || (rc = pg_down(h, Binv, d.Binv, 36 * n)) || (rc = pg_down(h, Aof, d.Aof, 36 * n)) ||
+        (rc = pg_down(h, Ji, d.Ji, 36 * m)) || (rc = pg_down(h, Jj, d.Jj, 36 * m)) || (rc = pg_down(h, rx, d.rx, 6 * m)) ||
+        (rc = pg_down(h, ferr, d.ferr, n + m)) || (rc = pg_down(h, fw, d.fw, n + m))) return rc;
+    if ((rc = read_scalars(h))) return rc;
+    if (err) *err = h->pg.h_sc->err;
+    if (wmin) *wmin = h->pg.h_sc->wmin;
+    return S2M_OK;
+}
+
+int s2m_debug_pg_apply(s2m_handle h, int32_t op, int32_t cols, const double* in, double* out)
+{
+    if (!h) return S2M_ERR_INVALID_ARG;
+    if (h->pg.pending) return pg_busy(h);
+    if (s2m_debug_pg_apply_check_args((int32_t)pg_n(h), std::max(pg_n_extra(h), 0), op, cols, in, out))
+        return fail(h, S2M_ERR_INVALID_ARG, "apply: op 0..3 (2 and 3 need an extra factor), cols 0..S2M_PG_BLOCK_COLUMNS, two arrays, a graph");
+    int rc = pg_hook_begin(h, true);
+    if (rc) return rc;
+    PgDev db = h->pg.dev;
+    PgCols c{};
+    if (cols > 0 && (rc = prepare_block(h, cols, db, c))) return rc;
+    // with an extra factor a column's u is 6 n_extra doubles apart, so the host's side-by-side columns are the device's
+    const size_t C = (size_t)std::max(cols, 1), nv = 6 * (size_t)db.n, nu = 6 * (size_t)db.n_extra;
+    double* src = op == S2M_DEBUG_PG_BWD ? db.g : op == S2M_DEBUG_PG_KT ? db.u : db.p;
+    const double* dst = op == S2M_DEBUG_PG_FWD ? db.t1 : op == S2M_DEBUG_PG_K ? db.u : db.t2;
+    if ((rc = pg_up(h, src, in, C * (op == S2M_DEBUG_PG_KT ? nu : nv)))) return rc;
+    S2M_HIP(h, cols > 0 ? pg_apply_cols(h->stream, db, c, op) : pg_apply(h->stream, db, op));
+    if ((rc = pg_down(h, out, dst, C * (op == S2M_DEBUG_PG_K ? nu : nv)))) return rc;
+    S2M_HIP(h, hipStreamSynchronize(h->stream));
+    return S2M_OK;
+}
+
+int s2m_debug_pg_cg(s2m_handle h, const s2m_pg_params* p, int32_t cols, const double* b, double* y, s2m_debug_pg_cg_out* out)
+{
+    if (!h) return S2M_ERR_INVALID_ARG;
+    if (h->pg.pending) return pg_busy(h);
+    s2m_pg_params prm;
+    if (p) prm = *p; else s2m_pg_default_params(&prm);
+    if (!params_ok(prm) || cols < 0 || cols > S2M_PG_BLOCK_COLUMNS || !b || !y || !out)
+        return fail(h, S2M_ERR_INVALID_ARG, "cg: valid params, cols 0..S2M_PG_BLOCK_COLUMNS, three arrays");
+    int rc = pg_hook_begin(h, true);
+    if (rc) return rc;
+    PgDev db = h->pg.dev;
+    PgCols c{};
+    if (cols > 0 && (rc = prepare_block(h, cols, db, c))) return rc;
+    const size_t C = (size_t)std::max(cols, 1), nv = 6 * (size_t)db.n;
+    if ((rc = pg_up(h, db.b, b, C * nv))) return rc;
+    int iters = 0;
+    if ((rc = cols > 0 ? run_cg_cols(h, db, c, prm) : run_cg(h, prm, &iters))) return rc;
+    if ((rc = pg_down(h, y, db.y, C * nv))) return rc;
+    S2M_HIP(h, hipStreamSynchronize(h->stream));
+    const PgScalars* hs = h->pg.h_sc + (cols > 0 ? 1 : 0);
+    for (size_t q = 0; q < C; q++) out[q] = s2m_debug_pg_cg_out{ hs[q].rr, hs[q].bb, hs[q].iters, hs[q].stop };
+    return S2M_OK;
+}
+
+int s2m_debug_pg_retract(s2m_handle h, int32_t n_variables, const double* delta, double* X)
+{
+    if (!h) return S2M_ERR_INVALID_ARG;
+    if (h->pg.pending) return pg_busy(h);
+    if (n_variables <= 0 || (size_t)n_variables != pg_n(h) || !delta || !X)
+        return fail(h, S2M_ERR_INVALID_ARG, "retract: 6 doubles in and 12 out for every variable of the graph");
+    int rc = pg_hook_begin(h, false);
+    if (rc) return rc;
+    const PgDev& d = h->pg.dev;
+    if ((rc = pg_up(h, d.delta, delta, 6 * (size_t)d.n))) return rc;
+    S2M_HIP(h, pg_retract(h->stream, d));
+    if ((rc = pg_down(h, X, d.Xtrial, 12 * (size_t)d.n))) return rc;
+    S2M_HIP(h, hipStreamSynchronize(h->stream));
+    return S2M_OK;
 }
 
 int s2m_pg_get_poses(s2m_handle h, int32_t first, int32_t count, float* xyzrpy)

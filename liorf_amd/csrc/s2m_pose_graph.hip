@@ -54,13 +54,13 @@ __device__ inline void so3_log(const double* R, double* phi)
     const double v[3] = { 0.5 * (R[7] - R[5]), 0.5 * (R[2] - R[6]), 0.5 * (R[3] - R[1]) };
     const double c = 0.5 * (R[0] + R[4] + R[8] - 1.0);
     const double s = sqrt(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]);
-    if (c < -0.99999) {                                  // near pi: the axis from the largest diagonal entry
+    if (c < -0.99999) {                                  // near pi: the axis from the symmetric part, (1 - cos th) a_k a
         const double th = atan2(s, c);
         int k = 0;
         if (R[4] > R[0]) k = 1;
         if (R[8] > R[k * 4]) k = 2;
-        double col[3] = { R[k], R[3 + k], R[6 + k] };
-        col[k] += 1.0;
+        double col[3] = { 0.5 * (R[k] + R[3 * k]), 0.5 * (R[3 + k] + R[3 * k + 1]), 0.5 * (R[6 + k] + R[3 * k + 2]) };
+        col[k] -= c;
         const double nrm = sqrt(col[0] * col[0] + col[1] * col[1] + col[2] * col[2]);
         double sgn = (col[0] * v[0] + col[1] * v[1] + col[2] * v[2]) < 0.0 ? -1.0 : 1.0;
         for (int i = 0; i < 3; i++) phi[i] = th * sgn * col[i] / nrm;
@@ -989,6 +989,37 @@ hipError_t pg_async_segment(hipStream_t s, const PgDev& d, PgRecord* rec, double
 hipError_t pg_fwd_y(hipStream_t s, const PgDev& d)
 {
     scan_solve(s, d.fwd, d.y, d.delta, nullptr);
+    return hipGetLastError();
+}
+
+hipError_t pg_apply(hipStream_t s, const PgDev& d, int op)
+{
+    if (d.n <= 0 || op < 0 || op > 3 || (op >= 2 && d.n_extra <= 0)) return hipErrorInvalidValue;
+    if (op == 0 || op == 2) scan_solve(s, d.fwd, d.p, d.t1, nullptr);
+    if (op == 1) scan_solve(s, d.bwd, d.g, d.t2, nullptr);
+    if (op == 2) k_pg_extra_u<<<blocks_for(d.n_extra), kPgThreads, 0, s>>>(d, d.t1, d.u, nullptr);
+    if (op == 3) kt_apply(s, d, nullptr);
+    return hipGetLastError();
+}
+
+hipError_t pg_apply_cols(hipStream_t s, const PgDev& d, const PgCols& c, int op)
+{
+    if (!cols_ok(d, c) || op < 0 || op > 3 || (op >= 2 && d.n_extra <= 0)) return hipErrorInvalidValue;
+    const unsigned C = (unsigned)c.cols;
+    if (op == 0 || op == 2) scan_solve_cols(s, d.fwd, c.loc_f, d.p, d.t1, c, nullptr);
+    if (op == 1) scan_solve_cols(s, d.bwd, c.loc_b, d.g, d.t2, c, nullptr);
+    if (op == 2) k_pg_extra_u_cols<<<dim3(blocks_for(d.n_extra), C), kPgThreads, 0, s>>>(d, c, d.t1, nullptr);
+    if (op == 3) {
+        k_pg_extra_gather_cols<<<dim3(blocks_for(d.n), C), kPgThreads, 0, s>>>(d, c, nullptr);
+        scan_solve_cols(s, d.bwd, c.loc_b, d.g, d.t2, c, nullptr);
+    }
+    return hipGetLastError();
+}
+
+hipError_t pg_retract(hipStream_t s, const PgDev& d)
+{
+    if (d.n <= 0) return hipErrorInvalidValue;
+    k_pg_retract<<<blocks_for(d.n), kPgThreads, 0, s>>>(d);
     return hipGetLastError();
 }
 

@@ -66,6 +66,11 @@ hipError_t pg_cg_iterations(hipStream_t s, const PgDev& d, int count);          
 hipError_t pg_step(hipStream_t s, const PgDev& d);                                // delta = J_c^-1 y, Xtrial = X (+) delta
 hipError_t pg_bwd_unit(hipStream_t s, const PgDev& d, int key, int axis);         // b = J_c^-T e_(6 key + axis)
 hipError_t pg_fwd_y(hipStream_t s, const PgDev& d);                               // delta = J_c^-1 y
+// One operator of the linearisation on the work vectors, by the launches pg_cg_iterations queues (the observation hooks of
+// include/liorf_s2m_debug.h): 0: t1 = J_c^-1 p;  1: t2 = J_c^-T g;  2: u = K p (t1 = J_c^-1 p on the way);  3: t2 = K^T u (through g).
+// 2 and 3 need an extra factor.
+hipError_t pg_apply(hipStream_t s, const PgDev& d, int op);
+hipError_t pg_retract(hipStream_t s, const PgDev& d);                             // Xtrial = X (+) delta
 
 // ---- the block form of the linear solve: C <= kPgBlockCols right-hand sides advance in lockstep through shared launches,
 // column c = grid row c (blockIdx.y).  `d` is a copy of the graph's PgDev whose vectors b .. delta, u, partial, sc and the
@@ -82,6 +87,7 @@ hipError_t pg_bwd_unit_cols(hipStream_t s, const PgDev& d, const PgCols& c, cons
 hipError_t pg_cg_begin_cols(hipStream_t s, const PgDev& d, const PgCols& c, double tol, int max_iters);
 hipError_t pg_cg_iterations_cols(hipStream_t s, const PgDev& d, const PgCols& c, int count);      // a stopped column is not touched
 hipError_t pg_fwd_y_cols(hipStream_t s, const PgDev& d, const PgCols& c);                         // delta_c = J_c^-1 y_c
+hipError_t pg_apply_cols(hipStream_t s, const PgDev& d, const PgCols& c, int op);                 // pg_apply on every column
 // rows[12 c + 0..5] = delta_c of key ka[c], rows[12 c + 6..11] = delta_c of key kb[c] (zeros where kb[c] < 0)
 hipError_t pg_rows_cols(hipStream_t s, const PgDev& d, const PgCols& c, const PgColAt& ka, const PgColAt& kb, double* rows);
 

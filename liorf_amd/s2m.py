@@ -50,6 +50,8 @@ ABI_SYMBOLS = [
     "s2m_pg_set_initial", "s2m_pg_add_odometry", "s2m_pg_optimize", "s2m_pg_get_poses", "s2m_pg_marginal", "s2m_pg_apply_to_store",
     "s2m_pg_marginals_check_args", "s2m_pg_marginals", "s2m_pg_joint_marginal",
     "s2m_pg_optimize_launch", "s2m_pg_optimize_poll", "s2m_pg_optimize_collect", "s2m_debug_pg_rebase",
+    "s2m_debug_pg_set_estimate", "s2m_debug_pg_linearize", "s2m_debug_pg_apply", "s2m_debug_pg_apply_check_args", "s2m_debug_pg_cg",
+    "s2m_debug_pg_retract",
 ]
 S2M_RING_U8, S2M_RING_U16, S2M_RING_I32 = 0, 1, 2
 S2M_TIME_F32, S2M_TIME_U32_NS, S2M_TIME_U32, S2M_TIME_F64_REL = 0, 1, 2, 3
@@ -63,6 +65,7 @@ S2M_WARN_LEAF_TOO_SMALL = 1
 S2M_PG_PRIOR, S2M_PG_BETWEEN, S2M_PG_GPS, S2M_PG_INITIAL = 0, 1, 2, 3
 S2M_PG_PENDING, S2M_PG_IDLE = 2, 3                       # s2m_pg_optimize_launch / _poll / _collect: queued or running; nothing pending
 S2M_PG_BLOCK_COLUMNS = 24                                # right-hand sides per pass of the block solve
+S2M_DEBUG_PG_FWD, S2M_DEBUG_PG_BWD, S2M_DEBUG_PG_K, S2M_DEBUG_PG_KT = 0, 1, 2, 3   # operators of s2m_debug_pg_apply
 PG_MARGINALS_KEYS_PER_PASS = S2M_PG_BLOCK_COLUMNS // 6   # keys one pass of s2m_pg_marginals serves
 
 
@@ -181,6 +184,11 @@ class PgResult(C.Structure):
     _fields_ = [("iterations", C.c_int32), ("inner_iterations", C.c_int32), ("converged", C.c_int32), ("n_variables", C.c_int32),
                 ("n_factors", C.c_int32), ("reserved", C.c_int32), ("error_before", C.c_double), ("error_after", C.c_double),
                 ("robust_weight_min", C.c_double)]
+
+
+class PgCgOut(C.Structure):
+    """s2m_debug_pg_cg_out (include/liorf_s2m_debug.h)."""
+    _fields_ = [("rr", C.c_double), ("bb", C.c_double), ("iters", C.c_int32), ("stop", C.c_int32)]
 
 
 class S2MError(RuntimeError):
@@ -324,6 +332,12 @@ def load_library(path: str | None = None) -> C.CDLL:
     L.s2m_pg_optimize_poll.argtypes = [vp, C.POINTER(PgResult)]
     L.s2m_pg_optimize_collect.argtypes = [vp, C.POINTER(PgResult)]
     L.s2m_debug_pg_rebase.argtypes = [dp, dp, dp]
+    L.s2m_debug_pg_set_estimate.argtypes = [vp, C.c_int32, dp]
+    L.s2m_debug_pg_linearize.argtypes = [vp, C.c_int32, C.c_int32] + [dp] * 10
+    L.s2m_debug_pg_apply.argtypes = [vp, C.c_int32, C.c_int32, dp, dp]
+    L.s2m_debug_pg_apply_check_args.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int32, dp, dp]
+    L.s2m_debug_pg_cg.argtypes = [vp, C.POINTER(PgParams), C.c_int32, dp, dp, C.POINTER(PgCgOut)]
+    L.s2m_debug_pg_retract.argtypes = [vp, C.c_int32, dp, dp]
     L.s2m_pg_get_poses.argtypes = [vp, C.c_int32, C.c_int32, fp]
     L.s2m_pg_marginal.argtypes = [vp, C.c_int32, dp]
     L.s2m_pg_apply_to_store.argtypes = [vp, C.c_int32, C.c_int32]
@@ -977,6 +991,57 @@ class MapOptimizationS2M:
             count = self.pgSize()[0] - first
         self._check(self.lib.s2m_pg_apply_to_store(self.h, first, count), "s2m_pg_apply_to_store")
 
+    # -- observation hooks of the pose graph's stages (include/liorf_s2m_debug.h) --------
+    def pgSetEstimate(self, key: int, R, t):
+        """s2m_debug_pg_set_estimate: the estimate of `key` from a 3x3 rotation and a translation in fp64, taken as they are."""
+        X = np.concatenate([np.asarray(R, np.float64).reshape(9), np.asarray(t, np.float64).reshape(3)])
+        self._check(self.lib.s2m_debug_pg_set_estimate(self.h, key, _dp(X)), "s2m_debug_pg_set_estimate")
+
+    def pgLinearize(self) -> dict:
+        """s2m_debug_pg_linearize at the current estimates: rc, Binv, Aof (chain, by key), Ji, Jj, rx (extra factors), ferr, fw
+        (chain first), err, wmin."""
+        n, nf = self.pgSize()
+        m = nf - n
+        o = dict(rc=np.zeros((n, 6)), Binv=np.zeros((n, 6, 6)), Aof=np.zeros((n, 6, 6)), Ji=np.zeros((m, 6, 6)), Jj=np.zeros((m, 6, 6)),
+                 rx=np.zeros((m, 6)), ferr=np.zeros(n + m), fw=np.zeros(n + m))
+        err, wmin = np.zeros(1), np.zeros(1)
+        self._check(self.lib.s2m_debug_pg_linearize(self.h, n, m, *[_dp(o[k]) for k in ("rc", "Binv", "Aof", "Ji", "Jj", "rx", "ferr", "fw")],
+                                                    _dp(err), _dp(wmin)), "s2m_debug_pg_linearize")
+        o["err"], o["wmin"] = float(err[0]), float(wmin[0])
+        return o
+
+    def pgApply(self, op: int, v, block: bool = False) -> np.ndarray:
+        """s2m_debug_pg_apply: one operator (S2M_DEBUG_PG_*) of the linearisation at the current estimates on the vector `v`
+        (single form) or, with block=True, on the rows of `v` (1 .. S2M_PG_BLOCK_COLUMNS of them) in the block form."""
+        n, nf = self.pgSize()
+        m = nf - n
+        a = np.ascontiguousarray(v, np.float64)
+        cols = a.shape[0] if block else 0
+        lin, lout = (6 * m if op == S2M_DEBUG_PG_KT else 6 * n), (6 * m if op == S2M_DEBUG_PG_K else 6 * n)
+        a = a.reshape(max(cols, 1), lin)
+        out = np.zeros((max(cols, 1), lout))
+        self._check(self.lib.s2m_debug_pg_apply(self.h, op, cols, _dp(a), _dp(out)), "s2m_debug_pg_apply")
+        return out if block else out[0]
+
+    def pgCg(self, b, params: PgParams | None = None, block: bool = False):
+        """s2m_debug_pg_cg: the CG on (I + K^T K) y = b at the current estimates; returns (y, [PgCgOut per column])."""
+        n = self.pgSize()[0]
+        a = np.ascontiguousarray(b, np.float64)
+        cols = a.shape[0] if block else 0
+        a = a.reshape(max(cols, 1), 6 * n)
+        y = np.zeros_like(a)
+        out = (PgCgOut * max(cols, 1))()
+        self._check(self.lib.s2m_debug_pg_cg(self.h, C.byref(params) if params is not None else None, cols, _dp(a), _dp(y), out), "s2m_debug_pg_cg")
+        return (y if block else y[0]), list(out)
+
+    def pgRetract(self, delta) -> np.ndarray:
+        """s2m_debug_pg_retract: (n, 12) states X (+) delta for the (n, 6) host `delta`; the estimates stay."""
+        n = self.pgSize()[0]
+        d = np.ascontiguousarray(delta, np.float64).reshape(n, 6)
+        X = np.zeros((n, 12))
+        self._check(self.lib.s2m_debug_pg_retract(self.h, n, _dp(d), _dp(X)), "s2m_debug_pg_retract")
+        return X
+
     def saveKeyFramesAndFactor(self, pose_xyzrpy, time: float, cloud=None, loops=(), params: PgParams | None = None):
         """saveKeyFramesAndFactor() (reference :1536-1609) without the saveFrame() gate and the GPS queue, which stay with the
         caller: odometry factor, the queued loop factors `loops` (tuples for addLoopFactor), the update - and, as the
@@ -1198,6 +1263,12 @@ def pg_rebase(a_launch, a_now, X) -> np.ndarray:
     if rc != S2M_OK:
         raise S2MError(rc, "s2m_debug_pg_rebase")
     return x
+
+
+def pg_apply_check_args(n_variables: int, n_extra: int, op: int, cols: int, has_in: bool = True, has_out: bool = True) -> int:
+    """s2m_debug_pg_apply_check_args (host only, no GPU): the status code."""
+    a = np.zeros(1)
+    return load_library().s2m_debug_pg_apply_check_args(n_variables, n_extra, op, cols, _dp(a) if has_in else None, _dp(a) if has_out else None)
 
 
 def pg_marginals_check_args(n_variables: int, keys, n_keys: int | None = None) -> int:

@@ -58,11 +58,11 @@ def so3_log(R):
     v = 0.5 * np.array([R[2, 1] - R[1, 2], R[0, 2] - R[2, 0], R[1, 0] - R[0, 1]])
     c = 0.5 * (R[0, 0] + R[1, 1] + R[2, 2] - 1.0)
     s = math.sqrt(float(v @ v))
-    if c < -0.99999:                       # near pi: the axis from the largest diagonal entry
+    if c < -0.99999:                       # near pi: the axis from the symmetric part, 0.5 (R + R^T) - c I = (1 - cos th) a a^T
         th = math.atan2(s, c)
         d = np.array([R[0, 0], R[1, 1], R[2, 2]])
         k = int(np.argmax(d))
-        col = (R[:, k] + np.eye(3)[k]).copy()
+        col = 0.5 * (R[:, k] + R[k, :]) - c * np.eye(3)[k]
         col /= math.sqrt(float(col @ col))
         if float(col @ v) < 0.0:
             col = -col
@@ -79,6 +79,17 @@ def so3_jr_inv(phi):
         return np.eye(3) + 0.5 * K + (K @ K) / 12.0
     th = math.sqrt(th2)
     return np.eye(3) + 0.5 * K + (1.0 / th2 - (1.0 + math.cos(th)) / (2.0 * th * math.sin(th))) * (K @ K)
+
+
+def so3_jr(phi):
+    th2 = float(phi @ phi)
+    K = hat(phi)
+    if th2 < 1e-10:
+        return np.eye(3) - 0.5 * K + (K @ K) / 6.0
+    th = math.sqrt(th2)
+    # (1 - cos th keeps 1.1e-16 / (th^2 / 2) of its digits: the entries of the K term are off by up to 2.2e-16 / th, 2e-11 just
+    # above the switch; the device's form, kept as it is - 2 sin^2(th / 2) would be exact)
+    return np.eye(3) - ((1.0 - math.cos(th)) / th2) * K + ((th - math.sin(th)) / (th2 * th)) * (K @ K)
 
 
 def retract(R, t, d):
@@ -191,21 +202,29 @@ def _factor_rows(g, X):
     return out
 
 
-def linearize(g, X):
-    """Whitened, robust-weighted rows.  Returns (list of (keys, blocks, r), error, minimum robust weight)."""
-    rows, err, wmin = [], 0.0, 1.0
+def linearize_factors(g, X):
+    """Every factor, whitened and robust-weighted: list of (keys, blocks, r, error term, robust weight)."""
+    out = []
     for keys, blocks, r, sw, k in _factor_rows(g, X):
         rw = r * sw
         e2 = float(rw @ rw)
         if k > 0.0:
             w = k * k / (k * k + e2)
-            err += 0.5 * k * k * math.log1p(e2 / (k * k))
-            wmin = min(wmin, w)
+            e = 0.5 * k * k * math.log1p(e2 / (k * k))
             s = math.sqrt(w)
         else:
-            err += 0.5 * e2
-            s = 1.0
-        rows.append((keys, tuple((B * sw[:, None]) * s for B in blocks), rw * s))
+            w, e, s = 1.0, 0.5 * e2, 1.0
+        out.append((keys, tuple((B * sw[:, None]) * s for B in blocks), rw * s, e, w))
+    return out
+
+
+def linearize(g, X):
+    """Whitened, robust-weighted rows.  Returns (list of (keys, blocks, r), error, minimum robust weight)."""
+    rows, err, wmin = [], 0.0, 1.0
+    for keys, blocks, r, e, w in linearize_factors(g, X):
+        err += e
+        wmin = min(wmin, w)
+        rows.append((keys, blocks, r))
     return rows, err, wmin
 
 

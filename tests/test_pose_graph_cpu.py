@@ -19,15 +19,20 @@ from liorf_amd import s2m  # noqa: E402
 PG_SYMBOLS = ["s2m_pg_default_params", "s2m_pg_check_args", "s2m_pg_reset", "s2m_pg_size", "s2m_pg_add_prior", "s2m_pg_add_between",
               "s2m_pg_add_gps", "s2m_pg_set_initial", "s2m_pg_add_odometry", "s2m_pg_optimize", "s2m_pg_get_poses", "s2m_pg_marginal",
               "s2m_pg_apply_to_store"]
+# the observation hooks of the stages: outside the drop-in boundary (include/liorf_s2m_debug.h)
+PG_DEBUG_SYMBOLS = ["s2m_debug_pg_rebase", "s2m_debug_pg_set_estimate", "s2m_debug_pg_linearize", "s2m_debug_pg_apply",
+                    "s2m_debug_pg_apply_check_args", "s2m_debug_pg_cg", "s2m_debug_pg_retract"]
 
 
 def test_symbols_are_exported_and_declared():
     lib = s2m.load_library()
     header = open(os.path.join(ROOT, "include", "liorf_s2m.h")).read()
-    for name in PG_SYMBOLS:
-        assert hasattr(lib, name), name
-        assert name in s2m.ABI_SYMBOLS, name
-        assert name + "(" in header, name
+    debug = open(os.path.join(ROOT, "include", "liorf_s2m_debug.h")).read()
+    for names, text, other in ((PG_SYMBOLS, header, debug), (PG_DEBUG_SYMBOLS, debug, header)):
+        for name in names:
+            assert hasattr(lib, name), name
+            assert name in s2m.ABI_SYMBOLS, name
+            assert name + "(" in text and name + "(" not in other, name
 
 
 def test_defaults_are_the_reference_literals():
@@ -74,19 +79,48 @@ def _rnd_pose(rng):
     return P.so3_exp(rng.normal(0, 0.8, 3)), rng.normal(0, 3, 3)
 
 
+def _check_jacobians(Xi, Xj, Z, h, tol):
+    _r, Ji, Jj = P.between_residual(Xi, Xj, *Z)
+    _rp, Dp = P.prior_residual(Xj, *Z)
+    worst = 0.0
+    for a in range(6):
+        d = np.zeros(6); d[a] = h
+        ni = (P.between_residual(P.retract(*Xi, d), Xj, *Z, jac=False) - P.between_residual(P.retract(*Xi, -d), Xj, *Z, jac=False)) / (2 * h)
+        nj = (P.between_residual(Xi, P.retract(*Xj, d), *Z, jac=False) - P.between_residual(Xi, P.retract(*Xj, -d), *Z, jac=False)) / (2 * h)
+        npr = (P.prior_residual(P.retract(*Xj, d), *Z)[0] - P.prior_residual(P.retract(*Xj, -d), *Z)[0]) / (2 * h)
+        worst = max(worst, np.abs(ni - Ji[:, a]).max(), np.abs(nj - Jj[:, a]).max(), np.abs(npr - Dp[:, a]).max())
+    assert worst < tol, worst
+    return worst
+
+
 def test_reference_jacobians_against_central_differences():
     rng = np.random.default_rng(P.SEED)
-    h = 1e-6
     for _ in range(10):
-        Xi, Xj, Z = _rnd_pose(rng), _rnd_pose(rng), _rnd_pose(rng)
-        _r, Ji, Jj = P.between_residual(Xi, Xj, *Z)
-        _rp, Dp = P.prior_residual(Xj, *Z)
+        _check_jacobians(_rnd_pose(rng), _rnd_pose(rng), _rnd_pose(rng), 1e-6, 1e-7)
+    # residual rotations of pi - d about a skew axis: Xj = Xi Z Exp(w) for the between factor, Xj = Z Exp(w) for the prior.
+    # The step stays inside the distance to pi (the log's cut) and, at 4.6e-3 and 4.4e-3, on its side of the branch threshold
+    # (4.472e-3): h = d / 100, at most 1e-6.  The differences' own rounding is 1e-16 / sin(theta) / h per entry in the general
+    # branch (5e-9 at d = 4.6e-3 with h = 1e-6), 1e-16 / h in the near-pi one (1e-8 at d = 1e-6 with h = 1e-8); 1e-6 covers
+    # both with the truncation h^2, and is a millionth of the 0.94 the log's former near-pi axis was off by.
+    axis = np.array([0.6, 0.64, 0.48]) / np.linalg.norm([0.6, 0.64, 0.48])
+    for d in (1e-2, 4.6e-3, 4.4e-3, 1e-3, 1e-6):
+        Xi, Z = _rnd_pose(rng), _rnd_pose(rng)
+        E = (P.so3_exp((math.pi - d) * axis), np.array([0.3, -0.2, 0.1]))
+        # the prior residual is taken at Xj against Z: give it the same residual rotation
+        Zp = (Z[0], Z[1])
+        Xj_prior = (Zp[0] @ E[0], Zp[1] + Zp[0] @ E[1])
+        h = min(1e-6, d / 100)
+        ZE = (Z[0] @ E[0], Z[1] + Z[0] @ E[1])
+        Xj = (Xi[0] @ ZE[0], Xi[1] + Xi[0] @ ZE[1])
+        worst = _check_jacobians(Xi, Xj, Z, h, 1e-6)
+        _rp, Dp = P.prior_residual(Xj_prior, *Zp)
         for a in range(6):
-            d = np.zeros(6); d[a] = h
-            ni = (P.between_residual(P.retract(*Xi, d), Xj, *Z, jac=False) - P.between_residual(P.retract(*Xi, -d), Xj, *Z, jac=False)) / (2 * h)
-            nj = (P.between_residual(Xi, P.retract(*Xj, d), *Z, jac=False) - P.between_residual(Xi, P.retract(*Xj, -d), *Z, jac=False)) / (2 * h)
-            npr = (P.prior_residual(P.retract(*Xj, d), *Z)[0] - P.prior_residual(P.retract(*Xj, -d), *Z)[0]) / (2 * h)
-            assert np.abs(ni - Ji[:, a]).max() < 1e-7 and np.abs(nj - Jj[:, a]).max() < 1e-7 and np.abs(npr - Dp[:, a]).max() < 1e-7
+            dd = np.zeros(6); dd[a] = h
+            npr = (P.prior_residual(P.retract(*Xj_prior, dd), *Zp)[0] - P.prior_residual(P.retract(*Xj_prior, -dd), *Zp)[0]) / (2 * h)
+            worst = max(worst, np.abs(npr - Dp[:, a]).max())
+        print("pi -", d, "largest gap to central differences", worst)
+        assert worst < 1e-6
+        assert abs(np.linalg.norm(P.between_residual(Xi, Xj, *Z, jac=False)[:3]) - (math.pi - d)) < 1e-12
 
 
 def test_reference_converges_to_a_stationary_point_and_its_solvers_agree():
