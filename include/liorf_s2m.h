@@ -583,6 +583,57 @@ int  s2m_sc_detect_loop(s2m_handle h, int32_t* loop_id, float* yaw_diff_rad, s2m
  * batched form in which this row is worth running on a GPU. */
 int  s2m_sc_distance(s2m_handle h, int32_t query_idx, const int32_t* cand_idx, int32_t m, double* dist, int32_t* shift);
 
+/* ---- ScanContext place query -------------------------------------------------------
+ * "Where in the stored map is this scan?": a query descriptor against EVERY stored descriptor of a range, on the
+ * device, and the K nearest keys under a threshold, each with its shift and yaw. Not a function of the reference:
+ * detectLoopClosureID compares the newest key with 3 ring-key neighbours at 7 of the 60 column shifts; this
+ * compares any descriptor with all keys, at 7 shifts or at all 60. Read-only; no existing call changes.
+ *
+ * Searched set. S is the keys of [first, first+count) outside [exclude_lo, exclude_hi). A stored-key query does
+ * not exclude itself; the caller does that with the window (exclude_lo = N-30, exclude_hi = N is the reference's
+ * NUM_EXCLUDE_RECENT).
+ * Distance, sector-key alignment (S2M_SC_ALIGN_SECTOR_KEY). d(q, c) and shift are distanceBtnScanContext(q, c)
+ * (:116-148). For a stored query they are bit for bit what s2m_sc_distance returns.
+ * Distance, full alignment (S2M_SC_ALIGN_FULL). Start from 10000000 and shift 0. For s = 0 .. 59 ascending, take
+ * distDirectSC(q, circshift(c, s)) (:69-91) whenever it is strictly smaller. Every sum runs left to right in fp64,
+ * like the oracle's restatement of distDirectSC. A NaN never wins: a candidate with no comparable sector keeps
+ * 10000000, as in the reference. The full distance is never above the sector-key one.
+ * Hits. A hit is a key of S with d < max_dist. The hits are ordered by ascending (d, key) and the first top_k are
+ * written; *n_hits is how many were written. `hits` has room for top_k records.
+ * Yaw. yaw_diff_rad is formed from shift exactly as s2m_sc_detect_loop forms it (:339).
+ * Query sources. _key queries with a stored key; _descriptor takes its sector key as an appended descriptor gets
+ * it (makeSectorkeyFromScancontext, :214-227); _scan builds the descriptor as s2m_sc_add_scan does; _projected
+ * builds it as s2m_sc_add_projected does, S2M_ERR_NO_SCAN before any s2m_project_scan. None of the four appends
+ * anything.
+ * Read-only. The calls leave the store, s2m_sc_size, the detector's rebuild counter and its searched set as they
+ * were: the next s2m_sc_detect_loop is bit for bit the one without the query. Like the other s2m_sc_* calls they
+ * work beside a pending loop closure or a pending pose-graph optimise; they run on the handle's main stream and
+ * touch only ScanContext buffers. One synchronisation per query; the ranking happens on the device.
+ * Errors and empty cases. S2M_ERR_INVALID_ARG: a null handle or null outputs; top_k outside 1..32; an unknown
+ * align; max_dist not in (0, 10000000], NaN included; first < 0, count < -1 or a range past the store; a _key
+ * query outside [0, N). S2M_OK with *n_hits = 0: an empty store; an empty S. p == NULL means the defaults. */
+#define S2M_SC_QUERY_MAX_K       32
+#define S2M_SC_ALIGN_SECTOR_KEY  0   /* distanceBtnScanContext as the reference: 7 shifts around fastAlignUsingVkey */
+#define S2M_SC_ALIGN_FULL        1   /* all 60 shifts */
+typedef struct s2m_sc_query_params {
+    int32_t first, count;            /* searched keys [first, first+count); count = -1: to the end of the store */
+    int32_t exclude_lo, exclude_hi;  /* keys in [exclude_lo, exclude_hi) are left out; lo >= hi: none */
+    int32_t top_k;                   /* 1 .. S2M_SC_QUERY_MAX_K */
+    int32_t align;                   /* S2M_SC_ALIGN_* */
+    double  max_dist;                /* a hit needs dist < max_dist; default SC_DIST_THRES 0.3 (Scancontext.h:95) */
+} s2m_sc_query_params;
+typedef struct s2m_sc_hit { double dist; int32_t key; int32_t shift; float yaw_diff_rad; int32_t reserved; } s2m_sc_hit;
+
+int  s2m_sc_query_default_params(s2m_sc_query_params* p);   /* 0, -1, 0, 0, 1, SECTOR_KEY, 0.3 */
+/* The argument table above for a store of n_stored keys: S2M_OK or S2M_ERR_INVALID_ARG. Host only, no handle. */
+int  s2m_sc_query_check_args(int32_t n_stored, const s2m_sc_query_params* p);
+int  s2m_sc_query_key       (s2m_handle h, int32_t key, const s2m_sc_query_params* p, s2m_sc_hit* hits, int32_t* n_hits);
+int  s2m_sc_query_descriptor(s2m_handle h, const double desc[S2M_SC_NUM_RING * S2M_SC_NUM_SECTOR], const s2m_sc_query_params* p,
+                             s2m_sc_hit* hits, int32_t* n_hits);
+int  s2m_sc_query_scan      (s2m_handle h, const void* pts, size_t n, size_t stride_bytes, const s2m_sc_query_params* p,
+                             s2m_sc_hit* hits, int32_t* n_hits);
+int  s2m_sc_query_projected (s2m_handle h, const s2m_sc_query_params* p, s2m_sc_hit* hits, int32_t* n_hits);
+
 /* ---- ICP loop-closure alignment ------------------------------------------
  * pcl::IterativeClosestPoint<PointType, PointType> as performRSLoopClosure / performSCLoopClosure configure
  * and run it (reference src/mapOptmization.cpp:571-586, :663-678): setMaxCorrespondenceDistance,

@@ -155,13 +155,15 @@ struct __attribute__((visibility("hidden"))) s2m_context {
     } voxel;
 
     // ScanContext (SCManager's containers, section 8(f) F3): the polar bins and descriptor + ring key of the cloud in hand, then
-    // the store - descriptors, fp32 ring keys, sector keys, by key-frame index - and the candidate list of s2m_sc_distance
+    // the store - descriptors, fp32 ring keys, sector keys, by key-frame index - and the candidate list of s2m_sc_distance; the place
+    // query's slot (descriptor + sector key of the query) and the workgroups' lists of their best hits
     struct ScanContext {
         DevBuf bins, out;
         DevBuf store_desc, store_ring, store_sector, cand;
+        DevBuf query, query_part;
         size_t n = 0, cap = 0, n_search = 0;
         int    counter = 0;                // tree_making_period_conter (include/Scancontext.cpp:270-283)
-        double* h_stage = nullptr;         // pinned [1200 + 20]: descriptor + ring key, or the detection's result
+        double* h_stage = nullptr;         // pinned [1200 + 20]: descriptor + ring key, or the detection's result, or the query's hits
     } sc;
 
     // key-frame store (cloudKeyPoses3D / cloudKeyPoses6D / surfCloudKeyFrames, :93-100): every key's 32-byte records in an arena of

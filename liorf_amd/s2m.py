@@ -38,6 +38,7 @@ ABI_SYMBOLS = [
     "s2m_icp_default_params", "s2m_icp_align", "s2m_debug_device_trig", "s2m_debug_device_hypot",
     "s2m_debug_lm_close", "s2m_debug_lm_close_check_args",
     "s2m_sc_reset", "s2m_sc_size", "s2m_sc_add_scan", "s2m_sc_add_descriptor", "s2m_sc_detect_loop", "s2m_sc_distance",
+    "s2m_sc_query_default_params", "s2m_sc_query_check_args", "s2m_sc_query_key", "s2m_sc_query_descriptor", "s2m_sc_query_scan", "s2m_sc_query_projected",
     "s2m_kf_default_params", "s2m_kf_reset", "s2m_kf_size", "s2m_kf_add", "s2m_kf_set_poses", "s2m_extract_surrounding",
     "s2m_loop_default_params", "s2m_loop_near_keyframes", "s2m_loop_align", "s2m_loop_closure_rs",
     "s2m_loop_align_launch", "s2m_loop_closure_rs_launch", "s2m_loop_poll", "s2m_loop_collect",
@@ -67,6 +68,9 @@ S2M_PG_PENDING, S2M_PG_IDLE = 2, 3                       # s2m_pg_optimize_launc
 S2M_PG_BLOCK_COLUMNS = 24                                # right-hand sides per pass of the block solve
 S2M_DEBUG_PG_FWD, S2M_DEBUG_PG_BWD, S2M_DEBUG_PG_K, S2M_DEBUG_PG_KT = 0, 1, 2, 3   # operators of s2m_debug_pg_apply
 PG_MARGINALS_KEYS_PER_PASS = S2M_PG_BLOCK_COLUMNS // 6   # keys one pass of s2m_pg_marginals serves
+S2M_SC_QUERY_MAX_K = 32
+S2M_SC_ALIGN_SECTOR_KEY, S2M_SC_ALIGN_FULL = 0, 1        # s2m_sc_query_params::align: 7 shifts around the sector-key guess; all 60
+SC_QUERY_MAX_GROUPS = 1024                               # kScQueryMaxGroups: workgroups of the query's distance kernel, 3 keys each per pass
 
 
 class Params(C.Structure):
@@ -105,6 +109,20 @@ class LmCloseOut(C.Structure):
 class ScMatch(C.Structure):
     _fields_ = [("min_dist", C.c_double), ("nn_idx", C.c_int32), ("nn_align", C.c_int32),
                 ("cand_idx", C.c_int32 * 3), ("cand_d2", C.c_float * 3)]
+
+
+class ScQueryParams(C.Structure):
+    """s2m_sc_query_params: the searched keys [first, first+count) (count = -1: to the end) outside [exclude_lo, exclude_hi)."""
+    _fields_ = [("first", C.c_int32), ("count", C.c_int32), ("exclude_lo", C.c_int32), ("exclude_hi", C.c_int32),
+                ("top_k", C.c_int32), ("align", C.c_int32), ("max_dist", C.c_double)]
+
+
+class ScHit(C.Structure):
+    _fields_ = [("dist", C.c_double), ("key", C.c_int32), ("shift", C.c_int32), ("yaw_diff_rad", C.c_float), ("reserved", C.c_int32)]
+
+
+SC_HIT_DTYPE = np.dtype([("dist", np.float64), ("key", np.int32), ("shift", np.int32), ("yaw_diff_rad", np.float32), ("reserved", np.int32)])
+assert SC_HIT_DTYPE.itemsize == C.sizeof(ScHit) == 24
 
 
 class IcpParams(C.Structure):
@@ -283,6 +301,13 @@ def load_library(path: str | None = None) -> C.CDLL:
     L.s2m_sc_add_descriptor.argtypes = [vp, dp]
     L.s2m_sc_detect_loop.argtypes = [vp, i32p, fp, C.POINTER(ScMatch)]
     L.s2m_sc_distance.argtypes = [vp, C.c_int32, i32p, C.c_int32, dp, i32p]
+    qp, hp = C.POINTER(ScQueryParams), C.POINTER(ScHit)
+    L.s2m_sc_query_default_params.argtypes = [qp]
+    L.s2m_sc_query_check_args.argtypes = [C.c_int32, qp]
+    L.s2m_sc_query_key.argtypes = [vp, C.c_int32, qp, hp, i32p]
+    L.s2m_sc_query_descriptor.argtypes = [vp, dp, qp, hp, i32p]
+    L.s2m_sc_query_scan.argtypes = [vp, vp, C.c_size_t, C.c_size_t, qp, hp, i32p]
+    L.s2m_sc_query_projected.argtypes = [vp, qp, hp, i32p]
     L.s2m_kf_default_params.argtypes = [C.POINTER(KfParams)]
     L.s2m_kf_reset.argtypes = [vp]
     L.s2m_kf_size.argtypes = [vp]
@@ -834,6 +859,33 @@ class MapOptimizationS2M:
                                              shift.ctypes.data_as(C.POINTER(C.c_int32))), "s2m_sc_distance")
         return dist, shift
 
+    # -- the place query: a descriptor against every stored key of a range, the K nearest under a threshold
+    def _sc_query(self, fn, what, args, params, kw):
+        p = params if params is not None else default_sc_query_params()
+        if kw:
+            p = default_sc_query_params(**{**{f: getattr(p, f) for f, _ in ScQueryParams._fields_}, **kw})
+        hits = np.zeros(S2M_SC_QUERY_MAX_K, SC_HIT_DTYPE)
+        n = C.c_int32(0)
+        self._check(fn(self.h, *args, C.byref(p), hits.ctypes.data_as(C.POINTER(ScHit)), C.byref(n)), what)
+        return hits[:n.value].copy()
+
+    def scQueryKey(self, key: int, params: "ScQueryParams | None" = None, **kw):
+        """s2m_sc_query_key: the hits (SC_HIT_DTYPE records, ascending (dist, key)) of stored key `key`; keyword arguments set
+        fields of the parameters."""
+        return self._sc_query(self.lib.s2m_sc_query_key, "s2m_sc_query_key", (int(key),), params, kw)
+
+    def scQueryDescriptor(self, desc, params: "ScQueryParams | None" = None, **kw):
+        d = np.ascontiguousarray(desc, np.float64).reshape(20, 60)
+        return self._sc_query(self.lib.s2m_sc_query_descriptor, "s2m_sc_query_descriptor", (d.ctypes.data_as(C.POINTER(C.c_double)),), params, kw)
+
+    def scQueryScan(self, scan, params: "ScQueryParams | None" = None, **kw):
+        a, n, st = _records(scan)
+        return self._sc_query(self.lib.s2m_sc_query_scan, "s2m_sc_query_scan", (a.ctypes.data, n, st), params, kw)
+
+    def scQueryProjected(self, params: "ScQueryParams | None" = None, **kw):
+        """The query with the descriptor of the cloud s2m_project_scan left on the device."""
+        return self._sc_query(self.lib.s2m_sc_query_projected, "s2m_sc_query_projected", (), params, kw)
+
     def makeScancontext(self, scan):
         """SCManager::makeScancontext + makeRingkeyFromScancontext (reference include/Scancontext.cpp:151-211)."""
         a, n, st = _records(scan)
@@ -1277,6 +1329,21 @@ def pg_marginals_check_args(n_variables: int, keys, n_keys: int | None = None) -
     if n_keys is None:
         n_keys = 0 if k is None else k.shape[0]
     return load_library().s2m_pg_marginals_check_args(n_variables, None if k is None else k.ctypes.data_as(C.POINTER(C.c_int32)), n_keys)
+
+
+def default_sc_query_params(**kw) -> ScQueryParams:
+    p = ScQueryParams()
+    load_library().s2m_sc_query_default_params(C.byref(p))
+    for k, v in kw.items():
+        if not hasattr(p, k):
+            raise AttributeError(k)
+        setattr(p, k, v)
+    return p
+
+
+def sc_query_check_args(n_stored: int, params: "ScQueryParams | None") -> int:
+    """s2m_sc_query_check_args (host only, no GPU): the status code.  params=None passes a null pointer (the defaults)."""
+    return load_library().s2m_sc_query_check_args(n_stored, None if params is None else C.byref(params))
 
 
 def default_kf_params(**kw) -> KfParams:
