@@ -110,6 +110,27 @@ int  s2m_debug_lm_close(s2m_handle h, int form, int iter, const double* rows, in
 int  s2m_debug_lm_close_check_args(int form, int iter, int max_iter, const double* rows, int n_rows, const float pose0[6],
                                    const float matP_in[36], const s2m_debug_lm_close_out* out);
 
+/* Observation hook: the preparation of the RESIDENT single scan, run again by either chain, and what it left.
+ *   chain  S2M_DEBUG_PREP_NEW     what s2m_set_scan launches: k_polar_count, k_polar_prefix, the scatter with the cell scan in it,
+ *                                 k_chunk_parts; with a pose the density wishes chunk by chunk with the state upload in the same
+ *                                 launch (k_wave_density_state, as s2m_optimize_launch), then k_chunk_table_density
+ *          S2M_DEBUG_PREP_LEGACY  the six kernels a scan slot of a batch runs (k_polar_scan and k_scatter_scan apart, k_chunk_table
+ *                                 at once); with a pose the state upload, k_wave_density over that table, k_chunk_table_density
+ *          S2M_DEBUG_PREP_READ    runs nothing: the buffers as they are
+ *   pose   NULL: the ordering only - the handle is left as s2m_set_scan leaves it (density re-split pending; after the legacy
+ *          chain with the extent-only table in place, after the new one with that table still to be built on demand -
+ *          asking for wave_table or n_waves is such a demand).
+ * Outputs, each optional: qperm n; qxyz 3 n (x, then y, then z, sorted order); chunk_parts and chunk_factor one per 64-point
+ * chunk (chunk_factor as the density kernel left it, BEFORE k_chunk_table_density consumed it; without a pose as it is);
+ * wave_table 2 per entry {first point, count}, room for the scan's table capacity (n/64 rounded up, times 12, plus 64 is
+ * enough); *n_waves the entries in use (-1 with READ while no table has been built). The source of the scan must still be
+ * readable (a host scan is: the library keeps its copy). The certificates of the scan are reset as by s2m_set_scan. */
+#define S2M_DEBUG_PREP_READ   (-1)
+#define S2M_DEBUG_PREP_NEW    0
+#define S2M_DEBUG_PREP_LEGACY 1
+int  s2m_debug_scan_prep(s2m_handle h, int32_t chain, const float pose[6], int32_t* qperm, float* qxyz, int32_t* chunk_parts,
+                         int32_t* chunk_factor, int32_t* wave_table, int32_t* n_waves);
+
 /* ---- the device loop of the ICP alignment (what s2m_loop_*_launch queues) -------------------------------------------
  * S2M_ICP_RANGE: iterations queued at a time; between two ranges the host looks at the state block once. */
 #define S2M_ICP_RANGE 8

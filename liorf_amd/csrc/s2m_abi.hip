@@ -204,7 +204,8 @@ int set_map_build(s2m_context* h, const void* pts, size_t n, size_t stride, bool
 
 // s2m_set_scan in three steps, so that the scan slots of a batch share the launches of the middle one:
 //   scan_slot_prepare   host side: sizes, buffers, the upload of a host source, the DevCtx fields - and the slot's row of the table
-//   launch_scan_prep    the six ordering kernels, one grid row per slot (blockIdx.y)
+//   launch_scan_prep    the ordering kernels, one grid row per slot (blockIdx.y): six for the slots of a batch, four for a single
+//                       scan (the cell scan inside the scatter; the wave table left to the scan's first optimisation)
 //   scan_slot_finish    bookkeeping
 int scan_slot_prepare(s2m_context* h, const void* pts, size_t n, size_t stride, bool on_device, PrepSlot* ps)
 {
@@ -279,6 +280,7 @@ int scan_slot_prepare(s2m_context* h, const void* pts, size_t n, size_t stride, 
     ps->cert = h->reg.cert.as<float4>(); ps->aux = h->reg.aux.as<int4>();
     ps->chunk_parts = h->reg.chunk_parts.as<int32_t>(); ps->wave_table = h->reg.wave_table.as<int2>(); ps->n_waves = h->reg.n_waves.as<int32_t>();
     ps->stamps = nullptr;                                 // (set_scan_impl: a single scan times its preparation)
+    h->reg.prep_slot = *ps;
 
     h->hctx.qx = h->reg.qx.as<float>(); h->hctx.qy = h->reg.qy.as<float>(); h->hctx.qz = h->reg.qz.as<float>();
     h->hctx.qperm = h->reg.qperm.as<int32_t>();
@@ -302,7 +304,11 @@ int scan_slot_prepare(s2m_context* h, const void* pts, size_t n, size_t stride, 
 }
 
 // the ordering kernels of `nslots` prepared slots (rows with n = 0 do nothing), on `stream`
-void launch_scan_prep(hipStream_t stream, const PrepTable& t, int nslots)
+// `single` (a scan of the handle's own, one slot): k_polar_count, k_polar_prefix, the scatter with the cell scan in it,
+// k_chunk_parts - and no wave table: the scan's first optimisation asks for the density wishes chunk by chunk
+// (k_wave_density_state) and k_chunk_table_density emits the table once; whatever else needs the extent-only table first
+// builds it through ensure_wave_table.
+void launch_scan_prep(hipStream_t stream, const PrepTable& t, int nslots, bool single = false)
 {
     int npb = 0, nb = 0, ncb = 0;
     for (int k = 0; k < nslots; k++) {
@@ -313,10 +319,35 @@ void launch_scan_prep(hipStream_t stream, const PrepTable& t, int nslots)
     if (npb == 0) return;
     hipLaunchKernelGGL(k_polar_count, dim3(npb, nslots), dim3(kPolarBlock), 0, stream, t);
     hipLaunchKernelGGL(k_polar_prefix, dim3(kPolarCells / 64, nslots), dim3(1024), 0, stream, t);
+    if (single) {
+        hipLaunchKernelGGL(k_scatter_scan_fold, dim3(npb, nslots), dim3(1024), 0, stream, t);
+        hipLaunchKernelGGL(k_chunk_parts, dim3(ncb, nslots), dim3(256), 0, stream, t);
+        return;
+    }
     hipLaunchKernelGGL(k_polar_scan, dim3(1, nslots), dim3(1024), 0, stream, t);
     hipLaunchKernelGGL(k_scatter_scan, dim3(nb, nslots), dim3(256), 0, stream, t);
     hipLaunchKernelGGL(k_chunk_parts, dim3(ncb, nslots), dim3(256), 0, stream, t);
     hipLaunchKernelGGL(k_chunk_table, dim3(1, nslots), dim3(1024), 0, stream, t);
+}
+
+// the PrepSlot row of the resident scan, as far as k_chunk_table reads it
+void table_slot_of(s2m_context* h, PrepSlot* ps)
+{
+    memset(ps, 0, sizeof(*ps));
+    ps->n = (int32_t)h->reg.n_q; ps->n_chunks = h->hctx.n_chunks; ps->capacity = h->hctx.table_cap;
+    ps->chunk_parts = h->reg.chunk_parts.as<int32_t>(); ps->wave_table = h->reg.wave_table.as<int2>(); ps->n_waves = h->reg.n_waves.as<int32_t>();
+}
+
+// The extent-only wave table of a single scan is built on demand: by whatever reads the table or its wave count before the
+// scan's first optimisation has emitted the density-aware one (the observation and timing hooks, a handle with the density
+// pass switched off).
+void ensure_wave_table(s2m_context* h)
+{
+    if (!h->reg.table_stale) return;
+    PrepTable t;
+    table_slot_of(h, &t.s[0]);
+    hipLaunchKernelGGL(k_chunk_table, dim3(1, 1), dim3(1024), 0, h->stream, t);
+    h->reg.table_stale = false;
 }
 
 }  // namespace
@@ -327,11 +358,14 @@ int s2m::host::set_scan_impl(s2m_context* h, const void* pts, size_t n, size_t s
     PrepTable t;
     int rc = scan_slot_prepare(h, pts, n, stride, on_device, &t.s[0]);
     if (rc) return rc;
-    if (n == 0) { h->reg.t_set_scan_ms = 0; h->reg.scan_timing_pending = false; return upload_ctx(h); }
+    if (n == 0) { h->reg.t_set_scan_ms = 0; h->reg.scan_timing_pending = false; h->reg.table_stale = false; return upload_ctx(h); }
     // the first and the last ordering kernel stamp the device's wall clock into the pinned block (s2m_last_timing): an event
     // record on either side is a packet of its own in the queue, 5.7 us of idle GPU each
+    // (the last one is k_chunk_parts: PrepSlot::stamps)
     t.s[0].stamps = h->reg.h_stamps + kStampPrep0;
-    launch_scan_prep(h->stream, t, 1);
+    const bool single = h->batch.parent == nullptr;       // the slots of a batch and of a stream of scans keep the six kernels
+    launch_scan_prep(h->stream, t, 1, single);
+    h->reg.table_stale = single;
     S2M_HIP(h, hipGetLastError());
     h->reg.scan_timing_pending = true;
     // (the DevCtx block goes to the device with the next launch that needs it: upload_ctx / push_state)
@@ -359,6 +393,7 @@ int push_state(s2m_context* h, const float pose[6], unsigned long long* stamp = 
 {
     DevState s;
     fill_state(h, &s, pose);
+    ensure_wave_table(h);                                 // (k_set_state copies the wave count)
     if (h->ctx_dirty) {
         hipLaunchKernelGGL(k_set_ctx_state, dim3(1), dim3(64), 0, h->stream, h->reg.dctx.as<DevCtx>(), h->hctx, h->reg.state.as<DevState>(), s,
                            (const int32_t*)h->reg.n_waves.as<int32_t>(), stamp);
@@ -380,7 +415,8 @@ int push_state(s2m_context* h, const float pose[6], unsigned long long* stamp = 
 // The plain form  R0 F0 R1 F1 ...  remains for A/B measurements (S2M_NO_FUSE=1).
 // Several scan slots (a batch) advance in lockstep: every launch has one grid row per slot.
 constexpr int kFuseMaxBlocks = 512;
-static_assert(sizeof(CtxTable) <= 4096 && sizeof(StateInitTable) <= 4096 && sizeof(PrepTable) <= 4096 && sizeof(SlotTable) <= 4096,
+static_assert(sizeof(CtxTable) <= 4096 && sizeof(StateInitTable) <= 4096 && sizeof(PrepTable) <= 4096 && sizeof(SlotTable) <= 4096 &&
+              sizeof(DensityStateArgs) <= 4096,
               "kernel arguments are limited to 4 KB");
 
 // what one loop launches over: the scan slots (one for a single scan), the widest grid among them, their common workgroup shape
@@ -394,6 +430,7 @@ struct LoopShape {
     bool split = false;     // C + S per iteration instead of R
     bool late = false;      // the split iterations of this loop come late (few rows on the worklist): small search grid
     bool split_auto = false; // split if the loop's iterations are closed by k_finalize and the lean certify kernel applies
+    bool wishes_done = false; // the density wishes of a pending re-split are in chunk_factor already (s2m_optimize_launch): the loop starts with k_chunk_table_density
     // a captured single-scan loop: the k_finalize that ends the range copies state + trace to `out` (the pinned mirror) and
     // stamps the wall clock at `stamp`; both null: the caller copies (plain launches, batches, diagnostics)
     DevState* out = nullptr;
@@ -478,7 +515,7 @@ inline void launch_density(s2m_context* h, const LoopShape& sh)
 {
     // re-split the wave table for the map density at the initial guess (the transform k_set_state just stored);
     // both kernels take everything from the DevCtx block, so the captured graph stays valid from scan to scan
-    hipLaunchKernelGGL(k_wave_density, dim3((sh.table_cap + 3) / 4, sh.nslots), dim3(256), 0, h->stream, sh.tbl, h->tune.density_raw);
+    if (!sh.wishes_done) hipLaunchKernelGGL(k_wave_density, dim3((sh.table_cap + 3) / 4, sh.nslots), dim3(256), 0, h->stream, sh.tbl, h->tune.density_raw);
     hipLaunchKernelGGL(k_chunk_table_density, dim3(1, sh.nslots), dim3(1024), 0, h->stream, sh.tbl);
 }
 
@@ -521,6 +558,7 @@ int get_graph(s2m_context* h, int nblocks, int part, hipGraphExec_t* out)
     // graph starts ~10 us after the graph's last kernel.)  The first range - the whole loop, mostly - also stamps its end.
     sh.out = &h->reg.h_state[1];
     sh.stamp = part == 2 ? nullptr : h->reg.h_stamps + kStampLoop1;
+    sh.wishes_done = h->batch.parent == nullptr;          // a single scan: k_wave_density_state ran as a plain launch in front of the graph
     const long long key = (((long long)h->hctx.table_cap * 4 + part) * 256 + (part ? h->tune.seg_iters : 0)) * 4 + (sh.split ? 1 : 0) + (sh.wpb == kBigWaves ? 2 : 0);
     auto it = h->reg.graphs.find(key);
     if (it != h->reg.graphs.end()) { *out = it->second; return S2M_OK; }
@@ -557,6 +595,7 @@ int launch_loop(s2m_context* h, int part = 0)
     }
     LoopShape sh = shape_of(h);
     sh.stamp = part == 2 ? nullptr : h->reg.h_stamps + kStampLoop1;
+    sh.wishes_done = h->batch.parent == nullptr;
     if (part == 2) S2M_HIP(h, hipEventRecord(h->reg.ev_a2, h->stream));
     enqueue_loop(h, sh, nullptr, false, part == 2 ? h->tune.seg_iters : 0, part == 1 ? h->tune.seg_iters : -1);
     S2M_HIP(h, hipGetLastError());
@@ -823,7 +862,20 @@ int s2m_optimize_launch(s2m_handle h, const float pose[6])
     if (h->reg.n_m == 0) { h->reg.pending_skipped = 1; return S2M_OK; }                    // :1297
     if ((int)h->reg.n_q <= h->prm.min_feats) { h->reg.pending_skipped = 2; return S2M_OK; } // :1300
     int rc;
-    if ((rc = push_state(h, pose, h->reg.h_stamps + kStampLoop0))) return rc;             // (with the DevCtx block when that changed)
+    if (!h->batch.parent && h->hctx.density_pending && h->tune.density_raw > 0) {
+        // the first optimisation of a single scan: the density wishes, the DevCtx block and the loop state in one plain launch
+        // (k_wave_density_state needs no wave table; the graph behind it starts with k_chunk_table_density)
+        DensityStateArgs a;
+        a.c = h->hctx;
+        fill_state(h, &a.v, pose);
+        a.cdst = h->reg.dctx.as<DevCtx>(); a.sdst = h->reg.state.as<DevState>();
+        a.stamp = h->reg.h_stamps + kStampLoop0;
+        a.raw_limit = h->tune.density_raw;
+        hipLaunchKernelGGL(k_wave_density_state, dim3((h->hctx.n_chunks + 3) / 4 + 1), dim3(256), 0, h->stream, a);       // (+ 1: the workgroup that stores the blocks)
+        S2M_HIP(h, hipGetLastError());
+        h->ctx_dirty = false;
+        h->reg.table_stale = false;                       // k_chunk_table_density emits the table
+    } else if ((rc = push_state(h, pose, h->reg.h_stamps + kStampLoop0))) return rc;      // (with the DevCtx block when that changed)
     h->reg.seg_pending = h->prm.early_exit && h->tune.seg_iters > 1 && h->tune.seg_iters < h->prm.max_iter;
     if ((rc = launch_loop(h, h->reg.seg_pending ? 1 : 0))) return rc;        // (state + trace come back with it)
     return S2M_OK;
@@ -1401,6 +1453,7 @@ int s2m_debug_lm_close(s2m_handle h, int form, int iter, const double* rows, int
     int rc;
     if ((rc = upload_ctx(h))) return rc;                   // (the parameters of the last s2m_set_params with it)
     // the rows a close reads: one per workgroup the wave table of the resident scan needs (k_finalize, k_register)
+    ensure_wave_table(h);
     int32_t n_waves = 0;
     S2M_HIP(h, hipMemcpyAsync(&n_waves, h->reg.n_waves.p, sizeof(n_waves), hipMemcpyDeviceToHost, h->stream));
     S2M_HIP(h, hipStreamSynchronize(h->stream));
@@ -1466,6 +1519,76 @@ int s2m_normal_eq(s2m_handle h, const float pose[6], float AtA[36], float AtB[6]
     if (AtA) memcpy(AtA, h->reg.h_state[1].AtA, sizeof(float) * 36);
     if (AtB) memcpy(AtB, h->reg.h_state[1].AtB, sizeof(float) * 6);
     if (n_sel) *n_sel = h->reg.h_state[1].n_sel_last;
+    return S2M_OK;
+}
+
+int s2m_debug_scan_prep(s2m_handle h, int32_t chain, const float pose[6], int32_t* qperm, float* qxyz, int32_t* chunk_parts,
+                        int32_t* chunk_factor, int32_t* wave_table, int32_t* n_waves)
+{
+    if (!h || chain < S2M_DEBUG_PREP_READ || chain > S2M_DEBUG_PREP_LEGACY) return S2M_ERR_INVALID_ARG;
+    if (h->batch.parent) return fail(h, S2M_ERR_INVALID_ARG, "a scan slot of a batch keeps the six-kernel chain");
+    if (h->reg.opt_pending) return fail(h, S2M_ERR_INVALID_ARG, "an optimize launch is pending: collect it first");
+    if (!h->reg.have_scan) return fail(h, S2M_ERR_NO_SCAN, "s2m_set_scan has not been called");
+    const size_t n = h->reg.n_q;
+    if (n == 0) { if (n_waves) *n_waves = 0; return S2M_OK; }
+    if (pose && chain != S2M_DEBUG_PREP_READ && h->reg.n_m == 0) return fail(h, S2M_ERR_NO_SCAN, "the density pass needs a map");
+    S2M_HIP(h, hipSetDevice(h->device));
+    const int n_chunks = h->hctx.n_chunks;
+    if (chain != S2M_DEBUG_PREP_READ) {
+        const bool legacy = chain == S2M_DEBUG_PREP_LEGACY;
+        PrepTable t;
+        t.s[0] = h->reg.prep_slot;
+        S2M_HIP(h, hipMemsetAsync(h->reg.chunk_factor.p, 0, sizeof(int32_t) * (size_t)(n_chunks + 1), h->stream));
+        launch_scan_prep(h->stream, t, 1, !legacy);
+        S2M_HIP(h, hipGetLastError());
+        h->reg.table_stale = !legacy;
+        h->hctx.density_pending = 1;
+        h->ctx_dirty = true;
+        if (pose) {
+            const LoopShape sh = shape_of(h);
+            if (legacy) {
+                int rc = push_state(h, pose);
+                if (rc) return rc;
+                hipLaunchKernelGGL(k_wave_density, dim3((sh.table_cap + 3) / 4, 1), dim3(256), 0, h->stream, sh.tbl, h->tune.density_raw);
+            } else {
+                DensityStateArgs a;
+                a.c = h->hctx;
+                fill_state(h, &a.v, pose);
+                a.cdst = h->reg.dctx.as<DevCtx>(); a.sdst = h->reg.state.as<DevState>();
+                a.stamp = nullptr;
+                a.raw_limit = h->tune.density_raw;
+                hipLaunchKernelGGL(k_wave_density_state, dim3((n_chunks + 3) / 4 + 1), dim3(256), 0, h->stream, a);
+                h->ctx_dirty = false;
+                h->reg.table_stale = false;
+            }
+            S2M_HIP(h, hipGetLastError());
+            // the wishes before k_chunk_table_density consumes them
+            if (chunk_factor) S2M_HIP(h, hipMemcpyAsync(chunk_factor, h->reg.chunk_factor.p, sizeof(int32_t) * (size_t)n_chunks, hipMemcpyDeviceToHost, h->stream));
+            hipLaunchKernelGGL(k_chunk_table_density, dim3(1, 1), dim3(1024), 0, h->stream, sh.tbl);
+            S2M_HIP(h, hipGetLastError());
+            h->hctx.density_pending = 0;                  // cleared on the device by the kernel: keep the host copy in step
+        } else if (wave_table || n_waves)
+            ensure_wave_table(h);
+    }
+    if ((!pose || chain == S2M_DEBUG_PREP_READ) && chunk_factor)
+        S2M_HIP(h, hipMemcpyAsync(chunk_factor, h->reg.chunk_factor.p, sizeof(int32_t) * (size_t)n_chunks, hipMemcpyDeviceToHost, h->stream));
+    if (qperm) S2M_HIP(h, hipMemcpyAsync(qperm, h->reg.qperm.p, sizeof(int32_t) * n, hipMemcpyDeviceToHost, h->stream));
+    if (qxyz) {
+        S2M_HIP(h, hipMemcpyAsync(qxyz, h->reg.qx.p, sizeof(float) * n, hipMemcpyDeviceToHost, h->stream));
+        S2M_HIP(h, hipMemcpyAsync(qxyz + n, h->reg.qy.p, sizeof(float) * n, hipMemcpyDeviceToHost, h->stream));
+        S2M_HIP(h, hipMemcpyAsync(qxyz + 2 * n, h->reg.qz.p, sizeof(float) * n, hipMemcpyDeviceToHost, h->stream));
+    }
+    if (chunk_parts) S2M_HIP(h, hipMemcpyAsync(chunk_parts, h->reg.chunk_parts.p, sizeof(int32_t) * (size_t)n_chunks, hipMemcpyDeviceToHost, h->stream));
+    int32_t nw = 0;
+    const bool have_table = !h->reg.table_stale;
+    if (have_table) S2M_HIP(h, hipMemcpyAsync(&nw, h->reg.n_waves.p, sizeof(nw), hipMemcpyDeviceToHost, h->stream));
+    S2M_HIP(h, hipStreamSynchronize(h->stream));
+    if (nw < 0 || nw > h->hctx.table_cap) return fail(h, S2M_ERR_HIP, "wave count outside the table");
+    if (wave_table && nw > 0) {
+        S2M_HIP(h, hipMemcpyAsync(wave_table, h->reg.wave_table.p, sizeof(int2) * (size_t)nw, hipMemcpyDeviceToHost, h->stream));
+        S2M_HIP(h, hipStreamSynchronize(h->stream));
+    }
+    if (n_waves) *n_waves = have_table ? nw : -1;
     return S2M_OK;
 }
 

@@ -41,7 +41,7 @@ struct DevBuf {
 
 constexpr size_t kDsStride = 32;       // filtered clouds are kept as pcl::PointXYZI records
 
-// s2m_context::Registration::h_stamps: k_polar_count starts, k_chunk_table ends (consecutive: PrepSlot::stamps), the state
+// s2m_context::Registration::h_stamps: k_polar_count starts, k_chunk_parts ends (consecutive: PrepSlot::stamps), the state
 // upload of s2m_optimize_launch ends, the k_finalize that closes the loop's (first) range ends
 enum { kStampPrep0 = 0, kStampPrep1 = 1, kStampLoop0 = 2, kStampLoop1 = 3, kStampCount = 4 };
 
@@ -92,6 +92,8 @@ struct __attribute__((visibility("hidden"))) s2m_context {
         bool seg_pending = false;          // the launch in flight was the first range only
         bool opt_pending = false;
         bool scan_timing_pending = false;
+        s2m::PrepSlot prep_slot{};         // the resident scan's row of the ordering kernels' table (s2m_debug_scan_prep runs them again)
+        bool table_stale = false;          // a single scan is resident whose extent-only wave table has not been built (ensure_wave_table)
         int pending_skipped = 0;
         float pending_pose_in[6] = { 0 };
         s2m_iter_trace last_trace[s2m::kMaxIter];

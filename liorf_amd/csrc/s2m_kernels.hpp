@@ -559,6 +559,74 @@ __global__ void k_scatter_scan(const PrepTable tbl)
     aux[pos] = make_int4(0, 0, 0, 0);
 }
 
+// k_polar_scan and k_scatter_scan in one launch (a single scan): every 1024-point workgroup builds the exclusive scan of the
+// 16384 cell totals for itself in LDS - k_polar_scan's integer arithmetic, 16 counts per thread, a wave scan, 16 wave sums -
+// and places its points as k_scatter_scan does, with cell_start[c] taken from LDS.  Nothing else reads q_cell_start, and
+// k_polar_prefix rewrites every count, so neither the scan's result nor zeroed counts are left in memory.
+// (The 16 wave sums pass through the first words of the 64 KB array before the scan overwrites them.)
+__global__ __launch_bounds__(1024) void k_scatter_scan_fold(const PrepTable tbl)
+{
+    const PrepSlot& ps = tbl.s[blockIdx.y];
+    const int n = ps.n;
+    if (n <= 0 || (int)blockIdx.x * 1024 >= n) return;    // (uniform per workgroup)
+    const unsigned char* __restrict__ pts = ps.pts; const size_t stride = ps.stride;
+    const int32_t* __restrict__ cell_of = ps.cell_of; const int32_t* __restrict__ rank_of = ps.rank_of;
+    const int32_t* __restrict__ counts = ps.counts; const int32_t* __restrict__ block_hist = ps.block_hist;
+    float* __restrict__ qx = ps.qx; float* __restrict__ qy = ps.qy; float* __restrict__ qz = ps.qz;
+    int32_t* __restrict__ qperm = ps.qperm; float4* __restrict__ cert = ps.cert; int4* __restrict__ aux = ps.aux;
+    __shared__ int32_t start[kPolarCells];
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    const int i = blockIdx.x * 1024 + t;
+    // the point's own loads first: they are in flight while the scan is built
+    int c = 0, rank = 0, before = 0;
+    float px = 0.0f, py = 0.0f, pz = 0.0f;
+    if (i < n) {
+        const float* p = reinterpret_cast<const float*>(pts + (size_t)i * stride);
+        c = cell_of[i]; rank = rank_of[i];
+        px = p[0]; py = p[1]; pz = p[2];
+        before = block_hist[(size_t)blockIdx.x * kPolarCells + c];     // (i / kPolarBlock == blockIdx.x: both are 1024)
+    }
+    int32_t v[16];
+    int32_t sum = 0;
+    const int4* c4 = reinterpret_cast<const int4*>(counts + t * 16);
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+        const int4 q = c4[k];
+        v[4 * k] = q.x; v[4 * k + 1] = q.y; v[4 * k + 2] = q.z; v[4 * k + 3] = q.w;
+        sum += q.x + q.y + q.z + q.w;
+    }
+    int32_t incl = sum;
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+        int32_t o = __shfl_up(incl, off, 64);
+        if (lane >= off) incl += o;
+    }
+    if (lane == 63) start[wave] = incl;
+    __syncthreads();
+    int32_t woff = 0;
+    for (int w = 0; w < wave; w++) woff += start[w];
+    __syncthreads();
+    int32_t run = woff + incl - sum;
+    int4* s4 = reinterpret_cast<int4*>(start + t * 16);
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+        int4 q;
+        q.x = run; run += v[4 * k];
+        q.y = run; run += v[4 * k + 1];
+        q.z = run; run += v[4 * k + 2];
+        q.w = run; run += v[4 * k + 3];
+        s4[k] = q;
+    }
+    __syncthreads();
+    if (i >= n) return;
+    // first point of the cell + points of the cell in earlier workgroups of k_polar_count + rank inside the workgroup
+    const int pos = start[c] + before + rank;
+    if ((unsigned)pos >= (unsigned)n) return;            // cannot happen while the histogram is consistent
+    qx[pos] = px; qy[pos] = py; qz[pos] = pz; qperm[pos] = i;
+    cert[pos] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);     // a new scan: no certificate (slack 0), no neighbour tuple, no plane
+    aux[pos] = make_int4(0, 0, 0, 0);
+}
+
 // Work-proportional wave assignment.  The sorted scan is cut into chunks of 64 points; a chunk
 // whose points spread over a large box (sparse far field, tall structures) would make its wave
 // stage and sweep a large map tile, and the slowest wave sets the kernel time.  Such chunks are
@@ -628,6 +696,8 @@ __global__ __launch_bounds__(256) void k_chunk_parts(const PrepTable tbl)
         // a small scan leaves most of the GPU idle: cut every chunk finer (base_parts) and large ones finer still
         parts[c] = min(8, max(p, base_parts) * ((p > 1 && base_parts > 1) ? 2 : 1));
     }
+    // the last ordering kernel of a single scan: its last chunk's wave stamps the end of the preparation (s2m_last_timing)
+    if (ps.stamps && c == n_chunks - 1 && lane == 0) ps.stamps[1] = wall_clock64();
 }
 
 // one workgroup: exclusive scan of parts[] and emission of the wave table {first point, count}.
@@ -1475,6 +1545,116 @@ __global__ __launch_bounds__(256) void k_wave_density(const SlotTable tbl, int r
     int f = raw <= raw_limit ? 1 : (raw <= 2 * raw_limit ? 2 : (raw <= 4 * raw_limit ? 4 : 8));
     f = min(f, max(e.y / 8, 1));                          // at least 8 points per wave
     if (lane == 0 && f > 1) atomicMax(&cp->chunk_factor[e.x >> 6], f);
+}
+
+// The same wishes for a single scan's first optimisation, without a wave table in front of it and with the state upload
+// folded in (a plain launch ahead of the captured loop: the DevCtx block and the loop state travel as kernel arguments).
+//   * One wave per 64-point CHUNK.  The extent-only table k_chunk_table would emit gives chunk c  p = min(parts[c], cap)
+//     entries of 64 / p points, cap = the first of 8, 4, 2, 1 under which the wishes fit the table (chunk_table_body without
+//     density wishes: policies 0-2, 3 / 6, 4 / 7, 5 / 8); every workgroup adds the four totals up for itself.
+//   * A part is a contiguous range of 64 / p lanes: segmented butterflies give every part its box, its row sum and its wish
+//     under k_wave_density's rules, and the chunk's wish is the maximum over its parts - what the per-entry atomicMax leaves.
+//   * Every wave takes the transform and the context fields from the arguments; one workgroup more than the chunks need (the
+//     last) stores both blocks and the start stamp as k_set_ctx_state does, beside the waves that work on chunks (n_waves of
+//     the state is set by k_chunk_table_density, the next kernel).
+//   * The points are fetched and transformed before the totals are added up: the two round trips overlap.
+struct DensityStateArgs {
+    DevCtx c; DevState v;
+    DevCtx* cdst; DevState* sdst;
+    unsigned long long* stamp;    // pinned, may be null
+    int32_t raw_limit;
+};
+__global__ __launch_bounds__(256) void k_wave_density_state(const DensityStateArgs a)
+{
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    if (blockIdx.x == gridDim.x - 1) {                    // (uniform: the workgroup behind the chunks')
+        if (threadIdx.x == 0) {
+            *a.cdst = a.c;
+            DevState v = a.v;
+            v.n_waves = 0;
+            *a.sdst = v;
+            if (a.stamp) *a.stamp = wall_clock64();
+        }
+        return;
+    }
+    const int n = a.c.n_q, n_chunks = a.c.n_chunks, capacity = a.c.table_cap;
+    const auto parts = G(a.c.chunk_parts);
+    const int c = blockIdx.x * 4 + wave;
+    const int i = c * 64 + lane;
+    const bool valid = c < n_chunks && i < n;
+    const int own_parts = c < n_chunks ? parts[c] : 1;
+    float sx = 0.0f, sy = 0.0f, sz = 0.0f;
+    if (valid) {
+        const float px = G(a.c.qx)[i], py = G(a.c.qy)[i], pz = G(a.c.qz)[i];
+        sx = ((a.v.T[0] * px + a.v.T[1] * py) + a.v.T[2]  * pz) + a.v.T[3];
+        sy = ((a.v.T[4] * px + a.v.T[5] * py) + a.v.T[6]  * pz) + a.v.T[7];
+        sz = ((a.v.T[8] * px + a.v.T[9] * py) + a.v.T[10] * pz) + a.v.T[11];
+    }
+    // the cap of the extent-only table
+    __shared__ int32_t tot_s[4][4];
+    int t8 = 0, t4 = 0, t2 = 0, t1 = 0;
+    for (int k = threadIdx.x; k < n_chunks; k += 256) {
+        const int p = parts[k];
+        t8 += min(p, 8); t4 += min(p, 4); t2 += min(p, 2); t1 += min(p, 1);
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        t8 += __shfl_xor(t8, off, 64); t4 += __shfl_xor(t4, off, 64); t2 += __shfl_xor(t2, off, 64); t1 += __shfl_xor(t1, off, 64);
+    }
+    if (lane == 0) { tot_s[wave][0] = t8; tot_s[wave][1] = t4; tot_s[wave][2] = t2; tot_s[wave][3] = t1; }
+    __syncthreads();
+    t8 = tot_s[0][0] + tot_s[1][0] + tot_s[2][0] + tot_s[3][0];
+    t4 = tot_s[0][1] + tot_s[1][1] + tot_s[2][1] + tot_s[3][1];
+    t2 = tot_s[0][2] + tot_s[1][2] + tot_s[2][2] + tot_s[3][2];
+    const int cap = t8 <= capacity ? 8 : (t4 <= capacity ? 4 : (t2 <= capacity ? 2 : 1));
+    if (c >= n_chunks) return;
+    const int p = min(own_parts, cap);                    // 1, 2, 4 or 8
+    const int per = 64 / p;
+    const int start = c * 64 + (lane / per) * per;        // the part's table entry: {start, cnt}
+    const int cnt = max(0, min(per, n - start));          // (a lane is inside its entry's count  <=>  i < n: valid)
+    const bool fin = valid && (fabsf(sx) < 3.0e38f) && (fabsf(sy) < 3.0e38f) && (fabsf(sz) < 3.0e38f);
+    float mnx = fin ? sx : INFINITY, mxx = fin ? sx : -INFINITY;
+    float mny = fin ? sy : INFINITY, mxy = fin ? sy : -INFINITY;
+    float mnz = fin ? sz : INFINITY, mxz = fin ? sz : -INFINITY;
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+        if (off < per) {                                  // (uniform over the wave)
+            mnx = fminf(mnx, __shfl_xor(mnx, off, 64)); mxx = fmaxf(mxx, __shfl_xor(mxx, off, 64));
+            mny = fminf(mny, __shfl_xor(mny, off, 64)); mxy = fmaxf(mxy, __shfl_xor(mxy, off, 64));
+            mnz = fminf(mnz, __shfl_xor(mnz, off, 64)); mxz = fmaxf(mxz, __shfl_xor(mxz, off, 64));
+        }
+    }
+    bool ok = mnx <= mxx;                                 // the part has a finite point
+    GridDesc g;
+    g.ox = a.c.g.ox; g.oy = a.c.g.oy; g.oz = a.c.g.oz; g.inv_e = a.c.g.inv_e; g.e = a.c.g.e;
+    g.nx = a.c.g.nx; g.ny = a.c.g.ny; g.nz = a.c.g.nz; g.ncells = a.c.g.ncells;
+    const auto cell_start = G(a.c.cell_start);
+    int raw = 0;
+    if (ok) {
+        const int bx0 = max(cell_coord(mnx, g.ox, g.inv_e, g.nx) - 1, 0), bx1 = min(cell_coord(mxx, g.ox, g.inv_e, g.nx) + 1, g.nx - 1);
+        const int by0 = max(cell_coord(mny, g.oy, g.inv_e, g.ny) - 1, 0), by1 = min(cell_coord(mxy, g.oy, g.inv_e, g.ny) + 1, g.ny - 1);
+        const int bz0 = max(cell_coord(mnz, g.oz, g.inv_e, g.nz) - 1, 0), bz1 = min(cell_coord(mxz, g.oz, g.inv_e, g.nz) + 1, g.nz - 1);
+        const int nyb = by1 - by0 + 1, nzb = bz1 - bz0 + 1;
+        ok = nyb * nzb <= kRowMax;                        // scattered points: the gather path's business, a finer cut does not help
+        if (ok) {
+            for (int r = lane & (per - 1); r < nyb * nzb; r += per) {
+                const int zq = r / nyb;
+                const int gcell = ((bz0 + zq) * g.ny + by0 + (r - zq * nyb)) * g.nx;
+                raw += cell_start[gcell + bx1 + 1] - cell_start[gcell + bx0];
+            }
+        }
+    }
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+        if (off < per) raw += __shfl_xor(raw, off, 64);   // (ok is uniform over a part: its lanes hold the same box)
+    }
+    const int raw_limit = a.raw_limit;
+    int f = raw <= raw_limit ? 1 : (raw <= 2 * raw_limit ? 2 : (raw <= 4 * raw_limit ? 4 : 8));
+    f = min(f, max(cnt / 8, 1));                          // at least 8 points per wave
+    f = ok ? f : 0;
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) f = max(f, __shfl_xor(f, off, 64));
+    if (lane == 0 && f > 1) a.c.chunk_factor[c] = f;      // (zero between uses: what atomicMax over the entries would leave)
 }
 
 #include "s2m_register.hpp"

@@ -118,7 +118,7 @@ struct PrepSlot {
     int32_t *cell_of, *rank_of, *block_hist, *counts, *cell_start;
     float *qx, *qy, *qz; int32_t* qperm; float4* cert; int4* aux;
     int32_t* chunk_parts; int2* wave_table; int32_t* n_waves;
-    unsigned long long* stamps;   // pinned, may be null (batches): [0] wall clock when k_polar_count starts, [1] when k_chunk_table ends
+    unsigned long long* stamps;   // pinned, may be null (batches): [0] wall clock when k_polar_count starts, [1] when the last workgroup of k_chunk_parts ends (k_chunk_table, where one follows, stamps again)
 };
 constexpr int kPrepSlots = 16;
 struct PrepTable { PrepSlot s[kPrepSlots]; };

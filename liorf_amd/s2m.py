@@ -33,6 +33,7 @@ ABI_SYMBOLS = [
     "s2m_optimize_batch", "s2m_batch_set_scan", "s2m_batch_set_scans", "s2m_slot_set_scan", "s2m_slot_optimize_launch", "s2m_slot_optimize_collect", "s2m_optimize_batch_launch", "s2m_optimize_batch_collect", "s2m_batch_get_trace",
     "s2m_get_trace", "s2m_surf_optimization", "s2m_normal_eq", "s2m_last_timing", "s2m_debug_deferred",
     "s2m_time_iteration_kernel", "s2m_time_iterations", "s2m_make_scancontext", "s2m_debug_wave_profile", "s2m_debug_time_steady", "s2m_time_loop_launches",
+    "s2m_debug_scan_prep",
     "s2m_voxel_downsample", "s2m_voxel_downsample_device", "s2m_downsample_scan", "s2m_extract_cloud",
     "s2m_transform_cloud",
     "s2m_icp_default_params", "s2m_icp_align", "s2m_debug_device_trig", "s2m_debug_device_hypot",
@@ -61,6 +62,7 @@ S2M_IMU_QUEUE_LENGTH = 2000
 S2M_KF_FROM_HOST, S2M_KF_FROM_DEVICE, S2M_KF_FROM_LAST_DOWNSAMPLE = 0, 1, 2
 S2M_LOOP_NONE, S2M_LOOP_ALREADY_CLOSED, S2M_LOOP_TOO_FEW_POINTS, S2M_LOOP_REJECTED, S2M_LOOP_ACCEPTED = 0, 1, 2, 3, 4
 S2M_LOOP_PENDING = 5                                     # a launched closure whose ICP is still queued or running
+S2M_DEBUG_PREP_READ, S2M_DEBUG_PREP_NEW, S2M_DEBUG_PREP_LEGACY = -1, 0, 1   # chains of s2m_debug_scan_prep (liorf_s2m_debug.h)
 S2M_ICP_RANGE = 8                                        # iterations the device loop queues at a time (liorf_s2m_debug.h)
 S2M_WARN_LEAF_TOO_SMALL = 1
 S2M_PG_PRIOR, S2M_PG_BETWEEN, S2M_PG_GPS, S2M_PG_INITIAL = 0, 1, 2, 3
@@ -280,6 +282,8 @@ def load_library(path: str | None = None) -> C.CDLL:
     L.s2m_debug_wave_profile.argtypes = [vp, fp, C.c_int, C.POINTER(C.c_uint64), C.c_size_t]
     L.s2m_debug_time_steady.argtypes = [vp, fp, C.c_int, C.c_int, fp]
     L.s2m_time_loop_launches.argtypes = [vp, fp, C.c_int, fp]
+    L.s2m_debug_scan_prep.argtypes = [vp, C.c_int32, fp, C.POINTER(C.c_int32), fp, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
+                                      C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
     L.s2m_make_scancontext.argtypes = [vp, vp, C.c_size_t, C.c_size_t, C.POINTER(C.c_double), C.POINTER(C.c_double)]
     szp = C.POINTER(C.c_size_t)
     for n in ("s2m_voxel_downsample", "s2m_voxel_downsample_device"):
@@ -768,6 +772,24 @@ class MapOptimizationS2M:
         self._check(self.lib.s2m_debug_lm_close(self.h, form, it, r.ctypes.data_as(C.POINTER(C.c_double)), r.shape[0], _fp(p),
                                                 int(degen_in), _fp(m), C.byref(out)), "s2m_debug_lm_close")
         return out
+
+    def scanPrep(self, chain: int = 0, pose=None) -> dict:
+        """Observation hook: run the preparation of the resident scan again (chain 0 = as setScan / launch do, 1 = the
+        six-kernel chain, -1 = nothing) and read back what it left; see s2m_debug_scan_prep."""
+        n = self.laserCloudSurfLastDSNum
+        nc = (n + 63) // 64
+        i32 = C.POINTER(C.c_int32)
+        qperm = np.zeros(n, np.int32)
+        qxyz = np.zeros((3, n), np.float32)
+        parts, factor = np.zeros(nc, np.int32), np.zeros(nc, np.int32)
+        table = np.zeros((nc * 12 + 64, 2), np.int32)
+        nw = C.c_int32(0)
+        p = None if pose is None else np.ascontiguousarray(pose, np.float32)
+        self._check(self.lib.s2m_debug_scan_prep(self.h, int(chain), None if p is None else _fp(p), qperm.ctypes.data_as(i32), _fp(qxyz),
+                                                 parts.ctypes.data_as(i32), factor.ctypes.data_as(i32), table.ctypes.data_as(i32),
+                                                 C.byref(nw)), "s2m_debug_scan_prep")
+        return dict(qperm=qperm, qxyz=qxyz, chunk_parts=parts, chunk_factor=factor, wave_table=table[:max(nw.value, 0)].copy(),
+                    n_waves=nw.value)
 
     def timing(self):
         a, b, c = C.c_float(0), C.c_float(0), C.c_float(0)
