@@ -743,6 +743,7 @@ int s2m_create(const s2m_params* p, s2m_handle* out)
         hipEventCreate(&h->reg.ev_a2) != hipSuccess || hipEventCreate(&h->reg.ev_b2) != hipSuccess ||
         hipEventCreateWithFlags(&h->reg.ev_up, hipEventDisableTiming) != hipSuccess) return bail(S2M_ERR_HIP);
     static_assert(sizeof(DevState) % 8 == 0, "the trace follows the state block");
+    static_assert((sizeof(DevState) + sizeof(s2m_iter_trace) * kMaxIter) % 64 == 0, "a batch's state blocks (kid_states) all start on a 64-byte line");
     if (hipHostMalloc((void**)&h->reg.h_state, sizeof(DevState) * 2 + sizeof(s2m_iter_trace) * kMaxIter) != hipSuccess) return bail(S2M_ERR_HIP);
     h->reg.h_trace = reinterpret_cast<s2m_iter_trace*>(h->reg.h_state + 2);
     if (hipHostMalloc((void**)&h->reg.h_mm, 64) != hipSuccess) return bail(S2M_ERR_HIP);

@@ -41,6 +41,38 @@ __device__ __forceinline__ GridDesc grid_of(CtxP cp)
     g.nx = cp->g.nx; g.ny = cp->g.ny; g.nz = cp->g.nz; g.ncells = cp->g.ncells;
     return g;
 }
+// The head of a registration launch.  Line 0 of DevCtx and line 0 of DevState are read whole, field by field, as the first
+// thing a kernel does - before the `done` branch, so that the two misses overlap and nothing is fetched where it is first
+// used, one dependent round trip per field group (both blocks are always allocated: reading them in a launch that returns at
+// once is harmless).  What they hold is exactly what the next requests need: the rows of partial sums the previous launch
+// left, the wave's first table entry, then its points.  LmParams: the four parameters the close reads at the end of its
+// serial part, from line 2 - asked for with the second group of requests.
+struct CtxHead { int32_t nblocks, n_q; const int2* wave_table; double* partials; const float *qx, *qy, *qz; float4 *cert, *plane_cache; };
+struct StateHead { int32_t done, n_waves, isDegenerate, T_valid; float pose[6]; };      // pose: pose2[slot]
+struct LmParams { int32_t min_corr, early_exit; double conv_deg, conv_cm; };
+// (kPin = false: the fields by name, fetched where the compiler sees fit - the search kernel, whose worklist loop would hold them
+// in registers it does not have.  a0, a1: the kernel's two scalar arguments, which lie in another line of the argument block
+// than the slot's pointers and would otherwise be fetched where they are first looked at)
+template <bool kPin = true>
+__device__ __forceinline__ void load_heads(CtxP cp, gptr<DevState> st, int slot, CtxHead& c, StateHead& s, int& a0, int& a1)
+{
+    c.nblocks = cp->nblocks; c.n_q = cp->n_q; c.wave_table = cp->wave_table; c.partials = cp->partials;
+    c.qx = cp->qx; c.qy = cp->qy; c.qz = cp->qz; c.cert = cp->cert; c.plane_cache = cp->plane_cache;
+    s.done = st->done; s.n_waves = st->n_waves; s.isDegenerate = st->isDegenerate; s.T_valid = st->T_valid;
+#pragma unroll
+    for (int k = 0; k < 6; k++) s.pose[k] = st->pose2[slot][k];
+    // (the values are wanted here, all at once: without this the compiler moves every load down to its first use)
+    if (kPin)
+    asm volatile("" : "+s"(c.nblocks), "+s"(c.n_q), "+s"(c.wave_table), "+s"(c.partials), "+s"(c.qx), "+s"(c.qy), "+s"(c.qz),
+                      "+s"(c.cert), "+s"(c.plane_cache), "+s"(s.done), "+s"(s.n_waves), "+s"(s.isDegenerate), "+s"(s.T_valid),
+                      "+s"(s.pose[0]), "+s"(s.pose[1]), "+s"(s.pose[2]), "+s"(s.pose[3]), "+s"(s.pose[4]), "+s"(s.pose[5]), "+s"(a0), "+s"(a1));
+}
+__device__ __forceinline__ LmParams lm_params(CtxP cp)
+{
+    LmParams p;
+    p.min_corr = cp->min_corr; p.early_exit = cp->early_exit; p.conv_deg = cp->conv_deg; p.conv_cm = cp->conv_cm;
+    return p;
+}
 __device__ __forceinline__ uint32_t f2ord(float f)
 {
     uint32_t u = __float_as_uint(f);
@@ -76,29 +108,29 @@ __device__ __forceinline__ void swap_if(bool c, int& a, int& b)
 // device results with the test host's libm.  |x| >= 120 does not occur for a pose angle and takes the fp64
 // library function.
 // ------------------------------------------------------------------------------------------
-struct SincosfTable { double sign[4]; double hpi_inv, hpi, c0, c1, c2, c3, c4, s1, s2, s3; };
-S2M_HD inline const SincosfTable& sincosf_table(int negate)
-{
-    static constexpr SincosfTable T[2] = {
-        { { 1.0, -1.0, -1.0, 1.0 }, 0x1.45F306DC9C883p+23, 0x1.921FB54442D18p0, 0x1p0, -0x1.ffffffd0c621cp-2, 0x1.55553e1068f19p-5,
-          -0x1.6c087e89a359dp-10, 0x1.99343027bf8c3p-16, -0x1.555545995a603p-3, 0x1.1107605230bc4p-7, -0x1.994eb3774cf24p-13 },
-        { { 1.0, -1.0, -1.0, 1.0 }, 0x1.45F306DC9C883p+23, 0x1.921FB54442D18p0, -0x1p0, 0x1.ffffffd0c621cp-2, -0x1.55553e1068f19p-5,
-          0x1.6c087e89a359dp-10, -0x1.99343027bf8c3p-16, -0x1.555545995a603p-3, 0x1.1107605230bc4p-7, -0x1.994eb3774cf24p-13 } };
-    return T[negate];
-}
+// The reduction constants and the polynomial coefficients (glibc's __sincosf_table[2]: the second set has c0..c4 negated) are
+// literals: instruction immediates on the device, where a table indexed at run time sits in memory and costs every caller a
+// dependent load or two in the middle of the polynomial.
+constexpr double kSincosfHpiInv = 0x1.45F306DC9C883p+23, kSincosfHpi = 0x1.921FB54442D18p0;
+S2M_HD inline double sincosf_sign(int n) { return ((n ^ (n >> 1)) & 1) ? -1.0 : 1.0; }   // {1, -1, -1, 1}[n & 3]
 S2M_HD inline uint32_t abstop12(float x)
 {
     uint32_t u;
     memcpy(&u, &x, 4);
     return (u >> 20) & 0x7ffu;
 }
-S2M_HD inline float sinf_poly(double x, double x2, const SincosfTable& p, int n)
+// neg: the second coefficient set
+S2M_HD inline float sinf_poly(double x, double x2, bool neg, int n)
 {
     if ((n & 1) == 0) {
-        const double x3 = x * x2, s1 = p.s2 + x2 * p.s3, x7 = x3 * x2, s = x + x3 * p.s1;
+        const double ps1 = -0x1.555545995a603p-3, ps2 = 0x1.1107605230bc4p-7, ps3 = -0x1.994eb3774cf24p-13;
+        const double x3 = x * x2, s1 = ps2 + x2 * ps3, x7 = x3 * x2, s = x + x3 * ps1;
         return (float)(s + x7 * s1);
     }
-    const double x4 = x2 * x2, c2 = p.c3 + x2 * p.c4, c1 = p.c0 + x2 * p.c1, x6 = x4 * x2, c = c1 + x4 * p.c2;
+    const double pc0 = neg ? -0x1p0 : 0x1p0, pc1 = neg ? 0x1.ffffffd0c621cp-2 : -0x1.ffffffd0c621cp-2;
+    const double pc2 = neg ? -0x1.55553e1068f19p-5 : 0x1.55553e1068f19p-5, pc3 = neg ? 0x1.6c087e89a359dp-10 : -0x1.6c087e89a359dp-10;
+    const double pc4 = neg ? -0x1.99343027bf8c3p-16 : 0x1.99343027bf8c3p-16;
+    const double x4 = x2 * x2, c2 = pc3 + x2 * pc4, c1 = pc0 + x2 * pc1, x6 = x4 * x2, c = c1 + x4 * pc2;
     return (float)(c + x6 * c2);
 }
 // which = 0: sinf(y), 1: cosf(y)
@@ -107,15 +139,14 @@ S2M_HD inline float glibc_sincosf(float y, int which)
     double x = (double)y;
     if (abstop12(y) < abstop12(0x1.921FB6p-1f)) {                      // |y| < pi/4
         if (abstop12(y) < abstop12(0x1p-12f)) return which ? 1.0f : y;
-        return sinf_poly(x, x * x, sincosf_table(0), which);
+        return sinf_poly(x, x * x, false, which);
     }
     if (abstop12(y) < abstop12(120.0f)) {
-        const SincosfTable& p0 = sincosf_table(0);
-        const double r = x * p0.hpi_inv;                                // reduce_fast: quadrant in bits 24..31
+        const double r = x * kSincosfHpiInv;                            // reduce_fast: quadrant in bits 24..31
         const int n = ((int32_t)r + 0x800000) >> 24;
-        x = x - (double)n * p0.hpi;
-        const double sgn = p0.sign[n & 3];
-        return sinf_poly(x * sgn, x * x, sincosf_table((n & 2) ? 1 : 0), n ^ which);
+        x = x - (double)n * kSincosfHpi;
+        const double sgn = sincosf_sign(n);
+        return sinf_poly(x * sgn, x * x, (n & 2) != 0, n ^ which);
     }
     return which ? (float)cos(x) : (float)sin(x);
 }
@@ -130,16 +161,14 @@ S2M_HD inline void glibc_sincosf_both(float y, float& sn, float& cs)
     if (abstop12(y) < abstop12(0x1.921FB6p-1f)) {                      // |y| < pi/4
         if (abstop12(y) < abstop12(0x1p-12f)) { sn = y; cs = 1.0f; return; }
     } else if (abstop12(y) < abstop12(120.0f)) {
-        const SincosfTable& p0 = sincosf_table(0);
-        const double r = x * p0.hpi_inv;
+        const double r = x * kSincosfHpiInv;
         n = ((int32_t)r + 0x800000) >> 24;
-        x = x - (double)n * p0.hpi;
-        x = x * p0.sign[n & 3];
+        x = x - (double)n * kSincosfHpi;
+        x = x * sincosf_sign(n);
         tbl = (n & 2) ? 1 : 0;
     } else { sn = (float)sin(x); cs = (float)cos(x); return; }
-    const SincosfTable& p = sincosf_table(tbl);
     const double x2 = x * x;
-    const float a = sinf_poly(x, x2, p, 0), b = sinf_poly(x, x2, p, 1);
+    const float a = sinf_poly(x, x2, tbl != 0, 0), b = sinf_poly(x, x2, tbl != 0, 1);
     sn = (n & 1) ? b : a;
     cs = (n & 1) ? a : b;
 }
@@ -1322,9 +1351,24 @@ struct LmShared {
 // `early` / `late`: work of the caller that does not depend on the pose and hides behind the serial part - called by every
 // thread once the partial sums are in (everything requested before the call has arrived by then), and again just before
 // the last barrier (wave 0: after the solve; the other waves: at once, they would only wait there).
+// The partial sums are asked for ahead of the call, as soon as the head of the launch is in (lm_request_rows: the first 16 rows
+// of each lane, which is all of them up to 16 * NT / 32 workgroups), so that they travel together with the caller's own first
+// requests; `lp`: the parameters of the tests at the end, read with the head as well.
+struct LmRows { double v[16]; };
+template <int NT>
+__device__ __forceinline__ void lm_request_rows(const CtxHead& ch, int nb_act, int iter, LmRows& r)
+{
+    constexpr int NG = NT / 32;
+    const int t = threadIdx.x, col = t & 31, grp = t >> 5;
+    const auto P = G((const double*)ch.partials) + (size_t)(iter & 1) * (size_t)ch.nblocks * kAcc;
+    const int nb = min(ch.nblocks, nb_act);             // active workgroups
+#pragma unroll
+    for (int u = 0; u < 16; u++) { const int b = grp + u * NG; r.v[u] = (col < kAcc && b < nb) ? P[(size_t)b * kAcc + col] : 0.0; }
+}
 struct NoHook { __device__ __forceinline__ void operator()() const {} };
 template <int NT, bool kFull, typename Early = NoHook, typename Late = NoHook>
-__device__ __forceinline__ bool lm_close_iteration(CtxP cp, gptr<DevState> st, int nb_act, int iter,
+__device__ __forceinline__ bool lm_close_iteration(CtxP cp, gptr<DevState> st, const CtxHead& ch, const LmParams& lp, const LmRows& rows,
+                                                   int nb_act, int iter,
                                                    bool writer, bool ne_only, const float (&pose0)[6], int degen0,
                                                    LmShared& sh, float* s_out, float (&pose_out)[6],
                                                    unsigned long long* stamps = nullptr,     // diagnostics: 5 wall-clock stamps
@@ -1334,11 +1378,13 @@ __device__ __forceinline__ bool lm_close_iteration(CtxP cp, gptr<DevState> st, i
     const auto trace = G(cp->trace);
     const int t = threadIdx.x, col = t & 31, grp = t >> 5, lane = t & 63, wave = t >> 6;
     double s = 0.0;
+#pragma unroll
+    for (int u = 0; u < 16; u++) s += rows.v[u];        // (rows that do not exist, and the columns past kAcc, are 0.0: s stays what it was)
     if (col < kAcc) {
-        const int nbk = cp->nblocks;
-        const auto P = G((const double*)cp->partials) + (size_t)(iter & 1) * (size_t)nbk * kAcc;
+        const int nbk = ch.nblocks;
+        const auto P = G((const double*)ch.partials) + (size_t)(iter & 1) * (size_t)nbk * kAcc;
         const int nb = min(nbk, nb_act);                // active workgroups
-        for (int b0 = grp; b0 < nb; b0 += 16 * NG) {    // 16 independent loads in flight per lane
+        for (int b0 = grp + 16 * NG; b0 < nb; b0 += 16 * NG) {    // 16 independent loads in flight per lane
             double v[16];
 #pragma unroll
             for (int u = 0; u < 16; u++) { const int b = b0 + u * NG; v[u] = (b < nb) ? P[(size_t)b * kAcc + col] : 0.0; }
@@ -1380,7 +1426,7 @@ __device__ __forceinline__ bool lm_close_iteration(CtxP cp, gptr<DevState> st, i
 
     if (kFull && iter == 0) {                           // :1242-1264, wave 1 lane 0
         __syncthreads();
-        if (wave == 1 && lane == 0 && (int)sh.tot[27] >= cp->min_corr) {
+        if (wave == 1 && lane == 0 && (int)sh.tot[27] >= lp.min_corr) {
             int degenerate = 0;
             if (!all_eigen_above(sh.AtA, cp->eig_thresh)) {
                 // the full restatement: cv::eigen, the row-zeroing loop, matP = matV.inv() * matV2
@@ -1407,7 +1453,7 @@ __device__ __forceinline__ bool lm_close_iteration(CtxP cp, gptr<DevState> st, i
     }
 
     if (wave == 0) {
-        if (n_sel < cp->min_corr) {                     // :1178-1180: false, pose unchanged
+        if (n_sel < lp.min_corr) {                     // :1178-1180: false, pose unchanged
             if (t == 0) {
                 if (writer) {
                     s2m_iter_trace tr;
@@ -1448,8 +1494,8 @@ __device__ __forceinline__ bool lm_close_iteration(CtxP cp, gptr<DevState> st, i
                 const float deltaR = (float)sqrt(r0 * r0 + r1 * r1 + r2 * r2);          // :1280-1283
                 const double t0 = (double)(X[3] * 100), t1 = (double)(X[4] * 100), t2 = (double)(X[5] * 100);
                 const float deltaT = (float)sqrt(t0 * t0 + t1 * t1 + t2 * t2);          // :1284-1287
-                const bool conv = ((double)deltaR < cp->conv_deg) && ((double)deltaT < cp->conv_cm);   // :1289
-                s_out[6] = (conv && cp->early_exit) ? 1.0f : 0.0f;                      // break (:1313-1314)
+                const bool conv = ((double)deltaR < lp.conv_deg) && ((double)deltaT < lp.conv_cm);   // :1289
+                s_out[6] = (conv && lp.early_exit) ? 1.0f : 0.0f;                      // break (:1313-1314)
                 if (writer) {
                     s2m_iter_trace tr;
                     tr.n_sel = n_sel; tr.stepped = 1; tr.deltaR = deltaR; tr.deltaT = deltaT;
@@ -1461,8 +1507,8 @@ __device__ __forceinline__ bool lm_close_iteration(CtxP cp, gptr<DevState> st, i
                     st->T_valid = 0;
                     store_trace(trace + iter, tr);
                     st->iters_run = iter + 1;
-                    if (conv && !st->converged) st->converged = 1;
-                    if (conv && cp->early_exit) st->done = 1;
+                    if (conv) st->converged = 1;           // (no test of the old value: a load here would first drain the stores above)
+                    if (conv && lp.early_exit) st->done = 1;
                 }
             }
         }
@@ -1689,19 +1735,26 @@ __global__ __launch_bounds__(kFinThreads) void k_finalize(const SlotTable tbl, i
 {
     const CtxP cp = ctx_const(tbl.ctx[blockIdx.y]);
     const auto st = G(tbl.st[blockIdx.y]);
-    // loop state, fetched up front (the state block is a kernel argument: no pointer chase through DevCtx)
-    const int done0 = st->done, degen0 = st->isDegenerate;
-    const int nb_act = (st->n_waves + cp->wpb - 1) / cp->wpb;
+    // loop state and the head of DevCtx, fetched up front (the state block is a kernel argument: no pointer chase through DevCtx)
+    CtxHead ch; StateHead hs;
+    load_heads(cp, st, iter & 1, ch, hs, iter, mode);
+    LmParams lp = lm_params(cp);
+    const int wpb = cp->wpb, max_iter = cp->max_iter;
+    const int done0 = hs.done, degen0 = hs.isDegenerate;
+    const int nb_act = (hs.n_waves + wpb - 1) / wpb;
     float pose0[6];
 #pragma unroll
-    for (int k = 0; k < 6; k++) pose0[k] = st->pose2[iter & 1][k];
-    if (mode == 0 && done0) { finalize_record_out(st, out, cp->max_iter, stamp); return; }
+    for (int k = 0; k < 6; k++) pose0[k] = hs.pose[k];
+    if (mode == 0 && done0) { finalize_record_out(st, out, max_iter, stamp); return; }
+    LmRows rows;
+    lm_request_rows<kFinThreads>(ch, nb_act, iter, rows);
+    asm volatile("" : "+s"(lp.min_corr), "+s"(lp.early_exit), "+s"(lp.conv_deg), "+s"(lp.conv_cm));   // (here, not at the end of the serial part)
     __shared__ LmShared sh;
     __shared__ float s_out[8];
     // the worklists of the search kernel start empty behind every close of its own (the certify kernel of the next launch appends)
     if (mode == 0 && threadIdx.x == 0 && cp->wl_count) { cp->wl_count[0] = 0; cp->wl_count[1] = 0; }
     float pose[6];
-    const bool ended = lm_close_iteration<kFinThreads, true>(cp, st, nb_act, iter, true, mode == 1, pose0, degen0, sh, s_out, pose);
+    const bool ended = lm_close_iteration<kFinThreads, true>(cp, st, ch, lp, rows, nb_act, iter, true, mode == 1, pose0, degen0, sh, s_out, pose);
     // the transform of the new pose, once, for every workgroup of the next registration launch (which would otherwise
     // rebuild it - a microsecond of dependent trig arithmetic in each of them)
     if (mode == 0 && !ended && threadIdx.x < 64) {
@@ -1717,7 +1770,7 @@ __global__ __launch_bounds__(kFinThreads) void k_finalize(const SlotTable tbl, i
     }
     if (out || stamp) {
         __syncthreads();                                  // what thread 0 and wave 1 stored above is part of the record
-        finalize_record_out(st, out, cp->max_iter, stamp);
+        finalize_record_out(st, out, max_iter, stamp);
     }
 }
 

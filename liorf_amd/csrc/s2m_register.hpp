@@ -1251,23 +1251,35 @@ __global__ __launch_bounds__(NW / EPW * 64, MINW) void k_certify_lean(const Slot
     constexpr int NWL = NW / EPW;                              // waves of this workgroup
     const CtxP cp = ctx_const(tbl.ctx[blockIdx.y]);
     const auto st = G(tbl.st[blockIdx.y]);
-    const int done = st->done, n_waves = st->n_waves;
+    CtxHead ch; StateHead hs;
+    int launch_unused = 0;
+    load_heads(cp, st, launch & 1, ch, hs, launch, launch_unused);
+    const int done = hs.done, n_waves = hs.n_waves;
     if (done) return;
     __shared__ double red[NW][32];
     __shared__ float park[EPW == 2 ? NWL : 1][7][64];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int nblocks = cp->nblocks;
+    const int nblocks = ch.nblocks;
     const int nb_act = min((n_waves + NW - 1) / NW, nblocks);
     const int b = (int)blockIdx.x;
     if (b >= nb_act) return;
-    const int nq = cp->n_q;
+    const int nq = ch.n_q;
     const int ablate = cp->ablate;
     const bool single = nb_act * NW >= n_waves;                // every wave of the partition has one entry at most
     // everything the entries need is requested together (the second entry's plane only once the first is under way: registers);
     // the entries are then taken one after the other by the same code (cur = the entry in hand)
     static_assert(EPW == 1 || EPW == 2, "one or two entries per wave");
-    const auto tb = G((const int2*)cp->wave_table);
+    const auto tb = G((const int2*)ch.wave_table);
     int2 chunkA = make_int2(0, 0), chunkB = make_int2(0, 0);
+    // the transform of this launch's pose, if k_finalize (or the host, for launch 0) has left it in the state block: asked for
+    // together with the table entry
+    float T[12], sc6[6];
+    if (hs.T_valid) {
+#pragma unroll
+        for (int k = 0; k < 12; k++) T[k] = st->T[k];
+#pragma unroll
+        for (int k = 0; k < 6; k++) sc6[k] = st->sc[k];
+    }
     {
         const int eA = wave * nb_act + b, eB = (wave + NWL) * nb_act + b;
         if (eA < n_waves) { chunkA.x = tb[eA].x; chunkA.y = tb[eA].y; }
@@ -1279,26 +1291,19 @@ __global__ __launch_bounds__(NW / EPW * 64, MINW) void k_certify_lean(const Slot
     v4f cert = { 0, 0, 0, 0 }, certB = { 0, 0, 0, 0 }, plane0 = { NAN, 0, 0, 0 };
     if (lane < chunkA.y && chunkA.x + lane < nq) {
         const int i = chunkA.x + lane;
-        px = G(cp->qx)[i]; py = G(cp->qy)[i]; pz = G(cp->qz)[i];                      // pointOri (:1085)
-        cert = G((const v4f*)cp->cert)[i];
-        plane0 = G((const v4f*)cp->plane_cache)[i];
+        px = G(ch.qx)[i]; py = G(ch.qy)[i]; pz = G(ch.qz)[i];                         // pointOri (:1085)
+        cert = G((const v4f*)ch.cert)[i];
+        plane0 = G((const v4f*)ch.plane_cache)[i];
     }
     if (EPW == 2 && lane < chunkB.y && chunkB.x + lane < nq) {
         const int i = chunkB.x + lane;
-        bx = G(cp->qx)[i]; by = G(cp->qy)[i]; bz = G(cp->qz)[i];
-        certB = G((const v4f*)cp->cert)[i];
+        bx = G(ch.qx)[i]; by = G(ch.qy)[i]; bz = G(ch.qz)[i];
+        certB = G((const v4f*)ch.cert)[i];
     }
-    // the transform of this launch's pose: left in the state block by k_finalize (or by the host for launch 0)
-    float T[12], sc6[6];
-    if (st->T_valid) {
-#pragma unroll
-        for (int k = 0; k < 12; k++) T[k] = st->T[k];
-#pragma unroll
-        for (int k = 0; k < 6; k++) sc6[k] = st->sc[k];
-    } else {
+    if (!hs.T_valid) {
         float pose[6];
 #pragma unroll
-        for (int k = 0; k < 6; k++) pose[k] = st->pose2[launch & 1][k];
+        for (int k = 0; k < 6; k++) pose[k] = hs.pose[k];
         build_transform(pose, lane, T, sc6);
     }
 #pragma unroll
@@ -1434,7 +1439,10 @@ __global__ __launch_bounds__(NW * 64, MINW) void k_register(const SlotTable tbl,
     // The loop state block never moves, so it comes with the kernel arguments: `done` and the wave count arrive
     // with the first round trip, in parallel with the DevCtx block, instead of behind a pointer chase.
     const auto st = G(tbl.st[blockIdx.y]);
-    const int done = st->done, n_waves = st->n_waves;
+    CtxHead ch; StateHead hs;
+    // (the pose this launch starts from: the one it runs with, or - closing the previous iteration first - the one that ran with)
+    load_heads<MODE != kSearch>(cp, st, (MODE != kSearch && (flags & kFlagSolvePrev) != 0) ? (launch - 1) & 1 : launch & 1, ch, hs, launch, flags);
+    const int done = hs.done, n_waves = hs.n_waves;
     if (!HOOK && done) return;
     const bool solve_prev = MODE != kSearch && (flags & kFlagSolvePrev) != 0;
     unsigned long long tk_start = 0, clk1 = 0, clk2 = 0;
@@ -1453,7 +1461,7 @@ __global__ __launch_bounds__(NW * 64, MINW) void k_register(const SlotTable tbl,
     __shared__ LmShared s_lm;                        // (kCertify: the close has no tile area to borrow)
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int nblocks = cp->nblocks;
+    const int nblocks = ch.nblocks;
     const int nb_act = min((n_waves + CNW - 1) / CNW, nblocks);            // workgroups the wave table needs
     // ---- which row of the partition this workgroup works on
     // (the search kernel over a worklist: workgroup j takes items j, j + gridDim.x, ... - late in a loop the list is short or
@@ -1481,29 +1489,64 @@ __global__ __launch_bounds__(NW * 64, MINW) void k_register(const SlotTable tbl,
     // the partition: neighbouring entries (similar cost: the sort runs from the dense near field to the sparse far
     // field) land on different CUs, which evens out both the work and the L2-miss queues.
     const int estride = nb_act * CNW;
-    const auto tb = G((const int2*)cp->wave_table);
-    const int nq = cp->n_q;
-    const GridDesc g = grid_of(cp);
-    const auto map = G((const v4f*)cp->map_sorted);
-    const auto cell_start = G(cp->cell_start);
-    const int ablate = cp->ablate;
-    const float gatef = cp->gate_f;
-
-    // everything of the first entry that does not depend on the pose is requested first: it is in flight while the
-    // previous iteration is closed below
+    const auto tb = G((const int2*)ch.wave_table);
+    const int nq = ch.n_q;
+    // What the head allows is asked for at once, and nothing is waited for in between: the wave's first table entry (by a scalar
+    // load - the table is only read here and the index is the same in every lane: waiting for it does not wait for the rows,
+    // which a vector load's counter would), the partial sums of the launch this one closes, lines 1 and 2 of DevCtx, and the
+    // transform where the host or k_finalize has left it (launches 0 and 1, the first launch of a later range).
     int e0 = wave * nb_act + b;
     int2 chunk = make_int2(0, 0);
-    if (e0 < n_waves) { chunk.x = tb[e0].x; chunk.y = tb[e0].y; }
-    chunk.x = __builtin_amdgcn_readfirstlane(chunk.x);       // wave-uniform: scalar registers
-    chunk.y = __builtin_amdgcn_readfirstlane(chunk.y);
+    unsigned long long entry0 = 0ull;                        // {first point, count} in one register pair: no copy, and so no wait, where the branch joins
+    if (MODE != kSearch) {
+        const int e0s = __builtin_amdgcn_readfirstlane(e0);
+        const auto tbs = (const __attribute__((address_space(4))) unsigned long long*)ch.wave_table;
+        static_assert(sizeof(int2) == 8, "a table entry is one 64-bit word");
+        if (e0s < n_waves) entry0 = tbs[e0s];
+    } else {
+        if (e0 < n_waves) { chunk.x = tb[e0].x; chunk.y = tb[e0].y; }
+        chunk.x = __builtin_amdgcn_readfirstlane(chunk.x);   // wave-uniform: scalar registers
+        chunk.y = __builtin_amdgcn_readfirstlane(chunk.y);
+    }
+    LmRows rows;
+    if (solve_prev) lm_request_rows<NW * 64>(ch, nb_act, launch - 1, rows);
+    GridDesc g = grid_of(cp);
+    auto map = G((const v4f*)cp->map_sorted);
+    auto cell_start = G(cp->cell_start);
+    int ablate = cp->ablate;
+    float gatef = cp->gate_f;
+    auto f_aux = G((const v4i*)cp->aux); auto f_front = G((const v4f*)cp->front); auto f_npos = G((const int32_t*)cp->npos);
+    auto f_plane_alt = G((const v4f*)cp->plane_alt); auto f_npos_alt = G((const int32_t*)cp->npos_alt);
+    LmParams lp = lm_params(cp);
+    float T[12], sc6[6];
+    if (MODE == kSearch) {                                   // (per worklist item, as before: nothing of the state is held across the loop)
+        hs.T_valid = st->T_valid;
+#pragma unroll
+        for (int k = 0; k < 6; k++) hs.pose[k] = st->pose2[launch & 1][k];
+    }
+    const bool have_T = !solve_prev && hs.T_valid;
+    if (MODE != kSearch && have_T) {
+        // (scalar loads - T and sc are written by k_finalize and by the search kernel's closing step, never by this build)
+        const auto sts = (const __attribute__((address_space(4))) DevState*)tbl.st[blockIdx.y];
+#pragma unroll
+        for (int k = 0; k < 12; k++) T[k] = sts->T[k];
+#pragma unroll
+        for (int k = 0; k < 6; k++) sc6[k] = sts->sc[k];
+    }
+    if (MODE != kSearch)
+        asm volatile("" : "+s"(entry0), "+s"(g.ox), "+s"(g.oy), "+s"(g.oz), "+s"(g.inv_e), "+s"(g.e), "+s"(g.nx), "+s"(g.ny),
+                          "+s"(g.nz), "+s"(g.ncells), "+s"(map), "+s"(cell_start), "+s"(ablate), "+s"(gatef), "+s"(f_aux), "+s"(f_front),
+                          "+s"(f_npos), "+s"(f_plane_alt), "+s"(f_npos_alt), "+s"(lp.min_corr), "+s"(lp.early_exit), "+s"(lp.conv_deg), "+s"(lp.conv_cm));
+    if (MODE != kSearch) { chunk.x = (int)(uint32_t)entry0; chunk.y = (int)(uint32_t)(entry0 >> 32); }
+    // the first entry's points: in flight while the previous iteration is closed below
     float px = 0.0f, py = 0.0f, pz = 0.0f;
     v4f cert = { 0, 0, 0, 0 }, plane0 = { NAN, 0, 0, 0 };
     const bool valid0 = lane < chunk.y && chunk.x + lane < nq;
     if (valid0) {
         const int i = chunk.x + lane;
-        px = G(cp->qx)[i]; py = G(cp->qy)[i]; pz = G(cp->qz)[i];                      // pointOri (:1085)
-        cert = G((const v4f*)cp->cert)[i];
-        plane0 = G((const v4f*)cp->plane_cache)[i];        // good as it is if the whole entry turns out to be certified
+        px = G(ch.qx)[i]; py = G(ch.qy)[i]; pz = G(ch.qz)[i];                         // pointOri (:1085)
+        cert = G((const v4f*)ch.cert)[i];
+        plane0 = G((const v4f*)ch.plane_cache)[i];         // good as it is if the whole entry turns out to be certified
     }
 
     // transPointAssociateToMap (:1069-1072) and the LM trig (:1170-1175). Launch 0 of a scan gets them
@@ -1514,44 +1557,44 @@ __global__ __launch_bounds__(NW * 64, MINW) void k_register(const SlotTable tbl,
     Fragile frag;
 #pragma unroll
     for (int k = 0; k < 6; k++) frag.fr[k] = v4f{ 0.0f, 0.0f, 0.0f, 0.0f };
-    float T[12], sc6[6];
-    if (!solve_prev && st->T_valid) {
+    if (MODE == kSearch && have_T) {
 #pragma unroll
         for (int k = 0; k < 12; k++) T[k] = st->T[k];
 #pragma unroll
         for (int k = 0; k < 6; k++) sc6[k] = st->sc[k];
-    } else {
+    }
+    if (!have_T) {
         float pose[6];
         if (solve_prev) {
             static_assert(MODE == kCertify || sizeof(LmShared) <= sizeof(v4f) * kTilePts * NW, "LM scratch must fit the tile area");
             LmShared& sh = (MODE == kCertify) ? s_lm : *reinterpret_cast<LmShared*>(&s_pts[0][0]);
-            const int degen0 = st->isDegenerate;
+            const int degen0 = hs.isDegenerate;
             float pose0[6];
 #pragma unroll
-            for (int k = 0; k < 6; k++) pose0[k] = st->pose2[(launch - 1) & 1][k];
+            for (int k = 0; k < 6; k++) pose0[k] = hs.pose[k];
             if (HOOK) lm_stamps[5] = wall_clock64();
             // lanes whose certificate leaves (next to) no slack fetch what their re-measurement needs behind the close
             auto early = [&]() {
                 if (!HOOK && valid0 && !(cert.w > kFragileSlack) && !(ablate & 3)) {
                     const int i = chunk.x + lane;
                     frag.on = true;
-                    frag.aux = G((const v4i*)cp->aux)[i];
+                    frag.aux = f_aux[i];
 #pragma unroll
-                    for (int j = 0; j < 5; j++) frag.opos[j] = G(cp->npos)[(size_t)j * nq + i];
+                    for (int j = 0; j < 5; j++) frag.opos[j] = f_npos[(size_t)j * nq + i];
 #pragma unroll
-                    for (int j = 0; j < 6; j++) frag.fr[j] = G((const v4f*)cp->front)[(size_t)j * nq + i];
+                    for (int j = 0; j < 6; j++) frag.fr[j] = f_front[(size_t)j * nq + i];
 #pragma unroll
-                    for (int j = 0; j < 5; j++) frag.alt[j] = G(cp->npos_alt)[(size_t)j * nq + i];
-                    frag.alt_plane = G((const v4f*)cp->plane_alt)[i];
+                    for (int j = 0; j < 5; j++) frag.alt[j] = f_npos_alt[(size_t)j * nq + i];
+                    frag.alt_plane = f_plane_alt[i];
                 }
             };
             auto late = [&]() {};
-            const bool ended = lm_close_iteration<NW * 64, false>(cp, st, nb_act, launch - 1, blockIdx.x == 0, false, pose0, degen0,
+            const bool ended = lm_close_iteration<NW * 64, false>(cp, st, ch, lp, rows, nb_act, launch - 1, blockIdx.x == 0, false, pose0, degen0,
                                                                  sh, s_lm_out, pose, HOOK ? lm_stamps : nullptr, early, late);
             if (ended) return;
         } else {
 #pragma unroll
-            for (int k = 0; k < 6; k++) pose[k] = st->pose2[launch & 1][k];
+            for (int k = 0; k < 6; k++) pose[k] = hs.pose[k];
         }
         build_transform(pose, lane, T, sc6);
     }
@@ -1805,7 +1848,13 @@ __global__ __launch_bounds__(NW * 64, MINW) void k_register(const SlotTable tbl,
         for (int k = 0; k < 6; k++) pose0[k] = st->pose2[launch & 1][k];
         const int degen0 = st->isDegenerate;
         if (tid == 0) { cp->wl_count[0] = 0; cp->wl_count[1] = 0; }
-        const bool ended = lm_close_iteration<NW * 64, false>(cp, st, nb_act, launch, true, false, pose0, degen0, sh, s_lm_out, pose);
+        // (read again, not kept from the head: the rows were only just written, and this is once per loop)
+        CtxHead ce{};
+        ce.nblocks = cp->nblocks; ce.partials = cp->partials;
+        LmRows rows_end;
+        lm_request_rows<NW * 64>(ce, nb_act, launch, rows_end);
+        const bool ended = lm_close_iteration<NW * 64, false>(cp, st, ce, lm_params(cp), rows_end, nb_act, launch, true, false, pose0, degen0,
+                                                             sh, s_lm_out, pose);
         if (!ended && tid < 64) {
             float Tn[12], scn[6];
             build_transform(pose, tid, Tn, scn);
