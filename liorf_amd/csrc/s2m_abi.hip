@@ -1,12 +1,13 @@
-// s2m_abi.hip — host side of the gfx950 scan-to-map path and the part of the C ABI (include/liorf_s2m.h) that launches its
-// kernels: create / destroy / params, the map index and the scan preparation, the LM loop and its graphs, batches and slots,
-// the debug and timing entry points, ScanContext.  The only translation unit that includes s2m_kernels.hpp / s2m_register.hpp.
+// s2m_abi.hip — host side of the gfx950 scan-to-map LM loop and the part of the C ABI (include/liorf_s2m.h) that launches its
+// kernels: create / destroy / params, the context and state uploads, the loop and its graphs, launch / collect, batches and
+// slots.  The only translation unit that includes s2m_kernels.hpp / s2m_register.hpp.
 //
-// Builds the map's uniform-grid index and the scan's locality order on the device (memory grow-only, sized by the actual
-// point counts), and runs the whole <= max_iter LM loop as one captured hipGraph (enqueue_loop) so that a scan costs one graph
-// launch and one synchronisation.  The handle is s2m_context.hpp's; the entry points that only orchestrate other units' stages
-// live in s2m_abi_voxel.hip, s2m_abi_keyframes.hip, s2m_abi_loop.hip and s2m_abi_front_end.hip.  There is no CPU fallback:
-// without a gfx950 device every entry point fails with S2M_ERR_NO_DEVICE.
+// Runs the whole <= max_iter LM loop as one captured hipGraph (enqueue_loop) so that a scan costs one graph launch and one
+// synchronisation.  The map index and the scan preparation in front of it are s2m_prep.hip's, the observation and timing hooks
+// s2m_abi_debug.hip's (they launch the loop's kernels through the functions s2m_context.hpp declares for this unit),
+// ScanContext s2m_sc.hip's and s2m_abi_sc.hip's.  The handle is s2m_context.hpp's; the entry points that only orchestrate
+// other units' stages live in s2m_abi_voxel.hip, s2m_abi_keyframes.hip, s2m_abi_loop.hip and s2m_abi_front_end.hip.  There is
+// no CPU fallback: without a gfx950 device every entry point fails with S2M_ERR_NO_DEVICE.
 #include <hip/hip_runtime.h>
 
 #include <cfloat>
@@ -27,21 +28,16 @@
 using namespace s2m;
 using namespace s2m::host;
 
-namespace {
-
-inline uint32_t host_f2ord(float f) { uint32_t u; memcpy(&u, &f, 4); return (u & 0x80000000u) ? ~u : (u | 0x80000000u); }
-inline float host_ord2f(uint32_t o) { uint32_t u = (o & 0x80000000u) ? (o & 0x7fffffffu) : ~o; float f; memcpy(&f, &u, 4); return f; }
-
 // milliseconds between two device stamps of the pinned block (valid once the stream has been synchronised behind the kernels
 // that wrote them)
-inline float stamps_ms(const s2m_context* h, int from, int to)
+float s2m::host::stamps_ms(const s2m_context* h, int from, int to)
 {
     const unsigned long long a = h->reg.h_stamps[from], b = h->reg.h_stamps[to];
     return (b > a && h->reg.wall_clock_khz > 0) ? (float)((double)(b - a) / (double)h->reg.wall_clock_khz) : 0.0f;
 }
 
 // the partial rows of a launch (two slots, by launch parity) and, behind them, the search kernel's worklist
-int ensure_rows(s2m_context* h, int nblocks)
+int s2m::host::ensure_rows(s2m_context* h, int nblocks)
 {
     const size_t rows = sizeof(double) * 2 * kAcc * (size_t)nblocks;
     int rc = ensure(h, h->reg.partials, rows + 64 + sizeof(int32_t) * 2 * (size_t)nblocks);
@@ -53,7 +49,7 @@ int ensure_rows(s2m_context* h, int nblocks)
     return S2M_OK;
 }
 
-int upload_ctx(s2m_context* h)
+int s2m::host::upload_ctx(s2m_context* h)
 {
     if (!h->ctx_dirty) return S2M_OK;
     hipLaunchKernelGGL(k_set_ctx, dim3(1), dim3(64), 0, h->stream, h->reg.dctx.as<DevCtx>(), h->hctx);
@@ -62,322 +58,7 @@ int upload_ctx(s2m_context* h)
     return S2M_OK;
 }
 
-// exclusive scan of counts[0..n) into out[0..n], out[n] = total
-int device_exclusive_scan(s2m_context* h, const int32_t* counts, int32_t* out, int n, int total)
-{
-    const int nb = (n + 1023) / 1024;
-    int rc = ensure(h, h->reg.block_sums, sizeof(int32_t) * (size_t)(nb + 1));
-    if (rc) return rc;
-    int32_t* sums = h->reg.block_sums.as<int32_t>();
-    hipLaunchKernelGGL(k_scan_local, dim3(nb), dim3(256), 0, h->stream, counts, out, sums, n);
-    if (nb <= 4096) hipLaunchKernelGGL(k_scan_add_fold, dim3(nb), dim3(256), 0, h->stream, out, (const int32_t*)sums, n, total);
-    else {
-        hipLaunchKernelGGL(k_scan_sums, dim3(1), dim3(1024), 0, h->stream, sums, nb);
-        hipLaunchKernelGGL(k_scan_add, dim3(nb), dim3(256), 0, h->stream, out, (const int32_t*)sums, n, total);
-    }
-    S2M_HIP(h, hipGetLastError());
-    return S2M_OK;
-}
-
-// bounding box of the finite points (device reduction + 24-byte readback)
-int device_bbox(s2m_context* h, const unsigned char* d_pts, size_t stride, int n, float mn[3], float mx[3])
-{
-    const int blocks = std::min((n + 255) / 256, 1024);
-    int rc = ensure(h, h->reg.mm, 64 + sizeof(uint32_t) * 8 * 1024);          // mm[0..5], then 8 words per workgroup from word 16 on
-    if (rc) return rc;
-    uint32_t* part = h->reg.mm.as<uint32_t>() + 16;
-    hipLaunchKernelGGL(k_bbox, dim3(blocks), dim3(256), 0, h->stream, d_pts, stride, n, part);
-    hipLaunchKernelGGL(k_bbox_fold, dim3(1), dim3(256), 0, h->stream, (const uint32_t*)part, blocks, h->reg.mm.as<uint32_t>());
-    S2M_HIP(h, hipGetLastError());
-    S2M_HIP(h, hipMemcpyAsync(h->reg.h_mm, h->reg.mm.p, 24, hipMemcpyDeviceToHost, h->stream));
-    S2M_HIP(h, hipStreamSynchronize(h->stream));
-    for (int d = 0; d < 3; d++) {
-        if (h->reg.h_mm[d] == 0xffffffffu || h->reg.h_mm[3 + d] == 0u) { mn[d] = 0.0f; mx[d] = 0.0f; }   // no finite value
-        else { mn[d] = host_ord2f(h->reg.h_mm[d]); mx[d] = host_ord2f(h->reg.h_mm[3 + d]); }
-    }
-    return S2M_OK;
-}
-
-int set_map_build(s2m_context* h, const void* pts, size_t n, size_t stride, bool on_device);
-
-}  // namespace
-
-// The index is rebuilt in place: once the rebuild has started the old index is gone, so a failure on the way leaves the handle
-// with NO map (n_m = 0, the reference's "no key poses yet" state, :1297), a new map epoch (batch slots drop what they adopted)
-// and no certificates - never the old point count over half-rewritten buffers.
-int s2m::host::set_map_impl(s2m_context* h, const void* pts, size_t n, size_t stride, bool on_device)
-{
-    int rc = check_records(h, pts, n, stride);
-    if (rc) return rc;
-    rc = set_map_build(h, pts, n, stride, on_device);
-    if (rc != S2M_OK && n > 0) {
-        const std::string why = h->err;
-        h->batch.map_epoch++;
-        h->reg.n_m = 0; h->hctx.n_m = 0; h->ctx_dirty = true;
-        if (h->reg.have_scan && h->reg.n_q > 0 && h->reg.cert.p) {
-            (void)hipMemsetAsync(h->reg.cert.p, 0, sizeof(float4) * h->reg.n_q, h->stream);
-            (void)hipMemsetAsync(h->reg.aux.p, 0, sizeof(int4) * h->reg.n_q, h->stream);
-        }
-        (void)upload_ctx(h);
-        (void)hipStreamSynchronize(h->stream);
-        h->err = why;
-    }
-    return rc;
-}
-
-namespace {
-
-int set_map_build(s2m_context* h, const void* pts, size_t n, size_t stride, bool on_device)
-{
-    int rc;
-    S2M_HIP(h, hipSetDevice(h->device));
-    S2M_HIP(h, hipEventRecord(h->reg.ev_c, h->stream));
-    if (n == 0) { h->batch.map_epoch++; h->reg.n_m = 0; h->hctx.n_m = 0; h->ctx_dirty = true; h->reg.t_set_map_ms = 0; return upload_ctx(h); }
-
-    const unsigned char* d_pts;
-    if (on_device) d_pts = static_cast<const unsigned char*>(pts);
-    else {
-        if ((rc = stage_host_records(h, h->reg.raw_map, pts, n * stride))) return rc;
-        d_pts = h->reg.raw_map.as<unsigned char>();
-    }
-    float mn[3], mx[3];
-    if ((rc = device_bbox(h, d_pts, stride, (int)n, mn, mx))) return rc;
-
-    // cell edge: every map point with fp32 d2 < gate_sq of a query lies in the 3x3x3 block
-    // around the query's cell once E >= sqrt(gate_sq) plus a margin that covers the fp32
-    // rounding of (v - o) * inv_e (<= 2.4e-5 cells at |v - o| <= 200).
-    // The edge is 2.5 % above the gate: a query's 3x3x3 cells then cover a ball of that much more than the gate around it,
-    // which is what lets a point with fewer than 5 neighbours inside the gate prove "and none just outside it either" and
-    // keep that verdict over the following launches (s2m_register.hpp, tier A) instead of searching again.
-    double E = std::sqrt(h->prm.gate_sq) * 1.025;
-    GridDesc g{};
-    for (int attempt = 0; attempt < 32; attempt++) {
-        const float Ef = (float)E;
-        g.inv_e = 1.0f / Ef; g.e = Ef;
-        g.ox = mn[0] - Ef; g.oy = mn[1] - Ef; g.oz = mn[2] - Ef;
-        double nx = std::floor(((double)mx[0] - g.ox) * g.inv_e) + 2.0;
-        double ny = std::floor(((double)mx[1] - g.oy) * g.inv_e) + 2.0;
-        double nz = std::floor(((double)mx[2] - g.oz) * g.inv_e) + 2.0;
-        if (nx * ny * nz <= (double)(1 << 27) && nx < 65536 && ny < 65536 && nz < 65536) {
-            g.nx = (int)nx; g.ny = (int)ny; g.nz = (int)nz; g.ncells = g.nx * g.ny * g.nz;
-            break;
-        }
-        E *= 2.0;     // coarser cells stay correct (only more candidates per query)
-        g.ncells = 0;
-    }
-    if (g.ncells <= 0) return fail(h, S2M_ERR_CAPACITY, "map extent too large for the search grid");
-
-    if ((rc = ensure(h, h->reg.map_sorted, sizeof(float4) * n))) return rc;
-    if ((rc = ensure(h, h->reg.m_counts, sizeof(int32_t) * ((size_t)g.ncells + 1)))) return rc;
-    if ((rc = ensure(h, h->reg.m_cell_start, sizeof(int32_t) * ((size_t)g.ncells + 1)))) return rc;
-    if ((rc = ensure(h, h->reg.m_cell_of, sizeof(int32_t) * n))) return rc;
-    if ((rc = ensure(h, h->reg.m_rank_of, sizeof(int32_t) * n))) return rc;
-
-    S2M_HIP(h, hipMemsetAsync(h->reg.m_counts.p, 0, sizeof(int32_t) * ((size_t)g.ncells + 1), h->stream));
-    const int nb = ((int)n + 255) / 256;
-    hipLaunchKernelGGL(k_bin_count, dim3(nb), dim3(256), 0, h->stream, d_pts, stride, (int)n, g,
-                       h->reg.m_cell_of.as<int32_t>(), h->reg.m_rank_of.as<int32_t>(), h->reg.m_counts.as<int32_t>());
-    S2M_HIP(h, hipGetLastError());
-    if ((rc = device_exclusive_scan(h, h->reg.m_counts.as<int32_t>(), h->reg.m_cell_start.as<int32_t>(), g.ncells, (int)n))) return rc;
-    hipLaunchKernelGGL(k_scatter_map, dim3(nb), dim3(256), 0, h->stream, d_pts, stride, (int)n,
-                       (const int32_t*)h->reg.m_cell_of.as<int32_t>(), (const int32_t*)h->reg.m_rank_of.as<int32_t>(),
-                       (const int32_t*)h->reg.m_cell_start.as<int32_t>(), h->reg.map_sorted.as<float4>());
-    S2M_HIP(h, hipGetLastError());
-
-    if (h->reg.have_scan && h->reg.n_q > 0 && h->reg.cert.p) {           // tuples and certificates of the old map are meaningless now
-        S2M_HIP(h, hipMemsetAsync(h->reg.cert.p, 0, sizeof(float4) * h->reg.n_q, h->stream));
-        S2M_HIP(h, hipMemsetAsync(h->reg.aux.p, 0, sizeof(int4) * h->reg.n_q, h->stream));
-    }
-    h->batch.map_epoch++;
-    h->reg.n_m = n;                                       // committed only now; a failure above leaves no map at all (set_map_impl)
-    h->hctx.n_m = (int32_t)n;
-    h->hctx.g = g;
-    h->hctx.map_sorted = h->reg.map_sorted.as<float4>();
-    h->hctx.cell_start = h->reg.m_cell_start.as<int32_t>();
-    h->ctx_dirty = true;
-    S2M_HIP(h, hipEventRecord(h->reg.ev_d, h->stream));
-    if ((rc = upload_ctx(h))) return rc;
-    S2M_HIP(h, hipStreamSynchronize(h->stream));     // the caller's buffer is free again
-    S2M_HIP(h, hipEventElapsedTime(&h->reg.t_set_map_ms, h->reg.ev_c, h->reg.ev_d));
-    return S2M_OK;
-}
-
-// s2m_set_scan in three steps, so that the scan slots of a batch share the launches of the middle one:
-//   scan_slot_prepare   host side: sizes, buffers, the upload of a host source, the DevCtx fields - and the slot's row of the table
-//   launch_scan_prep    the ordering kernels, one grid row per slot (blockIdx.y): six for the slots of a batch, four for a single
-//                       scan (the cell scan inside the scatter; the wave table left to the scan's first optimisation)
-//   scan_slot_finish    bookkeeping
-int scan_slot_prepare(s2m_context* h, const void* pts, size_t n, size_t stride, bool on_device, PrepSlot* ps)
-{
-    int rc = check_records(h, pts, n, stride);
-    if (rc) return rc;
-    memset(ps, 0, sizeof(*ps));
-    h->reg.n_q = n; h->reg.have_scan = true;
-    h->hctx.n_q = (int32_t)n;
-    // wave table capacity: every 64-point chunk plus a 50 % budget of extra waves for split chunks
-    const int n_chunks = (int)((n + 63) / 64);
-    constexpr int NW = kBlock / 64;
-    // how finely to cut when the scan alone cannot fill the GPU (~2048 co-resident waves): 1, 2, 4 or 8
-    int base_parts = 1;
-    while (base_parts < 8 && n_chunks * base_parts * 2 <= 2048) base_parts *= 2;
-    h->reg.base_parts = base_parts;
-    int nblocks = (n_chunks * base_parts + n_chunks / 2 + NW - 1) / NW;
-    nblocks = ((nblocks + kBlocksQuantum - 1) / kBlocksQuantum) * kBlocksQuantum;
-    if (nblocks == 0) nblocks = kBlocksQuantum;
-    const int table_cap = nblocks * NW;                   // wave-table entries: every chunk plus the budget for split chunks
-    // more entries than one 8-wave workgroup per CU holds: 16-wave workgroups, one per CU (s2m_types.h, kBigWaves)
-    const int wpb = (h->tune.big_blocks && n_chunks * base_parts > (kMaxBlocks / 2) * NW) ? kBigWaves : NW;
-    // the grid stays co-resident - one workgroup per CU in either shape (the 8-wave shape of a single scan is built for 2 waves
-    // per SIMD: 256 registers per lane, no scratch; the scan slots of a batch run the 128-register build, two per CU) - and waves
-    // loop over the table
-    nblocks = std::min((table_cap + wpb - 1) / wpb, (wpb == NW && h->batch.parent) ? kMaxBlocks : kMaxBlocks / 2);
-    if (h->batch.parent && h->tune.batch_entries > 1) nblocks = std::max((nblocks + h->tune.batch_entries - 1) / h->tune.batch_entries, 1);   // a batch slot: several entries per wave
-    h->hctx.wpb = wpb;
-    h->hctx.nblocks = nblocks;
-    h->hctx.table_cap = table_cap;
-    h->ctx_dirty = true;
-    if ((rc = ensure_rows(h, nblocks))) return rc;
-    if (n == 0) return S2M_OK;
-
-    const unsigned char* d_pts;
-    if (on_device) d_pts = static_cast<const unsigned char*>(pts);
-    else {
-        if ((rc = stage_host_records(h, h->reg.raw_scan, pts, n * stride))) return rc;
-        S2M_HIP(h, hipEventRecord(h->reg.ev_up, h->stream));   // waited for in scan_slot_finish: the caller's buffer is free when the call returns
-        d_pts = h->reg.raw_scan.as<unsigned char>();
-    }
-    // locality order of the scan: log-polar Z-order bins (k_polar_count), no host round trip
-    if ((rc = ensure(h, h->reg.qx, sizeof(float) * n))) return rc;
-    if ((rc = ensure(h, h->reg.qy, sizeof(float) * n))) return rc;
-    if ((rc = ensure(h, h->reg.qz, sizeof(float) * n))) return rc;
-    if ((rc = ensure(h, h->reg.qperm, sizeof(int32_t) * n))) return rc;
-    if ((rc = ensure(h, h->reg.npos, sizeof(int32_t) * 5 * n))) return rc;
-    if ((rc = ensure(h, h->reg.plane_cache, sizeof(float4) * n))) return rc;
-    if ((rc = ensure(h, h->reg.plane_alt, sizeof(float4) * n))) return rc;
-    if ((rc = ensure(h, h->reg.npos_alt, sizeof(int32_t) * 5 * n))) return rc;
-    if ((rc = ensure(h, h->reg.cert, sizeof(float4) * n))) return rc;           // cert and aux are reset by k_scatter_scan
-    if ((rc = ensure(h, h->reg.aux, sizeof(int4) * n))) return rc;
-    if ((rc = ensure(h, h->reg.front, sizeof(float4) * kNbrCap * n))) return rc;
-    if ((rc = ensure(h, h->reg.q_cell_start, sizeof(int32_t) * kPolarCells))) return rc;
-    if ((rc = ensure(h, h->reg.q_cell_of, sizeof(int32_t) * n))) return rc;
-    if ((rc = ensure(h, h->reg.q_rank_of, sizeof(int32_t) * n))) return rc;
-    const int npb = ((int)n + kPolarBlock - 1) / kPolarBlock;
-    if ((rc = ensure(h, h->reg.q_block_hist, sizeof(int32_t) * (size_t)kPolarCells * (size_t)npb))) return rc;
-    if ((rc = ensure(h, h->reg.chunk_parts, sizeof(int32_t) * (size_t)(n_chunks + 1)))) return rc;
-    {   // density wishes: all zero between uses (k_chunk_table_density clears what it consumes)
-        const void* before = h->reg.chunk_factor.p;
-        if ((rc = ensure(h, h->reg.chunk_factor, sizeof(int32_t) * (size_t)(n_chunks + 1)))) return rc;
-        if (h->reg.chunk_factor.p != before) S2M_HIP(h, hipMemsetAsync(h->reg.chunk_factor.p, 0, h->reg.chunk_factor.cap, h->stream));
-    }
-    if ((rc = ensure(h, h->reg.wave_table, sizeof(int2) * (size_t)table_cap))) return rc;
-    if ((rc = ensure(h, h->reg.n_waves, 64))) return rc;
-
-    ps->pts = d_pts; ps->stride = stride; ps->n = (int32_t)n; ps->n_chunks = n_chunks; ps->base_parts = base_parts;
-    ps->capacity = table_cap; ps->npb = npb;
-    ps->cell_of = h->reg.q_cell_of.as<int32_t>(); ps->rank_of = h->reg.q_rank_of.as<int32_t>(); ps->block_hist = h->reg.q_block_hist.as<int32_t>();
-    ps->counts = h->reg.q_counts.as<int32_t>(); ps->cell_start = h->reg.q_cell_start.as<int32_t>();
-    ps->qx = h->reg.qx.as<float>(); ps->qy = h->reg.qy.as<float>(); ps->qz = h->reg.qz.as<float>(); ps->qperm = h->reg.qperm.as<int32_t>();
-    ps->cert = h->reg.cert.as<float4>(); ps->aux = h->reg.aux.as<int4>();
-    ps->chunk_parts = h->reg.chunk_parts.as<int32_t>(); ps->wave_table = h->reg.wave_table.as<int2>(); ps->n_waves = h->reg.n_waves.as<int32_t>();
-    ps->stamps = nullptr;                                 // (set_scan_impl: a single scan times its preparation)
-    h->reg.prep_slot = *ps;
-
-    h->hctx.qx = h->reg.qx.as<float>(); h->hctx.qy = h->reg.qy.as<float>(); h->hctx.qz = h->reg.qz.as<float>();
-    h->hctx.qperm = h->reg.qperm.as<int32_t>();
-    h->hctx.wave_table = h->reg.wave_table.as<int2>();
-    h->hctx.n_waves = h->reg.n_waves.as<int32_t>();
-    h->hctx.wave_table_rw = h->reg.wave_table.as<int2>();
-    h->hctx.n_waves_rw = h->reg.n_waves.as<int32_t>();
-    h->hctx.chunk_parts = h->reg.chunk_parts.as<int32_t>();
-    h->hctx.chunk_factor = h->reg.chunk_factor.as<int32_t>();
-    h->hctx.n_chunks = n_chunks;
-    h->hctx.density_pending = 1;
-    h->hctx.npos = h->reg.npos.as<int32_t>();
-    h->hctx.cert = h->reg.cert.as<float4>();
-    h->hctx.aux = h->reg.aux.as<int4>();
-    h->hctx.front = h->reg.front.as<float4>();
-    h->hctx.plane_cache = h->reg.plane_cache.as<float4>();
-    h->hctx.plane_alt = h->reg.plane_alt.as<float4>();
-    h->hctx.npos_alt = h->reg.npos_alt.as<int32_t>();
-    h->ctx_dirty = true;
-    return S2M_OK;
-}
-
-// the ordering kernels of `nslots` prepared slots (rows with n = 0 do nothing), on `stream`
-// `single` (a scan of the handle's own, one slot): k_polar_count, k_polar_prefix, the scatter with the cell scan in it,
-// k_chunk_parts - and no wave table: the scan's first optimisation asks for the density wishes chunk by chunk
-// (k_wave_density_state) and k_chunk_table_density emits the table once; whatever else needs the extent-only table first
-// builds it through ensure_wave_table.
-void launch_scan_prep(hipStream_t stream, const PrepTable& t, int nslots, bool single = false)
-{
-    int npb = 0, nb = 0, ncb = 0;
-    for (int k = 0; k < nslots; k++) {
-        npb = std::max(npb, (int)t.s[k].npb);
-        nb = std::max(nb, (t.s[k].n + 255) / 256);
-        ncb = std::max(ncb, (t.s[k].n_chunks + 3) / 4);
-    }
-    if (npb == 0) return;
-    hipLaunchKernelGGL(k_polar_count, dim3(npb, nslots), dim3(kPolarBlock), 0, stream, t);
-    hipLaunchKernelGGL(k_polar_prefix, dim3(kPolarCells / 64, nslots), dim3(1024), 0, stream, t);
-    if (single) {
-        hipLaunchKernelGGL(k_scatter_scan_fold, dim3(npb, nslots), dim3(1024), 0, stream, t);
-        hipLaunchKernelGGL(k_chunk_parts, dim3(ncb, nslots), dim3(256), 0, stream, t);
-        return;
-    }
-    hipLaunchKernelGGL(k_polar_scan, dim3(1, nslots), dim3(1024), 0, stream, t);
-    hipLaunchKernelGGL(k_scatter_scan, dim3(nb, nslots), dim3(256), 0, stream, t);
-    hipLaunchKernelGGL(k_chunk_parts, dim3(ncb, nslots), dim3(256), 0, stream, t);
-    hipLaunchKernelGGL(k_chunk_table, dim3(1, nslots), dim3(1024), 0, stream, t);
-}
-
-// the PrepSlot row of the resident scan, as far as k_chunk_table reads it
-void table_slot_of(s2m_context* h, PrepSlot* ps)
-{
-    memset(ps, 0, sizeof(*ps));
-    ps->n = (int32_t)h->reg.n_q; ps->n_chunks = h->hctx.n_chunks; ps->capacity = h->hctx.table_cap;
-    ps->chunk_parts = h->reg.chunk_parts.as<int32_t>(); ps->wave_table = h->reg.wave_table.as<int2>(); ps->n_waves = h->reg.n_waves.as<int32_t>();
-}
-
-// The extent-only wave table of a single scan is built on demand: by whatever reads the table or its wave count before the
-// scan's first optimisation has emitted the density-aware one (the observation and timing hooks, a handle with the density
-// pass switched off).
-void ensure_wave_table(s2m_context* h)
-{
-    if (!h->reg.table_stale) return;
-    PrepTable t;
-    table_slot_of(h, &t.s[0]);
-    hipLaunchKernelGGL(k_chunk_table, dim3(1, 1), dim3(1024), 0, h->stream, t);
-    h->reg.table_stale = false;
-}
-
-}  // namespace
-
-int s2m::host::set_scan_impl(s2m_context* h, const void* pts, size_t n, size_t stride, bool on_device)
-{
-    S2M_HIP(h, hipSetDevice(h->device));
-    PrepTable t;
-    int rc = scan_slot_prepare(h, pts, n, stride, on_device, &t.s[0]);
-    if (rc) return rc;
-    if (n == 0) { h->reg.t_set_scan_ms = 0; h->reg.scan_timing_pending = false; h->reg.table_stale = false; return upload_ctx(h); }
-    // the first and the last ordering kernel stamp the device's wall clock into the pinned block (s2m_last_timing): an event
-    // record on either side is a packet of its own in the queue, 5.7 us of idle GPU each
-    // (the last one is k_chunk_parts: PrepSlot::stamps)
-    t.s[0].stamps = h->reg.h_stamps + kStampPrep0;
-    const bool single = h->batch.parent == nullptr;       // the slots of a batch and of a stream of scans keep the six kernels
-    launch_scan_prep(h->stream, t, 1, single);
-    h->reg.table_stale = single;
-    S2M_HIP(h, hipGetLastError());
-    h->reg.scan_timing_pending = true;
-    // (the DevCtx block goes to the device with the next launch that needs it: upload_ctx / push_state)
-    // A host source (pageable or pinned) has been copied by the time this returns; the ordering kernels behind the copy
-    // keep running.  A device-resident source is read asynchronously and must outlive the next synchronising call.
-    if (!on_device) S2M_HIP(h, hipEventSynchronize(h->reg.ev_up));
-    return S2M_OK;
-}
-
-namespace {
-
-void fill_state(s2m_context* h, DevState* s, const float pose[6])
+void s2m::host::fill_state(s2m_context* h, DevState* s, const float pose[6])
 {
     memset(s, 0, sizeof(*s));
     memcpy(s->pose, pose, 24);
@@ -388,8 +69,15 @@ void fill_state(s2m_context* h, DevState* s, const float pose[6])
     s->isDegenerate = h->reg.persist_degenerate;
 }
 
+// `s` as the loop state, with the wave count of the resident scan folded in (k_set_state)
 // `stamp` (pinned, may be null): where the kernel leaves the wall clock once the state is stored
-int push_state(s2m_context* h, const float pose[6], unsigned long long* stamp = nullptr)
+void s2m::host::store_state(s2m_context* h, const DevState& s, unsigned long long* stamp)
+{
+    hipLaunchKernelGGL(k_set_state, dim3(1), dim3(64), 0, h->stream, h->reg.state.as<DevState>(), s,
+                       (const int32_t*)h->reg.n_waves.as<int32_t>(), stamp);
+}
+
+int s2m::host::push_state(s2m_context* h, const float pose[6], unsigned long long* stamp)
 {
     DevState s;
     fill_state(h, &s, pose);
@@ -399,10 +87,27 @@ int push_state(s2m_context* h, const float pose[6], unsigned long long* stamp = 
                            (const int32_t*)h->reg.n_waves.as<int32_t>(), stamp);
         h->ctx_dirty = false;
     } else
-        hipLaunchKernelGGL(k_set_state, dim3(1), dim3(64), 0, h->stream, h->reg.state.as<DevState>(), s,
-                           (const int32_t*)h->reg.n_waves.as<int32_t>(), stamp);
+        store_state(h, s, stamp);
     S2M_HIP(h, hipGetLastError());
     return S2M_OK;
+}
+
+// The density wishes of a single scan's first optimisation from `pose`, with the DevCtx block and the loop state it starts from
+// (k_wave_density_state: one plain launch, no wave table needed); `stamp` as push_state's
+void s2m::host::launch_density_state(s2m_context* h, const float pose[6], unsigned long long* stamp)
+{
+    DensityStateArgs a;
+    a.c = h->hctx;
+    fill_state(h, &a.v, pose);
+    a.cdst = h->reg.dctx.as<DevCtx>(); a.sdst = h->reg.state.as<DevState>();
+    a.stamp = stamp;
+    a.raw_limit = h->tune.density_raw;
+    hipLaunchKernelGGL(k_wave_density_state, dim3((h->hctx.n_chunks + 3) / 4 + 1), dim3(256), 0, h->stream, a);       // (+ 1: the workgroup that stores the blocks)
+}
+
+void s2m::host::launch_chunk_table(hipStream_t stream, const PrepTable& t, int nslots)
+{
+    hipLaunchKernelGGL(k_chunk_table, dim3(1, nslots), dim3(1024), 0, stream, t);
 }
 
 // The LM loop (:1304-1315) as a launch sequence.  One iteration L is either one launch of the fused kernel R(L), or -
@@ -419,25 +124,7 @@ static_assert(sizeof(CtxTable) <= 4096 && sizeof(StateInitTable) <= 4096 && size
               sizeof(DensityStateArgs) <= 4096,
               "kernel arguments are limited to 4 KB");
 
-// what one loop launches over: the scan slots (one for a single scan), the widest grid among them, their common workgroup shape
-struct LoopShape {
-    SlotTable tbl;
-    int nslots = 1;
-    int nblocks = 0;        // grid.x of the registration kernels: the largest DevCtx::nblocks among the slots
-    int table_cap = 0;      // the largest wave-table capacity among the slots (grid of k_wave_density)
-    int wpb = kBlock / 64;  // waves per workgroup (DevCtx::wpb, the same for every slot)
-    bool batch = false;     // scan slots of a batch
-    bool split = false;     // C + S per iteration instead of R
-    bool late = false;      // the split iterations of this loop come late (few rows on the worklist): small search grid
-    bool split_auto = false; // split if the loop's iterations are closed by k_finalize and the lean certify kernel applies
-    bool wishes_done = false; // the density wishes of a pending re-split are in chunk_factor already (s2m_optimize_launch): the loop starts with k_chunk_table_density
-    // a captured single-scan loop: the k_finalize that ends the range copies state + trace to `out` (the pinned mirror) and
-    // stamps the wall clock at `stamp`; both null: the caller copies (plain launches, batches, diagnostics)
-    DevState* out = nullptr;
-    unsigned long long* stamp = nullptr;
-};
-
-LoopShape shape_of(s2m_context* h)
+LoopShape s2m::host::shape_of(s2m_context* h)
 {
     LoopShape sh;
     memset(&sh.tbl, 0, sizeof(sh.tbl));
@@ -449,27 +136,13 @@ LoopShape shape_of(s2m_context* h)
     return sh;
 }
 
+namespace {
+
 template <bool HOOK, int NW, int MINW, int MODE, int CNW>
 inline void launch_k(hipStream_t s, const LoopShape& sh, int L, int flags, int grid_x = 0)
 {
     hipLaunchKernelGGL((k_register<HOOK, NW, MINW, MODE, CNW>), dim3(grid_x > 0 ? std::min(grid_x, sh.nblocks) : sh.nblocks, sh.nslots), dim3(NW * 64), 0, s,
                        sh.tbl, L, flags);
-}
-
-// one fused launch R(L) in the workgroup shape of the scan (DevCtx::wpb); `hook`: the observation variant
-inline void launch_fused(s2m_context* h, const LoopShape& sh, bool hook, int L, int solve_prev)
-{
-    constexpr int NW = kBlock / 64;
-    const int fl = solve_prev ? kFlagSolvePrev : 0;
-    if (sh.wpb == kBigWaves) {
-        if (hook) launch_k<true, kBigWaves, 4, kFused, kBigWaves>(h->stream, sh, L, fl);
-        else      launch_k<false, kBigWaves, 4, kFused, kBigWaves>(h->stream, sh, L, fl);
-    } else if (sh.batch && h->tune.batch_minw == 4 && !hook) {
-        launch_k<false, NW, 4, kFused, NW>(h->stream, sh, L, fl);          // two workgroups per CU (spills in the search path)
-    } else {
-        if (hook) launch_k<true, NW, 2, kFused, NW>(h->stream, sh, L, fl);
-        else      launch_k<false, NW, 2, kFused, NW>(h->stream, sh, L, fl);
-    }
 }
 
 // the search kernel S(L): over the worklist C(L) left, or (all) over every workgroup
@@ -495,8 +168,26 @@ inline void launch_certify(s2m_context* h, const LoopShape& sh, int L, int solve
     else                     launch_k<false, NW, kCertifyWaves, kCertify, NW>(h->stream, sh, L, fl);
 }
 
+}  // namespace
+
+// one fused launch R(L) in the workgroup shape of the scan (DevCtx::wpb); `hook`: the observation variant
+void s2m::host::launch_fused(s2m_context* h, const LoopShape& sh, bool hook, int L, int solve_prev)
+{
+    constexpr int NW = kBlock / 64;
+    const int fl = solve_prev ? kFlagSolvePrev : 0;
+    if (sh.wpb == kBigWaves) {
+        if (hook) launch_k<true, kBigWaves, 4, kFused, kBigWaves>(h->stream, sh, L, fl);
+        else      launch_k<false, kBigWaves, 4, kFused, kBigWaves>(h->stream, sh, L, fl);
+    } else if (sh.batch && h->tune.batch_minw == 4 && !hook) {
+        launch_k<false, NW, 4, kFused, NW>(h->stream, sh, L, fl);          // two workgroups per CU (spills in the search path)
+    } else {
+        if (hook) launch_k<true, NW, 2, kFused, NW>(h->stream, sh, L, fl);
+        else      launch_k<false, NW, 2, kFused, NW>(h->stream, sh, L, fl);
+    }
+}
+
 // iteration L of the loop: R(L), or C(L) S(L)
-inline void launch_iteration(s2m_context* h, const LoopShape& sh, int L, int solve_prev, bool fused_loop = true)
+void s2m::host::launch_iteration(s2m_context* h, const LoopShape& sh, int L, int solve_prev, bool fused_loop)
 {
     if (!sh.split) { launch_fused(h, sh, false, L, solve_prev); return; }
     if (L == 0) { launch_search(h, sh, 0, true); return; }
@@ -505,18 +196,28 @@ inline void launch_iteration(s2m_context* h, const LoopShape& sh, int L, int sol
 }
 
 // ends_range: the last launch of the range (it hands the record over, see LoopShape::out)
-inline void launch_finalize(s2m_context* h, const LoopShape& sh, int L, int mode, bool ends_range = false)
+void s2m::host::launch_finalize(s2m_context* h, const LoopShape& sh, int L, int mode, bool ends_range)
 {
     hipLaunchKernelGGL(k_finalize, dim3(1, sh.nslots), dim3(kFinThreads), 0, h->stream, sh.tbl, L, mode,
                        ends_range ? sh.out : (DevState*)nullptr, ends_range ? sh.stamp : (unsigned long long*)nullptr);
 }
 
-inline void launch_density(s2m_context* h, const LoopShape& sh)
+// the two launches of launch_density: the wishes of every wave-table entry, and the table rebuilt from them
+void s2m::host::launch_density_wishes(s2m_context* h, const LoopShape& sh)
+{
+    hipLaunchKernelGGL(k_wave_density, dim3((sh.table_cap + 3) / 4, sh.nslots), dim3(256), 0, h->stream, sh.tbl, h->tune.density_raw);
+}
+void s2m::host::launch_density_table(s2m_context* h, const LoopShape& sh)
+{
+    hipLaunchKernelGGL(k_chunk_table_density, dim3(1, sh.nslots), dim3(1024), 0, h->stream, sh.tbl);
+}
+
+void s2m::host::launch_density(s2m_context* h, const LoopShape& sh)
 {
     // re-split the wave table for the map density at the initial guess (the transform k_set_state just stored);
     // both kernels take everything from the DevCtx block, so the captured graph stays valid from scan to scan
-    if (!sh.wishes_done) hipLaunchKernelGGL(k_wave_density, dim3((sh.table_cap + 3) / 4, sh.nslots), dim3(256), 0, h->stream, sh.tbl, h->tune.density_raw);
-    hipLaunchKernelGGL(k_chunk_table_density, dim3(1, sh.nslots), dim3(1024), 0, h->stream, sh.tbl);
+    if (!sh.wishes_done) launch_density_wishes(h, sh);
+    launch_density_table(h, sh);
 }
 
 // Launches L0 .. L1-1 of the loop.  A range that starts after launch 0 begins like launch 1 does (transform rebuilt from the
@@ -525,7 +226,7 @@ inline void launch_density(s2m_context* h, const LoopShape& sh)
 // `events`, if given, holds 2*n events recorded around every iteration's launches; with `coarse` only four pairs are recorded - around
 // launch 0, launch 1, the run of back-to-back launches 2 .. n-2 (slots 4, 5) and launch n-1 (slots 6, 7) - so that the event
 // packets do not break up the loop's back-to-back dispatch.
-void enqueue_loop(s2m_context* h, const LoopShape& sh_in, hipEvent_t* events, bool coarse = false, int L0 = 0, int L1 = -1)
+void s2m::host::enqueue_loop(s2m_context* h, const LoopShape& sh_in, hipEvent_t* events, bool coarse, int L0, int L1)
 {
     const int n = h->prm.max_iter;
     if (L1 < 0) L1 = n;
@@ -546,6 +247,8 @@ void enqueue_loop(s2m_context* h, const LoopShape& sh_in, hipEvent_t* events, bo
         if ((!fuse || L == 0 || L == L1 - 1) && !(sh.late && h->tune.close_in_search)) launch_finalize(h, sh, L, 0, L == L1 - 1);   // (late split: the search launch closes)
     }
 }
+
+namespace {
 
 // part 0: the whole loop; 1: launches 0 .. seg-1; 2: launches seg .. max_iter-1
 int get_graph(s2m_context* h, int nblocks, int part, hipGraphExec_t* out)
@@ -617,62 +320,7 @@ void params_to_ctx(s2m_context* h, const s2m_params& prm)
     h->ctx_dirty = true;
 }
 
-// ---- ScanContext store ---------------------------------------------------------------------------
-constexpr size_t kScDesc = (size_t)S2M_SC_NUM_RING * S2M_SC_NUM_SECTOR;
-
-// grow-with-copy (ensure() alone would drop the contents)
-int sc_reserve(s2m_context* h, size_t want)
-{
-    if (want <= h->sc.cap) return S2M_OK;
-    size_t cap = h->sc.cap ? h->sc.cap : 256;
-    while (cap < want) cap *= 2;
-    struct Part { DevBuf* b; size_t elem; } parts[3] = { { &h->sc.store_desc, sizeof(double) * kScDesc },
-                                                         { &h->sc.store_ring, sizeof(float) * S2M_SC_NUM_RING },
-                                                         { &h->sc.store_sector, sizeof(double) * S2M_SC_NUM_SECTOR } };
-    for (Part& p : parts) {
-        void* np = nullptr;
-        S2M_HIP(h, hipMalloc(&np, p.elem * cap));
-        if (h->sc.n) S2M_HIP(h, hipMemcpyAsync(np, p.b->p, p.elem * h->sc.n, hipMemcpyDeviceToDevice, h->stream));
-        S2M_HIP(h, hipStreamSynchronize(h->stream));
-        S2M_HIP(h, p.b->reset(np, p.elem * cap));
-    }
-    h->sc.cap = cap;
-    return S2M_OK;
-}
-
 }  // namespace
-
-// descriptor + ring key are in h->sc.out (device): append them as key frame sc.n
-int s2m::host::sc_append_from_out(s2m_context* h)
-{
-    int rc = sc_reserve(h, h->sc.n + 1);
-    if (rc) return rc;
-    hipLaunchKernelGGL(k_sc_append, dim3(1), dim3(kScThreads), 0, h->stream, (const double*)h->sc.out.as<double>(),
-                       h->sc.store_desc.as<double>(), h->sc.store_ring.as<float>(), h->sc.store_sector.as<double>(), (int)h->sc.n);
-    S2M_HIP(h, hipGetLastError());
-    h->sc.n++;
-    return S2M_OK;
-}
-
-// SCManager::makeScancontext + ring key of a host cloud into h->sc.out (device)
-int s2m::host::sc_build_descriptor(s2m_context* h, const void* pts, size_t n, size_t stride_bytes, bool on_device)
-{
-    S2M_HIP(h, hipMemsetAsync(h->sc.bins.p, 0, sizeof(uint32_t) * kScDesc, h->stream));
-    if (n > 0) {
-        const unsigned char* d_pts = static_cast<const unsigned char*>(pts);
-        if (!on_device) {
-            int rc = stage_host_records(h, h->reg.raw_scan, pts, n * stride_bytes);
-            if (rc) return rc;
-            d_pts = h->reg.raw_scan.as<unsigned char>();
-        }
-        const int blocks = std::min((int)((n + 255) / 256), 1024);
-        hipLaunchKernelGGL(k_sc_polar_max, dim3(blocks), dim3(256), 0, h->stream, d_pts, stride_bytes, (int)n, h->sc.bins.as<uint32_t>());
-    }
-    hipLaunchKernelGGL(k_sc_finish, dim3(1), dim3(64), 0, h->stream, (const uint32_t*)h->sc.bins.as<uint32_t>(),
-                       h->sc.out.as<double>(), h->sc.out.as<double>() + kScDesc);
-    S2M_HIP(h, hipGetLastError());
-    return S2M_OK;
-}
 
 // =============================================================================================
 // C ABI
@@ -866,13 +514,7 @@ int s2m_optimize_launch(s2m_handle h, const float pose[6])
     if (!h->batch.parent && h->hctx.density_pending && h->tune.density_raw > 0) {
         // the first optimisation of a single scan: the density wishes, the DevCtx block and the loop state in one plain launch
         // (k_wave_density_state needs no wave table; the graph behind it starts with k_chunk_table_density)
-        DensityStateArgs a;
-        a.c = h->hctx;
-        fill_state(h, &a.v, pose);
-        a.cdst = h->reg.dctx.as<DevCtx>(); a.sdst = h->reg.state.as<DevState>();
-        a.stamp = h->reg.h_stamps + kStampLoop0;
-        a.raw_limit = h->tune.density_raw;
-        hipLaunchKernelGGL(k_wave_density_state, dim3((h->hctx.n_chunks + 3) / 4 + 1), dim3(256), 0, h->stream, a);       // (+ 1: the workgroup that stores the blocks)
+        launch_density_state(h, pose, h->reg.h_stamps + kStampLoop0);
         S2M_HIP(h, hipGetLastError());
         h->ctx_dirty = false;
         h->reg.table_stale = false;                       // k_chunk_table_density emits the table
@@ -1321,287 +963,6 @@ int s2m_get_trace(s2m_handle h, s2m_iter_trace* out, int cap)
     return n;
 }
 
-int s2m_surf_optimization(s2m_handle h, const float pose[6], int32_t* idx5, float* d2_5, uint8_t* flag, float* coeff4)
-{
-    if (!h || !pose) return S2M_ERR_INVALID_ARG;
-    if (!h->reg.have_scan) return fail(h, S2M_ERR_NO_SCAN, "s2m_set_scan has not been called");
-    S2M_HIP(h, hipSetDevice(h->device));
-    const size_t n = h->reg.n_q;
-    if (n == 0) return S2M_OK;
-    if (h->reg.n_m == 0) {          // no map: nothing is ever gated
-        if (idx5) for (size_t i = 0; i < 5 * n; i++) idx5[i] = -1;
-        if (d2_5) for (size_t i = 0; i < 5 * n; i++) d2_5[i] = INFINITY;
-        if (flag) memset(flag, 0, n);
-        if (coeff4) memset(coeff4, 0, sizeof(float) * 4 * n);
-        return S2M_OK;
-    }
-    int rc;
-    if ((rc = ensure(h, h->reg.dbg_idx5, sizeof(int32_t) * 5 * n))) return rc;
-    if ((rc = ensure(h, h->reg.dbg_d2, sizeof(float) * 5 * n))) return rc;
-    if ((rc = ensure(h, h->reg.dbg_flag, n))) return rc;
-    if ((rc = ensure(h, h->reg.dbg_coeff, sizeof(float) * 4 * n))) return rc;
-    h->hctx.dbg_idx5 = h->reg.dbg_idx5.as<int32_t>(); h->hctx.dbg_d2 = h->reg.dbg_d2.as<float>();
-    h->hctx.dbg_flag = h->reg.dbg_flag.as<uint8_t>(); h->hctx.dbg_coeff = h->reg.dbg_coeff.as<float>();
-    h->ctx_dirty = true;
-    if ((rc = upload_ctx(h))) return rc;
-    if ((rc = push_state(h, pose))) return rc;
-    launch_fused(h, shape_of(h), true, 0, 0);
-    S2M_HIP(h, hipGetLastError());
-    if (idx5) S2M_HIP(h, hipMemcpyAsync(idx5, h->reg.dbg_idx5.p, sizeof(int32_t) * 5 * n, hipMemcpyDeviceToHost, h->stream));
-    if (d2_5) S2M_HIP(h, hipMemcpyAsync(d2_5, h->reg.dbg_d2.p, sizeof(float) * 5 * n, hipMemcpyDeviceToHost, h->stream));
-    if (flag) S2M_HIP(h, hipMemcpyAsync(flag, h->reg.dbg_flag.p, n, hipMemcpyDeviceToHost, h->stream));
-    if (coeff4) S2M_HIP(h, hipMemcpyAsync(coeff4, h->reg.dbg_coeff.p, sizeof(float) * 4 * n, hipMemcpyDeviceToHost, h->stream));
-    S2M_HIP(h, hipStreamSynchronize(h->stream));
-    h->hctx.dbg_idx5 = nullptr; h->hctx.dbg_d2 = nullptr; h->hctx.dbg_flag = nullptr; h->hctx.dbg_coeff = nullptr;
-    h->ctx_dirty = true;
-    return upload_ctx(h);
-}
-
-int s2m_debug_wave_profile(s2m_handle h, const float pose[6], int launches, uint64_t* out, size_t cap_waves)
-{
-    if (!h || !pose || !out || launches == 0) return S2M_ERR_INVALID_ARG;
-    if (!h->reg.have_scan || h->reg.n_m == 0 || h->reg.n_q == 0) return fail(h, S2M_ERR_NO_SCAN, "needs a resident scan and map");
-    S2M_HIP(h, hipSetDevice(h->device));
-    const size_t nwaves = (size_t)h->hctx.nblocks * (size_t)h->hctx.wpb;   // one record per wave of the grid
-    int rc;
-    if ((rc = ensure(h, h->reg.dbg_clk, sizeof(uint64_t) * kProfWords * nwaves))) return rc;
-    S2M_HIP(h, hipMemsetAsync(h->reg.dbg_clk.p, 0, sizeof(uint64_t) * kProfWords * nwaves, h->stream));
-    h->hctx.dbg_clk = h->reg.dbg_clk.as<unsigned long long>();
-    h->ctx_dirty = true;
-    if ((rc = upload_ctx(h))) return rc;
-    if ((rc = push_state(h, pose))) return rc;
-    if (launches < 0) {
-        // a real loop as enqueue_loop issues it (density re-split, R0 F0 R1 R2' ...); the recorded launch is number
-        // N = -launches - 1 (N = 0: the first launch of a scan), closing the iteration before it when the loop is fused
-        const LoopShape sh = shape_of(h);
-        const int nblocks = h->hctx.nblocks, N = -launches - 1;
-        const bool fuse = h->tune.fuse_solve && nblocks <= h->tune.fuse_max_blocks;
-        if (h->tune.density_raw > 0) launch_density(h, sh);
-        h->hctx.density_pending = 0;                      // cleared on the device by the kernel: keep the host copy in step
-        for (int L = 0; L < N; L++) {
-            launch_iteration(h, sh, L, (fuse && L >= 2) ? 1 : 0);
-            if (!fuse || L == 0) launch_finalize(h, sh, L, 0);
-        }
-        launch_fused(h, sh, true, N, (fuse && N >= 2) ? 1 : 0);
-    }
-    for (int rep = 0; rep < launches; rep++)
-        launch_fused(h, shape_of(h), true, 0, 0);
-    S2M_HIP(h, hipGetLastError());
-    const size_t n = nwaves < cap_waves ? nwaves : cap_waves;
-    S2M_HIP(h, hipMemcpyAsync(out, h->reg.dbg_clk.p, sizeof(uint64_t) * kProfWords * n, hipMemcpyDeviceToHost, h->stream));
-    S2M_HIP(h, hipStreamSynchronize(h->stream));
-    h->hctx.dbg_clk = nullptr;
-    h->ctx_dirty = true;
-    if ((rc = upload_ctx(h))) return rc;
-    return (int)n;
-}
-
-int s2m_debug_device_trig(s2m_handle h, const float* x, size_t n, float* s, float* c, float* a)
-{
-    if (!h || (n > 0 && (!x || !s || !c)) || n > (size_t)0x3fffffff) return S2M_ERR_INVALID_ARG;
-    if (n == 0) return S2M_OK;
-    S2M_HIP(h, hipSetDevice(h->device));
-    int rc = ensure(h, h->voxel.in, sizeof(float) * 4 * n);
-    if (rc) return rc;
-    float* d = h->voxel.in.as<float>();
-    S2M_HIP(h, hipMemcpyAsync(d, x, sizeof(float) * n, hipMemcpyHostToDevice, h->stream));
-    hipLaunchKernelGGL(k_debug_sincos, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, (const float*)d, (int)n, d + n, d + 2 * n,
-                       a ? d + 3 * n : (float*)nullptr);
-    S2M_HIP(h, hipGetLastError());
-    S2M_HIP(h, hipMemcpyAsync(s, d + n, sizeof(float) * n, hipMemcpyDeviceToHost, h->stream));
-    S2M_HIP(h, hipMemcpyAsync(c, d + 2 * n, sizeof(float) * n, hipMemcpyDeviceToHost, h->stream));
-    if (a) S2M_HIP(h, hipMemcpyAsync(a, d + 3 * n, sizeof(float) * n, hipMemcpyDeviceToHost, h->stream));
-    S2M_HIP(h, hipStreamSynchronize(h->stream));
-    return S2M_OK;
-}
-
-int s2m_debug_device_hypot(s2m_handle h, const float* x, const float* y, size_t n, float* r)
-{
-    if (!h || (n > 0 && (!x || !y || !r)) || n > (size_t)0x3fffffff) return S2M_ERR_INVALID_ARG;
-    if (n == 0) return S2M_OK;
-    S2M_HIP(h, hipSetDevice(h->device));
-    int rc = ensure(h, h->voxel.in, sizeof(float) * 3 * n);
-    if (rc) return rc;
-    float* d = h->voxel.in.as<float>();
-    S2M_HIP(h, hipMemcpyAsync(d, x, sizeof(float) * n, hipMemcpyHostToDevice, h->stream));
-    S2M_HIP(h, hipMemcpyAsync(d + n, y, sizeof(float) * n, hipMemcpyHostToDevice, h->stream));
-    hipLaunchKernelGGL(k_debug_hypot, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, (const float*)d, (const float*)(d + n), (int)n, d + 2 * n);
-    S2M_HIP(h, hipGetLastError());
-    S2M_HIP(h, hipMemcpyAsync(r, d + 2 * n, sizeof(float) * n, hipMemcpyDeviceToHost, h->stream));
-    S2M_HIP(h, hipStreamSynchronize(h->stream));
-    return S2M_OK;
-}
-
-int s2m_debug_lm_close_check_args(int form, int iter, int max_iter, const double* rows, int n_rows, const float pose0[6],
-                                  const float matP_in[36], const s2m_debug_lm_close_out* out)
-{
-    if (n_rows < 0 || (n_rows > 0 && !rows) || !pose0 || !matP_in || !out) return S2M_ERR_INVALID_ARG;
-    if (form != 0 && form != 1) return S2M_ERR_INVALID_ARG;
-    if (iter < 0 || iter >= max_iter) return S2M_ERR_INVALID_ARG;
-    if (form == 1 && iter == 0) return S2M_ERR_INVALID_ARG;     // launch 1 never closes: iteration 0 needs the degeneracy analysis
-    return S2M_OK;
-}
-
-int s2m_debug_lm_close(s2m_handle h, int form, int iter, const double* rows, int n_rows, const float pose0[6],
-                       int degen_in, const float matP_in[36], s2m_debug_lm_close_out* out)
-{
-    if (!h) return S2M_ERR_INVALID_ARG;
-    if (s2m_debug_lm_close_check_args(form, iter, h->prm.max_iter, rows, n_rows, pose0, matP_in, out))
-        return fail(h, S2M_ERR_INVALID_ARG, "null argument, form outside {0, 1}, iter outside 0 .. max_iter-1, or form 1 at iter 0");
-    if (h->reg.opt_pending) return fail(h, S2M_ERR_INVALID_ARG, "an optimize launch is pending: collect it first");
-    if (!h->reg.have_scan || h->reg.n_m == 0 || h->reg.n_q == 0) return fail(h, S2M_ERR_NO_SCAN, "needs a resident scan and map");
-    S2M_HIP(h, hipSetDevice(h->device));
-    int rc;
-    if ((rc = upload_ctx(h))) return rc;                   // (the parameters of the last s2m_set_params with it)
-    // the rows a close reads: one per workgroup the wave table of the resident scan needs (k_finalize, k_register)
-    ensure_wave_table(h);
-    int32_t n_waves = 0;
-    S2M_HIP(h, hipMemcpyAsync(&n_waves, h->reg.n_waves.p, sizeof(n_waves), hipMemcpyDeviceToHost, h->stream));
-    S2M_HIP(h, hipStreamSynchronize(h->stream));
-    const int nblocks = h->hctx.nblocks, wpb = h->hctx.wpb;
-    const int nb_act = std::min((n_waves + wpb - 1) / wpb, nblocks);
-    if (n_rows > nb_act) return fail(h, S2M_ERR_INVALID_ARG, "more rows than the resident scan has active workgroups");
-    std::vector<double> part((size_t)2 * (size_t)nblocks * kAcc, std::numeric_limits<double>::quiet_NaN());
-    double* slot = part.data() + (size_t)(iter & 1) * (size_t)nblocks * kAcc;
-    for (size_t k = 0; k < (size_t)nb_act * kAcc; k++) slot[k] = k < (size_t)n_rows * kAcc ? rows[k] : 0.0;
-    S2M_HIP(h, hipMemcpyAsync(h->reg.partials.p, part.data(), sizeof(double) * part.size(), hipMemcpyHostToDevice, h->stream));
-    DevState s;
-    fill_state(h, &s, pose0);
-    for (int k = 0; k < 6; k++) { s.pose2[iter & 1][k] = pose0[k]; s.pose2[(iter + 1) & 1][k] = NAN; }
-    s.T_valid = 0;
-    s.isDegenerate = degen_in;
-    memcpy(s.matP, matP_in, sizeof(s.matP));
-    hipLaunchKernelGGL(k_set_state, dim3(1), dim3(64), 0, h->stream, h->reg.state.as<DevState>(), s, (const int32_t*)h->reg.n_waves.as<int32_t>(),
-                       (unsigned long long*)nullptr);
-    S2M_HIP(h, hipMemsetAsync(h->hctx.trace + iter, 0xff, sizeof(s2m_iter_trace), h->stream));
-    const LoopShape sh = shape_of(h);
-    if (form == 0) launch_finalize(h, sh, iter, 0);
-    else           launch_fused(h, sh, false, iter + 1, 1);
-    S2M_HIP(h, hipGetLastError());
-    S2M_HIP(h, hipMemcpyAsync(&h->reg.h_state[1], h->reg.state.p, sizeof(DevState), hipMemcpyDeviceToHost, h->stream));
-    S2M_HIP(h, hipMemcpyAsync(&h->reg.h_trace[iter], h->hctx.trace + iter, sizeof(s2m_iter_trace), hipMemcpyDeviceToHost, h->stream));
-    S2M_HIP(h, hipStreamSynchronize(h->stream));
-    const DevState& r = h->reg.h_state[1];
-    memcpy(out->AtA, r.AtA, sizeof(out->AtA));
-    memcpy(out->AtB, r.AtB, sizeof(out->AtB));
-    out->n_sel_last = r.n_sel_last;
-    out->trace = h->reg.h_trace[iter];
-    memcpy(out->pose, r.pose, 24);
-    memcpy(out->pose_next, r.pose2[(iter + 1) & 1], 24);
-    out->iters_run = r.iters_run; out->converged = r.converged; out->done = r.done; out->stalled = r.stalled;
-    out->is_degenerate = r.isDegenerate;
-    out->n_rows_active = nb_act;
-    memcpy(out->matP, r.matP, sizeof(out->matP));
-    return S2M_OK;
-}
-
-int s2m_normal_eq(s2m_handle h, const float pose[6], float AtA[36], float AtB[6], int32_t* n_sel)
-{
-    if (!h || !pose) return S2M_ERR_INVALID_ARG;
-    if (!h->reg.have_scan) return fail(h, S2M_ERR_NO_SCAN, "s2m_set_scan has not been called");
-    S2M_HIP(h, hipSetDevice(h->device));
-    if (h->reg.n_m == 0 || h->reg.n_q == 0) {
-        if (AtA) memset(AtA, 0, sizeof(float) * 36);
-        if (AtB) memset(AtB, 0, sizeof(float) * 6);
-        if (n_sel) *n_sel = 0;
-        return S2M_OK;
-    }
-    int rc;
-    if ((rc = upload_ctx(h))) return rc;
-    if ((rc = push_state(h, pose))) return rc;
-    {
-        const LoopShape sh = shape_of(h);
-        launch_fused(h, sh, false, 0, 0);
-        launch_finalize(h, sh, 0, 1);
-    }
-    S2M_HIP(h, hipGetLastError());
-    S2M_HIP(h, hipMemcpyAsync(&h->reg.h_state[1], h->reg.state.p, sizeof(DevState), hipMemcpyDeviceToHost, h->stream));
-    S2M_HIP(h, hipStreamSynchronize(h->stream));
-    if (AtA) memcpy(AtA, h->reg.h_state[1].AtA, sizeof(float) * 36);
-    if (AtB) memcpy(AtB, h->reg.h_state[1].AtB, sizeof(float) * 6);
-    if (n_sel) *n_sel = h->reg.h_state[1].n_sel_last;
-    return S2M_OK;
-}
-
-int s2m_debug_scan_prep(s2m_handle h, int32_t chain, const float pose[6], int32_t* qperm, float* qxyz, int32_t* chunk_parts,
-                        int32_t* chunk_factor, int32_t* wave_table, int32_t* n_waves)
-{
-    if (!h || chain < S2M_DEBUG_PREP_READ || chain > S2M_DEBUG_PREP_LEGACY) return S2M_ERR_INVALID_ARG;
-    if (h->batch.parent) return fail(h, S2M_ERR_INVALID_ARG, "a scan slot of a batch keeps the six-kernel chain");
-    if (h->reg.opt_pending) return fail(h, S2M_ERR_INVALID_ARG, "an optimize launch is pending: collect it first");
-    if (!h->reg.have_scan) return fail(h, S2M_ERR_NO_SCAN, "s2m_set_scan has not been called");
-    const size_t n = h->reg.n_q;
-    if (n == 0) { if (n_waves) *n_waves = 0; return S2M_OK; }
-    if (pose && chain != S2M_DEBUG_PREP_READ && h->reg.n_m == 0) return fail(h, S2M_ERR_NO_SCAN, "the density pass needs a map");
-    S2M_HIP(h, hipSetDevice(h->device));
-    const int n_chunks = h->hctx.n_chunks;
-    if (chain != S2M_DEBUG_PREP_READ) {
-        const bool legacy = chain == S2M_DEBUG_PREP_LEGACY;
-        PrepTable t;
-        t.s[0] = h->reg.prep_slot;
-        S2M_HIP(h, hipMemsetAsync(h->reg.chunk_factor.p, 0, sizeof(int32_t) * (size_t)(n_chunks + 1), h->stream));
-        launch_scan_prep(h->stream, t, 1, !legacy);
-        S2M_HIP(h, hipGetLastError());
-        h->reg.table_stale = !legacy;
-        h->hctx.density_pending = 1;
-        h->ctx_dirty = true;
-        if (pose) {
-            const LoopShape sh = shape_of(h);
-            if (legacy) {
-                int rc = push_state(h, pose);
-                if (rc) return rc;
-                hipLaunchKernelGGL(k_wave_density, dim3((sh.table_cap + 3) / 4, 1), dim3(256), 0, h->stream, sh.tbl, h->tune.density_raw);
-            } else {
-                DensityStateArgs a;
-                a.c = h->hctx;
-                fill_state(h, &a.v, pose);
-                a.cdst = h->reg.dctx.as<DevCtx>(); a.sdst = h->reg.state.as<DevState>();
-                a.stamp = nullptr;
-                a.raw_limit = h->tune.density_raw;
-                hipLaunchKernelGGL(k_wave_density_state, dim3((n_chunks + 3) / 4 + 1), dim3(256), 0, h->stream, a);
-                h->ctx_dirty = false;
-                h->reg.table_stale = false;
-            }
-            S2M_HIP(h, hipGetLastError());
-            // the wishes before k_chunk_table_density consumes them
-            if (chunk_factor) S2M_HIP(h, hipMemcpyAsync(chunk_factor, h->reg.chunk_factor.p, sizeof(int32_t) * (size_t)n_chunks, hipMemcpyDeviceToHost, h->stream));
-            hipLaunchKernelGGL(k_chunk_table_density, dim3(1, 1), dim3(1024), 0, h->stream, sh.tbl);
-            S2M_HIP(h, hipGetLastError());
-            h->hctx.density_pending = 0;                  // cleared on the device by the kernel: keep the host copy in step
-        } else if (wave_table || n_waves)
-            ensure_wave_table(h);
-    }
-    if ((!pose || chain == S2M_DEBUG_PREP_READ) && chunk_factor)
-        S2M_HIP(h, hipMemcpyAsync(chunk_factor, h->reg.chunk_factor.p, sizeof(int32_t) * (size_t)n_chunks, hipMemcpyDeviceToHost, h->stream));
-    if (qperm) S2M_HIP(h, hipMemcpyAsync(qperm, h->reg.qperm.p, sizeof(int32_t) * n, hipMemcpyDeviceToHost, h->stream));
-    if (qxyz) {
-        S2M_HIP(h, hipMemcpyAsync(qxyz, h->reg.qx.p, sizeof(float) * n, hipMemcpyDeviceToHost, h->stream));
-        S2M_HIP(h, hipMemcpyAsync(qxyz + n, h->reg.qy.p, sizeof(float) * n, hipMemcpyDeviceToHost, h->stream));
-        S2M_HIP(h, hipMemcpyAsync(qxyz + 2 * n, h->reg.qz.p, sizeof(float) * n, hipMemcpyDeviceToHost, h->stream));
-    }
-    if (chunk_parts) S2M_HIP(h, hipMemcpyAsync(chunk_parts, h->reg.chunk_parts.p, sizeof(int32_t) * (size_t)n_chunks, hipMemcpyDeviceToHost, h->stream));
-    int32_t nw = 0;
-    const bool have_table = !h->reg.table_stale;
-    if (have_table) S2M_HIP(h, hipMemcpyAsync(&nw, h->reg.n_waves.p, sizeof(nw), hipMemcpyDeviceToHost, h->stream));
-    S2M_HIP(h, hipStreamSynchronize(h->stream));
-    if (nw < 0 || nw > h->hctx.table_cap) return fail(h, S2M_ERR_HIP, "wave count outside the table");
-    if (wave_table && nw > 0) {
-        S2M_HIP(h, hipMemcpyAsync(wave_table, h->reg.wave_table.p, sizeof(int2) * (size_t)nw, hipMemcpyDeviceToHost, h->stream));
-        S2M_HIP(h, hipStreamSynchronize(h->stream));
-    }
-    if (n_waves) *n_waves = have_table ? nw : -1;
-    return S2M_OK;
-}
-
-// Diagnostics: workgroups the certify kernels of the last collected loop handed to the search kernel (0 for a fused loop;
-// slot >= 0: that scan slot of the last batch).
-int s2m_debug_deferred(s2m_handle h, int slot)
-{
-    if (!h) return S2M_ERR_INVALID_ARG;
-    if (slot >= 0) { if (slot >= (int)h->batch.kids.size()) return S2M_ERR_INVALID_ARG; h = h->batch.kids[(size_t)slot]; }
-    return h->reg.h_state ? h->reg.h_state[1].deferred_total : 0;
-}
-
 // set_scan_ms: from the start of the first ordering kernel to the end of the last.  optimize_ms: from the end of the state upload
 // of s2m_optimize_launch to the end of the k_finalize that closes the loop (with early exit on: its first range; the second
 // range, where one was needed, is added from an event pair of its own).  Both intervals of a single scan are read from
@@ -1623,220 +984,5 @@ int s2m_last_timing(s2m_handle h, float* optimize_ms, float* set_map_ms, float* 
     return S2M_OK;
 }
 
-static int time_iterations_impl(s2m_handle h, const float pose[6], int reps, float* ms_mean, float* ms_per_iter)
-{
-    if (!h || !pose || reps < 1) return S2M_ERR_INVALID_ARG;
-    if (!h->reg.have_scan || h->reg.n_m == 0 || h->reg.n_q == 0) return fail(h, S2M_ERR_NO_SCAN, "needs a resident scan and map");
-    S2M_HIP(h, hipSetDevice(h->device));
-    int rc;
-    if ((rc = upload_ctx(h))) return rc;
-    const int nit = h->prm.max_iter;
-    if (h->reg.iter_events.size() < (size_t)(2 * nit)) {
-        const size_t old = h->reg.iter_events.size();
-        h->reg.iter_events.resize(2 * nit);
-        for (size_t k = old; k < h->reg.iter_events.size(); k++) S2M_HIP(h, hipEventCreate(&h->reg.iter_events[k]));
-    }
-    std::vector<double> per_iter((size_t)nit, 0.0);
-    for (int rep = 0; rep < reps; rep++) {
-        // a new scan starts without a prior or cached planes (what s2m_set_scan leaves behind)
-        S2M_HIP(h, hipMemsetAsync(h->reg.cert.p, 0, sizeof(float4) * h->reg.n_q, h->stream));
-        S2M_HIP(h, hipMemsetAsync(h->reg.aux.p, 0, sizeof(int4) * h->reg.n_q, h->stream));
-        if ((rc = push_state(h, pose))) return rc;
-        enqueue_loop(h, shape_of(h), h->reg.iter_events.data());     // the real loop, launched one by one between event pairs
-        h->hctx.density_pending = 0;
-        S2M_HIP(h, hipGetLastError());
-        S2M_HIP(h, hipStreamSynchronize(h->stream));
-        for (int it = 0; it < nit; it++) {
-            float ms = 0;
-            S2M_HIP(h, hipEventElapsedTime(&ms, h->reg.iter_events[2 * it], h->reg.iter_events[2 * it + 1]));
-            per_iter[(size_t)it] += ms;
-        }
-    }
-    double total = 0.0;
-    for (int it = 0; it < nit; it++) {
-        total += per_iter[(size_t)it];
-        if (ms_per_iter) ms_per_iter[it] = (float)(per_iter[(size_t)it] / reps);
-    }
-    if (ms_mean) *ms_mean = (float)(total / ((double)reps * nit));
-    return S2M_OK;
-}
-
-// Diagnostics: one full loop from `pose` (max_iter iterations, so early_exit should be off), then `reps` back-to-back
-// replays of the loop's last registration launch in the state the loop ended in (nearly every point certified):
-// solve_prev = 1 closes the iteration before it in its prologue each time (the steady launch of the fused loop),
-// 0 rebuilds the transform only.  Returns the mean time per replayed launch, gaps included.
-int s2m_debug_time_steady(s2m_handle h, const float pose[6], int reps, int solve_prev, float* us_per_launch)
-{
-    if (!h || !pose || reps < 1 || !us_per_launch) return S2M_ERR_INVALID_ARG;
-    if (!h->reg.have_scan || h->reg.n_m == 0 || h->reg.n_q == 0) return fail(h, S2M_ERR_NO_SCAN, "needs a resident scan and map");
-    float p[6];
-    memcpy(p, pose, 24);
-    s2m_result r;
-    int rc = s2m_optimize_resident(h, p, nullptr, &r);
-    if (rc) return rc;
-    if (r.skipped || r.iters_run != h->prm.max_iter) return fail(h, S2M_ERR_INVALID_ARG, "the loop ended early: switch early_exit off");
-    const LoopShape sh = shape_of(h);
-    const int L = h->prm.max_iter;
-    S2M_HIP(h, hipEventRecord(h->reg.ev_c, h->stream));
-    for (int k = 0; k < reps; k++)
-        launch_iteration(h, sh, sh.split ? L + (k & 1) : L, solve_prev ? 1 : 0);   // (split: the worklist slots alternate with the launch parity)
-    S2M_HIP(h, hipGetLastError());
-    S2M_HIP(h, hipEventRecord(h->reg.ev_d, h->stream));
-    S2M_HIP(h, hipStreamSynchronize(h->stream));
-    float ms = 0;
-    S2M_HIP(h, hipEventElapsedTime(&ms, h->reg.ev_c, h->reg.ev_d));
-    *us_per_launch = ms * 1e3f / (float)reps;
-    return S2M_OK;
-}
-
-// Mean duration of a k_register launch over `reps` whole LM loops (max_iter >= 5, fused loop), gaps between the back-to-back
-// launches included: HIP events on the handle's stream around launch 0, launch 1, the run of launches 2 .. n-2 and launch n-1.
-int s2m_time_loop_launches(s2m_handle h, const float pose[6], int reps, float* us_per_launch)
-{
-    if (!h || !pose || reps < 1 || !us_per_launch) return S2M_ERR_INVALID_ARG;
-    if (!h->reg.have_scan || h->reg.n_m == 0 || h->reg.n_q == 0) return fail(h, S2M_ERR_NO_SCAN, "needs a resident scan and map");
-    const int nit = h->prm.max_iter;
-    if (nit < 5) return fail(h, S2M_ERR_INVALID_ARG, "needs max_iter >= 5");
-    S2M_HIP(h, hipSetDevice(h->device));
-    int rc;
-    if ((rc = upload_ctx(h))) return rc;
-    while (h->reg.iter_events.size() < 8) { hipEvent_t e; S2M_HIP(h, hipEventCreate(&e)); h->reg.iter_events.push_back(e); }
-    double total_ms = 0.0;
-    for (int rep = 0; rep < reps; rep++) {
-        S2M_HIP(h, hipMemsetAsync(h->reg.cert.p, 0, sizeof(float4) * h->reg.n_q, h->stream));      // a new scan: no certificates, no neighbourhoods
-        S2M_HIP(h, hipMemsetAsync(h->reg.aux.p, 0, sizeof(int4) * h->reg.n_q, h->stream));
-        if ((rc = push_state(h, pose))) return rc;
-        enqueue_loop(h, shape_of(h), h->reg.iter_events.data(), true);
-        h->hctx.density_pending = 0;
-        S2M_HIP(h, hipGetLastError());
-        S2M_HIP(h, hipStreamSynchronize(h->stream));
-        for (int k = 0; k < 4; k++) {
-            float ms = 0;
-            S2M_HIP(h, hipEventElapsedTime(&ms, h->reg.iter_events[2 * k], h->reg.iter_events[2 * k + 1]));
-            total_ms += ms;
-        }
-    }
-    *us_per_launch = (float)(total_ms * 1e3 / ((double)reps * nit));
-    return S2M_OK;
-}
-
-int s2m_time_iteration_kernel(s2m_handle h, const float pose[6], int reps, float* ms_per_launch)
-{
-    if (!ms_per_launch) return S2M_ERR_INVALID_ARG;
-    return time_iterations_impl(h, pose, reps, ms_per_launch, nullptr);
-}
-
-int s2m_time_iterations(s2m_handle h, const float pose[6], int reps, float* ms_per_iter, int cap)
-{
-    if (!h || !ms_per_iter || cap < h->prm.max_iter) return S2M_ERR_INVALID_ARG;
-    return time_iterations_impl(h, pose, reps, nullptr, ms_per_iter);
-}
-
-int s2m_make_scancontext(s2m_handle h, const void* pts, size_t n, size_t stride_bytes,
-                         double desc[S2M_SC_NUM_RING * S2M_SC_NUM_SECTOR], double ringkey[S2M_SC_NUM_RING])
-{
-    int rc = check_records(h, pts, n, stride_bytes);
-    if (rc) return rc;
-    if (!desc || !ringkey) return S2M_ERR_INVALID_ARG;
-    S2M_HIP(h, hipSetDevice(h->device));
-    if ((rc = sc_build_descriptor(h, pts, n, stride_bytes))) return rc;
-    S2M_HIP(h, hipMemcpyAsync(h->sc.h_stage, h->sc.out.p, sizeof(double) * 1220, hipMemcpyDeviceToHost, h->stream));
-    S2M_HIP(h, hipStreamSynchronize(h->stream));
-    memcpy(desc, h->sc.h_stage, sizeof(double) * 1200);
-    memcpy(ringkey, h->sc.h_stage + 1200, sizeof(double) * 20);
-    return S2M_OK;
-}
-
-// ---- section 8(f) row F3: the SCManager loop detector ---------------------------------------------
-
-int s2m_sc_reset(s2m_handle h)
-{
-    if (!h) return S2M_ERR_INVALID_ARG;
-    h->sc.n = 0; h->sc.n_search = 0; h->sc.counter = 0;
-    return S2M_OK;
-}
-
-int s2m_sc_size(s2m_handle h) { return h ? (int)h->sc.n : S2M_ERR_INVALID_ARG; }
-
-int s2m_sc_add_scan(s2m_handle h, const void* pts, size_t n, size_t stride_bytes)
-{
-    int rc = check_records(h, pts, n, stride_bytes);
-    if (rc) return rc;
-    S2M_HIP(h, hipSetDevice(h->device));
-    if ((rc = sc_build_descriptor(h, pts, n, stride_bytes))) return rc;
-    if ((rc = sc_append_from_out(h))) return rc;
-    S2M_HIP(h, hipStreamSynchronize(h->stream));          // the caller's cloud is free again
-    return S2M_OK;
-}
-
-int s2m_sc_add_descriptor(s2m_handle h, const double desc[S2M_SC_NUM_RING * S2M_SC_NUM_SECTOR])
-{
-    if (!h || !desc) return S2M_ERR_INVALID_ARG;
-    S2M_HIP(h, hipSetDevice(h->device));
-    // ring key = row means, as makeRingkeyFromScancontext (:198-211) / k_sc_finish compute them
-    memcpy(h->sc.h_stage, desc, sizeof(double) * kScDesc);
-    for (int r = 0; r < S2M_SC_NUM_RING; r++) {
-        double a = 0.0;
-        for (int k = 0; k < S2M_SC_NUM_SECTOR; k++) a += desc[r * S2M_SC_NUM_SECTOR + k];
-        h->sc.h_stage[kScDesc + r] = a / 60.0;
-    }
-    S2M_HIP(h, hipMemcpyAsync(h->sc.out.p, h->sc.h_stage, sizeof(double) * 1220, hipMemcpyHostToDevice, h->stream));
-    int rc = sc_append_from_out(h);
-    if (rc) return rc;
-    S2M_HIP(h, hipStreamSynchronize(h->stream));          // h_sc is reused by the next call
-    return S2M_OK;
-}
-
-int s2m_sc_detect_loop(s2m_handle h, int32_t* loop_id, float* yaw_diff_rad, s2m_sc_match* detail)
-{
-    if (!h || !loop_id || !yaw_diff_rad) return S2M_ERR_INVALID_ARG;
-    *loop_id = -1; *yaw_diff_rad = 0.0f;
-    if (detail) { memset(detail, 0, sizeof(*detail)); detail->min_dist = 10000000; }
-    constexpr int NUM_EXCLUDE_RECENT = 30, TREE_MAKING_PERIOD = 10;       // Scancontext.h:89, :99
-    if ((int)h->sc.n < NUM_EXCLUDE_RECENT + 1) return S2M_OK;              // :263-267
-    // the reference rebuilds its kd-tree every TREE_MAKING_PERIOD_ calls; between rebuilds the search sees the older set
-    if (h->sc.counter % TREE_MAKING_PERIOD == 0) h->sc.n_search = h->sc.n - NUM_EXCLUDE_RECENT;
-    h->sc.counter = h->sc.counter + 1;
-    S2M_HIP(h, hipSetDevice(h->device));
-    // the kernel writes its 48-byte result straight into the pinned staging block (host-coherent memory the device can address):
-    // a copy behind the kernel would be a second trip through the queue, and one to pageable memory ~50 us more
-    static_assert(sizeof(ScDetectOut) <= sizeof(double) * 1220, "the result fits the pinned ScanContext staging block");
-    hipLaunchKernelGGL(k_sc_detect, dim3(1), dim3(kScThreads), 0, h->stream, (const double*)h->sc.store_desc.as<double>(),
-                       (const float*)h->sc.store_ring.as<float>(), (const double*)h->sc.store_sector.as<double>(),
-                       (int)h->sc.n, (int)h->sc.n_search, reinterpret_cast<ScDetectOut*>(h->sc.h_stage));
-    S2M_HIP(h, hipGetLastError());
-    S2M_HIP(h, hipStreamSynchronize(h->stream));
-    ScDetectOut o;
-    memcpy(&o, h->sc.h_stage, sizeof(o));
-    *loop_id = o.loop_id; *yaw_diff_rad = o.yaw_diff_rad;
-    if (detail) {
-        detail->min_dist = o.min_dist; detail->nn_idx = o.nn_idx; detail->nn_align = o.nn_align;
-        for (int k = 0; k < 3; k++) { detail->cand_idx[k] = o.cand_idx[k]; detail->cand_d2[k] = o.cand_d2[k]; }
-    }
-    return S2M_OK;
-}
-
-int s2m_sc_distance(s2m_handle h, int32_t query_idx, const int32_t* cand_idx, int32_t m, double* dist, int32_t* shift)
-{
-    if (!h || m < 0 || (m > 0 && (!cand_idx || !dist || !shift))) return S2M_ERR_INVALID_ARG;
-    if (query_idx < 0 || (size_t)query_idx >= h->sc.n) return fail(h, S2M_ERR_INVALID_ARG, "query index outside the descriptor store");
-    for (int32_t k = 0; k < m; k++)
-        if (cand_idx[k] < 0 || (size_t)cand_idx[k] >= h->sc.n) return fail(h, S2M_ERR_INVALID_ARG, "candidate index outside the descriptor store");
-    if (m == 0) return S2M_OK;
-    S2M_HIP(h, hipSetDevice(h->device));
-    const size_t off_d = ((sizeof(int32_t) * (size_t)m + 15) & ~(size_t)15), off_s = off_d + sizeof(double) * (size_t)m;
-    int rc = ensure(h, h->sc.cand, off_s + sizeof(int32_t) * (size_t)m);
-    if (rc) return rc;
-    unsigned char* base = h->sc.cand.as<unsigned char>();
-    S2M_HIP(h, hipMemcpyAsync(base, cand_idx, sizeof(int32_t) * (size_t)m, hipMemcpyHostToDevice, h->stream));
-    hipLaunchKernelGGL(k_sc_distance_batch, dim3((unsigned)m), dim3(kScThreads), 0, h->stream, (const double*)h->sc.store_desc.as<double>(),
-                       (const double*)h->sc.store_sector.as<double>(), (int)query_idx, (const int32_t*)base,
-                       (double*)(base + off_d), (int32_t*)(base + off_s));
-    S2M_HIP(h, hipGetLastError());
-    S2M_HIP(h, hipMemcpyAsync(dist, base + off_d, sizeof(double) * (size_t)m, hipMemcpyDeviceToHost, h->stream));
-    S2M_HIP(h, hipMemcpyAsync(shift, base + off_s, sizeof(int32_t) * (size_t)m, hipMemcpyDeviceToHost, h->stream));
-    S2M_HIP(h, hipStreamSynchronize(h->stream));
-    return S2M_OK;
-}
 
 }  // extern "C"

@@ -1,5 +1,6 @@
 // s2m_context.hpp — the handle behind the C ABI (struct s2m_context) and the host helpers that more than one stage uses.
-// Internal: included by the s2m_abi*.hip translation units only, never installed, and nothing declared here leaves the library.
+// Internal: included by the s2m_abi*.hip translation units, s2m_prep.hip and s2m_sc.hip only, never installed, and nothing declared
+// here leaves the library.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -314,9 +315,51 @@ inline void xyzrpy_to_transform(const float p[6], float T[12])
     host_pose_to_transform(rpyxyz, T, nullptr);
 }
 
-// ---- s2m_abi.hip (they launch kernels of s2m_kernels.hpp) ----
+// ---- s2m_abi.hip (the LM loop: the only unit that launches kernels of s2m_kernels.hpp / s2m_register.hpp; the scan preparation
+// and the observation and timing hooks reach them through these) ----
+float stamps_ms(const s2m_context* h, int from, int to);
+int ensure_rows(s2m_context* h, int nblocks);
+int upload_ctx(s2m_context* h);
+void fill_state(s2m_context* h, DevState* s, const float pose[6]);
+void store_state(s2m_context* h, const DevState& s, unsigned long long* stamp);
+int push_state(s2m_context* h, const float pose[6], unsigned long long* stamp = nullptr);
+void launch_density_state(s2m_context* h, const float pose[6], unsigned long long* stamp);
+// k_chunk_table, the extent-only wave table of `nslots` prepared slots (it shares chunk_table_body with k_chunk_table_density)
+void launch_chunk_table(hipStream_t stream, const PrepTable& t, int nslots);
+// what one loop launches over: the scan slots (one for a single scan), the widest grid among them, their common workgroup shape
+struct LoopShape {
+    SlotTable tbl;
+    int nslots = 1;
+    int nblocks = 0;        // grid.x of the registration kernels: the largest DevCtx::nblocks among the slots
+    int table_cap = 0;      // the largest wave-table capacity among the slots (grid of k_wave_density)
+    int wpb = kBlock / 64;  // waves per workgroup (DevCtx::wpb, the same for every slot)
+    bool batch = false;     // scan slots of a batch
+    bool split = false;     // C + S per iteration instead of R
+    bool late = false;      // the split iterations of this loop come late (few rows on the worklist): small search grid
+    bool split_auto = false; // split if the loop's iterations are closed by k_finalize and the lean certify kernel applies
+    bool wishes_done = false; // the density wishes of a pending re-split are in chunk_factor already (s2m_optimize_launch): the loop starts with k_chunk_table_density
+    // a captured single-scan loop: the k_finalize that ends the range copies state + trace to `out` (the pinned mirror) and
+    // stamps the wall clock at `stamp`; both null: the caller copies (plain launches, batches, diagnostics)
+    DevState* out = nullptr;
+    unsigned long long* stamp = nullptr;
+};
+LoopShape shape_of(s2m_context* h);
+void launch_fused(s2m_context* h, const LoopShape& sh, bool hook, int L, int solve_prev);
+void launch_iteration(s2m_context* h, const LoopShape& sh, int L, int solve_prev, bool fused_loop = true);
+void launch_finalize(s2m_context* h, const LoopShape& sh, int L, int mode, bool ends_range = false);
+void launch_density_wishes(s2m_context* h, const LoopShape& sh);
+void launch_density_table(s2m_context* h, const LoopShape& sh);
+void launch_density(s2m_context* h, const LoopShape& sh);
+void enqueue_loop(s2m_context* h, const LoopShape& sh_in, hipEvent_t* events, bool coarse = false, int L0 = 0, int L1 = -1);
+
+// ---- s2m_prep.hip (the map index and the scan preparation: kernels of s2m_prep.hpp) ----
 int set_map_impl(s2m_context* h, const void* pts, size_t n, size_t stride, bool on_device);
 int set_scan_impl(s2m_context* h, const void* pts, size_t n, size_t stride, bool on_device);
+int scan_slot_prepare(s2m_context* h, const void* pts, size_t n, size_t stride, bool on_device, PrepSlot* ps);
+void launch_scan_prep(hipStream_t stream, const PrepTable& t, int nslots, bool single = false);
+void ensure_wave_table(s2m_context* h);
+
+// ---- s2m_sc.hip ----
 // SCManager::makeScancontext + ring key of a cloud into h->sc.out (device); then: append them as key frame sc.n
 int sc_build_descriptor(s2m_context* h, const void* pts, size_t n, size_t stride_bytes, bool on_device = false);
 int sc_append_from_out(s2m_context* h);

@@ -10,9 +10,9 @@
 namespace s2m {
 namespace {
 
-// sinf / cosf as glibc >= 2.28 computes them: the arithmetic of s2m_kernels.hpp's glibc_sincosf_both, restated here because
-// that header defines the registration kernels (it cannot be included by a second translation unit) and its text is the
-// stamp of the registration profiles. Used by imageProjection's deskew (s2m_project.hip) and by the
+// sinf / cosf as glibc >= 2.28 computes them: the arithmetic of s2m_device.hpp's glibc_sincosf_both, restated here because
+// that header belongs to the registration path and its text is part of the stamp of the registration profiles (DESIGN.md
+// section 14): the stages outside that path keep a copy of their own. Used by imageProjection's deskew (s2m_project.hip) and by the
 // pose graph's correctPoses() (s2m_pose_graph.hip), which rebuilds the store's cached transforms as the host's libm would. tests/test_project_gpu.py compares every deskewed coordinate
 // with a host build that calls libm: the ordinary cases stay below pi/4 (the polynomial alone), the *_large_rotations cases
 // turn through several quadrants (the argument reduction). |angle| >= 120 rad, the fp64 library branch, is not exercised.

@@ -1,46 +1,20 @@
 // s2m_kernels.hpp — hand-written HIP kernels (gfx950 / CDNA4, wave64) of the scan-to-map
-// registration path. Compiled with -ffp-contract=off: every fp32 expression that mirrors the
+// registration path: the LM loop.  The heads of a launch, the wave table (extent-only and
+// re-split for the map's density), the closing step, k_register (s2m_register.hpp, included below), k_finalize and the
+// uploads of the context and state blocks.  Included by s2m_abi.hip alone: the code of a loop
+// kernel depends on which other loop kernels share its module, so they all stay in this one.
+// The map index and the scan ordering are s2m_prep.hpp's, the helpers shared with them s2m_device.hpp's.
+// Compiled with -ffp-contract=off: every fp32 expression that mirrors the
 // reference is evaluated as written (one rounding per operation), and HIP's default
 // correctly-rounded fp32 divide/sqrt keeps the per-correspondence arithmetic bit-identical
 // to an x86-64 (no-FMA) build of the reference.
 //
 // Reference citations are file:line into jimmyshe/liorf (src/mapOptmization.cpp unless named).
 #pragma once
-#include <float.h>
-#include <math.h>
-#include <string.h>
-#include "s2m_types.h"
-
-#if defined(__HIPCC__)
-#define S2M_HD __host__ __device__
-#else
-#define S2M_HD
-#endif
+#include "s2m_device.hpp"
 
 namespace s2m {
 
-// ------------------------------------------------------------------------------------------
-// small device helpers
-// ------------------------------------------------------------------------------------------
-// Pointers fetched from the DevCtx block in memory are generic to the compiler, and generic
-// (flat_*) loads return out of order, forcing vmcnt(0)+lgkmcnt(0) at every use. G() states
-// that they point to global memory so that global_load/global_store with counted waits are used.
-template <typename T> using gptr = __attribute__((address_space(1))) T*;
-template <typename T> __device__ __forceinline__ gptr<T> G(T* p) { return (gptr<T>)p; }
-typedef float v4f __attribute__((ext_vector_type(4)));
-// The DevCtx block of a scan is written by tiny kernels between the loops and only read by the registration kernels: seen
-// through the constant address space its fields - the buffer pointers above all - come by scalar loads into scalar
-// registers (a generic pointer makes every one of them a vector load into a pair of vector registers, because some store
-// of the kernel might alias it: sixteen registers per lane, and spills in the 128-register builds).
-typedef const __attribute__((address_space(4))) DevCtx* CtxP;
-__device__ __forceinline__ CtxP ctx_const(const DevCtx* p) { return (CtxP)p; }
-__device__ __forceinline__ GridDesc grid_of(CtxP cp)
-{
-    GridDesc g;
-    g.ox = cp->g.ox; g.oy = cp->g.oy; g.oz = cp->g.oz; g.inv_e = cp->g.inv_e; g.e = cp->g.e;
-    g.nx = cp->g.nx; g.ny = cp->g.ny; g.nz = cp->g.nz; g.ncells = cp->g.ncells;
-    return g;
-}
 // The head of a registration launch.  Line 0 of DevCtx and line 0 of DevState are read whole, field by field, as the first
 // thing a kernel does - before the `done` branch, so that the two misses overlap and nothing is fetched where it is first
 // used, one dependent round trip per field group (both blocks are always allocated: reading them in a launch that returns at
@@ -73,19 +47,6 @@ __device__ __forceinline__ LmParams lm_params(CtxP cp)
     p.min_corr = cp->min_corr; p.early_exit = cp->early_exit; p.conv_deg = cp->conv_deg; p.conv_cm = cp->conv_cm;
     return p;
 }
-__device__ __forceinline__ uint32_t f2ord(float f)
-{
-    uint32_t u = __float_as_uint(f);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-
-__device__ __forceinline__ int cell_coord(float v, float o, float inv_e, int n)
-{
-    float f = floorf((v - o) * inv_e);
-    f = fminf(fmaxf(f, 0.0f), (float)(n - 1));      // NaN -> 0, +-inf -> edge cells
-    return (int)f;
-}
-
 __device__ __forceinline__ void swap_if(bool c, float& a, float& b)
 {
     float t = a; a = c ? b : a; b = c ? t : b;
@@ -93,640 +54,6 @@ __device__ __forceinline__ void swap_if(bool c, float& a, float& b)
 __device__ __forceinline__ void swap_if(bool c, int& a, int& b)
 {
     int t = a; a = c ? b : a; b = c ? t : b;
-}
-
-// ------------------------------------------------------------------------------------------
-// sinf / cosf as glibc >= 2.28 computes them (sysdeps/ieee754/flt-32/s_sinf.c, s_cosf.c, s_sincosf.h;
-// S. Nagy's implementation [ext]): the reference builds its transform with std::sin/std::cos of floats
-// (pcl::getTransformation, :348-351, and the LM trig, :1170-1175), i.e. with the host's libm, and glibc's
-// sinf is not correctly rounded - near 0.3 rad it is one ulp off the correctly rounded value for 3 % of
-// the arguments.  One ulp in the transform is enough to flip a marginal correspondence, so the launches
-// that rebuild the transform on the device use the same arithmetic: argument reduction by a scaled
-// float-to-int conversion, degree-7 / degree-8 polynomials in fp64, one rounding to fp32 at the end.
-// Checked against glibc 2.35's sinf/cosf on 2e7 random arguments in [-4, 4]: no mismatch, with or without
-// FMA contraction of the polynomial; tests/test_parity_gpu.py::test_device_trig_is_the_hosts compares the
-// device results with the test host's libm.  |x| >= 120 does not occur for a pose angle and takes the fp64
-// library function.
-// ------------------------------------------------------------------------------------------
-// The reduction constants and the polynomial coefficients (glibc's __sincosf_table[2]: the second set has c0..c4 negated) are
-// literals: instruction immediates on the device, where a table indexed at run time sits in memory and costs every caller a
-// dependent load or two in the middle of the polynomial.
-constexpr double kSincosfHpiInv = 0x1.45F306DC9C883p+23, kSincosfHpi = 0x1.921FB54442D18p0;
-S2M_HD inline double sincosf_sign(int n) { return ((n ^ (n >> 1)) & 1) ? -1.0 : 1.0; }   // {1, -1, -1, 1}[n & 3]
-S2M_HD inline uint32_t abstop12(float x)
-{
-    uint32_t u;
-    memcpy(&u, &x, 4);
-    return (u >> 20) & 0x7ffu;
-}
-// neg: the second coefficient set
-S2M_HD inline float sinf_poly(double x, double x2, bool neg, int n)
-{
-    if ((n & 1) == 0) {
-        const double ps1 = -0x1.555545995a603p-3, ps2 = 0x1.1107605230bc4p-7, ps3 = -0x1.994eb3774cf24p-13;
-        const double x3 = x * x2, s1 = ps2 + x2 * ps3, x7 = x3 * x2, s = x + x3 * ps1;
-        return (float)(s + x7 * s1);
-    }
-    const double pc0 = neg ? -0x1p0 : 0x1p0, pc1 = neg ? 0x1.ffffffd0c621cp-2 : -0x1.ffffffd0c621cp-2;
-    const double pc2 = neg ? -0x1.55553e1068f19p-5 : 0x1.55553e1068f19p-5, pc3 = neg ? 0x1.6c087e89a359dp-10 : -0x1.6c087e89a359dp-10;
-    const double pc4 = neg ? -0x1.99343027bf8c3p-16 : 0x1.99343027bf8c3p-16;
-    const double x4 = x2 * x2, c2 = pc3 + x2 * pc4, c1 = pc0 + x2 * pc1, x6 = x4 * x2, c = c1 + x4 * pc2;
-    return (float)(c + x6 * c2);
-}
-// which = 0: sinf(y), 1: cosf(y)
-S2M_HD inline float glibc_sincosf(float y, int which)
-{
-    double x = (double)y;
-    if (abstop12(y) < abstop12(0x1.921FB6p-1f)) {                      // |y| < pi/4
-        if (abstop12(y) < abstop12(0x1p-12f)) return which ? 1.0f : y;
-        return sinf_poly(x, x * x, false, which);
-    }
-    if (abstop12(y) < abstop12(120.0f)) {
-        const double r = x * kSincosfHpiInv;                            // reduce_fast: quadrant in bits 24..31
-        const int n = ((int32_t)r + 0x800000) >> 24;
-        x = x - (double)n * kSincosfHpi;
-        const double sgn = sincosf_sign(n);
-        return sinf_poly(x * sgn, x * x, (n & 2) != 0, n ^ which);
-    }
-    return which ? (float)cos(x) : (float)sin(x);
-}
-
-// Both at once for the launches that rebuild the transform: one argument reduction, and the two polynomials (independent
-// chains) side by side; glibc's sinf and cosf share the reduction and differ only in which polynomial they return.
-S2M_HD inline void glibc_sincosf_both(float y, float& sn, float& cs)
-{
-    double x = (double)y;
-    int n = 0;
-    int tbl = 0;
-    if (abstop12(y) < abstop12(0x1.921FB6p-1f)) {                      // |y| < pi/4
-        if (abstop12(y) < abstop12(0x1p-12f)) { sn = y; cs = 1.0f; return; }
-    } else if (abstop12(y) < abstop12(120.0f)) {
-        const double r = x * kSincosfHpiInv;
-        n = ((int32_t)r + 0x800000) >> 24;
-        x = x - (double)n * kSincosfHpi;
-        x = x * sincosf_sign(n);
-        tbl = (n & 2) ? 1 : 0;
-    } else { sn = (float)sin(x); cs = (float)cos(x); return; }
-    const double x2 = x * x;
-    const float a = sinf_poly(x, x2, tbl != 0, 0), b = sinf_poly(x, x2, tbl != 0, 1);
-    sn = (n & 1) ? b : a;
-    cs = (n & 1) ? a : b;
-}
-
-// atanf as glibc computes it (sysdeps/ieee754/flt-32/s_atanf.c: the fdlibm algorithm in fp32 [ext]; no FMA
-// variant exists for it): SCManager's xy2theta (include/Scancontext.cpp:23-36) calls atan on a float, i.e. the
-// host's atanf, and a sector index is the ceiling of the angle - one ulp decides on which side of a sector
-// boundary a point falls.  Checked against glibc 2.35's atanf on 2e7 random arguments: no mismatch; the
-// GPU tests compare whole descriptors with the oracle, which calls the host's libm.
-S2M_HD inline float glibc_atanf(float x)
-{
-    const float atanhi[4] = { 4.6364760399e-01f, 7.8539812565e-01f, 9.8279368877e-01f, 1.5707962513e+00f };
-    const float atanlo[4] = { 5.0121582440e-09f, 3.7748947079e-08f, 3.4473217170e-08f, 7.5497894159e-08f };
-    const float aT[11] = { 3.3333334327e-01f, -2.0000000298e-01f, 1.4285714924e-01f, -1.1111110449e-01f, 9.0908870101e-02f, -7.6918758452e-02f,
-                           6.6610731184e-02f, -5.8335702866e-02f, 4.9768779427e-02f, -3.6531571299e-02f, 1.6285819933e-02f };
-    uint32_t u;
-    memcpy(&u, &x, 4);
-    const int32_t hx = (int32_t)u, ix = hx & 0x7fffffff;
-    int id;
-    if (ix >= 0x4c000000) {                              // |x| >= 2^25
-        if (ix > 0x7f800000) return x + x;               // NaN
-        return (hx > 0) ? atanhi[3] + atanlo[3] : -atanhi[3] - atanlo[3];
-    }
-    if (ix < 0x3ee00000) {                               // |x| < 0.4375
-        if (ix < 0x31000000) return x;                   // |x| < 2^-29
-        id = -1;
-    } else {
-        x = fabsf(x);
-        if (ix < 0x3f980000) {                           // |x| < 1.1875
-            if (ix < 0x3f300000) { id = 0; x = (2.0f * x - 1.0f) / (2.0f + x); }
-            else                 { id = 1; x = (x - 1.0f) / (x + 1.0f); }
-        } else {
-            if (ix < 0x401c0000) { id = 2; x = (x - 1.5f) / (1.0f + 1.5f * x); }
-            else                 { id = 3; x = -1.0f / x; }
-        }
-    }
-    const float z = x * x, w = z * z;
-    const float s1 = z * (aT[0] + w * (aT[2] + w * (aT[4] + w * (aT[6] + w * (aT[8] + w * aT[10])))));
-    const float s2 = w * (aT[1] + w * (aT[3] + w * (aT[5] + w * (aT[7] + w * aT[9]))));
-    if (id < 0) return x - x * (s1 + s2);
-    const float r = atanhi[id] - ((x * (s1 + s2) - atanlo[id]) - x);
-    return (hx < 0) ? -r : r;
-}
-
-// hypotf as glibc computes it (sysdeps/ieee754/flt-32/e_hypotf.c [ext]: glibc >= 2.35 states it this way, older
-// versions compute the same double expression): (float)sqrt((double)x * x + (double)y * y) with correctly rounded
-// fp64 multiply, add and sqrt, and +inf for an infinite argument whatever the other one is.  cv::eigen's Jacobi
-// rotations (eigen6_sym) call std::hypot on floats, i.e. the host's libm; the device library's hypotf scales by
-// the larger exponent and works in fp32 (fma, then the fp32 square root), which is a different rounding: one ulp
-// apart for about one argument pair in ten, and an ulp in a rotation moves the eigenvalues that the eig_thresh
-// comparison reads.  The products are exact in fp64 (24-bit factors), so contraction could not change the sum;
-// it stays unfused all the same.  tests/test_lm_close_gpu.py::test_device_hypot_is_the_hosts compares the device
-// results with the test host's libm.
-S2M_HD inline float glibc_hypotf(float x, float y)
-{
-    if (fabsf(x) == INFINITY || fabsf(y) == INFINITY) return INFINITY;
-    const double dx = (double)x, dy = (double)y;
-    const double xx = dx * dx, yy = dy * dy;
-    return (float)sqrt(xx + yy);
-}
-
-// ------------------------------------------------------------------------------------------
-// index build: bounding box, cell histogram with per-point rank, exclusive scan, scatter
-// ------------------------------------------------------------------------------------------
-// Bounding box of the finite coordinates, as ordered uints (min x, y, z, max x, y, z).  Every workgroup leaves its own box in
-// `part` (8 words each), k_bbox_fold puts them together: adds from every workgroup on one address are served one after the other on
-// this part (~6 ns each) - six of them from each of 782 workgroups were 15 of this kernel's 20 us at 200 k points.
-__global__ __launch_bounds__(256) void k_bbox(const unsigned char* __restrict__ pts, size_t stride, int n, uint32_t* __restrict__ part)
-{
-    __shared__ float smn[4][3], smx[4][3];
-    float mn[3] = { INFINITY, INFINITY, INFINITY }, mx[3] = { -INFINITY, -INFINITY, -INFINITY };
-    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
-        const float* p = reinterpret_cast<const float*>(pts + (size_t)i * stride);
-#pragma unroll
-        for (int d = 0; d < 3; d++) {
-            float v = p[d];
-            if (isfinite(v)) { mn[d] = fminf(mn[d], v); mx[d] = fmaxf(mx[d], v); }
-        }
-    }
-#pragma unroll
-    for (int d = 0; d < 3; d++) {
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) {
-            mn[d] = fminf(mn[d], __shfl_down(mn[d], off, 64));
-            mx[d] = fmaxf(mx[d], __shfl_down(mx[d], off, 64));
-        }
-    }
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (lane == 0) {
-#pragma unroll
-        for (int d = 0; d < 3; d++) { smn[wave][d] = mn[d]; smx[wave][d] = mx[d]; }
-    }
-    __syncthreads();
-    if (threadIdx.x < 3) {
-        const int d = threadIdx.x;
-        const float a = fminf(fminf(smn[0][d], smn[1][d]), fminf(smn[2][d], smn[3][d]));
-        const float b = fmaxf(fmaxf(smx[0][d], smx[1][d]), fmaxf(smx[2][d], smx[3][d]));
-        part[8 * blockIdx.x + d] = a <= b ? f2ord(a) : 0xffffffffu;          // (no finite value: the neutral elements)
-        part[8 * blockIdx.x + 3 + d] = a <= b ? f2ord(b) : 0u;
-    }
-}
-// mm[0..2] = min, mm[3..5] = max over the workgroups' boxes (0xffffffff / 0 where no coordinate was finite)
-__global__ __launch_bounds__(256) void k_bbox_fold(const uint32_t* __restrict__ part, int nparts, uint32_t* __restrict__ mm)
-{
-    __shared__ uint32_t slo[4][3], shi[4][3];
-    uint32_t lo[3] = { 0xffffffffu, 0xffffffffu, 0xffffffffu }, hi[3] = { 0u, 0u, 0u };
-    for (int b = threadIdx.x; b < nparts; b += 256) {
-#pragma unroll
-        for (int d = 0; d < 3; d++) { lo[d] = min(lo[d], part[8 * b + d]); hi[d] = max(hi[d], part[8 * b + 3 + d]); }
-    }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-#pragma unroll
-        for (int d = 0; d < 3; d++) {
-            lo[d] = min(lo[d], (uint32_t)__shfl_down((int)lo[d], off, 64));
-            hi[d] = max(hi[d], (uint32_t)__shfl_down((int)hi[d], off, 64));
-        }
-    }
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (lane == 0) {
-#pragma unroll
-        for (int d = 0; d < 3; d++) { slo[wave][d] = lo[d]; shi[wave][d] = hi[d]; }
-    }
-    __syncthreads();
-    if (threadIdx.x < 3) {
-        const int d = threadIdx.x;
-        mm[d] = min(min(slo[0][d], slo[1][d]), min(slo[2][d], slo[3][d]));
-        mm[3 + d] = max(max(shi[0][d], shi[1][d]), max(shi[2][d], shi[3][d]));
-    }
-}
-
-// linear cell id: x-fastest rows (map grid: a query's 3 x-neighbours are one contiguous run)
-__device__ __forceinline__ int lin_rows(const GridDesc& g, int cx, int cy, int cz)
-{
-    return (cz * g.ny + cy) * g.nx + cx;
-}
-// Scan locality order (ordering only, never results): lidar returns are binned on a
-// log-polar grid around the sensor (128 azimuth x 128 log-range bins; cell size grows with
-// range like the return spacing does, so cells hold a few points each and the rank atomics
-// do not pile up on the dense near-field cells), numbered along a Hilbert curve so that 64
-// consecutive sorted points form a compact patch; a rigid transform keeps it compact.
-constexpr int kPolarCells = 16384;
-// Hilbert curve index of (x, y) on a 128 x 128 grid: consecutive indices are always adjacent
-// cells (a Z-order curve jumps across the grid at every power-of-two boundary, and a wave that
-// straddles a jump gets a huge bounding box).
-__device__ __forceinline__ uint32_t hilbert128(uint32_t x, uint32_t y)
-{
-    uint32_t d = 0;
-#pragma unroll
-    for (uint32_t s = 64; s > 0; s >>= 1) {
-        const uint32_t rx = (x & s) ? 1u : 0u, ry = (y & s) ? 1u : 0u;
-        d += s * s * ((3u * rx) ^ ry);
-        if (ry == 0) {
-            if (rx == 1) { x = 127u - x; y = 127u - y; }
-            const uint32_t t = x; x = y; y = t;
-        }
-    }
-    return d;
-}
-__device__ __forceinline__ int polar_cell(float x, float y)
-{
-    const float rho = sqrtf(x * x + y * y);
-    float az = atan2f(y, x);                                  // [-pi, pi]
-    int ab = (int)((az + 3.14159265f) * (128.0f / 6.2831853f));
-    ab = min(max(ab, 0), 127);
-    float lr = (__log2f(fmaxf(rho, 0.5f)) + 1.0f) * (128.0f / 9.23f);   // 0.5 m .. 300 m
-    int rb = (rho == rho) ? min(max((int)lr, 0), 127) : 0;
-    if (!(az == az)) ab = 0;
-    return (int)hilbert128((uint32_t)ab, (uint32_t)rb);
-}
-
-// Histogram with per-point rank, DETERMINISTIC: the position of a scan point in the locality order depends on the
-// input alone, never on the order in which atomics happen to arrive - so the wave partition, the summation order of the
-// normal equations and with them every bit of a registration's result are reproducible from run to run.
-//   * inside a wave, points of the same cell are ranked by lane (match loop over the distinct cells of the wave);
-//   * the 16 waves of a workgroup add their cell counts to the workgroup's LDS histogram one after the other;
-//   * workgroup b writes its histogram as row b of a table; k_polar_prefix turns every column into an exclusive prefix
-//     over the workgroups (rank of the workgroup's first point in that cell) and the cell totals.
-// (Device-scope returning atomics, the obvious alternative, are also served memory-side on this multi-die part: 120 k
-// of them cost 27 us.)
-constexpr int kPolarBlock = 1024;
-__global__ __launch_bounds__(kPolarBlock) void k_polar_count(const PrepTable tbl)
-{
-    const PrepSlot& ps = tbl.s[blockIdx.y];
-    if ((int)blockIdx.x >= ps.npb) return;
-    if (ps.stamps && blockIdx.x == 0 && threadIdx.x == 0) ps.stamps[0] = wall_clock64();      // the scan preparation starts (s2m_last_timing)
-    const unsigned char* __restrict__ pts = ps.pts; const size_t stride = ps.stride; const int n = ps.n;
-    int32_t* __restrict__ cell_of = ps.cell_of; int32_t* __restrict__ rank_of = ps.rank_of; int32_t* __restrict__ block_hist = ps.block_hist;
-    __shared__ int32_t hist[kPolarCells];
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-    for (int k = t; k < kPolarCells; k += kPolarBlock) hist[k] = 0;
-    const int i = blockIdx.x * kPolarBlock + t;
-    int c = -1;
-    if (i < n) {
-        const float* p = reinterpret_cast<const float*>(pts + (size_t)i * stride);
-        c = polar_cell(p[0], p[1]);
-    }
-    // rank among the lanes of this wave that share the cell, the group's size and its first lane
-    int r_in = 0, cnt = 0, leader = lane;
-    unsigned long long todo = __ballot(c >= 0);
-    while (todo) {
-        const int first = (int)__builtin_ctzll(todo);
-        const int v = __builtin_amdgcn_readlane(c, first);
-        const unsigned long long same = __ballot(c == v);
-        if (c == v) { r_in = __popcll(same & ((1ull << lane) - 1ull)); cnt = __popcll(same); leader = first; }
-        todo &= ~same;
-    }
-    int base = 0;
-    for (int w = 0; w < kPolarBlock / 64; w++) {
-        __syncthreads();
-        if (wave == w && c >= 0 && leader == lane) { base = hist[c]; hist[c] = base + cnt; }     // distinct cells per leader: no conflict
-    }
-    base = __shfl(base, leader, 64);
-    __syncthreads();
-    if (i < n) { cell_of[i] = c; rank_of[i] = base + r_in; }
-    int32_t* row = block_hist + (size_t)blockIdx.x * kPolarCells;
-    for (int k = t; k < kPolarCells; k += kPolarBlock) row[k] = hist[k];
-}
-
-// Column-wise exclusive prefix of the workgroup histograms over the workgroups, in place, and the cell totals.
-// 64 columns x 16 segments of workgroups per 1024 threads: consecutive lanes read consecutive columns.
-__global__ __launch_bounds__(1024) void k_polar_prefix(const PrepTable tbl)
-{
-    const PrepSlot& ps = tbl.s[blockIdx.y];
-    if (ps.n <= 0) return;                                // an empty slot of a batch (its row of the table holds no buffers)
-    int32_t* __restrict__ H = ps.block_hist; const int nb = ps.npb; int32_t* __restrict__ counts = ps.counts;
-    __shared__ int32_t seg[16][64];
-    const int lane = threadIdx.x & 63, s = threadIdx.x >> 6;
-    const int col = blockIdx.x * 64 + lane;
-    const int per = (nb + 15) / 16, b0 = min(s * per, nb), b1 = min(b0 + per, nb);
-    int32_t sum = 0;
-    for (int b = b0; b < b1; b++) sum += H[(size_t)b * kPolarCells + col];
-    seg[s][lane] = sum;
-    __syncthreads();
-    int32_t run = 0, total = 0;
-#pragma unroll
-    for (int q = 0; q < 16; q++) { const int32_t v = seg[q][lane]; run += (q < s) ? v : 0; total += v; }
-    if (s == 0) counts[col] = total;
-    for (int b = b0; b < b1; b++) {
-        const size_t at = (size_t)b * kPolarCells + col;
-        const int32_t v = H[at];
-        H[at] = run;
-        run += v;
-    }
-}
-
-// exclusive scan of the 16384 polar cell counts by one workgroup (16 per thread); the counts are
-// zeroed as they are read, ready for the next scan
-__global__ __launch_bounds__(1024) void k_polar_scan(const PrepTable tbl)
-{
-    const PrepSlot& ps = tbl.s[blockIdx.y];
-    if (ps.n <= 0) return;                                // an empty slot of a batch
-    int32_t* __restrict__ counts = ps.counts; int32_t* __restrict__ start = ps.cell_start;
-    __shared__ int32_t wsum[16];
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-    int32_t v[16];
-    int32_t sum = 0;
-    int4* c4 = reinterpret_cast<int4*>(counts + t * 16);
-#pragma unroll
-    for (int k = 0; k < 4; k++) {
-        const int4 q = c4[k];
-        c4[k] = make_int4(0, 0, 0, 0);
-        v[4 * k] = q.x; v[4 * k + 1] = q.y; v[4 * k + 2] = q.z; v[4 * k + 3] = q.w;
-        sum += q.x + q.y + q.z + q.w;
-    }
-    int32_t incl = sum;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        int32_t o = __shfl_up(incl, off, 64);
-        if (lane >= off) incl += o;
-    }
-    if (lane == 63) wsum[wave] = incl;
-    __syncthreads();
-    int32_t woff = 0;
-    for (int w = 0; w < wave; w++) woff += wsum[w];
-    int32_t run = woff + incl - sum;
-    int4* s4 = reinterpret_cast<int4*>(start + t * 16);
-#pragma unroll
-    for (int k = 0; k < 4; k++) {
-        int4 q;
-        q.x = run; run += v[4 * k];
-        q.y = run; run += v[4 * k + 1];
-        q.z = run; run += v[4 * k + 2];
-        q.w = run; run += v[4 * k + 3];
-        s4[k] = q;
-    }
-}
-
-__global__ void k_bin_count(const unsigned char* __restrict__ pts, size_t stride, int n, GridDesc g,
-                            int32_t* __restrict__ cell_of, int32_t* __restrict__ rank_of,
-                            int32_t* __restrict__ counts)
-{
-    int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const float* p = reinterpret_cast<const float*>(pts + (size_t)i * stride);
-    int cx = cell_coord(p[0], g.ox, g.inv_e, g.nx);
-    int cy = cell_coord(p[1], g.oy, g.inv_e, g.ny);
-    int cz = cell_coord(p[2], g.oz, g.inv_e, g.nz);
-    int c = lin_rows(g, cx, cy, cz);
-    cell_of[i] = c;
-    rank_of[i] = atomicAdd(&counts[c], 1);
-}
-
-// exclusive scan, 1024 elements per 256-thread workgroup
-__global__ __launch_bounds__(256) void k_scan_local(const int32_t* __restrict__ in, int32_t* __restrict__ out,
-                                                    int32_t* __restrict__ block_sums, int n)
-{
-    __shared__ int32_t wsum[4];
-    const int base = blockIdx.x * 1024 + threadIdx.x * 4;
-    int32_t v[4];
-#pragma unroll
-    for (int k = 0; k < 4; k++) v[k] = (base + k < n) ? in[base + k] : 0;
-    int32_t t = v[0] + v[1] + v[2] + v[3];
-    int32_t incl = t;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        int32_t o = __shfl_up(incl, off, 64);
-        if (lane >= off) incl += o;
-    }
-    if (lane == 63) wsum[wave] = incl;
-    __syncthreads();
-    int32_t woff = 0;
-#pragma unroll
-    for (int w = 0; w < 4; w++) if (w < wave) woff += wsum[w];
-    int32_t excl = woff + incl - t;
-#pragma unroll
-    for (int k = 0; k < 4; k++) { if (base + k < n) out[base + k] = excl; excl += v[k]; }
-    if (threadIdx.x == 255) block_sums[blockIdx.x] = woff + incl;
-}
-
-// in-place exclusive scan of the block sums by one workgroup (any nb)
-__global__ __launch_bounds__(1024) void k_scan_sums(int32_t* __restrict__ sums, int nb)
-{
-    __shared__ int32_t wsum[16];
-    __shared__ int32_t carry_s;
-    if (threadIdx.x == 0) carry_s = 0;
-    __syncthreads();
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    for (int base = 0; base < nb; base += 1024) {
-        int i = base + threadIdx.x;
-        int32_t t = (i < nb) ? sums[i] : 0;
-        int32_t incl = t;
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) {
-            int32_t o = __shfl_up(incl, off, 64);
-            if (lane >= off) incl += o;
-        }
-        if (lane == 63) wsum[wave] = incl;
-        __syncthreads();
-        int32_t woff = 0;
-        for (int w = 0; w < wave; w++) woff += wsum[w];
-        int32_t carry = carry_s;
-        if (i < nb) sums[i] = carry + woff + incl - t;
-        __syncthreads();
-        if (threadIdx.x == 1023) carry_s = carry + woff + incl;
-        __syncthreads();
-    }
-}
-
-__global__ __launch_bounds__(256) void k_scan_add(int32_t* __restrict__ out, const int32_t* __restrict__ block_sums,
-                                                  int n, int total)
-{
-    const int base = blockIdx.x * 1024 + threadIdx.x * 4;
-    const int32_t off = block_sums[blockIdx.x];
-#pragma unroll
-    for (int k = 0; k < 4; k++) if (base + k < n) out[base + k] += off;
-    if (blockIdx.x == 0 && threadIdx.x == 0) out[n] = total;
-}
-
-// k_scan_sums and k_scan_add in one launch for grids of up to a few thousand workgroups: every workgroup adds up the sums of the
-// workgroups before it for itself (block_sums as k_scan_local left them)
-__global__ __launch_bounds__(256) void k_scan_add_fold(int32_t* __restrict__ out, const int32_t* __restrict__ block_sums, int n, int total)
-{
-    __shared__ int32_t wsum[4];
-    int32_t before = 0;
-    for (int j = threadIdx.x; j < (int)blockIdx.x; j += 256) before += block_sums[j];
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) before += __shfl_xor(before, o, 64);
-    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = before;
-    __syncthreads();
-    const int32_t off = wsum[0] + wsum[1] + wsum[2] + wsum[3];
-    const int base = blockIdx.x * 1024 + threadIdx.x * 4;
-#pragma unroll
-    for (int k = 0; k < 4; k++) if (base + k < n) out[base + k] += off;
-    if (blockIdx.x == 0 && threadIdx.x == 0) out[n] = total;
-}
-
-__global__ void k_scatter_map(const unsigned char* __restrict__ pts, size_t stride, int n,
-                              const int32_t* __restrict__ cell_of, const int32_t* __restrict__ rank_of,
-                              const int32_t* __restrict__ cell_start, float4* __restrict__ map_sorted)
-{
-    int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const float* p = reinterpret_cast<const float*>(pts + (size_t)i * stride);
-    int pos = cell_start[cell_of[i]] + rank_of[i];
-    map_sorted[pos] = make_float4(p[0], p[1], p[2], __int_as_float(i));
-}
-
-__global__ void k_scatter_scan(const PrepTable tbl)
-{
-    const PrepSlot& ps = tbl.s[blockIdx.y];
-    const unsigned char* __restrict__ pts = ps.pts; const size_t stride = ps.stride; const int n = ps.n;
-    const int32_t* __restrict__ cell_of = ps.cell_of; const int32_t* __restrict__ rank_of = ps.rank_of;
-    const int32_t* __restrict__ cell_start = ps.cell_start; const int32_t* __restrict__ block_hist = ps.block_hist;
-    float* __restrict__ qx = ps.qx; float* __restrict__ qy = ps.qy; float* __restrict__ qz = ps.qz;
-    int32_t* __restrict__ qperm = ps.qperm; float4* __restrict__ cert = ps.cert; int4* __restrict__ aux = ps.aux;
-    int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const float* p = reinterpret_cast<const float*>(pts + (size_t)i * stride);
-    const int c = cell_of[i];
-    // first point of the cell + points of the cell in earlier workgroups of k_polar_count + rank inside the workgroup
-    int pos = cell_start[c] + block_hist[(size_t)(i / kPolarBlock) * kPolarCells + c] + rank_of[i];
-    if ((unsigned)pos >= (unsigned)n) return;            // cannot happen while the histogram is consistent
-    qx[pos] = p[0]; qy[pos] = p[1]; qz[pos] = p[2]; qperm[pos] = i;
-    cert[pos] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);     // a new scan: no certificate (slack 0), no neighbour tuple, no plane
-    aux[pos] = make_int4(0, 0, 0, 0);
-}
-
-// k_polar_scan and k_scatter_scan in one launch (a single scan): every 1024-point workgroup builds the exclusive scan of the
-// 16384 cell totals for itself in LDS - k_polar_scan's integer arithmetic, 16 counts per thread, a wave scan, 16 wave sums -
-// and places its points as k_scatter_scan does, with cell_start[c] taken from LDS.  Nothing else reads q_cell_start, and
-// k_polar_prefix rewrites every count, so neither the scan's result nor zeroed counts are left in memory.
-// (The 16 wave sums pass through the first words of the 64 KB array before the scan overwrites them.)
-__global__ __launch_bounds__(1024) void k_scatter_scan_fold(const PrepTable tbl)
-{
-    const PrepSlot& ps = tbl.s[blockIdx.y];
-    const int n = ps.n;
-    if (n <= 0 || (int)blockIdx.x * 1024 >= n) return;    // (uniform per workgroup)
-    const unsigned char* __restrict__ pts = ps.pts; const size_t stride = ps.stride;
-    const int32_t* __restrict__ cell_of = ps.cell_of; const int32_t* __restrict__ rank_of = ps.rank_of;
-    const int32_t* __restrict__ counts = ps.counts; const int32_t* __restrict__ block_hist = ps.block_hist;
-    float* __restrict__ qx = ps.qx; float* __restrict__ qy = ps.qy; float* __restrict__ qz = ps.qz;
-    int32_t* __restrict__ qperm = ps.qperm; float4* __restrict__ cert = ps.cert; int4* __restrict__ aux = ps.aux;
-    __shared__ int32_t start[kPolarCells];
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-    const int i = blockIdx.x * 1024 + t;
-    // the point's own loads first: they are in flight while the scan is built
-    int c = 0, rank = 0, before = 0;
-    float px = 0.0f, py = 0.0f, pz = 0.0f;
-    if (i < n) {
-        const float* p = reinterpret_cast<const float*>(pts + (size_t)i * stride);
-        c = cell_of[i]; rank = rank_of[i];
-        px = p[0]; py = p[1]; pz = p[2];
-        before = block_hist[(size_t)blockIdx.x * kPolarCells + c];     // (i / kPolarBlock == blockIdx.x: both are 1024)
-    }
-    int32_t v[16];
-    int32_t sum = 0;
-    const int4* c4 = reinterpret_cast<const int4*>(counts + t * 16);
-#pragma unroll
-    for (int k = 0; k < 4; k++) {
-        const int4 q = c4[k];
-        v[4 * k] = q.x; v[4 * k + 1] = q.y; v[4 * k + 2] = q.z; v[4 * k + 3] = q.w;
-        sum += q.x + q.y + q.z + q.w;
-    }
-    int32_t incl = sum;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        int32_t o = __shfl_up(incl, off, 64);
-        if (lane >= off) incl += o;
-    }
-    if (lane == 63) start[wave] = incl;
-    __syncthreads();
-    int32_t woff = 0;
-    for (int w = 0; w < wave; w++) woff += start[w];
-    __syncthreads();
-    int32_t run = woff + incl - sum;
-    int4* s4 = reinterpret_cast<int4*>(start + t * 16);
-#pragma unroll
-    for (int k = 0; k < 4; k++) {
-        int4 q;
-        q.x = run; run += v[4 * k];
-        q.y = run; run += v[4 * k + 1];
-        q.z = run; run += v[4 * k + 2];
-        q.w = run; run += v[4 * k + 3];
-        s4[k] = q;
-    }
-    __syncthreads();
-    if (i >= n) return;
-    // first point of the cell + points of the cell in earlier workgroups of k_polar_count + rank inside the workgroup
-    const int pos = start[c] + before + rank;
-    if ((unsigned)pos >= (unsigned)n) return;            // cannot happen while the histogram is consistent
-    qx[pos] = px; qy[pos] = py; qz[pos] = pz; qperm[pos] = i;
-    cert[pos] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);     // a new scan: no certificate (slack 0), no neighbour tuple, no plane
-    aux[pos] = make_int4(0, 0, 0, 0);
-}
-
-// Work-proportional wave assignment.  The sorted scan is cut into chunks of 64 points; a chunk
-// whose points spread over a large box (sparse far field, tall structures) would make its wave
-// stage and sweep a large map tile, and the slowest wave sets the kernel time.  Such chunks are
-// given to 2, 4 or 8 waves (32 / 16 / 8 points each: tighter boxes, run in parallel).  The extent is
-// measured in the lidar frame - a rigid transform does not change it.
-__global__ __launch_bounds__(256) void k_chunk_parts(const PrepTable tbl)
-{
-    const PrepSlot& ps = tbl.s[blockIdx.y];
-    float* __restrict__ qx = ps.qx; float* __restrict__ qy = ps.qy; float* __restrict__ qz = ps.qz; int32_t* __restrict__ qperm = ps.qperm;
-    const int n = ps.n, n_chunks = ps.n_chunks, base_parts = ps.base_parts; int32_t* __restrict__ parts = ps.chunk_parts;
-    const int lane = threadIdx.x & 63;
-    const int c = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (c >= n_chunks) return;
-    const int i = c * 64 + lane;
-    const bool v = i < n;
-    float x = v ? qx[i] : 0.0f, y = v ? qy[i] : 0.0f, z = v ? qz[i] : 0.0f;
-    int perm = v ? qperm[i] : 0;
-    const bool f = v && fabsf(x) < 3.0e38f && fabsf(y) < 3.0e38f && fabsf(z) < 3.0e38f;
-    float mn[3] = { f ? x : INFINITY, f ? y : INFINITY, f ? z : INFINITY };
-    float mx[3] = { f ? x : -INFINITY, f ? y : -INFINITY, f ? z : -INFINITY };
-#pragma unroll
-    for (int d = 0; d < 3; d++) {
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) {
-            mn[d] = fminf(mn[d], __shfl_xor(mn[d], off, 64));
-            mx[d] = fmaxf(mx[d], __shfl_xor(mx[d], off, 64));
-        }
-    }
-    // Order inside the chunk: the polar cells ignore height and the rank inside a cell is arbitrary, so
-    // the 64 points of a chunk are in no useful order, and cutting the chunk into 2..8 waves would leave
-    // every part as large as the whole.  Sort the chunk along a 3-D Morton curve over its own bounding
-    // box (cubic cells, 16 along the longest axis; bitonic network over the wave, ties by scan index:
-    // deterministic), so that every part is a compact blob whatever the sensor's heading is.  Lanes past
-    // the end of the scan and non-finite points sort last.
-    if (mn[0] <= mx[0]) {
-        const float emax = fmaxf(fmaxf(mx[0] - mn[0], mx[1] - mn[1]), mx[2] - mn[2]);
-        const float sc = emax > 0.0f ? 15.99f / emax : 0.0f;
-        auto spread4 = [](uint32_t b) { return (b & 1u) | ((b & 2u) << 2) | ((b & 4u) << 4) | ((b & 8u) << 6); };   // bit k -> bit 3k
-        uint32_t key = 0x7fffffffu;
-        if (f) {
-            const uint32_t ix = (uint32_t)((x - mn[0]) * sc), iy = (uint32_t)((y - mn[1]) * sc), iz = (uint32_t)((z - mn[2]) * sc);
-            key = spread4(min(ix, 15u)) | (spread4(min(iy, 15u)) << 1) | (spread4(min(iz, 15u)) << 2);
-        }
-        int ord = v ? perm : 0x7fffffff;
-#pragma unroll
-        for (int k = 2; k <= 64; k <<= 1) {
-#pragma unroll
-            for (int j = k >> 1; j > 0; j >>= 1) {
-                const uint32_t okey = (uint32_t)__shfl_xor((int)key, j, 64);
-                const int oord = __shfl_xor(ord, j, 64), operm = __shfl_xor(perm, j, 64);
-                const float ox = __shfl_xor(x, j, 64), oy = __shfl_xor(y, j, 64), oz = __shfl_xor(z, j, 64);
-                const bool lower = (lane & j) == 0, asc = (lane & k) == 0;
-                const bool mine_first = (key < okey) || (key == okey && ord < oord);     // (key, ord) pairs of real points are distinct
-                const bool keep = (lower == asc) ? mine_first : !mine_first;
-                if (!keep) { key = okey; ord = oord; perm = operm; x = ox; y = oy; z = oz; }
-            }
-        }
-        if (v) { qx[i] = x; qy[i] = y; qz[i] = z; qperm[i] = perm; }
-    }
-    if (lane == 0) {
-        int p = 1;
-        if (mn[0] <= mx[0]) {
-            // cells a wave's box would span (1 m cells, +1 halo each side, bound radius)
-            const float vol = (mx[0] - mn[0] + 3.0f) * (mx[1] - mn[1] + 3.0f) * (mx[2] - mn[2] + 3.0f);
-            p = vol > 700.0f ? 4 : (vol > 180.0f ? 2 : 1);
-        }
-        // a small scan leaves most of the GPU idle: cut every chunk finer (base_parts) and large ones finer still
-        parts[c] = min(8, max(p, base_parts) * ((p > 1 && base_parts > 1) ? 2 : 1));
-    }
-    // the last ordering kernel of a single scan: its last chunk's wave stamps the end of the preparation (s2m_last_timing)
-    if (ps.stamps && c == n_chunks - 1 && lane == 0) ps.stamps[1] = wall_clock64();
 }
 
 // one workgroup: exclusive scan of parts[] and emission of the wave table {first point, count}.
@@ -1020,69 +347,6 @@ __device__ __forceinline__ void wave_lds_sync()
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-// wave64 reductions / scan on the DPP cross-lane path (VALU rate, no LDS round trips):
-// row_shr 1,2,4,8 inside the 16-lane rows, row_bcast:15 into rows 1 and 3, row_bcast:31 into
-// rows 2 and 3; lane 63 then holds the result.  All 64 lanes must be active.
-template <int CTRL, int ROW_MASK>
-__device__ __forceinline__ int dpp_i32(int old, int src)
-{
-    return __builtin_amdgcn_update_dpp(old, src, CTRL, ROW_MASK, 0xf, false);
-}
-template <int CTRL, int ROW_MASK>
-__device__ __forceinline__ float dpp_f32(float old, float src)
-{
-    return __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(old), __float_as_int(src), CTRL, ROW_MASK, 0xf, false));
-}
-__device__ __forceinline__ float wave_min_f32(float v)      // NaN-free inputs
-{
-    const float ID = INFINITY;
-    v = fminf(v, dpp_f32<0x111, 0xf>(ID, v)); v = fminf(v, dpp_f32<0x112, 0xf>(ID, v));
-    v = fminf(v, dpp_f32<0x114, 0xf>(ID, v)); v = fminf(v, dpp_f32<0x118, 0xf>(ID, v));
-    v = fminf(v, dpp_f32<0x142, 0xa>(ID, v)); v = fminf(v, dpp_f32<0x143, 0xc>(ID, v));
-    return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 63));
-}
-__device__ __forceinline__ float wave_max_f32(float v)
-{
-    const float ID = -INFINITY;
-    v = fmaxf(v, dpp_f32<0x111, 0xf>(ID, v)); v = fmaxf(v, dpp_f32<0x112, 0xf>(ID, v));
-    v = fmaxf(v, dpp_f32<0x114, 0xf>(ID, v)); v = fmaxf(v, dpp_f32<0x118, 0xf>(ID, v));
-    v = fmaxf(v, dpp_f32<0x142, 0xa>(ID, v)); v = fmaxf(v, dpp_f32<0x143, 0xc>(ID, v));
-    return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 63));
-}
-__device__ __forceinline__ int wave_max_i32(int v)
-{
-    constexpr int ID = (int)0x80000000;
-    v = max(v, dpp_i32<0x111, 0xf>(ID, v)); v = max(v, dpp_i32<0x112, 0xf>(ID, v));
-    v = max(v, dpp_i32<0x114, 0xf>(ID, v)); v = max(v, dpp_i32<0x118, 0xf>(ID, v));
-    v = max(v, dpp_i32<0x142, 0xa>(ID, v)); v = max(v, dpp_i32<0x143, 0xc>(ID, v));
-    return __builtin_amdgcn_readlane(v, 63);
-}
-__device__ __forceinline__ uint32_t wave_min_u32(uint32_t u)
-{
-    constexpr int ID = -1;                                   // 0xffffffff
-    int v = (int)u;
-    auto mn = [](int a, int b) { return (int)min((uint32_t)a, (uint32_t)b); };
-    v = mn(v, dpp_i32<0x111, 0xf>(ID, v)); v = mn(v, dpp_i32<0x112, 0xf>(ID, v));
-    v = mn(v, dpp_i32<0x114, 0xf>(ID, v)); v = mn(v, dpp_i32<0x118, 0xf>(ID, v));
-    v = mn(v, dpp_i32<0x142, 0xa>(ID, v)); v = mn(v, dpp_i32<0x143, 0xc>(ID, v));
-    return (uint32_t)__builtin_amdgcn_readlane(v, 63);
-}
-__device__ __forceinline__ uint32_t wave_or_u32(uint32_t u)
-{
-    int v = (int)u;
-    v |= dpp_i32<0x111, 0xf>(0, v); v |= dpp_i32<0x112, 0xf>(0, v);
-    v |= dpp_i32<0x114, 0xf>(0, v); v |= dpp_i32<0x118, 0xf>(0, v);
-    v |= dpp_i32<0x142, 0xa>(0, v); v |= dpp_i32<0x143, 0xc>(0, v);
-    return (uint32_t)__builtin_amdgcn_readlane(v, 63);
-}
-__device__ __forceinline__ int wave_incl_scan_i32(int v)
-{
-    v += dpp_i32<0x111, 0xf>(0, v); v += dpp_i32<0x112, 0xf>(0, v);
-    v += dpp_i32<0x114, 0xf>(0, v); v += dpp_i32<0x118, 0xf>(0, v);
-    v += dpp_i32<0x142, 0xa>(0, v); v += dpp_i32<0x143, 0xc>(0, v);
-    return v;
 }
 
 // (dy,dz) of the 9 rows of a 3x3x3 neighbourhood, centre row first so that the 5th-best bound
@@ -1522,23 +786,6 @@ __device__ __forceinline__ bool lm_close_iteration(CtxP cp, gptr<DevState> st, c
     return s_out[6] != 0.0f;
 }
 
-// transPointAssociateToMap (:1069-1072) and the LM trig (:1170-1175) from a pose: lanes 0..2 of the calling wave take one
-// angle each (glibc's sinf / cosf arithmetic, see glibc_sincosf: what the host's libm would return); result in every lane.
-__device__ __forceinline__ void build_transform(const float (&pose)[6], int lane, float (&T)[12], float (&sc6)[6])
-{
-    const float ang = (lane == 0) ? pose[2] : ((lane == 1) ? pose[1] : pose[0]);   // lane 0: yaw, 1: pitch, 2+: roll
-    float snf, csf;
-    glibc_sincosf_both(ang, snf, csf);
-    const float B = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(snf), 0)), A = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(csf), 0));
-    const float D = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(snf), 1)), C = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(csf), 1));
-    const float F = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(snf), 2)), E = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(csf), 2));
-    const float DE = D * E, DF = D * F;
-    T[0] = A * C; T[1] = A * DF - B * E; T[2]  = B * F + A * DE; T[3]  = pose[3];
-    T[4] = B * C; T[5] = A * E + B * DF; T[6]  = B * DE - A * F; T[7]  = pose[4];
-    T[8] = -D;    T[9] = C * F;          T[10] = C * E;          T[11] = pose[5];
-    sc6[0] = B; sc6[1] = A; sc6[2] = D; sc6[3] = C; sc6[4] = F; sc6[5] = E;
-}
-
 // ------------------------------------------------------------------------------------------
 // Density-aware re-split of the wave table, once per scan before launch 0.  k_chunk_parts can only
 // look at the extent of a chunk in the lidar frame; how many map points fall into a wave's box is
@@ -1774,21 +1021,6 @@ __global__ __launch_bounds__(kFinThreads) void k_finalize(const SlotTable tbl, i
     }
 }
 
-// Observation hook: the device's sinf / cosf of n arguments (tests compare them with the host's libm).
-__global__ __launch_bounds__(256) void k_debug_sincos(const float* __restrict__ x, int n, float* __restrict__ s, float* __restrict__ c,
-                                                      float* __restrict__ a)
-{
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) { s[i] = glibc_sincosf(x[i], 0); c[i] = glibc_sincosf(x[i], 1); if (a) a[i] = glibc_atanf(x[i]); }
-}
-
-// Observation hook: the hypotf of eigen6_sym's Jacobi rotations on n argument pairs (tests compare with the host's libm).
-__global__ __launch_bounds__(256) void k_debug_hypot(const float* __restrict__ x, const float* __restrict__ y, int n, float* __restrict__ r)
-{
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) r[i] = glibc_hypotf(x[i], y[i]);
-}
-
 // Parameter blocks travel as kernel arguments (copied at launch), so the host never has to
 // keep a staging buffer alive or synchronise to update them.
 __global__ void k_set_ctx(DevCtx* dst, DevCtx v) { if (threadIdx.x == 0 && blockIdx.x == 0) *dst = v; }
@@ -1823,200 +1055,6 @@ __global__ __launch_bounds__(256) void k_init_states(const StateInitTable t)
 __global__ void k_set_state(DevState* dst, DevState v, const int32_t* n_waves, unsigned long long* stamp)
 {
     if (threadIdx.x == 0 && blockIdx.x == 0) { v.n_waves = n_waves ? *n_waves : 0; *dst = v; if (stamp) *stamp = wall_clock64(); }
-}
-
-// ------------------------------------------------------------------------------------------
-// ScanContext descriptor (include/Scancontext.cpp:151-211): max-z polar histogram, 20 rings x
-// 60 sectors, LDS bins per workgroup merged with global atomicMax on an order-preserving
-// integer image of fp32 z; ring key = row mean.
-// ------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void k_sc_polar_max(const unsigned char* __restrict__ pts, size_t stride, int n,
-                                                      uint32_t* __restrict__ bins /*[1200], 0 = empty*/)
-{
-    __shared__ uint32_t lb[S2M_SC_NUM_RING * S2M_SC_NUM_SECTOR];
-    for (int k = threadIdx.x; k < S2M_SC_NUM_RING * S2M_SC_NUM_SECTOR; k += blockDim.x) lb[k] = 0u;
-    __syncthreads();
-    const double kdeg = 180.0 / M_PI;
-    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
-        const float* p = reinterpret_cast<const float*>(pts + (size_t)i * stride);
-        const float x = p[0], y = p[1];
-        const float z = (float)((double)p[2] + 2.0);                       // LIDAR_HEIGHT (:168)
-        const float rng = sqrtf(x * x + y * y);                            // :171
-        float th;                                                          // xy2theta (:23-36)
-        if ((x >= 0) & (y >= 0))      th = (float)(kdeg * (double)glibc_atanf(y / x));
-        else if ((x < 0) & (y >= 0))  th = (float)(180.0 - (kdeg * (double)glibc_atanf(y / (-x))));
-        else if ((x < 0) & (y < 0))   th = (float)(180.0 + (kdeg * (double)glibc_atanf(y / x)));
-        else if ((x >= 0) & (y < 0))  th = (float)(360.0 - (kdeg * (double)glibc_atanf((-y) / x)));
-        else th = NAN;
-        if ((double)rng > 80.0) continue;                                  // PC_MAX_RADIUS (:175)
-        if (!(z == z)) continue;                                           // NaN z never wins desc < z
-        const double rv = ceil(((double)rng / 80.0) * 20.0);               // :178
-        const double sv = ceil(((double)th / 360.0) * 60.0);               // :179
-        int ring = (rv != rv) ? 1 : (int)fmin(fmax(rv, 1.0), 20.0);
-        int sect = (sv != sv) ? 1 : (int)fmin(fmax(sv, 1.0), 60.0);
-        atomicMax(&lb[(ring - 1) * S2M_SC_NUM_SECTOR + (sect - 1)], f2ord(z));
-    }
-    __syncthreads();
-    for (int k = threadIdx.x; k < S2M_SC_NUM_RING * S2M_SC_NUM_SECTOR; k += blockDim.x)
-        if (lb[k]) atomicMax(&bins[k], lb[k]);
-}
-
-__global__ __launch_bounds__(64) void k_sc_finish(const uint32_t* __restrict__ bins, double* __restrict__ desc,
-                                                  double* __restrict__ ringkey)
-{
-    // one wave; lane r < 20 owns ring r
-    const int r = threadIdx.x;
-    if (r >= S2M_SC_NUM_RING) return;
-    double s = 0.0;
-    for (int k = 0; k < S2M_SC_NUM_SECTOR; k++) {
-        const uint32_t u = bins[r * S2M_SC_NUM_SECTOR + k];
-        double v = 0.0;                                                    // NO_POINT -> 0 (:187-190)
-        if (u) {
-            const uint32_t b = (u & 0x80000000u) ? (u & 0x7fffffffu) : ~u;
-            const float z = __uint_as_float(b);
-            // desc starts at -1000 and takes z only if -1000 < z (:182); -1000 -> 0 afterwards
-            v = ((double)z > -1000.0) ? (double)z : 0.0;
-        }
-        desc[r * S2M_SC_NUM_SECTOR + k] = v;
-        s += v;
-    }
-    ringkey[r] = s / 60.0;                                                 // row mean (:198-211)
-}
-
-// ------------------------------------------------------------------------------------------
-// ScanContext matching (reference include/Scancontext.cpp:69-148,
-// 214-344).  The SCManager's containers live on the device as three arrays indexed by key-frame
-// number: descriptors [n][20*60] fp64 (ring-major), ring keys [n][20] fp32 (eig2stdvec, :62-66),
-// sector keys [n][60] fp64.  Sizes are tiny (a descriptor is 9.6 KB), so one workgroup does a whole
-// detectLoopClosureID(); the batched kernel runs one workgroup per candidate.  All sums run left to
-// right in fp64 like the oracle's restatement, so distances are bit-identical to it.
-// ------------------------------------------------------------------------------------------
-}  // namespace s2m
-#include "s2m_sc_dist.hpp"          // kScThreads, kScShifts, ScShared, sc_distance_block: shared with the place query (s2m_sc_query.hip)
-namespace s2m {
-
-struct ScDetectOut {                   // mirrors s2m_sc_match + loop id / yaw
-    double  min_dist;
-    int32_t loop_id, nn_idx, nn_align;
-    float   yaw_diff_rad;
-    int32_t cand_idx[3];
-    float   cand_d2[3];
-};
-
-// makeAndSaveScancontextAndKeys (:236-250): descriptor + ring key (as k_sc_finish left them) into slot `idx`
-__global__ __launch_bounds__(kScThreads) void k_sc_append(const double* __restrict__ desc_ring, double* __restrict__ store_desc,
-                                                          float* __restrict__ store_ring, double* __restrict__ store_sector, int idx)
-{
-    constexpr int NR = S2M_SC_NUM_RING, NS = S2M_SC_NUM_SECTOR;
-    double* d = store_desc + (size_t)idx * NR * NS;
-    for (int k = threadIdx.x; k < NR * NS; k += kScThreads) d[k] = desc_ring[k];
-    if (threadIdx.x < NR) store_ring[(size_t)idx * NR + threadIdx.x] = (float)desc_ring[NR * NS + threadIdx.x];
-    if (threadIdx.x < NS) {                                                // makeSectorkeyFromScancontext (:214-227)
-        double a = 0.0;
-        for (int r = 0; r < NR; r++) a += desc_ring[r * NS + threadIdx.x];
-        store_sector[(size_t)idx * NS + threadIdx.x] = a / (double)NR;
-    }
-}
-
-// distanceBtnScanContext of descriptor `query` against cand[0..m): one workgroup per candidate
-__global__ __launch_bounds__(kScThreads) void k_sc_distance_batch(const double* __restrict__ store_desc, const double* __restrict__ store_sector,
-                                                                  int query, const int32_t* __restrict__ cand, double* __restrict__ dist,
-                                                                  int32_t* __restrict__ shift)
-{
-    __shared__ ScShared sh[1];
-    __shared__ int s_cand[1];
-    if (threadIdx.x == 0) s_cand[0] = cand[blockIdx.x];
-    __syncthreads();
-    sc_distance_block<1>(store_desc, store_sector, store_desc + (size_t)query * (S2M_SC_NUM_RING * S2M_SC_NUM_SECTOR),
-                         store_sector + (size_t)query * S2M_SC_NUM_SECTOR, s_cand, sh);
-    if (threadIdx.x == 0) { dist[blockIdx.x] = sh[0].dist_out; shift[blockIdx.x] = sh[0].shift_out; }
-}
-
-// detectLoopClosureID (:253-344) for the newest descriptor (index n_total - 1) against the ring keys
-// [0, n_search) (the contents of the reference's kd-tree at its last rebuild).  One workgroup: every thread keeps the three
-// nearest of its share of the keys, the lists are merged by a butterfly inside each wave and by one thread over the four waves
-// (order: distance, then index - the lower index wins a tie, whoever held it), then the three candidates are compared side by
-// side.  `out` may be pinned host memory (the result is 48 bytes: written where the host reads it, no copy behind the kernel).
-__device__ __forceinline__ bool sc_near_less(float da, int ia, float db, int ib) { return da < db || (da == db && ia < ib); }
-__device__ __forceinline__ void sc_near_insert(float (&bd)[3], int (&bi)[3], float d, int i)
-{
-    if (sc_near_less(d, i, bd[2], bi[2])) {
-        bd[2] = d; bi[2] = i;
-        if (sc_near_less(bd[2], bi[2], bd[1], bi[1])) { const float a = bd[1]; bd[1] = bd[2]; bd[2] = a; const int b2 = bi[1]; bi[1] = bi[2]; bi[2] = b2; }
-        if (sc_near_less(bd[1], bi[1], bd[0], bi[0])) { const float a = bd[0]; bd[0] = bd[1]; bd[1] = a; const int b2 = bi[0]; bi[0] = bi[1]; bi[1] = b2; }
-    }
-}
-
-__global__ __launch_bounds__(kScThreads) void k_sc_detect(const double* __restrict__ store_desc, const float* __restrict__ store_ring,
-                                                          const double* __restrict__ store_sector, int n_total, int n_search,
-                                                          ScDetectOut* __restrict__ out)
-{
-    constexpr int NR = S2M_SC_NUM_RING;
-    static_assert(NR % 4 == 0, "ring keys are read four floats at a time");
-    __shared__ ScShared sh[3];
-    __shared__ float s_d2[kScThreads / 64][3];
-    __shared__ int   s_ix[kScThreads / 64][3];
-    __shared__ int   s_cand[3];
-    const int t = threadIdx.x, q = n_total - 1;
-    // exact 3-NN over the fp32 ring keys, accumulation order of nanoflann's L2_Adaptor (groups of four);
-    // ties go to the lower index
-    float bd[3] = { INFINITY, INFINITY, INFINITY };
-    int bi[3] = { 0x7fffffff, 0x7fffffff, 0x7fffffff };
-    float4 qk[NR / 4];
-#pragma unroll
-    for (int g = 0; g < NR / 4; g++) qk[g] = reinterpret_cast<const float4*>(store_ring + (size_t)q * NR)[g];
-    for (int i = t; i < n_search; i += kScThreads) {
-        const float4* b = reinterpret_cast<const float4*>(store_ring + (size_t)i * NR);      // (rows are 80 bytes: 16-byte aligned)
-        float4 bk[NR / 4];
-#pragma unroll
-        for (int g = 0; g < NR / 4; g++) bk[g] = b[g];
-        float result = 0.0f;
-#pragma unroll
-        for (int g = 0; g < NR / 4; g++) {
-            const float d0 = qk[g].x - bk[g].x, d1 = qk[g].y - bk[g].y, d2 = qk[g].z - bk[g].z, d3 = qk[g].w - bk[g].w;
-            result += d0 * d0 + d1 * d1 + d2 * d2 + d3 * d3;
-        }
-        if (result < bd[2]) {                             // i ascends per thread: an equal distance stays behind
-            bd[2] = result; bi[2] = i;
-            if (bd[2] < bd[1]) { const float a = bd[1]; bd[1] = bd[2]; bd[2] = a; const int b2 = bi[1]; bi[1] = bi[2]; bi[2] = b2; }
-            if (bd[1] < bd[0]) { const float a = bd[0]; bd[0] = bd[1]; bd[1] = a; const int b2 = bi[0]; bi[0] = bi[1]; bi[1] = b2; }
-        }
-    }
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {              // both partners end with the same three
-        float pd[3]; int pi[3];
-#pragma unroll
-        for (int k = 0; k < 3; k++) { pd[k] = __shfl_xor(bd[k], off, 64); pi[k] = __shfl_xor(bi[k], off, 64); }
-#pragma unroll
-        for (int k = 0; k < 3; k++) sc_near_insert(bd, bi, pd[k], pi[k]);
-    }
-    if ((t & 63) == 0)
-        for (int k = 0; k < 3; k++) { s_d2[t >> 6][k] = bd[k]; s_ix[t >> 6][k] = bi[k]; }
-    __syncthreads();
-    if (t == 0) {
-        float fd[3] = { INFINITY, INFINITY, INFINITY };
-        int fi[3] = { 0x7fffffff, 0x7fffffff, 0x7fffffff };
-        for (int u = 0; u < kScThreads / 64; u++)
-            for (int k = 0; k < 3; k++) sc_near_insert(fd, fi, s_d2[u][k], s_ix[u][k]);
-        for (int k = 0; k < 3; k++) {
-            const bool have = fi[k] != 0x7fffffff;        // fewer keys than candidates: index 0 (:289 zero-initialised)
-            s_cand[k] = have ? fi[k] : 0;
-            out->cand_idx[k] = s_cand[k];
-            out->cand_d2[k] = have ? fd[k] : 0.0f;
-        }
-    }
-    __syncthreads();
-    sc_distance_block<3>(store_desc, store_sector, store_desc + (size_t)q * (NR * S2M_SC_NUM_SECTOR), store_sector + (size_t)q * S2M_SC_NUM_SECTOR,
-                         s_cand, sh);
-    if (t == 0) {
-        double min_dist = 10000000;
-        int nn_align = 0, nn_idx = 0;
-        for (int c = 0; c < 3; c++)                        // :302-316
-            if (sh[c].dist_out < min_dist) { min_dist = sh[c].dist_out; nn_align = sh[c].shift_out; nn_idx = s_cand[c]; }
-        out->min_dist = min_dist; out->nn_idx = nn_idx; out->nn_align = nn_align;
-        out->loop_id = (min_dist < 0.3) ? nn_idx : -1;    // SC_DIST_THRES (Scancontext.h:95)
-        out->yaw_diff_rad = (float)((double)(float)((double)nn_align * (360.0 / 60.0)) * M_PI / 180.0);   // deg2rad(float) (:17-20, :338)
-    }
 }
 
 }  // namespace s2m

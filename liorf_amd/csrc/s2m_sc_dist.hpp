@@ -1,5 +1,5 @@
 // s2m_sc_dist.hpp — distanceBtnScanContext (reference include/Scancontext.cpp:116-148) by one workgroup, shared by the detector
-// and batched distance (s2m_kernels.hpp) and by the place query (s2m_sc_query.hip).  Compiled with -ffp-contract=off; all sums
+// and batched distance (s2m_sc.hip) and by the place query (s2m_sc_query.hip).  Compiled with -ffp-contract=off; all sums
 // run left to right in fp64 like the oracle's restatement, so distances are bit-identical to it.
 #pragma once
 #include <hip/hip_runtime.h>

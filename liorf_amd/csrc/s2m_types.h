@@ -138,6 +138,7 @@ struct PrepSlot {
     int32_t* chunk_parts; int2* wave_table; int32_t* n_waves;
     unsigned long long* stamps;   // pinned, may be null (batches): [0] wall clock when k_polar_count starts, [1] when the last workgroup of k_chunk_parts ends (k_chunk_table, where one follows, stamps again)
 };
+constexpr int kPolarCells = 16384;     // cells of the scan's log-polar ordering grid (s2m_prep.hpp: 128 azimuth x 128 log-range bins)
 constexpr int kPrepSlots = 16;
 struct PrepTable { PrepSlot s[kPrepSlots]; };
 

@@ -386,7 +386,7 @@ def kernel_source_sha() -> str:
     import hashlib
     h = hashlib.sha256()
     d = os.path.join(_HERE, "csrc")
-    for f in ("s2m_kernels.hpp", "s2m_register.hpp", "s2m_types.h"):
+    for f in ("s2m_device.hpp", "s2m_prep.hpp", "s2m_kernels.hpp", "s2m_register.hpp", "s2m_types.h"):
         h.update(f.encode())
         h.update(open(os.path.join(d, f), "rb").read())
     return h.hexdigest()[:16]

@@ -205,7 +205,7 @@ def grid_of(map_xyz, gate_sq):
 
 
 def cell_of(p, g):
-    """cell_coord (s2m_kernels.hpp) in fp32."""
+    """cell_coord (s2m_device.hpp) in fp32."""
     p = np.asarray(p, F)
     f = np.floor(((p - g["origin"]).astype(F) * g["inv_e"]).astype(F))
     return np.clip(f, 0, g["dims"] - 1).astype(np.int64)

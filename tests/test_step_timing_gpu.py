@@ -1,4 +1,4 @@
-"""s2m_last_timing of a single scan (liorf_amd/csrc/s2m_abi.hip): set_scan_ms and optimize_ms are differences of wall-clock
+"""s2m_last_timing of a single scan (liorf_amd/csrc/s2m_abi.hip; the scan preparation it times is s2m_prep.hip's): set_scan_ms and optimize_ms are differences of wall-clock
 stamps that the kernels bracketing the two intervals store in pinned memory - no event record costs GPU time in a step.
 The intervals are device time inside the step, so each is positive and below the host's wall time of the step; the second
 range of an early-exit loop, timed by an event pair of its own, is still part of optimize_ms."""

@@ -1,4 +1,4 @@
-"""The device's sinf / cosf (glibc_sincosf of s2m_kernels.hpp, through the k_debug_sincos hook) on every branch of the restated
+"""The device's sinf / cosf (glibc_sincosf of s2m_device.hpp, through s2m_abi_debug.hip's k_debug_sincos hook) on every branch of the restated
 arithmetic, against the test host's libm the way tests/test_parity_gpu.py::test_device_trig_is_the_hosts compares them, bit for
 bit: the neighbours (three ulps each side, both signs) of the branch boundaries 2^-12, 0x1.921FB6p-1 (pi/4) and 120, k*pi/2
 with its neighbours (two ulps each side) for k = -76..76 - every quadrant and both coefficient sets - and 1e5 pose-like

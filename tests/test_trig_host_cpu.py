@@ -1,4 +1,4 @@
-"""glibc_sincosf_both (liorf_amd/csrc/s2m_glibc_trig.hpp, the twin of s2m_kernels.hpp's) against the build host's sinf / cosf,
+"""glibc_sincosf_both (liorf_amd/csrc/s2m_glibc_trig.hpp, the twin of s2m_device.hpp's) against the build host's sinf / cosf,
 bit for bit, on the CPU: tools/micro/trig_host_check.hip is compiled for the host and run.  Its arguments: 2e6 random values
 in [-4, 4], the neighbours (three ulps each side, both signs) of the branch boundaries 2^-12, 0x1.921FB6p-1 and 120, and
 k*pi/2 with its neighbours (two ulps each side) for k = -76..76.
