@@ -762,6 +762,44 @@ int  s2m_loop_closure_rs_launch(s2m_handle h, double time_cur, const s2m_loop_pa
 int  s2m_loop_poll(s2m_handle h, s2m_loop_result* out);      /* never waits for the device */
 int  s2m_loop_collect(s2m_handle h, s2m_loop_result* out);   /* waits; poll until not pending */
 
+/* ---- Verification: one key against several candidates, aligned in lockstep ---------------------------------------
+ * s2m_sc_query_* answers "which stored keys look like this one?" with a ranked list; descriptor distances rank places, they
+ * do not verify them. A verification aligns key_cur against n_cand <= S2M_LOOP_MAX_CANDIDATES stored keys at once: the n_cand
+ * alignments are independent and advance through the same kernel launches (the candidate is a grid dimension of every kernel
+ * of the device loop), so the whole costs about what its slowest alignment costs alone.
+ *   Records: record i is byte for byte what s2m_loop_align(h, key_cur, key_pre[i], base_key, p) returns on a handle whose
+ *       container does not hold key_cur - status, keys, sizes, icp, pose_from, pose_to - in the caller's order. The source
+ *       submap (key_cur, 0, base_key) is built once, the target submap (key_pre[i], search_num, base_key) of every candidate
+ *       into a buffer of its own. The container test comes first: a key_cur it holds gives S2M_LOOP_ALREADY_CLOSED in every
+ *       record. The size gates hold per candidate: n_prev < 1000 gives that candidate S2M_LOOP_TOO_FEW_POINTS at launch,
+ *       n_cur < 300 gives it to all of them.
+ *   s2m_loop_verify_launch returns without waiting for the alignments. If no candidate is left after the gates, `early`
+ *       holds the final records and nothing is pending; otherwise the candidates that are left carry S2M_LOOP_PENDING,
+ *       filled as s2m_loop_align_launch fills them, and their poses are kept as they are at launch. *best is -1.
+ *   s2m_loop_verify_poll never waits for the device; it moves the queued work on as s2m_loop_poll does (ranges until every
+ *       candidate's alignment has ended, then one fitness pass for all) and returns the records as they stand.
+ *       s2m_loop_verify_collect is the same with waits. s2m_loop_verify is launch plus collect; `out` takes n_cand records.
+ *   *best: the position of the accepted candidate with the least (icp.fitness_score, position), -1 if none is accepted
+ *       or while pending. Only key_cur -> key_pre[*best] goes into the container, when the result is collected; the other
+ *       records keep the status the single call would give, S2M_LOOP_ACCEPTED there meaning "passed the gate". So hits
+ *       that s2m_sc_query_* orders by descriptor distance are re-ranked by fitness.
+ *   A pending verification is a pending closure: every rule above about a pending closure holds for it. s2m_loop_poll and
+ *       s2m_loop_collect with a verification pending, and s2m_loop_verify_poll / _collect with a single closure pending,
+ *       return S2M_ERR_BUSY and touch nothing. With nothing pending the verify forms return S2M_OK, *n_out = 0, *best = -1.
+ *   Errors: n_cand outside [1, S2M_LOOP_MAX_CANDIDATES], a key outside the store, a candidate listed twice or equal to
+ *       key_cur give S2M_ERR_INVALID_ARG; s2m_loop_verify_check_args gives the same verdict from the store's size alone
+ *       (host code, no handle, no GPU). An empty store gives S2M_OK with S2M_LOOP_NONE records. *n_out holds the number
+ *       of records; cap below it gives S2M_ERR_CAPACITY after writing cap records. */
+#define S2M_LOOP_MAX_CANDIDATES  8
+int  s2m_loop_verify_check_args(int32_t n_stored, int32_t key_cur, const int32_t* key_pre, int32_t n_cand, int32_t base_key,
+                                const s2m_loop_params* p /* NULL = defaults */);
+int  s2m_loop_verify_launch(s2m_handle h, int32_t key_cur, const int32_t* key_pre, int32_t n_cand, int32_t base_key,
+                            const s2m_loop_params* p /* NULL = defaults */, s2m_loop_result* early /* n_cand records */, int32_t* best);
+int  s2m_loop_verify_poll(s2m_handle h, s2m_loop_result* out, int32_t cap, int32_t* n_out, int32_t* best);      /* never waits */
+int  s2m_loop_verify_collect(s2m_handle h, s2m_loop_result* out, int32_t cap, int32_t* n_out, int32_t* best);   /* waits */
+int  s2m_loop_verify(s2m_handle h, int32_t key_cur, const int32_t* key_pre, int32_t n_cand, int32_t base_key,
+                     const s2m_loop_params* p /* NULL = defaults */, s2m_loop_result* out /* n_cand records */, int32_t* best);
+
 /* ---- Pose graph: factors, optimise, correct the key-frame store --------------------------------------------------
  * saveKeyFramesAndFactor() with addOdomFactor / addGPSFactor / addLoopFactor (reference src/mapOptmization.cpp:1386-1534)
  * and correctPoses() (:1611-1642) as a batch solve on the device. The graph lives in the handle beside the key-frame

@@ -151,6 +151,11 @@ int  s2m_debug_icp_time_nearest(s2m_handle h, const void* src, size_t n_src, con
  * result is bit for bit that of s2m_icp_align. */
 int  s2m_debug_icp_align_device(s2m_handle h, const void* src, size_t n_src, const void* tgt, size_t n_tgt, size_t stride_bytes,
                                 const s2m_icp_params* p /* NULL = defaults */, s2m_icp_result* out);
+/* The same for one source against n_cand <= S2M_LOOP_MAX_CANDIDATES targets, aligned in lockstep by the slotted device loop
+ * (what s2m_loop_verify_launch queues): tgts[i] holds n_tgts[i] records of the source's stride, out takes n_cand results.
+ * out[i] is bit for bit s2m_icp_align(src, tgts[i]); the same target may be listed twice. */
+int  s2m_debug_icp_align_many_device(s2m_handle h, const void* src, size_t n_src, const void* const* tgts, const size_t* n_tgts, int32_t n_cand,
+                                     size_t stride_bytes, const s2m_icp_params* p /* NULL = defaults */, s2m_icp_result* out);
 /* Experiment switch of the device loop's search for the launches and debug calls that follow: the cell edge in units of
  * icp_leaf (0 = built in), the largest shell radius searched before a point goes to the brute force (0 = built in), and
  * use_grid (0 = brute force only, 1 = grid, < 0 = built in). */

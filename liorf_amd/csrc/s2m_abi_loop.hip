@@ -18,6 +18,7 @@ static void icp_result_out(const IcpResult& r, s2m_icp_result* out)
 }
 
 static_assert(S2M_ICP_RANGE == kIcpRange, "include/liorf_s2m_debug.h states the range length of the device loop");
+static_assert(S2M_LOOP_MAX_CANDIDATES == kIcpMaxSlots, "include/liorf_s2m.h states the slots of the device loop");
 
 int s2m::host::loop_busy(s2m_context* h)
 {
@@ -29,6 +30,7 @@ void s2m::host::loop_drop_pending(s2m_context* h, bool destroy)
     if (h->loop.stream) (void)hipStreamSynchronize(h->loop.stream);
     if (h->loop.icp) icp_dev_cancel(h->loop.icp);
     h->loop.pending = false;
+    h->loop.ver_n = 0;
     if (!destroy) return;
     if (h->loop.ev_submaps) (void)hipEventDestroy(h->loop.ev_submaps);
     if (h->loop.stream) (void)hipStreamDestroy(h->loop.stream);
@@ -171,10 +173,9 @@ int loop_gates(s2m_context* h, int32_t key_cur, int32_t key_pre, int32_t base_ke
     return S2M_OK;
 }
 
-// the fitness gate, the pose result and the container (:585-621, :707-715). T_cur, pose_pre: transCur of key_cur and the pose of
+// the fitness gate and the pose result (:585-620, :707-715). T_cur, pose_pre: transCur of key_cur and the pose of
 // key_pre - the store's for the synchronous call, the launch-time snapshot for a launched closure
-void loop_finish(s2m_context* h, const IcpResult& r, int32_t base_key, float fitness_score, const float T_cur[12], const float pose_pre[6],
-                 s2m_loop_result* out)
+void loop_judge(const IcpResult& r, int32_t base_key, float fitness_score, const float T_cur[12], const float pose_pre[6], s2m_loop_result* out)
 {
     icp_result_out(r, &out->icp);
     if (!r.converged || r.fitness > (double)fitness_score) { out->status = S2M_LOOP_REJECTED; return; }   // (:585)
@@ -187,7 +188,14 @@ void loop_finish(s2m_context* h, const IcpResult& r, int32_t base_key, float fit
         host_translation_and_euler(r.T, 4, out->pose_from);  // (:707); poseTo is the identity (:709)
     }
     out->status = S2M_LOOP_ACCEPTED;
-    h->loop.index[out->key_cur] = out->key_pre;             // loopIndexContainer[loopKeyCur] = loopKeyPre (:621)
+}
+
+// loop_judge and the container (:621)
+void loop_finish(s2m_context* h, const IcpResult& r, int32_t base_key, float fitness_score, const float T_cur[12], const float pose_pre[6],
+                 s2m_loop_result* out)
+{
+    loop_judge(r, base_key, fitness_score, T_cur, pose_pre, out);
+    if (out->status == S2M_LOOP_ACCEPTED) h->loop.index[out->key_cur] = out->key_pre;   // loopIndexContainer[loopKeyCur] = loopKeyPre
 }
 
 // s2m_icp_align's path on the device submaps: historyKeyframeSearchRadius*2 (a float), 100, 1e-6, 1e-6 (:572-576)
@@ -238,6 +246,8 @@ int loop_poll_impl(s2m_context* h, s2m_loop_result* out, bool wait)
 {
     if (!h) return S2M_ERR_INVALID_ARG;
     if (!out) return fail(h, S2M_ERR_INVALID_ARG, "null loop result");
+    if (h->loop.pending && h->loop.ver_n > 0)
+        return fail(h, S2M_ERR_BUSY, "a launched verification is pending: s2m_loop_verify_poll / s2m_loop_verify_collect it");
     loop_result_init(out);
     if (!h->loop.pending) return S2M_OK;                    // S2M_LOOP_NONE, keys -1
     S2M_HIP(h, hipSetDevice(h->device));
@@ -358,6 +368,180 @@ int s2m_loop_poll(s2m_handle h, s2m_loop_result* out) { return loop_poll_impl(h,
 
 int s2m_loop_collect(s2m_handle h, s2m_loop_result* out) { return loop_poll_impl(h, out, true); }
 
+// ---- verification: one key against several candidates, aligned in lockstep ------------------------------------------------
+
+namespace {
+
+// the checks of the candidate list that need no handle. *empty: the store is empty (S2M_OK, S2M_LOOP_NONE records)
+int verify_args(s2m_context* h, size_t N, int32_t key_cur, const int32_t* key_pre, int32_t n_cand, int32_t base_key, const s2m_loop_params* p,
+                s2m_loop_params* prm, bool* empty)
+{
+    *empty = false;
+    if (!key_pre || n_cand < 1 || n_cand > S2M_LOOP_MAX_CANDIDATES)
+        return fail(h, S2M_ERR_INVALID_ARG, "a verification takes 1 .. S2M_LOOP_MAX_CANDIDATES candidates");
+    const int rc = loop_params(h, p, prm);
+    if (rc) return rc;
+    if (N == 0) { *empty = true; return S2M_OK; }
+    if (!loop_key_ok(key_cur, N) || (base_key != -1 && !loop_key_ok(base_key, N)))
+        return fail(h, S2M_ERR_INVALID_ARG, "loop keys outside the key-frame store");
+    for (int32_t i = 0; i < n_cand; i++) {
+        if (!loop_key_ok(key_pre[i], N)) return fail(h, S2M_ERR_INVALID_ARG, "loop keys outside the key-frame store");
+        if (key_pre[i] == key_cur) return fail(h, S2M_ERR_INVALID_ARG, "a candidate is key_cur itself");
+        for (int32_t j = 0; j < i; j++)
+            if (key_pre[j] == key_pre[i]) return fail(h, S2M_ERR_INVALID_ARG, "a candidate is listed twice");
+    }
+    return S2M_OK;
+}
+
+// the accepted record with the least (icp.fitness_score, position), or -1
+int32_t verify_best(const s2m_loop_result* rec, int32_t n)
+{
+    int32_t best = -1;
+    for (int32_t i = 0; i < n; i++)
+        if (rec[i].status == S2M_LOOP_ACCEPTED && (best < 0 || rec[i].icp.fitness_score < rec[best].icp.fitness_score)) best = i;
+    return best;
+}
+
+// the container test, the source submap once, a target submap per candidate with the size gates of the single closure, then
+// the alignments of the candidates that are left queued in lockstep on the loop stream. rec: n_cand records.
+int verify_launch_impl(s2m_context* h, int32_t key_cur, const int32_t* key_pre, int32_t n_cand, int32_t base_key, const s2m_loop_params& prm,
+                       s2m_loop_result* rec)
+{
+    s2m_context::LoopClosure& L = h->loop;
+    for (int32_t i = 0; i < n_cand; i++) { rec[i].key_cur = key_cur; rec[i].key_pre = key_pre[i]; }
+    if (L.index.count(key_cur)) {
+        for (int32_t i = 0; i < n_cand; i++) rec[i].status = S2M_LOOP_ALREADY_CLOSED;
+        return S2M_OK;
+    }
+    VoxResult rc_cur;
+    int rc = loop_submap(h, key_cur, 0, base_key, prm.icp_leaf, L.cur, &rc_cur);
+    if (rc) return rc;
+    const unsigned char* d_tgt[S2M_LOOP_MAX_CANDIDATES];
+    size_t n_tgt[S2M_LOOP_MAX_CANDIDATES];
+    int32_t slot_of[S2M_LOOP_MAX_CANDIDATES];
+    int32_t slots = 0;
+    for (int32_t i = 0; i < n_cand; i++) {
+        VoxResult rc_prev;
+        if ((rc = loop_submap(h, key_pre[i], prm.search_num, base_key, prm.icp_leaf, L.ver_prev[i], &rc_prev))) return rc;
+        rec[i].n_cur = (int32_t)rc_cur.n_out;
+        rec[i].n_prev = (int32_t)rc_prev.n_out;
+        slot_of[i] = -1;
+        if (rc_cur.n_out < 300 || rc_prev.n_out < 1000) { rec[i].status = S2M_LOOP_TOO_FEW_POINTS; continue; }
+        d_tgt[slots] = L.ver_prev[i].as<unsigned char>();
+        n_tgt[slots] = rc_prev.n_out;
+        slot_of[i] = slots++;
+    }
+    if (slots == 0) return S2M_OK;
+    if ((rc = loop_stream(h))) return rc;
+    S2M_HIP(h, hipEventRecord(L.ev_submaps, h->stream));
+    S2M_HIP(h, hipStreamWaitEvent(L.stream, L.ev_submaps, 0));
+    const hipError_t e = icp_dev_begin_many(L.icp, L.stream, L.cur.as<unsigned char>(), rc_cur.n_out, d_tgt, n_tgt, slots, kDsStride,
+                                            loop_icp_params(prm), loop_tuning(h, prm.icp_leaf));
+    if (e != hipSuccess) {
+        (void)hipStreamSynchronize(L.stream);
+        return fail(h, S2M_ERR_HIP, "loop verification launch", e);
+    }
+    for (int32_t i = 0; i < n_cand; i++) {
+        if (slot_of[i] >= 0) rec[i].status = S2M_LOOP_PENDING;
+        L.ver_rec[i] = rec[i];
+        L.ver_slot[i] = slot_of[i];
+        memcpy(L.ver_pose_pre[i], &h->kf.pose[6 * (size_t)key_pre[i]], sizeof(L.ver_pose_pre[i]));
+    }
+    L.ver_n = n_cand; L.ver_slots = slots;
+    L.pend_fitness = prm.fitness_score;
+    L.pend_base_key = base_key;
+    memcpy(L.snap_T, h->kf.frame[(size_t)key_cur].T, sizeof(L.snap_T));
+    L.pending = true;
+    return S2M_OK;
+}
+
+int verify_launch_front(s2m_context* h, int32_t key_cur, const int32_t* key_pre, int32_t n_cand, int32_t base_key, const s2m_loop_params* p,
+                        s2m_loop_result* early, int32_t* best)
+{
+    if (!h) return S2M_ERR_INVALID_ARG;
+    if (!early || !best) return fail(h, S2M_ERR_INVALID_ARG, "null loop result");
+    int rc = loop_busy(h);
+    if (rc) return rc;
+    *best = -1;
+    s2m_loop_params prm;
+    bool empty;
+    if ((rc = verify_args(h, h->kf.time.size(), key_cur, key_pre, n_cand, base_key, p, &prm, &empty))) return rc;
+    for (int32_t i = 0; i < n_cand; i++) loop_result_init(&early[i]);
+    if (empty) return S2M_OK;
+    S2M_HIP(h, hipSetDevice(h->device));
+    return verify_launch_impl(h, key_cur, key_pre, n_cand, base_key, prm, early);
+}
+
+int verify_poll_impl(s2m_context* h, s2m_loop_result* out, int32_t cap, int32_t* n_out, int32_t* best, bool wait)
+{
+    if (!h) return S2M_ERR_INVALID_ARG;
+    if (!n_out || !best || cap < 0 || (cap > 0 && !out)) return fail(h, S2M_ERR_INVALID_ARG, "bad loop result buffer");
+    s2m_context::LoopClosure& L = h->loop;
+    if (L.pending && L.ver_n == 0)
+        return fail(h, S2M_ERR_BUSY, "a launched loop closure is pending: s2m_loop_poll / s2m_loop_collect it first");
+    *n_out = 0; *best = -1;
+    if (!L.pending) return S2M_OK;
+    S2M_HIP(h, hipSetDevice(h->device));
+    bool done = false;
+    IcpResult r[S2M_LOOP_MAX_CANDIDATES];
+    const hipError_t e = icp_dev_advance_many(L.icp, L.stream, wait, &done, r);
+    if (e != hipSuccess) {
+        loop_drop_pending(h, false);
+        return fail(h, S2M_ERR_HIP, "loop verification on the loop stream", e);
+    }
+    const int32_t n = L.ver_n;
+    if (done) {
+        for (int32_t i = 0; i < n; i++) {
+            if (L.ver_slot[i] < 0) continue;
+            L.ver_rec[i].status = S2M_LOOP_NONE;
+            loop_judge(r[L.ver_slot[i]], L.pend_base_key, L.pend_fitness, L.snap_T, L.ver_pose_pre[i], &L.ver_rec[i]);
+        }
+        *best = verify_best(L.ver_rec, n);
+        if (*best >= 0) L.index[L.ver_rec[*best].key_cur] = L.ver_rec[*best].key_pre;   // only the winner is a closure (:621)
+        L.pending = false;
+        L.ver_n = 0;
+    }
+    *n_out = n;
+    for (int32_t i = 0; i < std::min(n, cap); i++) out[i] = L.ver_rec[i];
+    if (cap < n) return fail(h, S2M_ERR_CAPACITY, "output buffer too small for the verification's records");
+    return S2M_OK;
+}
+
+}  // namespace
+
+int s2m_loop_verify_check_args(int32_t n_stored, int32_t key_cur, const int32_t* key_pre, int32_t n_cand, int32_t base_key, const s2m_loop_params* p)
+{
+    if (n_stored < 0) return S2M_ERR_INVALID_ARG;
+    s2m_loop_params prm;
+    bool empty;
+    return verify_args(nullptr, (size_t)n_stored, key_cur, key_pre, n_cand, base_key, p, &prm, &empty);
+}
+
+int s2m_loop_verify_launch(s2m_handle h, int32_t key_cur, const int32_t* key_pre, int32_t n_cand, int32_t base_key, const s2m_loop_params* p,
+                           s2m_loop_result* early, int32_t* best)
+{
+    return verify_launch_front(h, key_cur, key_pre, n_cand, base_key, p, early, best);
+}
+
+int s2m_loop_verify_poll(s2m_handle h, s2m_loop_result* out, int32_t cap, int32_t* n_out, int32_t* best)
+{
+    return verify_poll_impl(h, out, cap, n_out, best, false);
+}
+
+int s2m_loop_verify_collect(s2m_handle h, s2m_loop_result* out, int32_t cap, int32_t* n_out, int32_t* best)
+{
+    return verify_poll_impl(h, out, cap, n_out, best, true);
+}
+
+int s2m_loop_verify(s2m_handle h, int32_t key_cur, const int32_t* key_pre, int32_t n_cand, int32_t base_key, const s2m_loop_params* p,
+                    s2m_loop_result* out, int32_t* best)
+{
+    const int rc = verify_launch_front(h, key_cur, key_pre, n_cand, base_key, p, out, best);
+    if (rc || !h->loop.pending) return rc;
+    int32_t n = 0;
+    return verify_poll_impl(h, out, n_cand, &n, best, true);
+}
+
 // ---- diagnostics of the device loop (include/liorf_s2m_debug.h) ---------------------------------------------------------
 
 namespace {
@@ -456,5 +640,57 @@ int s2m_debug_icp_align_device(s2m_handle h, const void* src, size_t n_src, cons
     }
     S2M_HIP(h, hipStreamSynchronize(h->loop.stream));
     icp_result_out(r, out);
+    return S2M_OK;
+}
+
+int s2m_debug_icp_align_many_device(s2m_handle h, const void* src, size_t n_src, const void* const* tgts, const size_t* n_tgts, int32_t n_cand,
+                                    size_t stride_bytes, const s2m_icp_params* p, s2m_icp_result* out)
+{
+    if (!h) return S2M_ERR_INVALID_ARG;
+    if (!out || !tgts || !n_tgts || n_cand < 1 || n_cand > S2M_LOOP_MAX_CANDIDATES)
+        return fail(h, S2M_ERR_INVALID_ARG, "null ICP result or target list, or not 1 .. S2M_LOOP_MAX_CANDIDATES targets");
+    s2m_icp_params prm;
+    if (p) prm = *p; else s2m_icp_default_params(&prm);
+    if (!(prm.max_correspondence_distance > 0.0) || prm.max_iterations < 1)
+        return fail(h, S2M_ERR_INVALID_ARG, "ICP needs a positive correspondence distance and at least one iteration");
+    int rc = debug_stage(h, src, n_src, nullptr, 0, stride_bytes);
+    if (rc) return rc;
+    s2m_context::LoopClosure& L = h->loop;
+    const unsigned char* d_tgt[S2M_LOOP_MAX_CANDIDATES];
+    size_t n_tgt[S2M_LOOP_MAX_CANDIDATES];
+    int slot_of[S2M_LOOP_MAX_CANDIDATES];
+    int slots = 0;
+    for (int32_t i = 0; i < n_cand; i++) {                  // a slot per non-empty target, staged in the verification's submap buffers
+        if ((rc = check_records(h, tgts[i], n_tgts[i], stride_bytes))) return rc;
+        slot_of[i] = -1;
+        if (!n_src || !n_tgts[i]) continue;
+        if ((rc = ensure(h, L.ver_prev[i], n_tgts[i] * stride_bytes))) return rc;
+        S2M_HIP(h, hipMemcpyAsync(L.ver_prev[i].p, tgts[i], n_tgts[i] * stride_bytes, hipMemcpyHostToDevice, L.stream));
+        d_tgt[slots] = L.ver_prev[i].as<unsigned char>();
+        n_tgt[slots] = n_tgts[i];
+        slot_of[i] = slots++;
+    }
+    IcpResult r[S2M_LOOP_MAX_CANDIDATES];
+    if (slots) {
+        s2m_loop_params lp;
+        s2m_loop_default_params(&lp);
+        const IcpParams ip{ prm.max_correspondence_distance, prm.max_iterations, prm.transformation_epsilon, prm.euclidean_fitness_epsilon };
+        hipError_t e = icp_dev_begin_many(L.icp, L.stream, L.icp_src.as<unsigned char>(), n_src, d_tgt, n_tgt, slots, stride_bytes, ip,
+                                          loop_tuning(h, lp.icp_leaf));
+        bool done = false;
+        if (e == hipSuccess) e = icp_dev_advance_many(L.icp, L.stream, true, &done, r);
+        if (e != hipSuccess || !done) {
+            (void)hipStreamSynchronize(L.stream);
+            icp_dev_cancel(L.icp);
+            return fail(h, S2M_ERR_HIP, "ICP device loop", e);
+        }
+    }
+    S2M_HIP(h, hipStreamSynchronize(L.stream));
+    for (int32_t i = 0; i < n_cand; i++) {
+        IcpResult none;
+        for (int k = 0; k < 16; k++) none.T[k] = (k % 5 == 0) ? 1.0f : 0.0f;
+        none.converged = 0; none.iterations = 0; none.fitness = DBL_MAX;
+        icp_result_out(slot_of[i] >= 0 ? r[slot_of[i]] : none, &out[i]);
+    }
     return S2M_OK;
 }

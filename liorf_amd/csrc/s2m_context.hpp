@@ -202,6 +202,15 @@ struct __attribute__((visibility("hidden"))) s2m_context {
         int32_t pend_base_key = -1;
         float snap_T[12] = { 0 };          // kf.frame[key_cur].T at launch
         float snap_pose_pre[6] = { 0 };    // kf.pose[key_pre] at launch
+        // the launched verification (s2m_loop_verify_launch): a pending closure with several candidates. Its records in the caller's
+        // order, the slot of the device loop each one runs in (-1: decided at launch, it took none), the target submap of every
+        // slot, and the candidates' poses at launch. pend_fitness, pend_base_key and snap_T serve it as they serve a single closure.
+        int32_t ver_n = 0;                 // records of the pending verification; 0: the pending closure is a single one
+        int32_t ver_slots = 0;
+        s2m_loop_result ver_rec[S2M_LOOP_MAX_CANDIDATES]{};
+        int32_t ver_slot[S2M_LOOP_MAX_CANDIDATES] = { 0 };
+        float ver_pose_pre[S2M_LOOP_MAX_CANDIDATES][6] = { { 0 } };
+        DevBuf ver_prev[S2M_LOOP_MAX_CANDIDATES];
         s2m::IcpTuning tune{ 0.0f, s2m::kIcpShellCap, s2m::kIcpUseGrid ? 1 : 0 };   // cell: edge in units of the leaf (s2m_debug_icp_tuning)
     } loop;
 

@@ -19,7 +19,9 @@
 // 1-NN through a uniform grid over the target, built once per alignment, with a brute-force worklist for the points the grid
 // does not settle (same keys); the host's part of (2) becomes k_icp_close, which runs the host loop's own source
 // (s2m_icp_close.hpp); iterations are queued in ranges and every kernel behind the end of the alignment returns at entry.
-// DESIGN.md section 12 has the stopping rule of the grid search and its derivation.
+// The loop carries up to kIcpMaxSlots alignments of one source at once (icp_dev_begin_many: what s2m_loop_verify_launch queues),
+// the slot a grid dimension of every kernel; the single alignment is its one-slot case.
+// DESIGN.md section 12 has the stopping rule of the grid search and its derivation, and the slot layout.
 #include "s2m_icp.hpp"
 
 #include <algorithm>
@@ -227,18 +229,60 @@ __device__ __forceinline__ bool done_guard(const IcpDevBlock* blk, int phase) { 
 // the cell coordinate along one axis before floor and clamp: non-decreasing in x (a subtraction of and a product with constants)
 __device__ __forceinline__ float cell_coord(float x, float lo, float inv) { return (x - lo) * inv; }
 
-__global__ __launch_bounds__(64) void k_icp_begin(IcpDevBlock* blk)
+// The slots of the loop: one source against K <= kIcpMaxSlots targets, K independent alignments advanced by the same launches.
+// Every kernel of the loop takes this struct by value (as k_icp_transform takes Mat34: nothing is uploaded per launch) and its
+// slot from blockIdx.z; grids are sized by the largest slot and a workgroup beyond its own slot's extent returns at entry.
+// Inside a slot nothing differs from the single alignment, which is the K = 1 case: the same per-point arithmetic, the same
+// (d2, original index) minimum, the same number of partial rows (it depends on n_src only), the same fold, the same close.
+struct IcpSlots {
+    float4*             cur[kIcpMaxSlots];       // the moving source, n_src points each
+    const float4*       tgt[kIcpMaxSlots];
+    unsigned long long* best[kIcpMaxSlots];
+    double*             part[kIcpMaxSlots];
+    int*                list[kIcpMaxSlots];      // the fallback list of the grid search
+    float4*             gsorted[kIcpMaxSlots];   // the targets sorted by cell
+    int                 n_tgt[kIcpMaxSlots];
+    int                 slice_len[kIcpMaxSlots]; // the brute force's target slice (nn_shape of this slot)
+    IcpDevBlock*        blk;                     // K blocks back to back: one copy per range brings them all
+    int*                gcount;                  // kGridMaxCells ints per slot, as gstart and gend
+    int*                gstart;
+    int*                gend;
+    int                 n_src;
+};
+
+// records to float4 per slot: the K targets, or the one source into every slot's moving copy
+struct IcpLoad {
+    const unsigned char* src[kIcpMaxSlots];
+    float4*              dst[kIcpMaxSlots];
+    int                  n[kIcpMaxSlots];
+};
+
+__global__ __launch_bounds__(256) void k_icp_load_slots(IcpLoad L, size_t stride)
+{
+    const int s = blockIdx.z;
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= L.n[s]) return;
+    const float* p = reinterpret_cast<const float*>(L.src[s] + (size_t)i * stride);
+    L.dst[s][i] = make_float4(p[0], p[1], p[2], 0.0f);
+}
+
+__global__ __launch_bounds__(64) void k_icp_begin(IcpSlots S)
 {
     if (threadIdx.x != 0) return;
+    IcpDevBlock* blk = S.blk + blockIdx.z;
     icp_state_init(&blk->st);
     for (int a = 0; a < 3; a++) { blk->bbox[a] = 0xffffffffu; blk->bbox[3 + a] = 0u; }
     blk->wl_count = 0; blk->n_fallback = 0;
     blk->g.n_fin = 0; blk->g.usable = 0;
 }
 
-__global__ __launch_bounds__(256) void k_icp_grid_bbox(const float4* __restrict__ tgt, int n, IcpDevBlock* blk)
+__global__ __launch_bounds__(256) void k_icp_grid_bbox(IcpSlots S)
 {
     __shared__ unsigned sh[4][6];
+    const int n = S.n_tgt[blockIdx.z];
+    if ((int)(blockIdx.x * blockDim.x) >= n) return;
+    const float4* __restrict__ tgt = S.tgt[blockIdx.z];
+    IcpDevBlock* blk = S.blk + blockIdx.z;
     unsigned lo[3] = { 0xffffffffu, 0xffffffffu, 0xffffffffu }, hi[3] = { 0u, 0u, 0u };
     for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
         const float4 t = tgt[i];
@@ -263,9 +307,10 @@ __global__ __launch_bounds__(256) void k_icp_grid_bbox(const float4* __restrict_
 }
 
 // the grid's shape from the box: the edge asked for, enlarged until the box needs no more than kGridMaxCells cells
-__global__ __launch_bounds__(64) void k_icp_grid_setup(IcpDevBlock* blk, float cell_req)
+__global__ __launch_bounds__(64) void k_icp_grid_setup(IcpSlots S, float cell_req)
 {
     if (threadIdx.x != 0) return;
+    IcpDevBlock* blk = S.blk + blockIdx.z;
     IcpGrid g{};
     if (blk->bbox[0] == 0xffffffffu) { blk->g = g; return; }             // no finite target: n_fin stays 0
     float hi[3];
@@ -301,21 +346,29 @@ __device__ __forceinline__ int cell_of(const IcpGrid& g, const float4 t)
     return (min(max(cz, 0), g.n[2] - 1) * g.n[1] + min(max(cy, 0), g.n[1] - 1)) * g.n[0] + min(max(cx, 0), g.n[0] - 1);
 }
 
-__global__ __launch_bounds__(256) void k_icp_grid_count(const float4* __restrict__ tgt, int n, const IcpDevBlock* blk, int* __restrict__ counts)
+__global__ __launch_bounds__(256) void k_icp_grid_count(IcpSlots S)
 {
+    const int s = blockIdx.z;
+    const IcpDevBlock* blk = S.blk + s;
+    int* __restrict__ counts = S.gcount + (size_t)s * kGridMaxCells;
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n || !blk->g.usable) return;
-    const float4 t = tgt[i];
+    if (i >= S.n_tgt[s] || !blk->g.usable) return;
+    const float4 t = S.tgt[s][i];
     if (!(isfinite(t.x) && isfinite(t.y) && isfinite(t.z))) return;
     atomicAdd(&counts[cell_of(blk->g, t)], 1);
 }
 
 // exclusive scan of the cell counts in one workgroup: cstart[c] = first slot of cell c, cursor[c] the same (k_icp_grid_scatter
 // advances it to the cell's end, which is the next cell's start)
-__global__ __launch_bounds__(1024) void k_icp_grid_scan(IcpDevBlock* blk, const int* __restrict__ counts, int* __restrict__ cstart, int* __restrict__ cursor)
+__global__ __launch_bounds__(1024) void k_icp_grid_scan(IcpSlots S)
 {
     __shared__ int sh[1024];
+    IcpDevBlock* blk = S.blk + blockIdx.z;
     if (!blk->g.usable) return;
+    const size_t cells0 = (size_t)blockIdx.z * kGridMaxCells;
+    const int* __restrict__ counts = S.gcount + cells0;
+    int* __restrict__ cstart = S.gstart + cells0;
+    int* __restrict__ cursor = S.gend + cells0;
     const int ncells = blk->g.n[0] * blk->g.n[1] * blk->g.n[2];
     const int per = (ncells + 1023) / 1024;
     const int c0 = min(threadIdx.x * per, ncells), c1 = min(c0 + per, ncells);
@@ -334,12 +387,15 @@ __global__ __launch_bounds__(1024) void k_icp_grid_scan(IcpDevBlock* blk, const 
     if (threadIdx.x == 1023) blk->g.n_fin = sh[1023];
 }
 
-__global__ __launch_bounds__(256) void k_icp_grid_scatter(const float4* __restrict__ tgt, int n, const IcpDevBlock* blk, int* __restrict__ cursor,
-                                                          float4* __restrict__ sorted)
+__global__ __launch_bounds__(256) void k_icp_grid_scatter(IcpSlots S)
 {
+    const int s = blockIdx.z, n = S.n_tgt[s];
+    const IcpDevBlock* blk = S.blk + s;
+    int* __restrict__ cursor = S.gend + (size_t)s * kGridMaxCells;
+    float4* __restrict__ sorted = S.gsorted[s];
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n || !blk->g.usable) return;
-    const float4 t = tgt[i];
+    const float4 t = S.tgt[s][i];
     if (!(isfinite(t.x) && isfinite(t.y) && isfinite(t.z))) return;
     const int pos = atomicAdd(&cursor[cell_of(blk->g, t)], 1);             // the order inside a cell is arbitrary: the search takes a minimum
     if (pos >= 0 && pos < n) sorted[pos] = make_float4(t.x, t.y, t.z, __int_as_float(i));
@@ -395,15 +451,20 @@ __device__ __forceinline__ bool grid_settled(const IcpGrid& g, const float4 p, c
 // exact 1-NN through the grid: one lane per source point. First the 3 x 3 x 3 cells around the (clamped) cell of the point, their
 // nine row ranges fetched before any point is read; then shells of growing Chebyshev radius up to shell_cap. A point that is not
 // settled by then, or lies more than shell_cap cells outside the box, goes to the fallback list.
-__global__ __launch_bounds__(kGridThreads) void k_icp_nn_grid(const float4* __restrict__ cur, int n_src, IcpDevBlock* blk,
-                                                              const int* __restrict__ cstart, const int* __restrict__ cend,
-                                                              const float4* __restrict__ sorted, unsigned long long* __restrict__ best,
-                                                              int* __restrict__ list, int shell_cap, int phase)
+__global__ __launch_bounds__(kGridThreads) void k_icp_nn_grid(IcpSlots S, int shell_cap, int phase)
 {
+    const int s = blockIdx.z;
+    IcpDevBlock* blk = S.blk + s;
     if (done_guard(blk, phase)) return;
+    const int n_src = S.n_src;
     const int i = blockIdx.x * kGridThreads + threadIdx.x;
     if (i >= n_src) return;
-    const float4 p = cur[i];
+    const int* __restrict__ cstart = S.gstart + (size_t)s * kGridMaxCells;
+    const int* __restrict__ cend = S.gend + (size_t)s * kGridMaxCells;
+    const float4* __restrict__ sorted = S.gsorted[s];
+    unsigned long long* __restrict__ best = S.best[s];
+    int* __restrict__ list = S.list[s];
+    const float4 p = S.cur[s][i];
     const IcpGrid g = blk->g;
     if (!(isfinite(p.x) && isfinite(p.y) && isfinite(p.z)) || g.n_fin == 0) { best[i] = kNoMatch; return; }
     const float f[3] = { cell_coord(p.x, g.lo[0], g.inv), cell_coord(p.y, g.lo[1], g.inv), cell_coord(p.z, g.lo[2], g.inv) };
@@ -464,23 +525,29 @@ __global__ __launch_bounds__(kGridThreads) void k_icp_nn_grid(const float4* __re
     }
 }
 
-__global__ __launch_bounds__(256) void k_icp_reset_dev(unsigned long long* __restrict__ best, int n, const IcpDevBlock* blk, int phase)
+__global__ __launch_bounds__(256) void k_icp_reset_dev(IcpSlots S, int phase)
 {
-    if (done_guard(blk, phase)) return;
+    if (done_guard(S.blk + blockIdx.z, phase)) return;
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) best[i] = kNoMatch;
+    if (i < S.n_src) S.best[blockIdx.z][i] = kNoMatch;
 }
 
-// k_icp_nn for the sources a list names (list == nullptr: all of them, the device loop's brute-force search): workgroups past
-// the end of the list return at entry
-__global__ __launch_bounds__(kNnThreads) void k_icp_nn_list(const float4* __restrict__ cur, int n_src, const float4* __restrict__ tgt, int n_tgt,
-                                                            int slice_len, unsigned long long* __restrict__ best, const int* __restrict__ list,
-                                                            const IcpDevBlock* blk, int phase)
+// k_icp_nn for the sources a slot's list names (use_list == 0: all of them, the device loop's brute-force search): grid (source
+// blocks, target slices of the slot with most, slots); workgroups past the end of the list or of their slot's slices return at entry
+__global__ __launch_bounds__(kNnThreads) void k_icp_nn_list(IcpSlots S, int use_list, int phase)
 {
     __shared__ float4 tile[kNnTile];
+    const int s = blockIdx.z;
+    const IcpDevBlock* blk = S.blk + s;
     if (done_guard(blk, phase)) return;
+    const int n_src = S.n_src, n_tgt = S.n_tgt[s], slice_len = S.slice_len[s];
+    const int j0 = blockIdx.y * slice_len, j1 = min(j0 + slice_len, n_tgt);
+    if (j0 >= n_tgt) return;
+    const int* __restrict__ list = use_list ? S.list[s] : nullptr;
     const int count = list ? min(blk->wl_count, n_src) : n_src;
     if ((int)(blockIdx.x * kNnThreads) >= count) return;
+    const float4* __restrict__ cur = S.cur[s];
+    unsigned long long* __restrict__ best = S.best[s];
     const int w = blockIdx.x * kNnThreads + threadIdx.x;
     const bool valid = w < count;
     const int i = valid ? (list ? list[w] : w) : 0;
@@ -488,45 +555,46 @@ __global__ __launch_bounds__(kNnThreads) void k_icp_nn_list(const float4* __rest
     const bool fin = valid && isfinite(p.x) && isfinite(p.y) && isfinite(p.z);
     float bd = INFINITY;
     int bi = -1;
-    const int j0 = blockIdx.y * slice_len, j1 = min(j0 + slice_len, n_tgt);
-    nn_tiles(p, fin, tgt, j0, j1, tile, bd, bi);
+    nn_tiles(p, fin, S.tgt[s], j0, j1, tile, bd, bi);
     if (fin && bi >= 0)
         atomicMin(&best[i], ((unsigned long long)__float_as_uint(bd) << 32) | (unsigned)bi);
 }
 
-__global__ __launch_bounds__(256) void k_icp_sums_dev(const float4* __restrict__ cur, int n_src, const float4* __restrict__ tgt,
-                                                      const unsigned long long* __restrict__ best, double max_d2, double* __restrict__ part,
-                                                      const IcpDevBlock* blk, int phase)
+__global__ __launch_bounds__(256) void k_icp_sums_dev(IcpSlots S, double max_d2, int phase)
 {
     __shared__ double sh[4][17];
-    if (done_guard(blk, phase)) return;
-    sums_body(cur, n_src, tgt, best, max_d2, part, sh);
+    const int s = blockIdx.z;
+    if (done_guard(S.blk + s, phase)) return;
+    sums_body(S.cur[s], S.n_src, S.tgt[s], S.best[s], max_d2, S.part[s], sh);
 }
 
-__global__ __launch_bounds__(64) void k_icp_fold_dev(const double* __restrict__ part, int rows, IcpDevBlock* blk, int phase)
+__global__ __launch_bounds__(64) void k_icp_fold_dev(IcpSlots S, int rows, int phase)
 {
+    IcpDevBlock* blk = S.blk + blockIdx.z;
     if (done_guard(blk, phase)) return;
-    fold_body(part, rows, blk->sums);
+    fold_body(S.part[blockIdx.z], rows, blk->sums);
     if (threadIdx.x == 0) { blk->n_fallback = blk->wl_count; blk->wl_count = 0; }
 }
 
-// closes the iteration on the folded sums: one lane runs icp_close_step, the host loop's own source
-__global__ __launch_bounds__(64) void k_icp_close(IcpDevBlock* blk, IcpCloseParams prm)
+// closes the iteration on the folded sums: one lane per slot runs icp_close_step, the host loop's own source
+__global__ __launch_bounds__(64) void k_icp_close(IcpSlots S, IcpCloseParams prm)
 {
+    IcpDevBlock* blk = S.blk + blockIdx.z;
     if (threadIdx.x != 0 || blk->st.done) return;
-    double S[17];
-    for (int k = 0; k < 17; k++) S[k] = blk->sums[k];
+    double sums[17];
+    for (int k = 0; k < 17; k++) sums[k] = blk->sums[k];
     IcpLoopState st = blk->st;
-    icp_close_step(S, prm, &st);
+    icp_close_step(sums, prm, &st);
     blk->st = st;
 }
 
 // phase 0: the source moves by the step of the iteration just closed (not once the alignment has ended); phase 1: the reloaded
 // source moves by the final transformation
-__global__ __launch_bounds__(256) void k_icp_transform_dev(float4* __restrict__ cur, int n, const IcpDevBlock* blk, int phase)
+__global__ __launch_bounds__(256) void k_icp_transform_dev(IcpSlots S, int phase)
 {
+    const IcpDevBlock* blk = S.blk + blockIdx.z;
     if (done_guard(blk, phase)) return;
-    transform_body(cur, n, phase == 0 ? blk->st.T_step : blk->st.T);
+    transform_body(S.cur[blockIdx.z], S.n_src, phase == 0 ? blk->st.T_step : blk->st.T);
 }
 
 }  // namespace
@@ -541,12 +609,15 @@ struct IcpWorkspace {
     hipEvent_t ev = nullptr;
     struct Flight {
         int phase = 0;                   // 0 none, 1 a range of iterations is queued, 2 the fitness pass is queued
-        int n_src = 0, n_tgt = 0, queued = 0;
+        int n_src = 0, queued = 0;
         const unsigned char* d_src = nullptr;
         size_t stride = 0;
         IcpParams prm{};
         IcpTuning tune{};
     } fl;
+    // the slots the buffers are laid out for (dev_layout): what every kernel of the loop gets by value, and the launch shapes
+    IcpSlots S{};
+    int K = 0, n_tgt_max = 0, slices_max = 0;
 };
 
 IcpWorkspace* icp_create()
@@ -554,7 +625,8 @@ IcpWorkspace* icp_create()
     IcpWorkspace* w = new (std::nothrow) IcpWorkspace();
     if (!w) return nullptr;
     if (w->sums.ensure(sizeof(double) * 17) != hipSuccess || hipHostMalloc((void**)&w->h_sums, sizeof(double) * 17) != hipSuccess ||
-        w->blk.ensure(sizeof(IcpDevBlock)) != hipSuccess || hipHostMalloc((void**)&w->h_blk, sizeof(IcpDevBlock)) != hipSuccess ||
+        w->blk.ensure(sizeof(IcpDevBlock) * kIcpMaxSlots) != hipSuccess ||
+        hipHostMalloc((void**)&w->h_blk, sizeof(IcpDevBlock) * kIcpMaxSlots) != hipSuccess ||
         hipEventCreateWithFlags(&w->ev, hipEventDisableTiming) != hipSuccess) {
         icp_destroy(w);
         return nullptr;
@@ -608,72 +680,111 @@ hipError_t sums(IcpWorkspace* w, hipStream_t stream, int n_src, double max_d2)
     return hipStreamSynchronize(stream);
 }
 
-hipError_t ensure_clouds(IcpWorkspace* w, size_t n_src, size_t n_tgt)
+// The buffers of K slots - one source of n_src points, targets of n_tgt[k] - and w->S, their layout: a slot's moving source, keys,
+// partial rows and list are n_src (rows) apiece, its target and sorted target start where the slot before ends. Slot 0 starts
+// every buffer, so what the host loop (icp_align) uses is the K = 1 layout. tune: the device loop's list and, with the grid
+// on, its cell arrays are laid out too (nullptr: the host loop, which has neither).
+hipError_t dev_layout(IcpWorkspace* w, int K, size_t n_src, const size_t* n_tgt, const IcpTuning* tune)
 {
-    ICP_TRY(w->cur.ensure(sizeof(float4) * n_src)); ICP_TRY(w->tgt.ensure(sizeof(float4) * n_tgt));
-    ICP_TRY(w->best.ensure(sizeof(unsigned long long) * n_src));
-    return w->part.ensure(sizeof(double) * 17 * (size_t)std::min(((int)n_src + 255) / 256, kSumBlocks));
+    if (K < 1 || K > kIcpMaxSlots) return hipErrorInvalidValue;
+    size_t total = 0, most = 0;
+    for (int k = 0; k < K; k++) { total += n_tgt[k]; most = std::max(most, n_tgt[k]); }
+    if (n_src > (size_t)0x3fffffff || total > (size_t)0x3fffffff) return hipErrorInvalidValue;
+    const size_t rows = (size_t)std::min(((int)n_src + 255) / 256, kSumBlocks);
+    ICP_TRY(w->cur.ensure(sizeof(float4) * n_src * K)); ICP_TRY(w->tgt.ensure(sizeof(float4) * total));
+    ICP_TRY(w->best.ensure(sizeof(unsigned long long) * n_src * K));
+    ICP_TRY(w->part.ensure(sizeof(double) * 17 * rows * K));
+    const bool grid = tune && tune->use_grid;
+    if (tune) ICP_TRY(w->list.ensure(sizeof(int) * n_src * K));
+    if (grid) {
+        ICP_TRY(w->gcount.ensure(sizeof(int) * kGridMaxCells * (size_t)K)); ICP_TRY(w->gstart.ensure(sizeof(int) * kGridMaxCells * (size_t)K));
+        ICP_TRY(w->gend.ensure(sizeof(int) * kGridMaxCells * (size_t)K)); ICP_TRY(w->gsorted.ensure(sizeof(float4) * total));
+    }
+    IcpSlots S{};
+    size_t off = 0;
+    int slices_max = 1;
+    for (int k = 0; k < K; k++) {
+        S.cur[k] = w->cur.as<float4>() + n_src * k; S.tgt[k] = w->tgt.as<float4>() + off;
+        S.best[k] = w->best.as<unsigned long long>() + n_src * k; S.part[k] = w->part.as<double>() + 17 * rows * k;
+        S.list[k] = tune ? w->list.as<int>() + n_src * k : nullptr;
+        S.gsorted[k] = grid ? w->gsorted.as<float4>() + off : nullptr;
+        S.n_tgt[k] = (int)n_tgt[k];
+        int sb = 0, slices = 1;
+        if (n_src && n_tgt[k]) nn_shape((int)n_src, (int)n_tgt[k], &sb, &slices, &S.slice_len[k]);
+        slices_max = std::max(slices_max, slices);
+        off += n_tgt[k];
+    }
+    S.blk = w->blk.as<IcpDevBlock>();
+    S.gcount = w->gcount.as<int>(); S.gstart = w->gstart.as<int>(); S.gend = w->gend.as<int>();
+    S.n_src = (int)n_src;
+    w->S = S; w->K = K; w->n_tgt_max = (int)most; w->slices_max = slices_max;
+    return hipSuccess;
 }
 
-// the device loop's buffers, the block reset, and with the grid on: box, shape, counts, scan, scatter - once per alignment
-hipError_t dev_prepare(IcpWorkspace* w, hipStream_t stream, int n_src, int n_tgt, const IcpTuning& tune)
+hipError_t ensure_clouds(IcpWorkspace* w, size_t n_src, size_t n_tgt) { return dev_layout(w, 1, n_src, &n_tgt, nullptr); }
+
+// records -> float4: the K targets of the layout, or the one source into every slot's moving copy
+hipError_t load_slots(IcpWorkspace* w, hipStream_t stream, const unsigned char* d_src, const unsigned char* const* d_tgt, size_t stride)
 {
-    ICP_TRY(w->list.ensure(sizeof(int) * (size_t)n_src));
-    IcpDevBlock* blk = w->blk.as<IcpDevBlock>();
-    hipLaunchKernelGGL(k_icp_begin, dim3(1), dim3(64), 0, stream, blk);
+    IcpLoad L{};
+    int most = 0;
+    for (int k = 0; k < w->K; k++) {
+        L.src[k] = d_tgt ? d_tgt[k] : d_src;
+        L.dst[k] = d_tgt ? const_cast<float4*>(w->S.tgt[k]) : w->S.cur[k];
+        L.n[k] = d_tgt ? w->S.n_tgt[k] : w->S.n_src;
+        most = std::max(most, L.n[k]);
+    }
+    hipLaunchKernelGGL(k_icp_load_slots, dim3((most + 255) / 256, 1, w->K), dim3(256), 0, stream, L, stride);
+    return hipGetLastError();
+}
+
+// the block reset of every slot of the layout and, with the grid on: box, shape, counts, scan, scatter - once per alignment
+hipError_t dev_prepare(IcpWorkspace* w, hipStream_t stream, const IcpTuning& tune)
+{
+    const IcpSlots& S = w->S;
+    const unsigned K = (unsigned)w->K;
+    hipLaunchKernelGGL(k_icp_begin, dim3(1, 1, K), dim3(64), 0, stream, S);
     if (tune.use_grid) {
-        ICP_TRY(w->gcount.ensure(sizeof(int) * kGridMaxCells)); ICP_TRY(w->gstart.ensure(sizeof(int) * kGridMaxCells));
-        ICP_TRY(w->gend.ensure(sizeof(int) * kGridMaxCells)); ICP_TRY(w->gsorted.ensure(sizeof(float4) * (size_t)n_tgt));
-        ICP_TRY(hipMemsetAsync(w->gcount.p, 0, sizeof(int) * kGridMaxCells, stream));
-        const float4* tgt = w->tgt.as<float4>();
-        const int tb = (n_tgt + 255) / 256;
-        hipLaunchKernelGGL(k_icp_grid_bbox, dim3(std::min(tb, 256)), dim3(256), 0, stream, tgt, n_tgt, blk);
-        hipLaunchKernelGGL(k_icp_grid_setup, dim3(1), dim3(64), 0, stream, blk, tune.cell);
-        hipLaunchKernelGGL(k_icp_grid_count, dim3(tb), dim3(256), 0, stream, tgt, n_tgt, (const IcpDevBlock*)blk, w->gcount.as<int>());
-        hipLaunchKernelGGL(k_icp_grid_scan, dim3(1), dim3(1024), 0, stream, blk, (const int*)w->gcount.as<int>(), w->gstart.as<int>(), w->gend.as<int>());
-        hipLaunchKernelGGL(k_icp_grid_scatter, dim3(tb), dim3(256), 0, stream, tgt, n_tgt, (const IcpDevBlock*)blk, w->gend.as<int>(), w->gsorted.as<float4>());
+        ICP_TRY(hipMemsetAsync(w->gcount.p, 0, sizeof(int) * kGridMaxCells * (size_t)K, stream));
+        const int tb = (w->n_tgt_max + 255) / 256;
+        hipLaunchKernelGGL(k_icp_grid_bbox, dim3(std::min(tb, 256), 1, K), dim3(256), 0, stream, S);
+        hipLaunchKernelGGL(k_icp_grid_setup, dim3(1, 1, K), dim3(64), 0, stream, S, tune.cell);
+        hipLaunchKernelGGL(k_icp_grid_count, dim3(tb, 1, K), dim3(256), 0, stream, S);
+        hipLaunchKernelGGL(k_icp_grid_scan, dim3(1, 1, K), dim3(1024), 0, stream, S);
+        hipLaunchKernelGGL(k_icp_grid_scatter, dim3(tb, 1, K), dim3(256), 0, stream, S);
     }
     return hipGetLastError();
 }
 
-// one search of the device loop: the grid with its fallback, or (use_grid off) the brute force over every source
-hipError_t dev_nearest(IcpWorkspace* w, hipStream_t stream, int n_src, int n_tgt, const IcpTuning& tune, int phase)
+// one search of the device loop in every slot: the grid with its fallback, or (use_grid off) the brute force over every source
+hipError_t dev_nearest(IcpWorkspace* w, hipStream_t stream, const IcpTuning& tune, int phase)
 {
-    int sb, slices, slice_len;
-    nn_shape(n_src, n_tgt, &sb, &slices, &slice_len);
-    IcpDevBlock* blk = w->blk.as<IcpDevBlock>();
-    const float4* cur = w->cur.as<float4>();
-    const float4* tgt = w->tgt.as<float4>();
-    unsigned long long* best = w->best.as<unsigned long long>();
+    const IcpSlots& S = w->S;
+    const unsigned K = (unsigned)w->K;
+    const int n_src = S.n_src, sb = (n_src + kNnThreads - 1) / kNnThreads;
     if (tune.use_grid) {
-        hipLaunchKernelGGL(k_icp_nn_grid, dim3((n_src + kGridThreads - 1) / kGridThreads), dim3(kGridThreads), 0, stream, cur, n_src, blk,
-                           (const int*)w->gstart.as<int>(), (const int*)w->gend.as<int>(), (const float4*)w->gsorted.as<float4>(), best,
-                           w->list.as<int>(), std::max(1, tune.shell_cap), phase);
-        hipLaunchKernelGGL(k_icp_nn_list, dim3(sb, slices), dim3(kNnThreads), 0, stream, cur, n_src, tgt, n_tgt, slice_len, best,
-                           (const int*)w->list.as<int>(), (const IcpDevBlock*)blk, phase);
+        hipLaunchKernelGGL(k_icp_nn_grid, dim3((n_src + kGridThreads - 1) / kGridThreads, 1, K), dim3(kGridThreads), 0, stream, S,
+                           std::max(1, tune.shell_cap), phase);
+        hipLaunchKernelGGL(k_icp_nn_list, dim3(sb, w->slices_max, K), dim3(kNnThreads), 0, stream, S, 1, phase);
     } else {
-        hipLaunchKernelGGL(k_icp_reset_dev, dim3((n_src + 255) / 256), dim3(256), 0, stream, best, n_src, (const IcpDevBlock*)blk, phase);
-        hipLaunchKernelGGL(k_icp_nn_list, dim3(sb, slices), dim3(kNnThreads), 0, stream, cur, n_src, tgt, n_tgt, slice_len, best,
-                           (const int*)nullptr, (const IcpDevBlock*)blk, phase);
+        hipLaunchKernelGGL(k_icp_reset_dev, dim3((n_src + 255) / 256, 1, K), dim3(256), 0, stream, S, phase);
+        hipLaunchKernelGGL(k_icp_nn_list, dim3(sb, w->slices_max, K), dim3(kNnThreads), 0, stream, S, 0, phase);
     }
     return hipGetLastError();
 }
 
-hipError_t dev_sums(IcpWorkspace* w, hipStream_t stream, int n_src, double max_d2, int phase)
+hipError_t dev_sums(IcpWorkspace* w, hipStream_t stream, double max_d2, int phase)
 {
-    const int rows = std::min((n_src + 255) / 256, kSumBlocks);
-    IcpDevBlock* blk = w->blk.as<IcpDevBlock>();
-    hipLaunchKernelGGL(k_icp_sums_dev, dim3(rows), dim3(256), 0, stream, (const float4*)w->cur.as<float4>(), n_src,
-                       (const float4*)w->tgt.as<float4>(), (const unsigned long long*)w->best.as<unsigned long long>(), max_d2,
-                       w->part.as<double>(), (const IcpDevBlock*)blk, phase);
-    hipLaunchKernelGGL(k_icp_fold_dev, dim3(1), dim3(64), 0, stream, (const double*)w->part.as<double>(), rows, blk, phase);
+    const int rows = std::min((w->S.n_src + 255) / 256, kSumBlocks);
+    hipLaunchKernelGGL(k_icp_sums_dev, dim3(rows, 1, w->K), dim3(256), 0, stream, w->S, max_d2, phase);
+    hipLaunchKernelGGL(k_icp_fold_dev, dim3(1, 1, w->K), dim3(64), 0, stream, w->S, rows, phase);
     return hipGetLastError();
 }
 
-// the block to the host and the event the host tests: the end of everything queued so far
+// the blocks of all slots to the host in one copy, and the event the host tests: the end of everything queued so far
 hipError_t dev_mark(IcpWorkspace* w, hipStream_t stream)
 {
-    ICP_TRY(hipMemcpyAsync(w->h_blk, w->blk.p, sizeof(IcpDevBlock), hipMemcpyDeviceToHost, stream));
+    ICP_TRY(hipMemcpyAsync(w->h_blk, w->blk.p, sizeof(IcpDevBlock) * (size_t)w->K, hipMemcpyDeviceToHost, stream));
     return hipEventRecord(w->ev, stream);
 }
 
@@ -683,27 +794,25 @@ hipError_t dev_queue_range(IcpWorkspace* w, hipStream_t stream)
     const int n = std::min(kIcpRange, f.prm.max_iter - f.queued);
     const IcpCloseParams cp = icp_close_params(f.prm.max_iter, f.prm.trans_eps, f.prm.fit_eps);
     const double max_d2 = f.prm.max_corr_dist * f.prm.max_corr_dist;
-    IcpDevBlock* blk = w->blk.as<IcpDevBlock>();
     for (int k = 0; k < n; k++) {
-        ICP_TRY(dev_nearest(w, stream, f.n_src, f.n_tgt, f.tune, 0));
-        ICP_TRY(dev_sums(w, stream, f.n_src, max_d2, 0));
-        hipLaunchKernelGGL(k_icp_close, dim3(1), dim3(64), 0, stream, blk, cp);
-        hipLaunchKernelGGL(k_icp_transform_dev, dim3((f.n_src + 255) / 256), dim3(256), 0, stream, w->cur.as<float4>(), f.n_src, (const IcpDevBlock*)blk, 0);
+        ICP_TRY(dev_nearest(w, stream, f.tune, 0));
+        ICP_TRY(dev_sums(w, stream, max_d2, 0));
+        hipLaunchKernelGGL(k_icp_close, dim3(1, 1, w->K), dim3(64), 0, stream, w->S, cp);
+        hipLaunchKernelGGL(k_icp_transform_dev, dim3((f.n_src + 255) / 256, 1, w->K), dim3(256), 0, stream, w->S, 0);
         ICP_TRY(hipGetLastError());
     }
     f.queued += n;
     return dev_mark(w, stream);
 }
 
-// getFitnessScore(): the original source under the final transformation, nearest distances with no limit
+// getFitnessScore() of every slot: the original source under the slot's final transformation, nearest distances with no limit
 hipError_t dev_queue_fitness(IcpWorkspace* w, hipStream_t stream)
 {
     IcpWorkspace::Flight& f = w->fl;
-    hipLaunchKernelGGL(k_icp_load, dim3((f.n_src + 255) / 256), dim3(256), 0, stream, f.d_src, f.stride, f.n_src, w->cur.as<float4>());
-    hipLaunchKernelGGL(k_icp_transform_dev, dim3((f.n_src + 255) / 256), dim3(256), 0, stream, w->cur.as<float4>(), f.n_src,
-                       (const IcpDevBlock*)w->blk.as<IcpDevBlock>(), 1);
-    ICP_TRY(dev_nearest(w, stream, f.n_src, f.n_tgt, f.tune, 1));
-    ICP_TRY(dev_sums(w, stream, f.n_src, DBL_MAX, 1));
+    ICP_TRY(load_slots(w, stream, f.d_src, nullptr, f.stride));
+    hipLaunchKernelGGL(k_icp_transform_dev, dim3((f.n_src + 255) / 256, 1, w->K), dim3(256), 0, stream, w->S, 1);
+    ICP_TRY(dev_nearest(w, stream, f.tune, 1));
+    ICP_TRY(dev_sums(w, stream, DBL_MAX, 1));
     return dev_mark(w, stream);
 }
 
@@ -711,25 +820,30 @@ hipError_t dev_queue_fitness(IcpWorkspace* w, hipStream_t stream)
 
 void icp_dev_cancel(IcpWorkspace* w) { w->fl.phase = 0; }
 
-hipError_t icp_dev_begin(IcpWorkspace* w, hipStream_t stream, const unsigned char* d_src, size_t n_src_, const unsigned char* d_tgt,
-                         size_t n_tgt_, size_t stride, const IcpParams& prm, const IcpTuning& tune)
+hipError_t icp_dev_begin_many(IcpWorkspace* w, hipStream_t stream, const unsigned char* d_src, size_t n_src_, const unsigned char* const* d_tgt,
+                              const size_t* n_tgt, int n_slots, size_t stride, const IcpParams& prm, const IcpTuning& tune)
 {
-    const int n_src = (int)n_src_, n_tgt = (int)n_tgt_;
-    if (w->fl.phase != 0 || n_src <= 0 || n_tgt <= 0 || prm.max_iter < 1) return hipErrorInvalidValue;
-    ICP_TRY(ensure_clouds(w, n_src_, n_tgt_));
-    hipLaunchKernelGGL(k_icp_load, dim3((n_src + 255) / 256), dim3(256), 0, stream, d_src, stride, n_src, w->cur.as<float4>());
-    hipLaunchKernelGGL(k_icp_load, dim3((n_tgt + 255) / 256), dim3(256), 0, stream, d_tgt, stride, n_tgt, w->tgt.as<float4>());
-    ICP_TRY(hipGetLastError());
-    ICP_TRY(dev_prepare(w, stream, n_src, n_tgt, tune));
+    if (w->fl.phase != 0 || n_src_ == 0 || n_slots < 1 || n_slots > kIcpMaxSlots || prm.max_iter < 1) return hipErrorInvalidValue;
+    for (int k = 0; k < n_slots; k++) if (n_tgt[k] == 0) return hipErrorInvalidValue;
+    ICP_TRY(dev_layout(w, n_slots, n_src_, n_tgt, &tune));
+    ICP_TRY(load_slots(w, stream, d_src, nullptr, stride));
+    ICP_TRY(load_slots(w, stream, nullptr, d_tgt, stride));
+    ICP_TRY(dev_prepare(w, stream, tune));
     IcpWorkspace::Flight& f = w->fl;
     f = IcpWorkspace::Flight{};
-    f.n_src = n_src; f.n_tgt = n_tgt; f.d_src = d_src; f.stride = stride; f.prm = prm; f.tune = tune;
+    f.n_src = (int)n_src_; f.d_src = d_src; f.stride = stride; f.prm = prm; f.tune = tune;
     ICP_TRY(dev_queue_range(w, stream));
     f.phase = 1;
     return hipSuccess;
 }
 
-hipError_t icp_dev_advance(IcpWorkspace* w, hipStream_t stream, bool wait, bool* done, IcpResult* res)
+hipError_t icp_dev_begin(IcpWorkspace* w, hipStream_t stream, const unsigned char* d_src, size_t n_src, const unsigned char* d_tgt,
+                         size_t n_tgt, size_t stride, const IcpParams& prm, const IcpTuning& tune)
+{
+    return icp_dev_begin_many(w, stream, d_src, n_src, &d_tgt, &n_tgt, 1, stride, prm, tune);
+}
+
+hipError_t icp_dev_advance_many(IcpWorkspace* w, hipStream_t stream, bool wait, bool* done, IcpResult* res)
 {
     IcpWorkspace::Flight& f = w->fl;
     *done = false;
@@ -745,21 +859,30 @@ hipError_t icp_dev_advance(IcpWorkspace* w, hipStream_t stream, bool wait, bool*
         }
         hipError_t e = hipSuccess;
         if (f.phase == 1) {
-            if (w->h_blk->st.done) { e = dev_queue_fitness(w, stream); f.phase = 2; }
+            bool all_done = true;
+            for (int k = 0; k < w->K; k++) all_done = all_done && w->h_blk[k].st.done != 0;
+            if (all_done) { e = dev_queue_fitness(w, stream); f.phase = 2; }
             else if (f.queued >= f.prm.max_iter) e = hipErrorUnknown;     // max_iter closes end every alignment: not reached
             else e = dev_queue_range(w, stream);
             if (e != hipSuccess) { f.phase = 0; return e; }
             if (!wait) return hipSuccess;
             continue;
         }
-        const IcpDevBlock& b = *w->h_blk;
-        memcpy(res->T, b.st.T, sizeof(res->T));
-        res->converged = b.st.conv; res->iterations = b.st.it;
-        res->fitness = b.sums[0] > 0 ? b.sums[1] / b.sums[0] : DBL_MAX;
+        for (int k = 0; k < w->K; k++) {
+            const IcpDevBlock& b = w->h_blk[k];
+            memcpy(res[k].T, b.st.T, sizeof(res[k].T));
+            res[k].converged = b.st.conv; res[k].iterations = b.st.it;
+            res[k].fitness = b.sums[0] > 0 ? b.sums[1] / b.sums[0] : DBL_MAX;
+        }
         f.phase = 0;
         *done = true;
         return hipSuccess;
     }
+}
+
+hipError_t icp_dev_advance(IcpWorkspace* w, hipStream_t stream, bool wait, bool* done, IcpResult* res)
+{
+    return w->K == 1 ? icp_dev_advance_many(w, stream, wait, done, res) : hipErrorInvalidValue;
 }
 
 hipError_t icp_dev_nearest(IcpWorkspace* w, hipStream_t stream, const unsigned char* d_src, size_t n_src_, const unsigned char* d_tgt,
@@ -768,7 +891,7 @@ hipError_t icp_dev_nearest(IcpWorkspace* w, hipStream_t stream, const unsigned c
 {
     const int n_src = (int)n_src_, n_tgt = (int)n_tgt_;
     if (w->fl.phase != 0 || n_src <= 0 || n_tgt <= 0) return hipErrorInvalidValue;
-    ICP_TRY(ensure_clouds(w, n_src_, n_tgt_));
+    ICP_TRY(dev_layout(w, 1, n_src_, &n_tgt_, mode != 0 ? &tune_ : nullptr));
     hipLaunchKernelGGL(k_icp_load, dim3((n_src + 255) / 256), dim3(256), 0, stream, d_src, stride, n_src, w->cur.as<float4>());
     hipLaunchKernelGGL(k_icp_load, dim3((n_tgt + 255) / 256), dim3(256), 0, stream, d_tgt, stride, n_tgt, w->tgt.as<float4>());
     ICP_TRY(hipGetLastError());
@@ -783,13 +906,13 @@ hipError_t icp_dev_nearest(IcpWorkspace* w, hipStream_t stream, const unsigned c
         if (e == hipSuccess) e = hipEventCreate(&e2);
         if (e == hipSuccess) e = hipEventRecord(e0, stream);
     }
-    if (e == hipSuccess && mode != 0) e = dev_prepare(w, stream, n_src, n_tgt, tune);
+    if (e == hipSuccess && mode != 0) e = dev_prepare(w, stream, tune);
     if (e == hipSuccess && timed) e = hipEventRecord(e1, stream);
     for (int r = 0; e == hipSuccess && r < std::max(1, reps); r++) {
         if (mode == 0) e = nearest(w, stream, n_src, n_tgt);
         else {
-            if (r > 0) hipLaunchKernelGGL(k_icp_fold_dev, dim3(1), dim3(64), 0, stream, (const double*)w->part.as<double>(), 0, w->blk.as<IcpDevBlock>(), 1);   // (zeroes the list count)
-            e = dev_nearest(w, stream, n_src, n_tgt, tune, 1);
+            if (r > 0) hipLaunchKernelGGL(k_icp_fold_dev, dim3(1), dim3(64), 0, stream, w->S, 0, 1);   // (zeroes the list count)
+            e = dev_nearest(w, stream, tune, 1);
         }
     }
     if (e == hipSuccess && timed) e = hipEventRecord(e2, stream);

@@ -39,6 +39,14 @@ hipError_t icp_dev_begin(IcpWorkspace* w, hipStream_t stream, const unsigned cha
 // the fitness pass) without waiting for it; wait == true: the same with hipEventSynchronize until the result is there.
 // *done: `res` holds the result and nothing is in flight any more. d_src must stay as it was until then (the fitness pass reloads it).
 hipError_t icp_dev_advance(IcpWorkspace* w, hipStream_t stream, bool wait, bool* done, IcpResult* res);
+// The same for one source against n_slots <= kIcpMaxSlots targets: n_slots independent alignments advance through the same
+// launches (the slot is a grid dimension of every kernel of the loop; icp_dev_begin is the one-slot case). Ranges are queued
+// until every slot has ended - a slot that has ended idles meanwhile - then one fitness pass runs for all. res: n_slots results,
+// res[k] bit for bit what icp_dev_begin / icp_dev_advance give for d_tgt[k] alone. n_tgt[k] > 0.
+constexpr int kIcpMaxSlots = 8;
+hipError_t icp_dev_begin_many(IcpWorkspace* w, hipStream_t stream, const unsigned char* d_src, size_t n_src, const unsigned char* const* d_tgt,
+                              const size_t* n_tgt, int n_slots, size_t stride, const IcpParams& prm, const IcpTuning& tune);
+hipError_t icp_dev_advance_many(IcpWorkspace* w, hipStream_t stream, bool wait, bool* done, IcpResult* res);
 // one nearest-neighbour search of src against tgt, synchronously: mode 0 k_icp_nn, mode 1 the device loop's search (the grid with its
 // fallback, or with tune.use_grid off k_icp_nn_list over every source). keys: host,
 // n_src entries of (fp32 d2 bits << 32 | target index), ~0 = no match. reps > 0: the search `reps` times between events

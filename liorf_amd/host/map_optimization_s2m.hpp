@@ -510,6 +510,65 @@ public:
         return accepted();
     }
 
+    // -- verification: key_cur against up to S2M_LOOP_MAX_CANDIDATES stored keys, aligned in lockstep (s2m_loop_verify*) --
+    // lastVerify[i] is what loopAlign(key_cur, key_pre[i], base_key) gives on a container without key_cur; lastBest the position
+    // of the accepted record with the least (fitness, position) or -1. Only that pair goes into the container. A pending
+    // verification is a pending closure: the same lock discipline and the same BUSY calls as performRSLoopClosureLaunch().
+    std::vector<s2m_loop_result> lastVerify;
+    int lastBest = -1;
+    bool loopVerify(int key_cur, const std::vector<int32_t>& key_pre, int base_key = -1)
+    {
+        const s2m_loop_params p = loopParams();
+        lastVerify.assign(S2M_LOOP_MAX_CANDIDATES, s2m_loop_result{});
+        int32_t best = -1;
+        check(s2m_loop_verify(h_, key_cur, key_pre.data(), (int32_t)key_pre.size(), base_key, &p, lastVerify.data(), &best), "s2m_loop_verify");
+        lastVerify.resize(key_pre.size());
+        lastBest = best;
+        return verifyAccepted();
+    }
+    // true: a verification is pending (false: lastVerify is final)
+    bool loopVerifyLaunch(int key_cur, const std::vector<int32_t>& key_pre, int base_key = -1)
+    {
+        const s2m_loop_params p = loopParams();
+        lastVerify.assign(S2M_LOOP_MAX_CANDIDATES, s2m_loop_result{});
+        int32_t best = -1;
+        check(s2m_loop_verify_launch(h_, key_cur, key_pre.data(), (int32_t)key_pre.size(), base_key, &p, lastVerify.data(), &best),
+              "s2m_loop_verify_launch");
+        lastVerify.resize(key_pre.size());
+        lastBest = best;
+        return verifyPending();
+    }
+    bool verifyPending() const
+    {
+        for (const s2m_loop_result& r : lastVerify) if (r.status == S2M_LOOP_PENDING) return true;
+        return false;
+    }
+    // never waits for the device; true once the verification has ended with an accepted candidate
+    bool loopVerifyPoll() { return verifyFetch(false); }
+    // waits for the pending verification; true if a candidate was accepted
+    bool loopVerifyCollect() { return verifyFetch(true); }
+
+    // performSCLoopClosure() on the place query: the top_k hits of s2m_sc_query_key for the newest key (ordered by descriptor
+    // distance) verified in lockstep, SC form; the verification re-ranks them by fitness. true: lastVerify[lastBest] is the closure.
+    bool performSCLoopClosureVerified(int top_k)
+    {
+        lastVerify.clear();
+        lastBest = -1;
+        if (cloudKeyPoses6D.empty()) return false;
+        const int key_cur = (int)cloudKeyPoses6D.size() - 1;
+        s2m_sc_query_params q;
+        s2m_sc_query_default_params(&q);
+        q.top_k = top_k;
+        s2m_sc_hit hits[S2M_SC_QUERY_MAX_K];
+        int32_t n_hits = 0;
+        check(s2m_sc_query_key(h_, key_cur, &q, hits, &n_hits), "s2m_sc_query_key");
+        std::vector<int32_t> cand;
+        for (int32_t i = 0; i < n_hits && (int)cand.size() < S2M_LOOP_MAX_CANDIDATES; i++)
+            if (hits[i].key != key_cur) cand.push_back(hits[i].key);
+        if (cand.empty()) return false;
+        return loopVerify(key_cur, cand, 0);
+    }
+
     // void performSCLoopClosure() (:624-730): the ScanContext detector on this handle, then the store's extraction and ICP
     inline bool performSCLoopClosure(SCManagerS2M& scManager);
 
@@ -533,6 +592,23 @@ private:
         if (lastLoop.status != S2M_LOOP_ACCEPTED) return false;
         loopIndexContainer.emplace_back(lastLoop.key_cur, lastLoop.key_pre);
         return true;
+    }
+    bool verifyAccepted()
+    {
+        if (lastBest < 0) return false;
+        loopIndexContainer.emplace_back(lastVerify[(size_t)lastBest].key_cur, lastVerify[(size_t)lastBest].key_pre);
+        return true;
+    }
+    bool verifyFetch(bool wait)
+    {
+        lastVerify.assign(S2M_LOOP_MAX_CANDIDATES, s2m_loop_result{});
+        int32_t n = 0, best = -1;
+        check(wait ? s2m_loop_verify_collect(h_, lastVerify.data(), S2M_LOOP_MAX_CANDIDATES, &n, &best)
+                   : s2m_loop_verify_poll(h_, lastVerify.data(), S2M_LOOP_MAX_CANDIDATES, &n, &best),
+              wait ? "s2m_loop_verify_collect" : "s2m_loop_verify_poll");
+        lastVerify.resize((size_t)n);
+        lastBest = best;
+        return verifyAccepted();
     }
 
     void check(int rc, const char* what)

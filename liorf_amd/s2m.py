@@ -43,7 +43,9 @@ ABI_SYMBOLS = [
     "s2m_kf_default_params", "s2m_kf_reset", "s2m_kf_size", "s2m_kf_add", "s2m_kf_set_poses", "s2m_extract_surrounding",
     "s2m_loop_default_params", "s2m_loop_near_keyframes", "s2m_loop_align", "s2m_loop_closure_rs",
     "s2m_loop_align_launch", "s2m_loop_closure_rs_launch", "s2m_loop_poll", "s2m_loop_collect",
-    "s2m_debug_icp_nearest", "s2m_debug_icp_time_nearest", "s2m_debug_icp_align_device", "s2m_debug_icp_tuning",
+    "s2m_loop_verify_check_args", "s2m_loop_verify_launch", "s2m_loop_verify_poll", "s2m_loop_verify_collect", "s2m_loop_verify",
+    "s2m_debug_icp_nearest", "s2m_debug_icp_time_nearest", "s2m_debug_icp_align_device", "s2m_debug_icp_align_many_device",
+    "s2m_debug_icp_tuning",
     "s2m_gmap_default_params", "s2m_global_map", "s2m_kf_map_cloud",
     "s2m_scan_layout_preset", "s2m_project_default_params", "s2m_imu_deskew_info", "s2m_project_check_args", "s2m_project_scan",
     "s2m_downsample_projected", "s2m_sc_add_projected",
@@ -62,6 +64,7 @@ S2M_IMU_QUEUE_LENGTH = 2000
 S2M_KF_FROM_HOST, S2M_KF_FROM_DEVICE, S2M_KF_FROM_LAST_DOWNSAMPLE = 0, 1, 2
 S2M_LOOP_NONE, S2M_LOOP_ALREADY_CLOSED, S2M_LOOP_TOO_FEW_POINTS, S2M_LOOP_REJECTED, S2M_LOOP_ACCEPTED = 0, 1, 2, 3, 4
 S2M_LOOP_PENDING = 5                                     # a launched closure whose ICP is still queued or running
+S2M_LOOP_MAX_CANDIDATES = 8                              # candidates of one verification: the slots of the device loop
 S2M_DEBUG_PREP_READ, S2M_DEBUG_PREP_NEW, S2M_DEBUG_PREP_LEGACY = -1, 0, 1   # chains of s2m_debug_scan_prep (liorf_s2m_debug.h)
 S2M_ICP_RANGE = 8                                        # iterations the device loop queues at a time (liorf_s2m_debug.h)
 S2M_WARN_LEAF_TOO_SMALL = 1
@@ -327,6 +330,13 @@ def load_library(path: str | None = None) -> C.CDLL:
     L.s2m_loop_closure_rs_launch.argtypes = L.s2m_loop_closure_rs.argtypes
     L.s2m_loop_poll.argtypes = [vp, C.POINTER(LoopResult)]
     L.s2m_loop_collect.argtypes = [vp, C.POINTER(LoopResult)]
+    L.s2m_loop_verify_check_args.argtypes = [C.c_int32, C.c_int32, i32p, C.c_int32, C.c_int32, C.POINTER(LoopParams)]
+    L.s2m_loop_verify_launch.argtypes = [vp, C.c_int32, i32p, C.c_int32, C.c_int32, C.POINTER(LoopParams), C.POINTER(LoopResult), i32p]
+    L.s2m_loop_verify.argtypes = L.s2m_loop_verify_launch.argtypes
+    L.s2m_loop_verify_poll.argtypes = [vp, C.POINTER(LoopResult), C.c_int32, i32p, i32p]
+    L.s2m_loop_verify_collect.argtypes = L.s2m_loop_verify_poll.argtypes
+    L.s2m_debug_icp_align_many_device.argtypes = [vp, vp, C.c_size_t, C.POINTER(C.c_void_p), szp, C.c_int32, C.c_size_t, C.POINTER(IcpParams),
+                                                  C.POINTER(IcpResult)]
     L.s2m_debug_icp_nearest.argtypes = [vp, vp, C.c_size_t, vp, C.c_size_t, C.c_size_t, C.c_int32, vp, C.POINTER(C.c_int32)]
     L.s2m_debug_icp_time_nearest.argtypes = [vp, vp, C.c_size_t, vp, C.c_size_t, C.c_size_t, C.c_int32, C.c_int32, vp, C.POINTER(C.c_int32), fp, fp]
     L.s2m_debug_icp_align_device.argtypes = [vp, vp, C.c_size_t, vp, C.c_size_t, C.c_size_t, C.POINTER(IcpParams), C.POINTER(IcpResult)]
@@ -1242,6 +1252,73 @@ class MapOptimizationS2M:
         self._check(self.lib.s2m_loop_collect(self.h, C.byref(r)), "s2m_loop_collect")
         return r
 
+    # -- verification: key_cur against several candidates, aligned in lockstep ----------------------------------
+    def _verify_launch(self, fn, what, key_cur, key_pre, base_key, params):
+        keys = (C.c_int32 * max(len(key_pre), 1))(*[int(k) for k in key_pre])
+        recs = (LoopResult * S2M_LOOP_MAX_CANDIDATES)()
+        best = C.c_int32(-1)
+        pp = C.byref(params) if params is not None else None
+        self._check(fn(self.h, int(key_cur), keys, len(key_pre), int(base_key), pp, recs, C.byref(best)), what)
+        return [_copy_struct(recs[i]) for i in range(len(key_pre))], best.value
+
+    def loopVerify(self, key_cur: int, key_pre, base_key: int = -1, params: LoopParams | None = None):
+        """s2m_loop_verify: (records, best). records[i] is loopAlign(key_cur, key_pre[i], base_key) on a handle whose container does
+        not hold key_cur; best is the position of the accepted record with the least (fitness, position), or -1. Only that pair
+        goes into the container."""
+        return self._verify_launch(self.lib.s2m_loop_verify, "s2m_loop_verify", key_cur, key_pre, base_key, params)
+
+    def loopVerifyLaunch(self, key_cur: int, key_pre, base_key: int = -1, params: LoopParams | None = None):
+        """s2m_loop_verify_launch: (early records, -1). Candidates that passed the gates carry S2M_LOOP_PENDING; if none did the
+        records are final and nothing is pending."""
+        return self._verify_launch(self.lib.s2m_loop_verify_launch, "s2m_loop_verify_launch", key_cur, key_pre, base_key, params)
+
+    def _verify_poll(self, fn, what):
+        recs = (LoopResult * S2M_LOOP_MAX_CANDIDATES)()
+        n, best = C.c_int32(0), C.c_int32(-1)
+        self._check(fn(self.h, recs, S2M_LOOP_MAX_CANDIDATES, C.byref(n), C.byref(best)), what)
+        return [_copy_struct(recs[i]) for i in range(n.value)], best.value
+
+    def loopVerifyPoll(self):
+        """s2m_loop_verify_poll: never waits for the device. (records, best): pending records, the final ones, or ([], -1) with
+        nothing pending."""
+        return self._verify_poll(self.lib.s2m_loop_verify_poll, "s2m_loop_verify_poll")
+
+    def loopVerifyCollect(self):
+        """s2m_loop_verify_collect: loopVerifyPoll() with waits - the final records of the pending verification."""
+        return self._verify_poll(self.lib.s2m_loop_verify_collect, "s2m_loop_verify_collect")
+
+    def performSCLoopClosureVerified(self, top_k: int = 4, params: LoopParams | None = None, **query):
+        """performSCLoopClosure() on the place query: the top_k <= S2M_LOOP_MAX_CANDIDATES hits of scQueryKey for the newest key
+        (keyword arguments go to the query) verified in lockstep, SC form (base_key 0). The hits come ordered by descriptor
+        distance; the verification re-ranks them by fitness. Returns (records, best, hits)."""
+        n = self.kfSize()
+        if n <= 0:
+            return [], -1, np.zeros(0, SC_HIT_DTYPE)
+        hits = self.scQueryKey(n - 1, top_k=int(top_k), **query)
+        hits = hits[hits["key"] != n - 1][:S2M_LOOP_MAX_CANDIDATES]
+        if len(hits) == 0:
+            return [], -1, hits
+        recs, best = self.loopVerify(n - 1, [int(k) for k in hits["key"]], 0, params)
+        return recs, best, hits
+
+    def debugIcpAlignManyDevice(self, cureKeyframeCloud, prevKeyframeClouds, **params):
+        """s2m_debug_icp_align_many_device: one source against several targets by the slotted device loop (no size gate): a list of
+        (T 4x4, hasConverged, getFitnessScore, iterations), one per target."""
+        a, na, st = _records(cureKeyframeCloud)
+        tg = [_records(t) for t in prevKeyframeClouds]
+        if any(t[2] != st for t in tg):
+            raise ValueError("all clouds must share one record stride")
+        p = IcpParams()
+        self.lib.s2m_icp_default_params(C.byref(p))
+        for k, v in params.items():
+            setattr(p, k, v)
+        ptrs = (C.c_void_p * max(len(tg), 1))(*[t[0].ctypes.data for t in tg])
+        ns = (C.c_size_t * max(len(tg), 1))(*[t[1] for t in tg])
+        out = (IcpResult * max(len(tg), 1))()
+        self._check(self.lib.s2m_debug_icp_align_many_device(self.h, a.ctypes.data, na, ptrs, ns, len(tg), st, C.byref(p), out),
+                    "s2m_debug_icp_align_many_device")
+        return [(np.array(r.T, np.float32).reshape(4, 4), bool(r.converged), r.fitness_score, r.iterations) for r in out[:len(tg)]]
+
     def debugIcpNearest(self, src, tgt, mode: int, reps: int = 0):
         """s2m_debug_icp_nearest / s2m_debug_icp_time_nearest: (keys uint64 per source point, n_fallback[, us_build, us_search]);
         mode 0 = k_icp_nn, mode 1 = the grid search with its fallback."""
@@ -1361,6 +1438,27 @@ def default_sc_query_params(**kw) -> ScQueryParams:
             raise AttributeError(k)
         setattr(p, k, v)
     return p
+
+
+def _copy_struct(s):
+    """A ctypes structure of its own (an element of a ctypes array is a view into the array)."""
+    out = type(s)()
+    C.memmove(C.byref(out), C.byref(s), C.sizeof(s))
+    return out
+
+
+def loop_verify_check_args(n_stored: int, key_cur: int, key_pre, base_key: int = -1, params: "LoopParams | None" = None, n_cand=None) -> int:
+    """s2m_loop_verify_check_args (host only, no GPU): the status code. key_pre=None passes a null pointer; n_cand defaults to
+    len(key_pre)."""
+    keys = None if key_pre is None else (C.c_int32 * max(len(key_pre), 1))(*[int(k) for k in key_pre])
+    n = n_cand if n_cand is not None else (0 if key_pre is None else len(key_pre))
+    return load_library().s2m_loop_verify_check_args(n_stored, key_cur, keys, n, base_key, None if params is None else C.byref(params))
+
+
+def loop_verify_best(records) -> int:
+    """The model of *best: the position of the S2M_LOOP_ACCEPTED record with the least (icp.fitness_score, position), or -1."""
+    ranked = sorted((r.icp.fitness_score, i) for i, r in enumerate(records) if r.status == S2M_LOOP_ACCEPTED)
+    return ranked[0][1] if ranked else -1
 
 
 def sc_query_check_args(n_stored: int, params: "ScQueryParams | None") -> int:

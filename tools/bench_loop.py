@@ -25,6 +25,13 @@ search radius 15 m, search_num 25, ICP leaf 0.5, fitness 0.3, time window 30 s. 
                          k_icp_nn against the grid at several cell edges and shell caps, with the grid's build time and n_fallback
     registration_ms      (d) the early-exit registration of bench.py's scans (set_scan + optimize on host records) on this
                          handle, with and without a closure pending
+  python tools/bench_loop.py --verify                  only profiles/loop_verify_bench_line.json (--verify-out): on the same stores the
+                                                       K = 1, 2, 4, 8 nearest of the RS detector's radius candidates of the last key,
+    verify_collect_ms    (a) s2m_loop_verify_launch to the result of s2m_loop_verify_collect: the K alignments in lockstep
+    held_ms              (b) time the handle is held: the launch plus every s2m_loop_verify_poll, polled every --poll-us microseconds
+    sequential_ms        (c) the same K through K s2m_loop_align_launch + s2m_loop_collect pairs one after the other - the baseline;
+                         (a) and (c) take turns in one process after warm-up, medians of at least 10 repetitions, with (c)'s
+                         min-max spread; meets_bar: (a) is below (c) by more than that spread (K = 1: not above it by more)
   python tools/bench_loop.py --kernel-stats stats.csv  folds the k_loop_detect* and k_icp* rows of a rocprofv3
                                                        --kernel-trace --stats run into the JSON line
 """
@@ -163,8 +170,107 @@ def _async_row(eng, s2m, a, time_cur, rej, sync_ms, kc, kp, scans):
     return rows
 
 
+def _verify_row(eng, s2m, a, stored, times, rej):
+    """K candidates verified in lockstep against the same K through sequential launch + collect pairs (fitness -1: every
+    alignment runs to its end and is rejected, so the container stays empty and every repetition does the whole work)."""
+    lib, h = eng.lib, eng.h
+    n = len(times)
+    kc = n - 1
+    d = np.linalg.norm(stored[:, :3].astype(np.float64) - stored[kc, :3].astype(np.float64), axis=1)
+    near = [int(k) for k in np.argsort(d, kind="stable") if k != kc and d[k] <= 15.0 and abs(times[k] - times[kc]) > 30.0]
+    recs = (s2m.LoopResult * s2m.S2M_LOOP_MAX_CANDIDATES)()
+    one = s2m.LoopResult()
+    nn, best = C.c_int32(0), C.c_int32(-1)
+    pending, rejected = s2m.S2M_LOOP_PENDING, s2m.S2M_LOOP_REJECTED
+    row = {"radius_candidates": len(near), "poll_us": a.poll_us, "K": {}}
+
+    def lockstep(keys, poll_s):
+        K = len(keys)
+        t0 = time.perf_counter()
+        rc = lib.s2m_loop_verify_launch(h, kc, keys, K, -1, C.byref(rej), recs, C.byref(best))
+        held = time.perf_counter() - t0
+        assert rc == 0 and all(recs[i].status == pending for i in range(K)), (rc, [recs[i].status for i in range(K)])
+        if poll_s is None:
+            rc = lib.s2m_loop_verify_collect(h, recs, K, C.byref(nn), C.byref(best))
+            held = time.perf_counter() - t0
+        else:
+            while recs[0].status == pending:
+                time.sleep(poll_s)
+                p0 = time.perf_counter()
+                rc = lib.s2m_loop_verify_poll(h, recs, K, C.byref(nn), C.byref(best))
+                held += time.perf_counter() - p0
+                assert rc == 0
+        assert rc == 0 and nn.value == K and best.value == -1 and all(recs[i].status == rejected for i in range(K))
+        return time.perf_counter() - t0, held
+
+    def sequence(keys):
+        t0 = time.perf_counter()
+        for k in keys:
+            rc = lib.s2m_loop_align_launch(h, kc, k, -1, C.byref(rej), C.byref(one))
+            assert rc == 0 and one.status == pending, (rc, one.status)
+            rc = lib.s2m_loop_collect(h, C.byref(one))
+            assert rc == 0 and one.status == rejected
+        return time.perf_counter() - t0
+
+    for K in (1, 2, 4, 8):
+        if K > len(near):
+            break
+        cand = near[:K]
+        keys = (C.c_int32 * K)(*cand)
+        for _ in range(a.warmup):
+            lockstep(keys, None); sequence(cand)
+        ta, tc = [], []
+        for _ in range(max(a.reps, 10)):                     # (a) and (c) take turns
+            ta.append(lockstep(keys, None)[0]); tc.append(sequence(cand))
+        paced = [lockstep(keys, a.poll_us * 1e-6) for _ in range(max(a.reps, 10))]
+        ms = lambda v: round(1e3 * float(v), 4)
+        r = {"candidates": cand, "iterations": [recs[i].icp.iterations for i in range(K)], "n_prev": [recs[i].n_prev for i in range(K)],
+             "n_cur": recs[0].n_cur,
+             "verify_collect_ms": ms(np.median(ta)), "verify_collect_min_ms": ms(min(ta)), "verify_collect_max_ms": ms(max(ta)),
+             "held_ms": ms(np.median([p[1] for p in paced])), "paced_latency_ms": ms(np.median([p[0] for p in paced])),
+             "sequential_ms": ms(np.median(tc)), "sequential_min_ms": ms(min(tc)), "sequential_max_ms": ms(max(tc))}
+        r["sequential_spread_ms"] = round(r["sequential_max_ms"] - r["sequential_min_ms"], 4)
+        r["saved_ms"] = round(r["sequential_ms"] - r["verify_collect_ms"], 4)
+        # K >= 2: lockstep below the sequence by more than the sequence's own spread; K = 1: not slower by more than that spread
+        r["meets_bar"] = bool(r["saved_ms"] > r["sequential_spread_ms"]) if K > 1 else bool(-r["saved_ms"] <= r["sequential_spread_ms"])
+        row["K"][str(K)] = r
+    return row
+
+
+def _verify_main(a, s2m, sizes):
+    out = {"workload": "tools/bench_loop.py --verify: the revisit of the synchronous line; the K nearest of the RS detector's radius "
+                       "candidates (R 15 m, 30 s) of the last key verified in lockstep (s2m_loop_verify_launch + _collect) against the same "
+                       "K through sequential s2m_loop_align_launch + s2m_loop_collect pairs; search_num 25, leaf 0.5, fitness -1",
+           "reps": max(a.reps, 10), "warmup": a.warmup, "sizes": {}}
+    big = None
+    for n in sizes:
+        true = _true_poses(n)
+        if big is None:
+            big = _clouds([true[k] for k in range(N_BIG)] + [true[-1]])
+            small = big[1][:SMALL_PTS].copy()
+        stored = true.copy()
+        stored[-1] += DRIFT
+        stored = stored.astype(np.float32)
+        times = np.arange(n, dtype=np.float64)
+        eng = s2m.MapOptimizationS2M()
+        for k in range(n):
+            eng.saveKeyFrame(stored[k], times[k], big[k] if k < N_BIG else (big[-1] if k == n - 1 else small))
+        print(f"{n} keys stored", file=sys.stderr, flush=True)
+        rej = s2m.default_loop_params(search_radius=15.0, search_num=25, icp_leaf=0.5, fitness_score=-1.0)
+        out["sizes"][str(n)] = _verify_row(eng, s2m, a, stored, times, rej)
+        eng.close()
+    out["note"] = ("wall clock on the host, medians of (a) lockstep and (c) sequence taken in turns in one process after warm-up; "
+                   "held_ms: launch plus polls every poll_us; meets_bar: saved_ms > the sequence's own min-max spread (K = 1: not slower "
+                   "than the single launch + collect by more than that spread)")
+    print(json.dumps(out))
+    with open(a.verify_out, "w") as f:
+        f.write(json.dumps(out) + "\n")
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser()
+    ap.add_argument("--verify", action="store_true", help="measure the lockstep verification against sequential closures, and nothing else")
+    ap.add_argument("--verify-out", default=os.path.join(ROOT, "profiles", "loop_verify_bench_line.json"))
     ap.add_argument("--sizes", default="5000,50000")
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--reps", type=int, default=10)
@@ -183,6 +289,8 @@ def main(argv=None):
         scans = (synth.to_xyzi(cfgs[0]["map"]), [(synth.to_xyzi(c["scan"]), c["pose_init"]) for c in cfgs])
 
     sizes = [int(s) for s in a.sizes.split(",")]
+    if a.verify:
+        return _verify_main(a, s2m, sizes)
     out = {"workload": "revisit: 30 000-point frames at keys 0..27 and the last key, 1 000 points elsewhere; R 15, search_num 25, "
                        "leaf 0.5, fitness 0.3", "sizes": {}}
     big = None
