@@ -3,7 +3,6 @@
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
-#include <cfloat>
 #include <cstring>
 
 #include "s2m_context.hpp"
@@ -22,15 +21,14 @@ static_assert(S2M_LOOP_MAX_CANDIDATES == kIcpMaxSlots, "include/liorf_s2m.h stat
 
 int s2m::host::loop_busy(s2m_context* h)
 {
-    return h->loop.pending ? fail(h, S2M_ERR_BUSY, "a launched loop closure is pending: s2m_loop_poll / s2m_loop_collect it first") : S2M_OK;
+    return h->loop.pending != s2m_context::LoopClosure::kNone ? fail(h, S2M_ERR_BUSY, "a launched loop closure is pending: s2m_loop_poll / s2m_loop_collect it first") : S2M_OK;
 }
 
 void s2m::host::loop_drop_pending(s2m_context* h, bool destroy)
 {
     if (h->loop.stream) (void)hipStreamSynchronize(h->loop.stream);
     if (h->loop.icp) icp_dev_cancel(h->loop.icp);
-    h->loop.pending = false;
-    h->loop.ver_n = 0;
+    h->loop.pending = s2m_context::LoopClosure::kNone;
     if (!destroy) return;
     if (h->loop.ev_submaps) (void)hipEventDestroy(h->loop.ev_submaps);
     if (h->loop.stream) (void)hipStreamDestroy(h->loop.stream);
@@ -65,6 +63,17 @@ IcpTuning loop_tuning(const s2m_context* h, float leaf)
     return t;
 }
 
+// the caller's ICP parameters (null: the defaults), validated
+int icp_params_in(s2m_context* h, const s2m_icp_params* p, IcpParams* ip)
+{
+    s2m_icp_params prm;
+    if (p) prm = *p; else s2m_icp_default_params(&prm);
+    if (!(prm.max_correspondence_distance > 0.0) || prm.max_iterations < 1)
+        return fail(h, S2M_ERR_INVALID_ARG, "ICP needs a positive correspondence distance and at least one iteration");
+    *ip = IcpParams{ prm.max_correspondence_distance, prm.max_iterations, prm.transformation_epsilon, prm.euclidean_fitness_epsilon };
+    return S2M_OK;
+}
+
 }  // namespace
 
 // ---- section 8(f) row F4: ICP loop-closure alignment -----------------------------------------------
@@ -87,14 +96,11 @@ int s2m_icp_align(s2m_handle h, const void* src, size_t n_src, const void* tgt, 
     if ((rc = check_records(h, tgt, n_tgt, stride_bytes))) return rc;
     if (!out) return S2M_ERR_INVALID_ARG;
     if ((rc = loop_busy(h))) return rc;
-    s2m_icp_params prm;
-    if (p) prm = *p; else s2m_icp_default_params(&prm);
-    if (!(prm.max_correspondence_distance > 0.0) || prm.max_iterations < 1)
-        return fail(h, S2M_ERR_INVALID_ARG, "ICP needs a positive correspondence distance and at least one iteration");
+    IcpParams ip;
+    if ((rc = icp_params_in(h, p, &ip))) return rc;
     S2M_HIP(h, hipSetDevice(h->device));
     if (n_src && (rc = stage_host_records(h, h->loop.icp_src, src, n_src * stride_bytes))) return rc;
     if (n_tgt && (rc = stage_host_records(h, h->loop.icp_tgt, tgt, n_tgt * stride_bytes))) return rc;
-    IcpParams ip{ prm.max_correspondence_distance, prm.max_iterations, prm.transformation_epsilon, prm.euclidean_fitness_epsilon };
     IcpResult r;
     hipError_t e = icp_align(h->loop.icp, h->stream, h->loop.icp_src.as<unsigned char>(), n_src, h->loop.icp_tgt.as<unsigned char>(), n_tgt,
                              stride_bytes, ip, &r);
@@ -155,21 +161,32 @@ int loop_submap(s2m_context* h, int32_t key, int32_t search_num, int32_t loop_in
     return voxel_into(h, h->loop.xf.as<unsigned char>(), tab.total, kDsStride, leaf, dst, res);   // (waits for the counts)
 }
 
-// the container test, both submaps and the size gate (:565-566, :641-661). *decided: `out` is final (ALREADY_CLOSED, TOO_FEW_POINTS)
-int loop_gates(s2m_context* h, int32_t key_cur, int32_t key_pre, int32_t base_key, const s2m_loop_params& prm, s2m_loop_result* out, bool* decided)
+// The gates of one key against n_cand candidates (:565-566, :641-661): the container test, the source submap once, then a target
+// submap (loop.target(i)) and the size gate per candidate. rec: n_cand records as loop_result_init leaves them; one that the gates
+// decide is final (ALREADY_CLOSED, TOO_FEW_POINTS), the others keep S2M_LOOP_NONE and are what *open counts.
+int loop_gates(s2m_context* h, int32_t key_cur, const int32_t* key_pre, int32_t n_cand, int32_t base_key, const s2m_loop_params& prm,
+               s2m_loop_result* rec, int32_t* open)
 {
-    *decided = true;
-    out->key_cur = key_cur;
-    out->key_pre = key_pre;
-    if (h->loop.index.count(key_cur)) { out->status = S2M_LOOP_ALREADY_CLOSED; return S2M_OK; }
-    VoxResult rc_cur, rc_prev;
-    int rc = loop_submap(h, key_cur, 0, base_key, prm.icp_leaf, h->loop.cur, &rc_cur);
+    s2m_context::LoopClosure& L = h->loop;
+    *open = 0;
+    const bool closed = L.index.count(key_cur) != 0;
+    for (int32_t i = 0; i < n_cand; i++) {
+        rec[i].key_cur = key_cur;
+        rec[i].key_pre = key_pre[i];
+        if (closed) rec[i].status = S2M_LOOP_ALREADY_CLOSED;
+    }
+    if (closed) return S2M_OK;
+    VoxResult rc_cur;
+    int rc = loop_submap(h, key_cur, 0, base_key, prm.icp_leaf, L.cur, &rc_cur);
     if (rc) return rc;
-    if ((rc = loop_submap(h, key_pre, prm.search_num, base_key, prm.icp_leaf, h->loop.prev, &rc_prev))) return rc;
-    out->n_cur = (int32_t)rc_cur.n_out;
-    out->n_prev = (int32_t)rc_prev.n_out;
-    if (rc_cur.n_out < 300 || rc_prev.n_out < 1000) { out->status = S2M_LOOP_TOO_FEW_POINTS; return S2M_OK; }
-    *decided = false;
+    for (int32_t i = 0; i < n_cand; i++) {
+        VoxResult rc_prev;
+        if ((rc = loop_submap(h, key_pre[i], prm.search_num, base_key, prm.icp_leaf, L.target(i), &rc_prev))) return rc;
+        rec[i].n_cur = (int32_t)rc_cur.n_out;
+        rec[i].n_prev = (int32_t)rc_prev.n_out;
+        if (rc_cur.n_out < 300 || rc_prev.n_out < 1000) rec[i].status = S2M_LOOP_TOO_FEW_POINTS;
+        else ++*open;
+    }
     return S2M_OK;
 }
 
@@ -190,55 +207,104 @@ void loop_judge(const IcpResult& r, int32_t base_key, float fitness_score, const
     out->status = S2M_LOOP_ACCEPTED;
 }
 
-// loop_judge and the container (:621)
-void loop_finish(s2m_context* h, const IcpResult& r, int32_t base_key, float fitness_score, const float T_cur[12], const float pose_pre[6],
-                 s2m_loop_result* out)
+// the accepted record with the least (icp.fitness_score, position), or -1
+int32_t verify_best(const s2m_loop_result* rec, int32_t n)
 {
-    loop_judge(r, base_key, fitness_score, T_cur, pose_pre, out);
-    if (out->status == S2M_LOOP_ACCEPTED) h->loop.index[out->key_cur] = out->key_pre;   // loopIndexContainer[loopKeyCur] = loopKeyPre
+    int32_t best = -1;
+    for (int32_t i = 0; i < n; i++)
+        if (rec[i].status == S2M_LOOP_ACCEPTED && (best < 0 || rec[i].icp.fitness_score < rec[best].icp.fitness_score)) best = i;
+    return best;
 }
 
 // s2m_icp_align's path on the device submaps: historyKeyframeSearchRadius*2 (a float), 100, 1e-6, 1e-6 (:572-576)
 IcpParams loop_icp_params(const s2m_loop_params& prm) { return IcpParams{ (double)(prm.search_radius * 2.0f), 100, 1e-6, 1e-6 }; }
 
-// the container test, both submaps, the size gate, ICP, the fitness gate and the pose result (:565-621, :641-715)
+// the container test, both submaps, the size gate, ICP, the fitness gate, the pose result and the container (:565-621, :641-715)
 int loop_align_impl(s2m_context* h, int32_t key_cur, int32_t key_pre, int32_t base_key, const s2m_loop_params& prm, s2m_loop_result* out)
 {
-    bool decided;
-    int rc = loop_gates(h, key_cur, key_pre, base_key, prm, out, &decided);
-    if (rc || decided) return rc;
+    int32_t open;
+    int rc = loop_gates(h, key_cur, &key_pre, 1, base_key, prm, out, &open);
+    if (rc || !open) return rc;
     IcpResult r;
-    hipError_t e = icp_align(h->loop.icp, h->stream, h->loop.cur.as<unsigned char>(), (size_t)out->n_cur, h->loop.prev.as<unsigned char>(),
+    hipError_t e = icp_align(h->loop.icp, h->stream, h->loop.cur.as<unsigned char>(), (size_t)out->n_cur, h->loop.target(0).as<unsigned char>(),
                              (size_t)out->n_prev, kDsStride, loop_icp_params(prm), &r);
     if (e != hipSuccess) return fail(h, S2M_ERR_HIP, "loop ICP alignment", e);
     S2M_HIP(h, hipStreamSynchronize(h->stream));
-    loop_finish(h, r, base_key, prm.fitness_score, h->kf.frame[(size_t)key_cur].T, &h->kf.pose[6 * (size_t)key_pre], out);
+    loop_judge(r, base_key, prm.fitness_score, h->kf.frame[(size_t)key_cur].T, &h->kf.pose[6 * (size_t)key_pre], out);
+    if (out->status == S2M_LOOP_ACCEPTED) h->loop.index[key_cur] = key_pre;               // loopIndexContainer[loopKeyCur] = loopKeyPre (:621)
     return S2M_OK;
 }
 
-// the launched form: the same gates, then the whole ICP queued on the loop stream behind the submap writes
-int loop_launch_impl(s2m_context* h, int32_t key_cur, int32_t key_pre, int32_t base_key, const s2m_loop_params& prm, s2m_loop_result* early)
+// The launched form: the same gates, then the alignments of the candidates that are left queued in lockstep on the loop stream,
+// behind the submap writes. rec: n_cand records; who: the family of the call, which may poll the closure and names it in an error.
+int loop_launch(s2m_context* h, int32_t key_cur, const int32_t* key_pre, int32_t n_cand, int32_t base_key, const s2m_loop_params& prm,
+                s2m_loop_result* rec, s2m_context::LoopClosure::Pending who)
 {
-    bool decided;
-    int rc = loop_gates(h, key_cur, key_pre, base_key, prm, early, &decided);
-    if (rc || decided) return rc;
-    if ((rc = loop_stream(h))) return rc;
-    S2M_HIP(h, hipEventRecord(h->loop.ev_submaps, h->stream));
-    S2M_HIP(h, hipStreamWaitEvent(h->loop.stream, h->loop.ev_submaps, 0));
-    hipError_t e = icp_dev_begin(h->loop.icp, h->loop.stream, h->loop.cur.as<unsigned char>(), (size_t)early->n_cur,
-                                 h->loop.prev.as<unsigned char>(), (size_t)early->n_prev, kDsStride, loop_icp_params(prm),
-                                 loop_tuning(h, prm.icp_leaf));
-    if (e != hipSuccess) {
-        (void)hipStreamSynchronize(h->loop.stream);         // (whatever was queued before the failure ends before the buffers are used again)
-        return fail(h, S2M_ERR_HIP, "loop ICP launch", e);
+    s2m_context::LoopClosure& L = h->loop;
+    int32_t slots;
+    int rc = loop_gates(h, key_cur, key_pre, n_cand, base_key, prm, rec, &slots);
+    if (rc || !slots) return rc;
+    const unsigned char* d_tgt[S2M_LOOP_MAX_CANDIDATES];
+    size_t n_tgt[S2M_LOOP_MAX_CANDIDATES];
+    slots = 0;
+    for (int32_t i = 0; i < n_cand; i++) {
+        L.pend_slot[i] = -1;
+        if (rec[i].status != S2M_LOOP_NONE) continue;
+        d_tgt[slots] = L.target(i).as<unsigned char>();
+        n_tgt[slots] = (size_t)rec[i].n_prev;
+        L.pend_slot[i] = slots++;
     }
-    early->status = S2M_LOOP_PENDING;
-    h->loop.pend = *early;
-    h->loop.pend_fitness = prm.fitness_score;
-    h->loop.pend_base_key = base_key;
-    memcpy(h->loop.snap_T, h->kf.frame[(size_t)key_cur].T, sizeof(h->loop.snap_T));          // as the reference copies copy_cloudKeyPoses6D
-    memcpy(h->loop.snap_pose_pre, &h->kf.pose[6 * (size_t)key_pre], sizeof(h->loop.snap_pose_pre));
-    h->loop.pending = true;
+    if ((rc = loop_stream(h))) return rc;
+    S2M_HIP(h, hipEventRecord(L.ev_submaps, h->stream));
+    S2M_HIP(h, hipStreamWaitEvent(L.stream, L.ev_submaps, 0));
+    const hipError_t e = icp_dev_begin(L.icp, L.stream, L.cur.as<unsigned char>(), (size_t)rec[0].n_cur, d_tgt, n_tgt, slots, kDsStride,
+                                       loop_icp_params(prm), loop_tuning(h, prm.icp_leaf));
+    if (e != hipSuccess) {
+        (void)hipStreamSynchronize(L.stream);               // (whatever was queued before the failure ends before the buffers are used again)
+        return fail(h, S2M_ERR_HIP, who == L.kSingle ? "loop ICP launch" : "loop verification launch", e);
+    }
+    for (int32_t i = 0; i < n_cand; i++) {
+        if (L.pend_slot[i] >= 0) rec[i].status = S2M_LOOP_PENDING;
+        L.pend_rec[i] = rec[i];
+        memcpy(L.pend_pose_pre[i], &h->kf.pose[6 * (size_t)key_pre[i]], sizeof(L.pend_pose_pre[i]));
+    }
+    L.pend_n = n_cand;
+    L.pend_fitness = prm.fitness_score;
+    L.pend_base_key = base_key;
+    memcpy(L.snap_T, h->kf.frame[(size_t)key_cur].T, sizeof(L.snap_T));
+    L.pending = who;
+    return S2M_OK;
+}
+
+int loop_launch_single(s2m_context* h, int32_t key_cur, int32_t key_pre, int32_t base_key, const s2m_loop_params& prm, s2m_loop_result* early)
+{
+    return loop_launch(h, key_cur, &key_pre, 1, base_key, prm, early, s2m_context::LoopClosure::kSingle);
+}
+
+// A step of the pending closure: the device loop advanced (wait: to its end). Once it has ended the records that took a slot are
+// judged, the accepted one with the least fitness - of one record, that record if it was accepted - goes into the container (only
+// the winner is a closure, :621), *best names it and nothing is pending any more. The records are loop.pend_rec[0 .. pend_n).
+int loop_advance(s2m_context* h, bool wait, int32_t* best)
+{
+    s2m_context::LoopClosure& L = h->loop;
+    S2M_HIP(h, hipSetDevice(h->device));
+    bool done = false;
+    IcpResult r[S2M_LOOP_MAX_CANDIDATES];
+    const hipError_t e = icp_dev_advance(L.icp, L.stream, wait, &done, r);
+    if (e != hipSuccess) {
+        const char* what = L.pending == L.kSingle ? "loop ICP on the loop stream" : "loop verification on the loop stream";
+        loop_drop_pending(h, false);
+        return fail(h, S2M_ERR_HIP, what, e);
+    }
+    if (!done) return S2M_OK;
+    for (int32_t i = 0; i < L.pend_n; i++) {
+        if (L.pend_slot[i] < 0) continue;
+        L.pend_rec[i].status = S2M_LOOP_NONE;
+        loop_judge(r[L.pend_slot[i]], L.pend_base_key, L.pend_fitness, L.snap_T, L.pend_pose_pre[i], &L.pend_rec[i]);
+    }
+    *best = verify_best(L.pend_rec, L.pend_n);
+    if (*best >= 0) L.index[L.pend_rec[*best].key_cur] = L.pend_rec[*best].key_pre;
+    L.pending = L.kNone;
     return S2M_OK;
 }
 
@@ -246,23 +312,15 @@ int loop_poll_impl(s2m_context* h, s2m_loop_result* out, bool wait)
 {
     if (!h) return S2M_ERR_INVALID_ARG;
     if (!out) return fail(h, S2M_ERR_INVALID_ARG, "null loop result");
-    if (h->loop.pending && h->loop.ver_n > 0)
+    s2m_context::LoopClosure& L = h->loop;
+    if (L.pending == L.kVerify)
         return fail(h, S2M_ERR_BUSY, "a launched verification is pending: s2m_loop_verify_poll / s2m_loop_verify_collect it");
     loop_result_init(out);
-    if (!h->loop.pending) return S2M_OK;                    // S2M_LOOP_NONE, keys -1
-    S2M_HIP(h, hipSetDevice(h->device));
-    bool done = false;
-    IcpResult r;
-    const hipError_t e = icp_dev_advance(h->loop.icp, h->loop.stream, wait, &done, &r);
-    if (e != hipSuccess) {
-        loop_drop_pending(h, false);
-        return fail(h, S2M_ERR_HIP, "loop ICP on the loop stream", e);
-    }
-    *out = h->loop.pend;
-    if (!done) return S2M_OK;                               // S2M_LOOP_PENDING
-    h->loop.pending = false;
-    out->status = S2M_LOOP_NONE;
-    loop_finish(h, r, h->loop.pend_base_key, h->loop.pend_fitness, h->loop.snap_T, h->loop.snap_pose_pre, out);
+    if (L.pending == L.kNone) return S2M_OK;                // S2M_LOOP_NONE, keys -1
+    int32_t best;
+    const int rc = loop_advance(h, wait, &best);
+    if (rc) return rc;
+    *out = L.pend_rec[0];                                   // S2M_LOOP_PENDING, or the result
     return S2M_OK;
 }
 
@@ -356,12 +414,12 @@ int s2m_loop_closure_rs(s2m_handle h, double time_cur, const s2m_loop_params* p,
 
 int s2m_loop_align_launch(s2m_handle h, int32_t key_cur, int32_t key_pre, int32_t base_key, const s2m_loop_params* p, s2m_loop_result* early)
 {
-    return loop_align_front(h, key_cur, key_pre, base_key, p, early, loop_launch_impl);
+    return loop_align_front(h, key_cur, key_pre, base_key, p, early, loop_launch_single);
 }
 
 int s2m_loop_closure_rs_launch(s2m_handle h, double time_cur, const s2m_loop_params* p, s2m_loop_result* early)
 {
-    return loop_closure_rs_front(h, time_cur, p, early, loop_launch_impl);
+    return loop_closure_rs_front(h, time_cur, p, early, loop_launch_single);
 }
 
 int s2m_loop_poll(s2m_handle h, s2m_loop_result* out) { return loop_poll_impl(h, out, false); }
@@ -393,68 +451,6 @@ int verify_args(s2m_context* h, size_t N, int32_t key_cur, const int32_t* key_pr
     return S2M_OK;
 }
 
-// the accepted record with the least (icp.fitness_score, position), or -1
-int32_t verify_best(const s2m_loop_result* rec, int32_t n)
-{
-    int32_t best = -1;
-    for (int32_t i = 0; i < n; i++)
-        if (rec[i].status == S2M_LOOP_ACCEPTED && (best < 0 || rec[i].icp.fitness_score < rec[best].icp.fitness_score)) best = i;
-    return best;
-}
-
-// the container test, the source submap once, a target submap per candidate with the size gates of the single closure, then
-// the alignments of the candidates that are left queued in lockstep on the loop stream. rec: n_cand records.
-int verify_launch_impl(s2m_context* h, int32_t key_cur, const int32_t* key_pre, int32_t n_cand, int32_t base_key, const s2m_loop_params& prm,
-                       s2m_loop_result* rec)
-{
-    s2m_context::LoopClosure& L = h->loop;
-    for (int32_t i = 0; i < n_cand; i++) { rec[i].key_cur = key_cur; rec[i].key_pre = key_pre[i]; }
-    if (L.index.count(key_cur)) {
-        for (int32_t i = 0; i < n_cand; i++) rec[i].status = S2M_LOOP_ALREADY_CLOSED;
-        return S2M_OK;
-    }
-    VoxResult rc_cur;
-    int rc = loop_submap(h, key_cur, 0, base_key, prm.icp_leaf, L.cur, &rc_cur);
-    if (rc) return rc;
-    const unsigned char* d_tgt[S2M_LOOP_MAX_CANDIDATES];
-    size_t n_tgt[S2M_LOOP_MAX_CANDIDATES];
-    int32_t slot_of[S2M_LOOP_MAX_CANDIDATES];
-    int32_t slots = 0;
-    for (int32_t i = 0; i < n_cand; i++) {
-        VoxResult rc_prev;
-        if ((rc = loop_submap(h, key_pre[i], prm.search_num, base_key, prm.icp_leaf, L.ver_prev[i], &rc_prev))) return rc;
-        rec[i].n_cur = (int32_t)rc_cur.n_out;
-        rec[i].n_prev = (int32_t)rc_prev.n_out;
-        slot_of[i] = -1;
-        if (rc_cur.n_out < 300 || rc_prev.n_out < 1000) { rec[i].status = S2M_LOOP_TOO_FEW_POINTS; continue; }
-        d_tgt[slots] = L.ver_prev[i].as<unsigned char>();
-        n_tgt[slots] = rc_prev.n_out;
-        slot_of[i] = slots++;
-    }
-    if (slots == 0) return S2M_OK;
-    if ((rc = loop_stream(h))) return rc;
-    S2M_HIP(h, hipEventRecord(L.ev_submaps, h->stream));
-    S2M_HIP(h, hipStreamWaitEvent(L.stream, L.ev_submaps, 0));
-    const hipError_t e = icp_dev_begin_many(L.icp, L.stream, L.cur.as<unsigned char>(), rc_cur.n_out, d_tgt, n_tgt, slots, kDsStride,
-                                            loop_icp_params(prm), loop_tuning(h, prm.icp_leaf));
-    if (e != hipSuccess) {
-        (void)hipStreamSynchronize(L.stream);
-        return fail(h, S2M_ERR_HIP, "loop verification launch", e);
-    }
-    for (int32_t i = 0; i < n_cand; i++) {
-        if (slot_of[i] >= 0) rec[i].status = S2M_LOOP_PENDING;
-        L.ver_rec[i] = rec[i];
-        L.ver_slot[i] = slot_of[i];
-        memcpy(L.ver_pose_pre[i], &h->kf.pose[6 * (size_t)key_pre[i]], sizeof(L.ver_pose_pre[i]));
-    }
-    L.ver_n = n_cand; L.ver_slots = slots;
-    L.pend_fitness = prm.fitness_score;
-    L.pend_base_key = base_key;
-    memcpy(L.snap_T, h->kf.frame[(size_t)key_cur].T, sizeof(L.snap_T));
-    L.pending = true;
-    return S2M_OK;
-}
-
 int verify_launch_front(s2m_context* h, int32_t key_cur, const int32_t* key_pre, int32_t n_cand, int32_t base_key, const s2m_loop_params* p,
                         s2m_loop_result* early, int32_t* best)
 {
@@ -469,7 +465,7 @@ int verify_launch_front(s2m_context* h, int32_t key_cur, const int32_t* key_pre,
     for (int32_t i = 0; i < n_cand; i++) loop_result_init(&early[i]);
     if (empty) return S2M_OK;
     S2M_HIP(h, hipSetDevice(h->device));
-    return verify_launch_impl(h, key_cur, key_pre, n_cand, base_key, prm, early);
+    return loop_launch(h, key_cur, key_pre, n_cand, base_key, prm, early, s2m_context::LoopClosure::kVerify);
 }
 
 int verify_poll_impl(s2m_context* h, s2m_loop_result* out, int32_t cap, int32_t* n_out, int32_t* best, bool wait)
@@ -477,32 +473,15 @@ int verify_poll_impl(s2m_context* h, s2m_loop_result* out, int32_t cap, int32_t*
     if (!h) return S2M_ERR_INVALID_ARG;
     if (!n_out || !best || cap < 0 || (cap > 0 && !out)) return fail(h, S2M_ERR_INVALID_ARG, "bad loop result buffer");
     s2m_context::LoopClosure& L = h->loop;
-    if (L.pending && L.ver_n == 0)
+    if (L.pending == L.kSingle)
         return fail(h, S2M_ERR_BUSY, "a launched loop closure is pending: s2m_loop_poll / s2m_loop_collect it first");
     *n_out = 0; *best = -1;
-    if (!L.pending) return S2M_OK;
-    S2M_HIP(h, hipSetDevice(h->device));
-    bool done = false;
-    IcpResult r[S2M_LOOP_MAX_CANDIDATES];
-    const hipError_t e = icp_dev_advance_many(L.icp, L.stream, wait, &done, r);
-    if (e != hipSuccess) {
-        loop_drop_pending(h, false);
-        return fail(h, S2M_ERR_HIP, "loop verification on the loop stream", e);
-    }
-    const int32_t n = L.ver_n;
-    if (done) {
-        for (int32_t i = 0; i < n; i++) {
-            if (L.ver_slot[i] < 0) continue;
-            L.ver_rec[i].status = S2M_LOOP_NONE;
-            loop_judge(r[L.ver_slot[i]], L.pend_base_key, L.pend_fitness, L.snap_T, L.ver_pose_pre[i], &L.ver_rec[i]);
-        }
-        *best = verify_best(L.ver_rec, n);
-        if (*best >= 0) L.index[L.ver_rec[*best].key_cur] = L.ver_rec[*best].key_pre;   // only the winner is a closure (:621)
-        L.pending = false;
-        L.ver_n = 0;
-    }
+    if (L.pending == L.kNone) return S2M_OK;
+    const int rc = loop_advance(h, wait, best);
+    if (rc) return rc;
+    const int32_t n = L.pend_n;
     *n_out = n;
-    for (int32_t i = 0; i < std::min(n, cap); i++) out[i] = L.ver_rec[i];
+    for (int32_t i = 0; i < std::min(n, cap); i++) out[i] = L.pend_rec[i];
     if (cap < n) return fail(h, S2M_ERR_CAPACITY, "output buffer too small for the verification's records");
     return S2M_OK;
 }
@@ -537,7 +516,7 @@ int s2m_loop_verify(s2m_handle h, int32_t key_cur, const int32_t* key_pre, int32
                     s2m_loop_result* out, int32_t* best)
 {
     const int rc = verify_launch_front(h, key_cur, key_pre, n_cand, base_key, p, out, best);
-    if (rc || !h->loop.pending) return rc;
+    if (rc || h->loop.pending == s2m_context::LoopClosure::kNone) return rc;
     int32_t n = 0;
     return verify_poll_impl(h, out, n_cand, &n, best, true);
 }
@@ -559,6 +538,46 @@ int debug_stage(s2m_context* h, const void* src, size_t n_src, const void* tgt, 
     if ((rc = ensure(h, h->loop.icp_src, n_src * stride)) || (rc = ensure(h, h->loop.icp_tgt, n_tgt * stride))) return rc;
     if (n_src) S2M_HIP(h, hipMemcpyAsync(h->loop.icp_src.p, src, n_src * stride, hipMemcpyHostToDevice, h->loop.stream));
     if (n_tgt) S2M_HIP(h, hipMemcpyAsync(h->loop.icp_tgt.p, tgt, n_tgt * stride, hipMemcpyHostToDevice, h->loop.stream));
+    return S2M_OK;
+}
+
+// one host source against n_cand host targets through the device loop, waited for: a slot per non-empty target, staged in the
+// closure's target buffers; out: n_cand results (an empty cloud: icp_result_none)
+int debug_align_many(s2m_context* h, const void* src, size_t n_src, const void* const* tgts, const size_t* n_tgts, int32_t n_cand, size_t stride,
+                     const IcpParams& ip, s2m_icp_result* out)
+{
+    int rc = debug_stage(h, src, n_src, nullptr, 0, stride);
+    if (rc) return rc;
+    s2m_context::LoopClosure& L = h->loop;
+    const unsigned char* d_tgt[S2M_LOOP_MAX_CANDIDATES];
+    size_t n_tgt[S2M_LOOP_MAX_CANDIDATES];
+    int slot_of[S2M_LOOP_MAX_CANDIDATES];
+    int slots = 0;
+    for (int32_t i = 0; i < n_cand; i++) {
+        if ((rc = check_records(h, tgts[i], n_tgts[i], stride))) return rc;
+        slot_of[i] = -1;
+        if (!n_src || !n_tgts[i]) continue;
+        if ((rc = ensure(h, L.target(i), n_tgts[i] * stride))) return rc;
+        S2M_HIP(h, hipMemcpyAsync(L.target(i).p, tgts[i], n_tgts[i] * stride, hipMemcpyHostToDevice, L.stream));
+        d_tgt[slots] = L.target(i).as<unsigned char>();
+        n_tgt[slots] = n_tgts[i];
+        slot_of[i] = slots++;
+    }
+    IcpResult r[S2M_LOOP_MAX_CANDIDATES];
+    if (slots) {
+        s2m_loop_params lp;
+        s2m_loop_default_params(&lp);
+        hipError_t e = icp_dev_begin(L.icp, L.stream, L.icp_src.as<unsigned char>(), n_src, d_tgt, n_tgt, slots, stride, ip, loop_tuning(h, lp.icp_leaf));
+        bool done = false;
+        if (e == hipSuccess) e = icp_dev_advance(L.icp, L.stream, true, &done, r);
+        if (e != hipSuccess || !done) {
+            (void)hipStreamSynchronize(L.stream);
+            icp_dev_cancel(L.icp);
+            return fail(h, S2M_ERR_HIP, "ICP device loop", e);
+        }
+    }
+    S2M_HIP(h, hipStreamSynchronize(L.stream));
+    for (int32_t i = 0; i < n_cand; i++) icp_result_out(slot_of[i] >= 0 ? r[slot_of[i]] : icp_result_none(), &out[i]);
     return S2M_OK;
 }
 
@@ -615,32 +634,10 @@ int s2m_debug_icp_align_device(s2m_handle h, const void* src, size_t n_src, cons
 {
     if (!h) return S2M_ERR_INVALID_ARG;
     if (!out) return fail(h, S2M_ERR_INVALID_ARG, "null ICP result");
-    s2m_icp_params prm;
-    if (p) prm = *p; else s2m_icp_default_params(&prm);
-    if (!(prm.max_correspondence_distance > 0.0) || prm.max_iterations < 1)
-        return fail(h, S2M_ERR_INVALID_ARG, "ICP needs a positive correspondence distance and at least one iteration");
-    int rc = debug_stage(h, src, n_src, tgt, n_tgt, stride_bytes);
-    if (rc) return rc;
-    IcpResult r;
-    for (int i = 0; i < 16; i++) r.T[i] = (i % 5 == 0) ? 1.0f : 0.0f;
-    r.converged = 0; r.iterations = 0; r.fitness = DBL_MAX;
-    if (n_src && n_tgt) {
-        s2m_loop_params lp;
-        s2m_loop_default_params(&lp);
-        const IcpParams ip{ prm.max_correspondence_distance, prm.max_iterations, prm.transformation_epsilon, prm.euclidean_fitness_epsilon };
-        hipError_t e = icp_dev_begin(h->loop.icp, h->loop.stream, h->loop.icp_src.as<unsigned char>(), n_src, h->loop.icp_tgt.as<unsigned char>(),
-                                     n_tgt, stride_bytes, ip, loop_tuning(h, lp.icp_leaf));
-        bool done = false;
-        if (e == hipSuccess) e = icp_dev_advance(h->loop.icp, h->loop.stream, true, &done, &r);
-        if (e != hipSuccess || !done) {
-            (void)hipStreamSynchronize(h->loop.stream);
-            icp_dev_cancel(h->loop.icp);
-            return fail(h, S2M_ERR_HIP, "ICP device loop", e);
-        }
-    }
-    S2M_HIP(h, hipStreamSynchronize(h->loop.stream));
-    icp_result_out(r, out);
-    return S2M_OK;
+    IcpParams ip;
+    int rc = icp_params_in(h, p, &ip);
+    if (rc || (rc = check_records(h, src, n_src, stride_bytes)) || (rc = check_records(h, tgt, n_tgt, stride_bytes))) return rc;   // (both before BUSY)
+    return debug_align_many(h, src, n_src, &tgt, &n_tgt, 1, stride_bytes, ip, out);
 }
 
 int s2m_debug_icp_align_many_device(s2m_handle h, const void* src, size_t n_src, const void* const* tgts, const size_t* n_tgts, int32_t n_cand,
@@ -649,48 +646,7 @@ int s2m_debug_icp_align_many_device(s2m_handle h, const void* src, size_t n_src,
     if (!h) return S2M_ERR_INVALID_ARG;
     if (!out || !tgts || !n_tgts || n_cand < 1 || n_cand > S2M_LOOP_MAX_CANDIDATES)
         return fail(h, S2M_ERR_INVALID_ARG, "null ICP result or target list, or not 1 .. S2M_LOOP_MAX_CANDIDATES targets");
-    s2m_icp_params prm;
-    if (p) prm = *p; else s2m_icp_default_params(&prm);
-    if (!(prm.max_correspondence_distance > 0.0) || prm.max_iterations < 1)
-        return fail(h, S2M_ERR_INVALID_ARG, "ICP needs a positive correspondence distance and at least one iteration");
-    int rc = debug_stage(h, src, n_src, nullptr, 0, stride_bytes);
-    if (rc) return rc;
-    s2m_context::LoopClosure& L = h->loop;
-    const unsigned char* d_tgt[S2M_LOOP_MAX_CANDIDATES];
-    size_t n_tgt[S2M_LOOP_MAX_CANDIDATES];
-    int slot_of[S2M_LOOP_MAX_CANDIDATES];
-    int slots = 0;
-    for (int32_t i = 0; i < n_cand; i++) {                  // a slot per non-empty target, staged in the verification's submap buffers
-        if ((rc = check_records(h, tgts[i], n_tgts[i], stride_bytes))) return rc;
-        slot_of[i] = -1;
-        if (!n_src || !n_tgts[i]) continue;
-        if ((rc = ensure(h, L.ver_prev[i], n_tgts[i] * stride_bytes))) return rc;
-        S2M_HIP(h, hipMemcpyAsync(L.ver_prev[i].p, tgts[i], n_tgts[i] * stride_bytes, hipMemcpyHostToDevice, L.stream));
-        d_tgt[slots] = L.ver_prev[i].as<unsigned char>();
-        n_tgt[slots] = n_tgts[i];
-        slot_of[i] = slots++;
-    }
-    IcpResult r[S2M_LOOP_MAX_CANDIDATES];
-    if (slots) {
-        s2m_loop_params lp;
-        s2m_loop_default_params(&lp);
-        const IcpParams ip{ prm.max_correspondence_distance, prm.max_iterations, prm.transformation_epsilon, prm.euclidean_fitness_epsilon };
-        hipError_t e = icp_dev_begin_many(L.icp, L.stream, L.icp_src.as<unsigned char>(), n_src, d_tgt, n_tgt, slots, stride_bytes, ip,
-                                          loop_tuning(h, lp.icp_leaf));
-        bool done = false;
-        if (e == hipSuccess) e = icp_dev_advance_many(L.icp, L.stream, true, &done, r);
-        if (e != hipSuccess || !done) {
-            (void)hipStreamSynchronize(L.stream);
-            icp_dev_cancel(L.icp);
-            return fail(h, S2M_ERR_HIP, "ICP device loop", e);
-        }
-    }
-    S2M_HIP(h, hipStreamSynchronize(L.stream));
-    for (int32_t i = 0; i < n_cand; i++) {
-        IcpResult none;
-        for (int k = 0; k < 16; k++) none.T[k] = (k % 5 == 0) ? 1.0f : 0.0f;
-        none.converged = 0; none.iterations = 0; none.fitness = DBL_MAX;
-        icp_result_out(slot_of[i] >= 0 ? r[slot_of[i]] : none, &out[i]);
-    }
-    return S2M_OK;
+    IcpParams ip;
+    const int rc = icp_params_in(h, p, &ip);
+    return rc ? rc : debug_align_many(h, src, n_src, tgts, n_tgts, n_cand, stride_bytes, ip, out);
 }

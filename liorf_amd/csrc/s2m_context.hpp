@@ -186,31 +186,30 @@ struct __attribute__((visibility("hidden"))) s2m_context {
     } kf;
 
     // loop closure: the ICP alignment (section 8(f) F4) with its staging of host clouds, and against the store loopIndexContainer
-    // (:146), the transformed frames and the two filtered submaps
+    // (:146), the transformed frames, the source submap (cur) and the target submaps: candidate 0's in prev - the only one of the
+    // synchronous and the single launched closure, and where s2m_loop_near_keyframes builds - and candidates 1.. in ver_prev
     struct LoopClosure {
         s2m::IcpWorkspace* icp = nullptr;
         DevBuf icp_src, icp_tgt;
         std::map<int32_t, int32_t> index;
-        DevBuf xf, cur, prev;
-        // the launched closure (s2m_loop_*_launch): the stream its ICP runs on (lowest priority, created at the first launch), the
-        // event on the handle's stream behind the submap writes, and what the result needs from launch time
+        DevBuf xf, cur, prev, ver_prev[S2M_LOOP_MAX_CANDIDATES - 1];
+        DevBuf& target(int i) { return i == 0 ? prev : ver_prev[i - 1]; }
+        // the stream a launched closure's ICP runs on (lowest priority, created at the first launch) and the event on the handle's
+        // stream behind the submap writes
         hipStream_t stream = nullptr;
         hipEvent_t ev_submaps = nullptr;
-        bool pending = false;
-        s2m_loop_result pend{};            // key_cur, key_pre, n_cur, n_prev of the pending closure
+        // The one pending closure: what a launch queued on the loop stream and no poll or collect has brought back yet, and the
+        // family of calls that launched it - s2m_loop_*_launch (kSingle: one candidate) or s2m_loop_verify_launch (kVerify) - which
+        // is the family that may poll it. Its records in the caller's order, the slot of the device loop each one runs in (-1:
+        // decided at launch, it took none), and what the result needs from launch time, as the reference copies copy_cloudKeyPoses6D.
+        enum Pending { kNone, kSingle, kVerify } pending = kNone;
+        int32_t pend_n = 0;                // records of the pending closure
+        s2m_loop_result pend_rec[S2M_LOOP_MAX_CANDIDATES]{};
+        int32_t pend_slot[S2M_LOOP_MAX_CANDIDATES] = { 0 };
+        float pend_pose_pre[S2M_LOOP_MAX_CANDIDATES][6] = { { 0 } };   // kf.pose[key_pre] of every candidate at launch
+        float snap_T[12] = { 0 };          // kf.frame[key_cur].T at launch
         float pend_fitness = 0.0f;         // s2m_loop_params::fitness_score of the launch
         int32_t pend_base_key = -1;
-        float snap_T[12] = { 0 };          // kf.frame[key_cur].T at launch
-        float snap_pose_pre[6] = { 0 };    // kf.pose[key_pre] at launch
-        // the launched verification (s2m_loop_verify_launch): a pending closure with several candidates. Its records in the caller's
-        // order, the slot of the device loop each one runs in (-1: decided at launch, it took none), the target submap of every
-        // slot, and the candidates' poses at launch. pend_fitness, pend_base_key and snap_T serve it as they serve a single closure.
-        int32_t ver_n = 0;                 // records of the pending verification; 0: the pending closure is a single one
-        int32_t ver_slots = 0;
-        s2m_loop_result ver_rec[S2M_LOOP_MAX_CANDIDATES]{};
-        int32_t ver_slot[S2M_LOOP_MAX_CANDIDATES] = { 0 };
-        float ver_pose_pre[S2M_LOOP_MAX_CANDIDATES][6] = { { 0 } };
-        DevBuf ver_prev[S2M_LOOP_MAX_CANDIDATES];
         s2m::IcpTuning tune{ 0.0f, s2m::kIcpShellCap, s2m::kIcpUseGrid ? 1 : 0 };   // cell: edge in units of the leaf (s2m_debug_icp_tuning)
     } loop;
 

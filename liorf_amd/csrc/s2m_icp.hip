@@ -15,12 +15,16 @@
 // incremental transform, as PCL transforms input_transformed.  fp32 distances use the operation order
 // of the oracle ((dx*dx + dy*dy) + dz*dz, -ffp-contract=off), so correspondences are identical to it.
 //
-// The device loop (icp_dev_*, what s2m_loop_*_launch queues) is the same alignment without the host in it: (1) becomes an exact
-// 1-NN through a uniform grid over the target, built once per alignment, with a brute-force worklist for the points the grid
-// does not settle (same keys); the host's part of (2) becomes k_icp_close, which runs the host loop's own source
-// (s2m_icp_close.hpp); iterations are queued in ranges and every kernel behind the end of the alignment returns at entry.
-// The loop carries up to kIcpMaxSlots alignments of one source at once (icp_dev_begin_many: what s2m_loop_verify_launch queues),
-// the slot a grid dimension of every kernel; the single alignment is its one-slot case.
+// The device loop (icp_dev_*, what s2m_loop_*_launch and s2m_loop_verify_launch queue) is the same alignment without the host in
+// it: (1) becomes an exact 1-NN through a uniform grid over the target, built once per alignment, with a brute-force worklist for
+// the points the grid does not settle (same keys); the host's part of (2) becomes k_icp_close, which runs the host loop's own
+// source (s2m_icp_close.hpp); iterations are queued in ranges and every kernel behind the end of the alignment returns at entry.
+// The loop carries up to kIcpMaxSlots alignments of one source at once, the slot a grid dimension of every kernel; the single
+// alignment is its one-slot case.
+// The kernels are one set but for two. The host loop (icp_align) launches the loop's load, reset, sums and fold on the one-slot
+// layout and differs in who closes an iteration (the host, after a wait), in the search (always the brute force, through k_icp_nn:
+// k_icp_nn_list over every source computes the same keys but cost the loop 2-3 % of its time) and in k_icp_transform, which takes
+// the step from the host.
 // DESIGN.md section 12 has the stopping rule of the grid search and its derivation, and the slot layout.
 #include "s2m_icp.hpp"
 
@@ -39,7 +43,7 @@ namespace {
 constexpr int kNnThreads = 256;
 constexpr int kNnTile = 1024;                       // target points per LDS tile
 constexpr unsigned long long kNoMatch = ~0ull;
-constexpr int kSumBlocks = 256;                     // most k_icp_sums workgroups: rows of the partial-sum buffer
+constexpr int kSumBlocks = 256;                     // most k_icp_sums_dev workgroups: rows of the partial-sum buffer
 
 struct Buf {
     void*  p = nullptr;
@@ -55,20 +59,6 @@ struct Buf {
     }
     template <typename T> T* as() const { return reinterpret_cast<T*>(p); }
 };
-
-__global__ __launch_bounds__(256) void k_icp_load(const unsigned char* __restrict__ pts, size_t stride, int n, float4* __restrict__ out)
-{
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const float* p = reinterpret_cast<const float*>(pts + (size_t)i * stride);
-    out[i] = make_float4(p[0], p[1], p[2], 0.0f);
-}
-
-__global__ __launch_bounds__(256) void k_icp_reset(unsigned long long* __restrict__ best, int n)
-{
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) best[i] = kNoMatch;
-}
 
 // the tile loop of the brute-force search: target points [j0, j1) staged through LDS in tiles of kNnTile, the nearest of them to p
 // (lowest index among equals) left in bd / bi. Every thread of the workgroup calls it (the staging is collective).
@@ -103,7 +93,9 @@ __device__ __forceinline__ void nn_tiles(const float4 p, const bool fin, const f
     }
 }
 
-// grid (source blocks, target slices): 256 source points against target points [slice*len, (slice+1)*len)
+// The host loop's search: grid (source blocks, target slices), 256 source points against target points [slice*len, (slice+1)*len).
+// It is k_icp_nn_list without list, slot and guard, kept as a kernel of its own because it is measurably faster there (DESIGN.md
+// section 12): the loop waits for every iteration, and this kernel reaches its six arguments in one round trip.
 __global__ __launch_bounds__(kNnThreads) void k_icp_nn(const float4* __restrict__ cur, int n_src, const float4* __restrict__ tgt, int n_tgt,
                                                        int slice_len, unsigned long long* __restrict__ best)
 {
@@ -118,64 +110,6 @@ __global__ __launch_bounds__(kNnThreads) void k_icp_nn(const float4* __restrict_
     nn_tiles(p, fin, tgt, j0, j1, tile, bd, bi);
     if (fin && bi >= 0)       // d2 >= 0: its bit pattern orders like the value; NaN distances (non-finite targets) never win above
         atomicMin(&best[i], ((unsigned long long)__float_as_uint(bd) << 32) | (unsigned)bi);
-}
-
-// count, sum d2, centroids and raw cross moments of the correspondences with d2 <= max_d2 (fp64): this workgroup's row of `part`
-__device__ __forceinline__ void sums_body(const float4* __restrict__ cur, int n_src, const float4* __restrict__ tgt,
-                                          const unsigned long long* __restrict__ best, double max_d2, double* __restrict__ part,
-                                          double (*sh)[17])
-{
-    double a[17];
-#pragma unroll
-    for (int k = 0; k < 17; k++) a[k] = 0.0;
-    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n_src; i += gridDim.x * blockDim.x) {
-        const unsigned long long key = best[i];
-        if (key == kNoMatch) continue;
-        const float d2 = __uint_as_float((unsigned)(key >> 32));
-        if (!((double)d2 <= max_d2)) continue;                       // determineCorrespondences: distance[0] > max_dist_sqr -> skip
-        const float4 s = cur[i], t = tgt[(unsigned)key];
-        a[0] += 1.0; a[1] += (double)d2;
-        a[2] += s.x; a[3] += s.y; a[4] += s.z; a[5] += t.x; a[6] += t.y; a[7] += t.z;
-        a[8]  += (double)t.x * s.x; a[9]  += (double)t.x * s.y; a[10] += (double)t.x * s.z;
-        a[11] += (double)t.y * s.x; a[12] += (double)t.y * s.y; a[13] += (double)t.y * s.z;
-        a[14] += (double)t.z * s.x; a[15] += (double)t.z * s.y; a[16] += (double)t.z * s.z;
-    }
-#pragma unroll
-    for (int k = 0; k < 17; k++) {
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) a[k] += __shfl_down(a[k], off, 64);
-    }
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (lane == 0) {
-#pragma unroll
-        for (int k = 0; k < 17; k++) sh[wave][k] = a[k];
-    }
-    __syncthreads();
-    if (threadIdx.x < 17) part[17 * blockIdx.x + threadIdx.x] = sh[0][threadIdx.x] + sh[1][threadIdx.x] + sh[2][threadIdx.x] + sh[3][threadIdx.x];
-}
-
-__global__ __launch_bounds__(256) void k_icp_sums(const float4* __restrict__ cur, int n_src, const float4* __restrict__ tgt,
-                                                  const unsigned long long* __restrict__ best, float max_d2_f, double max_d2,
-                                                  double* __restrict__ part)
-{
-    __shared__ double sh[4][17];
-    (void)max_d2_f;
-    sums_body(cur, n_src, tgt, best, max_d2, part, sh);
-}
-
-// the rows of k_icp_sums folded in workgroup order
-__device__ __forceinline__ void fold_body(const double* __restrict__ part, int rows, double* __restrict__ sums)
-{
-    const int k = threadIdx.x;
-    if (k >= 17) return;
-    double a = 0.0;
-    for (int b = 0; b < rows; b++) a += part[17 * b + k];
-    sums[k] = a;
-}
-
-__global__ __launch_bounds__(64) void k_icp_fold(const double* __restrict__ part, int rows, double* __restrict__ sums)
-{
-    fold_body(part, rows, sums);
 }
 
 struct Mat34 { float m[12]; };
@@ -198,7 +132,8 @@ __global__ __launch_bounds__(256) void k_icp_transform(float4* __restrict__ cur,
 // ---- the device loop (icp_dev_*): an alignment that is queued and left alone ------------------------------------------------
 // Everything the loop carries lives in one device block, copied to the host in one piece at the end of a range of iterations.
 // phase 0 = a kernel of the iteration loop: it returns at entry once st.done is set (the idiom of k_pg_cg_*: no kernel waits on
-// another, the launches queued behind the end of an alignment are idle); phase 1 = the fitness pass, which runs after it.
+// another, the launches queued behind the end of an alignment are idle); phase 1 = the fitness pass, which runs after it, and
+// every launch of the host loop, which keeps its state on the host.
 
 struct IcpGrid {
     float lo[3];           // least finite target coordinate per axis: the grid's origin
@@ -532,8 +467,10 @@ __global__ __launch_bounds__(256) void k_icp_reset_dev(IcpSlots S, int phase)
     if (i < S.n_src) S.best[blockIdx.z][i] = kNoMatch;
 }
 
-// k_icp_nn for the sources a slot's list names (use_list == 0: all of them, the device loop's brute-force search): grid (source
-// blocks, target slices of the slot with most, slots); workgroups past the end of the list or of their slot's slices return at entry
+// the brute force of the device loop: 256 sources - those a slot's list names, or with use_list == 0 all of them (the search with
+// the grid off: k_icp_nn with a slot) - against target points [slice * len, (slice + 1) * len), the winner settled across slices by
+// atomicMin. Grid (source blocks, target slices of the slot with most, slots); workgroups past the end of the list or of their
+// slot's slices return at entry
 __global__ __launch_bounds__(kNnThreads) void k_icp_nn_list(IcpSlots S, int use_list, int phase)
 {
     __shared__ float4 tile[kNnTile];
@@ -560,6 +497,41 @@ __global__ __launch_bounds__(kNnThreads) void k_icp_nn_list(IcpSlots S, int use_
         atomicMin(&best[i], ((unsigned long long)__float_as_uint(bd) << 32) | (unsigned)bi);
 }
 
+// count, sum d2, centroids and raw cross moments of the correspondences with d2 <= max_d2 (fp64): this workgroup's row of `part`
+// (a function of its own for the __restrict__ of its parameters, which a kernel's locals would not carry)
+__device__ __forceinline__ void sums_body(const float4* __restrict__ cur, int n_src, const float4* __restrict__ tgt,
+                                          const unsigned long long* __restrict__ best, double max_d2, double* __restrict__ part,
+                                          double (*sh)[17])
+{
+    double a[17];
+#pragma unroll
+    for (int k = 0; k < 17; k++) a[k] = 0.0;
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n_src; i += gridDim.x * blockDim.x) {
+        const unsigned long long key = best[i];
+        if (key == kNoMatch) continue;
+        const float d2 = __uint_as_float((unsigned)(key >> 32));
+        if (!((double)d2 <= max_d2)) continue;                       // determineCorrespondences: distance[0] > max_dist_sqr -> skip
+        const float4 s = cur[i], t = tgt[(unsigned)key];
+        a[0] += 1.0; a[1] += (double)d2;
+        a[2] += s.x; a[3] += s.y; a[4] += s.z; a[5] += t.x; a[6] += t.y; a[7] += t.z;
+        a[8]  += (double)t.x * s.x; a[9]  += (double)t.x * s.y; a[10] += (double)t.x * s.z;
+        a[11] += (double)t.y * s.x; a[12] += (double)t.y * s.y; a[13] += (double)t.y * s.z;
+        a[14] += (double)t.z * s.x; a[15] += (double)t.z * s.y; a[16] += (double)t.z * s.z;
+    }
+#pragma unroll
+    for (int k = 0; k < 17; k++) {
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) a[k] += __shfl_down(a[k], off, 64);
+    }
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    if (lane == 0) {
+#pragma unroll
+        for (int k = 0; k < 17; k++) sh[wave][k] = a[k];
+    }
+    __syncthreads();
+    if (threadIdx.x < 17) part[17 * blockIdx.x + threadIdx.x] = sh[0][threadIdx.x] + sh[1][threadIdx.x] + sh[2][threadIdx.x] + sh[3][threadIdx.x];
+}
+
 __global__ __launch_bounds__(256) void k_icp_sums_dev(IcpSlots S, double max_d2, int phase)
 {
     __shared__ double sh[4][17];
@@ -568,12 +540,20 @@ __global__ __launch_bounds__(256) void k_icp_sums_dev(IcpSlots S, double max_d2,
     sums_body(S.cur[s], S.n_src, S.tgt[s], S.best[s], max_d2, S.part[s], sh);
 }
 
+// the rows of k_icp_sums_dev folded in workgroup order into the slot's block, and the fallback list closed. The host loop
+// (icp_align) runs this kernel too and has no list: it never runs beside a flight, so the two counts it rewrites are nobody's.
 __global__ __launch_bounds__(64) void k_icp_fold_dev(IcpSlots S, int rows, int phase)
 {
     IcpDevBlock* blk = S.blk + blockIdx.z;
     if (done_guard(blk, phase)) return;
-    fold_body(S.part[blockIdx.z], rows, blk->sums);
-    if (threadIdx.x == 0) { blk->n_fallback = blk->wl_count; blk->wl_count = 0; }
+    const int k = threadIdx.x;
+    if (k < 17) {
+        const double* __restrict__ part = S.part[blockIdx.z];
+        double a = 0.0;
+        for (int b = 0; b < rows; b++) a += part[17 * b + k];
+        blk->sums[k] = a;
+    }
+    if (k == 0) { blk->n_fallback = blk->wl_count; blk->wl_count = 0; }
 }
 
 // closes the iteration on the folded sums: one lane per slot runs icp_close_step, the host loop's own source
@@ -600,8 +580,8 @@ __global__ __launch_bounds__(256) void k_icp_transform_dev(IcpSlots S, int phase
 }  // namespace
 
 struct IcpWorkspace {
-    Buf cur, tgt, best, part, sums;
-    double* h_sums = nullptr;            // pinned, 17 doubles
+    Buf cur, tgt, best, part;
+    double* h_sums = nullptr;            // pinned, 17 doubles: slot 0's folded sums, what the host loop closes an iteration on
     // the device loop: its block with a pinned mirror, the grid (cell counts, starts, ends, the targets sorted by cell), the
     // fallback list, the event behind the work queued last, and what the host keeps about the alignment in flight
     Buf blk, gcount, gstart, gend, gsorted, list;
@@ -624,7 +604,7 @@ IcpWorkspace* icp_create()
 {
     IcpWorkspace* w = new (std::nothrow) IcpWorkspace();
     if (!w) return nullptr;
-    if (w->sums.ensure(sizeof(double) * 17) != hipSuccess || hipHostMalloc((void**)&w->h_sums, sizeof(double) * 17) != hipSuccess ||
+    if (hipHostMalloc((void**)&w->h_sums, sizeof(double) * 17) != hipSuccess ||
         w->blk.ensure(sizeof(IcpDevBlock) * kIcpMaxSlots) != hipSuccess ||
         hipHostMalloc((void**)&w->h_blk, sizeof(IcpDevBlock) * kIcpMaxSlots) != hipSuccess ||
         hipEventCreateWithFlags(&w->ev, hipEventDisableTiming) != hipSuccess) {
@@ -637,7 +617,7 @@ IcpWorkspace* icp_create()
 void icp_destroy(IcpWorkspace* w)
 {
     if (!w) return;
-    Buf* bufs[] = { &w->cur, &w->tgt, &w->best, &w->part, &w->sums, &w->blk, &w->gcount, &w->gstart, &w->gend, &w->gsorted, &w->list };
+    Buf* bufs[] = { &w->cur, &w->tgt, &w->best, &w->part, &w->blk, &w->gcount, &w->gstart, &w->gend, &w->gsorted, &w->list };
     for (Buf* b : bufs) if (b->p) (void)hipFree(b->p);
     if (w->h_sums) (void)hipHostFree(w->h_sums);
     if (w->h_blk) (void)hipHostFree(w->h_blk);
@@ -658,32 +638,10 @@ void nn_shape(int n_src, int n_tgt, int* sb_out, int* slices_out, int* slice_len
     *sb_out = sb; *slices_out = (n_tgt + slice_len - 1) / slice_len; *slice_len_out = slice_len;
 }
 
-hipError_t nearest(IcpWorkspace* w, hipStream_t stream, int n_src, int n_tgt)
-{
-    int sb, slices, slice_len;
-    nn_shape(n_src, n_tgt, &sb, &slices, &slice_len);
-    hipLaunchKernelGGL(k_icp_reset, dim3((n_src + 255) / 256), dim3(256), 0, stream, w->best.as<unsigned long long>(), n_src);
-    hipLaunchKernelGGL(k_icp_nn, dim3(sb, slices), dim3(kNnThreads), 0, stream, (const float4*)w->cur.as<float4>(), n_src,
-                       (const float4*)w->tgt.as<float4>(), n_tgt, slice_len, w->best.as<unsigned long long>());
-    return hipGetLastError();
-}
-
-hipError_t sums(IcpWorkspace* w, hipStream_t stream, int n_src, double max_d2)
-{
-    const int rows = std::min((n_src + 255) / 256, kSumBlocks);
-    hipLaunchKernelGGL(k_icp_sums, dim3(rows), dim3(256), 0, stream, (const float4*)w->cur.as<float4>(), n_src,
-                       (const float4*)w->tgt.as<float4>(), (const unsigned long long*)w->best.as<unsigned long long>(), 0.0f, max_d2,
-                       w->part.as<double>());
-    hipLaunchKernelGGL(k_icp_fold, dim3(1), dim3(64), 0, stream, (const double*)w->part.as<double>(), rows, w->sums.as<double>());
-    ICP_TRY(hipGetLastError());
-    ICP_TRY(hipMemcpyAsync(w->h_sums, w->sums.p, sizeof(double) * 17, hipMemcpyDeviceToHost, stream));
-    return hipStreamSynchronize(stream);
-}
-
 // The buffers of K slots - one source of n_src points, targets of n_tgt[k] - and w->S, their layout: a slot's moving source, keys,
 // partial rows and list are n_src (rows) apiece, its target and sorted target start where the slot before ends. Slot 0 starts
-// every buffer, so what the host loop (icp_align) uses is the K = 1 layout. tune: the device loop's list and, with the grid
-// on, its cell arrays are laid out too (nullptr: the host loop, which has neither).
+// every buffer; the host loop (icp_align) runs on the K = 1 layout. tune: the device loop's list and, with the grid on, its
+// cell arrays are laid out too (nullptr: the host loop, which has neither).
 hipError_t dev_layout(IcpWorkspace* w, int K, size_t n_src, const size_t* n_tgt, const IcpTuning* tune)
 {
     if (K < 1 || K > kIcpMaxSlots) return hipErrorInvalidValue;
@@ -720,8 +678,6 @@ hipError_t dev_layout(IcpWorkspace* w, int K, size_t n_src, const size_t* n_tgt,
     w->S = S; w->K = K; w->n_tgt_max = (int)most; w->slices_max = slices_max;
     return hipSuccess;
 }
-
-hipError_t ensure_clouds(IcpWorkspace* w, size_t n_src, size_t n_tgt) { return dev_layout(w, 1, n_src, &n_tgt, nullptr); }
 
 // records -> float4: the K targets of the layout, or the one source into every slot's moving copy
 hipError_t load_slots(IcpWorkspace* w, hipStream_t stream, const unsigned char* d_src, const unsigned char* const* d_tgt, size_t stride)
@@ -781,6 +737,25 @@ hipError_t dev_sums(IcpWorkspace* w, hipStream_t stream, double max_d2, int phas
     return hipGetLastError();
 }
 
+// What the host loop (icp_align) asks per iteration, on the K = 1 layout: the brute-force search, then the sums with slot 0's
+// folded sums brought to h_sums and one wait. phase 1: the host closes the iteration, so no kernel looks at the block's `done`.
+hipError_t host_nearest(IcpWorkspace* w, hipStream_t stream)
+{
+    const IcpSlots& S = w->S;
+    hipLaunchKernelGGL(k_icp_reset_dev, dim3((S.n_src + 255) / 256), dim3(256), 0, stream, S, 1);
+    hipLaunchKernelGGL(k_icp_nn, dim3((S.n_src + kNnThreads - 1) / kNnThreads, w->slices_max), dim3(kNnThreads), 0, stream,
+                       (const float4*)S.cur[0], S.n_src, S.tgt[0], S.n_tgt[0], S.slice_len[0], S.best[0]);
+    return hipGetLastError();
+}
+
+hipError_t host_sums(IcpWorkspace* w, hipStream_t stream, double max_d2)
+{
+    ICP_TRY(host_nearest(w, stream));
+    ICP_TRY(dev_sums(w, stream, max_d2, 1));
+    ICP_TRY(hipMemcpyAsync(w->h_sums, w->S.blk->sums, sizeof(double) * 17, hipMemcpyDeviceToHost, stream));
+    return hipStreamSynchronize(stream);
+}
+
 // the blocks of all slots to the host in one copy, and the event the host tests: the end of everything queued so far
 hipError_t dev_mark(IcpWorkspace* w, hipStream_t stream)
 {
@@ -820,8 +795,8 @@ hipError_t dev_queue_fitness(IcpWorkspace* w, hipStream_t stream)
 
 void icp_dev_cancel(IcpWorkspace* w) { w->fl.phase = 0; }
 
-hipError_t icp_dev_begin_many(IcpWorkspace* w, hipStream_t stream, const unsigned char* d_src, size_t n_src_, const unsigned char* const* d_tgt,
-                              const size_t* n_tgt, int n_slots, size_t stride, const IcpParams& prm, const IcpTuning& tune)
+hipError_t icp_dev_begin(IcpWorkspace* w, hipStream_t stream, const unsigned char* d_src, size_t n_src_, const unsigned char* const* d_tgt,
+                         const size_t* n_tgt, int n_slots, size_t stride, const IcpParams& prm, const IcpTuning& tune)
 {
     if (w->fl.phase != 0 || n_src_ == 0 || n_slots < 1 || n_slots > kIcpMaxSlots || prm.max_iter < 1) return hipErrorInvalidValue;
     for (int k = 0; k < n_slots; k++) if (n_tgt[k] == 0) return hipErrorInvalidValue;
@@ -837,13 +812,7 @@ hipError_t icp_dev_begin_many(IcpWorkspace* w, hipStream_t stream, const unsigne
     return hipSuccess;
 }
 
-hipError_t icp_dev_begin(IcpWorkspace* w, hipStream_t stream, const unsigned char* d_src, size_t n_src, const unsigned char* d_tgt,
-                         size_t n_tgt, size_t stride, const IcpParams& prm, const IcpTuning& tune)
-{
-    return icp_dev_begin_many(w, stream, d_src, n_src, &d_tgt, &n_tgt, 1, stride, prm, tune);
-}
-
-hipError_t icp_dev_advance_many(IcpWorkspace* w, hipStream_t stream, bool wait, bool* done, IcpResult* res)
+hipError_t icp_dev_advance(IcpWorkspace* w, hipStream_t stream, bool wait, bool* done, IcpResult* res)
 {
     IcpWorkspace::Flight& f = w->fl;
     *done = false;
@@ -880,23 +849,16 @@ hipError_t icp_dev_advance_many(IcpWorkspace* w, hipStream_t stream, bool wait, 
     }
 }
 
-hipError_t icp_dev_advance(IcpWorkspace* w, hipStream_t stream, bool wait, bool* done, IcpResult* res)
-{
-    return w->K == 1 ? icp_dev_advance_many(w, stream, wait, done, res) : hipErrorInvalidValue;
-}
-
 hipError_t icp_dev_nearest(IcpWorkspace* w, hipStream_t stream, const unsigned char* d_src, size_t n_src_, const unsigned char* d_tgt,
-                           size_t n_tgt_, size_t stride, int mode, const IcpTuning& tune_, unsigned long long* keys, int* n_fallback,
+                           size_t n_tgt_, size_t stride, int mode, const IcpTuning& tune, unsigned long long* keys, int* n_fallback,
                            int reps, float* us_build, float* us_search)
 {
     const int n_src = (int)n_src_, n_tgt = (int)n_tgt_;
     if (w->fl.phase != 0 || n_src <= 0 || n_tgt <= 0) return hipErrorInvalidValue;
-    ICP_TRY(dev_layout(w, 1, n_src_, &n_tgt_, mode != 0 ? &tune_ : nullptr));
-    hipLaunchKernelGGL(k_icp_load, dim3((n_src + 255) / 256), dim3(256), 0, stream, d_src, stride, n_src, w->cur.as<float4>());
-    hipLaunchKernelGGL(k_icp_load, dim3((n_tgt + 255) / 256), dim3(256), 0, stream, d_tgt, stride, n_tgt, w->tgt.as<float4>());
-    ICP_TRY(hipGetLastError());
-    IcpTuning tune = tune_;
-    const bool grid = tune.use_grid != 0;
+    const bool grid = mode != 0 && tune.use_grid != 0;
+    ICP_TRY(dev_layout(w, 1, n_src_, &n_tgt_, mode != 0 ? &tune : nullptr));
+    ICP_TRY(load_slots(w, stream, d_src, nullptr, stride));
+    ICP_TRY(load_slots(w, stream, nullptr, &d_tgt, stride));
     hipEvent_t e0 = nullptr, e1 = nullptr, e2 = nullptr;
     const bool timed = reps > 0;
     hipError_t e = hipSuccess;
@@ -909,11 +871,8 @@ hipError_t icp_dev_nearest(IcpWorkspace* w, hipStream_t stream, const unsigned c
     if (e == hipSuccess && mode != 0) e = dev_prepare(w, stream, tune);
     if (e == hipSuccess && timed) e = hipEventRecord(e1, stream);
     for (int r = 0; e == hipSuccess && r < std::max(1, reps); r++) {
-        if (mode == 0) e = nearest(w, stream, n_src, n_tgt);
-        else {
-            if (r > 0) hipLaunchKernelGGL(k_icp_fold_dev, dim3(1), dim3(64), 0, stream, w->S, 0, 1);   // (zeroes the list count)
-            e = dev_nearest(w, stream, tune, 1);
-        }
+        if (mode != 0 && r > 0) hipLaunchKernelGGL(k_icp_fold_dev, dim3(1), dim3(64), 0, stream, w->S, 0, 1);   // (zeroes the list count)
+        e = mode != 0 ? dev_nearest(w, stream, tune, 1) : host_nearest(w, stream);
     }
     if (e == hipSuccess && timed) e = hipEventRecord(e2, stream);
     if (e == hipSuccess && mode != 0) e = hipMemcpyAsync(w->h_blk, w->blk.p, sizeof(IcpDevBlock), hipMemcpyDeviceToHost, stream);
@@ -927,21 +886,20 @@ hipError_t icp_dev_nearest(IcpWorkspace* w, hipStream_t stream, const unsigned c
         if (us_search) *us_search = b * 1000.0f / (float)reps;
     }
     for (hipEvent_t ev : { e0, e1, e2 }) if (ev) (void)hipEventDestroy(ev);
-    if (n_fallback) *n_fallback = (mode != 0 && grid && e == hipSuccess) ? w->h_blk->wl_count : 0;
+    if (n_fallback) *n_fallback = (grid && e == hipSuccess) ? w->h_blk->wl_count : 0;
     return e;
 }
 
 hipError_t icp_align(IcpWorkspace* w, hipStream_t stream, const unsigned char* d_src, size_t n_src_, const unsigned char* d_tgt,
                      size_t n_tgt_, size_t stride, const IcpParams& prm, IcpResult* res)
 {
-    const int n_src = (int)n_src_, n_tgt = (int)n_tgt_;
-    for (int i = 0; i < 16; i++) res->T[i] = (i % 5 == 0) ? 1.0f : 0.0f;
-    res->converged = 0; res->iterations = 0; res->fitness = DBL_MAX;
-    if (n_src == 0 || n_tgt == 0) return hipSuccess;
-    ICP_TRY(ensure_clouds(w, n_src_, n_tgt_));
-    hipLaunchKernelGGL(k_icp_load, dim3((n_src + 255) / 256), dim3(256), 0, stream, d_src, stride, n_src, w->cur.as<float4>());
-    hipLaunchKernelGGL(k_icp_load, dim3((n_tgt + 255) / 256), dim3(256), 0, stream, d_tgt, stride, n_tgt, w->tgt.as<float4>());
-    ICP_TRY(hipGetLastError());
+    const int n_src = (int)n_src_;
+    *res = icp_result_none();
+    if (n_src_ == 0 || n_tgt_ == 0) return hipSuccess;
+    if (w->fl.phase != 0) return hipErrorInvalidValue;                    // (the layout is the flight's: the callers answer BUSY before)
+    ICP_TRY(dev_layout(w, 1, n_src_, &n_tgt_, nullptr));
+    ICP_TRY(load_slots(w, stream, d_src, nullptr, stride));
+    ICP_TRY(load_slots(w, stream, nullptr, &d_tgt, stride));
 
     // icp.hpp computeTransformation + default_convergence_criteria.hpp hasConverged: icp_close_step, between two synchronisations
     const double max_d2 = prm.max_corr_dist * prm.max_corr_dist;
@@ -949,8 +907,7 @@ hipError_t icp_align(IcpWorkspace* w, hipStream_t stream, const unsigned char* d
     IcpLoopState st;
     icp_state_init(&st);
     for (;;) {
-        ICP_TRY(nearest(w, stream, n_src, n_tgt));
-        ICP_TRY(sums(w, stream, n_src, max_d2));
+        ICP_TRY(host_sums(w, stream, max_d2));
         const int it_before = st.it;
         icp_close_step(w->h_sums, cp, &st);
         if (st.it != it_before) {                                         // (not on the `fewer than 3 correspondences` exit)
@@ -964,12 +921,11 @@ hipError_t icp_align(IcpWorkspace* w, hipStream_t stream, const unsigned char* d
     memcpy(res->T, st.T, sizeof(res->T));
     const int conv = st.conv, it = st.it;
     // getFitnessScore(): the original source under the final transform, mean squared nearest distance
-    hipLaunchKernelGGL(k_icp_load, dim3((n_src + 255) / 256), dim3(256), 0, stream, d_src, stride, n_src, w->cur.as<float4>());
+    ICP_TRY(load_slots(w, stream, d_src, nullptr, stride));
     Mat34 F34;
     memcpy(F34.m, res->T, sizeof(float) * 12);
     hipLaunchKernelGGL(k_icp_transform, dim3((n_src + 255) / 256), dim3(256), 0, stream, w->cur.as<float4>(), n_src, F34);
-    ICP_TRY(nearest(w, stream, n_src, n_tgt));
-    ICP_TRY(sums(w, stream, n_src, DBL_MAX));
+    ICP_TRY(host_sums(w, stream, DBL_MAX));
     res->fitness = w->h_sums[0] > 0 ? w->h_sums[1] / w->h_sums[0] : DBL_MAX;
     res->converged = conv; res->iterations = it;
     return hipSuccess;

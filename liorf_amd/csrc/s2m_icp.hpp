@@ -3,6 +3,7 @@
 // src/mapOptmization.cpp:571-586 and :663-678.  Implemented in s2m_icp.hip.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <cfloat>
 #include <cstddef>
 #include <cstdint>
 
@@ -14,43 +15,50 @@ void          icp_destroy(IcpWorkspace* w);
 
 struct IcpParams { double max_corr_dist; int max_iter; double trans_eps; double fit_eps; };
 struct IcpResult { float T[16]; int converged; int iterations; double fitness; };
+// no alignment took place (an empty cloud): the identity, not converged, no fitness
+inline IcpResult icp_result_none()
+{
+    IcpResult r{};
+    r.T[0] = r.T[5] = r.T[10] = r.T[15] = 1.0f;
+    r.fitness = DBL_MAX;
+    return r;
+}
 
 // src / tgt: device records (x, y, z at byte 0/4/8). Synchronises `stream` once per iteration (the
-// close of an iteration, icp_close_step, runs on the host between iterations).
+// close of an iteration, icp_close_step, runs on the host between iterations). Not beside a device loop in flight.
 hipError_t icp_align(IcpWorkspace* w, hipStream_t stream, const unsigned char* d_src, size_t n_src,
                      const unsigned char* d_tgt, size_t n_tgt, size_t stride, const IcpParams& prm, IcpResult* res);
 
 // ---- the device loop: the same alignment queued on a stream and left alone ------------------------------------------------
 // Every iteration is closed on the device (k_icp_close runs icp_close_step, the host loop's own source: s2m_icp_close.hpp), so
-// nothing waits between iterations. Iterations are queued in ranges of kIcpRange; a range ends with a copy of the state block
-// to the host and an event. Once the alignment has ended the remaining launches of its range return at entry.
+// nothing waits between iterations. Iterations are queued in ranges of kIcpRange; a range ends with a copy of the state blocks
+// to the host and an event. Once an alignment has ended the remaining launches of its range return at entry.
+// icp_align launches the loop's own load, reset, sums and fold kernels on the one-slot layout; only its search (k_icp_nn) and its
+// transform (k_icp_transform, the step by value from the host) are kernels of its own.
 constexpr int kIcpRange = 8;            // iterations queued at a time
 constexpr bool kIcpUseGrid = true;      // the device loop's search: the uniform grid with its brute-force fallback, or brute force only
 constexpr float kIcpCellLeaves = 2.0f;  // grid cell edge in units of icp_leaf
 constexpr int kIcpShellCap = 3;         // largest Chebyshev radius (cells) searched before a point goes to the brute force
+constexpr int kIcpMaxSlots = 8;
 
 struct IcpTuning { float cell; int shell_cap; int use_grid; };
 
 void icp_dev_cancel(IcpWorkspace* w);                                    // forget the alignment in flight (the caller has drained the stream)
-// loads both clouds, builds the grid over the target, queues the first range. n_src, n_tgt > 0. Does not wait.
-hipError_t icp_dev_begin(IcpWorkspace* w, hipStream_t stream, const unsigned char* d_src, size_t n_src, const unsigned char* d_tgt,
-                         size_t n_tgt, size_t stride, const IcpParams& prm, const IcpTuning& tune);
+// One source against n_slots <= kIcpMaxSlots targets (the single alignment: n_slots = 1): n_slots independent alignments advance
+// through the same launches, the slot a grid dimension of every kernel. Loads the clouds, builds a grid over every target, queues
+// the first range. n_src, n_tgt[k] > 0. Does not wait.
+hipError_t icp_dev_begin(IcpWorkspace* w, hipStream_t stream, const unsigned char* d_src, size_t n_src, const unsigned char* const* d_tgt,
+                         const size_t* n_tgt, int n_slots, size_t stride, const IcpParams& prm, const IcpTuning& tune);
 // wait == false: tests the event (hipEventQuery) and, where the queued work has ended, queues what follows (the next range, or
-// the fitness pass) without waiting for it; wait == true: the same with hipEventSynchronize until the result is there.
-// *done: `res` holds the result and nothing is in flight any more. d_src must stay as it was until then (the fitness pass reloads it).
+// the fitness pass) without waiting for it; wait == true: the same with hipEventSynchronize until the result is there. Ranges are
+// queued until every slot has ended - a slot that has ended idles meanwhile - then one fitness pass runs for all.
+// *done: `res` holds the n_slots results, res[k] bit for bit what d_tgt[k] alone gives, and nothing is in flight any more.
+// d_src must stay as it was until then (the fitness pass reloads it).
 hipError_t icp_dev_advance(IcpWorkspace* w, hipStream_t stream, bool wait, bool* done, IcpResult* res);
-// The same for one source against n_slots <= kIcpMaxSlots targets: n_slots independent alignments advance through the same
-// launches (the slot is a grid dimension of every kernel of the loop; icp_dev_begin is the one-slot case). Ranges are queued
-// until every slot has ended - a slot that has ended idles meanwhile - then one fitness pass runs for all. res: n_slots results,
-// res[k] bit for bit what icp_dev_begin / icp_dev_advance give for d_tgt[k] alone. n_tgt[k] > 0.
-constexpr int kIcpMaxSlots = 8;
-hipError_t icp_dev_begin_many(IcpWorkspace* w, hipStream_t stream, const unsigned char* d_src, size_t n_src, const unsigned char* const* d_tgt,
-                              const size_t* n_tgt, int n_slots, size_t stride, const IcpParams& prm, const IcpTuning& tune);
-hipError_t icp_dev_advance_many(IcpWorkspace* w, hipStream_t stream, bool wait, bool* done, IcpResult* res);
-// one nearest-neighbour search of src against tgt, synchronously: mode 0 k_icp_nn, mode 1 the device loop's search (the grid with its
-// fallback, or with tune.use_grid off k_icp_nn_list over every source). keys: host,
-// n_src entries of (fp32 d2 bits << 32 | target index), ~0 = no match. reps > 0: the search `reps` times between events
-// (us_search per search; us_build: the grid's construction).
+// one nearest-neighbour search of src against tgt, synchronously: mode 0 the host loop's search (k_icp_nn: nn_tiles over every
+// source), mode 1 the device loop's search (the grid with its fallback, or with tune.use_grid off k_icp_nn_list over every
+// source). keys: host, n_src entries of (fp32 d2 bits << 32 | target index), ~0 = no match. reps > 0: the search `reps`
+// times between events (us_search per search; us_build: the grid's construction).
 hipError_t icp_dev_nearest(IcpWorkspace* w, hipStream_t stream, const unsigned char* d_src, size_t n_src, const unsigned char* d_tgt,
                            size_t n_tgt, size_t stride, int mode, const IcpTuning& tune, unsigned long long* keys, int* n_fallback,
                            int reps, float* us_build, float* us_search);
