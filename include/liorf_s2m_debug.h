@@ -160,6 +160,28 @@ int  s2m_debug_icp_align_many_device(s2m_handle h, const void* src, size_t n_src
  * icp_leaf (0 = built in), the largest shell radius searched before a point goes to the brute force (0 = built in), and
  * use_grid (0 = brute force only, 1 = grid, < 0 = built in). */
 int  s2m_debug_icp_tuning(s2m_handle h, float cell_in_leaves, int32_t shell_cap, int32_t use_grid);
+/* Observation hook: the uniform grids the device loop builds over n_cand = 1 .. S2M_LOOP_MAX_CANDIDATES host targets (non-empty,
+ * records of one stride), laid out in slots as s2m_debug_icp_align_many_device lays them out and built by the loop's own
+ * launches (block reset, box, shape, counts, scan, scatter) - no source, no search, and built whatever use_grid says. The cell
+ * edge asked for is that of the other debug calls (the default icp_leaf times the edge of s2m_debug_icp_tuning).
+ * out[i]: the grid of tgts[i] as the device holds it - origin, cell edge and its reciprocal, cells per axis (x fastest), finite
+ * targets, and usable = 0 where no grid was built (an extent that overflows fp32; every source then goes to the brute force,
+ * the targets are not counted and n_fin is 1 where one is finite).
+ * cell_start, cell_end, order: each may be NULL, and so may each entry. cell_start[i] / cell_end[i] (room for
+ * S2M_DEBUG_ICP_GRID_MAX_CELLS) take, per cell, the range of the cell's targets in the slot's sorted targets; order[i] (room for
+ * n_tgts[i]) the index in tgts[i] of each of the n_fin sorted entries. Nothing is written to them for a target without a grid.
+ * S2M_ERR_BUSY while a launched closure is pending. s2m_debug_icp_grid_check_args: the argument checks on their own (host
+ * code, no handle, no GPU). */
+#define S2M_DEBUG_ICP_GRID_MAX_CELLS 262144
+typedef struct s2m_debug_icp_grid_out {
+    float   lo[3];
+    float   cell, inv;
+    int32_t n[3];
+    int32_t n_fin, usable;
+} s2m_debug_icp_grid_out;
+int  s2m_debug_icp_grid_check_args(const void* const* tgts, const size_t* n_tgts, int32_t n_cand, size_t stride_bytes, const s2m_debug_icp_grid_out* out);
+int  s2m_debug_icp_grid(s2m_handle h, const void* const* tgts, const size_t* n_tgts, int32_t n_cand, size_t stride_bytes,
+                        s2m_debug_icp_grid_out* out, int32_t* const* cell_start, int32_t* const* cell_end, int32_t* const* order);
 
 /* ---- the tail rule of a launched pose-graph optimise (s2m_pg_optimize_launch) ------------------------------------------
  * Host code, no handle, no GPU, and the code the library runs when a launched optimise delivers its result: states are 12

@@ -650,3 +650,41 @@ int s2m_debug_icp_align_many_device(s2m_handle h, const void* src, size_t n_src,
     const int rc = icp_params_in(h, p, &ip);
     return rc ? rc : debug_align_many(h, src, n_src, tgts, n_tgts, n_cand, stride_bytes, ip, out);
 }
+
+int s2m_debug_icp_grid_check_args(const void* const* tgts, const size_t* n_tgts, int32_t n_cand, size_t stride_bytes, const s2m_debug_icp_grid_out* out)
+{
+    if (!out || !tgts || !n_tgts || n_cand < 1 || n_cand > S2M_LOOP_MAX_CANDIDATES) return S2M_ERR_INVALID_ARG;
+    if (stride_bytes < 12 || (stride_bytes & 3)) return S2M_ERR_INVALID_ARG;
+    for (int32_t i = 0; i < n_cand; i++) {
+        if (!tgts[i] || n_tgts[i] == 0 || (reinterpret_cast<uintptr_t>(tgts[i]) & 3) != 0) return S2M_ERR_INVALID_ARG;
+        if (n_tgts[i] > (size_t)0x3fffffff) return S2M_ERR_CAPACITY;
+    }
+    return S2M_OK;
+}
+
+int s2m_debug_icp_grid(s2m_handle h, const void* const* tgts, const size_t* n_tgts, int32_t n_cand, size_t stride_bytes,
+                       s2m_debug_icp_grid_out* out, int32_t* const* cell_start, int32_t* const* cell_end, int32_t* const* order)
+{
+    static_assert(S2M_DEBUG_ICP_GRID_MAX_CELLS == kIcpGridMaxCells, "the header's array size is the grid's");
+    static_assert(sizeof(s2m_debug_icp_grid_out) == sizeof(IcpGridInfo) && sizeof(int32_t) == sizeof(int), "filled in place");
+    if (!h) return S2M_ERR_INVALID_ARG;
+    int rc = s2m_debug_icp_grid_check_args(tgts, n_tgts, n_cand, stride_bytes, out);
+    if (rc) return fail(h, rc, "grid: 1 .. S2M_LOOP_MAX_CANDIDATES non-empty targets of 4-byte aligned records (stride >= 12, a multiple of 4), an output array");
+    if ((rc = debug_stage(h, nullptr, 0, nullptr, 0, stride_bytes))) return rc;                  // (BUSY, the loop stream)
+    s2m_context::LoopClosure& L = h->loop;
+    const unsigned char* d_tgt[S2M_LOOP_MAX_CANDIDATES];
+    for (int32_t i = 0; i < n_cand; i++) {
+        if ((rc = ensure(h, L.target(i), n_tgts[i] * stride_bytes))) return rc;
+        S2M_HIP(h, hipMemcpyAsync(L.target(i).p, tgts[i], n_tgts[i] * stride_bytes, hipMemcpyHostToDevice, L.stream));
+        d_tgt[i] = L.target(i).as<unsigned char>();
+    }
+    s2m_loop_params lp;
+    s2m_loop_default_params(&lp);
+    const hipError_t e = icp_dev_grid(L.icp, L.stream, d_tgt, n_tgts, n_cand, stride_bytes, loop_tuning(h, lp.icp_leaf),
+                                      reinterpret_cast<IcpGridInfo*>(out), cell_start, cell_end, order);
+    if (e != hipSuccess) {
+        (void)hipStreamSynchronize(L.stream);
+        return fail(h, S2M_ERR_HIP, "ICP grid", e);
+    }
+    return S2M_OK;
+}

@@ -890,6 +890,38 @@ hipError_t icp_dev_nearest(IcpWorkspace* w, hipStream_t stream, const unsigned c
     return e;
 }
 
+hipError_t icp_dev_grid(IcpWorkspace* w, hipStream_t stream, const unsigned char* const* d_tgt, const size_t* n_tgt, int n_slots, size_t stride,
+                        const IcpTuning& tune, IcpGridInfo* info, int* const* cell_start, int* const* cell_end, int* const* order)
+{
+    static_assert(kIcpGridMaxCells == kGridMaxCells, "the hook's callers size their cell arrays by it");
+    if (w->fl.phase != 0 || n_slots < 1 || n_slots > kIcpMaxSlots) return hipErrorInvalidValue;
+    for (int k = 0; k < n_slots; k++) if (n_tgt[k] == 0) return hipErrorInvalidValue;
+    IcpTuning t = tune;
+    t.use_grid = 1;
+    ICP_TRY(dev_layout(w, n_slots, 0, n_tgt, &t));                        // (no source: nothing here reads a slot's source arrays)
+    ICP_TRY(load_slots(w, stream, nullptr, d_tgt, stride));
+    ICP_TRY(dev_prepare(w, stream, t));
+    ICP_TRY(hipMemcpyAsync(w->h_blk, w->blk.p, sizeof(IcpDevBlock) * (size_t)n_slots, hipMemcpyDeviceToHost, stream));
+    ICP_TRY(hipStreamSynchronize(stream));
+    for (int k = 0; k < n_slots; k++) {
+        const IcpGrid& g = w->h_blk[k].g;
+        IcpGridInfo& o = info[k];
+        for (int a = 0; a < 3; a++) { o.lo[a] = g.lo[a]; o.n[a] = g.n[a]; }
+        o.cell = g.cell; o.inv = g.inv; o.n_fin = g.n_fin; o.usable = g.usable;
+        if (!g.usable) continue;
+        const size_t ncells = (size_t)g.n[0] * (size_t)g.n[1] * (size_t)g.n[2];
+        if (ncells > (size_t)kGridMaxCells || g.n_fin < 0 || (size_t)g.n_fin > n_tgt[k]) return hipErrorUnknown;   // not reached
+        if (cell_start && cell_start[k])
+            ICP_TRY(hipMemcpyAsync(cell_start[k], w->S.gstart + (size_t)k * kGridMaxCells, sizeof(int) * ncells, hipMemcpyDeviceToHost, stream));
+        if (cell_end && cell_end[k])
+            ICP_TRY(hipMemcpyAsync(cell_end[k], w->S.gend + (size_t)k * kGridMaxCells, sizeof(int) * ncells, hipMemcpyDeviceToHost, stream));
+        if (order && order[k] && g.n_fin > 0)                             // the .w of every sorted entry: one int out of each float4
+            ICP_TRY(hipMemcpy2DAsync(order[k], sizeof(int), reinterpret_cast<const unsigned char*>(w->S.gsorted[k]) + 3 * sizeof(float),
+                                     sizeof(float4), sizeof(int), (size_t)g.n_fin, hipMemcpyDeviceToHost, stream));
+    }
+    return hipStreamSynchronize(stream);
+}
+
 hipError_t icp_align(IcpWorkspace* w, hipStream_t stream, const unsigned char* d_src, size_t n_src_, const unsigned char* d_tgt,
                      size_t n_tgt_, size_t stride, const IcpParams& prm, IcpResult* res)
 {

@@ -63,4 +63,15 @@ hipError_t icp_dev_nearest(IcpWorkspace* w, hipStream_t stream, const unsigned c
                            size_t n_tgt, size_t stride, int mode, const IcpTuning& tune, unsigned long long* keys, int* n_fallback,
                            int reps, float* us_build, float* us_search);
 
+// the grids of the device loop over n_slots <= kIcpMaxSlots targets, synchronously: the layout, the target load and the
+// preparation of icp_dev_begin (k_icp_begin, box, shape, counts, scan, scatter - built whatever tune.use_grid says), no source and
+// no search. info[k]: the slot's IcpGrid as the device holds it (without a grid the targets are not counted: n_fin is 1 where
+// one is finite). Each of cell_start / cell_end / order may be null, and so may each of their entries: cell_start[k] and
+// cell_end[k] take the n[0] * n[1] * n[2] cell starts and ends of slot k (room for kIcpGridMaxCells), order[k] the original
+// index of each of the n_fin entries of the slot's sorted targets (room for n_tgt[k]); nothing is written for a slot without a grid.
+constexpr int kIcpGridMaxCells = 1 << 18;
+struct IcpGridInfo { float lo[3]; float cell, inv; int n[3]; int n_fin; int usable; };
+hipError_t icp_dev_grid(IcpWorkspace* w, hipStream_t stream, const unsigned char* const* d_tgt, const size_t* n_tgt, int n_slots, size_t stride,
+                        const IcpTuning& tune, IcpGridInfo* info, int* const* cell_start, int* const* cell_end, int* const* order);
+
 }  // namespace s2m

@@ -45,7 +45,7 @@ ABI_SYMBOLS = [
     "s2m_loop_align_launch", "s2m_loop_closure_rs_launch", "s2m_loop_poll", "s2m_loop_collect",
     "s2m_loop_verify_check_args", "s2m_loop_verify_launch", "s2m_loop_verify_poll", "s2m_loop_verify_collect", "s2m_loop_verify",
     "s2m_debug_icp_nearest", "s2m_debug_icp_time_nearest", "s2m_debug_icp_align_device", "s2m_debug_icp_align_many_device",
-    "s2m_debug_icp_tuning",
+    "s2m_debug_icp_tuning", "s2m_debug_icp_grid_check_args", "s2m_debug_icp_grid",
     "s2m_gmap_default_params", "s2m_global_map", "s2m_kf_map_cloud",
     "s2m_scan_layout_preset", "s2m_project_default_params", "s2m_imu_deskew_info", "s2m_project_check_args", "s2m_project_scan",
     "s2m_downsample_projected", "s2m_sc_add_projected",
@@ -67,6 +67,7 @@ S2M_LOOP_PENDING = 5                                     # a launched closure wh
 S2M_LOOP_MAX_CANDIDATES = 8                              # candidates of one verification: the slots of the device loop
 S2M_DEBUG_PREP_READ, S2M_DEBUG_PREP_NEW, S2M_DEBUG_PREP_LEGACY = -1, 0, 1   # chains of s2m_debug_scan_prep (liorf_s2m_debug.h)
 S2M_ICP_RANGE = 8                                        # iterations the device loop queues at a time (liorf_s2m_debug.h)
+S2M_DEBUG_ICP_GRID_MAX_CELLS = 1 << 18                   # most cells of a grid of the device loop's search (liorf_s2m_debug.h)
 S2M_WARN_LEAF_TOO_SMALL = 1
 S2M_PG_PRIOR, S2M_PG_BETWEEN, S2M_PG_GPS, S2M_PG_INITIAL = 0, 1, 2, 3
 S2M_PG_PENDING, S2M_PG_IDLE = 2, 3                       # s2m_pg_optimize_launch / _poll / _collect: queued or running; nothing pending
@@ -137,6 +138,12 @@ class IcpParams(C.Structure):
 
 class IcpResult(C.Structure):
     _fields_ = [("T", C.c_float * 16), ("converged", C.c_int32), ("iterations", C.c_int32), ("fitness_score", C.c_double)]
+
+
+class IcpGridOut(C.Structure):
+    """s2m_debug_icp_grid_out (include/liorf_s2m_debug.h)."""
+    _fields_ = [("lo", C.c_float * 3), ("cell", C.c_float), ("inv", C.c_float), ("n", C.c_int32 * 3), ("n_fin", C.c_int32),
+                ("usable", C.c_int32)]
 
 
 class KfParams(C.Structure):
@@ -341,6 +348,9 @@ def load_library(path: str | None = None) -> C.CDLL:
     L.s2m_debug_icp_time_nearest.argtypes = [vp, vp, C.c_size_t, vp, C.c_size_t, C.c_size_t, C.c_int32, C.c_int32, vp, C.POINTER(C.c_int32), fp, fp]
     L.s2m_debug_icp_align_device.argtypes = [vp, vp, C.c_size_t, vp, C.c_size_t, C.c_size_t, C.POINTER(IcpParams), C.POINTER(IcpResult)]
     L.s2m_debug_icp_tuning.argtypes = [vp, C.c_float, C.c_int32, C.c_int32]
+    L.s2m_debug_icp_grid_check_args.argtypes = [C.POINTER(C.c_void_p), szp, C.c_int32, C.c_size_t, C.POINTER(IcpGridOut)]
+    L.s2m_debug_icp_grid.argtypes = [vp, C.POINTER(C.c_void_p), szp, C.c_int32, C.c_size_t, C.POINTER(IcpGridOut), C.POINTER(C.c_void_p),
+                                     C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]
     L.s2m_gmap_default_params.argtypes = [C.POINTER(GmapParams)]
     L.s2m_global_map.argtypes = [vp, C.POINTER(GmapParams), vp, C.c_size_t, C.c_size_t, szp, i32p, C.c_size_t, szp]
     L.s2m_kf_map_cloud.argtypes = [vp, C.c_int, C.c_int, C.c_float, vp, C.c_size_t, C.c_size_t, szp]
@@ -1351,6 +1361,32 @@ class MapOptimizationS2M:
         """s2m_debug_icp_tuning: the grid's cell edge (in leaves), the shell cap, grid on / off for what follows (0, 0, -1 = built in)."""
         self._check(self.lib.s2m_debug_icp_tuning(self.h, cell_in_leaves, shell_cap, use_grid), "s2m_debug_icp_tuning")
 
+    def debugIcpGrid(self, targets, tables: bool = True):
+        """s2m_debug_icp_grid: the grids the device loop builds over 1 .. S2M_LOOP_MAX_CANDIDATES targets, one dict per target:
+        lo (3 fp32), cell, inv (np.float32), n (3 ints), n_fin, usable and, with `tables` and where a grid was built, start and
+        end (prod(n) int32: per cell its range in the sorted targets) and order (n_fin int32: the original index of each entry)."""
+        tg = [_records(t) for t in targets]
+        if any(t[2] != tg[0][2] for t in tg):
+            raise ValueError("all clouds must share one record stride")
+        K = len(tg)
+        ptrs = (C.c_void_p * max(K, 1))(*[t[0].ctypes.data for t in tg])
+        ns = (C.c_size_t * max(K, 1))(*[t[1] for t in tg])
+        out = (IcpGridOut * max(K, 1))()
+        bufs = [[np.full(S2M_DEBUG_ICP_GRID_MAX_CELLS, -1, np.int32), np.full(S2M_DEBUG_ICP_GRID_MAX_CELLS, -1, np.int32),
+                 np.full(max(t[1], 1), -1, np.int32)] for t in tg] if tables else []
+        arrs = [(C.c_void_p * max(K, 1))(*[b[j].ctypes.data for b in bufs]) if tables else None for j in range(3)]
+        self._check(self.lib.s2m_debug_icp_grid(self.h, ptrs, ns, K, tg[0][2] if tg else 0, out, *arrs), "s2m_debug_icp_grid")
+        res = []
+        for k in range(K):
+            o = out[k]
+            g = dict(lo=np.array(o.lo, np.float32), cell=np.float32(o.cell), inv=np.float32(o.inv), n=tuple(int(v) for v in o.n),
+                     n_fin=int(o.n_fin), usable=int(o.usable))
+            if tables and g["usable"]:
+                nc = g["n"][0] * g["n"][1] * g["n"][2]
+                g.update(start=bufs[k][0][:nc], end=bufs[k][1][:nc], order=bufs[k][2][:g["n_fin"]])
+            res.append(g)
+        return res
+
     def performSCLoopClosure(self, params: LoopParams | None = None) -> LoopResult:
         """performSCLoopClosure() (reference :624-730): the ScanContext detector on this handle's SC store, then
         s2m_loop_align(kfSize() - 1, pre, 0, ..) (:634-655). yaw_diff is not used by the reference (:639)."""
@@ -1420,6 +1456,20 @@ def pg_apply_check_args(n_variables: int, n_extra: int, op: int, cols: int, has_
     """s2m_debug_pg_apply_check_args (host only, no GPU): the status code."""
     a = np.zeros(1)
     return load_library().s2m_debug_pg_apply_check_args(n_variables, n_extra, op, cols, _dp(a) if has_in else None, _dp(a) if has_out else None)
+
+
+def debug_icp_grid_check_args(targets, n_cand: int | None = None, stride: int | None = None, has_out: bool = True,
+                              has_list: bool = True, has_counts: bool = True) -> int:
+    """s2m_debug_icp_grid_check_args (host only, no GPU): the status code. targets: clouds, or None for a null entry."""
+    tg = [None if t is None else _records(t) for t in targets]
+    K = len(tg)
+    ptrs = (C.c_void_p * max(K, 1))(*[None if t is None else t[0].ctypes.data for t in tg])
+    ns = (C.c_size_t * max(K, 1))(*[1 if t is None else t[1] for t in tg])
+    if stride is None:
+        stride = next((t[2] for t in tg if t is not None), 16)
+    out = (IcpGridOut * max(K, 1))()
+    return load_library().s2m_debug_icp_grid_check_args(ptrs if has_list else None, ns if has_counts else None, K if n_cand is None else n_cand,
+                                                        stride, out if has_out else None)
 
 
 def pg_marginals_check_args(n_variables: int, keys, n_keys: int | None = None) -> int:

@@ -331,7 +331,8 @@ def test_too_few_correspondences_end_the_shared_state_machine(close_exe, tmp_pat
 # ---- the boundary -----------------------------------------------------------------------------------------------------
 
 NEW = ["s2m_loop_align_launch", "s2m_loop_closure_rs_launch", "s2m_loop_poll", "s2m_loop_collect", "s2m_debug_icp_nearest",
-       "s2m_debug_icp_time_nearest", "s2m_debug_icp_align_device", "s2m_debug_icp_tuning"]
+       "s2m_debug_icp_time_nearest", "s2m_debug_icp_align_device", "s2m_debug_icp_tuning", "s2m_debug_icp_grid",
+       "s2m_debug_icp_grid_check_args"]
 
 
 def test_new_symbols_and_constants_declared_bound_and_exported():
