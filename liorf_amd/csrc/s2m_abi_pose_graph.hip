@@ -76,6 +76,7 @@ void s2m::host::pg_drop_pending(s2m_context* h, bool destroy)
 namespace {
 
 constexpr size_t kPgMaxVars = (size_t)1 << 24;          // as the key-frame store
+constexpr int kPgCgChunk = 24;          // CG iterations after which the host reads the stop flags; a launched optimise's segment holds as many
 
 void pose_to_state(const float p[6], double X[12])     // Rot3::RzRyRx(roll, pitch, yaw), fp64
 {
@@ -197,7 +198,7 @@ int prepare(s2m_context* h)
     for (size_t k = 1; k < n; k++)
         if (chain_of[k] < 0) return fail(h, S2M_ERR_INVALID_ARG, "pose graph: a variable is not on the odometry chain from key 0");
     if ((rc = upload_state(h, 0, n))) return rc;
-    if (!g.h_sc) S2M_HIP(h, hipHostMalloc((void**)&g.h_sc, sizeof(PgScalars) * (1 + kPgBlockCols)));   // [0]: the single solve, then one per column
+    if (!g.h_sc) S2M_HIP(h, hipHostMalloc((void**)&g.h_sc, sizeof(PgScalars) * kPgBlockCols));   // one per column of a solve
     if (g.topo_dirty) {
         std::vector<char> on_chain(g.factors.size(), 0);
         std::vector<PgFactor> chain(n), extra;
@@ -250,23 +251,29 @@ int read_scalars(s2m_context* h)
     return S2M_OK;
 }
 
-// CG on (I + K^T K) y = b with the b in place; the stop flag is read once per chunk of iterations
-int run_cg(s2m_context* h, const s2m_pg_params& prm, int* iters)
+int pg_max_cg(const PgDev& d, const s2m_pg_params& prm)
 {
-    const PgDev& d = h->pg.dev;
-    int max_cg = prm.cg_max_iterations > 0 ? prm.cg_max_iterations : 6 * d.n_extra + 20;
-    if (d.n_extra == 0) max_cg = 1;                        // K = 0: the first step is exact
-    S2M_HIP(h, pg_cg_begin(h->stream, d, prm.cg_rel_tol, max_cg));
-    constexpr int kChunk = 24;
+    if (d.n_extra == 0) return 1;                          // K = 0: the first step is exact
+    return prm.cg_max_iterations > 0 ? prm.cg_max_iterations : 6 * d.n_extra + 20;
+}
+
+// CG on (I + K^T K) y_c = b_c for the columns of `c` with the b_c in place (kPgOne: the graph's own vectors); every column's
+// scalars come back in one copy per chunk of iterations (h_sc[c]); ends when all have stopped
+int run_cg(s2m_context* h, const PgDev& db, const PgCols& c, const s2m_pg_params& prm)
+{
+    const int max_cg = pg_max_cg(db, prm);
+    S2M_HIP(h, pg_cg_begin(h->stream, db, c, prm.cg_rel_tol, max_cg));
+    PgScalars* hs = h->pg.h_sc;
     for (int done = 0; done < max_cg;) {
-        const int c = std::min(kChunk, max_cg - done);
-        S2M_HIP(h, pg_cg_iterations(h->stream, d, c));
-        int rc = read_scalars(h);
-        if (rc) return rc;
-        done += c;
-        if (h->pg.h_sc->stop) break;
+        const int k = std::min(kPgCgChunk, max_cg - done);
+        S2M_HIP(h, pg_cg_iterations(h->stream, db, c, k));
+        S2M_HIP(h, hipMemcpyAsync(hs, db.sc, sizeof(PgScalars) * (size_t)c.cols, hipMemcpyDeviceToHost, h->stream));
+        S2M_HIP(h, hipStreamSynchronize(h->stream));
+        done += k;
+        bool all = true;
+        for (int q = 0; q < c.cols; q++) all = all && hs[q].stop;
+        if (all) break;
     }
-    *iters = h->pg.h_sc->iters;
     return S2M_OK;
 }
 
@@ -300,38 +307,16 @@ int prepare_block(s2m_context* h, int cols, PgDev& db, PgCols& c)
     return S2M_OK;
 }
 
-// run_cg for the columns of a block: the b_c in place; every column's scalars come back in one copy per chunk of
-// iterations (h_sc[1 + c]); ends when all have stopped
-int run_cg_cols(s2m_context* h, const PgDev& db, const PgCols& c, const s2m_pg_params& prm)
-{
-    int max_cg = prm.cg_max_iterations > 0 ? prm.cg_max_iterations : 6 * db.n_extra + 20;
-    if (db.n_extra == 0) max_cg = 1;
-    S2M_HIP(h, pg_cg_begin_cols(h->stream, db, c, prm.cg_rel_tol, max_cg));
-    constexpr int kChunk = 24;
-    PgScalars* hs = h->pg.h_sc + 1;
-    for (int done = 0; done < max_cg;) {
-        const int k = std::min(kChunk, max_cg - done);
-        S2M_HIP(h, pg_cg_iterations_cols(h->stream, db, c, k));
-        S2M_HIP(h, hipMemcpyAsync(hs, db.sc, sizeof(PgScalars) * (size_t)c.cols, hipMemcpyDeviceToHost, h->stream));
-        S2M_HIP(h, hipStreamSynchronize(h->stream));
-        done += k;
-        bool all = true;
-        for (int q = 0; q < c.cols; q++) all = all && hs[q].stop;
-        if (all) break;
-    }
-    return S2M_OK;
-}
-
 // One pass: column k is e_(at[k]) through J_c^-T, CG and J_c^-1; rows[12 k ..] holds its delta at keys ka[k] and kb[k].
 int solve_pass(s2m_context* h, const PgDev& db, const PgCols& c, const s2m_pg_params& prm, const PgColAt& at, const PgColAt& ka, const PgColAt& kb,
                double* rows)
 {
-    S2M_HIP(h, pg_bwd_unit_cols(h->stream, db, c, at));
-    int rc = run_cg_cols(h, db, c, prm);
+    S2M_HIP(h, pg_bwd_unit(h->stream, db, c, at));
+    int rc = run_cg(h, db, c, prm);
     if (rc) return rc;
-    S2M_HIP(h, pg_fwd_y_cols(h->stream, db, c));
+    S2M_HIP(h, pg_fwd_y(h->stream, db, c));
     double* dev_rows = h->pg.blk_rows.as<double>();
-    S2M_HIP(h, pg_rows_cols(h->stream, db, c, ka, kb, dev_rows));
+    S2M_HIP(h, pg_rows(h->stream, db, c, ka, kb, dev_rows));
     S2M_HIP(h, hipMemcpyAsync(rows, dev_rows, sizeof(double) * 12 * (size_t)c.cols, hipMemcpyDeviceToHost, h->stream));
     S2M_HIP(h, hipStreamSynchronize(h->stream));
     return S2M_OK;
@@ -341,6 +326,20 @@ bool params_ok(const s2m_pg_params& p)
 {
     return p.max_iterations >= 0 && p.cg_max_iterations >= 0 && p.relative_error_tol >= 0.0 && std::isfinite(p.relative_error_tol) &&
            p.absolute_error_tol >= 0.0 && std::isfinite(p.absolute_error_tol) && p.cg_rel_tol >= 0.0 && std::isfinite(p.cg_rel_tol);
+}
+
+// The head of a call that takes parameters: the defaults for null, the check, and the result of an empty graph.
+int pg_params(s2m_context* h, const s2m_pg_params* p, s2m_pg_params& prm, s2m_pg_result* res = nullptr)
+{
+    if (p) prm = *p; else s2m_pg_default_params(&prm);
+    if (!params_ok(prm)) return fail(h, S2M_ERR_INVALID_ARG, "pose-graph params: iteration counts and tolerances must be >= 0 and finite");
+    if (res) {
+        *res = s2m_pg_result{};
+        res->robust_weight_min = 1.0;
+        res->n_variables = (int32_t)pg_n(h);
+        res->n_factors = (int32_t)h->pg.factors.size();
+    }
+    return S2M_OK;
 }
 
 int add_factor(s2m_context* h, const PgFactor& f)
@@ -364,7 +363,6 @@ PgFactor make_factor(int type, int32_t i, int32_t j, const double X[12], const d
 }
 
 // ---- the launched optimise ----
-constexpr int kPgCgChunk = 24;          // CG iterations per segment: the chunk s2m_pg_optimize reads its stop flag after
 constexpr int kPgRangeSegments = 2;     // segments queued at a time; between two ranges the host looks at the record once
 
 int pg_busy(s2m_context* h)
@@ -531,16 +529,12 @@ int s2m_pg_optimize(s2m_handle h, const s2m_pg_params* p, s2m_pg_result* out)
     if (!h) return S2M_ERR_INVALID_ARG;
     if (h->pg.pending) return pg_busy(h);
     s2m_pg_params prm;
-    if (p) prm = *p; else s2m_pg_default_params(&prm);
-    if (!params_ok(prm)) return fail(h, S2M_ERR_INVALID_ARG, "pose-graph params: iteration counts and tolerances must be >= 0 and finite");
-    s2m_pg_result res{};
-    res.robust_weight_min = 1.0;
-    res.n_variables = (int32_t)pg_n(h);
-    res.n_factors = (int32_t)h->pg.factors.size();
+    s2m_pg_result res;
+    int rc = pg_params(h, p, prm, &res);
+    if (rc) return rc;
     if (out) *out = res;
     if (pg_n(h) == 0) return S2M_OK;
-    int rc = prepare(h);
-    if (rc) return rc;
+    if ((rc = prepare(h))) return rc;
     auto& g = h->pg;
     PgDev& d = g.dev;
     S2M_HIP(h, pg_linearize(h->stream, d, d.X));
@@ -550,9 +544,8 @@ int s2m_pg_optimize(s2m_handle h, const s2m_pg_params* p, s2m_pg_result* out)
     res.robust_weight_min = g.h_sc->wmin;
     for (int it = 0; it < prm.max_iterations; it++) {
         S2M_HIP(h, pg_rhs(h->stream, d));
-        int cg = 0;
-        if ((rc = run_cg(h, prm, &cg))) return rc;
-        res.inner_iterations += cg;
+        if ((rc = run_cg(h, d, kPgOne, prm))) return rc;
+        res.inner_iterations += g.h_sc->iters;
         S2M_HIP(h, pg_step(h->stream, d));
         S2M_HIP(h, pg_linearize(h->stream, d, d.Xtrial));  // the trial point's error, and the next step's linearisation if it is kept
         if ((rc = read_scalars(h))) return rc;
@@ -578,21 +571,17 @@ int s2m_pg_optimize_launch(s2m_handle h, const s2m_pg_params* p, s2m_pg_result* 
     if (!h) return S2M_ERR_INVALID_ARG;
     if (h->pg.pending) return pg_busy(h);
     s2m_pg_params prm;
-    if (p) prm = *p; else s2m_pg_default_params(&prm);
-    if (!params_ok(prm)) return fail(h, S2M_ERR_INVALID_ARG, "pose-graph params: iteration counts and tolerances must be >= 0 and finite");
-    s2m_pg_result res{};
-    res.robust_weight_min = 1.0;
-    res.n_variables = (int32_t)pg_n(h);
-    res.n_factors = (int32_t)h->pg.factors.size();
+    s2m_pg_result res;
+    int rc = pg_params(h, p, prm, &res);
+    if (rc) return rc;
     if (pg_n(h) == 0) { if (early) *early = res; return S2M_OK; }
     auto& g = h->pg;
-    int rc;
     if ((rc = host_current(h)) || (rc = prepare(h))) return rc;      // from here on the host needs nothing the device holds
     if ((rc = pg_stream(h)) || (rc = ensure(h, g.rec, sizeof(PgRecord)))) return rc;
     const PgDev& d = g.dev;
     g.n_l = pg_n(h); g.f_l = g.factors.size();
     g.pend_prm = prm;
-    g.pend_max_cg = d.n_extra == 0 ? 1 : prm.cg_max_iterations > 0 ? prm.cg_max_iterations : 6 * d.n_extra + 20;   // as run_cg
+    g.pend_max_cg = pg_max_cg(d, prm);
     std::copy(g.X.begin() + 12 * (g.n_l - 1), g.X.begin() + 12 * g.n_l, g.a_launch);
     S2M_HIP(h, hipEventRecord(g.ev_ready, h->stream));               // behind the uploads of prepare()
     S2M_HIP(h, hipStreamWaitEvent(g.stream, g.ev_ready, 0));
@@ -708,15 +697,15 @@ int s2m_debug_pg_apply(s2m_handle h, int32_t op, int32_t cols, const double* in,
         return fail(h, S2M_ERR_INVALID_ARG, "apply: op 0..3 (2 and 3 need an extra factor), cols 0..S2M_PG_BLOCK_COLUMNS, two arrays, a graph");
     int rc = pg_hook_begin(h, true);
     if (rc) return rc;
-    PgDev db = h->pg.dev;
-    PgCols c{};
+    PgDev db = h->pg.dev;                                   // cols == 0: one column on the graph's own vectors
+    PgCols c = kPgOne;
     if (cols > 0 && (rc = prepare_block(h, cols, db, c))) return rc;
     // with an extra factor a column's u is 6 n_extra doubles apart, so the host's side-by-side columns are the device's
-    const size_t C = (size_t)std::max(cols, 1), nv = 6 * (size_t)db.n, nu = 6 * (size_t)db.n_extra;
+    const size_t C = (size_t)c.cols, nv = 6 * (size_t)db.n, nu = 6 * (size_t)db.n_extra;
     double* src = op == S2M_DEBUG_PG_BWD ? db.g : op == S2M_DEBUG_PG_KT ? db.u : db.p;
     const double* dst = op == S2M_DEBUG_PG_FWD ? db.t1 : op == S2M_DEBUG_PG_K ? db.u : db.t2;
     if ((rc = pg_up(h, src, in, C * (op == S2M_DEBUG_PG_KT ? nu : nv)))) return rc;
-    S2M_HIP(h, cols > 0 ? pg_apply_cols(h->stream, db, c, op) : pg_apply(h->stream, db, op));
+    S2M_HIP(h, pg_apply(h->stream, db, c, op));
     if ((rc = pg_down(h, out, dst, C * (op == S2M_DEBUG_PG_K ? nu : nv)))) return rc;
     S2M_HIP(h, hipStreamSynchronize(h->stream));
     return S2M_OK;
@@ -727,21 +716,20 @@ int s2m_debug_pg_cg(s2m_handle h, const s2m_pg_params* p, int32_t cols, const do
     if (!h) return S2M_ERR_INVALID_ARG;
     if (h->pg.pending) return pg_busy(h);
     s2m_pg_params prm;
-    if (p) prm = *p; else s2m_pg_default_params(&prm);
-    if (!params_ok(prm) || cols < 0 || cols > S2M_PG_BLOCK_COLUMNS || !b || !y || !out)
-        return fail(h, S2M_ERR_INVALID_ARG, "cg: valid params, cols 0..S2M_PG_BLOCK_COLUMNS, three arrays");
-    int rc = pg_hook_begin(h, true);
+    int rc = pg_params(h, p, prm);
     if (rc) return rc;
-    PgDev db = h->pg.dev;
-    PgCols c{};
+    if (cols < 0 || cols > S2M_PG_BLOCK_COLUMNS || !b || !y || !out)
+        return fail(h, S2M_ERR_INVALID_ARG, "cg: cols 0..S2M_PG_BLOCK_COLUMNS, three arrays");
+    if ((rc = pg_hook_begin(h, true))) return rc;
+    PgDev db = h->pg.dev;                                   // cols == 0: one column on the graph's own vectors
+    PgCols c = kPgOne;
     if (cols > 0 && (rc = prepare_block(h, cols, db, c))) return rc;
-    const size_t C = (size_t)std::max(cols, 1), nv = 6 * (size_t)db.n;
+    const size_t C = (size_t)c.cols, nv = 6 * (size_t)db.n;
     if ((rc = pg_up(h, db.b, b, C * nv))) return rc;
-    int iters = 0;
-    if ((rc = cols > 0 ? run_cg_cols(h, db, c, prm) : run_cg(h, prm, &iters))) return rc;
+    if ((rc = run_cg(h, db, c, prm))) return rc;
     if ((rc = pg_down(h, y, db.y, C * nv))) return rc;
     S2M_HIP(h, hipStreamSynchronize(h->stream));
-    const PgScalars* hs = h->pg.h_sc + (cols > 0 ? 1 : 0);
+    const PgScalars* hs = h->pg.h_sc;
     for (size_t q = 0; q < C; q++) out[q] = s2m_debug_pg_cg_out{ hs[q].rr, hs[q].bb, hs[q].iters, hs[q].stop };
     return S2M_OK;
 }
@@ -790,11 +778,12 @@ int s2m_pg_marginal(s2m_handle h, int32_t key, double cov[36])
     const PgDev& d = h->pg.dev;
     S2M_HIP(h, pg_linearize(h->stream, d, d.X));
     // column a of (J^T J)^-1 = J_c^-1 (I + K^T K)^-1 J_c^-T e_a
-    for (int a = 0; a < 6; a++) {
-        S2M_HIP(h, pg_bwd_unit(h->stream, d, key, a));
-        int cg = 0;
-        if ((rc = run_cg(h, prm, &cg))) return rc;
-        S2M_HIP(h, pg_fwd_y(h->stream, d));
+    for (int a = 0; a < 6; a++) {                           // six one-column solves on the graph's own vectors, one after the other
+        PgColAt at{};
+        at.v[0] = 6 * key + a;
+        S2M_HIP(h, pg_bwd_unit(h->stream, d, kPgOne, at));
+        if ((rc = run_cg(h, d, kPgOne, prm))) return rc;
+        S2M_HIP(h, pg_fwd_y(h->stream, d, kPgOne));
         double col[6];
         S2M_HIP(h, hipMemcpyAsync(col, d.delta + 6 * (size_t)key, sizeof(col), hipMemcpyDeviceToHost, h->stream));
         S2M_HIP(h, hipStreamSynchronize(h->stream));

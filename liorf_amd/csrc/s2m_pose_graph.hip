@@ -196,10 +196,15 @@ __device__ void factor_eval(const PgFactor& f, const double* X, double* Ji, doub
     }
 }
 
-// (the bodies of the kernels that also have a gated form for the launched optimise, further down, are device functions: the two
-// forms run the same code)
-__device__ inline void linearize_body(const PgDev& d, const double* X)
+// A kernel's gate (PgGate in the header), read before any other load: true = return at the head.
+__device__ inline bool gated(PgGate g)
 {
+    return g.base && *reinterpret_cast<const int32_t*>(reinterpret_cast<const char*>(g.base) + blockIdx.y * g.stride);
+}
+
+__global__ void __launch_bounds__(kPgThreads) k_pg_linearize(PgDev d, const double* X, PgGate gate)
+{
+    if (gated(gate)) return;
     const int f = blockIdx.x * blockDim.x + threadIdx.x;
     if (f >= d.n + d.n_extra) return;
     if (f < d.n) {
@@ -217,11 +222,11 @@ __device__ inline void linearize_body(const PgDev& d, const double* X)
         factor_eval(d.extra[x], X, d.Ji + 36 * (size_t)x, d.Jj + 36 * (size_t)x, d.rx + 6 * (size_t)x, nullptr, d.ferr + f, d.fw + f);
     }
 }
-__global__ void __launch_bounds__(kPgThreads) k_pg_linearize(PgDev d, const double* X) { linearize_body(d, X); }
 
 // sum of the error terms and minimum of the weights, one workgroup, fixed order
-__device__ inline void err_reduce_body(const PgDev& d)
+__global__ void __launch_bounds__(kPgThreads) k_pg_err_reduce(PgDev d, PgGate gate)
 {
+    if (gated(gate)) return;
     __shared__ double se[kPgThreads], sw[kPgThreads];
     const int n = d.n + d.n_extra;
     double e = 0.0, w = 1.0;
@@ -234,11 +239,11 @@ __device__ inline void err_reduce_body(const PgDev& d)
     }
     if (threadIdx.x == 0) { d.sc->err = se[0]; d.sc->wmin = sw[0]; }
 }
-__global__ void __launch_bounds__(kPgThreads) k_pg_err_reduce(PgDev d) { err_reduce_body(d); }
 
 // level-0 matrices of both scans: forward M_i = -Binv_i A_(i-1), C0 = Binv_i; transposed (e = n-1-i) M_e = -(A_i Binv_i)^T, C0 = Binv_i^T
-__device__ inline void scan_m0_body(const PgDev& d)
+__global__ void __launch_bounds__(kPgThreads) k_pg_scan_m0(PgDev d, PgGate gate)
 {
+    if (gated(gate)) return;
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= d.n) return;
     const double* B = d.Binv + 36 * (size_t)i;
@@ -265,11 +270,11 @@ __device__ inline void scan_m0_body(const PgDev& d)
             Cb[a * 6 + b] = B[b * 6 + a];
         }
 }
-__global__ void __launch_bounds__(kPgThreads) k_pg_scan_m0(PgDev d) { scan_m0_body(d); }
 
 // prefix products inside each group, one thread per (group, column); the group's product is the next level's matrix
-__device__ inline void scan_pre_body(const double* M, double* Pre, double* Mnext, int n)
+__global__ void __launch_bounds__(kPgThreads) k_pg_scan_pre(const double* M, double* Pre, double* Mnext, int n, PgGate gate)
 {
+    if (gated(gate)) return;
     const int t = blockIdx.x * blockDim.x + threadIdx.x;
     const int g = t / 6, col = t % 6;
     const int e0 = g * kPgGroup;
@@ -285,16 +290,22 @@ __device__ inline void scan_pre_body(const double* M, double* Pre, double* Mnext
     if (Mnext)
         for (int a = 0; a < 6; a++) Mnext[36 * (size_t)g + a * 6 + col] = v[a];
 }
-__global__ void __launch_bounds__(kPgThreads) k_pg_scan_pre(const double* M, double* Pre, double* Mnext, int n) { scan_pre_body(M, Pre, Mnext, n); }
+
+// ---- the linear solve: one family of kernels for one right-hand side (the optimise, s2m_pg_marginal) and for C of them in
+// lockstep (PgCols in the header).  Column c = blockIdx.y: its vectors lie c * vec (u, loc) doubles behind column 0's, its
+// kPgDotBlocks partials and its PgScalars c places on; Binv, M, Pre, C0, Ji, Jj are shared.  blockIdx.x and threadIdx.x
+// have the same roles whatever the number of columns, so a column's sums run in one order.
 
 // up-sweep, one thread per group: the group's recurrence from a zero input
-__global__ void __launch_bounds__(64) k_pg_scan_up0(PgScan sc, const double* in, const int32_t* stop)
+__global__ void __launch_bounds__(64) k_pg_scan_up0(PgScan sc, size_t ls, const double* in, size_t vs, PgGate gate)
 {
-    if (stop && *stop) return;
+    if (gated(gate)) return;
     const int g = blockIdx.x * blockDim.x + threadIdx.x;
     const int n = sc.n[0], e0 = g * kPgGroup;
     if (e0 >= n) return;
     const int e1 = min(e0 + kPgGroup, n);
+    in += blockIdx.y * vs;
+    double* loc0 = sc.loc[0] + blockIdx.y * ls;
     double v[6] = { 0, 0, 0, 0, 0, 0 };
     for (int e = e0; e < e1; e++) {
         const double* x = in + 6 * (size_t)(sc.rev ? n - 1 - e : e);
@@ -302,52 +313,57 @@ __global__ void __launch_bounds__(64) k_pg_scan_up0(PgScan sc, const double* in,
         double c[6], o[6];
         mat6_vec(sc.C0 + 36 * (size_t)e, xin, c);
         mat6_vec(sc.M[0] + 36 * (size_t)e, v, o);
-        for (int a = 0; a < 6; a++) { v[a] = o[a] + c[a]; sc.loc[0][6 * (size_t)e + a] = v[a]; }
+        for (int a = 0; a < 6; a++) { v[a] = o[a] + c[a]; loc0[6 * (size_t)e + a] = v[a]; }
     }
 }
-__global__ void __launch_bounds__(64) k_pg_scan_up(PgScan sc, int lvl, const int32_t* stop)
+__global__ void __launch_bounds__(64) k_pg_scan_up(PgScan sc, size_t ls, int lvl, PgGate gate)
 {
-    if (stop && *stop) return;
+    if (gated(gate)) return;
     const int g = blockIdx.x * blockDim.x + threadIdx.x;
     const int n = sc.n[lvl], e0 = g * kPgGroup;
     if (e0 >= n) return;
     const int e1 = min(e0 + kPgGroup, n);
+    const double* below = sc.loc[lvl - 1] + blockIdx.y * ls;
+    double* here = sc.loc[lvl] + blockIdx.y * ls;
     double v[6] = { 0, 0, 0, 0, 0, 0 };
     for (int e = e0; e < e1; e++) {
         const int last = min(e * kPgGroup + kPgGroup, sc.n[lvl - 1]) - 1;
-        const double* c = sc.loc[lvl - 1] + 6 * (size_t)last;
+        const double* c = below + 6 * (size_t)last;
         double o[6];
         mat6_vec(sc.M[lvl] + 36 * (size_t)e, v, o);
-        for (int a = 0; a < 6; a++) { v[a] = o[a] + c[a]; sc.loc[lvl][6 * (size_t)e + a] = v[a]; }
+        for (int a = 0; a < 6; a++) { v[a] = o[a] + c[a]; here[6 * (size_t)e + a] = v[a]; }
     }
 }
 // down-sweep, one thread per element: add the carry that enters the element's group
-__global__ void __launch_bounds__(kPgThreads) k_pg_scan_down(PgScan sc, int lvl, double* out, const int32_t* stop)
+__global__ void __launch_bounds__(kPgThreads) k_pg_scan_down(PgScan sc, size_t ls, int lvl, double* out, size_t vs, PgGate gate)
 {
-    if (stop && *stop) return;
+    if (gated(gate)) return;
     const int e = blockIdx.x * blockDim.x + threadIdx.x;
     const int n = sc.n[lvl];
     if (e >= n) return;
     const int g = e / kPgGroup;
+    double* here = sc.loc[lvl] + blockIdx.y * ls;
     double v[6];
-    for (int a = 0; a < 6; a++) v[a] = sc.loc[lvl][6 * (size_t)e + a];
+    for (int a = 0; a < 6; a++) v[a] = here[6 * (size_t)e + a];
     if (g > 0) {
-        const double* xin = sc.loc[lvl + 1] + 6 * (size_t)(g - 1);
+        const double* xin = sc.loc[lvl + 1] + blockIdx.y * ls + 6 * (size_t)(g - 1);
         const double x6[6] = { xin[0], xin[1], xin[2], xin[3], xin[4], xin[5] };
         double o[6];
         mat6_vec(sc.Pre[lvl] + 36 * (size_t)e, x6, o);
         for (int a = 0; a < 6; a++) v[a] += o[a];
     }
-    double* dst = lvl == 0 ? out + 6 * (size_t)(sc.rev ? n - 1 - e : e) : sc.loc[lvl] + 6 * (size_t)e;
+    double* dst = lvl == 0 ? out + blockIdx.y * vs + 6 * (size_t)(sc.rev ? n - 1 - e : e) : here + 6 * (size_t)e;
     for (int a = 0; a < 6; a++) dst[a] = v[a];
 }
 
 // the extra factors: u_f = Ji x_i + Jj x_j; per key, in the order of its incidence list, g_k = sum J^T u
-__global__ void __launch_bounds__(kPgThreads) k_pg_extra_u(PgDev d, const double* x, double* u, const int32_t* stop)
+__global__ void __launch_bounds__(kPgThreads) k_pg_extra_u(PgDev d, PgCols s, const double* x, PgGate gate)
 {
-    if (stop && *stop) return;
+    if (gated(gate)) return;
     const int f = blockIdx.x * blockDim.x + threadIdx.x;
     if (f >= d.n_extra) return;
+    x += blockIdx.y * s.vec;
+    double* u = d.u + blockIdx.y * s.u;
     const PgFactor& fac = d.extra[f];
     double xi[6], o[6], o2[6] = { 0, 0, 0, 0, 0, 0 };
     for (int a = 0; a < 6; a++) xi[a] = x[6 * (size_t)fac.i + a];
@@ -358,11 +374,13 @@ __global__ void __launch_bounds__(kPgThreads) k_pg_extra_u(PgDev d, const double
     }
     for (int a = 0; a < 6; a++) u[6 * (size_t)f + a] = o[a] + o2[a];
 }
-__global__ void __launch_bounds__(kPgThreads) k_pg_extra_gather(PgDev d, const double* u, double* g, const int32_t* stop)
+__global__ void __launch_bounds__(kPgThreads) k_pg_extra_gather(PgDev d, PgCols s, PgGate gate)
 {
-    if (stop && *stop) return;
+    if (gated(gate)) return;
     const int k = blockIdx.x * blockDim.x + threadIdx.x;
     if (k >= d.n) return;
+    const double* u = d.u + blockIdx.y * s.u;
+    double* g = d.g + blockIdx.y * s.vec;
     double acc[6] = { 0, 0, 0, 0, 0, 0 };
     for (int q = d.inc_start[k]; q < d.inc_start[k + 1]; q++) {
         const PgIncidence in = d.inc[q];
@@ -373,7 +391,8 @@ __global__ void __launch_bounds__(kPgThreads) k_pg_extra_gather(PgDev d, const d
     for (int a = 0; a < 6; a++) g[6 * (size_t)k + a] = acc[a];
 }
 
-// ---- CG vector steps: every sum in a fixed order (kPgDotBlocks x kPgThreads strided partials, then one thread) ----
+// ---- CG vector steps: every sum in a fixed order (kPgDotBlocks x kPgThreads strided partials, then one thread).  The
+// iteration's kernels return at their head once the column's sc->stop is set.
 __device__ inline void block_partial(double a, double* partial)
 {
     __shared__ double sm[kPgThreads];
@@ -392,80 +411,112 @@ __device__ inline double partial_sum(const double* partial)
     return s;
 }
 
-__device__ inline void rhs_body(const PgDev& d, int have_t2)                        // b = -(rc + t2)
+__global__ void __launch_bounds__(kPgThreads) k_pg_cg_init(PgDev d, PgCols s, PgGate gate)   // y = 0, r = p = b, partial of b.b
 {
-    const int k = blockIdx.x * blockDim.x + threadIdx.x;
-    if (k < 6 * d.n) d.b[k] = -(d.rc[k] + (have_t2 ? d.t2[k] : 0.0));
-}
-__global__ void __launch_bounds__(kPgThreads) k_pg_rhs(PgDev d, int have_t2) { rhs_body(d, have_t2); }
-__device__ inline void cg_init_body(const PgDev& d)                                 // y = 0, r = p = b, partial of b.b
-{
+    if (gated(gate)) return;
+    const size_t at = blockIdx.y * s.vec;
+    const double* b = d.b + at;
+    double *y = d.y + at, *r = d.r + at, *p = d.p + at;
     double a = 0.0;
     for (int k = blockIdx.x * kPgThreads + threadIdx.x; k < 6 * d.n; k += kPgDotBlocks * kPgThreads) {
-        const double v = d.b[k];
-        d.y[k] = 0.0; d.r[k] = v; d.p[k] = v;
+        const double v = b[k];
+        y[k] = 0.0; r[k] = v; p[k] = v;
         a += v * v;
     }
-    block_partial(a, d.partial);
+    block_partial(a, d.partial + blockIdx.y * kPgDotBlocks);
 }
-__global__ void __launch_bounds__(kPgThreads) k_pg_cg_init(PgDev d) { cg_init_body(d); }
-__device__ inline void cg_init2_body(const PgDev& d, double tol, int max_iters)
+// (`close`: the launched optimise's head gate, shut behind the CG begin of a step that was opened; null otherwise)
+__global__ void k_pg_cg_init2(PgDev d, double tol, int max_iters, PgGate gate, int32_t* close)
 {
-    const double bb = partial_sum(d.partial);
-    d.sc->rr = bb; d.sc->bb = bb; d.sc->tol2 = tol * tol;
-    d.sc->iters = 0; d.sc->max_iters = max_iters;
-    d.sc->stop = (bb == 0.0 || max_iters <= 0) ? 1 : 0;
+    if (gated(gate)) return;
+    PgScalars* sc = d.sc + blockIdx.y;
+    const double bb = partial_sum(d.partial + blockIdx.y * kPgDotBlocks);
+    sc->rr = bb; sc->bb = bb; sc->tol2 = tol * tol;
+    sc->iters = 0; sc->max_iters = max_iters;
+    sc->stop = (bb == 0.0 || max_iters <= 0) ? 1 : 0;
+    if (close) *close = 1;
 }
-__global__ void k_pg_cg_init2(PgDev d, double tol, int max_iters) { cg_init2_body(d, tol, max_iters); }
-__global__ void __launch_bounds__(kPgThreads) k_pg_cg_q(PgDev d, int have_t2)       // q = p + K^T K p, partial of p.q
+__global__ void __launch_bounds__(kPgThreads) k_pg_cg_q(PgDev d, PgCols s, int have_t2)      // q = p + K^T K p, partial of p.q
 {
-    if (d.sc->stop) return;
+    if (d.sc[blockIdx.y].stop) return;
+    const size_t at = blockIdx.y * s.vec;
+    const double *pv = d.p + at, *t2 = d.t2 + at;
+    double* qv = d.q + at;
     double a = 0.0;
     for (int k = blockIdx.x * kPgThreads + threadIdx.x; k < 6 * d.n; k += kPgDotBlocks * kPgThreads) {
-        const double p = d.p[k], q = p + (have_t2 ? d.t2[k] : 0.0);
-        d.q[k] = q;
+        const double p = pv[k], q = p + (have_t2 ? t2[k] : 0.0);
+        qv[k] = q;
         a += p * q;
     }
-    block_partial(a, d.partial);
+    block_partial(a, d.partial + blockIdx.y * kPgDotBlocks);
 }
 __global__ void k_pg_cg_alpha(PgDev d)
 {
-    if (d.sc->stop) return;
-    const double pq = partial_sum(d.partial);
-    d.sc->pq = pq;
-    d.sc->alpha = pq > 0.0 ? d.sc->rr / pq : 0.0;
+    PgScalars* sc = d.sc + blockIdx.y;
+    if (sc->stop) return;
+    const double pq = partial_sum(d.partial + blockIdx.y * kPgDotBlocks);
+    sc->pq = pq;
+    sc->alpha = pq > 0.0 ? sc->rr / pq : 0.0;
 }
-__global__ void __launch_bounds__(kPgThreads) k_pg_cg_update(PgDev d)               // y += alpha p, r -= alpha q, partial of r.r
+__global__ void __launch_bounds__(kPgThreads) k_pg_cg_update(PgDev d, PgCols s)              // y += alpha p, r -= alpha q, partial of r.r
 {
-    if (d.sc->stop) return;
-    const double alpha = d.sc->alpha;
+    if (d.sc[blockIdx.y].stop) return;
+    const size_t at = blockIdx.y * s.vec;
+    const double *pv = d.p + at, *qv = d.q + at;
+    double *y = d.y + at, *rv = d.r + at;
+    const double alpha = d.sc[blockIdx.y].alpha;
     double a = 0.0;
     for (int k = blockIdx.x * kPgThreads + threadIdx.x; k < 6 * d.n; k += kPgDotBlocks * kPgThreads) {
-        d.y[k] += alpha * d.p[k];
-        const double r = d.r[k] - alpha * d.q[k];
-        d.r[k] = r;
+        y[k] += alpha * pv[k];
+        const double r = rv[k] - alpha * qv[k];
+        rv[k] = r;
         a += r * r;
     }
-    block_partial(a, d.partial);
+    block_partial(a, d.partial + blockIdx.y * kPgDotBlocks);
 }
 __global__ void k_pg_cg_beta(PgDev d)
 {
-    if (d.sc->stop) return;
-    const double rr = partial_sum(d.partial);
-    d.sc->beta = d.sc->rr > 0.0 ? rr / d.sc->rr : 0.0;
-    d.sc->rr = rr;
-    d.sc->iters += 1;
-    if (!(rr > d.sc->tol2 * d.sc->bb) || d.sc->iters >= d.sc->max_iters || !(d.sc->pq > 0.0)) d.sc->stop = 1;
+    PgScalars* sc = d.sc + blockIdx.y;
+    if (sc->stop) return;
+    const double rr = partial_sum(d.partial + blockIdx.y * kPgDotBlocks);
+    sc->beta = sc->rr > 0.0 ? rr / sc->rr : 0.0;
+    sc->rr = rr;
+    sc->iters += 1;
+    if (!(rr > sc->tol2 * sc->bb) || sc->iters >= sc->max_iters || !(sc->pq > 0.0)) sc->stop = 1;
 }
-__global__ void __launch_bounds__(kPgThreads) k_pg_cg_p(PgDev d)
+__global__ void __launch_bounds__(kPgThreads) k_pg_cg_p(PgDev d, PgCols s)
 {
-    if (d.sc->stop) return;
+    if (d.sc[blockIdx.y].stop) return;
     const int k = blockIdx.x * blockDim.x + threadIdx.x;
-    if (k < 6 * d.n) d.p[k] = d.r[k] + d.sc->beta * d.p[k];
+    const size_t at = blockIdx.y * s.vec;
+    if (k < 6 * d.n) d.p[at + k] = d.r[at + k] + d.sc[blockIdx.y].beta * d.p[at + k];
 }
 
-__device__ inline void retract_body(const PgDev& d)
+__global__ void __launch_bounds__(kPgThreads) k_pg_unit(PgDev d, PgCols s, PgColAt at)
 {
+    const int k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k < 6 * d.n) d.g[blockIdx.y * s.vec + k] = k == at.v[blockIdx.y] ? 1.0 : 0.0;
+}
+// the wanted rows of every column's delta, so that one copy brings a pass's result to the host
+__global__ void __launch_bounds__(64) k_pg_rows(PgDev d, PgCols s, PgColAt ka, PgColAt kb, double* rows)
+{
+    const int t = threadIdx.x;
+    if (t >= 12) return;
+    const int key = t < 6 ? ka.v[blockIdx.y] : kb.v[blockIdx.y];
+    const bool in = key >= 0 && key < d.n;
+    rows[12 * (size_t)blockIdx.y + t] = in ? d.delta[blockIdx.y * s.vec + 6 * (size_t)key + t % 6] : 0.0;
+}
+
+// ---- the step around the solve, on the graph's own vectors
+__global__ void __launch_bounds__(kPgThreads) k_pg_rhs(PgDev d, int have_t2, PgGate gate)    // b = -(rc + t2)
+{
+    if (gated(gate)) return;
+    const int k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k < 6 * d.n) d.b[k] = -(d.rc[k] + (have_t2 ? d.t2[k] : 0.0));
+}
+__global__ void __launch_bounds__(kPgThreads) k_pg_retract(PgDev d, PgGate gate)
+{
+    if (gated(gate)) return;
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= d.n) return;
     const double* X = d.X + 12 * (size_t)i;
@@ -479,15 +530,9 @@ __device__ inline void retract_body(const PgDev& d)
     for (int k = 0; k < 9; k++) O[k] = Rn[k];
     for (int k = 0; k < 3; k++) O[9 + k] = X[9 + k] + Rv[k];
 }
-__global__ void __launch_bounds__(kPgThreads) k_pg_retract(PgDev d) { retract_body(d); }
-
-__global__ void __launch_bounds__(kPgThreads) k_pg_unit(PgDev d, int at)
+__global__ void __launch_bounds__(kPgThreads) k_pg_copy(const double* src, double* dst, int n, PgGate gate)
 {
-    const int k = blockIdx.x * blockDim.x + threadIdx.x;
-    if (k < 6 * d.n) d.g[k] = k == at ? 1.0 : 0.0;
-}
-__global__ void __launch_bounds__(kPgThreads) k_pg_copy(const double* src, double* dst, int n)
-{
+    if (gated(gate)) return;
     const int k = blockIdx.x * blockDim.x + threadIdx.x;
     if (k < n) dst[k] = src[k];
 }
@@ -542,225 +587,11 @@ __global__ void __launch_bounds__(kPgThreads) k_pg_store_write(const float* stag
     for (int a = 0; a < 12; a++) frames[k].T[a] = q[6 + a];
 }
 
-// ---- the block form: the kernels above for C right-hand sides at once, column c = blockIdx.y (PgCols in the header).  Each
-// body is its single form's with the column's offsets applied, on the same device functions (mat6_vec, mat6_tvec_add,
-// block_partial, partial_sum) and with blockIdx.x / threadIdx.x in the same roles, so a column's sums run in the single
-// form's order; Binv, M, Pre, C0, Ji, Jj are shared by all columns.
-__device__ inline bool col_stopped(const PgScalars* scs) { return scs && scs[blockIdx.y].stop; }
-
-__global__ void __launch_bounds__(64) k_pg_scan_up0_cols(PgScan sc, size_t ls, const double* in, size_t vs, const PgScalars* scs)
-{
-    if (col_stopped(scs)) return;
-    const int g = blockIdx.x * blockDim.x + threadIdx.x;
-    const int n = sc.n[0], e0 = g * kPgGroup;
-    if (e0 >= n) return;
-    const int e1 = min(e0 + kPgGroup, n);
-    in += blockIdx.y * vs;
-    double* loc0 = sc.loc[0] + blockIdx.y * ls;
-    double v[6] = { 0, 0, 0, 0, 0, 0 };
-    for (int e = e0; e < e1; e++) {
-        const double* x = in + 6 * (size_t)(sc.rev ? n - 1 - e : e);
-        const double xin[6] = { x[0], x[1], x[2], x[3], x[4], x[5] };
-        double c[6], o[6];
-        mat6_vec(sc.C0 + 36 * (size_t)e, xin, c);
-        mat6_vec(sc.M[0] + 36 * (size_t)e, v, o);
-        for (int a = 0; a < 6; a++) { v[a] = o[a] + c[a]; loc0[6 * (size_t)e + a] = v[a]; }
-    }
-}
-__global__ void __launch_bounds__(64) k_pg_scan_up_cols(PgScan sc, size_t ls, int lvl, const PgScalars* scs)
-{
-    if (col_stopped(scs)) return;
-    const int g = blockIdx.x * blockDim.x + threadIdx.x;
-    const int n = sc.n[lvl], e0 = g * kPgGroup;
-    if (e0 >= n) return;
-    const int e1 = min(e0 + kPgGroup, n);
-    const double* below = sc.loc[lvl - 1] + blockIdx.y * ls;
-    double* here = sc.loc[lvl] + blockIdx.y * ls;
-    double v[6] = { 0, 0, 0, 0, 0, 0 };
-    for (int e = e0; e < e1; e++) {
-        const int last = min(e * kPgGroup + kPgGroup, sc.n[lvl - 1]) - 1;
-        const double* c = below + 6 * (size_t)last;
-        double o[6];
-        mat6_vec(sc.M[lvl] + 36 * (size_t)e, v, o);
-        for (int a = 0; a < 6; a++) { v[a] = o[a] + c[a]; here[6 * (size_t)e + a] = v[a]; }
-    }
-}
-__global__ void __launch_bounds__(kPgThreads) k_pg_scan_down_cols(PgScan sc, size_t ls, int lvl, double* out, size_t vs, const PgScalars* scs)
-{
-    if (col_stopped(scs)) return;
-    const int e = blockIdx.x * blockDim.x + threadIdx.x;
-    const int n = sc.n[lvl];
-    if (e >= n) return;
-    const int g = e / kPgGroup;
-    double* here = sc.loc[lvl] + blockIdx.y * ls;
-    double v[6];
-    for (int a = 0; a < 6; a++) v[a] = here[6 * (size_t)e + a];
-    if (g > 0) {
-        const double* xin = sc.loc[lvl + 1] + blockIdx.y * ls + 6 * (size_t)(g - 1);
-        const double x6[6] = { xin[0], xin[1], xin[2], xin[3], xin[4], xin[5] };
-        double o[6];
-        mat6_vec(sc.Pre[lvl] + 36 * (size_t)e, x6, o);
-        for (int a = 0; a < 6; a++) v[a] += o[a];
-    }
-    double* dst = lvl == 0 ? out + blockIdx.y * vs + 6 * (size_t)(sc.rev ? n - 1 - e : e) : here + 6 * (size_t)e;
-    for (int a = 0; a < 6; a++) dst[a] = v[a];
-}
-
-__global__ void __launch_bounds__(kPgThreads) k_pg_extra_u_cols(PgDev d, PgCols s, const double* x, const PgScalars* scs)
-{
-    if (col_stopped(scs)) return;
-    const int f = blockIdx.x * blockDim.x + threadIdx.x;
-    if (f >= d.n_extra) return;
-    x += blockIdx.y * s.vec;
-    double* u = d.u + blockIdx.y * s.u;
-    const PgFactor& fac = d.extra[f];
-    double xi[6], o[6], o2[6] = { 0, 0, 0, 0, 0, 0 };
-    for (int a = 0; a < 6; a++) xi[a] = x[6 * (size_t)fac.i + a];
-    mat6_vec(d.Ji + 36 * (size_t)f, xi, o);
-    if (fac.type == kPgBetween) {
-        for (int a = 0; a < 6; a++) xi[a] = x[6 * (size_t)fac.j + a];
-        mat6_vec(d.Jj + 36 * (size_t)f, xi, o2);
-    }
-    for (int a = 0; a < 6; a++) u[6 * (size_t)f + a] = o[a] + o2[a];
-}
-__global__ void __launch_bounds__(kPgThreads) k_pg_extra_gather_cols(PgDev d, PgCols s, const PgScalars* scs)
-{
-    if (col_stopped(scs)) return;
-    const int k = blockIdx.x * blockDim.x + threadIdx.x;
-    if (k >= d.n) return;
-    const double* u = d.u + blockIdx.y * s.u;
-    double* g = d.g + blockIdx.y * s.vec;
-    double acc[6] = { 0, 0, 0, 0, 0, 0 };
-    for (int q = d.inc_start[k]; q < d.inc_start[k + 1]; q++) {
-        const PgIncidence in = d.inc[q];
-        double uf[6];
-        for (int a = 0; a < 6; a++) uf[a] = u[6 * (size_t)in.factor + a];
-        mat6_tvec_add((in.side ? d.Jj : d.Ji) + 36 * (size_t)in.factor, uf, acc);
-    }
-    for (int a = 0; a < 6; a++) g[6 * (size_t)k + a] = acc[a];
-}
-
-__global__ void __launch_bounds__(kPgThreads) k_pg_cg_init_cols(PgDev d, PgCols s)
-{
-    const size_t at = blockIdx.y * s.vec;
-    const double* b = d.b + at;
-    double *y = d.y + at, *r = d.r + at, *p = d.p + at;
-    double a = 0.0;
-    for (int k = blockIdx.x * kPgThreads + threadIdx.x; k < 6 * d.n; k += kPgDotBlocks * kPgThreads) {
-        const double v = b[k];
-        y[k] = 0.0; r[k] = v; p[k] = v;
-        a += v * v;
-    }
-    block_partial(a, d.partial + blockIdx.y * kPgDotBlocks);
-}
-__global__ void k_pg_cg_init2_cols(PgDev d, double tol, int max_iters)
-{
-    PgScalars* sc = d.sc + blockIdx.y;
-    const double bb = partial_sum(d.partial + blockIdx.y * kPgDotBlocks);
-    sc->rr = bb; sc->bb = bb; sc->tol2 = tol * tol;
-    sc->iters = 0; sc->max_iters = max_iters;
-    sc->stop = (bb == 0.0 || max_iters <= 0) ? 1 : 0;
-}
-__global__ void __launch_bounds__(kPgThreads) k_pg_cg_q_cols(PgDev d, PgCols s, int have_t2)
-{
-    if (d.sc[blockIdx.y].stop) return;
-    const size_t at = blockIdx.y * s.vec;
-    const double *pv = d.p + at, *t2 = d.t2 + at;
-    double* qv = d.q + at;
-    double a = 0.0;
-    for (int k = blockIdx.x * kPgThreads + threadIdx.x; k < 6 * d.n; k += kPgDotBlocks * kPgThreads) {
-        const double p = pv[k], q = p + (have_t2 ? t2[k] : 0.0);
-        qv[k] = q;
-        a += p * q;
-    }
-    block_partial(a, d.partial + blockIdx.y * kPgDotBlocks);
-}
-__global__ void k_pg_cg_alpha_cols(PgDev d)
-{
-    PgScalars* sc = d.sc + blockIdx.y;
-    if (sc->stop) return;
-    const double pq = partial_sum(d.partial + blockIdx.y * kPgDotBlocks);
-    sc->pq = pq;
-    sc->alpha = pq > 0.0 ? sc->rr / pq : 0.0;
-}
-__global__ void __launch_bounds__(kPgThreads) k_pg_cg_update_cols(PgDev d, PgCols s)
-{
-    if (d.sc[blockIdx.y].stop) return;
-    const size_t at = blockIdx.y * s.vec;
-    const double *pv = d.p + at, *qv = d.q + at;
-    double *y = d.y + at, *rv = d.r + at;
-    const double alpha = d.sc[blockIdx.y].alpha;
-    double a = 0.0;
-    for (int k = blockIdx.x * kPgThreads + threadIdx.x; k < 6 * d.n; k += kPgDotBlocks * kPgThreads) {
-        y[k] += alpha * pv[k];
-        const double r = rv[k] - alpha * qv[k];
-        rv[k] = r;
-        a += r * r;
-    }
-    block_partial(a, d.partial + blockIdx.y * kPgDotBlocks);
-}
-__global__ void k_pg_cg_beta_cols(PgDev d)
-{
-    PgScalars* sc = d.sc + blockIdx.y;
-    if (sc->stop) return;
-    const double rr = partial_sum(d.partial + blockIdx.y * kPgDotBlocks);
-    sc->beta = sc->rr > 0.0 ? rr / sc->rr : 0.0;
-    sc->rr = rr;
-    sc->iters += 1;
-    if (!(rr > sc->tol2 * sc->bb) || sc->iters >= sc->max_iters || !(sc->pq > 0.0)) sc->stop = 1;
-}
-__global__ void __launch_bounds__(kPgThreads) k_pg_cg_p_cols(PgDev d, PgCols s)
-{
-    if (d.sc[blockIdx.y].stop) return;
-    const int k = blockIdx.x * blockDim.x + threadIdx.x;
-    const size_t at = blockIdx.y * s.vec;
-    if (k < 6 * d.n) d.p[at + k] = d.r[at + k] + d.sc[blockIdx.y].beta * d.p[at + k];
-}
-
-__global__ void __launch_bounds__(kPgThreads) k_pg_unit_cols(PgDev d, PgCols s, PgColAt at)
-{
-    const int k = blockIdx.x * blockDim.x + threadIdx.x;
-    if (k < 6 * d.n) d.g[blockIdx.y * s.vec + k] = k == at.v[blockIdx.y] ? 1.0 : 0.0;
-}
-// the wanted rows of every column's delta, so that one copy brings a pass's result to the host
-__global__ void __launch_bounds__(64) k_pg_rows_cols(PgDev d, PgCols s, PgColAt ka, PgColAt kb, double* rows)
-{
-    const int t = threadIdx.x;
-    if (t >= 12) return;
-    const int key = t < 6 ? ka.v[blockIdx.y] : kb.v[blockIdx.y];
-    const bool in = key >= 0 && key < d.n;
-    rows[12 * (size_t)blockIdx.y + t] = in ? d.delta[blockIdx.y * s.vec + 6 * (size_t)key + t % 6] : 0.0;
-}
-
 // ---- the launched optimise (s2m_pg_optimize_launch): the outer loop's decisions on the device.  PgRecord (in the header) holds
 // the result and three gates, each "nonzero = return at the head": skip_head (rhs and CG begin of a step), skip_tail (the step,
-// the trial point's linearisation and the close) and skip_keep (trial -> estimate).  A kernel reads its gate before anything
-// else and no kernel waits for another; the kernels of s2m_pg_optimize run between them unchanged (the scans and the extra
-// factors' products take the gate as their stop pointer, the CG iterations stop by sc->stop as ever).
-__global__ void __launch_bounds__(kPgThreads) k_pg_linearize_g(PgDev d, const double* X, const int32_t* skip) { if (*skip) return; linearize_body(d, X); }
-__global__ void __launch_bounds__(kPgThreads) k_pg_err_reduce_g(PgDev d, const int32_t* skip) { if (*skip) return; err_reduce_body(d); }
-__global__ void __launch_bounds__(kPgThreads) k_pg_scan_m0_g(PgDev d, const int32_t* skip) { if (*skip) return; scan_m0_body(d); }
-__global__ void __launch_bounds__(kPgThreads) k_pg_scan_pre_g(const double* M, double* Pre, double* Mnext, int n, const int32_t* skip)
-{
-    if (*skip) return;
-    scan_pre_body(M, Pre, Mnext, n);
-}
-__global__ void __launch_bounds__(kPgThreads) k_pg_rhs_g(PgDev d, int have_t2, const int32_t* skip) { if (*skip) return; rhs_body(d, have_t2); }
-__global__ void __launch_bounds__(kPgThreads) k_pg_cg_init_g(PgDev d, const int32_t* skip) { if (*skip) return; cg_init_body(d); }
-__global__ void __launch_bounds__(kPgThreads) k_pg_retract_g(PgDev d, const int32_t* skip) { if (*skip) return; retract_body(d); }
-__global__ void __launch_bounds__(kPgThreads) k_pg_copy_g(const double* src, double* dst, int n, const int32_t* skip)
-{
-    if (*skip) return;
-    const int k = blockIdx.x * blockDim.x + threadIdx.x;
-    if (k < n) dst[k] = src[k];
-}
-// the CG begin of a step that was opened; the head is closed behind it.  After `done` it is not opened again.
-__global__ void k_pg_cg_init2_g(PgDev d, double tol, int max_iters, PgRecord* rec)
-{
-    if (rec->skip_head) return;
-    cg_init2_body(d, tol, max_iters);
-    rec->skip_head = 1;
-}
+// the trial point's linearisation and the close) and skip_keep (trial -> estimate).  The kernels of s2m_pg_optimize run between
+// the four below with a record gate as their PgGate (the CG iterations stop by sc->stop as ever); no kernel waits for another.
+
 // behind the linearisation at the launch-time estimates: the record of s2m_pg_optimize before its first step
 __global__ void k_pg_open(PgDev d, PgRecord* rec, int max_iterations, double abs_tol, double rel_tol)
 {
@@ -806,143 +637,130 @@ __global__ void __launch_bounds__(kPgThreads) k_pg_keep(PgDev d, const PgRecord*
 
 inline int blocks_for(int n) { return (n + kPgThreads - 1) / kPgThreads; }
 
-// out = scan applied to in (both in key order)
-void scan_solve(hipStream_t s, const PgScan& sc, const double* in, double* out, const int32_t* stop)
-{
-    for (int l = 0; l < sc.levels; l++) {
-        const int groups = (sc.n[l] + kPgGroup - 1) / kPgGroup;
-        if (l == 0) k_pg_scan_up0<<<(groups + 63) / 64, 64, 0, s>>>(sc, in, stop);
-        else k_pg_scan_up<<<(groups + 63) / 64, 64, 0, s>>>(sc, l, stop);
-    }
-    for (int l = sc.levels - 2; l >= 1; l--) k_pg_scan_down<<<blocks_for(sc.n[l]), kPgThreads, 0, s>>>(sc, l, out, stop);
-    k_pg_scan_down<<<blocks_for(sc.n[0]), kPgThreads, 0, s>>>(sc, 0, out, stop);
-}
-
-void scan_build(hipStream_t s, const PgScan& sc)
-{
-    for (int l = 0; l < sc.levels; l++) {
-        const int groups = (sc.n[l] + kPgGroup - 1) / kPgGroup;
-        k_pg_scan_pre<<<blocks_for(groups * 6), kPgThreads, 0, s>>>(sc.M[l], sc.Pre[l], l + 1 < sc.levels ? sc.M[l + 1] : nullptr, sc.n[l]);
-    }
-}
-
-// t2 = K^T u for the u already in d.u
-void kt_apply(hipStream_t s, const PgDev& d, const int32_t* stop)
-{
-    k_pg_extra_gather<<<blocks_for(d.n), kPgThreads, 0, s>>>(d, d.u, d.g, stop);
-    scan_solve(s, d.bwd, d.g, d.t2, stop);
-}
-
-// the block form of scan_solve: every launch serves all columns (grid row = column)
-void scan_solve_cols(hipStream_t s, const PgScan& sc, size_t ls, const double* in, double* out, const PgCols& c, const PgScalars* scs)
+// out = scan applied to in (both in key order), for every column (grid row = column); ls: c.loc_f or c.loc_b, the scan's
+void scan_solve(hipStream_t s, const PgScan& sc, size_t ls, const double* in, double* out, const PgCols& c, PgGate gate)
 {
     const unsigned C = (unsigned)c.cols;
     for (int l = 0; l < sc.levels; l++) {
         const int groups = (sc.n[l] + kPgGroup - 1) / kPgGroup;
-        if (l == 0) k_pg_scan_up0_cols<<<dim3((groups + 63) / 64, C), 64, 0, s>>>(sc, ls, in, c.vec, scs);
-        else k_pg_scan_up_cols<<<dim3((groups + 63) / 64, C), 64, 0, s>>>(sc, ls, l, scs);
+        if (l == 0) k_pg_scan_up0<<<dim3((groups + 63) / 64, C), 64, 0, s>>>(sc, ls, in, c.vec, gate);
+        else k_pg_scan_up<<<dim3((groups + 63) / 64, C), 64, 0, s>>>(sc, ls, l, gate);
     }
-    for (int l = sc.levels - 2; l >= 1; l--) k_pg_scan_down_cols<<<dim3(blocks_for(sc.n[l]), C), kPgThreads, 0, s>>>(sc, ls, l, out, c.vec, scs);
-    k_pg_scan_down_cols<<<dim3(blocks_for(sc.n[0]), C), kPgThreads, 0, s>>>(sc, ls, 0, out, c.vec, scs);
+    for (int l = sc.levels - 2; l >= 1; l--) k_pg_scan_down<<<dim3(blocks_for(sc.n[l]), C), kPgThreads, 0, s>>>(sc, ls, l, out, c.vec, gate);
+    k_pg_scan_down<<<dim3(blocks_for(sc.n[0]), C), kPgThreads, 0, s>>>(sc, ls, 0, out, c.vec, gate);
+}
+
+void scan_build(hipStream_t s, const PgScan& sc, PgGate gate)
+{
+    for (int l = 0; l < sc.levels; l++) {
+        const int groups = (sc.n[l] + kPgGroup - 1) / kPgGroup;
+        k_pg_scan_pre<<<blocks_for(groups * 6), kPgThreads, 0, s>>>(sc.M[l], sc.Pre[l], l + 1 < sc.levels ? sc.M[l + 1] : nullptr, sc.n[l], gate);
+    }
+}
+
+// t2 = K^T u for the u already in d.u
+void kt_apply(hipStream_t s, const PgDev& d, const PgCols& c, PgGate gate)
+{
+    k_pg_extra_gather<<<dim3(blocks_for(d.n), c.cols), kPgThreads, 0, s>>>(d, c, gate);
+    scan_solve(s, d.bwd, c.loc_b, d.g, d.t2, c, gate);
 }
 
 bool cols_ok(const PgDev& d, const PgCols& c) { return d.n > 0 && c.cols >= 1 && c.cols <= kPgBlockCols; }
 
 }  // namespace
 
-hipError_t pg_bwd_unit_cols(hipStream_t s, const PgDev& d, const PgCols& c, const PgColAt& at)
+hipError_t pg_linearize(hipStream_t s, const PgDev& d, const double* X, PgGate gate)
 {
-    if (!cols_ok(d, c)) return hipErrorInvalidValue;
-    k_pg_unit_cols<<<dim3(blocks_for(6 * d.n), c.cols), kPgThreads, 0, s>>>(d, c, at);
-    scan_solve_cols(s, d.bwd, c.loc_b, d.g, d.b, c, nullptr);
+    if (d.n <= 0) return hipSuccess;
+    k_pg_linearize<<<blocks_for(d.n + d.n_extra), kPgThreads, 0, s>>>(d, X, gate);
+    k_pg_err_reduce<<<1, kPgThreads, 0, s>>>(d, gate);
+    k_pg_scan_m0<<<blocks_for(d.n), kPgThreads, 0, s>>>(d, gate);
+    scan_build(s, d.fwd, gate);
+    scan_build(s, d.bwd, gate);
     return hipGetLastError();
 }
 
-hipError_t pg_cg_begin_cols(hipStream_t s, const PgDev& d, const PgCols& c, double tol, int max_iters)
+hipError_t pg_rhs(hipStream_t s, const PgDev& d, PgGate gate)
 {
-    if (!cols_ok(d, c)) return hipErrorInvalidValue;
-    k_pg_cg_init_cols<<<dim3(kPgDotBlocks, c.cols), kPgThreads, 0, s>>>(d, c);
-    k_pg_cg_init2_cols<<<dim3(1, c.cols), 1, 0, s>>>(d, tol, max_iters);
+    if (d.n_extra > 0) {
+        k_pg_copy<<<blocks_for(6 * d.n_extra), kPgThreads, 0, s>>>(d.rx, d.u, 6 * d.n_extra, gate);
+        kt_apply(s, d, kPgOne, gate);
+    }
+    k_pg_rhs<<<blocks_for(6 * d.n), kPgThreads, 0, s>>>(d, d.n_extra > 0, gate);
     return hipGetLastError();
 }
 
-hipError_t pg_cg_iterations_cols(hipStream_t s, const PgDev& d, const PgCols& c, int count)
+hipError_t pg_step(hipStream_t s, const PgDev& d, PgGate gate)
+{
+    scan_solve(s, d.fwd, 0, d.y, d.delta, kPgOne, gate);
+    k_pg_retract<<<blocks_for(d.n), kPgThreads, 0, s>>>(d, gate);
+    return hipGetLastError();
+}
+
+hipError_t pg_retract(hipStream_t s, const PgDev& d)
+{
+    if (d.n <= 0) return hipErrorInvalidValue;
+    k_pg_retract<<<blocks_for(d.n), kPgThreads, 0, s>>>(d, PgGate{});
+    return hipGetLastError();
+}
+
+hipError_t pg_bwd_unit(hipStream_t s, const PgDev& d, const PgCols& c, const PgColAt& at)
+{
+    if (!cols_ok(d, c)) return hipErrorInvalidValue;
+    k_pg_unit<<<dim3(blocks_for(6 * d.n), c.cols), kPgThreads, 0, s>>>(d, c, at);
+    scan_solve(s, d.bwd, c.loc_b, d.g, d.b, c, PgGate{});
+    return hipGetLastError();
+}
+
+hipError_t pg_cg_begin(hipStream_t s, const PgDev& d, const PgCols& c, double tol, int max_iters, PgGate gate, int32_t* close)
+{
+    if (!cols_ok(d, c)) return hipErrorInvalidValue;
+    k_pg_cg_init<<<dim3(kPgDotBlocks, c.cols), kPgThreads, 0, s>>>(d, c, gate);
+    k_pg_cg_init2<<<dim3(1, c.cols), 1, 0, s>>>(d, tol, max_iters, gate, close);
+    return hipGetLastError();
+}
+
+hipError_t pg_cg_iterations(hipStream_t s, const PgDev& d, const PgCols& c, int count)
 {
     if (!cols_ok(d, c)) return hipErrorInvalidValue;
     const unsigned C = (unsigned)c.cols;
+    const PgGate stop{ &d.sc->stop, sizeof(PgScalars) };   // column c runs until its sc[c].stop
     for (int it = 0; it < count; it++) {
         if (d.n_extra > 0) {
-            scan_solve_cols(s, d.fwd, c.loc_f, d.p, d.t1, c, d.sc);
-            k_pg_extra_u_cols<<<dim3(blocks_for(d.n_extra), C), kPgThreads, 0, s>>>(d, c, d.t1, d.sc);
-            k_pg_extra_gather_cols<<<dim3(blocks_for(d.n), C), kPgThreads, 0, s>>>(d, c, d.sc);
-            scan_solve_cols(s, d.bwd, c.loc_b, d.g, d.t2, c, d.sc);
+            scan_solve(s, d.fwd, c.loc_f, d.p, d.t1, c, stop);
+            k_pg_extra_u<<<dim3(blocks_for(d.n_extra), C), kPgThreads, 0, s>>>(d, c, d.t1, stop);
+            kt_apply(s, d, c, stop);
         }
-        k_pg_cg_q_cols<<<dim3(kPgDotBlocks, C), kPgThreads, 0, s>>>(d, c, d.n_extra > 0);
-        k_pg_cg_alpha_cols<<<dim3(1, C), 1, 0, s>>>(d);
-        k_pg_cg_update_cols<<<dim3(kPgDotBlocks, C), kPgThreads, 0, s>>>(d, c);
-        k_pg_cg_beta_cols<<<dim3(1, C), 1, 0, s>>>(d);
-        k_pg_cg_p_cols<<<dim3(blocks_for(6 * d.n), C), kPgThreads, 0, s>>>(d, c);
+        k_pg_cg_q<<<dim3(kPgDotBlocks, C), kPgThreads, 0, s>>>(d, c, d.n_extra > 0);
+        k_pg_cg_alpha<<<dim3(1, C), 1, 0, s>>>(d);
+        k_pg_cg_update<<<dim3(kPgDotBlocks, C), kPgThreads, 0, s>>>(d, c);
+        k_pg_cg_beta<<<dim3(1, C), 1, 0, s>>>(d);
+        k_pg_cg_p<<<dim3(blocks_for(6 * d.n), C), kPgThreads, 0, s>>>(d, c);
     }
     return hipGetLastError();
 }
 
-hipError_t pg_fwd_y_cols(hipStream_t s, const PgDev& d, const PgCols& c)
+hipError_t pg_fwd_y(hipStream_t s, const PgDev& d, const PgCols& c)
 {
     if (!cols_ok(d, c)) return hipErrorInvalidValue;
-    scan_solve_cols(s, d.fwd, c.loc_f, d.y, d.delta, c, nullptr);
+    scan_solve(s, d.fwd, c.loc_f, d.y, d.delta, c, PgGate{});
     return hipGetLastError();
 }
 
-hipError_t pg_rows_cols(hipStream_t s, const PgDev& d, const PgCols& c, const PgColAt& ka, const PgColAt& kb, double* rows)
+hipError_t pg_rows(hipStream_t s, const PgDev& d, const PgCols& c, const PgColAt& ka, const PgColAt& kb, double* rows)
 {
     if (!cols_ok(d, c)) return hipErrorInvalidValue;
-    k_pg_rows_cols<<<dim3(1, c.cols), 64, 0, s>>>(d, c, ka, kb, rows);
+    k_pg_rows<<<dim3(1, c.cols), 64, 0, s>>>(d, c, ka, kb, rows);
     return hipGetLastError();
 }
 
-hipError_t pg_linearize(hipStream_t s, const PgDev& d, const double* X)
+hipError_t pg_apply(hipStream_t s, const PgDev& d, const PgCols& c, int op)
 {
-    if (d.n <= 0) return hipSuccess;
-    k_pg_linearize<<<blocks_for(d.n + d.n_extra), kPgThreads, 0, s>>>(d, X);
-    k_pg_err_reduce<<<1, kPgThreads, 0, s>>>(d);
-    k_pg_scan_m0<<<blocks_for(d.n), kPgThreads, 0, s>>>(d);
-    scan_build(s, d.fwd);
-    scan_build(s, d.bwd);
-    return hipGetLastError();
-}
-
-hipError_t pg_rhs(hipStream_t s, const PgDev& d)
-{
-    if (d.n_extra > 0) {
-        k_pg_copy<<<blocks_for(6 * d.n_extra), kPgThreads, 0, s>>>(d.rx, d.u, 6 * d.n_extra);
-        kt_apply(s, d, nullptr);
-    }
-    k_pg_rhs<<<blocks_for(6 * d.n), kPgThreads, 0, s>>>(d, d.n_extra > 0);
-    return hipGetLastError();
-}
-
-hipError_t pg_cg_begin(hipStream_t s, const PgDev& d, double tol, int max_iters)
-{
-    k_pg_cg_init<<<kPgDotBlocks, kPgThreads, 0, s>>>(d);
-    k_pg_cg_init2<<<1, 1, 0, s>>>(d, tol, max_iters);
-    return hipGetLastError();
-}
-
-hipError_t pg_cg_iterations(hipStream_t s, const PgDev& d, int count)
-{
-    const int32_t* stop = &d.sc->stop;
-    for (int it = 0; it < count; it++) {
-        if (d.n_extra > 0) {
-            scan_solve(s, d.fwd, d.p, d.t1, stop);
-            k_pg_extra_u<<<blocks_for(d.n_extra), kPgThreads, 0, s>>>(d, d.t1, d.u, stop);
-            kt_apply(s, d, stop);
-        }
-        k_pg_cg_q<<<kPgDotBlocks, kPgThreads, 0, s>>>(d, d.n_extra > 0);
-        k_pg_cg_alpha<<<1, 1, 0, s>>>(d);
-        k_pg_cg_update<<<kPgDotBlocks, kPgThreads, 0, s>>>(d);
-        k_pg_cg_beta<<<1, 1, 0, s>>>(d);
-        k_pg_cg_p<<<blocks_for(6 * d.n), kPgThreads, 0, s>>>(d);
-    }
+    if (!cols_ok(d, c) || op < 0 || op > 3 || (op >= 2 && d.n_extra <= 0)) return hipErrorInvalidValue;
+    if (op == 0 || op == 2) scan_solve(s, d.fwd, c.loc_f, d.p, d.t1, c, PgGate{});
+    if (op == 1) scan_solve(s, d.bwd, c.loc_b, d.g, d.t2, c, PgGate{});
+    if (op == 2) k_pg_extra_u<<<dim3(blocks_for(d.n_extra), c.cols), kPgThreads, 0, s>>>(d, c, d.t1, PgGate{});
+    if (op == 3) kt_apply(s, d, c, PgGate{});
     return hipGetLastError();
 }
 
@@ -958,82 +776,16 @@ hipError_t pg_async_open(hipStream_t s, const PgDev& d, PgRecord* rec, int max_i
 hipError_t pg_async_segment(hipStream_t s, const PgDev& d, PgRecord* rec, double tol, int max_cg, int cg_chunk)
 {
     if (d.n <= 0 || cg_chunk <= 0) return hipErrorInvalidValue;
-    const int32_t *head = &rec->skip_head, *tail = &rec->skip_tail;
-    // head of a step: pg_rhs and pg_cg_begin
-    if (d.n_extra > 0) {
-        k_pg_copy_g<<<blocks_for(6 * d.n_extra), kPgThreads, 0, s>>>(d.rx, d.u, 6 * d.n_extra, head);
-        kt_apply(s, d, head);
-    }
-    k_pg_rhs_g<<<blocks_for(6 * d.n), kPgThreads, 0, s>>>(d, d.n_extra > 0, head);
-    k_pg_cg_init_g<<<kPgDotBlocks, kPgThreads, 0, s>>>(d, head);
-    k_pg_cg_init2_g<<<1, 1, 0, s>>>(d, tol, max_cg, rec);
-    hipError_t e = pg_cg_iterations(s, d, cg_chunk);
-    if (e != hipSuccess) return e;
+    const PgGate head{ &rec->skip_head, 0 }, tail{ &rec->skip_tail, 0 };
+    hipError_t e;
+    // head of a step; the CG begin shuts it again
+    if ((e = pg_rhs(s, d, head)) || (e = pg_cg_begin(s, d, kPgOne, tol, max_cg, head, &rec->skip_head))) return e;
+    if ((e = pg_cg_iterations(s, d, kPgOne, cg_chunk))) return e;
     k_pg_gate<<<1, 1, 0, s>>>(d, rec);
-    // tail: pg_step, pg_linearize at the trial point, the close
-    scan_solve(s, d.fwd, d.y, d.delta, tail);
-    k_pg_retract_g<<<blocks_for(d.n), kPgThreads, 0, s>>>(d, tail);
-    k_pg_linearize_g<<<blocks_for(d.n + d.n_extra), kPgThreads, 0, s>>>(d, d.Xtrial, tail);
-    k_pg_err_reduce_g<<<1, kPgThreads, 0, s>>>(d, tail);
-    k_pg_scan_m0_g<<<blocks_for(d.n), kPgThreads, 0, s>>>(d, tail);
-    for (const PgScan* sc : { &d.fwd, &d.bwd })
-        for (int l = 0; l < sc->levels; l++) {
-            const int groups = (sc->n[l] + kPgGroup - 1) / kPgGroup;
-            k_pg_scan_pre_g<<<blocks_for(groups * 6), kPgThreads, 0, s>>>(sc->M[l], sc->Pre[l], l + 1 < sc->levels ? sc->M[l + 1] : nullptr, sc->n[l], tail);
-        }
+    // tail: the step, the trial point's linearisation, the close
+    if ((e = pg_step(s, d, tail)) || (e = pg_linearize(s, d, d.Xtrial, tail))) return e;
     k_pg_close<<<1, 1, 0, s>>>(d, rec);
     k_pg_keep<<<blocks_for(12 * d.n), kPgThreads, 0, s>>>(d, rec);
-    return hipGetLastError();
-}
-
-hipError_t pg_fwd_y(hipStream_t s, const PgDev& d)
-{
-    scan_solve(s, d.fwd, d.y, d.delta, nullptr);
-    return hipGetLastError();
-}
-
-hipError_t pg_apply(hipStream_t s, const PgDev& d, int op)
-{
-    if (d.n <= 0 || op < 0 || op > 3 || (op >= 2 && d.n_extra <= 0)) return hipErrorInvalidValue;
-    if (op == 0 || op == 2) scan_solve(s, d.fwd, d.p, d.t1, nullptr);
-    if (op == 1) scan_solve(s, d.bwd, d.g, d.t2, nullptr);
-    if (op == 2) k_pg_extra_u<<<blocks_for(d.n_extra), kPgThreads, 0, s>>>(d, d.t1, d.u, nullptr);
-    if (op == 3) kt_apply(s, d, nullptr);
-    return hipGetLastError();
-}
-
-hipError_t pg_apply_cols(hipStream_t s, const PgDev& d, const PgCols& c, int op)
-{
-    if (!cols_ok(d, c) || op < 0 || op > 3 || (op >= 2 && d.n_extra <= 0)) return hipErrorInvalidValue;
-    const unsigned C = (unsigned)c.cols;
-    if (op == 0 || op == 2) scan_solve_cols(s, d.fwd, c.loc_f, d.p, d.t1, c, nullptr);
-    if (op == 1) scan_solve_cols(s, d.bwd, c.loc_b, d.g, d.t2, c, nullptr);
-    if (op == 2) k_pg_extra_u_cols<<<dim3(blocks_for(d.n_extra), C), kPgThreads, 0, s>>>(d, c, d.t1, nullptr);
-    if (op == 3) {
-        k_pg_extra_gather_cols<<<dim3(blocks_for(d.n), C), kPgThreads, 0, s>>>(d, c, nullptr);
-        scan_solve_cols(s, d.bwd, c.loc_b, d.g, d.t2, c, nullptr);
-    }
-    return hipGetLastError();
-}
-
-hipError_t pg_retract(hipStream_t s, const PgDev& d)
-{
-    if (d.n <= 0) return hipErrorInvalidValue;
-    k_pg_retract<<<blocks_for(d.n), kPgThreads, 0, s>>>(d);
-    return hipGetLastError();
-}
-
-hipError_t pg_step(hipStream_t s, const PgDev& d)
-{
-    scan_solve(s, d.fwd, d.y, d.delta, nullptr);
-    k_pg_retract<<<blocks_for(d.n), kPgThreads, 0, s>>>(d);
-    return hipGetLastError();
-}
-
-hipError_t pg_bwd_unit(hipStream_t s, const PgDev& d, int key, int axis)
-{
-    k_pg_unit<<<blocks_for(6 * d.n), kPgThreads, 0, s>>>(d, 6 * key + axis);
-    scan_solve(s, d.bwd, d.g, d.b, nullptr);
     return hipGetLastError();
 }
 

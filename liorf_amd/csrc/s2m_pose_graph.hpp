@@ -59,44 +59,52 @@ struct PgDev {
     PgScalars* sc;
 };
 
-hipError_t pg_linearize(hipStream_t s, const PgDev& d, const double* X);           // -> Binv, Aof, rc, Ji, Jj, rx, ferr, fw, both scans, sc->err / wmin
-hipError_t pg_rhs(hipStream_t s, const PgDev& d);                                 // b = -(r_c + K^T r_x)
-hipError_t pg_cg_begin(hipStream_t s, const PgDev& d, double tol, int max_iters); // y = 0, r = p = b
-hipError_t pg_cg_iterations(hipStream_t s, const PgDev& d, int count);            // each a no-op once sc->stop is set
-hipError_t pg_step(hipStream_t s, const PgDev& d);                                // delta = J_c^-1 y, Xtrial = X (+) delta
-hipError_t pg_bwd_unit(hipStream_t s, const PgDev& d, int key, int axis);         // b = J_c^-T e_(6 key + axis)
-hipError_t pg_fwd_y(hipStream_t s, const PgDev& d);                               // delta = J_c^-1 y
-// One operator of the linearisation on the work vectors, by the launches pg_cg_iterations queues (the observation hooks of
-// include/liorf_s2m_debug.h): 0: t1 = J_c^-1 p;  1: t2 = J_c^-T g;  2: u = K p (t1 = J_c^-1 p on the way);  3: t2 = K^T u (through g).
-// 2 and 3 need an extra factor.
-hipError_t pg_apply(hipStream_t s, const PgDev& d, int op);
-hipError_t pg_retract(hipStream_t s, const PgDev& d);                             // Xtrial = X (+) delta
-
-// ---- the block form of the linear solve: C <= kPgBlockCols right-hand sides advance in lockstep through shared launches,
-// column c = grid row c (blockIdx.y).  `d` is a copy of the graph's PgDev whose vectors b .. delta, u, partial, sc and the
-// scans' loc[] point at column 0 of block storage; column c lies `vec` (`u`, `loc_f`, `loc_b`) doubles further on, its
-// kPgDotBlocks partials at partial + c kPgDotBlocks, its scalars at sc + c.  Every column runs the single form's per-column
-// code with the single form's assignment of elements to lanes and workgroups, and stops by its own flag, so column c is
-// bit for bit the single solve of the same right-hand side.
+// ---- One family of kernels serves the optimise, the marginals and the launched optimise.
+// Columns.  Every kernel of the linear solve (the chain scans, the extra factors' products, the CG steps, the unit vector)
+// takes its column from its grid row (blockIdx.y): C <= kPgBlockCols right-hand sides advance in lockstep through shared
+// launches.  `d` is then a copy of the graph's PgDev whose vectors b .. delta, u, partial, sc and the scans' loc[] point at
+// column 0 of block storage; column c lies `vec` (`u`, `loc_f`, `loc_b`) doubles further on, its kPgDotBlocks partials at
+// partial + c kPgDotBlocks, its scalars at sc + c, and it stops by its own flag.  The single solve is kPgOne on the graph's own
+// PgDev.  Since one kernel serves both, with the same assignment of elements to lanes and workgroups whatever the number of
+// columns, column c is by construction bit for bit the single solve of the same right-hand side.
 struct PgCols {
     int32_t cols, pad;
     size_t vec, u, loc_f, loc_b;
 };
+constexpr PgCols kPgOne{ 1, 0, 0, 0, 0, 0 };        // one column: no stride is ever applied
 struct PgColAt { int32_t v[kPgBlockCols]; };
-hipError_t pg_bwd_unit_cols(hipStream_t s, const PgDev& d, const PgCols& c, const PgColAt& at);   // b_c = J_c^-T e_(at[c])
-hipError_t pg_cg_begin_cols(hipStream_t s, const PgDev& d, const PgCols& c, double tol, int max_iters);
-hipError_t pg_cg_iterations_cols(hipStream_t s, const PgDev& d, const PgCols& c, int count);      // a stopped column is not touched
-hipError_t pg_fwd_y_cols(hipStream_t s, const PgDev& d, const PgCols& c);                         // delta_c = J_c^-1 y_c
-hipError_t pg_apply_cols(hipStream_t s, const PgDev& d, const PgCols& c, int op);                 // pg_apply on every column
+// Gates.  Every kernel but the CG iteration's own (they stop by sc[c].stop) takes a PgGate and reads it first, before any
+// other load: the int32 at base + c * stride bytes, nonzero = return at the head; a null base = run.  stride is
+// sizeof(PgScalars) where column c stops by sc[c].stop (the scans and products inside a CG iteration) and 0 for a gate of
+// the launched optimise's record.  No kernel waits for another.
+struct PgGate {
+    const int32_t* base;
+    size_t stride;
+};
+
+hipError_t pg_linearize(hipStream_t s, const PgDev& d, const double* X, PgGate gate = {});   // -> Binv, Aof, rc, Ji, Jj, rx, ferr, fw, both scans, sc->err / wmin
+hipError_t pg_rhs(hipStream_t s, const PgDev& d, PgGate gate = {});                          // b = -(r_c + K^T r_x)
+hipError_t pg_step(hipStream_t s, const PgDev& d, PgGate gate = {});                         // delta = J_c^-1 y, Xtrial = X (+) delta
+hipError_t pg_retract(hipStream_t s, const PgDev& d);                                        // Xtrial = X (+) delta
+// y_c = 0, r_c = p_c = b_c; `close`, if given, is set to 1 behind it (the launched optimise shuts its head gate there)
+hipError_t pg_cg_begin(hipStream_t s, const PgDev& d, const PgCols& c, double tol, int max_iters, PgGate gate = {}, int32_t* close = nullptr);
+hipError_t pg_cg_iterations(hipStream_t s, const PgDev& d, const PgCols& c, int count);      // a stopped column is not touched
+hipError_t pg_bwd_unit(hipStream_t s, const PgDev& d, const PgCols& c, const PgColAt& at);   // b_c = J_c^-T e_(at[c])
+hipError_t pg_fwd_y(hipStream_t s, const PgDev& d, const PgCols& c);                         // delta_c = J_c^-1 y_c
+// One operator of the linearisation on every column's work vectors, by the launches pg_cg_iterations queues (the observation
+// hooks of include/liorf_s2m_debug.h): 0: t1 = J_c^-1 p;  1: t2 = J_c^-T g;  2: u = K p (t1 = J_c^-1 p on the way);
+// 3: t2 = K^T u (through g).  2 and 3 need an extra factor.
+hipError_t pg_apply(hipStream_t s, const PgDev& d, const PgCols& c, int op);
 // rows[12 c + 0..5] = delta_c of key ka[c], rows[12 c + 6..11] = delta_c of key kb[c] (zeros where kb[c] < 0)
-hipError_t pg_rows_cols(hipStream_t s, const PgDev& d, const PgCols& c, const PgColAt& ka, const PgColAt& kb, double* rows);
+hipError_t pg_rows(hipStream_t s, const PgDev& d, const PgCols& c, const PgColAt& ka, const PgColAt& kb, double* rows);
 
 // ---- the launched optimise: the Gauss-Newton loop of s2m_pg_optimize with its decisions taken on the device.  The record holds
-// the result's fields, the running error, the gates of the kernels that return at their head (nonzero = skip) and A, the
-// estimate of the last variable (12 doubles) after the last kept step.  pg_async_open linearises at d.X and opens the record;
-// pg_async_segment queues, in this order: the head of a step (rhs, CG begin; runs if a step was opened), cg_chunk CG
-// iterations (they stop by sc->stop), and the tail (step, linearisation at the trial point, close, trial -> d.X if the step
-// is kept; runs if the CG has stopped).  Segments are queued back to back until `done` shows in the record; every kernel
+// the result's fields, the running error, the gates (nonzero = skip) and A, the estimate of the last variable (12 doubles)
+// after the last kept step.  pg_async_open linearises at d.X and opens the record (k_pg_open); pg_async_segment queues, in
+// this order: the head of a step (pg_rhs, pg_cg_begin gated by skip_head; runs if a step was opened), cg_chunk CG iterations
+// (they stop by sc->stop), k_pg_gate, and the tail (pg_step, pg_linearize at the trial point gated by skip_tail, k_pg_close,
+// k_pg_keep: trial -> d.X if the step is kept; runs if the CG has stopped).  These are the functions s2m_pg_optimize calls,
+// with a record gate where it passes none.  Segments are queued back to back until `done` shows in the record; every kernel
 // behind `done` returns at its head.  d.X holds the estimates throughout (no pointer swap).
 struct PgRecord {
     int32_t iterations, inner_iterations, converged, done;
