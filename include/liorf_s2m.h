@@ -296,6 +296,20 @@ int  s2m_kf_set_poses(s2m_handle h, int first, int count, const float* poses_xyz
 int  s2m_extract_surrounding(s2m_handle h, double time_cur, const s2m_kf_params* p /* NULL = defaults */,
                              void* out, size_t out_stride_bytes, size_t cap, size_t* n_out,
                              int32_t* keys, size_t keys_cap, size_t* n_keys);
+/* ---- The local map around a given position ------------------------------------------------------------------
+ * A node that starts, or recovers, inside a map it already holds is not at the newest key: it is wherever
+ * s2m_relocalize_scan (below) found it. This call is s2m_extract_surrounding with centre_xyz in place of P[N-1]:
+ *   (b) every key with d2(P[i], centre) < (float)(R*R), (c) the key-pose VoxelGrid, (d) the nearest key of every
+ *   centroid, (f) an entry dropped when sqrtf(|centroid - centre|^2) > R, (g) the transformed clouds concatenated,
+ *   filtered with leaf L and installed as the local map with its index - the same kernels; the centre reaches them
+ *   by value, and s2m_extract_surrounding / s2m_global_map hand them P[N-1]'s own bits.
+ *   There are no recent keys (e): recent_window_s is ignored, the times of a stored map belong to another session.
+ * With centre_xyz = P[N-1] the result is what s2m_extract_surrounding gives with recent_window_s = 0 and
+ * time_cur = t[N-1]. Capacity, counts, S2M_ERR_CAPACITY, the empty store and S2M_WARN_LEAF_TOO_SMALL behave as there.
+ * A null or non-finite centre is S2M_ERR_INVALID_ARG. */
+int  s2m_extract_surrounding_at(s2m_handle h, const float centre_xyz[3], const s2m_kf_params* p /* NULL = defaults */,
+                                void* out, size_t out_stride_bytes, size_t cap, size_t* n_out,
+                                int32_t* keys, size_t keys_cap, size_t* n_keys);
 
 /* ---- The global map and the saved map from the key-frame store -------------------------------------------
  * publishGlobalMap() (reference src/mapOptmization.cpp:453-502) and saveMapService() (:375-432) against the resident store,
@@ -637,7 +651,8 @@ int  s2m_sc_query_projected (s2m_handle h, const s2m_sc_query_params* p, s2m_sc_
 /* ---- ICP loop-closure alignment ------------------------------------------
  * pcl::IterativeClosestPoint<PointType, PointType> as performRSLoopClosure / performSCLoopClosure configure
  * and run it (reference src/mapOptmization.cpp:571-586, :663-678): setMaxCorrespondenceDistance,
- * setMaximumIterations, setTransformationEpsilon, setEuclideanFitnessEpsilon, RANSAC off, identity guess,
+ * setMaximumIterations, setTransformationEpsilon, setEuclideanFitnessEpsilon, RANSAC off, identity guess
+ * (s2m_icp_align_guess below takes one),
  * align(); then hasConverged(), getFitnessScore(), getFinalTransformation(). src = cureKeyframeCloud, tgt =
  * prevKeyframeCloud (host records). T is the row-major 4x4 final transformation (source -> target). As in
  * PCL, reaching max_iterations counts as converged; fewer than 3 correspondences does not. */
@@ -656,6 +671,20 @@ typedef struct s2m_icp_result {
 int  s2m_icp_default_params(s2m_icp_params* p);
 int  s2m_icp_align(s2m_handle h, const void* src, size_t n_src, const void* tgt, size_t n_tgt, size_t stride_bytes,
                    const s2m_icp_params* p /* NULL = defaults */, s2m_icp_result* out);
+/* ---- ICP with an initial guess --------------------------------------------------------------------------------
+ * pcl::IterativeClosestPoint::align(output, guess): final_transformation_ starts as `guess` (row-major 4x4), the
+ * source is moved by it before the first correspondence search, and everything after that is the loop of
+ * s2m_icp_align - so out->T includes the guess (source frame -> target frame) and the fitness pass, which applies the
+ * final T to the source as it was given, is the same pass.
+ * [ext] PCL's own point-transform arithmetic is not pinned here: the source is moved in fp32 as
+ *       m0*x + m1*y + m2*z + m3 per row, evaluated left to right without contraction - the arithmetic that moves the
+ *       source between iterations.
+ * guess == NULL, or a matrix equal to the identity (PCL tests `guess != Identity` the same way), is byte for byte
+ * s2m_icp_align. A guess with an entry that is not finite, or a last row other than 0 0 0 1, is S2M_ERR_INVALID_ARG.
+ * Busy rules as s2m_icp_align. */
+int  s2m_icp_align_guess(s2m_handle h, const void* src, size_t n_src, const void* tgt, size_t n_tgt, size_t stride_bytes,
+                         const float guess[16] /* row-major 4x4, NULL = identity */,
+                         const s2m_icp_params* p /* NULL = defaults */, s2m_icp_result* out);
 
 /* ---- Loop closure against the key-frame store (SURVEY.md section 8(f), row F4 with its inputs) -------------------
  * performRSLoopClosure() (reference src/mapOptmization.cpp:542-622) and the extraction / ICP / gate half of
@@ -799,6 +828,57 @@ int  s2m_loop_verify_poll(s2m_handle h, s2m_loop_result* out, int32_t cap, int32
 int  s2m_loop_verify_collect(s2m_handle h, s2m_loop_result* out, int32_t cap, int32_t* n_out, int32_t* best);   /* waits */
 int  s2m_loop_verify(s2m_handle h, int32_t key_cur, const int32_t* key_pre, int32_t n_cand, int32_t base_key,
                      const s2m_loop_params* p /* NULL = defaults */, s2m_loop_result* out /* n_cand records */, int32_t* best);
+
+/* ---- Relocalisation: where in the stored map is this scan, as a pose ------------------------------------------------
+ * From a fresh scan (not a key) to a pose in the map frame, so that s2m_extract_surrounding_at and s2m_optimize* can start
+ * or recover inside a map the handle already holds. ScanContext key i must be key-frame i (both stores filled in step).
+ *   1. Query: the scan's descriptor against the descriptor store exactly as s2m_sc_query_scan(p->query) - the hits are
+ *      bit for bit that call's. No hits: S2M_OK, *n_out = 0, *best = -1. A hit key >= s2m_kf_size: S2M_ERR_INVALID_ARG.
+ *   2. Source: the scan in its own frame through the VoxelGrid at loop.icp_leaf, once, into the loop's source buffer
+ *      (scan_ds, which S2M_KF_FROM_LAST_DOWNSAMPLE reads, is not touched). n_src < 300: every record
+ *      S2M_LOOP_TOO_FEW_POINTS.
+ *   3. Target per hit: loopFindNearKeyframes(hit.key, search_num, -1) at icp_leaf, in the map frame. n_tgt < 1000: that
+ *      record is S2M_LOOP_TOO_FEW_POINTS and takes no slot.
+ *   4. Guess per hit: G = T(pose[key]) * Rz(-yaw_diff_rad) (use_yaw = 0: G = T(pose[key])), T the key's stored 3x4, the
+ *      product in float, each entry ((a0 b0 + a1 b1) + a2 b2). The sign: the descriptor's sector index grows with
+ *      atan2(y, x), and a query that is the candidate's cloud turned by +12 degrees about z matches at shift 2, so a
+ *      query point is about Rz(+yaw) * candidate point and the way back into the key's frame is Rz(-yaw).
+ *   5. Alignment: the remaining hits through the slotted device loop in lockstep - one source, one target and one guess
+ *      per slot - with the loop's ICP settings (max correspondence distance (double)(search_radius * 2.0f), 100
+ *      iterations, 1e-6 / 1e-6). Record i's icp is byte for byte s2m_icp_align_guess(source, target i, guess i).
+ *      The call waits for the result.
+ *   6. Judgement: !converged or fitness_score > (double)loop.fitness_score gives S2M_LOOP_REJECTED, otherwise
+ *      S2M_LOOP_ACCEPTED with both pose forms. *best: the accepted record with the least (fitness_score, position), or
+ *      -1, as s2m_loop_verify chooses. Records are in the query's order: descriptor distance ranks places, it does not
+ *      verify them (a mirror place of a symmetric scene can rank first and still pass the gate), so the top hits are
+ *      aligned and the fitness decides.
+ * Read-only: the loop-index container, both stores, the detector's state, the installed map and its index, the scan
+ * (scan_ds included), the pose, the batch and stream slots stay as they were; the next registration and the next
+ * s2m_sc_detect_loop are bit for bit what they would be without the call. It uses the loop's buffers: with a launched
+ * closure or verification pending it returns S2M_ERR_BUSY and touches nothing.
+ * Errors (S2M_ERR_INVALID_ARG): a null handle or null outputs; top_k outside 1 .. S2M_LOOP_MAX_CANDIDATES; a query the
+ * s2m_sc_query_* argument table rejects; loop parameters s2m_loop_* reject. n == 0: S2M_OK with no records.
+ * s2m_relocalize_check_args gives the same verdict from the two store sizes alone (host code, no handle). */
+typedef struct s2m_reloc_params {
+    s2m_sc_query_params query;   /* top_k 1 .. S2M_LOOP_MAX_CANDIDATES; defaults as s2m_sc_query_default_params but top_k 4, S2M_SC_ALIGN_FULL */
+    s2m_loop_params     loop;    /* search_radius (max correspondence distance = 2x, as the loop), search_num, fitness_score, icp_leaf; time_diff_s unused */
+    int32_t             use_yaw; /* 1 (default): guess = T(pose[key]) * Rz(-yaw_diff_rad);  0: guess = T(pose[key]) */
+    int32_t             reserved;
+} s2m_reloc_params;
+typedef struct s2m_reloc_candidate {
+    s2m_sc_hit     hit;          /* as s2m_sc_query_scan returns it */
+    int32_t        status;       /* S2M_LOOP_TOO_FEW_POINTS / REJECTED / ACCEPTED */
+    int32_t        n_src, n_tgt;
+    float          guess[16];    /* the guess the alignment started from */
+    s2m_icp_result icp;          /* T maps the scan's frame into the map frame (guess included); valid when ICP ran */
+    float          pose_xyzrpy[6];       /* getTranslationAndEulerAngles(icp.T), accepted records */
+    float          pose_tobemapped[6];   /* the same as {roll, pitch, yaw, x, y, z}: what s2m_optimize* takes */
+} s2m_reloc_candidate;
+int  s2m_reloc_default_params(s2m_reloc_params* p);
+int  s2m_relocalize_check_args(int32_t n_sc, int32_t n_kf, const s2m_reloc_params* p);   /* host only, no handle */
+int  s2m_relocalize_scan(s2m_handle h, const void* pts, size_t n, size_t stride_bytes, int on_device,
+                         const s2m_reloc_params* p /* NULL = defaults */,
+                         s2m_reloc_candidate* out /* top_k records */, int32_t* n_out, int32_t* best);
 
 /* ---- Pose graph: factors, optimise, correct the key-frame store --------------------------------------------------
  * saveKeyFramesAndFactor() with addOdomFactor / addGPSFactor / addLoopFactor (reference src/mapOptmization.cpp:1386-1534)

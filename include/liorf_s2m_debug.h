@@ -156,6 +156,12 @@ int  s2m_debug_icp_align_device(s2m_handle h, const void* src, size_t n_src, con
  * out[i] is bit for bit s2m_icp_align(src, tgts[i]); the same target may be listed twice. */
 int  s2m_debug_icp_align_many_device(s2m_handle h, const void* src, size_t n_src, const void* const* tgts, const size_t* n_tgts, int32_t n_cand,
                                      size_t stride_bytes, const s2m_icp_params* p /* NULL = defaults */, s2m_icp_result* out);
+/* The same with a guess per target (guesses: n_cand row-major 4x4 back to back, or NULL for none): every slot of the device loop
+ * owns its moving copy of the source, loaded through its own guess. out[i] is bit for bit s2m_icp_align_guess(src, tgts[i],
+ * guesses + 16 * i), whatever the other slots hold. A guess s2m_icp_align_guess rejects is S2M_ERR_INVALID_ARG. */
+int  s2m_debug_icp_align_guess_many_device(s2m_handle h, const void* src, size_t n_src, const void* const* tgts, const size_t* n_tgts,
+                                           const float* guesses, int32_t n_cand, size_t stride_bytes,
+                                           const s2m_icp_params* p /* NULL = defaults */, s2m_icp_result* out);
 /* Experiment switch of the device loop's search for the launches and debug calls that follow: the cell edge in units of
  * icp_leaf (0 = built in), the largest shell radius searched before a point goes to the brute force (0 = built in), and
  * use_grid (0 = brute force only, 1 = grid, < 0 = built in). */

@@ -193,34 +193,24 @@ int s2m_kf_set_poses(s2m_handle h, int first, int count, const float* poses_xyzr
     return S2M_OK;
 }
 
-int s2m_extract_surrounding(s2m_handle h, double time_cur, const s2m_kf_params* p, void* out, size_t out_stride_bytes, size_t cap,
-                            size_t* n_out, int32_t* keys, size_t keys_cap, size_t* n_keys)
+namespace {
+
+// extractSurroundingKeyFrames around `centre` (null: P[N-1], the newest key's position as the store holds it) with the n_recent newest
+// keys as (e): the selection, the transform of the chosen frames, the VoxelGrid, the result installed as the local map with its index
+int extract_around(s2m_context* h, const float* centre, int n_recent, const s2m_kf_params& prm, void* out, size_t out_stride_bytes,
+                   size_t cap, size_t* n_out, int32_t* keys, size_t keys_cap, size_t* n_keys)
 {
-    if (!h) return S2M_ERR_INVALID_ARG;
-    s2m_kf_params prm;
-    if (p) prm = *p; else s2m_kf_default_params(&prm);
-    if (!(prm.search_radius > 0.0f) || !std::isfinite(prm.search_radius) || !(prm.density > 0.0f) || !std::isfinite(prm.density) ||
-        !std::isfinite(prm.recent_window_s) || !std::isfinite(time_cur))
-        return fail(h, S2M_ERR_INVALID_ARG, "search radius and density must be positive, window and time finite");
-    int rc = check_leaf(h, prm.map_leaf);
-    if (rc) return rc;
-    if (!n_out || bad_out(out, out_stride_bytes, cap) || (keys_cap > 0 && !keys)) return fail(h, S2M_ERR_INVALID_ARG, "bad output buffer");
-    *n_out = 0;
-    if (n_keys) *n_keys = 0;
     const size_t N = h->kf.time.size();
-    if (N == 0) return S2M_OK;                             // cloudKeyPoses3D->points.empty(): nothing changes (:1048-1049)
-    // (e) the recent keys: i = N-1, N-2, ... while timeLaserInfoCur - time < 10.0 (:1000-1007)
-    int n_recent = 0;
-    for (size_t i = N; i-- > 0 && time_cur - h->kf.time[i] < prm.recent_window_s;) n_recent++;
     S2M_HIP(h, hipSetDevice(h->device));
     KfSelect sel;
     KfTable tab;
-    hipError_t e = kf_select(h->voxel.ws, h->stream, h->kf.pos.as<float4>(), h->kf.frames.as<KfFrame>(), (int)N, n_recent,
-                             prm.search_radius, prm.density, &sel, &tab);
+    hipError_t e = kf_select(h->voxel.ws, h->stream, h->kf.pos.as<float4>(), h->kf.frames.as<KfFrame>(), (int)N,
+                             centre ? centre : &h->kf.pose[6 * (N - 1)], n_recent, prm.search_radius, prm.density, &sel, &tab);
     if (e != hipSuccess) return fail(h, S2M_ERR_HIP, "key-frame selection", e);
     if (n_keys) *n_keys = (size_t)sel.n_frames;
     if (sel.n_points > 0x3fffffffLL) return fail(h, S2M_ERR_CAPACITY, "too many points");
     VoxResult res;
+    int rc;
     if (sel.n_points > 0) {
         const size_t total = (size_t)sel.n_points;
         if ((rc = ensure(h, h->voxel.frames_xf, kDsStride * total))) return rc;
@@ -234,6 +224,54 @@ int s2m_extract_surrounding(s2m_handle h, double time_cur, const s2m_kf_params* 
     if ((rc = set_map_impl(h, h->voxel.map_ds.p, res.n_out, kDsStride, true))) return rc;
     return finish_cloud_and_keys(h, h->voxel.map_ds, res, out, out_stride_bytes, cap, "output buffer too small for the local map",
                                  sel, tab, keys, keys_cap);
+}
+
+// the parameter and buffer checks the two extractions share; *prm: the caller's parameters or the defaults
+int extract_args(s2m_context* h, const s2m_kf_params* p, s2m_kf_params* prm, const void* out, size_t out_stride_bytes, size_t cap,
+                 size_t* n_out, const int32_t* keys, size_t keys_cap, size_t* n_keys)
+{
+    if (p) *prm = *p; else s2m_kf_default_params(prm);
+    if (!(prm->search_radius > 0.0f) || !std::isfinite(prm->search_radius) || !(prm->density > 0.0f) || !std::isfinite(prm->density))
+        return fail(h, S2M_ERR_INVALID_ARG, "search radius and density must be positive, window and time finite");
+    const int rc = check_leaf(h, prm->map_leaf);
+    if (rc) return rc;
+    if (!n_out || bad_out(out, out_stride_bytes, cap) || (keys_cap > 0 && !keys)) return fail(h, S2M_ERR_INVALID_ARG, "bad output buffer");
+    *n_out = 0;
+    if (n_keys) *n_keys = 0;
+    return S2M_OK;
+}
+
+}  // namespace
+
+int s2m_extract_surrounding(s2m_handle h, double time_cur, const s2m_kf_params* p, void* out, size_t out_stride_bytes, size_t cap,
+                            size_t* n_out, int32_t* keys, size_t keys_cap, size_t* n_keys)
+{
+    if (!h) return S2M_ERR_INVALID_ARG;
+    if ((p && !std::isfinite(p->recent_window_s)) || !std::isfinite(time_cur))
+        return fail(h, S2M_ERR_INVALID_ARG, "search radius and density must be positive, window and time finite");
+    s2m_kf_params prm;
+    const int rc = extract_args(h, p, &prm, out, out_stride_bytes, cap, n_out, keys, keys_cap, n_keys);
+    if (rc) return rc;
+    const size_t N = h->kf.time.size();
+    if (N == 0) return S2M_OK;                             // cloudKeyPoses3D->points.empty(): nothing changes (:1048-1049)
+    // (e) the recent keys: i = N-1, N-2, ... while timeLaserInfoCur - time < 10.0 (:1000-1007)
+    int n_recent = 0;
+    for (size_t i = N; i-- > 0 && time_cur - h->kf.time[i] < prm.recent_window_s;) n_recent++;
+    return extract_around(h, nullptr, n_recent, prm, out, out_stride_bytes, cap, n_out, keys, keys_cap, n_keys);
+}
+
+// the local map around a given position: (b), (c), (d), (f), (g) with centre_xyz in place of P[N-1], no recent keys
+int s2m_extract_surrounding_at(s2m_handle h, const float centre_xyz[3], const s2m_kf_params* p, void* out, size_t out_stride_bytes, size_t cap,
+                               size_t* n_out, int32_t* keys, size_t keys_cap, size_t* n_keys)
+{
+    if (!h) return S2M_ERR_INVALID_ARG;
+    if (!centre_xyz || !std::isfinite(centre_xyz[0]) || !std::isfinite(centre_xyz[1]) || !std::isfinite(centre_xyz[2]))
+        return fail(h, S2M_ERR_INVALID_ARG, "the centre of the local map must be finite");
+    s2m_kf_params prm;
+    const int rc = extract_args(h, p, &prm, out, out_stride_bytes, cap, n_out, keys, keys_cap, n_keys);
+    if (rc) return rc;
+    if (h->kf.time.empty()) return S2M_OK;
+    return extract_around(h, centre_xyz, 0, prm, out, out_stride_bytes, cap, n_out, keys, keys_cap, n_keys);
 }
 
 // ---- the global map and the saved map from the key-frame store (publishGlobalMap :453-502, saveMapService :375-432) ---------
@@ -374,7 +412,7 @@ int s2m_global_map(s2m_handle h, const s2m_gmap_params* p, void* out, size_t out
     // test at the centroid (:466-491): kf_select with no recent keys
     KfSelect sel;
     KfTable tab;
-    hipError_t e = kf_select(h->voxel.ws, h->stream, h->kf.pos.as<float4>(), h->kf.frames.as<KfFrame>(), (int)N, 0,
+    hipError_t e = kf_select(h->voxel.ws, h->stream, h->kf.pos.as<float4>(), h->kf.frames.as<KfFrame>(), (int)N, &h->kf.pose[6 * (N - 1)], 0,
                              prm.search_radius, prm.pose_density, &sel, &tab);
     if (e != hipSuccess) return fail(h, S2M_ERR_HIP, "global-map key selection", e);
     if (n_keys) *n_keys = (size_t)sel.n_frames;

@@ -1,7 +1,9 @@
-// s2m_abi_loop.hip — C ABI of the loop closure: the ICP alignment of two host clouds (section 8(f) row F4) and detection, submaps
-// and alignment against the key-frame store.  Host orchestration of s2m_icp.hip's and s2m_voxel.hip's stages only.
+// s2m_abi_loop.hip — C ABI of the loop closure: the ICP alignment of two host clouds (section 8(f) row F4), with or without an
+// initial guess, detection, submaps and alignment against the key-frame store, and the relocalisation of a scan that is no key
+// (place query, guessed alignment of its hits in lockstep).  Host orchestration of s2m_icp.hip's and s2m_voxel.hip's stages only.
 #include <algorithm>
 #include <cmath>
+#include <cstdint>
 #include <cstdio>
 #include <cstring>
 
@@ -88,13 +90,34 @@ int s2m_icp_default_params(s2m_icp_params* p)
     return S2M_OK;
 }
 
+namespace {
+
+// an initial guess as align(output, guess) takes one: finite, last row 0 0 0 1
+int guess_ok(s2m_context* h, const float* g)
+{
+    for (int i = 0; i < 16; i++)
+        if (!std::isfinite(g[i])) return fail(h, S2M_ERR_INVALID_ARG, "the ICP guess has an entry that is not finite");
+    if (g[12] != 0.0f || g[13] != 0.0f || g[14] != 0.0f || g[15] != 1.0f)
+        return fail(h, S2M_ERR_INVALID_ARG, "the last row of the ICP guess must be 0 0 0 1");
+    return S2M_OK;
+}
+
+}  // namespace
+
 int s2m_icp_align(s2m_handle h, const void* src, size_t n_src, const void* tgt, size_t n_tgt, size_t stride_bytes,
                   const s2m_icp_params* p, s2m_icp_result* out)
+{
+    return s2m_icp_align_guess(h, src, n_src, tgt, n_tgt, stride_bytes, nullptr, p, out);
+}
+
+int s2m_icp_align_guess(s2m_handle h, const void* src, size_t n_src, const void* tgt, size_t n_tgt, size_t stride_bytes,
+                        const float guess[16], const s2m_icp_params* p, s2m_icp_result* out)
 {
     int rc = check_records(h, src, n_src, stride_bytes);
     if (rc) return rc;
     if ((rc = check_records(h, tgt, n_tgt, stride_bytes))) return rc;
     if (!out) return S2M_ERR_INVALID_ARG;
+    if (guess && (rc = guess_ok(h, guess))) return rc;
     if ((rc = loop_busy(h))) return rc;
     IcpParams ip;
     if ((rc = icp_params_in(h, p, &ip))) return rc;
@@ -103,7 +126,7 @@ int s2m_icp_align(s2m_handle h, const void* src, size_t n_src, const void* tgt, 
     if (n_tgt && (rc = stage_host_records(h, h->loop.icp_tgt, tgt, n_tgt * stride_bytes))) return rc;
     IcpResult r;
     hipError_t e = icp_align(h->loop.icp, h->stream, h->loop.icp_src.as<unsigned char>(), n_src, h->loop.icp_tgt.as<unsigned char>(), n_tgt,
-                             stride_bytes, ip, &r);
+                             stride_bytes, ip, &r, guess);
     if (e != hipSuccess) return fail(h, S2M_ERR_HIP, "ICP alignment", e);
     S2M_HIP(h, hipStreamSynchronize(h->stream));
     icp_result_out(r, out);
@@ -521,6 +544,142 @@ int s2m_loop_verify(s2m_handle h, int32_t key_cur, const int32_t* key_pre, int32
     return verify_poll_impl(h, out, n_cand, &n, best, true);
 }
 
+// ---- relocalisation: a scan that is no key against the stored map (place query, guessed alignment in lockstep) -------------
+
+int s2m_reloc_default_params(s2m_reloc_params* p)
+{
+    if (!p) return S2M_ERR_INVALID_ARG;
+    memset(p, 0, sizeof(*p));
+    s2m_sc_query_default_params(&p->query);
+    p->query.top_k = 4;
+    p->query.align = S2M_SC_ALIGN_FULL;
+    s2m_loop_default_params(&p->loop);
+    p->use_yaw = 1;
+    return S2M_OK;
+}
+
+namespace {
+
+int reloc_args(s2m_context* h, int64_t n_sc, int64_t n_kf, const s2m_reloc_params* p, s2m_reloc_params* prm)
+{
+    if (p) *prm = *p; else s2m_reloc_default_params(prm);
+    if (n_sc < 0 || n_kf < 0 || n_sc > INT32_MAX) return fail(h, S2M_ERR_INVALID_ARG, "relocalisation: a negative store size");
+    if (prm->query.top_k < 1 || prm->query.top_k > S2M_LOOP_MAX_CANDIDATES)
+        return fail(h, S2M_ERR_INVALID_ARG, "a relocalisation aligns the top 1 .. S2M_LOOP_MAX_CANDIDATES hits");
+    if (s2m_sc_query_check_args((int32_t)n_sc, &prm->query) != S2M_OK)
+        return fail(h, S2M_ERR_INVALID_ARG, "relocalisation: the query's align, max_dist or range is invalid");
+    s2m_loop_params lp;
+    const int rc = loop_params(h, &prm->loop, &lp);
+    return rc;
+}
+
+// G = T(pose[key]) * Rz(-yaw): the key's stored 3x4 times the turn that takes a query point back onto the candidate's (the
+// descriptor's shift says query ~ Rz(+yaw) * candidate), in float, each entry ((a0 b0 + a1 b1) + a2 b2)
+void reloc_guess(const float T_key[12], float yaw_diff_rad, bool use_yaw, float G[16])
+{
+    const float a = use_yaw ? -yaw_diff_rad : 0.0f;
+    const float c = cosf(a), s = sinf(a);
+    const float Rz[12] = { c, -s, 0.0f, 0.0f,   s, c, 0.0f, 0.0f,   0.0f, 0.0f, 1.0f, 0.0f };
+    if (use_yaw) host_affine_mul(T_key, Rz, G); else memcpy(G, T_key, sizeof(float) * 12);
+    G[12] = G[13] = G[14] = 0.0f; G[15] = 1.0f;
+}
+
+}  // namespace
+
+int s2m_relocalize_check_args(int32_t n_sc, int32_t n_kf, const s2m_reloc_params* p)
+{
+    s2m_reloc_params prm;
+    return reloc_args(nullptr, n_sc, n_kf, p, &prm);
+}
+
+int s2m_relocalize_scan(s2m_handle h, const void* pts, size_t n, size_t stride_bytes, int on_device, const s2m_reloc_params* p,
+                        s2m_reloc_candidate* out, int32_t* n_out, int32_t* best)
+{
+    if (!h) return S2M_ERR_INVALID_ARG;
+    if (!out || !n_out || !best) return fail(h, S2M_ERR_INVALID_ARG, "null relocalisation outputs");
+    int rc = check_records(h, pts, n, stride_bytes);
+    if (rc) return rc;
+    if ((rc = loop_busy(h))) return rc;
+    *n_out = 0; *best = -1;
+    s2m_reloc_params prm;
+    if ((rc = reloc_args(h, (int64_t)h->sc.n, (int64_t)h->kf.time.size(), p, &prm))) return rc;
+    if (n == 0) return S2M_OK;
+    S2M_HIP(h, hipSetDevice(h->device));
+    s2m_context::LoopClosure& L = h->loop;
+    // the scan in the loop's staging buffer (a host scan), where the query's descriptor and the source filter both read it
+    const unsigned char* d_pts = static_cast<const unsigned char*>(pts);
+    if (!on_device) {
+        if ((rc = stage_host_records(h, L.icp_src, pts, n * stride_bytes))) return rc;
+        d_pts = L.icp_src.as<unsigned char>();
+    }
+    // 1. the query: s2m_sc_query_scan's hits
+    s2m_sc_hit hits[S2M_LOOP_MAX_CANDIDATES];
+    int32_t n_hits = 0;
+    if ((rc = sc_query_device_scan(h, d_pts, n, stride_bytes, &prm.query, hits, &n_hits))) return rc;
+    if (n_hits == 0) return S2M_OK;
+    const size_t N = h->kf.time.size();
+    for (int32_t i = 0; i < n_hits; i++)
+        if (!loop_key_ok(hits[i].key, N))
+            return fail(h, S2M_ERR_INVALID_ARG, "relocalisation: a hit names a key the key-frame store does not hold (the two stores are out of step)");
+    // 2. the source: the scan in its own frame through the VoxelGrid at icp_leaf, once, into the loop's source buffer
+    VoxResult vs;
+    if ((rc = voxel_into(h, d_pts, n, stride_bytes, prm.loop.icp_leaf, L.cur, &vs))) return rc;
+    // 3. + 4. a target submap and a guess per hit; the size gates decide who takes a slot
+    const unsigned char* d_tgt[S2M_LOOP_MAX_CANDIDATES];
+    const float* guess[S2M_LOOP_MAX_CANDIDATES];
+    size_t n_tgt[S2M_LOOP_MAX_CANDIDATES];
+    int slot_of[S2M_LOOP_MAX_CANDIDATES];
+    int slots = 0;
+    for (int32_t i = 0; i < n_hits; i++) {
+        s2m_reloc_candidate& c = out[i];
+        memset(&c, 0, sizeof(c));
+        c.hit = hits[i];
+        c.icp.T[0] = c.icp.T[5] = c.icp.T[10] = c.icp.T[15] = 1.0f;
+        c.n_src = (int32_t)vs.n_out;
+        reloc_guess(h->kf.frame[(size_t)hits[i].key].T, hits[i].yaw_diff_rad, prm.use_yaw != 0, c.guess);
+        slot_of[i] = -1;
+        c.status = S2M_LOOP_TOO_FEW_POINTS;
+        if (vs.n_out < 300) continue;
+        VoxResult vt;
+        if ((rc = loop_submap(h, hits[i].key, prm.loop.search_num, -1, prm.loop.icp_leaf, L.target(i), &vt))) return rc;
+        c.n_tgt = (int32_t)vt.n_out;
+        if (vt.n_out < 1000) continue;
+        if ((rc = guess_ok(h, c.guess))) return rc;
+        c.status = S2M_LOOP_NONE;
+        d_tgt[slots] = L.target(i).as<unsigned char>();
+        n_tgt[slots] = vt.n_out;
+        guess[slots] = c.guess;
+        slot_of[i] = slots++;
+    }
+    *n_out = n_hits;
+    if (!slots) return S2M_OK;
+    // 5. the alignments in lockstep on the device loop, waited for
+    IcpResult r[S2M_LOOP_MAX_CANDIDATES];
+    hipError_t e = icp_dev_begin(L.icp, h->stream, L.cur.as<unsigned char>(), vs.n_out, d_tgt, n_tgt, slots, kDsStride, loop_icp_params(prm.loop),
+                                 loop_tuning(h, prm.loop.icp_leaf), guess);
+    bool done = false;
+    if (e == hipSuccess) e = icp_dev_advance(L.icp, h->stream, true, &done, r);
+    if (e != hipSuccess || !done) {
+        (void)hipStreamSynchronize(h->stream);
+        icp_dev_cancel(L.icp);
+        return fail(h, S2M_ERR_HIP, "relocalisation ICP", e);
+    }
+    S2M_HIP(h, hipStreamSynchronize(h->stream));
+    // 6. the fitness gate, both pose forms, the best record by (fitness, position)
+    for (int32_t i = 0; i < n_hits; i++) {
+        if (slot_of[i] < 0) continue;
+        s2m_reloc_candidate& c = out[i];
+        const IcpResult& ri = r[slot_of[i]];
+        icp_result_out(ri, &c.icp);
+        if (!ri.converged || ri.fitness > (double)prm.loop.fitness_score) { c.status = S2M_LOOP_REJECTED; continue; }
+        c.status = S2M_LOOP_ACCEPTED;
+        host_translation_and_euler(ri.T, 4, c.pose_xyzrpy);
+        for (int k = 0; k < 3; k++) { c.pose_tobemapped[k] = c.pose_xyzrpy[3 + k]; c.pose_tobemapped[3 + k] = c.pose_xyzrpy[k]; }
+        if (*best < 0 || c.icp.fitness_score < out[*best].icp.fitness_score) *best = i;
+    }
+    return S2M_OK;
+}
+
 // ---- diagnostics of the device loop (include/liorf_s2m_debug.h) ---------------------------------------------------------
 
 namespace {
@@ -544,7 +703,7 @@ int debug_stage(s2m_context* h, const void* src, size_t n_src, const void* tgt, 
 // one host source against n_cand host targets through the device loop, waited for: a slot per non-empty target, staged in the
 // closure's target buffers; out: n_cand results (an empty cloud: icp_result_none)
 int debug_align_many(s2m_context* h, const void* src, size_t n_src, const void* const* tgts, const size_t* n_tgts, int32_t n_cand, size_t stride,
-                     const IcpParams& ip, s2m_icp_result* out)
+                     const IcpParams& ip, s2m_icp_result* out, const float* guesses = nullptr /* n_cand row-major 4x4, or none */)
 {
     int rc = debug_stage(h, src, n_src, nullptr, 0, stride);
     if (rc) return rc;
@@ -552,11 +711,13 @@ int debug_align_many(s2m_context* h, const void* src, size_t n_src, const void* 
     const unsigned char* d_tgt[S2M_LOOP_MAX_CANDIDATES];
     size_t n_tgt[S2M_LOOP_MAX_CANDIDATES];
     int slot_of[S2M_LOOP_MAX_CANDIDATES];
+    const float* guess[S2M_LOOP_MAX_CANDIDATES];
     int slots = 0;
     for (int32_t i = 0; i < n_cand; i++) {
         if ((rc = check_records(h, tgts[i], n_tgts[i], stride))) return rc;
         slot_of[i] = -1;
         if (!n_src || !n_tgts[i]) continue;
+        guess[slots] = guesses ? guesses + 16 * (size_t)i : nullptr;
         if ((rc = ensure(h, L.target(i), n_tgts[i] * stride))) return rc;
         S2M_HIP(h, hipMemcpyAsync(L.target(i).p, tgts[i], n_tgts[i] * stride, hipMemcpyHostToDevice, L.stream));
         d_tgt[slots] = L.target(i).as<unsigned char>();
@@ -567,7 +728,7 @@ int debug_align_many(s2m_context* h, const void* src, size_t n_src, const void* 
     if (slots) {
         s2m_loop_params lp;
         s2m_loop_default_params(&lp);
-        hipError_t e = icp_dev_begin(L.icp, L.stream, L.icp_src.as<unsigned char>(), n_src, d_tgt, n_tgt, slots, stride, ip, loop_tuning(h, lp.icp_leaf));
+        hipError_t e = icp_dev_begin(L.icp, L.stream, L.icp_src.as<unsigned char>(), n_src, d_tgt, n_tgt, slots, stride, ip, loop_tuning(h, lp.icp_leaf), guess);
         bool done = false;
         if (e == hipSuccess) e = icp_dev_advance(L.icp, L.stream, true, &done, r);
         if (e != hipSuccess || !done) {
@@ -649,6 +810,18 @@ int s2m_debug_icp_align_many_device(s2m_handle h, const void* src, size_t n_src,
     IcpParams ip;
     const int rc = icp_params_in(h, p, &ip);
     return rc ? rc : debug_align_many(h, src, n_src, tgts, n_tgts, n_cand, stride_bytes, ip, out);
+}
+
+int s2m_debug_icp_align_guess_many_device(s2m_handle h, const void* src, size_t n_src, const void* const* tgts, const size_t* n_tgts,
+                                          const float* guesses, int32_t n_cand, size_t stride_bytes, const s2m_icp_params* p, s2m_icp_result* out)
+{
+    if (!h) return S2M_ERR_INVALID_ARG;
+    if (!out || !tgts || !n_tgts || n_cand < 1 || n_cand > S2M_LOOP_MAX_CANDIDATES)
+        return fail(h, S2M_ERR_INVALID_ARG, "null ICP result or target list, or not 1 .. S2M_LOOP_MAX_CANDIDATES targets");
+    IcpParams ip;
+    int rc = icp_params_in(h, p, &ip);
+    for (int32_t i = 0; !rc && guesses && i < n_cand; i++) rc = guess_ok(h, guesses + 16 * (size_t)i);
+    return rc ? rc : debug_align_many(h, src, n_src, tgts, n_tgts, n_cand, stride_bytes, ip, out, guesses);
 }
 
 int s2m_debug_icp_grid_check_args(const void* const* tgts, const size_t* n_tgts, int32_t n_cand, size_t stride_bytes, const s2m_debug_icp_grid_out* out)

@@ -83,6 +83,19 @@ int sc_query_run(s2m_context* h, const ScQueryPlan& q, const double* src_desc, c
 
 }  // namespace
 
+// s2m_sc_query_scan for a scan that is on the device already (the relocalisation's query): the same descriptor, the same hits
+int s2m::host::sc_query_device_scan(s2m_context* h, const void* d_pts, size_t n, size_t stride_bytes, const s2m_sc_query_params* p,
+                                    s2m_sc_hit* hits, int32_t* n_hits)
+{
+    ScQueryPlan q;
+    int rc = sc_query_check(h, p, hits, n_hits, &q);
+    if (rc) return rc;
+    if (q.n_s == 0) return S2M_OK;
+    if ((rc = ensure(h, h->sc.query, sizeof(double) * kScQuerySlot))) return rc;
+    if ((rc = sc_build_descriptor(h, d_pts, n, stride_bytes, true))) return rc;
+    return sc_query_run(h, q, h->sc.out.as<double>(), nullptr, hits, n_hits);
+}
+
 extern "C" {
 
 int s2m_sc_query_default_params(s2m_sc_query_params* p)

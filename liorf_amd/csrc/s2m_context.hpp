@@ -372,6 +372,11 @@ void ensure_wave_table(s2m_context* h);
 int sc_build_descriptor(s2m_context* h, const void* pts, size_t n, size_t stride_bytes, bool on_device = false);
 int sc_append_from_out(s2m_context* h);
 
+// ---- s2m_abi_sc_query.hip ----
+// s2m_sc_query_scan with the scan on the device (n records of stride_bytes): hits has room for p->top_k records
+int sc_query_device_scan(s2m_context* h, const void* d_pts, size_t n, size_t stride_bytes, const s2m_sc_query_params* p, s2m_sc_hit* hits,
+                         int32_t* n_hits);
+
 // ---- s2m_abi_loop.hip ----
 // S2M_ERR_BUSY while a launched loop closure is pending (the calls that use its buffers start with this)
 int loop_busy(s2m_context* h);

@@ -20,7 +20,8 @@
 // the points the grid does not settle (same keys); the host's part of (2) becomes k_icp_close, which runs the host loop's own
 // source (s2m_icp_close.hpp); iterations are queued in ranges and every kernel behind the end of the alignment returns at entry.
 // The loop carries up to kIcpMaxSlots alignments of one source at once, the slot a grid dimension of every kernel; the single
-// alignment is its one-slot case.
+// alignment is its one-slot case. Every slot owns its moving copy of the source, so each may start from a guess of its own
+// (align(output, guess): IcpGuesses, the source moved as it is loaded, the state's T started at the guess).
 // The kernels are one set but for two. The host loop (icp_align) launches the loop's load, reset, sums and fold on the one-slot
 // layout and differs in who closes an iteration (the host, after a wait), in the search (always the brute force, through k_icp_nn:
 // k_icp_nn_list over every source computes the same keys but cost the loop 2-3 % of its time) and in k_icp_transform, which takes
@@ -185,11 +186,22 @@ struct IcpSlots {
     int                 n_src;
 };
 
-// records to float4 per slot: the K targets, or the one source into every slot's moving copy
+// The initial guesses of the slots (pcl::IterativeClosestPoint::align(output, guess)): slot s with set[s] starts its
+// final_transformation_ at T[s] (row-major 4x4) and its moving source at T[s] * source; a slot without one starts at the identity
+// with the source as it is (PCL: `if (guess != Matrix4::Identity())`), which is the loop as it was before there were guesses.
+struct IcpGuesses {
+    float T[kIcpMaxSlots][16];
+    int   set[kIcpMaxSlots];
+};
+
+// records to float4 per slot: the K targets, or the one source into every slot's moving copy - there moved by the slot's guess
+// where it has one (move[s]; m[s]: the guess's 3x4), in transform_body's arithmetic
 struct IcpLoad {
     const unsigned char* src[kIcpMaxSlots];
     float4*              dst[kIcpMaxSlots];
     int                  n[kIcpMaxSlots];
+    int                  move[kIcpMaxSlots];
+    float                m[kIcpMaxSlots][12];
 };
 
 __global__ __launch_bounds__(256) void k_icp_load_slots(IcpLoad L, size_t stride)
@@ -198,14 +210,19 @@ __global__ __launch_bounds__(256) void k_icp_load_slots(IcpLoad L, size_t stride
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= L.n[s]) return;
     const float* p = reinterpret_cast<const float*>(L.src[s] + (size_t)i * stride);
-    L.dst[s][i] = make_float4(p[0], p[1], p[2], 0.0f);
+    const float x = p[0], y = p[1], z = p[2];
+    if (!L.move[s]) { L.dst[s][i] = make_float4(x, y, z, 0.0f); return; }
+    const float* m = L.m[s];
+    L.dst[s][i] = make_float4(m[0] * x + m[1] * y + m[2]  * z + m[3],
+                              m[4] * x + m[5] * y + m[6]  * z + m[7],
+                              m[8] * x + m[9] * y + m[10] * z + m[11], 0.0f);
 }
 
-__global__ __launch_bounds__(64) void k_icp_begin(IcpSlots S)
+__global__ __launch_bounds__(64) void k_icp_begin(IcpSlots S, IcpGuesses G)
 {
     if (threadIdx.x != 0) return;
     IcpDevBlock* blk = S.blk + blockIdx.z;
-    icp_state_init(&blk->st);
+    icp_state_init(&blk->st, G.set[blockIdx.z] ? G.T[blockIdx.z] : nullptr);
     for (int a = 0; a < 3; a++) { blk->bbox[a] = 0xffffffffu; blk->bbox[3 + a] = 0u; }
     blk->wl_count = 0; blk->n_fallback = 0;
     blk->g.n_fin = 0; blk->g.usable = 0;
@@ -598,6 +615,7 @@ struct IcpWorkspace {
     // the slots the buffers are laid out for (dev_layout): what every kernel of the loop gets by value, and the launch shapes
     IcpSlots S{};
     int K = 0, n_tgt_max = 0, slices_max = 0;
+    IcpGuesses G{};                      // the slots' initial guesses; dev_layout leaves none, set_guesses sets them for one alignment
 };
 
 IcpWorkspace* icp_create()
@@ -676,11 +694,31 @@ hipError_t dev_layout(IcpWorkspace* w, int K, size_t n_src, const size_t* n_tgt,
     S.gcount = w->gcount.as<int>(); S.gstart = w->gstart.as<int>(); S.gend = w->gend.as<int>();
     S.n_src = (int)n_src;
     w->S = S; w->K = K; w->n_tgt_max = (int)most; w->slices_max = slices_max;
+    w->G = IcpGuesses{};
     return hipSuccess;
 }
 
-// records -> float4: the K targets of the layout, or the one source into every slot's moving copy
-hipError_t load_slots(IcpWorkspace* w, hipStream_t stream, const unsigned char* d_src, const unsigned char* const* d_tgt, size_t stride)
+bool guess_is_identity(const float* g)
+{
+    for (int i = 0; i < 16; i++) if (g[i] != ((i % 5 == 0) ? 1.0f : 0.0f)) return false;
+    return true;
+}
+
+// the guesses of the layout's slots: guess[k] (row-major 4x4) for slot k; a null list, a null entry or the identity leave the slot
+// without one (`guess != Identity`, as PCL tests it), so that slot runs what it ran before there were guesses
+void set_guesses(IcpWorkspace* w, const float* const* guess)
+{
+    w->G = IcpGuesses{};
+    for (int k = 0; guess && k < w->K; k++) {
+        if (!guess[k] || guess_is_identity(guess[k])) continue;
+        memcpy(w->G.T[k], guess[k], sizeof(w->G.T[k]));
+        w->G.set[k] = 1;
+    }
+}
+
+// records -> float4: the K targets of the layout, or the one source into every slot's moving copy (guessed: moved by the slot's guess)
+hipError_t load_slots(IcpWorkspace* w, hipStream_t stream, const unsigned char* d_src, const unsigned char* const* d_tgt, size_t stride,
+                      bool guessed = false)
 {
     IcpLoad L{};
     int most = 0;
@@ -689,6 +727,7 @@ hipError_t load_slots(IcpWorkspace* w, hipStream_t stream, const unsigned char* 
         L.dst[k] = d_tgt ? const_cast<float4*>(w->S.tgt[k]) : w->S.cur[k];
         L.n[k] = d_tgt ? w->S.n_tgt[k] : w->S.n_src;
         most = std::max(most, L.n[k]);
+        if (guessed && !d_tgt && w->G.set[k]) { L.move[k] = 1; memcpy(L.m[k], w->G.T[k], sizeof(L.m[k])); }
     }
     hipLaunchKernelGGL(k_icp_load_slots, dim3((most + 255) / 256, 1, w->K), dim3(256), 0, stream, L, stride);
     return hipGetLastError();
@@ -699,7 +738,7 @@ hipError_t dev_prepare(IcpWorkspace* w, hipStream_t stream, const IcpTuning& tun
 {
     const IcpSlots& S = w->S;
     const unsigned K = (unsigned)w->K;
-    hipLaunchKernelGGL(k_icp_begin, dim3(1, 1, K), dim3(64), 0, stream, S);
+    hipLaunchKernelGGL(k_icp_begin, dim3(1, 1, K), dim3(64), 0, stream, S, w->G);
     if (tune.use_grid) {
         ICP_TRY(hipMemsetAsync(w->gcount.p, 0, sizeof(int) * kGridMaxCells * (size_t)K, stream));
         const int tb = (w->n_tgt_max + 255) / 256;
@@ -796,12 +835,13 @@ hipError_t dev_queue_fitness(IcpWorkspace* w, hipStream_t stream)
 void icp_dev_cancel(IcpWorkspace* w) { w->fl.phase = 0; }
 
 hipError_t icp_dev_begin(IcpWorkspace* w, hipStream_t stream, const unsigned char* d_src, size_t n_src_, const unsigned char* const* d_tgt,
-                         const size_t* n_tgt, int n_slots, size_t stride, const IcpParams& prm, const IcpTuning& tune)
+                         const size_t* n_tgt, int n_slots, size_t stride, const IcpParams& prm, const IcpTuning& tune, const float* const* guess)
 {
     if (w->fl.phase != 0 || n_src_ == 0 || n_slots < 1 || n_slots > kIcpMaxSlots || prm.max_iter < 1) return hipErrorInvalidValue;
     for (int k = 0; k < n_slots; k++) if (n_tgt[k] == 0) return hipErrorInvalidValue;
     ICP_TRY(dev_layout(w, n_slots, n_src_, n_tgt, &tune));
-    ICP_TRY(load_slots(w, stream, d_src, nullptr, stride));
+    set_guesses(w, guess);
+    ICP_TRY(load_slots(w, stream, d_src, nullptr, stride, true));
     ICP_TRY(load_slots(w, stream, nullptr, d_tgt, stride));
     ICP_TRY(dev_prepare(w, stream, tune));
     IcpWorkspace::Flight& f = w->fl;
@@ -923,21 +963,22 @@ hipError_t icp_dev_grid(IcpWorkspace* w, hipStream_t stream, const unsigned char
 }
 
 hipError_t icp_align(IcpWorkspace* w, hipStream_t stream, const unsigned char* d_src, size_t n_src_, const unsigned char* d_tgt,
-                     size_t n_tgt_, size_t stride, const IcpParams& prm, IcpResult* res)
+                     size_t n_tgt_, size_t stride, const IcpParams& prm, IcpResult* res, const float* guess)
 {
     const int n_src = (int)n_src_;
     *res = icp_result_none();
     if (n_src_ == 0 || n_tgt_ == 0) return hipSuccess;
     if (w->fl.phase != 0) return hipErrorInvalidValue;                    // (the layout is the flight's: the callers answer BUSY before)
     ICP_TRY(dev_layout(w, 1, n_src_, &n_tgt_, nullptr));
-    ICP_TRY(load_slots(w, stream, d_src, nullptr, stride));
+    set_guesses(w, &guess);
+    ICP_TRY(load_slots(w, stream, d_src, nullptr, stride, true));
     ICP_TRY(load_slots(w, stream, nullptr, &d_tgt, stride));
 
     // icp.hpp computeTransformation + default_convergence_criteria.hpp hasConverged: icp_close_step, between two synchronisations
     const double max_d2 = prm.max_corr_dist * prm.max_corr_dist;
     const IcpCloseParams cp = icp_close_params(prm.max_iter, prm.trans_eps, prm.fit_eps);
     IcpLoopState st;
-    icp_state_init(&st);
+    icp_state_init(&st, w->G.set[0] ? w->G.T[0] : nullptr);       // final_transformation_ = guess
     for (;;) {
         ICP_TRY(host_sums(w, stream, max_d2));
         const int it_before = st.it;

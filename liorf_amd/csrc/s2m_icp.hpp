@@ -26,8 +26,12 @@ inline IcpResult icp_result_none()
 
 // src / tgt: device records (x, y, z at byte 0/4/8). Synchronises `stream` once per iteration (the
 // close of an iteration, icp_close_step, runs on the host between iterations). Not beside a device loop in flight.
+// guess: align(output, guess) - a row-major 4x4 (host) that final_transformation_ starts from, the source moved by it (fp32,
+// m0*x + m1*y + m2*z + m3 left to right, k_icp_transform's arithmetic) before the first search; res->T includes it. Null or
+// equal to the identity: no guess, the alignment from the identity with the source as it is.
 hipError_t icp_align(IcpWorkspace* w, hipStream_t stream, const unsigned char* d_src, size_t n_src,
-                     const unsigned char* d_tgt, size_t n_tgt, size_t stride, const IcpParams& prm, IcpResult* res);
+                     const unsigned char* d_tgt, size_t n_tgt, size_t stride, const IcpParams& prm, IcpResult* res,
+                     const float* guess = nullptr);
 
 // ---- the device loop: the same alignment queued on a stream and left alone ------------------------------------------------
 // Every iteration is closed on the device (k_icp_close runs icp_close_step, the host loop's own source: s2m_icp_close.hpp), so
@@ -47,8 +51,12 @@ void icp_dev_cancel(IcpWorkspace* w);                                    // forg
 // One source against n_slots <= kIcpMaxSlots targets (the single alignment: n_slots = 1): n_slots independent alignments advance
 // through the same launches, the slot a grid dimension of every kernel. Loads the clouds, builds a grid over every target, queues
 // the first range. n_src, n_tgt[k] > 0. Does not wait.
+// guess: null, or n_slots pointers, each null or a row-major 4x4 (host, read before the call returns): slot k's guess as icp_align
+// takes one - every slot owns its moving copy of the source, so the slots may start at different places. Slot k gives the bits
+// icp_align gives for d_tgt[k] with guess[k].
 hipError_t icp_dev_begin(IcpWorkspace* w, hipStream_t stream, const unsigned char* d_src, size_t n_src, const unsigned char* const* d_tgt,
-                         const size_t* n_tgt, int n_slots, size_t stride, const IcpParams& prm, const IcpTuning& tune);
+                         const size_t* n_tgt, int n_slots, size_t stride, const IcpParams& prm, const IcpTuning& tune,
+                         const float* const* guess = nullptr);
 // wait == false: tests the event (hipEventQuery) and, where the queued work has ended, queues what follows (the next range, or
 // the fitness pass) without waiting for it; wait == true: the same with hipEventSynchronize until the result is there. Ranges are
 // queued until every slot has ended - a slot that has ended idles meanwhile - then one fitness pass runs for all.

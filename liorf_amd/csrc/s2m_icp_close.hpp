@@ -131,9 +131,10 @@ S2M_ICP_HD inline IcpCloseParams icp_close_params(int max_iter, double trans_eps
     return IcpCloseParams{ max_iter, 1.0 - trans_eps, trans_eps, 1e-12, fit_eps, 0 /* max_iterations_similar_transforms_ */ };
 }
 
-S2M_ICP_HD inline void icp_state_init(IcpLoopState* st)
+// guess: final_transformation_ at the start (align(output, guess)), a row-major 4x4; null: the identity
+S2M_ICP_HD inline void icp_state_init(IcpLoopState* st, const float* guess = nullptr)
 {
-    for (int i = 0; i < 16; i++) { st->T[i] = (i % 5 == 0) ? 1.0f : 0.0f; st->T_step[i] = st->T[i]; }
+    for (int i = 0; i < 16; i++) { st->T_step[i] = (i % 5 == 0) ? 1.0f : 0.0f; st->T[i] = guess ? guess[i] : st->T_step[i]; }
     st->prev_mse = DBL_MAX;
     st->it = 0; st->conv = 0; st->similar = 0; st->done = 0;
 }

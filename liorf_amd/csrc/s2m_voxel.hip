@@ -800,7 +800,7 @@ __device__ void kf_bitonic(unsigned long long* a, int P)
 // partial boxes). More than kKfTile candidates: nothing is done here but st->n_cand, and st->n_cent is 0 - the host runs the
 // device-wide sort (kf_select_wide) after its wait.
 template <bool PRE>
-__global__ __launch_bounds__(kKfThreads) void k_kf_select_candidates(const float4* __restrict__ pos, int n, float r2, float density,
+__global__ __launch_bounds__(kKfThreads) void k_kf_select_candidates(const float4* __restrict__ pos, int n, const float4 q, float r2, float density,
                                                                      unsigned long long* __restrict__ g_key, int32_t* __restrict__ g_ord,
                                                                      float4* __restrict__ cent, KfSelState* __restrict__ st,
                                                                      const VoxSetup* __restrict__ pre_vs, const uint32_t* __restrict__ cand_d2,
@@ -823,7 +823,6 @@ __global__ __launch_bounds__(kKfThreads) void k_kf_select_candidates(const float
         for (int r = tid; r < m; r += kKfThreads) g_key[r] = ((unsigned long long)cand_d2[r] << 32) | (uint32_t)cand_key[r];
         __syncthreads();
     } else {
-    const float4 q = pos[n - 1];
     // (b) every key with d2 < r2, compacted in key order, as (d2 bits, key): FLANN's sorted radius result once sorted
     uint32_t lo[3] = { 0xffffffffu, 0xffffffffu, 0xffffffffu }, hi[3] = { 0u, 0u, 0u };
     for (int base = 0; base < n; base += kKfThreads) {
@@ -938,7 +937,7 @@ __global__ __launch_bounds__(256) void k_kf_select_nearest(const float4* __restr
 // (e) + (f) + the frame table: entry e < n_cent is centroid e's key tested at the centroid, entry n_cent + r is key n-1-r tested at
 // its own position; an entry farther than `radius` from the newest key is dropped; survivors keep their order
 __global__ __launch_bounds__(kKfThreads) void k_kf_select_frames(const float4* __restrict__ pos, const KfFrame* __restrict__ frames, int n,
-                                                                 int n_recent, float radius, const float4* __restrict__ cent,
+                                                                 const float4 q, int n_recent, float radius, const float4* __restrict__ cent,
                                                                  const int32_t* __restrict__ nn, const KfSelState* __restrict__ st,
                                                                  int32_t* __restrict__ keys, const unsigned char** __restrict__ t_src,
                                                                  int32_t* __restrict__ t_off, float* __restrict__ t_T, KfSelect* out)
@@ -946,7 +945,6 @@ __global__ __launch_bounds__(kKfThreads) void k_kf_select_frames(const float4* _
     __shared__ int s_w[kKfThreads / 64];
     __shared__ long long s_wl[kKfThreads / 64];
     const int n_cent = st->n_cent, n_ent = n_cent + n_recent;
-    const float4 q = pos[n - 1];
     int nf = 0;
     long long np = 0;
     for (int base = 0; base < n_ent; base += kKfThreads) {
@@ -1005,13 +1003,12 @@ __device__ __forceinline__ int32_t kf_wave_sum(int32_t v)
     return v;
 }
 
-__global__ __launch_bounds__(256) void k_kf_radius_count(const float4* __restrict__ pos, int n, float r2, uint32_t* __restrict__ part)
+__global__ __launch_bounds__(256) void k_kf_radius_count(const float4* __restrict__ pos, int n, const float4 q, float r2, uint32_t* __restrict__ part)
 {
     __shared__ uint32_t s_mm[4][6];
     __shared__ int32_t s_c[4];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int base = blockIdx.x * kRsTile + wave * (kRsTile / 4);
-    const float4 q = pos[n - 1];
     uint32_t lo[3] = { 0xffffffffu, 0xffffffffu, 0xffffffffu }, hi[3] = { 0u, 0u, 0u };
     int32_t c = 0;
     for (int r = 0; r < kRsRounds; r++) {
@@ -1048,13 +1045,12 @@ __global__ __launch_bounds__(256) void k_kf_radius_count(const float4* __restric
     }
 }
 
-__global__ __launch_bounds__(256) void k_kf_radius_write(const float4* __restrict__ pos, int n, float r2, const uint32_t* __restrict__ part,
+__global__ __launch_bounds__(256) void k_kf_radius_write(const float4* __restrict__ pos, int n, const float4 q, float r2, const uint32_t* __restrict__ part,
                                                          uint32_t* __restrict__ cand_d2, int32_t* __restrict__ cand_key)
 {
     __shared__ int32_t wsum[4], bsum[4];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int base = blockIdx.x * kRsTile + wave * (kRsTile / 4);
-    const float4 q = pos[n - 1];
     int32_t before = 0;                               // hits in the blocks before this one
     for (int j = threadIdx.x; j < (int)blockIdx.x; j += 256) before += (int32_t)part[8 * j + 6];
     before = kf_wave_sum(before);
@@ -1376,11 +1372,12 @@ hipError_t kf_select_wide(VoxWorkspace* w, hipStream_t stream, const float4* d_p
 
 }  // namespace
 
-hipError_t kf_select(VoxWorkspace* w, hipStream_t stream, const float4* d_pos, const KfFrame* d_frames, int n, int n_recent,
-                     float radius, float density, KfSelect* out, KfTable* tab)
+hipError_t kf_select(VoxWorkspace* w, hipStream_t stream, const float4* d_pos, const KfFrame* d_frames, int n, const float centre[3],
+                     int n_recent, float radius, float density, KfSelect* out, KfTable* tab)
 {
     *out = KfSelect{};
     if (n <= 0) return hipSuccess;
+    const float4 q = make_float4(centre[0], centre[1], centre[2], 0.0f);   // the kernels' centre, by value (extractSurroundingKeyFrames: P[n-1])
     const bool wide = n > kKfTile;                             // (b) over the whole grid; (c) too when the candidates pass the tile
     size_t P = 1;
     while (P < (size_t)(wide ? kKfTile : n)) P <<= 1;
@@ -1407,12 +1404,12 @@ hipError_t kf_select(VoxWorkspace* w, hipStream_t stream, const float4* d_pos, c
     auto nearest_and_frames = [&]() {
         hipLaunchKernelGGL(k_kf_select_nearest, dim3((unsigned)(n < 1024 ? n : 1024)), dim3(256), 0, stream, d_pos, n, (const float4*)cent,
                            (const KfSelState*)st, nn);
-        hipLaunchKernelGGL(k_kf_select_frames, dim3(1), dim3(kKfThreads), 0, stream, d_pos, d_frames, n, n_recent, radius, (const float4*)cent,
+        hipLaunchKernelGGL(k_kf_select_frames, dim3(1), dim3(kKfThreads), 0, stream, d_pos, d_frames, n, q, n_recent, radius, (const float4*)cent,
                            (const int32_t*)nn, (const KfSelState*)st, (int32_t*)tab->keys, (const unsigned char**)t, (int32_t*)tab->offsets,
                            (float*)tab->T, w->h_kf);
     };
     if (!wide) {
-        hipLaunchKernelGGL(k_kf_select_candidates<false>, dim3(1), dim3(kKfThreads), 0, stream, d_pos, n, r2, density,
+        hipLaunchKernelGGL(k_kf_select_candidates<false>, dim3(1), dim3(kKfThreads), 0, stream, d_pos, n, q, r2, density,
                            w->kf_key.as<unsigned long long>(), w->kf_ord.as<int32_t>(), cent, st,
                            (const VoxSetup*)nullptr, (const uint32_t*)nullptr, (const int32_t*)nullptr);
     } else {
@@ -1421,12 +1418,12 @@ hipError_t kf_select(VoxWorkspace* w, hipStream_t stream, const float4* d_pos, c
         VOX_TRY(w->kf_vs.ensure(sizeof(VoxSetup)));
         VOX_TRY(w->keys_a.ensure(4 * (size_t)n)); VOX_TRY(w->vals_a.ensure(4 * (size_t)n));
         uint32_t* part = w->kf_part.as<uint32_t>();
-        hipLaunchKernelGGL(k_kf_radius_count, dim3(nblk), dim3(256), 0, stream, d_pos, n, r2, part);
+        hipLaunchKernelGGL(k_kf_radius_count, dim3(nblk), dim3(256), 0, stream, d_pos, n, q, r2, part);
         hipLaunchKernelGGL(k_vox_setup, dim3(1), dim3(64), 0, stream, w->kf_vs.as<VoxSetup>(), density, (const uint32_t*)part, nblk);
-        hipLaunchKernelGGL(k_kf_radius_write, dim3(nblk), dim3(256), 0, stream, d_pos, n, r2, (const uint32_t*)part,
+        hipLaunchKernelGGL(k_kf_radius_write, dim3(nblk), dim3(256), 0, stream, d_pos, n, q, r2, (const uint32_t*)part,
                            w->keys_a.as<uint32_t>(), w->vals_a.as<int32_t>());
         // up to kKfTile candidates: the single-workgroup kernel takes them from here; more: it only reports their number
-        hipLaunchKernelGGL(k_kf_select_candidates<true>, dim3(1), dim3(kKfThreads), 0, stream, d_pos, n, r2, density,
+        hipLaunchKernelGGL(k_kf_select_candidates<true>, dim3(1), dim3(kKfThreads), 0, stream, d_pos, n, q, r2, density,
                            w->kf_key.as<unsigned long long>(), w->kf_ord.as<int32_t>(), cent, st,
                            (const VoxSetup*)w->kf_vs.as<VoxSetup>(), (const uint32_t*)w->keys_a.as<uint32_t>(),
                            (const int32_t*)w->vals_a.as<int32_t>());

@@ -63,13 +63,15 @@ struct KfTable {                           // the frame table, device memory, va
     const float* T;
     const int32_t* keys;
 };
-// pos[k] = {x, y, z, 0} of key k, k = 0 .. n-1. n_recent: the newest keys whose time passes the recent-key test (:1000-1007, counted by
+// pos[k] = {x, y, z, 0} of key k, k = 0 .. n-1. centre: the point the radius search (b) and the distance filter (f) measure from, handed
+// to the kernels by value - extractSurroundingKeyFrames and the global map pass P[n-1]'s own bits, s2m_extract_surrounding_at any
+// finite point. n_recent: the newest keys whose time passes the recent-key test (:1000-1007, counted by
 // the caller in double). Chooses the frames (radius search, key-pose voxel filter with leaf `density`, nearest key of every
 // centroid, recent keys, distance filter), writes the table and synchronises `stream` once for the counts. Stores of more than
 // 4 096 keys run the radius search over the whole grid; more than 4 096 candidates are sorted and filtered by device-wide radix
 // passes after a first wait for their number (a second wait). Either way the result is that of the single-workgroup kernel.
-hipError_t kf_select(VoxWorkspace* w, hipStream_t stream, const float4* d_pos, const KfFrame* d_frames, int n, int n_recent,
-                     float radius, float density, KfSelect* out, KfTable* tab);
+hipError_t kf_select(VoxWorkspace* w, hipStream_t stream, const float4* d_pos, const KfFrame* d_frames, int n, const float centre[3],
+                     int n_recent, float radius, float density, KfSelect* out, KfTable* tab);
 
 // ---- detectLoopClosureDistance() (:732-765) on the same store: pos[k] and time[k] of key k = 0 .. n-1. *key_pre = the key with the
 // least (d2, k) among those with d2(P[k], P[n-1]) < radius * radius (fp32, as kf_select) and |time[k] - time_cur| > time_diff

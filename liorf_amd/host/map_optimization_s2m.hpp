@@ -190,6 +190,27 @@ public:
         }
     }
 
+    // s2m_extract_surrounding_at: the same around centre_xyz instead of the newest key, without the recent keys - the local map of
+    // a node that was localised in a stored map (relocalizeScan below) and is not at its newest key
+    void extractSurroundingKeyFramesAt(const float centre_xyz[3])
+    {
+        s2m_kf_params p;
+        s2m_kf_default_params(&p);
+        p.search_radius = surroundingKeyframeSearchRadius;
+        p.density = surroundingKeyframeDensity;
+        p.map_leaf = surroundingKeyframeMapLeafSize;
+        surroundingKeyInds.resize(2 * cloudKeyPoses6D.size() + 1);
+        size_t n_out = 0, n_keys = 0;
+        checkVoxel(s2m_extract_surrounding_at(h_, centre_xyz, &p, nullptr, sizeof(PointXYZI), 0, &n_out,
+                                              surroundingKeyInds.data(), surroundingKeyInds.size(), &n_keys),
+                   "s2m_extract_surrounding_at");
+        surroundingKeyInds.resize(n_keys);
+        if (!cloudKeyPoses6D.empty()) {
+            laserCloudSurfFromMapDSNum = (int)n_out;
+            haveKeyPoses = true;
+        }
+    }
+
     // the key-frame part of saveKeyFramesAndFactor() (:1549-1580): the pose after scan2MapOptimization() and
     // laserCloudSurfLastDS as downsampleCurrentScan() left it on the device (copied device to device)
     void saveKeyFrame()
@@ -448,6 +469,23 @@ public:
         return true;
     }
 
+    // icp.align(output, guess): the same block started at `guess` (row-major 4x4, nullptr: the identity - icpAlign);
+    // finalTransformation includes the guess
+    bool icpAlignGuess(const std::vector<PointXYZI>& cureKeyframeCloud, const std::vector<PointXYZI>& prevKeyframeCloud,
+                       const float guess[16], float finalTransformation[16])
+    {
+        if (cureKeyframeCloud.size() < 300 || prevKeyframeCloud.size() < 1000) return false;       // :565-566
+        s2m_icp_params p;
+        s2m_icp_default_params(&p);
+        p.max_correspondence_distance = historyKeyframeSearchRadius * 2;                            // :573
+        s2m_icp_result r;
+        check(s2m_icp_align_guess(h_, cureKeyframeCloud.data(), cureKeyframeCloud.size(), prevKeyframeCloud.data(),
+                                  prevKeyframeCloud.size(), sizeof(PointXYZI), guess, &p, &r), "s2m_icp_align_guess");
+        if (!r.converged || r.fitness_score > historyKeyframeFitnessScore) return false;            // :585-586
+        std::memcpy(finalTransformation, r.T, sizeof(r.T));
+        return true;
+    }
+
     // Loop closure against the resident key-frame store (:542-844): no host key-frame clouds and no kdtreeHistoryKeyPoses.
     // Every call runs under the lock the scan handler holds (one handle, calls not concurrent); the launched forms below hold it
     // up to the size gate only. GTSAM stays here: an
@@ -526,6 +564,29 @@ public:
         lastBest = best;
         return verifyAccepted();
     }
+    // -- relocalisation: where in the stored map is this scan (s2m_relocalize_scan) --
+    // The top relocTopK hits of the place query, each aligned from T(pose[key]) * Rz(-yaw) in lockstep; lastReloc holds the
+    // records in the query's order, lastRelocBest the accepted one with the least (fitness, position) or -1. true: a record was
+    // accepted, and transformTobeMapped is its pose - extractSurroundingKeyFramesAt(&transformTobeMapped[3]) installs the map there.
+    int relocTopK = 4;
+    std::vector<s2m_reloc_candidate> lastReloc;
+    int lastRelocBest = -1;
+    bool relocalizeScan(const std::vector<PointXYZI>& scan)
+    {
+        s2m_reloc_params p;
+        s2m_reloc_default_params(&p);
+        p.query.top_k = relocTopK;
+        p.loop = loopParams();
+        lastReloc.assign(S2M_LOOP_MAX_CANDIDATES, s2m_reloc_candidate{});
+        int32_t n = 0, best = -1;
+        check(s2m_relocalize_scan(h_, scan.data(), scan.size(), sizeof(PointXYZI), 0, &p, lastReloc.data(), &n, &best), "s2m_relocalize_scan");
+        lastReloc.resize((size_t)n);
+        lastRelocBest = best;
+        if (best < 0) return false;
+        std::memcpy(transformTobeMapped, lastReloc[(size_t)best].pose_tobemapped, sizeof(float) * 6);
+        return true;
+    }
+
     // true: a verification is pending (false: lastVerify is final)
     bool loopVerifyLaunch(int key_cur, const std::vector<int32_t>& key_pre, int base_key = -1)
     {

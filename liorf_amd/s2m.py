@@ -36,14 +36,16 @@ ABI_SYMBOLS = [
     "s2m_debug_scan_prep",
     "s2m_voxel_downsample", "s2m_voxel_downsample_device", "s2m_downsample_scan", "s2m_extract_cloud",
     "s2m_transform_cloud",
-    "s2m_icp_default_params", "s2m_icp_align", "s2m_debug_device_trig", "s2m_debug_device_hypot",
+    "s2m_icp_default_params", "s2m_icp_align", "s2m_icp_align_guess", "s2m_debug_device_trig", "s2m_debug_device_hypot",
     "s2m_debug_lm_close", "s2m_debug_lm_close_check_args",
     "s2m_sc_reset", "s2m_sc_size", "s2m_sc_add_scan", "s2m_sc_add_descriptor", "s2m_sc_detect_loop", "s2m_sc_distance",
     "s2m_sc_query_default_params", "s2m_sc_query_check_args", "s2m_sc_query_key", "s2m_sc_query_descriptor", "s2m_sc_query_scan", "s2m_sc_query_projected",
     "s2m_kf_default_params", "s2m_kf_reset", "s2m_kf_size", "s2m_kf_add", "s2m_kf_set_poses", "s2m_extract_surrounding",
+    "s2m_extract_surrounding_at",
     "s2m_loop_default_params", "s2m_loop_near_keyframes", "s2m_loop_align", "s2m_loop_closure_rs",
     "s2m_loop_align_launch", "s2m_loop_closure_rs_launch", "s2m_loop_poll", "s2m_loop_collect",
     "s2m_loop_verify_check_args", "s2m_loop_verify_launch", "s2m_loop_verify_poll", "s2m_loop_verify_collect", "s2m_loop_verify",
+    "s2m_reloc_default_params", "s2m_relocalize_check_args", "s2m_relocalize_scan", "s2m_debug_icp_align_guess_many_device",
     "s2m_debug_icp_nearest", "s2m_debug_icp_time_nearest", "s2m_debug_icp_align_device", "s2m_debug_icp_align_many_device",
     "s2m_debug_icp_tuning", "s2m_debug_icp_grid_check_args", "s2m_debug_icp_grid",
     "s2m_gmap_default_params", "s2m_global_map", "s2m_kf_map_cloud",
@@ -158,6 +160,17 @@ class LoopParams(C.Structure):
 class LoopResult(C.Structure):
     _fields_ = [("status", C.c_int32), ("key_cur", C.c_int32), ("key_pre", C.c_int32), ("n_cur", C.c_int32),
                 ("n_prev", C.c_int32), ("icp", IcpResult), ("pose_from", C.c_float * 6), ("pose_to", C.c_float * 6)]
+
+
+class RelocParams(C.Structure):
+    """s2m_reloc_params: the place query, the loop's submap / ICP / gate settings, and whether the hit's yaw goes into the guess."""
+    _fields_ = [("query", ScQueryParams), ("loop", LoopParams), ("use_yaw", C.c_int32), ("reserved", C.c_int32)]
+
+
+class RelocCandidate(C.Structure):
+    """s2m_reloc_candidate: one hit of the query with its alignment; icp.T maps the scan's frame into the map frame."""
+    _fields_ = [("hit", ScHit), ("status", C.c_int32), ("n_src", C.c_int32), ("n_tgt", C.c_int32), ("guess", C.c_float * 16),
+                ("icp", IcpResult), ("pose_xyzrpy", C.c_float * 6), ("pose_tobemapped", C.c_float * 6)]
 
 
 class GmapParams(C.Structure):
@@ -309,6 +322,7 @@ def load_library(path: str | None = None) -> C.CDLL:
     L.s2m_debug_lm_close_check_args.argtypes = [C.c_int, C.c_int, C.c_int, dp, C.c_int, fp, fp, C.POINTER(LmCloseOut)]
     L.s2m_icp_default_params.argtypes = [C.POINTER(IcpParams)]
     L.s2m_icp_align.argtypes = [vp, vp, C.c_size_t, vp, C.c_size_t, C.c_size_t, C.POINTER(IcpParams), C.POINTER(IcpResult)]
+    L.s2m_icp_align_guess.argtypes = [vp, vp, C.c_size_t, vp, C.c_size_t, C.c_size_t, fp, C.POINTER(IcpParams), C.POINTER(IcpResult)]
     L.s2m_sc_reset.argtypes = [vp]
     L.s2m_sc_size.argtypes = [vp]
     L.s2m_sc_add_scan.argtypes = [vp, vp, C.c_size_t, C.c_size_t]
@@ -329,6 +343,7 @@ def load_library(path: str | None = None) -> C.CDLL:
     L.s2m_kf_set_poses.argtypes = [vp, C.c_int, C.c_int, fp]
     L.s2m_extract_surrounding.argtypes = [vp, C.c_double, C.POINTER(KfParams), vp, C.c_size_t, C.c_size_t, szp, i32p,
                                           C.c_size_t, szp]
+    L.s2m_extract_surrounding_at.argtypes = [vp, fp, C.POINTER(KfParams), vp, C.c_size_t, C.c_size_t, szp, i32p, C.c_size_t, szp]
     L.s2m_loop_default_params.argtypes = [C.POINTER(LoopParams)]
     L.s2m_loop_near_keyframes.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, C.c_float, vp, C.c_size_t, C.c_size_t, szp]
     L.s2m_loop_align.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, C.POINTER(LoopParams), C.POINTER(LoopResult)]
@@ -344,6 +359,11 @@ def load_library(path: str | None = None) -> C.CDLL:
     L.s2m_loop_verify_collect.argtypes = L.s2m_loop_verify_poll.argtypes
     L.s2m_debug_icp_align_many_device.argtypes = [vp, vp, C.c_size_t, C.POINTER(C.c_void_p), szp, C.c_int32, C.c_size_t, C.POINTER(IcpParams),
                                                   C.POINTER(IcpResult)]
+    L.s2m_debug_icp_align_guess_many_device.argtypes = [vp, vp, C.c_size_t, C.POINTER(C.c_void_p), szp, fp, C.c_int32, C.c_size_t,
+                                                        C.POINTER(IcpParams), C.POINTER(IcpResult)]
+    L.s2m_reloc_default_params.argtypes = [C.POINTER(RelocParams)]
+    L.s2m_relocalize_check_args.argtypes = [C.c_int32, C.c_int32, C.POINTER(RelocParams)]
+    L.s2m_relocalize_scan.argtypes = [vp, vp, C.c_size_t, C.c_size_t, C.c_int, C.POINTER(RelocParams), C.POINTER(RelocCandidate), i32p, i32p]
     L.s2m_debug_icp_nearest.argtypes = [vp, vp, C.c_size_t, vp, C.c_size_t, C.c_size_t, C.c_int32, vp, C.POINTER(C.c_int32)]
     L.s2m_debug_icp_time_nearest.argtypes = [vp, vp, C.c_size_t, vp, C.c_size_t, C.c_size_t, C.c_int32, C.c_int32, vp, C.POINTER(C.c_int32), fp, fp]
     L.s2m_debug_icp_align_device.argtypes = [vp, vp, C.c_size_t, vp, C.c_size_t, C.c_size_t, C.POINTER(IcpParams), C.POINTER(IcpResult)]
@@ -869,6 +889,31 @@ class MapOptimizationS2M:
         self._check(self.lib.s2m_icp_align(self.h, a.ctypes.data, na, b.ctypes.data, nb, st, C.byref(p), C.byref(r)), "s2m_icp_align")
         return np.array(r.T, np.float32).reshape(4, 4), bool(r.converged), r.fitness_score, r.iterations
 
+    @staticmethod
+    def _guess_arg(guess):
+        """A row-major 4x4 as the float pointer s2m_icp_align_guess takes (None: a null pointer, the identity)."""
+        if guess is None:
+            return None, None
+        g = np.ascontiguousarray(guess, np.float32).reshape(16)
+        return g, _fp(g)
+
+    def icpAlignGuess(self, cureKeyframeCloud, prevKeyframeCloud, guess=None, **params):
+        """icp.align(output, guess): the alignment started at the 4x4 `guess` (None or the identity: icpAlign). The returned T
+        includes the guess. (T 4x4, hasConverged, getFitnessScore, iterations)."""
+        a, na, st = _records(cureKeyframeCloud)
+        b, nb, st2 = _records(prevKeyframeCloud)
+        if st != st2:
+            raise ValueError("both clouds must share one record stride")
+        p = IcpParams()
+        self.lib.s2m_icp_default_params(C.byref(p))
+        for k, v in params.items():
+            setattr(p, k, v)
+        r = IcpResult()
+        g, gp = self._guess_arg(guess)
+        self._check(self.lib.s2m_icp_align_guess(self.h, a.ctypes.data, na, b.ctypes.data, nb, st, gp, C.byref(p), C.byref(r)),
+                    "s2m_icp_align_guess")
+        return np.array(r.T, np.float32).reshape(4, 4), bool(r.converged), r.fitness_score, r.iterations
+
     # -- SCManager (reference include/Scancontext.cpp), SURVEY.md section 8(f) row F3 --------------
     def scReset(self):
         self._check(self.lib.s2m_sc_reset(self.h), "s2m_sc_reset")
@@ -987,6 +1032,58 @@ class MapOptimizationS2M:
         out = np.zeros((max(m.value, 1), 8), np.float32)
         run(out.ctypes.data, m.value)                 # (the same selection again: deterministic, same map)
         return k, out[:m.value]
+
+    def extractSurroundingKeyFramesAt(self, centre_xyz, params: KfParams | None = None, readback: bool = True, return_map: bool = False):
+        """s2m_extract_surrounding_at: extractSurroundingKeyFrames around `centre_xyz` instead of the newest key, without the
+        recent keys, installed as the local map. Returns as extractSurroundingKeyFrames does."""
+        n = max(self.kfSize(), 0)
+        keys = np.zeros(2 * n + 1, np.int32)
+        m, nk = C.c_size_t(0), C.c_size_t(0)
+        pp = C.byref(params) if params is not None else None
+        c = np.ascontiguousarray(centre_xyz, np.float32).reshape(3)
+
+        def run(out, cap):
+            return self._check_voxel(
+                self.lib.s2m_extract_surrounding_at(self.h, _fp(c), pp, out, 32, cap, C.byref(m),
+                                                    keys.ctypes.data_as(C.POINTER(C.c_int32)) if readback else None,
+                                                    keys.size if readback else 0, C.byref(nk)), "s2m_extract_surrounding_at")
+        self.leaf_too_small = run(None, 0)
+        self.laserCloudSurfFromMapDSNum = m.value
+        k = keys[:nk.value].copy() if readback else None
+        if not return_map:
+            return k
+        out = np.zeros((max(m.value, 1), 8), np.float32)
+        run(out.ctypes.data, m.value)                 # (the same selection again: deterministic, same map)
+        return k, out[:m.value]
+
+    # -- relocalisation: a scan that is no key against the stored map ---------------------------------------------
+    def relocalizeScan(self, scan, params: "RelocParams | None" = None, device_ptr=None):
+        """s2m_relocalize_scan: (records, best). records are the query's hits in its order, each aligned from
+        T(pose[key]) * Rz(-yaw); best is the accepted record with the least (fitness, position), or -1.
+        `device_ptr=(ptr, n, stride_bytes)` takes a scan that already lives in HBM."""
+        if device_ptr is not None:
+            ptr, n, st = device_ptr
+            src, on_dev = C.c_void_p(ptr), 1
+        else:
+            a, n, st = _records(scan)
+            src, on_dev = a.ctypes.data, 0
+        recs = (RelocCandidate * S2M_LOOP_MAX_CANDIDATES)()
+        n_out, best = C.c_int32(0), C.c_int32(-1)
+        pp = C.byref(params) if params is not None else None
+        self._check(self.lib.s2m_relocalize_scan(self.h, src, n, st, on_dev, pp, recs, C.byref(n_out), C.byref(best)), "s2m_relocalize_scan")
+        return [_copy_struct(recs[i]) for i in range(n_out.value)], best.value
+
+    def localizeInStoredMap(self, scan, reloc: "RelocParams | None" = None, kf: KfParams | None = None):
+        """Start (or recover) inside the stored map: relocalise `scan`, install the local map around the best pose and set
+        transformTobeMapped to it, so that downsampleCurrentScan + scan2MapOptimization track from there. Returns
+        (pose_tobemapped, records, best), the pose None when no hit was accepted (nothing is installed then)."""
+        recs, best = self.relocalizeScan(scan, reloc)
+        if best < 0:
+            return None, recs, best
+        pose = np.array(recs[best].pose_tobemapped, np.float32)
+        self.extractSurroundingKeyFramesAt(pose[3:6], kf, readback=False)
+        self.transformTobeMapped = pose.copy()
+        return pose, recs, best
 
     # -- the pose graph beside the store (reference :1386-1534, :1611-1642) --------
     def pgReset(self):
@@ -1329,6 +1426,25 @@ class MapOptimizationS2M:
                     "s2m_debug_icp_align_many_device")
         return [(np.array(r.T, np.float32).reshape(4, 4), bool(r.converged), r.fitness_score, r.iterations) for r in out[:len(tg)]]
 
+    def debugIcpAlignGuessManyDevice(self, cureKeyframeCloud, prevKeyframeClouds, guesses, **params):
+        """s2m_debug_icp_align_guess_many_device: debugIcpAlignManyDevice with a 4x4 guess per target (guesses=None: none); slot i
+        gives what icpAlignGuess(cure, prev[i], guesses[i]) gives."""
+        a, na, st = _records(cureKeyframeCloud)
+        tg = [_records(t) for t in prevKeyframeClouds]
+        if any(t[2] != st for t in tg):
+            raise ValueError("all clouds must share one record stride")
+        p = IcpParams()
+        self.lib.s2m_icp_default_params(C.byref(p))
+        for k, v in params.items():
+            setattr(p, k, v)
+        ptrs = (C.c_void_p * max(len(tg), 1))(*[t[0].ctypes.data for t in tg])
+        ns = (C.c_size_t * max(len(tg), 1))(*[t[1] for t in tg])
+        out = (IcpResult * max(len(tg), 1))()
+        g = None if guesses is None else np.ascontiguousarray(guesses, np.float32).reshape(len(tg), 16)
+        self._check(self.lib.s2m_debug_icp_align_guess_many_device(self.h, a.ctypes.data, na, ptrs, ns, None if g is None else _fp(g),
+                                                                   len(tg), st, C.byref(p), out), "s2m_debug_icp_align_guess_many_device")
+        return [(np.array(r.T, np.float32).reshape(4, 4), bool(r.converged), r.fitness_score, r.iterations) for r in out[:len(tg)]]
+
     def debugIcpNearest(self, src, tgt, mode: int, reps: int = 0):
         """s2m_debug_icp_nearest / s2m_debug_icp_time_nearest: (keys uint64 per source point, n_fallback[, us_build, us_search]);
         mode 0 = k_icp_nn, mode 1 = the grid search with its fallback."""
@@ -1509,6 +1625,23 @@ def loop_verify_best(records) -> int:
     """The model of *best: the position of the S2M_LOOP_ACCEPTED record with the least (icp.fitness_score, position), or -1."""
     ranked = sorted((r.icp.fitness_score, i) for i, r in enumerate(records) if r.status == S2M_LOOP_ACCEPTED)
     return ranked[0][1] if ranked else -1
+
+
+def default_reloc_params(**kw) -> RelocParams:
+    """s2m_reloc_default_params; keyword arguments set fields, `query_*` and `loop_*` those of the two nested structures."""
+    p = RelocParams()
+    load_library().s2m_reloc_default_params(C.byref(p))
+    for k, v in kw.items():
+        tgt, name = (p.query, k[6:]) if k.startswith("query_") else (p.loop, k[5:]) if k.startswith("loop_") else (p, k)
+        if not hasattr(tgt, name):
+            raise AttributeError(k)
+        setattr(tgt, name, v)
+    return p
+
+
+def relocalize_check_args(n_sc: int, n_kf: int, params: "RelocParams | None") -> int:
+    """s2m_relocalize_check_args (host only, no GPU): the status code. params=None passes a null pointer (the defaults)."""
+    return load_library().s2m_relocalize_check_args(n_sc, n_kf, None if params is None else C.byref(params))
 
 
 def sc_query_check_args(n_stored: int, params: "ScQueryParams | None") -> int:

@@ -32,6 +32,14 @@ search radius 15 m, search_num 25, ICP leaf 0.5, fitness 0.3, time window 30 s. 
     sequential_ms        (c) the same K through K s2m_loop_align_launch + s2m_loop_collect pairs one after the other - the baseline;
                          (a) and (c) take turns in one process after warm-up, medians of at least 10 repetitions, with (c)'s
                          min-max spread; meets_bar: (a) is below (c) by more than that spread (K = 1: not above it by more)
+  python tools/bench_loop.py --relocalize              only profiles/relocalize_bench_line.json (--relocalize-out): the first store of
+                                                       --sizes (5 000 keys) with every key's descriptor in the ScanContext store, and a
+                                                       30 000-point frame cast 0.7 m beside key 10 and turned by 0.5 rad as the query,
+    relocalize_ms        s2m_relocalize_scan from host records at top_k = 1, 4, 8 (all 60 shifts, the K nearest of keys 0 .. 27 - the
+                         keys that hold real frames - whatever their distance, search_num 25, leaf 0.5): the query, the source
+                         filter, a submap per hit, the alignments in lockstep; with the hits, their statuses and iterations, the
+                         best key and its distance from the true pose
+    query_ms             s2m_sc_query_scan alone with the same parameters; query_ms_all_keys: over all keys, threshold 0.3
   python tools/bench_loop.py --kernel-stats stats.csv  folds the k_loop_detect* and k_icp* rows of a rocprofv3
                                                        --kernel-trace --stats run into the JSON line
 """
@@ -267,8 +275,56 @@ def _verify_main(a, s2m, sizes):
         f.write(json.dumps(out) + "\n")
 
 
+def _relocalize_main(a, s2m, n):
+    from liorf_amd import synth
+    true = _true_poses(n)
+    big = _clouds([true[k] for k in range(N_BIG)] + [true[-1]])
+    small = big[1][:SMALL_PTS].copy()
+    stored = true.astype(np.float32)
+    eng = s2m.MapOptimizationS2M()
+    for k in range(n):
+        c = big[k] if k < N_BIG else (big[-1] if k == n - 1 else small)
+        eng.saveKeyFrame(stored[k], float(k), c)
+        eng.makeAndSaveScancontextAndKeys(c)
+    print(f"{n} keys stored", file=sys.stderr, flush=True)
+    q = true[10].copy()
+    q[:2] += (0.6, -0.4)
+    q[5] += 0.5
+    scene = synth.make_scene(seed=11, half=70.0, n_boxes=92)
+    scan = synth.to_xyzi(synth.make_scan(scene, np.array([q[3], q[4], q[5], q[0], q[1], 0.1 + q[2]]), "velodyne64", FRAME_PTS, seed=999))
+    out = {"workload": "tools/bench_loop.py --relocalize: s2m_relocalize_scan of a 30 000-point frame cast 0.7 m beside key 10 of the "
+                       f"{n}-key revisit and turned by 0.5 rad; all 60 shifts, the K nearest of keys 0..27 (max_dist 1e7), R 15, search_num 25, leaf 0.5, "
+                       "fitness 0.3",
+           "reps": a.reps, "warmup": a.warmup, "keys": n, "top_k": {}}
+    for K in (1, 4, 8):
+        # the query searches all keys with the default threshold first (query_ms_all_keys); the alignment is timed on the K nearest
+        # of the revisited stretch, keys 0 .. 27, which hold real frames: the other keys all hold the same 1 000-point cloud, whose
+        # descriptor is the same for every one of them, and admitting every hit would rank by key among them
+        prm = s2m.default_reloc_params(query_top_k=K, query_count=N_BIG, query_max_dist=10000000.0, loop_search_radius=15.0, loop_search_num=25,
+                                       loop_icp_leaf=0.5)
+        recs, best = eng.relocalizeScan(scan, prm)
+        row = {"hits": [r.hit.key for r in recs], "status": [r.status for r in recs], "iterations": [r.icp.iterations for r in recs],
+               "n_src": recs[0].n_src if recs else 0, "n_tgt": [r.n_tgt for r in recs], "best": best}
+        if best >= 0:
+            p = np.array(recs[best].pose_xyzrpy, np.float64)
+            row["best_key"] = recs[best].hit.key
+            row["best_position_error_m"] = round(float(np.linalg.norm(p[:3] - q[:3])), 5)
+            row["best_yaw_error_rad"] = round(float(abs((p[5] - q[5] + np.pi) % (2 * np.pi) - np.pi)), 6)
+        row["relocalize_ms"] = _median_ms(lambda: eng.relocalizeScan(scan, prm), a.warmup, a.reps)
+        row["query_ms"] = _median_ms(lambda: eng.scQueryScan(scan, prm.query), a.warmup, a.reps)
+        row["query_ms_all_keys"] = _median_ms(lambda: eng.scQueryScan(scan, top_k=K, align=s2m.S2M_SC_ALIGN_FULL), a.warmup, a.reps)
+        out["top_k"][str(K)] = row
+    eng.close()
+    out["note"] = "wall clock on the host, median after warm-up; the call waits for its result"
+    print(json.dumps(out))
+    with open(a.relocalize_out, "w") as f:
+        f.write(json.dumps(out) + "\n")
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser()
+    ap.add_argument("--relocalize", action="store_true", help="measure s2m_relocalize_scan at 1, 4 and 8 hits, and nothing else")
+    ap.add_argument("--relocalize-out", default=os.path.join(ROOT, "profiles", "relocalize_bench_line.json"))
     ap.add_argument("--verify", action="store_true", help="measure the lockstep verification against sequential closures, and nothing else")
     ap.add_argument("--verify-out", default=os.path.join(ROOT, "profiles", "loop_verify_bench_line.json"))
     ap.add_argument("--sizes", default="5000,50000")
@@ -291,6 +347,8 @@ def main(argv=None):
     sizes = [int(s) for s in a.sizes.split(",")]
     if a.verify:
         return _verify_main(a, s2m, sizes)
+    if a.relocalize:
+        return _relocalize_main(a, s2m, sizes[0])
     out = {"workload": "revisit: 30 000-point frames at keys 0..27 and the last key, 1 000 points elsewhere; R 15, search_num 25, "
                        "leaf 0.5, fitness 0.3", "sizes": {}}
     big = None
