@@ -167,7 +167,13 @@ int  s2m_optimize_collect(s2m_handle h, float pose[6], const s2m_imu_init* imu,
 int  s2m_optimize_batch(s2m_handle h, int n_scans, const void* const* scans, const size_t* sizes, size_t stride_bytes,
                         float* poses, const s2m_imu_init* imu, s2m_result* out);
 /* The same in steps: install scan b in slot b (host or device records; a device source must stay valid until the collect),
- * enqueue the batch without synchronising, synchronise and fetch. */
+ * enqueue the batch without synchronising, synchronise and fetch.
+ * One batch is in flight at a time: s2m_optimize_batch_launch is refused (S2M_ERR_INVALID_ARG, nothing changed) while a batch
+ * is pending or while one of its slots runs a loop of its own (s2m_slot_optimize_launch).
+ * A launch that is refused or fails leaves nothing pending: no slot of it can be collected.
+ * s2m_optimize_batch_collect takes the n_scans of the pending launch and is refused with any other, or with no batch pending.
+ * A collect ends the batch whatever it returns: after an error the results are lost and the slots are free again.
+ * s2m_set_params on `h` is refused while a batch or a slot is pending. */
 int  s2m_batch_set_scan(s2m_handle h, int slot, const void* pts, size_t n, size_t stride_bytes, int on_device);
 /* All slots 0 .. n_scans-1 at once: the ordering kernels of the n_scans scans share their launches (six launches for the batch
  * instead of six per scan; the host side of a batch of eight scans is otherwise a quarter of its wall time). */
@@ -180,7 +186,10 @@ int  s2m_batch_get_trace(s2m_handle h, int slot, s2m_iter_trace* out, int cap);
  * reference does downsampleCurrentScan() and scan2MapOptimization() strictly one after the other (:257-265).  Typical use:
  *     s2m_slot_set_scan(h, 0, scan0 ..);
  *     for i:  s2m_slot_optimize_launch(h, i & 1, guess_i);  s2m_slot_set_scan(h, (i + 1) & 1, scan_{i+1} ..);  s2m_slot_optimize_collect(h, i & 1, ..)
- * Every result is bitwise that of s2m_optimize on the same scan.  The map must not be replaced while a slot is in flight. */
+ * Every result is bitwise that of s2m_optimize on the same scan.  The map must not be replaced while a slot is in flight.
+ * Slots and batches do not cross: s2m_slot_optimize_launch is refused (S2M_ERR_INVALID_ARG, nothing changed) while a batch is
+ * pending, and a batch launch while a slot is in flight.
+ * s2m_slot_optimize_collect is refused on a slot that has no launch of its own pending; it ends that launch whatever it returns. */
 int  s2m_slot_set_scan(s2m_handle h, int slot, const void* pts, size_t n, size_t stride_bytes, int on_device);
 int  s2m_slot_optimize_launch(s2m_handle h, int slot, const float pose[6]);
 int  s2m_slot_optimize_collect(s2m_handle h, int slot, float pose[6], const s2m_imu_init* imu, s2m_result* out);

@@ -1,13 +1,14 @@
 // s2m_abi.hip — host side of the gfx950 scan-to-map LM loop and the part of the C ABI (include/liorf_s2m.h) that launches its
-// kernels: create / destroy / params, the context and state uploads, the loop and its graphs, launch / collect, batches and
-// slots.  The only translation unit that includes s2m_kernels.hpp / s2m_register.hpp.
+// kernels: create / destroy / params, the context and state uploads, the loop and its graphs, launch / collect of a single
+// scan.  The only translation unit that includes s2m_kernels.hpp / s2m_register.hpp.
 //
 // Runs the whole <= max_iter LM loop as one captured hipGraph (enqueue_loop) so that a scan costs one graph launch and one
-// synchronisation.  The map index and the scan preparation in front of it are s2m_prep.hip's, the observation and timing hooks
-// s2m_abi_debug.hip's (they launch the loop's kernels through the functions s2m_context.hpp declares for this unit),
-// ScanContext s2m_sc.hip's and s2m_abi_sc.hip's.  The handle is s2m_context.hpp's; the entry points that only orchestrate
-// other units' stages live in s2m_abi_voxel.hip, s2m_abi_keyframes.hip, s2m_abi_loop.hip and s2m_abi_front_end.hip.  There is
-// no CPU fallback: without a gfx950 device every entry point fails with S2M_ERR_NO_DEVICE.
+// synchronisation.  The map index and the scan preparation in front of it are s2m_prep.hip's, batches and slots
+// s2m_abi_batch.hip's, the observation and timing hooks s2m_abi_debug.hip's (both launch the loop's kernels through the
+// functions s2m_context.hpp declares for this unit), ScanContext s2m_sc.hip's and s2m_abi_sc.hip's.  The handle is
+// s2m_context.hpp's; the entry points that only orchestrate other units' stages live in s2m_abi_voxel.hip,
+// s2m_abi_keyframes.hip, s2m_abi_loop.hip and s2m_abi_front_end.hip.  There is no CPU fallback: without a gfx950 device every
+// entry point fails with S2M_ERR_NO_DEVICE.
 #include <hip/hip_runtime.h>
 
 #include <cfloat>
@@ -110,6 +111,18 @@ void s2m::host::launch_chunk_table(hipStream_t stream, const PrepTable& t, int n
     hipLaunchKernelGGL(k_chunk_table, dim3(1, nslots), dim3(1024), 0, stream, t);
 }
 
+void s2m::host::launch_set_ctxs(hipStream_t stream, CtxTable& t, int n)
+{
+    for (int j = n; j < kCtxSlots; j++) t.dst[j] = nullptr;
+    hipLaunchKernelGGL(k_set_ctxs, dim3(n), dim3(64), 0, stream, t);
+}
+
+void s2m::host::launch_init_states(hipStream_t stream, StateInitTable& t, int n)
+{
+    for (int j = n; j < kInitSlots; j++) t.s[j].dst = nullptr;
+    hipLaunchKernelGGL(k_init_states, dim3(n), dim3(256), 0, stream, t);
+}
+
 // The LM loop (:1304-1315) as a launch sequence.  One iteration L is either one launch of the fused kernel R(L), or -
 // split - the certify kernel C(L) followed by the search kernel S(L) for the workgroups C put on its worklist (launch 0 of a
 // scan, where nothing is certified yet: S alone, over every workgroup).  When the whole grid is co-resident iterations
@@ -131,7 +144,7 @@ LoopShape s2m::host::shape_of(s2m_context* h)
     sh.tbl.ctx[0] = h->reg.dctx.as<DevCtx>();
     sh.tbl.st[0] = h->reg.state.as<DevState>();
     sh.nslots = 1; sh.nblocks = h->hctx.nblocks; sh.table_cap = h->hctx.table_cap; sh.wpb = h->hctx.wpb;
-    sh.batch = h->batch.parent != nullptr && !h->batch.slot_mode;
+    sh.batch = h->batch.parent != nullptr && h->reg.pending != Reg::kSlot;    // (a slot's own loop is a single scan's)
     sh.split = h->tune.split_mode == 1;
     return sh;
 }
@@ -282,15 +295,14 @@ int get_graph(s2m_context* h, int nblocks, int part, hipGraphExec_t* out)
 int launch_loop(s2m_context* h, int part = 0)
 {
     const int nblocks = h->hctx.nblocks;
-    // The first range is timed by device stamps: its start by the state upload before it (s2m_optimize_launch), its end by the
-    // k_finalize that closes it.  The second range, issued only for a scan that did not converge in the first, keeps an event pair.
+    // The first range is timed by device stamps: its start by the state upload before it (optimize_launch), its end by the
+    // k_finalize that closes it.  The second range, issued only for a scan that did not converge in the first, keeps an event
+    // pair (second_range).
     if (h->tune.use_graph) {
         hipGraphExec_t exec = nullptr;
         int rc = get_graph(h, nblocks, part, &exec);
         if (rc == S2M_OK) {
-            if (part == 2) S2M_HIP(h, hipEventRecord(h->reg.ev_a2, h->stream));
             S2M_HIP(h, hipGraphLaunch(exec, h->stream));
-            if (part == 2) S2M_HIP(h, hipEventRecord(h->reg.ev_b2, h->stream));
             h->hctx.density_pending = 0;                  // cleared on the device by k_chunk_table_density: keep the host copy in step
             return S2M_OK;
         }
@@ -299,10 +311,8 @@ int launch_loop(s2m_context* h, int part = 0)
     LoopShape sh = shape_of(h);
     sh.stamp = part == 2 ? nullptr : h->reg.h_stamps + kStampLoop1;
     sh.wishes_done = h->batch.parent == nullptr;
-    if (part == 2) S2M_HIP(h, hipEventRecord(h->reg.ev_a2, h->stream));
     enqueue_loop(h, sh, nullptr, false, part == 2 ? h->tune.seg_iters : 0, part == 1 ? h->tune.seg_iters : -1);
     S2M_HIP(h, hipGetLastError());
-    if (part == 2) S2M_HIP(h, hipEventRecord(h->reg.ev_b2, h->stream));
     S2M_HIP(h, hipMemcpyAsync(&h->reg.h_state[1], h->reg.state.p, sizeof(DevState) + sizeof(s2m_iter_trace) * h->prm.max_iter, hipMemcpyDeviceToHost, h->stream));
     h->hctx.density_pending = 0;
     return S2M_OK;
@@ -321,6 +331,71 @@ void params_to_ctx(s2m_context* h, const s2m_params& prm)
 }
 
 }  // namespace
+
+// the soft conditions in front of the loop (:1297, :1300)
+bool s2m::host::optimize_gate(s2m_context* k, const float pose[6])
+{
+    memcpy(k->reg.pending_pose_in, pose, 24);
+    k->reg.pending_skipped = k->reg.n_m == 0 ? 1 : ((int)k->reg.n_q <= k->prm.min_feats ? 2 : 0);
+    return k->reg.pending_skipped == 0;
+}
+
+int s2m::host::optimize_launch(s2m_context* h, const float pose[6], Reg::Pending kind)
+{
+    if (!h->reg.have_scan) return fail(h, S2M_ERR_NO_SCAN, "s2m_set_scan has not been called");
+    S2M_HIP(h, hipSetDevice(h->device));
+    const bool runs = optimize_gate(h, pose);
+    h->reg.pending = kind;                                // (nothing refuses from here on; shape_of reads the kind)
+    if (!runs) return S2M_OK;
+    PendingGuard undo(h);
+    int rc;
+    if (!h->batch.parent && h->hctx.density_pending && h->tune.density_raw > 0) {
+        // the first optimisation of a single scan: the density wishes, the DevCtx block and the loop state in one plain launch
+        // (k_wave_density_state needs no wave table; the graph behind it starts with k_chunk_table_density)
+        launch_density_state(h, pose, h->reg.h_stamps + kStampLoop0);
+        S2M_HIP(h, hipGetLastError());
+        h->ctx_dirty = false;
+        h->reg.table_stale = false;                       // k_chunk_table_density emits the table
+    } else if ((rc = push_state(h, pose, h->reg.h_stamps + kStampLoop0))) return rc;      // (with the DevCtx block when that changed)
+    h->reg.seg_pending = two_ranges(h);
+    if ((rc = launch_loop(h, h->reg.seg_pending ? 1 : 0))) return rc;        // (state + trace come back with it)
+    undo.release();
+    return S2M_OK;
+}
+
+void s2m::host::collect_record(s2m_context* k, float pose[6], const s2m_imu_init* imu, s2m_result* out)
+{
+    s2m_result r;
+    memset(&r, 0, sizeof(r));
+    r.skipped = k->reg.pending_skipped;
+    k->reg.last_trace_n = 0;
+    float t[6];
+    memcpy(t, k->reg.pending_pose_in, 24);
+    if (!r.skipped) {
+        const DevState& s = k->reg.h_state[1];
+        memcpy(t, s.pose, 24);
+        r.iters_run = s.iters_run; r.converged = s.converged; r.is_degenerate = s.isDegenerate;
+        r.n_sel_last = s.n_sel_last;
+        k->reg.persist_degenerate = s.isDegenerate;
+        memcpy(k->reg.persist_matP, s.matP, sizeof(s.matP));
+        // trace: executed iterations; a loop that stalled at iteration k (fewer than min_corr correspondences,
+        // pose unchanged, :1178-1180) repeats that no-op record for the iterations the reference would still run
+        int n_exec = s.iters_run, stall_at = -1;
+        for (int i = 0; i < n_exec && i < kMaxIter; i++) {
+            if (stall_at >= 0) { k->reg.last_trace[i] = k->reg.last_trace[stall_at]; continue; }
+            k->reg.last_trace[i] = k->reg.h_trace[i];
+            if (s.stalled && !k->reg.h_trace[i].stepped) stall_at = i;
+        }
+        k->reg.last_trace_n = n_exec < kMaxIter ? n_exec : kMaxIter;
+        host_transform_update(k->prm, imu, t, r.affine);                           // :1317
+    } else {
+        host_pose_to_transform(t, r.affine, nullptr);
+        r.is_degenerate = k->reg.persist_degenerate;
+    }
+    memcpy(r.pose, t, 24);
+    memcpy(pose, t, 24);
+    if (out) *out = r;
+}
 
 // =============================================================================================
 // C ABI
@@ -391,8 +466,7 @@ int s2m_create(const s2m_params* p, s2m_handle* out)
         hipEventCreate(&h->reg.ev_a2) != hipSuccess || hipEventCreate(&h->reg.ev_b2) != hipSuccess ||
         hipEventCreateWithFlags(&h->reg.ev_up, hipEventDisableTiming) != hipSuccess) return bail(S2M_ERR_HIP);
     static_assert(sizeof(DevState) % 8 == 0, "the trace follows the state block");
-    static_assert((sizeof(DevState) + sizeof(s2m_iter_trace) * kMaxIter) % 64 == 0, "a batch's state blocks (kid_states) all start on a 64-byte line");
-    if (hipHostMalloc((void**)&h->reg.h_state, sizeof(DevState) * 2 + sizeof(s2m_iter_trace) * kMaxIter) != hipSuccess) return bail(S2M_ERR_HIP);
+    if (hipHostMalloc((void**)&h->reg.h_state, sizeof(DevState) + kSlotStateStride) != hipSuccess) return bail(S2M_ERR_HIP);
     h->reg.h_trace = reinterpret_cast<s2m_iter_trace*>(h->reg.h_state + 2);
     if (hipHostMalloc((void**)&h->reg.h_mm, 64) != hipSuccess) return bail(S2M_ERR_HIP);
     if (hipHostMalloc((void**)&h->reg.h_stamps, sizeof(unsigned long long) * kStampCount) != hipSuccess) return bail(S2M_ERR_HIP);
@@ -403,7 +477,7 @@ int s2m_create(const s2m_params* p, s2m_handle* out)
         h->reg.wall_clock_khz = khz;
     }
     if (hipHostMalloc((void**)&h->sc.h_stage, sizeof(double) * 1220) != hipSuccess) return bail(S2M_ERR_HIP);
-    if (ensure(h, h->reg.state, sizeof(DevState) + sizeof(s2m_iter_trace) * kMaxIter) ||      // loop state, then the trace
+    if (ensure(h, h->reg.state, kSlotStateStride) ||                                          // loop state, then the trace
         ensure(h, h->reg.dctx, sizeof(DevCtx)) || ensure(h, h->reg.mm, 64 + sizeof(uint32_t) * 8 * 1024) ||
         ensure(h, h->sc.bins, sizeof(uint32_t) * 1200) || ensure(h, h->sc.out, sizeof(double) * 1220) ||
         ensure(h, h->reg.q_counts, sizeof(int32_t) * kPolarCells))
@@ -477,7 +551,8 @@ int s2m_set_params(s2m_handle h, const s2m_params* p)
         p->gate_sq != h->prm.gate_sq)
         return fail(h, S2M_ERR_INVALID_ARG, "device_id, stream, k_neighbors and gate_sq are fixed at s2m_create (the search grid is built for the gate)");
     if (p->max_iter < 1 || p->max_iter > kMaxIter) return fail(h, S2M_ERR_INVALID_ARG, "max_iter out of range");
-    if (h->reg.opt_pending) return fail(h, S2M_ERR_INVALID_ARG, "an optimize launch is pending: collect it first");
+    if (h->reg.pending != Reg::kNone || slots_pending(h))   // (a slot in flight runs on a stream of its own, off the graphs dropped below)
+        return fail(h, S2M_ERR_INVALID_ARG, "an optimize launch is pending: collect it first");
     if (p->max_iter != h->prm.max_iter) {               // the captured loops hold max_iter launches
         S2M_HIP(h, hipSetDevice(h->device));
         S2M_HIP(h, hipStreamSynchronize(h->stream));
@@ -503,76 +578,24 @@ int s2m_set_scan_device(s2m_handle h, const void* d_pts, size_t n, size_t stride
 int s2m_optimize_launch(s2m_handle h, const float pose[6])
 {
     if (!h || !pose) return S2M_ERR_INVALID_ARG;
-    if (!h->reg.have_scan) return fail(h, S2M_ERR_NO_SCAN, "s2m_set_scan has not been called");
-    S2M_HIP(h, hipSetDevice(h->device));
-    memcpy(h->reg.pending_pose_in, pose, 24);
-    h->reg.opt_pending = true;
-    h->reg.pending_skipped = 0;
-    if (h->reg.n_m == 0) { h->reg.pending_skipped = 1; return S2M_OK; }                    // :1297
-    if ((int)h->reg.n_q <= h->prm.min_feats) { h->reg.pending_skipped = 2; return S2M_OK; } // :1300
-    int rc;
-    if (!h->batch.parent && h->hctx.density_pending && h->tune.density_raw > 0) {
-        // the first optimisation of a single scan: the density wishes, the DevCtx block and the loop state in one plain launch
-        // (k_wave_density_state needs no wave table; the graph behind it starts with k_chunk_table_density)
-        launch_density_state(h, pose, h->reg.h_stamps + kStampLoop0);
-        S2M_HIP(h, hipGetLastError());
-        h->ctx_dirty = false;
-        h->reg.table_stale = false;                       // k_chunk_table_density emits the table
-    } else if ((rc = push_state(h, pose, h->reg.h_stamps + kStampLoop0))) return rc;      // (with the DevCtx block when that changed)
-    h->reg.seg_pending = h->prm.early_exit && h->tune.seg_iters > 1 && h->tune.seg_iters < h->prm.max_iter;
-    if ((rc = launch_loop(h, h->reg.seg_pending ? 1 : 0))) return rc;        // (state + trace come back with it)
-    return S2M_OK;
+    return optimize_launch(h, pose, Reg::kSingle);
 }
 
 int s2m_optimize_collect(s2m_handle h, float pose[6], const s2m_imu_init* imu, s2m_result* out)
 {
     if (!h || !pose) return S2M_ERR_INVALID_ARG;
-    if (!h->reg.opt_pending) return fail(h, S2M_ERR_INVALID_ARG, "no optimize launch pending");
-    h->reg.opt_pending = false;
-    s2m_result r;
-    memset(&r, 0, sizeof(r));
-    r.skipped = h->reg.pending_skipped;
-    h->reg.last_trace_n = 0;
-    float t[6];
-    memcpy(t, h->reg.pending_pose_in, 24);
-    if (!r.skipped) {
+    if (h->reg.pending == Reg::kNone) return fail(h, S2M_ERR_INVALID_ARG, "no optimize launch pending");
+    PendingGuard done(h);
+    if (!h->reg.pending_skipped) {
         S2M_HIP(h, hipSetDevice(h->device));
         S2M_HIP(h, hipStreamSynchronize(h->stream));
-        if (h->batch.parent && !h->batch.slot_mode) h->reg.t_optimize_ms = h->batch.parent->reg.t_optimize_ms;      // a slot of a batch: the batch was timed as a whole
-        else h->reg.t_optimize_ms = stamps_ms(h, kStampLoop0, kStampLoop1);
-        if (h->reg.seg_pending && !h->reg.h_state[1].done) {
-            // the first range did not converge: the rest of the loop
-            int rc2 = launch_loop(h, 2);
-            if (rc2) return rc2;
-            S2M_HIP(h, hipStreamSynchronize(h->stream));
-            float t2 = 0.0f;
-            S2M_HIP(h, hipEventElapsedTime(&t2, h->reg.ev_a2, h->reg.ev_b2));
-            h->reg.t_optimize_ms += t2;
+        h->reg.t_optimize_ms = stamps_ms(h, kStampLoop0, kStampLoop1);
+        if (h->reg.seg_pending && !h->reg.h_state[1].done) {       // the first range did not converge: the rest of the loop
+            const int rc = second_range(h, [&] { return launch_loop(h, 2); });
+            if (rc) return rc;
         }
-        h->reg.seg_pending = false;
-        const DevState& s = h->reg.h_state[1];
-        memcpy(t, s.pose, 24);
-        r.iters_run = s.iters_run; r.converged = s.converged; r.is_degenerate = s.isDegenerate;
-        r.n_sel_last = s.n_sel_last;
-        h->reg.persist_degenerate = s.isDegenerate;
-        memcpy(h->reg.persist_matP, s.matP, sizeof(s.matP));
-        // trace: executed iterations; a loop that stalled at iteration k (fewer than min_corr correspondences,
-        // pose unchanged, :1178-1180) repeats that no-op record for the iterations the reference would still run
-        int n_exec = s.iters_run, stall_at = -1;
-        for (int i = 0; i < n_exec && i < kMaxIter; i++) {
-            if (stall_at >= 0) { h->reg.last_trace[i] = h->reg.last_trace[stall_at]; continue; }
-            h->reg.last_trace[i] = h->reg.h_trace[i];
-            if (s.stalled && !h->reg.h_trace[i].stepped) stall_at = i;
-        }
-        h->reg.last_trace_n = n_exec < kMaxIter ? n_exec : kMaxIter;
-        host_transform_update(h->prm, imu, t, r.affine);                           // :1317
-    } else {
-        host_pose_to_transform(t, r.affine, nullptr);
-        r.is_degenerate = h->reg.persist_degenerate;
     }
-    memcpy(r.pose, t, 24);
-    memcpy(pose, t, 24);
-    if (out) *out = r;
+    collect_record(h, pose, imu, out);
     return S2M_OK;
 }
 
@@ -589,370 +612,6 @@ int s2m_optimize(s2m_handle h, const void* scan, size_t n, size_t stride_bytes, 
     int rc = s2m_set_scan(h, scan, n, stride_bytes);
     if (rc) return rc;
     return s2m_optimize_resident(h, pose, imu, out);
-}
-
-// ---- a batch of scans against one resident map -------------------------------------------------------
-namespace {
-
-// field by field (the struct has padding): everything a slot has to take over from its parent
-bool same_params_but_stream(const s2m_params& a, const s2m_params& b)
-{
-    return a.struct_size == b.struct_size && a.device_id == b.device_id && a.k_neighbors == b.k_neighbors && a.gate_sq == b.gate_sq &&
-           a.plane_tol == b.plane_tol && a.weight_scale == b.weight_scale && a.weight_min == b.weight_min && a.min_corr == b.min_corr &&
-           a.min_feats == b.min_feats && a.max_iter == b.max_iter && a.eig_thresh == b.eig_thresh && a.conv_deg == b.conv_deg &&
-           a.conv_cm == b.conv_cm && a.z_tol == b.z_tol && a.rot_tol == b.rot_tol && a.imu_type == b.imu_type &&
-           a.imu_rpy_weight == b.imu_rpy_weight && a.early_exit == b.early_exit;
-}
-
-// child b borrows the parent's map index (no copy) and its per-scan certificates are void when the index changed
-int adopt_map(s2m_context* h, s2m_context* k)
-{
-    if (k->batch.adopted_epoch == h->batch.map_epoch) return S2M_OK;
-    k->reg.n_m = h->reg.n_m;
-    k->hctx.n_m = h->hctx.n_m;
-    k->hctx.g = h->hctx.g;
-    k->hctx.map_sorted = h->hctx.map_sorted;
-    k->hctx.cell_start = h->hctx.cell_start;
-    k->ctx_dirty = true;
-    k->batch.adopted_epoch = h->batch.map_epoch;
-    if (k->reg.have_scan && k->reg.n_q > 0 && k->reg.cert.p) {
-        S2M_HIP(k, hipMemsetAsync(k->reg.cert.p, 0, sizeof(float4) * k->reg.n_q, k->stream));
-        S2M_HIP(k, hipMemsetAsync(k->reg.aux.p, 0, sizeof(int4) * k->reg.n_q, k->stream));
-    }
-    return S2M_OK;
-}
-
-int ensure_kids(s2m_context* h, int n)
-{
-    while ((int)h->batch.kids.size() < n) {
-        s2m_params p = h->prm;
-        p.stream = h->stream;                              // everything outside the captured graph is ordered on the parent's stream
-        s2m_context* k = nullptr;
-        const int rc = s2m_create(&p, &k);
-        if (rc) return fail(h, rc, "batch: could not create a scan slot");
-        k->batch.parent = h;
-        k->hctx.ablate = h->hctx.ablate;
-        memcpy(k->hctx.tune, h->hctx.tune, sizeof(h->hctx.tune));
-        {   // the slot's loop state and trace live in the parent's block
-            constexpr size_t kStride = sizeof(DevState) + sizeof(s2m_iter_trace) * kMaxIter;
-            if (!h->batch.kid_states.p) {
-                if (ensure(h, h->batch.kid_states, kStride * kMaxSlots) != S2M_OK ||
-                    hipHostMalloc((void**)&h->batch.h_kid_states, sizeof(DevState) + kStride * kMaxSlots) != hipSuccess) {
-                    (void)s2m_destroy(k);
-                    return fail(h, S2M_ERR_HIP, "batch: state block allocation failed");
-                }
-            }
-            const size_t slot = h->batch.kids.size();
-            (void)k->reg.state.reset();                        // from here on an alias: forgotten, not freed, in s2m_destroy
-            (void)hipHostFree(k->reg.h_state);
-            k->reg.state.p = h->batch.kid_states.as<unsigned char>() + kStride * slot; k->reg.state.cap = kStride;
-            k->reg.h_state = reinterpret_cast<DevState*>(h->batch.h_kid_states + kStride * slot);      // [1] = the download area of this slot
-            k->reg.h_trace = reinterpret_cast<s2m_iter_trace*>(k->reg.h_state + 2);
-            k->batch.state_borrowed = true;
-            k->hctx.state = k->reg.state.as<DevState>();
-            k->hctx.trace = reinterpret_cast<s2m_iter_trace*>(k->reg.state.as<DevState>() + 1);
-            k->ctx_dirty = true;
-        }
-        h->batch.kids.push_back(k);
-        hipStream_t st = nullptr;
-        hipEvent_t ev = nullptr, ev2 = nullptr;
-        // The streams of neighbouring slots get different priorities.  HIP deals a process's streams of one priority onto a small
-        // pool of hardware queues in creation order (GPU_MAX_HW_QUEUES, default 4), and two streams that land on one queue run
-        // strictly one after the other: with other streams alive in the process (a ROS node has them) the two slots of a stream
-        // of scans could end up sharing a queue and lose the overlap of one's preparation with the other's loop.  Streams of
-        // different priority never share a hardware queue, whatever else the process has created.
-        int prio_least = 0, prio_greatest = 0;
-        (void)hipDeviceGetStreamPriorityRange(&prio_least, &prio_greatest);
-        const int prio = (h->batch.kids.size() & 1) ? prio_greatest : prio_least;
-        if (hipStreamCreateWithPriority(&st, hipStreamNonBlocking, prio) != hipSuccess || hipEventCreateWithFlags(&ev, hipEventDisableTiming) != hipSuccess ||
-            hipEventCreateWithFlags(&ev2, hipEventDisableTiming) != hipSuccess)
-            return fail(h, S2M_ERR_HIP, "batch: stream / event creation failed");
-        h->batch.branch_streams.push_back(st);
-        h->batch.branch_events.push_back(ev);
-        h->batch.prep_events.push_back(ev2);
-        h->batch.prep_pending.push_back(0);
-    }
-    if (!h->batch.ev_fork && hipEventCreateWithFlags(&h->batch.ev_fork, hipEventDisableTiming) != hipSuccess) return fail(h, S2M_ERR_HIP, "batch: event creation failed");
-    if (!h->batch.ev_prep && hipEventCreateWithFlags(&h->batch.ev_prep, hipEventDisableTiming) != hipSuccess) return fail(h, S2M_ERR_HIP, "batch: event creation failed");
-    return S2M_OK;
-}
-
-// One graph for the whole batch.  Lockstep (default): the slots' loops advance together, every launch of the loop has one
-// grid row per slot (slots of different workgroup shape form groups, one loop per group on a branch of its own).  Otherwise
-// (S2M_LOCKSTEP=0, A/B measurements): a fork, one branch per scan with that scan's loop, a join.
-// part 0: the whole loop; 1: launches 0 .. seg-1; 2: launches seg .. max_iter-1 (as get_graph)
-int get_batch_graph(s2m_context* h, const std::vector<int>& live, int part, hipGraphExec_t* out)
-{
-    std::vector<int> key;
-    key.push_back(part); key.push_back(part ? h->tune.seg_iters : 0);
-    for (int b : live) { key.push_back(b); key.push_back(h->batch.kids[(size_t)b]->hctx.table_cap); key.push_back(h->batch.kids[(size_t)b]->hctx.wpb); }
-    auto it = h->batch.graphs.find(key);
-    if (it != h->batch.graphs.end()) { *out = it->second; return S2M_OK; }
-    hipGraph_t graph = nullptr;
-    hipGraphExec_t exec = nullptr;
-    // the loops to run: (shape, stream to run it on)
-    std::vector<LoopShape> loops;
-    if (h->tune.lockstep) {
-        for (int wpb : { kBlock / 64, kBigWaves }) {
-            LoopShape sh;
-            memset(&sh.tbl, 0, sizeof(sh.tbl));
-            sh.nslots = 0; sh.wpb = wpb; sh.batch = true;
-            for (int b : live) {
-                s2m_context* k = h->batch.kids[(size_t)b];
-                if (k->hctx.wpb != wpb) continue;
-                sh.tbl.ctx[sh.nslots] = k->reg.dctx.as<DevCtx>();
-                sh.tbl.st[sh.nslots] = k->reg.state.as<DevState>();
-                sh.nslots++;
-                sh.nblocks = std::max(sh.nblocks, k->hctx.nblocks);
-                sh.table_cap = std::max(sh.table_cap, k->hctx.table_cap);
-            }
-            sh.split = h->tune.split_mode == 1;         // (default: decided in enqueue_loop - split where the loop is not fused)
-            sh.split_auto = h->tune.split_mode == 2 || h->tune.split_mode < 0;   // (default: certify (lean) + search from launch split_from on, where k_finalize closes the iterations)
-            if (sh.nslots) loops.push_back(sh);
-        }
-    } else
-        for (int b : live) loops.push_back(shape_of(h->batch.kids[(size_t)b]));
-    S2M_HIP(h, hipStreamBeginCapture(h->stream, hipStreamCaptureModeThreadLocal));
-    bool ok = hipEventRecord(h->batch.ev_fork, h->stream) == hipSuccess;
-    hipStream_t keep = h->stream;
-    for (size_t j = 0; j < loops.size(); j++) {
-        hipStream_t br = h->batch.branch_streams[j];
-        ok = ok && hipStreamWaitEvent(br, h->batch.ev_fork, 0) == hipSuccess;
-        h->stream = br;                                       // (enqueue_loop launches on the handle's stream; settings are the parent's)
-        enqueue_loop(h, loops[j], nullptr, false, part == 2 ? h->tune.seg_iters : 0, part == 1 ? h->tune.seg_iters : -1);
-        h->stream = keep;
-        ok = ok && hipEventRecord(h->batch.branch_events[j], br) == hipSuccess;
-        ok = ok && hipStreamWaitEvent(h->stream, h->batch.branch_events[j], 0) == hipSuccess;
-    }
-    hipError_t e = hipStreamEndCapture(h->stream, &graph);
-    if (!ok || e != hipSuccess || !graph) return fail(h, S2M_ERR_HIP, "batch: stream capture failed", e);
-    e = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
-    (void)hipGraphDestroy(graph);
-    if (e != hipSuccess) return fail(h, S2M_ERR_HIP, "batch: hipGraphInstantiate", e);
-    h->batch.graphs[key] = exec;
-    *out = exec;
-    return S2M_OK;
-}
-
-}  // namespace
-
-int s2m_batch_set_scan(s2m_handle h, int slot, const void* pts, size_t n, size_t stride_bytes, int on_device)
-{
-    if (!h || slot < 0 || slot >= 64) return S2M_ERR_INVALID_ARG;
-    S2M_HIP(h, hipSetDevice(h->device));
-    int rc = ensure_kids(h, slot + 1);
-    if (rc) return rc;
-    s2m_context* k = h->batch.kids[(size_t)slot];
-    if ((rc = adopt_map(h, k))) return fail(h, rc, k->err.c_str());
-    // The ordering of one slot's scan does not depend on the others': it runs on the slot's own stream, behind everything
-    // issued on the handle's stream so far (the previous batch read the slot's buffers), and the batch launch waits for it.
-    hipStream_t br = h->batch.branch_streams[(size_t)slot];
-    S2M_HIP(h, hipEventRecord(h->batch.ev_prep, h->stream));
-    S2M_HIP(h, hipStreamWaitEvent(br, h->batch.ev_prep, 0));
-    k->stream = br;
-    rc = set_scan_impl(k, pts, n, stride_bytes, on_device != 0);
-    k->stream = h->stream;
-    if (rc) { (void)hipStreamSynchronize(br); return fail(h, rc, k->err.c_str()); }
-    S2M_HIP(h, hipEventRecord(h->batch.prep_events[(size_t)slot], br));
-    h->batch.prep_pending[(size_t)slot] = 1;
-    return S2M_OK;
-}
-
-int s2m_batch_set_scans(s2m_handle h, int n_scans, const void* const* scans, const size_t* sizes, size_t stride_bytes, int on_device)
-{
-    if (!h || n_scans < 1 || n_scans > kMaxSlots || !scans || !sizes) return S2M_ERR_INVALID_ARG;
-    S2M_HIP(h, hipSetDevice(h->device));
-    int rc = ensure_kids(h, n_scans);
-    if (rc) return rc;
-    // Work still queued on a slot's own stream (a preparation from s2m_batch_set_scan, a loop from s2m_slot_optimize_launch)
-    // uses the buffers this call rewrites: the handle's stream waits for it first.
-    for (int b = 0; b < n_scans; b++) {
-        S2M_HIP(h, hipEventRecord(h->batch.prep_events[(size_t)b], h->batch.branch_streams[(size_t)b]));
-        S2M_HIP(h, hipStreamWaitEvent(h->stream, h->batch.prep_events[(size_t)b], 0));
-        h->batch.prep_pending[(size_t)b] = 0;
-    }
-    for (int b0 = 0; b0 < n_scans; b0 += kPrepSlots) {
-        PrepTable t;
-        const int nb = std::min(kPrepSlots, n_scans - b0);
-        for (int j = 0; j < nb; j++) {
-            s2m_context* k = h->batch.kids[(size_t)(b0 + j)];
-            if ((rc = adopt_map(h, k)) == S2M_OK) rc = scan_slot_prepare(k, scans[b0 + j], sizes[b0 + j], stride_bytes, on_device != 0, &t.s[j]);
-            if (rc) {
-                // no slot of this call holds a scan after a failure: the groups before this one were ordered, but a batch
-                // of which some scans are missing is of no use to the caller
-                for (int q = 0; q <= b0 + j; q++) h->batch.kids[(size_t)q]->reg.have_scan = false;
-                (void)hipStreamSynchronize(h->stream);
-                return fail(h, rc, k->err.c_str());
-            }
-            k->reg.t_set_scan_ms = 0; k->reg.scan_timing_pending = false;
-        }
-        launch_scan_prep(h->stream, t, nb);
-        S2M_HIP(h, hipGetLastError());
-    }
-    if (!on_device) S2M_HIP(h, hipStreamSynchronize(h->stream));       // the callers' buffers are free again
-    return S2M_OK;
-}
-
-// ---- a stream of scans: slot k's preparation and loop run on slot k's own stream, so that the ordering of scan i+1 (slot B)
-// overlaps the LM loop of scan i (slot A) - the reference does the two strictly one after the other (:257-265) ----------
-int s2m_slot_set_scan(s2m_handle h, int slot, const void* pts, size_t n, size_t stride_bytes, int on_device)
-{ return s2m_batch_set_scan(h, slot, pts, n, stride_bytes, on_device); }
-
-int s2m_slot_optimize_launch(s2m_handle h, int slot, const float pose[6])
-{
-    if (!h || slot < 0 || slot >= (int)h->batch.kids.size() || !pose) return S2M_ERR_INVALID_ARG;
-    s2m_context* k = h->batch.kids[(size_t)slot];
-    if (!k->reg.have_scan) return fail(h, S2M_ERR_NO_SCAN, "s2m_slot_set_scan has not been called for this slot");
-    S2M_HIP(h, hipSetDevice(h->device));
-    int rc;
-    if (!same_params_but_stream(k->prm, h->prm)) {
-        s2m_params p = h->prm;
-        p.stream = k->prm.stream;
-        if ((rc = s2m_set_params(k, &p))) return fail(h, rc, k->err.c_str());
-    }
-    h->batch.prep_pending[(size_t)slot] = 0;                       // (the preparation is ahead of the loop on the same stream)
-    k->stream = h->batch.branch_streams[(size_t)slot];
-    k->batch.slot_mode = true;
-    rc = adopt_map(h, k);
-    if (!rc) rc = s2m_optimize_launch(k, pose);
-    k->stream = h->stream;
-    return rc ? fail(h, rc, k->err.c_str()) : S2M_OK;
-}
-
-int s2m_slot_optimize_collect(s2m_handle h, int slot, float pose[6], const s2m_imu_init* imu, s2m_result* out)
-{
-    if (!h || slot < 0 || slot >= (int)h->batch.kids.size() || !pose) return S2M_ERR_INVALID_ARG;
-    s2m_context* k = h->batch.kids[(size_t)slot];
-    k->stream = h->batch.branch_streams[(size_t)slot];
-    const int rc = s2m_optimize_collect(k, pose, imu, out);
-    k->stream = h->stream;
-    k->batch.slot_mode = false;
-    return rc ? fail(h, rc, k->err.c_str()) : S2M_OK;
-}
-
-int s2m_optimize_batch_launch(s2m_handle h, int n_scans, const float* poses)
-{
-    if (!h || n_scans < 1 || n_scans > 64 || !poses) return S2M_ERR_INVALID_ARG;
-    if ((int)h->batch.kids.size() < n_scans) return fail(h, S2M_ERR_NO_SCAN, "s2m_batch_set_scan has not been called for every slot");
-    S2M_HIP(h, hipSetDevice(h->device));
-    std::vector<int> live;
-    int rc;
-    for (size_t b = 0; b < h->batch.prep_pending.size(); b++)
-        if (h->batch.prep_pending[b]) { S2M_HIP(h, hipStreamWaitEvent(h->stream, h->batch.prep_events[b], 0)); h->batch.prep_pending[b] = 0; }
-    for (int b = 0; b < n_scans; b++) {
-        s2m_context* k = h->batch.kids[(size_t)b];
-        if (!k->reg.have_scan) return fail(h, S2M_ERR_NO_SCAN, "s2m_batch_set_scan has not been called for every slot");
-        if (!same_params_but_stream(k->prm, h->prm)) {     // any parameter changed on the parent since the slot was made
-            s2m_params p = h->prm;
-            p.stream = k->prm.stream;
-            if ((rc = s2m_set_params(k, &p))) return fail(h, rc, k->err.c_str());
-        }
-        if ((rc = adopt_map(h, k))) return fail(h, rc, k->err.c_str());
-        memcpy(k->reg.pending_pose_in, poses + 6 * (size_t)b, 24);
-        k->reg.opt_pending = true;
-        k->reg.pending_skipped = 0;
-        if (k->reg.n_m == 0) { k->reg.pending_skipped = 1; continue; }                            // :1297
-        if ((int)k->reg.n_q <= k->prm.min_feats) { k->reg.pending_skipped = 2; continue; }         // :1300
-        live.push_back(b);
-    }
-    {   // DevCtx blocks that changed and the loop state every live slot starts from: one launch per kCtxSlots / kInitSlots slots
-        CtxTable ct; int nc = 0;
-        auto flush_ctx = [&]() { if (nc) { for (int j = nc; j < kCtxSlots; j++) ct.dst[j] = nullptr; hipLaunchKernelGGL(k_set_ctxs, dim3(nc), dim3(64), 0, h->stream, ct); nc = 0; } };
-        for (int b = 0; b < n_scans; b++) {
-            s2m_context* k = h->batch.kids[(size_t)b];
-            if (!k->ctx_dirty) continue;
-            ct.dst[nc] = k->reg.dctx.as<DevCtx>(); ct.v[nc] = k->hctx; nc++;
-            k->ctx_dirty = false;
-            if (nc == kCtxSlots) flush_ctx();
-        }
-        flush_ctx();
-        StateInitTable it; int ni = 0;
-        auto flush_init = [&]() { if (ni) { for (int j = ni; j < kInitSlots; j++) it.s[j].dst = nullptr; hipLaunchKernelGGL(k_init_states, dim3(ni), dim3(256), 0, h->stream, it); ni = 0; } };
-        for (int b : live) {
-            s2m_context* k = h->batch.kids[(size_t)b];
-            DevState s0;
-            fill_state(k, &s0, poses + 6 * (size_t)b);
-            StateInit& si = it.s[ni++];
-            si.dst = k->reg.state.as<DevState>(); si.n_waves = k->reg.n_waves.as<int32_t>();
-            memcpy(si.pose, s0.pose, sizeof(si.pose)); memcpy(si.T, s0.T, sizeof(si.T)); memcpy(si.sc, s0.sc, sizeof(si.sc));
-            memcpy(si.matP, s0.matP, sizeof(si.matP)); si.isDegenerate = s0.isDegenerate;
-            if (ni == kInitSlots) flush_init();
-        }
-        flush_init();
-        S2M_HIP(h, hipGetLastError());
-    }
-    // With early exit on the loops are issued as launches 0 .. seg-1 and, only if some slot has not converged by then, the rest
-    // (s2m_optimize_batch_collect looks at the slots' `done` flags, which come back with the states anyway): the launches behind
-    // the convergence of every slot - idle, but a kernel boundary and a k_finalize each - were a fifth of an early-exit batch.
-    h->batch.seg_pending = h->prm.early_exit && h->tune.seg_iters > 1 && h->tune.seg_iters < h->prm.max_iter;
-    h->batch.live = live;
-    S2M_HIP(h, hipEventRecord(h->reg.ev_a, h->stream));
-    if (!live.empty()) {
-        hipGraphExec_t exec = nullptr;
-        if ((rc = get_batch_graph(h, live, h->batch.seg_pending ? 1 : 0, &exec))) return rc;
-        S2M_HIP(h, hipGraphLaunch(exec, h->stream));
-    }
-    S2M_HIP(h, hipEventRecord(h->reg.ev_b, h->stream));
-    for (int b : live) h->batch.kids[(size_t)b]->hctx.density_pending = 0;
-    if (!live.empty()) {
-        // state + trace of every slot up to the last live one, in one copy (the slots' blocks are contiguous)
-        constexpr size_t kStride = sizeof(DevState) + sizeof(s2m_iter_trace) * kMaxIter;
-        const size_t upto = (size_t)live.back() + 1;
-        S2M_HIP(h, hipMemcpyAsync(h->batch.h_kid_states + sizeof(DevState), h->batch.kid_states.p, kStride * upto, hipMemcpyDeviceToHost, h->stream));
-    }
-    return S2M_OK;
-}
-
-int s2m_optimize_batch_collect(s2m_handle h, int n_scans, float* poses, const s2m_imu_init* imu, s2m_result* out)
-{
-    if (!h || n_scans < 1 || (int)h->batch.kids.size() < n_scans || !poses) return S2M_ERR_INVALID_ARG;
-    S2M_HIP(h, hipSetDevice(h->device));
-    S2M_HIP(h, hipStreamSynchronize(h->stream));
-    S2M_HIP(h, hipEventElapsedTime(&h->reg.t_optimize_ms, h->reg.ev_a, h->reg.ev_b));
-    if (h->batch.seg_pending && !h->batch.live.empty()) {
-        h->batch.seg_pending = false;
-        bool all_done = true;
-        for (int b : h->batch.live) all_done = all_done && h->batch.kids[(size_t)b]->reg.h_state[1].done != 0;
-        if (!all_done) {
-            // some slot needs more than the first range: the rest of the loop for all of them (a converged slot's launches return at once)
-            hipGraphExec_t exec = nullptr;
-            int rc2 = get_batch_graph(h, h->batch.live, 2, &exec);
-            if (rc2) return rc2;
-            S2M_HIP(h, hipEventRecord(h->reg.ev_a2, h->stream));
-            S2M_HIP(h, hipGraphLaunch(exec, h->stream));
-            S2M_HIP(h, hipEventRecord(h->reg.ev_b2, h->stream));
-            constexpr size_t kStride = sizeof(DevState) + sizeof(s2m_iter_trace) * kMaxIter;
-            const size_t upto = (size_t)h->batch.live.back() + 1;
-            S2M_HIP(h, hipMemcpyAsync(h->batch.h_kid_states + sizeof(DevState), h->batch.kid_states.p, kStride * upto, hipMemcpyDeviceToHost, h->stream));
-            S2M_HIP(h, hipStreamSynchronize(h->stream));
-            float t2 = 0.0f;
-            S2M_HIP(h, hipEventElapsedTime(&t2, h->reg.ev_a2, h->reg.ev_b2));
-            h->reg.t_optimize_ms += t2;
-        }
-    }
-    for (int b = 0; b < n_scans; b++) {
-        s2m_context* k = h->batch.kids[(size_t)b];
-        const int rc = s2m_optimize_collect(k, poses + 6 * (size_t)b, imu ? imu + b : nullptr, out ? out + b : nullptr);
-        if (rc) return fail(h, rc, k->err.c_str());
-    }
-    return S2M_OK;
-}
-
-int s2m_optimize_batch(s2m_handle h, int n_scans, const void* const* scans, const size_t* sizes, size_t stride_bytes,
-                       float* poses, const s2m_imu_init* imu, s2m_result* out)
-{
-    if (!h || n_scans < 1 || n_scans > 64 || !scans || !sizes || !poses) return S2M_ERR_INVALID_ARG;
-    int rc = s2m_batch_set_scans(h, n_scans, scans, sizes, stride_bytes, 0);
-    if (rc) return rc;
-    rc = s2m_optimize_batch_launch(h, n_scans, poses);
-    if (rc) return rc;
-    return s2m_optimize_batch_collect(h, n_scans, poses, imu, out);
-}
-
-int s2m_batch_get_trace(s2m_handle h, int slot, s2m_iter_trace* out, int cap)
-{
-    if (!h || slot < 0 || slot >= (int)h->batch.kids.size()) return S2M_ERR_INVALID_ARG;
-    return s2m_get_trace(h->batch.kids[(size_t)slot], out, cap);
 }
 
 int s2m_get_trace(s2m_handle h, s2m_iter_trace* out, int cap)

@@ -165,7 +165,7 @@ int s2m_debug_lm_close(s2m_handle h, int form, int iter, const double* rows, int
     if (!h) return S2M_ERR_INVALID_ARG;
     if (s2m_debug_lm_close_check_args(form, iter, h->prm.max_iter, rows, n_rows, pose0, matP_in, out))
         return fail(h, S2M_ERR_INVALID_ARG, "null argument, form outside {0, 1}, iter outside 0 .. max_iter-1, or form 1 at iter 0");
-    if (h->reg.opt_pending) return fail(h, S2M_ERR_INVALID_ARG, "an optimize launch is pending: collect it first");
+    if (h->reg.pending != Reg::kNone) return fail(h, S2M_ERR_INVALID_ARG, "an optimize launch is pending: collect it first");
     if (!h->reg.have_scan || h->reg.n_m == 0 || h->reg.n_q == 0) return fail(h, S2M_ERR_NO_SCAN, "needs a resident scan and map");
     S2M_HIP(h, hipSetDevice(h->device));
     int rc;
@@ -244,7 +244,7 @@ int s2m_debug_scan_prep(s2m_handle h, int32_t chain, const float pose[6], int32_
 {
     if (!h || chain < S2M_DEBUG_PREP_READ || chain > S2M_DEBUG_PREP_LEGACY) return S2M_ERR_INVALID_ARG;
     if (h->batch.parent) return fail(h, S2M_ERR_INVALID_ARG, "a scan slot of a batch keeps the six-kernel chain");
-    if (h->reg.opt_pending) return fail(h, S2M_ERR_INVALID_ARG, "an optimize launch is pending: collect it first");
+    if (h->reg.pending != Reg::kNone) return fail(h, S2M_ERR_INVALID_ARG, "an optimize launch is pending: collect it first");
     if (!h->reg.have_scan) return fail(h, S2M_ERR_NO_SCAN, "s2m_set_scan has not been called");
     const size_t n = h->reg.n_q;
     if (n == 0) { if (n_waves) *n_waves = 0; return S2M_OK; }

@@ -39,21 +39,12 @@ void s2m::host::loop_drop_pending(s2m_context* h, bool destroy)
 
 namespace {
 
-// The loop stream: the lowest priority the device offers, so that a closure yields to the registration kernels. A device
-// that reports no range (or an error) gives a stream of the default priority; that is said once on stderr.
+// The loop stream: the lowest priority the device offers (create_stream), so that a closure yields to the registration kernels.
 int loop_stream(s2m_context* h)
 {
     if (h->loop.stream) return S2M_OK;
-    int least = 0, greatest = 0;
-    const hipError_t e = hipDeviceGetStreamPriorityRange(&least, &greatest);
-    if (e != hipSuccess || least == greatest) {
-        (void)hipGetLastError();
-        fprintf(stderr, "liorf_s2m: no stream priority range on device %d (%s): the loop-closure stream runs at the default priority\n",
-                h->device, e != hipSuccess ? hipGetErrorString(e) : "least == greatest");
-        S2M_HIP(h, hipStreamCreateWithFlags(&h->loop.stream, hipStreamNonBlocking));
-    } else {
-        S2M_HIP(h, hipStreamCreateWithPriority(&h->loop.stream, hipStreamNonBlocking, least));
-    }
+    const int rc = create_stream(h, &h->loop.stream, false, "the loop-closure stream");
+    if (rc) return rc;
     S2M_HIP(h, hipEventCreateWithFlags(&h->loop.ev_submaps, hipEventDisableTiming));
     return S2M_OK;
 }

@@ -370,24 +370,13 @@ int pg_busy(s2m_context* h)
     return h->pg.pending ? fail(h, S2M_ERR_BUSY, "a launched pose-graph optimise is pending: s2m_pg_optimize_poll / s2m_pg_optimize_collect it first") : S2M_OK;
 }
 
-// The pose-graph stream: the lowest priority the device offers, as the loop stream, so that the solve yields to the
-// registration kernels. A device that reports no range (or an error) gives a stream of the default priority; that is said
-// once on stderr.
+// The pose-graph stream: the lowest priority the device offers (create_stream), as the loop stream, so that the solve yields to
+// the registration kernels.
 int pg_stream(s2m_context* h)
 {
     auto& g = h->pg;
-    if (!g.stream) {
-        int least = 0, greatest = 0;
-        const hipError_t e = hipDeviceGetStreamPriorityRange(&least, &greatest);
-        if (e != hipSuccess || least == greatest) {
-            (void)hipGetLastError();
-            fprintf(stderr, "liorf_s2m: no stream priority range on device %d (%s): the pose-graph stream runs at the default priority\n",
-                    h->device, e != hipSuccess ? hipGetErrorString(e) : "least == greatest");
-            S2M_HIP(h, hipStreamCreateWithFlags(&g.stream, hipStreamNonBlocking));
-        } else {
-            S2M_HIP(h, hipStreamCreateWithPriority(&g.stream, hipStreamNonBlocking, least));
-        }
-    }
+    int rc;
+    if (!g.stream && (rc = create_stream(h, &g.stream, false, "the pose-graph stream"))) return rc;
     if (!g.ev_ready) S2M_HIP(h, hipEventCreateWithFlags(&g.ev_ready, hipEventDisableTiming));
     if (!g.ev_range) S2M_HIP(h, hipEventCreateWithFlags(&g.ev_range, hipEventDisableTiming));
     if (!g.h_rec) S2M_HIP(h, hipHostMalloc((void**)&g.h_rec, sizeof(PgRecord)));

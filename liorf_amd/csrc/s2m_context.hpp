@@ -6,6 +6,7 @@
 
 #include <cstddef>
 #include <cstdint>
+#include <cstdio>
 #include <map>
 #include <string>
 #include <vector>
@@ -90,8 +91,20 @@ struct __attribute__((visibility("hidden"))) s2m_context {
         hipEvent_t ev_a2 = nullptr, ev_b2 = nullptr;     // around the second range of launches
         float t_optimize_ms = 0, t_set_map_ms = 0, t_set_scan_ms = 0;
         int base_parts = 1;
+        // The one pending optimise of this context: what a launch queued and no collect has brought back yet. kSingle: the
+        // handle's own loop (s2m_optimize_launch). A slot is pending as kSlot - a loop of its own on its own stream
+        // (s2m_slot_optimize_launch) - or as kBatch, a row of the parent's batch; the parent records that batch in Batch::pend_n,
+        // live and seg_pending. The rules, for every launch and collect:
+        //  - A launch marks a context pending only after everything that can refuse has passed (arguments, have_scan, the
+        //    parameter sync and adopt_map, for every slot of the call): a refused call marks nothing. A call that fails after
+        //    marking (capture, graph launch, a HIP error) un-marks what it marked before it returns.
+        //  - A collect clears what it collects on every exit (PendingGuard): pending and seg_pending, and for a batch the
+        //    parent's record and every slot of that batch.
+        //  - s2m_optimize_launch twice without a collect stays allowed: the collect brings back the most recent launch.
+        //  - A batch and a slot's own loop do not cross: no batch launch over a slot pending as kSlot or under a pending batch, no
+        //    slot launch under a pending batch, and no s2m_set_params on a parent while one of its slots is pending.
+        enum Pending { kNone, kSingle, kSlot, kBatch } pending = kNone;
         bool seg_pending = false;          // the launch in flight was the first range only
-        bool opt_pending = false;
         bool scan_timing_pending = false;
         s2m::PrepSlot prep_slot{};         // the resident scan's row of the ordering kernels' table (s2m_debug_scan_prep runs them again)
         bool table_stale = false;          // a single scan is resident whose extent-only wave table has not been built (ensure_wave_table)
@@ -116,9 +129,9 @@ struct __attribute__((visibility("hidden"))) s2m_context {
         // loop state + trace of every slot in one block (device) with a pinned mirror: one copy brings all of a batch's results back
         DevBuf kid_states;
         unsigned char* h_kid_states = nullptr;
-        bool slot_mode = false;            // (a slot running a loop of its own on its own stream: s2m_slot_optimize_*)
         bool state_borrowed = false;       // (a slot: `reg.state` and `reg.h_state` point into the parent's blocks)
         std::map<std::vector<int>, hipGraphExec_t> graphs;
+        int pend_n = 0;                    // n_scans of the batch in flight (0: none); its slots 0 .. pend_n-1 are pending as kBatch
         std::vector<int> live;             // the slots of the batch in flight that run a loop
         bool seg_pending = false;          // the batch in flight was issued as its first range of launches only (early exit on)
         unsigned long long map_epoch = 0;  // bumped by every s2m_set_map: children re-adopt the index when it changed
@@ -262,6 +275,8 @@ struct __attribute__((visibility("hidden"))) s2m_context {
 namespace s2m {
 namespace host __attribute__((visibility("hidden"))) {
 
+using Reg = s2m_context::Registration;
+
 inline int fail(s2m_context* h, int code, const char* what, hipError_t e = hipSuccess)
 {
     if (h) {
@@ -323,8 +338,52 @@ inline void xyzrpy_to_transform(const float p[6], float T[12])
     host_pose_to_transform(rpyxyz, T, nullptr);
 }
 
-// ---- s2m_abi.hip (the LM loop: the only unit that launches kernels of s2m_kernels.hpp / s2m_register.hpp; the scan preparation
-// and the observation and timing hooks reach them through these) ----
+// A stream at the highest (`high`) or the lowest priority the device offers: the slots' streams alternate between the two, a
+// loop closure and a pose-graph solve run at the lowest so that they yield to the registration kernels. A device that reports
+// no range (or an error) gives a stream of the default priority; that is said on stderr, `who` naming the stream.
+inline int create_stream(s2m_context* h, hipStream_t* out, bool high, const char* who)
+{
+    int least = 0, greatest = 0;
+    const hipError_t e = hipDeviceGetStreamPriorityRange(&least, &greatest);
+    if (e != hipSuccess || least == greatest) {
+        (void)hipGetLastError();
+        fprintf(stderr, "liorf_s2m: no stream priority range on device %d (%s): %s runs at the default priority\n", h->device,
+                e != hipSuccess ? hipGetErrorString(e) : "least == greatest", who);
+        S2M_HIP(h, hipStreamCreateWithFlags(out, hipStreamNonBlocking));
+    } else {
+        S2M_HIP(h, hipStreamCreateWithPriority(out, hipStreamNonBlocking, high ? greatest : least));
+    }
+    return S2M_OK;
+}
+
+// puts a context on another stream for a scope (a slot on its own stream, the parent on a branch of the batch graph's capture)
+struct OnStream {
+    s2m_context* h;
+    hipStream_t keep;
+    OnStream(s2m_context* h_, hipStream_t s) : h(h_), keep(h_->stream) { h->stream = s; }
+    OnStream(const OnStream&) = delete;
+    ~OnStream() { h->stream = keep; }
+};
+
+// Forgets the pending optimise of `h` when the scope ends - with n_slots > 0 the batch of n_slots slots that `h` is the parent
+// of. A collect holds one for its whole body; a launch from its first mark on, release()d when everything is queued.
+struct PendingGuard {
+    s2m_context* h;
+    int n_slots;
+    explicit PendingGuard(s2m_context* h_, int n_slots_ = 0) : h(h_), n_slots(n_slots_) {}
+    PendingGuard(const PendingGuard&) = delete;
+    void release() { h = nullptr; }
+    ~PendingGuard()
+    {
+        if (!h) return;
+        if (n_slots == 0) { h->reg.pending = Reg::kNone; h->reg.seg_pending = false; return; }
+        for (int b = 0; b < n_slots; b++) { PendingGuard slot(h->batch.kids[(size_t)b]); }
+        h->batch.pend_n = 0; h->batch.seg_pending = false; h->batch.live.clear();
+    }
+};
+
+// ---- s2m_abi.hip (the LM loop: the only unit that launches kernels of s2m_kernels.hpp / s2m_register.hpp; the scan preparation,
+// the batches and slots and the observation and timing hooks reach them through these) ----
 float stamps_ms(const s2m_context* h, int from, int to);
 int ensure_rows(s2m_context* h, int nblocks);
 int upload_ctx(s2m_context* h);
@@ -334,6 +393,10 @@ int push_state(s2m_context* h, const float pose[6], unsigned long long* stamp = 
 void launch_density_state(s2m_context* h, const float pose[6], unsigned long long* stamp);
 // k_chunk_table, the extent-only wave table of `nslots` prepared slots (it shares chunk_table_body with k_chunk_table_density)
 void launch_chunk_table(hipStream_t stream, const PrepTable& t, int nslots);
+// k_set_ctxs / k_init_states over the first n entries of a table (a batch launch: the DevCtx blocks that changed, the loop
+// states its live slots start from); the entries behind them are marked unused here
+void launch_set_ctxs(hipStream_t stream, CtxTable& t, int n);
+void launch_init_states(hipStream_t stream, StateInitTable& t, int n);
 // what one loop launches over: the scan slots (one for a single scan), the widest grid among them, their common workgroup shape
 struct LoopShape {
     SlotTable tbl;
@@ -359,6 +422,38 @@ void launch_density_wishes(s2m_context* h, const LoopShape& sh);
 void launch_density_table(s2m_context* h, const LoopShape& sh);
 void launch_density(s2m_context* h, const LoopShape& sh);
 void enqueue_loop(s2m_context* h, const LoopShape& sh_in, hipEvent_t* events, bool coarse = false, int L0 = 0, int L1 = -1);
+// The launch and the collect of one context's loop, shared by the single-scan, slot and batch entry points.
+// optimize_gate: the soft conditions :1297 / :1300 for the optimisation of k's resident scan from `pose` (pending_pose_in,
+// pending_skipped); true: a loop runs.  two_ranges: with early exit on a loop is issued as launches 0 .. seg-1 and, only for
+// what has not converged by then, the rest.  optimize_launch: s2m_optimize_launch with the kind it is pending as.
+// collect_record: the host-only half of a collect, once the record is in the pinned mirror - result, persistent state, trace,
+// transformUpdate (:1317), or the skipped case.
+bool optimize_gate(s2m_context* k, const float pose[6]);
+inline bool two_ranges(const s2m_context* h) { return h->prm.early_exit && h->tune.seg_iters > 1 && h->tune.seg_iters < h->prm.max_iter; }
+int optimize_launch(s2m_context* h, const float pose[6], Reg::Pending kind);
+void collect_record(s2m_context* k, float pose[6], const s2m_imu_init* imu, s2m_result* out);
+// The second range, for what did not converge in the first: `issue` queues it on h's stream with whatever brings the record
+// back; it is waited for and timed by an event pair of its own, added to t_optimize_ms.
+template <typename Issue> int second_range(s2m_context* h, Issue issue)
+{
+    S2M_HIP(h, hipEventRecord(h->reg.ev_a2, h->stream));
+    const int rc = issue();
+    if (rc) return rc;
+    S2M_HIP(h, hipEventRecord(h->reg.ev_b2, h->stream));
+    S2M_HIP(h, hipStreamSynchronize(h->stream));
+    float t2 = 0.0f;
+    S2M_HIP(h, hipEventElapsedTime(&t2, h->reg.ev_a2, h->reg.ev_b2));
+    h->reg.t_optimize_ms += t2;
+    return S2M_OK;
+}
+
+// a slot of `h` has an optimise pending, of its own or as a row of a batch (s2m_set_params would pull the graphs from under it)
+inline bool slots_pending(const s2m_context* h)
+{
+    for (const s2m_context* k : h->batch.kids)
+        if (k->reg.pending != Reg::kNone) return true;
+    return false;
+}
 
 // ---- s2m_prep.hip (the map index and the scan preparation: kernels of s2m_prep.hpp) ----
 int set_map_impl(s2m_context* h, const void* pts, size_t n, size_t stride, bool on_device);

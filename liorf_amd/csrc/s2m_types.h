@@ -54,6 +54,9 @@ struct alignas(64) DevState {
 };
 static_assert(offsetof(DevState, done) == 0 && offsetof(DevState, pose2) == 16 && offsetof(DevState, T) == 64 &&
               offsetof(DevState, sc) == 112 && sizeof(DevState) % 64 == 0, "DevState: the prologue's fields fill the first line");
+// a loop's state block with its trace behind it: what one copy brings back, and the stride of a batch's slots in their common block
+constexpr size_t kSlotStateStride = sizeof(DevState) + sizeof(s2m_iter_trace) * kMaxIter;
+static_assert(kSlotStateStride % 64 == 0, "a batch's state blocks all start on a 64-byte line");
 
 // Everything a kernel needs, in device memory so a captured graph stays valid when
 // buffers grow or the grid changes; kernels receive only a pointer to this.

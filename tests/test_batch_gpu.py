@@ -2,22 +2,19 @@
 graph (BASELINE config 4 on a single GPU).  Bar: every scan's result, trace and transformUpdate() output are BITWISE
 those of a separate s2m_optimize call on a handle of its own; soft conditions (:1297, :1300) per slot; slots are
 reusable across batches, batch sizes and maps.  The oracle checks one batch end to end."""
+import os
+import sys
+
 import numpy as np
 import pytest
 
 from liorf_amd import s2m, synth
 from oracle import oracle as O
 
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "ref"))
+from solo_ref import solo as _solo  # noqa: E402
+
 pytestmark = pytest.mark.gpu
-
-
-def _solo(m, scan, pose, imu=None, **kw):
-    g = s2m.MapOptimizationS2M(**kw)
-    g.setInputCloud(m)
-    r = g.optimize(scan, pose, imu=imu)
-    tr = np.array([t.pose[:] for t in g.trace()], np.float32)
-    g.close()
-    return np.array(r.pose, np.float32), (r.iters_run, r.converged, r.is_degenerate, r.n_sel_last, r.skipped), np.array(r.affine, np.float32), tr
 
 
 def test_batch_equals_separate_calls_bitwise():
