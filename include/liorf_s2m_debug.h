@@ -5,7 +5,7 @@
  * what the repository's own tools and tests use to look inside the registration path - per-launch timing of the
  * registration kernel, per-wave stage stamps, the device's sinf / cosf / atanf arithmetic, worklist statistics - and the
  * list of environment switches the library reads at s2m_create for A/B experiments.  They may change between rounds.
- * The observation hooks (s2m_debug_device_*, s2m_debug_lm_close, s2m_debug_icp_*, s2m_debug_pg_*) run the product's own
+ * The observation hooks (s2m_debug_device_*, s2m_debug_lm_rows, s2m_debug_lm_close, s2m_debug_icp_*, s2m_debug_pg_*) run the product's own
  * kernels on given inputs and hand back what a stage wrote, so that tests can hold a stage against a reference of its own.
  *
  * Environment switches (all optional; defaults are what bench.py measures):
@@ -109,6 +109,36 @@ int  s2m_debug_lm_close(s2m_handle h, int form, int iter, const double* rows, in
  * - rows may be null when n_rows == 0 -, n_rows < 0, form outside {0, 1}, iter outside 0 .. max_iter-1, form 1 at iter 0). */
 int  s2m_debug_lm_close_check_args(int form, int iter, int max_iter, const double* rows, int n_rows, const float pose0[6],
                                    const float matP_in[36], const s2m_debug_lm_close_out* out);
+
+/* Observation hook: the partial rows ONE registration launch wrote - the stage between the plane fit and the close:
+ * residual and weight, the Jacobian row (:1216-1234), the 28 products, the wave reduction, the workgroup's row.
+ *   launch 0      what s2m_normal_eq queues in front of its k_finalize: the state upload at `pose`, then the first launch of
+ *                 a scan (trig from the host's libm)
+ *   launch N > 0  a real loop from `pose` exactly as s2m_optimize issues it (density re-split, R0 F0 R1 R2' ..., or certify +
+ *                 search under S2M_SPLIT=1, one k_finalize per iteration under S2M_NO_FUSE=1) up to and including launch N,
+ *                 nothing behind it. early_exit must be off and N < max_iter (S2M_ERR_INVALID_ARG otherwise)
+ *   rows          takes n_rows_active x 28 doubles from slot launch & 1 of the partial rows (layout as s2m_debug_lm_close);
+ *                 cap_rows smaller than n_rows_active: S2M_ERR_INVALID_ARG, with `out` filled in
+ *   wave_table    optional: the {first point, count} entries launch N read, n_waves of them (room for the table's capacity,
+ *                 see s2m_debug_scan_prep). Workgroup b's row sums the entries e with e % n_rows_active == b.
+ * S2M_ERR_INVALID_ARG while an optimise is pending or on a scan slot of a batch; needs a resident scan and map
+ * (S2M_ERR_NO_SCAN). No kernel exists for the hook: it queues what the product queues and copies back what the launch wrote.
+ * Afterwards the handle is where s2m_set_scan left it - isDegenerate and matP that persist from scan to scan untouched, a
+ * density re-split the hook's loop consumed pending again - so the next registration on the handle is the one a handle that
+ * never saw the hook computes. */
+typedef struct s2m_debug_lm_rows_out {
+    int32_t n_rows_active;     /* workgroups the wave table needs: entries over waves per workgroup, rounded up, the grid at most */
+    int32_t wpb, nblocks;      /* waves per workgroup and grid of the registration kernels              */
+    int32_t n_waves;           /* wave-table entries launch N read                                      */
+    float   pose_used[6];      /* the pose launch N ran with (N = 0: `pose`)                            */
+    int32_t done;              /* the loop's done flag after the launches before N                      */
+} s2m_debug_lm_rows_out;
+int  s2m_debug_lm_rows(s2m_handle h, const float pose[6], int launch, double* rows, int cap_rows, s2m_debug_lm_rows_out* out,
+                       int32_t* wave_table);
+/* The argument checks of s2m_debug_lm_rows that need no handle and no GPU: S2M_OK or S2M_ERR_INVALID_ARG (a null pose or
+ * out, rows null with cap_rows > 0, cap_rows < 0, launch outside 0 .. max_iter-1, launch > 0 with early_exit on). */
+int  s2m_debug_lm_rows_check_args(const float pose[6], int launch, int max_iter, int early_exit, const double* rows, int cap_rows,
+                                  const s2m_debug_lm_rows_out* out);
 
 /* Observation hook: the preparation of the RESIDENT single scan, run again by either chain, and what it left.
  *   chain  S2M_DEBUG_PREP_NEW     what s2m_set_scan launches: k_polar_count, k_polar_prefix, the scatter with the cell scan in it,

@@ -211,6 +211,66 @@ int s2m_debug_lm_close(s2m_handle h, int form, int iter, const double* rows, int
     return S2M_OK;
 }
 
+int s2m_debug_lm_rows_check_args(const float pose[6], int launch, int max_iter, int early_exit, const double* rows, int cap_rows,
+                                 const s2m_debug_lm_rows_out* out)
+{
+    if (!pose || !out || cap_rows < 0 || (cap_rows > 0 && !rows)) return S2M_ERR_INVALID_ARG;
+    if (launch < 0 || launch >= max_iter) return S2M_ERR_INVALID_ARG;
+    if (launch > 0 && early_exit) return S2M_ERR_INVALID_ARG;  // a loop that may end before launch N has no launch N
+    return S2M_OK;
+}
+
+int s2m_debug_lm_rows(s2m_handle h, const float pose[6], int launch, double* rows, int cap_rows, s2m_debug_lm_rows_out* out,
+                      int32_t* wave_table)
+{
+    if (!h) return S2M_ERR_INVALID_ARG;
+    if (s2m_debug_lm_rows_check_args(pose, launch, h->prm.max_iter, h->prm.early_exit, rows, cap_rows, out))
+        return fail(h, S2M_ERR_INVALID_ARG, "null argument, launch outside 0 .. max_iter-1, or launch > 0 with early_exit on");
+    if (h->batch.parent) return fail(h, S2M_ERR_INVALID_ARG, "a scan slot of a batch has no loop of its own to observe");
+    if (h->reg.pending != Reg::kNone) return fail(h, S2M_ERR_INVALID_ARG, "an optimize launch is pending: collect it first");
+    if (!h->reg.have_scan || h->reg.n_m == 0 || h->reg.n_q == 0) return fail(h, S2M_ERR_NO_SCAN, "needs a resident scan and map");
+    S2M_HIP(h, hipSetDevice(h->device));
+    int rc;
+    if ((rc = upload_ctx(h))) return rc;
+    const bool resplit = launch > 0 && h->hctx.density_pending && h->tune.density_raw > 0;   // the hook's loop consumes the scan's re-split
+    if ((rc = push_state(h, pose))) return rc;
+    const LoopShape sh = shape_of(h);
+    if (launch == 0) launch_fused(h, sh, false, 0, 0);      // (s2m_normal_eq's first launch)
+    else {
+        // enqueue_loop's launches 0 .. N, without the k_finalize behind launch N
+        const bool fuse = h->tune.fuse_solve && sh.nblocks * sh.nslots <= h->tune.fuse_max_blocks;
+        if (h->tune.density_raw > 0) launch_density(h, sh);
+        h->hctx.density_pending = 0;                      // cleared on the device by the kernel: keep the host copy in step
+        for (int L = 0; L <= launch; L++) {
+            launch_iteration(h, sh, L, (fuse && L >= 2) ? 1 : 0, fuse);
+            if (L < launch && (!fuse || L == 0)) launch_finalize(h, sh, L, 0);
+        }
+    }
+    S2M_HIP(h, hipGetLastError());
+    int32_t nw = 0;
+    S2M_HIP(h, hipMemcpyAsync(&h->reg.h_state[1], h->reg.state.p, sizeof(DevState), hipMemcpyDeviceToHost, h->stream));
+    S2M_HIP(h, hipMemcpyAsync(&nw, h->reg.n_waves.p, sizeof(nw), hipMemcpyDeviceToHost, h->stream));
+    S2M_HIP(h, hipStreamSynchronize(h->stream));
+    if (resplit) {                                          // back to where s2m_set_scan left the scan: the table is rebuilt from chunk_parts on demand
+        h->hctx.density_pending = 1;
+        h->reg.table_stale = true;
+        h->ctx_dirty = true;
+    }
+    if (nw < 0 || nw > h->hctx.table_cap) return fail(h, S2M_ERR_HIP, "wave count outside the table");
+    const DevState& r = h->reg.h_state[1];
+    const int nblocks = h->hctx.nblocks, wpb = h->hctx.wpb;
+    const int nb_act = std::min((nw + wpb - 1) / wpb, nblocks);
+    out->n_rows_active = nb_act; out->wpb = wpb; out->nblocks = nblocks; out->n_waves = nw;
+    memcpy(out->pose_used, launch == 0 ? pose : r.pose2[launch & 1], 24);
+    out->done = r.done;
+    if (cap_rows < nb_act) return fail(h, S2M_ERR_INVALID_ARG, "fewer rows offered than the resident scan has active workgroups");
+    const double* slot = h->reg.partials.as<double>() + (size_t)(launch & 1) * (size_t)nblocks * kAcc;
+    if (nb_act > 0) S2M_HIP(h, hipMemcpyAsync(rows, slot, sizeof(double) * (size_t)nb_act * kAcc, hipMemcpyDeviceToHost, h->stream));
+    if (wave_table && nw > 0) S2M_HIP(h, hipMemcpyAsync(wave_table, h->reg.wave_table.p, sizeof(int2) * (size_t)nw, hipMemcpyDeviceToHost, h->stream));
+    S2M_HIP(h, hipStreamSynchronize(h->stream));
+    return S2M_OK;
+}
+
 int s2m_normal_eq(s2m_handle h, const float pose[6], float AtA[36], float AtB[6], int32_t* n_sel)
 {
     if (!h || !pose) return S2M_ERR_INVALID_ARG;

@@ -37,7 +37,7 @@ ABI_SYMBOLS = [
     "s2m_voxel_downsample", "s2m_voxel_downsample_device", "s2m_downsample_scan", "s2m_extract_cloud",
     "s2m_transform_cloud",
     "s2m_icp_default_params", "s2m_icp_align", "s2m_icp_align_guess", "s2m_debug_device_trig", "s2m_debug_device_hypot",
-    "s2m_debug_lm_close", "s2m_debug_lm_close_check_args",
+    "s2m_debug_lm_close", "s2m_debug_lm_close_check_args", "s2m_debug_lm_rows", "s2m_debug_lm_rows_check_args",
     "s2m_sc_reset", "s2m_sc_size", "s2m_sc_add_scan", "s2m_sc_add_descriptor", "s2m_sc_detect_loop", "s2m_sc_distance",
     "s2m_sc_query_default_params", "s2m_sc_query_check_args", "s2m_sc_query_key", "s2m_sc_query_descriptor", "s2m_sc_query_scan", "s2m_sc_query_projected",
     "s2m_kf_default_params", "s2m_kf_reset", "s2m_kf_size", "s2m_kf_add", "s2m_kf_set_poses", "s2m_extract_surrounding",
@@ -112,6 +112,12 @@ class LmCloseOut(C.Structure):
                 ("pose", C.c_float * 6), ("pose_next", C.c_float * 6), ("iters_run", C.c_int32), ("converged", C.c_int32),
                 ("done", C.c_int32), ("stalled", C.c_int32), ("is_degenerate", C.c_int32), ("n_rows_active", C.c_int32),
                 ("matP", C.c_float * 36)]
+
+
+class LmRowsOut(C.Structure):
+    """s2m_debug_lm_rows_out (include/liorf_s2m_debug.h)."""
+    _fields_ = [("n_rows_active", C.c_int32), ("wpb", C.c_int32), ("nblocks", C.c_int32), ("n_waves", C.c_int32),
+                ("pose_used", C.c_float * 6), ("done", C.c_int32)]
 
 
 class ScMatch(C.Structure):
@@ -320,6 +326,8 @@ def load_library(path: str | None = None) -> C.CDLL:
     L.s2m_debug_device_hypot.argtypes = [vp, fp, fp, C.c_size_t, fp]
     L.s2m_debug_lm_close.argtypes = [vp, C.c_int, C.c_int, dp, C.c_int, fp, C.c_int, fp, C.POINTER(LmCloseOut)]
     L.s2m_debug_lm_close_check_args.argtypes = [C.c_int, C.c_int, C.c_int, dp, C.c_int, fp, fp, C.POINTER(LmCloseOut)]
+    L.s2m_debug_lm_rows.argtypes = [vp, fp, C.c_int, dp, C.c_int, C.POINTER(LmRowsOut), i32p]
+    L.s2m_debug_lm_rows_check_args.argtypes = [fp, C.c_int, C.c_int, C.c_int, dp, C.c_int, C.POINTER(LmRowsOut)]
     L.s2m_icp_default_params.argtypes = [C.POINTER(IcpParams)]
     L.s2m_icp_align.argtypes = [vp, vp, C.c_size_t, vp, C.c_size_t, C.c_size_t, C.POINTER(IcpParams), C.POINTER(IcpResult)]
     L.s2m_icp_align_guess.argtypes = [vp, vp, C.c_size_t, vp, C.c_size_t, C.c_size_t, fp, C.POINTER(IcpParams), C.POINTER(IcpResult)]
@@ -812,6 +820,19 @@ class MapOptimizationS2M:
         self._check(self.lib.s2m_debug_lm_close(self.h, form, it, r.ctypes.data_as(C.POINTER(C.c_double)), r.shape[0], _fp(p),
                                                 int(degen_in), _fp(m), C.byref(out)), "s2m_debug_lm_close")
         return out
+
+    def lmRows(self, pose, launch: int = 0, table: bool = True):
+        """Observation hook: the partial rows registration launch `launch` wrote (0: the first launch of a scan at `pose`;
+        N > 0: launch N of a real loop from `pose`); see s2m_debug_lm_rows. Returns (rows (n_rows_active, 28) float64,
+        LmRowsOut, wave table (n_waves, 2) int32 or None)."""
+        p = np.ascontiguousarray(pose, np.float32).reshape(6)
+        cap = 512                                              # (kMaxBlocks: no scan has more active workgroups)
+        rows = np.zeros((cap, 28), np.float64)
+        wt = np.zeros(((self.laserCloudSurfLastDSNum + 63) // 64 * 12 + 64, 2), np.int32) if table else None
+        out = LmRowsOut()
+        self._check(self.lib.s2m_debug_lm_rows(self.h, _fp(p), int(launch), rows.ctypes.data_as(C.POINTER(C.c_double)), cap, C.byref(out),
+                                               None if wt is None else wt.ctypes.data_as(C.POINTER(C.c_int32))), "s2m_debug_lm_rows")
+        return rows[:out.n_rows_active].copy(), out, None if wt is None else wt[:out.n_waves].copy()
 
     def scanPrep(self, chain: int = 0, pose=None) -> dict:
         """Observation hook: run the preparation of the resident scan again (chain 0 = as setScan / launch do, 1 = the
