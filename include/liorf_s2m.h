@@ -1023,6 +1023,60 @@ int  s2m_pg_joint_marginal(s2m_handle h, int32_t key_a, int32_t key_b, double co
  * leaves the store as it was. */
 int  s2m_pg_apply_to_store(s2m_handle h, int32_t first, int32_t count);
 
+/* ---- Saving and loading a session ---------------------------------------------------------------------------
+ * One little-endian byte stream (format version 1) holds the primary state of a handle: the key-frame
+ * store (pose, time, point count and the 32-byte records of every key, all eight words as they are stored), the ScanContext
+ * store (the fp64 descriptors, n_search and the detector's call counter), the loop container's (key_cur, key_pre) pairs and the
+ * pose graph (the factors in the order they were added, the fp64 estimates, which variables have a value). Not in it:
+ * parameters, the installed map, the scan, scan_ds and cloud_deskewed, anything pending, caller-owned state such as
+ * s2m_guess_state, and everything derived - key transforms, device positions, ring and sector keys, the pose graph's device
+ * tables - which a load rebuilds by the paths the per-key calls use, so that after a successful load the handle answers every
+ * call of this ABI bit for bit as the handle that saved did at that moment, and s2m_kf_add / s2m_sc_add_* / s2m_pg_add_*
+ * continue from there.
+ * The stream is a fixed header (magic, version, all counts, every section's byte size), six sections and a footer with a
+ * checksum per section and one over header and footer. The checksum - two 64-bit sums over 32-bit words, computed on the
+ * device while it moves the bytes - is an integrity check against truncation and corruption, NOT a security measure: do not
+ * load a file from a source you do not trust on the strength of it.
+ * The bulk (records, descriptors) never passes through host code: device -> pinned chunk -> callback, and back; the device packs
+ * chunk k+1 while the callback has chunk k.
+ *   s2m_session_write_fn / s2m_session_read_fn: called in stream order with chunks of any size; 0 = ok. A write callback's
+ *       `data`, and a read callback's, are valid during the call only. Any other return ends the call with S2M_ERR_IO, except
+ *       that a read callback may return S2M_ERR_FORMAT for "the stream has ended", which is passed on.
+ *   s2m_session_info_of: what a save would write now (host only; fields of a pending launch are not waited for).
+ *   s2m_session_save reads only. It first brings the library's host mirror of the estimates up to date where the device's
+ *       are newer, as s2m_pg_get_poses does. S2M_ERR_BUSY while a launched loop closure or verification or a launched
+ *       pose-graph optimise is pending. The bytes do not depend on the chunk size or on how the callback is called.
+ *   s2m_session_load needs the key-frame store, the ScanContext store, the loop container and the pose graph EMPTY:
+ *       otherwise S2M_ERR_INVALID_ARG, nothing touched - s2m_kf_reset, s2m_sc_reset and s2m_pg_reset first. S2M_ERR_BUSY as
+ *       for a save. A load that fails at ANY point - a callback, a checksum, the content, a HIP error - leaves all four
+ *       empty again, never half filled. It reports the first failure in stream order: content it cannot use as it arrives
+ *       (S2M_ERR_FORMAT), then the checksums at the footer (S2M_ERR_CHECKSUM).
+ *   s2m_session_save_file / s2m_session_load_file: the two above on a file (a file that ends early is S2M_ERR_FORMAT).
+ *   s2m_session_check: a whole blob in memory, without a handle or a device: the structure (magic, version, the byte count;
+ *       S2M_ERR_FORMAT), then every checksum, the header's first (S2M_ERR_CHECKSUM), then the content (S2M_ERR_FORMAT):
+ *       section sizes that follow from the counts; at most 2^24 keys, descriptors and variables; point counts >= 0 that sum
+ *       to the record section; finite poses and times; 0 <= n_search <= n, counter >= 0; loop pairs ascending in key_cur,
+ *       both keys stored; every factor what s2m_pg_check_args accepts for a graph that holds its keys, with the rows of its
+ *       type; and variables and values that the add calls can have produced in that factor order (a key is new only as the
+ *       next variable, or it already holds a value). s2m_session_load checks the same. */
+#define S2M_ERR_FORMAT        -7   /* session: bad magic, unknown version, truncated stream or inconsistent content */
+#define S2M_ERR_CHECKSUM      -8   /* session: a section's or the header's checksum does not match                   */
+#define S2M_ERR_IO            -9   /* session: a callback or a file call failed                                      */
+#define S2M_SESSION_VERSION    1
+typedef int (*s2m_session_write_fn)(void* user, const void* data, size_t bytes);   /* 0 = ok */
+typedef int (*s2m_session_read_fn)(void* user, void* data, size_t bytes);          /* 0 = ok, fills exactly `bytes` */
+typedef struct s2m_session_info {
+    uint32_t version;
+    int32_t  n_keys, n_descriptors, n_loop_pairs, n_variables, n_factors;
+    uint64_t n_points, bytes;
+} s2m_session_info;
+int  s2m_session_info_of(s2m_handle h, s2m_session_info* out);
+int  s2m_session_save(s2m_handle h, s2m_session_write_fn w, void* user);
+int  s2m_session_load(s2m_handle h, s2m_session_read_fn r, void* user, s2m_session_info* out /* may be NULL */);
+int  s2m_session_save_file(s2m_handle h, const char* path);
+int  s2m_session_load_file(s2m_handle h, const char* path, s2m_session_info* out /* may be NULL */);
+int  s2m_session_check(const void* blob, size_t bytes, s2m_session_info* out /* may be NULL */);
+
 #ifdef __cplusplus
 }
 #endif

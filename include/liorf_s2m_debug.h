@@ -272,6 +272,18 @@ int  s2m_debug_pg_cg(s2m_handle h, const s2m_pg_params* p, int32_t cols, const d
 /* X[12 k ..] = estimate of key k (+) delta[6 k ..] through k_pg_retract; the estimates stay. n_variables must be the graph's. */
 int  s2m_debug_pg_retract(s2m_handle h, int32_t n_variables, const double* delta, double* X);
 
+/* ---- saving and loading a session: the staging chunk and the state a load rebuilds ----
+ * s2m_debug_session_chunk: the bytes of one staging chunk of s2m_session_save / s2m_session_load (default 16 MiB; 0 restores
+ *   it): a multiple of 32, at least 1024, so that a store of a few dozen small keys crosses many chunk edges. The blob does
+ *   not depend on it.
+ * s2m_debug_sc_keys: the fp32 ring keys (count x 20) and fp64 sector keys (count x 60) of descriptors first .. first+count-1
+ *   as the store holds them.
+ * s2m_debug_kf_frame: key `key`'s cached transform in the library's host mirror and in the device's frame table, its device
+ *   position (x, y, z, 0) and the point count of the device's entry. */
+int  s2m_debug_session_chunk(s2m_handle h, size_t chunk_bytes);
+int  s2m_debug_sc_keys(s2m_handle h, int32_t first, int32_t count, float* ring, double* sector);
+int  s2m_debug_kf_frame(s2m_handle h, int32_t key, float T_host[12], float T_device[12], float pos_device[4], int32_t* n_device);
+
 #ifdef __cplusplus
 }
 #endif

@@ -168,6 +168,44 @@ int s2m_kf_add(s2m_handle h, const float pose_xyzrpy[6], double time, const void
     return S2M_OK;
 }
 
+int s2m::host::copy_pipeline(s2m_context* h)
+{
+    if (!h->gmap.copy_stream) S2M_HIP(h, hipStreamCreateWithFlags(&h->gmap.copy_stream, hipStreamNonBlocking));
+    for (int k = 0; k < 2; k++) {
+        if (!h->gmap.ev_xf[k]) S2M_HIP(h, hipEventCreateWithFlags(&h->gmap.ev_xf[k], hipEventDisableTiming));
+        if (!h->gmap.ev_cp[k]) S2M_HIP(h, hipEventCreateWithFlags(&h->gmap.ev_cp[k], hipEventDisableTiming));
+    }
+    return S2M_OK;
+}
+
+int s2m::host::kf_install_keys(s2m_context* h, size_t n, const float* pose_xyzrpy, const double* time, const int32_t* counts)
+{
+    if (!h->kf.time.empty() || !h->kf.blocks.empty()) return fail(h, S2M_ERR_INVALID_ARG, "the key-frame store is not empty");
+    if (n == 0) return S2M_OK;
+    S2M_HIP(h, hipSetDevice(h->device));
+    int rc = kf_reserve(h, n);
+    if (rc) return rc;
+    std::vector<float4> pos(n);
+    std::vector<KfFrame> fr(n);
+    for (size_t k = 0; k < n; k++) {
+        const size_t bytes = kDsStride * (size_t)counts[k];
+        unsigned char* dst = nullptr;
+        if ((rc = kf_arena_take(h, bytes, &dst))) return rc;
+        h->kf.block_used += bytes;
+        const float* q = pose_xyzrpy + 6 * k;
+        fr[k] = kf_frame_of(q, dst, counts[k]);
+        pos[k] = make_float4(q[0], q[1], q[2], 0.0f);
+    }
+    S2M_HIP(h, hipMemcpyAsync(h->kf.pos.p, pos.data(), sizeof(float4) * n, hipMemcpyHostToDevice, h->stream));
+    S2M_HIP(h, hipMemcpyAsync(h->kf.frames.p, fr.data(), sizeof(KfFrame) * n, hipMemcpyHostToDevice, h->stream));
+    S2M_HIP(h, hipMemcpyAsync(h->kf.tdev.p, time, sizeof(double) * n, hipMemcpyHostToDevice, h->stream));
+    S2M_HIP(h, hipStreamSynchronize(h->stream));          // (the host vectors above are read by the copies until here)
+    h->kf.pose.assign(pose_xyzrpy, pose_xyzrpy + 6 * n);
+    h->kf.time.assign(time, time + n);
+    h->kf.frame = std::move(fr);
+    return S2M_OK;
+}
+
 int s2m_kf_set_poses(s2m_handle h, int first, int count, const float* poses_xyzrpy)
 {
     if (!h) return S2M_ERR_INVALID_ARG;
@@ -353,11 +391,7 @@ int map_copy_out_chunked(s2m_context* h, int first, int count, size_t m, void* o
     if (rc) return rc;
     for (int k = 0; k < 2 && k < (int)chunks.size(); k++)
         if ((rc = ensure(h, h->gmap.stage[k], kDsStride * biggest))) return rc;
-    if (!h->gmap.copy_stream) S2M_HIP(h, hipStreamCreateWithFlags(&h->gmap.copy_stream, hipStreamNonBlocking));
-    for (int k = 0; k < 2; k++) {
-        if (!h->gmap.ev_xf[k]) S2M_HIP(h, hipEventCreateWithFlags(&h->gmap.ev_xf[k], hipEventDisableTiming));
-        if (!h->gmap.ev_cp[k]) S2M_HIP(h, hipEventCreateWithFlags(&h->gmap.ev_cp[k], hipEventDisableTiming));
-    }
+    if ((rc = copy_pipeline(h))) return rc;
     unsigned char* d_tab = h->gmap.tab.as<unsigned char>();
     S2M_HIP(h, hipMemcpyAsync(d_tab, tab.data(), tab.size(), hipMemcpyHostToDevice, h->stream));
     const unsigned char* const* d_src = reinterpret_cast<const unsigned char* const*>(d_tab);

@@ -424,6 +424,8 @@ int advance(s2m_context* h, s2m_pg_result* out)
 
 }  // namespace
 
+int s2m::host::pg_host_current(s2m_context* h) { return host_current(h); }
+
 int s2m_pg_reset(s2m_handle h)
 {
     if (!h) return S2M_ERR_INVALID_ARG;

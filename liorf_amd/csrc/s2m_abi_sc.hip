@@ -4,6 +4,7 @@
 
 #include "s2m_context.hpp"
 #include "s2m_sc.hpp"
+#include "s2m_sc_keys.hpp"
 
 using namespace s2m;
 using namespace s2m::host;
@@ -59,11 +60,7 @@ int s2m_sc_add_descriptor(s2m_handle h, const double desc[S2M_SC_NUM_RING * S2M_
     S2M_HIP(h, hipSetDevice(h->device));
     // ring key = row means, as makeRingkeyFromScancontext (:198-211) / k_sc_finish compute them
     memcpy(h->sc.h_stage, desc, sizeof(double) * kScDesc);
-    for (int r = 0; r < S2M_SC_NUM_RING; r++) {
-        double a = 0.0;
-        for (int k = 0; k < S2M_SC_NUM_SECTOR; k++) a += desc[r * S2M_SC_NUM_SECTOR + k];
-        h->sc.h_stage[kScDesc + r] = a / 60.0;
-    }
+    for (int r = 0; r < S2M_SC_NUM_RING; r++) h->sc.h_stage[kScDesc + r] = sc_ring_key([&](int k) { return desc[r * S2M_SC_NUM_SECTOR + k]; });
     S2M_HIP(h, hipMemcpyAsync(h->sc.out.p, h->sc.h_stage, sizeof(double) * 1220, hipMemcpyHostToDevice, h->stream));
     int rc = sc_append_from_out(h);
     if (rc) return rc;

@@ -270,6 +270,15 @@ struct __attribute__((visibility("hidden"))) s2m_context {
         int pend_max_cg = 0;
         double a_launch[12] = { 0 };               // variable n_l - 1 at launch
     } pg;
+
+    // saving and loading a session (s2m_abi_session.hip): the segment table of a section on the device, the workgroups' checksum
+    // partials, and two pinned chunks that take turns with gmap's two device staging buffers on gmap's copy stream
+    struct Session {
+        DevBuf tab, partial;
+        unsigned char* h_chunk[2] = { nullptr, nullptr };      // pinned, h_chunk_cap bytes each
+        size_t h_chunk_cap = 0;
+        size_t chunk_bytes = 0;                                // 0: the default (s2m_debug_session_chunk sets a small one)
+    } sess;
 };
 
 namespace s2m {
@@ -466,6 +475,8 @@ void ensure_wave_table(s2m_context* h);
 // SCManager::makeScancontext + ring key of a cloud into h->sc.out (device); then: append them as key frame sc.n
 int sc_build_descriptor(s2m_context* h, const void* pts, size_t n, size_t stride_bytes, bool on_device = false);
 int sc_append_from_out(s2m_context* h);
+// the store's three arrays hold `want` descriptors (grow-with-copy)
+int sc_reserve(s2m_context* h, size_t want);
 
 // ---- s2m_abi_sc_query.hip ----
 // s2m_sc_query_scan with the scan on the device (n records of stride_bytes): hits has room for p->top_k records
@@ -482,6 +493,17 @@ void loop_drop_pending(s2m_context* h, bool destroy);
 // waits for the pose-graph stream and forgets the pending optimise (s2m_pg_reset, s2m_destroy); `destroy`: stream, events and the
 // pinned record go too
 void pg_drop_pending(s2m_context* h, bool destroy);
+// the host mirror of the estimates holds the newest values (the device's, where an accepted step made them newer)
+int pg_host_current(s2m_context* h);
+
+// ---- s2m_abi_keyframes.hip ----
+// gmap's copy stream and its two pairs of events exist (the chunked copy-out of the saved map and of a session share them)
+int copy_pipeline(s2m_context* h);
+// n keys into an EMPTY store in one go (a session load): poses {x, y, z, roll, pitch, yaw}, times and point counts; every key
+// gets its place in the arena, as n s2m_kf_add would give them, and its transform and position by the path of s2m_kf_add, with
+// one upload per device array.  The records themselves are written by the caller, to frame[k].src.  A failure leaves the store
+// for s2m_kf_reset.
+int kf_install_keys(s2m_context* h, size_t n, const float* pose_xyzrpy, const double* time, const int32_t* counts);
 
 // ---- s2m_abi_voxel.hip ----
 // VoxelGrid of a device cloud into `dst` (grown to hold one record per input point, the worst case).

@@ -10,6 +10,7 @@
 #include "s2m_device.hpp"
 #include "s2m_sc_dist.hpp"          // kScThreads, kScShifts, ScShared, sc_distance_block: shared with the place query (s2m_sc_query.hip)
 #include "s2m_sc.hpp"
+#include "s2m_sc_keys.hpp"          // sc_ring_key, sc_sector_key: shared with the host add and the session load
 
 using namespace s2m;
 using namespace s2m::host;
@@ -58,8 +59,7 @@ __global__ __launch_bounds__(64) void k_sc_finish(const uint32_t* __restrict__ b
     // one wave; lane r < 20 owns ring r
     const int r = threadIdx.x;
     if (r >= S2M_SC_NUM_RING) return;
-    double s = 0.0;
-    for (int k = 0; k < S2M_SC_NUM_SECTOR; k++) {
+    ringkey[r] = sc_ring_key([&](int k) {                                  // row mean (:198-211) of the values as they are stored
         const uint32_t u = bins[r * S2M_SC_NUM_SECTOR + k];
         double v = 0.0;                                                    // NO_POINT -> 0 (:187-190)
         if (u) {
@@ -69,9 +69,8 @@ __global__ __launch_bounds__(64) void k_sc_finish(const uint32_t* __restrict__ b
             v = ((double)z > -1000.0) ? (double)z : 0.0;
         }
         desc[r * S2M_SC_NUM_SECTOR + k] = v;
-        s += v;
-    }
-    ringkey[r] = s / 60.0;                                                 // row mean (:198-211)
+        return v;
+    });
 }
 
 // ------------------------------------------------------------------------------------------
@@ -91,11 +90,8 @@ __global__ __launch_bounds__(kScThreads) void k_sc_append(const double* __restri
     double* d = store_desc + (size_t)idx * NR * NS;
     for (int k = threadIdx.x; k < NR * NS; k += kScThreads) d[k] = desc_ring[k];
     if (threadIdx.x < NR) store_ring[(size_t)idx * NR + threadIdx.x] = (float)desc_ring[NR * NS + threadIdx.x];
-    if (threadIdx.x < NS) {                                                // makeSectorkeyFromScancontext (:214-227)
-        double a = 0.0;
-        for (int r = 0; r < NR; r++) a += desc_ring[r * NS + threadIdx.x];
-        store_sector[(size_t)idx * NS + threadIdx.x] = a / (double)NR;
-    }
+    if (threadIdx.x < NS)                                                  // makeSectorkeyFromScancontext (:214-227)
+        store_sector[(size_t)idx * NS + threadIdx.x] = sc_sector_key([&](int r) { return desc_ring[r * NS + threadIdx.x]; });
 }
 
 // distanceBtnScanContext of descriptor `query` against cand[0..m): one workgroup per candidate
@@ -218,8 +214,10 @@ namespace {
 // ---- ScanContext store ---------------------------------------------------------------------------
 constexpr size_t kScDesc = (size_t)S2M_SC_NUM_RING * S2M_SC_NUM_SECTOR;
 
+}  // namespace
+
 // grow-with-copy (ensure() alone would drop the contents)
-int sc_reserve(s2m_context* h, size_t want)
+int s2m::host::sc_reserve(s2m_context* h, size_t want)
 {
     if (want <= h->sc.cap) return S2M_OK;
     size_t cap = h->sc.cap ? h->sc.cap : 256;
@@ -237,8 +235,6 @@ int sc_reserve(s2m_context* h, size_t want)
     h->sc.cap = cap;
     return S2M_OK;
 }
-
-}  // namespace
 
 // descriptor + ring key are in h->sc.out (device): append them as key frame sc.n
 int s2m::host::sc_append_from_out(s2m_context* h)

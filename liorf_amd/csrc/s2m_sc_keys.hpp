@@ -1,0 +1,31 @@
+// s2m_sc_keys.hpp — the two keys of a ScanContext descriptor, stated once: the ring key (row mean, makeRingkeyFromScancontext,
+// include/Scancontext.cpp:198-211) and the sector key (column mean, makeSectorkeyFromScancontext, :214-227).  Both sum left to
+// right in fp64.  Every place that makes a key calls these - k_sc_finish and k_sc_append (s2m_sc.hip), s2m_sc_add_descriptor on
+// the host (s2m_abi_sc.hip) and the batch rebuild of a loaded session (k_sc_keys_batch, s2m_session.hip) - so a store that was
+// loaded holds bit for bit the keys the incremental adds left.  Compiled with -ffp-contract=off like everything else.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include "../../include/liorf_s2m.h"
+
+namespace s2m {
+
+// mean of ring r's 60 sectors; at(k) is the descriptor's value at (r, k)
+template <typename At>
+__host__ __device__ __forceinline__ double sc_ring_key(At at)
+{
+    double s = 0.0;
+    for (int k = 0; k < S2M_SC_NUM_SECTOR; k++) s += at(k);
+    return s / 60.0;
+}
+
+// mean of a sector's 20 rings; at(r) is the descriptor's value at (r, sector)
+template <typename At>
+__host__ __device__ __forceinline__ double sc_sector_key(At at)
+{
+    double a = 0.0;
+    for (int r = 0; r < S2M_SC_NUM_RING; r++) a += at(r);
+    return a / (double)S2M_SC_NUM_RING;
+}
+
+}  // namespace s2m

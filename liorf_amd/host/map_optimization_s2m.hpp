@@ -587,6 +587,32 @@ public:
         return true;
     }
 
+    // -- a session: the key-frame store, the ScanContext store, the loop container and the pose graph in one file
+    // (s2m_session_save_file / s2m_session_load_file). A node that starts in yesterday's map: loadSession(path),
+    // relocalizeScan(scan), extractSurroundingKeyFramesAt(&transformTobeMapped[3]), scan2MapOptimization().
+    void saveSession(const std::string& path) { check(s2m_session_save_file(h_, path.c_str()), "s2m_session_save_file"); }
+    // Into a node that has stored nothing yet (the library refuses anything else). The clouds stay in the library's store -
+    // surfCloudKeyFrames is not filled - and cloudKeyPoses6D mirrors the loaded keys with the pose graph's estimates where the
+    // graph holds them (after correctPoses() they are the store's poses), intensity = index; the keys' times stay with the library.
+    s2m_session_info loadSession(const std::string& path)
+    {
+        s2m_session_info info{};
+        check(s2m_session_load_file(h_, path.c_str(), &info), "s2m_session_load_file");
+        cloudKeyPoses6D.assign((size_t)info.n_keys, PointTypePose{});
+        const int32_t n = info.n_keys < info.n_variables ? info.n_keys : info.n_variables;
+        std::vector<float> v(6 * (size_t)n);
+        if (n > 0) check(s2m_pg_get_poses(h_, 0, n, v.data()), "s2m_pg_get_poses");
+        for (int32_t k = 0; k < info.n_keys; k++) {
+            PointTypePose& q = cloudKeyPoses6D[(size_t)k];
+            q.intensity = (float)k;
+            if (k < n) { q.x = v[6 * k]; q.y = v[6 * k + 1]; q.z = v[6 * k + 2]; q.roll = v[6 * k + 3]; q.pitch = v[6 * k + 4]; q.yaw = v[6 * k + 5]; }
+        }
+        surfCloudKeyFrames.clear();
+        loopQueue.clear();
+        aLoopIsClosed = false;
+        return info;
+    }
+
     // true: a verification is pending (false: lastVerify is final)
     bool loopVerifyLaunch(int key_cur, const std::vector<int32_t>& key_pre, int base_key = -1)
     {

@@ -22,8 +22,9 @@ LIB_PATH = os.environ.get("S2M_LIB") or os.path.join(_HERE, "libliorf_s2m.so")  
 S2M_OK = 0
 S2M_ERR_CAPACITY = -5
 S2M_ERR_BUSY = -6
+S2M_ERR_FORMAT, S2M_ERR_CHECKSUM, S2M_ERR_IO = -7, -8, -9   # saving and loading a session
 ERRORS = {-1: "S2M_ERR_INVALID_ARG", -2: "S2M_ERR_NO_DEVICE", -3: "S2M_ERR_HIP", -4: "S2M_ERR_NO_SCAN",
-          -5: "S2M_ERR_CAPACITY", -6: "S2M_ERR_BUSY"}
+          -5: "S2M_ERR_CAPACITY", -6: "S2M_ERR_BUSY", -7: "S2M_ERR_FORMAT", -8: "S2M_ERR_CHECKSUM", -9: "S2M_ERR_IO"}
 
 # every symbol include/liorf_s2m.h declares
 ABI_SYMBOLS = [
@@ -58,7 +59,10 @@ ABI_SYMBOLS = [
     "s2m_pg_optimize_launch", "s2m_pg_optimize_poll", "s2m_pg_optimize_collect", "s2m_debug_pg_rebase",
     "s2m_debug_pg_set_estimate", "s2m_debug_pg_linearize", "s2m_debug_pg_apply", "s2m_debug_pg_apply_check_args", "s2m_debug_pg_cg",
     "s2m_debug_pg_retract",
+    "s2m_session_info_of", "s2m_session_save", "s2m_session_load", "s2m_session_save_file", "s2m_session_load_file", "s2m_session_check",
+    "s2m_debug_session_chunk", "s2m_debug_sc_keys", "s2m_debug_kf_frame",
 ]
+S2M_SESSION_VERSION = 1
 S2M_RING_U8, S2M_RING_U16, S2M_RING_I32 = 0, 1, 2
 S2M_TIME_F32, S2M_TIME_U32_NS, S2M_TIME_U32, S2M_TIME_F64_REL = 0, 1, 2, 3
 S2M_SENSOR_VELODYNE, S2M_SENSOR_LIVOX, S2M_SENSOR_OUSTER, S2M_SENSOR_MULRAN, S2M_SENSOR_ROBOSENSE = 0, 1, 2, 3, 4
@@ -240,8 +244,19 @@ class PgCgOut(C.Structure):
     _fields_ = [("rr", C.c_double), ("bb", C.c_double), ("iters", C.c_int32), ("stop", C.c_int32)]
 
 
+class SessionInfo(C.Structure):
+    """s2m_session_info: what a session blob holds."""
+    _fields_ = [("version", C.c_uint32), ("n_keys", C.c_int32), ("n_descriptors", C.c_int32), ("n_loop_pairs", C.c_int32),
+                ("n_variables", C.c_int32), ("n_factors", C.c_int32), ("n_points", C.c_uint64), ("bytes", C.c_uint64)]
+
+
+SESSION_WRITE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_size_t)
+SESSION_READ_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_size_t)
+
+
 class S2MError(RuntimeError):
-    pass
+    """`code` is the status the library returned, where one did."""
+    code = None
 
 
 _LIB = None
@@ -423,6 +438,15 @@ def load_library(path: str | None = None) -> C.CDLL:
     L.s2m_pg_joint_marginal.argtypes = [vp, C.c_int32, C.c_int32, dp]
     L.s2m_update_initial_guess.argtypes = [C.POINTER(GuessState), C.POINTER(C.c_float), C.c_int, C.POINTER(GuessInfo), C.c_int, C.c_int,
                                            C.POINTER(C.c_float)]
+    L.s2m_session_info_of.argtypes = [vp, C.POINTER(SessionInfo)]
+    L.s2m_session_save.argtypes = [vp, SESSION_WRITE_FN, vp]
+    L.s2m_session_load.argtypes = [vp, SESSION_READ_FN, vp, C.POINTER(SessionInfo)]
+    L.s2m_session_save_file.argtypes = [vp, C.c_char_p]
+    L.s2m_session_load_file.argtypes = [vp, C.c_char_p, C.POINTER(SessionInfo)]
+    L.s2m_session_check.argtypes = [vp, C.c_size_t, C.POINTER(SessionInfo)]
+    L.s2m_debug_session_chunk.argtypes = [vp, C.c_size_t]
+    L.s2m_debug_sc_keys.argtypes = [vp, C.c_int32, C.c_int32, fp, dp]
+    L.s2m_debug_kf_frame.argtypes = [vp, C.c_int32, fp, fp, fp, i32p]
     if path is None:
         _LIB = L
     return L
@@ -446,6 +470,19 @@ def default_params(**kw) -> Params:
     for k, v in kw.items():
         setattr(p, k, v)
     return p
+
+
+def session_check(blob) -> SessionInfo:
+    """s2m_session_check: structure, checksums and content of a session blob, on the host, without a handle or a GPU. Returns
+    what it holds; raises S2MError (`code`: S2M_ERR_FORMAT or S2M_ERR_CHECKSUM) otherwise."""
+    b = bytes(blob)
+    out = SessionInfo()
+    rc = load_library().s2m_session_check(b, len(b), C.byref(out))
+    if rc != S2M_OK:
+        e = S2MError(f"s2m_session_check: {ERRORS.get(rc, rc)}")
+        e.code = rc
+        raise e
+    return out
 
 
 def _fp(a):
@@ -494,7 +531,9 @@ class MapOptimizationS2M:
     def _check(self, rc: int, what: str):
         if rc != S2M_OK:
             msg = self.lib.s2m_last_error(self.h)
-            raise S2MError(f"{what}: {ERRORS.get(rc, rc)}: {msg.decode() if msg else ''}")
+            e = S2MError(f"{what}: {ERRORS.get(rc, rc)}: {msg.decode() if msg else ''}")
+            e.code = rc
+            raise e
 
     def setParams(self, **kw):
         """s2m_set_params: the ParamServer values the path reads at every call in the reference
@@ -1105,6 +1144,82 @@ class MapOptimizationS2M:
         self.extractSurroundingKeyFramesAt(pose[3:6], kf, readback=False)
         self.transformTobeMapped = pose.copy()
         return pose, recs, best
+
+    # -- saving and loading a session: key frames, descriptors, loop pairs, pose graph ------------------------------
+    def session_info(self) -> SessionInfo:
+        """s2m_session_info_of: what session_save() would write now."""
+        out = SessionInfo()
+        self._check(self.lib.s2m_session_info_of(self.h, C.byref(out)), "s2m_session_info_of")
+        return out
+
+    def session_save(self, write=None) -> bytes | None:
+        """s2m_session_save: the session blob as bytes, or, with `write` (a callable taking each chunk as bytes, in stream
+        order; an exception or a true return value fails the save), nothing."""
+        parts = []
+
+        def cb(_user, data, n):
+            try:
+                chunk = C.string_at(data, n)
+                if write is None:
+                    parts.append(chunk)
+                    return 0
+                return 1 if write(chunk) else 0
+            except Exception:                           # (no exception crosses the C boundary)
+                return 1
+        self._check(self.lib.s2m_session_save(self.h, SESSION_WRITE_FN(cb), None), "s2m_session_save")
+        return b"".join(parts) if write is None else None
+
+    def session_load(self, blob=None, read=None) -> SessionInfo:
+        """s2m_session_load into this handle, whose stores and pose graph must be empty: from `blob` (bytes), or from `read`,
+        a callable (n) -> n bytes in stream order (fewer bytes, an exception or None fail the load). A blob that ends
+        early is S2M_ERR_FORMAT."""
+        buf = (C.c_char * max(len(blob), 1)).from_buffer_copy(bytes(blob) or b"\0") if blob is not None else None
+        at = [0]
+
+        def cb(_user, data, n):
+            try:
+                if buf is not None:
+                    if at[0] + n > len(blob):
+                        return S2M_ERR_FORMAT            # the stream has ended
+                    C.memmove(data, C.addressof(buf) + at[0], n)
+                    at[0] += n
+                    return 0
+                chunk = read(n)
+                if chunk is None or len(chunk) != n:
+                    return 1
+                C.memmove(data, bytes(chunk), n)
+                return 0
+            except Exception:
+                return 1
+        out = SessionInfo()
+        self._check(self.lib.s2m_session_load(self.h, SESSION_READ_FN(cb), None, C.byref(out)), "s2m_session_load")
+        return out
+
+    def session_save_file(self, path: str):
+        self._check(self.lib.s2m_session_save_file(self.h, os.fsencode(path)), "s2m_session_save_file")
+
+    def session_load_file(self, path: str) -> SessionInfo:
+        out = SessionInfo()
+        self._check(self.lib.s2m_session_load_file(self.h, os.fsencode(path), C.byref(out)), "s2m_session_load_file")
+        return out
+
+    def sessionChunk(self, chunk_bytes: int):
+        """s2m_debug_session_chunk: the staging chunk of session_save / session_load (0: the default)."""
+        self._check(self.lib.s2m_debug_session_chunk(self.h, chunk_bytes), "s2m_debug_session_chunk")
+
+    def scKeys(self, first: int = 0, count: int | None = None):
+        """s2m_debug_sc_keys: (ring keys (count, 20) float32, sector keys (count, 60) float64) as the store holds them."""
+        if count is None:
+            count = self.scSize() - first
+        ring, sector = np.zeros((max(count, 0), 20), np.float32), np.zeros((max(count, 0), 60), np.float64)
+        self._check(self.lib.s2m_debug_sc_keys(self.h, first, count, _fp(ring), _dp(sector)), "s2m_debug_sc_keys")
+        return ring, sector
+
+    def kfFrame(self, key: int):
+        """s2m_debug_kf_frame: (T of the host mirror, T of the device's frame table, device position, device point count)."""
+        th, td, pos, n = np.zeros(12, np.float32), np.zeros(12, np.float32), np.zeros(4, np.float32), C.c_int32(0)
+        self._check(self.lib.s2m_debug_kf_frame(self.h, key, _fp(th), _fp(td), _fp(pos), C.byref(n)), "s2m_debug_kf_frame")
+        return th, td, pos, n.value
 
     # -- the pose graph beside the store (reference :1386-1534, :1611-1642) --------
     def pgReset(self):
