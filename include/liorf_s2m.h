@@ -657,6 +657,45 @@ int  s2m_sc_query_scan      (s2m_handle h, const void* pts, size_t n, size_t str
                              s2m_sc_hit* hits, int32_t* n_hits);
 int  s2m_sc_query_projected (s2m_handle h, const s2m_sc_query_params* p, s2m_sc_hit* hits, int32_t* n_hits);
 
+/* ---- The place query for many queries at once ----------------------------------------
+ * "Which pairs of keys of this session are the same place?" and "which keys of this session are places of that
+ * other session?": m queries - stored keys, or descriptors from elsewhere - against the store in one call, as a
+ * tiled all-pairs problem on the device instead of m single queries.
+ *
+ * Rows. Row i is hits[i * top_k ..]; its first n_hits[i] records are valid, the records behind them are left as
+ * the caller had them. Row i is bit for bit what s2m_sc_query_key(keys[i]) or s2m_sc_query_descriptor(descs +
+ * 1200 * i) returns for the same searched set: dist, key, shift, yaw_diff_rad, reserved = 0, in the same
+ * (dist, key) order, with the same 10000000 / NaN rule. keys may repeat and come in any order.
+ * Searched set. Per query exactly the single query's set (q: range, fixed window), and for a stored-key query
+ * ALSO without the keys c with keys[i] + rel_lo <= c < keys[i] + rel_hi (sums in 64 bits; rel_lo >= rel_hi:
+ * no relative window). The detector's exclusion, "nothing from the 30 most recent keys on", is rel_lo = -29,
+ * rel_hi = INT32_MAX: key i is compared with the keys 0 .. i-30. A descriptor has no key to be relative to: a
+ * non-empty relative window on s2m_sc_query_descriptors is an error.
+ * Read-only, exactly as the single query: the store, s2m_sc_size, the detector's counter and its searched set
+ * are untouched; the calls work beside a pending closure, verification or optimise and run on the handle's main
+ * stream. The queries go through in passes whose lists, staged queries and rows take at most 64 MiB of device
+ * memory whatever m and N are; a call synchronises once per pass, never once per query.
+ * s2m_sc_get_descriptors copies the stored descriptors first .. first+count-1 out, bit for bit what was added
+ * (20x60 row-major doubles each): what a node needs to carry one session's descriptors to another handle.
+ * Errors. S2M_ERR_INVALID_ARG: what the single query rejects; m < 0; null keys / descs / outputs with m > 0; a
+ * key outside [0, N); a non-empty relative window on a descriptor query; a range of s2m_sc_get_descriptors
+ * outside the store. S2M_OK: m == 0 writes nothing; an empty store or an empty set gives n_hits[i] = 0.
+ * p == NULL means the defaults. */
+typedef struct s2m_sc_query_many_params {
+    s2m_sc_query_params q;   /* range, fixed window, top_k, align, max_dist: per query exactly as in the single query */
+    int32_t rel_lo, rel_hi;  /* stored-key queries: ALSO leave out c with key + rel_lo <= c < key + rel_hi
+                                (sums in 64 bits); rel_lo >= rel_hi: none */
+} s2m_sc_query_many_params;
+
+int  s2m_sc_query_many_default_params(s2m_sc_query_many_params* p);   /* single-query defaults, rel 0, 0 */
+/* The argument table above for a store of n_stored keys and m queries: S2M_OK or S2M_ERR_INVALID_ARG. Host only. */
+int  s2m_sc_query_many_check_args(int32_t n_stored, int32_t m, const s2m_sc_query_many_params* p, int32_t descriptor_query);
+int  s2m_sc_query_keys(s2m_handle h, const int32_t* keys, int32_t m, const s2m_sc_query_many_params* p,
+                       s2m_sc_hit* hits /* m * top_k */, int32_t* n_hits /* m */);
+int  s2m_sc_query_descriptors(s2m_handle h, const double* descs /* m * 1200, row-major as s2m_sc_add_descriptor */, int32_t m,
+                              const s2m_sc_query_many_params* p, s2m_sc_hit* hits, int32_t* n_hits);
+int  s2m_sc_get_descriptors(s2m_handle h, int32_t first, int32_t count, double* descs /* count * 1200 */);
+
 /* ---- ICP loop-closure alignment ------------------------------------------
  * pcl::IterativeClosestPoint<PointType, PointType> as performRSLoopClosure / performSCLoopClosure configure
  * and run it (reference src/mapOptmization.cpp:571-586, :663-678): setMaxCorrespondenceDistance,

@@ -284,6 +284,16 @@ int  s2m_debug_session_chunk(s2m_handle h, size_t chunk_bytes);
 int  s2m_debug_sc_keys(s2m_handle h, int32_t first, int32_t count, float* ring, double* sector);
 int  s2m_debug_kf_frame(s2m_handle h, int32_t key, float T_host[12], float T_device[12], float pos_device[4], int32_t* n_device);
 
+/* ---- the many-query form of the place query: its passes and the shape of its kernel ----
+ * s2m_debug_sc_query_many_pass: at most this many queries per pass of s2m_sc_query_keys / _descriptors (0 restores the
+ *   default, as many as the 64 MiB scratch bound allows). The rows do not depend on it.
+ * s2m_debug_sc_query_many_shape: the stored descriptors a workgroup of k_sc_many_dist holds in LDS (tile_cands) and the
+ *   queries it walks past them (block_queries), so that tests can place their sizes at the kernel's edges.
+ * s2m_debug_sc_query_many_last: the passes of the handle's last many-query and the device bytes one of them used. */
+int  s2m_debug_sc_query_many_pass(s2m_handle h, int32_t queries_per_pass);
+int  s2m_debug_sc_query_many_shape(int32_t* tile_cands, int32_t* block_queries);
+int  s2m_debug_sc_query_many_last(s2m_handle h, int32_t* passes, size_t* scratch_bytes);
+
 #ifdef __cplusplus
 }
 #endif

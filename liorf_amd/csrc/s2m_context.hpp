@@ -177,6 +177,14 @@ struct __attribute__((visibility("hidden"))) s2m_context {
         DevBuf bins, out;
         DevBuf store_desc, store_ring, store_sector, cand;
         DevBuf query, query_part;
+        // the many-query's pass (s2m_sc_many.hpp): the queries' keys or descriptors + sector keys, their column norms, the
+        // (query, tile group) lists, the rows; together at most kScManyScratchMax.  h_many: pinned, the pass's upload | rows
+        DevBuf many_in, many_qnorm, many_part, many_out;
+        unsigned char* h_many = nullptr;
+        size_t h_many_cap = 0;
+        int    many_pass = 0;              // queries per pass; 0: as many as the scratch bound allows (s2m_debug_sc_query_many_pass)
+        int    many_last_passes = 0;       // of the last many-query: its passes and the device bytes of one pass
+        size_t many_last_scratch = 0;
         size_t n = 0, cap = 0, n_search = 0;
         int    counter = 0;                // tree_making_period_conter (include/Scancontext.cpp:270-283)
         double* h_stage = nullptr;         // pinned [1200 + 20]: descriptor + ring key, or the detection's result, or the query's hits

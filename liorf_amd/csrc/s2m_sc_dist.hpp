@@ -1,6 +1,8 @@
-// s2m_sc_dist.hpp — distanceBtnScanContext (reference include/Scancontext.cpp:116-148) by one workgroup, shared by the detector
-// and batched distance (s2m_sc.hip) and by the place query (s2m_sc_query.hip).  Compiled with -ffp-contract=off; all sums
-// run left to right in fp64 like the oracle's restatement, so distances are bit-identical to it.
+// s2m_sc_dist.hpp — the distance of two ScanContext descriptors: the arithmetic of a pair as device functions of one thread's
+// share each, called by every kernel that compares descriptors, and distanceBtnScanContext (reference
+// include/Scancontext.cpp:116-148) by one workgroup, shared by the detector and batched distance (s2m_sc.hip) and by the place
+// query (s2m_sc_query.hip).  Compiled with -ffp-contract=off; all sums run left to right in fp64 like the oracle's restatement,
+// so distances are bit-identical to it.
 #pragma once
 #include <hip/hip_runtime.h>
 #include "../../include/liorf_s2m.h"
@@ -20,6 +22,93 @@ struct ScShared {
     double dist_out;                                     // the result: distance and the shift it was found at
     int    shift_out;
 };
+
+// ---- the arithmetic of one descriptor pair, stated once ----------------------------------------------------------------
+// Every kernel that compares two descriptors - the detector and the batched distance (s2m_sc.hip), the place query
+// (s2m_sc_query.hip) and the many-query (s2m_sc_many.hip) - calls these, so they agree bit for bit however the pairs are cut
+// over threads.  Each function is one thread's work and each sum runs left to right in fp64.
+
+// ||column||: at(r) is the column's value in ring r.  It does not depend on the shift the column is paired with.
+template <typename At>
+__device__ __forceinline__ double sc_col_norm(At at)
+{
+    double n = 0.0;
+#pragma unroll
+    for (int r = 0; r < S2M_SC_NUM_RING; r++) { const double b = at(r); n += b * b; }
+    return sqrt(n);
+}
+
+// the 20-term dot product of two columns (distDirectSC, :69-91)
+template <typename A, typename B>
+__device__ __forceinline__ double sc_col_dot(A a, B b)
+{
+    double dot = 0.0;
+#pragma unroll
+    for (int r = 0; r < S2M_SC_NUM_RING; r++) dot += a(r) * b(r);
+    return dot;
+}
+
+// a sector pair counts when both columns are non-empty; its cosine similarity
+__device__ __forceinline__ bool sc_sector_sim(double dot, double n1, double n2, double* sim)
+{
+    const bool skip = (n1 == 0) | (n2 == 0);
+    *sim = skip ? 0.0 : dot / (n1 * n2);
+    return !skip;
+}
+
+// 1 - mean of the similarities of the sectors that count, sectors ascending.  No branch and no select on the sum's chain: a
+// sector that does not count holds sim = +0.0 (sc_sector_sim), and sum + 0.0 is sum bit for bit - the sum starts at +0.0 and a
+// sum in round-to-nearest is -0.0 only when both terms are, so it never is -0.0; a NaN or an infinity stays what it is - so
+// adding every sector is the reference's "add the sectors that count".  0/0 = NaN when no sector counts: never a minimum.
+template <typename Eff, typename Sim>
+__device__ __forceinline__ double sc_sector_sum_dist(Eff eff, Sim sim)
+{
+    int num_eff = 0;
+    double sum = 0;
+#pragma unroll 20
+    for (int j = 0; j < S2M_SC_NUM_SECTOR; j++) {
+        sum = sum + sim(j);
+        num_eff += eff(j) ? 1 : 0;
+    }
+    return 1.0 - sum / (double)num_eff;
+}
+
+// the strict minimum over shifts visited in ascending order, from 10000000 / shift 0
+__device__ __forceinline__ void sc_min_update(double d, int shift, double* best, int* best_shift)
+{
+    if (d < *best) { *best = d; *best_shift = shift; }
+}
+
+// fastAlignUsingVkey (:94-113), one shift: ||vkey1 - circshift(vkey2, s)||
+template <typename V1, typename V2>
+__device__ __forceinline__ double sc_vkey_shift_norm(V1 v1, V2 v2, int s)
+{
+    double a = 0.0;
+    for (int j = 0; j < S2M_SC_NUM_SECTOR; j++) {
+        int j2 = j - s; j2 += (j2 < 0) ? S2M_SC_NUM_SECTOR : 0;
+        const double d = v1(j) - v2(j2);
+        a += d * d;
+    }
+    return sqrt(a);
+}
+
+// ... its argmin a0 (strict, ascending) and the search space a0, a0 +- 1..3 (mod 60), sorted ascending (:122-129)
+template <typename Vn>
+__device__ __forceinline__ void sc_search_shifts(Vn vnorm, int (&sp)[kScShifts])
+{
+    constexpr int NS = S2M_SC_NUM_SECTOR;
+    int a0 = 0;
+    double best = 10000000;
+    for (int s = 0; s < NS; s++) sc_min_update(vnorm(s), s, &best, &a0);
+    sp[0] = a0;
+    for (int ii = 1; ii <= (kScShifts - 1) / 2; ii++) { sp[2 * ii - 1] = (a0 + ii + NS) % NS; sp[2 * ii] = (a0 - ii + NS) % NS; }
+    for (int a = 1; a < kScShifts; a++) {            // insertion sort
+        const int v = sp[a];
+        int b = a - 1;
+        while (b >= 0 && sp[b] > v) { sp[b + 1] = sp[b]; b--; }
+        sp[b + 1] = v;
+    }
+}
 
 // distanceBtnScanContext(query, cand[c]) (:116-148) for NC candidates side by side by one workgroup: every phase of the
 // reference's function is spread over (candidate, shift) or (candidate, shift, sector) tasks, every sum is taken by one thread
@@ -41,30 +130,13 @@ __device__ __forceinline__ void sc_distance_block(const double* __restrict__ sto
     __syncthreads();
     for (int task = t; task < NC * NS; task += kScThreads) {              // fastAlignUsingVkey (:94-113), one shift per task
         const int c = task / NS, s = task - c * NS;
-        double a = 0.0;
-        for (int j = 0; j < NS; j++) {
-            int j2 = j - s; j2 += (j2 < 0) ? NS : 0;
-            const double d = sh[c].v1[j] - sh[c].v2[j2];
-            a += d * d;
-        }
-        sh[c].vnorm[s] = sqrt(a);
+        sh[c].vnorm[s] = sc_vkey_shift_norm([&](int j) { return sh[c].v1[j]; }, [&](int j) { return sh[c].v2[j]; }, s);
     }
     __syncthreads();
     if (t < NC) {
         ScShared& m = sh[t];
-        int a0 = 0;
-        double best = 10000000;
-        for (int s = 0; s < NS; s++) if (m.vnorm[s] < best) { a0 = s; best = m.vnorm[s]; }
-        // search space a0, a0 +- 1..3 (mod 60), ascending (:122-129)
         int sp[kScShifts];
-        sp[0] = a0;
-        for (int ii = 1; ii <= (kScShifts - 1) / 2; ii++) { sp[2 * ii - 1] = (a0 + ii + NS) % NS; sp[2 * ii] = (a0 - ii + NS) % NS; }
-        for (int a = 1; a < kScShifts; a++) {            // insertion sort
-            const int v = sp[a];
-            int b = a - 1;
-            while (b >= 0 && sp[b] > v) { sp[b + 1] = sp[b]; b--; }
-            sp[b + 1] = v;
-        }
+        sc_search_shifts([&](int s) { return m.vnorm[s]; }, sp);
         for (int k = 0; k < kScShifts; k++) m.shifts[k] = sp[k];
     }
     __syncthreads();
@@ -73,31 +145,21 @@ __device__ __forceinline__ void sc_distance_block(const double* __restrict__ sto
         const int k = rem / NS, j = rem - k * NS;
         int j2 = j - sh[c].shifts[k]; j2 += (j2 < 0) ? NS : 0;            // circshift (:39-59)
         const double* __restrict__ sc2 = store_desc + (size_t)cand[c] * NR * NS;
-        double n1 = 0.0, n2 = 0.0, dot = 0.0;
-#pragma unroll
-        for (int r = 0; r < NR; r++) {
-            const double a = sc1[r * NS + j], b = sc2[r * NS + j2];
-            n1 += a * a; n2 += b * b; dot += a * b;
-        }
-        n1 = sqrt(n1); n2 = sqrt(n2);
-        const bool skip = (n1 == 0) | (n2 == 0);
-        sh[c].eff[k][j] = skip ? 0 : 1;
-        sh[c].sim[k][j] = skip ? 0.0 : dot / (n1 * n2);
+        const auto a = [&](int r) { return sc1[r * NS + j]; };
+        const auto b = [&](int r) { return sc2[r * NS + j2]; };
+        sh[c].eff[k][j] = sc_sector_sim(sc_col_dot(a, b), sc_col_norm(a), sc_col_norm(b), &sh[c].sim[k][j]) ? 1 : 0;
     }
     __syncthreads();
     if (t < NC * kScShifts) {
         const int c = t / kScShifts, k = t - c * kScShifts;
-        int num_eff = 0;
-        double sum = 0;
-        for (int j = 0; j < NS; j++) if (sh[c].eff[k][j]) { sum = sum + sh[c].sim[k][j]; num_eff = num_eff + 1; }
-        sh[c].dist[k] = 1.0 - sum / (double)num_eff;      // 0/0 = NaN when no sector counts, as in the reference
+        sh[c].dist[k] = sc_sector_sum_dist([&](int j) { return sh[c].eff[k][j] != 0; }, [&](int j) { return sh[c].sim[k][j]; });
     }
     __syncthreads();
     if (t < NC) {
         ScShared& m = sh[t];
         int argmin_shift = 0;
         double min_sc_dist = 10000000;
-        for (int k = 0; k < kScShifts; k++) if (m.dist[k] < min_sc_dist) { argmin_shift = m.shifts[k]; min_sc_dist = m.dist[k]; }
+        for (int k = 0; k < kScShifts; k++) sc_min_update(m.dist[k], m.shifts[k], &min_sc_dist, &argmin_shift);
         m.dist_out = min_sc_dist; m.shift_out = argmin_shift;
     }
     __syncthreads();

@@ -10,6 +10,7 @@
 #include <type_traits>
 
 #include "s2m_sc_dist.hpp"
+#include "s2m_sc_keys.hpp"
 #include "s2m_sc_query.hpp"
 
 namespace s2m {
@@ -30,14 +31,8 @@ __global__ __launch_bounds__(kScThreads) void k_sc_query_prepare(const double* s
 {
     const int t = threadIdx.x;
     if (t < NS) {
-        double key;
-        if (src_sector) key = src_sector[t];
-        else {                                                             // makeSectorkeyFromScancontext (:214-227) as k_sc_append
-            double a = 0.0;
-            for (int r = 0; r < NR; r++) a += src_desc[r * NS + t];
-            key = a / (double)NR;
-        }
-        slot[ND + t] = key;
+        // makeSectorkeyFromScancontext (:214-227) as k_sc_append
+        slot[ND + t] = src_sector ? src_sector[t] : sc_sector_key([&](int r) { return src_desc[r * NS + t]; });
     }
     if (src_desc != slot)
         for (int k = t; k < ND; k += kScThreads) slot[k] = src_desc[k];
@@ -72,10 +67,7 @@ __device__ __forceinline__ void sc_full_block(const double* __restrict__ store_d
     __syncthreads();
     for (int task = t; task < kScQueryCands * NS; task += kScThreads) {
         const int c = task / NS, jc = task - c * NS;
-        double n2 = 0.0;
-#pragma unroll
-        for (int r = 0; r < NR; r++) { const double b = m.c[c][r * NS + jc]; n2 += b * b; }
-        m.cnorm[c][jc] = sqrt(n2);
+        m.cnorm[c][jc] = sc_col_norm([&](int r) { return m.c[c][r * NS + jc]; });
     }
     __syncthreads();
     for (int s0 = 0; s0 < NS; s0 += kScFullChunk) {
@@ -84,33 +76,20 @@ __device__ __forceinline__ void sc_full_block(const double* __restrict__ store_d
                 int j2 = j - (s0 + k); j2 += (j2 < 0) ? NS : 0;            // circshift (:39-59)
 #pragma unroll
                 for (int c = 0; c < kScQueryCands; c++) {
-                    double dot = 0.0;
-#pragma unroll
-                    for (int r = 0; r < NR; r++) dot += qcol[r] * m.c[c][r * NS + j2];
-                    const double n2 = m.cnorm[c][j2];
-                    const bool skip = (n1 == 0) | (n2 == 0);
-                    m.eff[c][k][j] = skip ? 0 : 1;
-                    m.sim[c][k][j] = skip ? 0.0 : dot / (n1 * n2);
+                    const double dot = sc_col_dot([&](int r) { return qcol[r]; }, [&](int r) { return m.c[c][r * NS + j2]; });
+                    m.eff[c][k][j] = sc_sector_sim(dot, n1, m.cnorm[c][j2], &m.sim[c][k][j]) ? 1 : 0;
                 }
             }
         }
         __syncthreads();
         if (t < kScQueryCands * kScFullChunk) {
             const int c = t / kScFullChunk, k = t - c * kScFullChunk;
-            int num_eff = 0;
-            double sum = 0;
-#pragma unroll 20
-            for (int jj = 0; jj < NS; jj++) {             // (a select, not a branch: the loads do not wait for the sum)
-                const bool e = m.eff[c][k][jj] != 0;
-                const double v = sum + m.sim[c][k][jj];
-                sum = e ? v : sum; num_eff += e ? 1 : 0;
-            }
-            m.dist[c][k] = 1.0 - sum / (double)num_eff;   // 0/0 = NaN when no sector counts: never the minimum
+            m.dist[c][k] = sc_sector_sum_dist([&](int jj) { return m.eff[c][k][jj] != 0; }, [&](int jj) { return m.sim[c][k][jj]; });
         }
         __syncthreads();
         if (t < kScQueryCands)
             for (int k = 0; k < kScFullChunk; k++)
-                if (m.dist[t][k] < m.dist_out[t]) { m.dist_out[t] = m.dist[t][k]; m.shift_out[t] = s0 + k; }
+                sc_min_update(m.dist[t][k], s0 + k, &m.dist_out[t], &m.shift_out[t]);
         // (the next chunk writes sim / eff only; dist is written again behind its barrier)
     }
     __syncthreads();
@@ -132,8 +111,8 @@ __global__ __launch_bounds__(kScThreads) void k_sc_query_dist(const double* __re
     if constexpr (ALIGN == S2M_SC_ALIGN_FULL) {
         const int j = t % NS;
 #pragma unroll
-        for (int r = 0; r < NR; r++) { qcol[r] = slot[r * NS + j]; n1 += qcol[r] * qcol[r]; }
-        n1 = sqrt(n1);
+        for (int r = 0; r < NR; r++) qcol[r] = slot[r * NS + j];
+        n1 = sc_col_norm([&](int r) { return qcol[r]; });
     } else {
         for (int k = t; k < (ND + NS) / 2; k += kScThreads) {
             const double2 v = reinterpret_cast<const double2*>(slot)[k];

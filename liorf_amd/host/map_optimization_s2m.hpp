@@ -656,6 +656,50 @@ public:
         return loopVerify(key_cur, cand, 0);
     }
 
+    // The place query for many queries at once (s2m_sc_query_keys / _descriptors): row i holds the hits of query i, each row what
+    // s2m_sc_query_key / _descriptor returns for the same searched set. p.rel_lo / rel_hi leave out a window around each key.
+    std::vector<std::vector<s2m_sc_hit>> scQueryKeys(const std::vector<int32_t>& keys, const s2m_sc_query_many_params& p)
+    {
+        std::vector<s2m_sc_hit> hits(keys.size() * (size_t)(p.q.top_k > 0 ? p.q.top_k : 0));
+        std::vector<int32_t> n(keys.size(), 0);
+        check(s2m_sc_query_keys(h_, keys.data(), (int32_t)keys.size(), &p, hits.data(), n.data()), "s2m_sc_query_keys");
+        return scRows(hits, n, p.q.top_k);
+    }
+    // descs: m x 1200 doubles, row-major as s2m_sc_add_descriptor takes them
+    std::vector<std::vector<s2m_sc_hit>> scQueryDescriptors(const std::vector<double>& descs, const s2m_sc_query_many_params& p)
+    {
+        const size_t m = descs.size() / (S2M_SC_NUM_RING * S2M_SC_NUM_SECTOR);
+        std::vector<s2m_sc_hit> hits(m * (size_t)(p.q.top_k > 0 ? p.q.top_k : 0));
+        std::vector<int32_t> n(m, 0);
+        check(s2m_sc_query_descriptors(h_, descs.data(), (int32_t)m, &p, hits.data(), n.data()), "s2m_sc_query_descriptors");
+        return scRows(hits, n, p.q.top_k);
+    }
+    // the stored descriptors first .. first+count-1, bit for bit what was added
+    std::vector<double> scGetDescriptors(int32_t first, int32_t count)
+    {
+        std::vector<double> descs((size_t)(count > 0 ? count : 0) * S2M_SC_NUM_RING * S2M_SC_NUM_SECTOR);
+        check(s2m_sc_get_descriptors(h_, first, count, descs.data()), "s2m_sc_get_descriptors");
+        return descs;
+    }
+    // Loop discovery over a whole session (after a load, say): every stored key against the keys at least `gap` before it. The
+    // candidates come in key_cur order, per key by (dist, key_pre); a node hands each key_cur's to loopVerify.
+    struct SessionLoop { int32_t key_cur, key_pre; double dist; float yaw; };
+    std::vector<SessionLoop> findSessionLoops(int gap, double max_dist, int top_k, int align)
+    {
+        s2m_sc_query_many_params p;
+        s2m_sc_query_many_default_params(&p);
+        p.q.top_k = top_k; p.q.align = align; p.q.max_dist = max_dist;
+        p.rel_lo = 1 - gap; p.rel_hi = INT32_MAX;
+        const int n_keys = s2m_sc_size(h_);
+        std::vector<int32_t> keys((size_t)(n_keys > 0 ? n_keys : 0));
+        for (size_t k = 0; k < keys.size(); k++) keys[k] = (int32_t)k;
+        std::vector<SessionLoop> out;
+        const std::vector<std::vector<s2m_sc_hit>> rows = scQueryKeys(keys, p);
+        for (size_t k = 0; k < rows.size(); k++)
+            for (const s2m_sc_hit& hit : rows[k]) out.push_back(SessionLoop{ (int32_t)k, hit.key, hit.dist, hit.yaw_diff_rad });
+        return out;
+    }
+
     // void performSCLoopClosure() (:624-730): the ScanContext detector on this handle, then the store's extraction and ICP
     inline bool performSCLoopClosure(SCManagerS2M& scManager);
 
@@ -674,6 +718,12 @@ public:
     s2m_handle handle() const { return h_; }
 
 private:
+    static std::vector<std::vector<s2m_sc_hit>> scRows(const std::vector<s2m_sc_hit>& hits, const std::vector<int32_t>& n, int top_k)
+    {
+        std::vector<std::vector<s2m_sc_hit>> rows(n.size());
+        for (size_t i = 0; i < n.size(); i++) rows[i].assign(hits.begin() + i * (size_t)top_k, hits.begin() + i * (size_t)top_k + n[i]);
+        return rows;
+    }
     bool accepted()
     {
         if (lastLoop.status != S2M_LOOP_ACCEPTED) return false;

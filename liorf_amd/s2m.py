@@ -41,6 +41,8 @@ ABI_SYMBOLS = [
     "s2m_debug_lm_close", "s2m_debug_lm_close_check_args", "s2m_debug_lm_rows", "s2m_debug_lm_rows_check_args",
     "s2m_sc_reset", "s2m_sc_size", "s2m_sc_add_scan", "s2m_sc_add_descriptor", "s2m_sc_detect_loop", "s2m_sc_distance",
     "s2m_sc_query_default_params", "s2m_sc_query_check_args", "s2m_sc_query_key", "s2m_sc_query_descriptor", "s2m_sc_query_scan", "s2m_sc_query_projected",
+    "s2m_sc_query_many_default_params", "s2m_sc_query_many_check_args", "s2m_sc_query_keys", "s2m_sc_query_descriptors", "s2m_sc_get_descriptors",
+    "s2m_debug_sc_query_many_pass", "s2m_debug_sc_query_many_shape", "s2m_debug_sc_query_many_last",
     "s2m_kf_default_params", "s2m_kf_reset", "s2m_kf_size", "s2m_kf_add", "s2m_kf_set_poses", "s2m_extract_surrounding",
     "s2m_extract_surrounding_at",
     "s2m_loop_default_params", "s2m_loop_near_keyframes", "s2m_loop_align", "s2m_loop_closure_rs",
@@ -133,6 +135,12 @@ class ScQueryParams(C.Structure):
     """s2m_sc_query_params: the searched keys [first, first+count) (count = -1: to the end) outside [exclude_lo, exclude_hi)."""
     _fields_ = [("first", C.c_int32), ("count", C.c_int32), ("exclude_lo", C.c_int32), ("exclude_hi", C.c_int32),
                 ("top_k", C.c_int32), ("align", C.c_int32), ("max_dist", C.c_double)]
+
+
+class ScQueryManyParams(C.Structure):
+    """s2m_sc_query_many_params: the single query's parameters per query, and for stored-key queries the relative window
+    [key + rel_lo, key + rel_hi) that is left out as well."""
+    _fields_ = [("q", ScQueryParams), ("rel_lo", C.c_int32), ("rel_hi", C.c_int32)]
 
 
 class ScHit(C.Structure):
@@ -359,6 +367,15 @@ def load_library(path: str | None = None) -> C.CDLL:
     L.s2m_sc_query_descriptor.argtypes = [vp, dp, qp, hp, i32p]
     L.s2m_sc_query_scan.argtypes = [vp, vp, C.c_size_t, C.c_size_t, qp, hp, i32p]
     L.s2m_sc_query_projected.argtypes = [vp, qp, hp, i32p]
+    mp = C.POINTER(ScQueryManyParams)
+    L.s2m_sc_query_many_default_params.argtypes = [mp]
+    L.s2m_sc_query_many_check_args.argtypes = [C.c_int32, C.c_int32, mp, C.c_int32]
+    L.s2m_sc_query_keys.argtypes = [vp, i32p, C.c_int32, mp, hp, i32p]
+    L.s2m_sc_query_descriptors.argtypes = [vp, dp, C.c_int32, mp, hp, i32p]
+    L.s2m_sc_get_descriptors.argtypes = [vp, C.c_int32, C.c_int32, dp]
+    L.s2m_debug_sc_query_many_pass.argtypes = [vp, C.c_int32]
+    L.s2m_debug_sc_query_many_shape.argtypes = [i32p, i32p]
+    L.s2m_debug_sc_query_many_last.argtypes = [vp, i32p, C.POINTER(C.c_size_t)]
     L.s2m_kf_default_params.argtypes = [C.POINTER(KfParams)]
     L.s2m_kf_reset.argtypes = [vp]
     L.s2m_kf_size.argtypes = [vp]
@@ -1032,6 +1049,55 @@ class MapOptimizationS2M:
     def scQueryProjected(self, params: "ScQueryParams | None" = None, **kw):
         """The query with the descriptor of the cloud s2m_project_scan left on the device."""
         return self._sc_query(self.lib.s2m_sc_query_projected, "s2m_sc_query_projected", (), params, kw)
+
+    # -- the place query for many queries at once (DESIGN.md section 20)
+    def _sc_query_many(self, fn, what, arg, m, params, kw):
+        p = params if params is not None else default_sc_query_many_params()
+        if kw:
+            p = default_sc_query_many_params(**{**_sc_many_fields(p), **kw})
+        k = max(int(p.q.top_k), 1)
+        hits = np.zeros((max(m, 1), k), SC_HIT_DTYPE)
+        n = np.zeros(max(m, 1), np.int32)
+        self._check(fn(self.h, arg, m, C.byref(p), hits.ctypes.data_as(C.POINTER(ScHit)), n.ctypes.data_as(C.POINTER(C.c_int32))), what)
+        return [hits[i, :n[i]].copy() for i in range(m)]
+
+    def scQueryKeys(self, keys, params: "ScQueryManyParams | None" = None, **kw):
+        """s2m_sc_query_keys: for every stored key of `keys` its hits (SC_HIT_DTYPE records, ascending (dist, key)), each row what
+        scQueryKey returns for the same searched set.  Keyword arguments set fields of the single query's parameters, and
+        rel_lo / rel_hi the window around each query's own key that is left out as well."""
+        k = np.ascontiguousarray(keys, np.int32).reshape(-1)
+        return self._sc_query_many(self.lib.s2m_sc_query_keys, "s2m_sc_query_keys", k.ctypes.data_as(C.POINTER(C.c_int32)), len(k), params, kw)
+
+    def scQueryDescriptors(self, descs, params: "ScQueryManyParams | None" = None, **kw):
+        """s2m_sc_query_descriptors: the same for descriptors from elsewhere, (m, 20, 60) doubles."""
+        d = np.ascontiguousarray(descs, np.float64).reshape(-1, 20, 60)
+        return self._sc_query_many(self.lib.s2m_sc_query_descriptors, "s2m_sc_query_descriptors", d.ctypes.data_as(C.POINTER(C.c_double)), len(d),
+                                   params, kw)
+
+    def scGetDescriptors(self, first: int = 0, count: "int | None" = None):
+        """s2m_sc_get_descriptors: the stored descriptors first .. first+count-1 as (count, 20, 60) doubles, bit for bit what was added."""
+        if count is None:
+            count = self.scSize() - first
+        out = np.zeros((max(count, 0), 20, 60), np.float64)
+        self._check(self.lib.s2m_sc_get_descriptors(self.h, first, count, out.ctypes.data_as(C.POINTER(C.c_double))), "s2m_sc_get_descriptors")
+        return out
+
+    def findSessionLoops(self, gap: int = 30, max_dist: float = 0.3, top_k: int = 1, align: int = S2M_SC_ALIGN_FULL):
+        """Every stored key against the keys at least `gap` before it: the (key_cur, key_pre, dist, yaw_diff_rad) candidates a node
+        hands to loopVerify, in key_cur order and per key in (dist, key_pre) order."""
+        n = self.scSize()
+        rows = self.scQueryKeys(np.arange(n, dtype=np.int32), top_k=top_k, align=align, max_dist=max_dist, rel_lo=1 - int(gap), rel_hi=2**31 - 1)
+        return [(cur, int(h["key"]), float(h["dist"]), float(h["yaw_diff_rad"])) for cur, row in enumerate(rows) for h in row]
+
+    def scQueryManyPass(self, queries_per_pass: int):
+        """s2m_debug_sc_query_many_pass: at most this many queries per pass (0: the default)."""
+        self._check(self.lib.s2m_debug_sc_query_many_pass(self.h, queries_per_pass), "s2m_debug_sc_query_many_pass")
+
+    def scQueryManyLast(self):
+        """s2m_debug_sc_query_many_last: (passes, device bytes of one pass) of the last many-query."""
+        n, b = C.c_int32(0), C.c_size_t(0)
+        self._check(self.lib.s2m_debug_sc_query_many_last(self.h, C.byref(n), C.byref(b)), "s2m_debug_sc_query_many_last")
+        return n.value, b.value
 
     def makeScancontext(self, scan):
         """SCManager::makeScancontext + makeRingkeyFromScancontext (reference include/Scancontext.cpp:151-211)."""
@@ -1740,6 +1806,34 @@ def default_sc_query_params(**kw) -> ScQueryParams:
             raise AttributeError(k)
         setattr(p, k, v)
     return p
+
+
+def _sc_many_fields(p) -> dict:
+    return {**{f: getattr(p.q, f) for f, _ in ScQueryParams._fields_}, "rel_lo": p.rel_lo, "rel_hi": p.rel_hi}
+
+
+def default_sc_query_many_params(**kw) -> ScQueryManyParams:
+    """s2m_sc_query_many_default_params; keyword arguments set rel_lo, rel_hi and the fields of the single query's parameters."""
+    p = ScQueryManyParams()
+    load_library().s2m_sc_query_many_default_params(C.byref(p))
+    for k, v in kw.items():
+        tgt = p if k in ("rel_lo", "rel_hi") else p.q
+        if not hasattr(tgt, k):
+            raise AttributeError(k)
+        setattr(tgt, k, v)
+    return p
+
+
+def sc_query_many_check_args(n_stored: int, m: int, params: "ScQueryManyParams | None", descriptor_query: bool = False) -> int:
+    """s2m_sc_query_many_check_args (host only, no GPU): the status code.  params=None passes a null pointer (the defaults)."""
+    return load_library().s2m_sc_query_many_check_args(n_stored, m, None if params is None else C.byref(params), int(descriptor_query))
+
+
+def sc_query_many_shape():
+    """s2m_debug_sc_query_many_shape: (stored descriptors of a tile, queries of a block) of k_sc_many_dist."""
+    t, b = C.c_int32(0), C.c_int32(0)
+    load_library().s2m_debug_sc_query_many_shape(C.byref(t), C.byref(b))
+    return t.value, b.value
 
 
 def _copy_struct(s):
