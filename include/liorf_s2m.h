@@ -877,6 +877,38 @@ int  s2m_loop_verify_collect(s2m_handle h, s2m_loop_result* out, int32_t cap, in
 int  s2m_loop_verify(s2m_handle h, int32_t key_cur, const int32_t* key_pre, int32_t n_cand, int32_t base_key,
                      const s2m_loop_params* p /* NULL = defaults */, s2m_loop_result* out /* n_cand records */, int32_t* best);
 
+/* ---- Verification of many keys: the candidate rows of s2m_sc_query_keys in one call -------------------------------------
+ * s2m_sc_query_keys names the loop candidates of a whole session; s2m_loop_verify_many verifies them. Row r is key_cur[r]
+ * against key_pre[r * row_stride .. + n_cand[r]), 1 <= row_stride <= S2M_LOOP_MAX_CANDIDATES, 0 <= n_cand[r] <= row_stride:
+ * the shape of that call's hits / n_hits. out (m * row_stride records) and best (m) are laid out alike.
+ *   Contract: records, best[] and the container afterwards are byte for byte what this loop leaves on the same handle:
+ *       for r: if n_cand[r]: s2m_loop_verify(h, key_cur[r], key_pre + r * row_stride, n_cand[r], base_key, p,
+ *                                            out + r * row_stride, &best[r])
+ *       - S2M_LOOP_ALREADY_CLOSED for a key_cur the container held before the call, S2M_LOOP_TOO_FEW_POINTS per candidate
+ *       or per row, the pose result from the store's poses; only each row's winner enters the container. A row with
+ *       n_cand[r] == 0 writes no record and gives best[r] = -1; records behind n_cand[r] are left as the caller had them.
+ *   Passes: consecutive rows are taken while the sum of their n_cand stays within S2M_LOOP_MANY_MAX_PAIRS; a row is never
+ *       split, and the plan depends on the arguments alone. Within a pass the submaps of every row are built by the single
+ *       call's path (one wait each) into buffers that hold them all, then every pair the gates left open is aligned in
+ *       lockstep by the device loop (the pairs' descriptions in a table in device memory, one wait per range of
+ *       iterations), then the rows are judged. The call is synchronous; a caller bounds the time it holds the handle by
+ *       the rows it passes per call. There is no launched form.
+ *   key_cur must be distinct over the rows that have candidates (the rows must not depend on one another's results): a
+ *       repeat is S2M_ERR_INVALID_ARG, and so are m < 0, null arrays with m > 0, row_stride or n_cand[r] out of range and
+ *       everything s2m_loop_verify rejects in a row - all before any device work, with out, best and the container
+ *       untouched. s2m_loop_verify_many_check_args gives the same verdict from the store's size alone (host code).
+ *       m == 0 is S2M_OK and writes nothing; an empty store gives S2M_LOOP_NONE records and best -1.
+ *   S2M_ERR_BUSY, nothing touched, while a launched closure or verification is pending.
+ *   A HIP error in pass k fails the call as s2m_loop_verify fails: the rows of the passes before keep their records and
+ *       their winners stay in the container; the records of pass k and of later rows are S2M_LOOP_NONE with key_cur -1. */
+#define S2M_LOOP_MANY_MAX_PAIRS  64
+int  s2m_loop_verify_many_check_args(int32_t n_stored, const int32_t* key_cur, const int32_t* key_pre, const int32_t* n_cand,
+                                     int32_t m, int32_t row_stride, int32_t base_key, const s2m_loop_params* p);   /* host only */
+int  s2m_loop_verify_many(s2m_handle h, const int32_t* key_cur /* m */, const int32_t* key_pre /* m * row_stride */,
+                          const int32_t* n_cand /* m */, int32_t m, int32_t row_stride, int32_t base_key,
+                          const s2m_loop_params* p /* NULL = defaults */,
+                          s2m_loop_result* out /* m * row_stride */, int32_t* best /* m */);
+
 /* ---- Relocalisation: where in the stored map is this scan, as a pose ------------------------------------------------
  * From a fresh scan (not a key) to a pose in the map frame, so that s2m_extract_surrounding_at and s2m_optimize* can start
  * or recover inside a map the handle already holds. ScanContext key i must be key-frame i (both stores filled in step).

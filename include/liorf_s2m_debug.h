@@ -294,6 +294,22 @@ int  s2m_debug_sc_query_many_pass(s2m_handle h, int32_t queries_per_pass);
 int  s2m_debug_sc_query_many_shape(int32_t* tile_cands, int32_t* block_queries);
 int  s2m_debug_sc_query_many_last(s2m_handle h, int32_t* passes, size_t* scratch_bytes);
 
+/* The table form of the device loop (icp_pairs_begin / icp_pairs_advance): n_pairs <= S2M_LOOP_MANY_MAX_PAIRS host pairs, each
+ * with its own source and target (no size gate) and optionally a guess (guesses: NULL, or n_pairs pointers, each NULL or a
+ * row-major 4x4), aligned in lockstep as s2m_debug_icp_align_many_device aligns the slots of one source. out[k] is bit for bit
+ * s2m_icp_align(srcs[k], tgts[k]) / s2m_icp_align_guess with guesses[k]; a pair with an empty cloud gives that call's result
+ * for it. n_pairs outside 1 .. S2M_LOOP_MANY_MAX_PAIRS is S2M_ERR_INVALID_ARG; S2M_ERR_BUSY while a closure is pending. */
+int  s2m_debug_icp_align_pairs_device(s2m_handle h, const void* const* srcs, const size_t* n_srcs, const void* const* tgts,
+                                      const size_t* n_tgts, int32_t n_pairs, size_t stride_bytes, const float* const* guesses,
+                                      const s2m_icp_params* p, s2m_icp_result* out);
+/* s2m_loop_verify_many: the pairs of a pass for the calls that follow (0: the default, S2M_LOOP_MANY_MAX_PAIRS; other values are
+ * clamped to [S2M_LOOP_MAX_CANDIDATES, S2M_LOOP_MANY_MAX_PAIRS]); what the last call did - its passes, the pairs it aligned, and
+ * the bytes the handle holds for the submaps of a pass; and the plan on its own (host only, no handle): first_row_of_pass takes
+ * *n_pass + 1 <= m + 1 entries, pass k being rows [first_row_of_pass[k], first_row_of_pass[k + 1]). */
+int  s2m_debug_loop_verify_many_pass(s2m_handle h, int32_t pairs_per_pass);
+int  s2m_debug_loop_verify_many_last(s2m_handle h, int32_t* passes, int32_t* pairs_aligned, size_t* bytes);
+int  s2m_debug_loop_verify_many_plan(const int32_t* n_cand, int32_t m, int32_t pairs_per_pass, int32_t* first_row_of_pass, int32_t* n_pass);
+
 #ifdef __cplusplus
 }
 #endif

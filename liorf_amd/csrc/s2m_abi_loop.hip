@@ -6,6 +6,7 @@
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
+#include <vector>
 
 #include "s2m_context.hpp"
 
@@ -535,6 +536,218 @@ int s2m_loop_verify(s2m_handle h, int32_t key_cur, const int32_t* key_pre, int32
     return verify_poll_impl(h, out, n_cand, &n, best, true);
 }
 
+// ---- verification of many keys: the pairs of a pass aligned in lockstep through the pair table ---------------------------
+
+static_assert(S2M_LOOP_MANY_MAX_PAIRS == kIcpMaxPairs, "include/liorf_s2m.h states the pairs of a pass");
+
+namespace {
+
+int many_pairs_per_pass(int32_t asked)
+{
+    return asked <= 0 ? kIcpMaxPairs : std::min(std::max((int)asked, (int)S2M_LOOP_MAX_CANDIDATES), kIcpMaxPairs);
+}
+
+// The plan: consecutive rows while the sum of their n_cand stays within pairs_per_pass, a row never split, a row without
+// candidates taking no room. first[k] .. first[k + 1]: the rows of pass k (first: m + 1 entries at most). A function of the
+// arguments alone: what the gates leave does not enter it.
+int32_t many_plan(const int32_t* n_cand, int32_t m, int pairs_per_pass, int32_t* first)
+{
+    int32_t n_pass = 0, used = 0;
+    for (int32_t r = 0; r < m; r++) {
+        if (r == 0 || used + n_cand[r] > pairs_per_pass) { first[n_pass++] = r; used = 0; }
+        used += n_cand[r];
+    }
+    first[n_pass] = m;
+    return n_pass;
+}
+
+// every check of s2m_loop_verify_many that needs no handle. *empty: the store is empty
+int many_args(s2m_context* h, size_t N, const int32_t* key_cur, const int32_t* key_pre, const int32_t* n_cand, int32_t m, int32_t row_stride,
+              int32_t base_key, const s2m_loop_params* p, s2m_loop_params* prm, bool* empty)
+{
+    *empty = N == 0;
+    if (m < 0) return fail(h, S2M_ERR_INVALID_ARG, "a negative number of rows");
+    if (row_stride < 1 || row_stride > S2M_LOOP_MAX_CANDIDATES)
+        return fail(h, S2M_ERR_INVALID_ARG, "row_stride must be 1 .. S2M_LOOP_MAX_CANDIDATES");
+    int rc = loop_params(h, p, prm);
+    if (rc) return rc;
+    if (m == 0) return S2M_OK;
+    if (!key_cur || !key_pre || !n_cand) return fail(h, S2M_ERR_INVALID_ARG, "null row arrays");
+    for (int32_t r = 0; r < m; r++) {
+        if (n_cand[r] < 0 || n_cand[r] > row_stride) return fail(h, S2M_ERR_INVALID_ARG, "a row has more candidates than row_stride, or fewer than none");
+        if (n_cand[r] == 0) continue;
+        s2m_loop_params row_prm;
+        bool row_empty;
+        if ((rc = verify_args(h, N, key_cur[r], key_pre + (size_t)r * row_stride, n_cand[r], base_key, p, &row_prm, &row_empty))) return rc;
+    }
+    // the rows must not depend on one another's results: key_cur distinct over the rows that have candidates
+    std::vector<int32_t> keys;
+    for (int32_t r = 0; r < m; r++) if (n_cand[r]) keys.push_back(key_cur[r]);
+    std::sort(keys.begin(), keys.end());
+    if (std::adjacent_find(keys.begin(), keys.end()) != keys.end()) return fail(h, S2M_ERR_INVALID_ARG, "a key_cur is named by two rows");
+    return S2M_OK;
+}
+
+// Room for `need` bytes in the arena of a pass, the many_used bytes it holds kept (a larger arena takes them over). stream: the
+// stream the arena is written on.
+int arena_reserve(s2m_context* h, hipStream_t stream, size_t need)
+{
+    s2m_context::LoopClosure& L = h->loop;
+    if (need <= L.many_arena.cap) return S2M_OK;
+    const size_t want = std::max(need + need / 2, (size_t)1 << 20);
+    void* q = nullptr;
+    S2M_HIP(h, hipMalloc(&q, want));
+    hipError_t e = L.many_used ? hipMemcpyAsync(q, L.many_arena.p, L.many_used, hipMemcpyDeviceToDevice, stream) : hipSuccess;
+    if (e == hipSuccess) e = hipStreamSynchronize(stream);
+    if (e != hipSuccess) { (void)hipFree(q); return fail(h, S2M_ERR_HIP, "the submaps of a verification pass", e); }
+    S2M_HIP(h, L.many_arena.reset(q, want));
+    return S2M_OK;
+}
+
+// n records of `src` (a submap as voxel_into left it) to the end of the arena, on the handle's stream; *off: where they start
+int arena_put(s2m_context* h, const DevBuf& src, size_t n, size_t* off)
+{
+    s2m_context::LoopClosure& L = h->loop;
+    const size_t bytes = (n * kDsStride + 255) / 256 * 256;
+    const int rc = arena_reserve(h, h->stream, L.many_used + bytes);
+    if (rc) return rc;
+    *off = L.many_used;
+    S2M_HIP(h, hipMemcpyAsync(L.many_arena.as<unsigned char>() + L.many_used, src.p, n * kDsStride, hipMemcpyDeviceToDevice, h->stream));
+    L.many_used += bytes;
+    return S2M_OK;
+}
+
+// One pass: rows [r0, r1). The gates and submaps of every row by the path of the single call - built where the single call builds
+// them, the filtered records of the pairs the gates left open then copied into the pass's arena, behind the stream's order, before
+// the next row builds over them; one lockstep alignment of those pairs; the judge, the best rule and the container per row.
+int many_pass(s2m_context* h, const int32_t* key_cur, const int32_t* key_pre, const int32_t* n_cand, int32_t r0, int32_t r1, int32_t row_stride,
+              int32_t base_key, const s2m_loop_params& prm, s2m_loop_result* out, int32_t* best)
+{
+    s2m_context::LoopClosure& L = h->loop;
+    const unsigned char *d_src[kIcpMaxPairs], *d_tgt[kIcpMaxPairs];
+    size_t n_src[kIcpMaxPairs], n_tgt[kIcpMaxPairs], off_src[kIcpMaxPairs], off_tgt[kIcpMaxPairs];
+    s2m_loop_result* rec_of[kIcpMaxPairs];
+    int pairs = 0, cands = 0;
+    L.many_used = 0;
+    for (int32_t r = r0; r < r1; r++) {
+        if (!n_cand[r]) continue;
+        if (cands + n_cand[r] > kIcpMaxPairs) return fail(h, S2M_ERR_CAPACITY, "a pass of more than kIcpMaxPairs pairs");   // not reached
+        s2m_loop_result* rec = out + (size_t)r * row_stride;
+        int32_t open;
+        int rc = loop_gates(h, key_cur[r], key_pre + (size_t)r * row_stride, n_cand[r], base_key, prm, rec, &open);
+        if (rc) return rc;
+        size_t row_src = 0;
+        if (open && (rc = arena_put(h, L.cur, (size_t)rec[0].n_cur, &row_src))) return rc;   // (n_cur: the same in every record of the row)
+        for (int32_t i = 0; open && i < n_cand[r]; i++) {
+            if (rec[i].status != S2M_LOOP_NONE) continue;
+            if ((rc = arena_put(h, L.target(i), (size_t)rec[i].n_prev, &off_tgt[pairs]))) return rc;
+            off_src[pairs] = row_src;
+            n_src[pairs] = (size_t)rec[i].n_cur; n_tgt[pairs] = (size_t)rec[i].n_prev;
+            rec_of[pairs++] = &rec[i];
+        }
+        cands += n_cand[r];
+    }
+    for (int k = 0; k < pairs; k++) {                       // (the arena may have moved while it grew: addresses last)
+        d_src[k] = L.many_arena.as<unsigned char>() + off_src[k];
+        d_tgt[k] = L.many_arena.as<unsigned char>() + off_tgt[k];
+    }
+    if (pairs) {
+        IcpResult res[kIcpMaxPairs];
+        hipError_t e = icp_pairs_begin(L.icp, h->stream, d_src, n_src, d_tgt, n_tgt, pairs, kDsStride, loop_icp_params(prm), loop_tuning(h, prm.icp_leaf));
+        bool done = false;
+        if (e == hipSuccess) e = icp_pairs_advance(L.icp, h->stream, true, &done, res);
+        if (e != hipSuccess || !done) {
+            (void)hipStreamSynchronize(h->stream);
+            icp_dev_cancel(L.icp);
+            return fail(h, S2M_ERR_HIP, "loop verification of many keys", e);
+        }
+        S2M_HIP(h, hipStreamSynchronize(h->stream));
+        for (int k = 0; k < pairs; k++) {
+            s2m_loop_result* o = rec_of[k];
+            loop_judge(res[k], base_key, prm.fitness_score, h->kf.frame[(size_t)o->key_cur].T, &h->kf.pose[6 * (size_t)o->key_pre], o);
+        }
+        L.many_last_pairs += pairs;
+    }
+    for (int32_t r = r0; r < r1; r++) {
+        if (!n_cand[r]) continue;
+        const s2m_loop_result* rec = out + (size_t)r * row_stride;
+        best[r] = verify_best(rec, n_cand[r]);
+        if (best[r] >= 0) L.index[rec[best[r]].key_cur] = rec[best[r]].key_pre;           // only the winner is a closure (:621)
+    }
+    return S2M_OK;
+}
+
+}  // namespace
+
+int s2m_loop_verify_many_check_args(int32_t n_stored, const int32_t* key_cur, const int32_t* key_pre, const int32_t* n_cand, int32_t m,
+                                    int32_t row_stride, int32_t base_key, const s2m_loop_params* p)
+{
+    if (n_stored < 0) return S2M_ERR_INVALID_ARG;
+    s2m_loop_params prm;
+    bool empty;
+    return many_args(nullptr, (size_t)n_stored, key_cur, key_pre, n_cand, m, row_stride, base_key, p, &prm, &empty);
+}
+
+int s2m_loop_verify_many(s2m_handle h, const int32_t* key_cur, const int32_t* key_pre, const int32_t* n_cand, int32_t m, int32_t row_stride,
+                         int32_t base_key, const s2m_loop_params* p, s2m_loop_result* out, int32_t* best)
+{
+    if (!h) return S2M_ERR_INVALID_ARG;
+    if (m > 0 && (!out || !best)) return fail(h, S2M_ERR_INVALID_ARG, "null loop results");
+    int rc = loop_busy(h);
+    if (rc) return rc;
+    s2m_loop_params prm;
+    bool empty;
+    if ((rc = many_args(h, h->kf.time.size(), key_cur, key_pre, n_cand, m, row_stride, base_key, p, &prm, &empty))) return rc;
+    s2m_context::LoopClosure& L = h->loop;
+    L.many_last_passes = L.many_last_pairs = 0;
+    if (m == 0) return S2M_OK;
+    for (int32_t r = 0; r < m; r++) {
+        best[r] = -1;
+        for (int32_t i = 0; i < n_cand[r]; i++) loop_result_init(&out[(size_t)r * row_stride + i]);
+    }
+    if (empty) return S2M_OK;
+    S2M_HIP(h, hipSetDevice(h->device));
+    std::vector<int32_t> first((size_t)m + 1);
+    const int32_t n_pass = many_plan(n_cand, m, many_pairs_per_pass(L.many_pairs_per_pass), first.data());
+    for (int32_t k = 0; k < n_pass; k++) {
+        rc = many_pass(h, key_cur, key_pre, n_cand, first[k], first[k + 1], row_stride, base_key, prm, out, best);
+        if (rc) {                                           // the rows of the passes before keep what they have; this pass's rows as the later ones
+            for (int32_t r = first[k]; r < first[k + 1]; r++) {
+                best[r] = -1;
+                for (int32_t i = 0; i < n_cand[r]; i++) loop_result_init(&out[(size_t)r * row_stride + i]);
+            }
+            return rc;
+        }
+        L.many_last_passes++;
+    }
+    return S2M_OK;
+}
+
+int s2m_debug_loop_verify_many_pass(s2m_handle h, int32_t pairs_per_pass)
+{
+    if (!h) return S2M_ERR_INVALID_ARG;
+    if (pairs_per_pass < 0) return fail(h, S2M_ERR_INVALID_ARG, "pairs per pass must not be negative");
+    h->loop.many_pairs_per_pass = pairs_per_pass == 0 ? 0 : many_pairs_per_pass(pairs_per_pass);
+    return S2M_OK;
+}
+
+int s2m_debug_loop_verify_many_last(s2m_handle h, int32_t* passes, int32_t* pairs_aligned, size_t* bytes)
+{
+    if (!h) return S2M_ERR_INVALID_ARG;
+    if (passes) *passes = h->loop.many_last_passes;
+    if (pairs_aligned) *pairs_aligned = h->loop.many_last_pairs;
+    if (bytes) *bytes = h->loop.many_arena.cap;
+    return S2M_OK;
+}
+
+int s2m_debug_loop_verify_many_plan(const int32_t* n_cand, int32_t m, int32_t pairs_per_pass, int32_t* first_row_of_pass, int32_t* n_pass)
+{
+    if (m < 0 || pairs_per_pass < 0 || !first_row_of_pass || !n_pass || (m > 0 && !n_cand)) return S2M_ERR_INVALID_ARG;
+    for (int32_t r = 0; r < m; r++) if (n_cand[r] < 0 || n_cand[r] > S2M_LOOP_MAX_CANDIDATES) return S2M_ERR_INVALID_ARG;
+    *n_pass = many_plan(n_cand, m, many_pairs_per_pass(pairs_per_pass), first_row_of_pass);
+    return S2M_OK;
+}
+
 // ---- relocalisation: a scan that is no key against the stored map (place query, guessed alignment in lockstep) -------------
 
 int s2m_reloc_default_params(s2m_reloc_params* p)
@@ -813,6 +1026,62 @@ int s2m_debug_icp_align_guess_many_device(s2m_handle h, const void* src, size_t 
     int rc = icp_params_in(h, p, &ip);
     for (int32_t i = 0; !rc && guesses && i < n_cand; i++) rc = guess_ok(h, guesses + 16 * (size_t)i);
     return rc ? rc : debug_align_many(h, src, n_src, tgts, n_tgts, n_cand, stride_bytes, ip, out, guesses);
+}
+
+// P host pairs through the table form of the device loop, waited for: the clouds staged in the arena of a many-keys pass
+int s2m_debug_icp_align_pairs_device(s2m_handle h, const void* const* srcs, const size_t* n_srcs, const void* const* tgts, const size_t* n_tgts,
+                                     int32_t n_pairs, size_t stride_bytes, const float* const* guesses, const s2m_icp_params* p, s2m_icp_result* out)
+{
+    if (!h) return S2M_ERR_INVALID_ARG;
+    if (!out || !srcs || !n_srcs || !tgts || !n_tgts || n_pairs < 1 || n_pairs > kIcpMaxPairs)
+        return fail(h, S2M_ERR_INVALID_ARG, "null ICP results or cloud lists, or not 1 .. 64 pairs");
+    IcpParams ip;
+    int rc = icp_params_in(h, p, &ip);
+    for (int32_t k = 0; !rc && k < n_pairs; k++) {
+        if ((rc = check_records(h, srcs[k], n_srcs[k], stride_bytes)) || (rc = check_records(h, tgts[k], n_tgts[k], stride_bytes))) break;
+        if (guesses && guesses[k]) rc = guess_ok(h, guesses[k]);
+    }
+    if (rc || (rc = debug_stage(h, nullptr, 0, nullptr, 0, stride_bytes))) return rc;             // (BUSY, the loop stream)
+    s2m_context::LoopClosure& L = h->loop;
+    const unsigned char *d_src[kIcpMaxPairs], *d_tgt[kIcpMaxPairs];
+    size_t ns[kIcpMaxPairs], nt[kIcpMaxPairs];
+    const float* guess[kIcpMaxPairs];
+    int pair_of[kIcpMaxPairs];
+    int pairs = 0;
+    size_t total = 0;
+    const auto room = [&](size_t n) { return (n * stride_bytes + 255) / 256 * 256; };
+    for (int32_t k = 0; k < n_pairs; k++) if (n_srcs[k] && n_tgts[k]) total += room(n_srcs[k]) + room(n_tgts[k]);
+    L.many_used = 0;
+    if ((rc = arena_reserve(h, L.stream, total))) return rc;
+    unsigned char* at = L.many_arena.as<unsigned char>();
+    for (int32_t k = 0; k < n_pairs; k++) {
+        pair_of[k] = -1;
+        if (!n_srcs[k] || !n_tgts[k]) continue;
+        S2M_HIP(h, hipMemcpyAsync(at, srcs[k], n_srcs[k] * stride_bytes, hipMemcpyHostToDevice, L.stream));
+        d_src[pairs] = at; ns[pairs] = n_srcs[k];
+        at += room(n_srcs[k]);
+        S2M_HIP(h, hipMemcpyAsync(at, tgts[k], n_tgts[k] * stride_bytes, hipMemcpyHostToDevice, L.stream));
+        d_tgt[pairs] = at; nt[pairs] = n_tgts[k];
+        at += room(n_tgts[k]);
+        guess[pairs] = guesses ? guesses[k] : nullptr;
+        pair_of[k] = pairs++;
+    }
+    IcpResult r[kIcpMaxPairs];
+    if (pairs) {
+        s2m_loop_params lp;
+        s2m_loop_default_params(&lp);
+        hipError_t e = icp_pairs_begin(L.icp, L.stream, d_src, ns, d_tgt, nt, pairs, stride_bytes, ip, loop_tuning(h, lp.icp_leaf), guess);
+        bool done = false;
+        if (e == hipSuccess) e = icp_pairs_advance(L.icp, L.stream, true, &done, r);
+        if (e != hipSuccess || !done) {
+            (void)hipStreamSynchronize(L.stream);
+            icp_dev_cancel(L.icp);
+            return fail(h, S2M_ERR_HIP, "ICP device loop over pairs", e);
+        }
+    }
+    S2M_HIP(h, hipStreamSynchronize(L.stream));
+    for (int32_t k = 0; k < n_pairs; k++) icp_result_out(pair_of[k] >= 0 ? r[pair_of[k]] : icp_result_none(), &out[k]);
+    return S2M_OK;
 }
 
 int s2m_debug_icp_grid_check_args(const void* const* tgts, const size_t* n_tgts, int32_t n_cand, size_t stride_bytes, const s2m_debug_icp_grid_out* out)

@@ -232,6 +232,14 @@ struct __attribute__((visibility("hidden"))) s2m_context {
         float pend_fitness = 0.0f;         // s2m_loop_params::fitness_score of the launch
         int32_t pend_base_key = -1;
         s2m::IcpTuning tune{ 0.0f, s2m::kIcpShellCap, s2m::kIcpUseGrid ? 1 : 0 };   // cell: edge in units of the leaf (s2m_debug_icp_tuning)
+        // s2m_loop_verify_many: the submaps of one pass, all held at once - a source per row, a target per pair - back to back in
+        // one arena: a submap is built in cur / target(i) as ever and its filtered records are copied behind the ones before
+        // (many_used bytes so far). The arena grows to the largest pass it has held and is kept.
+        // pairs_per_pass: s2m_debug_loop_verify_many_pass (0: kIcpMaxPairs); last_*: what the call made last did.
+        DevBuf many_arena;
+        size_t many_used = 0;
+        int32_t many_pairs_per_pass = 0;
+        int32_t many_last_passes = 0, many_last_pairs = 0;
     } loop;
 
     // the global map and the saved map from the store: transformed frames, the filtered cloud, the chunked copy-out (frame table,

@@ -22,6 +22,10 @@
 // The loop carries up to kIcpMaxSlots alignments of one source at once, the slot a grid dimension of every kernel; the single
 // alignment is its one-slot case. Every slot owns its moving copy of the source, so each may start from a guess of its own
 // (align(output, guess): IcpGuesses, the source moved as it is loaded, the state's T started at the guess).
+// A second layout beside the slots carries up to kIcpMaxPairs alignments that each have a source of their own (icp_pairs_*, what
+// s2m_loop_verify_many queues): the pairs' descriptions are a table in device memory, uploaded once per alignment set. The kernels
+// of the loop are written once over "the view of slot s" and instantiated for both layouts; what a kernel derives from the launch
+// where all slots share n_src (the partial rows, the stride over the source) is the pair's own in the table form.
 // The kernels are one set but for two. The host loop (icp_align) launches the loop's load, reset, sums and fold on the one-slot
 // layout and differs in who closes an iteration (the host, after a wait), in the search (always the brute force, through k_icp_nn:
 // k_icp_nn_list over every source computes the same keys but cost the loop 2-3 % of its time) and in k_icp_transform, which takes
@@ -170,7 +174,37 @@ __device__ __forceinline__ float cell_coord(float x, float lo, float inv) { retu
 // slot from blockIdx.z; grids are sized by the largest slot and a workgroup beyond its own slot's extent returns at entry.
 // Inside a slot nothing differs from the single alignment, which is the K = 1 case: the same per-point arithmetic, the same
 // (d2, original index) minimum, the same number of partial rows (it depends on n_src only), the same fold, the same close.
+// The view of slot s: what a kernel of the loop reads about the alignment it works on. The kernels are written once over it and
+// instantiated twice: for IcpSlots by value, which builds the view from its arrays (n_src shared, rows and guess not in it: the
+// launch carries them), and for the pair table (IcpPairs), whose entries are views in device memory with every field the pair's own.
+struct IcpView {
+    float4*             cur;                     // the moving source, n_src points
+    const float4*       tgt;
+    unsigned long long* best;
+    double*             part;
+    int*                list;                    // the fallback list of the grid search
+    float4*             gsorted;                 // the targets sorted by cell
+    IcpDevBlock*        blk;
+    int*                gcount;                  // kGridMaxCells ints, as gstart and gend
+    int*                gstart;
+    int*                gend;
+    const unsigned char* d_src;                  // (table only) the records the source and the target are loaded from
+    const unsigned char* d_tgt;
+    int                 n_tgt;
+    int                 slice_len;               // the brute force's target slice (nn_shape of this slot)
+    int                 n_src;
+    int                 rows;                    // (table only) partial rows: min(ceil(n_src / 256), kSumBlocks)
+    int                 guess_set;               // (table only) the guess, as IcpGuesses holds it
+    float               guess[16];
+};
+
+// The slots of the loop: one source against K <= kIcpMaxSlots targets, K independent alignments advanced by the same launches.
+// Every kernel of the loop takes this struct by value (as k_icp_transform takes Mat34: nothing is uploaded per launch) and its
+// slot from blockIdx.z; grids are sized by the largest slot and a workgroup beyond its own slot's extent returns at entry.
+// Inside a slot nothing differs from the single alignment, which is the K = 1 case: the same per-point arithmetic, the same
+// (d2, original index) minimum, the same number of partial rows (it depends on n_src only), the same fold, the same close.
 struct IcpSlots {
+    static constexpr bool kPerPair = false;      // one n_src: every slot has the launch's rows, no workgroup is beyond them
     float4*             cur[kIcpMaxSlots];       // the moving source, n_src points each
     const float4*       tgt[kIcpMaxSlots];
     unsigned long long* best[kIcpMaxSlots];
@@ -184,6 +218,55 @@ struct IcpSlots {
     int*                gstart;
     int*                gend;
     int                 n_src;
+    // the view of slot s: each field read from the kernel's arguments where the kernel asks for it
+    struct Ref {
+        const IcpSlots& S;
+        const int s;
+        __device__ __forceinline__ float4* cur() const { return S.cur[s]; }
+        __device__ __forceinline__ const float4* tgt() const { return S.tgt[s]; }
+        __device__ __forceinline__ unsigned long long* best() const { return S.best[s]; }
+        __device__ __forceinline__ double* part() const { return S.part[s]; }
+        __device__ __forceinline__ int* list() const { return S.list[s]; }
+        __device__ __forceinline__ float4* gsorted() const { return S.gsorted[s]; }
+        __device__ __forceinline__ IcpDevBlock* blk() const { return S.blk + s; }
+        __device__ __forceinline__ int* gcount() const { return S.gcount + (size_t)s * kGridMaxCells; }
+        __device__ __forceinline__ int* gstart() const { return S.gstart + (size_t)s * kGridMaxCells; }
+        __device__ __forceinline__ int* gend() const { return S.gend + (size_t)s * kGridMaxCells; }
+        __device__ __forceinline__ int n_tgt() const { return S.n_tgt[s]; }
+        __device__ __forceinline__ int slice_len() const { return S.slice_len[s]; }
+        __device__ __forceinline__ int n_src() const { return S.n_src; }
+        __device__ __forceinline__ int rows() const { return 0; }             // (kPerPair only: the launch carries the rows)
+    };
+    __device__ __forceinline__ Ref view(int s) const { return Ref{ *this, s }; }
+    __device__ __forceinline__ const IcpView* table() const { return nullptr; }
+};
+
+// The pairs of the loop: P <= kIcpMaxPairs alignments, each with its own source, target and guess. The table is an array of views
+// in device memory, written in pinned host memory and uploaded once per alignment set ahead of the first kernel; a kernel takes
+// its address and finds its pair by blockIdx.z. Grids are sized by the largest pair; what a slot's kernels derive from the launch
+// (the partial rows and their stride) is here the pair's own, so that a pair computes what it computes alone.
+struct IcpPairs {
+    static constexpr bool kPerPair = true;
+    const IcpView* t;
+    struct Ref {
+        const IcpView& p;
+        __device__ __forceinline__ float4* cur() const { return p.cur; }
+        __device__ __forceinline__ const float4* tgt() const { return p.tgt; }
+        __device__ __forceinline__ unsigned long long* best() const { return p.best; }
+        __device__ __forceinline__ double* part() const { return p.part; }
+        __device__ __forceinline__ int* list() const { return p.list; }
+        __device__ __forceinline__ float4* gsorted() const { return p.gsorted; }
+        __device__ __forceinline__ IcpDevBlock* blk() const { return p.blk; }
+        __device__ __forceinline__ int* gcount() const { return p.gcount; }
+        __device__ __forceinline__ int* gstart() const { return p.gstart; }
+        __device__ __forceinline__ int* gend() const { return p.gend; }
+        __device__ __forceinline__ int n_tgt() const { return p.n_tgt; }
+        __device__ __forceinline__ int slice_len() const { return p.slice_len; }
+        __device__ __forceinline__ int n_src() const { return p.n_src; }
+        __device__ __forceinline__ int rows() const { return p.rows; }
+    };
+    __device__ __forceinline__ Ref view(int s) const { return Ref{ t[s] }; }
+    __device__ __forceinline__ const IcpView* table() const { return t; }
 };
 
 // The initial guesses of the slots (pcl::IterativeClosestPoint::align(output, guess)): slot s with set[s] starts its
@@ -192,7 +275,16 @@ struct IcpSlots {
 struct IcpGuesses {
     float T[kIcpMaxSlots][16];
     int   set[kIcpMaxSlots];
+    __device__ __forceinline__ const float* of(int s, const IcpView*) const { return set[s] ? T[s] : nullptr; }
 };
+// the table form: the guess is in the pair's view
+struct IcpPairGuesses {
+    int unused;
+    __device__ __forceinline__ const float* of(int s, const IcpView* t) const { return t[s].guess_set ? t[s].guess : nullptr; }
+};
+
+// one load: n records at src to float4 at dst, moved by the 3x4 m where move is set
+struct IcpLoadItem { const unsigned char* src; float4* dst; int n; int move; const float* m; };
 
 // records to float4 per slot: the K targets, or the one source into every slot's moving copy - there moved by the slot's guess
 // where it has one (move[s]; m[s]: the guess's 3x4), in transform_body's arithmetic
@@ -202,39 +294,55 @@ struct IcpLoad {
     int                  n[kIcpMaxSlots];
     int                  move[kIcpMaxSlots];
     float                m[kIcpMaxSlots][12];
+    __device__ __forceinline__ IcpLoadItem item(int s) const { return IcpLoadItem{ src[s], dst[s], n[s], move[s], m[s] }; }
+};
+// the table form. what: 0 the targets, 1 the sources as they are (the fitness pass), 2 the sources moved by their guesses
+struct IcpPairLoad {
+    const IcpView* t;
+    int what;
+    __device__ __forceinline__ IcpLoadItem item(int s) const
+    {
+        const IcpView& v = t[s];
+        if (what == 0) return IcpLoadItem{ v.d_tgt, const_cast<float4*>(v.tgt), v.n_tgt, 0, v.guess };
+        return IcpLoadItem{ v.d_src, v.cur, v.n_src, what == 2 ? v.guess_set : 0, v.guess };
+    }
 };
 
-__global__ __launch_bounds__(256) void k_icp_load_slots(IcpLoad L, size_t stride)
+template <class L>
+__global__ __launch_bounds__(256) void k_icp_load_slots(L ld, size_t stride)
 {
-    const int s = blockIdx.z;
+    const IcpLoadItem it = ld.item(blockIdx.z);
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= L.n[s]) return;
-    const float* p = reinterpret_cast<const float*>(L.src[s] + (size_t)i * stride);
+    if (i >= it.n) return;
+    const float* p = reinterpret_cast<const float*>(it.src + (size_t)i * stride);
     const float x = p[0], y = p[1], z = p[2];
-    if (!L.move[s]) { L.dst[s][i] = make_float4(x, y, z, 0.0f); return; }
-    const float* m = L.m[s];
-    L.dst[s][i] = make_float4(m[0] * x + m[1] * y + m[2]  * z + m[3],
-                              m[4] * x + m[5] * y + m[6]  * z + m[7],
-                              m[8] * x + m[9] * y + m[10] * z + m[11], 0.0f);
+    if (!it.move) { it.dst[i] = make_float4(x, y, z, 0.0f); return; }
+    const float* m = it.m;
+    it.dst[i] = make_float4(m[0] * x + m[1] * y + m[2]  * z + m[3],
+                            m[4] * x + m[5] * y + m[6]  * z + m[7],
+                            m[8] * x + m[9] * y + m[10] * z + m[11], 0.0f);
 }
 
-__global__ __launch_bounds__(64) void k_icp_begin(IcpSlots S, IcpGuesses G)
+template <class V, class GV>
+__global__ __launch_bounds__(64) void k_icp_begin(V S, GV G)
 {
     if (threadIdx.x != 0) return;
-    IcpDevBlock* blk = S.blk + blockIdx.z;
-    icp_state_init(&blk->st, G.set[blockIdx.z] ? G.T[blockIdx.z] : nullptr);
+    IcpDevBlock* blk = S.view(blockIdx.z).blk();
+    icp_state_init(&blk->st, G.of(blockIdx.z, S.table()));
     for (int a = 0; a < 3; a++) { blk->bbox[a] = 0xffffffffu; blk->bbox[3 + a] = 0u; }
     blk->wl_count = 0; blk->n_fallback = 0;
     blk->g.n_fin = 0; blk->g.usable = 0;
 }
 
-__global__ __launch_bounds__(256) void k_icp_grid_bbox(IcpSlots S)
+template <class V>
+__global__ __launch_bounds__(256) void k_icp_grid_bbox(V S)
 {
     __shared__ unsigned sh[4][6];
-    const int n = S.n_tgt[blockIdx.z];
+    const auto v = S.view(blockIdx.z);
+    const int n = v.n_tgt();
     if ((int)(blockIdx.x * blockDim.x) >= n) return;
-    const float4* __restrict__ tgt = S.tgt[blockIdx.z];
-    IcpDevBlock* blk = S.blk + blockIdx.z;
+    const float4* __restrict__ tgt = v.tgt();
+    IcpDevBlock* blk = v.blk();
     unsigned lo[3] = { 0xffffffffu, 0xffffffffu, 0xffffffffu }, hi[3] = { 0u, 0u, 0u };
     for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
         const float4 t = tgt[i];
@@ -259,10 +367,11 @@ __global__ __launch_bounds__(256) void k_icp_grid_bbox(IcpSlots S)
 }
 
 // the grid's shape from the box: the edge asked for, enlarged until the box needs no more than kGridMaxCells cells
-__global__ __launch_bounds__(64) void k_icp_grid_setup(IcpSlots S, float cell_req)
+template <class V>
+__global__ __launch_bounds__(64) void k_icp_grid_setup(V S, float cell_req)
 {
     if (threadIdx.x != 0) return;
-    IcpDevBlock* blk = S.blk + blockIdx.z;
+    IcpDevBlock* blk = S.view(blockIdx.z).blk();
     IcpGrid g{};
     if (blk->bbox[0] == 0xffffffffu) { blk->g = g; return; }             // no finite target: n_fin stays 0
     float hi[3];
@@ -298,29 +407,31 @@ __device__ __forceinline__ int cell_of(const IcpGrid& g, const float4 t)
     return (min(max(cz, 0), g.n[2] - 1) * g.n[1] + min(max(cy, 0), g.n[1] - 1)) * g.n[0] + min(max(cx, 0), g.n[0] - 1);
 }
 
-__global__ __launch_bounds__(256) void k_icp_grid_count(IcpSlots S)
+template <class V>
+__global__ __launch_bounds__(256) void k_icp_grid_count(V S)
 {
-    const int s = blockIdx.z;
-    const IcpDevBlock* blk = S.blk + s;
-    int* __restrict__ counts = S.gcount + (size_t)s * kGridMaxCells;
+    const auto v = S.view(blockIdx.z);
+    const IcpDevBlock* blk = v.blk();
+    int* __restrict__ counts = v.gcount();
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= S.n_tgt[s] || !blk->g.usable) return;
-    const float4 t = S.tgt[s][i];
+    if (i >= v.n_tgt() || !blk->g.usable) return;
+    const float4 t = v.tgt()[i];
     if (!(isfinite(t.x) && isfinite(t.y) && isfinite(t.z))) return;
     atomicAdd(&counts[cell_of(blk->g, t)], 1);
 }
 
 // exclusive scan of the cell counts in one workgroup: cstart[c] = first slot of cell c, cursor[c] the same (k_icp_grid_scatter
 // advances it to the cell's end, which is the next cell's start)
-__global__ __launch_bounds__(1024) void k_icp_grid_scan(IcpSlots S)
+template <class V>
+__global__ __launch_bounds__(1024) void k_icp_grid_scan(V S)
 {
     __shared__ int sh[1024];
-    IcpDevBlock* blk = S.blk + blockIdx.z;
+    const auto v = S.view(blockIdx.z);
+    IcpDevBlock* blk = v.blk();
     if (!blk->g.usable) return;
-    const size_t cells0 = (size_t)blockIdx.z * kGridMaxCells;
-    const int* __restrict__ counts = S.gcount + cells0;
-    int* __restrict__ cstart = S.gstart + cells0;
-    int* __restrict__ cursor = S.gend + cells0;
+    const int* __restrict__ counts = v.gcount();
+    int* __restrict__ cstart = v.gstart();
+    int* __restrict__ cursor = v.gend();
     const int ncells = blk->g.n[0] * blk->g.n[1] * blk->g.n[2];
     const int per = (ncells + 1023) / 1024;
     const int c0 = min(threadIdx.x * per, ncells), c1 = min(c0 + per, ncells);
@@ -339,15 +450,17 @@ __global__ __launch_bounds__(1024) void k_icp_grid_scan(IcpSlots S)
     if (threadIdx.x == 1023) blk->g.n_fin = sh[1023];
 }
 
-__global__ __launch_bounds__(256) void k_icp_grid_scatter(IcpSlots S)
+template <class V>
+__global__ __launch_bounds__(256) void k_icp_grid_scatter(V S)
 {
-    const int s = blockIdx.z, n = S.n_tgt[s];
-    const IcpDevBlock* blk = S.blk + s;
-    int* __restrict__ cursor = S.gend + (size_t)s * kGridMaxCells;
-    float4* __restrict__ sorted = S.gsorted[s];
+    const auto v = S.view(blockIdx.z);
+    const int n = v.n_tgt();
+    const IcpDevBlock* blk = v.blk();
+    int* __restrict__ cursor = v.gend();
+    float4* __restrict__ sorted = v.gsorted();
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n || !blk->g.usable) return;
-    const float4 t = S.tgt[s][i];
+    const float4 t = v.tgt()[i];
     if (!(isfinite(t.x) && isfinite(t.y) && isfinite(t.z))) return;
     const int pos = atomicAdd(&cursor[cell_of(blk->g, t)], 1);             // the order inside a cell is arbitrary: the search takes a minimum
     if (pos >= 0 && pos < n) sorted[pos] = make_float4(t.x, t.y, t.z, __int_as_float(i));
@@ -403,20 +516,21 @@ __device__ __forceinline__ bool grid_settled(const IcpGrid& g, const float4 p, c
 // exact 1-NN through the grid: one lane per source point. First the 3 x 3 x 3 cells around the (clamped) cell of the point, their
 // nine row ranges fetched before any point is read; then shells of growing Chebyshev radius up to shell_cap. A point that is not
 // settled by then, or lies more than shell_cap cells outside the box, goes to the fallback list.
-__global__ __launch_bounds__(kGridThreads) void k_icp_nn_grid(IcpSlots S, int shell_cap, int phase)
+template <class V>
+__global__ __launch_bounds__(kGridThreads) void k_icp_nn_grid(V S, int shell_cap, int phase)
 {
-    const int s = blockIdx.z;
-    IcpDevBlock* blk = S.blk + s;
+    const auto v = S.view(blockIdx.z);
+    IcpDevBlock* blk = v.blk();
     if (done_guard(blk, phase)) return;
-    const int n_src = S.n_src;
+    const int n_src = v.n_src();
     const int i = blockIdx.x * kGridThreads + threadIdx.x;
     if (i >= n_src) return;
-    const int* __restrict__ cstart = S.gstart + (size_t)s * kGridMaxCells;
-    const int* __restrict__ cend = S.gend + (size_t)s * kGridMaxCells;
-    const float4* __restrict__ sorted = S.gsorted[s];
-    unsigned long long* __restrict__ best = S.best[s];
-    int* __restrict__ list = S.list[s];
-    const float4 p = S.cur[s][i];
+    const int* __restrict__ cstart = v.gstart();
+    const int* __restrict__ cend = v.gend();
+    const float4* __restrict__ sorted = v.gsorted();
+    unsigned long long* __restrict__ best = v.best();
+    int* __restrict__ list = v.list();
+    const float4 p = v.cur()[i];
     const IcpGrid g = blk->g;
     if (!(isfinite(p.x) && isfinite(p.y) && isfinite(p.z)) || g.n_fin == 0) { best[i] = kNoMatch; return; }
     const float f[3] = { cell_coord(p.x, g.lo[0], g.inv), cell_coord(p.y, g.lo[1], g.inv), cell_coord(p.z, g.lo[2], g.inv) };
@@ -477,31 +591,34 @@ __global__ __launch_bounds__(kGridThreads) void k_icp_nn_grid(IcpSlots S, int sh
     }
 }
 
-__global__ __launch_bounds__(256) void k_icp_reset_dev(IcpSlots S, int phase)
+template <class V>
+__global__ __launch_bounds__(256) void k_icp_reset_dev(V S, int phase)
 {
-    if (done_guard(S.blk + blockIdx.z, phase)) return;
+    const auto v = S.view(blockIdx.z);
+    if (done_guard(v.blk(), phase)) return;
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < S.n_src) S.best[blockIdx.z][i] = kNoMatch;
+    if (i < v.n_src()) v.best()[i] = kNoMatch;
 }
 
 // the brute force of the device loop: 256 sources - those a slot's list names, or with use_list == 0 all of them (the search with
 // the grid off: k_icp_nn with a slot) - against target points [slice * len, (slice + 1) * len), the winner settled across slices by
 // atomicMin. Grid (source blocks, target slices of the slot with most, slots); workgroups past the end of the list or of their
 // slot's slices return at entry
-__global__ __launch_bounds__(kNnThreads) void k_icp_nn_list(IcpSlots S, int use_list, int phase)
+template <class V>
+__global__ __launch_bounds__(kNnThreads) void k_icp_nn_list(V S, int use_list, int phase)
 {
     __shared__ float4 tile[kNnTile];
-    const int s = blockIdx.z;
-    const IcpDevBlock* blk = S.blk + s;
+    const auto v = S.view(blockIdx.z);
+    const IcpDevBlock* blk = v.blk();
     if (done_guard(blk, phase)) return;
-    const int n_src = S.n_src, n_tgt = S.n_tgt[s], slice_len = S.slice_len[s];
+    const int n_src = v.n_src(), n_tgt = v.n_tgt(), slice_len = v.slice_len();
     const int j0 = blockIdx.y * slice_len, j1 = min(j0 + slice_len, n_tgt);
     if (j0 >= n_tgt) return;
-    const int* __restrict__ list = use_list ? S.list[s] : nullptr;
+    const int* __restrict__ list = use_list ? v.list() : nullptr;
     const int count = list ? min(blk->wl_count, n_src) : n_src;
     if ((int)(blockIdx.x * kNnThreads) >= count) return;
-    const float4* __restrict__ cur = S.cur[s];
-    unsigned long long* __restrict__ best = S.best[s];
+    const float4* __restrict__ cur = v.cur();
+    unsigned long long* __restrict__ best = v.best();
     const int w = blockIdx.x * kNnThreads + threadIdx.x;
     const bool valid = w < count;
     const int i = valid ? (list ? list[w] : w) : 0;
@@ -509,21 +626,24 @@ __global__ __launch_bounds__(kNnThreads) void k_icp_nn_list(IcpSlots S, int use_
     const bool fin = valid && isfinite(p.x) && isfinite(p.y) && isfinite(p.z);
     float bd = INFINITY;
     int bi = -1;
-    nn_tiles(p, fin, S.tgt[s], j0, j1, tile, bd, bi);
+    nn_tiles(p, fin, v.tgt(), j0, j1, tile, bd, bi);
     if (fin && bi >= 0)
         atomicMin(&best[i], ((unsigned long long)__float_as_uint(bd) << 32) | (unsigned)bi);
 }
 
 // count, sum d2, centroids and raw cross moments of the correspondences with d2 <= max_d2 (fp64): this workgroup's row of `part`
-// (a function of its own for the __restrict__ of its parameters, which a kernel's locals would not carry)
+// (a function of its own for the __restrict__ of its parameters, which a kernel's locals would not carry). The stride is the threads
+// of all rows of this alignment: the launch's where every slot has the launch's rows, own_rows * 256 in the table form (kOwnRows:
+// a grid sized by a larger pair must not change which points a row sums)
+template <bool kOwnRows>
 __device__ __forceinline__ void sums_body(const float4* __restrict__ cur, int n_src, const float4* __restrict__ tgt,
                                           const unsigned long long* __restrict__ best, double max_d2, double* __restrict__ part,
-                                          double (*sh)[17])
+                                          double (*sh)[17], const int own_rows)
 {
     double a[17];
 #pragma unroll
     for (int k = 0; k < 17; k++) a[k] = 0.0;
-    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n_src; i += gridDim.x * blockDim.x) {
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n_src; i += (kOwnRows ? own_rows : gridDim.x) * blockDim.x) {
         const unsigned long long key = best[i];
         if (key == kNoMatch) continue;
         const float d2 = __uint_as_float((unsigned)(key >> 32));
@@ -549,23 +669,30 @@ __device__ __forceinline__ void sums_body(const float4* __restrict__ cur, int n_
     if (threadIdx.x < 17) part[17 * blockIdx.x + threadIdx.x] = sh[0][threadIdx.x] + sh[1][threadIdx.x] + sh[2][threadIdx.x] + sh[3][threadIdx.x];
 }
 
-__global__ __launch_bounds__(256) void k_icp_sums_dev(IcpSlots S, double max_d2, int phase)
+template <class V>
+__global__ __launch_bounds__(256) void k_icp_sums_dev(V S, double max_d2, int phase)
 {
     __shared__ double sh[4][17];
-    const int s = blockIdx.z;
-    if (done_guard(S.blk + s, phase)) return;
-    sums_body(S.cur[s], S.n_src, S.tgt[s], S.best[s], max_d2, S.part[s], sh);
+    const auto v = S.view(blockIdx.z);
+    if (done_guard(v.blk(), phase)) return;
+    if constexpr (V::kPerPair) {
+        if ((int)blockIdx.x >= v.rows()) return;
+    }
+    sums_body<V::kPerPair>(v.cur(), v.n_src(), v.tgt(), v.best(), max_d2, v.part(), sh, v.rows());
 }
 
 // the rows of k_icp_sums_dev folded in workgroup order into the slot's block, and the fallback list closed. The host loop
 // (icp_align) runs this kernel too and has no list: it never runs beside a flight, so the two counts it rewrites are nobody's.
-__global__ __launch_bounds__(64) void k_icp_fold_dev(IcpSlots S, int rows, int phase)
+template <class V>
+__global__ __launch_bounds__(64) void k_icp_fold_dev(V S, int rows, int phase)
 {
-    IcpDevBlock* blk = S.blk + blockIdx.z;
+    const auto v = S.view(blockIdx.z);
+    IcpDevBlock* blk = v.blk();
     if (done_guard(blk, phase)) return;
+    if constexpr (V::kPerPair) rows = v.rows();                              // (the launch names the most of any pair)
     const int k = threadIdx.x;
     if (k < 17) {
-        const double* __restrict__ part = S.part[blockIdx.z];
+        const double* __restrict__ part = v.part();
         double a = 0.0;
         for (int b = 0; b < rows; b++) a += part[17 * b + k];
         blk->sums[k] = a;
@@ -574,9 +701,10 @@ __global__ __launch_bounds__(64) void k_icp_fold_dev(IcpSlots S, int rows, int p
 }
 
 // closes the iteration on the folded sums: one lane per slot runs icp_close_step, the host loop's own source
-__global__ __launch_bounds__(64) void k_icp_close(IcpSlots S, IcpCloseParams prm)
+template <class V>
+__global__ __launch_bounds__(64) void k_icp_close(V S, IcpCloseParams prm)
 {
-    IcpDevBlock* blk = S.blk + blockIdx.z;
+    IcpDevBlock* blk = S.view(blockIdx.z).blk();
     if (threadIdx.x != 0 || blk->st.done) return;
     double sums[17];
     for (int k = 0; k < 17; k++) sums[k] = blk->sums[k];
@@ -587,11 +715,13 @@ __global__ __launch_bounds__(64) void k_icp_close(IcpSlots S, IcpCloseParams prm
 
 // phase 0: the source moves by the step of the iteration just closed (not once the alignment has ended); phase 1: the reloaded
 // source moves by the final transformation
-__global__ __launch_bounds__(256) void k_icp_transform_dev(IcpSlots S, int phase)
+template <class V>
+__global__ __launch_bounds__(256) void k_icp_transform_dev(V S, int phase)
 {
-    const IcpDevBlock* blk = S.blk + blockIdx.z;
+    const auto v = S.view(blockIdx.z);
+    const IcpDevBlock* blk = v.blk();
     if (done_guard(blk, phase)) return;
-    transform_body(S.cur[blockIdx.z], S.n_src, phase == 0 ? blk->st.T_step : blk->st.T);
+    transform_body(v.cur(), v.n_src(), phase == 0 ? blk->st.T_step : blk->st.T);
 }
 
 }  // namespace
@@ -602,11 +732,17 @@ struct IcpWorkspace {
     // the device loop: its block with a pinned mirror, the grid (cell counts, starts, ends, the targets sorted by cell), the
     // fallback list, the event behind the work queued last, and what the host keeps about the alignment in flight
     Buf blk, gcount, gstart, gend, gsorted, list;
-    IcpDevBlock* h_blk = nullptr;
+    IcpDevBlock* h_blk = nullptr;        // pinned, h_blk_n blocks: kIcpMaxSlots, kIcpMaxPairs from the first pair table on
+    int h_blk_n = 0;
+    // the pair table: its device copy and the pinned host array it is written in (kIcpMaxPairs views). Both, and the larger
+    // block arrays, come with the first table (pairs_room): a handle that never aligns pairs allocates what it always did
+    Buf tab;
+    IcpView* h_tab = nullptr;
     hipEvent_t ev = nullptr;
     struct Flight {
         int phase = 0;                   // 0 none, 1 a range of iterations is queued, 2 the fitness pass is queued
         int n_src = 0, queued = 0;
+        bool pairs = false;              // the table form: the sources are the table's (d_src, n_src: the largest pair's extent)
         const unsigned char* d_src = nullptr;
         size_t stride = 0;
         IcpParams prm{};
@@ -614,7 +750,9 @@ struct IcpWorkspace {
     } fl;
     // the slots the buffers are laid out for (dev_layout): what every kernel of the loop gets by value, and the launch shapes
     IcpSlots S{};
-    int K = 0, n_tgt_max = 0, slices_max = 0;
+    IcpPairs P{};                        // the table the buffers are laid out for (pairs_layout)
+    // what the launches are sized by: slots or pairs, and the most of any of them (the slots share n_src and its rows)
+    int K = 0, n_tgt_max = 0, slices_max = 0, n_src_max = 0, rows_max = 0;
     IcpGuesses G{};                      // the slots' initial guesses; dev_layout leaves none, set_guesses sets them for one alignment
 };
 
@@ -622,6 +760,7 @@ IcpWorkspace* icp_create()
 {
     IcpWorkspace* w = new (std::nothrow) IcpWorkspace();
     if (!w) return nullptr;
+    w->h_blk_n = kIcpMaxSlots;
     if (hipHostMalloc((void**)&w->h_sums, sizeof(double) * 17) != hipSuccess ||
         w->blk.ensure(sizeof(IcpDevBlock) * kIcpMaxSlots) != hipSuccess ||
         hipHostMalloc((void**)&w->h_blk, sizeof(IcpDevBlock) * kIcpMaxSlots) != hipSuccess ||
@@ -635,10 +774,11 @@ IcpWorkspace* icp_create()
 void icp_destroy(IcpWorkspace* w)
 {
     if (!w) return;
-    Buf* bufs[] = { &w->cur, &w->tgt, &w->best, &w->part, &w->blk, &w->gcount, &w->gstart, &w->gend, &w->gsorted, &w->list };
+    Buf* bufs[] = { &w->cur, &w->tgt, &w->best, &w->part, &w->blk, &w->gcount, &w->gstart, &w->gend, &w->gsorted, &w->list, &w->tab };
     for (Buf* b : bufs) if (b->p) (void)hipFree(b->p);
     if (w->h_sums) (void)hipHostFree(w->h_sums);
     if (w->h_blk) (void)hipHostFree(w->h_blk);
+    if (w->h_tab) (void)hipHostFree(w->h_tab);
     if (w->ev) (void)hipEventDestroy(w->ev);
     delete w;
 }
@@ -654,6 +794,12 @@ void nn_shape(int n_src, int n_tgt, int* sb_out, int* slices_out, int* slice_len
     slices = std::max(1, std::min(slices, (n_tgt + kNnTile - 1) / kNnTile));
     const int slice_len = (((n_tgt + slices - 1) / slices) + kNnTile - 1) / kNnTile * kNnTile;
     *sb_out = sb; *slices_out = (n_tgt + slice_len - 1) / slice_len; *slice_len_out = slice_len;
+}
+
+bool guess_is_identity(const float* g)
+{
+    for (int i = 0; i < 16; i++) if (g[i] != ((i % 5 == 0) ? 1.0f : 0.0f)) return false;
+    return true;
 }
 
 // The buffers of K slots - one source of n_src points, targets of n_tgt[k] - and w->S, their layout: a slot's moving source, keys,
@@ -694,14 +840,91 @@ hipError_t dev_layout(IcpWorkspace* w, int K, size_t n_src, const size_t* n_tgt,
     S.gcount = w->gcount.as<int>(); S.gstart = w->gstart.as<int>(); S.gend = w->gend.as<int>();
     S.n_src = (int)n_src;
     w->S = S; w->K = K; w->n_tgt_max = (int)most; w->slices_max = slices_max;
+    w->n_src_max = (int)n_src; w->rows_max = (int)rows;
     w->G = IcpGuesses{};
     return hipSuccess;
 }
 
-bool guess_is_identity(const float* g)
+// The buffers of P pairs - sources of n_src[k] points, targets of n_tgt[k] - and their table in w->h_tab: the buffers are the
+// slots' own, a pair's stretch of each starting where the pair before ends (cur, best, list by sources; tgt, gsorted by targets;
+// part by rows), the blocks and the cell arrays one per pair. A pair's rows and slices are those of the single alignment of its
+// sizes. The table still has to be uploaded (pairs_upload).
+// what only the table form needs, once: blocks and their pinned mirror for kIcpMaxPairs, the table and its pinned image
+// (nothing is in flight: the old blocks hold nothing that is still wanted)
+hipError_t pairs_room(IcpWorkspace* w)
 {
-    for (int i = 0; i < 16; i++) if (g[i] != ((i % 5 == 0) ? 1.0f : 0.0f)) return false;
-    return true;
+    ICP_TRY(w->blk.ensure(sizeof(IcpDevBlock) * kIcpMaxPairs));
+    if (w->h_blk_n < kIcpMaxPairs) {
+        IcpDevBlock* q = nullptr;
+        ICP_TRY(hipHostMalloc((void**)&q, sizeof(IcpDevBlock) * kIcpMaxPairs));
+        if (w->h_blk) (void)hipHostFree(w->h_blk);
+        w->h_blk = q; w->h_blk_n = kIcpMaxPairs;
+    }
+    ICP_TRY(w->tab.ensure(sizeof(IcpView) * kIcpMaxPairs));
+    if (!w->h_tab) ICP_TRY(hipHostMalloc((void**)&w->h_tab, sizeof(IcpView) * kIcpMaxPairs));
+    return hipSuccess;
+}
+
+hipError_t pairs_layout(IcpWorkspace* w, int P, const unsigned char* const* d_src, const size_t* n_src, const unsigned char* const* d_tgt,
+                        const size_t* n_tgt, const IcpTuning& tune, const float* const* guess)
+{
+    if (P < 1 || P > kIcpMaxPairs) return hipErrorInvalidValue;
+    size_t tot_src = 0, tot_tgt = 0, tot_rows = 0, most_src = 0, most_tgt = 0;
+    for (int k = 0; k < P; k++) {
+        if (n_src[k] == 0 || n_tgt[k] == 0 || n_src[k] > (size_t)0x3fffffff || n_tgt[k] > (size_t)0x3fffffff) return hipErrorInvalidValue;
+        tot_src += n_src[k]; tot_tgt += n_tgt[k];
+        tot_rows += (size_t)std::min(((int)n_src[k] + 255) / 256, kSumBlocks);
+        most_src = std::max(most_src, n_src[k]); most_tgt = std::max(most_tgt, n_tgt[k]);
+    }
+    if (tot_src > (size_t)0x3fffffff || tot_tgt > (size_t)0x3fffffff) return hipErrorInvalidValue;
+    ICP_TRY(pairs_room(w));
+    ICP_TRY(w->cur.ensure(sizeof(float4) * tot_src)); ICP_TRY(w->tgt.ensure(sizeof(float4) * tot_tgt));
+    ICP_TRY(w->best.ensure(sizeof(unsigned long long) * tot_src));
+    ICP_TRY(w->part.ensure(sizeof(double) * 17 * tot_rows));
+    ICP_TRY(w->list.ensure(sizeof(int) * tot_src));
+    const bool grid = tune.use_grid != 0;
+    if (grid) {
+        ICP_TRY(w->gcount.ensure(sizeof(int) * kGridMaxCells * (size_t)P)); ICP_TRY(w->gstart.ensure(sizeof(int) * kGridMaxCells * (size_t)P));
+        ICP_TRY(w->gend.ensure(sizeof(int) * kGridMaxCells * (size_t)P)); ICP_TRY(w->gsorted.ensure(sizeof(float4) * tot_tgt));
+    }
+    size_t so = 0, to = 0, ro = 0;
+    int slices_max = 1, rows_max = 1;
+    for (int k = 0; k < P; k++) {
+        IcpView v{};
+        v.cur = w->cur.as<float4>() + so; v.tgt = w->tgt.as<float4>() + to;
+        v.best = w->best.as<unsigned long long>() + so; v.part = w->part.as<double>() + 17 * ro;
+        v.list = w->list.as<int>() + so;
+        v.gsorted = grid ? w->gsorted.as<float4>() + to : nullptr;
+        v.blk = w->blk.as<IcpDevBlock>() + k;
+        v.gcount = grid ? w->gcount.as<int>() + (size_t)k * kGridMaxCells : nullptr;
+        v.gstart = grid ? w->gstart.as<int>() + (size_t)k * kGridMaxCells : nullptr;
+        v.gend = grid ? w->gend.as<int>() + (size_t)k * kGridMaxCells : nullptr;
+        v.d_src = d_src[k]; v.d_tgt = d_tgt[k];
+        v.n_src = (int)n_src[k]; v.n_tgt = (int)n_tgt[k];
+        v.rows = std::min((v.n_src + 255) / 256, kSumBlocks);
+        int sb = 0, slices = 1;
+        nn_shape(v.n_src, v.n_tgt, &sb, &slices, &v.slice_len);
+        if (guess && guess[k] && !guess_is_identity(guess[k])) { v.guess_set = 1; memcpy(v.guess, guess[k], sizeof(v.guess)); }
+        w->h_tab[k] = v;
+        slices_max = std::max(slices_max, slices); rows_max = std::max(rows_max, v.rows);
+        so += n_src[k]; to += n_tgt[k]; ro += (size_t)v.rows;
+    }
+    w->P = IcpPairs{ w->tab.as<IcpView>() };
+    w->K = P; w->n_tgt_max = (int)most_tgt; w->slices_max = slices_max; w->n_src_max = (int)most_src; w->rows_max = rows_max;
+    return hipSuccess;
+}
+
+hipError_t pairs_upload(IcpWorkspace* w, hipStream_t stream)
+{
+    return hipMemcpyAsync(w->tab.p, w->h_tab, sizeof(IcpView) * (size_t)w->K, hipMemcpyHostToDevice, stream);
+}
+
+// the table's loads: what = 0 the targets, 1 the sources as they are, 2 the sources moved by their guesses
+hipError_t load_pairs(IcpWorkspace* w, hipStream_t stream, size_t stride, int what)
+{
+    const int most = what == 0 ? w->n_tgt_max : w->n_src_max;
+    hipLaunchKernelGGL(k_icp_load_slots<IcpPairLoad>, dim3((most + 255) / 256, 1, w->K), dim3(256), 0, stream, IcpPairLoad{ w->P.t, what }, stride);
+    return hipGetLastError();
 }
 
 // the guesses of the layout's slots: guess[k] (row-major 4x4) for slot k; a null list, a null entry or the identity leave the slot
@@ -729,59 +952,66 @@ hipError_t load_slots(IcpWorkspace* w, hipStream_t stream, const unsigned char* 
         most = std::max(most, L.n[k]);
         if (guessed && !d_tgt && w->G.set[k]) { L.move[k] = 1; memcpy(L.m[k], w->G.T[k], sizeof(L.m[k])); }
     }
-    hipLaunchKernelGGL(k_icp_load_slots, dim3((most + 255) / 256, 1, w->K), dim3(256), 0, stream, L, stride);
+    hipLaunchKernelGGL(k_icp_load_slots<IcpLoad>, dim3((most + 255) / 256, 1, w->K), dim3(256), 0, stream, L, stride);
     return hipGetLastError();
 }
 
 // the block reset of every slot of the layout and, with the grid on: box, shape, counts, scan, scatter - once per alignment
-hipError_t dev_prepare(IcpWorkspace* w, hipStream_t stream, const IcpTuning& tune)
+template <class V, class GV>
+hipError_t dev_prepare_v(IcpWorkspace* w, hipStream_t stream, const IcpTuning& tune, const V& S, const GV& G)
 {
-    const IcpSlots& S = w->S;
     const unsigned K = (unsigned)w->K;
-    hipLaunchKernelGGL(k_icp_begin, dim3(1, 1, K), dim3(64), 0, stream, S, w->G);
+    hipLaunchKernelGGL((k_icp_begin<V, GV>), dim3(1, 1, K), dim3(64), 0, stream, S, G);
     if (tune.use_grid) {
         ICP_TRY(hipMemsetAsync(w->gcount.p, 0, sizeof(int) * kGridMaxCells * (size_t)K, stream));
         const int tb = (w->n_tgt_max + 255) / 256;
-        hipLaunchKernelGGL(k_icp_grid_bbox, dim3(std::min(tb, 256), 1, K), dim3(256), 0, stream, S);
-        hipLaunchKernelGGL(k_icp_grid_setup, dim3(1, 1, K), dim3(64), 0, stream, S, tune.cell);
-        hipLaunchKernelGGL(k_icp_grid_count, dim3(tb, 1, K), dim3(256), 0, stream, S);
-        hipLaunchKernelGGL(k_icp_grid_scan, dim3(1, 1, K), dim3(1024), 0, stream, S);
-        hipLaunchKernelGGL(k_icp_grid_scatter, dim3(tb, 1, K), dim3(256), 0, stream, S);
+        hipLaunchKernelGGL(k_icp_grid_bbox<V>, dim3(std::min(tb, 256), 1, K), dim3(256), 0, stream, S);
+        hipLaunchKernelGGL(k_icp_grid_setup<V>, dim3(1, 1, K), dim3(64), 0, stream, S, tune.cell);
+        hipLaunchKernelGGL(k_icp_grid_count<V>, dim3(tb, 1, K), dim3(256), 0, stream, S);
+        hipLaunchKernelGGL(k_icp_grid_scan<V>, dim3(1, 1, K), dim3(1024), 0, stream, S);
+        hipLaunchKernelGGL(k_icp_grid_scatter<V>, dim3(tb, 1, K), dim3(256), 0, stream, S);
     }
     return hipGetLastError();
 }
+
+hipError_t dev_prepare(IcpWorkspace* w, hipStream_t stream, const IcpTuning& tune) { return dev_prepare_v(w, stream, tune, w->S, w->G); }
 
 // one search of the device loop in every slot: the grid with its fallback, or (use_grid off) the brute force over every source
-hipError_t dev_nearest(IcpWorkspace* w, hipStream_t stream, const IcpTuning& tune, int phase)
+template <class V>
+hipError_t dev_nearest_v(IcpWorkspace* w, hipStream_t stream, const IcpTuning& tune, int phase, const V& S)
 {
-    const IcpSlots& S = w->S;
     const unsigned K = (unsigned)w->K;
-    const int n_src = S.n_src, sb = (n_src + kNnThreads - 1) / kNnThreads;
+    const int n_src = w->n_src_max, sb = (n_src + kNnThreads - 1) / kNnThreads;
     if (tune.use_grid) {
-        hipLaunchKernelGGL(k_icp_nn_grid, dim3((n_src + kGridThreads - 1) / kGridThreads, 1, K), dim3(kGridThreads), 0, stream, S,
+        hipLaunchKernelGGL(k_icp_nn_grid<V>, dim3((n_src + kGridThreads - 1) / kGridThreads, 1, K), dim3(kGridThreads), 0, stream, S,
                            std::max(1, tune.shell_cap), phase);
-        hipLaunchKernelGGL(k_icp_nn_list, dim3(sb, w->slices_max, K), dim3(kNnThreads), 0, stream, S, 1, phase);
+        hipLaunchKernelGGL(k_icp_nn_list<V>, dim3(sb, w->slices_max, K), dim3(kNnThreads), 0, stream, S, 1, phase);
     } else {
-        hipLaunchKernelGGL(k_icp_reset_dev, dim3((n_src + 255) / 256, 1, K), dim3(256), 0, stream, S, phase);
-        hipLaunchKernelGGL(k_icp_nn_list, dim3(sb, w->slices_max, K), dim3(kNnThreads), 0, stream, S, 0, phase);
+        hipLaunchKernelGGL(k_icp_reset_dev<V>, dim3((n_src + 255) / 256, 1, K), dim3(256), 0, stream, S, phase);
+        hipLaunchKernelGGL(k_icp_nn_list<V>, dim3(sb, w->slices_max, K), dim3(kNnThreads), 0, stream, S, 0, phase);
     }
     return hipGetLastError();
 }
 
-hipError_t dev_sums(IcpWorkspace* w, hipStream_t stream, double max_d2, int phase)
+hipError_t dev_nearest(IcpWorkspace* w, hipStream_t stream, const IcpTuning& tune, int phase) { return dev_nearest_v(w, stream, tune, phase, w->S); }
+
+template <class V>
+hipError_t dev_sums_v(IcpWorkspace* w, hipStream_t stream, double max_d2, int phase, const V& S)
 {
-    const int rows = std::min((w->S.n_src + 255) / 256, kSumBlocks);
-    hipLaunchKernelGGL(k_icp_sums_dev, dim3(rows, 1, w->K), dim3(256), 0, stream, w->S, max_d2, phase);
-    hipLaunchKernelGGL(k_icp_fold_dev, dim3(1, 1, w->K), dim3(64), 0, stream, w->S, rows, phase);
+    const int rows = w->rows_max;
+    hipLaunchKernelGGL(k_icp_sums_dev<V>, dim3(rows, 1, w->K), dim3(256), 0, stream, S, max_d2, phase);
+    hipLaunchKernelGGL(k_icp_fold_dev<V>, dim3(1, 1, w->K), dim3(64), 0, stream, S, rows, phase);
     return hipGetLastError();
 }
+
+hipError_t dev_sums(IcpWorkspace* w, hipStream_t stream, double max_d2, int phase) { return dev_sums_v(w, stream, max_d2, phase, w->S); }
 
 // What the host loop (icp_align) asks per iteration, on the K = 1 layout: the brute-force search, then the sums with slot 0's
 // folded sums brought to h_sums and one wait. phase 1: the host closes the iteration, so no kernel looks at the block's `done`.
 hipError_t host_nearest(IcpWorkspace* w, hipStream_t stream)
 {
     const IcpSlots& S = w->S;
-    hipLaunchKernelGGL(k_icp_reset_dev, dim3((S.n_src + 255) / 256), dim3(256), 0, stream, S, 1);
+    hipLaunchKernelGGL(k_icp_reset_dev<IcpSlots>, dim3((S.n_src + 255) / 256), dim3(256), 0, stream, S, 1);
     hipLaunchKernelGGL(k_icp_nn, dim3((S.n_src + kNnThreads - 1) / kNnThreads, w->slices_max), dim3(kNnThreads), 0, stream,
                        (const float4*)S.cur[0], S.n_src, S.tgt[0], S.n_tgt[0], S.slice_len[0], S.best[0]);
     return hipGetLastError();
@@ -802,32 +1032,45 @@ hipError_t dev_mark(IcpWorkspace* w, hipStream_t stream)
     return hipEventRecord(w->ev, stream);
 }
 
-hipError_t dev_queue_range(IcpWorkspace* w, hipStream_t stream)
+template <class V>
+hipError_t dev_queue_range_v(IcpWorkspace* w, hipStream_t stream, const V& S)
 {
     IcpWorkspace::Flight& f = w->fl;
     const int n = std::min(kIcpRange, f.prm.max_iter - f.queued);
     const IcpCloseParams cp = icp_close_params(f.prm.max_iter, f.prm.trans_eps, f.prm.fit_eps);
     const double max_d2 = f.prm.max_corr_dist * f.prm.max_corr_dist;
     for (int k = 0; k < n; k++) {
-        ICP_TRY(dev_nearest(w, stream, f.tune, 0));
-        ICP_TRY(dev_sums(w, stream, max_d2, 0));
-        hipLaunchKernelGGL(k_icp_close, dim3(1, 1, w->K), dim3(64), 0, stream, w->S, cp);
-        hipLaunchKernelGGL(k_icp_transform_dev, dim3((f.n_src + 255) / 256, 1, w->K), dim3(256), 0, stream, w->S, 0);
+        ICP_TRY(dev_nearest_v(w, stream, f.tune, 0, S));
+        ICP_TRY(dev_sums_v(w, stream, max_d2, 0, S));
+        hipLaunchKernelGGL(k_icp_close<V>, dim3(1, 1, w->K), dim3(64), 0, stream, S, cp);
+        hipLaunchKernelGGL(k_icp_transform_dev<V>, dim3((f.n_src + 255) / 256, 1, w->K), dim3(256), 0, stream, S, 0);
         ICP_TRY(hipGetLastError());
     }
     f.queued += n;
     return dev_mark(w, stream);
 }
 
+hipError_t dev_queue_range(IcpWorkspace* w, hipStream_t stream)
+{
+    return w->fl.pairs ? dev_queue_range_v(w, stream, w->P) : dev_queue_range_v(w, stream, w->S);
+}
+
 // getFitnessScore() of every slot: the original source under the slot's final transformation, nearest distances with no limit
-hipError_t dev_queue_fitness(IcpWorkspace* w, hipStream_t stream)
+template <class V>
+hipError_t dev_queue_fitness_v(IcpWorkspace* w, hipStream_t stream, const V& S)
 {
     IcpWorkspace::Flight& f = w->fl;
-    ICP_TRY(load_slots(w, stream, f.d_src, nullptr, f.stride));
-    hipLaunchKernelGGL(k_icp_transform_dev, dim3((f.n_src + 255) / 256, 1, w->K), dim3(256), 0, stream, w->S, 1);
-    ICP_TRY(dev_nearest(w, stream, f.tune, 1));
-    ICP_TRY(dev_sums(w, stream, DBL_MAX, 1));
+    if constexpr (V::kPerPair) ICP_TRY(load_pairs(w, stream, f.stride, 1));
+    else ICP_TRY(load_slots(w, stream, f.d_src, nullptr, f.stride));
+    hipLaunchKernelGGL(k_icp_transform_dev<V>, dim3((f.n_src + 255) / 256, 1, w->K), dim3(256), 0, stream, S, 1);
+    ICP_TRY(dev_nearest_v(w, stream, f.tune, 1, S));
+    ICP_TRY(dev_sums_v(w, stream, DBL_MAX, 1, S));
     return dev_mark(w, stream);
+}
+
+hipError_t dev_queue_fitness(IcpWorkspace* w, hipStream_t stream)
+{
+    return w->fl.pairs ? dev_queue_fitness_v(w, stream, w->P) : dev_queue_fitness_v(w, stream, w->S);
 }
 
 }  // namespace
@@ -852,7 +1095,48 @@ hipError_t icp_dev_begin(IcpWorkspace* w, hipStream_t stream, const unsigned cha
     return hipSuccess;
 }
 
+hipError_t icp_pairs_begin(IcpWorkspace* w, hipStream_t stream, const unsigned char* const* d_src, const size_t* n_src,
+                           const unsigned char* const* d_tgt, const size_t* n_tgt, int n_pairs, size_t stride, const IcpParams& prm,
+                           const IcpTuning& tune, const float* const* guess)
+{
+    if (w->fl.phase != 0 || n_pairs < 1 || n_pairs > kIcpMaxPairs || prm.max_iter < 1) return hipErrorInvalidValue;
+    ICP_TRY(pairs_layout(w, n_pairs, d_src, n_src, d_tgt, n_tgt, tune, guess));
+    ICP_TRY(pairs_upload(w, stream));
+    ICP_TRY(load_pairs(w, stream, stride, 2));
+    ICP_TRY(load_pairs(w, stream, stride, 0));
+    ICP_TRY(dev_prepare_v(w, stream, tune, w->P, IcpPairGuesses{ 0 }));
+    IcpWorkspace::Flight& f = w->fl;
+    f = IcpWorkspace::Flight{};
+    f.pairs = true; f.n_src = w->n_src_max; f.stride = stride; f.prm = prm; f.tune = tune;
+    ICP_TRY(dev_queue_range(w, stream));
+    f.phase = 1;
+    return hipSuccess;
+}
+
+namespace {
+
+hipError_t advance(IcpWorkspace* w, hipStream_t stream, bool wait, bool* done, IcpResult* res);
+
+}  // namespace
+
 hipError_t icp_dev_advance(IcpWorkspace* w, hipStream_t stream, bool wait, bool* done, IcpResult* res)
+{
+    *done = false;
+    if (w->fl.pairs) return hipErrorInvalidValue;                         // (res holds kIcpMaxSlots results)
+    return advance(w, stream, wait, done, res);
+}
+
+hipError_t icp_pairs_advance(IcpWorkspace* w, hipStream_t stream, bool wait, bool* done, IcpResult* res)
+{
+    *done = false;
+    if (!w->fl.pairs) return hipErrorInvalidValue;
+    return advance(w, stream, wait, done, res);
+}
+
+namespace {
+
+// the step of either layout: K is the slots or the pairs, everything else is the flight's
+hipError_t advance(IcpWorkspace* w, hipStream_t stream, bool wait, bool* done, IcpResult* res)
 {
     IcpWorkspace::Flight& f = w->fl;
     *done = false;
@@ -889,6 +1173,8 @@ hipError_t icp_dev_advance(IcpWorkspace* w, hipStream_t stream, bool wait, bool*
     }
 }
 
+}  // namespace
+
 hipError_t icp_dev_nearest(IcpWorkspace* w, hipStream_t stream, const unsigned char* d_src, size_t n_src_, const unsigned char* d_tgt,
                            size_t n_tgt_, size_t stride, int mode, const IcpTuning& tune, unsigned long long* keys, int* n_fallback,
                            int reps, float* us_build, float* us_search)
@@ -911,7 +1197,7 @@ hipError_t icp_dev_nearest(IcpWorkspace* w, hipStream_t stream, const unsigned c
     if (e == hipSuccess && mode != 0) e = dev_prepare(w, stream, tune);
     if (e == hipSuccess && timed) e = hipEventRecord(e1, stream);
     for (int r = 0; e == hipSuccess && r < std::max(1, reps); r++) {
-        if (mode != 0 && r > 0) hipLaunchKernelGGL(k_icp_fold_dev, dim3(1), dim3(64), 0, stream, w->S, 0, 1);   // (zeroes the list count)
+        if (mode != 0 && r > 0) hipLaunchKernelGGL(k_icp_fold_dev<IcpSlots>, dim3(1), dim3(64), 0, stream, w->S, 0, 1);   // (zeroes the list count)
         e = mode != 0 ? dev_nearest(w, stream, tune, 1) : host_nearest(w, stream);
     }
     if (e == hipSuccess && timed) e = hipEventRecord(e2, stream);

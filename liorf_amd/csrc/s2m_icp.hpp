@@ -44,6 +44,7 @@ constexpr bool kIcpUseGrid = true;      // the device loop's search: the uniform
 constexpr float kIcpCellLeaves = 2.0f;  // grid cell edge in units of icp_leaf
 constexpr int kIcpShellCap = 3;         // largest Chebyshev radius (cells) searched before a point goes to the brute force
 constexpr int kIcpMaxSlots = 8;
+constexpr int kIcpMaxPairs = 64;         // alignments of the pair table (icp_pairs_*)
 
 struct IcpTuning { float cell; int shell_cap; int use_grid; };
 
@@ -63,6 +64,15 @@ hipError_t icp_dev_begin(IcpWorkspace* w, hipStream_t stream, const unsigned cha
 // *done: `res` holds the n_slots results, res[k] bit for bit what d_tgt[k] alone gives, and nothing is in flight any more.
 // d_src must stay as it was until then (the fitness pass reloads it).
 hipError_t icp_dev_advance(IcpWorkspace* w, hipStream_t stream, bool wait, bool* done, IcpResult* res);
+// The table form: n_pairs <= kIcpMaxPairs independent alignments, pair k with its own source (d_src[k], n_src[k] > 0), target
+// (d_tgt[k], n_tgt[k] > 0) and guess (guess: null, or n_pairs pointers as icp_dev_begin takes them), advanced by the same launches
+// through the same kernels: the pairs' descriptions go to the device once, as a table, and a kernel finds its pair by blockIdx.z.
+// The contract is icp_dev_begin's / icp_dev_advance's: ranges of kIcpRange, a pair that has ended idles, one fitness pass for
+// all, res[k] (n_pairs results) bit for bit what icp_align gives for pair k alone, the sources untouched until *done.
+hipError_t icp_pairs_begin(IcpWorkspace* w, hipStream_t stream, const unsigned char* const* d_src, const size_t* n_src,
+                           const unsigned char* const* d_tgt, const size_t* n_tgt, int n_pairs, size_t stride, const IcpParams& prm,
+                           const IcpTuning& tune, const float* const* guess = nullptr);
+hipError_t icp_pairs_advance(IcpWorkspace* w, hipStream_t stream, bool wait, bool* done, IcpResult* res);
 // one nearest-neighbour search of src against tgt, synchronously: mode 0 the host loop's search (k_icp_nn: nn_tiles over every
 // source), mode 1 the device loop's search (the grid with its fallback, or with tune.use_grid off k_icp_nn_list over every
 // source). keys: host, n_src entries of (fp32 d2 bits << 32 | target index), ~0 = no match. reps > 0: the search `reps`

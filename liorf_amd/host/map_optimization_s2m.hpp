@@ -8,9 +8,11 @@
 // call scan2MapOptimization(), read transformTobeMapped / isDegenerate /
 // incrementalOdometryAffineBack.  All arithmetic runs in the HIP library; there is no CPU path here.
 #pragma once
+#include <algorithm>
 #include <cmath>
 #include <cstdint>
 #include <cstring>
+#include <functional>
 #include <stdexcept>
 #include <string>
 #include <utility>
@@ -698,6 +700,53 @@ public:
         for (size_t k = 0; k < rows.size(); k++)
             for (const s2m_sc_hit& hit : rows[k]) out.push_back(SessionLoop{ (int32_t)k, hit.key, hit.dist, hit.yaw_diff_rad });
         return out;
+    }
+
+    // s2m_loop_verify_many: the candidate rows of many keys verified in one call, row r what loopVerify(rows[r].key_cur,
+    // rows[r].key_pre, base_key) gives in turn (records, best, the container). A row without candidates gives no records and -1.
+    struct VerifyRow { int32_t key_cur; std::vector<int32_t> key_pre; };
+    struct VerifiedRow { std::vector<s2m_loop_result> records; int32_t best; };
+    std::vector<VerifiedRow> loopVerifyMany(const std::vector<VerifyRow>& rows, int base_key = -1)
+    {
+        const s2m_loop_params p = loopParams();
+        size_t stride = 1;
+        for (const VerifyRow& r : rows) stride = std::max(stride, r.key_pre.size());
+        std::vector<int32_t> key_cur(rows.size()), n_cand(rows.size()), best(rows.size(), -1), key_pre(rows.size() * stride, 0);
+        for (size_t r = 0; r < rows.size(); r++) {
+            key_cur[r] = rows[r].key_cur;
+            n_cand[r] = (int32_t)rows[r].key_pre.size();
+            std::copy(rows[r].key_pre.begin(), rows[r].key_pre.end(), key_pre.begin() + r * stride);
+        }
+        std::vector<s2m_loop_result> recs(rows.size() * stride, s2m_loop_result{});
+        check(s2m_loop_verify_many(h_, key_cur.data(), key_pre.data(), n_cand.data(), (int32_t)rows.size(), (int32_t)stride, base_key, &p,
+                                   recs.data(), best.data()), "s2m_loop_verify_many");
+        std::vector<VerifiedRow> out(rows.size());
+        for (size_t r = 0; r < rows.size(); r++) {
+            out[r].records.assign(recs.begin() + r * stride, recs.begin() + r * stride + n_cand[r]);
+            out[r].best = best[r];
+        }
+        return out;
+    }
+    // findSessionLoops' query followed by loopVerifyMany in chunks of rows_per_call rows: the winning records, one per key that has
+    // an accepted candidate, in key_cur order. between_chunks (may be empty) is called after every chunk: a node releases the scan
+    // handler's lock there and takes it again, so the lock is held for rows_per_call rows at a time.
+    std::vector<s2m_loop_result> verifySessionLoops(int gap, double max_dist, int top_k, int align, int base_key, int rows_per_call,
+                                                    const std::function<void()>& between_chunks = {})
+    {
+        std::vector<VerifyRow> rows;
+        for (const SessionLoop& c : findSessionLoops(gap, max_dist, std::min(top_k, (int)S2M_LOOP_MAX_CANDIDATES), align)) {
+            if (rows.empty() || rows.back().key_cur != c.key_cur) rows.push_back(VerifyRow{ c.key_cur, {} });
+            rows.back().key_pre.push_back(c.key_pre);
+        }
+        std::vector<s2m_loop_result> won;
+        const size_t step = (size_t)std::max(rows_per_call, 1);
+        for (size_t i = 0; i < rows.size(); i += step) {
+            const std::vector<VerifyRow> chunk(rows.begin() + i, rows.begin() + std::min(rows.size(), i + step));
+            for (const VerifiedRow& v : loopVerifyMany(chunk, base_key))
+                if (v.best >= 0) won.push_back(v.records[(size_t)v.best]);
+            if (between_chunks) between_chunks();
+        }
+        return won;
     }
 
     // void performSCLoopClosure() (:624-730): the ScanContext detector on this handle, then the store's extraction and ICP

@@ -48,6 +48,8 @@ ABI_SYMBOLS = [
     "s2m_loop_default_params", "s2m_loop_near_keyframes", "s2m_loop_align", "s2m_loop_closure_rs",
     "s2m_loop_align_launch", "s2m_loop_closure_rs_launch", "s2m_loop_poll", "s2m_loop_collect",
     "s2m_loop_verify_check_args", "s2m_loop_verify_launch", "s2m_loop_verify_poll", "s2m_loop_verify_collect", "s2m_loop_verify",
+    "s2m_loop_verify_many_check_args", "s2m_loop_verify_many", "s2m_debug_icp_align_pairs_device",
+    "s2m_debug_loop_verify_many_pass", "s2m_debug_loop_verify_many_last", "s2m_debug_loop_verify_many_plan",
     "s2m_reloc_default_params", "s2m_relocalize_check_args", "s2m_relocalize_scan", "s2m_debug_icp_align_guess_many_device",
     "s2m_debug_icp_nearest", "s2m_debug_icp_time_nearest", "s2m_debug_icp_align_device", "s2m_debug_icp_align_many_device",
     "s2m_debug_icp_tuning", "s2m_debug_icp_grid_check_args", "s2m_debug_icp_grid",
@@ -73,6 +75,7 @@ S2M_KF_FROM_HOST, S2M_KF_FROM_DEVICE, S2M_KF_FROM_LAST_DOWNSAMPLE = 0, 1, 2
 S2M_LOOP_NONE, S2M_LOOP_ALREADY_CLOSED, S2M_LOOP_TOO_FEW_POINTS, S2M_LOOP_REJECTED, S2M_LOOP_ACCEPTED = 0, 1, 2, 3, 4
 S2M_LOOP_PENDING = 5                                     # a launched closure whose ICP is still queued or running
 S2M_LOOP_MAX_CANDIDATES = 8                              # candidates of one verification: the slots of the device loop
+S2M_LOOP_MANY_MAX_PAIRS = 64      # pairs of one pass of s2m_loop_verify_many
 S2M_DEBUG_PREP_READ, S2M_DEBUG_PREP_NEW, S2M_DEBUG_PREP_LEGACY = -1, 0, 1   # chains of s2m_debug_scan_prep (liorf_s2m_debug.h)
 S2M_ICP_RANGE = 8                                        # iterations the device loop queues at a time (liorf_s2m_debug.h)
 S2M_DEBUG_ICP_GRID_MAX_CELLS = 1 << 18                   # most cells of a grid of the device loop's search (liorf_s2m_debug.h)
@@ -397,6 +400,13 @@ def load_library(path: str | None = None) -> C.CDLL:
     L.s2m_loop_verify.argtypes = L.s2m_loop_verify_launch.argtypes
     L.s2m_loop_verify_poll.argtypes = [vp, C.POINTER(LoopResult), C.c_int32, i32p, i32p]
     L.s2m_loop_verify_collect.argtypes = L.s2m_loop_verify_poll.argtypes
+    L.s2m_loop_verify_many_check_args.argtypes = [C.c_int32, i32p, i32p, i32p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(LoopParams)]
+    L.s2m_loop_verify_many.argtypes = [vp, i32p, i32p, i32p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(LoopParams), C.POINTER(LoopResult), i32p]
+    L.s2m_debug_icp_align_pairs_device.argtypes = [vp, C.POINTER(C.c_void_p), szp, C.POINTER(C.c_void_p), szp, C.c_int32, C.c_size_t,
+                                                   C.POINTER(C.c_void_p), C.POINTER(IcpParams), C.POINTER(IcpResult)]
+    L.s2m_debug_loop_verify_many_pass.argtypes = [vp, C.c_int32]
+    L.s2m_debug_loop_verify_many_last.argtypes = [vp, i32p, i32p, szp]
+    L.s2m_debug_loop_verify_many_plan.argtypes = [i32p, C.c_int32, C.c_int32, i32p, i32p]
     L.s2m_debug_icp_align_many_device.argtypes = [vp, vp, C.c_size_t, C.POINTER(C.c_void_p), szp, C.c_int32, C.c_size_t, C.POINTER(IcpParams),
                                                   C.POINTER(IcpResult)]
     L.s2m_debug_icp_align_guess_many_device.argtypes = [vp, vp, C.c_size_t, C.POINTER(C.c_void_p), szp, fp, C.c_int32, C.c_size_t,
@@ -1596,6 +1606,67 @@ class MapOptimizationS2M:
         """s2m_loop_verify_collect: loopVerifyPoll() with waits - the final records of the pending verification."""
         return self._verify_poll(self.lib.s2m_loop_verify_collect, "s2m_loop_verify_collect")
 
+    # -- verification of many keys: the rows of scQueryKeys in one call (DESIGN.md section 12) ---------------------------
+    def loopVerifyMany(self, rows, base_key: int = -1, params: LoopParams | None = None):
+        """s2m_loop_verify_many: rows = [(key_cur, [key_pre...]), ...] -> (records per row, best per row), each row what
+        loopVerify(key_cur, key_pre, base_key, params) gives in turn; a row without candidates gives ([], -1)."""
+        key_cur, key_pre, n_cand, stride = _verify_many_rows(rows)
+        m = len(rows)
+        recs = (LoopResult * max(m * stride, 1))()
+        best = (C.c_int32 * max(m, 1))(*([-1] * max(m, 1)))
+        pp = C.byref(params) if params is not None else None
+        self._check(self.lib.s2m_loop_verify_many(self.h, key_cur, key_pre, n_cand, m, stride, int(base_key), pp, recs, best), "s2m_loop_verify_many")
+        return ([[_copy_struct(recs[r * stride + i]) for i in range(n_cand[r])] for r in range(m)], [best[r] for r in range(m)])
+
+    def verifySessionLoops(self, gap: int = 30, max_dist: float = 0.3, top_k: int = 1, align: int = S2M_SC_ALIGN_FULL, base_key: int = 0,
+                           params: LoopParams | None = None, rows_per_call: int = 64):
+        """findSessionLoops' query followed by loopVerifyMany in chunks of rows_per_call rows (a node releases its lock between
+        chunks): the winning records, one per key that has an accepted candidate, in key_cur order."""
+        top_k = min(int(top_k), S2M_LOOP_MAX_CANDIDATES)
+        n = self.scSize()
+        hits = self.scQueryKeys(np.arange(n, dtype=np.int32), top_k=top_k, align=align, max_dist=max_dist, rel_lo=1 - int(gap), rel_hi=2**31 - 1)
+        rows = [(cur, [int(h["key"]) for h in row]) for cur, row in enumerate(hits) if len(row)]
+        won = []
+        for i in range(0, len(rows), max(int(rows_per_call), 1)):
+            recs, best = self.loopVerifyMany(rows[i:i + max(int(rows_per_call), 1)], base_key, params)
+            won += [r[b] for r, b in zip(recs, best) if b >= 0]
+        return won
+
+    def debugLoopVerifyManyPass(self, pairs_per_pass: int = 0):
+        """s2m_debug_loop_verify_many_pass: the pairs of a pass of loopVerifyMany (0: the default; clamped to [8, 64])."""
+        self._check(self.lib.s2m_debug_loop_verify_many_pass(self.h, int(pairs_per_pass)), "s2m_debug_loop_verify_many_pass")
+
+    def debugLoopVerifyManyLast(self):
+        """s2m_debug_loop_verify_many_last: (passes, pairs aligned, bytes held for the submaps of a pass) of the last loopVerifyMany."""
+        n, k, b = C.c_int32(0), C.c_int32(0), C.c_size_t(0)
+        self._check(self.lib.s2m_debug_loop_verify_many_last(self.h, C.byref(n), C.byref(k), C.byref(b)), "s2m_debug_loop_verify_many_last")
+        return n.value, k.value, b.value
+
+    def debugIcpAlignPairsDevice(self, pairs, guesses=None, **params):
+        """s2m_debug_icp_align_pairs_device: pairs = [(source, target), ...] through the table form of the device loop (no size
+        gate), guesses None or one entry per pair (None or a 4x4): a list of (T 4x4, hasConverged, getFitnessScore, iterations)."""
+        sr = [_records(a) for a, _ in pairs]
+        tg = [_records(b) for _, b in pairs]
+        st = sr[0][2] if sr else 0
+        if any(t[2] != st for t in sr + tg):
+            raise ValueError("all clouds must share one record stride")
+        p = IcpParams()
+        self.lib.s2m_icp_default_params(C.byref(p))
+        for k, v in params.items():
+            setattr(p, k, v)
+        P = len(pairs)
+        sp = (C.c_void_p * max(P, 1))(*[t[0].ctypes.data for t in sr])
+        sn = (C.c_size_t * max(P, 1))(*[t[1] for t in sr])
+        tp = (C.c_void_p * max(P, 1))(*[t[0].ctypes.data for t in tg])
+        tn = (C.c_size_t * max(P, 1))(*[t[1] for t in tg])
+        gs = None
+        if guesses is not None:
+            keep = [None if g is None else np.ascontiguousarray(g, np.float32).reshape(16) for g in guesses]
+            gs = (C.c_void_p * max(P, 1))(*[None if g is None else g.ctypes.data for g in keep])
+        out = (IcpResult * max(P, 1))()
+        self._check(self.lib.s2m_debug_icp_align_pairs_device(self.h, sp, sn, tp, tn, P, st, gs, C.byref(p), out), "s2m_debug_icp_align_pairs_device")
+        return [(np.array(r.T, np.float32).reshape(4, 4), bool(r.converged), r.fitness_score, r.iterations) for r in out[:P]]
+
     def performSCLoopClosureVerified(self, top_k: int = 4, params: LoopParams | None = None, **query):
         """performSCLoopClosure() on the place query: the top_k <= S2M_LOOP_MAX_CANDIDATES hits of scQueryKey for the newest key
         (keyword arguments go to the query) verified in lockstep, SC form (base_key 0). The hits come ordered by descriptor
@@ -1849,6 +1920,48 @@ def loop_verify_check_args(n_stored: int, key_cur: int, key_pre, base_key: int =
     keys = None if key_pre is None else (C.c_int32 * max(len(key_pre), 1))(*[int(k) for k in key_pre])
     n = n_cand if n_cand is not None else (0 if key_pre is None else len(key_pre))
     return load_library().s2m_loop_verify_check_args(n_stored, key_cur, keys, n, base_key, None if params is None else C.byref(params))
+
+
+def _verify_many_rows(rows):
+    """rows = [(key_cur, [key_pre...]), ...] as the arrays of s2m_loop_verify_many: (key_cur, key_pre, n_cand, row_stride)."""
+    m = len(rows)
+    stride = max([len(c) for _, c in rows] + [1])
+    key_cur = (C.c_int32 * max(m, 1))(*[int(k) for k, _ in rows])
+    n_cand = (C.c_int32 * max(m, 1))(*[len(c) for _, c in rows])
+    key_pre = (C.c_int32 * max(m * stride, 1))()
+    for r, (_, c) in enumerate(rows):
+        for i, k in enumerate(c):
+            key_pre[r * stride + i] = int(k)
+    return key_cur, key_pre, n_cand, stride
+
+
+def loop_verify_many_check_args(n_stored: int, rows, base_key: int = -1, params: "LoopParams | None" = None, m=None, row_stride=None,
+                                n_cand=None) -> int:
+    """s2m_loop_verify_many_check_args (host only, no GPU): the status code. rows as loopVerifyMany takes them (None: null
+    arrays); m, row_stride and n_cand override what the rows imply."""
+    if rows is None:
+        key_cur = key_pre = nc = None
+        mm, stride = 0, 1
+    else:
+        key_cur, key_pre, nc, stride = _verify_many_rows(rows)
+        mm = len(rows)
+    if n_cand is not None:
+        nc = (C.c_int32 * max(len(n_cand), 1))(*[int(v) for v in n_cand])
+    return load_library().s2m_loop_verify_many_check_args(n_stored, key_cur, key_pre, nc, mm if m is None else m,
+                                                          stride if row_stride is None else row_stride, base_key,
+                                                          None if params is None else C.byref(params))
+
+
+def loop_verify_many_plan(n_cand, pairs_per_pass: int = 0):
+    """s2m_debug_loop_verify_many_plan (host only, no GPU): the first row of every pass and, last, m."""
+    m = len(n_cand)
+    nc = (C.c_int32 * max(m, 1))(*[int(v) for v in n_cand])
+    first = (C.c_int32 * (m + 1))()
+    n_pass = C.c_int32(0)
+    rc = load_library().s2m_debug_loop_verify_many_plan(nc, m, int(pairs_per_pass), first, C.byref(n_pass))
+    if rc != 0:
+        raise RuntimeError(f"s2m_debug_loop_verify_many_plan failed ({rc})")
+    return [first[k] for k in range(n_pass.value + 1)]
 
 
 def loop_verify_best(records) -> int:

@@ -32,6 +32,16 @@ search radius 15 m, search_num 25, ICP leaf 0.5, fitness 0.3, time window 30 s. 
     sequential_ms        (c) the same K through K s2m_loop_align_launch + s2m_loop_collect pairs one after the other - the baseline;
                          (a) and (c) take turns in one process after warm-up, medians of at least 10 repetitions, with (c)'s
                          min-max spread; meets_bar: (a) is below (c) by more than that spread (K = 1: not above it by more)
+  python tools/bench_loop.py --verify-many             only profiles/loop_verify_many_bench_line.json (--verify-many-out): on the first store of
+                                                       --sizes (5 000 keys) the last m = 16, 64, 256 keys as rows, each against the K = 4
+                                                       nearest of its RS radius candidates (a row may have fewer, or none), fitness -1;
+                                                       and, as "first28", keys 0 .. 27 as rows - the keys that hold real frames, so
+                                                       that every pair passes the size gates (--verify-many-cases picks the cases),
+    many_ms              (a) s2m_loop_verify_many over the rows, one call
+    loop_ms              (b) a loop of s2m_loop_verify over the same rows through the raw C call - the baseline; the rows of (a) and
+                         (b) are compared as bytes before anything is timed; (a) and (b) take turns after two warm-up rounds,
+                         medians of at least 5 repetitions with min .. max; meets_bar at m = 64: (a) below (b) by more than (b)'s own
+                         min .. max spread, at m = 16: (a) not above (b)
   python tools/bench_loop.py --relocalize              only profiles/relocalize_bench_line.json (--relocalize-out): the first store of
                                                        --sizes (5 000 keys) with every key's descriptor in the ScanContext store, and a
                                                        30 000-point frame cast 0.7 m beside key 10 and turned by 0.5 rad as the query,
@@ -100,8 +110,9 @@ def _stats(path):
     with open(path) as f:
         for r in csv.DictReader(f):
             m = re.search(r"k_loop_detect\w*|k_icp\w*", r.get("Name", ""))
-            if m:
-                rows[m.group(0)] = {"calls": int(r["Calls"]), "avg_us": round(float(r["AverageNs"]) / 1e3, 3)}
+            if m:                                                  # (the loop's kernels are templates: the table form apart)
+                name = m.group(0) + ("<pairs>" if "IcpPair" in r.get("Name", "") else "")
+                rows[name] = {"calls": int(r["Calls"]), "avg_us": round(float(r["AverageNs"]) / 1e3, 3)}
     return rows
 
 
@@ -275,6 +286,92 @@ def _verify_main(a, s2m, sizes):
         f.write(json.dumps(out) + "\n")
 
 
+def _verify_many_main(a, s2m, n):
+    """s2m_loop_verify_many against the loop of s2m_loop_verify it stands for, on the revisit store of --verify."""
+    true = _true_poses(n)
+    big = _clouds([true[k] for k in range(N_BIG)] + [true[-1]])
+    small = big[1][:SMALL_PTS].copy()
+    stored = true.copy()
+    stored[-1] += DRIFT
+    stored = stored.astype(np.float32)
+    times = np.arange(n, dtype=np.float64)
+    eng = s2m.MapOptimizationS2M()
+    for k in range(n):
+        eng.saveKeyFrame(stored[k], times[k], big[k] if k < N_BIG else (big[-1] if k == n - 1 else small))
+    print(f"{n} keys stored", file=sys.stderr, flush=True)
+    rej = s2m.default_loop_params(search_radius=15.0, search_num=25, icp_leaf=0.5, fitness_score=-1.0)
+    lib, h = eng.lib, eng.h
+    K = 4
+    reps = max(a.reps, 5)
+    xyz = stored[:, :3].astype(np.float64)
+    out = {"workload": "tools/bench_loop.py --verify-many: the revisit of --verify; rows are the last m keys, each against the K = 4 nearest of "
+                       "its RS radius candidates (R 15 m, 30 s; fewer where it has fewer), s2m_loop_verify_many against a loop of "
+                       "s2m_loop_verify over the same rows; search_num 25, leaf 0.5, fitness -1",
+           "keys": n, "reps": reps, "warmup": 2, "m": {}}
+    for case in a.verify_many_cases.split(","):
+        # the last m keys; or "first28": keys 0 .. 27, the ones that hold real frames, so that every row passes the size gates
+        cur_keys = list(range(N_BIG)) if case == "first28" else list(range(n - int(case), n))
+        m = len(cur_keys)
+        rows = []
+        for kc in cur_keys:
+            d = np.linalg.norm(xyz - xyz[kc], axis=1)
+            near = [int(k) for k in np.argsort(d, kind="stable") if k != kc and d[k] <= 15.0 and abs(times[k] - times[kc]) > 30.0]
+            rows.append((kc, near[:K]))
+        key_cur, key_pre, n_cand, stride = s2m._verify_many_rows(rows)
+        size = C.sizeof(s2m.LoopResult)
+        recs_a, recs_b = (s2m.LoopResult * (m * stride))(), (s2m.LoopResult * (m * stride))()
+        best_a, best_b = (C.c_int32 * m)(), (C.c_int32 * m)()
+
+        def many():
+            t0 = time.perf_counter()
+            rc = lib.s2m_loop_verify_many(h, key_cur, key_pre, n_cand, m, stride, -1, C.byref(rej), recs_a, best_a)
+            assert rc == 0, rc
+            return time.perf_counter() - t0
+
+        def loop():
+            t0 = time.perf_counter()
+            for r in range(m):
+                best_b[r] = -1
+                if n_cand[r]:
+                    rc = lib.s2m_loop_verify(h, key_cur[r], C.cast(C.byref(key_pre, 4 * r * stride), C.POINTER(C.c_int32)), n_cand[r], -1,
+                                             C.byref(rej), C.cast(C.byref(recs_b, size * r * stride), C.POINTER(s2m.LoopResult)),
+                                             C.cast(C.byref(best_b, 4 * r), C.POINTER(C.c_int32)))
+                    assert rc == 0, rc
+            return time.perf_counter() - t0
+
+        many(); loop()                                           # the rows as bytes, before anything is timed
+        for r in range(m):
+            for i in range(n_cand[r]):
+                ga, gb = recs_a[r * stride + i], recs_b[r * stride + i]
+                assert C.string_at(C.addressof(ga), size) == C.string_at(C.addressof(gb), size), (m, r, i, ga.status, gb.status)
+        assert list(best_a) == list(best_b)
+        passes, pairs, nbytes = eng.debugLoopVerifyManyLast()
+        status = [recs_a[r * stride + i].status for r in range(m) for i in range(n_cand[r])]
+        many(); loop()                                           # two warm-up rounds with the one above
+        ta, tb = [], []
+        for _ in range(reps):                                    # the two sides take turns
+            ta.append(many()); tb.append(loop())
+        ms = lambda v: round(1e3 * float(v), 4)
+        r = {"rows_with_candidates": int(sum(1 for v in n_cand if v)), "candidates": int(sum(n_cand)), "pairs_aligned": pairs, "passes": passes,
+             "submap_bytes": nbytes, "status_counts": {str(k): status.count(k) for k in sorted(set(status))},
+             "iterations": [recs_a[r * stride + i].icp.iterations for r in range(m) for i in range(n_cand[r])],
+             "many_ms": ms(np.median(ta)), "many_min_ms": ms(min(ta)), "many_max_ms": ms(max(ta)),
+             "loop_ms": ms(np.median(tb)), "loop_min_ms": ms(min(tb)), "loop_max_ms": ms(max(tb))}
+        r["loop_spread_ms"] = round(r["loop_max_ms"] - r["loop_min_ms"], 4)
+        r["saved_ms"] = round(r["loop_ms"] - r["many_ms"], 4)
+        if pairs:
+            r["many_ms_per_pair"] = round(r["many_ms"] / pairs, 4)
+            r["loop_ms_per_pair"] = round(r["loop_ms"] / pairs, 4)
+        r["meets_bar"] = bool(r["saved_ms"] > r["loop_spread_ms"]) if m >= 64 or case == "first28" else bool(r["saved_ms"] >= 0.0)
+        out["m"][case] = r
+    eng.close()
+    out["note"] = ("wall clock on the host; the call and the loop take turns in one process after two warm-up rounds, medians with min .. max; "
+                   "meets_bar: m >= 64 saved_ms > the loop's own min .. max spread, m = 16 the call is not slower than the loop")
+    print(json.dumps(out))
+    with open(a.verify_many_out, "w") as f:
+        f.write(json.dumps(out) + "\n")
+
+
 def _relocalize_main(a, s2m, n):
     from liorf_amd import synth
     true = _true_poses(n)
@@ -327,6 +424,9 @@ def main(argv=None):
     ap.add_argument("--relocalize-out", default=os.path.join(ROOT, "profiles", "relocalize_bench_line.json"))
     ap.add_argument("--verify", action="store_true", help="measure the lockstep verification against sequential closures, and nothing else")
     ap.add_argument("--verify-out", default=os.path.join(ROOT, "profiles", "loop_verify_bench_line.json"))
+    ap.add_argument("--verify-many", action="store_true", help="measure s2m_loop_verify_many against a loop of s2m_loop_verify, and nothing else")
+    ap.add_argument("--verify-many-out", default=os.path.join(ROOT, "profiles", "loop_verify_many_bench_line.json"))
+    ap.add_argument("--verify-many-cases", default="16,64,256,first28", help="m = the last m keys as rows; first28 = keys 0 .. 27 as rows")
     ap.add_argument("--sizes", default="5000,50000")
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--reps", type=int, default=10)
@@ -347,6 +447,8 @@ def main(argv=None):
     sizes = [int(s) for s in a.sizes.split(",")]
     if a.verify:
         return _verify_main(a, s2m, sizes)
+    if a.verify_many:
+        return _verify_many_main(a, s2m, sizes[0])
     if a.relocalize:
         return _relocalize_main(a, s2m, sizes[0])
     out = {"workload": "revisit: 30 000-point frames at keys 0..27 and the last key, 1 000 points elsewhere; R 15, search_num 25, "
