@@ -959,6 +959,17 @@ int  s2m_relocalize_check_args(int32_t n_sc, int32_t n_kf, const s2m_reloc_param
 int  s2m_relocalize_scan(s2m_handle h, const void* pts, size_t n, size_t stride_bytes, int on_device,
                          const s2m_reloc_params* p /* NULL = defaults */,
                          s2m_reloc_candidate* out /* top_k records */, int32_t* n_out, int32_t* best);
+/* s2m_relocalize_scan for a key the store already holds: "where is key k of an appended, still unplaced session in the
+ * rest of the map". The query is the key's stored descriptor, as s2m_sc_query_key(p->query); the source is the key's own
+ * records in its own frame, read straight from the store on the device through the VoxelGrid at loop.icp_leaf. The target
+ * submap of a hit is loopFindNearKeyframes(hit.key, search_num, -1) with its neighbours CLAMPED to the searched range
+ * [query.first, query.first + query.count) of the query: a submap at the boundary never takes keys of the other session.
+ * Guess, lockstep alignment, gates, records and *best are steps 4 to 6 above; with descriptors that were made from the stored
+ * clouds and a range that holds every hit's neighbours the records are byte for byte s2m_relocalize_scan of the key's cloud.
+ * Read-only; S2M_ERR_BUSY as there. A key outside the key-frame store, or without a descriptor: S2M_ERR_INVALID_ARG. A key
+ * without records: S2M_OK with no records. */
+int  s2m_relocalize_key(s2m_handle h, int32_t key, const s2m_reloc_params* p /* NULL = defaults */,
+                        s2m_reloc_candidate* out /* top_k records */, int32_t* n_out, int32_t* best);
 
 /* ---- Pose graph: factors, optimise, correct the key-frame store --------------------------------------------------
  * saveKeyFramesAndFactor() with addOdomFactor / addGPSFactor / addLoopFactor (reference src/mapOptmization.cpp:1386-1534)
@@ -1147,6 +1158,64 @@ int  s2m_session_load(s2m_handle h, s2m_session_read_fn r, void* user, s2m_sessi
 int  s2m_session_save_file(s2m_handle h, const char* path);
 int  s2m_session_load_file(s2m_handle h, const char* path, s2m_session_info* out /* may be NULL */);
 int  s2m_session_check(const void* blob, size_t bytes, s2m_session_info* out /* may be NULL */);
+
+/* ---- Appending a saved session behind the stored keys, and placing it -----------------
+ * With N0 keys in the handle (session A), a blob of session B (format version 1, unchanged) becomes keys N0 .. N0+nK-1.
+ * A "state" is 12 doubles {R row-major, t}; the state of a float pose is Rot3::RzRyRx of it in fp64 with libm, as
+ * s2m_pg_set_initial makes it; A o X is R' = A_R R, t' = A_R t + A_t, every entry ((a0 b0 + a1 b1) + a2 b2) in fp64 without
+ * contraction, the translation that sum plus A_t.
+ *   s2m_session_append: anchor_xyzrpy NULL = "as stored": nothing is composed, every pose and estimate keeps its bits (an
+ *       identity anchor is not the same: it would turn -0.0 into +0.0). Otherwise A = the state of the anchor, and
+ *         - a key's store pose becomes the float read-out (s2m_pg_get_poses' rule) of A o state(stored pose), its position
+ *           record and cached transform follow from those floats as s2m_pg_apply_to_store makes them;
+ *         - an estimate X becomes A o X; a prior's state P becomes A o P; a GPS factor's z becomes A_R z + A_t with its
+ *           variances as stored - the diagonal covariance is NOT rotated; a between factor is unchanged.
+ *       Times, point counts and records are kept as stored, byte for byte, in arena space behind A's keys, so the next
+ *       s2m_kf_add continues as after nK adds. Descriptors go behind the store's own; n_search and the detector's counter
+ *       stay the handle's. A stored loop pair (cur, pre) becomes (cur + N0, pre + N0). Factors keep their order with keys
+ *       + N0, behind one new factor, the junction: between(N0-1 -> N0), robust_k 0, variances junction_var (NULL: 1.0 for
+ *       all six - loose beside an odometry or loop factor), measured X[N0-1]^-1 o X'[N0] at the appended estimates, so its
+ *       residual there is rounding-sized. It gives the merged graph the odometry chain s2m_pg_optimize needs.
+ *       Preconditions, judged from the blob's header alone (S2M_ERR_INVALID_ARG, nothing touched): N0 >= 1 (an empty handle
+ *       is s2m_session_load's); N0 + nK <= 2^24; with descriptors in the blob s2m_sc_size == N0 and nD <= nK; with variables
+ *       in the blob the graph holds exactly N0 variables and nV <= nK; a finite anchor; positive finite variances.
+ *       s2m_session_append_check_args gives that verdict from two s2m_session_info on the host, without a handle.
+ *       S2M_ERR_BUSY exactly when save and load return it. B's variable 0 or A's variable N0-1 without a value is
+ *       S2M_ERR_INVALID_ARG, found when the variables have arrived; a placed result that is not finite likewise.
+ *       A failure at ANY point - a callback, an early end, a checksum, the content, a HIP error, the two late checks - leaves
+ *       all four containers exactly as they were before the call (not emptied), arena blocks taken by the call released.
+ *       Status codes and their order are s2m_session_load's. info_out (may be NULL): what the blob holds, the first new key
+ *       and the junction's index in the factor list (-1: the blob has no variables).
+ *   s2m_session_place: moves the session appended last by D = the state of move_xyzrpy: X <- D o X for its variables, its
+ *       store poses likewise, priors and GPS factors of its keys as above, the junction measured again at the new estimates.
+ *       Keys added after the append are not moved. One kernel launch (k_session_place) and one wait. Append with anchor A is,
+ *       byte for byte, append with NULL followed by s2m_session_place(A). No appended session: S2M_ERR_INVALID_ARG; anything
+ *       pending: S2M_ERR_BUSY; a result that is not finite: S2M_ERR_INVALID_ARG, handle as before.
+ *   s2m_session_appended: the key range [first, first + count) of the session appended last, -1 and 0 when there is none:
+ *       s2m_kf_reset, s2m_pg_reset and s2m_session_load forget it.
+ *   s2m_session_anchor_from_pairs: host only, fp64, libm, no handle. Pair i (a pose of session B in B's frame, the same
+ *       pose in the map's frame, both {x, y, z, roll, pitch, yaw}) gives A_i = state(map_i) o state(session_i)^-1. j supports
+ *       i when |A_i.t - A_j.t| <= tol_m and acos(clamp((trace(A_i.R^T A_j.R) - 1) / 2)) <= tol_rad. anchor_out is the A_i
+ *       with the most supporters (itself included; ties: the least summed translation distance to its supporters, then the
+ *       lower index) read out as floats by s2m_pg_get_poses' rule. No averaging: one wrong pair must not bend the anchor.
+ *       *n_inliers, *chosen (either may be NULL): its supporters and i. m <= 0, null arrays, tolerances that are negative
+ *       or not finite, or inputs that are not finite: S2M_ERR_INVALID_ARG.
+ * A merged handle keeps B's key times as they are (the recent-keys rule of s2m_extract_surrounding reads them so), and
+ * index neighbourhoods cross the boundary: loop submaps around N0-1 / N0 take keys of the other session. */
+typedef struct s2m_session_append_info {
+    s2m_session_info blob;
+    int32_t first_key, junction_factor;
+} s2m_session_append_info;
+int  s2m_session_append_check_args(const s2m_session_info* have, const s2m_session_info* blob_info, const float* anchor_xyzrpy /* NULL: as stored */,
+                                   const double* junction_var /* NULL: 1.0 x 6 */);
+int  s2m_session_append(s2m_handle h, s2m_session_read_fn r, void* user, const float* anchor_xyzrpy, const double* junction_var,
+                        s2m_session_append_info* info_out /* may be NULL */);
+int  s2m_session_append_file(s2m_handle h, const char* path, const float* anchor_xyzrpy, const double* junction_var,
+                             s2m_session_append_info* info_out /* may be NULL */);
+int  s2m_session_place(s2m_handle h, const float move_xyzrpy[6]);
+int  s2m_session_appended(s2m_handle h, int32_t* first, int32_t* count);
+int  s2m_session_anchor_from_pairs(const float* pose_in_session, const float* pose_in_map, int32_t m, double tol_m, double tol_rad,
+                                   float anchor_out[6], int32_t* n_inliers, int32_t* chosen);
 
 #ifdef __cplusplus
 }

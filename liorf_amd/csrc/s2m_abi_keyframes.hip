@@ -37,6 +37,7 @@ int s2m_kf_reset(s2m_handle h)
     h->kf.block_used = h->kf.block_cap = 0;
     h->kf.pose.clear(); h->kf.time.clear(); h->kf.frame.clear();
     h->loop.index.clear();
+    h->sess.forget_appended();
     if (e != hipSuccess) return fail(h, S2M_ERR_HIP, "hipFree of a key-frame block", e);
     return S2M_OK;
 }
@@ -180,10 +181,11 @@ int s2m::host::copy_pipeline(s2m_context* h)
 
 int s2m::host::kf_install_keys(s2m_context* h, size_t n, const float* pose_xyzrpy, const double* time, const int32_t* counts)
 {
-    if (!h->kf.time.empty() || !h->kf.blocks.empty()) return fail(h, S2M_ERR_INVALID_ARG, "the key-frame store is not empty");
+    const size_t N0 = h->kf.time.size();
     if (n == 0) return S2M_OK;
+    if (N0 + n > kKfMaxKeys) return fail(h, S2M_ERR_CAPACITY, "key-frame store full (2^24 keys)");
     S2M_HIP(h, hipSetDevice(h->device));
-    int rc = kf_reserve(h, n);
+    int rc = kf_reserve(h, N0 + n);
     if (rc) return rc;
     std::vector<float4> pos(n);
     std::vector<KfFrame> fr(n);
@@ -196,14 +198,21 @@ int s2m::host::kf_install_keys(s2m_context* h, size_t n, const float* pose_xyzrp
         fr[k] = kf_frame_of(q, dst, counts[k]);
         pos[k] = make_float4(q[0], q[1], q[2], 0.0f);
     }
-    S2M_HIP(h, hipMemcpyAsync(h->kf.pos.p, pos.data(), sizeof(float4) * n, hipMemcpyHostToDevice, h->stream));
-    S2M_HIP(h, hipMemcpyAsync(h->kf.frames.p, fr.data(), sizeof(KfFrame) * n, hipMemcpyHostToDevice, h->stream));
-    S2M_HIP(h, hipMemcpyAsync(h->kf.tdev.p, time, sizeof(double) * n, hipMemcpyHostToDevice, h->stream));
+    S2M_HIP(h, hipMemcpyAsync(h->kf.pos.as<float4>() + N0, pos.data(), sizeof(float4) * n, hipMemcpyHostToDevice, h->stream));
+    S2M_HIP(h, hipMemcpyAsync(h->kf.frames.as<KfFrame>() + N0, fr.data(), sizeof(KfFrame) * n, hipMemcpyHostToDevice, h->stream));
+    S2M_HIP(h, hipMemcpyAsync(h->kf.tdev.as<double>() + N0, time, sizeof(double) * n, hipMemcpyHostToDevice, h->stream));
     S2M_HIP(h, hipStreamSynchronize(h->stream));          // (the host vectors above are read by the copies until here)
-    h->kf.pose.assign(pose_xyzrpy, pose_xyzrpy + 6 * n);
-    h->kf.time.assign(time, time + n);
-    h->kf.frame = std::move(fr);
+    h->kf.pose.insert(h->kf.pose.end(), pose_xyzrpy, pose_xyzrpy + 6 * n);
+    h->kf.time.insert(h->kf.time.end(), time, time + n);
+    h->kf.frame.insert(h->kf.frame.end(), fr.begin(), fr.end());
     return S2M_OK;
+}
+
+void s2m::host::kf_truncate(s2m_context* h, const KfMark& m)
+{
+    while (h->kf.blocks.size() > m.n_blocks) { (void)hipFree(h->kf.blocks.back()); h->kf.blocks.pop_back(); }
+    h->kf.block_used = m.block_used; h->kf.block_cap = m.block_cap;
+    h->kf.pose.resize(6 * m.n_keys); h->kf.time.resize(m.n_keys); h->kf.frame.resize(m.n_keys);
 }
 
 int s2m_kf_set_poses(s2m_handle h, int first, int count, const float* poses_xyzrpy)

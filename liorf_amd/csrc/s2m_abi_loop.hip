@@ -158,11 +158,15 @@ void loop_result_init(s2m_loop_result* o)
 
 // loopFindNearKeyframes(key, search_num, loop_index) (:821-844) into `dst`: the frame table from the host mirror of the store, then
 // the transform and the VoxelGrid of s2m_extract_cloud. An empty concatenation is not filtered (res->n_out = 0).
-int loop_submap(s2m_context* h, int32_t key, int32_t search_num, int32_t loop_index, float leaf, DevBuf& dst, VoxResult* res)
+// With a clamp [clamp_lo, clamp_hi) the neighbours stay inside it (clamp_hi < 0: the whole store, as the reference): a submap at
+// the boundary of an appended, still unplaced session takes no key of the other one (s2m_relocalize_key).
+int loop_submap(s2m_context* h, int32_t key, int32_t search_num, int32_t loop_index, float leaf, DevBuf& dst, VoxResult* res,
+                long long clamp_lo = 0, long long clamp_hi = -1)
 {
     *res = VoxResult{};
     const long long N = (long long)h->kf.time.size();
-    const long long lo = std::max(0LL, (long long)key - search_num), hi = std::min(N - 1, (long long)key + search_num);
+    const long long end = clamp_hi < 0 ? N : std::min(N, clamp_hi);
+    const long long lo = std::max(std::max(0LL, clamp_lo), (long long)key - search_num), hi = std::min(end - 1, (long long)key + search_num);
     FrameTable tab;
     for (long long k = lo; k <= hi; k++) {                  // i = -search_num .. search_num, keyNear outside [0, N) skipped
         const KfFrame& f = h->kf.frame[(size_t)k];
@@ -788,6 +792,9 @@ void reloc_guess(const float T_key[12], float yaw_diff_rad, bool use_yaw, float 
     G[12] = G[13] = G[14] = 0.0f; G[15] = 1.0f;
 }
 
+int reloc_from_hits(s2m_context* h, const s2m_reloc_params& prm, const unsigned char* d_pts, size_t n, size_t stride_bytes, const s2m_sc_hit* hits,
+                    int32_t n_hits, long long clamp_lo, long long clamp_hi, s2m_reloc_candidate* out, int32_t* n_out, int32_t* best);
+
 }  // namespace
 
 int s2m_relocalize_check_args(int32_t n_sc, int32_t n_kf, const s2m_reloc_params* p)
@@ -820,6 +827,19 @@ int s2m_relocalize_scan(s2m_handle h, const void* pts, size_t n, size_t stride_b
     s2m_sc_hit hits[S2M_LOOP_MAX_CANDIDATES];
     int32_t n_hits = 0;
     if ((rc = sc_query_device_scan(h, d_pts, n, stride_bytes, &prm.query, hits, &n_hits))) return rc;
+    return reloc_from_hits(h, prm, d_pts, n, stride_bytes, hits, n_hits, 0, -1, out, n_out, best);
+}
+
+namespace {
+
+// Steps 2 to 6 of a relocalisation, from the query's hits on: the source (n records on the device, in their own frame) through the
+// VoxelGrid, a target submap - its neighbours inside [clamp_lo, clamp_hi), see loop_submap - and a guess per hit, the alignments in
+// lockstep, the gates, both pose forms and *best.
+int reloc_from_hits(s2m_context* h, const s2m_reloc_params& prm, const unsigned char* d_pts, size_t n, size_t stride_bytes, const s2m_sc_hit* hits,
+                    int32_t n_hits, long long clamp_lo, long long clamp_hi, s2m_reloc_candidate* out, int32_t* n_out, int32_t* best)
+{
+    int rc;
+    s2m_context::LoopClosure& L = h->loop;
     if (n_hits == 0) return S2M_OK;
     const size_t N = h->kf.time.size();
     for (int32_t i = 0; i < n_hits; i++)
@@ -845,7 +865,7 @@ int s2m_relocalize_scan(s2m_handle h, const void* pts, size_t n, size_t stride_b
         c.status = S2M_LOOP_TOO_FEW_POINTS;
         if (vs.n_out < 300) continue;
         VoxResult vt;
-        if ((rc = loop_submap(h, hits[i].key, prm.loop.search_num, -1, prm.loop.icp_leaf, L.target(i), &vt))) return rc;
+        if ((rc = loop_submap(h, hits[i].key, prm.loop.search_num, -1, prm.loop.icp_leaf, L.target(i), &vt, clamp_lo, clamp_hi))) return rc;
         c.n_tgt = (int32_t)vt.n_out;
         if (vt.n_out < 1000) continue;
         if ((rc = guess_ok(h, c.guess))) return rc;
@@ -882,6 +902,31 @@ int s2m_relocalize_scan(s2m_handle h, const void* pts, size_t n, size_t stride_b
         if (*best < 0 || c.icp.fitness_score < out[*best].icp.fitness_score) *best = i;
     }
     return S2M_OK;
+}
+
+}  // namespace
+
+int s2m_relocalize_key(s2m_handle h, int32_t key, const s2m_reloc_params* p, s2m_reloc_candidate* out, int32_t* n_out, int32_t* best)
+{
+    if (!h) return S2M_ERR_INVALID_ARG;
+    if (!out || !n_out || !best) return fail(h, S2M_ERR_INVALID_ARG, "null relocalisation outputs");
+    int rc = loop_busy(h);
+    if (rc) return rc;
+    *n_out = 0; *best = -1;
+    s2m_reloc_params prm;
+    if ((rc = reloc_args(h, (int64_t)h->sc.n, (int64_t)h->kf.time.size(), p, &prm))) return rc;
+    if (key < 0 || (size_t)key >= h->kf.time.size() || (size_t)key >= h->sc.n)
+        return fail(h, S2M_ERR_INVALID_ARG, "relocalisation: the key is outside the key-frame store or has no descriptor");
+    const KfFrame& f = h->kf.frame[(size_t)key];
+    if (f.n == 0) return S2M_OK;
+    S2M_HIP(h, hipSetDevice(h->device));
+    // 1. the query: the key's stored descriptor against the searched range
+    s2m_sc_hit hits[S2M_LOOP_MAX_CANDIDATES];
+    int32_t n_hits = 0;
+    if ((rc = s2m_sc_query_key(h, key, &prm.query, hits, &n_hits))) return rc;
+    // 2 .. 6 with the key's own records, straight from the arena, as the source, and submaps that stay inside the searched range
+    const long long lo = prm.query.first, hi = prm.query.count < 0 ? (long long)h->sc.n : lo + prm.query.count;
+    return reloc_from_hits(h, prm, f.src, (size_t)f.n, kDsStride, hits, n_hits, lo, hi, out, n_out, best);
 }
 
 // ---- diagnostics of the device loop (include/liorf_s2m_debug.h) ---------------------------------------------------------

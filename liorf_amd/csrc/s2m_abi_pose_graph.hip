@@ -425,6 +425,7 @@ int advance(s2m_context* h, s2m_pg_result* out)
 }  // namespace
 
 int s2m::host::pg_host_current(s2m_context* h) { return host_current(h); }
+void s2m::host::pg_pose_to_state(const float pose_xyzrpy[6], double X[12]) { pose_to_state(pose_xyzrpy, X); }
 
 int s2m_pg_reset(s2m_handle h)
 {
@@ -433,6 +434,7 @@ int s2m_pg_reset(s2m_handle h)
     if (g.pending) { (void)hipSetDevice(h->device); pg_drop_pending(h, false); }
     g.factors.clear(); g.X.clear(); g.has_init.clear(); g.dirty.clear();
     g.dev_newer = false; g.topo_dirty = true; g.n_dev = 0;
+    h->sess.forget_appended();
     return S2M_OK;
 }
 

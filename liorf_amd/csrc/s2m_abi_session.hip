@@ -1,9 +1,11 @@
 // s2m_abi_session.hip — C ABI of saving and loading a session: the blob's format (restated independently
 // in tests/ref/session_ref.py), its checks on the host, and the two streams - device -> pinned chunk -> callback and back -
 // around s2m_session.hip's kernels.  The small sections (keys, loop pairs, factors, variables) are built and read here; the
-// bulk (records, descriptors) is moved and summed by the device and only handed through.
+// bulk (records, descriptors) is moved and summed by the device and only handed through.  Behind them the append of a saved
+// session to a handle that holds one, its placement by a rigid anchor and the anchor from pose pairs.
 #include <algorithm>
 #include <cmath>
+#include <cstddef>
 #include <cstdio>
 #include <cstring>
 #include <new>
@@ -369,17 +371,19 @@ template <typename Read> int stream_in(s2m_context* h, const Section& s, Sum* su
     return pipe_sum(p, sum);
 }
 
-Section cloud_section(const s2m_context* h)
+// the records of keys first .. of the store
+Section cloud_section(const s2m_context* h, size_t first = 0)
 {
     Section s;
-    for (const KfFrame& f : h->kf.frame) s.push(f.src, (uint64_t)f.n);
+    for (size_t k = first; k < h->kf.frame.size(); k++) s.push(h->kf.frame[k].src, (uint64_t)h->kf.frame[k].n);
     return s;
 }
 
-Section desc_section(const s2m_context* h, size_t n)
+// descriptors first .. first+n-1 of the store
+Section desc_section(const s2m_context* h, size_t n, size_t first = 0)
 {
     Section s;
-    s.push(h->sc.store_desc.as<unsigned char>(), (uint64_t)n * (kDescBytes / kSessUnit));
+    s.push(h->sc.store_desc.as<unsigned char>() + kDescBytes * first, (uint64_t)n * (kDescBytes / kSessUnit));
     return s;
 }
 
@@ -489,7 +493,7 @@ int load_impl(s2m_context* h, s2m_session_read_fn r, void* user, s2m_session_inf
 
     // everything has arrived and holds: the derived state, then the counts
     if (hd.n_desc > 0) {
-        session_launch_sc_keys(h->stream, h->sc.store_desc.as<double>(), h->sc.store_ring.as<float>(), h->sc.store_sector.as<double>(), hd.n_desc);
+        session_launch_sc_keys(h->stream, h->sc.store_desc.as<double>(), h->sc.store_ring.as<float>(), h->sc.store_sector.as<double>(), 0, hd.n_desc);
         S2M_HIP(h, hipGetLastError());
         S2M_HIP(h, hipStreamSynchronize(h->stream));
     }
@@ -509,6 +513,258 @@ int load_impl(s2m_context* h, s2m_session_read_fn r, void* user, s2m_session_inf
     g.dirty.assign(n, 1);                                   // the next optimise uploads every estimate and builds its tables
     g.dev_newer = false; g.topo_dirty = true; g.n_dev = 0;
     info_from(hd, out);
+    return S2M_OK;
+}
+
+// ---- appending a session and placing it -------------------------------------------------
+
+// A o X: R' = A_R R, t' = A_R t + A_t, every sum ((a0 b0 + a1 b1) + a2 b2); k_session_place's sess_compose on the host
+void compose(const double A[12], const double X[12], double O[12])
+{
+    for (int i = 0; i < 3; i++) {
+        for (int j = 0; j < 3; j++) O[i * 3 + j] = (A[i * 3] * X[j] + A[i * 3 + 1] * X[3 + j]) + A[i * 3 + 2] * X[6 + j];
+        O[9 + i] = ((A[i * 3] * X[9] + A[i * 3 + 1] * X[10]) + A[i * 3 + 2] * X[11]) + A[9 + i];
+    }
+}
+
+// L^-1 o X, summed as s2m_pg_add_odometry sums poseFrom.between(poseTo)
+void between_of(const double L[12], const double X[12], double Z[12])
+{
+    for (int a = 0; a < 3; a++) {
+        for (int b = 0; b < 3; b++) Z[a * 3 + b] = L[a] * X[b] + L[3 + a] * X[3 + b] + L[6 + a] * X[6 + b];
+        Z[9 + a] = L[a] * (X[9] - L[9]) + L[3 + a] * (X[10] - L[10]) + L[6 + a] * (X[11] - L[11]);
+    }
+}
+
+// X^-1: R^T, -(R^T t)
+void inverse_of(const double X[12], double O[12])
+{
+    for (int i = 0; i < 3; i++) {
+        for (int j = 0; j < 3; j++) O[i * 3 + j] = X[j * 3 + i];
+        O[9 + i] = -((X[i] * X[9] + X[3 + i] * X[10]) + X[6 + i] * X[11]);
+    }
+}
+
+// a prior's state or a GPS factor's position under the move A (a between factor is relative: unchanged)
+void move_factor(const double A[12], PgFactor& f)
+{
+    if (f.type == kPgBetween) return;
+    double X[12], O[12];
+    std::copy(f.R, f.R + 9, X);
+    std::copy(f.t, f.t + 3, X + 9);
+    compose(A, X, O);
+    if (f.type == kPgPrior) std::copy(O, O + 9, f.R);       // (GPS: the rotation block stays the identity it is stored as)
+    std::copy(O + 9, O + 12, f.t);
+}
+
+bool finite6(const float* p) { for (int a = 0; a < 6; a++) if (!std::isfinite(p[a])) return false; return true; }
+
+// One launch of k_session_place over `count` keys and the one wait for its results: the stored poses at `pose`, key k's estimate
+// by est_of(k, X) (false: it has none). back: the staging block on the host, laid out as SessPlaced's out_*. Nothing of the
+// store or the graph is touched; a result that is not finite is S2M_ERR_INVALID_ARG.
+template <typename EstOf> int place_run(s2m_context* h, const double D[12], size_t count, const float* pose, EstOf est_of, std::vector<unsigned char>& back)
+{
+    const SessPlaced l{ count };
+    std::vector<unsigned char> in(l.in_bytes(), 0);
+    for (size_t k = 0; k < count; k++) {
+        double S[12], X[12] = { 0 };
+        pg_pose_to_state(pose + 6 * k, S);
+        const int32_t has = est_of(k, X) ? 1 : 0;
+        memcpy(in.data() + l.in_state() + 96 * k, S, 96);
+        memcpy(in.data() + l.in_est() + 96 * k, X, 96);
+        memcpy(in.data() + l.in_has() + 4 * k, &has, 4);
+    }
+    back.assign(l.out_bytes(), 0);
+    int rc;
+    if ((rc = ensure(h, h->sess.place_in, l.in_bytes())) || (rc = ensure(h, h->sess.place_out, l.out_bytes()))) return rc;
+    SessMove A;
+    std::copy(D, D + 12, A.a);
+    unsigned char* out = h->sess.place_out.as<unsigned char>();
+    S2M_HIP(h, hipMemcpyAsync(h->sess.place_in.p, in.data(), in.size(), hipMemcpyHostToDevice, h->stream));
+    S2M_HIP(h, hipMemsetAsync(out + l.out_bad(), 0, 16, h->stream));
+    session_launch_place(h->stream, A, h->sess.place_in.as<unsigned char>(), (int)count, out);
+    S2M_HIP(h, hipGetLastError());
+    S2M_HIP(h, hipMemcpyAsync(back.data(), out, back.size(), hipMemcpyDeviceToHost, h->stream));
+    S2M_HIP(h, hipStreamSynchronize(h->stream));
+    int32_t bad;
+    memcpy(&bad, back.data() + l.out_bad(), 4);
+    if (bad) return fail(h, S2M_ERR_INVALID_ARG, "session place: a moved pose or estimate is not finite; the handle is unchanged");
+    return S2M_OK;
+}
+
+// the staged poses, positions and transforms of keys first .. first+count-1 into the store: on the device by copies behind the
+// kernel on the same stream (no wait), on the host into the mirrors
+int place_into_store(s2m_context* h, const std::vector<unsigned char>& back, size_t first, size_t count)
+{
+    const SessPlaced l{ count };
+    const unsigned char* out = h->sess.place_out.as<unsigned char>();
+    S2M_HIP(h, hipMemcpyAsync(h->kf.pos.as<float4>() + first, out + l.out_pos(), sizeof(float4) * count, hipMemcpyDeviceToDevice, h->stream));
+    static_assert(offsetof(KfFrame, T) == 0, "the cached transform leads a KfFrame");
+    S2M_HIP(h, hipMemcpy2DAsync(h->kf.frames.as<KfFrame>() + first, sizeof(KfFrame), out + l.out_T(), sizeof(float) * 12, sizeof(float) * 12, count,
+                                hipMemcpyDeviceToDevice, h->stream));
+    memcpy(h->kf.pose.data() + 6 * first, back.data() + l.out_pose(), sizeof(float) * 6 * count);
+    for (size_t k = 0; k < count; k++) memcpy(h->kf.frame[first + k].T, back.data() + l.out_T() + 48 * k, 48);
+    return S2M_OK;
+}
+
+PgFactor junction_factor(int32_t n0, const double L[12], const double X[12], const double var[6])
+{
+    PgFactor f{};
+    f.type = kPgBetween; f.i = n0 - 1; f.j = n0; f.rows = 6; f.k = 0.0;
+    double Z[12];
+    between_of(L, X, Z);
+    std::copy(Z, Z + 9, f.R);
+    std::copy(Z + 9, Z + 12, f.t);
+    for (int a = 0; a < 6; a++) f.sw[a] = 1.0 / std::sqrt(var[a]);
+    return f;
+}
+
+const double kJunctionVar[6] = { 1.0, 1.0, 1.0, 1.0, 1.0, 1.0 };
+
+int append_impl(s2m_context* h, s2m_session_read_fn r, void* user, const float* anchor, const double* jvar, s2m_session_append_info* out,
+                const KfMark& mark)
+{
+    auto read = [&](void* p, size_t bytes) -> int {
+        if (bytes == 0) return S2M_OK;
+        const int rc = r(user, p, bytes);
+        if (rc == 0) return S2M_OK;
+        return rc == S2M_ERR_FORMAT ? fail(h, S2M_ERR_FORMAT, "session append: the stream ends early") : fail(h, S2M_ERR_IO, "session append: the read callback failed");
+    };
+    auto bad = [&](const char* what) { return fail(h, S2M_ERR_FORMAT, what); };
+    int rc;
+    unsigned char header[kHeaderBytes], footer[kFooterBytes];
+    Header hd;
+    if ((rc = read(header, kHeaderBytes))) return rc;
+    if (decode_header(header, hd)) return bad("session append: not a session of format version 1");
+    if (check_counts(hd)) return bad("session append: the header's counts and sizes do not agree");
+    s2m_session_info have, blob;
+    info_from(header_of(h), &have);
+    info_from(hd, &blob);
+    if (s2m_session_append_check_args(&have, &blob, anchor, jvar))
+        return fail(h, S2M_ERR_INVALID_ARG, "session append: a handle with keys; at most 2^24 keys in all; with descriptors (variables) in the blob a "
+                                            "ScanContext store (pose graph) of exactly as many as the handle has keys and no more of them than the blob has "
+                                            "keys; a finite anchor; positive finite variances");
+    if ((rc = pg_host_current(h))) return rc;              // the junction is measured from A's newest estimate
+    const size_t N0 = mark.n_keys, nK = (size_t)hd.n_keys, nD = (size_t)hd.n_desc, nV = (size_t)hd.n_vars;
+    Sum sums[kSecCount];
+    std::vector<unsigned char> sec[kSecCount];
+    auto host_section = [&](int k) -> int {
+        sec[k].resize(hd.sec[k]);
+        const int e = read(sec[k].data(), sec[k].size());
+        if (e == S2M_OK) sum_words(sums[k], sec[k].data(), sec[k].size(), 0);
+        return e;
+    };
+    // key frames: behind the store's own, the records to arena space taken by s2m_kf_add's rule
+    if ((rc = host_section(kSecKeys))) return rc;
+    if (check_keys(sec[kSecKeys].data(), hd)) return bad("session append: key poses, times or point counts");
+    {
+        std::vector<float> pose(6 * nK);
+        std::vector<double> time(nK);
+        std::vector<int32_t> counts(nK);
+        for (size_t k = 0; k < nK; k++) {
+            const unsigned char* p = sec[kSecKeys].data() + kKeyBytes * k;
+            for (int a = 0; a < 6; a++) pose[6 * k + a] = get<float>(p + 4 * a);
+            time[k] = get<double>(p + 24);
+            counts[k] = get<int32_t>(p + 32);
+        }
+        if ((rc = kf_install_keys(h, nK, pose.data(), time.data(), counts.data()))) return rc;
+    }
+    if ((rc = stream_in(h, cloud_section(h, N0), &sums[kSecCloud], read))) return rc;
+    // descriptors: behind the store's own; the store counts them only at the end
+    if (nD > 0) {
+        if ((rc = sc_reserve(h, N0 + nD))) return rc;
+        if ((rc = stream_in(h, desc_section(h, nD, N0), &sums[kSecDesc], read))) return rc;
+    }
+    if ((rc = host_section(kSecLoops)) || (rc = host_section(kSecFactors)) || (rc = host_section(kSecVars))) return rc;
+    if ((rc = read(footer, kFooterBytes))) return rc;
+    if (check_footer(header, footer)) return fail(h, S2M_ERR_CHECKSUM, "session append: the header's checksum does not match");
+    for (int k = 0; k < kSecCount; k++)
+        if (!(sums[k] == footer_sum(footer, k))) return fail(h, S2M_ERR_CHECKSUM, "session append: a section's checksum does not match");
+    if (check_pairs(sec[kSecLoops].data(), hd)) return bad("session append: loop pairs");
+    if (check_graph(sec[kSecFactors].data(), sec[kSecVars].data(), hd)) return bad("session append: pose-graph factors or variables");
+    const unsigned char* vars = sec[kSecVars].data();
+    auto has_value = [&](size_t k) { return k < nV && get<uint32_t>(vars + kVarBytes * nV + 4 * k) != 0; };
+    if (nV > 0 && (!has_value(0) || !h->pg.has_init[N0 - 1]))
+        return fail(h, S2M_ERR_INVALID_ARG, "session append: the junction needs a value of the handle's last variable and of the blob's first");
+
+    // everything has arrived and holds: the derived state, the placement, then - host only - the graph, the pairs and the counts
+    if (nD > 0) {
+        session_launch_sc_keys(h->stream, h->sc.store_desc.as<double>(), h->sc.store_ring.as<float>(), h->sc.store_sector.as<double>(), (int)N0, (int)nD);
+        S2M_HIP(h, hipGetLastError());
+        S2M_HIP(h, hipStreamSynchronize(h->stream));
+    }
+    std::vector<double> X(12 * nV);
+    if (nV) memcpy(X.data(), vars, kVarBytes * nV);
+    double A[12];
+    if (anchor && nK > 0) {
+        pg_pose_to_state(anchor, A);
+        std::vector<unsigned char> back;
+        auto est_of = [&](size_t k, double* o) { if (!has_value(k)) return false; std::copy(X.begin() + 12 * k, X.begin() + 12 * (k + 1), o); return true; };
+        if ((rc = place_run(h, A, nK, h->kf.pose.data() + 6 * N0, est_of, back))) return rc;
+        if ((rc = place_into_store(h, back, N0, nK))) return rc;
+        const SessPlaced l{ nK };
+        for (size_t k = 0; k < nV; k++) if (has_value(k)) memcpy(X.data() + 12 * k, back.data() + l.out_est() + 96 * k, 96);
+    }
+    auto& g = h->pg;
+    const size_t nF = (size_t)hd.n_factors;
+    g.factors.reserve(g.factors.size() + nF + 1);           // (nothing below throws: the containers end whole)
+    g.X.reserve(g.X.size() + 12 * nV); g.has_init.reserve(N0 + nV); g.dirty.reserve(N0 + nV);
+    int32_t junction = -1;
+    if (nV > 0) {
+        junction = (int32_t)g.factors.size();
+        g.factors.push_back(junction_factor((int32_t)N0, g.X.data() + 12 * (N0 - 1), X.data(), jvar ? jvar : kJunctionVar));
+        for (size_t x = 0; x < nF; x++) {
+            PgFactor f = decode_factor(sec[kSecFactors].data() + kFactorBytes * x);
+            f.i += (int32_t)N0;
+            if (f.type == kPgBetween) f.j += (int32_t)N0;
+            if (anchor) move_factor(A, f);
+            g.factors.push_back(f);
+        }
+        g.X.insert(g.X.end(), X.begin(), X.end());
+        for (size_t k = 0; k < nV; k++) { g.has_init.push_back(has_value(k) ? 1 : 0); g.dirty.push_back(1); }
+        g.topo_dirty = true;
+    }
+    for (int32_t k = 0; k < hd.n_pairs; k++) {
+        const unsigned char* p = sec[kSecLoops].data() + kPairBytes * (size_t)k;
+        h->loop.index[get<int32_t>(p) + (int32_t)N0] = get<int32_t>(p + 4) + (int32_t)N0;
+    }
+    h->sc.n += nD;
+    h->sess.app_first = (int32_t)N0; h->sess.app_count = (int32_t)nK; h->sess.app_junction = junction;
+    if (out) { out->blob = blob; out->first_key = (int32_t)N0; out->junction_factor = junction; }
+    return S2M_OK;
+}
+
+int place_impl(s2m_context* h, const float move[6])
+{
+    int rc;
+    if ((rc = pg_host_current(h))) return rc;
+    auto& g = h->pg;
+    const size_t first = (size_t)h->sess.app_first, count = (size_t)h->sess.app_count;
+    if (count == 0) return S2M_OK;
+    double D[12];
+    pg_pose_to_state(move, D);
+    auto has_value = [&](size_t k) { return first + k < g.has_init.size() && g.has_init[first + k]; };
+    auto est_of = [&](size_t k, double* o) { if (!has_value(k)) return false; std::copy(g.X.begin() + 12 * (first + k), g.X.begin() + 12 * (first + k + 1), o); return true; };
+    std::vector<unsigned char> back;
+    if ((rc = place_run(h, D, count, h->kf.pose.data() + 6 * first, est_of, back))) return rc;
+    if ((rc = place_into_store(h, back, first, count))) return rc;
+    const SessPlaced l{ count };
+    for (size_t k = 0; k < count; k++) {
+        if (!has_value(k)) continue;
+        memcpy(g.X.data() + 12 * (first + k), back.data() + l.out_est() + 96 * k, 96);
+        g.dirty[first + k] = 1;
+    }
+    for (PgFactor& f : g.factors)
+        if (f.type != kPgBetween && (size_t)f.i >= first && (size_t)f.i < first + count) move_factor(D, f);
+    const int32_t j = h->sess.app_junction;
+    if (j >= 0 && (size_t)j < g.factors.size()) {          // measured again, at the new estimates; its variances stay
+        PgFactor& f = g.factors[(size_t)j];
+        double Z[12];
+        between_of(g.X.data() + 12 * (first - 1), g.X.data() + 12 * first, Z);
+        std::copy(Z, Z + 9, f.R);
+        std::copy(Z + 9, Z + 12, f.t);
+    }
+    g.topo_dirty = true;
     return S2M_OK;
 }
 
@@ -554,6 +810,7 @@ int s2m_session_load(s2m_handle h, s2m_session_read_fn r, void* user, s2m_sessio
         return fail(h, S2M_ERR_INVALID_ARG, "session load: the key-frame store, the ScanContext store, the loop container and the pose graph must be "
                                             "empty: s2m_kf_reset, s2m_sc_reset and s2m_pg_reset first");
     S2M_HIP(h, hipSetDevice(h->device));
+    h->sess.forget_appended();
     try {
         rc = load_impl(h, r, user, out);
     } catch (const std::bad_alloc&) {                       // (a header that asks for more than the host has)
@@ -590,6 +847,123 @@ int s2m_session_load_file(s2m_handle h, const char* path, s2m_session_info* out)
     const int rc = s2m_session_load(h, file_read, &u, out);
     (void)fclose(u.f);
     return rc;
+}
+
+int s2m_session_append_check_args(const s2m_session_info* have, const s2m_session_info* blob_info, const float* anchor_xyzrpy, const double* junction_var)
+{
+    if (!have || !blob_info) return S2M_ERR_INVALID_ARG;
+    const int64_t n0 = have->n_keys, nk = blob_info->n_keys;
+    if (n0 < 1 || nk < 0 || n0 + nk > kMaxCount) return S2M_ERR_INVALID_ARG;
+    if (blob_info->n_descriptors < 0 || blob_info->n_variables < 0) return S2M_ERR_INVALID_ARG;
+    if (blob_info->n_descriptors > 0 && (have->n_descriptors != n0 || blob_info->n_descriptors > nk)) return S2M_ERR_INVALID_ARG;
+    if (blob_info->n_variables > 0 && (have->n_variables != n0 || blob_info->n_variables > nk)) return S2M_ERR_INVALID_ARG;
+    if (anchor_xyzrpy && !finite6(anchor_xyzrpy)) return S2M_ERR_INVALID_ARG;
+    if (junction_var)
+        for (int a = 0; a < 6; a++) if (!(junction_var[a] > 0.0) || !std::isfinite(junction_var[a])) return S2M_ERR_INVALID_ARG;
+    return S2M_OK;
+}
+
+int s2m_session_append(s2m_handle h, s2m_session_read_fn r, void* user, const float* anchor_xyzrpy, const double* junction_var,
+                       s2m_session_append_info* info_out)
+{
+    if (!h) return S2M_ERR_INVALID_ARG;
+    if (!r) return fail(h, S2M_ERR_INVALID_ARG, "session append: null read callback");
+    int rc = session_busy(h);
+    if (rc) return rc;
+    S2M_HIP(h, hipSetDevice(h->device));
+    const KfMark mark = kf_mark(h);
+    try {
+        rc = append_impl(h, r, user, anchor_xyzrpy, junction_var, info_out, mark);
+    } catch (const std::bad_alloc&) {                       // (a header that asks for more than the host has)
+        rc = fail(h, S2M_ERR_CAPACITY, "session append: out of host memory");
+    }
+    if (rc) {                                               // as before the call: the graph, the pairs and the counts were not reached
+        drain(h);
+        kf_truncate(h, mark);
+    }
+    return rc;
+}
+
+int s2m_session_append_file(s2m_handle h, const char* path, const float* anchor_xyzrpy, const double* junction_var, s2m_session_append_info* info_out)
+{
+    if (!h) return S2M_ERR_INVALID_ARG;
+    if (!path) return fail(h, S2M_ERR_INVALID_ARG, "session append: null path");
+    FileUser u{ fopen(path, "rb") };
+    if (!u.f) return fail(h, S2M_ERR_IO, "session append: the file cannot be opened");
+    const int rc = s2m_session_append(h, file_read, &u, anchor_xyzrpy, junction_var, info_out);
+    (void)fclose(u.f);
+    return rc;
+}
+
+int s2m_session_place(s2m_handle h, const float move_xyzrpy[6])
+{
+    if (!h) return S2M_ERR_INVALID_ARG;
+    if (!move_xyzrpy || !finite6(move_xyzrpy)) return fail(h, S2M_ERR_INVALID_ARG, "session place: the move must be finite");
+    if (h->sess.app_first < 0) return fail(h, S2M_ERR_INVALID_ARG, "session place: no appended session (s2m_session_append first)");
+    int rc = session_busy(h);
+    if (rc) return rc;
+    S2M_HIP(h, hipSetDevice(h->device));
+    try {
+        return place_impl(h, move_xyzrpy);
+    } catch (const std::bad_alloc&) {
+        drain(h);
+        return fail(h, S2M_ERR_CAPACITY, "session place: out of host memory");
+    }
+}
+
+int s2m_session_appended(s2m_handle h, int32_t* first, int32_t* count)
+{
+    if (!h) return S2M_ERR_INVALID_ARG;
+    if (first) *first = h->sess.app_first;
+    if (count) *count = h->sess.app_count;
+    return S2M_OK;
+}
+
+int s2m_session_anchor_from_pairs(const float* pose_in_session, const float* pose_in_map, int32_t m, double tol_m, double tol_rad,
+                                  float anchor_out[6], int32_t* n_inliers, int32_t* chosen)
+{
+    if (!pose_in_session || !pose_in_map || !anchor_out || m <= 0 || !(tol_m >= 0.0) || !std::isfinite(tol_m) || !(tol_rad >= 0.0) ||
+        !std::isfinite(tol_rad)) return S2M_ERR_INVALID_ARG;
+    for (int32_t i = 0; i < m; i++)
+        if (!finite6(pose_in_session + 6 * (size_t)i) || !finite6(pose_in_map + 6 * (size_t)i)) return S2M_ERR_INVALID_ARG;
+    try {
+        std::vector<double> A(12 * (size_t)m);
+        for (int32_t i = 0; i < m; i++) {                   // A_i = state(map_i) o state(session_i)^-1
+            double S[12], M[12], Si[12];
+            pg_pose_to_state(pose_in_session + 6 * (size_t)i, S);
+            pg_pose_to_state(pose_in_map + 6 * (size_t)i, M);
+            inverse_of(S, Si);
+            compose(M, Si, A.data() + 12 * (size_t)i);
+        }
+        int32_t best = -1, best_n = 0;
+        double best_sum = 0.0;
+        for (int32_t i = 0; i < m; i++) {
+            const double* a = A.data() + 12 * (size_t)i;
+            int32_t n = 0;
+            double sum = 0.0;
+            for (int32_t j = 0; j < m; j++) {
+                const double* b = A.data() + 12 * (size_t)j;
+                const double dx = a[9] - b[9], dy = a[10] - b[10], dz = a[11] - b[11];
+                const double dist = std::sqrt((dx * dx + dy * dy) + dz * dz);
+                double tr = 0.0;
+                for (int k = 0; k < 9; k++) tr += a[k] * b[k];                 // trace(A_i.R^T A_j.R), entry by entry, left to right
+                const double ang = std::acos(std::min(1.0, std::max(-1.0, (tr - 1.0) / 2.0)));
+                if (dist <= tol_m && ang <= tol_rad) { n++; sum += dist; }
+            }
+            if (best < 0 || n > best_n || (n == best_n && sum < best_sum)) { best = i; best_n = n; best_sum = sum; }
+        }
+        const double* P = A.data() + 12 * (size_t)best;     // k_pg_poses' read-out, with the host's libm
+        const double s = std::fmin(1.0, std::fmax(-1.0, -P[6]));
+        anchor_out[0] = (float)P[9]; anchor_out[1] = (float)P[10]; anchor_out[2] = (float)P[11];
+        anchor_out[3] = (float)std::atan2(P[7], P[8]);
+        anchor_out[4] = (float)std::asin(s);
+        anchor_out[5] = (float)std::atan2(P[3], P[0]);
+        if (n_inliers) *n_inliers = best_n;
+        if (chosen) *chosen = best;
+    } catch (const std::bad_alloc&) {
+        return S2M_ERR_CAPACITY;
+    }
+    return S2M_OK;
 }
 
 int s2m_session_check(const void* blob, size_t bytes, s2m_session_info* out)

@@ -294,6 +294,11 @@ struct __attribute__((visibility("hidden"))) s2m_context {
         unsigned char* h_chunk[2] = { nullptr, nullptr };      // pinned, h_chunk_cap bytes each
         size_t h_chunk_cap = 0;
         size_t chunk_bytes = 0;                                // 0: the default (s2m_debug_session_chunk sets a small one)
+        // the session appended last (s2m_session_append): its keys [app_first, app_first + app_count) and the index of its
+        // junction factor (-1: none); k_session_place's input and staging blocks
+        int32_t app_first = -1, app_count = 0, app_junction = -1;
+        DevBuf place_in, place_out;
+        void forget_appended() { app_first = -1; app_count = 0; app_junction = -1; }
     } sess;
 };
 
@@ -511,15 +516,22 @@ void loop_drop_pending(s2m_context* h, bool destroy);
 void pg_drop_pending(s2m_context* h, bool destroy);
 // the host mirror of the estimates holds the newest values (the device's, where an accepted step made them newer)
 int pg_host_current(s2m_context* h);
+// Rot3::RzRyRx(roll, pitch, yaw) and t of a float pose in fp64 with libm, as s2m_pg_set_initial makes an estimate of it
+void pg_pose_to_state(const float pose_xyzrpy[6], double X[12]);
 
 // ---- s2m_abi_keyframes.hip ----
 // gmap's copy stream and its two pairs of events exist (the chunked copy-out of the saved map and of a session share them)
 int copy_pipeline(s2m_context* h);
-// n keys into an EMPTY store in one go (a session load): poses {x, y, z, roll, pitch, yaw}, times and point counts; every key
-// gets its place in the arena, as n s2m_kf_add would give them, and its transform and position by the path of s2m_kf_add, with
-// one upload per device array.  The records themselves are written by the caller, to frame[k].src.  A failure leaves the store
-// for s2m_kf_reset.
+// n keys behind the N0 the store holds, in one go (a session load: N0 = 0; an append): poses {x, y, z, roll, pitch, yaw}, times
+// and point counts; every key gets its place in the arena, as n s2m_kf_add would give them, and its transform and position by
+// the path of s2m_kf_add, with one upload per device array.  The records themselves are written by the caller, to
+// frame[N0 + k].src.  A failure leaves the store for s2m_kf_reset, or for kf_truncate to a KfMark taken before the call.
 int kf_install_keys(s2m_context* h, size_t n, const float* pose_xyzrpy, const double* time, const int32_t* counts);
+// The store's extent - keys, arena blocks, the last block's fill and size - and the way back to it: blocks taken since are
+// released (nothing on a stream may still write to them), the host mirrors shrink.  The device arrays only ever grew.
+struct KfMark { size_t n_keys, n_blocks, block_used, block_cap; };
+inline KfMark kf_mark(const s2m_context* h) { return KfMark{ h->kf.time.size(), h->kf.blocks.size(), h->kf.block_used, h->kf.block_cap }; }
+void kf_truncate(s2m_context* h, const KfMark& m);
 
 // ---- s2m_abi_voxel.hip ----
 // VoxelGrid of a device cloud into `dst` (grown to hold one record per input point, the worst case).

@@ -4,7 +4,7 @@
 
 #include <cmath>
 
-#include "s2m_glibc_trig.hpp"
+#include "s2m_pose_readout.hpp"
 #include "s2m_voxel.hpp"
 
 namespace s2m {
@@ -542,13 +542,8 @@ __global__ void __launch_bounds__(kPgThreads) k_pg_poses(const double* X, int fi
 {
     const int k = blockIdx.x * blockDim.x + threadIdx.x;
     if (k >= count) return;
-    const double* P = X + 12 * (size_t)(first + k);
-    const double s = fmin(1.0, fmax(-1.0, -P[6]));
     float* o = out + 6 * (size_t)k;
-    o[0] = (float)P[9]; o[1] = (float)P[10]; o[2] = (float)P[11];
-    o[3] = (float)atan2(P[7], P[8]);
-    o[4] = (float)asin(s);
-    o[5] = (float)atan2(P[3], P[0]);
+    pose_readout(X + 12 * (size_t)(first + k), o);
     if (pos) pos[k] = make_float4(o[0], o[1], o[2], 0.0f);
 }
 
@@ -559,23 +554,14 @@ __global__ void __launch_bounds__(kPgThreads) k_pg_store_stage(const double* X, 
 {
     const int k = blockIdx.x * blockDim.x + threadIdx.x;
     if (k >= count) return;
-    const double* P = X + 12 * (size_t)(first + k);
-    const double s = fmin(1.0, fmax(-1.0, -P[6]));
-    float o[6] = { (float)P[9], (float)P[10], (float)P[11], (float)atan2(P[7], P[8]), (float)asin(s), (float)atan2(P[3], P[0]) };
+    float o[6];
+    pose_readout(X + 12 * (size_t)(first + k), o);
     bool ok = true;
     for (int a = 0; a < 6; a++) ok = ok && isfinite(o[a]);
     if (!ok) *bad = 1;
-    float A, B, C, D, E, F;
-    glibc_sincosf_both(o[5], B, A);
-    glibc_sincosf_both(o[4], D, C);
-    glibc_sincosf_both(o[3], F, E);
-    const float DE = D * E, DF = D * F;
     float* q = stage + 18 * (size_t)k;
     for (int a = 0; a < 6; a++) q[a] = o[a];
-    float* T = q + 6;
-    T[0] = A * C; T[1] = A * DF - B * E; T[2]  = B * F + A * DE; T[3]  = o[0];
-    T[4] = B * C; T[5] = A * E + B * DF; T[6]  = B * DE - A * F; T[7]  = o[1];
-    T[8] = -D;    T[9] = C * F;          T[10] = C * E;          T[11] = o[2];
+    pose_transform(o, q + 6);
 }
 // second half: cloudKeyPoses3D and every key's cached transform from the staged values
 __global__ void __launch_bounds__(kPgThreads) k_pg_store_write(const float* stage, int count, float4* pos, KfFrame* frames)

@@ -615,6 +615,71 @@ public:
         return info;
     }
 
+    // -- one map from two runs (s2m_session_append, s2m_relocalize_key, s2m_session_anchor_from_pairs, s2m_session_place) --
+    // A saved session behind the keys the node holds, placed by `anchor` {x, y, z, roll, pitch, yaw} (nullptr: as stored).
+    // cloudKeyPoses6D grows by the appended keys as loadSession fills it; surfCloudKeyFrames stays with the library.
+    s2m_session_append_info sessionAppend(const std::string& path, const float* anchor = nullptr, const double* junction_var = nullptr)
+    {
+        s2m_session_append_info info{};
+        check(s2m_session_append_file(h_, path.c_str(), anchor, junction_var, &info), "s2m_session_append_file");
+        cloudKeyPoses6D.resize((size_t)info.first_key + (size_t)info.blob.n_keys, PointTypePose{});
+        refreshAppendedPoses(info.first_key, info.blob.n_keys < info.blob.n_variables ? info.blob.n_keys : info.blob.n_variables);
+        return info;
+    }
+    void sessionPlace(const float move[6])
+    {
+        check(s2m_session_place(h_, move), "s2m_session_place");
+        int32_t first = -1, count = 0, nv = 0;
+        check(s2m_session_appended(h_, &first, &count), "s2m_session_appended");
+        check(s2m_pg_size(h_, &nv, nullptr), "s2m_pg_size");
+        refreshAppendedPoses(first, nv - first < count ? nv - first : count);
+    }
+    // relocalizeScan for a stored key, against keys [first, first + count) only; does not touch transformTobeMapped
+    bool relocalizeKey(int key, int first, int count)
+    {
+        s2m_reloc_params p;
+        s2m_reloc_default_params(&p);
+        p.query.top_k = relocTopK;
+        p.query.first = first; p.query.count = count;
+        p.loop = loopParams();
+        lastReloc.assign(S2M_LOOP_MAX_CANDIDATES, s2m_reloc_candidate{});
+        int32_t n = 0, best = -1;
+        check(s2m_relocalize_key(h_, key, &p, lastReloc.data(), &n, &best), "s2m_relocalize_key");
+        lastReloc.resize((size_t)n);
+        lastRelocBest = best;
+        return best >= 0;
+    }
+    // the anchor most of the pairs (a pose in the session's frame, the same pose in the map's frame) agree on; returns its supporters
+    static int anchorFromPairs(const std::vector<float>& pose_in_session, const std::vector<float>& pose_in_map, float anchor[6],
+                               double tol_m = 1.0, double tol_rad = 0.1)
+    {
+        int32_t n = 0;
+        if (s2m_session_anchor_from_pairs(pose_in_session.data(), pose_in_map.data(), (int32_t)(pose_in_session.size() / 6), tol_m, tol_rad, anchor,
+                                          &n, nullptr) != S2M_OK) return 0;
+        return n;
+    }
+    // The first half of the merge workflow: append unplaced, relocalise the probe keys of the appended
+    // session against the keys held before, take the anchor most accepted probes agree on and place the session by it. Returns
+    // the supporters (0: no probe was accepted, the session stays as stored). The probes need pose-graph variables in the file.
+    int mergeSession(const std::string& path, const std::vector<int>& probe_keys, double tol_m = 1.0, double tol_rad = 0.1)
+    {
+        const s2m_session_append_info info = sessionAppend(path);
+        std::vector<float> in_session, in_map;
+        for (int k : probe_keys) {
+            if (k < 0 || k >= info.blob.n_variables || !relocalizeKey(info.first_key + k, 0, info.first_key)) continue;
+            float v[6];
+            check(s2m_pg_get_poses(h_, info.first_key + k, 1, v), "s2m_pg_get_poses");
+            in_session.insert(in_session.end(), v, v + 6);
+            const float* q = lastReloc[(size_t)lastRelocBest].pose_xyzrpy;
+            in_map.insert(in_map.end(), q, q + 6);
+        }
+        if (in_session.empty()) return 0;
+        float anchor[6];
+        const int n = anchorFromPairs(in_session, in_map, anchor, tol_m, tol_rad);
+        if (n > 0) sessionPlace(anchor);
+        return n;
+    }
+
     // true: a verification is pending (false: lastVerify is final)
     bool loopVerifyLaunch(int key_cur, const std::vector<int32_t>& key_pre, int base_key = -1)
     {
@@ -806,6 +871,18 @@ private:
         if (rc != S2M_PG_PENDING && rc != S2M_PG_IDLE) check(rc, what);
         if (rc == S2M_OK) lastGraphResult = *r;
         return rc;
+    }
+    // cloudKeyPoses6D[first .. first+n) from the pose graph's estimates (an appended session's keys, after an append or a place)
+    void refreshAppendedPoses(int32_t first, int32_t n)
+    {
+        if (first < 0 || n <= 0) return;
+        std::vector<float> v(6 * (size_t)n);
+        check(s2m_pg_get_poses(h_, first, n, v.data()), "s2m_pg_get_poses");
+        for (int32_t k = 0; k < n; k++) {
+            PointTypePose& q = cloudKeyPoses6D[(size_t)(first + k)];
+            q.intensity = (float)(first + k);
+            q.x = v[6 * k]; q.y = v[6 * k + 1]; q.z = v[6 * k + 2]; q.roll = v[6 * k + 3]; q.pitch = v[6 * k + 4]; q.yaw = v[6 * k + 5];
+        }
     }
     // S2M_WARN_LEAF_TOO_SMALL is PCL's PCL_WARN case (output = input): not an error
     void checkVoxel(int rc, const char* what) { if (rc != S2M_WARN_LEAF_TOO_SMALL) check(rc, what); }

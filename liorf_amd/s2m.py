@@ -65,6 +65,8 @@ ABI_SYMBOLS = [
     "s2m_debug_pg_retract",
     "s2m_session_info_of", "s2m_session_save", "s2m_session_load", "s2m_session_save_file", "s2m_session_load_file", "s2m_session_check",
     "s2m_debug_session_chunk", "s2m_debug_sc_keys", "s2m_debug_kf_frame",
+    "s2m_session_append_check_args", "s2m_session_append", "s2m_session_append_file", "s2m_session_place", "s2m_session_appended",
+    "s2m_session_anchor_from_pairs", "s2m_relocalize_key",
 ]
 S2M_SESSION_VERSION = 1
 S2M_RING_U8, S2M_RING_U16, S2M_RING_I32 = 0, 1, 2
@@ -259,6 +261,11 @@ class SessionInfo(C.Structure):
     """s2m_session_info: what a session blob holds."""
     _fields_ = [("version", C.c_uint32), ("n_keys", C.c_int32), ("n_descriptors", C.c_int32), ("n_loop_pairs", C.c_int32),
                 ("n_variables", C.c_int32), ("n_factors", C.c_int32), ("n_points", C.c_uint64), ("bytes", C.c_uint64)]
+
+
+class SessionAppendInfo(C.Structure):
+    """s2m_session_append_info: what the appended blob held, the first new key, the junction's index in the factor list (-1: none)."""
+    _fields_ = [("blob", SessionInfo), ("first_key", C.c_int32), ("junction_factor", C.c_int32)]
 
 
 SESSION_WRITE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_size_t)
@@ -472,6 +479,13 @@ def load_library(path: str | None = None) -> C.CDLL:
     L.s2m_session_load_file.argtypes = [vp, C.c_char_p, C.POINTER(SessionInfo)]
     L.s2m_session_check.argtypes = [vp, C.c_size_t, C.POINTER(SessionInfo)]
     L.s2m_debug_session_chunk.argtypes = [vp, C.c_size_t]
+    L.s2m_session_append_check_args.argtypes = [C.POINTER(SessionInfo), C.POINTER(SessionInfo), fp, dp]
+    L.s2m_session_append.argtypes = [vp, SESSION_READ_FN, vp, fp, dp, C.POINTER(SessionAppendInfo)]
+    L.s2m_session_append_file.argtypes = [vp, C.c_char_p, fp, dp, C.POINTER(SessionAppendInfo)]
+    L.s2m_session_place.argtypes = [vp, fp]
+    L.s2m_relocalize_key.argtypes = [vp, C.c_int32, C.POINTER(RelocParams), C.POINTER(RelocCandidate), i32p, i32p]
+    L.s2m_session_appended.argtypes = [vp, i32p, i32p]
+    L.s2m_session_anchor_from_pairs.argtypes = [fp, fp, C.c_int32, C.c_double, C.c_double, fp, i32p, i32p]
     L.s2m_debug_sc_keys.argtypes = [vp, C.c_int32, C.c_int32, fp, dp]
     L.s2m_debug_kf_frame.argtypes = [vp, C.c_int32, fp, fp, fp, i32p]
     if path is None:
@@ -514,6 +528,47 @@ def session_check(blob) -> SessionInfo:
 
 def _fp(a):
     return a.ctypes.data_as(C.POINTER(C.c_float))
+
+
+def _opt_f32(v, n=6):
+    """(keep-alive array, pointer) of an optional float vector: None stays NULL."""
+    if v is None:
+        return None, None
+    a = np.ascontiguousarray(v, np.float32).reshape(n)
+    return a, _fp(a)
+
+
+def _opt_f64(v, n=6):
+    if v is None:
+        return None, None
+    a = np.ascontiguousarray(v, np.float64).reshape(n)
+    return a, a.ctypes.data_as(C.POINTER(C.c_double))
+
+
+def session_append_check_args(have: SessionInfo, blob_info: SessionInfo, anchor=None, junction_var=None) -> int:
+    """s2m_session_append_check_args: the precondition verdict of s2m_session_append from what the handle holds and what the
+    blob's header states (host only, no handle, no GPU): S2M_OK or S2M_ERR_INVALID_ARG."""
+    _a, pa = _opt_f32(anchor)
+    _v, pv = _opt_f64(junction_var)
+    return load_library().s2m_session_append_check_args(C.byref(have) if have is not None else None,
+                                                        C.byref(blob_info) if blob_info is not None else None, pa, pv)
+
+
+def anchorFromPairs(pose_in_session, pose_in_map, tol_m: float = 1.0, tol_rad: float = 0.1):
+    """s2m_session_anchor_from_pairs (host only): the anchor {x, y, z, roll, pitch, yaw} that most of the pairs (a pose of the
+    session in its own frame, the same pose in the map's frame) agree on, its number of supporters and the pair it came from."""
+    a = np.ascontiguousarray(pose_in_session, np.float32).reshape(-1, 6)
+    b = np.ascontiguousarray(pose_in_map, np.float32).reshape(-1, 6)
+    if a.shape != b.shape:
+        raise ValueError("as many poses in the session as in the map")
+    out = np.zeros(6, np.float32)
+    n, chosen = C.c_int32(0), C.c_int32(-1)
+    rc = load_library().s2m_session_anchor_from_pairs(_fp(a), _fp(b), a.shape[0], float(tol_m), float(tol_rad), _fp(out), C.byref(n), C.byref(chosen))
+    if rc != S2M_OK:
+        e = S2MError(f"s2m_session_anchor_from_pairs: {ERRORS.get(rc, rc)}")
+        e.code = rc
+        raise e
+    return out, n.value, chosen.value
 
 
 def _records(a) -> tuple[np.ndarray, int, int]:
@@ -1209,6 +1264,44 @@ class MapOptimizationS2M:
         self._check(self.lib.s2m_relocalize_scan(self.h, src, n, st, on_dev, pp, recs, C.byref(n_out), C.byref(best)), "s2m_relocalize_scan")
         return [_copy_struct(recs[i]) for i in range(n_out.value)], best.value
 
+    def relocalizeKey(self, key: int, params: "RelocParams | None" = None):
+        """s2m_relocalize_key: relocalizeScan for a key the store holds - its stored descriptor as the query, its own records
+        as the source, target submaps clamped to the query's searched range. (records, best)."""
+        recs = (RelocCandidate * S2M_LOOP_MAX_CANDIDATES)()
+        n_out, best = C.c_int32(0), C.c_int32(-1)
+        pp = C.byref(params) if params is not None else None
+        self._check(self.lib.s2m_relocalize_key(self.h, key, pp, recs, C.byref(n_out), C.byref(best)), "s2m_relocalize_key")
+        return [_copy_struct(recs[i]) for i in range(n_out.value)], best.value
+
+    def mergeSession(self, path_or_blob, probe_keys, reloc: "RelocParams | None" = None, tol_m: float = 1.0, tol_rad: float = 0.1,
+                     junction_var=None, probe_poses=None):
+        """The first half of the merge workflow: append the saved session unplaced, relocalise the
+        keys `probe_keys` of it (indices in the appended session) against the keys the handle held, take the anchor most of
+        the accepted ones agree on, and place the session by it. Returns (append info, anchor or None, supporters); with no
+        accepted probe the session stays as stored (anchor None). probe_poses: the probes' poses in the session's own frame
+        (None: the appended graph's estimates, which the blob must hold for them). The caller goes on with scQueryKeys of [N0, N) against
+        first = 0, count = N0, loopVerifyMany, pgAddBetween, pgOptimize and pgApplyToStore."""
+        if isinstance(path_or_blob, (bytes, bytearray, memoryview)):
+            info = self.sessionAppend(blob=bytes(path_or_blob), junction_var=junction_var)
+        else:
+            info = self.sessionAppendFile(path_or_blob, junction_var=junction_var)
+        n0 = info.first_key
+        prm = reloc if reloc is not None else default_reloc_params()
+        prm.query.first, prm.query.count = 0, n0
+        in_session, in_map = [], []
+        for i, k in enumerate(probe_keys):
+            if probe_poses is None and int(k) >= info.blob.n_variables:
+                raise ValueError("a probe key without a pose-graph variable needs probe_poses")
+            recs, best = self.relocalizeKey(n0 + int(k), prm)
+            if best >= 0:
+                in_session.append(np.array(probe_poses[i] if probe_poses is not None else self.pgPoses(n0 + int(k), 1)[0], np.float32))
+                in_map.append(np.array(recs[best].pose_xyzrpy, np.float32))
+        if not in_session:
+            return info, None, 0
+        anchor, n_in, _ = anchorFromPairs(in_session, in_map, tol_m, tol_rad)
+        self.sessionPlace(anchor)
+        return info, anchor, n_in
+
     def localizeInStoredMap(self, scan, reloc: "RelocParams | None" = None, kf: KfParams | None = None):
         """Start (or recover) inside the stored map: relocalise `scan`, install the local map around the best pose and set
         transformTobeMapped to it, so that downsampleCurrentScan + scan2MapOptimization track from there. Returns
@@ -1270,6 +1363,56 @@ class MapOptimizationS2M:
         out = SessionInfo()
         self._check(self.lib.s2m_session_load(self.h, SESSION_READ_FN(cb), None, C.byref(out)), "s2m_session_load")
         return out
+
+    @staticmethod
+    def _read_callback(blob, read):
+        buf = (C.c_char * max(len(blob), 1)).from_buffer_copy(bytes(blob) or b"\0") if blob is not None else None
+        at = [0]
+
+        def cb(_user, data, n):
+            try:
+                if buf is not None:
+                    if at[0] + n > len(blob):
+                        return S2M_ERR_FORMAT            # the stream has ended
+                    C.memmove(data, C.addressof(buf) + at[0], n)
+                    at[0] += n
+                    return 0
+                chunk = read(n)
+                if chunk is None or len(chunk) != n:
+                    return 1
+                C.memmove(data, bytes(chunk), n)
+                return 0
+            except Exception:
+                return 1
+        return SESSION_READ_FN(cb)
+
+    def sessionAppend(self, blob=None, read=None, anchor=None, junction_var=None) -> SessionAppendInfo:
+        """s2m_session_append: a saved session (`blob`, or `read` as session_load takes it) behind the stored keys, placed by
+        `anchor` {x, y, z, roll, pitch, yaw} (None: as stored); the junction factor's variances (None: 1.0 x 6)."""
+        _a, pa = _opt_f32(anchor)
+        _v, pv = _opt_f64(junction_var)
+        out = SessionAppendInfo()
+        cb = self._read_callback(blob, read)
+        self._check(self.lib.s2m_session_append(self.h, cb, None, pa, pv, C.byref(out)), "s2m_session_append")
+        return out
+
+    def sessionAppendFile(self, path: str, anchor=None, junction_var=None) -> SessionAppendInfo:
+        _a, pa = _opt_f32(anchor)
+        _v, pv = _opt_f64(junction_var)
+        out = SessionAppendInfo()
+        self._check(self.lib.s2m_session_append_file(self.h, os.fsencode(path), pa, pv, C.byref(out)), "s2m_session_append_file")
+        return out
+
+    def sessionPlace(self, move):
+        """s2m_session_place: moves the session appended last by `move` {x, y, z, roll, pitch, yaw}."""
+        a, pa = _opt_f32(move)
+        self._check(self.lib.s2m_session_place(self.h, pa), "s2m_session_place")
+
+    def sessionAppended(self) -> tuple[int, int]:
+        """s2m_session_appended: (first key, count) of the session appended last; (-1, 0): none."""
+        first, count = C.c_int32(0), C.c_int32(0)
+        self._check(self.lib.s2m_session_appended(self.h, C.byref(first), C.byref(count)), "s2m_session_appended")
+        return first.value, count.value
 
     def session_save_file(self, path: str):
         self._check(self.lib.s2m_session_save_file(self.h, os.fsencode(path)), "s2m_session_save_file")

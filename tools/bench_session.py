@@ -13,6 +13,14 @@ closure of the last key as a between factor. Medians after warm-up of:
 The line goes to stdout and to profiles/session_bench_line.json (--out).
 
   python tools/bench_session.py [--keys 5000] [--reps 5] [--warmup 1]
+
+With --append the same blob is appended behind itself instead (s2m_session_append into a handle that holds the session already),
+as stored and with an anchor, beside s2m_session_load of the blob into a reset handle in the same process, and
+s2m_session_place alone; the line goes to profiles/session_append_bench_line.json. The expectation to report against is
+"an append costs about one load": append_over_load is that ratio.
+  append_ms          s2m_session_append with a NULL anchor: the handle is reset and loaded again before every repetition (not timed)
+  append_anchor_ms   the same with an anchor (k_session_place over the appended keys, the factors moved on the host)
+  place_ms           s2m_session_place of the appended session
 """
 import argparse
 import ctypes as C
@@ -49,8 +57,11 @@ def main(argv=None):
     ap.add_argument("--keys", type=int, default=5000)
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=1)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "session_bench_line.json"))
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--append", action="store_true", help="time s2m_session_append / s2m_session_place instead")
     a = ap.parse_args(argv)
+    if a.out is None:
+        a.out = os.path.join(ROOT, "profiles", "session_append_bench_line.json" if a.append else "session_bench_line.json")
     from liorf_amd import s2m
 
     n = a.keys
@@ -120,6 +131,44 @@ def main(argv=None):
         rc = new.lib.s2m_session_load(new.h, rd_c, None, None)
         assert rc == 0, rc
     load_ms = _median_ms(load, a.warmup, a.reps, reset)
+
+    if a.append:
+        anchor = (C.c_float * 6)(12.0, -7.0, 0.4, 0.02, -0.03, 0.4)
+
+        def reload():
+            reset()
+            load()
+            rewind()
+
+        def append(anc):
+            rc = new.lib.s2m_session_append(new.h, rd_c, None, anc, None, None)
+            assert rc == 0, rc
+        append_ms = _median_ms(lambda: append(None), a.warmup, a.reps, reload)
+        append_anchor_ms = _median_ms(lambda: append(anchor), a.warmup, a.reps, reload)
+        assert new.sessionAppended() == (n, n)
+        move = (C.c_float * 6)(0.01, -0.02, 0.0, 0.0, 0.0, 0.001)
+
+        def place():
+            rc = new.lib.s2m_session_place(new.h, move)
+            assert rc == 0, rc
+        place_ms = _median_ms(place, a.warmup, a.reps)
+        s2m.session_check(new.session_save())
+        new.close()
+        eng.close()
+        names = ("median", "min", "max")
+        out = {"workload": f"tools/bench_session.py --append: the {n}-key revisit of tools/bench_loop.py appended behind itself",
+               "keys": n, "points": int(info.n_points), "blob_bytes": size, "reps": a.reps, "warmup": a.warmup,
+               "load_ms": dict(zip(names, load_ms)), "append_ms": dict(zip(names, append_ms)),
+               "append_anchor_ms": dict(zip(names, append_anchor_ms)), "place_ms": dict(zip(names, place_ms)),
+               "append_over_load": round(append_ms[0] / load_ms[0], 2), "append_anchor_over_load": round(append_anchor_ms[0] / load_ms[0], 2),
+               "place_over_load": round(place_ms[0] / load_ms[0], 3),
+               "note": "wall clock on the host, same process; the load is s2m_session_load of the same blob into a reset handle; an "
+                       "append includes the callback's memmove of every chunk as the load does"}
+        line = json.dumps(out)
+        print(line)
+        with open(a.out, "w") as f:
+            f.write(line + "\n")
+        return
 
     # the baseline: the same handle by the per-key adds, from the same host data (descriptors out of the blob)
     hdr = struct.unpack("<II7iIQ6QQ", blob[8:112])
