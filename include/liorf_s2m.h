@@ -696,6 +696,58 @@ int  s2m_sc_query_descriptors(s2m_handle h, const double* descs /* m * 1200, row
                               const s2m_sc_query_many_params* p, s2m_sc_hit* hits, int32_t* n_hits);
 int  s2m_sc_get_descriptors(s2m_handle h, int32_t first, int32_t count, double* descs /* count * 1200 */);
 
+/* ---- The place query behind a ring-key prefilter --------------------------------------
+ * The two-stage search of detectLoopClosureID (:253-344) for any query: the rotation-invariant 20-float ring key
+ * names n_candidates keys of the searched set, and only those are compared column by column. The exhaustive
+ * queries above cost (queries x searched keys) descriptor pairs; these cost (queries x n_candidates). The caller
+ * chooses n_candidates and with it recall against time: 3 is the detector's choice; an n_candidates of at least
+ * the size of the searched set gives the exhaustive query's row bit for bit. A single query is m = 1.
+ *
+ * Ring-key distance. d2(q, c) is the squared L2 distance of two fp32 ring keys in the order of nanoflann's
+ * L2_Adaptor - five groups of four, result += d0*d0 + d1*d1 + d2*d2 + d3*d3, fp32, uncontracted - the statement
+ * s2m_sc_detect_loop's three-neighbour search uses. A stored key's ring key is the stored fp32 row; an external
+ * descriptor's is (float) of its row means, exactly what s2m_sc_add_descriptor would store for it: a descriptor
+ * query equals the key query of the same descriptor once added.
+ * Neighbour set. S_i is query i's searched set exactly as s2m_sc_query_keys / _descriptors define it (range,
+ * fixed window and, for a stored-key query, the relative window, sums in 64 bits); a stored-key query does not
+ * exclude itself unless a window does. R_i is the first n_candidates keys of { c in S_i : d2(q_i, c) < +inf } in
+ * ascending (d2, key) order. A NaN or infinite d2 is never a neighbour, so |R_i| may be below n_candidates.
+ * s2m_sc_ring_neighbours_*: row i is out[i * n_candidates ..], R_i in that order; n_out[i] = |R_i|.
+ * Hits. s2m_sc_query_*_ring: row i is hits[i * top_k ..], the ranking the single query would give were its
+ * searched set R_i: the keys of R_i with dist < max_dist in ascending (dist, key) order, the first top_k; dist,
+ * shift and yaw_diff_rad as every other place query forms them (both alignments), reserved = 0, the same
+ * 10000000 / NaN rule. Records behind n_out[i] / n_hits[i] are left as the caller had them.
+ * Read-only, exactly as the many-query: the store, s2m_sc_size, the detector's counter and its searched set are
+ * untouched; the calls work beside a pending closure, verification or optimise, run on the handle's main stream,
+ * touch only ScanContext buffers, go through in passes of at most 64 MiB of device memory and synchronise once
+ * per pass, never once per query.
+ * Errors. S2M_ERR_INVALID_ARG: a null handle; everything s2m_sc_query_many_check_args rejects (the neighbour
+ * calls check top_k, align and max_dist too and do not use them); n_candidates outside 1 ..
+ * S2M_SC_RING_MAX_CAND; reserved != 0; null queries or outputs with m > 0; a key outside [0, N). The outputs are
+ * then untouched. S2M_OK: m == 0 writes nothing; an empty store or an empty S_i gives 0 for that row.
+ * p == NULL means the defaults. */
+#define S2M_SC_RING_MAX_CAND 256
+typedef struct s2m_sc_ring_params {
+    s2m_sc_query_many_params m;   /* searched set, top_k, align, max_dist: exactly as in the many-query */
+    int32_t n_candidates;         /* 1 .. S2M_SC_RING_MAX_CAND; default 3 = NUM_CANDIDATES_FROM_TREE */
+    int32_t reserved;             /* 0 */
+} s2m_sc_ring_params;
+typedef struct s2m_sc_ring_neighbour { float d2; int32_t key; } s2m_sc_ring_neighbour;
+
+int  s2m_sc_ring_default_params(s2m_sc_ring_params* p);   /* the many-query's defaults, n_candidates 3, reserved 0 */
+/* The argument table above for a store of n_stored keys and m queries: S2M_OK or S2M_ERR_INVALID_ARG. Host only, no handle. */
+int  s2m_sc_ring_check_args(int32_t n_stored, int32_t m, const s2m_sc_ring_params* p, int32_t descriptor_query);
+/* stage one alone */
+int  s2m_sc_ring_neighbours_keys(s2m_handle h, const int32_t* keys, int32_t m, const s2m_sc_ring_params* p,
+                                 s2m_sc_ring_neighbour* out /* m * n_candidates */, int32_t* n_out /* m */);
+int  s2m_sc_ring_neighbours_descriptors(s2m_handle h, const double* descs /* m * 1200 */, int32_t m, const s2m_sc_ring_params* p,
+                                        s2m_sc_ring_neighbour* out, int32_t* n_out);
+/* both stages */
+int  s2m_sc_query_keys_ring(s2m_handle h, const int32_t* keys, int32_t m, const s2m_sc_ring_params* p,
+                            s2m_sc_hit* hits /* m * top_k */, int32_t* n_hits /* m */);
+int  s2m_sc_query_descriptors_ring(s2m_handle h, const double* descs /* m * 1200 */, int32_t m, const s2m_sc_ring_params* p,
+                                   s2m_sc_hit* hits, int32_t* n_hits);
+
 /* ---- ICP loop-closure alignment ------------------------------------------
  * pcl::IterativeClosestPoint<PointType, PointType> as performRSLoopClosure / performSCLoopClosure configure
  * and run it (reference src/mapOptmization.cpp:571-586, :663-678): setMaxCorrespondenceDistance,

@@ -294,6 +294,17 @@ int  s2m_debug_sc_query_many_pass(s2m_handle h, int32_t queries_per_pass);
 int  s2m_debug_sc_query_many_shape(int32_t* tile_cands, int32_t* block_queries);
 int  s2m_debug_sc_query_many_last(s2m_handle h, int32_t* passes, size_t* scratch_bytes);
 
+/* ---- the ring-key prefilter of the place query: its passes and the shape of its selection kernel ----
+ * s2m_debug_sc_ring_pass: at most this many queries per pass of the s2m_sc_ring_neighbours_* / s2m_sc_query_*_ring calls (0
+ *   restores the default, as many as the 64 MiB scratch bound allows, at most 65535). The rows do not depend on it.
+ * s2m_debug_sc_ring_shape: the stored ring keys a workgroup of k_sc_ring_select holds in LDS (tile_keys), the queries it walks
+ *   past them (block_queries) and the 64-bit words of a query's candidate buffer (buffer_words), so that tests can place their
+ *   sizes at the kernel's edges. A workgroup walks every tile of the range: there are no tile groups.
+ * s2m_debug_sc_ring_last: the passes of the handle's last ring call and the device bytes one of them used. */
+int  s2m_debug_sc_ring_pass(s2m_handle h, int32_t queries_per_pass);
+int  s2m_debug_sc_ring_shape(int32_t* tile_keys, int32_t* block_queries, int32_t* buffer_words);
+int  s2m_debug_sc_ring_last(s2m_handle h, int32_t* passes, size_t* scratch_bytes);
+
 /* The table form of the device loop (icp_pairs_begin / icp_pairs_advance): n_pairs <= S2M_LOOP_MANY_MAX_PAIRS host pairs, each
  * with its own source and target (no size gate) and optionally a guess (guesses: NULL, or n_pairs pointers, each NULL or a
  * row-major 4x4), aligned in lockstep as s2m_debug_icp_align_many_device aligns the slots of one source. out[k] is bit for bit

@@ -1,12 +1,14 @@
 // s2m_abi_sc_query.hip — C ABI of the ScanContext place query (s2m_sc_query.hip's kernels): the argument
 // table, the searched set, the four query sources; and of its many-query form (s2m_sc_many.hip's kernels; section 20): the
-// passes, their staging and the rows.  Read-only on the store and the detector's counters.
+// passes, their staging and the rows; and of the ring-key prefilter (s2m_sc_ring.hip's kernels; section 22), the many-query's
+// passes with a neighbour list per query.  Read-only on the store and the detector's counters.
 #include <algorithm>
 #include <cstring>
 
 #include "s2m_context.hpp"
 #include "s2m_sc_many.hpp"
 #include "s2m_sc_query.hpp"
+#include "s2m_sc_ring.hpp"
 
 using namespace s2m;
 using namespace s2m::host;
@@ -186,6 +188,116 @@ int sc_many_run(s2m_context* h, bool by_key, const int32_t* keys, const double* 
     return S2M_OK;
 }
 
+
+// ---- the ring-key prefilter ---------------------------------------------------------------
+
+const s2m_sc_ring_params kScRingDefaults = { { { 0, -1, 0, 0, 1, S2M_SC_ALIGN_SECTOR_KEY, 0.3 }, 0, 0 }, 3, 0 };   // NUM_CANDIDATES_FROM_TREE (Scancontext.h:91)
+static_assert(sizeof(s2m_sc_ring_params) == 48 && sizeof(s2m_sc_ring_neighbour) == 8, "the ring query's records on both sides of the ABI");
+
+bool sc_ring_args_ok(int32_t n, int32_t m, const s2m_sc_ring_params& p, int32_t descriptor_query)
+{
+    if (s2m_sc_query_many_check_args(n, m, &p.m, descriptor_query) != S2M_OK) return false;
+    return p.n_candidates >= 1 && p.n_candidates <= S2M_SC_RING_MAX_CAND && p.reserved == 0;
+}
+
+// m queries - stored keys (by_key) or external descriptors - in passes of at most kScManyScratchMax of device memory; per pass
+// one upload, the kernels, one download, one wait.  both: stage two and the rows (hits, n_out = n_hits), else the neighbour
+// lists (nb, n_out).
+int sc_ring_run(s2m_context* h, bool by_key, bool both, const int32_t* keys, const double* descs, int32_t m, const s2m_sc_ring_params* pp,
+                s2m_sc_ring_neighbour* nb, s2m_sc_hit* hits, int32_t* n_out)
+{
+    if (!h) return S2M_ERR_INVALID_ARG;
+    const s2m_sc_ring_params p = pp ? *pp : kScRingDefaults;
+    const int64_t n = (int64_t)h->sc.n;
+    if (!sc_ring_args_ok((int32_t)n, m, p, !by_key))
+        return fail(h, S2M_ERR_INVALID_ARG, "s2m_sc_ring: what the many-query rejects, n_candidates outside 1..256 or reserved != 0");
+    if (m == 0) return S2M_OK;
+    if (!(both ? (void*)hits : (void*)nb) || !n_out || !(by_key ? (const void*)keys : (const void*)descs))
+        return fail(h, S2M_ERR_INVALID_ARG, "s2m_sc_ring: null queries or outputs with m > 0");
+    if (keys)
+        for (int32_t i = 0; i < m; i++)
+            if (keys[i] < 0 || (int64_t)keys[i] >= n) return fail(h, S2M_ERR_INVALID_ARG, "query key outside the descriptor store");
+    ScManySet set{};
+    set.first = p.m.q.first;
+    set.end = (int32_t)(p.m.q.count < 0 ? n : (int64_t)p.m.q.first + p.m.q.count);
+    set.ex_lo = p.m.q.exclude_lo; set.ex_hi = p.m.q.exclude_hi; set.rel_lo = p.m.rel_lo; set.rel_hi = p.m.rel_hi;
+    h->sc.ring_last_passes = 0; h->sc.ring_last_scratch = 0;
+    if (set.first >= set.end) { std::fill(n_out, n_out + m, 0); return S2M_OK; }     // an empty range: an empty set for every query
+    S2M_HIP(h, hipSetDevice(h->device));
+    const int K = p.m.q.top_k, C = p.n_candidates;
+    const size_t in_q = keys ? sizeof(int32_t) : kScRingExtBytes, up_q = keys ? sizeof(int32_t) : sizeof(double) * kScDesc;
+    const size_t cand_q = sc_ring_cand_bytes(C), dist_q = both ? sc_ring_dist_bytes(C) : 0, out_q = both ? sc_ring_out_bytes(K) : 0;
+    const size_t per_q = in_q + cand_q + dist_q + out_q;
+    size_t pass = std::max<size_t>(1, (kScManyScratchMax - 256) / per_q);  // (256: every part of a buffer starts on a 16-byte boundary)
+    if (!keys) pass = std::min(pass, std::max<size_t>(1, kScManyPinnedUp / up_q));
+    pass = std::min<size_t>(pass, 65535);                                  // k_sc_ring_dist: one grid row per query
+    if (h->sc.ring_pass > 0) pass = std::min<size_t>(pass, (size_t)h->sc.ring_pass);
+    pass = std::min<size_t>(pass, (size_t)m);
+    const auto up16 = [](size_t b) { return (b + 15) & ~(size_t)15; };
+    const size_t ext_sector_off = up16(sizeof(double) * kScDesc * pass), ext_ring_off = ext_sector_off + up16(sizeof(double) * S2M_SC_NUM_SECTOR * pass);
+    const size_t in_bytes = keys ? sizeof(int32_t) * pass : ext_ring_off + kScRingKeyBytes * pass;
+    const size_t cand_n_off = up16(sizeof(s2m_sc_ring_neighbour) * (size_t)C * pass), shift_off = up16(sizeof(double) * (size_t)C * pass);
+    const size_t out_n_off = up16(sizeof(s2m_sc_hit) * (size_t)K * pass);
+    int rc;
+    if ((rc = sc_many_ensure(h, h->sc.ring_in, in_bytes)) || (rc = sc_many_ensure(h, h->sc.ring_cand, cand_n_off + sizeof(int32_t) * pass))) return rc;
+    if (both && ((rc = sc_many_ensure(h, h->sc.ring_dist, shift_off + sizeof(int32_t) * (size_t)C * pass)) ||
+                 (rc = sc_many_ensure(h, h->sc.ring_out, out_n_off + sizeof(int32_t) * pass))))
+        return rc;
+    const size_t up_bytes = up16(up_q * pass), down_a = up16((both ? sizeof(s2m_sc_hit) * (size_t)K : sizeof(s2m_sc_ring_neighbour) * (size_t)C) * pass);
+    const size_t pinned = up_bytes + down_a + sizeof(int32_t) * pass;
+    if (pinned > h->sc.h_many_cap) {
+        if (h->sc.h_many) S2M_HIP(h, hipHostFree(h->sc.h_many));
+        h->sc.h_many = nullptr; h->sc.h_many_cap = 0;
+        S2M_HIP(h, hipHostMalloc((void**)&h->sc.h_many, pinned));
+        h->sc.h_many_cap = pinned;
+    }
+    h->sc.ring_last_scratch = per_q * pass;
+    unsigned char* h_up = h->sc.h_many;
+    unsigned char* h_rows = h->sc.h_many + up_bytes;
+    int32_t* h_counts = reinterpret_cast<int32_t*>(h_rows + down_a);
+    const size_t rec = both ? sizeof(s2m_sc_hit) : sizeof(s2m_sc_ring_neighbour), width = both ? (size_t)K : (size_t)C;
+    for (size_t i0 = 0; i0 < (size_t)m; i0 += pass) {
+        const size_t mp = std::min(pass, (size_t)m - i0);
+        ScRingArgs a{};
+        a.store_desc = h->sc.store_desc.as<double>(); a.store_ring = h->sc.store_ring.as<float>(); a.store_sector = h->sc.store_sector.as<double>();
+        if (keys) {
+            memcpy(h_up, keys + i0, sizeof(int32_t) * mp);
+            a.keys = h->sc.ring_in.as<int32_t>();
+        } else {
+            memcpy(h_up, descs + kScDesc * i0, sizeof(double) * kScDesc * mp);
+            a.ext_desc = h->sc.ring_in.as<double>();
+            a.ext_sector = reinterpret_cast<double*>(h->sc.ring_in.as<unsigned char>() + ext_sector_off);
+            a.ext_ring = reinterpret_cast<float*>(h->sc.ring_in.as<unsigned char>() + ext_ring_off);
+        }
+        S2M_HIP(h, hipMemcpyAsync(h->sc.ring_in.p, h_up, up_q * mp, hipMemcpyHostToDevice, h->stream));
+        a.m = (int)mp; a.set = set; a.n_cand = C;
+        a.cand = h->sc.ring_cand.as<s2m_sc_ring_neighbour>();
+        a.n_out = reinterpret_cast<int32_t*>(h->sc.ring_cand.as<unsigned char>() + cand_n_off);
+        a.top_k = K; a.align = p.m.q.align; a.max_dist = p.m.q.max_dist;
+        const void* d_rows = a.cand; const int32_t* d_counts = a.n_out;
+        if (both) {
+            a.dist = h->sc.ring_dist.as<double>();
+            a.shift = reinterpret_cast<int32_t*>(h->sc.ring_dist.as<unsigned char>() + shift_off);
+            a.out_hits = h->sc.ring_out.as<s2m_sc_hit>();
+            a.out_n = reinterpret_cast<int32_t*>(h->sc.ring_out.as<unsigned char>() + out_n_off);
+            d_rows = a.out_hits; d_counts = a.out_n;
+        }
+        S2M_HIP(h, sc_ring_launch(h->stream, a));
+        S2M_HIP(h, hipMemcpyAsync(h_rows, d_rows, rec * width * mp, hipMemcpyDeviceToHost, h->stream));
+        S2M_HIP(h, hipMemcpyAsync(h_counts, d_counts, sizeof(int32_t) * mp, hipMemcpyDeviceToHost, h->stream));
+        S2M_HIP(h, hipStreamSynchronize(h->stream));      // the one wait of the pass: the pinned block is free again
+        h->sc.ring_last_passes++;
+        for (size_t i = 0; i < mp; i++) {
+            const int32_t c = h_counts[i];
+            if (c < 0 || (size_t)c > width) return fail(h, S2M_ERR_HIP, "s2m_sc_ring: the device left no count");
+            unsigned char* dst = both ? reinterpret_cast<unsigned char*>(hits) : reinterpret_cast<unsigned char*>(nb);
+            memcpy(dst + (i0 + i) * width * rec, h_rows + i * width * rec, rec * (size_t)c);   // the records behind stay the caller's
+            n_out[i0 + i] = c;
+        }
+    }
+    return S2M_OK;
+}
+
 }  // namespace
 
 // s2m_sc_query_scan for a scan that is on the device already (the relocalisation's query): the same descriptor, the same hits
@@ -292,6 +404,39 @@ int s2m_sc_query_descriptors(s2m_handle h, const double* descs, int32_t m, const
     return sc_many_run(h, false, nullptr, descs, m, p, hits, n_hits);
 }
 
+int s2m_sc_ring_default_params(s2m_sc_ring_params* p)
+{
+    if (!p) return S2M_ERR_INVALID_ARG;
+    *p = kScRingDefaults;
+    return S2M_OK;
+}
+
+int s2m_sc_ring_check_args(int32_t n_stored, int32_t m, const s2m_sc_ring_params* p, int32_t descriptor_query)
+{
+    return sc_ring_args_ok(n_stored, m, p ? *p : kScRingDefaults, descriptor_query) ? S2M_OK : S2M_ERR_INVALID_ARG;
+}
+
+int s2m_sc_ring_neighbours_keys(s2m_handle h, const int32_t* keys, int32_t m, const s2m_sc_ring_params* p, s2m_sc_ring_neighbour* out, int32_t* n_out)
+{
+    return sc_ring_run(h, true, false, keys, nullptr, m, p, out, nullptr, n_out);
+}
+
+int s2m_sc_ring_neighbours_descriptors(s2m_handle h, const double* descs, int32_t m, const s2m_sc_ring_params* p, s2m_sc_ring_neighbour* out,
+                                       int32_t* n_out)
+{
+    return sc_ring_run(h, false, false, nullptr, descs, m, p, out, nullptr, n_out);
+}
+
+int s2m_sc_query_keys_ring(s2m_handle h, const int32_t* keys, int32_t m, const s2m_sc_ring_params* p, s2m_sc_hit* hits, int32_t* n_hits)
+{
+    return sc_ring_run(h, true, true, keys, nullptr, m, p, nullptr, hits, n_hits);
+}
+
+int s2m_sc_query_descriptors_ring(s2m_handle h, const double* descs, int32_t m, const s2m_sc_ring_params* p, s2m_sc_hit* hits, int32_t* n_hits)
+{
+    return sc_ring_run(h, false, true, nullptr, descs, m, p, nullptr, hits, n_hits);
+}
+
 int s2m_sc_get_descriptors(s2m_handle h, int32_t first, int32_t count, double* descs)
 {
     if (!h) return S2M_ERR_INVALID_ARG;
@@ -325,6 +470,28 @@ int s2m_debug_sc_query_many_last(s2m_handle h, int32_t* passes, size_t* scratch_
 {
     if (!h || !passes || !scratch_bytes) return S2M_ERR_INVALID_ARG;
     *passes = h->sc.many_last_passes; *scratch_bytes = h->sc.many_last_scratch;
+    return S2M_OK;
+}
+
+int s2m_debug_sc_ring_pass(s2m_handle h, int32_t queries_per_pass)
+{
+    if (!h) return S2M_ERR_INVALID_ARG;
+    if (queries_per_pass < 0) return fail(h, S2M_ERR_INVALID_ARG, "ring-query pass: 0 (the default) or a positive number of queries");
+    h->sc.ring_pass = queries_per_pass;
+    return S2M_OK;
+}
+
+int s2m_debug_sc_ring_shape(int32_t* tile_keys, int32_t* block_queries, int32_t* buffer_words)
+{
+    if (!tile_keys || !block_queries || !buffer_words) return S2M_ERR_INVALID_ARG;
+    *tile_keys = kScRingTile; *block_queries = kScRingBlock; *buffer_words = kScRingBuf;
+    return S2M_OK;
+}
+
+int s2m_debug_sc_ring_last(s2m_handle h, int32_t* passes, size_t* scratch_bytes)
+{
+    if (!h || !passes || !scratch_bytes) return S2M_ERR_INVALID_ARG;
+    *passes = h->sc.ring_last_passes; *scratch_bytes = h->sc.ring_last_scratch;
     return S2M_OK;
 }
 

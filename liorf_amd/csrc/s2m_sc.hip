@@ -146,12 +146,7 @@ __global__ __launch_bounds__(kScThreads) void k_sc_detect(const double* __restri
         float4 bk[NR / 4];
 #pragma unroll
         for (int g = 0; g < NR / 4; g++) bk[g] = b[g];
-        float result = 0.0f;
-#pragma unroll
-        for (int g = 0; g < NR / 4; g++) {
-            const float d0 = qk[g].x - bk[g].x, d1 = qk[g].y - bk[g].y, d2 = qk[g].z - bk[g].z, d3 = qk[g].w - bk[g].w;
-            result += d0 * d0 + d1 * d1 + d2 * d2 + d3 * d3;
-        }
+        const float result = sc_ring_d2(qk, bk);
         if (result < bd[2]) {                             // i ascends per thread: an equal distance stays behind
             bd[2] = result; bi[2] = i;
             if (bd[2] < bd[1]) { const float a = bd[1]; bd[1] = bd[2]; bd[2] = a; const int b2 = bi[1]; bi[1] = bi[2]; bi[2] = b2; }

@@ -19,6 +19,20 @@ __host__ __device__ __forceinline__ double sc_ring_key(At at)
     return s / 60.0;
 }
 
+// squared L2 distance of two fp32 ring keys, each held as five float4: the accumulation order of nanoflann's L2_Adaptor (groups
+// of four), fp32, uncontracted.  The detector's three-neighbour search (k_sc_detect) and the ring-key prefilter of the place
+// query (s2m_sc_ring.hip) both call this, so they agree bit for bit.
+__device__ __forceinline__ float sc_ring_d2(const float4 (&q)[S2M_SC_NUM_RING / 4], const float4 (&b)[S2M_SC_NUM_RING / 4])
+{
+    float result = 0.0f;
+#pragma unroll
+    for (int g = 0; g < S2M_SC_NUM_RING / 4; g++) {
+        const float d0 = q[g].x - b[g].x, d1 = q[g].y - b[g].y, d2 = q[g].z - b[g].z, d3 = q[g].w - b[g].w;
+        result += d0 * d0 + d1 * d1 + d2 * d2 + d3 * d3;
+    }
+    return result;
+}
+
 // mean of a sector's 20 rings; at(r) is the descriptor's value at (r, sector)
 template <typename At>
 __host__ __device__ __forceinline__ double sc_sector_key(At at)

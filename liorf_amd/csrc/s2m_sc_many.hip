@@ -50,15 +50,6 @@ __device__ __forceinline__ const double* sc_many_qsector(const ScManyDev& a, int
     return a.keys ? a.store_sector + (size_t)a.keys[i] * NS : a.ext_sector + (size_t)i * NS;
 }
 
-// c is in the searched set of a query with stored key qkey (-1: an external descriptor)
-__device__ __forceinline__ bool sc_many_in_set(const ScManySet& s, int qkey, int c)
-{
-    if (c < s.first || c >= s.end) return false;
-    if (c >= s.ex_lo && c < s.ex_hi) return false;
-    if (qkey >= 0 && s.rel_lo < s.rel_hi && (long long)c >= (long long)qkey + s.rel_lo && (long long)c < (long long)qkey + s.rel_hi) return false;
-    return true;
-}
-
 // (d, key, shift) into a list of at most top_k, ascending (distance, key)
 __device__ __forceinline__ void sc_many_insert(double* hd, int* hk, int* hs, int* n_held, int top_k, double d, int key, int shift)
 {

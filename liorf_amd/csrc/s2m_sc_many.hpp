@@ -20,6 +20,16 @@ struct ScManySet {
     int32_t first, end, ex_lo, ex_hi, rel_lo, rel_hi;
 };
 
+// c is in the searched set of a query with stored key qkey (-1: an external descriptor); shared with the ring-key prefilter
+// (s2m_sc_ring.hip)
+__device__ __forceinline__ bool sc_many_in_set(const ScManySet& s, int qkey, int c)
+{
+    if (c < s.first || c >= s.end) return false;
+    if (c >= s.ex_lo && c < s.ex_hi) return false;
+    if (qkey >= 0 && s.rel_lo < s.rel_hi && (long long)c >= (long long)qkey + s.rel_lo && (long long)c < (long long)qkey + s.rel_hi) return false;
+    return true;
+}
+
 inline int sc_many_tiles(int n_range) { return (n_range + kScManyTile - 1) / kScManyTile; }
 inline int sc_many_groups(int n_range) { const int t = sc_many_tiles(n_range); return t < kScManyMaxGroups ? t : kScManyMaxGroups; }
 

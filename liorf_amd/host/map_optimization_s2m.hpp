@@ -741,6 +741,33 @@ public:
         check(s2m_sc_query_descriptors(h_, descs.data(), (int32_t)m, &p, hits.data(), n.data()), "s2m_sc_query_descriptors");
         return scRows(hits, n, p.q.top_k);
     }
+    // The place query behind a ring-key prefilter (s2m_sc_query_keys_ring / s2m_sc_ring_neighbours_keys):
+    // scQueryKeys with every query's searched set cut to its p.n_candidates ring-key neighbours; and those neighbours themselves.
+    std::vector<std::vector<s2m_sc_hit>> scQueryKeysRing(const std::vector<int32_t>& keys, const s2m_sc_ring_params& p)
+    {
+        std::vector<s2m_sc_hit> hits(keys.size() * (size_t)(p.m.q.top_k > 0 ? p.m.q.top_k : 0));
+        std::vector<int32_t> n(keys.size(), 0);
+        check(s2m_sc_query_keys_ring(h_, keys.data(), (int32_t)keys.size(), &p, hits.data(), n.data()), "s2m_sc_query_keys_ring");
+        return scRows(hits, n, p.m.q.top_k);
+    }
+    std::vector<std::vector<s2m_sc_hit>> scQueryDescriptorsRing(const std::vector<double>& descs, const s2m_sc_ring_params& p)
+    {
+        const size_t m = descs.size() / (S2M_SC_NUM_RING * S2M_SC_NUM_SECTOR);
+        std::vector<s2m_sc_hit> hits(m * (size_t)(p.m.q.top_k > 0 ? p.m.q.top_k : 0));
+        std::vector<int32_t> n(m, 0);
+        check(s2m_sc_query_descriptors_ring(h_, descs.data(), (int32_t)m, &p, hits.data(), n.data()), "s2m_sc_query_descriptors_ring");
+        return scRows(hits, n, p.m.q.top_k);
+    }
+    std::vector<std::vector<s2m_sc_ring_neighbour>> scRingNeighboursKeys(const std::vector<int32_t>& keys, const s2m_sc_ring_params& p)
+    {
+        const size_t c = (size_t)(p.n_candidates > 0 ? p.n_candidates : 0);
+        std::vector<s2m_sc_ring_neighbour> nb(keys.size() * c);
+        std::vector<int32_t> n(keys.size(), 0);
+        check(s2m_sc_ring_neighbours_keys(h_, keys.data(), (int32_t)keys.size(), &p, nb.data(), n.data()), "s2m_sc_ring_neighbours_keys");
+        std::vector<std::vector<s2m_sc_ring_neighbour>> rows(keys.size());
+        for (size_t i = 0; i < rows.size(); i++) rows[i].assign(nb.begin() + i * c, nb.begin() + i * c + n[i]);
+        return rows;
+    }
     // the stored descriptors first .. first+count-1, bit for bit what was added
     std::vector<double> scGetDescriptors(int32_t first, int32_t count)
     {
@@ -751,17 +778,20 @@ public:
     // Loop discovery over a whole session (after a load, say): every stored key against the keys at least `gap` before it. The
     // candidates come in key_cur order, per key by (dist, key_pre); a node hands each key_cur's to loopVerify.
     struct SessionLoop { int32_t key_cur, key_pre; double dist; float yaw; };
-    std::vector<SessionLoop> findSessionLoops(int gap, double max_dist, int top_k, int align)
+    // ring_candidates > 0: every key against its ring_candidates ring-key neighbours among them only (scQueryKeysRing).
+    std::vector<SessionLoop> findSessionLoops(int gap, double max_dist, int top_k, int align, int ring_candidates = 0)
     {
-        s2m_sc_query_many_params p;
-        s2m_sc_query_many_default_params(&p);
+        s2m_sc_ring_params rp;
+        s2m_sc_ring_default_params(&rp);
+        s2m_sc_query_many_params& p = rp.m;
         p.q.top_k = top_k; p.q.align = align; p.q.max_dist = max_dist;
         p.rel_lo = 1 - gap; p.rel_hi = INT32_MAX;
+        rp.n_candidates = ring_candidates;
         const int n_keys = s2m_sc_size(h_);
         std::vector<int32_t> keys((size_t)(n_keys > 0 ? n_keys : 0));
         for (size_t k = 0; k < keys.size(); k++) keys[k] = (int32_t)k;
         std::vector<SessionLoop> out;
-        const std::vector<std::vector<s2m_sc_hit>> rows = scQueryKeys(keys, p);
+        const std::vector<std::vector<s2m_sc_hit>> rows = ring_candidates > 0 ? scQueryKeysRing(keys, rp) : scQueryKeys(keys, p);
         for (size_t k = 0; k < rows.size(); k++)
             for (const s2m_sc_hit& hit : rows[k]) out.push_back(SessionLoop{ (int32_t)k, hit.key, hit.dist, hit.yaw_diff_rad });
         return out;
@@ -796,10 +826,10 @@ public:
     // an accepted candidate, in key_cur order. between_chunks (may be empty) is called after every chunk: a node releases the scan
     // handler's lock there and takes it again, so the lock is held for rows_per_call rows at a time.
     std::vector<s2m_loop_result> verifySessionLoops(int gap, double max_dist, int top_k, int align, int base_key, int rows_per_call,
-                                                    const std::function<void()>& between_chunks = {})
+                                                    const std::function<void()>& between_chunks = {}, int ring_candidates = 0)
     {
         std::vector<VerifyRow> rows;
-        for (const SessionLoop& c : findSessionLoops(gap, max_dist, std::min(top_k, (int)S2M_LOOP_MAX_CANDIDATES), align)) {
+        for (const SessionLoop& c : findSessionLoops(gap, max_dist, std::min(top_k, (int)S2M_LOOP_MAX_CANDIDATES), align, ring_candidates)) {
             if (rows.empty() || rows.back().key_cur != c.key_cur) rows.push_back(VerifyRow{ c.key_cur, {} });
             rows.back().key_pre.push_back(c.key_pre);
         }

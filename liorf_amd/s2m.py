@@ -43,6 +43,8 @@ ABI_SYMBOLS = [
     "s2m_sc_query_default_params", "s2m_sc_query_check_args", "s2m_sc_query_key", "s2m_sc_query_descriptor", "s2m_sc_query_scan", "s2m_sc_query_projected",
     "s2m_sc_query_many_default_params", "s2m_sc_query_many_check_args", "s2m_sc_query_keys", "s2m_sc_query_descriptors", "s2m_sc_get_descriptors",
     "s2m_debug_sc_query_many_pass", "s2m_debug_sc_query_many_shape", "s2m_debug_sc_query_many_last",
+    "s2m_sc_ring_default_params", "s2m_sc_ring_check_args", "s2m_sc_ring_neighbours_keys", "s2m_sc_ring_neighbours_descriptors",
+    "s2m_sc_query_keys_ring", "s2m_sc_query_descriptors_ring", "s2m_debug_sc_ring_pass", "s2m_debug_sc_ring_shape", "s2m_debug_sc_ring_last",
     "s2m_kf_default_params", "s2m_kf_reset", "s2m_kf_size", "s2m_kf_add", "s2m_kf_set_poses", "s2m_extract_surrounding",
     "s2m_extract_surrounding_at",
     "s2m_loop_default_params", "s2m_loop_near_keyframes", "s2m_loop_align", "s2m_loop_closure_rs",
@@ -146,6 +148,20 @@ class ScQueryManyParams(C.Structure):
     """s2m_sc_query_many_params: the single query's parameters per query, and for stored-key queries the relative window
     [key + rel_lo, key + rel_hi) that is left out as well."""
     _fields_ = [("q", ScQueryParams), ("rel_lo", C.c_int32), ("rel_hi", C.c_int32)]
+
+
+class ScRingParams(C.Structure):
+    """s2m_sc_ring_params: the many-query's parameters and the number of ring-key neighbours that go on to the column-by-column
+    distance (1 .. S2M_SC_RING_MAX_CAND; 3 is the detector's NUM_CANDIDATES_FROM_TREE)."""
+    _fields_ = [("m", ScQueryManyParams), ("n_candidates", C.c_int32), ("reserved", C.c_int32)]
+
+
+class ScRingNeighbour(C.Structure):
+    _fields_ = [("d2", C.c_float), ("key", C.c_int32)]
+
+
+SC_RING_NEIGHBOUR_DTYPE = np.dtype([("d2", np.float32), ("key", np.int32)])
+S2M_SC_RING_MAX_CAND = 256
 
 
 class ScHit(C.Structure):
@@ -386,6 +402,16 @@ def load_library(path: str | None = None) -> C.CDLL:
     L.s2m_debug_sc_query_many_pass.argtypes = [vp, C.c_int32]
     L.s2m_debug_sc_query_many_shape.argtypes = [i32p, i32p]
     L.s2m_debug_sc_query_many_last.argtypes = [vp, i32p, C.POINTER(C.c_size_t)]
+    rp, nbp = C.POINTER(ScRingParams), C.POINTER(ScRingNeighbour)
+    L.s2m_sc_ring_default_params.argtypes = [rp]
+    L.s2m_sc_ring_check_args.argtypes = [C.c_int32, C.c_int32, rp, C.c_int32]
+    L.s2m_sc_ring_neighbours_keys.argtypes = [vp, i32p, C.c_int32, rp, nbp, i32p]
+    L.s2m_sc_ring_neighbours_descriptors.argtypes = [vp, dp, C.c_int32, rp, nbp, i32p]
+    L.s2m_sc_query_keys_ring.argtypes = [vp, i32p, C.c_int32, rp, hp, i32p]
+    L.s2m_sc_query_descriptors_ring.argtypes = [vp, dp, C.c_int32, rp, hp, i32p]
+    L.s2m_debug_sc_ring_pass.argtypes = [vp, C.c_int32]
+    L.s2m_debug_sc_ring_shape.argtypes = [i32p, i32p, i32p]
+    L.s2m_debug_sc_ring_last.argtypes = [vp, i32p, C.POINTER(C.c_size_t)]
     L.s2m_kf_default_params.argtypes = [C.POINTER(KfParams)]
     L.s2m_kf_reset.argtypes = [vp]
     L.s2m_kf_size.argtypes = [vp]
@@ -1147,12 +1173,67 @@ class MapOptimizationS2M:
         self._check(self.lib.s2m_sc_get_descriptors(self.h, first, count, out.ctypes.data_as(C.POINTER(C.c_double))), "s2m_sc_get_descriptors")
         return out
 
-    def findSessionLoops(self, gap: int = 30, max_dist: float = 0.3, top_k: int = 1, align: int = S2M_SC_ALIGN_FULL):
+    def _sessionLoopRows(self, gap, max_dist, top_k, align, ring_candidates):
+        """Every stored key against the keys at least `gap` before it: exhaustively (ring_candidates=None), or against its
+        ring_candidates ring-key neighbours among them."""
+        keys = np.arange(self.scSize(), dtype=np.int32)
+        kw = dict(top_k=top_k, align=align, max_dist=max_dist, rel_lo=1 - int(gap), rel_hi=2**31 - 1)
+        if ring_candidates is None:
+            return self.scQueryKeys(keys, **kw)
+        return self.scQueryKeysRing(keys, n_candidates=int(ring_candidates), **kw)
+
+    def findSessionLoops(self, gap: int = 30, max_dist: float = 0.3, top_k: int = 1, align: int = S2M_SC_ALIGN_FULL, ring_candidates=None):
         """Every stored key against the keys at least `gap` before it: the (key_cur, key_pre, dist, yaw_diff_rad) candidates a node
-        hands to loopVerify, in key_cur order and per key in (dist, key_pre) order."""
-        n = self.scSize()
-        rows = self.scQueryKeys(np.arange(n, dtype=np.int32), top_k=top_k, align=align, max_dist=max_dist, rel_lo=1 - int(gap), rel_hi=2**31 - 1)
+        hands to loopVerify, in key_cur order and per key in (dist, key_pre) order.  ring_candidates=C compares every key with its
+        C ring-key neighbours only (scQueryKeysRing) instead of with all of them."""
+        rows = self._sessionLoopRows(gap, max_dist, top_k, align, ring_candidates)
         return [(cur, int(h["key"]), float(h["dist"]), float(h["yaw_diff_rad"])) for cur, row in enumerate(rows) for h in row]
+
+    # -- the place query behind a ring-key prefilter (DESIGN.md section 22)
+    def _sc_ring(self, fn, what, arg, m, params, kw, both):
+        p = params if params is not None else default_sc_ring_params()
+        if kw:
+            p = default_sc_ring_params(**{**_sc_ring_fields(p), **kw})
+        width = max(int(p.m.q.top_k), 1) if both else max(int(p.n_candidates), 1)
+        rows = np.zeros((max(m, 1), width), SC_HIT_DTYPE if both else SC_RING_NEIGHBOUR_DTYPE)
+        n = np.zeros(max(m, 1), np.int32)
+        self._check(fn(self.h, arg, m, C.byref(p), rows.ctypes.data_as(C.POINTER(ScHit if both else ScRingNeighbour)),
+                       n.ctypes.data_as(C.POINTER(C.c_int32))), what)
+        return [rows[i, :n[i]].copy() for i in range(m)]
+
+    def scRingNeighboursKeys(self, keys, params: "ScRingParams | None" = None, **kw):
+        """s2m_sc_ring_neighbours_keys: for every stored key of `keys` its n_candidates ring-key neighbours in its searched set
+        (SC_RING_NEIGHBOUR_DTYPE records, ascending (d2, key)).  Keyword arguments set n_candidates and the many-query's fields."""
+        k = np.ascontiguousarray(keys, np.int32).reshape(-1)
+        return self._sc_ring(self.lib.s2m_sc_ring_neighbours_keys, "s2m_sc_ring_neighbours_keys", k.ctypes.data_as(C.POINTER(C.c_int32)), len(k),
+                             params, kw, False)
+
+    def scRingNeighboursDescriptors(self, descs, params: "ScRingParams | None" = None, **kw):
+        """s2m_sc_ring_neighbours_descriptors: the same for descriptors from elsewhere, (m, 20, 60) doubles."""
+        d = np.ascontiguousarray(descs, np.float64).reshape(-1, 20, 60)
+        return self._sc_ring(self.lib.s2m_sc_ring_neighbours_descriptors, "s2m_sc_ring_neighbours_descriptors",
+                             d.ctypes.data_as(C.POINTER(C.c_double)), len(d), params, kw, False)
+
+    def scQueryKeysRing(self, keys, params: "ScRingParams | None" = None, **kw):
+        """s2m_sc_query_keys_ring: scQueryKeys with every query's searched set cut to its n_candidates ring-key neighbours."""
+        k = np.ascontiguousarray(keys, np.int32).reshape(-1)
+        return self._sc_ring(self.lib.s2m_sc_query_keys_ring, "s2m_sc_query_keys_ring", k.ctypes.data_as(C.POINTER(C.c_int32)), len(k), params, kw, True)
+
+    def scQueryDescriptorsRing(self, descs, params: "ScRingParams | None" = None, **kw):
+        """s2m_sc_query_descriptors_ring: the same for descriptors from elsewhere, (m, 20, 60) doubles."""
+        d = np.ascontiguousarray(descs, np.float64).reshape(-1, 20, 60)
+        return self._sc_ring(self.lib.s2m_sc_query_descriptors_ring, "s2m_sc_query_descriptors_ring", d.ctypes.data_as(C.POINTER(C.c_double)), len(d),
+                             params, kw, True)
+
+    def scRingPass(self, queries_per_pass: int):
+        """s2m_debug_sc_ring_pass: at most this many queries per pass of the ring calls (0: the default)."""
+        self._check(self.lib.s2m_debug_sc_ring_pass(self.h, queries_per_pass), "s2m_debug_sc_ring_pass")
+
+    def scRingLast(self):
+        """s2m_debug_sc_ring_last: (passes, device bytes of one pass) of the last ring call."""
+        n, b = C.c_int32(0), C.c_size_t(0)
+        self._check(self.lib.s2m_debug_sc_ring_last(self.h, C.byref(n), C.byref(b)), "s2m_debug_sc_ring_last")
+        return n.value, b.value
 
     def scQueryManyPass(self, queries_per_pass: int):
         """s2m_debug_sc_query_many_pass: at most this many queries per pass (0: the default)."""
@@ -1762,12 +1843,11 @@ class MapOptimizationS2M:
         return ([[_copy_struct(recs[r * stride + i]) for i in range(n_cand[r])] for r in range(m)], [best[r] for r in range(m)])
 
     def verifySessionLoops(self, gap: int = 30, max_dist: float = 0.3, top_k: int = 1, align: int = S2M_SC_ALIGN_FULL, base_key: int = 0,
-                           params: LoopParams | None = None, rows_per_call: int = 64):
-        """findSessionLoops' query followed by loopVerifyMany in chunks of rows_per_call rows (a node releases its lock between
-        chunks): the winning records, one per key that has an accepted candidate, in key_cur order."""
+                           params: LoopParams | None = None, rows_per_call: int = 64, ring_candidates=None):
+        """findSessionLoops' query (ring_candidates as there) followed by loopVerifyMany in chunks of rows_per_call rows (a node
+        releases its lock between chunks): the winning records, one per key that has an accepted candidate, in key_cur order."""
         top_k = min(int(top_k), S2M_LOOP_MAX_CANDIDATES)
-        n = self.scSize()
-        hits = self.scQueryKeys(np.arange(n, dtype=np.int32), top_k=top_k, align=align, max_dist=max_dist, rel_lo=1 - int(gap), rel_hi=2**31 - 1)
+        hits = self._sessionLoopRows(gap, max_dist, top_k, align, ring_candidates)
         rows = [(cur, [int(h["key"]) for h in row]) for cur, row in enumerate(hits) if len(row)]
         won = []
         for i in range(0, len(rows), max(int(rows_per_call), 1)):
@@ -2041,6 +2121,35 @@ def default_sc_query_many_params(**kw) -> ScQueryManyParams:
 def sc_query_many_check_args(n_stored: int, m: int, params: "ScQueryManyParams | None", descriptor_query: bool = False) -> int:
     """s2m_sc_query_many_check_args (host only, no GPU): the status code.  params=None passes a null pointer (the defaults)."""
     return load_library().s2m_sc_query_many_check_args(n_stored, m, None if params is None else C.byref(params), int(descriptor_query))
+
+
+def _sc_ring_fields(p) -> dict:
+    return {**_sc_many_fields(p.m), "n_candidates": p.n_candidates, "reserved": p.reserved}
+
+
+def default_sc_ring_params(**kw) -> ScRingParams:
+    """s2m_sc_ring_default_params; keyword arguments set n_candidates, reserved and the fields of the many-query's parameters."""
+    p = ScRingParams()
+    load_library().s2m_sc_ring_default_params(C.byref(p))
+    for k, v in kw.items():
+        tgt = p if k in ("n_candidates", "reserved") else p.m if k in ("rel_lo", "rel_hi") else p.m.q
+        if not hasattr(tgt, k):
+            raise AttributeError(k)
+        setattr(tgt, k, v)
+    return p
+
+
+def sc_ring_check_args(n_stored: int, m: int, params: "ScRingParams | None", descriptor_query: bool = False) -> int:
+    """s2m_sc_ring_check_args (host only, no GPU): the status code.  params=None passes a null pointer (the defaults)."""
+    return load_library().s2m_sc_ring_check_args(n_stored, m, None if params is None else C.byref(params), int(descriptor_query))
+
+
+def sc_ring_shape():
+    """s2m_debug_sc_ring_shape: (stored ring keys of a tile, queries of a block, words of a query's candidate buffer) of
+    k_sc_ring_select."""
+    t, b, w = C.c_int32(0), C.c_int32(0), C.c_int32(0)
+    load_library().s2m_debug_sc_ring_shape(C.byref(t), C.byref(b), C.byref(w))
+    return t.value, b.value, w.value
 
 
 def sc_query_many_shape():
