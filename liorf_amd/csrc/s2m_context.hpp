@@ -182,16 +182,15 @@ struct __attribute__((visibility("hidden"))) s2m_context {
         DevBuf many_in, many_qnorm, many_part, many_out;
         unsigned char* h_many = nullptr;
         size_t h_many_cap = 0;
-        int    many_pass = 0;              // queries per pass; 0: as many as the scratch bound allows (s2m_debug_sc_query_many_pass)
-        int    many_last_passes = 0;       // of the last many-query: its passes and the device bytes of one pass
-        size_t many_last_scratch = 0;
+        // pass: queries per pass, 0: as many as the scratch bound allows (s2m_debug_sc_query_many_pass / s2m_debug_sc_ring_pass);
+        // last_*: of the last call, its passes and the device bytes of one pass
+        struct ScPassState { int pass = 0; int last_passes = 0; size_t last_scratch = 0; };
+        ScPassState many;
         // the ring-key prefilter's pass (s2m_sc_ring.hpp): the queries' keys or descriptors + sector keys + fp32 ring keys, the
         // neighbour lists and their sizes, the candidates' distances and shifts, the rows; together at most kScManyScratchMax.
         // The pinned block of a pass is h_many.
         DevBuf ring_in, ring_cand, ring_dist, ring_out;
-        int    ring_pass = 0;              // queries per pass; 0: as many as the scratch bound allows (s2m_debug_sc_ring_pass)
-        int    ring_last_passes = 0;       // of the last ring query: its passes and the device bytes of one pass
-        size_t ring_last_scratch = 0;
+        ScPassState ring;
         size_t n = 0, cap = 0, n_search = 0;
         int    counter = 0;                // tree_making_period_conter (include/Scancontext.cpp:270-283)
         double* h_stage = nullptr;         // pinned [1200 + 20]: descriptor + ring key, or the detection's result, or the query's hits

@@ -1,8 +1,9 @@
 // s2m_sc_dist.hpp — the distance of two ScanContext descriptors: the arithmetic of a pair as device functions of one thread's
 // share each, called by every kernel that compares descriptors, and distanceBtnScanContext (reference
-// include/Scancontext.cpp:116-148) by one workgroup, shared by the detector and batched distance (s2m_sc.hip) and by the place
-// query (s2m_sc_query.hip).  Compiled with -ffp-contract=off; all sums run left to right in fp64 like the oracle's restatement,
-// so distances are bit-identical to it.
+// include/Scancontext.cpp:116-148) by one workgroup, shared by the detector and batched distance (s2m_sc.hip), the place query
+// (s2m_sc_query.hip) and the ring-key prefilter (s2m_sc_ring.hip); beside it the full alignment over all 60 shifts by one
+// workgroup (sc_full_block), shared by the last two.  Compiled with -ffp-contract=off; all sums run left to right in fp64 like
+// the oracle's restatement, so distances are bit-identical to it.
 #pragma once
 #include <hip/hip_runtime.h>
 #include "../../include/liorf_s2m.h"
@@ -163,6 +164,75 @@ __device__ __forceinline__ void sc_distance_block(const double* __restrict__ sto
         m.dist_out = min_sc_dist; m.shift_out = argmin_shift;
     }
     __syncthreads();
+}
+
+constexpr int kScFullChunk = 12;       // shifts of the full alignment a workgroup evaluates between two barriers
+constexpr int kScFullLanes = 4;        // ... by 4 x 60 threads: thread (g, j) owns sector j of the query and the shifts g, g + 4, ... of a chunk
+static_assert(S2M_SC_NUM_SECTOR % kScFullChunk == 0 && kScFullChunk % kScFullLanes == 0, "the chunks cover the 60 shifts");
+static_assert(kScFullLanes * S2M_SC_NUM_SECTOR <= kScThreads, "one thread per (lane, sector)");
+static_assert(S2M_SC_NUM_SECTOR % 2 == 0, "descriptors are staged two doubles at a time");
+
+// LDS of the full alignment: the NC candidates, their column norms, one chunk of similarities
+template <int NC>
+struct alignas(16) ScFullShared {
+    double c[NC][S2M_SC_NUM_RING * S2M_SC_NUM_SECTOR];
+    double cnorm[NC][S2M_SC_NUM_SECTOR];
+    double sim[NC][kScFullChunk][S2M_SC_NUM_SECTOR];
+    unsigned char eff[NC][kScFullChunk][S2M_SC_NUM_SECTOR];
+    double dist[NC][kScFullChunk];
+    double dist_out[NC];                                 // the result: distance and the shift it was found at
+    int    shift_out[NC];
+};
+
+// min over s = 0..59 ascending of distDirectSC(query, circshift(cand[c], s)) (:69-91), strict, from 10000000 / shift 0, for NC
+// candidates side by side by one workgroup (the single query and the ring-key prefilter; the many-query's two queries x four
+// candidates are its own arrangement of the same functions).  A column's norm does not depend on the shift it is paired with: 60
+// norms per descriptor, then one independent left-to-right dot product of 20 terms per (shift, sector).  Thread (g, j) =
+// (t / 60, t % 60), t < 240, holds column j of the query (qcol) and its norm (n1) in registers, so a term costs one LDS read.
+// `cand` lives in LDS.  The block has no barrier at either end, the callers' own serve: one between writing `cand` (and reading the
+// scratch of a previous call) and the call; thread c leaves the results in m.dist_out[c] / m.shift_out[c], and a caller in which
+// another thread reads them puts one behind the call.
+template <int NC>
+__device__ __forceinline__ void sc_full_block(const double* __restrict__ store_desc, const double (&qcol)[S2M_SC_NUM_RING], double n1, const int* cand,
+                                              ScFullShared<NC>& m)
+{
+    constexpr int NR = S2M_SC_NUM_RING, NS = S2M_SC_NUM_SECTOR, ND = NR * NS;
+    static_assert(NC * kScFullChunk <= kScThreads, "one thread per sector sum");
+    const int t = threadIdx.x;
+    const int g = t / NS, j = t - g * NS;
+    for (int task = t; task < NC * (ND / 2); task += kScThreads) {
+        const int c = task / (ND / 2), k = task - c * (ND / 2);
+        reinterpret_cast<double2*>(m.c[c])[k] = reinterpret_cast<const double2*>(store_desc + (size_t)cand[c] * ND)[k];   // (slots are 9600 bytes: 16-byte aligned)
+    }
+    if (t < NC) { m.dist_out[t] = 10000000; m.shift_out[t] = 0; }
+    __syncthreads();
+    for (int task = t; task < NC * NS; task += kScThreads) {
+        const int c = task / NS, jc = task - c * NS;
+        m.cnorm[c][jc] = sc_col_norm([&](int r) { return m.c[c][r * NS + jc]; });
+    }
+    __syncthreads();
+    for (int s0 = 0; s0 < NS; s0 += kScFullChunk) {
+        if (g < kScFullLanes) {
+            for (int k = g; k < kScFullChunk; k += kScFullLanes) {
+                int j2 = j - (s0 + k); j2 += (j2 < 0) ? NS : 0;            // circshift (:39-59)
+#pragma unroll
+                for (int c = 0; c < NC; c++) {
+                    const double dot = sc_col_dot([&](int r) { return qcol[r]; }, [&](int r) { return m.c[c][r * NS + j2]; });
+                    m.eff[c][k][j] = sc_sector_sim(dot, n1, m.cnorm[c][j2], &m.sim[c][k][j]) ? 1 : 0;
+                }
+            }
+        }
+        __syncthreads();
+        if (t < NC * kScFullChunk) {
+            const int c = t / kScFullChunk, k = t - c * kScFullChunk;
+            m.dist[c][k] = sc_sector_sum_dist([&](int jj) { return m.eff[c][k][jj] != 0; }, [&](int jj) { return m.sim[c][k][jj]; });
+        }
+        __syncthreads();
+        if (t < NC)
+            for (int k = 0; k < kScFullChunk; k++)
+                sc_min_update(m.dist[t][k], s0 + k, &m.dist_out[t], &m.shift_out[t]);
+        // (the next chunk writes sim / eff only; dist is written again behind its barrier)
+    }
 }
 
 // yaw difference of a column shift: deg2rad(float) of shift * PC_UNIT_SECTORANGLE (:17-20, :338-339)

@@ -1,8 +1,8 @@
 // s2m_sc_keys.hpp — the two keys of a ScanContext descriptor, stated once: the ring key (row mean, makeRingkeyFromScancontext,
 // include/Scancontext.cpp:198-211) and the sector key (column mean, makeSectorkeyFromScancontext, :214-227).  Both sum left to
 // right in fp64.  Every place that makes a key calls these - k_sc_finish and k_sc_append (s2m_sc.hip), s2m_sc_add_descriptor on
-// the host (s2m_abi_sc.hip) and the batch rebuild of a loaded session (k_sc_keys_batch, s2m_session.hip) - so a store that was
-// loaded holds bit for bit the keys the incremental adds left.  Compiled with -ffp-contract=off like everything else.
+// the host (s2m_abi_sc.hip), the batch rebuild of a loaded session (k_sc_keys_batch, s2m_session.hip) and, through sc_ext_keys,
+// the place query's three prepare kernels - so a store that was loaded holds bit for bit the keys the incremental adds left.  Compiled with -ffp-contract=off like everything else.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -40,6 +40,16 @@ __host__ __device__ __forceinline__ double sc_sector_key(At at)
     double a = 0.0;
     for (int r = 0; r < S2M_SC_NUM_RING; r++) a += at(r);
     return a / (double)S2M_SC_NUM_RING;
+}
+
+// The keys of an external descriptor q for a query, by threads t = 0 .. 63 of a workgroup: its sector key and, where `ring` is
+// given, its ring key as s2m_sc_add_descriptor stores it ((float) of the row mean).  The prepare kernels of the place query, the
+// many-query and the ring-key prefilter call this.
+__device__ __forceinline__ void sc_ext_keys(const double* q, int t, double* sector, float* ring)
+{
+    constexpr int NR = S2M_SC_NUM_RING, NS = S2M_SC_NUM_SECTOR;
+    if (ring && t < NR) ring[t] = (float)sc_ring_key([&](int k) { return q[t * NS + k]; });
+    if (t < NS) sector[t] = sc_sector_key([&](int r) { return q[r * NS + t]; });
 }
 
 }  // namespace s2m

@@ -13,6 +13,7 @@
 #include "s2m_sc_dist.hpp"
 #include "s2m_sc_keys.hpp"
 #include "s2m_sc_many.hpp"
+#include "s2m_sc_rank.hpp"
 
 namespace s2m {
 
@@ -39,8 +40,6 @@ struct ScManyDev {                     // what the kernels read of ScManyArgs
     double max_dist;
 };
 
-__device__ __forceinline__ bool sc_hit_less(double da, int ka, double db, int kb) { return da < db || (da == db && ka < kb); }
-
 __device__ __forceinline__ const double* sc_many_qdesc(const ScManyDev& a, int i)
 {
     return a.keys ? a.store_desc + (size_t)a.keys[i] * ND : a.ext_desc + (size_t)i * ND;
@@ -48,17 +47,6 @@ __device__ __forceinline__ const double* sc_many_qdesc(const ScManyDev& a, int i
 __device__ __forceinline__ const double* sc_many_qsector(const ScManyDev& a, int i)
 {
     return a.keys ? a.store_sector + (size_t)a.keys[i] * NS : a.ext_sector + (size_t)i * NS;
-}
-
-// (d, key, shift) into a list of at most top_k, ascending (distance, key)
-__device__ __forceinline__ void sc_many_insert(double* hd, int* hk, int* hs, int* n_held, int top_k, double d, int key, int shift)
-{
-    int n = *n_held;
-    if (n == top_k && !sc_hit_less(d, key, hd[top_k - 1], hk[top_k - 1])) return;
-    int p = (n < top_k) ? n++ : top_k - 1;
-    while (p > 0 && sc_hit_less(d, key, hd[p - 1], hk[p - 1])) { hd[p] = hd[p - 1]; hk[p] = hk[p - 1]; hs[p] = hs[p - 1]; p--; }
-    hd[p] = d; hk[p] = key; hs[p] = shift;
-    *n_held = n;
 }
 
 // One workgroup per query: the 60 column norms, and for an external descriptor its sector key (makeSectorkeyFromScancontext).
@@ -69,7 +57,7 @@ __global__ __launch_bounds__(kPrepThreads) void k_sc_many_prepare(ScManyDev a, d
     const double* __restrict__ q = sc_many_qdesc(a, i);
     const auto col = [&](int r) { return q[r * NS + t]; };
     qnorm[(size_t)i * NS + t] = sc_col_norm(col);
-    if (!a.keys) ext_sector[(size_t)i * NS + t] = sc_sector_key(col);
+    if (!a.keys) sc_ext_keys(q, t, ext_sector + (size_t)i * NS, nullptr);
 }
 
 // the tile: T stored descriptors, their column norms and (sector-key alignment) sector keys
@@ -181,7 +169,7 @@ __global__ __launch_bounds__(kScThreads) void k_sc_many_dist(ScManyDev a, double
                             if (dg < d || (dg == d && dg < 10000000 && sgg < shift)) { d = dg; shift = sgg; }
                         }
                         if (d < a.max_dist && sc_many_in_set(a.set, s_qkey[qq + t], c0 + c))
-                            sc_many_insert(s_hd[qq + t], s_hk[qq + t], s_hs[qq + t], &s_held[qq + t], a.top_k, d, c0 + c, shift);
+                            sc_hit_insert(s_hd[qq + t], s_hk[qq + t], s_hs[qq + t], &s_held[qq + t], a.top_k, d, c0 + c, shift);
                     }
                 }
                 // (dist_out is written again behind the barriers of the next query pair's chunks)
@@ -227,7 +215,7 @@ __global__ __launch_bounds__(kScThreads) void k_sc_many_dist(ScManyDev a, double
                         double d = 10000000; int shift = 0;
                         for (int k = 0; k < kScShifts; k++) sc_min_update(s_m.dist[c][k], s_m.shifts[c][k], &d, &shift);
                         if (d < a.max_dist && sc_many_in_set(a.set, s_qkey[qq], c0 + c))
-                            sc_many_insert(s_hd[qq], s_hk[qq], s_hs[qq], &s_held[qq], a.top_k, d, c0 + c, shift);
+                            sc_hit_insert(s_hd[qq], s_hk[qq], s_hs[qq], &s_held[qq], a.top_k, d, c0 + c, shift);
                     }
                 }
             }
@@ -236,10 +224,7 @@ __global__ __launch_bounds__(kScThreads) void k_sc_many_dist(ScManyDev a, double
     __syncthreads();
     for (int task = t; task < nq * a.top_k; task += kScThreads) {
         const int qq = task / a.top_k, k = task - qq * a.top_k;
-        const bool have = k < s_held[qq];
-        const size_t e = ((size_t)(q0 + qq) * gridDim.x + blockIdx.x) * a.top_k + k;
-        part_d[e] = have ? s_hd[qq][k] : INFINITY;
-        part_ks[e] = make_int2(have ? s_hk[qq][k] : INT_MAX, have ? s_hs[qq][k] : 0);
+        sc_hit_store(part_d, part_ks, ((size_t)(q0 + qq) * gridDim.x + blockIdx.x) * a.top_k + k, s_hd[qq], s_hk[qq], s_hs[qq], s_held[qq], k);
     }
 }
 
@@ -260,18 +245,9 @@ __global__ __launch_bounds__(kScThreads) void k_sc_many_select(const double* __r
             const int2 ks = part_ks[e];
             if (sc_hit_less(d, ks.x, bd, bk)) { bd = d; bk = ks.x; bs = ks.y; bg = lane; }
         }
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) {
-            const double od = __shfl_xor(bd, off, 64);
-            const int ok = __shfl_xor(bk, off, 64), os = __shfl_xor(bs, off, 64), og = __shfl_xor(bg, off, 64);
-            if (sc_hit_less(od, ok, bd, bk)) { bd = od; bk = ok; bs = os; bg = og; }
-        }
+        sc_hit_wave_min(bd, bk, bs, bg);
         if (bg < 0) break;                                // every list is used up (the same for all lanes)
-        if (lane == 0) {
-            s2m_sc_hit hit;
-            hit.dist = bd; hit.key = bk; hit.shift = bs; hit.yaw_diff_rad = sc_shift_to_yaw(bs); hit.reserved = 0;
-            out_hits[(size_t)qi * top_k + round] = hit;
-        }
+        if (lane == 0) out_hits[(size_t)qi * top_k + round] = sc_hit_record(bd, bk, bs);
         n_hits = round + 1;
         if (bg == lane) head++;
     }

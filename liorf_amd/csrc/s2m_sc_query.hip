@@ -12,87 +12,23 @@
 #include "s2m_sc_dist.hpp"
 #include "s2m_sc_keys.hpp"
 #include "s2m_sc_query.hpp"
+#include "s2m_sc_rank.hpp"
 
 namespace s2m {
 
 namespace {
 
 constexpr int NR = S2M_SC_NUM_RING, NS = S2M_SC_NUM_SECTOR, ND = NR * NS;
-constexpr int kScFullChunk = 12;       // shifts of the full alignment a workgroup evaluates between two barriers
-constexpr int kScFullLanes = 4;        // ... by 4 x 60 threads: thread (g, j) owns sector j of the query and the shifts g, g + 4, ... of a chunk
-static_assert(NS % kScFullChunk == 0 && kScFullChunk % kScFullLanes == 0, "the chunks cover the 60 shifts");
-static_assert(kScFullLanes * NS <= kScThreads && kScQueryCands * kScFullChunk <= kScThreads, "one thread per task");
 static_assert(ND % 2 == 0 && NS % 2 == 0, "descriptors and sector keys are staged two doubles at a time");
-
-__device__ __forceinline__ bool sc_hit_less(double da, int ka, double db, int kb) { return da < db || (da == db && ka < kb); }
 
 // the query's descriptor and sector key into the slot.  src_desc may be the slot itself (a descriptor uploaded in place).
 __global__ __launch_bounds__(kScThreads) void k_sc_query_prepare(const double* src_desc, const double* src_sector, double* slot)
 {
     const int t = threadIdx.x;
-    if (t < NS) {
-        // makeSectorkeyFromScancontext (:214-227) as k_sc_append
-        slot[ND + t] = src_sector ? src_sector[t] : sc_sector_key([&](int r) { return src_desc[r * NS + t]; });
-    }
+    if (!src_sector) sc_ext_keys(src_desc, t, slot + ND, nullptr);     // makeSectorkeyFromScancontext (:214-227) as k_sc_append
+    else if (t < NS) slot[ND + t] = src_sector[t];
     if (src_desc != slot)
         for (int k = t; k < ND; k += kScThreads) slot[k] = src_desc[k];
-}
-
-// LDS of the full alignment: the three candidates, their column norms, one chunk of similarities
-struct alignas(16) ScFullShared {
-    double c[kScQueryCands][ND];
-    double cnorm[kScQueryCands][NS];
-    double sim[kScQueryCands][kScFullChunk][NS];
-    unsigned char eff[kScQueryCands][kScFullChunk][NS];
-    double dist[kScQueryCands][kScFullChunk];
-    double dist_out[kScQueryCands];
-    int    shift_out[kScQueryCands];
-};
-
-// min over s = 0..59 ascending of distDirectSC(query, circshift(cand[c], s)) (:69-91), strict, from 10000000 / shift 0, for the
-// three candidates side by side.  A column's norm does not depend on the shift it is paired with: 60 norms per descriptor, then
-// one independent left-to-right dot product of 20 terms per (shift, sector).  Thread (g, j) = (t / 60, t % 60), t < 240, holds
-// column j of the query (qcol) and its norm (n1) in registers for the whole kernel, so a term costs one LDS read.
-__device__ __forceinline__ void sc_full_block(const double* __restrict__ store_desc, const double (&qcol)[NR], double n1, const int* cand,
-                                              ScFullShared& m)
-{
-    const int t = threadIdx.x;
-    const int g = t / NS, j = t - g * NS;
-    __syncthreads();                                     // the scratch may still be read from the previous triple
-    for (int task = t; task < kScQueryCands * (ND / 2); task += kScThreads) {
-        const int c = task / (ND / 2), k = task - c * (ND / 2);
-        reinterpret_cast<double2*>(m.c[c])[k] = reinterpret_cast<const double2*>(store_desc + (size_t)cand[c] * ND)[k];   // (slots are 9600 bytes: 16-byte aligned)
-    }
-    if (t < kScQueryCands) { m.dist_out[t] = 10000000; m.shift_out[t] = 0; }
-    __syncthreads();
-    for (int task = t; task < kScQueryCands * NS; task += kScThreads) {
-        const int c = task / NS, jc = task - c * NS;
-        m.cnorm[c][jc] = sc_col_norm([&](int r) { return m.c[c][r * NS + jc]; });
-    }
-    __syncthreads();
-    for (int s0 = 0; s0 < NS; s0 += kScFullChunk) {
-        if (g < kScFullLanes) {
-            for (int k = g; k < kScFullChunk; k += kScFullLanes) {
-                int j2 = j - (s0 + k); j2 += (j2 < 0) ? NS : 0;            // circshift (:39-59)
-#pragma unroll
-                for (int c = 0; c < kScQueryCands; c++) {
-                    const double dot = sc_col_dot([&](int r) { return qcol[r]; }, [&](int r) { return m.c[c][r * NS + j2]; });
-                    m.eff[c][k][j] = sc_sector_sim(dot, n1, m.cnorm[c][j2], &m.sim[c][k][j]) ? 1 : 0;
-                }
-            }
-        }
-        __syncthreads();
-        if (t < kScQueryCands * kScFullChunk) {
-            const int c = t / kScFullChunk, k = t - c * kScFullChunk;
-            m.dist[c][k] = sc_sector_sum_dist([&](int jj) { return m.eff[c][k][jj] != 0; }, [&](int jj) { return m.sim[c][k][jj]; });
-        }
-        __syncthreads();
-        if (t < kScQueryCands)
-            for (int k = 0; k < kScFullChunk; k++)
-                sc_min_update(m.dist[t][k], s0 + k, &m.dist_out[t], &m.shift_out[t]);
-        // (the next chunk writes sim / eff only; dist is written again behind its barrier)
-    }
-    __syncthreads();
 }
 
 template <int ALIGN>
@@ -100,7 +36,7 @@ __global__ __launch_bounds__(kScThreads) void k_sc_query_dist(const double* __re
                                                               const double* __restrict__ slot, int first, int n_before, int skip, int n_s,
                                                               int top_k, double max_dist, double* __restrict__ part_d, int2* __restrict__ part_ks)
 {
-    using Scratch = typename std::conditional<ALIGN == S2M_SC_ALIGN_FULL, ScFullShared, ScShared[kScQueryCands]>::type;
+    using Scratch = typename std::conditional<ALIGN == S2M_SC_ALIGN_FULL, ScFullShared<kScQueryCands>, ScShared[kScQueryCands]>::type;
     __shared__ Scratch s_m;
     __shared__ int    s_cand[kScQueryCands];
     __shared__ double s_hd[S2M_SC_QUERY_MAX_K];          // this workgroup's best, ascending (distance, key)
@@ -127,30 +63,21 @@ __global__ __launch_bounds__(kScThreads) void k_sc_query_dist(const double* __re
             const int i = i0 + (t < nc ? t : 0);          // a short tail compares its first key again and drops the result
             s_cand[t] = first + i + (i >= n_before ? skip : 0);
         }
-        __syncthreads();
-        if constexpr (ALIGN == S2M_SC_ALIGN_FULL) sc_full_block(store_desc, qcol, n1, s_cand, s_m);
+        __syncthreads();                                  // s_cand is written (and the scratch free since the previous triple's last barrier)
+        if constexpr (ALIGN == S2M_SC_ALIGN_FULL) { sc_full_block(store_desc, qcol, n1, s_cand, s_m); __syncthreads(); }   // thread 0 reads three threads' results
         else sc_distance_block<kScQueryCands>(store_desc, store_sector, s_q, s_qkey, s_cand, s_m);
         if (t == 0) {
             for (int c = 0; c < nc; c++) {
                 double d; int shift;
                 if constexpr (ALIGN == S2M_SC_ALIGN_FULL) { d = s_m.dist_out[c]; shift = s_m.shift_out[c]; }
                 else { d = s_m[c].dist_out; shift = s_m[c].shift_out; }
-                const int key = s_cand[c];
-                if (!(d < max_dist)) continue;
-                if (n_held == top_k && !sc_hit_less(d, key, s_hd[top_k - 1], s_hk[top_k - 1])) continue;
-                int p = (n_held < top_k) ? n_held++ : top_k - 1;
-                while (p > 0 && sc_hit_less(d, key, s_hd[p - 1], s_hk[p - 1])) { s_hd[p] = s_hd[p - 1]; s_hk[p] = s_hk[p - 1]; s_hs[p] = s_hs[p - 1]; p--; }
-                s_hd[p] = d; s_hk[p] = key; s_hs[p] = shift;
+                if (d < max_dist) sc_hit_insert(s_hd, s_hk, s_hs, &n_held, top_k, d, s_cand[c], shift);
             }
         }
         __syncthreads();                                  // s_cand is read until here
     }
     if (t == 0)
-        for (int k = 0; k < top_k; k++) {
-            const bool have = k < n_held;
-            part_d[(size_t)blockIdx.x * top_k + k] = have ? s_hd[k] : INFINITY;
-            part_ks[(size_t)blockIdx.x * top_k + k] = make_int2(have ? s_hk[k] : INT_MAX, have ? s_hs[k] : 0);
-        }
+        for (int k = 0; k < top_k; k++) sc_hit_store(part_d, part_ks, (size_t)blockIdx.x * top_k + k, s_hd, s_hk, s_hs, n_held, k);
 }
 
 // The workgroups' lists (each ascending, padded with (inf, INT_MAX)) into the final K: thread t holds the heads of lists t,
@@ -179,12 +106,7 @@ __global__ __launch_bounds__(kScThreads) void k_sc_query_select(const double* __
                 if (sc_hit_less(d, ks.x, bd, bk)) { bd = d; bk = ks.x; bs = ks.y; bg = g; }
             }
         }
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) {
-            const double od = __shfl_xor(bd, off, 64);
-            const int ok = __shfl_xor(bk, off, 64), os = __shfl_xor(bs, off, 64), og = __shfl_xor(bg, off, 64);
-            if (sc_hit_less(od, ok, bd, bk)) { bd = od; bk = ok; bs = os; bg = og; }
-        }
+        sc_hit_wave_min(bd, bk, bs, bg);
         if ((t & 63) == 0) { w_d[t >> 6] = bd; w_k[t >> 6] = bk; w_s[t >> 6] = bs; w_g[t >> 6] = bg; }
         __syncthreads();
         bd = w_d[0]; bk = w_k[0]; bs = w_s[0]; bg = w_g[0];
@@ -193,11 +115,7 @@ __global__ __launch_bounds__(kScThreads) void k_sc_query_select(const double* __
             if (sc_hit_less(w_d[w], w_k[w], bd, bk)) { bd = w_d[w]; bk = w_k[w]; bs = w_s[w]; bg = w_g[w]; }
         __syncthreads();                                  // w_* are written again in the next round
         if (bg < 0) break;                                // every list is used up (the same for all threads)
-        if (t == 0) {
-            s2m_sc_hit hit;
-            hit.dist = bd; hit.key = bk; hit.shift = bs; hit.yaw_diff_rad = sc_shift_to_yaw(bs); hit.reserved = 0;
-            out->hits[round] = hit;
-        }
+        if (t == 0) out->hits[round] = sc_hit_record(bd, bk, bs);
         n_hits = round + 1;
 #pragma unroll
         for (int u = 0; u < kLists; u++)

@@ -13,6 +13,7 @@
 
 #include "s2m_sc_dist.hpp"
 #include "s2m_sc_keys.hpp"
+#include "s2m_sc_rank.hpp"
 #include "s2m_sc_ring.hpp"
 
 namespace s2m {
@@ -25,24 +26,17 @@ constexpr int T = kScRingTile, B = kScRingBlock, BUF = kScRingBuf;
 constexpr int kSelThreads = 64;                       // k_sc_ring_select: one wave a workgroup, so every barrier is the wave's own
 constexpr int kOwn = BUF / kSelThreads;               // buffer words a lane ranks in a prune
 constexpr int NC = kScRingCands;
-constexpr int kFullChunk = 12;                        // full alignment: shifts between two barriers, by 4 x 60 threads: thread (g, j) owns
-constexpr int kFullLanes = 4;                         // ... sector j of the query and the shifts g, g + 4, ... of a chunk
 constexpr unsigned long long kRingInf = 0x7f800000ull << 32;   // bits(+inf) << 32: a word below it is a neighbour
 static_assert(NR % 4 == 0 && BUF % kSelThreads == 0 && T % kSelThreads == 0, "whole float4, whole wave steps");
-static_assert(NS % kFullChunk == 0 && kFullChunk % kFullLanes == 0 && kFullLanes * NS <= kScThreads && NC * kFullChunk <= kScThreads, "the chunks cover the 60 shifts, one thread per task");
 static_assert(S2M_SC_RING_MAX_CAND <= 4 * 64, "k_sc_ring_rank: four records a lane");
 static_assert(sizeof(s2m_sc_ring_neighbour) == 8, "a neighbour is (d2, key)");
 
-__device__ __forceinline__ bool sc_hit_less(double da, int ka, double db, int kb) { return da < db || (da == db && ka < kb); }
-
 // One workgroup per external descriptor: its ring key as s2m_sc_add_descriptor stores it ((float) of the row mean) and its
-// sector key (makeSectorkeyFromScancontext), k_sc_many_prepare's statement.
+// sector key (makeSectorkeyFromScancontext): sc_ext_keys.
 __global__ __launch_bounds__(64) void k_sc_ring_prepare(const double* __restrict__ ext_desc, double* __restrict__ ext_sector, float* __restrict__ ext_ring)
 {
-    const int i = blockIdx.x, t = threadIdx.x;
-    const double* __restrict__ q = ext_desc + (size_t)i * ND;
-    if (t < NR) ext_ring[(size_t)i * NR + t] = (float)sc_ring_key([&](int k) { return q[t * NS + k]; });
-    if (t < NS) ext_sector[(size_t)i * NS + t] = sc_sector_key([&](int r) { return q[r * NS + t]; });
+    const int i = blockIdx.x;
+    sc_ext_keys(ext_desc + (size_t)i * ND, threadIdx.x, ext_sector + (size_t)i * NS, ext_ring + (size_t)i * NR);
 }
 
 // buf[0, held): distinct words in any order -> buf[0, min(held, n_cand)): the smallest, ascending.  Every lane counts, for each
@@ -139,21 +133,9 @@ __global__ __launch_bounds__(kSelThreads) void k_sc_ring_select(const float* __r
     }
 }
 
-// LDS of the full alignment: the three candidates, their column norms, one chunk of similarities
-struct alignas(16) ScRingFull {
-    double c[NC][ND];
-    double cnorm[NC][NS];
-    double sim[NC][kFullChunk][NS];
-    unsigned char eff[NC][kFullChunk][NS];
-    double dist[NC][kFullChunk];
-    double dist_out[NC];
-    int    shift_out[NC];
-};
-
 // Stage two: workgroup (x, i) compares query i with R_i[3x .. 3x + 3).  Sector-key alignment is sc_distance_block, the
-// detector's own call.  Full alignment: min over s = 0 .. 59 ascending of distDirectSC(query, circshift(cand, s)), strict, from
-// 10000000 / shift 0; thread (g, j) holds column j of the query and its norm in registers, a column's norm is taken once per
-// descriptor, every dot product and every sector sum is one thread's, left to right.
+// detector's own call; full alignment is sc_full_block, the single query's: thread (g, j) holds column j of the query and its norm
+// in registers as there.
 template <int ALIGN>
 __global__ __launch_bounds__(kScThreads) void k_sc_ring_dist(const double* __restrict__ store_desc, const double* __restrict__ store_sector,
                                                              const int32_t* __restrict__ keys, const double* __restrict__ ext_desc,
@@ -171,44 +153,12 @@ __global__ __launch_bounds__(kScThreads) void k_sc_ring_dist(const double* __res
     const double* __restrict__ q = keys ? store_desc + (size_t)keys[i] * ND : ext_desc + (size_t)i * ND;
     const size_t e = (size_t)i * n_cand + j0;
     if constexpr (ALIGN == S2M_SC_ALIGN_FULL) {
-        __shared__ ScRingFull m;
-        const int g = t / NS, j = t - g * NS;
+        __shared__ ScFullShared<NC> m;
+        const int j = t % NS;
         double qcol[NR];
 #pragma unroll
         for (int r = 0; r < NR; r++) qcol[r] = q[r * NS + j];
-        const double n1 = sc_col_norm([&](int r) { return qcol[r]; });
-        for (int task = t; task < NC * (ND / 2); task += kScThreads) {
-            const int c = task / (ND / 2), k = task - c * (ND / 2);
-            reinterpret_cast<double2*>(m.c[c])[k] = reinterpret_cast<const double2*>(store_desc + (size_t)s_cand[c] * ND)[k];   // (slots are 9600 bytes: 16-byte aligned)
-        }
-        if (t < NC) { m.dist_out[t] = 10000000; m.shift_out[t] = 0; }
-        __syncthreads();
-        for (int task = t; task < NC * NS; task += kScThreads) {
-            const int c = task / NS, jc = task - c * NS;
-            m.cnorm[c][jc] = sc_col_norm([&](int r) { return m.c[c][r * NS + jc]; });
-        }
-        __syncthreads();
-        for (int s0 = 0; s0 < NS; s0 += kFullChunk) {
-            if (g < kFullLanes) {
-                for (int k = g; k < kFullChunk; k += kFullLanes) {
-                    int j2 = j - (s0 + k); j2 += (j2 < 0) ? NS : 0;        // circshift (:39-59)
-#pragma unroll
-                    for (int c = 0; c < NC; c++) {
-                        const double dot = sc_col_dot([&](int r) { return qcol[r]; }, [&](int r) { return m.c[c][r * NS + j2]; });
-                        m.eff[c][k][j] = sc_sector_sim(dot, n1, m.cnorm[c][j2], &m.sim[c][k][j]) ? 1 : 0;
-                    }
-                }
-            }
-            __syncthreads();
-            if (t < NC * kFullChunk) {
-                const int c = t / kFullChunk, k = t - c * kFullChunk;
-                m.dist[c][k] = sc_sector_sum_dist([&](int jj) { return m.eff[c][k][jj] != 0; }, [&](int jj) { return m.sim[c][k][jj]; });
-            }
-            __syncthreads();
-            if (t < NC)
-                for (int k = 0; k < kFullChunk; k++) sc_min_update(m.dist[t][k], s0 + k, &m.dist_out[t], &m.shift_out[t]);
-            // (the next chunk writes sim / eff only; dist is written again behind its barrier)
-        }
+        sc_full_block<NC>(store_desc, qcol, sc_col_norm([&](int r) { return qcol[r]; }), s_cand, m);
         if (t < nc) { dist[e + t] = m.dist_out[t]; shift[e + t] = m.shift_out[t]; }
     } else {
         __shared__ ScShared sh[NC];
@@ -248,18 +198,9 @@ __global__ __launch_bounds__(kScThreads) void k_sc_ring_rank(int m, int n_cand, 
 #pragma unroll
         for (int u = 0; u < U; u++)
             if (sc_hit_less(rd[u], rk[u], bd, bk)) { bd = rd[u]; bk = rk[u]; bs = rs[u]; }
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) {
-            const double od = __shfl_xor(bd, off, 64);
-            const int ok = __shfl_xor(bk, off, 64), os = __shfl_xor(bs, off, 64);
-            if (sc_hit_less(od, ok, bd, bk)) { bd = od; bk = ok; bs = os; }
-        }
+        sc_hit_wave_min(bd, bk, bs);
         if (bk == INT_MAX) break;                         // no hit is left (the same for all lanes)
-        if (lane == 0) {
-            s2m_sc_hit hit;
-            hit.dist = bd; hit.key = bk; hit.shift = bs; hit.yaw_diff_rad = sc_shift_to_yaw(bs); hit.reserved = 0;
-            out_hits[(size_t)qi * top_k + round] = hit;
-        }
+        if (lane == 0) out_hits[(size_t)qi * top_k + round] = sc_hit_record(bd, bk, bs);
         n_hits = round + 1;
 #pragma unroll
         for (int u = 0; u < U; u++)

@@ -730,7 +730,7 @@ public:
         std::vector<s2m_sc_hit> hits(keys.size() * (size_t)(p.q.top_k > 0 ? p.q.top_k : 0));
         std::vector<int32_t> n(keys.size(), 0);
         check(s2m_sc_query_keys(h_, keys.data(), (int32_t)keys.size(), &p, hits.data(), n.data()), "s2m_sc_query_keys");
-        return scRows(hits, n, p.q.top_k);
+        return split_rows(hits, n, p.q.top_k);
     }
     // descs: m x 1200 doubles, row-major as s2m_sc_add_descriptor takes them
     std::vector<std::vector<s2m_sc_hit>> scQueryDescriptors(const std::vector<double>& descs, const s2m_sc_query_many_params& p)
@@ -739,7 +739,7 @@ public:
         std::vector<s2m_sc_hit> hits(m * (size_t)(p.q.top_k > 0 ? p.q.top_k : 0));
         std::vector<int32_t> n(m, 0);
         check(s2m_sc_query_descriptors(h_, descs.data(), (int32_t)m, &p, hits.data(), n.data()), "s2m_sc_query_descriptors");
-        return scRows(hits, n, p.q.top_k);
+        return split_rows(hits, n, p.q.top_k);
     }
     // The place query behind a ring-key prefilter (s2m_sc_query_keys_ring / s2m_sc_ring_neighbours_keys):
     // scQueryKeys with every query's searched set cut to its p.n_candidates ring-key neighbours; and those neighbours themselves.
@@ -748,7 +748,7 @@ public:
         std::vector<s2m_sc_hit> hits(keys.size() * (size_t)(p.m.q.top_k > 0 ? p.m.q.top_k : 0));
         std::vector<int32_t> n(keys.size(), 0);
         check(s2m_sc_query_keys_ring(h_, keys.data(), (int32_t)keys.size(), &p, hits.data(), n.data()), "s2m_sc_query_keys_ring");
-        return scRows(hits, n, p.m.q.top_k);
+        return split_rows(hits, n, p.m.q.top_k);
     }
     std::vector<std::vector<s2m_sc_hit>> scQueryDescriptorsRing(const std::vector<double>& descs, const s2m_sc_ring_params& p)
     {
@@ -756,7 +756,7 @@ public:
         std::vector<s2m_sc_hit> hits(m * (size_t)(p.m.q.top_k > 0 ? p.m.q.top_k : 0));
         std::vector<int32_t> n(m, 0);
         check(s2m_sc_query_descriptors_ring(h_, descs.data(), (int32_t)m, &p, hits.data(), n.data()), "s2m_sc_query_descriptors_ring");
-        return scRows(hits, n, p.m.q.top_k);
+        return split_rows(hits, n, p.m.q.top_k);
     }
     std::vector<std::vector<s2m_sc_ring_neighbour>> scRingNeighboursKeys(const std::vector<int32_t>& keys, const s2m_sc_ring_params& p)
     {
@@ -764,9 +764,7 @@ public:
         std::vector<s2m_sc_ring_neighbour> nb(keys.size() * c);
         std::vector<int32_t> n(keys.size(), 0);
         check(s2m_sc_ring_neighbours_keys(h_, keys.data(), (int32_t)keys.size(), &p, nb.data(), n.data()), "s2m_sc_ring_neighbours_keys");
-        std::vector<std::vector<s2m_sc_ring_neighbour>> rows(keys.size());
-        for (size_t i = 0; i < rows.size(); i++) rows[i].assign(nb.begin() + i * c, nb.begin() + i * c + n[i]);
-        return rows;
+        return split_rows(nb, n, c);
     }
     // the stored descriptors first .. first+count-1, bit for bit what was added
     std::vector<double> scGetDescriptors(int32_t first, int32_t count)
@@ -862,10 +860,12 @@ public:
     s2m_handle handle() const { return h_; }
 
 private:
-    static std::vector<std::vector<s2m_sc_hit>> scRows(const std::vector<s2m_sc_hit>& hits, const std::vector<int32_t>& n, int top_k)
+    // row i: the first counts[i] of the `width` records the flat block holds for it
+    template <typename T>
+    static std::vector<std::vector<T>> split_rows(const std::vector<T>& flat, const std::vector<int32_t>& counts, size_t width)
     {
-        std::vector<std::vector<s2m_sc_hit>> rows(n.size());
-        for (size_t i = 0; i < n.size(); i++) rows[i].assign(hits.begin() + i * (size_t)top_k, hits.begin() + i * (size_t)top_k + n[i]);
+        std::vector<std::vector<T>> rows(counts.size());
+        for (size_t i = 0; i < counts.size(); i++) rows[i].assign(flat.begin() + i * width, flat.begin() + i * width + counts[i]);
         return rows;
     }
     bool accepted()

@@ -1142,28 +1142,38 @@ class MapOptimizationS2M:
         return self._sc_query(self.lib.s2m_sc_query_projected, "s2m_sc_query_projected", (), params, kw)
 
     # -- the place query for many queries at once
-    def _sc_query_many(self, fn, what, arg, m, params, kw):
-        p = params if params is not None else default_sc_query_many_params()
+    @staticmethod
+    def _sc_queries(queries, descs: bool):
+        """The queries of a many-query call - stored keys, or (m, 20, 60) descriptors - as a contiguous array and its pointer."""
+        a = np.ascontiguousarray(queries, np.float64).reshape(-1, 20, 60) if descs else np.ascontiguousarray(queries, np.int32).reshape(-1)
+        return a, a.ctypes.data_as(C.POINTER(C.c_double if descs else C.c_int32))
+
+    def _sc_query_rows(self, what, queries, descs, params, kw, defaults_fn, fields_fn, width_fn, rec_dtype, rec_ctype):
+        """One row of at most width_fn(parameters) records per query from the library call `what`."""
+        p = params if params is not None else defaults_fn()
         if kw:
-            p = default_sc_query_many_params(**{**_sc_many_fields(p), **kw})
-        k = max(int(p.q.top_k), 1)
-        hits = np.zeros((max(m, 1), k), SC_HIT_DTYPE)
+            p = defaults_fn(**{**fields_fn(p), **kw})
+        a, ptr = self._sc_queries(queries, descs)
+        m = len(a)
+        rows = np.zeros((max(m, 1), max(int(width_fn(p)), 1)), rec_dtype)
         n = np.zeros(max(m, 1), np.int32)
-        self._check(fn(self.h, arg, m, C.byref(p), hits.ctypes.data_as(C.POINTER(ScHit)), n.ctypes.data_as(C.POINTER(C.c_int32))), what)
-        return [hits[i, :n[i]].copy() for i in range(m)]
+        self._check(getattr(self.lib, what)(self.h, ptr, m, C.byref(p), rows.ctypes.data_as(C.POINTER(rec_ctype)),
+                                            n.ctypes.data_as(C.POINTER(C.c_int32))), what)
+        return [rows[i, :n[i]].copy() for i in range(m)]
+
+    def _sc_query_many(self, what, queries, descs, params, kw):
+        return self._sc_query_rows(what, queries, descs, params, kw, default_sc_query_many_params, _sc_many_fields, lambda p: p.q.top_k,
+                                   SC_HIT_DTYPE, ScHit)
 
     def scQueryKeys(self, keys, params: "ScQueryManyParams | None" = None, **kw):
         """s2m_sc_query_keys: for every stored key of `keys` its hits (SC_HIT_DTYPE records, ascending (dist, key)), each row what
         scQueryKey returns for the same searched set.  Keyword arguments set fields of the single query's parameters, and
         rel_lo / rel_hi the window around each query's own key that is left out as well."""
-        k = np.ascontiguousarray(keys, np.int32).reshape(-1)
-        return self._sc_query_many(self.lib.s2m_sc_query_keys, "s2m_sc_query_keys", k.ctypes.data_as(C.POINTER(C.c_int32)), len(k), params, kw)
+        return self._sc_query_many("s2m_sc_query_keys", keys, False, params, kw)
 
     def scQueryDescriptors(self, descs, params: "ScQueryManyParams | None" = None, **kw):
         """s2m_sc_query_descriptors: the same for descriptors from elsewhere, (m, 20, 60) doubles."""
-        d = np.ascontiguousarray(descs, np.float64).reshape(-1, 20, 60)
-        return self._sc_query_many(self.lib.s2m_sc_query_descriptors, "s2m_sc_query_descriptors", d.ctypes.data_as(C.POINTER(C.c_double)), len(d),
-                                   params, kw)
+        return self._sc_query_many("s2m_sc_query_descriptors", descs, True, params, kw)
 
     def scGetDescriptors(self, first: int = 0, count: "int | None" = None):
         """s2m_sc_get_descriptors: the stored descriptors first .. first+count-1 as (count, 20, 60) doubles, bit for bit what was added."""
@@ -1190,40 +1200,27 @@ class MapOptimizationS2M:
         return [(cur, int(h["key"]), float(h["dist"]), float(h["yaw_diff_rad"])) for cur, row in enumerate(rows) for h in row]
 
     # -- the place query behind a ring-key prefilter
-    def _sc_ring(self, fn, what, arg, m, params, kw, both):
-        p = params if params is not None else default_sc_ring_params()
-        if kw:
-            p = default_sc_ring_params(**{**_sc_ring_fields(p), **kw})
-        width = max(int(p.m.q.top_k), 1) if both else max(int(p.n_candidates), 1)
-        rows = np.zeros((max(m, 1), width), SC_HIT_DTYPE if both else SC_RING_NEIGHBOUR_DTYPE)
-        n = np.zeros(max(m, 1), np.int32)
-        self._check(fn(self.h, arg, m, C.byref(p), rows.ctypes.data_as(C.POINTER(ScHit if both else ScRingNeighbour)),
-                       n.ctypes.data_as(C.POINTER(C.c_int32))), what)
-        return [rows[i, :n[i]].copy() for i in range(m)]
+    def _sc_ring(self, what, queries, descs, params, kw, both):
+        """both: the rows of hits behind the prefilter; else the neighbour lists."""
+        shape = (lambda p: p.m.q.top_k, SC_HIT_DTYPE, ScHit) if both else (lambda p: p.n_candidates, SC_RING_NEIGHBOUR_DTYPE, ScRingNeighbour)
+        return self._sc_query_rows(what, queries, descs, params, kw, default_sc_ring_params, _sc_ring_fields, *shape)
 
     def scRingNeighboursKeys(self, keys, params: "ScRingParams | None" = None, **kw):
         """s2m_sc_ring_neighbours_keys: for every stored key of `keys` its n_candidates ring-key neighbours in its searched set
         (SC_RING_NEIGHBOUR_DTYPE records, ascending (d2, key)).  Keyword arguments set n_candidates and the many-query's fields."""
-        k = np.ascontiguousarray(keys, np.int32).reshape(-1)
-        return self._sc_ring(self.lib.s2m_sc_ring_neighbours_keys, "s2m_sc_ring_neighbours_keys", k.ctypes.data_as(C.POINTER(C.c_int32)), len(k),
-                             params, kw, False)
+        return self._sc_ring("s2m_sc_ring_neighbours_keys", keys, False, params, kw, False)
 
     def scRingNeighboursDescriptors(self, descs, params: "ScRingParams | None" = None, **kw):
         """s2m_sc_ring_neighbours_descriptors: the same for descriptors from elsewhere, (m, 20, 60) doubles."""
-        d = np.ascontiguousarray(descs, np.float64).reshape(-1, 20, 60)
-        return self._sc_ring(self.lib.s2m_sc_ring_neighbours_descriptors, "s2m_sc_ring_neighbours_descriptors",
-                             d.ctypes.data_as(C.POINTER(C.c_double)), len(d), params, kw, False)
+        return self._sc_ring("s2m_sc_ring_neighbours_descriptors", descs, True, params, kw, False)
 
     def scQueryKeysRing(self, keys, params: "ScRingParams | None" = None, **kw):
         """s2m_sc_query_keys_ring: scQueryKeys with every query's searched set cut to its n_candidates ring-key neighbours."""
-        k = np.ascontiguousarray(keys, np.int32).reshape(-1)
-        return self._sc_ring(self.lib.s2m_sc_query_keys_ring, "s2m_sc_query_keys_ring", k.ctypes.data_as(C.POINTER(C.c_int32)), len(k), params, kw, True)
+        return self._sc_ring("s2m_sc_query_keys_ring", keys, False, params, kw, True)
 
     def scQueryDescriptorsRing(self, descs, params: "ScRingParams | None" = None, **kw):
         """s2m_sc_query_descriptors_ring: the same for descriptors from elsewhere, (m, 20, 60) doubles."""
-        d = np.ascontiguousarray(descs, np.float64).reshape(-1, 20, 60)
-        return self._sc_ring(self.lib.s2m_sc_query_descriptors_ring, "s2m_sc_query_descriptors_ring", d.ctypes.data_as(C.POINTER(C.c_double)), len(d),
-                             params, kw, True)
+        return self._sc_ring("s2m_sc_query_descriptors_ring", descs, True, params, kw, True)
 
     def scRingPass(self, queries_per_pass: int):
         """s2m_debug_sc_ring_pass: at most this many queries per pass of the ring calls (0: the default)."""

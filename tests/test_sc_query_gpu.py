@@ -2,6 +2,7 @@
 (tests/ref/sc_query_ref.py, on the oracle).  The bar everywhere: keys and shifts equal, dist equal as uint64, yaw_diff_rad
 equal as uint32 (Q.same_hits).  No tolerance is involved."""
 import ctypes as C
+import functools
 import os
 import sys
 
@@ -28,6 +29,7 @@ def gpu():
 
 
 def fill(g, descs):
+    g.sc_query_store = None
     g.scReset()
     for d in descs:
         g.scAddDescriptor(d)
@@ -164,9 +166,10 @@ def test_ties_and_empty_descriptors(gpu):
         assert len(gpu.scQueryDescriptor(np.zeros((20, 60)), top_k=32, align=align, max_dist=BIG)) == 0
 
 
-def test_more_than_one_pass_of_the_grid(gpu):
-    """3 x kScQueryMaxGroups + 28 keys: the workgroups walk a second pass, the last one with a tail of one key.  Revisits of
-    the query at keys 5, 3071, 3072, 3099 and exact copies at 1000 and 3090."""
+@functools.lru_cache(maxsize=None)
+def store_3100():
+    """(descs, place): 3 x kScQueryMaxGroups + 28 descriptors with revisits of `place` at keys 5, 3071, 3072, 3099 and exact copies
+    at 1000 and 3090."""
     n = 3 * s2m.SC_QUERY_MAX_GROUPS + 28
     assert n == 3100
     descs = make_descriptors(n, seed=31)
@@ -175,7 +178,22 @@ def test_more_than_one_pass_of_the_grid(gpu):
         descs[k] = revisit(place, 7 * i + 3, 0.04, 40 + i)
     descs[1000] = place.copy()
     descs[3090] = place.copy()
-    fill(gpu, descs)
+    return descs, place
+
+
+def fill_3100(g):
+    """The store holds store_3100(); one that is there already is kept (the queries leave the store alone)."""
+    descs, place = store_3100()
+    if getattr(g, "sc_query_store", None) != 3100:
+        fill(g, descs)
+    g.sc_query_store = 3100
+    return descs, place
+
+
+def test_more_than_one_pass_of_the_grid(gpu):
+    """3 x kScQueryMaxGroups + 28 keys: the workgroups walk a second pass, the last one with a tail of one key.  Revisits of
+    the query at keys 5, 3071, 3072, 3099 and exact copies at 1000 and 3090."""
+    descs, place = fill_3100(gpu)
     want = Q.query(descs, place, top_k=8, align=SK)
     assert sorted(want["key"].tolist()) == [5, 1000, 3071, 3072, 3090, 3099] and want["key"][:2].tolist() == [1000, 3090]
     check(gpu.scQueryDescriptor(place, top_k=8, align=SK), want, "3100 keys")
@@ -186,6 +204,26 @@ def test_more_than_one_pass_of_the_grid(gpu):
     want = Q.query(descs, place, top_k=8, align=FULL, max_dist=BIG, **sub)
     assert want["key"][0] == 3090 and set(want["key"][:4].tolist()) == {3071, 3072, 3090, 3099}
     check(gpu.scQueryDescriptor(place, top_k=8, align=FULL, max_dist=BIG, **sub), want, "600 keys, full")
+
+
+# the model's top 8 of store_3100()'s place at full alignment over the whole store and any threshold: the six planted keys (distance
+# below 1e-4) and the two nearest random descriptors (0.4268, 0.4337; the next is 0.4388), from one run of
+# Q.rank(Q.all_distances(descs, place, FULL), range(3100), 8, BIG) on the CPU
+TOP8_FULL_3100 = [5, 1000, 1584, 3069, 3071, 3072, 3090, 3099]
+
+
+def test_full_alignment_on_a_second_pass_of_the_grid(gpu):
+    """Full alignment over all 3100 keys: 1024 workgroups, of which the first ten compare a second triple (the last a tail of one
+    key) in the LDS the first one used.  The single query's row is the many-query's row for the same set as bytes - another
+    kernel - and the model's over its top 8."""
+    descs, place = fill_3100(gpu)
+    kw = dict(top_k=8, align=FULL, max_dist=BIG)
+    want = Q.rank(Q.all_distances(descs, place, FULL, TOP8_FULL_3100), TOP8_FULL_3100, 8, BIG)
+    assert want["key"][:2].tolist() == [1000, 3090] and sorted(want["key"].tolist()) == TOP8_FULL_3100
+    many = gpu.scQueryKeys([1000], **kw)[0]
+    for what, got in (("stored query", gpu.scQueryKey(1000, **kw)), ("descriptor", gpu.scQueryDescriptor(place, **kw))):
+        assert got.tobytes() == many.tobytes(), (what, got, many)
+        check(got, want, what)
 
 
 def test_ring_key_case_on_the_device(gpu):

@@ -225,6 +225,25 @@ def test_rows_equal_the_model(gpu, align):
     assert [len(r) for r in gpu.scRingNeighboursKeys(keys, n_candidates=10, first=5, count=2)] == [2] * len(keys)
 
 
+def test_full_alignment_on_short_rows(gpu):
+    """n_candidates = 10 and windows that leave |R_i| = 1, 2, 4, 5: the last triple of a row holds one or two candidates, and a
+    row ends exactly on a triple plus one.  Each row is s2m_sc_query_keys' / _descriptors' row for the same window as bytes, and
+    the model's."""
+    descs = small_store()
+    keys32 = R.ring_keys(descs)
+    fill(gpu, descs, "small")
+    keys = [47, 6, 3, 31, 40]
+    ext = [revisit(descs[20], 11, 0.05, 3)]
+    for count in (1, 2, 4, 5):
+        kw = dict(top_k=5, align=FULL, max_dist=BIG, first=5, count=count)
+        for what, got, exhaustive, want in (
+                ("keys", gpu.scQueryKeysRing(keys, n_candidates=10, **kw), gpu.scQueryKeys(keys, **kw), R.query_many_ring(descs, keys, 10, keys32=keys32, **kw)),
+                ("ext", gpu.scQueryDescriptorsRing(ext, n_candidates=10, **kw), gpu.scQueryDescriptors(ext, **kw), R.query_many_ring(descs, ext, 10, keys32=keys32, **kw))):
+            assert [len(r) for r in got] == [count] * len(got), (what, count)
+            assert [r.tobytes() for r in got] == [r.tobytes() for r in exhaustive], (what, count, got, exhaustive)
+            check_rows(got, want, (what, count))
+
+
 # ---- equality with the calls that exist ----------------------------------------------------------------------------------------
 
 @pytest.mark.parametrize("align", [SK, FULL])
