@@ -161,7 +161,8 @@ int  s2m_optimize_collect(s2m_handle h, float pose[6], const s2m_imu_init* imu,
  * launch of the loop carries one grid row per scan, so that while one scan's workgroups wait on a dependent load the others'
  * points are processed.
  * Results are those of n_scans separate s2m_optimize calls, bit for bit.
- *   scans[b], sizes[b]    laserCloudSurfLastDS of scan b (host records, stride_bytes as everywhere)
+ * In every function of this group n_scans is 1 to 64 and slot is 0 to 63: anything else is S2M_ERR_INVALID_ARG with nothing changed.
+ *   scans[b], sizes[b]   laserCloudSurfLastDS of scan b (host records, stride_bytes as everywhere)
  *   poses[6*b .. 6*b+5]   in: initial guess of scan b, out: its transformTobeMapped
  *   imu                   NULL, or n_scans entries;  out: NULL, or n_scans entries */
 int  s2m_optimize_batch(s2m_handle h, int n_scans, const void* const* scans, const size_t* sizes, size_t stride_bytes,

@@ -321,6 +321,34 @@ int  s2m_debug_loop_verify_many_pass(s2m_handle h, int32_t pairs_per_pass);
 int  s2m_debug_loop_verify_many_last(s2m_handle h, int32_t* passes, int32_t* pairs_aligned, size_t* bytes);
 int  s2m_debug_loop_verify_many_plan(const int32_t* n_cand, int32_t m, int32_t pairs_per_pass, int32_t* first_row_of_pass, int32_t* n_pass);
 
+/* ---- what a batch issued (s2m_batch_set_scans, s2m_optimize_batch_launch / _collect, s2m_optimize_batch) ----
+ * Host only, no kernel and no device memory: every number is noted where the library issues the launch or takes the decision,
+ * none is worked out from n_scans afterwards. It proves which path a batch took; the results are held to their bits elsewhere.
+ *   n_scans, n_live: the last batch launch's slots, and those of them that ran a loop (the others were skipped, :1297 / :1300).
+ *   ctx_launches, init_launches: launches of k_set_ctxs (the slots whose DevCtx block had changed, 8 a launch) and of
+ *     k_init_states (the live slots, 12 a launch) by that batch launch.
+ *   prep_launches: scan-ordering tables (16 slots each) the s2m_batch_set_scans before that batch launch issued; a table of
+ *     empty scans only is not issued. s2m_batch_set_scan / s2m_slot_set_scan do not count here.
+ *   ranges_issued: graph launches of the batch, 0 (no live slot), 1, or 2 (early exit on and some slot not done after the
+ *     first range; known once the batch is collected).
+ *   graph_cached: 1 if every one of them was a graph captured by an earlier batch, 0 if one was captured now (or none issued).
+ *   n_loops, loop[]: the lockstep loops of the graph, one per workgroup shape in use (the first two are reported): waves per
+ *     workgroup, grid rows (slots), grid columns (workgroups), fused = 1 if the iterations close inside the registration kernel
+ *     and 0 if k_finalize closes them, and first_split: the first launch, over the ranges issued, that ran the certify and
+ *     the search kernel instead of the fused one (-1: none).
+ * S2M_ERR_INVALID_ARG for a null argument. Before the first batch launch everything is 0 (first_split -1). */
+typedef struct s2m_debug_batch_loop {
+    int32_t wpb, nslots, nblocks, fused, first_split;
+} s2m_debug_batch_loop;
+typedef struct s2m_debug_batch_last_out {
+    int32_t n_scans, n_live;
+    int32_t ctx_launches, init_launches, prep_launches;
+    int32_t ranges_issued, graph_cached;
+    int32_t n_loops;
+    s2m_debug_batch_loop loop[2];
+} s2m_debug_batch_last_out;
+int  s2m_debug_batch_last(s2m_handle h, s2m_debug_batch_last_out* out);
+
 #ifdef __cplusplus
 }
 #endif

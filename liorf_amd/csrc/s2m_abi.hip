@@ -111,16 +111,18 @@ void s2m::host::launch_chunk_table(hipStream_t stream, const PrepTable& t, int n
     hipLaunchKernelGGL(k_chunk_table, dim3(1, nslots), dim3(1024), 0, stream, t);
 }
 
-void s2m::host::launch_set_ctxs(hipStream_t stream, CtxTable& t, int n)
+void s2m::host::launch_set_ctxs(hipStream_t stream, CtxTable& t, int n, int* issued)
 {
     for (int j = n; j < kCtxSlots; j++) t.dst[j] = nullptr;
     hipLaunchKernelGGL(k_set_ctxs, dim3(n), dim3(64), 0, stream, t);
+    if (issued) ++*issued;
 }
 
-void s2m::host::launch_init_states(hipStream_t stream, StateInitTable& t, int n)
+void s2m::host::launch_init_states(hipStream_t stream, StateInitTable& t, int n, int* issued)
 {
     for (int j = n; j < kInitSlots; j++) t.s[j].dst = nullptr;
     hipLaunchKernelGGL(k_init_states, dim3(n), dim3(256), 0, stream, t);
+    if (issued) ++*issued;
 }
 
 // The LM loop (:1304-1315) as a launch sequence.  One iteration L is either one launch of the fused kernel R(L), or -
@@ -206,6 +208,7 @@ void s2m::host::launch_iteration(s2m_context* h, const LoopShape& sh, int L, int
     if (L == 0) { launch_search(h, sh, 0, true); return; }
     launch_certify(h, sh, L, solve_prev, fused_loop);
     launch_search(h, sh, L, false, sh.late);
+    if (h->reg.last_loop.first_split < 0) h->reg.last_loop.first_split = L;
 }
 
 // ends_range: the last launch of the range (it hands the record over, see LoopShape::out)
@@ -245,6 +248,7 @@ void s2m::host::enqueue_loop(s2m_context* h, const LoopShape& sh_in, hipEvent_t*
     if (L1 < 0) L1 = n;
     const bool fuse = h->tune.fuse_solve && sh_in.nblocks * sh_in.nslots <= h->tune.fuse_max_blocks;     // the whole grid co-resident (see above)
     LoopShape sh = sh_in;
+    h->reg.last_loop = LoopIssued{ sh.wpb, sh.nslots, sh.nblocks, fuse ? 1 : 0, -1 };       // (launch_iteration notes the first certify + search)
     // S2M_SPLIT=2: from launch `split_from` on (the first launches search most points: there the certify kernel is only one
     // more launch in front of the search) the iterations of a loop closed by k_finalize run certify (lean) + search
     const bool split_late = sh.split_auto && !fuse && sh.wpb == kBlock / 64 && h->tune.lean_certify;   // (with early exit on these launches are the second range: issued only for scans that need them)
@@ -515,7 +519,7 @@ int s2m_destroy(s2m_handle h)
     for (s2m_context* k : h->batch.kids) (void)s2m_destroy(k);
     h->batch.kids.clear();
     if (h->batch.state_borrowed) { h->reg.state.forget(); h->reg.h_state = nullptr; }    // (the parent's blocks)
-    for (auto& kv : h->batch.graphs) (void)hipGraphExecDestroy(kv.second);
+    for (auto& kv : h->batch.graphs) (void)hipGraphExecDestroy(kv.second.exec);
     for (auto& kv : h->reg.graphs) (void)hipGraphExecDestroy(kv.second);
     for (const std::vector<hipEvent_t>* evs : { &h->batch.branch_events, &h->batch.prep_events, &h->reg.iter_events })
         for (hipEvent_t e : *evs) (void)hipEventDestroy(e);
@@ -558,7 +562,7 @@ int s2m_set_params(s2m_handle h, const s2m_params* p)
         S2M_HIP(h, hipStreamSynchronize(h->stream));
         for (auto& kv : h->reg.graphs) (void)hipGraphExecDestroy(kv.second);
         h->reg.graphs.clear();
-        for (auto& kv : h->batch.graphs) (void)hipGraphExecDestroy(kv.second);     // (every branch of a batch graph is such a loop)
+        for (auto& kv : h->batch.graphs) (void)hipGraphExecDestroy(kv.second.exec);     // (every branch of a batch graph is such a loop)
         h->batch.graphs.clear();
     }
     h->prm = *p;

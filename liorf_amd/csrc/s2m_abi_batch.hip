@@ -112,14 +112,16 @@ int ensure_kids(s2m_context* h, int n)
 // of the loop has one grid row per slot (slots of different workgroup shape form groups, one loop per group on a branch of its
 // own).  Otherwise (S2M_LOCKSTEP=0, A/B measurements): a fork, one branch per scan with that scan's loop, a join.
 // part 0: the whole loop; 1: launches 0 .. seg-1; 2: launches seg .. max_iter-1 (as a single scan's graph)
-int get_batch_graph(s2m_context* h, int part, hipGraphExec_t* out)
+int get_batch_graph(s2m_context* h, int part, const s2m_context::Batch::Graph** out)
 {
     const std::vector<int>& live = h->batch.live;
     std::vector<int> key;
     key.push_back(part); key.push_back(part ? h->tune.seg_iters : 0);
     for (int b : live) { key.push_back(b); key.push_back(h->batch.kids[(size_t)b]->hctx.table_cap); key.push_back(h->batch.kids[(size_t)b]->hctx.wpb); }
     auto it = h->batch.graphs.find(key);
-    if (it != h->batch.graphs.end()) { *out = it->second; return S2M_OK; }
+    if (it != h->batch.graphs.end()) { h->batch.last.graph_hits++; *out = &it->second; return S2M_OK; }
+    h->batch.last.graph_captures++;
+    std::vector<LoopIssued> issued;
     hipGraph_t graph = nullptr;
     hipGraphExec_t exec = nullptr;
     // the loops to run: (shape, stream to run it on)
@@ -152,6 +154,7 @@ int get_batch_graph(s2m_context* h, int part, hipGraphExec_t* out)
         {
             OnStream on(h, br);                               // (enqueue_loop launches on the handle's stream; settings are the parent's)
             enqueue_loop(h, loops[j], nullptr, false, part == 2 ? h->tune.seg_iters : 0, part == 1 ? h->tune.seg_iters : -1);
+            issued.push_back(h->reg.last_loop);
         }
         ok = ok && hipEventRecord(h->batch.branch_events[j], br) == hipSuccess;
         ok = ok && hipStreamWaitEvent(h->stream, h->batch.branch_events[j], 0) == hipSuccess;
@@ -161,8 +164,9 @@ int get_batch_graph(s2m_context* h, int part, hipGraphExec_t* out)
     e = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
     (void)hipGraphDestroy(graph);
     if (e != hipSuccess) return fail(h, S2M_ERR_HIP, "batch: hipGraphInstantiate", e);
-    h->batch.graphs[key] = exec;
-    *out = exec;
+    s2m_context::Batch::Graph& g = h->batch.graphs[key];
+    g.exec = exec; g.loops = std::move(issued);
+    *out = &g;
     return S2M_OK;
 }
 
@@ -170,10 +174,19 @@ int get_batch_graph(s2m_context* h, int part, hipGraphExec_t* out)
 // copy (the slots' blocks are contiguous)
 int launch_batch_graph(s2m_context* h, int part)
 {
-    hipGraphExec_t exec = nullptr;
-    const int rc = get_batch_graph(h, part, &exec);
+    const s2m_context::Batch::Graph* g = nullptr;
+    const int rc = get_batch_graph(h, part, &g);
     if (rc) return rc;
-    S2M_HIP(h, hipGraphLaunch(exec, h->stream));
+    S2M_HIP(h, hipGraphLaunch(g->exec, h->stream));
+    // (s2m_debug_batch_last: the loops of this range as enqueue_loop noted them; a second range adds its certify + search launch)
+    s2m_context::Batch::Last& last = h->batch.last;
+    last.n_loops = (int)g->loops.size();
+    for (size_t j = 0; j < g->loops.size() && j < 2; j++) {
+        const int split_before = last.ranges_issued ? last.loop[j].first_split : -1;
+        last.loop[j] = g->loops[j];
+        if (split_before >= 0) last.loop[j].first_split = split_before;
+    }
+    last.ranges_issued++;
     return S2M_OK;
 }
 int fetch_slot_states(s2m_context* h)
@@ -223,6 +236,7 @@ int s2m_batch_set_scans(s2m_handle h, int n_scans, const void* const* scans, con
         S2M_HIP(h, hipStreamWaitEvent(h->stream, h->batch.prep_events[(size_t)b], 0));
         h->batch.prep_pending[(size_t)b] = 0;
     }
+    h->batch.last.prep_launches = 0;
     for (int b0 = 0; b0 < n_scans; b0 += kPrepSlots) {
         PrepTable t;
         const int nb = std::min(kPrepSlots, n_scans - b0);
@@ -238,7 +252,7 @@ int s2m_batch_set_scans(s2m_handle h, int n_scans, const void* const* scans, con
             }
             k->reg.t_set_scan_ms = 0; k->reg.scan_timing_pending = false;
         }
-        launch_scan_prep(h->stream, t, nb);
+        launch_scan_prep(h->stream, t, nb, false, &h->batch.last.prep_launches);
         S2M_HIP(h, hipGetLastError());
     }
     if (!on_device) S2M_HIP(h, hipStreamSynchronize(h->stream));       // the callers' buffers are free again
@@ -295,11 +309,16 @@ int s2m_optimize_batch_launch(s2m_handle h, int n_scans, const float* poses)
     PendingGuard undo(h, n_scans);
     std::vector<int>& live = h->batch.live;
     h->batch.pend_n = n_scans;
+    s2m_context::Batch::Last& last = h->batch.last;
+    const int prep_launches = last.prep_launches;          // (of the s2m_batch_set_scans before this launch)
+    last = s2m_context::Batch::Last();
+    last.prep_launches = prep_launches;
+    last.n_scans = n_scans;
     live.clear();
     for (int b = 0; b < n_scans; b++) {
         s2m_context* k = h->batch.kids[(size_t)b];
         k->reg.pending = Reg::kBatch;
-        if (optimize_gate(k, poses + 6 * (size_t)b)) live.push_back(b);
+        if (optimize_gate(k, poses + 6 * (size_t)b)) { live.push_back(b); last.n_live++; }
     }
     {   // DevCtx blocks that changed and the loop state every live slot starts from: one launch per kCtxSlots / kInitSlots slots
         CtxTable ct; int nc = 0;
@@ -308,9 +327,9 @@ int s2m_optimize_batch_launch(s2m_handle h, int n_scans, const float* poses)
             if (!k->ctx_dirty) continue;
             ct.dst[nc] = k->reg.dctx.as<DevCtx>(); ct.v[nc] = k->hctx;
             k->ctx_dirty = false;
-            if (++nc == kCtxSlots) { launch_set_ctxs(h->stream, ct, nc); nc = 0; }
+            if (++nc == kCtxSlots) { launch_set_ctxs(h->stream, ct, nc, &last.ctx_launches); nc = 0; }
         }
-        if (nc) launch_set_ctxs(h->stream, ct, nc);
+        if (nc) launch_set_ctxs(h->stream, ct, nc, &last.ctx_launches);
         StateInitTable it; int ni = 0;
         for (int b : live) {
             s2m_context* k = h->batch.kids[(size_t)b];
@@ -320,9 +339,9 @@ int s2m_optimize_batch_launch(s2m_handle h, int n_scans, const float* poses)
             si.dst = k->reg.state.as<DevState>(); si.n_waves = k->reg.n_waves.as<int32_t>();
             memcpy(si.pose, s0.pose, sizeof(si.pose)); memcpy(si.T, s0.T, sizeof(si.T)); memcpy(si.sc, s0.sc, sizeof(si.sc));
             memcpy(si.matP, s0.matP, sizeof(si.matP)); si.isDegenerate = s0.isDegenerate;
-            if (++ni == kInitSlots) { launch_init_states(h->stream, it, ni); ni = 0; }
+            if (++ni == kInitSlots) { launch_init_states(h->stream, it, ni, &last.init_launches); ni = 0; }
         }
-        if (ni) launch_init_states(h->stream, it, ni);
+        if (ni) launch_init_states(h->stream, it, ni, &last.init_launches);
         S2M_HIP(h, hipGetLastError());
     }
     // With early exit on the loops are issued as launches 0 .. seg-1 and, only if some slot has not converged by then, the rest

@@ -481,4 +481,23 @@ int s2m_time_iterations(s2m_handle h, const float pose[6], int reps, float* ms_p
     return time_iterations_impl(h, pose, reps, nullptr, ms_per_iter);
 }
 
+// Host only: a copy of the notes the batch entry points took where they issued their launches (s2m_context::Batch::last).
+int s2m_debug_batch_last(s2m_handle h, s2m_debug_batch_last_out* out)
+{
+    if (!h || !out) return S2M_ERR_INVALID_ARG;
+    const s2m_context::Batch::Last& last = h->batch.last;
+    memset(out, 0, sizeof(*out));
+    out->n_scans = last.n_scans; out->n_live = last.n_live;
+    out->ctx_launches = last.ctx_launches; out->init_launches = last.init_launches; out->prep_launches = last.prep_launches;
+    out->ranges_issued = last.ranges_issued;
+    out->graph_cached = last.graph_hits > 0 && last.graph_captures == 0;
+    out->n_loops = last.n_loops;
+    for (int j = 0; j < 2; j++) {
+        const LoopIssued& l = last.loop[j];
+        out->loop[j].wpb = l.wpb; out->loop[j].nslots = l.nslots; out->loop[j].nblocks = l.nblocks;
+        out->loop[j].fused = l.fused; out->loop[j].first_split = l.first_split;
+    }
+    return S2M_OK;
+}
+
 }  // extern "C"

@@ -47,6 +47,10 @@ constexpr size_t kDsStride = 32;       // filtered clouds are kept as pcl::Point
 // upload of s2m_optimize_launch ends, the k_finalize that closes the loop's (first) range ends
 enum { kStampPrep0 = 0, kStampPrep1 = 1, kStampLoop0 = 2, kStampLoop1 = 3, kStampCount = 4 };
 
+// What enqueue_loop issued, noted as it decided it: the grid (nblocks x nslots workgroups of wpb waves), whether the iterations
+// close inside the registration kernel (fused) or by k_finalize, and the first launch that ran certify + search (-1: none)
+struct LoopIssued { int wpb = 0, nslots = 0, nblocks = 0, fused = 0, first_split = -1; };
+
 }  // namespace host
 }  // namespace s2m
 
@@ -86,6 +90,7 @@ struct __attribute__((visibility("hidden"))) s2m_context {
         float persist_matP[36] = { 0 };
 
         std::map<long long, hipGraphExec_t> graphs;
+        s2m::host::LoopIssued last_loop;   // of the last enqueue_loop on this context (a batch keeps them with its graphs)
         std::vector<hipEvent_t> iter_events;
         hipEvent_t ev_a = nullptr, ev_b = nullptr, ev_c = nullptr, ev_d = nullptr, ev_up = nullptr;
         hipEvent_t ev_a2 = nullptr, ev_b2 = nullptr;     // around the second range of launches
@@ -130,7 +135,17 @@ struct __attribute__((visibility("hidden"))) s2m_context {
         DevBuf kid_states;
         unsigned char* h_kid_states = nullptr;
         bool state_borrowed = false;       // (a slot: `reg.state` and `reg.h_state` point into the parent's blocks)
-        std::map<std::vector<int>, hipGraphExec_t> graphs;
+        struct Graph { hipGraphExec_t exec = nullptr; std::vector<s2m::host::LoopIssued> loops; };   // (loops: what enqueue_loop noted at the capture)
+        std::map<std::vector<int>, Graph> graphs;
+        // What the last s2m_batch_set_scans (prep_launches) and the last batch launch / collect issued, each count taken where
+        // the launch is issued or the decision falls (s2m_debug_batch_last): observation only, nothing reads it back.
+        struct Last {
+            int n_scans = 0, n_live = 0;
+            int ctx_launches = 0, init_launches = 0, prep_launches = 0;
+            int ranges_issued = 0, graph_hits = 0, graph_captures = 0;
+            int n_loops = 0;
+            s2m::host::LoopIssued loop[2];
+        } last;
         int pend_n = 0;                    // n_scans of the batch in flight (0: none); its slots 0 .. pend_n-1 are pending as kBatch
         std::vector<int> live;             // the slots of the batch in flight that run a loop
         bool seg_pending = false;          // the batch in flight was issued as its first range of launches only (early exit on)
@@ -430,9 +445,9 @@ void launch_density_state(s2m_context* h, const float pose[6], unsigned long lon
 // k_chunk_table, the extent-only wave table of `nslots` prepared slots (it shares chunk_table_body with k_chunk_table_density)
 void launch_chunk_table(hipStream_t stream, const PrepTable& t, int nslots);
 // k_set_ctxs / k_init_states over the first n entries of a table (a batch launch: the DevCtx blocks that changed, the loop
-// states its live slots start from); the entries behind them are marked unused here
-void launch_set_ctxs(hipStream_t stream, CtxTable& t, int n);
-void launch_init_states(hipStream_t stream, StateInitTable& t, int n);
+// states its live slots start from); the entries behind them are marked unused here.  `issued`, if given, counts the launch.
+void launch_set_ctxs(hipStream_t stream, CtxTable& t, int n, int* issued = nullptr);
+void launch_init_states(hipStream_t stream, StateInitTable& t, int n, int* issued = nullptr);
 // what one loop launches over: the scan slots (one for a single scan), the widest grid among them, their common workgroup shape
 struct LoopShape {
     SlotTable tbl;
@@ -495,7 +510,7 @@ inline bool slots_pending(const s2m_context* h)
 int set_map_impl(s2m_context* h, const void* pts, size_t n, size_t stride, bool on_device);
 int set_scan_impl(s2m_context* h, const void* pts, size_t n, size_t stride, bool on_device);
 int scan_slot_prepare(s2m_context* h, const void* pts, size_t n, size_t stride, bool on_device, PrepSlot* ps);
-void launch_scan_prep(hipStream_t stream, const PrepTable& t, int nslots, bool single = false);
+void launch_scan_prep(hipStream_t stream, const PrepTable& t, int nslots, bool single = false, int* issued = nullptr);
 void ensure_wave_table(s2m_context* h);
 
 // ---- s2m_sc.hip ----

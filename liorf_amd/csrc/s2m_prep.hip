@@ -268,7 +268,7 @@ int s2m::host::scan_slot_prepare(s2m_context* h, const void* pts, size_t n, size
 // k_chunk_parts - and no wave table: the scan's first optimisation asks for the density wishes chunk by chunk
 // (k_wave_density_state) and k_chunk_table_density emits the table once; whatever else needs the extent-only table first
 // builds it through ensure_wave_table.
-void s2m::host::launch_scan_prep(hipStream_t stream, const PrepTable& t, int nslots, bool single)
+void s2m::host::launch_scan_prep(hipStream_t stream, const PrepTable& t, int nslots, bool single, int* issued)
 {
     int npb = 0, nb = 0, ncb = 0;
     for (int k = 0; k < nslots; k++) {
@@ -277,6 +277,7 @@ void s2m::host::launch_scan_prep(hipStream_t stream, const PrepTable& t, int nsl
         ncb = std::max(ncb, (t.s[k].n_chunks + 3) / 4);
     }
     if (npb == 0) return;
+    if (issued) ++*issued;                                // (a table of empty rows only is not launched, and not counted)
     hipLaunchKernelGGL(k_polar_count, dim3(npb, nslots), dim3(kPolarBlock), 0, stream, t);
     hipLaunchKernelGGL(k_polar_prefix, dim3(kPolarCells / 64, nslots), dim3(1024), 0, stream, t);
     if (single) {

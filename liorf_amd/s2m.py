@@ -51,7 +51,7 @@ ABI_SYMBOLS = [
     "s2m_loop_align_launch", "s2m_loop_closure_rs_launch", "s2m_loop_poll", "s2m_loop_collect",
     "s2m_loop_verify_check_args", "s2m_loop_verify_launch", "s2m_loop_verify_poll", "s2m_loop_verify_collect", "s2m_loop_verify",
     "s2m_loop_verify_many_check_args", "s2m_loop_verify_many", "s2m_debug_icp_align_pairs_device",
-    "s2m_debug_loop_verify_many_pass", "s2m_debug_loop_verify_many_last", "s2m_debug_loop_verify_many_plan",
+    "s2m_debug_loop_verify_many_pass", "s2m_debug_loop_verify_many_last", "s2m_debug_loop_verify_many_plan", "s2m_debug_batch_last",
     "s2m_reloc_default_params", "s2m_relocalize_check_args", "s2m_relocalize_scan", "s2m_debug_icp_align_guess_many_device",
     "s2m_debug_icp_nearest", "s2m_debug_icp_time_nearest", "s2m_debug_icp_align_device", "s2m_debug_icp_align_many_device",
     "s2m_debug_icp_tuning", "s2m_debug_icp_grid_check_args", "s2m_debug_icp_grid",
@@ -288,6 +288,18 @@ SESSION_WRITE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_size_t)
 SESSION_READ_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_size_t)
 
 
+class BatchLoop(C.Structure):
+    """s2m_debug_batch_loop (include/liorf_s2m_debug.h)."""
+    _fields_ = [("wpb", C.c_int32), ("nslots", C.c_int32), ("nblocks", C.c_int32), ("fused", C.c_int32), ("first_split", C.c_int32)]
+
+
+class BatchLast(C.Structure):
+    """s2m_debug_batch_last_out (include/liorf_s2m_debug.h)."""
+    _fields_ = [("n_scans", C.c_int32), ("n_live", C.c_int32),
+                ("ctx_launches", C.c_int32), ("init_launches", C.c_int32), ("prep_launches", C.c_int32),
+                ("ranges_issued", C.c_int32), ("graph_cached", C.c_int32), ("n_loops", C.c_int32), ("loop", BatchLoop * 2)]
+
+
 class S2MError(RuntimeError):
     """`code` is the status the library returned, where one did."""
     code = None
@@ -440,6 +452,7 @@ def load_library(path: str | None = None) -> C.CDLL:
     L.s2m_debug_loop_verify_many_pass.argtypes = [vp, C.c_int32]
     L.s2m_debug_loop_verify_many_last.argtypes = [vp, i32p, i32p, szp]
     L.s2m_debug_loop_verify_many_plan.argtypes = [i32p, C.c_int32, C.c_int32, i32p, i32p]
+    L.s2m_debug_batch_last.argtypes = [vp, C.POINTER(BatchLast)]
     L.s2m_debug_icp_align_many_device.argtypes = [vp, vp, C.c_size_t, C.POINTER(C.c_void_p), szp, C.c_int32, C.c_size_t, C.POINTER(IcpParams),
                                                   C.POINTER(IcpResult)]
     L.s2m_debug_icp_align_guess_many_device.argtypes = [vp, vp, C.c_size_t, C.POINTER(C.c_void_p), szp, fp, C.c_int32, C.c_size_t,
@@ -910,6 +923,12 @@ class MapOptimizationS2M:
         self._check(self.lib.s2m_optimize_batch(self.h, n, ptrs, sizes, st, _fp(p), im, res), "s2m_optimize_batch")
         self._batch_n = n
         return p, [res[k] for k in range(n)]
+
+    def batchLast(self) -> BatchLast:
+        """s2m_debug_batch_last: what the last batchSetScans and batch launch / collect issued, noted where they issued it."""
+        out = BatchLast()
+        self._check(self.lib.s2m_debug_batch_last(self.h, C.byref(out)), "s2m_debug_batch_last")
+        return out
 
     def batchTrace(self, slot: int) -> list[IterTrace]:
         buf = (IterTrace * 64)()
