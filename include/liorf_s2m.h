@@ -962,6 +962,58 @@ int  s2m_loop_verify_many(s2m_handle h, const int32_t* key_cur /* m */, const in
                           const s2m_loop_params* p /* NULL = defaults */,
                           s2m_loop_result* out /* m * row_stride */, int32_t* best /* m */);
 
+/* ---- Loop candidates by position, for many keys: detectLoopClosureDistance (:732-765) for any stored keys ---------------
+ * s2m_loop_closure_rs detects for key N-1 alone, its first candidate only, and aligns at once. s2m_loop_detect_keys is that
+ * detection on its own for m stored keys against the store, top_k candidates per key, in the row shape
+ * s2m_loop_verify_many takes with base_key = -1 (key_cur = keys, row_stride = top_k, key_pre, n_cand). After a
+ * s2m_session_load, a s2m_session_place or a s2m_pg_optimize the poses have just been made consistent: the keys that now
+ * lie within the radius of older keys are the loops that densify the graph.
+ *   Distance: d2(c, q) of the stored positions of keys c and q, ((dx*dx + dy*dy) + dz*dz) in fp32 without contraction - the
+ *       statement of s2m_loop_closure_rs and s2m_extract_surrounding.
+ *   Candidate: key c is a candidate of query i when c is in the searched set, d2(c, keys[i]) < (float)(R*R) with R*R formed
+ *       in float as s2m_loop_closure_rs forms it, and fabs(t[c] - T_i) > (double)time_diff_s, where T_i = time_cur[i] if
+ *       time_cur is given and t[keys[i]] otherwise. A NaN on either side of a comparison fails it.
+ *   Searched set of query i: c in [first, first + count) (count = -1: to the end of the store), outside
+ *       [exclude_lo, exclude_hi) and outside [keys[i] + rel_lo, keys[i] + rel_hi), the sums in 64 bits; a window with
+ *       lo >= hi leaves nothing out.
+ *   The query key itself is not left out by name. With the stored times the time gate leaves it out for every
+ *       time_diff_s >= 0 (|0| > W is false); with an external time_cur it can appear in its own row, as it can in the
+ *       reference's radius result.
+ *   Row i: the first top_k candidates in ascending (bits of d2, key) order in key_pre[i * top_k ..] and d2[i * top_k ..]
+ *       (d2 may be NULL), their number in n_cand[i]; the entries behind n_cand[i] stay as the caller had them. keys may
+ *       repeat and come in any order; a row depends on its own query alone, and is bit for bit the same however the work is
+ *       cut into tiles, store splits and passes.
+ *   The detector: keys = {N-1}, time_cur = {timeLaserInfoCur}, top_k = 1 and the whole store give the row of the detection
+ *       inside s2m_loop_closure_rs: that call reports S2M_LOOP_NONE exactly when the row is empty or holds N-1, and otherwise
+ *       its key_pre is key_pre[0].
+ *   Read-only, with buffers of its own: nothing of the key store, the loop container, the voxel workspace, the scan or the
+ *       map is touched. It runs on the handle's stream and works beside a pending launched closure, a pending verification
+ *       and a pending optimise: it never returns S2M_ERR_BUSY.
+ *   Passes: the queries go through in passes of at most 64 MiB of device memory, whatever m and N are, with one wait per
+ *       pass; the plan depends on the arguments alone.
+ *   S2M_ERR_INVALID_ARG, outputs untouched: a null handle; m < 0; null keys, key_pre or n_cand with m > 0; a key outside
+ *       [0, N); a time_cur[i] that is not finite; top_k outside 1 .. S2M_LOOP_MAX_CANDIDATES; reserved != 0; first < 0,
+ *       count < -1 or a range past the store; a radius or time difference that s2m_loop_params would reject.
+ *       s2m_loop_detect_keys_check_args gives the same verdict from the store's size alone (host code, no handle; the values
+ *       of time_cur and the outputs are the call's own checks).
+ *   S2M_OK without work: m == 0 writes nothing; an empty searched range gives n_cand[i] = 0, and so does an empty store,
+ *       which holds no key for a query to be outside of (its keys are not looked at). */
+typedef struct s2m_loop_detect_params {
+    float   search_radius;           /* historyKeyframeSearchRadius   10.0  include/utility.h:245; range as s2m_loop_params */
+    float   time_diff_s;             /* historyKeyframeSearchTimeDiff 30.0  include/utility.h:246; range as s2m_loop_params */
+    int32_t first, count;            /* searched keys [first, first+count); count = -1: to the end of the store */
+    int32_t exclude_lo, exclude_hi;  /* fixed window left out; lo >= hi: none */
+    int32_t rel_lo, rel_hi;          /* ALSO leave out c with key + rel_lo <= c < key + rel_hi (sums in 64 bits); lo >= hi: none */
+    int32_t top_k;                   /* 1 .. S2M_LOOP_MAX_CANDIDATES; default 1 */
+    int32_t reserved;                /* 0 */
+} s2m_loop_detect_params;
+int  s2m_loop_detect_default_params(s2m_loop_detect_params* p);
+int  s2m_loop_detect_keys_check_args(int32_t n_stored, const int32_t* keys, int32_t m, int has_time_cur,
+                                     const s2m_loop_detect_params* p /* NULL = defaults */);   /* host only, no handle */
+int  s2m_loop_detect_keys(s2m_handle h, const int32_t* keys /* m */, const double* time_cur /* m, or NULL */, int32_t m,
+                          const s2m_loop_detect_params* p /* NULL = defaults */,
+                          int32_t* key_pre /* m * top_k */, float* d2 /* m * top_k, may be NULL */, int32_t* n_cand /* m */);
+
 /* ---- Relocalisation: where in the stored map is this scan, as a pose ------------------------------------------------
  * From a fresh scan (not a key) to a pose in the map frame, so that s2m_extract_surrounding_at and s2m_optimize* can start
  * or recover inside a map the handle already holds. ScanContext key i must be key-frame i (both stores filled in step).

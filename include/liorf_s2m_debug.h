@@ -321,6 +321,20 @@ int  s2m_debug_loop_verify_many_pass(s2m_handle h, int32_t pairs_per_pass);
 int  s2m_debug_loop_verify_many_last(s2m_handle h, int32_t* passes, int32_t* pairs_aligned, size_t* bytes);
 int  s2m_debug_loop_verify_many_plan(const int32_t* n_cand, int32_t m, int32_t pairs_per_pass, int32_t* first_row_of_pass, int32_t* n_pass);
 
+/* ---- the loop detection by position for many keys: its passes and the shape of its kernel ----
+ * s2m_debug_loop_detect_pass: at most this many queries per pass of s2m_loop_detect_keys (0 restores the default, as many as
+ *   the 64 MiB scratch bound allows). The rows do not depend on it.
+ * s2m_debug_loop_detect_shape: the stored keys a workgroup of k_loop_detect_many holds in LDS (tile_keys), the queries it walks
+ *   past them (block_queries) and the most store splits of a grid (max_splits), so that tests can place their sizes at the
+ *   kernel's edges.
+ * s2m_debug_loop_detect_last: the passes of the handle's last s2m_loop_detect_keys and the device bytes one of them used.
+ * s2m_debug_loop_detect_splits: at most this many store splits per grid (0 restores the plan's own, which takes more splits the
+ *   fewer queries a pass holds). The rows do not depend on it; the benchmark uses it to show what the splits buy. */
+int  s2m_debug_loop_detect_pass(s2m_handle h, int32_t queries_per_pass);
+int  s2m_debug_loop_detect_splits(s2m_handle h, int32_t max_splits);
+int  s2m_debug_loop_detect_shape(int32_t* tile_keys, int32_t* block_queries, int32_t* max_splits);
+int  s2m_debug_loop_detect_last(s2m_handle h, int32_t* passes, size_t* scratch_bytes);
+
 /* ---- what a batch issued (s2m_batch_set_scans, s2m_optimize_batch_launch / _collect, s2m_optimize_batch) ----
  * Host only, no kernel and no device memory: every number is noted where the library issues the launch or takes the decision,
  * none is worked out from n_scans afterwards. It proves which path a batch took; the results are held to their bits elsewhere.

@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "s2m_context.hpp"
+#include "s2m_loop_detect_plan.hpp"    // loop_radius_time_ok: the radius and time test shared with s2m_loop_detect_keys
 
 using namespace s2m;
 using namespace s2m::host;
@@ -143,8 +144,7 @@ namespace {
 int loop_params(s2m_context* h, const s2m_loop_params* p, s2m_loop_params* prm)
 {
     if (p) *prm = *p; else s2m_loop_default_params(prm);
-    if (!(prm->search_radius > 0.0f) || !std::isfinite(prm->search_radius) || !std::isfinite(prm->time_diff_s) ||
-        prm->search_num < 0 || std::isnan(prm->fitness_score))
+    if (!loop_radius_time_ok(prm->search_radius, prm->time_diff_s) || prm->search_num < 0 || std::isnan(prm->fitness_score))
         return fail(h, S2M_ERR_INVALID_ARG, "loop search radius must be positive, time window finite, search_num >= 0");
     return check_leaf(h, prm->icp_leaf);
 }

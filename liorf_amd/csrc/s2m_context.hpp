@@ -263,6 +263,18 @@ struct __attribute__((visibility("hidden"))) s2m_context {
         int32_t many_last_passes = 0, many_last_pairs = 0;
     } loop;
 
+    // loop detection by position for many keys (s2m_loop_detect_keys, s2m_loop_detect.hpp): buffers of its own - the pass's keys and
+    // times, the (query, split) lists, the rows - together at most kScManyScratchMax, and the pinned block of a pass (upload |
+    // rows).  pass: queries per pass, 0: as many as the bound allows (s2m_debug_loop_detect_pass); max_splits: a cap on the store
+    // splits of a grid, 0: the plan's own (s2m_debug_loop_detect_splits); last_*: of the last call.
+    struct LoopDetect {
+        DevBuf in, part, out;
+        unsigned char* h_pass = nullptr;
+        size_t h_pass_cap = 0;
+        int pass = 0, max_splits = 0, last_passes = 0;
+        size_t last_scratch = 0;
+    } ldet;
+
     // the global map and the saved map from the store: transformed frames, the filtered cloud, the chunked copy-out (frame table,
     // two staging buffers that take turns, a copy stream and its events)
     struct GlobalMap {

@@ -12,6 +12,7 @@
 // CPU oracle defines, so centroids are bit-identical to it. Run starts (where the sorted key changes)
 // are compacted in two kernels (k_heads_*). Compiled with -ffp-contract=off like the rest.
 #include "s2m_voxel.hpp"
+#include "s2m_kf_d2.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -750,12 +751,7 @@ struct KfSelState {
     int32_t n_cent;
 };
 
-// FLANN's L2_Simple accumulation: ((dx^2 + dy^2) + dz^2), fp32, no contraction
-__device__ __forceinline__ float kf_d2(float4 a, float4 b)
-{
-    const float dx = a.x - b.x, dy = a.y - b.y, dz = a.z - b.z;
-    return (dx * dx + dy * dy) + dz * dz;
-}
+// (kf_d2, the squared distance of two key positions: s2m_kf_d2.hpp)
 
 // exclusive prefix of v over the workgroup (kKfThreads lanes) and its total; s_w: kKfThreads / 64 words of LDS
 template <typename T>

@@ -842,6 +842,73 @@ public:
         return won;
     }
 
+    // Loop candidates by position for many keys (s2m_loop_detect_keys): detectLoopClosureDistance() for
+    // every key of `keys` against the searched set of p, row i as a VerifyRow - what loopVerifyMany(rows, -1) takes - with the
+    // fp32 squared distances alike in d2 (may be null). time_cur: empty (a query's time is its key's) or one time per key.
+    std::vector<VerifyRow> loopDetectKeys(const std::vector<int32_t>& keys, const std::vector<double>& time_cur, const s2m_loop_detect_params& p,
+                                          std::vector<std::vector<float>>* d2 = nullptr)
+    {
+        if (!time_cur.empty() && time_cur.size() != keys.size()) throw std::invalid_argument("loopDetectKeys: one time per key");
+        const size_t K = (size_t)(p.top_k > 0 ? p.top_k : 0);
+        std::vector<int32_t> key_pre(keys.size() * K, -1), n(keys.size(), 0);
+        std::vector<float> dist(keys.size() * K, 0.0f);
+        check(s2m_loop_detect_keys(h_, keys.data(), time_cur.empty() ? nullptr : time_cur.data(), (int32_t)keys.size(), &p, key_pre.data(),
+                                   dist.data(), n.data()), "s2m_loop_detect_keys");
+        std::vector<VerifyRow> rows(keys.size());
+        if (d2) d2->assign(keys.size(), {});
+        for (size_t i = 0; i < keys.size(); i++) {
+            rows[i].key_cur = keys[i];
+            rows[i].key_pre.assign(key_pre.begin() + i * K, key_pre.begin() + i * K + n[i]);
+            if (d2) (*d2)[i].assign(dist.begin() + i * K, dist.begin() + i * K + n[i]);
+        }
+        return rows;
+    }
+    // Every stored key, or `keys`, against the whole store by position: the candidates a node hands to loopVerifyMany(rows, -1),
+    // in the order of the keys and per key by (d2, key_pre). Take them after a place or an optimise has made the poses
+    // consistent; before the two trajectories agree, take findSessionLoops' descriptor candidates.
+    struct DistanceLoop { int32_t key_cur, key_pre; float d2; };
+    std::vector<int32_t> allKeys() const
+    {
+        const int n_keys = s2m_kf_size(h_);
+        std::vector<int32_t> keys((size_t)(n_keys > 0 ? n_keys : 0));
+        for (size_t k = 0; k < keys.size(); k++) keys[k] = (int32_t)k;
+        return keys;
+    }
+    s2m_loop_detect_params loopDetectParams(float radius, float time_diff, int top_k) const
+    {
+        s2m_loop_detect_params p;
+        s2m_loop_detect_default_params(&p);
+        p.search_radius = radius; p.time_diff_s = time_diff; p.top_k = top_k;
+        return p;
+    }
+    std::vector<DistanceLoop> findSessionLoopsByDistance(float radius, float time_diff, int top_k, const std::vector<int32_t>* keys = nullptr)
+    {
+        std::vector<std::vector<float>> d2;
+        const std::vector<VerifyRow> rows = loopDetectKeys(keys ? *keys : allKeys(), {}, loopDetectParams(radius, time_diff, top_k), &d2);
+        std::vector<DistanceLoop> out;
+        for (size_t r = 0; r < rows.size(); r++)
+            for (size_t i = 0; i < rows[r].key_pre.size(); i++) out.push_back(DistanceLoop{ rows[r].key_cur, rows[r].key_pre[i], d2[r][i] });
+        return out;
+    }
+    // findSessionLoopsByDistance's query followed by loopVerifyMany in chunks of rows_per_call rows, as verifySessionLoops: the
+    // winning records, one per key that has an accepted candidate. `keys` must be distinct.
+    std::vector<s2m_loop_result> verifySessionLoopsByDistance(float radius, float time_diff, int top_k, const std::vector<int32_t>* keys,
+                                                              int base_key, int rows_per_call, const std::function<void()>& between_chunks = {})
+    {
+        std::vector<VerifyRow> rows;
+        for (VerifyRow& r : loopDetectKeys(keys ? *keys : allKeys(), {}, loopDetectParams(radius, time_diff, std::min(top_k, (int)S2M_LOOP_MAX_CANDIDATES))))
+            if (!r.key_pre.empty()) rows.push_back(std::move(r));
+        std::vector<s2m_loop_result> won;
+        const size_t step = (size_t)std::max(rows_per_call, 1);
+        for (size_t i = 0; i < rows.size(); i += step) {
+            const std::vector<VerifyRow> chunk(rows.begin() + i, rows.begin() + std::min(rows.size(), i + step));
+            for (const VerifiedRow& v : loopVerifyMany(chunk, base_key))
+                if (v.best >= 0) won.push_back(v.records[(size_t)v.best]);
+            if (between_chunks) between_chunks();
+        }
+        return won;
+    }
+
     // void performSCLoopClosure() (:624-730): the ScanContext detector on this handle, then the store's extraction and ICP
     inline bool performSCLoopClosure(SCManagerS2M& scManager);
 

@@ -182,6 +182,14 @@ static int run_loop(char** argv, bool async)
     std::vector<liorf_amd::PointXYZI> near;
     if (i > 0) node.loopFindNearKeyframes(near, i - 1, node.historyKeyframeSearchNum, -1);
     std::printf("near %zu\n", near.size());
+    if (i > 0) {
+        // the position candidates of the last key and their verification (loopDetectKeys behind both); stderr: the lines above
+        // are the record a caller compares
+        const std::vector<int32_t> last{ (int32_t)(i - 1) };
+        const size_t n_cand = node.findSessionLoopsByDistance(node.historyKeyframeSearchRadius, node.historyKeyframeSearchTimeDiff, 2, &last).size();
+        const size_t n_won = node.verifySessionLoopsByDistance(node.historyKeyframeSearchRadius, node.historyKeyframeSearchTimeDiff, 2, &last, -1, 64).size();
+        std::fprintf(stderr, "by distance: key %d, %zu candidates, %zu verified\n", i - 1, n_cand, n_won);
+    }
     return 0;
 }
 

@@ -52,6 +52,8 @@ ABI_SYMBOLS = [
     "s2m_loop_verify_check_args", "s2m_loop_verify_launch", "s2m_loop_verify_poll", "s2m_loop_verify_collect", "s2m_loop_verify",
     "s2m_loop_verify_many_check_args", "s2m_loop_verify_many", "s2m_debug_icp_align_pairs_device",
     "s2m_debug_loop_verify_many_pass", "s2m_debug_loop_verify_many_last", "s2m_debug_loop_verify_many_plan", "s2m_debug_batch_last",
+    "s2m_loop_detect_default_params", "s2m_loop_detect_keys_check_args", "s2m_loop_detect_keys",
+    "s2m_debug_loop_detect_pass", "s2m_debug_loop_detect_shape", "s2m_debug_loop_detect_last", "s2m_debug_loop_detect_splits",
     "s2m_reloc_default_params", "s2m_relocalize_check_args", "s2m_relocalize_scan", "s2m_debug_icp_align_guess_many_device",
     "s2m_debug_icp_nearest", "s2m_debug_icp_time_nearest", "s2m_debug_icp_align_device", "s2m_debug_icp_align_many_device",
     "s2m_debug_icp_tuning", "s2m_debug_icp_grid_check_args", "s2m_debug_icp_grid",
@@ -194,6 +196,13 @@ class KfParams(C.Structure):
 class LoopParams(C.Structure):
     _fields_ = [("search_radius", C.c_float), ("time_diff_s", C.c_float), ("search_num", C.c_int32),
                 ("fitness_score", C.c_float), ("icp_leaf", C.c_float)]
+
+
+class LoopDetectParams(C.Structure):
+    """s2m_loop_detect_params: radius and time gate, the searched range, the fixed and the relative window, top_k."""
+    _fields_ = [("search_radius", C.c_float), ("time_diff_s", C.c_float), ("first", C.c_int32), ("count", C.c_int32),
+                ("exclude_lo", C.c_int32), ("exclude_hi", C.c_int32), ("rel_lo", C.c_int32), ("rel_hi", C.c_int32),
+                ("top_k", C.c_int32), ("reserved", C.c_int32)]
 
 
 class LoopResult(C.Structure):
@@ -452,6 +461,14 @@ def load_library(path: str | None = None) -> C.CDLL:
     L.s2m_debug_loop_verify_many_pass.argtypes = [vp, C.c_int32]
     L.s2m_debug_loop_verify_many_last.argtypes = [vp, i32p, i32p, szp]
     L.s2m_debug_loop_verify_many_plan.argtypes = [i32p, C.c_int32, C.c_int32, i32p, i32p]
+    ldp = C.POINTER(LoopDetectParams)
+    L.s2m_loop_detect_default_params.argtypes = [ldp]
+    L.s2m_loop_detect_keys_check_args.argtypes = [C.c_int32, i32p, C.c_int32, C.c_int, ldp]
+    L.s2m_loop_detect_keys.argtypes = [vp, i32p, dp, C.c_int32, ldp, i32p, fp, i32p]
+    L.s2m_debug_loop_detect_pass.argtypes = [vp, C.c_int32]
+    L.s2m_debug_loop_detect_splits.argtypes = [vp, C.c_int32]
+    L.s2m_debug_loop_detect_shape.argtypes = [i32p, i32p, i32p]
+    L.s2m_debug_loop_detect_last.argtypes = [vp, i32p, szp]
     L.s2m_debug_batch_last.argtypes = [vp, C.POINTER(BatchLast)]
     L.s2m_debug_icp_align_many_device.argtypes = [vp, vp, C.c_size_t, C.POINTER(C.c_void_p), szp, C.c_int32, C.c_size_t, C.POINTER(IcpParams),
                                                   C.POINTER(IcpResult)]
@@ -1871,6 +1888,70 @@ class MapOptimizationS2M:
             won += [r[b] for r, b in zip(recs, best) if b >= 0]
         return won
 
+    # -- loop candidates by position for many keys -------------------------------------------------
+    def loopDetectKeys(self, keys, time_cur=None, params: "LoopDetectParams | None" = None, **kw):
+        """s2m_loop_detect_keys: for every stored key of `keys` its candidates by position, ascending (d2, key): (rows, d2 rows),
+        rows = [(key, [key_pre...]), ...] as loopVerifyMany(rows, base_key=-1) takes them, d2 rows the fp32 squared distances
+        alike.  time_cur: None (a query's time is its key's) or one time per key.  Keyword arguments set fields of the
+        parameters (search_radius, time_diff_s, first, count, exclude_lo / _hi, rel_lo / _hi, top_k)."""
+        p = default_loop_detect_params(**kw) if params is None else _copy_struct(params)
+        if params is not None:
+            for k, v in kw.items():
+                if not hasattr(p, k):
+                    raise AttributeError(k)
+                setattr(p, k, v)
+        keys = np.ascontiguousarray(keys, np.int32).reshape(-1)
+        m, K = len(keys), max(int(p.top_k), 0)
+        tc = None if time_cur is None else np.ascontiguousarray(time_cur, np.float64).reshape(-1)
+        if tc is not None and len(tc) != m:
+            raise ValueError("time_cur: one time per key")
+        key_pre = np.full((m, K), -1, np.int32)
+        d2 = np.full((m, K), np.inf, np.float32)
+        n = np.zeros(m, np.int32)
+        self._check(self.lib.s2m_loop_detect_keys(self.h, keys.ctypes.data_as(C.POINTER(C.c_int32)),
+                                                  None if tc is None else tc.ctypes.data_as(C.POINTER(C.c_double)), m, C.byref(p),
+                                                  key_pre.ctypes.data_as(C.POINTER(C.c_int32)), d2.ctypes.data_as(C.POINTER(C.c_float)),
+                                                  n.ctypes.data_as(C.POINTER(C.c_int32))), "s2m_loop_detect_keys")
+        return ([(int(keys[i]), [int(k) for k in key_pre[i, :n[i]]]) for i in range(m)], [d2[i, :n[i]].copy() for i in range(m)])
+
+    def findSessionLoopsByDistance(self, radius: float = 10.0, time_diff: float = 30.0, top_k: int = 1, keys=None):
+        """Every stored key, or `keys`, against the whole store by position: the (key_cur, key_pre, d2) candidates a node hands to
+        loopVerifyMany(base_key=-1), in the order of the keys and per key in (d2, key_pre) order."""
+        if keys is None:
+            keys = np.arange(self.kfSize(), dtype=np.int32)
+        rows, d2 = self.loopDetectKeys(keys, search_radius=radius, time_diff_s=time_diff, top_k=top_k)
+        return [(cur, pre, float(d)) for (cur, pres), ds in zip(rows, d2) for pre, d in zip(pres, ds)]
+
+    def verifySessionLoopsByDistance(self, radius: float = 10.0, time_diff: float = 30.0, top_k: int = 1, keys=None, base_key: int = -1,
+                                     params: LoopParams | None = None, rows_per_call: int = 64):
+        """findSessionLoopsByDistance's query followed by loopVerifyMany in chunks of rows_per_call rows (a node releases its lock
+        between chunks): the winning records, one per key that has an accepted candidate, in the order of the keys.  `keys` must
+        be distinct, as loopVerifyMany asks."""
+        top_k = min(int(top_k), S2M_LOOP_MAX_CANDIDATES)
+        if keys is None:
+            keys = np.arange(self.kfSize(), dtype=np.int32)
+        rows, _ = self.loopDetectKeys(keys, search_radius=radius, time_diff_s=time_diff, top_k=top_k)
+        rows = [r for r in rows if len(r[1])]
+        won = []
+        for i in range(0, len(rows), max(int(rows_per_call), 1)):
+            recs, best = self.loopVerifyMany(rows[i:i + max(int(rows_per_call), 1)], base_key, params)
+            won += [r[b] for r, b in zip(recs, best) if b >= 0]
+        return won
+
+    def debugLoopDetectPass(self, queries_per_pass: int = 0):
+        """s2m_debug_loop_detect_pass: at most this many queries per pass of loopDetectKeys (0: the default)."""
+        self._check(self.lib.s2m_debug_loop_detect_pass(self.h, int(queries_per_pass)), "s2m_debug_loop_detect_pass")
+
+    def debugLoopDetectSplits(self, max_splits: int = 0):
+        """s2m_debug_loop_detect_splits: at most this many store splits per grid of loopDetectKeys (0: the plan's own)."""
+        self._check(self.lib.s2m_debug_loop_detect_splits(self.h, int(max_splits)), "s2m_debug_loop_detect_splits")
+
+    def debugLoopDetectLast(self):
+        """s2m_debug_loop_detect_last: (passes, device bytes of one pass) of the last loopDetectKeys."""
+        n, b = C.c_int32(0), C.c_size_t(0)
+        self._check(self.lib.s2m_debug_loop_detect_last(self.h, C.byref(n), C.byref(b)), "s2m_debug_loop_detect_last")
+        return n.value, b.value
+
     def debugLoopVerifyManyPass(self, pairs_per_pass: int = 0):
         """s2m_debug_loop_verify_many_pass: the pairs of a pass of loopVerifyMany (0: the default; clamped to [8, 64])."""
         self._check(self.lib.s2m_debug_loop_verify_many_pass(self.h, int(pairs_per_pass)), "s2m_debug_loop_verify_many_pass")
@@ -2230,6 +2311,32 @@ def loop_verify_many_plan(n_cand, pairs_per_pass: int = 0):
     if rc != 0:
         raise RuntimeError(f"s2m_debug_loop_verify_many_plan failed ({rc})")
     return [first[k] for k in range(n_pass.value + 1)]
+
+
+def default_loop_detect_params(**kw) -> LoopDetectParams:
+    """s2m_loop_detect_default_params; keyword arguments set fields."""
+    p = LoopDetectParams()
+    load_library().s2m_loop_detect_default_params(C.byref(p))
+    for k, v in kw.items():
+        if not hasattr(p, k):
+            raise AttributeError(k)
+        setattr(p, k, v)
+    return p
+
+
+def loop_detect_keys_check_args(n_stored: int, keys, params: "LoopDetectParams | None" = None, m=None, has_time_cur: bool = False) -> int:
+    """s2m_loop_detect_keys_check_args (host only, no GPU): the status code. keys=None passes a null pointer; m defaults to
+    len(keys); params=None passes a null pointer (the defaults)."""
+    arr = None if keys is None else (C.c_int32 * max(len(keys), 1))(*[int(k) for k in keys])
+    mm = m if m is not None else (0 if keys is None else len(keys))
+    return load_library().s2m_loop_detect_keys_check_args(n_stored, arr, mm, int(has_time_cur), None if params is None else C.byref(params))
+
+
+def loop_detect_shape():
+    """s2m_debug_loop_detect_shape: (stored keys of a tile, queries of a block, most store splits) of k_loop_detect_many."""
+    t, b, s = C.c_int32(0), C.c_int32(0), C.c_int32(0)
+    load_library().s2m_debug_loop_detect_shape(C.byref(t), C.byref(b), C.byref(s))
+    return t.value, b.value, s.value
 
 
 def loop_verify_best(records) -> int:

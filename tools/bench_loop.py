@@ -50,6 +50,13 @@ search radius 15 m, search_num 25, ICP leaf 0.5, fitness 0.3, time window 30 s. 
                          filter, a submap per hit, the alignments in lockstep; with the hits, their statuses and iterations, the
                          best key and its distance from the true pose
     query_ms             s2m_sc_query_scan alone with the same parameters; query_ms_all_keys: over all keys, threshold 0.3
+  python tools/bench_loop.py --detect-many             only profiles/loop_detect_many_bench_line.json (--detect-many-out): stores of
+                                                       --sizes one-point key frames on two laps of a circle (only poses and times matter),
+    detect_keys_ms       s2m_loop_detect_keys through the Python mirror, all keys against all keys and the last 64 keys against
+                         all keys, top_k 1 and 8 (R 15 m, 30 s); c_call_ms the C call on numpy arrays; c_call_one_split_ms the 64
+                         queries with the store splits switched off (s2m_debug_loop_detect_splits)
+    host_numpy_ms        the same rows from a host copy of the poses by numpy brute force in chunks of 256 queries (some rows are
+                         compared with the device's before anything is timed), host_ckdtree_ms by scipy's cKDTree if scipy is there
   python tools/bench_loop.py --kernel-stats stats.csv  folds the k_loop_detect* and k_icp* rows of a rocprofv3
                                                        --kernel-trace --stats run into the JSON line
 """
@@ -418,8 +425,103 @@ def _relocalize_main(a, s2m, n):
         f.write(json.dumps(out) + "\n")
 
 
+def _two_lap_poses(n):
+    """n keys 1 s apart at 0.5 m spacing on two laps of one circle, the second lap 0.3 m outside the first: every key of the
+    second lap has the keys of the first within the radius around it."""
+    half = n // 2
+    th = 2 * np.pi * (np.arange(n) % half) / half
+    r = 0.5 * half / (2 * np.pi) + 0.3 * (np.arange(n) >= half)
+    p = np.zeros((n, 6), np.float32)
+    p[:, 0], p[:, 1], p[:, 5] = r * np.sin(th), r * (1 - np.cos(th)), th
+    return p
+
+
+def _host_radius_rows(xyz, times, keys, r2, w, top_k, chunk=256):
+    """What a node does today from its host copy of the poses: a brute-force radius search in numpy, in chunks of queries."""
+    rows = []
+    for i0 in range(0, len(keys), chunk):
+        k = keys[i0:i0 + chunk]
+        d = xyz[None, :, :] - xyz[k][:, None, :]
+        d2 = (d[:, :, 0] * d[:, :, 0] + d[:, :, 1] * d[:, :, 1]) + d[:, :, 2] * d[:, :, 2]
+        ok = (d2 < r2) & (np.abs(times[None, :] - times[k][:, None]) > w)
+        for j in range(len(k)):
+            c = np.flatnonzero(ok[j])
+            rows.append(c[np.lexsort((c, d2[j, c]))][:top_k])
+    return rows
+
+
+def _detect_many_main(a, s2m, sizes):
+    """s2m_loop_detect_keys on stores of one-point key frames (only poses and times matter) against a host radius search."""
+    try:
+        from scipy.spatial import cKDTree
+    except ImportError:
+        cKDTree = None
+    R, W = 15.0, 30.0
+    r2 = np.float32(R) * np.float32(R)
+    one = np.array([[1.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 0.0]], np.float32)
+    out = {"workload": "tools/bench_loop.py --detect-many: two laps of a circle at 0.5 m key spacing, 1 s apart, the second lap 0.3 m outside the "
+                       "first; s2m_loop_detect_keys (R 15 m, 30 s) for all keys against all keys at top_k 1 and 8, and for the last 64 keys, "
+                       "against a numpy brute-force radius search over the host copy of the poses in chunks of 256 queries"
+                       + (" and scipy's cKDTree (build + query_ball_point + time gate + sort)" if cKDTree else "; scipy is not installed"),
+           "reps": a.reps, "warmup": a.warmup, "tile_block_max_splits": list(s2m.loop_detect_shape()), "sizes": {}}
+    for n in sizes:
+        poses = _two_lap_poses(n)
+        times = np.arange(n, dtype=np.float64)
+        eng = s2m.MapOptimizationS2M()
+        for k in range(n):
+            eng.saveKeyFrame(poses[k], times[k], one)
+        print(f"{n} keys stored", file=sys.stderr, flush=True)
+        xyz = poses[:, :3].copy()
+        allk = np.arange(n, dtype=np.int32)
+        row = {}
+        for name, keys in (("all", allk), ("last64", allk[-64:])):
+            for K in (1, 8):
+                got = eng.loopDetectKeys(keys, search_radius=R, time_diff_s=W, top_k=K)[0]
+                probe = keys[:: max(len(keys) // 64, 1)]                       # the rows of some queries against the host search, before timing
+                want = _host_radius_rows(xyz, times, probe, r2, W, K)
+                index = {int(k): i for i, k in enumerate(keys)}
+                assert all(got[index[int(k)]][1] == [int(v) for v in w] for k, w in zip(probe, want)), (n, name, K)
+                r = {"queries": int(len(keys)), "candidates": int(sum(len(c) for _, c in got)),
+                     "detect_keys_ms": _median_ms(lambda: eng.loopDetectKeys(keys, search_radius=R, time_diff_s=W, top_k=K), a.warmup, a.reps)}
+                prm = s2m.default_loop_detect_params(search_radius=R, time_diff_s=W, top_k=K)
+                kp, d2, nc = np.zeros((len(keys), K), np.int32), np.zeros((len(keys), K), np.float32), np.zeros(len(keys), np.int32)
+                raw = lambda: eng.lib.s2m_loop_detect_keys(eng.h, keys.ctypes.data_as(C.POINTER(C.c_int32)), None, len(keys), C.byref(prm),
+                                                           kp.ctypes.data_as(C.POINTER(C.c_int32)), d2.ctypes.data_as(C.POINTER(C.c_float)),
+                                                           nc.ctypes.data_as(C.POINTER(C.c_int32)))
+                r["c_call_ms"] = _median_ms(raw, a.warmup, a.reps)             # without the mirror's Python lists
+                r["passes"], r["scratch_bytes"] = eng.debugLoopDetectLast()
+                r["pair_tests"] = int(len(keys)) * n
+                if name == "last64":                                           # what the store splits buy: the same call in one split
+                    eng.debugLoopDetectSplits(1)
+                    r["c_call_one_split_ms"] = _median_ms(raw, a.warmup, a.reps)
+                    eng.debugLoopDetectSplits(0)
+                if name == "last64" or n <= 5000:
+                    r["host_numpy_ms"] = _median_ms(lambda: _host_radius_rows(xyz, times, keys, r2, W, K), 1, 3)
+                else:                                                          # 2.5e9 pairs in numpy: a sample of 1 024 queries, scaled
+                    r["host_numpy_ms_scaled_from_1024_queries"] = round(_median_ms(lambda: _host_radius_rows(xyz, times, keys[:1024], r2, W, K), 0, 1) * len(keys) / 1024, 2)
+                if cKDTree is not None:
+                    def tree():
+                        t = cKDTree(xyz)
+                        for q, c in zip(keys, t.query_ball_point(xyz[keys], R)):
+                            c = np.asarray(c, np.int64)
+                            c = c[np.abs(times[c] - times[q]) > W]
+                            c[np.argsort(((xyz[c] - xyz[q]) ** 2).sum(1), kind="stable")][:K]
+                    r["host_ckdtree_ms"] = _median_ms(tree, 1, 3)
+                row[f"{name}_top{K}"] = r
+        eng.close()
+        out["sizes"][str(n)] = row
+    out["note"] = ("wall clock on the host, median after warm-up; every call ends with the library's own synchronisation; detect_keys_ms is the "
+                   "Python mirror (it builds lists of rows), c_call_ms the C call on numpy arrays; the store holds no pose graph, so the host "
+                   "side starts from the node's own copy of the poses - the copy-out a node pays on top is not in host_*_ms")
+    print(json.dumps(out))
+    with open(a.detect_many_out, "w") as f:
+        f.write(json.dumps(out) + "\n")
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser()
+    ap.add_argument("--detect-many", action="store_true", help="measure s2m_loop_detect_keys against a host radius search, and nothing else")
+    ap.add_argument("--detect-many-out", default=os.path.join(ROOT, "profiles", "loop_detect_many_bench_line.json"))
     ap.add_argument("--relocalize", action="store_true", help="measure s2m_relocalize_scan at 1, 4 and 8 hits, and nothing else")
     ap.add_argument("--relocalize-out", default=os.path.join(ROOT, "profiles", "relocalize_bench_line.json"))
     ap.add_argument("--verify", action="store_true", help="measure the lockstep verification against sequential closures, and nothing else")
@@ -445,6 +547,8 @@ def main(argv=None):
         scans = (synth.to_xyzi(cfgs[0]["map"]), [(synth.to_xyzi(c["scan"]), c["pose_init"]) for c in cfgs])
 
     sizes = [int(s) for s in a.sizes.split(",")]
+    if a.detect_many:
+        return _detect_many_main(a, s2m, sizes)
     if a.verify:
         return _verify_main(a, s2m, sizes)
     if a.verify_many:
