@@ -1209,6 +1209,59 @@ int  s2m_pg_joint_marginal(s2m_handle h, int32_t key_a, int32_t key_b, double co
  * every variable in it needs a value (S2M_ERR_INVALID_ARG); an estimate that is not finite is S2M_ERR_INVALID_ARG and
  * leaves the store as it was. */
 int  s2m_pg_apply_to_store(s2m_handle h, int32_t first, int32_t count);
+/* The mutually consistent loops among many candidates, before any of them enters the graph.
+ * key_from, key_to and rel_xyzrpy are what the caller would give s2m_pg_add_between: candidate p claims
+ * Z_p = X_from^-1 X_to. Two candidates are consistent if the cycle they close through the current estimates returns to
+ * the identity within a tolerance that grows with the length of chain the cycle runs over; the call returns a large set
+ * of candidates that are consistent pair by pair. It is a heuristic with a fixed rule, stated below - NOT the maximum
+ * clique, which it can miss. The four default tolerances are a starting point that has not been measured on real data.
+ *   State read: the graph's current estimates (R row-major then t, fp64). Nothing is added to the graph, no estimate
+ *       changes, and the call writes only device buffers of its own.
+ *   Measurements: every rel_xyzrpy becomes (R, t) in fp64 on the host exactly as s2m_pg_add_between converts it.
+ *   Chain length, in integers: step[0] = 0, step[k] = llrint(1e6 * sqrt(((dx*dx + dy*dy) + dz*dz))) of the translation
+ *       difference of estimates k-1 and k (micrometres; a step of 2.5e11 or more, or one that is not finite, counts as
+ *       2.5e11, so that the sum over 2^24 keys fits); s[k] their inclusive prefix sum in int64, recomputed in every
+ *       call. For a pair (p, q): L = (double)(|s[from_p] - s[from_q]| + |s[to_p] - s[to_q]|) * 1e-6 metres.
+ *   Pair measure, for a < b in the caller's order, SE(3) products in fp64 without fused multiply-add: O_t = X_to_a^-1 X_to_b,
+ *       O_f = X_from_a^-1 X_from_b, M1 = Z_a O_t, M2 = O_f Z_b, D = M1^-1 M2. Every 3x3 entry is ((a0*b0 + a1*b1) + a2*b2),
+ *       every inverse (R^T, -(R^T t)), every translation of a product (R t') + t in that association.
+ *       rho2 = ((3 - R_D00) - R_D11) - R_D22 (the squared chord 4 sin^2(angle / 2)), d2 = (tx*tx + ty*ty) + tz*tz of D.
+ *       The pair is consistent iff rho2 <= (tol_chord + rate_chord*L)^2 and d2 <= (tol_m + rate_m*L)^2.
+ *   Matrix: bit q % 64 of word p * ((m + 63) / 64) + q / 64 is the pair (p, q). (q, p) is the pair (p, q), evaluated with the
+ *       operands in candidate order, so the matrix is symmetric; the diagonal is 0; a measure that is not finite is not
+ *       consistent; the bits of a row's last word behind m are 0. degree[p] is the number of set bits of row p.
+ *   Selection: rank the candidates by (degree descending, index ascending). From every start v grow S = {v}, C = row(v);
+ *       while C is not empty take its best-ranked member u, add it to S and set C &= row(u). The result is the largest S,
+ *       equal sizes going to the best-ranked start: selected[p] = 1 for its members, n_selected, and start = v. With m == 1
+ *       the one candidate is selected. The result is a fixed function of the inputs, bit for bit, run to run.
+ *   S2M_ERR_BUSY, nothing touched, while a launched optimise is pending (it writes the estimates); a pending loop closure
+ *       or verification does not matter.
+ *   S2M_ERR_INVALID_ARG, outputs untouched: a null handle; m < 0 or m > S2M_PG_CONSISTENCY_MAX; null key_from, key_to,
+ *       rel_xyzrpy or selected with m > 0; a key outside [0, n_variables) or key_from == key_to; a rel_xyzrpy that is not
+ *       finite; a tolerance or rate that is negative or not finite; nonzero reserved; a variable of the graph without an
+ *       initial value. m == 0 is S2M_OK with zero counts (start = -1).
+ *   s2m_pg_consistency_check_args: the checks of the arrays and params on their own (host code, no handle, no GPU). */
+#define S2M_PG_CONSISTENCY_MAX 4096          /* candidates per call; 64 words of 64 bits per row */
+typedef struct s2m_pg_consistency_params {
+    double  tol_m;       /* translation tolerance at zero chain length, metres              0.3    */
+    double  tol_chord;   /* rotation tolerance at zero chain length, as a chord 2 sin(a/2)  0.03   */
+    double  rate_m;      /* metres of tolerance per metre of chain travelled                0.02   */
+    double  rate_chord;  /* chord per metre of chain travelled                              0.0005 */
+    int32_t reserved[4]; /* 0 */
+} s2m_pg_consistency_params;
+typedef struct s2m_pg_consistency_result {
+    int32_t n_candidates, n_selected;
+    int32_t start;          /* the candidate the winning set was grown from */
+    int32_t reserved;
+    int64_t n_consistent_pairs;   /* set bits of the matrix / 2 */
+} s2m_pg_consistency_result;
+int  s2m_pg_consistency_default_params(s2m_pg_consistency_params* p);
+int  s2m_pg_consistency_check_args(int32_t n_variables, const int32_t* key_from, const int32_t* key_to, const float* rel_xyzrpy,
+                                   int32_t m, const s2m_pg_consistency_params* p /* NULL = defaults */);
+int  s2m_pg_consistent_loops(s2m_handle h, const int32_t* key_from, const int32_t* key_to, const float* rel_xyzrpy /* m * 6 */,
+                             int32_t m, const s2m_pg_consistency_params* p /* NULL = defaults */,
+                             uint8_t* selected /* m: 1 = in the set */, int32_t* degree /* m, may be NULL */,
+                             uint64_t* matrix /* m * ((m + 63) / 64) words, may be NULL */, s2m_pg_consistency_result* out /* may be NULL */);
 
 /* ---- Saving and loading a session ---------------------------------------------------------------------------
  * One little-endian byte stream (format version 1) holds the primary state of a handle: the key-frame

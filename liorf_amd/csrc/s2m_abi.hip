@@ -532,7 +532,7 @@ int s2m_destroy(s2m_handle h)
     vox_destroy(h->voxel.ws);
     icp_destroy(h->loop.icp);
     for (void* p : { (void*)h->batch.h_kid_states, (void*)h->reg.h_state, (void*)h->reg.h_mm, (void*)h->reg.h_stamps, (void*)h->sc.h_stage, (void*)h->sc.h_many, (void*)h->ldet.h_pass, (void*)h->proj.h_count,
-                     (void*)h->pg.h_sc, (void*)h->sess.h_chunk[0], (void*)h->sess.h_chunk[1] })
+                     (void*)h->pg.h_sc, (void*)h->pgc.h_io, (void*)h->sess.h_chunk[0], (void*)h->sess.h_chunk[1] })
         if (p) (void)hipHostFree(p);
     delete h;                                              // every DevBuf and the key-frame arena go with their owners
     return S2M_OK;

@@ -426,6 +426,7 @@ int advance(s2m_context* h, s2m_pg_result* out)
 
 int s2m::host::pg_host_current(s2m_context* h) { return host_current(h); }
 void s2m::host::pg_pose_to_state(const float pose_xyzrpy[6], double X[12]) { pose_to_state(pose_xyzrpy, X); }
+int s2m::host::pg_device_current(s2m_context* h) { return upload_state(h, 0, pg_n(h)); }
 
 int s2m_pg_reset(s2m_handle h)
 {

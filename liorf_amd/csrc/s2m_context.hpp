@@ -320,6 +320,16 @@ struct __attribute__((visibility("hidden"))) s2m_context {
         double a_launch[12] = { 0 };               // variable n_l - 1 at launch
     } pg;
 
+    // the mutually consistent loops among many candidates (s2m_pg_consistent_loops, s2m_pg_consistency.hpp): buffers of its own, all
+    // grow-only - the chain length and its block sums, the candidate table, the matrix in the caller's and in rank order, ranks |
+    // order | set sizes, the block of the one download (selected | degree | record) - and the pinned block (the table up | that
+    // block down).  It reads pg.est and writes nothing else of the handle.
+    struct PgConsistency {
+        DevBuf s, blk, cand, mat, mat_rank, rank, out;
+        unsigned char* h_io = nullptr;
+        size_t h_io_cap = 0;
+    } pgc;
+
     // saving and loading a session (s2m_abi_session.hip): the segment table of a section on the device, the workgroups' checksum
     // partials, and two pinned chunks that take turns with gmap's two device staging buffers on gmap's copy stream
     struct Session {
@@ -551,6 +561,8 @@ void pg_drop_pending(s2m_context* h, bool destroy);
 int pg_host_current(s2m_context* h);
 // Rot3::RzRyRx(roll, pitch, yaw) and t of a float pose in fp64 with libm, as s2m_pg_set_initial makes an estimate of it
 void pg_pose_to_state(const float pose_xyzrpy[6], double X[12]);
+// pg.est holds the newest estimate of every variable, as an optimise finds it (S2M_ERR_INVALID_ARG: a variable without a value)
+int pg_device_current(s2m_context* h);
 
 // ---- s2m_abi_keyframes.hip ----
 // gmap's copy stream and its two pairs of events exist (the chunked copy-out of the saved map and of a session share them)

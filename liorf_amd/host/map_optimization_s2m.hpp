@@ -909,6 +909,64 @@ public:
         return won;
     }
 
+    // The mutually consistent loops among many candidates (s2m_pg_consistent_loops), between the
+    // verification and the graph: candidates as s2m_pg_add_between would take them against the graph's current estimates;
+    // keep[i] != 0 for the ones kept. The set is the library's stated greedy rule, not the maximum clique; the default
+    // tolerances have not been measured on real data. Nothing is added to the graph. lastConsistency holds the counts.
+    s2m_pg_consistency_result lastConsistency{};
+    std::vector<uint8_t> pgConsistentLoops(const std::vector<int32_t>& key_from, const std::vector<int32_t>& key_to, const std::vector<float>& rel_xyzrpy,
+                                           const s2m_pg_consistency_params* params = nullptr, std::vector<int32_t>* degree = nullptr)
+    {
+        const size_t m = key_from.size();
+        if (key_to.size() != m || rel_xyzrpy.size() != 6 * m) throw std::runtime_error("pgConsistentLoops: one key pair and six floats per candidate");
+        std::vector<uint8_t> keep(m, 0);
+        if (degree) degree->assign(m, 0);
+        check(s2m_pg_consistent_loops(h_, key_from.data(), key_to.data(), rel_xyzrpy.data(), (int32_t)m, params, keep.data(),
+                                      degree ? degree->data() : nullptr, nullptr, &lastConsistency), "s2m_pg_consistent_loops");
+        return keep;
+    }
+    // poseFrom.between(poseTo) of two {x, y, z, roll, pitch, yaw} poses (Rot3::RzRyRx) in fp64, as a float pose vector: what
+    // addLoopFactor hands to s2m_pg_add_between for an accepted s2m_loop_result
+    static void betweenXyzrpy(const float from[6], const float to[6], float rel[6])
+    {
+        auto mat = [](const float p[6], double R[9]) {
+            const double cr = std::cos((double)p[3]), sr = std::sin((double)p[3]), cp = std::cos((double)p[4]), sp = std::sin((double)p[4]);
+            const double cy = std::cos((double)p[5]), sy = std::sin((double)p[5]);
+            R[0] = cy * cp; R[1] = cy * sp * sr - sy * cr; R[2] = sy * sr + cy * sp * cr;
+            R[3] = sy * cp; R[4] = cy * cr + sy * sp * sr; R[5] = sy * sp * cr - cy * sr;
+            R[6] = -sp;     R[7] = cp * sr;                R[8] = cp * cr;
+        };
+        double A[9], B[9], R[9], t[3];
+        mat(from, A);
+        mat(to, B);
+        for (int i = 0; i < 3; i++) {
+            for (int j = 0; j < 3; j++) R[i * 3 + j] = A[i] * B[j] + A[3 + i] * B[3 + j] + A[6 + i] * B[6 + j];
+            t[i] = A[i] * ((double)to[0] - from[0]) + A[3 + i] * ((double)to[1] - from[1]) + A[6 + i] * ((double)to[2] - from[2]);
+        }
+        rel[0] = (float)t[0]; rel[1] = (float)t[1]; rel[2] = (float)t[2];
+        rel[3] = (float)std::atan2(R[7], R[8]);
+        rel[4] = (float)std::asin(std::min(1.0, std::max(-1.0, -R[6])));
+        rel[5] = (float)std::atan2(R[3], R[0]);
+    }
+    // The records of verifySessionLoops / verifySessionLoopsByDistance that pgConsistentLoops keeps, in their order: record r is
+    // the candidate (key_cur, key_pre, pose_from.between(pose_to)). Pass the kept ones on to the graph.
+    std::vector<s2m_loop_result> selectConsistentLoops(const std::vector<s2m_loop_result>& records, const s2m_pg_consistency_params* params = nullptr)
+    {
+        std::vector<int32_t> from, to;
+        std::vector<float> rel(6 * records.size());
+        for (size_t r = 0; r < records.size(); r++) {
+            from.push_back(records[r].key_cur);
+            to.push_back(records[r].key_pre);
+            betweenXyzrpy(records[r].pose_from, records[r].pose_to, rel.data() + 6 * r);
+        }
+        std::vector<s2m_loop_result> kept;
+        if (records.empty()) return kept;
+        const std::vector<uint8_t> keep = pgConsistentLoops(from, to, rel, params);
+        for (size_t r = 0; r < records.size(); r++)
+            if (keep[r]) kept.push_back(records[r]);
+        return kept;
+    }
+
     // void performSCLoopClosure() (:624-730): the ScanContext detector on this handle, then the store's extraction and ICP
     inline bool performSCLoopClosure(SCManagerS2M& scManager);
 

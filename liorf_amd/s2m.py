@@ -67,6 +67,7 @@ ABI_SYMBOLS = [
     "s2m_pg_optimize_launch", "s2m_pg_optimize_poll", "s2m_pg_optimize_collect", "s2m_debug_pg_rebase",
     "s2m_debug_pg_set_estimate", "s2m_debug_pg_linearize", "s2m_debug_pg_apply", "s2m_debug_pg_apply_check_args", "s2m_debug_pg_cg",
     "s2m_debug_pg_retract",
+    "s2m_pg_consistency_default_params", "s2m_pg_consistency_check_args", "s2m_pg_consistent_loops",
     "s2m_session_info_of", "s2m_session_save", "s2m_session_load", "s2m_session_save_file", "s2m_session_load_file", "s2m_session_check",
     "s2m_debug_session_chunk", "s2m_debug_sc_keys", "s2m_debug_kf_frame",
     "s2m_session_append_check_args", "s2m_session_append", "s2m_session_append_file", "s2m_session_place", "s2m_session_appended",
@@ -91,6 +92,7 @@ S2M_PG_PENDING, S2M_PG_IDLE = 2, 3                       # s2m_pg_optimize_launc
 S2M_PG_BLOCK_COLUMNS = 24                                # right-hand sides per pass of the block solve
 S2M_DEBUG_PG_FWD, S2M_DEBUG_PG_BWD, S2M_DEBUG_PG_K, S2M_DEBUG_PG_KT = 0, 1, 2, 3   # operators of s2m_debug_pg_apply
 PG_MARGINALS_KEYS_PER_PASS = S2M_PG_BLOCK_COLUMNS // 6   # keys one pass of s2m_pg_marginals serves
+S2M_PG_CONSISTENCY_MAX = 4096                            # candidates of one s2m_pg_consistent_loops: 64 words of 64 bits per row
 S2M_SC_QUERY_MAX_K = 32
 S2M_SC_ALIGN_SECTOR_KEY, S2M_SC_ALIGN_FULL = 0, 1        # s2m_sc_query_params::align: 7 shifts around the sector-key guess; all 60
 SC_QUERY_MAX_GROUPS = 1024                               # kScQueryMaxGroups: workgroups of the query's distance kernel, 3 keys each per pass
@@ -275,6 +277,19 @@ class PgResult(C.Structure):
     _fields_ = [("iterations", C.c_int32), ("inner_iterations", C.c_int32), ("converged", C.c_int32), ("n_variables", C.c_int32),
                 ("n_factors", C.c_int32), ("reserved", C.c_int32), ("error_before", C.c_double), ("error_after", C.c_double),
                 ("robust_weight_min", C.c_double)]
+
+
+class PgConsistencyParams(C.Structure):
+    """s2m_pg_consistency_params: the tolerances at zero chain length and their growth per metre of chain (translation in metres,
+    rotation as a chord 2 sin(angle / 2)).  The defaults are a starting point that has not been measured on real data."""
+    _fields_ = [("tol_m", C.c_double), ("tol_chord", C.c_double), ("rate_m", C.c_double), ("rate_chord", C.c_double),
+                ("reserved", C.c_int32 * 4)]
+
+
+class PgConsistencyResult(C.Structure):
+    """s2m_pg_consistency_result: the counts, the candidate the winning set was grown from, the set bits of the matrix / 2."""
+    _fields_ = [("n_candidates", C.c_int32), ("n_selected", C.c_int32), ("start", C.c_int32), ("reserved", C.c_int32),
+                ("n_consistent_pairs", C.c_int64)]
 
 
 class PgCgOut(C.Structure):
@@ -526,6 +541,10 @@ def load_library(path: str | None = None) -> C.CDLL:
     L.s2m_pg_marginals_check_args.argtypes = [C.c_int32, i32p, C.c_int32]
     L.s2m_pg_marginals.argtypes = [vp, i32p, C.c_int32, dp]
     L.s2m_pg_joint_marginal.argtypes = [vp, C.c_int32, C.c_int32, dp]
+    L.s2m_pg_consistency_default_params.argtypes = [C.POINTER(PgConsistencyParams)]
+    L.s2m_pg_consistency_check_args.argtypes = [C.c_int32, i32p, i32p, fp, C.c_int32, C.POINTER(PgConsistencyParams)]
+    L.s2m_pg_consistent_loops.argtypes = [vp, i32p, i32p, fp, C.c_int32, C.POINTER(PgConsistencyParams), C.POINTER(C.c_uint8), i32p,
+                                          C.POINTER(C.c_uint64), C.POINTER(PgConsistencyResult)]
     L.s2m_update_initial_guess.argtypes = [C.POINTER(GuessState), C.POINTER(C.c_float), C.c_int, C.POINTER(GuessInfo), C.c_int, C.c_int,
                                            C.POINTER(C.c_float)]
     L.s2m_session_info_of.argtypes = [vp, C.POINTER(SessionInfo)]
@@ -1938,6 +1957,42 @@ class MapOptimizationS2M:
             won += [r[b] for r, b in zip(recs, best) if b >= 0]
         return won
 
+    # -- the mutually consistent loops among many candidates ---------------------------------------
+    def pgConsistentLoops(self, key_from, key_to, rel, params: "PgConsistencyParams | None" = None, matrix: bool = False):
+        """s2m_pg_consistent_loops: candidates as pgAddBetween would take them (key_from[i], key_to[i], rel[i] = the between
+        pose) against the graph's current estimates.  Returns (selected (m,) bool, degree (m,) int32, PgConsistencyResult), and
+        with matrix=True a fourth item, the (m, (m + 63) // 64) uint64 bit rows.  The set is the stated greedy rule's, not the
+        maximum clique; nothing is added to the graph."""
+        kf = np.ascontiguousarray(key_from, np.int32).reshape(-1)
+        kt = np.ascontiguousarray(key_to, np.int32).reshape(-1)
+        r = np.ascontiguousarray(rel, np.float32).reshape(-1, 6)
+        m = len(kf)
+        if len(kt) != m or len(r) != m:
+            raise ValueError("key_from, key_to and rel: one entry per candidate")
+        sel = np.zeros(max(m, 1), np.uint8)
+        deg = np.zeros(max(m, 1), np.int32)
+        mat = np.zeros((max(m, 1), max((m + 63) // 64, 1)), np.uint64) if matrix else None
+        out = PgConsistencyResult()
+        i32p = C.POINTER(C.c_int32)
+        self._check(self.lib.s2m_pg_consistent_loops(self.h, kf.ctypes.data_as(i32p), kt.ctypes.data_as(i32p), _fp(r), m,
+                                                     C.byref(params) if params is not None else None,
+                                                     sel.ctypes.data_as(C.POINTER(C.c_uint8)), deg.ctypes.data_as(i32p),
+                                                     mat.ctypes.data_as(C.POINTER(C.c_uint64)) if matrix else None, C.byref(out)),
+                    "s2m_pg_consistent_loops")
+        res = (sel[:m].astype(bool), deg[:m], out)
+        return res + (mat[:m, :(m + 63) // 64],) if matrix else res
+
+    def selectConsistentLoops(self, records, params: "PgConsistencyParams | None" = None):
+        """The records of verifySessionLoops / verifySessionLoopsByDistance (accepted LoopResults) that pgConsistentLoops keeps,
+        in their order: each record is the candidate (key_cur, key_pre, pose_from.between(pose_to)) that addLoopFactor would
+        add.  Between the verification and the graph: pass the kept ones to addLoopFactor."""
+        records = list(records)
+        if not records:
+            return []
+        rel = np.array([between_xyzrpy(np.array(r.pose_from), np.array(r.pose_to)) for r in records], np.float32)
+        sel, _, _ = self.pgConsistentLoops([r.key_cur for r in records], [r.key_pre for r in records], rel, params)
+        return [r for r, s in zip(records, sel) if s]
+
     def debugLoopDetectPass(self, queries_per_pass: int = 0):
         """s2m_debug_loop_detect_pass: at most this many queries per pass of loopDetectKeys (0: the default)."""
         self._check(self.lib.s2m_debug_loop_detect_pass(self.h, int(queries_per_pass)), "s2m_debug_loop_detect_pass")
@@ -2147,6 +2202,32 @@ def pg_check_args(kind: int, n_variables: int, key_a: int, key_b: int, values, v
     w = None if var is None else np.ascontiguousarray(var, np.float64)
     return load_library().s2m_pg_check_args(kind, n_variables, key_a, key_b, None if v is None else _fp(v),
                                             None if w is None else _dp(w), float(robust_k))
+
+
+def default_pg_consistency_params(**kw) -> PgConsistencyParams:
+    """s2m_pg_consistency_default_params; keyword arguments set fields."""
+    p = PgConsistencyParams()
+    rc = load_library().s2m_pg_consistency_default_params(C.byref(p))
+    if rc != S2M_OK:
+        raise S2MError(rc, "s2m_pg_consistency_default_params")
+    for k, v in kw.items():
+        if not hasattr(p, k):
+            raise AttributeError(k)
+        setattr(p, k, v)
+    return p
+
+
+def pg_consistency_check_args(n_variables: int, key_from, key_to, rel, params: "PgConsistencyParams | None" = None, m=None) -> int:
+    """s2m_pg_consistency_check_args (host only, no GPU): the status code.  None for an array passes a null pointer; m defaults
+    to len(key_from); params=None passes a null pointer (the defaults)."""
+    kf = None if key_from is None else np.ascontiguousarray(key_from, np.int32).reshape(-1)
+    kt = None if key_to is None else np.ascontiguousarray(key_to, np.int32).reshape(-1)
+    r = None if rel is None else np.ascontiguousarray(rel, np.float32).reshape(-1)
+    mm = m if m is not None else (0 if kf is None else len(kf))
+    i32p = C.POINTER(C.c_int32)
+    return load_library().s2m_pg_consistency_check_args(n_variables, None if kf is None else kf.ctypes.data_as(i32p),
+                                                        None if kt is None else kt.ctypes.data_as(i32p), None if r is None else _fp(r),
+                                                        mm, None if params is None else C.byref(params))
 
 
 def pg_rebase(a_launch, a_now, X) -> np.ndarray:

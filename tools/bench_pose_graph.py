@@ -29,6 +29,13 @@ session, for the same one optimise after one added loop (medians of --reps runs 
   registration_ms        (d) a 12 000 x 30 000 registration (set_scan + optimize) alone and with the optimise pending
 
   python tools/bench_pose_graph.py --async --sizes 2000,10000 --out profiles/pose_graph_async_bench_line.json
+
+--consistency times s2m_pg_consistent_loops, the whole C call from the host arrays to the selection, at
+64, 512 and 4096 candidates on the dead-reckoned estimates of the figure-of-eight at 10 000 keys (median and minimum of --reps
+calls after a warm-up call), beside the NumPy model of the same call in the same process (model_ms, one run) and whether the two
+agree (equals_model):
+
+  python tools/bench_pose_graph.py --consistency --reps 7 --out profiles/pg_consistency_bench_line.json
 """
 import argparse
 import ctypes as C
@@ -221,6 +228,53 @@ def async_one_size(n, reps, poll_us, scans):
         m.close()
 
 
+def consistency_sizes(n, ms, reps):
+    """s2m_pg_consistent_loops, the whole C call, on the dead-reckoned estimates of the figure-of-eight at n keys: m candidates,
+    three in four true loops from second-lap keys to their first-lap keys (ground truth plus the loops' noise), one in four a
+    false loop between two unrelated keys; beside it the NumPy model (tests/ref/pg_consistency_ref.py) in the same process."""
+    import pg_consistency_ref as R
+    g = P.figure_eight(n, 0)
+    truth = P.figure_eight(n, 0, truth_only=True)
+    half = n // 2
+    X = R.states_of(g.X)
+    gpu = s2m.MapOptimizationS2M()
+    out = {}
+    try:
+        gpu.pgReset()
+        for k, x in enumerate(X):
+            gpu.pgSetEstimate(k, x[:9], x[9:])
+        for m in ms:
+            rng = np.random.default_rng(P.SEED + m)
+            kf = np.sort(rng.choice(np.arange(half, n), m, replace=False)).astype(np.int32)
+            kt = (kf - half).astype(np.int32)
+            false = rng.random(m) < 0.25
+            kt[false] = ((kt[false] + rng.integers(half // 8, half - half // 8, int(false.sum()))) % half).astype(np.int32)
+            rel = np.empty((m, 6), np.float32)
+            for c in range(m):
+                a, b = truth[kf[c]], truth[kf[c] - half]                     # a false loop claims the true relation for another key
+                Rz = a[0].T @ b[0] @ P.so3_exp(rng.normal(0.0, 5e-3, 3))
+                rel[c] = P.xyzrpy_from_pose(Rz, a[0].T @ (b[1] - a[1]) + rng.normal(0.0, 0.03, 3)).astype(np.float32)
+            t = []
+            for rep in range(reps + 1):                                    # the first call is the warm-up (it sizes the buffers)
+                t0 = time.perf_counter()
+                sel, deg, rec = gpu.pgConsistentLoops(kf, kt, rel)
+                if rep > 0:
+                    t.append(time.perf_counter() - t0)
+            t0 = time.perf_counter()
+            want = R.run(X, kf, kt, rel)
+            model_s = time.perf_counter() - t0
+            same = bool(np.array_equal(sel, want["selected"]) and np.array_equal(deg, want["degree"]) and rec.start == want["start"] and
+                        rec.n_consistent_pairs == want["n_consistent_pairs"])
+            out[str(m)] = dict(call_ms=round(1e3 * float(np.median(t)), 4), call_min_ms=round(1e3 * float(np.min(t)), 4),
+                               model_ms=round(1e3 * model_s, 1), n_selected=int(rec.n_selected), n_true=int((~false).sum()),
+                               true_selected=int((sel & ~false).sum()), false_selected=int((sel & false).sum()),
+                               n_consistent_pairs=int(rec.n_consistent_pairs), equals_model=same, reps=reps)
+            print(m, json.dumps(out[str(m)]), file=sys.stderr, flush=True)
+    finally:
+        gpu.close()
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--sizes", default="2000,10000,50000")
@@ -229,7 +283,20 @@ def main():
     ap.add_argument("--marginals", action="store_true", help="time the covariance read-out instead of the optimise")
     ap.add_argument("--async", dest="run_async", action="store_true", help="time the launched optimise against the synchronous call")
     ap.add_argument("--poll-us", type=float, default=200.0, help="--async: sleep between two polls")
+    ap.add_argument("--consistency", action="store_true", help="time s2m_pg_consistent_loops beside its NumPy model")
+    ap.add_argument("--candidates", default="64,512,4096", help="--consistency: the candidate counts")
+    ap.add_argument("--keys", type=int, default=10000, help="--consistency: keys of the figure-of-eight")
     a = ap.parse_args()
+    if a.consistency:
+        line = {"workload": "figure-of-eight driven twice, dead-reckoned estimates, %d keys; loop candidates, three in four true, default "
+                            "tolerances; the whole s2m_pg_consistent_loops call and the NumPy model (seed %d)" % (a.keys, P.SEED),
+                "keys": a.keys, "candidates": consistency_sizes(a.keys, [int(x) for x in a.candidates.split(",")], a.reps)}
+        txt = json.dumps(line)
+        print(txt)
+        if a.out:
+            with open(a.out, "w") as f:
+                f.write(txt + "\n")
+        return
     if a.run_async:
         cfgs = [synth.make_config("small", scan_index=k) for k in range(4)]
         scans = (synth.to_xyzi(cfgs[0]["map"]), [(synth.to_xyzi(c["scan"]), c["pose_init"]) for c in cfgs])
