@@ -3,30 +3,30 @@ the joint marginal's off-diagonal blocks and the bound the device is held to, 10
 
     python tests/golden/make_golden_pose_graph_marginals.py
 
-As make_golden_pose_graph.py: the graph is optimised by the dense square-root reference; the reference joint covariance is
-the 12x12 sub-block of the dense inverse of J^T J; the floor is its gap to the same block from the SVD of J, per 3x3 block
-type (rr, rt, tr, tt) of the two off-diagonal 6x6 blocks, each relative to that block's norm; the factor 10 is the project's
-margin for differing summation orders.  The diagonal 6x6 blocks need no bound: the device returns s2m_pg_marginal's bits there.
+As make_golden_pose_graph.py: the graph is optimised by the dense square-root reference; the reference joint covariance is the
+12x12 block of V diag(s^-2) V^T from the SVD of J; the floor is the larger gap to it of the QR of J and of the chain route (the
+CPU model of the device's solve; tests/ref/pose_graph_cov_ref.py), per 3x3 block type (rr, rt, tr, tt) of the two off-diagonal
+6x6 blocks, each 3x3 block relative to its own norm; the factor 10 is the project's margin for differing summation orders.
+Where the chain route lies more than 10 times farther from the SVD than the QR does, its gap is its own error and does not count
+(pose_graph_cov_ref.floors; recorded under "chain_route_left_out"): gps_120's tt, 2.2e-7 of Woodbury's cancellation at the key
+the GPS factor pins, against 2e-11 for the QR and 6e-12 for the device.  None
+of the three routes forms J^T J, whose fp64 inverse - the reference before - left rt and tr floors of 0.2 to 1.0, bounds above 1
+that a zero block passed, and a tt bound of 6 %.  The diagonal 6x6 blocks need no bound here: the device returns
+s2m_pg_marginal's bits there, which tests/test_pose_graph_gpu.py and tests/test_pose_graph_cov_gpu.py hold.
 
-Which blocks are informative.  J^T J has an eigenvalue of 1e-8 (the prior's translation weight), and its dense inverse
-carries the noise of that in the small rotation-translation covariances, as marginal_rt does in pose_graph_bounds.json.
-The floors written by this script:
-  loops_200 (10, 150): rr 6e-8 and tt 0.6 % - informative; rt 0.23, tr 0.29 - bounds above 1, which say little.
-  loops_200 (0, 199):  rr 6e-8 and tt 0.6 % - informative; rt and tr 1.0 - the two references share no digit there
-      (key 0 is held by the prior, its rotation hardly correlates with key 199's translation), the bound of 10 says nothing.
-  gps_120 (60, 119):   rr 3e-8 and tt 2e-9 - informative; rt 0.18, tr 0.33 - bounds above 1 again.
-So every case checks the rotation-rotation and translation-translation cross blocks sharply and the mixed ones loosely.
+Blocks that are zero to rounding are held relative to their scale, sqrt(|rr| |tt|) of the two keys' own blocks, under
+"held_floor" / "held_bound": in loops_200 (0, 199) key 199's rotation against key 0's translation (the prior leaves it free and
+no rotation moves it), in gps_120 (60, 119) key 119's rotation against key 60's translation (the GPS factor pins it).
 The bounds are not tightened by hand.
 """
 import json
 import os
 import sys
 
-import numpy as np  # noqa: F401
-
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.join(HERE, "..", "ref"))
 import pose_graph_cases as CS  # noqa: E402
+import pose_graph_cov_ref as V  # noqa: E402
 import pose_graph_marginals_ref as M  # noqa: E402
 import pose_graph_ref as P  # noqa: E402
 
@@ -38,9 +38,14 @@ def main():
             graphs[name] = CS.build(name)
             P.optimize(graphs[name], "dense_sqrt")
         g = graphs[name]
-        floor = M.cross_gaps(M.joint_svd(g, a, b), M.joint_dense(g, a, b))
-        out[M.case_id(name, a, b)] = dict(keys=[a, b], floor=floor, bound={k: 10 * v for k, v in floor.items()})
-        print(M.case_id(name, a, b), json.dumps(floor))
+        want = M.joint_svd(g, a, b)
+        both, left_out = V.floors({r: M.cross_gaps(f(g, [a, b]), want) for r, f in (("qr", V.cov_qr), ("chain", V.cov_chain))})
+        floor = {k: v for k, v in both.items() if not k.endswith("_held")}
+        held = {k: v for k, v in both.items() if k.endswith("_held")}
+        out[M.case_id(name, a, b)] = dict(keys=[a, b], floor=floor, bound={k: V.MARGIN * v for k, v in floor.items()},
+                                          held_floor=held, held_bound={k: V.MARGIN * v for k, v in held.items()},
+                                          chain_route_left_out=left_out)
+        print(M.case_id(name, a, b), json.dumps(both), "chain route left out:", json.dumps(left_out))
     with open(os.path.join(HERE, "pose_graph_marginals_bounds.json"), "w") as f:
         json.dump(out, f, indent=1, sort_keys=True)
         f.write("\n")

@@ -33,6 +33,11 @@ def build(name):
     raise KeyError(name)
 
 
+def marginal_keys(n):
+    """The keys whose marginals the small graphs are held on: the last (the one a node reads), the middle, and key 32."""
+    return [n - 1, n // 2, 32]
+
+
 def quanta(poses):
     """Rounding of a float pose vector: (rotation, translation) sizes of one ulp at the largest magnitude."""
     return Q32 * np.pi, Q32 * float(np.abs(np.asarray(poses)[:, :3]).max())

@@ -319,7 +319,10 @@ def optimize(g, solver="dense_sqrt", max_iterations=MAX_ITERATIONS, rel_tol=REL_
 
 
 def marginal(g, key, X=None):
-    """Covariance of `key` in its tangent (rotation, translation): dense inverse of J^T J at X."""
+    """Covariance of `key` in its tangent (rotation, translation): dense inverse of J^T J at X.  With the first prior's
+    translation variance of 1e8, J^T J has a condition number of 1e16: the rotation block is good to 6e-8, the translation block
+    to 0.5 % and the mixed blocks to 10-50 % of their norm.  Good for magnitudes and for graphs without that prior; the device
+    is held to pose_graph_cov_ref's routes, which do not square J."""
     X = g.X if X is None else X
     J, _ = assemble(linearize(g, X)[0], g.n)
     H = (J.T @ J).toarray()

@@ -1,6 +1,7 @@
 """GPU tests of the pose graph (include/liorf_s2m.h, "Pose graph"; reference src/mapOptmization.cpp:1386-1642) against
 the CPU reference tests/ref/pose_graph_ref.py.  Bounds: tests/golden/pose_graph_bounds.json, written by
-tests/golden/make_golden_pose_graph.py (10 x the disagreement of two CPU solves)."""
+tests/golden/make_golden_pose_graph.py (10 x the disagreement of two CPU solves; for the marginals, of the QR and the chain
+route of tests/ref/pose_graph_cov_ref.py with the SVD of J - none of them squares J)."""
 import ctypes as C
 import json
 import os
@@ -12,6 +13,7 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tests", "ref"))
 import pose_graph_cases as CS  # noqa: E402
+import pose_graph_cov_ref as V  # noqa: E402
 import pose_graph_ref as P  # noqa: E402
 from liorf_amd import s2m, synth  # noqa: E402
 
@@ -50,7 +52,8 @@ def _check_error(name, got, want):
 def test_small_graph_matches_the_dense_square_root_reference(gpu, name):
     g = CS.build(name)
     res, poses = _solve_on_device(gpu, g)
-    cov = gpu.pgMarginal(g.n - 1)
+    mkeys = CS.marginal_keys(g.n)
+    covs = [gpu.pgMarginal(k) for k in mkeys]
     ref = P.optimize(g, "dense_sqrt")
     want = CS.to_f32(g.poses())
     b = BOUNDS[name]["bound"]
@@ -68,18 +71,19 @@ def test_small_graph_matches_the_dense_square_root_reference(gpu, name):
         assert res.robust_weight_min < 0.05 and abs(res.robust_weight_min - ref.robust_weight_min) <= 1e-6 * ref.robust_weight_min
     else:
         assert res.robust_weight_min == 1.0
-    # (d) the last key's marginal against the dense inverse
-    want_cov = P.marginal(g, g.n - 1)
-    r3, t3 = slice(0, 3), slice(3, 6)
-    for blk, ra, rb in (("rr", r3, r3), ("rt", r3, t3), ("tt", t3, t3)):
-        gap = float(np.linalg.norm(cov[ra, rb] - want_cov[ra, rb]) / np.linalg.norm(want_cov[ra, rb]))
-        print(name, "marginal", blk, "gap", gap, "bound", b["marginal_" + blk])
-        assert gap <= b["marginal_" + blk]
-    assert np.allclose(cov, cov.T, rtol=1e-6, atol=1e-9 * np.abs(cov).max())
+    # (d) the marginals of the last key, the middle key and key 32 against the SVD of J, values and symmetry per 3x3 block type
+    mb = {k[len("marginal_"):]: v for k, v in b.items() if k.startswith("marginal_")}
+    want_cov = V.cov_svd(g, mkeys)
+    for k, cov in zip(mkeys, covs):
+        want = V.sub(want_cov, mkeys, [k])
+        gaps, sym = V.block_gaps(cov, want), V.symmetry_gaps(cov, want)
+        print(name, "marginal of key", k, "gaps", V.worst(gaps), "symmetry", V.worst(sym), "bounds", mb)
+        assert not V.within(gaps, mb), k
+        assert not V.within(sym, mb), k
     # a second run of the same case is bitwise the first
     res2, poses2 = _solve_on_device(gpu, CS.build(name))
     assert _res_tuple(res) == _res_tuple(res2) and np.array_equal(poses, poses2)
-    assert np.array_equal(cov, gpu.pgMarginal(g.n - 1))
+    assert np.array_equal(covs[0], gpu.pgMarginal(g.n - 1))
 
 
 # ---- (b) 2 000 and 10 000 keys ----------------------------------------------------------------------------------
