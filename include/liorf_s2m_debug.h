@@ -313,6 +313,40 @@ int  s2m_debug_sc_ring_last(s2m_handle h, int32_t* passes, size_t* scratch_bytes
 int  s2m_debug_icp_align_pairs_device(s2m_handle h, const void* const* srcs, const size_t* n_srcs, const void* const* tgts,
                                       const size_t* n_tgts, int32_t n_pairs, size_t stride_bytes, const float* const* guesses,
                                       const s2m_icp_params* p, s2m_icp_result* out);
+/* Observation hook: the close of one ICP iteration on the device (k_icp_close: Umeyama, the composition of T, PCL's convergence
+ * state machine - liorf_amd/csrc/s2m_icp_close.hpp, the source the host loop runs too). No kernel exists for the hook: the
+ * n <= S2M_LOOP_MANY_MAX_PAIRS state blocks of the table form take sums[17 k ..] (count, sum d2, sum src 3, sum tgt 3, sum tgt
+ * src^T 9 row-major) and the state in[k], k_icp_close is launched once over all of them as an iteration launches it, out[k] is the
+ * state it left. p: max_iterations, transformation_epsilon and euclidean_fitness_epsilon are read (NULL = defaults). A state that
+ * comes in done comes back untouched. S2M_ERR_BUSY while a launched closure is pending; afterwards the handle is in the
+ * state of one that never saw the hook (every alignment lays its blocks out anew). s2m_debug_icp_close_check_args: the
+ * argument checks on their own (host code, no handle, no GPU). */
+typedef struct s2m_debug_icp_state {
+    float   T[16];          /* final_transformation_ so far, row-major */
+    float   T_step[16];     /* transformation_ of the iteration closed last */
+    double  prev_mse;       /* correspondences_prev_mse_ */
+    int32_t it, conv, similar, done;
+} s2m_debug_icp_state;
+int  s2m_debug_icp_close_check_args(int32_t n, const double* sums, const s2m_debug_icp_state* in, const s2m_icp_params* p,
+                                    const s2m_debug_icp_state* out);
+int  s2m_debug_icp_close(s2m_handle h, int32_t n, const double* sums, const s2m_debug_icp_state* in, const s2m_icp_params* p /* NULL = defaults */,
+                         s2m_debug_icp_state* out);
+/* Observation hook: the 17 sums of iteration 0 of n_pairs alignments of host clouds, staged as s2m_debug_icp_align_pairs_device
+ * stages them. form S2M_DEBUG_ICP_SUMS_SLOTS: one source (srcs[k] == srcs[0], n_srcs[k] == n_srcs[0]) against n_pairs <=
+ * S2M_LOOP_MAX_CANDIDATES targets, laid out, loaded and prepared as the slotted device loop begins; S2M_DEBUG_ICP_SUMS_TABLE:
+ * n_pairs <= S2M_LOOP_MANY_MAX_PAIRS pairs as the table form begins. Then one search, k_icp_sums_dev and k_icp_fold_dev exactly as
+ * the first iteration queues them - no close, no transform, no guess. Every cloud is non-empty. sums: n_pairs x 17 folded sums
+ * (layout as s2m_debug_icp_close takes them) of the correspondences with d2 <= max_correspondence_distance^2; n_rows[k]: the
+ * partial rows of alignment k, min(ceil(n_src / 256), 256); parts, keys: NULL, or per alignment NULL or room for 256 x 17 partial
+ * sums (n_rows[k] rows are written, in the order they are folded) and for the n_srcs[k] keys of the search (s2m_debug_icp_nearest).
+ * S2M_ERR_BUSY while a launched closure is pending. s2m_debug_icp_sums_check_args: the argument checks on their own. */
+#define S2M_DEBUG_ICP_SUMS_SLOTS 0
+#define S2M_DEBUG_ICP_SUMS_TABLE 1
+int  s2m_debug_icp_sums_check_args(const void* const* srcs, const size_t* n_srcs, const void* const* tgts, const size_t* n_tgts, int32_t n_pairs,
+                                   size_t stride_bytes, int32_t form, const double* sums, const int32_t* n_rows);
+int  s2m_debug_icp_sums(s2m_handle h, const void* const* srcs, const size_t* n_srcs, const void* const* tgts, const size_t* n_tgts, int32_t n_pairs,
+                        size_t stride_bytes, int32_t form, double max_correspondence_distance, double* sums, int32_t* n_rows,
+                        double* const* parts, uint64_t* const* keys);
 /* s2m_loop_verify_many: the pairs of a pass for the calls that follow (0: the default, S2M_LOOP_MANY_MAX_PAIRS; other values are
  * clamped to [S2M_LOOP_MAX_CANDIDATES, S2M_LOOP_MANY_MAX_PAIRS]); what the last call did - its passes, the pairs it aligned, and
  * the bytes the handle holds for the submaps of a pass; and the plan on its own (host only, no handle): first_row_of_pass takes

@@ -1166,3 +1166,89 @@ int s2m_debug_icp_grid(s2m_handle h, const void* const* tgts, const size_t* n_tg
     }
     return S2M_OK;
 }
+
+// ---- the close and the sums of an ICP iteration on their own (tests/test_icp_close_gpu.py) ------------------------------------
+
+int s2m_debug_icp_close_check_args(int32_t n, const double* sums, const s2m_debug_icp_state* in, const s2m_icp_params* p, const s2m_debug_icp_state* out)
+{
+    if (n < 1 || n > S2M_LOOP_MANY_MAX_PAIRS || !sums || !in || !out) return S2M_ERR_INVALID_ARG;
+    if (p && (!(p->max_correspondence_distance > 0.0) || p->max_iterations < 1)) return S2M_ERR_INVALID_ARG;
+    return S2M_OK;
+}
+
+int s2m_debug_icp_close(s2m_handle h, int32_t n, const double* sums, const s2m_debug_icp_state* in, const s2m_icp_params* p, s2m_debug_icp_state* out)
+{
+    static_assert(sizeof(s2m_debug_icp_state) == sizeof(IcpLoopState) && offsetof(s2m_debug_icp_state, prev_mse) == offsetof(IcpLoopState, prev_mse) &&
+                  offsetof(s2m_debug_icp_state, done) == offsetof(IcpLoopState, done), "handed over in place");
+    static_assert(S2M_LOOP_MANY_MAX_PAIRS == kIcpMaxPairs, "a block per pair of the table");
+    if (!h) return S2M_ERR_INVALID_ARG;
+    int rc = s2m_debug_icp_close_check_args(n, sums, in, p, out);
+    if (rc) return fail(h, rc, "close: 1 .. S2M_LOOP_MANY_MAX_PAIRS rows of sums and states, valid ICP parameters");
+    IcpParams ip;
+    if ((rc = icp_params_in(h, p, &ip)) || (rc = debug_stage(h, nullptr, 0, nullptr, 0, 16))) return rc;     // (BUSY, the loop stream)
+    const hipError_t e = icp_dev_close(h->loop.icp, h->loop.stream, n, sums, reinterpret_cast<const IcpLoopState*>(in), ip,
+                                       reinterpret_cast<IcpLoopState*>(out));
+    if (e != hipSuccess) {
+        (void)hipStreamSynchronize(h->loop.stream);
+        return fail(h, S2M_ERR_HIP, "ICP close", e);
+    }
+    return S2M_OK;
+}
+
+int s2m_debug_icp_sums_check_args(const void* const* srcs, const size_t* n_srcs, const void* const* tgts, const size_t* n_tgts, int32_t n_pairs,
+                                  size_t stride_bytes, int32_t form, const double* sums, const int32_t* n_rows)
+{
+    if (form != S2M_DEBUG_ICP_SUMS_SLOTS && form != S2M_DEBUG_ICP_SUMS_TABLE) return S2M_ERR_INVALID_ARG;
+    if (!srcs || !n_srcs || !tgts || !n_tgts || !sums || !n_rows) return S2M_ERR_INVALID_ARG;
+    if (n_pairs < 1 || n_pairs > (form == S2M_DEBUG_ICP_SUMS_TABLE ? S2M_LOOP_MANY_MAX_PAIRS : S2M_LOOP_MAX_CANDIDATES)) return S2M_ERR_INVALID_ARG;
+    if (stride_bytes < 12 || (stride_bytes & 3)) return S2M_ERR_INVALID_ARG;
+    for (int32_t k = 0; k < n_pairs; k++) {
+        if (!srcs[k] || !tgts[k] || n_srcs[k] == 0 || n_tgts[k] == 0) return S2M_ERR_INVALID_ARG;
+        if ((reinterpret_cast<uintptr_t>(srcs[k]) & 3) != 0 || (reinterpret_cast<uintptr_t>(tgts[k]) & 3) != 0) return S2M_ERR_INVALID_ARG;
+        if (n_srcs[k] > (size_t)0x3fffffff || n_tgts[k] > (size_t)0x3fffffff) return S2M_ERR_CAPACITY;
+        if (form == S2M_DEBUG_ICP_SUMS_SLOTS && (srcs[k] != srcs[0] || n_srcs[k] != n_srcs[0])) return S2M_ERR_INVALID_ARG;
+    }
+    return S2M_OK;
+}
+
+int s2m_debug_icp_sums(s2m_handle h, const void* const* srcs, const size_t* n_srcs, const void* const* tgts, const size_t* n_tgts, int32_t n_pairs,
+                       size_t stride_bytes, int32_t form, double max_correspondence_distance, double* sums, int32_t* n_rows,
+                       double* const* parts, uint64_t* const* keys)
+{
+    static_assert(S2M_LOOP_MAX_CANDIDATES == kIcpMaxSlots && sizeof(int32_t) == sizeof(int), "a slot per target; n_rows filled in place");
+    if (!h) return S2M_ERR_INVALID_ARG;
+    int rc = s2m_debug_icp_sums_check_args(srcs, n_srcs, tgts, n_tgts, n_pairs, stride_bytes, form, sums, n_rows);
+    if (rc) return fail(h, rc, "sums: non-empty clouds of 4-byte aligned records, 1 .. 8 targets of one source (slots) or 1 .. 64 pairs (table)");
+    if (!(max_correspondence_distance > 0.0)) return fail(h, S2M_ERR_INVALID_ARG, "ICP needs a positive correspondence distance");
+    if ((rc = debug_stage(h, nullptr, 0, nullptr, 0, stride_bytes))) return rc;                  // (BUSY, the loop stream)
+    const bool table = form == S2M_DEBUG_ICP_SUMS_TABLE;
+    s2m_context::LoopClosure& L = h->loop;
+    const unsigned char *d_src[kIcpMaxPairs], *d_tgt[kIcpMaxPairs];
+    const auto room = [&](size_t n) { return (n * stride_bytes + 255) / 256 * 256; };
+    size_t total = 0;
+    for (int32_t k = 0; k < n_pairs; k++) total += (table || k == 0 ? room(n_srcs[k]) : 0) + room(n_tgts[k]);
+    L.many_used = 0;
+    if ((rc = arena_reserve(h, L.stream, total))) return rc;
+    unsigned char* at = L.many_arena.as<unsigned char>();
+    for (int32_t k = 0; k < n_pairs; k++) {
+        if (table || k == 0) {
+            S2M_HIP(h, hipMemcpyAsync(at, srcs[k], n_srcs[k] * stride_bytes, hipMemcpyHostToDevice, L.stream));
+            d_src[k] = at;
+            at += room(n_srcs[k]);
+        } else {
+            d_src[k] = d_src[0];
+        }
+        S2M_HIP(h, hipMemcpyAsync(at, tgts[k], n_tgts[k] * stride_bytes, hipMemcpyHostToDevice, L.stream));
+        d_tgt[k] = at;
+        at += room(n_tgts[k]);
+    }
+    s2m_loop_params lp;
+    s2m_loop_default_params(&lp);
+    const hipError_t e = icp_dev_sums(L.icp, L.stream, table, d_src, n_srcs, d_tgt, n_tgts, n_pairs, stride_bytes, max_correspondence_distance,
+                                      loop_tuning(h, lp.icp_leaf), sums, n_rows, parts, reinterpret_cast<unsigned long long* const*>(keys));
+    if (e != hipSuccess) {
+        (void)hipStreamSynchronize(L.stream);
+        return fail(h, S2M_ERR_HIP, "ICP sums", e);
+    }
+    return S2M_OK;
+}

@@ -1248,6 +1248,71 @@ hipError_t icp_dev_grid(IcpWorkspace* w, hipStream_t stream, const unsigned char
     return hipStreamSynchronize(stream);
 }
 
+hipError_t icp_dev_close(IcpWorkspace* w, hipStream_t stream, int n, const double* sums, const IcpLoopState* in, const IcpParams& prm,
+                         IcpLoopState* out)
+{
+    if (w->fl.phase != 0 || n < 1 || n > kIcpMaxPairs || prm.max_iter < 1) return hipErrorInvalidValue;
+    ICP_TRY(pairs_room(w));
+    for (int k = 0; k < n; k++) {                                         // a table of blocks: the close reads nothing else of a view
+        IcpView v{};
+        v.blk = w->blk.as<IcpDevBlock>() + k;
+        w->h_tab[k] = v;
+        IcpDevBlock b{};
+        b.st = in[k];
+        memcpy(b.sums, sums + 17 * (size_t)k, sizeof(b.sums));
+        w->h_blk[k] = b;
+    }
+    w->P = IcpPairs{ w->tab.as<IcpView>() };
+    w->K = n;
+    ICP_TRY(pairs_upload(w, stream));
+    ICP_TRY(hipMemcpyAsync(w->blk.p, w->h_blk, sizeof(IcpDevBlock) * (size_t)n, hipMemcpyHostToDevice, stream));
+    hipLaunchKernelGGL(k_icp_close<IcpPairs>, dim3(1, 1, n), dim3(64), 0, stream, w->P, icp_close_params(prm.max_iter, prm.trans_eps, prm.fit_eps));
+    ICP_TRY(hipGetLastError());
+    ICP_TRY(hipMemcpyAsync(w->h_blk, w->blk.p, sizeof(IcpDevBlock) * (size_t)n, hipMemcpyDeviceToHost, stream));
+    ICP_TRY(hipStreamSynchronize(stream));
+    for (int k = 0; k < n; k++) out[k] = w->h_blk[k].st;
+    return hipSuccess;
+}
+
+hipError_t icp_dev_sums(IcpWorkspace* w, hipStream_t stream, bool table, const unsigned char* const* d_src, const size_t* n_src,
+                        const unsigned char* const* d_tgt, const size_t* n_tgt, int n, size_t stride, double max_corr_dist,
+                        const IcpTuning& tune, double* sums, int* n_rows, double* const* parts, unsigned long long* const* keys)
+{
+    if (w->fl.phase != 0 || n < 1 || n > (table ? kIcpMaxPairs : kIcpMaxSlots)) return hipErrorInvalidValue;
+    for (int k = 0; k < n; k++) if (n_src[table ? k : 0] == 0 || n_tgt[k] == 0) return hipErrorInvalidValue;
+    const double max_d2 = max_corr_dist * max_corr_dist;
+    if (table) {                                                          // icp_pairs_begin up to its first range
+        ICP_TRY(pairs_layout(w, n, d_src, n_src, d_tgt, n_tgt, tune, nullptr));
+        ICP_TRY(pairs_upload(w, stream));
+        ICP_TRY(load_pairs(w, stream, stride, 2));
+        ICP_TRY(load_pairs(w, stream, stride, 0));
+        ICP_TRY(dev_prepare_v(w, stream, tune, w->P, IcpPairGuesses{ 0 }));
+        ICP_TRY(dev_nearest_v(w, stream, tune, 0, w->P));
+        ICP_TRY(dev_sums_v(w, stream, max_d2, 0, w->P));
+    } else {                                                              // icp_dev_begin up to its first range
+        ICP_TRY(dev_layout(w, n, n_src[0], n_tgt, &tune));
+        set_guesses(w, nullptr);
+        ICP_TRY(load_slots(w, stream, d_src[0], nullptr, stride, true));
+        ICP_TRY(load_slots(w, stream, nullptr, d_tgt, stride));
+        ICP_TRY(dev_prepare(w, stream, tune));
+        ICP_TRY(dev_nearest(w, stream, tune, 0));
+        ICP_TRY(dev_sums(w, stream, max_d2, 0));
+    }
+    ICP_TRY(hipMemcpyAsync(w->h_blk, w->blk.p, sizeof(IcpDevBlock) * (size_t)n, hipMemcpyDeviceToHost, stream));
+    for (int k = 0; k < n; k++) {
+        const int rows = table ? w->h_tab[k].rows : w->rows_max;
+        const size_t ns = n_src[table ? k : 0];
+        n_rows[k] = rows;
+        if (parts && parts[k])
+            ICP_TRY(hipMemcpyAsync(parts[k], table ? w->h_tab[k].part : w->S.part[k], sizeof(double) * 17 * (size_t)rows, hipMemcpyDeviceToHost, stream));
+        if (keys && keys[k])
+            ICP_TRY(hipMemcpyAsync(keys[k], table ? w->h_tab[k].best : w->S.best[k], sizeof(unsigned long long) * ns, hipMemcpyDeviceToHost, stream));
+    }
+    ICP_TRY(hipStreamSynchronize(stream));
+    for (int k = 0; k < n; k++) memcpy(sums + 17 * (size_t)k, w->h_blk[k].sums, sizeof(double) * 17);
+    return hipSuccess;
+}
+
 hipError_t icp_align(IcpWorkspace* w, hipStream_t stream, const unsigned char* d_src, size_t n_src_, const unsigned char* d_tgt,
                      size_t n_tgt_, size_t stride, const IcpParams& prm, IcpResult* res, const float* guess)
 {

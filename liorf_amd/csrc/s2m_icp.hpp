@@ -7,6 +7,8 @@
 #include <cstddef>
 #include <cstdint>
 
+#include "s2m_icp_close.hpp"
+
 namespace s2m {
 
 struct IcpWorkspace;
@@ -91,5 +93,19 @@ constexpr int kIcpGridMaxCells = 1 << 18;
 struct IcpGridInfo { float lo[3]; float cell, inv; int n[3]; int n_fin; int usable; };
 hipError_t icp_dev_grid(IcpWorkspace* w, hipStream_t stream, const unsigned char* const* d_tgt, const size_t* n_tgt, int n_slots, size_t stride,
                         const IcpTuning& tune, IcpGridInfo* info, int* const* cell_start, int* const* cell_end, int* const* order);
+
+// the close of one iteration on the device, synchronously: n <= kIcpMaxPairs blocks of the table form take sums[17 k ..] and
+// the state in[k], k_icp_close runs once over all of them (the loop's own launch), out[k] is the state it left. A state that
+// comes in done comes back as it was.
+hipError_t icp_dev_close(IcpWorkspace* w, hipStream_t stream, int n, const double* sums, const IcpLoopState* in, const IcpParams& prm,
+                         IcpLoopState* out);
+// the sums of iteration 0 of n alignments, synchronously: the layout, the loads and the preparation of icp_dev_begin (table ==
+// false: one source d_src[0] of n_src[0] points against n <= kIcpMaxSlots targets) or of icp_pairs_begin (table: n <=
+// kIcpMaxPairs pairs), then one search, k_icp_sums_dev and k_icp_fold_dev as the first range queues them - no close, no
+// transform. sums: n x 17 folded sums; n_rows[k]: the partial rows of alignment k; parts, keys: null, or per alignment null or
+// room for 17 * 256 partial sums (n_rows[k] rows are written) and for the n_src keys of the search.
+hipError_t icp_dev_sums(IcpWorkspace* w, hipStream_t stream, bool table, const unsigned char* const* d_src, const size_t* n_src,
+                        const unsigned char* const* d_tgt, const size_t* n_tgt, int n, size_t stride, double max_corr_dist,
+                        const IcpTuning& tune, double* sums, int* n_rows, double* const* parts, unsigned long long* const* keys);
 
 }  // namespace s2m

@@ -81,6 +81,21 @@ S2M_ICP_HD inline void host_svd3(const double A[9], double U[9], double S[3], do
             }
     for (int j = 0; j < 3; j++)
         for (int k = 0; k < 3; k++) U[k * 3 + j] = S[j] > 1e-300 ? icp_div(W[k * 3 + j], S[j]) : 0.0;
+    // U is orthonormal for every input, as Eigen's JacobiSVD returns it. Rank 0 (A = 0: no rotation ran, V = I): U = I.
+    if (!(S[0] > 1e-300)) { for (int i = 0; i < 9; i++) U[i] = (i % 4 == 0) ? 1.0 : 0.0; return; }
+    // Rank 1 (column 1 of W is zero, or what the rotations left of a zero: W[., 1] / S[1] would be column 0 again): column 1 is
+    // column 0 crossed with the axis of its smallest |component| (the first of equals), normalised; column 2 follows below.
+    if (S[1] <= 1e-12 * S[0]) {
+        const double u0 = U[0], u1 = U[3], u2 = U[6];
+        int ax = 0;
+        if (icp_fabs(u1) < icp_fabs(u0)) ax = 1;
+        if (icp_fabs(u2) < icp_fabs(ax == 0 ? u0 : u1)) ax = 2;
+        const double c0 = ax == 0 ? 0.0 : (ax == 1 ? -u2 : u1);          // (u0, u1, u2) x e_ax
+        const double c1 = ax == 0 ? u2 : (ax == 1 ? 0.0 : -u0);
+        const double c2 = ax == 0 ? -u1 : (ax == 1 ? u0 : 0.0);
+        const double nrm = icp_sqrt((c0 * c0 + c1 * c1) + c2 * c2);
+        U[1] = icp_div(c0, nrm); U[4] = icp_div(c1, nrm); U[7] = icp_div(c2, nrm);
+    }
     if (S[2] <= 1e-12 * S[0]) {          // rank-deficient: complete U to an orthonormal basis
         U[2] = U[3] * U[7] - U[6] * U[4]; U[5] = U[6] * U[1] - U[0] * U[7]; U[8] = U[0] * U[4] - U[3] * U[1];
     }

@@ -57,6 +57,7 @@ ABI_SYMBOLS = [
     "s2m_reloc_default_params", "s2m_relocalize_check_args", "s2m_relocalize_scan", "s2m_debug_icp_align_guess_many_device",
     "s2m_debug_icp_nearest", "s2m_debug_icp_time_nearest", "s2m_debug_icp_align_device", "s2m_debug_icp_align_many_device",
     "s2m_debug_icp_tuning", "s2m_debug_icp_grid_check_args", "s2m_debug_icp_grid",
+    "s2m_debug_icp_close_check_args", "s2m_debug_icp_close", "s2m_debug_icp_sums_check_args", "s2m_debug_icp_sums",
     "s2m_gmap_default_params", "s2m_global_map", "s2m_kf_map_cloud",
     "s2m_scan_layout_preset", "s2m_project_default_params", "s2m_imu_deskew_info", "s2m_project_check_args", "s2m_project_scan",
     "s2m_downsample_projected", "s2m_sc_add_projected",
@@ -189,6 +190,12 @@ class IcpGridOut(C.Structure):
     """s2m_debug_icp_grid_out (include/liorf_s2m_debug.h)."""
     _fields_ = [("lo", C.c_float * 3), ("cell", C.c_float), ("inv", C.c_float), ("n", C.c_int32 * 3), ("n_fin", C.c_int32),
                 ("usable", C.c_int32)]
+
+
+class IcpLoopStateWords(C.Structure):
+    """s2m_debug_icp_state (include/liorf_s2m_debug.h) as the 38 32-bit words it is made of: T 16 floats, T_step 16 floats,
+    prev_mse (a double, two words), it, conv, similar, done."""
+    _fields_ = [("w", C.c_uint32 * 38)]
 
 
 class KfParams(C.Structure):
@@ -496,6 +503,12 @@ def load_library(path: str | None = None) -> C.CDLL:
     L.s2m_debug_icp_time_nearest.argtypes = [vp, vp, C.c_size_t, vp, C.c_size_t, C.c_size_t, C.c_int32, C.c_int32, vp, C.POINTER(C.c_int32), fp, fp]
     L.s2m_debug_icp_align_device.argtypes = [vp, vp, C.c_size_t, vp, C.c_size_t, C.c_size_t, C.POINTER(IcpParams), C.POINTER(IcpResult)]
     L.s2m_debug_icp_tuning.argtypes = [vp, C.c_float, C.c_int32, C.c_int32]
+    L.s2m_debug_icp_close_check_args.argtypes = [C.c_int32, dp, vp, C.POINTER(IcpParams), vp]
+    L.s2m_debug_icp_close.argtypes = [vp, C.c_int32, dp, vp, C.POINTER(IcpParams), vp]
+    L.s2m_debug_icp_sums_check_args.argtypes = [C.POINTER(C.c_void_p), szp, C.POINTER(C.c_void_p), szp, C.c_int32, C.c_size_t, C.c_int32, dp,
+                                                C.POINTER(C.c_int32)]
+    L.s2m_debug_icp_sums.argtypes = [vp, C.POINTER(C.c_void_p), szp, C.POINTER(C.c_void_p), szp, C.c_int32, C.c_size_t, C.c_int32, C.c_double, dp,
+                                     C.POINTER(C.c_int32), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]
     L.s2m_debug_icp_grid_check_args.argtypes = [C.POINTER(C.c_void_p), szp, C.c_int32, C.c_size_t, C.POINTER(IcpGridOut)]
     L.s2m_debug_icp_grid.argtypes = [vp, C.POINTER(C.c_void_p), szp, C.c_int32, C.c_size_t, C.POINTER(IcpGridOut), C.POINTER(C.c_void_p),
                                      C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]
@@ -2041,6 +2054,57 @@ class MapOptimizationS2M:
         out = (IcpResult * max(P, 1))()
         self._check(self.lib.s2m_debug_icp_align_pairs_device(self.h, sp, sn, tp, tn, P, st, gs, C.byref(p), out), "s2m_debug_icp_align_pairs_device")
         return [(np.array(r.T, np.float32).reshape(4, 4), bool(r.converged), r.fitness_score, r.iterations) for r in out[:P]]
+
+    def debugIcpClose(self, sums, states, **params):
+        """s2m_debug_icp_close: sums (n, 17) float64 and states (n, 38) uint32 (s2m_debug_icp_state word by word), n <= 64, closed
+        by one launch of k_icp_close; keyword arguments are fields of the ICP parameters. Returns the outgoing states, (n, 38) uint32."""
+        S = np.ascontiguousarray(sums, np.float64).reshape(-1, 17)
+        w = np.ascontiguousarray(states, np.uint32).reshape(-1, 38)
+        if S.shape[0] != w.shape[0]:
+            raise ValueError("one state per row of sums")
+        p = IcpParams()
+        self.lib.s2m_icp_default_params(C.byref(p))
+        for k, v in params.items():
+            setattr(p, k, v)
+        out = np.zeros_like(w)
+        self._check(self.lib.s2m_debug_icp_close(self.h, S.shape[0], S.ctypes.data_as(C.POINTER(C.c_double)), w.ctypes.data, C.byref(p),
+                                                 out.ctypes.data), "s2m_debug_icp_close")
+        return out
+
+    def debugIcpSums(self, pairs, table, max_correspondence_distance, want_parts=False, want_keys=False):
+        """s2m_debug_icp_sums: pairs = [(source, target), ...]; table False: the slot form (every source the same array), True: the
+        table form. Returns a list of dicts: sums (17 float64), rows, and where asked for parts (rows x 17) and keys (uint64 per source)."""
+        sr = [_records(a) for a, _ in pairs]
+        tg = [_records(b) for _, b in pairs]
+        st = sr[0][2] if sr else 0
+        if any(t[2] != st for t in sr + tg):
+            raise ValueError("all clouds must share one record stride")
+        if not table:
+            if any(a is not pairs[0][0] for a, _ in pairs):
+                raise ValueError("the slot form has one source")
+            sr = [sr[0]] * len(sr)
+        P = len(pairs)
+        sp = (C.c_void_p * max(P, 1))(*[t[0].ctypes.data for t in sr])
+        sn = (C.c_size_t * max(P, 1))(*[t[1] for t in sr])
+        tp = (C.c_void_p * max(P, 1))(*[t[0].ctypes.data for t in tg])
+        tn = (C.c_size_t * max(P, 1))(*[t[1] for t in tg])
+        sums, rows = np.zeros((max(P, 1), 17)), np.zeros(max(P, 1), np.int32)
+        parts = [np.zeros((256, 17)) for _ in range(P)] if want_parts else None
+        keys = [np.zeros(t[1], np.uint64) for t in sr] if want_keys else None
+        pp = (C.c_void_p * max(P, 1))(*[a.ctypes.data for a in parts]) if parts else None
+        kp = (C.c_void_p * max(P, 1))(*[a.ctypes.data for a in keys]) if keys else None
+        self._check(self.lib.s2m_debug_icp_sums(self.h, sp, sn, tp, tn, P, st, 1 if table else 0, float(max_correspondence_distance),
+                                                sums.ctypes.data_as(C.POINTER(C.c_double)), rows.ctypes.data_as(C.POINTER(C.c_int32)), pp, kp),
+                    "s2m_debug_icp_sums")
+        out = []
+        for k in range(P):
+            d = dict(sums=sums[k].copy(), rows=int(rows[k]))
+            if parts:
+                d["parts"] = parts[k][:d["rows"]]
+            if keys:
+                d["keys"] = keys[k]
+            out.append(d)
+        return out
 
     def performSCLoopClosureVerified(self, top_k: int = 4, params: LoopParams | None = None, **query):
         """performSCLoopClosure() on the place query: the top_k <= S2M_LOOP_MAX_CANDIDATES hits of scQueryKey for the newest key

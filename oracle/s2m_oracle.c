@@ -1256,6 +1256,20 @@ static void icp_svd3(const double A[9], double U[9], double S[3], double V[9])
         for (int k = 0; k < 3; k++) { double t1 = W[k * 3 + i]; W[k * 3 + i] = W[k * 3 + j]; W[k * 3 + j] = t1; double t2 = V[k * 3 + i]; V[k * 3 + i] = V[k * 3 + j]; V[k * 3 + j] = t2; }
     }
     for (int j = 0; j < 3; j++) for (int k = 0; k < 3; k++) U[k * 3 + j] = S[j] > 1e-300 ? W[k * 3 + j] / S[j] : 0.0;
+    /* U orthonormal for every input, like Eigen's JacobiSVD. Rank 0 (A = 0, V = I): U = I */
+    if (!(S[0] > 1e-300)) { for (int i = 0; i < 9; i++) U[i] = (i % 4 == 0) ? 1.0 : 0.0; return; }
+    /* rank 1: column 1 = column 0 x the axis of its smallest |component| (the first of equals), normalised */
+    if (S[1] <= 1e-12 * S[0]) {
+        const double u0 = U[0], u1 = U[3], u2 = U[6];
+        int ax = 0;
+        if (fabs(u1) < fabs(u0)) ax = 1;
+        if (fabs(u2) < fabs(ax == 0 ? u0 : u1)) ax = 2;
+        const double c0 = ax == 0 ? 0.0 : (ax == 1 ? -u2 : u1);
+        const double c1 = ax == 0 ? u2 : (ax == 1 ? 0.0 : -u0);
+        const double c2 = ax == 0 ? -u1 : (ax == 1 ? u0 : 0.0);
+        const double nrm = sqrt((c0 * c0 + c1 * c1) + c2 * c2);
+        U[1] = c0 / nrm; U[4] = c1 / nrm; U[7] = c2 / nrm;
+    }
     /* complete a rank-deficient U to an orthonormal basis (cross products) */
     if (S[2] <= 1e-12 * S[0]) {
         U[2] = U[3] * U[7] - U[6] * U[4]; U[5] = U[6] * U[1] - U[0] * U[7]; U[8] = U[0] * U[4] - U[3] * U[1];

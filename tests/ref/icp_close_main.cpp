@@ -4,6 +4,10 @@
 //   icp_close_main align src.bin n_src tgt.bin n_tgt max_corr_dist max_iter
 //                                          a brute-force ICP on packed xyz floats whose iterations icp_close_step closes;
 //                                          stdout: converged iterations, then T as 16 hex words
+//   icp_close_main close                   stdin: lines of 57 numbers (hex floats, integers in decimal): the 17 sums, the incoming
+//                                          IcpLoopState (T 16, T_step 16, prev_mse, it, conv, similar, done), max_iter, trans_eps,
+//                                          fit_eps; stdout: the outgoing state as the 38 32-bit hex words of the struct. A state
+//                                          that comes in done is not closed (k_icp_close's guard).
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -51,6 +55,32 @@ int main(int argc, char** argv)
         }
         return 0;
     }
+    if (argc >= 2 && !strcmp(argv[1], "close")) {
+        static_assert(sizeof(s2m::IcpLoopState) == 38 * sizeof(uint32_t), "printed as 38 words");
+        char line[8192];
+        while (fgets(line, sizeof(line), stdin)) {
+            double v[57];
+            char* p = line;
+            int k = 0;
+            for (; k < 57; k++) {
+                char* e;
+                v[k] = strtod(p, &e);
+                if (e == p) break;
+                p = e;
+            }
+            if (k < 57) continue;
+            s2m::IcpLoopState st;
+            for (int i = 0; i < 16; i++) { st.T[i] = (float)v[17 + i]; st.T_step[i] = (float)v[33 + i]; }
+            st.prev_mse = v[49];
+            st.it = (int)v[50]; st.conv = (int)v[51]; st.similar = (int)v[52]; st.done = (int)v[53];
+            const s2m::IcpCloseParams cp = s2m::icp_close_params((int)v[54], v[55], v[56]);
+            if (!st.done) s2m::icp_close_step(v, cp, &st);
+            uint32_t w[38];
+            memcpy(w, &st, sizeof(w));
+            for (int i = 0; i < 38; i++) printf("%08x%c", w[i], i == 37 ? '\n' : ' ');
+        }
+        return 0;
+    }
     if (argc == 8 && !strcmp(argv[1], "align")) {
         const size_t ns = strtoul(argv[3], nullptr, 10), nt = strtoul(argv[5], nullptr, 10);
         std::vector<float> cur = read_xyz(argv[2], ns);
@@ -93,6 +123,6 @@ int main(int argc, char** argv)
         print_T(st.T);
         return 0;
     }
-    fprintf(stderr, "usage: icp_close_main umeyama | align src.bin n_src tgt.bin n_tgt max_corr_dist max_iter\n");
+    fprintf(stderr, "usage: icp_close_main umeyama | close | align src.bin n_src tgt.bin n_tgt max_corr_dist max_iter\n");
     return 2;
 }

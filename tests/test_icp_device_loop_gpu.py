@@ -61,9 +61,13 @@ def test_device_loop_on_three_targets(gpu, n_src):
 @pytest.mark.parametrize("n_tgt", [1, 2])
 @pytest.mark.parametrize("n_src", [3, 257])
 def test_device_loop_on_one_or_two_targets(gpu, n_tgt, n_src):
-    """Rank 0 or 1 cross-covariances: the rotation is rounding noise, and the same noise in both loops."""
+    """Rank 0 or 1 cross-covariances up to rounding noise: the rotation is fixed by that noise, the same noise in both loops, and
+    it is a rotation all the same - R R^T = I and det R = 1 to 4e-7, the bar of tests/test_icp_close_cpu.py for one Umeyama step
+    (so it is asked of the alignment that ends after one iteration)."""
     src, tgt = edge_scene(n_tgt, n_src, seed=7 + n_tgt)
-    _both(gpu, src, tgt, max_correspondence_distance=30.0, max_iterations=1)
+    T, _, _, _ = _both(gpu, src, tgt, max_correspondence_distance=30.0, max_iterations=1)
+    Rm = T[:3, :3].astype(np.float64)
+    assert np.abs(Rm @ Rm.T - np.eye(3)).max() <= 4e-7 and abs(np.linalg.det(Rm) - 1.0) <= 4e-7, T
     _both(gpu, src, tgt, max_correspondence_distance=30.0)
 
 
