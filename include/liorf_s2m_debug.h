@@ -284,6 +284,39 @@ int  s2m_debug_session_chunk(s2m_handle h, size_t chunk_bytes);
 int  s2m_debug_sc_keys(s2m_handle h, int32_t first, int32_t count, float* ring, double* sector);
 int  s2m_debug_kf_frame(s2m_handle h, int32_t key, float T_host[12], float T_device[12], float pos_device[4], int32_t* n_device);
 
+/* ---- the key-frame selection stage by stage ----
+ * s2m_debug_kf_select_last: what the most recent key-frame selection on the handle (s2m_extract_surrounding,
+ *   s2m_extract_surrounding_at, s2m_global_map) left in device memory, copied out as it stands - no kernel runs. The caller
+ *   sets the capacities and the four pointers; the hook fills the rest.
+ *     path: S2M_DEBUG_KF_NARROW - a store of up to 4 096 keys, everything in one workgroup; S2M_DEBUG_KF_PRE - a larger store,
+ *       the radius search over the whole grid and up to 4 096 candidates handed to that workgroup; S2M_DEBUG_KF_WIDE - more
+ *       candidates, sorted and filtered by the device-wide radix passes. A note the host takes where it decides.
+ *     n_cand, n_cent, n_frames, n_points: radius candidates (b), centroids of the key-pose filter (c), entries of the frame table
+ *       after (f), records of the concatenated cloud.
+ *     cent, nn: the first min(n_cent, cent_cap) centroids (x, y, z each) in ascending voxel index and the nearest key of each (d).
+ *     keys, offsets: the first min(n_frames, frames_cap) keys of the frame table, and - when frames_cap >= n_frames - its
+ *       n_frames + 1 offsets (offsets has room for frames_cap + 1 entries).
+ *   S2M_ERR_INVALID_ARG for a null handle or out, or a null array with a capacity above 0; S2M_ERR_NO_SCAN before the first
+ *   selection on the handle (one on an empty store does not count); S2M_ERR_CAPACITY, with the counts and what fits written,
+ *   when n_cent > cent_cap or n_frames > frames_cap.
+ * s2m_debug_kf_select_last_check_args: the argument checks on their own (host code, no handle, no GPU). */
+#define S2M_DEBUG_KF_NARROW 0
+#define S2M_DEBUG_KF_PRE    1
+#define S2M_DEBUG_KF_WIDE   2
+typedef struct s2m_debug_kf_select_out {
+    int32_t  path;
+    int32_t  n_cand, n_cent, n_frames;
+    int64_t  n_points;
+    size_t   cent_cap;      /* in: room in cent (x 3 floats) and nn */
+    float*   cent;
+    int32_t* nn;
+    size_t   frames_cap;    /* in: room in keys; offsets holds frames_cap + 1 */
+    int32_t* keys;
+    int32_t* offsets;
+} s2m_debug_kf_select_out;
+int  s2m_debug_kf_select_last_check_args(const s2m_debug_kf_select_out* out);
+int  s2m_debug_kf_select_last(s2m_handle h, s2m_debug_kf_select_out* out);
+
 /* ---- the many-query form of the place query: its passes and the shape of its kernel ----
  * s2m_debug_sc_query_many_pass: at most this many queries per pass of s2m_sc_query_keys / _descriptors (0 restores the
  *   default, as many as the 64 MiB scratch bound allows). The rows do not depend on it.

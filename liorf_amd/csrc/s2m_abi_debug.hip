@@ -1,6 +1,6 @@
 // s2m_abi_debug.hip — the observation and timing hooks of the registration path (include/liorf_s2m_debug.h and the s2m_time_* /
 // s2m_surf_optimization / s2m_normal_eq entry points): single stages and launches of the LM loop run on their own, the scan
-// preparation run again, the restated libm pinned.  It reaches the loop through the host functions s2m_abi.hip defines
+// preparation run again, the restated libm pinned - and the copy-out of the last key-frame selection's stages.  It reaches the loop through the host functions s2m_abi.hip defines
 // (s2m_context.hpp) and never includes s2m_kernels.hpp / s2m_register.hpp: a second unit that instantiates k_register would
 // compile every build twice.  Its two kernels include s2m_device.hpp, so the trig they pin is the one k_register compiles.
 #include <hip/hip_runtime.h>
@@ -479,6 +479,42 @@ int s2m_time_iterations(s2m_handle h, const float pose[6], int reps, float* ms_p
 {
     if (!h || !ms_per_iter || cap < h->prm.max_iter) return S2M_ERR_INVALID_ARG;
     return time_iterations_impl(h, pose, reps, nullptr, ms_per_iter);
+}
+
+int s2m_debug_kf_select_last_check_args(const s2m_debug_kf_select_out* out)
+{
+    if (!out) return S2M_ERR_INVALID_ARG;
+    if (out->cent_cap > 0 && (!out->cent || !out->nn)) return S2M_ERR_INVALID_ARG;
+    if (out->frames_cap > 0 && (!out->keys || !out->offsets)) return S2M_ERR_INVALID_ARG;
+    return S2M_OK;
+}
+
+// Observation hook: the stages the last kf_select on the handle's workspace left resident (s2m_voxel.hpp, KfLast), copied out as they
+// stand.  No kernel runs; the float4 centroids are narrowed to xyz on the host.
+int s2m_debug_kf_select_last(s2m_handle h, s2m_debug_kf_select_out* out)
+{
+    if (!h) return S2M_ERR_INVALID_ARG;
+    if (s2m_debug_kf_select_last_check_args(out)) return fail(h, S2M_ERR_INVALID_ARG, "null output, or a null array with a capacity above 0");
+    KfLast last;
+    if (!kf_select_last(h->voxel.ws, &last)) return fail(h, S2M_ERR_NO_SCAN, "no key-frame selection has run on the handle");
+    out->path = last.path;
+    out->n_cand = last.sel.n_cand; out->n_cent = last.sel.n_cent; out->n_frames = last.sel.n_frames;
+    out->n_points = last.sel.n_points;
+    S2M_HIP(h, hipSetDevice(h->device));
+    const size_t n_cent = (size_t)last.sel.n_cent, n_frames = (size_t)last.sel.n_frames;
+    const size_t nc = std::min(n_cent, out->cent_cap), nf = std::min(n_frames, out->frames_cap);
+    std::vector<float> c4(4 * nc);
+    if (nc > 0) {
+        S2M_HIP(h, hipMemcpyAsync(c4.data(), last.cent, sizeof(float) * 4 * nc, hipMemcpyDeviceToHost, h->stream));
+        S2M_HIP(h, hipMemcpyAsync(out->nn, last.nn, sizeof(int32_t) * nc, hipMemcpyDeviceToHost, h->stream));
+    }
+    if (nf > 0) S2M_HIP(h, hipMemcpyAsync(out->keys, last.tab.keys, sizeof(int32_t) * nf, hipMemcpyDeviceToHost, h->stream));
+    if (out->frames_cap > 0 && nf == n_frames)
+        S2M_HIP(h, hipMemcpyAsync(out->offsets, last.tab.offsets, sizeof(int32_t) * (n_frames + 1), hipMemcpyDeviceToHost, h->stream));
+    S2M_HIP(h, hipStreamSynchronize(h->stream));
+    for (size_t k = 0; k < nc; k++) memcpy(out->cent + 3 * k, c4.data() + 4 * k, sizeof(float) * 3);
+    if (n_cent > out->cent_cap || n_frames > out->frames_cap) return fail(h, S2M_ERR_CAPACITY, "fewer centroids or frames offered than the selection holds");
+    return S2M_OK;
 }
 
 // Host only: a copy of the notes the batch entry points took where they issued their launches (s2m_context::Batch::last).

@@ -1182,6 +1182,9 @@ struct VoxWorkspace {
     Buf kf_part, kf_vs, kf_sp;            // ... stores past kKfTile keys: the radius scan's partial boxes and counts, the key-pose filter's
                                           // setup, the candidate positions in (voxel, rank) order
     KfSelect* h_kf = nullptr;             // pinned
+    int kf_path = -1;                     // what the last kf_select took (kf_select_last): -1 none yet, 0 narrow, 1 pre, 2 wide
+    KfSelect kf_sel;                      // ... its counts
+    KfTable kf_last_tab;                  // ... and its frame table
     Buf loop_part;                        // loop detection: one partial minimum per workgroup
     unsigned long long* h_loop = nullptr; // pinned: its result
 };
@@ -1373,6 +1376,7 @@ hipError_t kf_select(VoxWorkspace* w, hipStream_t stream, const float4* d_pos, c
 {
     *out = KfSelect{};
     if (n <= 0) return hipSuccess;
+    w->kf_path = -1;                                           // (the buffers are about to change: nothing to observe until this selection ends)
     const float4 q = make_float4(centre[0], centre[1], centre[2], 0.0f);   // the kernels' centre, by value (extractSurroundingKeyFrames: P[n-1])
     const bool wide = n > kKfTile;                             // (b) over the whole grid; (c) too when the candidates pass the tile
     size_t P = 1;
@@ -1427,15 +1431,29 @@ hipError_t kf_select(VoxWorkspace* w, hipStream_t stream, const float4* d_pos, c
     nearest_and_frames();
     VOX_TRY(hipGetLastError());
     VOX_TRY(hipStreamSynchronize(stream));                   // the one wait: the counts size the transform launch
+    int path = wide ? 1 : 0;
     if (wide && w->h_kf->n_cand > kKfTile) {
         // more candidates than the tile: the pass above chose no centroid; the device-wide sort, then (d) - (f) again (a second wait)
+        path = 2;
         VOX_TRY(kf_select_wide(w, stream, d_pos, w->h_kf->n_cand));
         nearest_and_frames();
         VOX_TRY(hipGetLastError());
         VOX_TRY(hipStreamSynchronize(stream));
     }
     *out = *w->h_kf;
+    w->kf_path = path; w->kf_sel = *out; w->kf_last_tab = *tab;
     return hipSuccess;
+}
+
+bool kf_select_last(const VoxWorkspace* w, KfLast* out)
+{
+    if (!w || w->kf_path < 0) return false;
+    out->path = w->kf_path;
+    out->sel = w->kf_sel;
+    out->cent = w->kf_cent.as<float4>();
+    out->nn = w->kf_nn.as<int32_t>();
+    out->tab = w->kf_last_tab;
+    return true;
 }
 
 hipError_t loop_detect(VoxWorkspace* w, hipStream_t stream, const float4* d_pos, const double* d_time, int n, float radius,

@@ -73,6 +73,19 @@ struct KfTable {                           // the frame table, device memory, va
 hipError_t kf_select(VoxWorkspace* w, hipStream_t stream, const float4* d_pos, const KfFrame* d_frames, int n, const float centre[3],
                      int n_recent, float radius, float density, KfSelect* out, KfTable* tab);
 
+// What the most recent kf_select on the workspace left resident, for the observation hook s2m_debug_kf_select_last: the path it took
+// (a host-side note: 0 the single-workgroup kernel on a store of up to 4 096 keys, 1 the radius search over the whole grid with up
+// to 4 096 candidates, 2 the device-wide sorts), its counts, the centroids of (c) as {x, y, z, 0} and the nearest key of each (d),
+// and the frame table. The device pointers are valid until the next kf_select on the workspace. false: no selection has ended yet.
+struct KfLast {
+    int           path;
+    KfSelect      sel;
+    const float4* cent;                    // sel.n_cent entries
+    const int32_t* nn;                     // sel.n_cent entries
+    KfTable       tab;                     // sel.n_frames entries, sel.n_frames + 1 offsets
+};
+bool kf_select_last(const VoxWorkspace* w, KfLast* out);
+
 // ---- detectLoopClosureDistance() (:732-765) on the same store: pos[k] and time[k] of key k = 0 .. n-1. *key_pre = the key with the
 // least (d2, k) among those with d2(P[k], P[n-1]) < radius * radius (fp32, as kf_select) and |time[k] - time_cur| > time_diff
 // (double), or -1. Two launches over all keys and one wait on `stream` for the result.

@@ -71,6 +71,7 @@ ABI_SYMBOLS = [
     "s2m_pg_consistency_default_params", "s2m_pg_consistency_check_args", "s2m_pg_consistent_loops",
     "s2m_session_info_of", "s2m_session_save", "s2m_session_load", "s2m_session_save_file", "s2m_session_load_file", "s2m_session_check",
     "s2m_debug_session_chunk", "s2m_debug_sc_keys", "s2m_debug_kf_frame",
+    "s2m_debug_kf_select_last", "s2m_debug_kf_select_last_check_args",
     "s2m_session_append_check_args", "s2m_session_append", "s2m_session_append_file", "s2m_session_place", "s2m_session_appended",
     "s2m_session_anchor_from_pairs", "s2m_relocalize_key",
 ]
@@ -88,6 +89,7 @@ S2M_DEBUG_PREP_READ, S2M_DEBUG_PREP_NEW, S2M_DEBUG_PREP_LEGACY = -1, 0, 1   # ch
 S2M_ICP_RANGE = 8                                        # iterations the device loop queues at a time (liorf_s2m_debug.h)
 S2M_DEBUG_ICP_GRID_MAX_CELLS = 1 << 18                   # most cells of a grid of the device loop's search (liorf_s2m_debug.h)
 S2M_WARN_LEAF_TOO_SMALL = 1
+S2M_DEBUG_KF_NARROW, S2M_DEBUG_KF_PRE, S2M_DEBUG_KF_WIDE = 0, 1, 2   # s2m_debug_kf_select_out::path (liorf_s2m_debug.h)
 S2M_PG_PRIOR, S2M_PG_BETWEEN, S2M_PG_GPS, S2M_PG_INITIAL = 0, 1, 2, 3
 S2M_PG_PENDING, S2M_PG_IDLE = 2, 3                       # s2m_pg_optimize_launch / _poll / _collect: queued or running; nothing pending
 S2M_PG_BLOCK_COLUMNS = 24                                # right-hand sides per pass of the block solve
@@ -329,6 +331,13 @@ class BatchLast(C.Structure):
     _fields_ = [("n_scans", C.c_int32), ("n_live", C.c_int32),
                 ("ctx_launches", C.c_int32), ("init_launches", C.c_int32), ("prep_launches", C.c_int32),
                 ("ranges_issued", C.c_int32), ("graph_cached", C.c_int32), ("n_loops", C.c_int32), ("loop", BatchLoop * 2)]
+
+
+class KfSelectOut(C.Structure):
+    """s2m_debug_kf_select_out (include/liorf_s2m_debug.h)."""
+    _fields_ = [("path", C.c_int32), ("n_cand", C.c_int32), ("n_cent", C.c_int32), ("n_frames", C.c_int32), ("n_points", C.c_int64),
+                ("cent_cap", C.c_size_t), ("cent", C.POINTER(C.c_float)), ("nn", C.POINTER(C.c_int32)),
+                ("frames_cap", C.c_size_t), ("keys", C.POINTER(C.c_int32)), ("offsets", C.POINTER(C.c_int32))]
 
 
 class S2MError(RuntimeError):
@@ -576,6 +585,8 @@ def load_library(path: str | None = None) -> C.CDLL:
     L.s2m_session_anchor_from_pairs.argtypes = [fp, fp, C.c_int32, C.c_double, C.c_double, fp, i32p, i32p]
     L.s2m_debug_sc_keys.argtypes = [vp, C.c_int32, C.c_int32, fp, dp]
     L.s2m_debug_kf_frame.argtypes = [vp, C.c_int32, fp, fp, fp, i32p]
+    L.s2m_debug_kf_select_last.argtypes = [vp, C.POINTER(KfSelectOut)]
+    L.s2m_debug_kf_select_last_check_args.argtypes = [C.POINTER(KfSelectOut)]
     if path is None:
         _LIB = L
     return L
@@ -1585,6 +1596,20 @@ class MapOptimizationS2M:
         th, td, pos, n = np.zeros(12, np.float32), np.zeros(12, np.float32), np.zeros(4, np.float32), C.c_int32(0)
         self._check(self.lib.s2m_debug_kf_frame(self.h, key, _fp(th), _fp(td), _fp(pos), C.byref(n)), "s2m_debug_kf_frame")
         return th, td, pos, n.value
+
+    def kfSelectLast(self):
+        """s2m_debug_kf_select_last: the stages of the handle's last key-frame selection as a dict - path, n_cand, n_cent, n_frames,
+        n_points, cent (n_cent x 3 fp32), nn (n_cent), keys (n_frames), offsets (n_frames + 1)."""
+        n = max(self.kfSize(), 0)
+        cent, nn = np.zeros((n, 3), np.float32), np.zeros(n, np.int32)
+        keys, off = np.zeros(2 * n + 1, np.int32), np.zeros(2 * n + 2, np.int32)
+        i32 = C.POINTER(C.c_int32)
+        o = KfSelectOut(cent_cap=n, cent=_fp(cent), nn=nn.ctypes.data_as(i32), frames_cap=keys.size,
+                        keys=keys.ctypes.data_as(i32), offsets=off.ctypes.data_as(i32))
+        self._check(self.lib.s2m_debug_kf_select_last(self.h, C.byref(o)), "s2m_debug_kf_select_last")
+        return {"path": o.path, "n_cand": o.n_cand, "n_cent": o.n_cent, "n_frames": o.n_frames, "n_points": o.n_points,
+                "cent": cent[:o.n_cent].copy(), "nn": nn[:o.n_cent].copy(), "keys": keys[:o.n_frames].copy(),
+                "offsets": off[:o.n_frames + 1].copy()}
 
     # -- the pose graph beside the store (reference :1386-1534, :1611-1642) --------
     def pgReset(self):
