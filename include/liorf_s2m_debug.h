@@ -338,7 +338,7 @@ int  s2m_debug_sc_ring_pass(s2m_handle h, int32_t queries_per_pass);
 int  s2m_debug_sc_ring_shape(int32_t* tile_keys, int32_t* block_queries, int32_t* buffer_words);
 int  s2m_debug_sc_ring_last(s2m_handle h, int32_t* passes, size_t* scratch_bytes);
 
-/* The table form of the device loop (icp_pairs_begin / icp_pairs_advance): n_pairs <= S2M_LOOP_MANY_MAX_PAIRS host pairs, each
+/* The table form of the device loop (icp_dev_begin / icp_dev_advance of a table set): n_pairs <= S2M_LOOP_MANY_MAX_PAIRS host pairs, each
  * with its own source and target (no size gate) and optionally a guess (guesses: NULL, or n_pairs pointers, each NULL or a
  * row-major 4x4), aligned in lockstep as s2m_debug_icp_align_many_device aligns the slots of one source. out[k] is bit for bit
  * s2m_icp_align(srcs[k], tgts[k]) / s2m_icp_align_guess with guesses[k]; a pair with an empty cloud gives that call's result

@@ -7,7 +7,7 @@
 // s2m_abi_batch.hip's, the observation and timing hooks s2m_abi_debug.hip's (both launch the loop's kernels through the
 // functions s2m_context.hpp declares for this unit), ScanContext s2m_sc.hip's and s2m_abi_sc.hip's.  The handle is
 // s2m_context.hpp's; the entry points that only orchestrate other units' stages live in s2m_abi_voxel.hip,
-// s2m_abi_keyframes.hip, s2m_abi_loop.hip and s2m_abi_front_end.hip.  There is no CPU fallback: without a gfx950 device every
+// s2m_abi_keyframes.hip, s2m_abi_loop.hip, s2m_abi_icp.hip, s2m_abi_reloc.hip and s2m_abi_front_end.hip.  There is no CPU fallback: without a gfx950 device every
 // entry point fails with S2M_ERR_NO_DEVICE.
 #include <hip/hip_runtime.h>
 

@@ -1,6 +1,8 @@
-// s2m_abi_loop.hip — C ABI of the loop closure: the ICP alignment of two host clouds (section 8(f) row F4), with or without an
-// initial guess, detection, submaps and alignment against the key-frame store, and the relocalisation of a scan that is no key
-// (place query, guessed alignment of its hits in lockstep).  Host orchestration of s2m_icp.hip's and s2m_voxel.hip's stages only.
+// s2m_abi_loop.hip — C ABI of the loop closure against the key-frame store: detection, submaps, gates and judge, the closure and
+// its launched form (launch / poll / collect), the verification of one key against several candidates and of many keys at once.
+// Host orchestration of s2m_icp.hip's and s2m_voxel.hip's stages only.  What the alignment of host clouds (s2m_abi_icp.hip) and
+// the relocalisation (s2m_abi_reloc.hip) share with it is defined first: the loop stream, the parameters, the submap, the list of
+// alignments with its waited run, the arena.
 #include <algorithm>
 #include <cmath>
 #include <cstdint>
@@ -14,7 +16,7 @@
 using namespace s2m;
 using namespace s2m::host;
 
-static void icp_result_out(const IcpResult& r, s2m_icp_result* out)
+void s2m::host::icp_result_out(const IcpResult& r, s2m_icp_result* out)
 {
     memcpy(out->T, r.T, sizeof(r.T));
     out->converged = r.converged; out->iterations = r.iterations; out->fitness_score = r.fitness;
@@ -39,10 +41,8 @@ void s2m::host::loop_drop_pending(s2m_context* h, bool destroy)
     h->loop.ev_submaps = nullptr; h->loop.stream = nullptr;
 }
 
-namespace {
-
 // The loop stream: the lowest priority the device offers (create_stream), so that a closure yields to the registration kernels.
-int loop_stream(s2m_context* h)
+int s2m::host::loop_stream(s2m_context* h)
 {
     if (h->loop.stream) return S2M_OK;
     const int rc = create_stream(h, &h->loop.stream, false, "the loop-closure stream");
@@ -51,7 +51,7 @@ int loop_stream(s2m_context* h)
     return S2M_OK;
 }
 
-IcpTuning loop_tuning(const s2m_context* h, float leaf)
+IcpTuning s2m::host::loop_tuning(const s2m_context* h, float leaf)
 {
     IcpTuning t = h->loop.tune;
     t.cell = (t.cell > 0.0f ? t.cell : kIcpCellLeaves) * leaf;
@@ -59,7 +59,7 @@ IcpTuning loop_tuning(const s2m_context* h, float leaf)
 }
 
 // the caller's ICP parameters (null: the defaults), validated
-int icp_params_in(s2m_context* h, const s2m_icp_params* p, IcpParams* ip)
+int s2m::host::icp_params_in(s2m_context* h, const s2m_icp_params* p, IcpParams* ip)
 {
     s2m_icp_params prm;
     if (p) prm = *p; else s2m_icp_default_params(&prm);
@@ -69,60 +69,13 @@ int icp_params_in(s2m_context* h, const s2m_icp_params* p, IcpParams* ip)
     return S2M_OK;
 }
 
-}  // namespace
-
-// ---- section 8(f) row F4: ICP loop-closure alignment -----------------------------------------------
-
-int s2m_icp_default_params(s2m_icp_params* p)
-{
-    if (!p) return S2M_ERR_INVALID_ARG;
-    p->max_correspondence_distance = 20.0;      // historyKeyframeSearchRadius (10, include/utility.h:245) * 2 (:573)
-    p->max_iterations = 100;                    // :574
-    p->transformation_epsilon = 1e-6;           // :575
-    p->euclidean_fitness_epsilon = 1e-6;        // :576
-    return S2M_OK;
-}
-
-namespace {
-
 // an initial guess as align(output, guess) takes one: finite, last row 0 0 0 1
-int guess_ok(s2m_context* h, const float* g)
+int s2m::host::guess_ok(s2m_context* h, const float* g)
 {
     for (int i = 0; i < 16; i++)
         if (!std::isfinite(g[i])) return fail(h, S2M_ERR_INVALID_ARG, "the ICP guess has an entry that is not finite");
     if (g[12] != 0.0f || g[13] != 0.0f || g[14] != 0.0f || g[15] != 1.0f)
         return fail(h, S2M_ERR_INVALID_ARG, "the last row of the ICP guess must be 0 0 0 1");
-    return S2M_OK;
-}
-
-}  // namespace
-
-int s2m_icp_align(s2m_handle h, const void* src, size_t n_src, const void* tgt, size_t n_tgt, size_t stride_bytes,
-                  const s2m_icp_params* p, s2m_icp_result* out)
-{
-    return s2m_icp_align_guess(h, src, n_src, tgt, n_tgt, stride_bytes, nullptr, p, out);
-}
-
-int s2m_icp_align_guess(s2m_handle h, const void* src, size_t n_src, const void* tgt, size_t n_tgt, size_t stride_bytes,
-                        const float guess[16], const s2m_icp_params* p, s2m_icp_result* out)
-{
-    int rc = check_records(h, src, n_src, stride_bytes);
-    if (rc) return rc;
-    if ((rc = check_records(h, tgt, n_tgt, stride_bytes))) return rc;
-    if (!out) return S2M_ERR_INVALID_ARG;
-    if (guess && (rc = guess_ok(h, guess))) return rc;
-    if ((rc = loop_busy(h))) return rc;
-    IcpParams ip;
-    if ((rc = icp_params_in(h, p, &ip))) return rc;
-    S2M_HIP(h, hipSetDevice(h->device));
-    if (n_src && (rc = stage_host_records(h, h->loop.icp_src, src, n_src * stride_bytes))) return rc;
-    if (n_tgt && (rc = stage_host_records(h, h->loop.icp_tgt, tgt, n_tgt * stride_bytes))) return rc;
-    IcpResult r;
-    hipError_t e = icp_align(h->loop.icp, h->stream, h->loop.icp_src.as<unsigned char>(), n_src, h->loop.icp_tgt.as<unsigned char>(), n_tgt,
-                             stride_bytes, ip, &r, guess);
-    if (e != hipSuccess) return fail(h, S2M_ERR_HIP, "ICP alignment", e);
-    S2M_HIP(h, hipStreamSynchronize(h->stream));
-    icp_result_out(r, out);
     return S2M_OK;
 }
 
@@ -139,9 +92,7 @@ int s2m_loop_default_params(s2m_loop_params* p)
     return S2M_OK;
 }
 
-namespace {
-
-int loop_params(s2m_context* h, const s2m_loop_params* p, s2m_loop_params* prm)
+int s2m::host::loop_params(s2m_context* h, const s2m_loop_params* p, s2m_loop_params* prm)
 {
     if (p) *prm = *p; else s2m_loop_default_params(prm);
     if (!loop_radius_time_ok(prm->search_radius, prm->time_diff_s) || prm->search_num < 0 || std::isnan(prm->fitness_score))
@@ -149,19 +100,12 @@ int loop_params(s2m_context* h, const s2m_loop_params* p, s2m_loop_params* prm)
     return check_leaf(h, prm->icp_leaf);
 }
 
-void loop_result_init(s2m_loop_result* o)
-{
-    memset(o, 0, sizeof(*o));
-    o->status = S2M_LOOP_NONE;
-    o->key_cur = o->key_pre = -1;
-}
-
 // loopFindNearKeyframes(key, search_num, loop_index) (:821-844) into `dst`: the frame table from the host mirror of the store, then
 // the transform and the VoxelGrid of s2m_extract_cloud. An empty concatenation is not filtered (res->n_out = 0).
 // With a clamp [clamp_lo, clamp_hi) the neighbours stay inside it (clamp_hi < 0: the whole store, as the reference): a submap at
 // the boundary of an appended, still unplaced session takes no key of the other one (s2m_relocalize_key).
-int loop_submap(s2m_context* h, int32_t key, int32_t search_num, int32_t loop_index, float leaf, DevBuf& dst, VoxResult* res,
-                long long clamp_lo = 0, long long clamp_hi = -1)
+int s2m::host::loop_submap(s2m_context* h, int32_t key, int32_t search_num, int32_t loop_index, float leaf, DevBuf& dst, VoxResult* res,
+                           long long clamp_lo, long long clamp_hi)
 {
     *res = VoxResult{};
     const long long N = (long long)h->kf.time.size();
@@ -178,6 +122,67 @@ int loop_submap(s2m_context* h, int32_t key, int32_t search_num, int32_t loop_in
     int rc = tab.transform_into(h, h->loop.xf, kDsStride, "loop submap transform");
     if (rc) return rc;
     return voxel_into(h, h->loop.xf.as<unsigned char>(), tab.total, kDsStride, leaf, dst, res);   // (waits for the counts)
+}
+
+// s2m_icp_align's path on the device submaps: historyKeyframeSearchRadius*2 (a float), 100, 1e-6, 1e-6 (:572-576)
+IcpParams s2m::host::loop_icp_params(const s2m_loop_params& prm) { return IcpParams{ (double)(prm.search_radius * 2.0f), 100, 1e-6, 1e-6 }; }
+
+bool s2m::host::loop_key_ok(int32_t k, size_t N) { return k >= 0 && (size_t)k < N; }
+
+// The list's alignments begun on `stream` and advanced with waits to their end, then the stream waited for: al.res[k] is the
+// result of alignment k. An empty list only waits for the stream. what: the caller's words for a failure, after which the stream
+// has been drained and nothing is in flight.
+int s2m::host::icp_list_align(s2m_context* h, hipStream_t stream, IcpList& al, const IcpParams& ip, float leaf, const char* what)
+{
+    if (al.n) {
+        hipError_t e = icp_dev_begin(h->loop.icp, stream, al.set(), ip, loop_tuning(h, leaf));
+        bool done = false;
+        if (e == hipSuccess) e = icp_dev_advance(h->loop.icp, stream, true, &done, al.res, kIcpMaxPairs);
+        if (e != hipSuccess || !done) {
+            (void)hipStreamSynchronize(stream);
+            icp_dev_cancel(h->loop.icp);
+            return fail(h, S2M_ERR_HIP, what, e);
+        }
+    }
+    S2M_HIP(h, hipStreamSynchronize(stream));
+    return S2M_OK;
+}
+
+// Room for `need` bytes in the arena of a pass, the many_used bytes it holds kept (a larger arena takes them over). stream: the
+// stream the arena is written on.
+static int arena_reserve(s2m_context* h, hipStream_t stream, size_t need)
+{
+    s2m_context::LoopClosure& L = h->loop;
+    if (need <= L.many_arena.cap) return S2M_OK;
+    const size_t want = std::max(need + need / 2, (size_t)1 << 20);
+    void* q = nullptr;
+    S2M_HIP(h, hipMalloc(&q, want));
+    hipError_t e = L.many_used ? hipMemcpyAsync(q, L.many_arena.p, L.many_used, hipMemcpyDeviceToDevice, stream) : hipSuccess;
+    if (e == hipSuccess) e = hipStreamSynchronize(stream);
+    if (e != hipSuccess) { (void)hipFree(q); return fail(h, S2M_ERR_HIP, "the submaps of a verification pass", e); }
+    S2M_HIP(h, L.many_arena.reset(q, want));
+    return S2M_OK;
+}
+
+int s2m::host::arena_put(s2m_context* h, hipStream_t stream, const void* src, hipMemcpyKind kind, size_t bytes, size_t* off)
+{
+    s2m_context::LoopClosure& L = h->loop;
+    const size_t room = (bytes + 255) / 256 * 256;
+    const int rc = arena_reserve(h, stream, L.many_used + room);
+    if (rc) return rc;
+    *off = L.many_used;
+    S2M_HIP(h, hipMemcpyAsync(L.many_arena.as<unsigned char>() + L.many_used, src, bytes, kind, stream));
+    L.many_used += room;
+    return S2M_OK;
+}
+
+namespace {
+
+void loop_result_init(s2m_loop_result* o)
+{
+    memset(o, 0, sizeof(*o));
+    o->status = S2M_LOOP_NONE;
+    o->key_cur = o->key_pre = -1;
 }
 
 // The gates of one key against n_cand candidates (:565-566, :641-661): the container test, the source submap once, then a target
@@ -235,9 +240,6 @@ int32_t verify_best(const s2m_loop_result* rec, int32_t n)
     return best;
 }
 
-// s2m_icp_align's path on the device submaps: historyKeyframeSearchRadius*2 (a float), 100, 1e-6, 1e-6 (:572-576)
-IcpParams loop_icp_params(const s2m_loop_params& prm) { return IcpParams{ (double)(prm.search_radius * 2.0f), 100, 1e-6, 1e-6 }; }
-
 // the container test, both submaps, the size gate, ICP, the fitness gate, the pose result and the container (:565-621, :641-715)
 int loop_align_impl(s2m_context* h, int32_t key_cur, int32_t key_pre, int32_t base_key, const s2m_loop_params& prm, s2m_loop_result* out)
 {
@@ -263,21 +265,13 @@ int loop_launch(s2m_context* h, int32_t key_cur, const int32_t* key_pre, int32_t
     int32_t slots;
     int rc = loop_gates(h, key_cur, key_pre, n_cand, base_key, prm, rec, &slots);
     if (rc || !slots) return rc;
-    const unsigned char* d_tgt[S2M_LOOP_MAX_CANDIDATES];
-    size_t n_tgt[S2M_LOOP_MAX_CANDIDATES];
-    slots = 0;
-    for (int32_t i = 0; i < n_cand; i++) {
-        L.pend_slot[i] = -1;
-        if (rec[i].status != S2M_LOOP_NONE) continue;
-        d_tgt[slots] = L.target(i).as<unsigned char>();
-        n_tgt[slots] = (size_t)rec[i].n_prev;
-        L.pend_slot[i] = slots++;
-    }
+    IcpList al(IcpForm::kSlots, kDsStride);
+    for (int32_t i = 0; i < n_cand; i++)
+        L.pend_slot[i] = rec[i].status != S2M_LOOP_NONE ? -1 : al.add(L.cur.p, (size_t)rec[0].n_cur, L.target(i).p, (size_t)rec[i].n_prev, nullptr, i);
     if ((rc = loop_stream(h))) return rc;
     S2M_HIP(h, hipEventRecord(L.ev_submaps, h->stream));
     S2M_HIP(h, hipStreamWaitEvent(L.stream, L.ev_submaps, 0));
-    const hipError_t e = icp_dev_begin(L.icp, L.stream, L.cur.as<unsigned char>(), (size_t)rec[0].n_cur, d_tgt, n_tgt, slots, kDsStride,
-                                       loop_icp_params(prm), loop_tuning(h, prm.icp_leaf));
+    const hipError_t e = icp_dev_begin(L.icp, L.stream, al.set(), loop_icp_params(prm), loop_tuning(h, prm.icp_leaf));
     if (e != hipSuccess) {
         (void)hipStreamSynchronize(L.stream);               // (whatever was queued before the failure ends before the buffers are used again)
         return fail(h, S2M_ERR_HIP, who == L.kSingle ? "loop ICP launch" : "loop verification launch", e);
@@ -309,7 +303,7 @@ int loop_advance(s2m_context* h, bool wait, int32_t* best)
     S2M_HIP(h, hipSetDevice(h->device));
     bool done = false;
     IcpResult r[S2M_LOOP_MAX_CANDIDATES];
-    const hipError_t e = icp_dev_advance(L.icp, L.stream, wait, &done, r);
+    const hipError_t e = icp_dev_advance(L.icp, L.stream, wait, &done, r, S2M_LOOP_MAX_CANDIDATES);
     if (e != hipSuccess) {
         const char* what = L.pending == L.kSingle ? "loop ICP on the loop stream" : "loop verification on the loop stream";
         loop_drop_pending(h, false);
@@ -342,8 +336,6 @@ int loop_poll_impl(s2m_context* h, s2m_loop_result* out, bool wait)
     *out = L.pend_rec[0];                                   // S2M_LOOP_PENDING, or the result
     return S2M_OK;
 }
-
-bool loop_key_ok(int32_t k, size_t N) { return k >= 0 && (size_t)k < N; }
 
 }  // namespace
 
@@ -592,35 +584,6 @@ int many_args(s2m_context* h, size_t N, const int32_t* key_cur, const int32_t* k
     return S2M_OK;
 }
 
-// Room for `need` bytes in the arena of a pass, the many_used bytes it holds kept (a larger arena takes them over). stream: the
-// stream the arena is written on.
-int arena_reserve(s2m_context* h, hipStream_t stream, size_t need)
-{
-    s2m_context::LoopClosure& L = h->loop;
-    if (need <= L.many_arena.cap) return S2M_OK;
-    const size_t want = std::max(need + need / 2, (size_t)1 << 20);
-    void* q = nullptr;
-    S2M_HIP(h, hipMalloc(&q, want));
-    hipError_t e = L.many_used ? hipMemcpyAsync(q, L.many_arena.p, L.many_used, hipMemcpyDeviceToDevice, stream) : hipSuccess;
-    if (e == hipSuccess) e = hipStreamSynchronize(stream);
-    if (e != hipSuccess) { (void)hipFree(q); return fail(h, S2M_ERR_HIP, "the submaps of a verification pass", e); }
-    S2M_HIP(h, L.many_arena.reset(q, want));
-    return S2M_OK;
-}
-
-// n records of `src` (a submap as voxel_into left it) to the end of the arena, on the handle's stream; *off: where they start
-int arena_put(s2m_context* h, const DevBuf& src, size_t n, size_t* off)
-{
-    s2m_context::LoopClosure& L = h->loop;
-    const size_t bytes = (n * kDsStride + 255) / 256 * 256;
-    const int rc = arena_reserve(h, h->stream, L.many_used + bytes);
-    if (rc) return rc;
-    *off = L.many_used;
-    S2M_HIP(h, hipMemcpyAsync(L.many_arena.as<unsigned char>() + L.many_used, src.p, n * kDsStride, hipMemcpyDeviceToDevice, h->stream));
-    L.many_used += bytes;
-    return S2M_OK;
-}
-
 // One pass: rows [r0, r1). The gates and submaps of every row by the path of the single call - built where the single call builds
 // them, the filtered records of the pairs the gates left open then copied into the pass's arena, behind the stream's order, before
 // the next row builds over them; one lockstep alignment of those pairs; the judge, the best rule and the container per row.
@@ -628,49 +591,31 @@ int many_pass(s2m_context* h, const int32_t* key_cur, const int32_t* key_pre, co
               int32_t base_key, const s2m_loop_params& prm, s2m_loop_result* out, int32_t* best)
 {
     s2m_context::LoopClosure& L = h->loop;
-    const unsigned char *d_src[kIcpMaxPairs], *d_tgt[kIcpMaxPairs];
-    size_t n_src[kIcpMaxPairs], n_tgt[kIcpMaxPairs], off_src[kIcpMaxPairs], off_tgt[kIcpMaxPairs];
-    s2m_loop_result* rec_of[kIcpMaxPairs];
-    int pairs = 0, cands = 0;
+    IcpList al(IcpForm::kTable, kDsStride, &L.many_arena);  // (the arena may move while it grows: the list keeps offsets)
+    int cands = 0, rc;
     L.many_used = 0;
     for (int32_t r = r0; r < r1; r++) {
         if (!n_cand[r]) continue;
         if (cands + n_cand[r] > kIcpMaxPairs) return fail(h, S2M_ERR_CAPACITY, "a pass of more than kIcpMaxPairs pairs");   // not reached
         s2m_loop_result* rec = out + (size_t)r * row_stride;
         int32_t open;
-        int rc = loop_gates(h, key_cur[r], key_pre + (size_t)r * row_stride, n_cand[r], base_key, prm, rec, &open);
-        if (rc) return rc;
-        size_t row_src = 0;
-        if (open && (rc = arena_put(h, L.cur, (size_t)rec[0].n_cur, &row_src))) return rc;   // (n_cur: the same in every record of the row)
+        if ((rc = loop_gates(h, key_cur[r], key_pre + (size_t)r * row_stride, n_cand[r], base_key, prm, rec, &open))) return rc;
+        size_t row_src = 0, tgt = 0;                        // (n_cur: the same in every record of the row)
+        if (open && (rc = arena_put(h, h->stream, L.cur.p, hipMemcpyDeviceToDevice, (size_t)rec[0].n_cur * kDsStride, &row_src))) return rc;
         for (int32_t i = 0; open && i < n_cand[r]; i++) {
             if (rec[i].status != S2M_LOOP_NONE) continue;
-            if ((rc = arena_put(h, L.target(i), (size_t)rec[i].n_prev, &off_tgt[pairs]))) return rc;
-            off_src[pairs] = row_src;
-            n_src[pairs] = (size_t)rec[i].n_cur; n_tgt[pairs] = (size_t)rec[i].n_prev;
-            rec_of[pairs++] = &rec[i];
+            if ((rc = arena_put(h, h->stream, L.target(i).p, hipMemcpyDeviceToDevice, (size_t)rec[i].n_prev * kDsStride, &tgt))) return rc;
+            al.add_at(row_src, (size_t)rec[i].n_cur, tgt, (size_t)rec[i].n_prev, nullptr, (size_t)(&rec[i] - out));
         }
         cands += n_cand[r];
     }
-    for (int k = 0; k < pairs; k++) {                       // (the arena may have moved while it grew: addresses last)
-        d_src[k] = L.many_arena.as<unsigned char>() + off_src[k];
-        d_tgt[k] = L.many_arena.as<unsigned char>() + off_tgt[k];
-    }
-    if (pairs) {
-        IcpResult res[kIcpMaxPairs];
-        hipError_t e = icp_pairs_begin(L.icp, h->stream, d_src, n_src, d_tgt, n_tgt, pairs, kDsStride, loop_icp_params(prm), loop_tuning(h, prm.icp_leaf));
-        bool done = false;
-        if (e == hipSuccess) e = icp_pairs_advance(L.icp, h->stream, true, &done, res);
-        if (e != hipSuccess || !done) {
-            (void)hipStreamSynchronize(h->stream);
-            icp_dev_cancel(L.icp);
-            return fail(h, S2M_ERR_HIP, "loop verification of many keys", e);
+    if (al.n) {
+        if ((rc = icp_list_align(h, h->stream, al, loop_icp_params(prm), prm.icp_leaf, "loop verification of many keys"))) return rc;
+        for (int k = 0; k < al.n; k++) {
+            s2m_loop_result* o = &out[al.who[k]];
+            loop_judge(al.res[k], base_key, prm.fitness_score, h->kf.frame[(size_t)o->key_cur].T, &h->kf.pose[6 * (size_t)o->key_pre], o);
         }
-        S2M_HIP(h, hipStreamSynchronize(h->stream));
-        for (int k = 0; k < pairs; k++) {
-            s2m_loop_result* o = rec_of[k];
-            loop_judge(res[k], base_key, prm.fitness_score, h->kf.frame[(size_t)o->key_cur].T, &h->kf.pose[6 * (size_t)o->key_pre], o);
-        }
-        L.many_last_pairs += pairs;
+        L.many_last_pairs += al.n;
     }
     for (int32_t r = r0; r < r1; r++) {
         if (!n_cand[r]) continue;
@@ -752,503 +697,3 @@ int s2m_debug_loop_verify_many_plan(const int32_t* n_cand, int32_t m, int32_t pa
     return S2M_OK;
 }
 
-// ---- relocalisation: a scan that is no key against the stored map (place query, guessed alignment in lockstep) -------------
-
-int s2m_reloc_default_params(s2m_reloc_params* p)
-{
-    if (!p) return S2M_ERR_INVALID_ARG;
-    memset(p, 0, sizeof(*p));
-    s2m_sc_query_default_params(&p->query);
-    p->query.top_k = 4;
-    p->query.align = S2M_SC_ALIGN_FULL;
-    s2m_loop_default_params(&p->loop);
-    p->use_yaw = 1;
-    return S2M_OK;
-}
-
-namespace {
-
-int reloc_args(s2m_context* h, int64_t n_sc, int64_t n_kf, const s2m_reloc_params* p, s2m_reloc_params* prm)
-{
-    if (p) *prm = *p; else s2m_reloc_default_params(prm);
-    if (n_sc < 0 || n_kf < 0 || n_sc > INT32_MAX) return fail(h, S2M_ERR_INVALID_ARG, "relocalisation: a negative store size");
-    if (prm->query.top_k < 1 || prm->query.top_k > S2M_LOOP_MAX_CANDIDATES)
-        return fail(h, S2M_ERR_INVALID_ARG, "a relocalisation aligns the top 1 .. S2M_LOOP_MAX_CANDIDATES hits");
-    if (s2m_sc_query_check_args((int32_t)n_sc, &prm->query) != S2M_OK)
-        return fail(h, S2M_ERR_INVALID_ARG, "relocalisation: the query's align, max_dist or range is invalid");
-    s2m_loop_params lp;
-    const int rc = loop_params(h, &prm->loop, &lp);
-    return rc;
-}
-
-// G = T(pose[key]) * Rz(-yaw): the key's stored 3x4 times the turn that takes a query point back onto the candidate's (the
-// descriptor's shift says query ~ Rz(+yaw) * candidate), in float, each entry ((a0 b0 + a1 b1) + a2 b2)
-void reloc_guess(const float T_key[12], float yaw_diff_rad, bool use_yaw, float G[16])
-{
-    const float a = use_yaw ? -yaw_diff_rad : 0.0f;
-    const float c = cosf(a), s = sinf(a);
-    const float Rz[12] = { c, -s, 0.0f, 0.0f,   s, c, 0.0f, 0.0f,   0.0f, 0.0f, 1.0f, 0.0f };
-    if (use_yaw) host_affine_mul(T_key, Rz, G); else memcpy(G, T_key, sizeof(float) * 12);
-    G[12] = G[13] = G[14] = 0.0f; G[15] = 1.0f;
-}
-
-int reloc_from_hits(s2m_context* h, const s2m_reloc_params& prm, const unsigned char* d_pts, size_t n, size_t stride_bytes, const s2m_sc_hit* hits,
-                    int32_t n_hits, long long clamp_lo, long long clamp_hi, s2m_reloc_candidate* out, int32_t* n_out, int32_t* best);
-
-}  // namespace
-
-int s2m_relocalize_check_args(int32_t n_sc, int32_t n_kf, const s2m_reloc_params* p)
-{
-    s2m_reloc_params prm;
-    return reloc_args(nullptr, n_sc, n_kf, p, &prm);
-}
-
-int s2m_relocalize_scan(s2m_handle h, const void* pts, size_t n, size_t stride_bytes, int on_device, const s2m_reloc_params* p,
-                        s2m_reloc_candidate* out, int32_t* n_out, int32_t* best)
-{
-    if (!h) return S2M_ERR_INVALID_ARG;
-    if (!out || !n_out || !best) return fail(h, S2M_ERR_INVALID_ARG, "null relocalisation outputs");
-    int rc = check_records(h, pts, n, stride_bytes);
-    if (rc) return rc;
-    if ((rc = loop_busy(h))) return rc;
-    *n_out = 0; *best = -1;
-    s2m_reloc_params prm;
-    if ((rc = reloc_args(h, (int64_t)h->sc.n, (int64_t)h->kf.time.size(), p, &prm))) return rc;
-    if (n == 0) return S2M_OK;
-    S2M_HIP(h, hipSetDevice(h->device));
-    s2m_context::LoopClosure& L = h->loop;
-    // the scan in the loop's staging buffer (a host scan), where the query's descriptor and the source filter both read it
-    const unsigned char* d_pts = static_cast<const unsigned char*>(pts);
-    if (!on_device) {
-        if ((rc = stage_host_records(h, L.icp_src, pts, n * stride_bytes))) return rc;
-        d_pts = L.icp_src.as<unsigned char>();
-    }
-    // 1. the query: s2m_sc_query_scan's hits
-    s2m_sc_hit hits[S2M_LOOP_MAX_CANDIDATES];
-    int32_t n_hits = 0;
-    if ((rc = sc_query_device_scan(h, d_pts, n, stride_bytes, &prm.query, hits, &n_hits))) return rc;
-    return reloc_from_hits(h, prm, d_pts, n, stride_bytes, hits, n_hits, 0, -1, out, n_out, best);
-}
-
-namespace {
-
-// Steps 2 to 6 of a relocalisation, from the query's hits on: the source (n records on the device, in their own frame) through the
-// VoxelGrid, a target submap - its neighbours inside [clamp_lo, clamp_hi), see loop_submap - and a guess per hit, the alignments in
-// lockstep, the gates, both pose forms and *best.
-int reloc_from_hits(s2m_context* h, const s2m_reloc_params& prm, const unsigned char* d_pts, size_t n, size_t stride_bytes, const s2m_sc_hit* hits,
-                    int32_t n_hits, long long clamp_lo, long long clamp_hi, s2m_reloc_candidate* out, int32_t* n_out, int32_t* best)
-{
-    int rc;
-    s2m_context::LoopClosure& L = h->loop;
-    if (n_hits == 0) return S2M_OK;
-    const size_t N = h->kf.time.size();
-    for (int32_t i = 0; i < n_hits; i++)
-        if (!loop_key_ok(hits[i].key, N))
-            return fail(h, S2M_ERR_INVALID_ARG, "relocalisation: a hit names a key the key-frame store does not hold (the two stores are out of step)");
-    // 2. the source: the scan in its own frame through the VoxelGrid at icp_leaf, once, into the loop's source buffer
-    VoxResult vs;
-    if ((rc = voxel_into(h, d_pts, n, stride_bytes, prm.loop.icp_leaf, L.cur, &vs))) return rc;
-    // 3. + 4. a target submap and a guess per hit; the size gates decide who takes a slot
-    const unsigned char* d_tgt[S2M_LOOP_MAX_CANDIDATES];
-    const float* guess[S2M_LOOP_MAX_CANDIDATES];
-    size_t n_tgt[S2M_LOOP_MAX_CANDIDATES];
-    int slot_of[S2M_LOOP_MAX_CANDIDATES];
-    int slots = 0;
-    for (int32_t i = 0; i < n_hits; i++) {
-        s2m_reloc_candidate& c = out[i];
-        memset(&c, 0, sizeof(c));
-        c.hit = hits[i];
-        c.icp.T[0] = c.icp.T[5] = c.icp.T[10] = c.icp.T[15] = 1.0f;
-        c.n_src = (int32_t)vs.n_out;
-        reloc_guess(h->kf.frame[(size_t)hits[i].key].T, hits[i].yaw_diff_rad, prm.use_yaw != 0, c.guess);
-        slot_of[i] = -1;
-        c.status = S2M_LOOP_TOO_FEW_POINTS;
-        if (vs.n_out < 300) continue;
-        VoxResult vt;
-        if ((rc = loop_submap(h, hits[i].key, prm.loop.search_num, -1, prm.loop.icp_leaf, L.target(i), &vt, clamp_lo, clamp_hi))) return rc;
-        c.n_tgt = (int32_t)vt.n_out;
-        if (vt.n_out < 1000) continue;
-        if ((rc = guess_ok(h, c.guess))) return rc;
-        c.status = S2M_LOOP_NONE;
-        d_tgt[slots] = L.target(i).as<unsigned char>();
-        n_tgt[slots] = vt.n_out;
-        guess[slots] = c.guess;
-        slot_of[i] = slots++;
-    }
-    *n_out = n_hits;
-    if (!slots) return S2M_OK;
-    // 5. the alignments in lockstep on the device loop, waited for
-    IcpResult r[S2M_LOOP_MAX_CANDIDATES];
-    hipError_t e = icp_dev_begin(L.icp, h->stream, L.cur.as<unsigned char>(), vs.n_out, d_tgt, n_tgt, slots, kDsStride, loop_icp_params(prm.loop),
-                                 loop_tuning(h, prm.loop.icp_leaf), guess);
-    bool done = false;
-    if (e == hipSuccess) e = icp_dev_advance(L.icp, h->stream, true, &done, r);
-    if (e != hipSuccess || !done) {
-        (void)hipStreamSynchronize(h->stream);
-        icp_dev_cancel(L.icp);
-        return fail(h, S2M_ERR_HIP, "relocalisation ICP", e);
-    }
-    S2M_HIP(h, hipStreamSynchronize(h->stream));
-    // 6. the fitness gate, both pose forms, the best record by (fitness, position)
-    for (int32_t i = 0; i < n_hits; i++) {
-        if (slot_of[i] < 0) continue;
-        s2m_reloc_candidate& c = out[i];
-        const IcpResult& ri = r[slot_of[i]];
-        icp_result_out(ri, &c.icp);
-        if (!ri.converged || ri.fitness > (double)prm.loop.fitness_score) { c.status = S2M_LOOP_REJECTED; continue; }
-        c.status = S2M_LOOP_ACCEPTED;
-        host_translation_and_euler(ri.T, 4, c.pose_xyzrpy);
-        for (int k = 0; k < 3; k++) { c.pose_tobemapped[k] = c.pose_xyzrpy[3 + k]; c.pose_tobemapped[3 + k] = c.pose_xyzrpy[k]; }
-        if (*best < 0 || c.icp.fitness_score < out[*best].icp.fitness_score) *best = i;
-    }
-    return S2M_OK;
-}
-
-}  // namespace
-
-int s2m_relocalize_key(s2m_handle h, int32_t key, const s2m_reloc_params* p, s2m_reloc_candidate* out, int32_t* n_out, int32_t* best)
-{
-    if (!h) return S2M_ERR_INVALID_ARG;
-    if (!out || !n_out || !best) return fail(h, S2M_ERR_INVALID_ARG, "null relocalisation outputs");
-    int rc = loop_busy(h);
-    if (rc) return rc;
-    *n_out = 0; *best = -1;
-    s2m_reloc_params prm;
-    if ((rc = reloc_args(h, (int64_t)h->sc.n, (int64_t)h->kf.time.size(), p, &prm))) return rc;
-    if (key < 0 || (size_t)key >= h->kf.time.size() || (size_t)key >= h->sc.n)
-        return fail(h, S2M_ERR_INVALID_ARG, "relocalisation: the key is outside the key-frame store or has no descriptor");
-    const KfFrame& f = h->kf.frame[(size_t)key];
-    if (f.n == 0) return S2M_OK;
-    S2M_HIP(h, hipSetDevice(h->device));
-    // 1. the query: the key's stored descriptor against the searched range
-    s2m_sc_hit hits[S2M_LOOP_MAX_CANDIDATES];
-    int32_t n_hits = 0;
-    if ((rc = s2m_sc_query_key(h, key, &prm.query, hits, &n_hits))) return rc;
-    // 2 .. 6 with the key's own records, straight from the arena, as the source, and submaps that stay inside the searched range
-    const long long lo = prm.query.first, hi = prm.query.count < 0 ? (long long)h->sc.n : lo + prm.query.count;
-    return reloc_from_hits(h, prm, f.src, (size_t)f.n, kDsStride, hits, n_hits, lo, hi, out, n_out, best);
-}
-
-// ---- diagnostics of the device loop (include/liorf_s2m_debug.h) ---------------------------------------------------------
-
-namespace {
-
-// both host clouds into the ICP staging buffers, on the loop stream
-int debug_stage(s2m_context* h, const void* src, size_t n_src, const void* tgt, size_t n_tgt, size_t stride)
-{
-    int rc = check_records(h, src, n_src, stride);
-    if (rc) return rc;
-    if ((rc = check_records(h, tgt, n_tgt, stride))) return rc;
-    if ((rc = loop_busy(h))) return rc;
-    S2M_HIP(h, hipSetDevice(h->device));
-    if ((rc = loop_stream(h))) return rc;
-    S2M_HIP(h, hipStreamSynchronize(h->stream));            // (the staging buffers are the synchronous call's too)
-    if ((rc = ensure(h, h->loop.icp_src, n_src * stride)) || (rc = ensure(h, h->loop.icp_tgt, n_tgt * stride))) return rc;
-    if (n_src) S2M_HIP(h, hipMemcpyAsync(h->loop.icp_src.p, src, n_src * stride, hipMemcpyHostToDevice, h->loop.stream));
-    if (n_tgt) S2M_HIP(h, hipMemcpyAsync(h->loop.icp_tgt.p, tgt, n_tgt * stride, hipMemcpyHostToDevice, h->loop.stream));
-    return S2M_OK;
-}
-
-// one host source against n_cand host targets through the device loop, waited for: a slot per non-empty target, staged in the
-// closure's target buffers; out: n_cand results (an empty cloud: icp_result_none)
-int debug_align_many(s2m_context* h, const void* src, size_t n_src, const void* const* tgts, const size_t* n_tgts, int32_t n_cand, size_t stride,
-                     const IcpParams& ip, s2m_icp_result* out, const float* guesses = nullptr /* n_cand row-major 4x4, or none */)
-{
-    int rc = debug_stage(h, src, n_src, nullptr, 0, stride);
-    if (rc) return rc;
-    s2m_context::LoopClosure& L = h->loop;
-    const unsigned char* d_tgt[S2M_LOOP_MAX_CANDIDATES];
-    size_t n_tgt[S2M_LOOP_MAX_CANDIDATES];
-    int slot_of[S2M_LOOP_MAX_CANDIDATES];
-    const float* guess[S2M_LOOP_MAX_CANDIDATES];
-    int slots = 0;
-    for (int32_t i = 0; i < n_cand; i++) {
-        if ((rc = check_records(h, tgts[i], n_tgts[i], stride))) return rc;
-        slot_of[i] = -1;
-        if (!n_src || !n_tgts[i]) continue;
-        guess[slots] = guesses ? guesses + 16 * (size_t)i : nullptr;
-        if ((rc = ensure(h, L.target(i), n_tgts[i] * stride))) return rc;
-        S2M_HIP(h, hipMemcpyAsync(L.target(i).p, tgts[i], n_tgts[i] * stride, hipMemcpyHostToDevice, L.stream));
-        d_tgt[slots] = L.target(i).as<unsigned char>();
-        n_tgt[slots] = n_tgts[i];
-        slot_of[i] = slots++;
-    }
-    IcpResult r[S2M_LOOP_MAX_CANDIDATES];
-    if (slots) {
-        s2m_loop_params lp;
-        s2m_loop_default_params(&lp);
-        hipError_t e = icp_dev_begin(L.icp, L.stream, L.icp_src.as<unsigned char>(), n_src, d_tgt, n_tgt, slots, stride, ip, loop_tuning(h, lp.icp_leaf), guess);
-        bool done = false;
-        if (e == hipSuccess) e = icp_dev_advance(L.icp, L.stream, true, &done, r);
-        if (e != hipSuccess || !done) {
-            (void)hipStreamSynchronize(L.stream);
-            icp_dev_cancel(L.icp);
-            return fail(h, S2M_ERR_HIP, "ICP device loop", e);
-        }
-    }
-    S2M_HIP(h, hipStreamSynchronize(L.stream));
-    for (int32_t i = 0; i < n_cand; i++) icp_result_out(slot_of[i] >= 0 ? r[slot_of[i]] : icp_result_none(), &out[i]);
-    return S2M_OK;
-}
-
-}  // namespace
-
-int s2m_debug_icp_tuning(s2m_handle h, float cell_in_leaves, int32_t shell_cap, int32_t use_grid)
-{
-    if (!h) return S2M_ERR_INVALID_ARG;
-    if (!(cell_in_leaves >= 0.0f) || !std::isfinite(cell_in_leaves) || shell_cap < 0)
-        return fail(h, S2M_ERR_INVALID_ARG, "cell edge (in leaves) and shell cap must not be negative");
-    const int rc = loop_busy(h);
-    if (rc) return rc;
-    h->loop.tune.cell = cell_in_leaves;                     // 0: the built-in edge
-    h->loop.tune.shell_cap = shell_cap > 0 ? shell_cap : kIcpShellCap;
-    h->loop.tune.use_grid = use_grid < 0 ? (kIcpUseGrid ? 1 : 0) : (use_grid != 0);
-    return S2M_OK;
-}
-
-int s2m_debug_icp_nearest(s2m_handle h, const void* src, size_t n_src, const void* tgt, size_t n_tgt, size_t stride_bytes, int32_t mode,
-                          uint64_t* keys, int32_t* n_fallback)
-{
-    return s2m_debug_icp_time_nearest(h, src, n_src, tgt, n_tgt, stride_bytes, mode, 0, keys, n_fallback, nullptr, nullptr);
-}
-
-int s2m_debug_icp_time_nearest(s2m_handle h, const void* src, size_t n_src, const void* tgt, size_t n_tgt, size_t stride_bytes, int32_t mode,
-                               int32_t reps, uint64_t* keys, int32_t* n_fallback, float* us_build, float* us_search)
-{
-    if (!h) return S2M_ERR_INVALID_ARG;
-    if ((mode != 0 && mode != 1) || reps < 0 || (n_src && !keys && reps == 0)) return fail(h, S2M_ERR_INVALID_ARG, "mode is 0 or 1, keys must not be null");
-    int rc = debug_stage(h, src, n_src, tgt, n_tgt, stride_bytes);
-    if (rc) return rc;
-    if (n_fallback) *n_fallback = 0;
-    if (us_build) *us_build = 0.0f;
-    if (us_search) *us_search = 0.0f;
-    if (n_src == 0) return S2M_OK;
-    if (n_tgt == 0) {                                       // no target: no source has a match
-        for (size_t i = 0; keys && i < n_src; i++) keys[i] = ~0ull;
-        S2M_HIP(h, hipStreamSynchronize(h->loop.stream));
-        return S2M_OK;
-    }
-    s2m_loop_params lp;
-    s2m_loop_default_params(&lp);
-    int nf = 0;
-    const hipError_t e = icp_dev_nearest(h->loop.icp, h->loop.stream, h->loop.icp_src.as<unsigned char>(), n_src, h->loop.icp_tgt.as<unsigned char>(),
-                                         n_tgt, stride_bytes, mode, loop_tuning(h, lp.icp_leaf), reinterpret_cast<unsigned long long*>(keys), &nf,
-                                         reps, us_build, us_search);
-    if (e != hipSuccess) return fail(h, S2M_ERR_HIP, "ICP nearest-neighbour search", e);
-    if (n_fallback) *n_fallback = nf;
-    return S2M_OK;
-}
-
-int s2m_debug_icp_align_device(s2m_handle h, const void* src, size_t n_src, const void* tgt, size_t n_tgt, size_t stride_bytes,
-                               const s2m_icp_params* p, s2m_icp_result* out)
-{
-    if (!h) return S2M_ERR_INVALID_ARG;
-    if (!out) return fail(h, S2M_ERR_INVALID_ARG, "null ICP result");
-    IcpParams ip;
-    int rc = icp_params_in(h, p, &ip);
-    if (rc || (rc = check_records(h, src, n_src, stride_bytes)) || (rc = check_records(h, tgt, n_tgt, stride_bytes))) return rc;   // (both before BUSY)
-    return debug_align_many(h, src, n_src, &tgt, &n_tgt, 1, stride_bytes, ip, out);
-}
-
-int s2m_debug_icp_align_many_device(s2m_handle h, const void* src, size_t n_src, const void* const* tgts, const size_t* n_tgts, int32_t n_cand,
-                                    size_t stride_bytes, const s2m_icp_params* p, s2m_icp_result* out)
-{
-    if (!h) return S2M_ERR_INVALID_ARG;
-    if (!out || !tgts || !n_tgts || n_cand < 1 || n_cand > S2M_LOOP_MAX_CANDIDATES)
-        return fail(h, S2M_ERR_INVALID_ARG, "null ICP result or target list, or not 1 .. S2M_LOOP_MAX_CANDIDATES targets");
-    IcpParams ip;
-    const int rc = icp_params_in(h, p, &ip);
-    return rc ? rc : debug_align_many(h, src, n_src, tgts, n_tgts, n_cand, stride_bytes, ip, out);
-}
-
-int s2m_debug_icp_align_guess_many_device(s2m_handle h, const void* src, size_t n_src, const void* const* tgts, const size_t* n_tgts,
-                                          const float* guesses, int32_t n_cand, size_t stride_bytes, const s2m_icp_params* p, s2m_icp_result* out)
-{
-    if (!h) return S2M_ERR_INVALID_ARG;
-    if (!out || !tgts || !n_tgts || n_cand < 1 || n_cand > S2M_LOOP_MAX_CANDIDATES)
-        return fail(h, S2M_ERR_INVALID_ARG, "null ICP result or target list, or not 1 .. S2M_LOOP_MAX_CANDIDATES targets");
-    IcpParams ip;
-    int rc = icp_params_in(h, p, &ip);
-    for (int32_t i = 0; !rc && guesses && i < n_cand; i++) rc = guess_ok(h, guesses + 16 * (size_t)i);
-    return rc ? rc : debug_align_many(h, src, n_src, tgts, n_tgts, n_cand, stride_bytes, ip, out, guesses);
-}
-
-// P host pairs through the table form of the device loop, waited for: the clouds staged in the arena of a many-keys pass
-int s2m_debug_icp_align_pairs_device(s2m_handle h, const void* const* srcs, const size_t* n_srcs, const void* const* tgts, const size_t* n_tgts,
-                                     int32_t n_pairs, size_t stride_bytes, const float* const* guesses, const s2m_icp_params* p, s2m_icp_result* out)
-{
-    if (!h) return S2M_ERR_INVALID_ARG;
-    if (!out || !srcs || !n_srcs || !tgts || !n_tgts || n_pairs < 1 || n_pairs > kIcpMaxPairs)
-        return fail(h, S2M_ERR_INVALID_ARG, "null ICP results or cloud lists, or not 1 .. 64 pairs");
-    IcpParams ip;
-    int rc = icp_params_in(h, p, &ip);
-    for (int32_t k = 0; !rc && k < n_pairs; k++) {
-        if ((rc = check_records(h, srcs[k], n_srcs[k], stride_bytes)) || (rc = check_records(h, tgts[k], n_tgts[k], stride_bytes))) break;
-        if (guesses && guesses[k]) rc = guess_ok(h, guesses[k]);
-    }
-    if (rc || (rc = debug_stage(h, nullptr, 0, nullptr, 0, stride_bytes))) return rc;             // (BUSY, the loop stream)
-    s2m_context::LoopClosure& L = h->loop;
-    const unsigned char *d_src[kIcpMaxPairs], *d_tgt[kIcpMaxPairs];
-    size_t ns[kIcpMaxPairs], nt[kIcpMaxPairs];
-    const float* guess[kIcpMaxPairs];
-    int pair_of[kIcpMaxPairs];
-    int pairs = 0;
-    size_t total = 0;
-    const auto room = [&](size_t n) { return (n * stride_bytes + 255) / 256 * 256; };
-    for (int32_t k = 0; k < n_pairs; k++) if (n_srcs[k] && n_tgts[k]) total += room(n_srcs[k]) + room(n_tgts[k]);
-    L.many_used = 0;
-    if ((rc = arena_reserve(h, L.stream, total))) return rc;
-    unsigned char* at = L.many_arena.as<unsigned char>();
-    for (int32_t k = 0; k < n_pairs; k++) {
-        pair_of[k] = -1;
-        if (!n_srcs[k] || !n_tgts[k]) continue;
-        S2M_HIP(h, hipMemcpyAsync(at, srcs[k], n_srcs[k] * stride_bytes, hipMemcpyHostToDevice, L.stream));
-        d_src[pairs] = at; ns[pairs] = n_srcs[k];
-        at += room(n_srcs[k]);
-        S2M_HIP(h, hipMemcpyAsync(at, tgts[k], n_tgts[k] * stride_bytes, hipMemcpyHostToDevice, L.stream));
-        d_tgt[pairs] = at; nt[pairs] = n_tgts[k];
-        at += room(n_tgts[k]);
-        guess[pairs] = guesses ? guesses[k] : nullptr;
-        pair_of[k] = pairs++;
-    }
-    IcpResult r[kIcpMaxPairs];
-    if (pairs) {
-        s2m_loop_params lp;
-        s2m_loop_default_params(&lp);
-        hipError_t e = icp_pairs_begin(L.icp, L.stream, d_src, ns, d_tgt, nt, pairs, stride_bytes, ip, loop_tuning(h, lp.icp_leaf), guess);
-        bool done = false;
-        if (e == hipSuccess) e = icp_pairs_advance(L.icp, L.stream, true, &done, r);
-        if (e != hipSuccess || !done) {
-            (void)hipStreamSynchronize(L.stream);
-            icp_dev_cancel(L.icp);
-            return fail(h, S2M_ERR_HIP, "ICP device loop over pairs", e);
-        }
-    }
-    S2M_HIP(h, hipStreamSynchronize(L.stream));
-    for (int32_t k = 0; k < n_pairs; k++) icp_result_out(pair_of[k] >= 0 ? r[pair_of[k]] : icp_result_none(), &out[k]);
-    return S2M_OK;
-}
-
-int s2m_debug_icp_grid_check_args(const void* const* tgts, const size_t* n_tgts, int32_t n_cand, size_t stride_bytes, const s2m_debug_icp_grid_out* out)
-{
-    if (!out || !tgts || !n_tgts || n_cand < 1 || n_cand > S2M_LOOP_MAX_CANDIDATES) return S2M_ERR_INVALID_ARG;
-    if (stride_bytes < 12 || (stride_bytes & 3)) return S2M_ERR_INVALID_ARG;
-    for (int32_t i = 0; i < n_cand; i++) {
-        if (!tgts[i] || n_tgts[i] == 0 || (reinterpret_cast<uintptr_t>(tgts[i]) & 3) != 0) return S2M_ERR_INVALID_ARG;
-        if (n_tgts[i] > (size_t)0x3fffffff) return S2M_ERR_CAPACITY;
-    }
-    return S2M_OK;
-}
-
-int s2m_debug_icp_grid(s2m_handle h, const void* const* tgts, const size_t* n_tgts, int32_t n_cand, size_t stride_bytes,
-                       s2m_debug_icp_grid_out* out, int32_t* const* cell_start, int32_t* const* cell_end, int32_t* const* order)
-{
-    static_assert(S2M_DEBUG_ICP_GRID_MAX_CELLS == kIcpGridMaxCells, "the header's array size is the grid's");
-    static_assert(sizeof(s2m_debug_icp_grid_out) == sizeof(IcpGridInfo) && sizeof(int32_t) == sizeof(int), "filled in place");
-    if (!h) return S2M_ERR_INVALID_ARG;
-    int rc = s2m_debug_icp_grid_check_args(tgts, n_tgts, n_cand, stride_bytes, out);
-    if (rc) return fail(h, rc, "grid: 1 .. S2M_LOOP_MAX_CANDIDATES non-empty targets of 4-byte aligned records (stride >= 12, a multiple of 4), an output array");
-    if ((rc = debug_stage(h, nullptr, 0, nullptr, 0, stride_bytes))) return rc;                  // (BUSY, the loop stream)
-    s2m_context::LoopClosure& L = h->loop;
-    const unsigned char* d_tgt[S2M_LOOP_MAX_CANDIDATES];
-    for (int32_t i = 0; i < n_cand; i++) {
-        if ((rc = ensure(h, L.target(i), n_tgts[i] * stride_bytes))) return rc;
-        S2M_HIP(h, hipMemcpyAsync(L.target(i).p, tgts[i], n_tgts[i] * stride_bytes, hipMemcpyHostToDevice, L.stream));
-        d_tgt[i] = L.target(i).as<unsigned char>();
-    }
-    s2m_loop_params lp;
-    s2m_loop_default_params(&lp);
-    const hipError_t e = icp_dev_grid(L.icp, L.stream, d_tgt, n_tgts, n_cand, stride_bytes, loop_tuning(h, lp.icp_leaf),
-                                      reinterpret_cast<IcpGridInfo*>(out), cell_start, cell_end, order);
-    if (e != hipSuccess) {
-        (void)hipStreamSynchronize(L.stream);
-        return fail(h, S2M_ERR_HIP, "ICP grid", e);
-    }
-    return S2M_OK;
-}
-
-// ---- the close and the sums of an ICP iteration on their own (tests/test_icp_close_gpu.py) ------------------------------------
-
-int s2m_debug_icp_close_check_args(int32_t n, const double* sums, const s2m_debug_icp_state* in, const s2m_icp_params* p, const s2m_debug_icp_state* out)
-{
-    if (n < 1 || n > S2M_LOOP_MANY_MAX_PAIRS || !sums || !in || !out) return S2M_ERR_INVALID_ARG;
-    if (p && (!(p->max_correspondence_distance > 0.0) || p->max_iterations < 1)) return S2M_ERR_INVALID_ARG;
-    return S2M_OK;
-}
-
-int s2m_debug_icp_close(s2m_handle h, int32_t n, const double* sums, const s2m_debug_icp_state* in, const s2m_icp_params* p, s2m_debug_icp_state* out)
-{
-    static_assert(sizeof(s2m_debug_icp_state) == sizeof(IcpLoopState) && offsetof(s2m_debug_icp_state, prev_mse) == offsetof(IcpLoopState, prev_mse) &&
-                  offsetof(s2m_debug_icp_state, done) == offsetof(IcpLoopState, done), "handed over in place");
-    static_assert(S2M_LOOP_MANY_MAX_PAIRS == kIcpMaxPairs, "a block per pair of the table");
-    if (!h) return S2M_ERR_INVALID_ARG;
-    int rc = s2m_debug_icp_close_check_args(n, sums, in, p, out);
-    if (rc) return fail(h, rc, "close: 1 .. S2M_LOOP_MANY_MAX_PAIRS rows of sums and states, valid ICP parameters");
-    IcpParams ip;
-    if ((rc = icp_params_in(h, p, &ip)) || (rc = debug_stage(h, nullptr, 0, nullptr, 0, 16))) return rc;     // (BUSY, the loop stream)
-    const hipError_t e = icp_dev_close(h->loop.icp, h->loop.stream, n, sums, reinterpret_cast<const IcpLoopState*>(in), ip,
-                                       reinterpret_cast<IcpLoopState*>(out));
-    if (e != hipSuccess) {
-        (void)hipStreamSynchronize(h->loop.stream);
-        return fail(h, S2M_ERR_HIP, "ICP close", e);
-    }
-    return S2M_OK;
-}
-
-int s2m_debug_icp_sums_check_args(const void* const* srcs, const size_t* n_srcs, const void* const* tgts, const size_t* n_tgts, int32_t n_pairs,
-                                  size_t stride_bytes, int32_t form, const double* sums, const int32_t* n_rows)
-{
-    if (form != S2M_DEBUG_ICP_SUMS_SLOTS && form != S2M_DEBUG_ICP_SUMS_TABLE) return S2M_ERR_INVALID_ARG;
-    if (!srcs || !n_srcs || !tgts || !n_tgts || !sums || !n_rows) return S2M_ERR_INVALID_ARG;
-    if (n_pairs < 1 || n_pairs > (form == S2M_DEBUG_ICP_SUMS_TABLE ? S2M_LOOP_MANY_MAX_PAIRS : S2M_LOOP_MAX_CANDIDATES)) return S2M_ERR_INVALID_ARG;
-    if (stride_bytes < 12 || (stride_bytes & 3)) return S2M_ERR_INVALID_ARG;
-    for (int32_t k = 0; k < n_pairs; k++) {
-        if (!srcs[k] || !tgts[k] || n_srcs[k] == 0 || n_tgts[k] == 0) return S2M_ERR_INVALID_ARG;
-        if ((reinterpret_cast<uintptr_t>(srcs[k]) & 3) != 0 || (reinterpret_cast<uintptr_t>(tgts[k]) & 3) != 0) return S2M_ERR_INVALID_ARG;
-        if (n_srcs[k] > (size_t)0x3fffffff || n_tgts[k] > (size_t)0x3fffffff) return S2M_ERR_CAPACITY;
-        if (form == S2M_DEBUG_ICP_SUMS_SLOTS && (srcs[k] != srcs[0] || n_srcs[k] != n_srcs[0])) return S2M_ERR_INVALID_ARG;
-    }
-    return S2M_OK;
-}
-
-int s2m_debug_icp_sums(s2m_handle h, const void* const* srcs, const size_t* n_srcs, const void* const* tgts, const size_t* n_tgts, int32_t n_pairs,
-                       size_t stride_bytes, int32_t form, double max_correspondence_distance, double* sums, int32_t* n_rows,
-                       double* const* parts, uint64_t* const* keys)
-{
-    static_assert(S2M_LOOP_MAX_CANDIDATES == kIcpMaxSlots && sizeof(int32_t) == sizeof(int), "a slot per target; n_rows filled in place");
-    if (!h) return S2M_ERR_INVALID_ARG;
-    int rc = s2m_debug_icp_sums_check_args(srcs, n_srcs, tgts, n_tgts, n_pairs, stride_bytes, form, sums, n_rows);
-    if (rc) return fail(h, rc, "sums: non-empty clouds of 4-byte aligned records, 1 .. 8 targets of one source (slots) or 1 .. 64 pairs (table)");
-    if (!(max_correspondence_distance > 0.0)) return fail(h, S2M_ERR_INVALID_ARG, "ICP needs a positive correspondence distance");
-    if ((rc = debug_stage(h, nullptr, 0, nullptr, 0, stride_bytes))) return rc;                  // (BUSY, the loop stream)
-    const bool table = form == S2M_DEBUG_ICP_SUMS_TABLE;
-    s2m_context::LoopClosure& L = h->loop;
-    const unsigned char *d_src[kIcpMaxPairs], *d_tgt[kIcpMaxPairs];
-    const auto room = [&](size_t n) { return (n * stride_bytes + 255) / 256 * 256; };
-    size_t total = 0;
-    for (int32_t k = 0; k < n_pairs; k++) total += (table || k == 0 ? room(n_srcs[k]) : 0) + room(n_tgts[k]);
-    L.many_used = 0;
-    if ((rc = arena_reserve(h, L.stream, total))) return rc;
-    unsigned char* at = L.many_arena.as<unsigned char>();
-    for (int32_t k = 0; k < n_pairs; k++) {
-        if (table || k == 0) {
-            S2M_HIP(h, hipMemcpyAsync(at, srcs[k], n_srcs[k] * stride_bytes, hipMemcpyHostToDevice, L.stream));
-            d_src[k] = at;
-            at += room(n_srcs[k]);
-        } else {
-            d_src[k] = d_src[0];
-        }
-        S2M_HIP(h, hipMemcpyAsync(at, tgts[k], n_tgts[k] * stride_bytes, hipMemcpyHostToDevice, L.stream));
-        d_tgt[k] = at;
-        at += room(n_tgts[k]);
-    }
-    s2m_loop_params lp;
-    s2m_loop_default_params(&lp);
-    const hipError_t e = icp_dev_sums(L.icp, L.stream, table, d_src, n_srcs, d_tgt, n_tgts, n_pairs, stride_bytes, max_correspondence_distance,
-                                      loop_tuning(h, lp.icp_leaf), sums, n_rows, parts, reinterpret_cast<unsigned long long* const*>(keys));
-    if (e != hipSuccess) {
-        (void)hipStreamSynchronize(L.stream);
-        return fail(h, S2M_ERR_HIP, "ICP sums", e);
-    }
-    return S2M_OK;
-}

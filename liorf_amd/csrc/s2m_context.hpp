@@ -552,6 +552,59 @@ int sc_query_device_scan(s2m_context* h, const void* d_pts, size_t n, size_t str
 int loop_busy(s2m_context* h);
 // waits for the loop stream and forgets the pending closure (s2m_kf_reset, s2m_destroy); `destroy`: the stream and event go too
 void loop_drop_pending(s2m_context* h, bool destroy);
+// what the loop closure shares with the alignment of host clouds (s2m_abi_icp.hip) and the relocalisation (s2m_abi_reloc.hip):
+// the loop stream and its event exist; the handle's tuning of the device loop at a leaf; the caller's ICP parameters (null: the
+// defaults) and an initial guess, validated; a result in the ABI's form
+int loop_stream(s2m_context* h);
+s2m::IcpTuning loop_tuning(const s2m_context* h, float leaf);
+int icp_params_in(s2m_context* h, const s2m_icp_params* p, s2m::IcpParams* ip);
+int guess_ok(s2m_context* h, const float* g);
+void icp_result_out(const s2m::IcpResult& r, s2m_icp_result* out);
+// the caller's loop parameters (null: the defaults), validated; the ICP parameters of a closure; a key of a store of N
+int loop_params(s2m_context* h, const s2m_loop_params* p, s2m_loop_params* prm);
+s2m::IcpParams loop_icp_params(const s2m_loop_params& prm);
+bool loop_key_ok(int32_t k, size_t N);
+int loop_submap(s2m_context* h, int32_t key, int32_t search_num, int32_t loop_index, float leaf, DevBuf& dst, VoxResult* res,
+                long long clamp_lo = 0, long long clamp_hi = -1);
+// The alignments a caller wants run together, in the form it names (s2m::IcpSet): it adds them as its gates leave them open and
+// reads res[k] of alignment k once they have run. who[k]: the caller's own index of alignment k - its candidate, its record -
+// so that no caller keeps a table beside the list. The slot form takes the same source with every add. arena: the clouds are
+// offsets (add_at) in this buffer, which may move while it grows, and become addresses when the set is made.
+struct IcpList {
+    const s2m::IcpForm form;
+    const size_t       stride;
+    const DevBuf*      arena;
+    int                n = 0;
+    uintptr_t          src[s2m::kIcpMaxPairs], tgt[s2m::kIcpMaxPairs];
+    size_t             n_src[s2m::kIcpMaxPairs], n_tgt[s2m::kIcpMaxPairs], who[s2m::kIcpMaxPairs];
+    const float*       guess[s2m::kIcpMaxPairs];
+    s2m::IcpResult     res[s2m::kIcpMaxPairs];
+    const unsigned char *d_src[s2m::kIcpMaxPairs], *d_tgt[s2m::kIcpMaxPairs];       // (made by set())
+    IcpList(s2m::IcpForm f, size_t stride_bytes, const DevBuf* in = nullptr) : form(f), stride(stride_bytes), arena(in) {}
+    // the alignment's index
+    int add_at(uintptr_t s, size_t ns, uintptr_t t, size_t nt, const float* g, size_t w)
+    {
+        src[n] = s; n_src[n] = ns; tgt[n] = t; n_tgt[n] = nt; guess[n] = g; who[n] = w;
+        return n++;
+    }
+    int add(const void* s, size_t ns, const void* t, size_t nt, const float* g, size_t w)
+    {
+        return add_at(reinterpret_cast<uintptr_t>(s), ns, reinterpret_cast<uintptr_t>(t), nt, g, w);
+    }
+    s2m::IcpSet set()
+    {
+        const uintptr_t base = arena ? reinterpret_cast<uintptr_t>(arena->p) : 0;
+        for (int k = 0; k < n; k++) {
+            d_src[k] = reinterpret_cast<const unsigned char*>(base + src[k]);
+            d_tgt[k] = reinterpret_cast<const unsigned char*>(base + tgt[k]);
+        }
+        return s2m::IcpSet{ form, n, d_src, n_src, d_tgt, n_tgt, guess, stride };
+    }
+};
+int icp_list_align(s2m_context* h, hipStream_t stream, IcpList& al, const s2m::IcpParams& ip, float leaf, const char* what);
+// `bytes` of src (kind: from the host or from the device) to the end of the many-keys arena, on `stream`, a stretch rounded up to
+// 256 bytes; *off: where they start. The many_used bytes the arena holds are kept when it grows (the caller starts at 0).
+int arena_put(s2m_context* h, hipStream_t stream, const void* src, hipMemcpyKind kind, size_t bytes, size_t* off);
 
 // ---- s2m_abi_pose_graph.hip ----
 // waits for the pose-graph stream and forgets the pending optimise (s2m_pg_reset, s2m_destroy); `destroy`: stream, events and the

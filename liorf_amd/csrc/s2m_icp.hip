@@ -22,8 +22,9 @@
 // The loop carries up to kIcpMaxSlots alignments of one source at once, the slot a grid dimension of every kernel; the single
 // alignment is its one-slot case. Every slot owns its moving copy of the source, so each may start from a guess of its own
 // (align(output, guess): IcpGuesses, the source moved as it is loaded, the state's T started at the guess).
-// A second layout beside the slots carries up to kIcpMaxPairs alignments that each have a source of their own (icp_pairs_*, what
-// s2m_loop_verify_many queues): the pairs' descriptions are a table in device memory, uploaded once per alignment set. The kernels
+// A second layout beside the slots carries up to kIcpMaxPairs alignments that each have a source of their own (IcpForm::kTable, what
+// s2m_loop_verify_many queues): the pairs' descriptions are a table in device memory, uploaded once per alignment set. The host
+// starts and advances either form through one driver over one layout (s2m_icp_layout.hpp); the caller names the form. The kernels
 // of the loop are written once over "the view of slot s" and instantiated for both layouts; what a kernel derives from the launch
 // where all slots share n_src (the partial rows, the stride over the source) is the pair's own in the table form.
 // The kernels are one set but for two. The host loop (icp_align) launches the loop's load, reset, sums and fold on the one-slot
@@ -38,6 +39,7 @@
 #include <cmath>
 #include <cstring>
 #include <new>
+#include <type_traits>
 
 #include "s2m_icp_close.hpp"
 
@@ -45,10 +47,7 @@ namespace s2m {
 
 namespace {
 
-constexpr int kNnThreads = 256;
-constexpr int kNnTile = 1024;                       // target points per LDS tile
-constexpr unsigned long long kNoMatch = ~0ull;
-constexpr int kSumBlocks = 256;                     // most k_icp_sums_dev workgroups: rows of the partial-sum buffer
+constexpr unsigned long long kNoMatch = ~0ull;      // (kNnThreads, kNnTile, kSumBlocks: s2m_icp_layout.hpp)
 
 struct Buf {
     void*  p = nullptr;
@@ -169,11 +168,6 @@ __device__ __forceinline__ bool done_guard(const IcpDevBlock* blk, int phase) { 
 // the cell coordinate along one axis before floor and clamp: non-decreasing in x (a subtraction of and a product with constants)
 __device__ __forceinline__ float cell_coord(float x, float lo, float inv) { return (x - lo) * inv; }
 
-// The slots of the loop: one source against K <= kIcpMaxSlots targets, K independent alignments advanced by the same launches.
-// Every kernel of the loop takes this struct by value (as k_icp_transform takes Mat34: nothing is uploaded per launch) and its
-// slot from blockIdx.z; grids are sized by the largest slot and a workgroup beyond its own slot's extent returns at entry.
-// Inside a slot nothing differs from the single alignment, which is the K = 1 case: the same per-point arithmetic, the same
-// (d2, original index) minimum, the same number of partial rows (it depends on n_src only), the same fold, the same close.
 // The view of slot s: what a kernel of the loop reads about the alignment it works on. The kernels are written once over it and
 // instantiated twice: for IcpSlots by value, which builds the view from its arrays (n_src shared, rows and guess not in it: the
 // launch carries them), and for the pair table (IcpPairs), whose entries are views in device memory with every field the pair's own.
@@ -741,19 +735,21 @@ struct IcpWorkspace {
     hipEvent_t ev = nullptr;
     struct Flight {
         int phase = 0;                   // 0 none, 1 a range of iterations is queued, 2 the fitness pass is queued
-        int n_src = 0, queued = 0;
-        bool pairs = false;              // the table form: the sources are the table's (d_src, n_src: the largest pair's extent)
-        const unsigned char* d_src = nullptr;
-        size_t stride = 0;
+        int queued = 0;
         IcpParams prm{};
         IcpTuning tune{};
     } fl;
-    // the slots the buffers are laid out for (dev_layout): what every kernel of the loop gets by value, and the launch shapes
+    // The set the buffers are laid out for (dev_layout): its form, the stride of its records and a view per alignment - the
+    // table's in h_tab, the slots' in slot_view, with the records each is loaded from (the fitness pass loads the sources again).
+    IcpForm form = IcpForm::kSlots;
+    size_t stride = 0;
+    IcpView slot_view[kIcpMaxSlots]{};
+    // what the kernels of the loop take: the slots by value with their guesses, made from the views, or the table's address
     IcpSlots S{};
-    IcpPairs P{};                        // the table the buffers are laid out for (pairs_layout)
-    // what the launches are sized by: slots or pairs, and the most of any of them (the slots share n_src and its rows)
+    IcpGuesses G{};
+    IcpPairs P{};
+    // what the launches are sized by: the alignments, and the most of any of them (the slots share n_src and its rows)
     int K = 0, n_tgt_max = 0, slices_max = 0, n_src_max = 0, rows_max = 0;
-    IcpGuesses G{};                      // the slots' initial guesses; dev_layout leaves none, set_guesses sets them for one alignment
 };
 
 IcpWorkspace* icp_create()
@@ -787,68 +783,12 @@ void icp_destroy(IcpWorkspace* w)
 
 namespace {
 
-void nn_shape(int n_src, int n_tgt, int* sb_out, int* slices_out, int* slice_len_out)
-{
-    const int sb = (n_src + kNnThreads - 1) / kNnThreads;
-    int slices = (1024 + sb - 1) / sb;                                   // ~1000 workgroups in flight
-    slices = std::max(1, std::min(slices, (n_tgt + kNnTile - 1) / kNnTile));
-    const int slice_len = (((n_tgt + slices - 1) / slices) + kNnTile - 1) / kNnTile * kNnTile;
-    *sb_out = sb; *slices_out = (n_tgt + slice_len - 1) / slice_len; *slice_len_out = slice_len;
-}
-
 bool guess_is_identity(const float* g)
 {
     for (int i = 0; i < 16; i++) if (g[i] != ((i % 5 == 0) ? 1.0f : 0.0f)) return false;
     return true;
 }
 
-// The buffers of K slots - one source of n_src points, targets of n_tgt[k] - and w->S, their layout: a slot's moving source, keys,
-// partial rows and list are n_src (rows) apiece, its target and sorted target start where the slot before ends. Slot 0 starts
-// every buffer; the host loop (icp_align) runs on the K = 1 layout. tune: the device loop's list and, with the grid on, its
-// cell arrays are laid out too (nullptr: the host loop, which has neither).
-hipError_t dev_layout(IcpWorkspace* w, int K, size_t n_src, const size_t* n_tgt, const IcpTuning* tune)
-{
-    if (K < 1 || K > kIcpMaxSlots) return hipErrorInvalidValue;
-    size_t total = 0, most = 0;
-    for (int k = 0; k < K; k++) { total += n_tgt[k]; most = std::max(most, n_tgt[k]); }
-    if (n_src > (size_t)0x3fffffff || total > (size_t)0x3fffffff) return hipErrorInvalidValue;
-    const size_t rows = (size_t)std::min(((int)n_src + 255) / 256, kSumBlocks);
-    ICP_TRY(w->cur.ensure(sizeof(float4) * n_src * K)); ICP_TRY(w->tgt.ensure(sizeof(float4) * total));
-    ICP_TRY(w->best.ensure(sizeof(unsigned long long) * n_src * K));
-    ICP_TRY(w->part.ensure(sizeof(double) * 17 * rows * K));
-    const bool grid = tune && tune->use_grid;
-    if (tune) ICP_TRY(w->list.ensure(sizeof(int) * n_src * K));
-    if (grid) {
-        ICP_TRY(w->gcount.ensure(sizeof(int) * kGridMaxCells * (size_t)K)); ICP_TRY(w->gstart.ensure(sizeof(int) * kGridMaxCells * (size_t)K));
-        ICP_TRY(w->gend.ensure(sizeof(int) * kGridMaxCells * (size_t)K)); ICP_TRY(w->gsorted.ensure(sizeof(float4) * total));
-    }
-    IcpSlots S{};
-    size_t off = 0;
-    int slices_max = 1;
-    for (int k = 0; k < K; k++) {
-        S.cur[k] = w->cur.as<float4>() + n_src * k; S.tgt[k] = w->tgt.as<float4>() + off;
-        S.best[k] = w->best.as<unsigned long long>() + n_src * k; S.part[k] = w->part.as<double>() + 17 * rows * k;
-        S.list[k] = tune ? w->list.as<int>() + n_src * k : nullptr;
-        S.gsorted[k] = grid ? w->gsorted.as<float4>() + off : nullptr;
-        S.n_tgt[k] = (int)n_tgt[k];
-        int sb = 0, slices = 1;
-        if (n_src && n_tgt[k]) nn_shape((int)n_src, (int)n_tgt[k], &sb, &slices, &S.slice_len[k]);
-        slices_max = std::max(slices_max, slices);
-        off += n_tgt[k];
-    }
-    S.blk = w->blk.as<IcpDevBlock>();
-    S.gcount = w->gcount.as<int>(); S.gstart = w->gstart.as<int>(); S.gend = w->gend.as<int>();
-    S.n_src = (int)n_src;
-    w->S = S; w->K = K; w->n_tgt_max = (int)most; w->slices_max = slices_max;
-    w->n_src_max = (int)n_src; w->rows_max = (int)rows;
-    w->G = IcpGuesses{};
-    return hipSuccess;
-}
-
-// The buffers of P pairs - sources of n_src[k] points, targets of n_tgt[k] - and their table in w->h_tab: the buffers are the
-// slots' own, a pair's stretch of each starting where the pair before ends (cur, best, list by sources; tgt, gsorted by targets;
-// part by rows), the blocks and the cell arrays one per pair. A pair's rows and slices are those of the single alignment of its
-// sizes. The table still has to be uploaded (pairs_upload).
 // what only the table form needs, once: blocks and their pinned mirror for kIcpMaxPairs, the table and its pinned image
 // (nothing is in flight: the old blocks hold nothing that is still wanted)
 hipError_t pairs_room(IcpWorkspace* w)
@@ -865,148 +805,166 @@ hipError_t pairs_room(IcpWorkspace* w)
     return hipSuccess;
 }
 
-hipError_t pairs_layout(IcpWorkspace* w, int P, const unsigned char* const* d_src, const size_t* n_src, const unsigned char* const* d_tgt,
-                        const size_t* n_tgt, const IcpTuning& tune, const float* const* guess)
+IcpView* views(IcpWorkspace* w) { return w->form == IcpForm::kTable ? w->h_tab : w->slot_view; }
+
+// The buffers of a set and its views: the buffers are one set for both forms, an alignment's stretch of each starting where the
+// one before ends (icp_layout: cur, best, list by sources; tgt, gsorted by targets; part by rows), the blocks and the cell arrays
+// one per alignment; alignment 0 starts every buffer. An alignment's rows and slices are those of the single alignment of its
+// sizes. A guess that is null or the identity leaves its alignment without one (`guess != Identity`, as PCL tests it), so that it
+// runs what it ran before there were guesses. The slots and their guesses are then filled from the views; the table is the views
+// themselves, in h_tab, and still has to be uploaded (dev_set_up). The host loop (icp_align) runs on the one-slot layout.
+// tune: the device loop's list and, with the grid on, its cell arrays are laid out too (nullptr: the host loop, which has neither).
+hipError_t dev_layout(IcpWorkspace* w, const IcpSet& a, const IcpTuning* tune)
 {
-    if (P < 1 || P > kIcpMaxPairs) return hipErrorInvalidValue;
-    size_t tot_src = 0, tot_tgt = 0, tot_rows = 0, most_src = 0, most_tgt = 0;
-    for (int k = 0; k < P; k++) {
-        if (n_src[k] == 0 || n_tgt[k] == 0 || n_src[k] > (size_t)0x3fffffff || n_tgt[k] > (size_t)0x3fffffff) return hipErrorInvalidValue;
-        tot_src += n_src[k]; tot_tgt += n_tgt[k];
-        tot_rows += (size_t)std::min(((int)n_src[k] + 255) / 256, kSumBlocks);
-        most_src = std::max(most_src, n_src[k]); most_tgt = std::max(most_tgt, n_tgt[k]);
-    }
-    if (tot_src > (size_t)0x3fffffff || tot_tgt > (size_t)0x3fffffff) return hipErrorInvalidValue;
-    ICP_TRY(pairs_room(w));
-    ICP_TRY(w->cur.ensure(sizeof(float4) * tot_src)); ICP_TRY(w->tgt.ensure(sizeof(float4) * tot_tgt));
-    ICP_TRY(w->best.ensure(sizeof(unsigned long long) * tot_src));
-    ICP_TRY(w->part.ensure(sizeof(double) * 17 * tot_rows));
-    ICP_TRY(w->list.ensure(sizeof(int) * tot_src));
-    const bool grid = tune.use_grid != 0;
+    const bool table = a.form == IcpForm::kTable;
+    IcpLayout L;
+    if (!icp_layout(a.n, !table, a.n_src, a.n_tgt, &L)) return hipErrorInvalidValue;
+    if (table) ICP_TRY(pairs_room(w));
+    const size_t K = (size_t)a.n;
+    ICP_TRY(w->cur.ensure(sizeof(float4) * L.tot_src)); ICP_TRY(w->tgt.ensure(sizeof(float4) * L.tot_tgt));
+    ICP_TRY(w->best.ensure(sizeof(unsigned long long) * L.tot_src));
+    ICP_TRY(w->part.ensure(sizeof(double) * 17 * L.tot_rows));
+    const bool grid = tune && tune->use_grid;
+    if (tune) ICP_TRY(w->list.ensure(sizeof(int) * L.tot_src));
     if (grid) {
-        ICP_TRY(w->gcount.ensure(sizeof(int) * kGridMaxCells * (size_t)P)); ICP_TRY(w->gstart.ensure(sizeof(int) * kGridMaxCells * (size_t)P));
-        ICP_TRY(w->gend.ensure(sizeof(int) * kGridMaxCells * (size_t)P)); ICP_TRY(w->gsorted.ensure(sizeof(float4) * tot_tgt));
+        ICP_TRY(w->gcount.ensure(sizeof(int) * kGridMaxCells * K)); ICP_TRY(w->gstart.ensure(sizeof(int) * kGridMaxCells * K));
+        ICP_TRY(w->gend.ensure(sizeof(int) * kGridMaxCells * K)); ICP_TRY(w->gsorted.ensure(sizeof(float4) * L.tot_tgt));
     }
-    size_t so = 0, to = 0, ro = 0;
-    int slices_max = 1, rows_max = 1;
-    for (int k = 0; k < P; k++) {
+    w->form = a.form; w->stride = a.stride;
+    IcpView* view = views(w);
+    for (int k = 0; k < a.n; k++) {
+        const IcpLayoutItem& at = L.at[k];
         IcpView v{};
-        v.cur = w->cur.as<float4>() + so; v.tgt = w->tgt.as<float4>() + to;
-        v.best = w->best.as<unsigned long long>() + so; v.part = w->part.as<double>() + 17 * ro;
-        v.list = w->list.as<int>() + so;
-        v.gsorted = grid ? w->gsorted.as<float4>() + to : nullptr;
+        v.cur = w->cur.as<float4>() + at.src_off; v.tgt = w->tgt.as<float4>() + at.tgt_off;
+        v.best = w->best.as<unsigned long long>() + at.src_off; v.part = w->part.as<double>() + 17 * at.row_off;
+        v.list = tune ? w->list.as<int>() + at.src_off : nullptr;
+        v.gsorted = grid ? w->gsorted.as<float4>() + at.tgt_off : nullptr;
         v.blk = w->blk.as<IcpDevBlock>() + k;
         v.gcount = grid ? w->gcount.as<int>() + (size_t)k * kGridMaxCells : nullptr;
         v.gstart = grid ? w->gstart.as<int>() + (size_t)k * kGridMaxCells : nullptr;
         v.gend = grid ? w->gend.as<int>() + (size_t)k * kGridMaxCells : nullptr;
-        v.d_src = d_src[k]; v.d_tgt = d_tgt[k];
-        v.n_src = (int)n_src[k]; v.n_tgt = (int)n_tgt[k];
-        v.rows = std::min((v.n_src + 255) / 256, kSumBlocks);
-        int sb = 0, slices = 1;
-        nn_shape(v.n_src, v.n_tgt, &sb, &slices, &v.slice_len);
-        if (guess && guess[k] && !guess_is_identity(guess[k])) { v.guess_set = 1; memcpy(v.guess, guess[k], sizeof(v.guess)); }
-        w->h_tab[k] = v;
-        slices_max = std::max(slices_max, slices); rows_max = std::max(rows_max, v.rows);
-        so += n_src[k]; to += n_tgt[k]; ro += (size_t)v.rows;
+        v.d_src = a.d_src ? a.d_src[table ? k : 0] : nullptr; v.d_tgt = a.d_tgt[k];
+        v.n_src = at.n_src; v.n_tgt = at.n_tgt; v.rows = at.rows; v.slice_len = at.slice_len;
+        if (a.guess && a.guess[k] && !guess_is_identity(a.guess[k])) { v.guess_set = 1; memcpy(v.guess, a.guess[k], sizeof(v.guess)); }
+        view[k] = v;
     }
-    w->P = IcpPairs{ w->tab.as<IcpView>() };
-    w->K = P; w->n_tgt_max = (int)most_tgt; w->slices_max = slices_max; w->n_src_max = (int)most_src; w->rows_max = rows_max;
+    if (table) {
+        w->P = IcpPairs{ w->tab.as<IcpView>() };
+    } else {
+        IcpSlots S{};
+        IcpGuesses G{};
+        for (int k = 0; k < a.n; k++) {
+            const IcpView& v = view[k];
+            S.cur[k] = v.cur; S.tgt[k] = v.tgt; S.best[k] = v.best; S.part[k] = v.part; S.list[k] = v.list; S.gsorted[k] = v.gsorted;
+            S.n_tgt[k] = v.n_tgt; S.slice_len[k] = v.slice_len;
+            if (v.guess_set) { G.set[k] = 1; memcpy(G.T[k], v.guess, sizeof(G.T[k])); }
+        }
+        S.blk = w->blk.as<IcpDevBlock>();
+        S.gcount = w->gcount.as<int>(); S.gstart = w->gstart.as<int>(); S.gend = w->gend.as<int>();
+        S.n_src = L.n_src_max;
+        w->S = S; w->G = G;
+    }
+    w->K = a.n; w->n_tgt_max = L.n_tgt_max; w->slices_max = L.slices_max; w->n_src_max = L.n_src_max; w->rows_max = L.rows_max;
     return hipSuccess;
 }
 
-hipError_t pairs_upload(IcpWorkspace* w, hipStream_t stream)
+// The one dispatch from the layout's form to what its kernels take: the slots by value with their guesses, or the table's
+// address, whose guesses are in the views. f: a generic lambda (S, G); a kernel is instantiated for the type of S it is given.
+template <class F>
+hipError_t with_form(IcpWorkspace* w, F&& f)
 {
-    return hipMemcpyAsync(w->tab.p, w->h_tab, sizeof(IcpView) * (size_t)w->K, hipMemcpyHostToDevice, stream);
+    return w->form == IcpForm::kTable ? f(w->P, IcpPairGuesses{ 0 }) : f(w->S, w->G);
 }
 
-// the table's loads: what = 0 the targets, 1 the sources as they are, 2 the sources moved by their guesses
-hipError_t load_pairs(IcpWorkspace* w, hipStream_t stream, size_t stride, int what)
+// records -> float4 for every alignment of the layout. what (IcpPairLoad's codes): the targets, the sources as they are (the
+// fitness pass) or the sources moved by their guesses, each slot's into its own moving copy
+enum { kLoadTargets = 0, kLoadSources = 1, kLoadSourcesMoved = 2 };
+hipError_t load(IcpWorkspace* w, hipStream_t stream, int what)
 {
-    const int most = what == 0 ? w->n_tgt_max : w->n_src_max;
-    hipLaunchKernelGGL(k_icp_load_slots<IcpPairLoad>, dim3((most + 255) / 256, 1, w->K), dim3(256), 0, stream, IcpPairLoad{ w->P.t, what }, stride);
-    return hipGetLastError();
-}
-
-// the guesses of the layout's slots: guess[k] (row-major 4x4) for slot k; a null list, a null entry or the identity leave the slot
-// without one (`guess != Identity`, as PCL tests it), so that slot runs what it ran before there were guesses
-void set_guesses(IcpWorkspace* w, const float* const* guess)
-{
-    w->G = IcpGuesses{};
-    for (int k = 0; guess && k < w->K; k++) {
-        if (!guess[k] || guess_is_identity(guess[k])) continue;
-        memcpy(w->G.T[k], guess[k], sizeof(w->G.T[k]));
-        w->G.set[k] = 1;
+    const int most = what == kLoadTargets ? w->n_tgt_max : w->n_src_max;
+    const dim3 grid((most + 255) / 256, 1, w->K);
+    if (w->form == IcpForm::kTable) {
+        hipLaunchKernelGGL(k_icp_load_slots<IcpPairLoad>, grid, dim3(256), 0, stream, IcpPairLoad{ w->P.t, what }, w->stride);
+        return hipGetLastError();
     }
-}
-
-// records -> float4: the K targets of the layout, or the one source into every slot's moving copy (guessed: moved by the slot's guess)
-hipError_t load_slots(IcpWorkspace* w, hipStream_t stream, const unsigned char* d_src, const unsigned char* const* d_tgt, size_t stride,
-                      bool guessed = false)
-{
     IcpLoad L{};
-    int most = 0;
     for (int k = 0; k < w->K; k++) {
-        L.src[k] = d_tgt ? d_tgt[k] : d_src;
-        L.dst[k] = d_tgt ? const_cast<float4*>(w->S.tgt[k]) : w->S.cur[k];
-        L.n[k] = d_tgt ? w->S.n_tgt[k] : w->S.n_src;
-        most = std::max(most, L.n[k]);
-        if (guessed && !d_tgt && w->G.set[k]) { L.move[k] = 1; memcpy(L.m[k], w->G.T[k], sizeof(L.m[k])); }
+        const IcpView& v = w->slot_view[k];
+        L.src[k] = what == kLoadTargets ? v.d_tgt : v.d_src;
+        L.dst[k] = what == kLoadTargets ? const_cast<float4*>(v.tgt) : v.cur;
+        L.n[k] = what == kLoadTargets ? v.n_tgt : v.n_src;
+        if (what == kLoadSourcesMoved && v.guess_set) { L.move[k] = 1; memcpy(L.m[k], v.guess, sizeof(L.m[k])); }
     }
-    hipLaunchKernelGGL(k_icp_load_slots<IcpLoad>, dim3((most + 255) / 256, 1, w->K), dim3(256), 0, stream, L, stride);
+    hipLaunchKernelGGL(k_icp_load_slots<IcpLoad>, grid, dim3(256), 0, stream, L, w->stride);
     return hipGetLastError();
 }
 
-// the block reset of every slot of the layout and, with the grid on: box, shape, counts, scan, scatter - once per alignment
-template <class V, class GV>
-hipError_t dev_prepare_v(IcpWorkspace* w, hipStream_t stream, const IcpTuning& tune, const V& S, const GV& G)
+// the block reset of every alignment of the layout and, with the grid on: box, shape, counts, scan, scatter - once per set
+hipError_t dev_prepare(IcpWorkspace* w, hipStream_t stream, const IcpTuning& tune)
 {
-    const unsigned K = (unsigned)w->K;
-    hipLaunchKernelGGL((k_icp_begin<V, GV>), dim3(1, 1, K), dim3(64), 0, stream, S, G);
-    if (tune.use_grid) {
-        ICP_TRY(hipMemsetAsync(w->gcount.p, 0, sizeof(int) * kGridMaxCells * (size_t)K, stream));
-        const int tb = (w->n_tgt_max + 255) / 256;
-        hipLaunchKernelGGL(k_icp_grid_bbox<V>, dim3(std::min(tb, 256), 1, K), dim3(256), 0, stream, S);
-        hipLaunchKernelGGL(k_icp_grid_setup<V>, dim3(1, 1, K), dim3(64), 0, stream, S, tune.cell);
-        hipLaunchKernelGGL(k_icp_grid_count<V>, dim3(tb, 1, K), dim3(256), 0, stream, S);
-        hipLaunchKernelGGL(k_icp_grid_scan<V>, dim3(1, 1, K), dim3(1024), 0, stream, S);
-        hipLaunchKernelGGL(k_icp_grid_scatter<V>, dim3(tb, 1, K), dim3(256), 0, stream, S);
-    }
-    return hipGetLastError();
+    return with_form(w, [&](const auto& S, const auto& G) -> hipError_t {
+        using V = std::decay_t<decltype(S)>;
+        using GV = std::decay_t<decltype(G)>;
+        const unsigned K = (unsigned)w->K;
+        hipLaunchKernelGGL((k_icp_begin<V, GV>), dim3(1, 1, K), dim3(64), 0, stream, S, G);
+        if (tune.use_grid) {
+            ICP_TRY(hipMemsetAsync(w->gcount.p, 0, sizeof(int) * kGridMaxCells * (size_t)K, stream));
+            const int tb = (w->n_tgt_max + 255) / 256;
+            hipLaunchKernelGGL(k_icp_grid_bbox<V>, dim3(std::min(tb, 256), 1, K), dim3(256), 0, stream, S);
+            hipLaunchKernelGGL(k_icp_grid_setup<V>, dim3(1, 1, K), dim3(64), 0, stream, S, tune.cell);
+            hipLaunchKernelGGL(k_icp_grid_count<V>, dim3(tb, 1, K), dim3(256), 0, stream, S);
+            hipLaunchKernelGGL(k_icp_grid_scan<V>, dim3(1, 1, K), dim3(1024), 0, stream, S);
+            hipLaunchKernelGGL(k_icp_grid_scatter<V>, dim3(tb, 1, K), dim3(256), 0, stream, S);
+        }
+        return hipGetLastError();
+    });
 }
 
-hipError_t dev_prepare(IcpWorkspace* w, hipStream_t stream, const IcpTuning& tune) { return dev_prepare_v(w, stream, tune, w->S, w->G); }
-
-// one search of the device loop in every slot: the grid with its fallback, or (use_grid off) the brute force over every source
-template <class V>
-hipError_t dev_nearest_v(IcpWorkspace* w, hipStream_t stream, const IcpTuning& tune, int phase, const V& S)
+// one search of the device loop in every alignment: the grid with its fallback, or (use_grid off) the brute force over every source
+hipError_t dev_nearest(IcpWorkspace* w, hipStream_t stream, const IcpTuning& tune, int phase)
 {
-    const unsigned K = (unsigned)w->K;
-    const int n_src = w->n_src_max, sb = (n_src + kNnThreads - 1) / kNnThreads;
-    if (tune.use_grid) {
-        hipLaunchKernelGGL(k_icp_nn_grid<V>, dim3((n_src + kGridThreads - 1) / kGridThreads, 1, K), dim3(kGridThreads), 0, stream, S,
-                           std::max(1, tune.shell_cap), phase);
-        hipLaunchKernelGGL(k_icp_nn_list<V>, dim3(sb, w->slices_max, K), dim3(kNnThreads), 0, stream, S, 1, phase);
-    } else {
-        hipLaunchKernelGGL(k_icp_reset_dev<V>, dim3((n_src + 255) / 256, 1, K), dim3(256), 0, stream, S, phase);
-        hipLaunchKernelGGL(k_icp_nn_list<V>, dim3(sb, w->slices_max, K), dim3(kNnThreads), 0, stream, S, 0, phase);
-    }
-    return hipGetLastError();
+    return with_form(w, [&](const auto& S, const auto&) -> hipError_t {
+        using V = std::decay_t<decltype(S)>;
+        const unsigned K = (unsigned)w->K;
+        const int n_src = w->n_src_max, sb = (n_src + kNnThreads - 1) / kNnThreads;
+        if (tune.use_grid) {
+            hipLaunchKernelGGL(k_icp_nn_grid<V>, dim3((n_src + kGridThreads - 1) / kGridThreads, 1, K), dim3(kGridThreads), 0, stream, S,
+                               std::max(1, tune.shell_cap), phase);
+            hipLaunchKernelGGL(k_icp_nn_list<V>, dim3(sb, w->slices_max, K), dim3(kNnThreads), 0, stream, S, 1, phase);
+        } else {
+            hipLaunchKernelGGL(k_icp_reset_dev<V>, dim3((n_src + 255) / 256, 1, K), dim3(256), 0, stream, S, phase);
+            hipLaunchKernelGGL(k_icp_nn_list<V>, dim3(sb, w->slices_max, K), dim3(kNnThreads), 0, stream, S, 0, phase);
+        }
+        return hipGetLastError();
+    });
 }
 
-hipError_t dev_nearest(IcpWorkspace* w, hipStream_t stream, const IcpTuning& tune, int phase) { return dev_nearest_v(w, stream, tune, phase, w->S); }
-
-template <class V>
-hipError_t dev_sums_v(IcpWorkspace* w, hipStream_t stream, double max_d2, int phase, const V& S)
+hipError_t dev_sums(IcpWorkspace* w, hipStream_t stream, double max_d2, int phase)
 {
-    const int rows = w->rows_max;
-    hipLaunchKernelGGL(k_icp_sums_dev<V>, dim3(rows, 1, w->K), dim3(256), 0, stream, S, max_d2, phase);
-    hipLaunchKernelGGL(k_icp_fold_dev<V>, dim3(1, 1, w->K), dim3(64), 0, stream, S, rows, phase);
-    return hipGetLastError();
+    return with_form(w, [&](const auto& S, const auto&) -> hipError_t {
+        using V = std::decay_t<decltype(S)>;
+        const int rows = w->rows_max;
+        hipLaunchKernelGGL(k_icp_sums_dev<V>, dim3(rows, 1, w->K), dim3(256), 0, stream, S, max_d2, phase);
+        hipLaunchKernelGGL(k_icp_fold_dev<V>, dim3(1, 1, w->K), dim3(64), 0, stream, S, rows, phase);
+        return hipGetLastError();
+    });
 }
 
-hipError_t dev_sums(IcpWorkspace* w, hipStream_t stream, double max_d2, int phase) { return dev_sums_v(w, stream, max_d2, phase, w->S); }
+// Everything of a set up to and including the preparation: the layout with its guesses, the table's upload, the sources moved by
+// their guesses, the targets, the blocks and the grids. Every cloud of the set holds a point.
+hipError_t dev_set_up(IcpWorkspace* w, hipStream_t stream, const IcpSet& a, const IcpTuning& tune)
+{
+    const bool table = a.form == IcpForm::kTable;
+    if (a.n < 1 || a.n > kIcpMaxPairs) return hipErrorInvalidValue;
+    for (int k = 0; k < a.n; k++) if (a.n_src[table ? k : 0] == 0 || a.n_tgt[k] == 0) return hipErrorInvalidValue;
+    ICP_TRY(dev_layout(w, a, &tune));
+    if (table) ICP_TRY(hipMemcpyAsync(w->tab.p, w->h_tab, sizeof(IcpView) * (size_t)w->K, hipMemcpyHostToDevice, stream));
+    ICP_TRY(load(w, stream, kLoadSourcesMoved));
+    ICP_TRY(load(w, stream, kLoadTargets));
+    return dev_prepare(w, stream, tune);
+}
 
-// What the host loop (icp_align) asks per iteration, on the K = 1 layout: the brute-force search, then the sums with slot 0's
+// What the host loop (icp_align) asks per iteration, on the one-slot layout: the brute-force search, then the sums with slot 0's
 // folded sums brought to h_sums and one wait. phase 1: the host closes the iteration, so no kernel looks at the block's `done`.
 hipError_t host_nearest(IcpWorkspace* w, hipStream_t stream)
 {
@@ -1025,122 +983,68 @@ hipError_t host_sums(IcpWorkspace* w, hipStream_t stream, double max_d2)
     return hipStreamSynchronize(stream);
 }
 
-// the blocks of all slots to the host in one copy, and the event the host tests: the end of everything queued so far
+// the blocks of all alignments to the host in one copy, and the event the host tests: the end of everything queued so far
 hipError_t dev_mark(IcpWorkspace* w, hipStream_t stream)
 {
     ICP_TRY(hipMemcpyAsync(w->h_blk, w->blk.p, sizeof(IcpDevBlock) * (size_t)w->K, hipMemcpyDeviceToHost, stream));
     return hipEventRecord(w->ev, stream);
 }
 
-template <class V>
-hipError_t dev_queue_range_v(IcpWorkspace* w, hipStream_t stream, const V& S)
+hipError_t dev_queue_range(IcpWorkspace* w, hipStream_t stream)
 {
     IcpWorkspace::Flight& f = w->fl;
     const int n = std::min(kIcpRange, f.prm.max_iter - f.queued);
     const IcpCloseParams cp = icp_close_params(f.prm.max_iter, f.prm.trans_eps, f.prm.fit_eps);
     const double max_d2 = f.prm.max_corr_dist * f.prm.max_corr_dist;
     for (int k = 0; k < n; k++) {
-        ICP_TRY(dev_nearest_v(w, stream, f.tune, 0, S));
-        ICP_TRY(dev_sums_v(w, stream, max_d2, 0, S));
-        hipLaunchKernelGGL(k_icp_close<V>, dim3(1, 1, w->K), dim3(64), 0, stream, S, cp);
-        hipLaunchKernelGGL(k_icp_transform_dev<V>, dim3((f.n_src + 255) / 256, 1, w->K), dim3(256), 0, stream, S, 0);
-        ICP_TRY(hipGetLastError());
+        ICP_TRY(dev_nearest(w, stream, f.tune, 0));
+        ICP_TRY(dev_sums(w, stream, max_d2, 0));
+        ICP_TRY(with_form(w, [&](const auto& S, const auto&) -> hipError_t {
+            using V = std::decay_t<decltype(S)>;
+            hipLaunchKernelGGL(k_icp_close<V>, dim3(1, 1, w->K), dim3(64), 0, stream, S, cp);
+            hipLaunchKernelGGL(k_icp_transform_dev<V>, dim3((w->n_src_max + 255) / 256, 1, w->K), dim3(256), 0, stream, S, 0);
+            return hipGetLastError();
+        }));
     }
     f.queued += n;
     return dev_mark(w, stream);
 }
 
-hipError_t dev_queue_range(IcpWorkspace* w, hipStream_t stream)
-{
-    return w->fl.pairs ? dev_queue_range_v(w, stream, w->P) : dev_queue_range_v(w, stream, w->S);
-}
-
-// getFitnessScore() of every slot: the original source under the slot's final transformation, nearest distances with no limit
-template <class V>
-hipError_t dev_queue_fitness_v(IcpWorkspace* w, hipStream_t stream, const V& S)
-{
-    IcpWorkspace::Flight& f = w->fl;
-    if constexpr (V::kPerPair) ICP_TRY(load_pairs(w, stream, f.stride, 1));
-    else ICP_TRY(load_slots(w, stream, f.d_src, nullptr, f.stride));
-    hipLaunchKernelGGL(k_icp_transform_dev<V>, dim3((f.n_src + 255) / 256, 1, w->K), dim3(256), 0, stream, S, 1);
-    ICP_TRY(dev_nearest_v(w, stream, f.tune, 1, S));
-    ICP_TRY(dev_sums_v(w, stream, DBL_MAX, 1, S));
-    return dev_mark(w, stream);
-}
-
+// getFitnessScore() of every alignment: the original source under its final transformation, nearest distances with no limit
 hipError_t dev_queue_fitness(IcpWorkspace* w, hipStream_t stream)
 {
-    return w->fl.pairs ? dev_queue_fitness_v(w, stream, w->P) : dev_queue_fitness_v(w, stream, w->S);
+    ICP_TRY(load(w, stream, kLoadSources));
+    ICP_TRY(with_form(w, [&](const auto& S, const auto&) -> hipError_t {
+        using V = std::decay_t<decltype(S)>;
+        hipLaunchKernelGGL(k_icp_transform_dev<V>, dim3((w->n_src_max + 255) / 256, 1, w->K), dim3(256), 0, stream, S, 1);
+        return hipSuccess;
+    }));
+    ICP_TRY(dev_nearest(w, stream, w->fl.tune, 1));
+    ICP_TRY(dev_sums(w, stream, DBL_MAX, 1));
+    return dev_mark(w, stream);
 }
 
 }  // namespace
 
 void icp_dev_cancel(IcpWorkspace* w) { w->fl.phase = 0; }
 
-hipError_t icp_dev_begin(IcpWorkspace* w, hipStream_t stream, const unsigned char* d_src, size_t n_src_, const unsigned char* const* d_tgt,
-                         const size_t* n_tgt, int n_slots, size_t stride, const IcpParams& prm, const IcpTuning& tune, const float* const* guess)
+hipError_t icp_dev_begin(IcpWorkspace* w, hipStream_t stream, const IcpSet& set, const IcpParams& prm, const IcpTuning& tune)
 {
-    if (w->fl.phase != 0 || n_src_ == 0 || n_slots < 1 || n_slots > kIcpMaxSlots || prm.max_iter < 1) return hipErrorInvalidValue;
-    for (int k = 0; k < n_slots; k++) if (n_tgt[k] == 0) return hipErrorInvalidValue;
-    ICP_TRY(dev_layout(w, n_slots, n_src_, n_tgt, &tune));
-    set_guesses(w, guess);
-    ICP_TRY(load_slots(w, stream, d_src, nullptr, stride, true));
-    ICP_TRY(load_slots(w, stream, nullptr, d_tgt, stride));
-    ICP_TRY(dev_prepare(w, stream, tune));
+    if (w->fl.phase != 0 || prm.max_iter < 1) return hipErrorInvalidValue;
+    ICP_TRY(dev_set_up(w, stream, set, tune));
     IcpWorkspace::Flight& f = w->fl;
     f = IcpWorkspace::Flight{};
-    f.n_src = (int)n_src_; f.d_src = d_src; f.stride = stride; f.prm = prm; f.tune = tune;
+    f.prm = prm; f.tune = tune;
     ICP_TRY(dev_queue_range(w, stream));
     f.phase = 1;
     return hipSuccess;
 }
 
-hipError_t icp_pairs_begin(IcpWorkspace* w, hipStream_t stream, const unsigned char* const* d_src, const size_t* n_src,
-                           const unsigned char* const* d_tgt, const size_t* n_tgt, int n_pairs, size_t stride, const IcpParams& prm,
-                           const IcpTuning& tune, const float* const* guess)
-{
-    if (w->fl.phase != 0 || n_pairs < 1 || n_pairs > kIcpMaxPairs || prm.max_iter < 1) return hipErrorInvalidValue;
-    ICP_TRY(pairs_layout(w, n_pairs, d_src, n_src, d_tgt, n_tgt, tune, guess));
-    ICP_TRY(pairs_upload(w, stream));
-    ICP_TRY(load_pairs(w, stream, stride, 2));
-    ICP_TRY(load_pairs(w, stream, stride, 0));
-    ICP_TRY(dev_prepare_v(w, stream, tune, w->P, IcpPairGuesses{ 0 }));
-    IcpWorkspace::Flight& f = w->fl;
-    f = IcpWorkspace::Flight{};
-    f.pairs = true; f.n_src = w->n_src_max; f.stride = stride; f.prm = prm; f.tune = tune;
-    ICP_TRY(dev_queue_range(w, stream));
-    f.phase = 1;
-    return hipSuccess;
-}
-
-namespace {
-
-hipError_t advance(IcpWorkspace* w, hipStream_t stream, bool wait, bool* done, IcpResult* res);
-
-}  // namespace
-
-hipError_t icp_dev_advance(IcpWorkspace* w, hipStream_t stream, bool wait, bool* done, IcpResult* res)
-{
-    *done = false;
-    if (w->fl.pairs) return hipErrorInvalidValue;                         // (res holds kIcpMaxSlots results)
-    return advance(w, stream, wait, done, res);
-}
-
-hipError_t icp_pairs_advance(IcpWorkspace* w, hipStream_t stream, bool wait, bool* done, IcpResult* res)
-{
-    *done = false;
-    if (!w->fl.pairs) return hipErrorInvalidValue;
-    return advance(w, stream, wait, done, res);
-}
-
-namespace {
-
-// the step of either layout: K is the slots or the pairs, everything else is the flight's
-hipError_t advance(IcpWorkspace* w, hipStream_t stream, bool wait, bool* done, IcpResult* res)
+hipError_t icp_dev_advance(IcpWorkspace* w, hipStream_t stream, bool wait, bool* done, IcpResult* res, int res_cap)
 {
     IcpWorkspace::Flight& f = w->fl;
     *done = false;
-    if (f.phase == 0) return hipErrorInvalidValue;
+    if (f.phase == 0 || w->K > res_cap) return hipErrorInvalidValue;
     for (;;) {
         if (wait) {
             const hipError_t e = hipEventSynchronize(w->ev);
@@ -1173,8 +1077,6 @@ hipError_t advance(IcpWorkspace* w, hipStream_t stream, bool wait, bool* done, I
     }
 }
 
-}  // namespace
-
 hipError_t icp_dev_nearest(IcpWorkspace* w, hipStream_t stream, const unsigned char* d_src, size_t n_src_, const unsigned char* d_tgt,
                            size_t n_tgt_, size_t stride, int mode, const IcpTuning& tune, unsigned long long* keys, int* n_fallback,
                            int reps, float* us_build, float* us_search)
@@ -1182,9 +1084,9 @@ hipError_t icp_dev_nearest(IcpWorkspace* w, hipStream_t stream, const unsigned c
     const int n_src = (int)n_src_, n_tgt = (int)n_tgt_;
     if (w->fl.phase != 0 || n_src <= 0 || n_tgt <= 0) return hipErrorInvalidValue;
     const bool grid = mode != 0 && tune.use_grid != 0;
-    ICP_TRY(dev_layout(w, 1, n_src_, &n_tgt_, mode != 0 ? &tune : nullptr));
-    ICP_TRY(load_slots(w, stream, d_src, nullptr, stride));
-    ICP_TRY(load_slots(w, stream, nullptr, &d_tgt, stride));
+    ICP_TRY(dev_layout(w, IcpSet{ IcpForm::kSlots, 1, &d_src, &n_src_, &d_tgt, &n_tgt_, nullptr, stride }, mode != 0 ? &tune : nullptr));
+    ICP_TRY(load(w, stream, kLoadSources));
+    ICP_TRY(load(w, stream, kLoadTargets));
     hipEvent_t e0 = nullptr, e1 = nullptr, e2 = nullptr;
     const bool timed = reps > 0;
     hipError_t e = hipSuccess;
@@ -1224,25 +1126,25 @@ hipError_t icp_dev_grid(IcpWorkspace* w, hipStream_t stream, const unsigned char
     for (int k = 0; k < n_slots; k++) if (n_tgt[k] == 0) return hipErrorInvalidValue;
     IcpTuning t = tune;
     t.use_grid = 1;
-    ICP_TRY(dev_layout(w, n_slots, 0, n_tgt, &t));                        // (no source: nothing here reads a slot's source arrays)
-    ICP_TRY(load_slots(w, stream, nullptr, d_tgt, stride));
+    const size_t no_src = 0;                                              // (no source: nothing here reads a slot's source arrays)
+    ICP_TRY(dev_layout(w, IcpSet{ IcpForm::kSlots, n_slots, nullptr, &no_src, d_tgt, n_tgt, nullptr, stride }, &t));
+    ICP_TRY(load(w, stream, kLoadTargets));
     ICP_TRY(dev_prepare(w, stream, t));
     ICP_TRY(hipMemcpyAsync(w->h_blk, w->blk.p, sizeof(IcpDevBlock) * (size_t)n_slots, hipMemcpyDeviceToHost, stream));
     ICP_TRY(hipStreamSynchronize(stream));
     for (int k = 0; k < n_slots; k++) {
         const IcpGrid& g = w->h_blk[k].g;
+        const IcpView& v = w->slot_view[k];
         IcpGridInfo& o = info[k];
         for (int a = 0; a < 3; a++) { o.lo[a] = g.lo[a]; o.n[a] = g.n[a]; }
         o.cell = g.cell; o.inv = g.inv; o.n_fin = g.n_fin; o.usable = g.usable;
         if (!g.usable) continue;
         const size_t ncells = (size_t)g.n[0] * (size_t)g.n[1] * (size_t)g.n[2];
         if (ncells > (size_t)kGridMaxCells || g.n_fin < 0 || (size_t)g.n_fin > n_tgt[k]) return hipErrorUnknown;   // not reached
-        if (cell_start && cell_start[k])
-            ICP_TRY(hipMemcpyAsync(cell_start[k], w->S.gstart + (size_t)k * kGridMaxCells, sizeof(int) * ncells, hipMemcpyDeviceToHost, stream));
-        if (cell_end && cell_end[k])
-            ICP_TRY(hipMemcpyAsync(cell_end[k], w->S.gend + (size_t)k * kGridMaxCells, sizeof(int) * ncells, hipMemcpyDeviceToHost, stream));
+        if (cell_start && cell_start[k]) ICP_TRY(hipMemcpyAsync(cell_start[k], v.gstart, sizeof(int) * ncells, hipMemcpyDeviceToHost, stream));
+        if (cell_end && cell_end[k]) ICP_TRY(hipMemcpyAsync(cell_end[k], v.gend, sizeof(int) * ncells, hipMemcpyDeviceToHost, stream));
         if (order && order[k] && g.n_fin > 0)                             // the .w of every sorted entry: one int out of each float4
-            ICP_TRY(hipMemcpy2DAsync(order[k], sizeof(int), reinterpret_cast<const unsigned char*>(w->S.gsorted[k]) + 3 * sizeof(float),
+            ICP_TRY(hipMemcpy2DAsync(order[k], sizeof(int), reinterpret_cast<const unsigned char*>(v.gsorted) + 3 * sizeof(float),
                                      sizeof(float4), sizeof(int), (size_t)g.n_fin, hipMemcpyDeviceToHost, stream));
     }
     return hipStreamSynchronize(stream);
@@ -1262,9 +1164,10 @@ hipError_t icp_dev_close(IcpWorkspace* w, hipStream_t stream, int n, const doubl
         memcpy(b.sums, sums + 17 * (size_t)k, sizeof(b.sums));
         w->h_blk[k] = b;
     }
+    w->form = IcpForm::kTable;
     w->P = IcpPairs{ w->tab.as<IcpView>() };
     w->K = n;
-    ICP_TRY(pairs_upload(w, stream));
+    ICP_TRY(hipMemcpyAsync(w->tab.p, w->h_tab, sizeof(IcpView) * (size_t)n, hipMemcpyHostToDevice, stream));
     ICP_TRY(hipMemcpyAsync(w->blk.p, w->h_blk, sizeof(IcpDevBlock) * (size_t)n, hipMemcpyHostToDevice, stream));
     hipLaunchKernelGGL(k_icp_close<IcpPairs>, dim3(1, 1, n), dim3(64), 0, stream, w->P, icp_close_params(prm.max_iter, prm.trans_eps, prm.fit_eps));
     ICP_TRY(hipGetLastError());
@@ -1274,39 +1177,20 @@ hipError_t icp_dev_close(IcpWorkspace* w, hipStream_t stream, int n, const doubl
     return hipSuccess;
 }
 
-hipError_t icp_dev_sums(IcpWorkspace* w, hipStream_t stream, bool table, const unsigned char* const* d_src, const size_t* n_src,
-                        const unsigned char* const* d_tgt, const size_t* n_tgt, int n, size_t stride, double max_corr_dist,
-                        const IcpTuning& tune, double* sums, int* n_rows, double* const* parts, unsigned long long* const* keys)
+hipError_t icp_dev_sums(IcpWorkspace* w, hipStream_t stream, const IcpSet& set, double max_corr_dist, const IcpTuning& tune, double* sums,
+                        int* n_rows, double* const* parts, unsigned long long* const* keys)
 {
-    if (w->fl.phase != 0 || n < 1 || n > (table ? kIcpMaxPairs : kIcpMaxSlots)) return hipErrorInvalidValue;
-    for (int k = 0; k < n; k++) if (n_src[table ? k : 0] == 0 || n_tgt[k] == 0) return hipErrorInvalidValue;
-    const double max_d2 = max_corr_dist * max_corr_dist;
-    if (table) {                                                          // icp_pairs_begin up to its first range
-        ICP_TRY(pairs_layout(w, n, d_src, n_src, d_tgt, n_tgt, tune, nullptr));
-        ICP_TRY(pairs_upload(w, stream));
-        ICP_TRY(load_pairs(w, stream, stride, 2));
-        ICP_TRY(load_pairs(w, stream, stride, 0));
-        ICP_TRY(dev_prepare_v(w, stream, tune, w->P, IcpPairGuesses{ 0 }));
-        ICP_TRY(dev_nearest_v(w, stream, tune, 0, w->P));
-        ICP_TRY(dev_sums_v(w, stream, max_d2, 0, w->P));
-    } else {                                                              // icp_dev_begin up to its first range
-        ICP_TRY(dev_layout(w, n, n_src[0], n_tgt, &tune));
-        set_guesses(w, nullptr);
-        ICP_TRY(load_slots(w, stream, d_src[0], nullptr, stride, true));
-        ICP_TRY(load_slots(w, stream, nullptr, d_tgt, stride));
-        ICP_TRY(dev_prepare(w, stream, tune));
-        ICP_TRY(dev_nearest(w, stream, tune, 0));
-        ICP_TRY(dev_sums(w, stream, max_d2, 0));
-    }
+    if (w->fl.phase != 0) return hipErrorInvalidValue;
+    ICP_TRY(dev_set_up(w, stream, set, tune));
+    ICP_TRY(dev_nearest(w, stream, tune, 0));
+    ICP_TRY(dev_sums(w, stream, max_corr_dist * max_corr_dist, 0));
+    const int n = set.n;
     ICP_TRY(hipMemcpyAsync(w->h_blk, w->blk.p, sizeof(IcpDevBlock) * (size_t)n, hipMemcpyDeviceToHost, stream));
     for (int k = 0; k < n; k++) {
-        const int rows = table ? w->h_tab[k].rows : w->rows_max;
-        const size_t ns = n_src[table ? k : 0];
-        n_rows[k] = rows;
-        if (parts && parts[k])
-            ICP_TRY(hipMemcpyAsync(parts[k], table ? w->h_tab[k].part : w->S.part[k], sizeof(double) * 17 * (size_t)rows, hipMemcpyDeviceToHost, stream));
-        if (keys && keys[k])
-            ICP_TRY(hipMemcpyAsync(keys[k], table ? w->h_tab[k].best : w->S.best[k], sizeof(unsigned long long) * ns, hipMemcpyDeviceToHost, stream));
+        const IcpView& v = views(w)[k];
+        n_rows[k] = v.rows;
+        if (parts && parts[k]) ICP_TRY(hipMemcpyAsync(parts[k], v.part, sizeof(double) * 17 * (size_t)v.rows, hipMemcpyDeviceToHost, stream));
+        if (keys && keys[k]) ICP_TRY(hipMemcpyAsync(keys[k], v.best, sizeof(unsigned long long) * (size_t)v.n_src, hipMemcpyDeviceToHost, stream));
     }
     ICP_TRY(hipStreamSynchronize(stream));
     for (int k = 0; k < n; k++) memcpy(sums + 17 * (size_t)k, w->h_blk[k].sums, sizeof(double) * 17);
@@ -1320,10 +1204,9 @@ hipError_t icp_align(IcpWorkspace* w, hipStream_t stream, const unsigned char* d
     *res = icp_result_none();
     if (n_src_ == 0 || n_tgt_ == 0) return hipSuccess;
     if (w->fl.phase != 0) return hipErrorInvalidValue;                    // (the layout is the flight's: the callers answer BUSY before)
-    ICP_TRY(dev_layout(w, 1, n_src_, &n_tgt_, nullptr));
-    set_guesses(w, &guess);
-    ICP_TRY(load_slots(w, stream, d_src, nullptr, stride, true));
-    ICP_TRY(load_slots(w, stream, nullptr, &d_tgt, stride));
+    ICP_TRY(dev_layout(w, IcpSet{ IcpForm::kSlots, 1, &d_src, &n_src_, &d_tgt, &n_tgt_, &guess, stride }, nullptr));
+    ICP_TRY(load(w, stream, kLoadSourcesMoved));
+    ICP_TRY(load(w, stream, kLoadTargets));
 
     // icp.hpp computeTransformation + default_convergence_criteria.hpp hasConverged: icp_close_step, between two synchronisations
     const double max_d2 = prm.max_corr_dist * prm.max_corr_dist;
@@ -1345,7 +1228,7 @@ hipError_t icp_align(IcpWorkspace* w, hipStream_t stream, const unsigned char* d
     memcpy(res->T, st.T, sizeof(res->T));
     const int conv = st.conv, it = st.it;
     // getFitnessScore(): the original source under the final transform, mean squared nearest distance
-    ICP_TRY(load_slots(w, stream, d_src, nullptr, stride));
+    ICP_TRY(load(w, stream, kLoadSources));
     Mat34 F34;
     memcpy(F34.m, res->T, sizeof(float) * 12);
     hipLaunchKernelGGL(k_icp_transform, dim3((n_src + 255) / 256), dim3(256), 0, stream, w->cur.as<float4>(), n_src, F34);

@@ -8,6 +8,7 @@
 #include <cstdint>
 
 #include "s2m_icp_close.hpp"
+#include "s2m_icp_layout.hpp"    // kIcpMaxSlots, kIcpMaxPairs
 
 namespace s2m {
 
@@ -45,36 +46,39 @@ constexpr int kIcpRange = 8;            // iterations queued at a time (DESIGN.m
 constexpr bool kIcpUseGrid = true;      // the device loop's search: the uniform grid with its brute-force fallback, or brute force only
 constexpr float kIcpCellLeaves = 2.0f;  // grid cell edge in units of icp_leaf
 constexpr int kIcpShellCap = 3;         // largest Chebyshev radius (cells) searched before a point goes to the brute force
-constexpr int kIcpMaxSlots = 8;
-constexpr int kIcpMaxPairs = 64;         // alignments of the pair table (icp_pairs_*)
-
 struct IcpTuning { float cell; int shell_cap; int use_grid; };
 
+// What to align: n independent alignments advanced by the same launches through the same kernels, in the form the caller names.
+// kSlots: one source (d_src[0], n_src[0]) against n <= kIcpMaxSlots targets, the single alignment its n = 1 case; the slots go to
+// every kernel by value and a slot is a grid dimension. kTable: n <= kIcpMaxPairs pairs, pair k with a source of its own
+// (d_src[k], n_src[k]); the pairs' descriptions go to the device once, as a table, and a kernel finds its pair by blockIdx.z.
+// The two forms launch different instantiations of the kernels, so the form is never chosen from the sizes.
+// d_src, d_tgt: device records (x, y, z at byte 0/4/8, `stride` bytes apart). guess: null, or n pointers, each null or a
+// row-major 4x4 (host, read before the call that takes the set returns): alignment k's guess as icp_align takes one - every
+// alignment owns its moving copy of its source, so they may start at different places.
+enum class IcpForm { kSlots, kTable };
+struct IcpSet {
+    IcpForm                     form;
+    int                         n;
+    const unsigned char* const* d_src;
+    const size_t*               n_src;
+    const unsigned char* const* d_tgt;
+    const size_t*               n_tgt;
+    const float* const*         guess;
+    size_t                      stride;
+};
+
 void icp_dev_cancel(IcpWorkspace* w);                                    // forget the alignment in flight (the caller has drained the stream)
-// One source against n_slots <= kIcpMaxSlots targets (the single alignment: n_slots = 1): n_slots independent alignments advance
-// through the same launches, the slot a grid dimension of every kernel. Loads the clouds, builds a grid over every target, queues
-// the first range. n_src, n_tgt[k] > 0. Does not wait.
-// guess: null, or n_slots pointers, each null or a row-major 4x4 (host, read before the call returns): slot k's guess as icp_align
-// takes one - every slot owns its moving copy of the source, so the slots may start at different places. Slot k gives the bits
-// icp_align gives for d_tgt[k] with guess[k].
-hipError_t icp_dev_begin(IcpWorkspace* w, hipStream_t stream, const unsigned char* d_src, size_t n_src, const unsigned char* const* d_tgt,
-                         const size_t* n_tgt, int n_slots, size_t stride, const IcpParams& prm, const IcpTuning& tune,
-                         const float* const* guess = nullptr);
+// Loads the clouds of the set (every size > 0), builds a grid over every target, queues the first range. Does not wait.
+// Alignment k gives the bits icp_align gives for its source, its target and its guess alone.
+hipError_t icp_dev_begin(IcpWorkspace* w, hipStream_t stream, const IcpSet& set, const IcpParams& prm, const IcpTuning& tune);
 // wait == false: tests the event (hipEventQuery) and, where the queued work has ended, queues what follows (the next range, or
 // the fitness pass) without waiting for it; wait == true: the same with hipEventSynchronize until the result is there. Ranges are
-// queued until every slot has ended - a slot that has ended idles meanwhile - then one fitness pass runs for all.
-// *done: `res` holds the n_slots results, res[k] bit for bit what d_tgt[k] alone gives, and nothing is in flight any more.
-// d_src must stay as it was until then (the fitness pass reloads it).
-hipError_t icp_dev_advance(IcpWorkspace* w, hipStream_t stream, bool wait, bool* done, IcpResult* res);
-// The table form: n_pairs <= kIcpMaxPairs independent alignments, pair k with its own source (d_src[k], n_src[k] > 0), target
-// (d_tgt[k], n_tgt[k] > 0) and guess (guess: null, or n_pairs pointers as icp_dev_begin takes them), advanced by the same launches
-// through the same kernels: the pairs' descriptions go to the device once, as a table, and a kernel finds its pair by blockIdx.z.
-// The contract is icp_dev_begin's / icp_dev_advance's: ranges of kIcpRange, a pair that has ended idles, one fitness pass for
-// all, res[k] (n_pairs results) bit for bit what icp_align gives for pair k alone, the sources untouched until *done.
-hipError_t icp_pairs_begin(IcpWorkspace* w, hipStream_t stream, const unsigned char* const* d_src, const size_t* n_src,
-                           const unsigned char* const* d_tgt, const size_t* n_tgt, int n_pairs, size_t stride, const IcpParams& prm,
-                           const IcpTuning& tune, const float* const* guess = nullptr);
-hipError_t icp_pairs_advance(IcpWorkspace* w, hipStream_t stream, bool wait, bool* done, IcpResult* res);
+// queued until every alignment has ended - one that has ended idles meanwhile - then one fitness pass runs for all.
+// res: room for res_cap results; a flight of more alignments than that is refused.
+// *done: `res` holds the set's n results, res[k] bit for bit what alignment k alone gives, and nothing is in flight any more.
+// The sources must stay as they were until then (the fitness pass reloads them).
+hipError_t icp_dev_advance(IcpWorkspace* w, hipStream_t stream, bool wait, bool* done, IcpResult* res, int res_cap);
 // one nearest-neighbour search of src against tgt, synchronously: mode 0 the host loop's search (k_icp_nn: nn_tiles over every
 // source), mode 1 the device loop's search (the grid with its fallback, or with tune.use_grid off k_icp_nn_list over every
 // source). keys: host, n_src entries of (fp32 d2 bits << 32 | target index), ~0 = no match. reps > 0: the search `reps`
@@ -99,13 +103,11 @@ hipError_t icp_dev_grid(IcpWorkspace* w, hipStream_t stream, const unsigned char
 // comes in done comes back as it was.
 hipError_t icp_dev_close(IcpWorkspace* w, hipStream_t stream, int n, const double* sums, const IcpLoopState* in, const IcpParams& prm,
                          IcpLoopState* out);
-// the sums of iteration 0 of n alignments, synchronously: the layout, the loads and the preparation of icp_dev_begin (table ==
-// false: one source d_src[0] of n_src[0] points against n <= kIcpMaxSlots targets) or of icp_pairs_begin (table: n <=
-// kIcpMaxPairs pairs), then one search, k_icp_sums_dev and k_icp_fold_dev as the first range queues them - no close, no
-// transform. sums: n x 17 folded sums; n_rows[k]: the partial rows of alignment k; parts, keys: null, or per alignment null or
-// room for 17 * 256 partial sums (n_rows[k] rows are written) and for the n_src keys of the search.
-hipError_t icp_dev_sums(IcpWorkspace* w, hipStream_t stream, bool table, const unsigned char* const* d_src, const size_t* n_src,
-                        const unsigned char* const* d_tgt, const size_t* n_tgt, int n, size_t stride, double max_corr_dist,
-                        const IcpTuning& tune, double* sums, int* n_rows, double* const* parts, unsigned long long* const* keys);
+// the sums of iteration 0 of a set, synchronously: icp_dev_begin up to and including the preparation, then one search,
+// k_icp_sums_dev and k_icp_fold_dev as the first range queues them - no close, no transform. sums: n x 17 folded sums; n_rows[k]:
+// the partial rows of alignment k; parts, keys: null, or per alignment null or room for 17 * 256 partial sums (n_rows[k] rows are
+// written) and for the n_src keys of the search.
+hipError_t icp_dev_sums(IcpWorkspace* w, hipStream_t stream, const IcpSet& set, double max_corr_dist, const IcpTuning& tune, double* sums,
+                        int* n_rows, double* const* parts, unsigned long long* const* keys);
 
 }  // namespace s2m

@@ -1,6 +1,9 @@
 """CPU tests of the oracle's restatement of the ICP loop-closure alignment (SURVEY.md section 8(f) row F4;
 reference src/mapOptmization.cpp:571-586 -> pcl::IterativeClosestPoint, PCL 1.10 [ext]) against independent
 numpy statements.  PARITY UNPINNED: PCL is not vendored and the reference holds no fixture."""
+import os
+import subprocess
+
 import numpy as np
 
 from liorf_amd import synth
@@ -58,3 +61,15 @@ def test_icp_recovers_a_known_motion():
     far = src.copy(); far[:, 0] += 500.0
     Tf, convf, _, itsf = O.icp_align(far, tgt, max_corr_dist=1.0)
     assert not convf and itsf == 0 and np.array_equal(Tf, np.eye(4, dtype=np.float32))
+
+
+def test_alignment_set_layout_stand_alone_under_sanitizers(tmp_path):
+    """Where the alignments of a set lie in the ICP workspace's buffers is plain host code (s2m_icp_layout.hpp): a program of its
+    own, built with -fsanitize=address,undefined by the host compiler, walks it at the sizes where it can go wrong."""
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    exe = str(tmp_path / "icp_layout_main")
+    subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
+                           "-static-libasan", "-static-libubsan",               # the runtimes are part of the program
+                           "-I", os.path.join(root, "liorf_amd", "csrc"), "-o", exe, os.path.join(root, "tests", "ref", "icp_layout_main.cpp")])
+    out = subprocess.run([exe], capture_output=True, text=True, timeout=120)
+    assert out.returncode == 0 and out.stdout.startswith("ok "), out.stdout + out.stderr
